@@ -18,6 +18,11 @@ three-launch fallback path) against the HBM roofline with the algorithmic 39 B/p
 achieved = 39 B * pixels / average kernel duration (HIP events on the launch stream inside the timed region).
 `cpu_baseline` times the real reference (oracle/_ref, kind "reference") -- or, where that build is absent, the CPU
 oracle (kind "port") -- on a bounded band of the same image on this host's cores (rank 0, N = 1 only).
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the line.  `--full` adds everything else the
+line has carried (cpu_baseline, PSNR, cold-start and `_perf`-style figures, two-stream / cold-context / host-pointer rates, the
+headline's planes against the reference's checksums and config.other_workloads).  `--dump-outputs DIR` writes what the last timed
+step computed (rank 0) as DIR/<name>.npy: see dump_outputs().
 """
 import argparse
 import json
@@ -154,6 +159,53 @@ def emit(line):
     line["errors"] = list(ERRORS)
     line["warnings"] = list(WARNINGS)
     print(json.dumps(line), flush=True)
+
+
+DUMP_SAMPLE_BYTES = 52_000_000  # --dump-outputs: the sampled values of all arrays together ...
+DUMP_TILE_BYTES = 6_000_000     # ... and their tile sums: with the .npy headers well under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the outputs of the last timed step, so that two builds can be compared output for output.  `arrays`: [(name, device tensor)], int32 (32-bit
+    words, read as unsigned) or uint8.  Per array, two files:
+      DIR/<name>.npy            the values at a fixed, seeded sample of positions (all of them where the array is small enough): float64 for 32-bit words, float32 for bytes
+      DIR/<name>_tile_sums.npy  float64 (rows x cols) sums over a grid of at most 128 x 128 tiles that covers every element (exact below 2^53)
+    The positions depend only on the array's size and the number of arrays, so the same arguments give the same positions on every run."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    item = {torch.int32: 8, torch.uint8: 4}
+    for name, t in arrays:
+        if t.dtype not in item:
+            raise TypeError("dump_outputs: %s has dtype %s" % (name, t.dtype))
+    n_sample = max(1, DUMP_SAMPLE_BYTES // sum(item[t.dtype] for _, t in arrays))
+    grid = max(1, min(128, int((DUMP_TILE_BYTES / 8 / len(arrays)) ** 0.5)))
+    total = 0
+    for name, t in arrays:
+        t2 = t.reshape(t.shape[0], -1) if t.dim() >= 2 else t.reshape(1, -1)
+        h, w = t2.shape
+        words = t2.to(torch.int64)
+        if t.dtype == torch.int32:
+            words &= 0xFFFFFFFF
+        gy, gx = min(grid, h), min(grid, w)
+        th, tw = -(-h // gy), -(-w // gx)
+        assert th * tw < (1 << (21 if t.dtype == torch.int32 else 45)), "dump_outputs: tiles of %s too large for exact float64 sums" % name
+        padded = torch.zeros((gy * th, gx * tw), dtype=torch.int64, device=t.device)
+        padded[:h, :w] = words
+        sums = padded.view(gy, th, gx, tw).sum(dim=(1, 3)).cpu().numpy().astype(np.float64)
+        n = h * w
+        if n <= n_sample:
+            vals = words.reshape(-1)
+        else:
+            idx = np.sort(np.random.default_rng([0x6C696D67, n, n_sample]).choice(n, n_sample, replace=False))
+            vals = words.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        vals = vals.cpu().numpy().astype(np.float64 if t.dtype == torch.int32 else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), vals)
+        np.save(os.path.join(out_dir, name + "_tile_sums.npy"), sums)
+        total += vals.nbytes + sums.nbytes
+        del words, padded
+    return {"dir": out_dir, "arrays": [name for name, _ in arrays], "samples_per_array": int(n_sample), "tile_grid": grid, "bytes": int(total)}
 
 
 def pmc_entry(key):
@@ -414,6 +466,10 @@ def run_sharded(args, g, dist, rank, world):
         collective = {"backend": None if dist is None else dist.get_backend(), "world_size": world, "rccl_version": info["rccl_version"], "comm_ranks": info["ranks"]}
     else:
         collective = collective_evidence(g, dist, rank, world)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # this rank's units: image i of its list (config 4) / strip i (config 5)
+        import limg_amd
+        dumped = dump_outputs(args.dump_outputs, [("unit%02d_%s" % (i, k), planes[k]) for i, (_, planes) in enumerate(units) for k in limg_amd.PLANES])
     golden = verify_golden(args, units, rows, rank, world, dist, single_chain, W, H, kind) if (args.verify_golden and not COLLECTIVES_OFF) else None
 
     # reassembly on rank 0 (config 5: the strips of the one image; config 4: every image's planes), timed apart
@@ -503,7 +559,7 @@ def run_sharded(args, g, dist, rank, world):
             "config": {"workload": name + ", errorFactor %d, fast bit-crush" % args.error_factor,
                        "parallelism": "no data-path collective; plane reassembly on rank 0 timed apart",
                        "gather_ms": None if gather_ms is None else round(gather_ms, 3), "gathered_bytes_rank0": gathered_bytes,
-                       "collective": collective, "golden": golden,
+                       "collective": collective, "golden": golden, "dumped_outputs": dumped,
                        "gather_backend": None if dist is None else dist.get_backend(), "gathered": "LMG3 streams, decoded on rank 0" if args.gather_stream else "planes"},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
                          "traffic": None if not pmc or pmc.get("fetch_kib") is None else int((2 * pmc["fetch_kib"] + pmc["write_kib"]) * 1024),
@@ -641,6 +697,9 @@ def run_blocked(args, g, dist, rank, world, W, H):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     g.check()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, sorted(planes.items()))
     # Throughput over a stream of images: the per-image critical path is host work upstream makes serial (greedy merge, one AES chain), so images are pipelined ACROSS
     # contexts -- K host threads, each with its own context and HIP stream: image i+1's pass 1 / similarity kernels and image i's host merge + chain walk overlap.
     pipe = None
@@ -687,10 +746,10 @@ def run_blocked(args, g, dist, rank, world, W, H):
             "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / args.steps, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "u8/i32 integer stage + f32 float stage (bit-exact vs the reference)", "data": "synthetic",
             "config": {"workload": "synthetic %dx%d RGBA %s (seed 1+rank) per GPU, errorFactor %d" % (W, H, args.workload, args.error_factor), "rectangles": nreg,
-                       "blocks": (W // 8) * (H // 8), "psnr_db": round(psnr, 4), "stage_ms": mean, "pipelined_stream": pipe},
+                       "blocks": (W // 8) * (H // 8), "psnr_db": round(psnr, 4), "stage_ms": mean, "pipelined_stream": pipe, "dumped_outputs": dumped},
             "roofline": blocked_roofline(px, mean, "blocked_%dx%d_%s%s" % (W, H, args.workload, "" if args.error_factor == 100 else "_ef%d" % args.error_factor)),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 from oracle.bind import Oracle, Ref, ref_available
                 orc = Oracle()
@@ -749,6 +808,9 @@ def run_stream(args, g, dist, rank, world, W, H):
     el_e, k_e = timed(lambda: g.encode_stream_device(img, True, out=st, error_factor=args.error_factor, want_size=False))
     el_d, k_d = timed(lambda: g.decode_stream_device(st, nbytes, W, H, out=dec))
     g.check()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, [("stream", st[:nbytes]), ("pDecoded", dec)])
     if rank == 0:
         px = W * H
         enc_ms = float(k_e[0::2].sum(axis=1).mean()) if len(k_e) else 0.0   # k_fit_tpb + k_encode_persistent (compact outputs)
@@ -763,7 +825,7 @@ def run_stream(args, g, dist, rank, world, W, H):
             "dtype": "u8/i32 integer stage + f32 float stage", "data": "synthetic",
             "config": {"workload": "synthetic %dx%d RGBA %s (seed 1+rank) per GPU, errorFactor %d" % (W, H, args.workload, args.error_factor),
                        "stream_bytes": int(nbytes), "stream_bytes_per_px": round(nbytes / px, 4), "roundtrip_equals_pDecoded": same,
-                       "decode_Mpixels_per_s": round(world * px * args.steps / el_d / 1e6, 1), "decode_ms_per_step": round(el_d * 1e3 / args.steps, 4)},
+                       "decode_Mpixels_per_s": round(world * px * args.steps / el_d / 1e6, 1), "decode_ms_per_step": round(el_d * 1e3 / args.steps, 4), "dumped_outputs": dumped},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
                          "traffic": None if not pmc_entry("stream_%dx%d_%s" % (W, H, args.workload)) else int((2 * pmc_entry("stream_%dx%d_%s" % (W, H, args.workload))["fetch_kib"] + pmc_entry("stream_%dx%d_%s" % (W, H, args.workload))["write_kib"]) * 1024),
                          "valu_busy": (pmc_entry("stream_%dx%d_%s" % (W, H, args.workload)) or {}).get("valu_busy"), "pmc_key": "stream_%dx%d_%s" % (W, H, args.workload),
@@ -964,7 +1026,13 @@ def main():
     ap.add_argument("--ragged-bands", type=int, default=0, help="limg_hip_options.ragged_bands (images with a partial last block column: bands of the host walk's pipeline; -1 = off)")
     ap.add_argument("--walk-threads", type=int, default=0, help="limg_hip_options.ragged_walk_threads (several chains: host threads that walk them; 1 = serial)")
     ap.add_argument("--whole-image-ragged", action="store_true", help="A/B: height-ragged images through the whole-image ragged path (host walk over every dither call)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: cpu_baseline, PSNR, cold-start and _perf-style figures, two-stream / cold-context / "
+                                                     "host-pointer rates, the headline's planes against the reference and config.other_workloads (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy "
+                                                                        "(a fixed, seeded sample of every output array + exact tile sums; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.width, args.height = parse_size(args.size)
     args.size = args.width  # (the square-size uses below: configs 4 / 5, cpu_baseline)
 
@@ -1104,11 +1172,15 @@ def main():
     torch.cuda.synchronize()
     g.check()  # a look-back timeout inside the timed loop would void the line
     collective = collective_evidence(g, dist, rank, n_gpus)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, [(k, planes[k]) for k in limg_amd.PLANES if k in planes]
+                              + ([("records", rec), ("shifts", sh)] if args.compact else []))
 
     # cold cost of a SECOND, smaller size class on the warm context (the noise table is a prefix stream and the scratch only grows: nothing is rebuilt), and of a
     # fresh context whose table is built on the host the way rounds 1-2 did (limg_hip_options.host_noise_table), for comparison
     cold = {}
-    if rank == 0 and n_gpus == 1 and not args.no_host_rate and W >= 4096 and W == H:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_host_rate and W >= 4096 and W == H:
         w2 = W // 2
         img2 = g.synth_device(args.workload, w2, w2, seed=5)
         planes2 = g.alloc_planes_device(w2, w2)
@@ -1133,17 +1205,19 @@ def main():
     px = W * H
     ms_per_step = elapsed * 1e3 / args.steps
     value = n_gpus * px * args.steps / elapsed / 1e6
-    psnr = float("nan") if args.compact else g.compare_device(img, planes["pDecoded"], not args.rgb)[0]
+    psnr = float("nan") if (args.compact or not args.full) else g.compare_device(img, planes["pDecoded"], not args.rgb)[0]
     bytes_per_px = (4 + 3 + 68.0 / 64) if args.compact else ALGO_BYTES_PER_PX
 
     if rank == 0:
-        # `_perf` style on the GPU (SURVEY 8(d) last row; src/limg.cpp:2140-2173): the E step alone -- fit, factors, shift search -- nothing stored
-        g.profile_begin()
-        for _ in range(5):
-            g.encode3d_device(img, not args.rgb, None, error_factor=args.error_factor, pool_threads=0, fast=not args.accurate)
-        torch.cuda.synchronize()
-        kperf = g.profile_end(5)
-        perf_ms = float(kperf[1:, 0].mean()) if len(kperf) > 1 else None
+        perf_ms = None
+        if args.full:
+            # `_perf` style on the GPU (SURVEY 8(d) last row; src/limg.cpp:2140-2173): the E step alone -- fit, factors, shift search -- nothing stored
+            g.profile_begin()
+            for _ in range(5):
+                g.encode3d_device(img, not args.rgb, None, error_factor=args.error_factor, pool_threads=0, fast=not args.accurate)
+            torch.cuda.synchronize()
+            kperf = g.profile_end(5)
+            perf_ms = float(kperf[1:, 0].mean()) if len(kperf) > 1 else None
 
         kavg = kernels.mean(axis=0) if len(kernels) else np.zeros(3)
         # the kernels listed in roofline.kernels_ms, nothing else: fused = k_fit_tpb + k_encode_persistent (the one persistent launch with --legacy-float-stage); split = the three intervals
@@ -1178,7 +1252,7 @@ def main():
                        "images_per_step": n_gpus, "parallelism": "independent image per GPU, no data-path collective", "psnr_db": None if psnr != psnr else round(psnr, 4),
                        "first_encode_ms": round(first_encode_ms, 2), "cold": cold,
                        "perf_style_ms": None if perf_ms is None else round(perf_ms, 4),
-                       "perf_style_Mpixels_per_s": None if not perf_ms else round(px / perf_ms / 1e3, 1)},
+                       "perf_style_Mpixels_per_s": None if not perf_ms else round(px / perf_ms / 1e3, 1), "full": args.full, "dumped_outputs": dumped},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
                          "traffic": traffic,
                          "algorithmic_bytes_per_launch": int(bytes_per_px * px),
@@ -1198,7 +1272,7 @@ def main():
                                   "(HIP events on the launch stream). "
                                   "The kernel is VALU-issue-bound, not HBM-bound: see `valu`")},
         }
-        if n_gpus == 1 and not args.no_host_rate and not (args.split or args.compact or args.forced_shift >= 0 or ragged):
+        if args.full and n_gpus == 1 and not args.no_host_rate and not (args.split or args.compact or args.forced_shift >= 0 or ragged):
             try:  # what a service encoding a stream of images gets: two contexts on two HIP streams, images alternating (never `value`: the kernels overlap)
                 line["config"]["two_streams"] = two_stream_rate(g, img, planes, W, H, args)
             except Exception as e:
@@ -1208,17 +1282,17 @@ def main():
                 line["config"]["multi_context"] = multi_context_rate(img, W, H, args, args.contexts)
             except Exception as e:
                 line["config"]["multi_context"] = leg_failed("multi_context", e)
-        if n_gpus == 1 and not args.no_host_rate and not (args.split or args.compact or ragged):
+        if args.full and n_gpus == 1 and not args.no_host_rate and not (args.split or args.compact or ragged):
             try:  # what a per-request service pays that makes a context per image: init + first encode (noise table, scratch) + shutdown
                 line["config"]["cold_context_per_image"] = cold_context_rate(dev, img, planes, W, H, args)
             except Exception as e:
                 line["config"]["cold_context_per_image"] = leg_failed("cold_context_per_image", e)
-        if n_gpus == 1 and not args.no_host_rate:
+        if args.full and n_gpus == 1 and not args.no_host_rate:
             try:
                 line["config"]["host_entry"] = host_entry_rate(g, W, H, args)
             except Exception as e:
                 line["config"]["host_entry"] = leg_failed("host_entry", e)
-        default_line = (n_gpus == 1 and not args.no_host_rate and (W, H) == (8192, 8192) and args.workload == "photo_noise" and args.error_factor == 100 and args.pool_threads == 0 and
+        default_line = (args.full and n_gpus == 1 and not args.no_host_rate and (W, H) == (8192, 8192) and args.workload == "photo_noise" and args.error_factor == 100 and args.pool_threads == 0 and
                         args.float_mode == "exact" and not (args.split or args.compact or args.accurate or args.rgb or args.graph or args.legacy_float_stage or args.forced_shift >= 0))
         if default_line or args.other_workloads:
             # the headline image itself against the real reference, then every other BASELINE config once (never part of `value`)
@@ -1234,7 +1308,7 @@ def main():
             del planes, img
             torch.cuda.empty_cache()
             line["config"]["other_workloads"] = other_workloads(g, dev, args)
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(W, 1, height=H)
             except Exception as e:  # the checker does not void the measurement, but the line says so and the process fails

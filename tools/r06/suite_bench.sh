@@ -3,7 +3,7 @@
 # head / lib_sha / src_sha; a failed leg makes bench.py exit non-zero, which is recorded in rc.txt).  tools/r06/collect.sh copies them to profiles/r06_bench_final_<mode>.json.
 O=gpurun_out/r06_final; mkdir -p $O; : > $O/rc.txt
 Q="--no-cpu-baseline --no-host-rate"
-run() { name=$1; shift; python bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; echo "$name rc=$?" >> $O/rc.txt; }
+run() { name=$1; shift; python bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; echo "$name rc=$?" >> $O/rc.txt; }
 run default
 run accurate_rg4096 --accurate --size 4096 --workload random_gradient --steps 10 $Q
 run host_pool2 --steps 5 --pool-threads 2 --no-cpu-baseline
