@@ -24,7 +24,7 @@ typedef struct limg_hip_test_options
   int32_t wg_per_cu;          /* A/B: workgroups per CU of the persistent kernel's launch, 1 .. its launch bound (6; values above are ignored) */
   int32_t whole_image_ragged; /* non-0: an image whose width is whole 8x8 blocks but whose last block row is partial goes through the whole-image ragged path (host
                                  chain walk over every dither call) instead of fast path + last row; same planes either way */
-  int32_t pipeline;           /* A/B knobs of the sub-batch pipeline (see limg_hip_api.hip) */
+  int32_t pipeline;           /* A/B knobs of the sub-batch pipeline (see limg_hip_encode.hip) */
   int32_t fail_chain_phase1;  /* non-0: limg_hip_encode3d_single_chain_device behaves as if this rank's E step had failed (abort rule in limg_hip.h) */
   int32_t blocked_no_bound;   /* non-0: the merged-block encoder's similarity kernel evaluates the 27-colour loop for every pair its early exits leave open, without
                                  the certain-match / certain-failure bounds in front of it (limg_hip_blocked.hip).  Same bits either way */

@@ -13,7 +13,11 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "liblimg_hip.so")
 TEST_OUT = os.path.join(HERE, "liblimg_hip_test.so")
 TEST_FLAGS = ["-DLIMG_HIP_TEST_HOOKS"]
-SOURCES = ["limg_hip_kernels.hip", "limg_hip_fit_tpb.hip", "limg_hip_stream.hip", "limg_hip_blocked.hip", "limg_hip_synth.hip", "limg_hip_noise_gpu.hip", "limg_hip_api.hip", "limg_hip_noise.cpp", "limg_hip_blocked_host.cpp"]
+SOURCES = ["limg_hip_kernels.hip", "limg_hip_fit_tpb.hip", "limg_hip_stream.hip", "limg_hip_blocked.hip", "limg_hip_synth.hip", "limg_hip_noise_gpu.hip",
+           "limg_hip_api.hip", "limg_hip_noise_table.hip", "limg_hip_encode.hip", "limg_hip_encode_ragged.hip", "limg_hip_host_entry.hip", "limg_hip_stream_api.hip",
+           "limg_hip_blocked_api.hip", "limg_hip_multi.hip", "limg_hip_noise.cpp", "limg_hip_blocked_host.cpp"]
+# the library exports the C ABI of include/limg_hip.h (limg_hip_*) and nothing else: the host units' shared internals and the C++ runtime's template instances stay local
+EXPORTS = os.path.join(CSRC, "limg_hip.map")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 # per-source extras.  limg_hip_kernels.hip: every atomic in it is issued by one lane (block queue, ticket, look-back descriptors); LLVM's atomic optimizer would still
 # wrap each in its wave-aggregation prologue (v_mbcnt x 2, compare, s_bcnt1, broadcast, add) -- five vector instructions per 8x8 block for nothing
@@ -90,7 +94,7 @@ def build(force=False, verbose=False, extra_flags=(), out_dir=None, test_hooks=F
     with ThreadPoolExecutor(max_workers=int(os.environ.get("LIMG_BUILD_JOBS", "4"))) as ex:
         objs = list(ex.map(run, jobs))
     check_isa(out_dir, extra_flags, test_hooks, verbose)  # before the link: no library without it
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + EXPORTS, "-o", out] + objs
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

@@ -108,11 +108,7 @@ namespace limg_hip
       for (int z = 0; z < 3; z++)
 #pragma unroll 1
         for (int y = 0; y < 3; y++)
-#ifdef LIMG_MATCH_ROLL_X
-#pragma unroll 1
-#else
 #pragma unroll
-#endif
           for (int x = 0; x < 3; x++)
           {
             const float xf = x * 0.5f, yf = y * 0.5f, zf = z * 0.5f;
@@ -224,11 +220,7 @@ namespace limg_hip
       for (int z = 0; z < 3; z++)
 #pragma unroll 1
         for (int y = 0; y < 3; y++)
-#ifdef LIMG_MATCH_ROLL_X
-#pragma unroll 1
-#else
 #pragma unroll
-#endif
           for (int x = 0; x < 3; x++)
           {
             const float xf = x * 0.5f, yf = y * 0.5f, zf = z * 0.5f;
@@ -325,11 +317,8 @@ namespace limg_hip
     // a list in LDS.  Step 2: the expensive loop over the list only, two candidates per lane.
     template <int CH>
     // Three workgroups per CU (168 VGPRs, three dwords of scratch) instead of the two the compiler takes by itself (218): 14.7-15.0 -> 13.8-14.0 ms per 8192^2 image and
-    // 3.23 -> 3.49 Gpixel/s over four contexts (tools/r04/run27.sh, same box); four (128 VGPRs, 344 B of scratch, or 192 B with the x loop rolled) is slower: 17.7 ms.
-#ifndef LIMG_MATCH_WGS
-#define LIMG_MATCH_WGS 3
-#endif
-    __global__ __launch_bounds__(256, LIMG_MATCH_WGS) void k_blocked_match(const BlockedParams p)
+    // 3.23 -> 3.49 Gpixel/s over four contexts (same box); four (128 VGPRs, 344 B of scratch, or 192 B with the x loop rolled) is slower: 17.7 ms.
+    __global__ __launch_bounds__(256, 3) void k_blocked_match(const BlockedParams p)
     {
       __shared__ unsigned short sList[4][kMatchWords * 64];
       __shared__ unsigned long long sWords[4][kMatchWords];
@@ -379,9 +368,6 @@ namespace limg_hip
         count += (uint32_t)__builtin_popcountll(open);
       }
       wave_lds_fence();
-#ifdef LIMG_MATCH_SKIP2 // timing experiment only (wrong results; tools/r04/run9.sh): how much of the kernel is the expensive evaluation?
-      count = 0;
-#endif
       for (uint32_t k = 0; k < count; k += 128)
       {
         const uint32_t i0 = k + lane, i1 = k + 64 + lane;

@@ -171,10 +171,7 @@ namespace limg_hip
 
   namespace
   {
-#ifndef LIMG_MERGE_PF_CENTRE
-#define LIMG_MERGE_PF_CENTRE 4
-#endif
-    constexpr uint32_t kCentreAhead = LIMG_MERGE_PF_CENTRE; // (A/B hook: 0 = the look-ahead requests the seeds' own rows only)
+    constexpr uint32_t kCentreAhead = 4; // (0 would make the look-ahead request the seeds' own rows only)
 
     struct Merge
     {
@@ -321,7 +318,7 @@ namespace limg_hip
           };
           for (; ox < bx; ox++)
           {
-#if defined(__x86_64__) && !defined(LIMG_MERGE_NO_SIMD_SCAN)
+#if defined(__x86_64__)
             // the next seed that is unused and flagged, sixteen at a time (both arrays carry 16 bytes of padding behind their last row; what a load takes from the
             // next row is masked off): most seeds of a pass are skipped -- in use, or flagged hopeless -- and one branch per seed was a third of the merge
             if (frow)

@@ -1,0 +1,252 @@
+// Host-only internals of liblimg_hip.so shared by the host translation units (limg_hip_api.hip and the units it was split into): the context and its buffers,
+// the error macro, and the helpers more than one unit calls.  The kernel files include limg_hip_internal.h only.  Not part of the C ABI.
+#ifndef LIMG_HIP_CONTEXT_H
+#define LIMG_HIP_CONTEXT_H
+
+#include "limg_hip_internal.h"
+#ifdef LIMG_HIP_TEST_HOOKS
+#include "../../include/limg_hip_test_hooks.h"
+#define TOPT(c, member) ((c)->topt.member)
+#else
+#define TOPT(c, member) 0 /* the product has no test hooks: every use folds to the default */
+#endif
+#include "limg_hip_rccl.h"
+
+#include <stddef.h>
+#include <stdio.h>
+#include <string.h>
+#include <new>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+#define HIP_TRY(expr)                                                                                                     \
+  do                                                                                                                      \
+  {                                                                                                                       \
+    const hipError_t e_ = (expr);                                                                                         \
+    if (e_ != hipSuccess)                                                                                                 \
+    {                                                                                                                     \
+      fprintf(stderr, "limg_hip: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__);            \
+      return limg_hip_error_Generic;                                                                                      \
+    }                                                                                                                     \
+  } while (0)
+
+struct DevBuf
+{
+  void *p = nullptr;
+  size_t cap = 0;
+  limg_hip_result ensure(size_t bytes)
+  {
+    if (bytes <= cap) return limg_hip_success;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; return limg_hip_error_MemoryAllocationFailure; }
+    cap = bytes;
+    return limg_hip_success;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// pinned host memory owned by the context (staging of the merged-block encoder's host stages: no zero fill, full-rate PCIe copies)
+struct HostBuf
+{
+  void *p = nullptr;
+  size_t cap = 0;
+  limg_hip_result ensure(size_t bytes)
+  {
+    if (bytes <= cap) return limg_hip_success;
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = bytes + bytes / 4; // grow with slack: sizes depend on the image content
+    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return limg_hip_error_MemoryAllocationFailure; }
+    cap = want;
+    return limg_hip_success;
+  }
+  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
+struct limg_hip_context
+{
+  // The reference's entry points are re-entrant (scratch on the stack, src/limg.cpp:1890-1891; the only globals are CPUID flags, src/limg_simd.cpp:57-60), so a
+  // caller may encode from several threads at once.  A context owns device scratch, so the blocking host-pointer entries (what the shim's limg_encode3d_test & co.
+  // call) serialise on this mutex: any number of threads may share one context through them.  The asynchronous *_device entries enqueue work that uses that
+  // scratch after they return: one context per stream there (documented in limg_hip.h).
+  std::recursive_mutex hostEntry;
+  int device = 0;
+  limg_hip_options opt;
+#ifdef LIMG_HIP_TEST_HOOKS
+  limg_hip_test_options topt; // liblimg_hip_test.so only (include/limg_hip_test_hooks.h)
+#endif
+  DevBuf records, shifts, stripCalls, stripBase; // per-block / per-strip scratch
+  DevBuf invN;                                   // per block 1 / |normal|^2 of the three factors (k_fit_tpb -> E step)
+  DevBuf noise;                                  // static dither noise table (full-block chains)
+  bool noisePcg = false;                         // which generator the table was built with
+  size_t noiseCount = 0;                         // entries generated so far
+  uint64_t noiseNext = limg_hip::kDitherSeed;           // chain value after the last generated entry
+  DevBuf noiseDyn;                               // data-dependent chains (images with partial blocks)
+  DevBuf noiseStates;                            // ... their per-call chain values + pixel counts as the host uploads them (k_noise_expand -> noiseDyn)
+  DevBuf noiseCk;                                // the chain checkpoints (limg_noise_checkpoints.h) on the device: the GPU fills the noise table from them
+  size_t noiseCkCount = 0;                       // ... how many dense values (every 1024th call) are there: the embedded ones, or more (ensure_checkpoints)
+  std::vector<uint64_t> noiseCkHost;             // ... and, once an image has reached beyond the embedded dense values, the host copy they were uploaded from
+  DevBuf park;                                   // persistent kernel: 2 x 8 KiB per workgroup
+  DevBuf batchTable;                             // batched encode: one ImageIO per image
+  hipStream_t fitStream = nullptr;               // batched encode in sub-batches: k_fit_tpb of sub-batch k + 1 runs here, next to the persistent kernel of sub-batch k
+  std::vector<hipEvent_t> pipeEvents;            // ... and the events that fork it from / join it to the caller's stream
+  HostBuf hStage;                                // pinned staging of the ragged paths' host step (shift words down; chain bases and noise up)
+  hipEvent_t hStageEvent = nullptr;              // ... recorded behind the last asynchronous H2D copy that reads it: waited for before it is written, grown or freed again
+  bool hStageBusy = false;
+  std::vector<hipEvent_t> raggedEvents;          // banded ragged encode: "the shift words of band b are down"
+  DevBuf stats;                                  // limg_hip_options.collect_stats: the reference's 3 + 27 bit counters of the last encode
+  hipStream_t statsStream = nullptr;
+  int statsState = 0;                            // 0 = none, 1 = on the device (8x8 path), 2 = in statsHost (merged-block encoder)
+  bool statsAccumulate = false;                  // a batched encode in several launch pairs: the pairs after the first add to the counters instead of restarting them
+  uint64_t statsHost[30] = { 0 };
+  uint64_t statsPixels = 0;
+  DevBuf lookback;                               // fused path: ticket (16 B) then one 8-byte descriptor per work strip
+  DevBuf accTable;                               // accurate search: automaton expanded to 32-byte entries (built on the first accurate encode)
+  DevBuf devStatus;                              // sticky look-back timeout word: never touched by the per-launch memset, cleared by limg_hip_check_device_status
+  DevBuf in, planes;                             // staging for the host-pointer entry points
+  hipStream_t hostCopyStream = nullptr;          // ... the downloads of the finished bands (second host thread)
+  hipStream_t hostStream = nullptr;              // ... in row bands: the bands' kernels run here, their events tell the download thread when a band is done
+  std::vector<hipEvent_t> hostEvents;
+  DevBuf hostWords;                              // ... per band its dither-call total and its chain base (one chain through the bands)
+  DevBuf cmp;                                    // 8-byte accumulator of limg_hip_compare
+  DevBuf bFlags, bBound;
+  DevBuf bOrder; // merged-block encoder: per batch the order its workgroups take the rectangles in
+  DevBuf bMatch, bRegions, bOut, bPx, bFac, bNoise, bNoiseBase; // merged-block encoder: similarity bits, region table / results, scratch (gathered pixels, factor bytes), noise
+  HostBuf hFlags;
+  HostBuf hRec, hBits, hDesc, hOut, hNoise, hNoiseBase;
+  hipStream_t workStream = nullptr; // the merged-block encoder's worker thread launches on its own stream
+  std::vector<hipStream_t> workStreams; // ... its fit + search batches round-robin on these
+  hipStream_t storeStream = nullptr; // ... and the noise expansion + store kernels of a batch on a second one
+  DevBuf bCalls;                     // per dither call of the merged-block encoder: chain value, noise offset, pixel count (host walk -> k_noise_expand_calls)
+  std::vector<hipEvent_t> workEvents;        // one per batch of the merged-block encoder's worker that is in flight on the GPU
+  hipStream_t copyStream = nullptr;      // copies of the similarity-bit bands, behind the kernels that produce them
+  std::vector<hipEvent_t> bandEvents;
+  std::vector<limg_hip::HostRegion> lastRegions;
+  size_t lastBlocks = 0;                     // blocks of the last merged-block encode (what hBits / lastRegions describe)
+  double blockedMs[6] = { 0, 0, 0, 0, 0, 0 };
+  double blockedKernelMs[4] = { 0, 0, 0, 0 }; // the last merged-block encode, HIP events: pass 1 (k_fit_tpb) / the k_blocked_match launches / the k_blocked_fit_search launches /
+                                             // the noise-expansion + store launches (the last two summed over the worker's batches)
+  std::vector<hipEvent_t> workTimers;        // [4 i .. 4 i + 3]: begin / end of batch slot i's fit + search kernel, begin / end of its expansion + store kernels;
+                                             // [4 kInFlight ..]: begin of pass 1, end of pass 1 = begin of the similarity kernels, their end
+  // multi-GPU (RCCL over xGMI): one communicator per context, created by limg_hip_comm_init
+  ncclComm_t comm = nullptr;
+  int commRank = 0, commWorld = 1;
+  // limg_hip_encode3d_chain_device: phase 2 is only valid right after phase 1 of the same strip (the context holds the intermediate results)
+  const void *chainIn = nullptr;
+  size_t chainX = 0, chainY = 0, chainBefore = 0;
+  const void *chainFac[3] = { nullptr, nullptr, nullptr }; // phase 1 left the pre-dither factor bytes in these planes
+  int chainAlpha = 0, chainFast = 0;
+  uint32_t chainEf = 0;
+  DevBuf commWords; // [0] this rank's value, [1] its chain base, [8 ...] the all-gathered values
+  DevBuf streamFac, streamTiles, streamUnits, streamStatus, streamBuf; // stream packer: 3 factor planes, per-tile payload words; decode status word; host-entry staging
+  // optional per-kernel timing (bench): 4 events per encode, recorded on the caller's stream, read back in one go
+  int persistentWorkgroups = 1280; // 5 x the device's CU count (set at init): the unit the launches scale (x 6 / 5 with the float stage in its own kernel)
+  bool forceSplit = false; // options: run the three-kernel path even where the fused kernel applies (A/B, tests)
+  bool profiling = false;
+  std::vector<hipEvent_t> events;
+  size_t eventsUsed = 0;
+
+  // every device buffer above, in ONE list: what limg_hip_shutdown frees and limg_hip_context_device_bytes counts (a buffer added to the context goes here)
+  template <class Ctx, class F>
+  static void for_each_device_buffer(Ctx &c, F &&f)
+  {
+    for (auto *b : { &c.records, &c.shifts, &c.stripCalls, &c.stripBase, &c.invN, &c.noise, &c.noiseDyn, &c.noiseStates, &c.noiseCk, &c.park, &c.batchTable, &c.stats,
+                     &c.lookback, &c.accTable, &c.devStatus, &c.in, &c.planes, &c.hostWords, &c.cmp, &c.bFlags, &c.bBound, &c.bOrder, &c.bMatch, &c.bRegions, &c.bOut,
+                     &c.bPx, &c.bFac, &c.bNoise, &c.bNoiseBase, &c.bCalls, &c.commWords, &c.streamFac, &c.streamTiles, &c.streamUnits, &c.streamStatus, &c.streamBuf })
+      f(*b);
+  }
+};
+
+namespace limg_hip
+{
+  // limg_hip_noise.cpp: the dither chain on the host
+  uint64_t chain_call(uint64_t h, unsigned n, uint8_t *noise64, bool forceSoft, bool pcg);
+  uint64_t fill_noise_table(uint64_t h, uint8_t *noise, size_t count, bool pcg);
+  uint64_t chain_checkpoints(uint64_t h, size_t calls, size_t every, uint64_t *pOut, bool pcg);
+  void chain_walk_rows(uint64_t &h, size_t &call, uint32_t by0, uint32_t by1, uint32_t blocksX, uint32_t stripsX, size_t sizeX, size_t sizeY, uint32_t chainCount, uint32_t chainRows,
+                       const uint32_t *shifts, uint32_t *stripBase, unsigned long long *states, uint8_t *pixels, size_t maxCalls, bool pcg);
+  size_t chain_walk_blocks(uint64_t h0, uint32_t blocksX, uint32_t blocksY, uint32_t stripsX, size_t sizeX, size_t sizeY, uint32_t chainCount, uint32_t chainRows, const uint32_t *shifts,
+                           uint32_t *stripBase, unsigned long long *states, uint8_t *pixels, size_t maxCalls, bool pcg);
+
+  // ---- noise table (limg_hip_noise_table.hip) ----
+  size_t checkpoint_reach();
+  bool dense_checkpoints_host(size_t first, size_t count, uint64_t *pOut);
+  limg_hip_result ensure_checkpoints(limg_hip_context *c, size_t calls);
+  limg_hip_result grow_noise_table(limg_hip_context *c, size_t entries, hipStream_t stream);
+  bool chain_value_at(uint64_t calls, uint64_t *pValue);
+
+  // ---- profiling (limg_hip_api.hip) ----
+  void mark(limg_hip_context *c, hipStream_t stream);
+
+  // work(0) .. work(n - 1), each on a host thread of its own where the host lets us start one.  A thread that cannot be created (EAGAIN under a pid / thread limit) or a
+  // pool that cannot be allocated must neither leave joinable threads behind (their destructor calls std::terminate) nor send an exception across the extern "C"
+  // boundary: whatever did not get a thread runs on the calling thread.  `work` itself must not throw.
+  template <class F>
+  void run_on_threads(unsigned n, F &&work) noexcept
+  {
+    std::thread *pool = n > 1 ? new (std::nothrow) std::thread[n - 1] : nullptr; // default-constructed: not joinable
+    unsigned started = 0;
+    if (pool)
+      for (; started < n - 1; started++)
+      {
+        try { pool[started] = std::thread(work, started + 1); }
+        catch (...) { break; }
+      }
+    work(0u);
+    for (unsigned t = started + 1; t < n; t++) work(t);
+    for (unsigned t = 0; t < started; t++) pool[t].join();
+    delete[] pool;
+  }
+
+  // ---- the 8x8 encode (limg_hip_encode.hip, limg_hip_encode_ragged.hip) ----
+  struct Partition { uint32_t chainCount, chainRows; };
+  Partition partition(size_t sizeY, int poolThreads); // src/limg.cpp:2114-2134 in block rows
+
+  // What the public entries add to the plain (single image, whole encode) call.
+  struct EncodeExtra
+  {
+    bool streamRaw = false, fitOnly = false;
+    uint32_t *stripWords = nullptr; // stream mode, images of whole blocks: per work strip the payload words of its blocks (EncodeParams::stripWords)
+    int chainPhase = 0; // 0 = whole encode; 1 = E step + scan only (writes *dChainCalls); 2 = F step only (reads *dChainBase).  1 and 2 always take the split path.
+    unsigned long long *dChainCalls = nullptr;
+    const unsigned long long *dChainBase = nullptr;
+    size_t chainBlocksBefore = 0;
+    // batch (host array of batchCount entries, batchCount > 1): the images of a batched encode -- same shape, whole 8x8 blocks, all 11 planes -- in one launch
+    // pair (or, limg_hip_options.batch_sub_images, a pipeline of launch pairs); dIn / dInfo are then those of image 0.  The caller has checked all of that.
+    const ImageIO *batch = nullptr;
+    size_t batchCount = 1;
+    // ---- a sub-image of a larger encode (the two parts of an image whose last block row is partial: encode_height_ragged) ----
+    bool inner = false;            // part of a larger encode: no statistics launch of its own, no reset of the context's chain / statistics state
+    int marks = 2;                 // profiling events: 2 = all four, 1 = all but the last, 0 = none
+    const Partition *part = nullptr; // the dither-chain partition of the WHOLE image (a sub-image cannot derive it from its own height)
+    size_t scratchRow0 = 0;        // this sub-image's first block row in the per-block scratch (and in the caller's compact outputs)
+    size_t scratchRows = 0;        // block rows the scratch must hold (0: this call's own)
+    const unsigned long long *dPrevDesc = nullptr; // ragged sub-image: its chain continues the one whose dither-call count is the low word of this look-back descriptor
+  };
+
+  limg_hip_result encode_device(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *dInfo,
+                                const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast, hipStream_t stream, const EncodeExtra &x = EncodeExtra());
+
+  // One encode as encode_device has set it up: what every launch path reads.
+  struct EncodeJob
+  {
+    limg_hip_context *c;
+    hipStream_t stream;
+    const EncodeExtra &x;
+    const limg_hip_encode3d_info *dInfo;
+    size_t sizeX, sizeY;
+    EncodeParams p;
+    Partition pt;
+    int channels;
+    bool ragged, fullPlanes, fused, wantStats;
+    size_t blocks, strips; // of all images of the launch
+    void mark_if(int level) const { if (x.marks >= level) mark(c, stream); } // profiling events: x.marks says which of an encode's four this call records
+  };
+  limg_hip_result encode_stats(const EncodeJob &e);
+  // images with partial edge blocks (limg_hip_encode_ragged.hip): the split path's kernels around a dither chain the host walks
+  limg_hip_result encode_ragged(EncodeJob &e);
+}
+
+#endif

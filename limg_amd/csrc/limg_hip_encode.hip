@@ -1,0 +1,605 @@
+// limg_hip_encode.hip -- the 8x8 encode: its parameters, the launch paths of an image of whole blocks (fused, sub-batch pipeline, chain phases, split) and the
+// dispatcher that picks one (encode_device); the *_device, batch, chain and stats entries of the C ABI.  Images with partial edge blocks: limg_hip_encode_ragged.hip.
+// Mirrors the reference's driver (src/limg.cpp:2175-2265 threshold/flag setup, :2105-2138 strip partition).
+#include "limg_hip_context.h"
+#include "limg_search_table_accurate.h"
+
+using namespace limg_hip;
+
+namespace limg_hip
+{
+  // src/limg.cpp:2114-2134 in block rows
+  Partition partition(size_t sizeY, int poolThreads)
+  {
+    Partition pt = { 1, 0 };
+    if (poolThreads <= 0) return pt;
+    size_t thread_count = (size_t)poolThreads * 4;
+    size_t y_range = ((sizeY / kBlock) / thread_count) * kBlock;
+    if (y_range == 0)
+    {
+      thread_count = (size_t)poolThreads;
+      y_range = ((sizeY / kBlock) / thread_count) * kBlock;
+    }
+    if (y_range == 0) return pt; // every strip but the last is empty
+    pt.chainCount = (uint32_t)thread_count;
+    pt.chainRows = (uint32_t)(y_range / kBlock);
+    return pt;
+  }
+
+  // the reference's "Average Block Bits" counters (src/limg.cpp:1971-1999) of this encode, left on the device for limg_hip_last_stats
+  limg_hip_result encode_stats(const EncodeJob &e)
+  {
+    limg_hip_context *const c = e.c;
+    const EncodeParams &p = e.p;
+    if (!e.wantStats || e.x.inner) return limg_hip_success;
+    limg_hip_result rs;
+    if ((rs = c->stats.ensure(30 * 8)) != limg_hip_success) return rs;
+    if (!c->statsAccumulate) HIP_TRY(hipMemsetAsync(c->stats.p, 0, 30 * 8, e.stream));
+    launch_shift_stats(p.shifts, p.blocksX, p.blocksY, p.blocksY * p.batchCount, p.sizeX, p.sizeY, (unsigned long long *)c->stats.p, e.stream);
+    c->statsStream = e.stream; c->statsState = 1;
+    c->statsPixels = (c->statsAccumulate ? c->statsPixels : 0) + (uint64_t)e.sizeX * e.sizeY * e.x.batchCount;
+    return limg_hip_success;
+  }
+}
+
+namespace
+{
+  uint32_t chain_of_row(const Partition &pt, uint32_t row)
+  {
+    if (pt.chainCount <= 1 || pt.chainRows == 0) return 0;
+    const uint32_t c = row / pt.chainRows;
+    return c < pt.chainCount - 1 ? c : pt.chainCount - 1;
+  }
+
+  // The accurate search's automaton (tools/make_search_table.py, src/limg_bit_crush.h:668-830) in the form the kernel's scalar loads want: 8 dwords per state,
+  // every field in a dword of its own = { a | phase2 << 5 | final << 31, byte offset on pass, byte offset on fail, b, c, mul(a), mul(b), mul(c) }.  Bits 24..26 of the two
+  // offsets say which factors' shifts the SUCCESSOR's triple changes against this state's (A, B, C): a state of this DAG has several predecessors, so the change mask is a
+  // property of the edge -- with it the kernel needs no record of the shifts its cached terms were built for and no three compares per trial.
+  limg_hip_result ensure_accurate_table(limg_hip_context *c)
+  {
+    if (c->accTable.p) return limg_hip_success;
+    static const uint32_t compact[LIMG_SEARCH_ACC_STATES][2] = LIMG_SEARCH_ACC_TABLE_INIT;
+    static const uint32_t mul[9] = { 1, 2, 4, 8, 17, 36, 85, 255, 256 }; // (1 << s) + decode_bias(s), src/limg_bit_crush_simd.h:611-619
+    std::vector<uint32_t> wide((size_t)LIMG_SEARCH_ACC_STATES * 8);
+    for (size_t i = 0; i < (size_t)LIMG_SEARCH_ACC_STATES; i++)
+    {
+      const uint32_t w0 = compact[i][0], w1 = compact[i][1];
+      uint32_t *e = &wide[i * 8];
+      if (w0 >> 31) { e[0] = 1u << 31; continue; }
+      const uint32_t a = w0 & 15u, b = (w0 >> 4) & 15u, cc = (w0 >> 8) & 15u;
+      e[0] = a | ((w0 & 0x1000u) ? 0x20u : 0u);
+      e[1] = (w1 & 0xFFFFu) * 32u; e[2] = (w1 >> 16) * 32u;
+      e[3] = b; e[4] = cc;
+      e[5] = mul[a]; e[6] = mul[b]; e[7] = mul[cc];
+    }
+    static_assert((size_t)LIMG_SEARCH_ACC_STATES * 32u < (1u << 24), "offsets leave bits 24..26 free");
+    for (size_t i = 0; i < (size_t)LIMG_SEARCH_ACC_STATES; i++)
+    {
+      uint32_t *e = &wide[i * 8];
+      if (e[0] >> 31) continue;
+      for (int k = 1; k <= 2; k++)
+      {
+        const uint32_t *n = &wide[(e[k] / 32u) * 8];
+        uint32_t mask = 0;
+        if (!(n[0] >> 31)) mask = ((n[0] & 31u) != (e[0] & 31u) ? 1u : 0u) | (n[3] != e[3] ? 2u : 0u) | (n[4] != e[4] ? 4u : 0u);
+        e[k] |= mask << 24;
+      }
+    }
+    limg_hip_result r = c->accTable.ensure(wide.size() * 4);
+    if (r != limg_hip_success) return r;
+    if (hipMemcpy(c->accTable.p, wide.data(), wide.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { c->accTable.release(); return limg_hip_error_Generic; }
+    return limg_hip_success;
+  }
+
+  limg_hip_result ensure_pipe_events(limg_hip_context *c, size_t n)
+  {
+    if (!c->fitStream) HIP_TRY(hipStreamCreateWithFlags(&c->fitStream, hipStreamNonBlocking));
+    while (c->pipeEvents.size() < n)
+    {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      c->pipeEvents.push_back(e);
+    }
+    return limg_hip_success;
+  }
+
+  limg_hip_result encode_height_ragged(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *dInfo,
+                                       const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast, hipStream_t stream, const EncodeExtra &x);
+
+  // The whole 8x8 encode's EncodeParams: geometry, thresholds and flags, the per-block / per-strip scratch, the vector-access flags, the batch table and the noise
+  // table; then the chain-phase arguments and which kernels apply (e.fused, p.prefit).
+  limg_hip_result encode_params(EncodeJob &e, const uint32_t *dIn, const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast)
+  {
+    limg_hip_context *const c = e.c;
+    const EncodeExtra &x = e.x;
+    const limg_hip_encode3d_info *const dInfo = e.dInfo;
+    const size_t sizeX = e.sizeX, sizeY = e.sizeY, batchCount = x.batchCount;
+    const ImageIO *const batch = x.batch;
+    EncodeParams &p = e.p;
+    memset(&p, 0, sizeof(p));
+    p.io.in = dIn;
+    p.sizeX = (uint32_t)sizeX; p.sizeY = (uint32_t)sizeY;
+    p.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock);
+    p.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
+    p.stripsX = (p.blocksX + kStripBlocks - 1) / kStripBlocks;
+    // thresholds and flags, src/limg.cpp:2186-2212
+    const uint64_t maxPixel = (uint64_t)0x6 * (errorFactor / 2) * 7, maxBlock = (uint64_t)0x4 * (errorFactor / 2) * 7;
+    p.maxPixel32 = maxPixel > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxPixel;
+    p.maxBlock = maxBlock;
+    { const uint64_t lim = (maxBlock * 64ull + 15ull) >> 4; p.blockLimitFull = lim > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim; }
+    p.crushBits = errorFactor != 0;
+    p.fast = fast != 0;
+    p.accTable = nullptr;
+    if (!p.fast && p.crushBits)
+    {
+      limg_hip_result ra = ensure_accurate_table(c);
+      if (ra != limg_hip_success) return ra;
+      p.accTable = (const uint32_t *)c->accTable.p;
+    }
+    const bool forced = c->opt.forced_shift[0] >= 0 && c->opt.forced_shift[0] <= 8 && c->opt.forced_shift[1] >= 0 && c->opt.forced_shift[1] <= 8 &&
+                        c->opt.forced_shift[2] >= 0 && c->opt.forced_shift[2] <= 8;
+    for (int i = 0; i < 3; i++) p.forced[i] = forced ? c->opt.forced_shift[i] : -1;
+    p.floatFast = (c->opt.float_mode == 1 && !x.fitOnly) ? 1 : 0;
+    p.recordLimit = TOPT(c, record_limit) > 0 ? TOPT(c, record_limit) - 1 : 2700; // see kTermBias in limg_hip_kernels.hip: 3 * 2700 + 1 < 0x2000
+    const Partition pt = e.pt = x.part ? *x.part : partition(sizeY, poolThreads);
+    p.chainCount = pt.chainCount; p.chainRows = pt.chainRows;
+
+    p.batchCount = (uint32_t)batchCount;
+    p.imageStrips = p.stripsX * p.blocksY;
+    e.blocks = (size_t)p.blocksX * p.blocksY * batchCount; e.strips = (size_t)p.stripsX * p.blocksY * batchCount;
+    // the per-block / per-strip scratch: sized for the larger encode this call may be a part of, addressed from this part's first block row
+    const size_t scratchRows = x.scratchRows > (size_t)p.blocksY * batchCount ? x.scratchRows : (size_t)p.blocksY * batchCount;
+    const size_t scratchBlocks = scratchRows * p.blocksX, scratchStrips = scratchRows * p.stripsX;
+    const size_t blockOff = x.scratchRow0 * p.blocksX, stripOff = x.scratchRow0 * p.stripsX;
+    limg_hip_result r;
+    if (compact && compact->pRecords) p.records = compact->pRecords + blockOff;
+    else { if ((r = c->records.ensure(scratchBlocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r; p.records = (limg_hip_block_record *)c->records.p + blockOff; }
+    if (compact && compact->pShifts) p.shifts = compact->pShifts + blockOff;
+    else { if ((r = c->shifts.ensure(scratchBlocks * 4)) != limg_hip_success) return r; p.shifts = (uint32_t *)c->shifts.p + blockOff; }
+    if ((r = c->invN.ensure(scratchBlocks * 16)) != limg_hip_success) return r;
+    p.invN = (float *)c->invN.p + blockOff * 4;
+    if ((r = c->stripCalls.ensure(scratchStrips * 4)) != limg_hip_success) return r;
+    if ((r = c->stripBase.ensure(scratchStrips * 4)) != limg_hip_success) return r;
+    p.stripCalls = (uint32_t *)c->stripCalls.p + stripOff; p.stripBase = (uint32_t *)c->stripBase.p + stripOff;
+    const bool fullPlanes = e.fullPlanes;
+    p.storePlanes = dInfo != nullptr;
+    p.fullPlanes = fullPlanes;
+    p.streamRaw = x.streamRaw && !fullPlanes;
+    p.stripWords = (x.streamRaw && !fullPlanes) ? x.stripWords : nullptr;
+    p.fitOnly = x.fitOnly && !dInfo;
+    if (dInfo) p.io.info = *dInfo;
+    // 16-byte vector access straight on caller pointers only where the address is 16-byte aligned for every row: sliced or offset
+    // device pointers take the dword paths
+    p.vecIn = (sizeX % 4 == 0) && (((uintptr_t)dIn) & 15u) == 0;
+    p.vecPlanes = 0;
+    if (dInfo && fullPlanes && sizeX % 4 == 0)
+    {
+      uintptr_t bits = 0;
+      const void *const *pp = reinterpret_cast<const void *const *>(dInfo);
+      for (int i = 1; i < 8; i++) bits |= (uintptr_t)pp[i]; // pShiftABCX .. pColCMax
+      p.vecPlanes = (bits & 15u) == 0;
+    }
+    p.vecFactors8 = dInfo && (sizeX % 8 == 0) && ((((uintptr_t)dInfo->pFactorsA) | ((uintptr_t)dInfo->pFactorsB) | ((uintptr_t)dInfo->pFactorsC)) & 7u) == 0;
+    p.vecDecoded = dInfo && fullPlanes && (sizeX % 4 == 0) && (((uintptr_t)dInfo->pDecoded) & 15u) == 0;
+    p.vecFactors = dInfo && (sizeX % 16 == 0) && ((((uintptr_t)dInfo->pFactorsA) | ((uintptr_t)dInfo->pFactorsB) | ((uintptr_t)dInfo->pFactorsC)) & 15u) == 0;
+    if (batchCount > 1)
+    { // the 16-byte access paths only if every image of the batch allows them; the table goes to the device behind whatever the stream still holds
+      for (size_t i = 1; i < batchCount; i++)
+      {
+        uintptr_t bits = 0;
+        const void *const *pp = reinterpret_cast<const void *const *>(&batch[i].info);
+        for (int k = 1; k < 8; k++) bits |= (uintptr_t)pp[k];
+        p.vecPlanes = p.vecPlanes && (bits & 15u) == 0;
+        p.vecIn = p.vecIn && (((uintptr_t)batch[i].in) & 15u) == 0;
+        p.vecDecoded = p.vecDecoded && (((uintptr_t)batch[i].info.pDecoded) & 15u) == 0;
+        p.vecFactors8 = p.vecFactors8 && ((((uintptr_t)batch[i].info.pFactorsA) | ((uintptr_t)batch[i].info.pFactorsB) | ((uintptr_t)batch[i].info.pFactorsC)) & 7u) == 0;
+        p.vecFactors = p.vecFactors && ((((uintptr_t)batch[i].info.pFactorsA) | ((uintptr_t)batch[i].info.pFactorsB) | ((uintptr_t)batch[i].info.pFactorsC)) & 15u) == 0;
+      }
+      if ((r = c->batchTable.ensure(batchCount * sizeof(ImageIO))) != limg_hip_success) return r;
+      launch_set_batch_table((ImageIO *)c->batchTable.p, batch, batchCount, e.stream); // through kernel arguments: stream-ordered, and the host array may die right away
+      p.batch = (const ImageIO *)c->batchTable.p;
+    }
+
+    if (dInfo && !e.ragged)
+    {
+      // longest chain, in blocks: every block makes at most 3 dither calls
+      uint32_t maxRows = p.blocksY;
+      if (pt.chainCount > 1 && (pt.chainCount - 1) * pt.chainRows < p.blocksY) maxRows = p.blocksY - (pt.chainCount - 1) * pt.chainRows; // the last chain takes the remainder, never fewer rows than the others
+      if ((r = grow_noise_table(c, ((size_t)maxRows * p.blocksX + x.chainBlocksBefore) * 3, e.stream)) != limg_hip_success) return r;
+      p.noise = (const uint8_t *)c->noise.p;
+      p.noiseLast = (uint32_t)(c->noiseCount - 1);
+    }
+
+    const int chainPhase = x.chainPhase;
+    if (chainPhase != 0 && (e.ragged || !dInfo || poolThreads != 0)) return limg_hip_error_InvalidParameter; // a chain shared between GPUs: whole 8x8 blocks, one chain
+    p.chainCallsOut = chainPhase == 1 ? x.dChainCalls : nullptr;
+    p.chainBase = chainPhase == 2 ? x.dChainBase : nullptr;
+    // The float stage as its own launch, one lane per block (limg_hip_fit_tpb.hip), wherever every block is a whole 8x8: the E step then starts from the records.
+    p.prefit = (!e.ragged && c->opt.legacy_float_stage == 0 && (((uintptr_t)p.records) & 15u) == 0) ? 1 : 0; // k_fit_tpb stores records 16 bytes at a time
+    e.fused = dInfo != nullptr && !e.ragged && (!c->forceSplit || batchCount > 1) && chainPhase == 0;
+    e.wantStats = c->opt.collect_stats != 0 && dInfo != nullptr && chainPhase == 0;
+    return limg_hip_success;
+  }
+
+  // the persistent kernel's ticket (16 B) and one 8-byte look-back descriptor per work strip, zero at its start: k_fit_tpb clears them on its way (one launch
+  // and its gaps less per image); without that kernel, a memset
+  limg_hip_result fused_scratch(EncodeJob &e, const limg_hip_compact_out *compact)
+  {
+    limg_hip_context *const c = e.c;
+    EncodeParams &p = e.p;
+    limg_hip_result r;
+    if ((r = c->lookback.ensure(16 * (e.x.batchCount + 1) + e.strips * 8)) != limg_hip_success) return r; // (room for one ticket per sub-batch)
+    p.ticket = (uint32_t *)c->lookback.p;
+    p.desc = (unsigned long long *)((uint8_t *)c->lookback.p + 16);
+    p.zeroLookback = p.prefit ? 1 : 0;
+    if (!p.prefit) HIP_TRY(hipMemsetAsync(c->lookback.p, 0, 16 + e.strips * 8, e.stream));
+    if (!c->devStatus.p)
+    {
+      if ((r = c->devStatus.ensure(16)) != limg_hip_success) return r;
+      HIP_TRY(hipMemsetAsync(c->devStatus.p, 0, 16, e.stream));
+    }
+    p.timeout = (uint32_t *)c->devStatus.p;
+#ifdef LIMG_HIP_TEST_HOOKS
+    p.lookbackSpins = c->topt.lookback_spins > 0 ? (uint32_t)c->topt.lookback_spins : (1u << 22);
+    p.testSkipStrip = c->topt.skip_publish_strip > 0 ? (uint32_t)c->topt.skip_publish_strip - 1u : ~0u;
+    p.testBaseErrStrip = c->topt.base_error_strip > 0 ? (uint32_t)c->topt.base_error_strip - 1u : ~0u;
+#endif
+    p.compactOut = compact != nullptr || e.wantStats; // the statistics are reduced from the raster-order shift words
+    if ((r = c->park.ensure((size_t)(c->persistentWorkgroups / 5 * 6) * 2 * 8192)) != limg_hip_success) return r; // 6 workgroups per CU: the kernel's launch bound
+    p.park = (uint8_t *)c->park.p;
+    return limg_hip_success;
+  }
+
+  // workgroups per CU of the persistent kernel: 6 once the float stage is out (7 fit and were measured: no faster, the kernel is issue-bound), 5 with it inside;
+  // limg_hip_options.test_wg_per_cu lowers it (A/B runs), never above the launch bound the park slots are sized for
+  int wg_per_cu(const limg_hip_context *c, int deflt)
+  {
+    const int t = TOPT(c, wg_per_cu);
+    return (t >= 1 && t < deflt) ? t : deflt;
+  }
+
+  // A list of images as a PIPELINE of launch pairs (limg_hip_options.batch_sub_images): k_fit_tpb of sub-batch k + 1 runs on a stream of the context's own next to
+  // the persistent kernel of sub-batch k.  On content with short searches (BASELINE configs 2 / 4: ~2 trials per block) the persistent kernel waits for its plane
+  // stores a third of the time while k_fit_tpb is pure vector work: side by side they fill each other's gaps.  The persistent kernel leaves the float stage room
+  // to be resident: 5 workgroups per CU instead of 6 (at 6 x 80 VGPRs nothing else fits on a SIMD) for every sub-batch but the last.
+  // Measured on 4096^2 random-gradient lists (profiles/archive/r04_pipeline_sweep.md): 64 images 66.5 -> 73.3 Gpixel/s in sub-batches of 8 (4: 70.9, 16: 71.9); 16 images
+  // +3.5 % in sub-batches of 4; 8 images and fewer: nothing to gain (the lone first float stage and the 5-workgroup launches cost what the overlap saves).
+  size_t sub_batch_images(const EncodeJob &e)
+  {
+    const limg_hip_options &o = e.c->opt;
+    if (!e.fused || e.x.batchCount <= 1 || !e.p.prefit) return 0;
+    if (o.batch_sub_images > 0) return (size_t)o.batch_sub_images;
+    if (o.batch_sub_images == 0) return e.x.batchCount >= 32 ? 8 : (e.x.batchCount >= 16 ? 4 : 0);
+    return 0;
+  }
+
+  limg_hip_result encode_sub_batches(EncodeJob &e, size_t subImages)
+  {
+    limg_hip_context *const c = e.c;
+    const EncodeParams &p = e.p;
+    const size_t batchCount = e.x.batchCount;
+    const hipStream_t stream = e.stream;
+    // A/B hook (limg_hip_options.test_pipeline): bits 0..3 = 1 + k_fit_tpb's wave priority, bits 4..7 = workgroups per CU of the overlapped persistent launches,
+    // bits 8..15 = images of the first sub-batch (whose float stage runs alone)
+    const uint32_t knobs = (uint32_t)TOPT(c, pipeline);
+    const int fitPrio = (knobs & 15u) ? (int)(knobs & 15u) - 1 : 0, wgOverlapRaw = ((knobs >> 4) & 15u) ? (int)((knobs >> 4) & 15u) : 5,
+              wgOverlap = wgOverlapRaw > 6 ? 6 : wgOverlapRaw; // never above the launch bound the park slots are sized for
+    const size_t firstSub = ((knobs >> 8) & 255u) && ((knobs >> 8) & 255u) < subImages ? (size_t)((knobs >> 8) & 255u) : subImages;
+    const size_t nSub = 1 + (batchCount - firstSub + subImages - 1) / subImages;
+    limg_hip_result r;
+    if ((r = ensure_pipe_events(c, 2 * nSub + 1)) != limg_hip_success) return r;
+    const size_t imgBlocks = (size_t)p.blocksX * p.blocksY, imgStrips = (size_t)p.imageStrips;
+    auto sub = [&](size_t k) -> EncodeParams
+    {
+      EncodeParams q = p;
+      const size_t i0 = k == 0 ? 0 : firstSub + (k - 1) * subImages, want = k == 0 ? firstSub : subImages, n = batchCount - i0 < want ? batchCount - i0 : want;
+      q.batch = p.batch + i0; q.batchCount = (uint32_t)n;
+      q.io = e.x.batch[i0]; // (what the kernels read when a sub-batch is a single image)
+      q.records = p.records + i0 * imgBlocks; q.shifts = p.shifts + i0 * imgBlocks; q.invN = p.invN + i0 * imgBlocks * 4;
+      uint8_t *lb = (uint8_t *)c->lookback.p + k * 16 + i0 * imgStrips * 8; // sub-batch k: its ticket, then the descriptors of its strips
+      q.ticket = (uint32_t *)lb; q.desc = (unsigned long long *)(lb + 16);
+      q.fitPrio = k == 0 ? 0 : fitPrio;
+      return q;
+    };
+    hipStream_t fs = c->fitStream;
+    hipEvent_t *ev = c->pipeEvents.data(); // [0]: fork; [1 + 2 k]: k_fit_tpb of sub-batch k done; [2 + 2 k]: the persistent kernel of sub-batch k is next on `stream`
+    e.mark_if(1);
+    HIP_TRY(hipEventRecord(ev[0], stream)); // everything the caller's stream holds so far (inputs, the image table, earlier encodes that use the scratch)
+    HIP_TRY(hipStreamWaitEvent(fs, ev[0], 0));
+    launch_fit_tpb(sub(0), e.channels, fs);
+    HIP_TRY(hipEventRecord(ev[1], fs));
+    for (size_t k = 0; k < nSub; k++)
+    {
+      HIP_TRY(hipStreamWaitEvent(stream, ev[1 + 2 * k], 0));
+      if (k == 0) e.mark_if(1); // (k_fit_tpb of the first sub-batch: the only float-stage work that runs alone)
+      if (k + 1 < nSub)
+      {
+        HIP_TRY(hipEventRecord(ev[2 + 2 * k], stream));
+        HIP_TRY(hipStreamWaitEvent(fs, ev[2 + 2 * k], 0));
+        launch_fit_tpb(sub(k + 1), e.channels, fs);
+        HIP_TRY(hipEventRecord(ev[3 + 2 * k], fs));
+      }
+      launch_encode_persistent(sub(k), e.channels, c->persistentWorkgroups / 5 * (k + 1 < nSub ? wgOverlap : wg_per_cu(c, 6)), stream);
+    }
+    e.mark_if(1); e.mark_if(2);
+    HIP_TRY(hipGetLastError());
+    return encode_stats(e);
+  }
+
+  // k_fit_tpb (where the float stage is its own launch) + the persistent kernel: E step, look-back scan and F step of every strip in one launch
+  limg_hip_result encode_fused(EncodeJob &e)
+  {
+    const EncodeParams &p = e.p;
+    if (p.prefit)
+    {
+      e.mark_if(1);
+      launch_fit_tpb(p, e.channels, e.stream);
+    }
+    e.mark_if(1);
+    launch_encode_persistent(p, e.channels, e.c->persistentWorkgroups / 5 * wg_per_cu(e.c, p.prefit ? 6 : 5), e.stream);
+    e.mark_if(1);
+    if (p.prefit) e.mark_if(2); else { e.mark_if(1); e.mark_if(2); } // 4 events per encode: with the float stage as its own launch the intervals are {k_fit_tpb, k_encode_persistent, -}
+    HIP_TRY(hipGetLastError());
+    return encode_stats(e);
+  }
+
+  // phase 2 of a chain encode: the E step and the scan of this very image ran in phase 1 -- records, shift words, strip bases and the pre-dither factor bytes are
+  // where they left them
+  limg_hip_result encode_chain_phase2(EncodeJob &e)
+  {
+    mark(e.c, e.stream); // a chain encode records 4 events over its two phases: intervals {E step + scan, exchange between the phases, F step}
+    launch_dither_store(e.p, e.channels, e.stream);
+    mark(e.c, e.stream);
+    HIP_TRY(hipGetLastError());
+    return limg_hip_success;
+  }
+
+  // The split path on an image of whole blocks: [k_fit_tpb] + k_fit_search, the strip scan, k_dither_store.  Also pass 1 of the merged-block encoder (records only),
+  // `_perf` (nothing to store) and phase 1 of a chain encode (E step + scan).
+  limg_hip_result encode_split(EncodeJob &e)
+  {
+    const EncodeParams &p = e.p;
+    if (p.prefit)
+    {
+      e.mark_if(1);
+      launch_fit_tpb(p, e.channels, e.stream);
+      if (p.fitOnly)
+      { // pass 1 of the merged-block encoder: the records are all it wants
+        e.mark_if(1); e.mark_if(1); e.mark_if(2);
+        HIP_TRY(hipGetLastError());
+        return limg_hip_success;
+      }
+    }
+    else e.mark_if(1); // split path intervals: {k_fit_tpb + k_fit_search, scan, k_dither_store}
+    launch_fit_search(p, e.channels, e.stream);
+    if (e.x.chainPhase != 1) e.mark_if(1);
+    if (!e.dInfo)
+    {
+      e.mark_if(1); e.mark_if(2);
+      HIP_TRY(hipGetLastError());
+      return limg_hip_success; // `_perf` behaviour: nothing to dither into, nothing to store
+    }
+    launch_strip_scan(p, e.stream);
+    if (e.x.chainPhase == 1)
+    {
+      mark(e.c, e.stream);
+      HIP_TRY(hipGetLastError());
+      return limg_hip_success;
+    }
+    e.mark_if(1);
+    launch_dither_store(p, e.channels, e.stream);
+    e.mark_if(2);
+    HIP_TRY(hipGetLastError());
+    return encode_stats(e);
+  }
+}
+
+namespace limg_hip
+{
+  // One 8x8 encode, whichever of its paths applies.
+  limg_hip_result encode_device(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *dInfo,
+                                const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast, hipStream_t stream, const EncodeExtra &x)
+  {
+    const int chainPhase = x.chainPhase;
+    const size_t batchCount = x.batchCount;
+    if (!c || !dIn) return limg_hip_error_ArgumentNull;
+    if (chainPhase == 0 && !x.inner) c->chainIn = nullptr; // the context's per-block scratch is about to be reused
+    if (sizeX == 0 || sizeY == 0 || sizeX > 0x7FFFFFF8ull || sizeY > 0x7FFFFFF8ull) return limg_hip_error_InvalidParameter;
+    bool fullPlanes = true;
+    if (dInfo)
+    {
+      // either all 11 planes, or (compact mode) only the three factor planes with the eight uint32 planes all NULL
+      const void *const *pp = reinterpret_cast<const void *const *>(dInfo);
+      int n32 = 0;
+      for (int i = 0; i < 8; i++) n32 += pp[i] != nullptr;
+      for (int i = 8; i < 11; i++)
+        if (!pp[i]) return limg_hip_error_ArgumentNull;
+      if (n32 != 0 && n32 != 8) return limg_hip_error_ArgumentNull;
+      fullPlanes = n32 == 8;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const bool ragged = (sizeX % kBlock) != 0 || (sizeY % kBlock) != 0;
+    // An image whose WIDTH is whole blocks but whose last block row is partial (BASELINE config 1's shape class: 1024 x 618): every block row but the last
+    // is on the fast path (its dither chain is the seed's orbit, the noise table applies); only the last row needs the host to walk its chain.
+    if (ragged && sizeX % kBlock == 0 && sizeY > (size_t)kBlock && dInfo && chainPhase == 0 && batchCount == 1 && !x.inner && !x.fitOnly && !c->forceSplit &&
+        c->opt.legacy_float_stage == 0 && c->opt.dither_pcg == 0 && TOPT(c, whole_image_ragged) == 0)
+    {
+      if (((sizeX / kBlock) * ((sizeY + kBlock - 1) / kBlock)) * 3 <= checkpoint_reach())
+        return encode_height_ragged(c, dIn, sizeX, sizeY, hasAlpha, dInfo, compact, errorFactor, poolThreads, fast, stream, x);
+    }
+
+    EncodeJob e = { c, stream, x, dInfo, sizeX, sizeY };
+    e.channels = hasAlpha ? 4 : 3;
+    e.ragged = ragged;
+    e.fullPlanes = fullPlanes;
+    limg_hip_result r;
+    if ((r = encode_params(e, dIn, compact, errorFactor, poolThreads, fast)) != limg_hip_success) return r;
+    if (chainPhase == 0 && !x.inner && !c->statsAccumulate) c->statsState = 0;
+    if (batchCount > 1 && (!e.fused || !e.p.prefit || !fullPlanes)) return limg_hip_error_InvalidParameter; // (limg_hip_encode3d_batch_device sends such lists through one encode per image instead)
+    if (e.fused && (r = fused_scratch(e, compact)) != limg_hip_success) return r;
+
+    const size_t subImages = sub_batch_images(e);
+    if (subImages > 0 && subImages < batchCount) return encode_sub_batches(e, subImages); // a list of images as a pipeline of launch pairs
+    if (e.fused) return encode_fused(e);                                                    // [k_fit_tpb +] the persistent kernel
+    if (chainPhase == 2) return encode_chain_phase2(e);                                     // k_dither_store behind a chain encode's phase 1
+    if (!ragged) return encode_split(e);                                                    // [k_fit_tpb +] k_fit_search, scan, k_dither_store
+    return encode_ragged(e);                                                                // k_fit_search, the host's chain walk, k_dither_store
+  }
+}
+
+namespace
+{
+  // sizeX % 8 == 0, sizeY % 8 != 0, at least two block rows (reference: the rx x ry gather of src/limg.cpp:1899-1905 only ever sees ry < 8 in the last block row,
+  // and a dither call over 8 ry pixels is ry AES rounds, :824-879): the block rows above the last one are an image of whole blocks -- k_fit_tpb + persistent kernel
+  // with the chain partition of the WHOLE image -- and the last row goes through the split path's kernels as a one-row sub-image whose chain starts where the
+  // persistent kernel's last strip left it: that call count is the low word of the strip's look-back descriptor, and the chain value there comes from the embedded
+  // checkpoints (at most 1023 calls on foot).  The host's share is then one block row: blocksX shift words down, <= 3 blocksX calls of ry rounds, their noise up.
+  limg_hip_result encode_height_ragged(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *dInfo,
+                                       const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast, hipStream_t stream, const EncodeExtra &x)
+  {
+    const size_t topY = (sizeY / kBlock) * kBlock, blocksX = sizeX / kBlock, blocksY = topY / kBlock + 1, stripsX = (blocksX + kStripBlocks - 1) / kStripBlocks;
+    const Partition pt = partition(sizeY, poolThreads);
+    c->chainIn = nullptr;
+    c->statsState = 0;
+    limg_hip_result r;
+    EncodeExtra xt;
+    xt.streamRaw = x.streamRaw; xt.inner = true; xt.marks = 1; xt.part = &pt; xt.scratchRows = blocksY;
+    if ((r = encode_device(c, dIn, sizeX, topY, hasAlpha, dInfo, compact, errorFactor, poolThreads, fast, stream, xt)) != limg_hip_success) return r;
+    // the last block row
+    limg_hip_encode3d_info low = *dInfo;
+    {
+      const size_t skip = topY * sizeX; // pixels above the last block row, in every plane
+      uint32_t **words[] = { &low.pDecoded, &low.pShiftABCX, &low.pColAMin, &low.pColAMax, &low.pColBMin, &low.pColBMax, &low.pColCMin, &low.pColCMax };
+      uint8_t **bytes[] = { &low.pFactorsA, &low.pFactorsB, &low.pFactorsC };
+      for (uint32_t **p : words) if (*p) *p += skip;
+      for (uint8_t **p : bytes) if (*p) *p += skip;
+    }
+    EncodeExtra xb;
+    xb.streamRaw = x.streamRaw; xb.inner = true; xb.marks = 0; xb.scratchRow0 = blocksY - 1; xb.scratchRows = blocksY;
+    const Partition one = { 1, 0 };
+    xb.part = &one;
+    const bool sameChain = chain_of_row(pt, (uint32_t)blocksY - 1) == chain_of_row(pt, (uint32_t)blocksY - 2);
+    if (sameChain) xb.dPrevDesc = (const unsigned long long *)((const uint8_t *)c->lookback.p + 16) + ((blocksY - 1) * stripsX - 1);
+    if ((r = encode_device(c, dIn + topY * sizeX, sizeX, sizeY - topY, hasAlpha, &low, compact, errorFactor, 0, fast, stream, xb)) != limg_hip_success) return r;
+    mark(c, stream);
+    if (c->opt.collect_stats != 0)
+    {
+      if ((r = c->stats.ensure(30 * 8)) != limg_hip_success) return r;
+      HIP_TRY(hipMemsetAsync(c->stats.p, 0, 30 * 8, stream));
+      const uint32_t *shifts = (compact && compact->pShifts) ? compact->pShifts : (const uint32_t *)c->shifts.p;
+      launch_shift_stats(shifts, (uint32_t)blocksX, (uint32_t)blocksY, (uint32_t)blocksY, (uint32_t)sizeX, (uint32_t)sizeY, (unsigned long long *)c->stats.p, stream);
+      c->statsStream = stream; c->statsState = 1; c->statsPixels = (uint64_t)sizeX * sizeY;
+    }
+    return limg_hip_success;
+  }
+}
+
+extern "C"
+{
+  limg_hip_result limg_hip_host_partition(size_t sizeY, int poolThreads, uint32_t *pChainCount, uint32_t *pChainBlockRows)
+  {
+    if (!pChainCount || !pChainBlockRows) return limg_hip_error_ArgumentNull;
+    const Partition pt = partition(sizeY, poolThreads);
+    *pChainCount = pt.chainCount;
+    *pChainBlockRows = pt.chainRows;
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_encode3d_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *pInfo,
+                                           const limg_hip_compact_out *pCompact, uint32_t errorFactor, int poolThreads, int fastBitCrushing, void *stream)
+  {
+    return encode_device(c, pIn, sizeX, sizeY, hasAlpha, pInfo, pCompact, errorFactor, poolThreads, fastBitCrushing, (hipStream_t)stream);
+  }
+
+  // The reference encodes a list of images by calling limg_encode3d_test(_perf) once per image (src/main.cpp:278-323).  Here the images of one shape go through ONE
+  // launch pair: one k_fit_tpb grid over the blocks of all images and one persistent launch whose tickets run through the strips of image 0, image 1, ...;
+  // every image starts its own dither chain(s), so each image's planes are those of a single encode.  A small image alone cannot fill the chip for long
+  // (a 4096^2 image is ~5 strips per workgroup: ramp-up and drain are a third of its encode); a batch amortises both.
+  limg_hip_result limg_hip_encode3d_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                 const limg_hip_encode3d_info *pInfos, uint32_t errorFactor, int poolThreads, int fastBitCrushing, void *stream)
+  {
+    if (!c || !ppIn || !pInfos) return limg_hip_error_ArgumentNull;
+    if (count == 0) return limg_hip_success;
+    if (sizeX == 0 || sizeY == 0 || sizeX > 0x7FFFFFF8ull || sizeY > 0x7FFFFFF8ull) return limg_hip_error_InvalidParameter;
+    bool full = true;
+    for (size_t i = 0; i < count; i++)
+    {
+      if (!ppIn[i]) return limg_hip_error_ArgumentNull;
+      const void *const *pp = reinterpret_cast<const void *const *>(&pInfos[i]);
+      for (int k = 8; k < 11; k++)
+        if (!pp[k]) return limg_hip_error_ArgumentNull;
+      int n32 = 0;
+      for (int k = 0; k < 8; k++) n32 += pp[k] != nullptr;
+      if (n32 != 0 && n32 != 8) return limg_hip_error_ArgumentNull;
+      full = full && n32 == 8;
+    }
+    const bool ragged = (sizeX % kBlock) != 0 || (sizeY % kBlock) != 0;
+    const size_t blocks = ((sizeX + kBlock - 1) / kBlock) * ((sizeY + kBlock - 1) / kBlock), strips = ((sizeX + kBlock * kStripBlocks - 1) / (kBlock * kStripBlocks)) * ((sizeY + kBlock - 1) / kBlock);
+    // per-block scratch of a launch pair is bounded (1 GiB of records): longer lists go in several launch pairs
+    size_t chunk = (size_t)(1ull << 30) / (blocks * sizeof(limg_hip_block_record));
+    if (chunk * strips > 0x7FFFFFFFull) chunk = 0x7FFFFFFFull / strips; // strip ids are 32 bits
+    if (chunk < 1) chunk = 1;
+    if (TOPT(c, batch_chunk) > 0) chunk = (size_t)TOPT(c, batch_chunk);
+    const bool oneByOne = count == 1 || ragged || !full || c->opt.legacy_float_stage != 0 || c->forceSplit;
+    std::vector<ImageIO> table;
+    limg_hip_result r = limg_hip_success;
+    for (size_t i0 = 0; i0 < count && r == limg_hip_success;)
+    {
+      const size_t n = oneByOne ? 1 : (count - i0 < chunk ? count - i0 : chunk);
+      c->statsAccumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, however many launch pairs it took
+      if (n == 1) r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, &pInfos[i0], nullptr, errorFactor, poolThreads, fastBitCrushing, (hipStream_t)stream);
+      else
+      {
+        table.resize(n);
+        for (size_t i = 0; i < n; i++) { table[i].in = ppIn[i0 + i]; table[i].info = pInfos[i0 + i]; }
+        EncodeExtra x;
+        x.batch = table.data(); x.batchCount = n;
+        r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, &pInfos[i0], nullptr, errorFactor, poolThreads, fastBitCrushing, (hipStream_t)stream, x);
+      }
+      i0 += n;
+    }
+    c->statsAccumulate = false;
+    return r;
+  }
+
+  limg_hip_result limg_hip_encode3d_chain_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *pInfo,
+                                                 uint32_t errorFactor, int fastBitCrushing, int phase, uint64_t *pCallsDevice, const uint64_t *pChainBaseDevice,
+                                                 size_t blocksBefore, void *stream)
+  {
+    if (phase != 1 && phase != 2) return limg_hip_error_InvalidParameter;
+    if (!c || (phase == 1 && !pCallsDevice) || (phase == 2 && !pChainBaseDevice) || !pInfo) return limg_hip_error_ArgumentNull;
+    // phase 2 continues the phase 1 the context holds: same strip, same planes (phase 1 left the pre-dither factor bytes in them), same parameters, and a noise
+    // table that was sized for the same chain position
+    if (phase == 2 && (c->chainIn != pIn || c->chainX != sizeX || c->chainY != sizeY || c->chainFac[0] != pInfo->pFactorsA || c->chainFac[1] != pInfo->pFactorsB ||
+                       c->chainFac[2] != pInfo->pFactorsC || c->chainAlpha != (hasAlpha != 0) || c->chainEf != errorFactor || c->chainFast != (fastBitCrushing != 0) ||
+                       c->chainBefore != blocksBefore))
+      return limg_hip_error_InvalidParameter; // no matching phase 1 pending
+    c->chainIn = nullptr;
+    EncodeExtra x;
+    x.chainPhase = phase; x.dChainCalls = (unsigned long long *)pCallsDevice; x.dChainBase = (const unsigned long long *)pChainBaseDevice; x.chainBlocksBefore = blocksBefore;
+    const limg_hip_result r = encode_device(c, pIn, sizeX, sizeY, hasAlpha, pInfo, nullptr, errorFactor, 0, fastBitCrushing, (hipStream_t)stream, x);
+    if (r == limg_hip_success && phase == 1)
+    {
+      c->chainIn = pIn; c->chainX = sizeX; c->chainY = sizeY; c->chainBefore = blocksBefore;
+      c->chainFac[0] = pInfo->pFactorsA; c->chainFac[1] = pInfo->pFactorsB; c->chainFac[2] = pInfo->pFactorsC;
+      c->chainAlpha = hasAlpha != 0; c->chainEf = errorFactor; c->chainFast = fastBitCrushing != 0;
+    }
+    return r;
+  }
+
+  // The reference's limg_encode3d_test accumulates its bit statistics on its own stack (`accum_bits`, src/limg.cpp:1975-1976) and prints them before it returns
+  // (:2232-2248): they are always the statistics of THAT call, whatever other threads encode meanwhile.  Same here: the counters are fetched inside the region the
+  // context's mutex covers, and collect_stats is switched on for this call only -- no option of a shared context is modified for good.
+  limg_hip_result limg_hip_encode3d_stats(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, limg_hip_encode3d_info *pInfo, uint32_t errorFactor,
+                                          int poolThreads, int fastBitCrushing, uint64_t *pCounters30, uint64_t *pPixels)
+  {
+    if (!c || !pCounters30) return limg_hip_error_ArgumentNull;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    const int32_t was = c->opt.collect_stats;
+    c->opt.collect_stats = 1;
+    limg_hip_result r = limg_hip_encode3d(c, pIn, sizeX, sizeY, hasAlpha, pInfo, errorFactor, poolThreads, fastBitCrushing);
+    if (r == limg_hip_success) r = limg_hip_last_stats(c, pCounters30, pPixels);
+    c->opt.collect_stats = was;
+    return r;
+  }
+}

@@ -27,30 +27,14 @@ namespace limg_hip
     // = 12 per CU) set the occupancy.  Otherwise the 64 blocks' pixels are staged in LDS first (dword loads), 17 KiB per wave, two waves per workgroup
     // (2 x 17 + 8 KiB => 3 workgroups = 6 waves per CU).  Occupancy is not what the kernel lacks: forced down to 61 VGPRs (8 waves per SIMD) it runs at the same
     // speed -- it is issue-bound on its instruction count.
-#ifndef LIMG_TPB_WG_WAVES
-#define LIMG_TPB_WG_WAVES 4
-#endif
-    template <bool DIRECT> constexpr int tpb_waves() { return DIRECT ? LIMG_TPB_WG_WAVES : 2; } // waves per workgroup: they share one copy of the table
+    template <bool DIRECT> constexpr int tpb_waves() { return DIRECT ? 4 : 2; } // waves per workgroup: they share one copy of the table
 
     // The eight rows of a lane's block, two per iteration, the NEXT two already requested: a pass is a chain of (load 32 bytes, 8 pixels of arithmetic) per row, and
     // with few waves on a SIMD -- a 4096^2 image is one round of 4 waves per SIMD, the sub-batch pipeline leaves this kernel one -- nothing else covers the load's
     // latency.  (The last iteration re-requests rows 6 and 7: harmless, and the loop stays free of a branch.)
-#ifndef LIMG_TPB_WAVES_PER_SIMD
-#define LIMG_TPB_WAVES_PER_SIMD 5
-#endif
     template <class BODY>
     __device__ __forceinline__ void for_rows(const uint32_t *my, const uint32_t pitch, BODY &&body)
     {
-#ifdef LIMG_TPB_NO_PREFETCH // A/B: the round-3 form, one row per iteration, loaded where it is used
-#pragma unroll 1
-      for (int r = 0; r < 8; r++)
-      {
-        const uint4 u = *reinterpret_cast<const uint4 *>(my + r * pitch), w = *reinterpret_cast<const uint4 *>(my + r * pitch + 4);
-        const uint32_t q[8] = { u.x, u.y, u.z, u.w, w.x, w.y, w.z, w.w };
-        body(r, q);
-      }
-      return;
-#endif
       uint4 u0 = *reinterpret_cast<const uint4 *>(my), w0 = *reinterpret_cast<const uint4 *>(my + 4);
       uint4 u1 = *reinterpret_cast<const uint4 *>(my + pitch), w1 = *reinterpret_cast<const uint4 *>(my + pitch + 4);
 #pragma unroll 1
@@ -74,7 +58,7 @@ namespace limg_hip
     template <int CH, bool FAST, bool DIRECT>
     // (8 waves per SIMD asked for explicitly: left to itself the compiler settles on 61 registers or on 132 depending on details of the epilogue; measured equal in
     //  speed on large images -- the kernel is issue-bound -- but a 4096^2 image is a single round of 4096 waves, where residency is what there is)
-    __global__ __launch_bounds__(64 * tpb_waves<DIRECT>(), DIRECT ? LIMG_TPB_WAVES_PER_SIMD : 1) void k_fit_tpb(const EncodeParams p)
+    __global__ __launch_bounds__(64 * tpb_waves<DIRECT>(), DIRECT ? 5 : 1) void k_fit_tpb(const EncodeParams p)
     {
       constexpr int kTpbWaves = tpb_waves<DIRECT>();
       __shared__ __attribute__((aligned(16))) uint32_t s_pxAll[kTpbWaves][DIRECT ? 4 : 64 * kTpbStride];

@@ -1,4 +1,4 @@
-// Internal declarations shared by the host API (limg_hip_api.hip) and the kernel files.  Not part of the C ABI.
+// Internal declarations shared by the host units (limg_hip_context.h and the files that include it) and the kernel files.  Not part of the C ABI.
 #ifndef LIMG_HIP_INTERNAL_H
 #define LIMG_HIP_INTERNAL_H
 

@@ -40,10 +40,8 @@ namespace limg_hip
 {
   namespace
   {
-#ifndef LIMG_PRIO_E
-#define LIMG_PRIO_E 2
-#endif
     constexpr int kThreads = 256;
+    constexpr int kPrioE = 2; // wave priority of the persistent kernel's E step (s_setprio)
     constexpr int kWaves = 4;
     constexpr int kBlocksPerWave = 8;
     constexpr int kRowDw = 264; // LDS pixel-row stride in dwords: 256 px + 8 pad => bank = (8*row + x) mod 32, conflict-free per 32-lane half
@@ -191,34 +189,17 @@ namespace limg_hip
     {
       const SearchEntry *tab = reinterpret_cast<const SearchEntry *>(table);
       uint32_t bestA = 0, bestB = 0, bestC = 0, minBe = 0xFFFFFFFFu;
-      // Measured and NOT adopted (LIMG_ACC_CACHE=1 builds it): the accurate search walks the shift cube row by row -- c innermost
+      // Measured and NOT adopted (removed from the tree, see git history): the accurate search walks the shift cube row by row -- c innermost
       // (src/limg_bit_crush.h:700-760) -- so factor C's shift changes with nearly every one of its ~70 trials per block while it only takes nine values; its terms for
       // the shifts 0..7 can be built once per block and picked per trial out of a 16-register vector with the wave-uniform shift as the index (VGPR index mode:
       // s_set_gpr_idx_on, two v_mov, s_set_gpr_idx_off; one 16-wide vector because LLVM expands a dynamic extract of up to 8 elements into compares and selects).
       // At equal occupancy that is 2 % faster (4.39 vs 4.49 ms at 5 workgroups per CU), but its 16 registers cost the sixth workgroup per CU, which is worth 7.5 %
       // (4.16 ms without the cache at 6).
-#ifndef LIMG_ACC_CACHE
-#define LIMG_ACC_CACHE 0
-#endif
-      typedef uint32_t u32x16_t __attribute__((ext_vector_type(16)));
-      u32x16_t cT;
-      if (LIMG_ACC_CACHE)
-      {
-        constexpr uint32_t mulOf[8] = { 1, 2, 4, 8, 17, 36, 85, 255 }; // (1 << s) + decode_bias(s)
-#pragma unroll
-        for (int sft = 0; sft < 8; sft++)
-        {
-          uint32_t rg; int bl;
-          make_terms(t.fC, (uint32_t)sft, mulOf[sft], t.nC, t.mC, rg, bl);
-          cT[sft] = rg; cT[8 + sft] = (uint32_t)bl;
-        }
-      }
-      { // the first triple is the fast search's: built unconditionally, so that the cached terms need no initial value
+      { // the first triple is the fast search's
         constexpr uint32_t root[8] = LIMG_SEARCH_ROOT;
         rebuild_A(t, root[0] & 31u, root[5]);
         rebuild_B(t, root[3], root[6]);
-        if (LIMG_ACC_CACHE) { t.tC_RG = cT[root[4]]; t.tC_B = (int)cT[8 + root[4]]; t.cC = root[4]; }
-        else rebuild_C(t, root[4], root[7]);
+        rebuild_C(t, root[4], root[7]);
       }
       uint8s_t e = sload8(tab, 0u);
       // which factors state 0's triple changes against the root triple built above (every later edge carries its mask in bits 24..26 of the successor offset)
@@ -229,16 +210,7 @@ namespace limg_hip
         const uint32_t a = e[0] & 31u;
         if (mask & 1u) rebuild_A(t, a, e[5]);
         if (mask & 2u) rebuild_B(t, e[3], e[6]);
-        if (LIMG_ACC_CACHE)
-        {
-          if (mask & 4u)
-          {
-            const uint32_t c = e[4];
-            if (c > 7) { t.tC_RG = (uint32_t)term_bias(2) * 0x10001u; t.tC_B = 0; }
-            else { t.tC_RG = cT[c]; t.tC_B = (int)cT[8 + c]; }
-          }
-        }
-        else if (mask & 4u) rebuild_C(t, e[4], e[7]);
+        if (mask & 4u) rebuild_C(t, e[4], e[7]);
         const uint32_t err = trial_pixel_error<FULL>(t, active);
         uint32_t off = e[2];
         if (__builtin_amdgcn_ballot_w64(err > maxPixel32) == 0ull)
@@ -395,25 +367,17 @@ namespace limg_hip
     // the rows allow it (p.vecPlanes: width a multiple of 4, 16-byte aligned planes), 4 bytes per lane = one row per instruction otherwise
     // The 35 bytes per pixel of output planes are written once and never read by this library: stored NON-TEMPORALLY (global_store ... nt) they do not push the
     // data the kernels DO come back to out of the L2 -- a strip's parked results (8 KiB written by its E step, read by its F step), the records and k_fit_tpb's
-    // rows.  -DLIMG_PLANE_STORES_TEMPORAL builds the plain stores (A/B, tools/r05/ab_nt_stores.sh, same box: 4096^2 gradient 0.331 -> 0.285 ms, config 4 72.6 ->
+    // rows.  Against plain stores (A/B, same box: 4096^2 gradient 0.331 -> 0.285 ms, config 4 72.6 ->
     // 74.9 Gpx/s, 8192^2 photo-noise 1.374 -> 1.360 ms; the HBM byte counters do not move -- the parked data still goes out and comes back -- the time does).
     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
     __device__ __forceinline__ void plane_store16(void *dst, const uint4 &v)
     {
-#ifdef LIMG_PLANE_STORES_TEMPORAL
-      *reinterpret_cast<uint4 *>(dst) = v;
-#else
       __builtin_nontemporal_store(u32x4_t{ v.x, v.y, v.z, v.w }, reinterpret_cast<u32x4_t *>(dst));
-#endif
     }
     __device__ __forceinline__ void plane_store8(void *dst, const uint2 &v)
     {
-#ifdef LIMG_PLANE_STORES_TEMPORAL
-      *reinterpret_cast<uint2 *>(dst) = v;
-#else
       __builtin_nontemporal_store(u32x2_t{ v.x, v.y }, reinterpret_cast<u32x2_t *>(dst));
-#endif
     }
 
     template <class P, class IO>
@@ -560,16 +524,8 @@ namespace limg_hip
       between();
       const uint8_t *facRow = L.fac + r * kFacRow + sb * kBlock;
       const int *nm = L.nm + sb * 24;
-#ifdef LIMG_X_NOGEN
-      const bool generic = false;
-#else
       const bool generic = __builtin_amdgcn_ballot_w64((fl & 1u) != 0u) != 0ull;   // wave-uniform
-#endif
-#ifdef LIMG_X_NOALPHA
-      const bool anyAlpha = false;
-#else
       const bool anyAlpha = CH == 4 && __builtin_amdgcn_ballot_w64((fl & 2u) != 0u) != 0ull;
-#endif
       const bool rawEscape = !p.fullPlanes && p.streamRaw; // compact stream: a factor at shift 8 keeps its raw byte (raw-escape of the container)
       // per-lane constants of factor k from its shift s: the shift the dither applies (0 unless 1..7), minus half the dither range, the re-expansion multiplier
       // (1 << s) + decode_bias(s) with decode_bias = {0,0,0,0,1,4,21,127,0} = byte s of a constant pair (selector 8: a zero sign fill), the bits the crushed byte keeps
@@ -1781,10 +1737,7 @@ namespace limg_hip
     // Progress: a look-back only waits for strips with smaller tickets; those were drawn earlier by workgroups that are running, and an E step never waits
     // (see "decoupled look-back" above: no strip id is ever derived from blockIdx).
     template <int CH, bool FAST, bool PREFIT, bool ACC>
-#ifndef LIMG_ACC_WG
-#define LIMG_ACC_WG 6
-#endif
-    __global__ __launch_bounds__(kThreads, PREFIT ? (ACC ? LIMG_ACC_WG : 6) : 5) void k_encode_persistent(const EncodeParams p)
+    __global__ __launch_bounds__(kThreads, PREFIT ? 6 : 5) void k_encode_persistent(const EncodeParams p)
     {
       __shared__ __attribute__((aligned(16))) uint8_t s_lds[lds_layout<PREFIT>().total];
       __shared__ uint32_t s_ticket;
@@ -1805,7 +1758,7 @@ namespace limg_hip
       // of data-dependent search lengths before the E and F steps of a CU's six workgroups interleave.  Workgroups are dealt out to the 256 CUs residency slot
       // by slot, so slot k (= blockIdx.x / 256) starts k * 3.4 us late: measured -0.5 % on the kernel, and harmless where the placement differs.
       for (uint32_t i = 0; i < (blockIdx.x >> 8); i++) __builtin_amdgcn_s_sleep(127);
-      __builtin_amdgcn_s_setprio(LIMG_PRIO_E);
+      __builtin_amdgcn_s_setprio(kPrioE);
       for (;;)
       {
         __syncthreads(); // the previous step's LDS use is over (and the rsqrt table is in place)
@@ -1839,7 +1792,7 @@ namespace limg_hip
           __builtin_amdgcn_s_setprio(0);
           const uint32_t head0 = prevImg * pf->imageStrips;
           dither_store_strip<CH, true>(*pf, *io_of(pf, prevImg), prev, prev - head0, prevImg * pf->blocksY, head0, s_lds + kLdsStrip, park + (slot ^ 1u) * kParkBytes, tid_f);
-          __builtin_amdgcn_s_setprio(LIMG_PRIO_E);
+          __builtin_amdgcn_s_setprio(kPrioE);
         }
         if (t >= S) break;
         prev = t; prevImg = img;

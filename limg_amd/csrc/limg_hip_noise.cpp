@@ -202,7 +202,7 @@ namespace limg_hip
   }
 #endif
 
-  // The 8x8 path's chain walk over an image with partial edge blocks (limg_hip_api.hip: the whole image, or the last block row of an image whose width is whole
+  // The 8x8 path's chain walk over an image with partial edge blocks (limg_hip_encode_ragged.hip: the whole image, or the last block row of an image whose width is whole
   // blocks), raster order, chains restarting at the strip partition's boundaries (src/limg.cpp:2114-2134): same recording as above, per dither call the value it starts
   // from and its pixel count; per work strip (32 blocks) the index of its first call.  Template on the AES-NI use so that the rounds are inline in the hot variant.
   namespace
@@ -253,7 +253,7 @@ namespace limg_hip
   }
 
   // Block rows [by0, by1) of the walk: continues from chain value `h` at call index `call` (both updated), restarts the chain where the partition says so.  The rows of
-  // an image may be walked in pieces, in order (the band pipeline of limg_hip_api.hip), and chains that start at the seed may be walked by different threads at once.
+  // an image may be walked in pieces, in order (the band pipeline of limg_hip_encode_ragged.hip), and chains that start at the seed may be walked by different threads at once.
   void chain_walk_rows(uint64_t &h, size_t &call, uint32_t by0, uint32_t by1, uint32_t blocksX, uint32_t stripsX, size_t sizeX, size_t sizeY, uint32_t chainCount, uint32_t chainRows,
                        const uint32_t *shifts, uint32_t *stripBase, unsigned long long *states, uint8_t *pixels, size_t maxCalls, bool pcg)
   {

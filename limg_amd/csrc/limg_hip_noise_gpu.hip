@@ -204,7 +204,7 @@ namespace limg_hip
     return table;
   }
 
-  // the chain value every LIMG_NOISE_FAR_EVERY calls, through 2^27 calls: what reaches beyond the dense table (limg_hip_api.hip ensure_checkpoints turns the far values an
+  // the chain value every LIMG_NOISE_FAR_EVERY calls, through 2^27 calls: what reaches beyond the dense table (limg_hip_noise_table.hip ensure_checkpoints turns the far values an
   // image needs into dense ones: LIMG_NOISE_FAR_EVERY calls on foot per far value, on host threads)
   const uint64_t *noise_checkpoints_far_host(size_t *pCount, size_t *pEvery)
   {

@@ -1,5 +1,5 @@
 """Maximum sizes (the reference has no size limit but memory, src/limg.cpp:2175-2265): an image of more than 5.59 M blocks, whose dither chain is longer than the embedded dense
-checkpoints reach (16 Mi calls) -- the context then makes the dense values it lacks from the embedded FAR checkpoints (limg_hip_api.hip ensure_checkpoints) -- and whose planes'
+checkpoints reach (16 Mi calls) -- the context then makes the dense values it lacks from the embedded FAR checkpoints (limg_hip_noise_table.hip ensure_checkpoints) -- and whose planes'
 byte offsets pass 2^32.  24576^2 = 604 Mpixels, 9.4 M blocks, up to 28 M dither calls, ~22 GiB of device memory at a time (tools/huge_image_check.py is the same at 32768^2 = 1 Gpixel).
 The whole image IS pinned against the real reference: tests/golden/fullsize.json `pn24576_strips` holds, per strip of 3072 rows, the position-sensitive 64-bit checksums of the
 eleven planes the reference (oracle/_ref, one chain, one thread, 5 minutes in the build container: tools/make_golden_fullsize.py) wrote -- computed here on the device.  Around it,

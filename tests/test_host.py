@@ -328,7 +328,7 @@ def test_noise_checkpoints_are_the_chain():
 
 
 def test_dense_checkpoints_beyond_the_embedded_table():
-    """What a context uploads for an image of more than 5.59 M blocks (limg_hip_api.hip ensure_checkpoints): dense chain values beyond the embedded table's 16 Mi calls,
+    """What a context uploads for an image of more than 5.59 M blocks (limg_hip_noise_table.hip ensure_checkpoints): dense chain values beyond the embedded table's 16 Mi calls,
     made from the far table on host threads (limg_hip_host_dense_checkpoints) == the serial walk; across the boundary, over whole and partial far stretches; refused
     beyond the far table's reach."""
     import ctypes as C

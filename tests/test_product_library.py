@@ -29,6 +29,12 @@ def test_exports():
     for sym in limg_amd.TEST_ABI_SYMBOLS:
         assert sym not in plain and (" T " + sym + "\n") in hooks, sym
     assert not re.search(r"test", plain, re.I), [ln for ln in plain.splitlines() if re.search(r"test", ln, re.I)]
+    # the C ABI and nothing else: every defined limg_hip_* symbol is one of the ABI's, and no internal of the library (namespace limg_hip) is exported
+    for lib, want in ((PLAIN, set(limg_amd.ABI_SYMBOLS)), (limg_amd.TEST_LIB_PATH, set(limg_amd.ABI_SYMBOLS + limg_amd.TEST_ABI_SYMBOLS))):
+        names = [ln.split()[-1] for ln in subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout.splitlines() if ln.strip()]
+        assert {n for n in names if n.startswith("limg_hip_")} == want, (lib, sorted({n for n in names if n.startswith("limg_hip_")} ^ want))
+        demangled = subprocess.run(["nm", "-D", "--defined-only", "-C", lib], capture_output=True, text=True, check=True).stdout
+        assert "limg_hip::" not in demangled, (lib, [ln for ln in demangled.splitlines() if "limg_hip::" in ln])
     header = open(os.path.join(ROOT, "include", "limg_hip.h")).read()
     body = header[header.index("typedef struct limg_hip_options"):header.index("} limg_hip_options;")]
     assert "test_" not in body and "uint32_t struct_size;" in body

@@ -224,7 +224,7 @@ def build_accurate():
 
 def encode_accurate(trans):
     """compact entry = (a | b << 4 | c << 8 | phase2 << 12 | final << 31,  next on pass | next on fail << 16) -- state indices; the library expands it at context
-    creation into the 32-byte form the kernel reads (limg_hip_api.hip)."""
+    creation into the 32-byte form the kernel reads (limg_hip_encode.hip ensure_accurate_table)."""
     assert len(trans) < 65536
     words = []
     for t in trans:
