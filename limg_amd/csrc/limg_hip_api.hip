@@ -148,7 +148,7 @@ extern "C"
   // Blocks until the device is idle and reports a look-back timeout of the persistent kernel as limg_hip_error_Generic.  Observed once, in round 4: a build whose
   // workgroups took their first strip from blockIdx instead of the ticket dead-locked two contexts' kernels against each other until the bound fired;
   // with every strip id drawn from the ticket a look-back cannot wait on a workgroup that is not running.  The bound stays as the safety net, and a timeout is loud:
-  // the strips behind it store nothing chain-dependent (limg_hip_kernels.hip "decoupled look-back").
+  // the strips behind it store nothing chain-dependent (limg_hip_lookback.h "decoupled look-back").
   limg_hip_result limg_hip_check_device_status(limg_hip_context *c)
   {
     if (!c) return limg_hip_error_ArgumentNull;

@@ -1,4 +1,4 @@
-// limg_hip_device.h -- device helpers shared by the kernel files (limg_hip_kernels.hip: 8x8 blocks; limg_hip_blocked.hip: merged regions):
+// limg_hip_device.h -- device helpers shared by the kernel files (limg_hip_kernels.hip and the headers it includes: 8x8 blocks; limg_hip_blocked.hip: merged regions):
 // wave64 reductions, the x86 float semantics of the reference's SSE path (DPPS order, RSQRTPS table, sign-normalised unit vectors), the generic
 // 32-bit bit-crush trial (a9) and the literal shift searches (a10-a12).  Everything lives in an anonymous namespace: each including
 // translation unit gets its own copy (including the 4 KiB RSQRTPS table).  Reference file:line citations are at each function.
@@ -296,8 +296,8 @@ namespace limg_hip
       mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mx), 63));
     }
 
-    __device__ __forceinline__ float vmin_(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-    __device__ __forceinline__ float vmax_(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+    __device__ __forceinline__ float vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+    __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
     // Exact min and max of FOUR independent value pairs over the wave at once, results wave-uniform.  gfx950's lane-swap instructions fold the values into
     // one register on the way down: v_permlane32_swap puts the two halves of a pair of values side by side (one op then reduces both from 64 to 32 lanes),
@@ -308,12 +308,12 @@ namespace limg_hip
       auto swap32 = [](float a, float b, float &x, float &y) { auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false); x = __uint_as_float(r[0]); y = __uint_as_float(r[1]); };
       auto swap16 = [](float a, float b, float &x, float &y) { auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false); x = __uint_as_float(r[0]); y = __uint_as_float(r[1]); };
       float x, y;
-      swap32(mn[0], mn[1], x, y); const float n01 = vmin_(x, y); // lanes 0..31: value 0 (64 -> 32 lanes), lanes 32..63: value 1
-      swap32(mx[0], mx[1], x, y); const float x01 = vmax_(x, y);
-      swap32(mn[2], mn[3], x, y); const float n23 = vmin_(x, y);
-      swap32(mx[2], mx[3], x, y); const float x23 = vmax_(x, y);
-      swap16(n01, n23, x, y); float n = vmin_(x, y); // rows of 16 lanes: values 0, 2, 1, 3
-      swap16(x01, x23, x, y); float m = vmax_(x, y);
+      swap32(mn[0], mn[1], x, y); const float n01 = vmin(x, y); // lanes 0..31: value 0 (64 -> 32 lanes), lanes 32..63: value 1
+      swap32(mx[0], mx[1], x, y); const float x01 = vmax(x, y);
+      swap32(mn[2], mn[3], x, y); const float n23 = vmin(x, y);
+      swap32(mx[2], mx[3], x, y); const float x23 = vmax(x, y);
+      swap16(n01, n23, x, y); float n = vmin(x, y); // rows of 16 lanes: values 0, 2, 1, 3
+      swap16(x01, x23, x, y); float m = vmax(x, y);
       asm volatile(
           "s_nop 1\n\t"
           "v_min_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
@@ -340,8 +340,6 @@ namespace limg_hip
 
     __device__ __forceinline__ float vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
     __device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-    __device__ __forceinline__ float vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-    __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
     // ---- 4-channel float vectors in "DPPS order" -----------------------------------------------------------------------------
     // A pixel-space vector lives in two register pairs a = (x0, x2), b = (x1, x3): then DPPS's (x0y0 + x1y1) + (x2y2 + x3y3)

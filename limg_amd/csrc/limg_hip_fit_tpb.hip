@@ -3,7 +3,7 @@
 // reference: limg_encode_sum_to_decomposition_state src/limg.cpp:466-497, limg_encode_get_block_factors_accurate_from_state_3d_{3,4}
 // src/limg_factorization.h:382-576 / :578-794, record rounding :764-790.
 //
-// Why a second mapping.  With lane == pixel (limg_hip_kernels.hip) every per-block quantity of the fit is a wave reduction: two channel sums, six extrema and --
+// Why a second mapping.  With lane == pixel (limg_hip_float_pixel.h) every per-block quantity of the fit is a wave reduction: two channel sums, six extrema and --
 // the expensive one, because the reference accumulates in pixel order -- three direction sums that have to be parked in LDS and walked by 16 lanes.  The float
 // stage is a chain of four passes whose per-pixel arithmetic is tiny next to that bookkeeping (~510 of the kernel's ~1060 VALU instructions per block).  With
 // lane == block the same per-pixel arithmetic is issued once per pixel for 64 blocks (identical cost per block), and every reduction disappears: a direction sum
@@ -142,7 +142,7 @@ namespace limg_hip
       avg.b = float2_t{ (float)(int)(s13 & 0xFFFF), CH == 4 ? (float)(int)(s13 >> 16) : 0.0f } * inv_count;
       const V4 zero4 = { float2_t{ 0.0f, 0.0f }, float2_t{ 0.0f, 0.0f } };
 
-      // the epilogue of a direction sum: dir = sum / N, 1 / (dir . dir) in DPPS order, all-zero test (== serial_sums2 of limg_hip_kernels.hip)
+      // the epilogue of a direction sum: dir = sum / N, 1 / (dir . dir) in DPPS order, all-zero test (== serial_sums2 of limg_hip_float_pixel.h)
       auto finish_dir = [&](const V4 &acc, V4 &dir, float &inv, bool &zero)
       {
         dir = acc * inv_count;
@@ -342,19 +342,8 @@ namespace limg_hip
   void launch_fit_tpb(const EncodeParams &p, int channels, hipStream_t s)
   {
     const uint32_t units = ((p.blocksX + 63u) / 64u) * p.blocksY * p.batchCount;
-    const int v = (channels == 4 ? 4 : 0) | (p.floatFast ? 2 : 0) | (p.vecIn ? 1 : 0);
-#define LIMG_TPB_LAUNCH(CH, FAST, DIRECT) hipLaunchKernelGGL((k_fit_tpb<CH, FAST, DIRECT>), dim3((units + tpb_waves<DIRECT>() - 1) / tpb_waves<DIRECT>()), dim3(64 * tpb_waves<DIRECT>()), 0, s, p)
-    switch (v)
-    {
-    case 0: LIMG_TPB_LAUNCH(3, false, false); break;
-    case 1: LIMG_TPB_LAUNCH(3, false, true); break;
-    case 2: LIMG_TPB_LAUNCH(3, true, false); break;
-    case 3: LIMG_TPB_LAUNCH(3, true, true); break;
-    case 4: LIMG_TPB_LAUNCH(4, false, false); break;
-    case 5: LIMG_TPB_LAUNCH(4, false, true); break;
-    case 6: LIMG_TPB_LAUNCH(4, true, false); break;
-    default: LIMG_TPB_LAUNCH(4, true, true); break;
-    }
-#undef LIMG_TPB_LAUNCH
+    with_flags([&](auto rgba, auto FAST, auto DIRECT)
+               { hipLaunchKernelGGL((k_fit_tpb<rgba ? 4 : 3, FAST, DIRECT>), dim3((units + tpb_waves<DIRECT>() - 1) / tpb_waves<DIRECT>()), dim3(64 * tpb_waves<DIRECT>()), 0, s, p); },
+               channels == 4, p.floatFast != 0, p.vecIn != 0);
   }
 }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <functional>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/limg_hip.h"
@@ -14,6 +15,9 @@ namespace limg_hip
 {
   constexpr int kBlock = 8;        // limg_MinBlockSize (reference: src/limg_internal.h:158)
   constexpr int kStripBlocks = 32; // image blocks per workgroup ("work strip": 256 x 8 px)
+  constexpr int kThreads = 256;     // threads of a work strip's workgroup (limg_hip_kernels.hip)
+  constexpr int kWaves = 4;
+  constexpr int kBlocksPerWave = 8; // kStripBlocks / kWaves: a wave's blocks in the E step's float stage and the F step
   constexpr uint64_t kDitherSeed = 0xCA7F00D15BADF00DULL; // reference: src/limg.cpp:1893
 
   // The caller's pointers of one image: input pixels and the 11 output planes.  A batched encode (limg_hip_encode3d_batch_device) holds one of these per image
@@ -115,6 +119,15 @@ namespace limg_hip
   void launch_noise_expand(uint8_t *noise, const unsigned long long *dStates, const uint8_t *dPixels, size_t calls, bool pcg, hipStream_t s);
   void launch_noise_expand_calls(uint8_t *noise, const unsigned long long *dStates, const unsigned long long *dOffsets, const uint32_t *dPixels, size_t calls, bool pcg, hipStream_t s);
   void launch_set_batch_table(ImageIO *dTable, const ImageIO *hTable, size_t count, hipStream_t s);
+  // f(std::bool_constant<flag>()...): run-time flags as the template arguments of a kernel, so that a launcher names its kernel once and every combination of
+  // the flags is instantiated
+  template <class F> void with_flags(F &&f) { f(); }
+  template <class F, class... Flags> void with_flags(F &&f, bool flag, Flags... rest)
+  {
+    if (!flag) with_flags([&](auto... b) { f(std::false_type(), b...); }, rest...);
+    else with_flags([&](auto... b) { f(std::true_type(), b...); }, rest...);
+  }
+
   void launch_fit_tpb(const EncodeParams &p, int channels, hipStream_t s);
   void launch_fit_search(const EncodeParams &p, int channels, hipStream_t s);
   void launch_encode_persistent(const EncodeParams &p, int channels, int workgroups, hipStream_t s);

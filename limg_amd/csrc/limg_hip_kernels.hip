@@ -31,912 +31,27 @@
 //     LDS and 16 lanes (4 blocks x 4 channels) each walk one serial 64-term chain -- ~2 instructions per term for 16
 //     chains at once instead of a 64-step dependent chain per block;
 //   * correctly rounded division (hipcc default), once per batch and lane-parallel; round-to-nearest-even conversions.
-#include "limg_hip_device.h"
-#include "limg_search_table.h"
-
-#include <type_traits>
+//
+// This file holds the E step (fit_search_strip), the split path's scan, the F step (dither_store_strip), the kernels and their launchers.  The parts
+// they are built from live in headers that only this file includes, so that all of it stays one translation unit under this file's compile flags:
+//   limg_hip_search.h      the packed trial, the two search automata, the generic-path search
+//   limg_hip_phase_f.h     the F step's parts: LDS areas, preparation, plane stores, the rows / pixels phases, first dither calls
+//   limg_hip_float_pixel.h the lane == pixel float stage's per-block state and direction sums
+//   limg_hip_lookback.h    the decoupled look-back over the per-strip dither-call counts
+#include "limg_hip_search.h"
+#include "limg_hip_phase_f.h"
+#include "limg_hip_float_pixel.h"
+#include "limg_hip_lookback.h"
 
 namespace limg_hip
 {
   namespace
   {
-    constexpr int kThreads = 256;
     constexpr int kPrioE = 2; // wave priority of the persistent kernel's E step (s_setprio)
-    constexpr int kWaves = 4;
-    constexpr int kBlocksPerWave = 8;
-    constexpr int kRowDw = 264; // LDS pixel-row stride in dwords: 256 px + 8 pad => bank = (8*row + x) mod 32, conflict-free per 32-lane half
-    constexpr int kVDw = 260;   // per-block stride of the parked contributions: 64 px * 4 ch + 4 pad => the (block, channel) walkers hit 32 distinct banks
-
-    // decision automaton of the default shift search (tools/make_search_table.py); read with scalar loads
-    struct __attribute__((aligned(32))) SearchEntry { uint32_t w[8]; };
-    __constant__ SearchEntry d_search_tab[LIMG_SEARCH_STATES] = LIMG_SEARCH_TABLE_INIT;
-
-    // ---- a9, packed form ------------------------------------------------------------------------------------------------
-    // Same integers as `trial` above, arranged for gfx950's packed 16-bit VALU:
-    //  * per factor X the three RGB terms  tXc = (decX * nX[c] + (minX[c] << 8) + 128) >> 8  are kept between trials (R,G packed in one VGPR, B in another) and
-    //    only recomputed when that factor's shift changes;
-    //  * they are kept NEGATED: -floor(x / 256) == floor((255 - x) / 256), so (d * -n + (255 - m)) >> 8 is minus the term at the same cost, and factor A's
-    //    additive constant also carries the pixel (<< 8, per lane).  The three cached values of a channel then sum to  px - estimate  directly: no subtraction in
-    //    the trial;
-    //  * px - clamp(S, 0, 255) == clamp(px - S, px - 255, px), so the clamp and the difference are one max and one min against per-pixel bounds prepared once per
-    //    block;
-    //  * the R and G halves of a packed term carry a bias (A 0x3000, B 0x3000, C 0x2000, folded into the additive constants) that keeps every half a positive
-    //    16-bit number -- one plain 32-bit add3 then adds the halves independently -- and the biases sum to 0x8000: the sum is the difference in OFFSET BINARY, which
-    //    unsigned v_pk_max / v_pk_min clamp correctly against bounds biased the same way, and whose square modulo 2^16 is the square of the difference itself
-    //    ((e + 0x8000)^2 = e^2 + 0x10000 e + 2^30, |e| <= 255).  So the bias is never removed;
-    //  * the weighted squared error is one v_dot2_u32_u16, one select and one shift-add.
-    // Valid while every term stays inside (-0x2000, 0x2000): a term is (d * n + (min << 8) + 128) >> 8 with d <= 255 and n = max - min, so
-    // |term| <= |min| + |n| + 1 <= 3 L + 1 when every record value is at most L in magnitude: L = p.recordLimit = 2700 (3 * 2700 + 1 = 8101 < 8192).  Then every
-    // biased half lies in (0, 0x5100) and three of them sum to less than 65536 (no carry between the halves or out of the register).  A fit of byte pixels cannot
-    // get near it (|A| <= 765, |B| <= 1020, |C| <= 2040); phase E falls back to the generic 32-bit form otherwise.
-    typedef short short2_t __attribute__((ext_vector_type(2)));
-    typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
-    __device__ __forceinline__ constexpr int term_bias(int factor) { return factor == 2 ? 0x2000 : 0x3000; } // sum over the factors == 0x8000
-    // additive constant of factor f, channel c, for a record minimum `lo`: negated, rounding constant reflected, RG halves biased
-    __device__ __forceinline__ int term_const(int f, int c, int lo) { return 255 - ((lo << 8) + 128) + (c < 2 ? (term_bias(f) << 8) : 0); }
-
-    struct TrialState
-    {
-      // per pixel, fixed for the block
-      uint32_t fA, fB, fC;
-      uint32_t loRG, hiRG; // (R - 255 + 0x8000) | (G - 255 + 0x8000) << 16 and (R + 0x8000) | (G + 0x8000) << 16
-      int pxB, pxBlo;
-      // record view: n* = -(max - min) (wave-uniform), m* = term_const(...) (wave-uniform for B and C; factor A's also carry the pixel's channel << 8, per lane)
-      int nA[3], nB[3], nC[3];
-      int mA[3], mB[3], mC[3];
-      // cached terms and the shifts they were built for
-      uint32_t tA_RG, tB_RG, tC_RG;
-      int tA_B, tB_B, tC_B;
-      uint32_t cA, cB, cC;
-    };
-
-    __device__ __forceinline__ void make_terms(const uint32_t f, const uint32_t s, const uint32_t mul, const int n[3], const int m[3], uint32_t &tRG, int &tB)
-    {
-      const int d = (int)mul_u24_uniform(f >> (s & 31u), mul); // mul == shift_mul(s); <= 255 * 256; shift and multiplier are wave-uniform in the packed trial
-      const int t0 = mad_i24(d, n[0], m[0]), t1 = mad_i24(d, n[1], m[1]), t2 = mad_i24(d, n[2], m[2]);
-      tRG = __builtin_amdgcn_perm((uint32_t)t1, (uint32_t)t0, 0x06050201u); // ((t1 >> 8) & 0xFFFF) << 16 | ((t0 >> 8) & 0xFFFF)
-      tB = t2 >> 8;
-    }
-
-    // the three factors' cached terms, each rebuilt on demand (shift 8: f >> 8 == 0 => term == minA, as upstream; for B and C upstream zeroes min too,
-    // src/limg_bit_crush_simd.h:593-609)
-    __device__ __forceinline__ void rebuild_A(TrialState &t, const uint32_t sA, const uint32_t mul) { make_terms(t.fA, sA, mul, t.nA, t.mA, t.tA_RG, t.tA_B); t.cA = sA; }
-    __device__ __forceinline__ void rebuild_B(TrialState &t, const uint32_t sB, const uint32_t mul)
-    {
-      if (sB > 7) { t.tB_RG = (uint32_t)term_bias(1) * 0x10001u; t.tB_B = 0; }
-      else make_terms(t.fB, sB, mul, t.nB, t.mB, t.tB_RG, t.tB_B);
-      t.cB = sB;
-    }
-    __device__ __forceinline__ void rebuild_C(TrialState &t, const uint32_t sC, const uint32_t mul)
-    {
-      if (sC > 7) { t.tC_RG = (uint32_t)term_bias(2) * 0x10001u; t.tC_B = 0; }
-      else make_terms(t.fC, sC, mul, t.nC, t.mC, t.tC_RG, t.tC_B);
-      t.cC = sC;
-    }
-
-    // the trial proper on the cached terms: clamp, differences, weighted squared error per pixel
-    template <bool FULL>
-    __device__ __forceinline__ uint32_t trial_pixel_error(const TrialState &t, const bool active)
-    {
-      const uint32_t dRG = t.tA_RG + t.tB_RG + t.tC_RG; // (R - estimate + 0x8000) | (G - estimate + 0x8000) << 16: no carry crosses the halves
-      const int dBraw = t.tA_B + t.tB_B + t.tC_B;        // B - estimate
-      ushort2_t eu = __builtin_bit_cast(ushort2_t, dRG);
-      eu = __builtin_elementwise_max(eu, __builtin_bit_cast(ushort2_t, t.loRG));
-      eu = __builtin_elementwise_min(eu, __builtin_bit_cast(ushort2_t, t.hiRG));
-      int dB = med3_i32(dBraw, t.pxBlo, t.pxB); // clamp(px - S, px - 255, px)
-      const ushort2_t sq = eu * eu; // (d + 0x8000)^2 mod 2^16 == d^2 <= 65025
-      const uint32_t sqB = (uint32_t)mul_i24(dB, dB);
-      // weights (R, G, B) = (2, 4, 3) while dR^2 < 0x4000, else (3, 4, 2)  ==  2 * (dR^2 + 2 dG^2 + dB^2) + (dB^2 or dR^2): one dot product with constant weights,
-      // one select (the red square is picked out of the packed pair by the select's operand modifier), one shift-add
-      const bool low_red = sq.x < 0x4000;
-      const uint32_t half = __builtin_amdgcn_udot2(sq, __builtin_bit_cast(ushort2_t, 0x00020001u), sqB, false);
-      const uint32_t extra = low_red ? sqB : (__builtin_bit_cast(uint32_t, sq) & 0xFFFFu);
-      uint32_t err = (half << 1) + extra;
-      if (!FULL) err = active ? err : 0u;
-      return err;
-    }
-
-    // a10 + a11 as a table-driven automaton: one trial loop; the outcome of a trial picks the byte offset of the next state's 32-byte entry, which one scalar load
-    // fetches.  The scalar side of the loop is kept minimal -- the scalar unit (one per CU) is a co-bottleneck of this kernel: 8 extra scalar instructions per
-    // trial cost 10 % (measured) -- so an entry says WHICH factors its triple changes against its predecessor's (the automaton is a tree: no compares against
-    // cached shifts), holds byte offsets (no shifts) and the re-expansion multipliers, and the table's base address stays in SGPRs.  The load is NOT issued
-    // ahead for both outcomes: the other waves of the SIMD cover its latency, and the two address computations, the second load and the selects between two
-    // prefetched entries were scalar instructions too (measured equal, with less code).
-    typedef unsigned int uint8s_t __attribute__((ext_vector_type(8)));
-    __device__ __forceinline__ uint8s_t sload8(const SearchEntry *base, uint32_t byteOffset)
-    {
-      uint8s_t v;
-      asm volatile("s_load_dwordx8 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(base), "s"(byteOffset) : "memory");
-      return v;
-    }
-
-    template <bool FULL>
-    __device__ __forceinline__ void search_fast_automaton(TrialState &t, const bool active, const uint32_t maxPixel32, const uint32_t blockLimit, uint32_t shift[3])
-    {
-      const SearchEntry *tab = d_search_tab;
-      asm volatile("" : "+s"(tab)); // opaque: otherwise the address is rematerialised (s_getpc + 2 adds) in every iteration
-      // entry 0 as immediates (the opaque base above would make reading it a memory round trip per block)
-      // its three factors are built here, unconditionally and with immediate operands (the loop then starts with nothing to rebuild): the cached terms need no
-      // initial value at all
-      constexpr uint32_t root[8] = LIMG_SEARCH_ROOT;
-      rebuild_A(t, root[0] & 31u, root[5]);
-      rebuild_B(t, root[3], root[6]);
-      rebuild_C(t, root[4], root[7]);
-      uint8s_t e = { root[0] & ~0xE0u, root[1], root[2], root[3], root[4], root[5], root[6], root[7] };
-      while (!(e[0] >> 31))
-      { // every field sits in an SGPR of its own: no extraction.  (e[0] & 31 is the shift amount as v_lshrrev_b32 reads it -- the mask costs nothing)
-        if (e[0] & 0x20u) rebuild_A(t, e[0] & 31u, e[5]);
-        if (e[0] & 0x40u) rebuild_B(t, e[3], e[6]);
-        if (e[0] & 0x80u) rebuild_C(t, e[4], e[7]);
-        const uint32_t err = trial_pixel_error<FULL>(t, active);
-        // two tails on purpose: a pixel failure (the common way to fail) needs no outcome flag, no select and no block sum
-        uint32_t off;
-        if (__builtin_amdgcn_ballot_w64(err > maxPixel32) != 0ull) off = e[2];
-        else off = (wave_sum(err) < blockLimit) ? e[1] : e[2]; // be * 16 < maxBlock * n, see phase E
-        e = sload8(tab, off);
-      }
-      shift[0] = e[0] & 31u; shift[1] = e[3]; shift[2] = e[4];
-    }
-
-    // a12 as an automaton (limg_search_table_accurate.h, a DAG of ~19 k states in global memory, expanded by the context): which trials the accurate search runs
-    // depends on pass / fail outcomes only, so its three nested scalar loops -- which, not the trials, were the cost of this mode -- become one table walk.  What
-    // the block errors decide stays here: a passing phase-1 trial becomes the result; a passing phase-2 trial only if its error is below the best so far
-    // (src/limg_bit_crush.h:774-826; `have` is always set by then).  A state has several predecessors, so the factors to rebuild come from comparing with the cached
-    // shifts (t.cA..cC).
-    template <bool FULL>
-    __device__ __forceinline__ void search_accurate_automaton(TrialState &t, const bool active, const uint32_t maxPixel32, const uint32_t blockLimit, const uint32_t *table,
-                                                              uint32_t shift[3])
-    {
-      const SearchEntry *tab = reinterpret_cast<const SearchEntry *>(table);
-      uint32_t bestA = 0, bestB = 0, bestC = 0, minBe = 0xFFFFFFFFu;
-      // Measured and NOT adopted (removed from the tree, see git history): the accurate search walks the shift cube row by row -- c innermost
-      // (src/limg_bit_crush.h:700-760) -- so factor C's shift changes with nearly every one of its ~70 trials per block while it only takes nine values; its terms for
-      // the shifts 0..7 can be built once per block and picked per trial out of a 16-register vector with the wave-uniform shift as the index (VGPR index mode:
-      // s_set_gpr_idx_on, two v_mov, s_set_gpr_idx_off; one 16-wide vector because LLVM expands a dynamic extract of up to 8 elements into compares and selects).
-      // At equal occupancy that is 2 % faster (4.39 vs 4.49 ms at 5 workgroups per CU), but its 16 registers cost the sixth workgroup per CU, which is worth 7.5 %
-      // (4.16 ms without the cache at 6).
-      { // the first triple is the fast search's
-        constexpr uint32_t root[8] = LIMG_SEARCH_ROOT;
-        rebuild_A(t, root[0] & 31u, root[5]);
-        rebuild_B(t, root[3], root[6]);
-        rebuild_C(t, root[4], root[7]);
-      }
-      uint8s_t e = sload8(tab, 0u);
-      // which factors state 0's triple changes against the root triple built above (every later edge carries its mask in bits 24..26 of the successor offset)
-      constexpr uint32_t rootT[8] = LIMG_SEARCH_ROOT;
-      uint32_t mask = ((e[0] & 31u) != (rootT[0] & 31u) ? 1u : 0u) | (e[3] != rootT[3] ? 2u : 0u) | (e[4] != rootT[4] ? 4u : 0u);
-      while (!(e[0] >> 31))
-      {
-        const uint32_t a = e[0] & 31u;
-        if (mask & 1u) rebuild_A(t, a, e[5]);
-        if (mask & 2u) rebuild_B(t, e[3], e[6]);
-        if (mask & 4u) rebuild_C(t, e[4], e[7]);
-        const uint32_t err = trial_pixel_error<FULL>(t, active);
-        uint32_t off = e[2];
-        if (__builtin_amdgcn_ballot_w64(err > maxPixel32) == 0ull)
-        {
-          const uint32_t be = wave_sum(err);
-          if (be < blockLimit) // be * 16 < maxBlock * n, see phase E
-          {
-            off = e[1];
-            if (!(e[0] & 0x20u) || be < minBe) { bestA = a; bestB = e[3]; bestC = e[4]; minBe = be; }
-          }
-        }
-        mask = off >> 24;
-        e = sload8(tab, off & 0xFFFFFFu);
-      }
-      shift[0] = bestA; shift[1] = bestB; shift[2] = bestC;
-    }
-
-    // generic-path search (see phase E): real function, rarely if ever executed
-    __device__ __attribute__((noinline)) uint32_t search_generic(uint32_t px, uint32_t fA, uint32_t fB, uint32_t fC, const int16_t *rec /* LDS */, bool active,
-                                                                 uint32_t maxPixel32, uint64_t maxBlockN, bool fast)
-    {
-      RecU r;
-#pragma unroll
-      for (int c = 0; c < 3; c++)
-      {
-        const int loA = rec[c], hiA = rec[4 + c], loB = rec[8 + c], hiB = rec[12 + c], loC = rec[16 + c], hiC = rec[20 + c];
-        r.nA[c] = sgpr(hiA - loA); r.nB[c] = sgpr(hiB - loB); r.nC[c] = sgpr(hiC - loC);
-        r.mA[c] = sgpr((int)(((uint32_t)loA << 8) + 128u)); r.mB[c] = sgpr((int)(((uint32_t)loB << 8) + 128u)); r.mC[c] = sgpr((int)(((uint32_t)loC << 8) + 128u));
-      }
-      uint32_t shift[3] = { 0, 0, 0 };
-      auto T = [&](uint32_t a, uint32_t bb, uint32_t c, uint32_t &be2) -> bool { return trial(px, fA, fB, fC, r, a, bb, c, active, maxPixel32, maxBlockN, be2); };
-      if (fast) search_fast(T, shift);
-      else search_accurate(T, shift);
-      return shift[0] | (shift[1] << 8) | (shift[2] << 16);
-    }
-
-    // =====================================================================================================================
-    // phase F / kernel 3: dither (a13), plane stores (a15), decode (a16) for one work strip
-    // =====================================================================================================================
-
-    // The strip's factor bytes in LDS (written by the E step lane == pixel, read by the F step lane == (block, row) 8 bytes at a time): [3 planes][8 rows] of
-    // 256 bytes at a row stride of 320 -- 80 dwords = 16 mod 64 banks, so the 32 lanes (4 rows x 8 blocks) that a ds_read_b64 serves at a time hit 64 distinct banks
-    // (at a stride of 256 all rows of a block share two banks).
-    constexpr int kFacRow = 320, kFacPlane = 8 * kFacRow, kFacBytes = 3 * kFacPlane;
-
-    // LDS areas of phase F.  In the fused kernel they overlay the (then dead) parked-contribution area of k_fit_search.
-    struct StripLds
-    {
-      uint8_t *fac;    // [3][8][kFacRow]  pre-dither factor bytes of the strip (plane-row layout)
-      uint32_t *dec;   // [4 waves][8 rows][64]  decoded pixels
-      uint8_t *out;    // == fac: a lane's output byte replaces the pre-dither byte it has just read (same index)
-      uint32_t *cst;   // [7][32][4]  per-block constants of the 7 block-uniform planes, each four times over: a 16-byte store takes it from one ds_read_b128
-      int32_t *nm;     // [32 blocks][2][3][4]  effective integer normals / additive constants of the decode
-      uint32_t *shift; // [32]  shift words
-      uint32_t *first; // [32]  first dither-call index of each block
-      uint32_t *flags; // [32]  bit 0: some record value beyond p.recordLimit (generic 32-bit decode), bit 1: the alpha lane varies inside the block; bits 8..15: its value when it does not
-      const int16_t *rec; // record of block sb at rec + sb * recStride
-      int recStride;
-    };
-    constexpr int kPhaseFBytes = kFacBytes + 8192 + 3584 + 3072 + 128 + 128 + 128; // the output factor bytes replace the pre-dither ones in place
-
-    __device__ __forceinline__ StripLds carve_phase_f(uint8_t *base, const int16_t *rec, int recStride)
-    {
-      StripLds L;
-      L.fac = base;
-      L.dec = reinterpret_cast<uint32_t *>(base + kFacBytes);
-      L.out = base;
-      L.cst = reinterpret_cast<uint32_t *>(base + kFacBytes + 8192);
-      L.nm = reinterpret_cast<int32_t *>(base + kFacBytes + 8192 + 3584);
-      L.shift = reinterpret_cast<uint32_t *>(base + kFacBytes + 8192 + 3584 + 3072);
-      L.first = L.shift + 32;
-      L.flags = L.shift + 64;
-      L.rec = rec; L.recStride = recStride;
-      return L;
-    }
-
-    // Per-wave preparation from records + shifts (lane-parallel over the wave's 8 blocks): the 7 block-uniform plane values
-    // (src/limg.cpp:2006-2036) and the effective decode constants (src/limg_decode.h:139-196 / :40-101).
-    // The decode's additive constants of the R and G lanes carry the packed form's biases (term_bias: 0x3000, 0x3000, 0x2000 -- they sum to 0x8000): see phase_f_rows.
-    __device__ __forceinline__ constexpr int decode_bias(int factor, int c) { return c < 2 ? (term_bias(factor) << 8) : 0; }
-
-    template <int CH>
-    __device__ __forceinline__ void phase_f_prepare(const StripLds &L, int lane, int wave, int recordLimit)
-    {
-      if (lane < 56)
-      {
-        const int b = lane / 7, k = lane - b * 7, sb = wave * kBlocksPerWave + b;
-        const int16_t *rec = L.rec + sb * L.recStride;
-        uint32_t v;
-        if (k == 0)
-        {
-          const uint32_t w = L.shift[sb];
-          const uint32_t pat[3] = { (w & 0xFF), ((w >> 8) & 0xFF), ((w >> 16) & 0xFF) };
-          // bit_to_pattern {0,0x22,...,0xEE,0xFF}: 0x22 * s, except s == 8 -> 0xFF
-          const uint32_t pa = pat[0] == 8 ? 0xFFu : pat[0] * 0x22u, pb = pat[1] == 8 ? 0xFFu : pat[1] * 0x22u, pc = pat[2] == 8 ? 0xFFu : pat[2] * 0x22u;
-          v = 0xFF000000u | (pa << 16) | (pb << 8) | pc;
-        }
-        else
-        {
-          v = 0;
-#pragma unroll
-          for (int c = 0; c < CH; c++)
-          {
-            int q = rec[(k - 1) * 4 + c] + (k >= 3 ? 0x80 : 0);
-            q = q < 0 ? 0 : (q > 255 ? 255 : q);
-            v |= (uint32_t)q << (8 * c);
-          }
-          if (CH == 3) v |= 0xFF000000u;
-        }
-        reinterpret_cast<uint4 *>(L.cst)[k * kStripBlocks + sb] = make_uint4(v, v, v, v);
-      }
-      if (lane < kBlocksPerWave)
-      { // per-block flags of the decode: whether the alpha lane is one value for the block (and which); bit 0 -- a record value beyond the packed form's range, never
-        // from a fit of byte pixels -- is OR-ed in below by whichever lane meets such a value
-        const int sb = wave * kBlocksPerWave + lane;
-        const int16_t *rec = L.rec + sb * L.recStride;
-        uint32_t fl;
-        if (CH == 3) fl = 255u << 8; // src/limg_decode.h:95-97: the three 0xFFFF minima clamp to 255
-        else
-        {
-          const bool varies = rec[7] != rec[3] || rec[15] != rec[11] || rec[23] != rec[19]; // an alpha normal (max - min) is never zeroed, not even at shift 8
-          int a = rec[3] + rec[11] + rec[19]; // ((m << 8) + 128) >> 8 == m for each of the three terms
-          a = a < 0 ? 0 : (a > 255 ? 255 : a);
-          fl = varies ? 2u : ((uint32_t)a << 8);
-        }
-        L.flags[sb] = fl;
-      }
-      wave_lds_fence();
-#pragma unroll
-      for (int r = 0; r < 2; r++)
-      {
-        const int idx = r * 64 + lane;
-        if (idx < 96)
-        {
-          const int b = idx / 12, fc = idx - b * 12, f = fc >> 2, c = fc & 3, sb = wave * kBlocksPerWave + b;
-          const int16_t *rec = L.rec + sb * L.recStride;
-          const uint32_t sh = (L.shift[sb] >> (8 * f)) & 0xFF;
-          const int lo = rec[f * 8 + c], hi = rec[f * 8 + 4 + c];
-          if ((uint32_t)(lo + recordLimit) > 2u * (uint32_t)recordLimit || (uint32_t)(hi + recordLimit) > 2u * (uint32_t)recordLimit) atomicOr(&L.flags[sb], 1u); // |value| > limit
-          int n = hi - lo, m = lo;
-          if (c < 3)
-          {
-            if (sh > 7) { n = 0; if (f > 0) m = 0; }
-          }
-          else if (CH == 3) { n = 0; m = 0xFFFF; }
-          int *dst = L.nm + sb * 24;
-          dst[f * 4 + c] = n;
-          dst[12 + f * 4 + c] = (int)(((uint32_t)m << 8) + 128u + (uint32_t)(c < 2 ? (f == 2 ? 0x200000 : 0x300000) : 0)); // + decode_bias(f, c)
-        }
-      }
-    }
-
-    // the 7 block-uniform planes, straight from registers: 16 bytes per lane = four rows of 256 contiguous bytes (8 blocks x 8 px) per store instruction where
-    // the rows allow it (p.vecPlanes: width a multiple of 4, 16-byte aligned planes), 4 bytes per lane = one row per instruction otherwise
-    // The 35 bytes per pixel of output planes are written once and never read by this library: stored NON-TEMPORALLY (global_store ... nt) they do not push the
-    // data the kernels DO come back to out of the L2 -- a strip's parked results (8 KiB written by its E step, read by its F step), the records and k_fit_tpb's
-    // rows.  Against plain stores (A/B, same box: 4096^2 gradient 0.331 -> 0.285 ms, config 4 72.6 ->
-    // 74.9 Gpx/s, 8192^2 photo-noise 1.374 -> 1.360 ms; the HBM byte counters do not move -- the parked data still goes out and comes back -- the time does).
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-    __device__ __forceinline__ void plane_store16(void *dst, const uint4 &v)
-    {
-      __builtin_nontemporal_store(u32x4_t{ v.x, v.y, v.z, v.w }, reinterpret_cast<u32x4_t *>(dst));
-    }
-    __device__ __forceinline__ void plane_store8(void *dst, const uint2 &v)
-    {
-      __builtin_nontemporal_store(u32x2_t{ v.x, v.y }, reinterpret_cast<u32x2_t *>(dst));
-    }
-
-    template <class P, class IO>
-    // halves: bit 0 = the strip's rows 0..3, bit 1 = rows 4..7 (the F step issues them at two different points, each beside a memory round trip of its own; the
-    // one-row-per-instruction form stores everything with bit 0)
-    __device__ __forceinline__ void phase_f_store_const(const P &p, const IO &io, const StripLds &L, uint32_t x0, uint32_t y0, uint32_t ry, int lane, int wave, const uint32_t halves = 3u)
-    {
-      const uint32_t wx0 = x0 + wave * 64;
-      if (wx0 >= p.sizeX) return;
-      const uint32_t ww = min(p.sizeX - wx0, 64u);
-      uint32_t *planes[7] = { io.info.pShiftABCX, io.info.pColAMin, io.info.pColAMax, io.info.pColBMin, io.info.pColBMax, io.info.pColCMin, io.info.pColCMax };
-      if (p.vecPlanes)
-      {
-        const uint32_t col = ((uint32_t)lane & 15u) * 4u, rsub = (uint32_t)lane >> 4; // 16 lanes per row, 4 rows per instruction
-        const uint4 *cst = reinterpret_cast<const uint4 *>(L.cst) + wave * kBlocksPerWave + (col >> 3); // read per store: the LDS pipe has the room, registers do not
-        if (col < ww)
-#pragma unroll
-          for (uint32_t half = 0; half < 2; half++)
-          {
-            const uint32_t row = half * 4 + rsub;
-            if (row < ry && ((halves >> half) & 1u))
-            {
-              size_t g = (size_t)(y0 + row) * p.sizeX + wx0 + col;
-              asm volatile("" : "+v"(g)); // one offset for the seven planes (left to itself the compiler adds its three loop-invariant parts to every plane's base separately)
-#pragma unroll
-              for (int k = 0; k < 7; k++) plane_store16(planes[k] + g, cst[k * kStripBlocks]);
-            }
-          }
-        return;
-      }
-      if (!(halves & 1u)) return;
-      uint32_t cst[7];
-#pragma unroll
-      for (int k = 0; k < 7; k++) cst[k] = L.cst[(k * kStripBlocks + wave * kBlocksPerWave + (lane >> 3)) * 4];
-      if ((uint32_t)lane < ww)
-        for (uint32_t row = 0; row < ry; row++)
-        {
-          const size_t g = (size_t)(y0 + row) * p.sizeX + wx0 + lane;
-#pragma unroll
-          for (int k = 0; k < 7; k++) planes[k][g] = cst[k];
-        }
-    }
-
-    // ---- phase F for strips of whole 8x8 blocks: lane == (block j of the wave's 8, row r), 8 pixels per lane ------------------------------------------------
-    // With lane == pixel (phase_f_pixels below, which strips with partial blocks keep) everything per block is scalar work -- shift fields, dither on / off
-    // branches, multipliers: ~50 scalar instructions a block on a scalar unit the search already loads -- every plane goes through LDS staging to reach
-    // 16-byte stores, and the decode runs unpacked.  Here a lane owns one row of one block:
-    //  * its per-block values (shifts, multipliers, dither masks, decode constants) are ordinary per-lane registers: no scalar code at all;
-    //  * its 8 pixels leave as two 16-byte stores (pDecoded) and three 8-byte stores (factor planes) straight from registers; the inputs are three 8-byte
-    //    LDS reads (pre-dither factor bytes) and up to three 8-byte loads of the noise stream;
-    //  * byte lanes are addressed by SDWA operand selects: one v_add_u32_sdwa adds byte i of the factor dword and byte i of the (pre-masked) noise dword, one
-    //    v_and_b32_sdwa with dst_sel:BYTE_i inserts the crushed byte (clamped value with the dropped bits cleared == (v >> s) << s) into the output dword;
-    //  * the decode (a16, src/limg_decode.h:137-236) takes the trial's packed form: per factor three 24-bit multiply-adds, the R and G terms packed into one
-    //    register by one v_perm_b32 (both >> 8 included), biased so that a plain v_add3_u32 sums the halves independently (0x3000 + 0x3000 + 0x2000 = 0x8000: the sum is
-    //    the estimate in offset binary, clamped by unsigned packed max / min against 0x8000 / 0x80FF, and its low byte IS the clamped estimate); the alpha lane is one
-    //    value per block unless its normals are non-zero (wave-uniform test).  Valid for record values up to p.recordLimit like the trial; beyond (never from a fit
-    //    of byte pixels) the wave takes the plain 32-bit form.
-    template <int B> __device__ __forceinline__ uint32_t add_byte_sdwa(uint32_t a, uint32_t b)
-    {
-      uint32_t r;
-      if (B == 0) asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_0" : "=v"(r) : "v"(a), "v"(b));
-      else if (B == 1) asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:BYTE_1" : "=v"(r) : "v"(a), "v"(b));
-      else if (B == 2) asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:BYTE_2" : "=v"(r) : "v"(a), "v"(b));
-      else asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:BYTE_3" : "=v"(r) : "v"(a), "v"(b));
-      return r;
-    }
-    // acc.byte[B] = (a & b) & 0xFF, the other bytes of acc kept
-    template <int B> __device__ __forceinline__ void and_into_byte_sdwa(uint32_t &acc, uint32_t a, uint32_t b)
-    {
-      if (B == 0) asm("v_and_b32_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(acc) : "v"(a), "v"(b));
-      else if (B == 1) asm("v_and_b32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(acc) : "v"(a), "v"(b));
-      else if (B == 2) asm("v_and_b32_sdwa %0, %1, %2 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(acc) : "v"(a), "v"(b));
-      else asm("v_and_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(acc) : "v"(a), "v"(b));
-    }
-
-    // One factor of the lane's 8 pixels: dither, crushed output bytes (stored by the caller), and the factor's terms of the decode added to the accumulators
-    // (first factor: assigned).  accRG: R and G terms packed and biased, accB: B terms, accA: alpha terms (only when the wave has a block whose alpha varies).
-    template <int K, bool ALPHA>
-    __device__ __forceinline__ void rows_factor(const uint2 fac, const uint2 nzm, const uint32_t negHalf, const uint32_t shr, const uint32_t mul, const uint32_t keep, const int4 n,
-                                                const int4 m, uint32_t accRG[8], int accB[8], int accA[8], uint32_t &outLo, uint32_t &outHi)
-    {
-      outLo = 0; outHi = 0;
-      auto pixel = [&](auto BI, auto HI)
-      {
-        constexpr int B = decltype(BI)::value, H = decltype(HI)::value, I = H * 4 + B;
-        // src/limg.cpp:824-879 per byte: v = clamp(f + (noise & ditherSize) - ditherOffset, 0, 255) >> shift; a factor that does not dither has mask 0, offset 0, shift 0
-        const uint32_t t = (uint32_t)med3_i32((int)(add_byte_sdwa<B>(H ? fac.y : fac.x, H ? nzm.y : nzm.x) + negHalf), 0, 255);
-        and_into_byte_sdwa<B>(H ? outHi : outLo, t, keep); // (v >> s) << s: what the factor plane holds (src/limg.cpp:2054-2062; shift 8 => 0)
-        const int d = (int)mul_u24(t >> shr, mul);          // a16: dec = v * mul (the raw byte at shift 8)
-        const int t0 = mad_i24(d, n.x, m.x), t1 = mad_i24(d, n.y, m.y), t2 = mad_i24(d, n.z, m.z);
-        const uint32_t rg = __builtin_amdgcn_perm((uint32_t)t1, (uint32_t)t0, 0x06050201u);
-        if (K == 0) { accRG[I] = rg; accB[I] = t2 >> 8; }
-        else { accRG[I] += rg; accB[I] += t2 >> 8; }
-        if (ALPHA)
-        {
-          const int ta = mad_i24(d, n.w, m.w) >> 8;
-          if (K == 0) accA[I] = ta; else accA[I] += ta;
-          asm volatile("" : "+v"(accA[I]));
-        }
-        // the accumulators are materialised here: otherwise the packing of this factor's terms sinks to their next use (the next factor's adds) and every pixel's three
-        // products stay live until then
-        asm volatile("" : "+v"(accRG[I]), "+v"(accB[I]));
-      };
-      // two pixels at a time (the scheduler would otherwise run all eight pixels' multiply-adds ahead of their packing: 24 temporaries)
-      pixel(std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
-      pixel(std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
-      __builtin_amdgcn_sched_barrier(0);
-      pixel(std::integral_constant<int, 2>(), std::integral_constant<int, 0>());
-      pixel(std::integral_constant<int, 3>(), std::integral_constant<int, 0>());
-      __builtin_amdgcn_sched_barrier(0);
-      pixel(std::integral_constant<int, 0>(), std::integral_constant<int, 1>());
-      pixel(std::integral_constant<int, 1>(), std::integral_constant<int, 1>());
-      __builtin_amdgcn_sched_barrier(0);
-      pixel(std::integral_constant<int, 2>(), std::integral_constant<int, 1>());
-      pixel(std::integral_constant<int, 3>(), std::integral_constant<int, 1>());
-      __builtin_amdgcn_sched_barrier(0);
-    }
-
-    // `between`: work that does not depend on the noise bytes (the seven uniform planes' stores: 28 of the 35 output bytes per pixel), run right after the noise
-    // loads are issued -- their round trip to HBM (the table is 200 MB: no cache holds it) then runs beside those stores instead of in front of the decode
-    template <int CH, class P, class IO, class BETWEEN>
-    __device__ __forceinline__ void phase_f_rows(const P &p, const IO &io, const StripLds &L, const uint32_t strip, const uint32_t x0, const uint32_t y0, const int lane, const int wave,
-                                                 BETWEEN &&between)
-    {
-      const uint32_t j = (uint32_t)lane & 7u, r = (uint32_t)lane >> 3;
-      const uint32_t sb = (uint32_t)wave * kBlocksPerWave + j, bx = strip * kStripBlocks + sb;
-      const bool valid = bx < p.blocksX;
-      const uint32_t w = L.shift[sb], fl = L.flags[sb]; // (shift word 0 for blocks past the right edge)
-      uint32_t call = L.first[sb];
-      const size_t g = (size_t)(y0 + r) * p.sizeX + x0 + sb * kBlock; // the lane's 8 pixels in every plane
-      // the noise bytes of the lane's row for every factor that dithers: requested first, used factor by factor
-      uint2 nz[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-      {
-        const uint32_t s = (w >> (8 * k)) & 0xFFu;
-        nz[k] = make_uint2(0u, 0u);
-        if (((s - 1u) < 7u) && valid) // shifts 1..7 dither (src/limg.cpp:1951-1958)
-        {
-          nz[k] = *reinterpret_cast<const uint2 *>(p.noise + (size_t)min(call, p.noiseLast) * 64 + r * 8);
-          call++;
-        }
-      }
-      between();
-      const uint8_t *facRow = L.fac + r * kFacRow + sb * kBlock;
-      const int *nm = L.nm + sb * 24;
-      const bool generic = __builtin_amdgcn_ballot_w64((fl & 1u) != 0u) != 0ull;   // wave-uniform
-      const bool anyAlpha = CH == 4 && __builtin_amdgcn_ballot_w64((fl & 2u) != 0u) != 0ull;
-      const bool rawEscape = !p.fullPlanes && p.streamRaw; // compact stream: a factor at shift 8 keeps its raw byte (raw-escape of the container)
-      // per-lane constants of factor k from its shift s: the shift the dither applies (0 unless 1..7), minus half the dither range, the re-expansion multiplier
-      // (1 << s) + decode_bias(s) with decode_bias = {0,0,0,0,1,4,21,127,0} = byte s of a constant pair (selector 8: a zero sign fill), the bits the crushed byte keeps
-      auto consts = [&](int k, uint32_t &negHalf, uint32_t &shr, uint32_t &mul, uint32_t &keep, uint2 &fq, uint2 &nzm)
-      {
-        const uint32_t s = (w >> (8 * k)) & 0xFFu;
-        shr = (((s - 1u) < 7u) && valid) ? s : 0u;
-        negHalf = 0u - ((1u << shr) >> 1);
-        mul = (1u << s) + __builtin_amdgcn_perm(0x7F150401u, 0u, s);
-        keep = (0xFFu << s) & 0xFFu;
-        if (rawEscape && s == 8) keep = 0xFFu;
-        fq = *reinterpret_cast<const uint2 *>(facRow + k * kFacPlane);
-        const uint32_t m4 = __builtin_amdgcn_perm(0u, (1u << shr) - 1u, 0u); // noise & ditherSize for four pixels at a time: the mask's byte in all four lanes
-        nzm = make_uint2(nz[k].x & m4, nz[k].y & m4);
-      };
-      uint8_t *planes8[3] = { io.info.pFactorsA, io.info.pFactorsB, io.info.pFactorsC };
-      auto store_factor = [&](int k, uint32_t lo, uint32_t hi)
-      {
-        if (!valid) return;
-        if (p.vecFactors8) plane_store8(planes8[k] + g, make_uint2(lo, hi));
-        else
-        {
-#pragma unroll
-          for (int i = 0; i < 4; i++) { planes8[k][g + i] = (uint8_t)(lo >> (8 * i)); planes8[k][g + 4 + i] = (uint8_t)(hi >> (8 * i)); }
-        }
-      };
-      uint32_t px[8];
-      if (!generic)
-      {
-        uint32_t accRG[8], lo, hi, negHalf, shr, mul, keep;
-        int accB[8], accA[8];
-        uint2 fq, nzm;
-        // (scheduling barriers: left alone the compiler interleaves the three factors and keeps everything live at once -- 113 VGPRs, where 80 are allowed)
-#define LIMG_ROWS_FACTOR(K, ALPHA)                                                                                                                         \
-        consts(K, negHalf, shr, mul, keep, fq, nzm);                                                                                                      \
-        rows_factor<K, ALPHA>(fq, nzm, negHalf, shr, mul, keep, *reinterpret_cast<const int4 *>(nm + 4 * K), *reinterpret_cast<const int4 *>(nm + 12 + 4 * K), accRG, accB, accA, lo, hi); \
-        store_factor(K, lo, hi);                                                                                                                          \
-        __builtin_amdgcn_sched_barrier(0)
-        if (anyAlpha)
-        { // some block of this wave has a varying alpha lane (its normals are live even at shift 8)
-          LIMG_ROWS_FACTOR(0, true); LIMG_ROWS_FACTOR(1, true); LIMG_ROWS_FACTOR(2, true);
-        }
-        else
-        {
-          LIMG_ROWS_FACTOR(0, false); LIMG_ROWS_FACTOR(1, false); LIMG_ROWS_FACTOR(2, false);
-        }
-#undef LIMG_ROWS_FACTOR
-        if (!p.fullPlanes) return;
-        const uint32_t alphaConst = fl & 0xFF00u;
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-        {
-          ushort2_t e = __builtin_bit_cast(ushort2_t, accRG[i]); // estimate + 0x8000 in both halves
-          e = __builtin_elementwise_max(e, __builtin_bit_cast(ushort2_t, 0x80008000u));
-          e = __builtin_elementwise_min(e, __builtin_bit_cast(ushort2_t, 0x80FF80FFu));
-          uint32_t ba = (uint32_t)med3_i32(accB[i], 0, 255);
-          if (anyAlpha) ba |= (uint32_t)med3_i32(accA[i], 0, 255) << 8;
-          else ba |= alphaConst;
-          px[i] = __builtin_amdgcn_perm(ba, __builtin_bit_cast(uint32_t, e), 0x05040200u); // R = low byte of the low half, G = low byte of the high half, B, A
-        }
-      }
-      else
-      { // a record value beyond the packed form's range somewhere in this wave (never from a fit of byte pixels): any int16 record, 32-bit terms, the low 32 bits of
-        // the products like PMULLD (the form of phase_f_pixels).  A rolled loop, one pixel at a time, constants re-read from LDS: this path must not set the
-        // kernel's register count.
-        uint32_t outLo[3] = { 0, 0, 0 }, outHi[3] = { 0, 0, 0 };
-#pragma unroll 1
-        for (int i = 0; i < 8; i++)
-        {
-          const uint32_t bsh = 8u * ((uint32_t)i & 3u);
-          int d[3];
-#pragma unroll
-          for (int k = 0; k < 3; k++)
-          {
-            uint32_t negHalf, shr, mul, keep;
-            uint2 fq, nzm;
-            consts(k, negHalf, shr, mul, keep, fq, nzm);
-            const uint32_t fb = ((i < 4 ? fq.x : fq.y) >> bsh) & 0xFFu, nb = ((i < 4 ? nzm.x : nzm.y) >> bsh) & 0xFFu;
-            const uint32_t t = (uint32_t)med3_i32((int)(fb + nb + negHalf), 0, 255);
-            if (i < 4) outLo[k] |= (t & keep) << bsh; else outHi[k] |= (t & keep) << bsh;
-            d[k] = (int)mul_u24(t >> shr, mul);
-          }
-          uint32_t out = 0;
-#pragma unroll
-          for (int c = 0; c < 4; c++)
-          {
-            int est = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) est += mad_i24(d[k], nm[k * 4 + c], nm[12 + k * 4 + c] - decode_bias(k, c)) >> 8;
-            out |= (uint32_t)med3_i32(est, 0, 255) << (8 * c);
-          }
-          if (valid && p.fullPlanes) io.info.pDecoded[g + i] = out;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) store_factor(k, outLo[k], outHi[k]);
-        return;
-      }
-      if (!valid) return; // (strips of whole blocks: every row r < 8 exists)
-      uint32_t *dst = io.info.pDecoded + g;
-      if (p.vecDecoded)
-      {
-        plane_store16(dst, make_uint4(px[0], px[1], px[2], px[3]));
-        plane_store16(dst + 4, make_uint4(px[4], px[5], px[6], px[7]));
-      }
-      else
-      {
-#pragma unroll
-        for (int i = 0; i < 8; i++) dst[i] = px[i];
-      }
-    }
-
-    // dither + decode of the wave's 8 blocks into the per-wave staging areas, then the per-pixel planes' stores
-    template <int CH, class P, class IO>
-    __device__ __forceinline__ void phase_f_pixels(const P &p, const IO &io, const StripLds &L, uint32_t strip, uint32_t x0, uint32_t y0, uint32_t ry, int lane, int wave, int tid)
-    {
-      uint32_t *dec = L.dec + wave * 512;
-      uint8_t *out = L.out; // [3 planes][8 rows][256 px]: strip-wide rows, so that the stores below write whole 128-byte lines
-      // The noise bytes are requested for a group of kNoiseGroup blocks at a time (up to 3 independent 64-byte loads per block in flight): fetched block by
-      // block, each block would expose a full memory round trip; all 8 at once (24 registers) pushes the kernel over the 80 VGPRs that 6 workgroups per CU allow.
-      constexpr int kNoiseGroup = 4;
-#pragma unroll
-      for (int g0 = 0; g0 < kBlocksPerWave; g0 += kNoiseGroup)
-      {
-      uint32_t nz8[kNoiseGroup][3];
-#pragma unroll
-      for (int bb = 0; bb < kNoiseGroup; bb++)
-      {
-        const uint32_t sb = wave * kBlocksPerWave + g0 + bb;
-        const uint32_t w = (uint32_t)sgpr((int)L.shift[sb]);
-        uint32_t call = (uint32_t)sgpr((int)L.first[sb]);
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-        {
-          const uint32_t s = (w >> (8 * k)) & 0xFF;
-          nz8[bb][k] = 0;
-          if (s != 0 && s != 8)
-          {
-            nz8[bb][k] = p.noise[(size_t)min(call, p.noiseLast) * 64 + lane];
-            call++;
-          }
-        }
-      }
-#pragma unroll
-      for (int bb = 0; bb < kNoiseGroup; bb++)
-      {
-        const int b = g0 + bb;
-        const uint32_t sb = wave * kBlocksPerWave + b;
-        const uint32_t bx = strip * kStripBlocks + sb;
-        if (bx >= p.blocksX) continue;
-        const uint32_t rx = min(p.sizeX - bx * kBlock, (uint32_t)kBlock), n = rx * ry;
-        const bool active = (uint32_t)lane < n;
-        uint32_t lx, ly;
-        if (rx == 8) { lx = lane & 7; ly = lane >> 3; }
-        else { const uint32_t l = active ? (uint32_t)lane : 0u; ly = l / rx; lx = l - ly * rx; }
-        const uint32_t o = ly * kFacRow + sb * kBlock + lx;
-        const uint32_t w = (uint32_t)sgpr((int)L.shift[sb]);
-        const uint32_t shift[3] = { w & 0xFF, (w >> 8) & 0xFF, (w >> 16) & 0xFF };
-
-        uint32_t f[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-        {
-          uint32_t v = L.fac[k * kFacPlane + o];
-          const uint32_t s = shift[k];
-          if (s != 0 && s != 8)
-          { // src/limg.cpp:824-879: (lane16 & ditherSize) - ditherOffset, add, clamp, shift
-            int t = (int)v + ((int)(nz8[bb][k] & ((1u << s) - 1u)) - (int)(1u << (s - 1)));
-            t = t < 0 ? 0 : (t > 255 ? 255 : t);
-            v = (uint32_t)t >> s;
-          }
-          f[k] = v;
-        }
-
-        if (!p.fullPlanes)
-        { // compact mode: only the crushed factor bytes are wanted
-          if (active)
-          {
-#pragma unroll
-            for (int k = 0; k < 3; k++) out[k * kFacPlane + o] = (uint8_t)(f[k] << ((p.streamRaw && shift[k] == 8) ? 0u : shift[k]));
-          }
-          continue;
-        }
-        // decode: dec_k = byte * mul_k, est_c = sum_k (dec_k * n_k[c] + m_k[c]) >> 8, clamp.  24-bit multiplies are exact here:
-        // dec <= 255 * 256 and |n| <= 65535 (difference of two int16), and v_mad_i32_i24 keeps the low 32 bits like PMULLD.
-        const int *nm = L.nm + sb * 24;
-        uint32_t decoded = 0;
-        const int dA = (int)(f[0] * shift_mul(shift[0])), dB = (int)(f[1] * shift_mul(shift[1])), dC = (int)(f[2] * shift_mul(shift[2]));
-        const int4 nA = *reinterpret_cast<const int4 *>(nm), nB = *reinterpret_cast<const int4 *>(nm + 4), nC = *reinterpret_cast<const int4 *>(nm + 8);
-        const int4 mA = *reinterpret_cast<const int4 *>(nm + 12), mB = *reinterpret_cast<const int4 *>(nm + 16), mC = *reinterpret_cast<const int4 *>(nm + 20);
-        const int nAa[4] = { nA.x, nA.y, nA.z, nA.w }, nBa[4] = { nB.x, nB.y, nB.z, nB.w }, nCa[4] = { nC.x, nC.y, nC.z, nC.w };
-        const int mAa[4] = { mA.x - decode_bias(0, 0), mA.y - decode_bias(0, 1), mA.z, mA.w }, mBa[4] = { mB.x - decode_bias(1, 0), mB.y - decode_bias(1, 1), mB.z, mB.w },
-                  mCa[4] = { mC.x - decode_bias(2, 0), mC.y - decode_bias(2, 1), mC.z, mC.w }; // (this form is exact for any record: no bias)
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-        {
-          int est = (mad_i24(dA, nAa[c], mAa[c]) >> 8) + (mad_i24(dB, nBa[c], mBa[c]) >> 8) + (mad_i24(dC, nCa[c], mCa[c]) >> 8);
-          est = est < 0 ? 0 : (est > 255 ? 255 : est);
-          decoded |= (uint32_t)est << (8 * c);
-        }
-        if (active)
-        {
-          const uint32_t wo = ly * 64 + b * kBlock + lx;
-          dec[wo] = decoded;
-#pragma unroll
-          for (int k = 0; k < 3; k++) out[k * kFacPlane + o] = (uint8_t)(f[k] << shift[k]); // shift 8 => 0 (src/limg.cpp:2054-2062)
-        }
-      }
-      } // noise groups
-      wave_lds_fence();
-
-      const uint32_t wx0 = x0 + wave * 64;
-      if (wx0 < p.sizeX && p.fullPlanes)
-      {
-        const uint32_t ww = min(p.sizeX - wx0, 64u);
-        if ((uint32_t)lane < ww)
-          for (uint32_t row = 0; row < ry; row++) io.info.pDecoded[(size_t)(y0 + row) * p.sizeX + wx0 + lane] = dec[row * 64 + lane];
-      }
-      __syncthreads(); // the three factor planes are stored strip-wide: 16 bytes per lane, whole rows of 256 bytes
-      {
-        const uint32_t stripW = min(p.sizeX - x0, (uint32_t)(kStripBlocks * kBlock));
-        uint8_t *planes8[3] = { io.info.pFactorsA, io.info.pFactorsB, io.info.pFactorsC };
-        if (p.vecFactors)
-        {
-          for (int i = tid; i < 384; i += kThreads)
-          {
-            const int pl = i >> 7, row = (i & 127) >> 4, col = (i & 15) * 16;
-            if ((uint32_t)row < ry && (uint32_t)col < stripW)
-              *reinterpret_cast<uint4 *>(planes8[pl] + (size_t)(y0 + row) * p.sizeX + x0 + col) = *reinterpret_cast<const uint4 *>(out + pl * kFacPlane + row * kFacRow + col);
-          }
-        }
-        else
-        {
-          for (int i = tid; i < 3 * 2048; i += kThreads)
-          {
-            const int pl = i >> 11, row = (i & 2047) >> 8, col = i & 255;
-            if ((uint32_t)row < ry && (uint32_t)col < stripW) planes8[pl][(size_t)(y0 + row) * p.sizeX + x0 + col] = out[pl * kFacPlane + row * kFacRow + col];
-          }
-        }
-      }
-    }
-
-    // exclusive prefix of the dither-call counts of the strip's 32 blocks (wave 0), on top of the strip's base
-    __device__ __forceinline__ void phase_f_first_calls(const StripLds &L, uint32_t base, int lane)
-    {
-      const uint32_t w = lane < kStripBlocks ? L.shift[lane] : 0u;
-      const uint32_t calls = w >> 24;
-      uint32_t incl = calls;
-#pragma unroll
-      for (int off = 1; off < 32; off <<= 1)
-      {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
-        if (lane >= off) incl += up;
-      }
-      if (lane < kStripBlocks) L.first[lane] = base + incl - calls;
-    }
 
     // =====================================================================================================================
     // kernel 1: fit + factors + shift search
     // =====================================================================================================================
-
-    // Per-block state in LDS.  The first 120 bytes are the float-stage state; once the record has been produced they are
-    // dead and the same bytes carry what phase E needs (`BlkE` view).
-    struct BlkF
-    {
-      float avg[4], dirA[4], dirB[4], dirC[4], est0[4]; // 80
-      float mm[6];                                      // 104: minA maxA minB maxB minC maxC
-      float inv_count, invA, invB, invC;                // 120
-      uint32_t flags, n;                                // 128
-      int16_t rec[24];                                  // 176
-      float pad[4];                                     // 192
-    };
-    struct BlkE
-    {
-      float nrm[3][4]; // 48: float normals (max - min) of A, B, C            (slot order x0 x2 x1 x3)
-      float off[3][4]; // 96: float dirA_min, dirB_offset, dirC_offset         (slot order)
-      float invN[3];   // 108
-    };
-    static_assert(sizeof(BlkE) <= 120, "BlkE must fit the dead float-stage fields");
-    static_assert(sizeof(BlkF) == 192, "BlkF layout");
-
-    enum : int { kDirA = 0, kDirB = 1, kDirC = 2 };
-    constexpr int kBatch = 4; // blocks per wave whose pass contributions are parked at a time
-    constexpr uint32_t kBig = 16u; // some |record value| > kRecordLimit => generic 32-bit trial
-
-    // Pixel-order accumulation (as `serial_sums`) followed, lane-parallel over the wave's 8 blocks, by everything the next
-    // phase needs of the new direction: 1 / (dir . dir) with the DPPS order (correctly rounded division, once per 8 blocks)
-    // and the all-zero flag.
-    template <int CH, int WHICH, bool FAST>
-    __device__ __forceinline__ void serial_sums2(const float *V, BlkF *blk, int lane)
-    {
-      wave_lds_fence();
-      if (lane < 4 * kBatch)
-      {
-        const int b = lane >> 2, c = lane & 3;
-        const float *src = V + b * kVDw + c;
-        float s = 0.0f;
-#pragma unroll 16
-        for (int i = 0; i < 64; i++) s = s + src[i * 4];
-        const float dir = s * blk[b].inv_count;
-        float *dst = WHICH == kDirA ? blk[b].dirA : (WHICH == kDirB ? blk[b].dirB : blk[b].dirC);
-        dst[c] = dir;
-        // (p0 + p1) + (p2 + p3) inside each quad of lanes (slot order x0 x2 x1 x3: channels 0,1 sit in slots 0,2); float add is
-        // commutative, so the two xor butterflies give exactly that
-        float p = (CH == 3 && c == 3) ? 0.0f : dir * dir;
-        p = p + __int_as_float(dpp<0x4E, 0xF>(0, __float_as_int(p))); // slot ^ 2
-        p = p + __int_as_float(dpp<0xB1, 0xF>(0, __float_as_int(p))); // slot ^ 1
-        uint32_t z = (dir == 0.0f) ? 1u : 0u;
-        z &= (uint32_t)dpp<0xB1, 0xF>(0, (int)z);
-        z &= (uint32_t)dpp<0x4E, 0xF>(0, (int)z);
-        const float inv = FAST ? __builtin_amdgcn_rcpf(p) : 1.0f / p;
-        if (c == 0)
-        {
-          if (WHICH == kDirA) { blk[b].invA = inv; if (z) blk[b].flags |= kZeroA | kZeroB | kZeroC; }
-          else if (WHICH == kDirB) { blk[b].invB = inv; if (z) blk[b].flags |= kZeroB | kZeroC; }
-          else { blk[b].invC = inv; if (z) blk[b].flags |= kZeroC; }
-        }
-      }
-      wave_lds_fence();
-    }
-
-    // ---- decoupled look-back over the per-strip dither-call counts (fused path) ------------------------------------------
-    // One 8-byte descriptor per work strip: value in the low word, status in the high word (0 = nothing yet, 1 = this strip's
-    // own count, 2 = inclusive count of the chain up to and including this strip; the inclusive VALUE kBasePoison = a look-back
-    // gave up here or earlier in the chain).  Written and read with relaxed agent-scope 8-byte atomics only: value and status travel in one granule, so no other ordering is needed.
-    // Progress: EVERY strip id is drawn from the atomic ticket by a workgroup that is already running (k_encode_persistent), so
-    // the holders of all smaller ids are resident whatever else shares the GPU -- other contexts' persistent kernels included --
-    // and each of them publishes its count at the end of an E step, which never waits.  A look-back therefore terminates
-    // without any assumption about how many workgroups of the grid are resident.  (Reference: strips on a thread pool always
-    // complete and the entry points are re-entrant, src/limg.cpp:1890-1893, :2131-2136.)
-    // The spin is bounded all the same (a protocol bug must not hang the GPU).  A timeout is LOUD: the strip raises the
-    // context's sticky status word, publishes the poison value as its inclusive count and stores none of its chain-dependent planes;
-    // every later strip of the chain finds the poison at once (no second spin), hands it on and stores nothing either.  (A poison STATUS of
-    // its own, tested with one more ballot per poll, cost the 4-channel kernel two spilled VGPRs at its 80-register limit; the value does not.)  The host-pointer entries and
-    // limg_hip_check_device_status then return limg_hip_error_Generic.
-    constexpr uint32_t kDescAggregate = 1u, kDescInclusive = 2u;
-    constexpr uint32_t kBasePoison = 0xFFFFFFFFu; // (a chain has < 2^26 dither calls: 3 per block)
-
-    __device__ __forceinline__ void desc_store(unsigned long long *d, uint32_t status, uint32_t value)
-    {
-      __hip_atomic_store(d, ((unsigned long long)status << 32) | value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __device__ __forceinline__ unsigned long long desc_load(unsigned long long *d)
-    {
-      return __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-
-    // bound of one look-back wait, in polls (~seconds); fault injection (a shorter bound, a strip that never publishes) exists in the test build only
-    template <class P>
-    __device__ __forceinline__ uint32_t lookback_spin_bound(const P &p)
-    {
-#ifdef LIMG_HIP_TEST_HOOKS
-      return p.lookbackSpins;
-#else
-      (void)p;
-      return 1u << 22;
-#endif
-    }
-    template <class P>
-    __device__ __forceinline__ bool publishes(const P &p, uint32_t id)
-    {
-#ifdef LIMG_HIP_TEST_HOOKS
-      return id != p.testSkipStrip;
-#else
-      (void)p; (void)id;
-      return true;
-#endif
-    }
-
-    // called by all 64 lanes of one wave; returns the number of dither calls of the chain before strip `id`, or kBasePoison
-    template <class P>
-    __device__ __forceinline__ uint32_t lookback_base(const P &p, uint32_t id, uint32_t headId, uint32_t agg, int lane)
-    {
-      if (id == headId) return 0u;
-      uint32_t base = 0;
-      int hi = (int)id - 1; // nearest predecessor not yet accounted for
-      for (;;)
-      {
-        const int j = hi - lane; // lane 0 looks at the nearest one
-        const bool inrange = j >= (int)headId;
-        unsigned long long d = ((unsigned long long)kDescInclusive << 32); // before the chain head: inclusive 0
-        uint32_t spins = 0;
-        for (;;)
-        {
-          if (inrange) d = desc_load(p.desc + j);
-          const uint64_t incl = __builtin_amdgcn_ballot_w64((uint32_t)(d >> 32) == kDescInclusive);
-          const uint64_t none = __builtin_amdgcn_ballot_w64((uint32_t)(d >> 32) == 0u);
-          // every strip nearer than the nearest inclusive one must have published at least its own count
-          const uint64_t nearer = incl ? ((incl & (0ull - incl)) - 1ull) : ~0ull;
-          if ((none & nearer) == 0ull)
-          {
-            const uint32_t v = (uint32_t)d;
-            if (incl)
-            {
-              const int fl = __builtin_ctzll(incl);
-              const uint32_t vi = (uint32_t)__builtin_amdgcn_readlane((int)v, fl);
-              base += wave_sum(lane <= fl ? v : 0u);
-              return vi == kBasePoison ? kBasePoison : base; // (a poisoned predecessor publishes "inclusive, kBasePoison")
-            }
-            base += wave_sum(v);
-            break;
-          }
-          if (++spins > lookback_spin_bound(p))
-          {
-            if (lane == 0) atomicExch(p.timeout, 1u);
-            return kBasePoison;
-          }
-          __builtin_amdgcn_s_sleep(2);
-        }
-        hi -= 64;
-      }
-    }
 
     // LDS of an E task (fit + search of one work strip); the F task's areas overlay `V`.
     constexpr int kLdsStrip = 0, kLdsV = kLdsStrip + 8 * kRowDw * 4, kLdsVBytes = kWaves * kBatch * kVDw * 4;
@@ -1801,41 +916,26 @@ namespace limg_hip
     }
   } // namespace
 
-  // kernel variant by (channels, float mode, float stage already done by k_fit_tpb, accurate search)
-#define LIMG_DISPATCH_ACC(KERNEL, GRID, BLOCK, S, P, ACC)                                               \
-  do                                                                                                    \
-  {                                                                                                     \
-    const int v_ = (channels == 4 ? 4 : 0) | ((P).floatFast ? 2 : 0) | ((P).prefit ? 1 : 0);            \
-    switch (v_)                                                                                         \
-    {                                                                                                   \
-    case 0: hipLaunchKernelGGL((KERNEL<3, false, false, ACC>), GRID, BLOCK, 0, S, P); break;            \
-    case 1: hipLaunchKernelGGL((KERNEL<3, false, true, ACC>), GRID, BLOCK, 0, S, P); break;             \
-    case 2: hipLaunchKernelGGL((KERNEL<3, true, false, ACC>), GRID, BLOCK, 0, S, P); break;             \
-    case 3: hipLaunchKernelGGL((KERNEL<3, true, true, ACC>), GRID, BLOCK, 0, S, P); break;              \
-    case 4: hipLaunchKernelGGL((KERNEL<4, false, false, ACC>), GRID, BLOCK, 0, S, P); break;            \
-    case 5: hipLaunchKernelGGL((KERNEL<4, false, true, ACC>), GRID, BLOCK, 0, S, P); break;             \
-    case 6: hipLaunchKernelGGL((KERNEL<4, true, false, ACC>), GRID, BLOCK, 0, S, P); break;             \
-    default: hipLaunchKernelGGL((KERNEL<4, true, true, ACC>), GRID, BLOCK, 0, S, P); break;             \
-    }                                                                                                   \
-  } while (0)
-#define LIMG_DISPATCH(KERNEL, GRID, BLOCK, S, P)                                                        \
-  do                                                                                                    \
-  {                                                                                                     \
-    if ((P).fast || !(P).crushBits) LIMG_DISPATCH_ACC(KERNEL, GRID, BLOCK, S, P, false);                \
-    else LIMG_DISPATCH_ACC(KERNEL, GRID, BLOCK, S, P, true);                                            \
-  } while (0)
+  // the kernel instance for (channels, float mode, float stage already done by k_fit_tpb, accurate search): launch(CH, FAST, PREFIT, ACC), each an
+  // std::integral_constant
+  template <class Launch>
+  void with_encode_variant(const EncodeParams &p, int channels, Launch &&launch)
+  {
+    with_flags([&](auto acc, auto rgba, auto fast, auto prefit) { launch(std::integral_constant<int, rgba ? 4 : 3>(), fast, prefit, acc); }, !p.fast && p.crushBits,
+               channels == 4, p.floatFast != 0, p.prefit != 0);
+  }
 
   void launch_fit_search(const EncodeParams &p, int channels, hipStream_t s)
   {
     const dim3 grid(p.stripsX * p.blocksY), block(kThreads);
-    LIMG_DISPATCH(k_fit_search, grid, block, s, p);
+    with_encode_variant(p, channels, [&](auto CH, auto FAST, auto PREFIT, auto ACC) { hipLaunchKernelGGL((k_fit_search<CH, FAST, PREFIT, ACC>), grid, block, 0, s, p); });
   }
 
   void launch_encode_persistent(const EncodeParams &p, int channels, int workgroups, hipStream_t s)
   {
     const uint32_t strips = p.imageStrips * p.batchCount;
     const dim3 grid(strips < (uint32_t)workgroups ? strips : (uint32_t)workgroups), block(kThreads);
-    LIMG_DISPATCH(k_encode_persistent, grid, block, s, p);
+    with_encode_variant(p, channels, [&](auto CH, auto FAST, auto PREFIT, auto ACC) { hipLaunchKernelGGL((k_encode_persistent<CH, FAST, PREFIT, ACC>), grid, block, 0, s, p); });
   }
 
   namespace

@@ -28,7 +28,7 @@ namespace limg_hip
     constexpr int kTile = 256;
     constexpr int kEntry = 56;
     constexpr int kGroupBytes = 8 * 192; // payload of 8 blocks, worst case
-    constexpr int kPackedLimit = 2700;   // |record value| up to which the packed decode's 16-bit terms are exact (limg_hip_kernels.hip "a9, packed form": 3 * 2700 + 1 < 0x2000)
+    constexpr int kPackedLimit = 2700;   // |record value| up to which the packed decode's 16-bit terms are exact (limg_hip_search.h "a9, packed form": 3 * 2700 + 1 < 0x2000)
     typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
 
     __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
@@ -509,7 +509,7 @@ namespace limg_hip
     // known, ahead of the (long) constant preparation.  Units go to waves with a fixed stride: there is no dependence between units, so no ticket is needed.
     // The re-expansion multiplier is folded into the normals (value * (mul * n) == (value * mul) * n exactly: 8 + 21 bits for records the packed form accepts);
     // blocks with larger records (never from a fit of byte pixels) keep both apart and take the generic loop.
-    // a16 for the 8 pixels of one block row in the packed form of the F step (limg_hip_kernels.hip phase_f_rows), factor by factor: per factor and pixel one v_bfe_u32 and
+    // a16 for the 8 pixels of one block row in the packed form of the F step (limg_hip_phase_f.h phase_f_rows), factor by factor: per factor and pixel one v_bfe_u32 and
     // three 24-bit multiply-adds (the re-expansion multiplier sits in the normals).  The terms never live as 32-bit values: one v_perm_b32 packs a pixel's R and G terms
     // (>> 8 included) into the halves of a register, another the B terms of a PAIR of pixels; the additive constants carry biases (0x3000 + 0x3000 + 0x2000 = 0x8000
     // over the three factors) so that plain 32-bit adds sum the halves independently and the sums are the estimates in offset binary, which unsigned packed max / min
@@ -717,7 +717,7 @@ namespace limg_hip
               S.nm[lane][12 + f * 4 + c] = (int)(((uint32_t)m << 8) + 128u + (uint32_t)(c < 3 ? (f == 2 ? 0x200000 : 0x300000) : 0)); // R, G and B carry the packed form's biases
             }
           }
-          { // per-block flags of the packed decode (same rules as the F step's phase_f_prepare, limg_hip_kernels.hip)
+          { // per-block flags of the packed decode (same rules as the F step's phase_f_prepare, limg_hip_phase_f.h)
             uint32_t fl = big;
             if (channels == 3) fl |= 255u << 8;
             else

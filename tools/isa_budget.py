@@ -17,8 +17,11 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "limg_amd", "csrc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-gline-tables-only", "-S", "--cuda-device-only"]
+sys.path.insert(0, ROOT)
+from limg_amd.build import CSRC, compile_line  # noqa: E402  (the objects' own compile line)
+
+# the encode path's device code: limg_hip_kernels.hip and the headers only it includes, then the helpers it shares with the other kernel files
+ENCODE_FILES = ["limg_hip_kernels.hip", "limg_hip_search.h", "limg_hip_phase_f.h", "limg_hip_float_pixel.h", "limg_hip_lookback.h", "limg_hip_device.h"]
 
 
 def function_ranges(path):
@@ -64,9 +67,9 @@ def marker(path, text, after=0):
     raise SystemExit("marker not found: " + text)
 
 
-def assemble(src, extra=()):
+def assemble(src):
     out = tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
-    cmd = ["/opt/rocm/bin/hipcc"] + FLAGS + list(extra) + ["-o", out, os.path.join(CSRC, src)]
+    cmd = compile_line(src) + ["-gline-tables-only", "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, src)]
     subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return out
 
@@ -128,23 +131,24 @@ def budget(instrs, phases, default):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_by_workload.json"))
-    ap.add_argument("--calibration", default=os.path.join(ROOT, "profiles", "r04_isa_calibration.json"), help="measured aggregates from tools/isa_calibrate.py")
+    ap.add_argument("--calibration", default=os.path.join(ROOT, "profiles", "archive", "r04_isa_calibration.json"), help="measured aggregates from tools/isa_calibrate.py")
     ap.add_argument("--trials", type=float, default=12.1, help="trials per block of the workload (oracle statistics: 8192^2 photo-noise, errorFactor 100)")
     ap.add_argument("--rebuilds", type=float, default=19.4, help="factor rebuilds per block that are not to shift 8 (same statistics; the first triple's three included in 'trial set-up')")
     ap.add_argument("--sums", type=float, default=10.0, help="block-error sums per block (trials that no pixel fails)")
     ap.add_argument("--dithers", type=float, default=2.2, help="dithered factors per block (shifts 1..7)")
     args = ap.parse_args()
     K = os.path.join(CSRC, "limg_hip_kernels.hip")
-    D = os.path.join(CSRC, "limg_hip_device.h")
-    fk, fd = function_ranges(K), function_ranges(D)
     kf = "limg_hip_kernels.hip"
+    funcs = {}  # name -> (file, first line, last line)
+    for f in ENCODE_FILES:
+        for name, (a, b) in function_ranges(os.path.join(CSRC, f)).items():
+            funcs.setdefault(name, (f, a, b))
 
-    def fn(name, table=fk, file=kf):
-        a, b = table[name]
-        return (file, a, b)
+    def fn(name):
+        return funcs[name]
 
     # sub-ranges of fit_search_strip by markers in the source
-    e0, e1 = fk["fit_search_strip"]
+    e1 = funcs["fit_search_strip"][2]
     m_stage = marker(K, "// ---- stage: the strip's pixel rows into LDS")
     m_prefit = marker(K, "the records of the wave's 8 blocks as k_fit_tpb left them")
     m_float = marker(K, "// The float stage runs in batches of kBatch blocks per wave")
@@ -154,7 +158,7 @@ def main():
     m_shift = marker(K, "uint32_t shift[3] = { 0, 0, 0 };", after=m_a8)
     m_calls = marker(K, "// dither calls this block will make (src/limg.cpp:1951-1958)")
     m_after = marker(K, "if (lane == 0) s_calls[wave] = waveCalls;")
-    asm = assemble("limg_hip_kernels.hip", ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"])
+    asm = assemble("limg_hip_kernels.hip")
     asm_fit = assemble("limg_hip_fit_tpb.hip")
     print("# Per-phase instruction budget of the encode path (generated by tools/isa_budget.py from the assembly of the committed sources)\n")
     print("Kernel variants of the headline workload: `k_fit_tpb<4, false, true>`, `k_encode_persistent<4, false, true, false>` (RGBA, EXACT float stage, records from k_fit_tpb, default search).")
@@ -164,7 +168,7 @@ def main():
     phases = [
         ("search: trial core (a9)", [fn("trial_pixel_error")]),
         ("search: factor rebuild (make_terms)", [fn("make_terms"), fn("rebuild_A"), fn("rebuild_B"), fn("rebuild_C")]),
-        ("search: block-error sum (wave_sum)", [("limg_hip_device.h",) + fd["wave_sum"]]),
+        ("search: block-error sum (wave_sum)", [fn("wave_sum")]),
         ("search: automaton loop / entry load", [fn("search_fast_automaton"), fn("sload8")]),
         ("search: accurate automaton (other variant)", [fn("search_accurate_automaton")]),
         ("E: strip staging (pixels -> LDS)", [(kf, m_stage, m_prefit - 1)]),
