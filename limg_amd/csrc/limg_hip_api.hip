@@ -108,9 +108,8 @@ extern "C"
     for (hipEvent_t e : c->hostEvents) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->pipeEvents) (void)hipEventDestroy(e);
     if (c->comm && rccl().ok) (void)rccl().CommDestroy(c->comm);
-    if (c->workStream) (void)hipStreamDestroy(c->workStream);
+    if (c->searchStream) (void)hipStreamDestroy(c->searchStream);
     if (c->storeStream) (void)hipStreamDestroy(c->storeStream);
-    for (hipStream_t st : c->workStreams) (void)hipStreamDestroy(st);
     for (hipEvent_t e : c->workEvents) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->workTimers) (void)hipEventDestroy(e);
     if (c->copyStream) (void)hipStreamDestroy(c->copyStream);

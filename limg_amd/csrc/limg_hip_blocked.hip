@@ -72,58 +72,9 @@ namespace limg_hip
       f[2] = dot_seq<CH>(t, s.nC) * s.invC;
     }
 
-    // src/limg.cpp:1137-1268; same operations in the same order as blocked_matches_host
-    template <int CH>
-    __device__ bool m_matches(const limg_hip_block_record &a, const limg_hip_block_record &b)
-    {
-      MState sa, sb;
-      m_init<CH>(a, sa);
-      m_init<CH>(b, sb);
-      const float w[4] = { 2, 4, 3, 3 };
-      float avgDiffSq = 0, lenA[3] = { 3, 3, 3 }, lenB[3] = { 3, 3, 3 };
-#pragma unroll
-      for (int i = 0; i < CH; i++)
-      {
-        const float d = a.avg[i] - b.avg[i];
-        avgDiffSq += d * d * w[i];
-        lenA[0] += (sa.nA[i] * sa.nA[i]) * w[i]; lenB[0] += (sb.nA[i] * sb.nA[i]) * w[i];
-        lenA[1] += (sa.nB[i] * sa.nB[i]) * w[i]; lenB[1] += (sb.nB[i] * sb.nB[i]) * w[i];
-        lenA[2] += (sa.nC[i] * sa.nC[i]) * w[i]; lenB[2] += (sb.nC[i] * sb.nC[i]) * w[i];
-      }
-      const float sumA = lenA[0] + lenA[1] + lenA[2], sumB = lenB[0] + lenB[1] + lenB[2];
-      const float ratio = (sumA + 1) / (sumB + 1);
-      const float maxAvg = (float)(16 * 3 * CH), maxRange = (float)(200 * 3 * CH);
-      if (avgDiffSq < maxAvg && sumA < maxRange && sumB < maxRange) return true;
-      if (ratio > 1.375f || ratio < (1.f / 1.375f)) return false;
-      float invA[3], invB[3];
-#pragma unroll
-      for (int i = 0; i < 3; i++) { invA[i] = 1.0f / lenA[i]; invB[i] = 1.0f / lenB[i]; }
-#pragma unroll
-      for (int i = 1; i < 3; i++) { invA[i] *= 2.f; invB[i] *= 2.f; }
-      float fb[3];
-      m_factors<CH>(a.avg, b, sb, fb);
-      const float termB = fabsf(fb[0]) * invB[0] + fabsf(0.5f - fb[1]) * invB[1] + fabsf(0.5f - fb[2]) * invB[2];
-      float sum = 0;
-#pragma unroll 1
-      for (int z = 0; z < 3; z++)
-#pragma unroll 1
-        for (int y = 0; y < 3; y++)
-#pragma unroll
-          for (int x = 0; x < 3; x++)
-          {
-            const float xf = x * 0.5f, yf = y * 0.5f, zf = z * 0.5f;
-            float color[4], fa[3];
-#pragma unroll
-            for (int i = 0; i < CH; i++) color[i] = sb.nA[i] * xf + sb.nB[i] * yf + sb.nC[i] * zf;
-            m_factors<CH>(color, a, sa, fa);
-            sum += fabsf(fa[0]) * invA[0] + fabsf(0.5f - fa[1]) * invA[1] + fabsf(0.5f - fa[2]) * invA[2];
-            sum += termB;
-          }
-      return sum * (1.f / 27) < 3.0f;
-    }
-
-    // The same predicate for two candidates per lane, on float2 operands: every operation is elementwise and rounds exactly like its scalar
-    // twin (v_pk_mul_f32 / v_pk_add_f32, IEEE division per component), so both components equal m_matches bit for bit at half the VALU issue.
+    // The predicate (src/limg.cpp:1137-1268) for two candidates per lane, on float2 operands: the operations of the scalar predicate (blocked_matches_host) in the
+    // same order, each elementwise and rounded exactly like its scalar form (v_pk_mul_f32 / v_pk_add_f32, IEEE division per component), so both components
+    // equal it bit for bit at half the VALU issue.
     template <typename T>
     __device__ __forceinline__ float2_t splat2(T v) { return float2_t{ (float)v, (float)v }; }
     __device__ __forceinline__ float2_t pair2(float x, float y) { return float2_t{ x, y }; }

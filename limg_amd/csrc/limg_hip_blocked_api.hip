@@ -9,6 +9,349 @@
 
 using namespace limg_hip;
 
+namespace
+{
+  using clk = std::chrono::steady_clock;
+  double ms(clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+  bool add_elapsed(double &ms, hipEvent_t a, hipEvent_t b) { float t = 0; if (hipEventElapsedTime(&t, a, b) != hipSuccess) return false; ms += t; return true; }
+
+  constexpr size_t kInFlight = 32; // batches of the worker (below) whose fit + search kernel has been enqueued and whose chain has not been walked yet
+  constexpr uint32_t kBands = 16;  // the similarity bits are produced and copied in this many bands of block rows
+
+  // f(m) for the member pointer m of each of the 13 planes the encoder writes: every member of limg_hip_blocked_encode3d_info but pBlockError, in member order
+  template <class F> void for_each_written_plane(F &&f)
+  {
+    using I = limg_hip_blocked_encode3d_info;
+    auto each = [&](auto... m) { (f(m), ...); };
+    each(&I::pDecoded, &I::pFactorsA, &I::pFactorsB, &I::pFactorsC, &I::pBitsPerPixel, &I::pShiftABCX, &I::pColAMin, &I::pColAMax, &I::pColBMin, &I::pColBMax, &I::pColCMin,
+         &I::pColCMax, &I::pBlockIndex);
+  }
+  bool has_written_planes(const limg_hip_blocked_encode3d_info &info) { bool all = true; for_each_written_plane([&](auto m) { all = all && info.*m; }); return all; }
+
+  size_t copy_regions(const std::vector<HostRegion> &regs, limg_hip_region *pRegions, size_t capacity)
+  {
+    for (size_t i = 0; pRegions && i < regs.size() && i < capacity; i++) pRegions[i] = { regs[i].ox, regs[i].oy, regs[i].rx, regs[i].ry };
+    return regs.size();
+  }
+
+  // One merged-block encode as set_up and ensure_resources lay it out.  Fixed before the pipeline starts; while it runs, the merge writes a rectangle's desc and
+  // npx entries before it publishes the rectangle, and the worker reads them after.
+  struct BlockedJob
+  {
+    limg_hip_context *c;
+    hipStream_t s; // the caller's
+    size_t sizeX, sizeY, blocks, maxCalls;
+    uint32_t blocksX, blocksY, bandRows, nBands;
+    int channels; bool pcg; // pcg: limg_hip_options.dither_pcg
+    BlockedParams bp;
+    hipEvent_t *frontTimers; // begin of pass 1, its end = begin of the similarity kernels, their end
+    // the context's pinned staging, and per dither call its chain value, noise offset and pixel count on the host (call*) and on the device (dCall*)
+    limg_hip_block_record *hRec; unsigned long long *hBits; uint8_t *hFlags;
+    RegionDesc *desc; RegionOut *hOut; unsigned long long *noiseBase;
+    unsigned long long *callState, *callOff, *dCallState, *dCallOff;
+    uint32_t *callPx, *dCallPx;
+    uint32_t *npx; // per rectangle its pixel count
+  };
+
+  // Set-up: the shape, and every field of BlockedParams that does not point into the context's buffers.
+  limg_hip_result set_up(BlockedJob &j, limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_blocked_encode3d_info &info,
+                         uint32_t errorFactor, int fastBitCrushing, void *stream)
+  {
+    j.c = c; j.s = (hipStream_t)stream; j.sizeX = sizeX; j.sizeY = sizeY; j.channels = hasAlpha ? 4 : 3; j.pcg = c->opt.dither_pcg != 0;
+    j.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); j.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
+    j.blocks = (size_t)j.blocksX * j.blocksY; j.maxCalls = 3 * j.blocks;
+    j.bandRows = (j.blocksY + kBands - 1) / kBands; j.nBands = (j.blocksY + j.bandRows - 1) / j.bandRows;
+    const uint64_t capMax = ((uint64_t)sizeX * sizeY + 3ull * j.blocks + 3ull) & ~3ull; // every rectangle's scratch slice is rounded up to a multiple of 4
+    if (capMax > 0xFFFFFFF0ull) return limg_hip_error_InvalidParameter;
+    BlockedParams &bp = j.bp;
+    memset(&bp, 0, sizeof(bp));
+    bp.in = pIn; bp.sizeX = (uint32_t)sizeX; bp.sizeY = (uint32_t)sizeY; bp.blocksX = j.blocksX; bp.blocksY = j.blocksY; bp.channels = (uint32_t)j.channels;
+    const uint64_t maxPixel = (uint64_t)0x6 * (errorFactor / 2) * 7, maxBlock = (uint64_t)0x4 * (errorFactor / 2) * 7; // src/limg.cpp:2343-2368, same values as the 8x8 path
+    bp.maxPixel32 = maxPixel > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxPixel;
+    bp.maxBlock = maxBlock;
+    bp.crushBits = errorFactor != 0; bp.fast = fastBitCrushing != 0;
+    const bool forced = c->opt.forced_shift[0] >= 0 && c->opt.forced_shift[0] <= 8 && c->opt.forced_shift[1] >= 0 && c->opt.forced_shift[1] <= 8 &&
+                        c->opt.forced_shift[2] >= 0 && c->opt.forced_shift[2] <= 8;
+    for (int i = 0; i < 3; i++) bp.forced[i] = forced ? c->opt.forced_shift[i] : -1;
+    bp.info = info;
+    bp.scratchCap = (uint32_t)capMax;
+    // k_blocked_store's 4-pixels-per-lane form: whole blocks (every rectangle row is a multiple of 8 pixels, every scratch / noise offset a multiple of 4) and planes
+    // whose rows start 16-byte (32-bit planes) / 4-byte (byte planes) aligned
+    uintptr_t w = 0, b8 = 0;
+    for_each_written_plane([&](auto m) { (sizeof(*(info.*m)) == 4 ? w : b8) |= (uintptr_t)(info.*m); });
+    bp.vecStore = (sizeX % kBlock == 0 && sizeY % kBlock == 0 && (w & 15u) == 0 && (b8 & 3u) == 0 && TOPT(c, blocked_no_vec_store) == 0) ? 1 : 0;
+    return limg_hip_success;
+  }
+
+  limg_hip_result ensure_events(std::vector<hipEvent_t> &events, size_t n, unsigned flags)
+  { for (hipEvent_t e; events.size() < n; events.push_back(e)) HIP_TRY(hipEventCreateWithFlags(&e, flags)); return limg_hip_success; }
+  limg_hip_result ensure_stream(hipStream_t &stream) { if (!stream) HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); return limg_hip_success; }
+
+  // Resources: every buffer, stream and event of the call, before anything is enqueued -- a failure leaves no work in flight.  Buffers are sized for the worst
+  // case, so that nothing is reallocated while the pipeline runs.
+  limg_hip_result ensure_resources(BlockedJob &j)
+  {
+    limg_hip_context *c = j.c;
+    const size_t blocks = j.blocks, maxCalls = j.maxCalls, px = j.sizeX * j.sizeY, capMax = j.bp.scratchCap;
+    const bool bound = TOPT(c, blocked_no_bound) == 0;
+    limg_hip_result r = ensure_events(c->workTimers, 4 * kInFlight + 3, hipEventDefault);
+    auto need = [&r](auto &buf, size_t bytes) { if (r == limg_hip_success) r = buf.ensure(bytes); };
+    need(c->bMatch, blocks * kMatchWords * 8); need(c->bFlags, blocks); need(c->hFlags, blocks + 16); // (+ 16: the merge's scan reads 16 flags at a time)
+    if (bound) need(c->bBound, blocks * 16);
+    need(c->hRec, blocks * sizeof(limg_hip_block_record)); need(c->hBits, blocks * kMatchWords * 8);
+    if (r == limg_hip_success) r = ensure_events(c->bandEvents, 2 * kBands + 1, hipEventDisableTiming);
+    need(c->hDesc, blocks * sizeof(RegionDesc)); need(c->hOut, blocks * sizeof(RegionOut)); need(c->hNoiseBase, blocks * 8 + 8);
+    need(c->hNoise, maxCalls * 20 + 64); need(c->bCalls, maxCalls * 20 + 64); // per dither call 8 + 8 + 4 bytes
+    need(c->bRegions, blocks * sizeof(RegionDesc)); need(c->bOut, blocks * sizeof(RegionOut)); need(c->bNoiseBase, blocks * 8 + 8); need(c->bOrder, blocks * 4);
+    need(c->bNoise, 3 * px + 64); need(c->bPx, capMax * 4); need(c->bFac, capMax * 3);
+    for (hipStream_t *st : { &c->copyStream, &c->searchStream, &c->storeStream }) // (in this order: HIP maps streams to hardware queues in creation order)
+      if (r == limg_hip_success) r = ensure_stream(*st);
+    if (r == limg_hip_success) r = ensure_events(c->workEvents, kInFlight, hipEventDisableTiming);
+    if (r != limg_hip_success) return r;
+    try { c->regionPx.resize(blocks); }
+    catch (const std::bad_alloc &) { return limg_hip_error_MemoryAllocationFailure; }
+    j.npx = c->regionPx.data();
+    j.frontTimers = c->workTimers.data() + 4 * kInFlight;
+    j.hRec = (limg_hip_block_record *)c->hRec.p; j.hBits = (unsigned long long *)c->hBits.p; j.hFlags = (uint8_t *)c->hFlags.p;
+    j.desc = (RegionDesc *)c->hDesc.p; j.hOut = (RegionOut *)c->hOut.p; j.noiseBase = (unsigned long long *)c->hNoiseBase.p;
+    j.callState = (unsigned long long *)c->hNoise.p; j.callOff = j.callState + maxCalls; j.callPx = (uint32_t *)(j.callOff + maxCalls);
+    j.dCallState = (unsigned long long *)c->bCalls.p; j.dCallOff = j.dCallState + maxCalls; j.dCallPx = (uint32_t *)(j.dCallOff + maxCalls);
+    j.bp.matchBits = (unsigned long long *)c->bMatch.p; j.bp.matchFlags = (uint8_t *)c->bFlags.p;
+    if (bound) j.bp.matchBound = (float *)c->bBound.p;
+    j.bp.scratchPx = (uint32_t *)c->bPx.p; j.bp.scratchFac = (uint8_t *)c->bFac.p; j.bp.noise = (const uint8_t *)c->bNoise.p;
+    return limg_hip_success;
+  }
+
+  // Similarity bands: the bits are produced and copied band by band (block rows) so that the merge, which consumes seeds in raster order, can start after the
+  // first band: kernel launches on `s`, copies on a second stream chained by events.  Returns once the first band is on the host.
+  limg_hip_result similarity_bands(BlockedJob &j)
+  {
+    limg_hip_context *c = j.c;
+    BlockedParams &bp = j.bp;
+    const hipStream_t s = j.s, cs = c->copyStream;
+    // The records go to the host as well, but the merge reads them only for pairs outside the similarity window (a few dozen per image): their copy (64 MB for 8192^2,
+    // 1.3 ms of PCIe) is queued BEHIND the first two bands' bits, and the merge waits for it when it first needs a record -- not before it starts.
+    HIP_TRY(hipEventRecord(j.frontTimers[1], s));
+    c->lastBlocks = j.blocks;
+    launch_blocked_bounds(bp, s);
+    for (uint32_t b = 0; b < j.nBands; b++)
+    {
+      const uint32_t row0 = b * j.bandRows, rows = min(j.bandRows, j.blocksY - row0);
+      bp.seedBase = row0 * j.blocksX; bp.seedCount = rows * j.blocksX;
+      launch_blocked_match(bp, s);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(c->bandEvents[2 * b], s));
+      HIP_TRY(hipStreamWaitEvent(cs, c->bandEvents[2 * b], 0));
+      HIP_TRY(hipMemcpyAsync(j.hBits + (size_t)bp.seedBase * kMatchWords, bp.matchBits + (size_t)bp.seedBase * kMatchWords, (size_t)bp.seedCount * kMatchWords * 8,
+                             hipMemcpyDeviceToHost, cs));
+      HIP_TRY(hipMemcpyAsync(j.hFlags + bp.seedBase, bp.matchFlags + bp.seedBase, bp.seedCount, hipMemcpyDeviceToHost, cs));
+      HIP_TRY(hipEventRecord(c->bandEvents[2 * b + 1], cs));
+      if (b == 1 || (b == 0 && j.nBands == 1))
+      {
+        HIP_TRY(hipMemcpyAsync(j.hRec, c->records.p, j.blocks * sizeof(limg_hip_block_record), hipMemcpyDeviceToHost, cs)); // (`cs` has waited for a band's kernel: pass 1 is long done)
+        HIP_TRY(hipEventRecord(c->bandEvents[2 * kBands], cs)); // "records are on the host"
+      }
+    }
+    HIP_TRY(hipEventRecord(j.frontTimers[2], s)); // (`s` holds nothing but the similarity kernels between the two timers: the copies run on `cs`)
+    HIP_TRY(hipEventSynchronize(c->bandEvents[1])); // the first band's bits: the merge can start
+    return limg_hip_success;
+  }
+
+  // The rest of the call is a two-thread pipeline.  The calling thread runs the greedy raster merge (serial by construction; it only looks the similarity bits up)
+  // and publishes finished rectangles every few thousand; a worker thread takes them batch by batch, in creation order: fit + search kernel, copy of the shift
+  // words, dither chain walk for the batch (the chain is serial too, but independent of the merge), noise upload, store kernel.
+  struct Pipe { std::mutex m; std::condition_variable cv; size_t ready = 0; bool finished = false; }; // rectangles [0, ready) are published
+
+  // Producer: the merge; its progress callback lays the finished rectangles out (pixel counts, scratch slices) and hands them over.
+  struct Merge
+  {
+    BlockedJob &j;
+    Pipe &pipe;
+    uint32_t bandsReady = 0;
+    bool recordsHere = false, bandError = false, failed = false;
+    size_t laid = 0; uint64_t cap = 0; // rectangles laid out, their scratch
+    clk::time_point end;
+    void need_records() { if (!recordsHere && hipEventSynchronize(j.c->bandEvents[2 * kBands]) != hipSuccess) bandError = true; recordsHere = true; }
+    void need_seed_row(uint32_t row)
+    {
+      for (; bandsReady < j.nBands && row >= bandsReady * j.bandRows; bandsReady++)
+        if (hipEventSynchronize(j.c->bandEvents[2 * bandsReady + 1]) != hipSuccess) bandError = true;
+    }
+    void publish(size_t count)
+    {
+      for (size_t i = laid; i < count; i++)
+      {
+        const HostRegion &h = j.c->lastRegions[i];
+        size_t xpx = (size_t)h.rx * kBlock, ypx = (size_t)h.ry * kBlock;
+        if (h.ox + h.rx == j.blocksX && (j.sizeX % kBlock)) xpx = xpx - kBlock + j.sizeX % kBlock;
+        if (h.oy + h.ry == j.blocksY && (j.sizeY % kBlock)) ypx = ypx - kBlock + j.sizeY % kBlock;
+        j.npx[i] = (uint32_t)(xpx * ypx);
+        j.desc[i] = { h.ox, h.oy, h.rx, h.ry, h.keep, (uint32_t)cap, { 0, 0 } };
+        cap += ((uint64_t)j.npx[i] + 3) & ~3ull;
+      }
+      laid = count;
+      { std::lock_guard<std::mutex> lk(pipe.m); pipe.ready = count; }
+      pipe.cv.notify_one();
+    }
+    void run() noexcept
+    {
+      try
+      {
+        const std::function<void()> records = [this] { need_records(); };
+        const std::function<void(uint32_t)> seedRow = [this](uint32_t row) { need_seed_row(row); };
+        const std::function<void(size_t)> progress = [this](size_t count) { publish(count); };
+        blocked_merge(j.hRec, j.hBits, j.blocksX, j.blocksY, j.channels, j.c->lastRegions, &progress, &seedRow, j.hFlags, &records);
+      }
+      catch (...) { failed = true; } // out of host memory: the worker must still be released
+      need_seed_row(j.blocksY - 1); // every band's copy is complete before the staging buffers can be reused
+      need_records();
+      end = clk::now();
+      { std::lock_guard<std::mutex> lk(pipe.m); pipe.finished = true; }
+      pipe.cv.notify_one();
+    }
+  };
+
+  // Worker: the GPU runs AHEAD of this thread: whatever the merge has published goes to the device at once (rectangle table up, fit + search kernel, records and
+  // shift words back, one event per batch, up to kInFlight batches), and the chain -- this thread's real work, serial by construction -- is walked batch by batch
+  // in creation order as the results arrive.  (Rounds 2-3 kept one batch in flight: every batch's GPU round trip was waited for, 11-20 ms per image.)
+  // One batch = everything the merge has published when the worker looks; one stream for the fit + search kernels.  Measured on one box (profiles/archive/r04_blocked_pipeline.md):
+  // batches capped at 8 K ... 64 K rectangles, two or four streams round-robin, a high-priority stream -- all within +-2 ms of this, most of them worse: the GPU
+  // (similarity kernels 13 ms + fit / search kernels 13 ms per 8192^2 image) is as busy as the two host threads, so reordering its queue buys nothing.
+  struct Worker
+  {
+    struct Batch { size_t r0, r1, ev; }; // rectangles [r0, r1); ev: its slot of workEvents / workTimers
+    const BlockedJob &j;
+    Pipe &pipe;
+    limg_hip_context *const c = j.c;
+    Batch queue[kInFlight]; // FIFO: batches [head, tail), batch k in queue[k % kInFlight]
+    size_t head = 0, tail = 0, issued = 0; // issued: rectangles taken from the merge
+    bool fin = false;                      // ... all of them
+    uint64_t chain = kDitherSeed, noiseOff = 0; size_t callCount = 0; // the dither chain walked so far
+    double kernelMs[2] = { 0, 0 };   // HIP events, summed over the batches: fit + search, noise expansion + store
+    double busy[3] = { 0, 0, 0 };    // fit + search (incl. copies), chain walk, store launch
+    bool storeTimed[kInFlight] = {}; // slot i's store timers hold a finished-or-enqueued interval that has not been added up yet
+    limg_hip_result result = limg_hip_success;
+    static constexpr size_t kOrderFrom = 512; // batches from this many rectangles on get the device-side "large rectangles first" order (k_blocked_order)
+    // enqueue_published is called at the top of every round AND between the pieces of a batch's chain walk: a batch's walk takes milliseconds, and what the merge
+    // publishes meanwhile should be on the GPU (kernel latency: the life of its largest rectangle, 0.6-2 ms) before this thread comes looking for it -- not be
+    // enqueued when the walk is over.  A kernel's duration is the life of its largest rectangle whatever the batch's size and the batches of a stream run one after
+    // the other, so a look from inside a walk (minNew > 0) takes a batch only when it is worth a launch; a look with nothing else to do takes whatever there is.
+    // (same-box A/B of these three and of the merge's first report, tools/r04/run38.sh: photo-noise 27.5-27.7 ms against 28.8-32.0 with "any size, looks every
+    //  8192 rectangles, first report at 4096", gradient 20.3-20.4 against 19.9-21.1)
+    static constexpr size_t kWorthWithOneInFlight = 16384, kWorthFromInsideAWalk = 8192, kWalkPiece = 2048;
+    BlockedParams params_of(const Batch &b) const
+    {
+      BlockedParams q = j.bp;
+      q.regions = (const RegionDesc *)c->bRegions.p + b.r0; q.nRegions = (uint32_t)(b.r1 - b.r0); q.regionBase = (uint32_t)b.r0;
+      q.out = (RegionOut *)c->bOut.p + b.r0; q.noiseBase = (const unsigned long long *)c->bNoiseBase.p + b.r0;
+      q.order = (b.r1 - b.r0 >= kOrderFrom && TOPT(c, blocked_no_order) == 0) ? (uint32_t *)c->bOrder.p + b.r0 : nullptr; // (a small batch is one round of workgroups anyway)
+      return q;
+    }
+    // Everything the merge has published since the last look goes to the GPU as one batch.  mayWait: nothing is left to walk, so wait for the merge.
+    void enqueue_published(bool mayWait, size_t minNew)
+    {
+      if (fin || tail - head >= kInFlight) return;
+      size_t r0 = 0, r1 = 0;
+      {
+        std::unique_lock<std::mutex> lk(pipe.m);
+        if (mayWait) pipe.cv.wait(lk, [&] { return pipe.ready > issued || pipe.finished; });
+        if (pipe.ready == issued) fin = pipe.finished;
+        else if (pipe.ready - issued >= minNew || pipe.finished) { r0 = issued; r1 = issued = pipe.ready; }
+      }
+      if (r1 == r0) return;
+      const Batch nb = { r0, r1, tail % kInFlight };
+      if (storeTimed[nb.ev]) // the slot comes round again: its previous batch's store kernels were enqueued kInFlight batches ago
+        if (hipEventSynchronize(c->workTimers[4 * nb.ev + 3]) == hipSuccess) add_elapsed(kernelMs[1], c->workTimers[4 * nb.ev + 2], c->workTimers[4 * nb.ev + 3]);
+      storeTimed[nb.ev] = false;
+      if (result == limg_hip_success)
+      {
+        const size_t n = r1 - r0;
+        const BlockedParams q = params_of(nb);
+        const hipStream_t bs = c->searchStream;
+        bool ok = hipMemcpyAsync((RegionDesc *)c->bRegions.p + r0, j.desc + r0, n * sizeof(RegionDesc), hipMemcpyHostToDevice, bs) == hipSuccess;
+        ok = ok && hipEventRecord(c->workTimers[4 * nb.ev], bs) == hipSuccess;
+        if (ok) { launch_blocked_order(q, bs); launch_blocked_fit_search(q, bs); ok = hipGetLastError() == hipSuccess; }
+        ok = ok && hipEventRecord(c->workTimers[4 * nb.ev + 1], bs) == hipSuccess;
+        ok = ok && hipMemcpyAsync(j.hOut + r0, (RegionOut *)c->bOut.p + r0, n * sizeof(RegionOut), hipMemcpyDeviceToHost, bs) == hipSuccess;
+        ok = ok && hipEventRecord(c->workEvents[nb.ev], bs) == hipSuccess;
+        if (!ok) result = limg_hip_error_Generic;
+      }
+      queue[tail++ % kInFlight] = nb;
+    }
+    // The oldest batch in flight, once its shift words are back: walk its stretch of the dither chain and enqueue its noise expansion and store.  (`pending` is a
+    // copy: the walk may queue a new batch in its slot.)
+    void walk_and_store(const Batch pending, clk::time_point w0)
+    {
+      if (result != limg_hip_success) return;
+      bool ok = hipEventSynchronize(c->workEvents[pending.ev]) == hipSuccess;
+      if (ok) add_elapsed(kernelMs[0], c->workTimers[4 * pending.ev], c->workTimers[4 * pending.ev + 1]);
+      const clk::time_point w1 = clk::now();
+      // the dither chain (src/limg_internal.h:711, src/limg.cpp:1541-1551): one chain through all rectangles in creation order; a call over N
+      // pixels advances it by floor(N / 8) AES rounds + N % 8 PCG steps, so it is walked here -- for the chain VALUES only: every call's start value, pixel
+      // count and place in the noise buffer go up (20 bytes per call) and k_noise_expand_calls produces the byte every pixel adds on the device.  (Rounds
+      // 1-3 wrote the bytes here and uploaded them: 200 MB per 8192^2 image through this thread's store buffers and over PCIe.)
+      const size_t call0 = callCount;
+      // (kWalkPiece rectangles between two looks at what the merge has published: 0.1-0.6 ms of chain)
+      for (size_t w = pending.r0; ok && w < pending.r1; w += kWalkPiece)
+      {
+        const size_t n = pending.r1 - w < kWalkPiece ? pending.r1 - w : kWalkPiece;
+        chain = chain_walk_batch(chain, n, reinterpret_cast<const uint8_t *>(&j.hOut[w].shiftWord), sizeof(RegionOut), j.npx + w, j.noiseBase + w, j.callState, j.callOff,
+                                 j.callPx, noiseOff, callCount, j.maxCalls, j.pcg);
+        if (w + n < pending.r1) enqueue_published(false, kWorthFromInsideAWalk);
+      }
+      const clk::time_point w2 = clk::now();
+      const size_t nc = callCount - call0;
+      const hipStream_t ss = c->storeStream; // noise expansion + store kernels of a batch: beside the next batch's fit + search kernel, not behind it
+      ok = ok && hipStreamWaitEvent(ss, c->workEvents[pending.ev], 0) == hipSuccess; // this batch's records and shift words are in bOut
+      ok = ok && hipEventRecord(c->workTimers[4 * pending.ev + 2], ss) == hipSuccess;
+      if (ok && nc)
+      {
+        ok = hipMemcpyAsync(j.dCallState + call0, j.callState + call0, nc * 8, hipMemcpyHostToDevice, ss) == hipSuccess &&
+             hipMemcpyAsync(j.dCallOff + call0, j.callOff + call0, nc * 8, hipMemcpyHostToDevice, ss) == hipSuccess &&
+             hipMemcpyAsync(j.dCallPx + call0, j.callPx + call0, nc * 4, hipMemcpyHostToDevice, ss) == hipSuccess;
+        if (ok) { launch_noise_expand_calls((uint8_t *)c->bNoise.p, j.dCallState + call0, j.dCallOff + call0, j.dCallPx + call0, nc, j.pcg, ss); ok = hipGetLastError() == hipSuccess; }
+      }
+      ok = ok && hipMemcpyAsync((unsigned long long *)c->bNoiseBase.p + pending.r0, j.noiseBase + pending.r0, (pending.r1 - pending.r0) * 8, hipMemcpyHostToDevice, ss) == hipSuccess;
+      if (ok) { launch_blocked_store(params_of(pending), ss); ok = hipGetLastError() == hipSuccess; }
+      if (ok && hipEventRecord(c->workTimers[4 * pending.ev + 3], ss) == hipSuccess) storeTimed[pending.ev] = true;
+      const clk::time_point w3 = clk::now();
+      busy[0] += ms(w0, w1); busy[1] += ms(w1, w2); busy[2] += ms(w2, w3);
+      if (!ok) result = limg_hip_error_Generic;
+    }
+    void run() noexcept
+    {
+      if (hipSetDevice(c->device) != hipSuccess) result = limg_hip_error_Generic;
+      for (;;)
+      {
+        const clk::time_point w0 = clk::now();
+        enqueue_published(head == tail, head == tail ? 0 : kWorthWithOneInFlight); // (with a batch in flight to wait for and walk, small change accumulates meanwhile)
+        if (head < tail) walk_and_store(queue[head++ % kInFlight], w0);
+        if (fin && head == tail) break;
+      }
+      if (hipStreamSynchronize(c->searchStream) != hipSuccess && result == limg_hip_success) result = limg_hip_error_Generic;
+      if (hipStreamSynchronize(c->storeStream) != hipSuccess && result == limg_hip_success) result = limg_hip_error_Generic;
+      for (size_t i = 0; i < kInFlight; i++)
+        if (storeTimed[i]) add_elapsed(kernelMs[1], c->workTimers[4 * i + 2], c->workTimers[4 * i + 3]);
+    }
+  };
+
+  // Statistics: src/limg.cpp:1561-1590 per rectangle: (8 - shift) bits for each of its pixels, and the pixels by shift
+  void collect_stats(const BlockedJob &j)
+  {
+    limg_hip_context *c = j.c;
+    memset(c->statsHost, 0, sizeof(c->statsHost));
+    for (size_t i = 0; i < c->lastRegions.size(); i++)
+      for (int f = 0; f < 3; f++)
+      {
+        uint32_t sh = (j.hOut[i].shiftWord >> (8 * f)) & 0xFFu;
+        if (sh > 8) sh = 8;
+        c->statsHost[f] += (uint64_t)(8 - sh) * j.npx[i];
+        c->statsHost[3 + 9 * f + sh] += j.npx[i];
+      }
+    c->statsState = 2; c->statsPixels = (uint64_t)j.sizeX * j.sizeY;
+  }
+}
+
 extern "C"
 {
   int limg_hip_host_blocked_matches(int channels, const limg_hip_block_record *pSeed, const limg_hip_block_record *pCandidate)
@@ -36,9 +379,7 @@ extern "C"
       }
     }
     blocked_merge(pFits, (const unsigned long long *)pMatchBits, (uint32_t)blocksX, (uint32_t)blocksY, channels, regs, nullptr, nullptr, pMatchBits ? flags.data() : nullptr);
-    *pCount = regs.size();
-    if (pRegions)
-      for (size_t i = 0; i < regs.size() && i < capacity; i++) pRegions[i] = { regs[i].ox, regs[i].oy, regs[i].rx, regs[i].ry };
+    *pCount = copy_regions(regs, pRegions, capacity);
     return limg_hip_success;
   }
 
@@ -67,374 +408,41 @@ extern "C"
   limg_hip_result limg_hip_blocked_encode3d_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_blocked_encode3d_info *pInfo,
                                                    uint32_t errorFactor, int fastBitCrushing, void *stream)
   {
-    if (!c || !pIn || !pInfo) return limg_hip_error_ArgumentNull;
-    if (!pInfo->pDecoded || !pInfo->pFactorsA || !pInfo->pFactorsB || !pInfo->pFactorsC || !pInfo->pBitsPerPixel || !pInfo->pShiftABCX || !pInfo->pColAMin || !pInfo->pColAMax ||
-        !pInfo->pColBMin || !pInfo->pColBMax || !pInfo->pColCMin || !pInfo->pColCMax || !pInfo->pBlockIndex)
-      return limg_hip_error_ArgumentNull;
+    if (!c || !pIn || !pInfo || !has_written_planes(*pInfo)) return limg_hip_error_ArgumentNull;
     if (sizeX == 0 || sizeY == 0 || sizeX > 0x7FFFFFF8ull || sizeY > 0x7FFFFFF8ull || sizeX * sizeY > 0x60000000ull) return limg_hip_error_InvalidParameter;
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    using clk = std::chrono::steady_clock;
-    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const clk::time_point t0 = clk::now();
-    const int channels = hasAlpha ? 4 : 3;
-    const uint32_t blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock), blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
-    const size_t blocks = (size_t)blocksX * blocksY;
-    limg_hip_result r;
-
-    constexpr size_t kInFlight = 32; // batches of the worker (below) whose fit + search kernel has been enqueued and whose chain has not been walked yet
-    while (c->workTimers.size() < 4 * kInFlight + 3)
-    {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      c->workTimers.push_back(e);
-    }
-    hipEvent_t *frontTimers = c->workTimers.data() + 4 * kInFlight;
-
+    BlockedJob j; limg_hip_result r;
+    if ((r = set_up(j, c, pIn, sizeX, sizeY, hasAlpha, *pInfo, errorFactor, fastBitCrushing, stream)) != limg_hip_success) return r;
+    if ((r = ensure_resources(j)) != limg_hip_success) return r;
     // pass 1 (src/limg.cpp:1088-1119): every block's own fit = the 8x8 path's E step, records only
-    EncodeExtra x1;
-    x1.fitOnly = true;
-    HIP_TRY(hipEventRecord(frontTimers[0], s));
-    if ((r = encode_device(c, pIn, sizeX, sizeY, hasAlpha, nullptr, nullptr, errorFactor, 0, fastBitCrushing, s, x1)) != limg_hip_success) return r;
-
-    BlockedParams bp;
-    memset(&bp, 0, sizeof(bp));
-    bp.in = pIn; bp.sizeX = (uint32_t)sizeX; bp.sizeY = (uint32_t)sizeY; bp.blocksX = blocksX; bp.blocksY = blocksY; bp.channels = (uint32_t)channels;
-    const uint64_t maxPixel = (uint64_t)0x6 * (errorFactor / 2) * 7, maxBlock = (uint64_t)0x4 * (errorFactor / 2) * 7; // src/limg.cpp:2343-2368, same values as the 8x8 path
-    bp.maxPixel32 = maxPixel > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxPixel;
-    bp.maxBlock = maxBlock;
-    bp.crushBits = errorFactor != 0; bp.fast = fastBitCrushing != 0;
-    const bool forced = c->opt.forced_shift[0] >= 0 && c->opt.forced_shift[0] <= 8 && c->opt.forced_shift[1] >= 0 && c->opt.forced_shift[1] <= 8 &&
-                        c->opt.forced_shift[2] >= 0 && c->opt.forced_shift[2] <= 8;
-    for (int i = 0; i < 3; i++) bp.forced[i] = forced ? c->opt.forced_shift[i] : -1;
-    bp.pass1 = (const limg_hip_block_record *)c->records.p;
-    if ((r = c->bMatch.ensure(blocks * kMatchWords * 8)) != limg_hip_success) return r;
-    bp.matchBits = (unsigned long long *)c->bMatch.p;
-    if ((r = c->bFlags.ensure(blocks)) != limg_hip_success) return r;
-    if ((r = c->hFlags.ensure(blocks + 16)) != limg_hip_success) return r; // (+ 16: the merge's scan reads 16 flags at a time)
-    bp.matchFlags = (uint8_t *)c->bFlags.p;
-    if (TOPT(c, blocked_no_bound) == 0)
-    {
-      if ((r = c->bBound.ensure(blocks * 16)) != limg_hip_success) return r;
-      bp.matchBound = (float *)c->bBound.p;
-    }
-    uint8_t *hFlags = (uint8_t *)c->hFlags.p;
-    bp.info = *pInfo;
-    // The similarity bits are produced and copied band by band (block rows) so that the merge, which consumes seeds in raster order, can start
-    // after the first band: kernel launches on `s`, copies on a second stream chained by events.
-    if ((r = c->hRec.ensure(blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
-    if ((r = c->hBits.ensure(blocks * kMatchWords * 8)) != limg_hip_success) return r;
-    limg_hip_block_record *hRec = (limg_hip_block_record *)c->hRec.p;
-    unsigned long long *hBits = (unsigned long long *)c->hBits.p;
-    constexpr uint32_t kBands = 16;
-    const uint32_t bandRows = (blocksY + kBands - 1) / kBands, nBands = (blocksY + bandRows - 1) / bandRows;
-    if (!c->copyStream) HIP_TRY(hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
-    while (c->bandEvents.size() < 2 * kBands + 1)
-    {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      c->bandEvents.push_back(e);
-    }
-    hipStream_t cs = c->copyStream;
-    // The records go to the host as well, but the merge reads them only for pairs outside the similarity window (a few dozen per image): their copy (64 MB for 8192^2,
-    // 1.3 ms of PCIe) is queued BEHIND the first two bands' bits, and the merge waits for it when it first needs a record -- not before it starts.
-    hipEvent_t evPass1 = c->bandEvents[2 * kBands];
-    HIP_TRY(hipEventRecord(frontTimers[1], s));
-    auto copy_records = [&]() -> limg_hip_result
-    {
-      HIP_TRY(hipMemcpyAsync(hRec, c->records.p, blocks * sizeof(limg_hip_block_record), hipMemcpyDeviceToHost, cs)); // (`cs` has waited for a band's kernel: pass 1 is long done)
-      HIP_TRY(hipEventRecord(evPass1, cs)); // "records are on the host"
-      return limg_hip_success;
-    };
-    c->lastBlocks = blocks;
-    launch_blocked_bounds(bp, s);
-    for (uint32_t b = 0; b < nBands; b++)
-    {
-      const uint32_t row0 = b * bandRows, rows = min(bandRows, blocksY - row0);
-      bp.seedBase = row0 * blocksX; bp.seedCount = rows * blocksX;
-      launch_blocked_match(bp, s);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(c->bandEvents[2 * b], s));
-      HIP_TRY(hipStreamWaitEvent(cs, c->bandEvents[2 * b], 0));
-      HIP_TRY(hipMemcpyAsync(hBits + (size_t)bp.seedBase * kMatchWords, (unsigned long long *)c->bMatch.p + (size_t)bp.seedBase * kMatchWords, (size_t)bp.seedCount * kMatchWords * 8,
-                             hipMemcpyDeviceToHost, cs));
-      HIP_TRY(hipMemcpyAsync(hFlags + bp.seedBase, (uint8_t *)c->bFlags.p + bp.seedBase, bp.seedCount, hipMemcpyDeviceToHost, cs));
-      HIP_TRY(hipEventRecord(c->bandEvents[2 * b + 1], cs));
-      if (b == 1 || (b == 0 && nBands == 1))
-        if ((r = copy_records()) != limg_hip_success) return r;
-    }
-    HIP_TRY(hipEventRecord(frontTimers[2], s)); // (`s` holds nothing but the similarity kernels between the two timers: the copies run on `cs`)
-    HIP_TRY(hipEventSynchronize(c->bandEvents[1])); // the first band's bits: the merge can start
+    EncodeExtra x1; x1.fitOnly = true;
+    HIP_TRY(hipEventRecord(j.frontTimers[0], j.s));
+    if ((r = encode_device(c, pIn, sizeX, sizeY, hasAlpha, nullptr, nullptr, errorFactor, 0, fastBitCrushing, j.s, x1)) != limg_hip_success) return r;
+    j.bp.pass1 = (const limg_hip_block_record *)c->records.p;
+    if ((r = similarity_bands(j)) != limg_hip_success) { (void)hipStreamSynchronize(c->copyStream); return r; } // (no copy into the pinned staging may outlive the call)
     const clk::time_point t1 = clk::now();
-    uint32_t bandsReady = 0;
-    bool bandError = false, recordsHere = false;
-    const std::function<void()> needRecords = [&]() {
-      if (!recordsHere && hipEventSynchronize(evPass1) != hipSuccess) bandError = true;
-      recordsHere = true;
-    };
-    const std::function<void(uint32_t)> needSeedRow = [&](uint32_t row) {
-      while (bandsReady < nBands && row >= bandsReady * bandRows)
-      {
-        if (hipEventSynchronize(c->bandEvents[2 * bandsReady + 1]) != hipSuccess) bandError = true;
-        bandsReady++;
-      }
-    };
-
-    // Everything after this point is a two-thread pipeline.  This thread runs the greedy raster merge (serial by construction; it only looks the
-    // similarity bits up) and publishes finished rectangles every few thousand; a worker thread takes them batch by batch, in creation order:
-    // fit + search kernel, copy of the shift words, dither chain walk for the batch (the chain is serial too, but independent of the merge),
-    // noise upload, store kernel.  Buffers are sized for the worst case up front so that nothing is reallocated while both threads run.
-    const size_t px = sizeX * sizeY;
-    const uint64_t capMax = ((uint64_t)px + 3ull * blocks + 3ull) & ~3ull; // every rectangle's scratch slice is rounded up to a multiple of 4
-    if (capMax > 0xFFFFFFF0ull) return limg_hip_error_InvalidParameter;
-    if ((r = c->hDesc.ensure(blocks * sizeof(RegionDesc))) != limg_hip_success) return r;
-    if ((r = c->hOut.ensure(blocks * sizeof(RegionOut))) != limg_hip_success) return r;
-    if ((r = c->hNoiseBase.ensure(blocks * 8 + 8)) != limg_hip_success) return r;
-    const size_t maxCalls = 3 * blocks; // per dither call: the chain value it starts from (8 B), where its noise bytes go (8 B), its pixel count (4 B)
-    if ((r = c->hNoise.ensure(maxCalls * 20 + 64)) != limg_hip_success) return r;
-    if ((r = c->bCalls.ensure(maxCalls * 20 + 64)) != limg_hip_success) return r;
-    if ((r = c->bRegions.ensure(blocks * sizeof(RegionDesc))) != limg_hip_success) return r;
-    if ((r = c->bOut.ensure(blocks * sizeof(RegionOut))) != limg_hip_success) return r;
-    if ((r = c->bNoiseBase.ensure(blocks * 8 + 8)) != limg_hip_success) return r;
-    if ((r = c->bOrder.ensure(blocks * 4)) != limg_hip_success) return r;
-    if ((r = c->bNoise.ensure(3 * px + 64)) != limg_hip_success) return r;
-    if ((r = c->bPx.ensure(capMax * 4)) != limg_hip_success) return r;
-    if ((r = c->bFac.ensure(capMax * 3)) != limg_hip_success) return r;
-    if (!c->workStream) HIP_TRY(hipStreamCreateWithFlags(&c->workStream, hipStreamNonBlocking));
-    RegionDesc *desc = (RegionDesc *)c->hDesc.p;
-    RegionOut *hOut = (RegionOut *)c->hOut.p;
-    unsigned long long *noiseBase = (unsigned long long *)c->hNoiseBase.p;
-    unsigned long long *callState = (unsigned long long *)c->hNoise.p, *callOff = callState + maxCalls;
-    uint32_t *callPx = (uint32_t *)(callOff + maxCalls);
-    unsigned long long *dCallState = (unsigned long long *)c->bCalls.p, *dCallOff = dCallState + maxCalls;
-    uint32_t *dCallPx = (uint32_t *)(dCallOff + maxCalls);
-    std::vector<uint32_t> npx(blocks);
-    bp.scratchPx = (uint32_t *)c->bPx.p; bp.scratchFac = (uint8_t *)c->bFac.p; bp.scratchCap = (uint32_t)capMax;
-    {
-      // k_blocked_store's 4-pixels-per-lane form: whole blocks (every rectangle row is a multiple of 8 pixels, every scratch / noise offset a multiple of 4) and planes
-      // whose rows start 16-byte (32-bit planes) / 4-byte (byte planes) aligned
-      const limg_hip_blocked_encode3d_info &bi = bp.info;
-      uintptr_t w = 0, b8 = 0;
-      const void *words[] = { bi.pDecoded, bi.pShiftABCX, bi.pColAMin, bi.pColAMax, bi.pColBMin, bi.pColBMax, bi.pColCMin, bi.pColCMax, bi.pBlockIndex };
-      const void *bytes[] = { bi.pFactorsA, bi.pFactorsB, bi.pFactorsC, bi.pBitsPerPixel };
-      for (const void *q : words) w |= (uintptr_t)q;
-      for (const void *q : bytes) b8 |= (uintptr_t)q;
-      bp.vecStore = (sizeX % kBlock == 0 && sizeY % kBlock == 0 && (w & 15u) == 0 && (b8 & 3u) == 0 && TOPT(c, blocked_no_vec_store) == 0) ? 1 : 0;
-    }
-    bp.noise = (const uint8_t *)c->bNoise.p;
-
-    struct Pipe { std::mutex m; std::condition_variable cv; size_t ready = 0; bool finished = false; } pipe;
-    limg_hip_result workerResult = limg_hip_success;
-    double busy[3] = { 0, 0, 0 }; // worker: fit + search (incl. copies), chain walk, store launch
-    const bool pcg = c->opt.dither_pcg != 0;
-    // One batch = everything the merge has published when the worker looks; one stream for the fit + search kernels.  Measured on one box (profiles/archive/r04_blocked_pipeline.md):
-    // batches capped at 8 K ... 64 K rectangles, two or four streams round-robin, a high-priority stream -- all within +-2 ms of this, most of them worse: the GPU
-    // (similarity kernels 13 ms + fit / search kernels 13 ms per 8192^2 image) is as busy as the two host threads, so reordering its queue buys nothing.
-    constexpr size_t kBatchRegions = (size_t)1 << 30;
-    constexpr size_t kWorkStreams = 1;
-    while (c->workStreams.size() < kWorkStreams)
-    {
-      hipStream_t st;
-      HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      c->workStreams.push_back(st);
-    }
-    if (!c->storeStream) HIP_TRY(hipStreamCreateWithFlags(&c->storeStream, hipStreamNonBlocking));
-    hipStream_t ss = c->storeStream; // noise expansion + store kernels of a batch: beside the next batch's fit + search kernel, not behind it
-
-    while (c->workEvents.size() < kInFlight)
-    {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      c->workEvents.push_back(e);
-    }
-
-    double kernelMs[2] = { 0, 0 };
-    std::vector<uint8_t> storeTimed(kInFlight, 0); // slot i's store timers hold a finished-or-enqueued interval that has not been added up yet
-
-    std::thread worker([&]() {
-      if (hipSetDevice(c->device) != hipSuccess) { workerResult = limg_hip_error_Generic; }
-      // The GPU runs AHEAD of this thread: whatever the merge has published goes to the device at once (rectangle table up, fit + search kernel, records and
-      // shift words back, one event per batch, up to kInFlight batches), and the chain -- this thread's real work, serial by construction -- is walked batch by batch
-      // in creation order as the results arrive.  (Rounds 2-3 kept one batch in flight: every batch's GPU round trip was waited for, 11-20 ms per image.)
-      struct Batch { size_t r0 = 0, r1 = 0; size_t ev = 0; };
-      std::vector<Batch> queue; // FIFO: [head, queue.size())
-      size_t head = 0, issued = 0, evNext = 0;
-      uint64_t chain = kDitherSeed, noiseOff = 0;
-      size_t callCount = 0;
-      bool fin = false;
-      constexpr size_t kOrderFrom = 512; // batches from this many rectangles on get the device-side "large rectangles first" order (k_blocked_order)
-      auto params_of = [&](const Batch &b) {
-        BlockedParams q = bp;
-        q.regions = (const RegionDesc *)c->bRegions.p + b.r0; q.nRegions = (uint32_t)(b.r1 - b.r0); q.regionBase = (uint32_t)b.r0;
-        q.out = (RegionOut *)c->bOut.p + b.r0;
-        q.noiseBase = (const unsigned long long *)c->bNoiseBase.p + b.r0;
-        q.order = (b.r1 - b.r0 >= kOrderFrom && TOPT(c, blocked_no_order) == 0) ? (uint32_t *)c->bOrder.p + b.r0 : nullptr; // (a small batch is one round of workgroups anyway)
-        return q;
-      };
-      // Everything the merge has published since the last look goes to the GPU.  mayWait: nothing is left to walk, so wait for the merge.  Called at the top of
-      // every round AND between the pieces of a batch's chain walk: a batch's walk takes milliseconds, and what the merge publishes meanwhile should be on the GPU
-      // (kernel latency: the life of its largest rectangle, 0.6-2 ms) before this thread comes looking for it -- not be enqueued when the walk is over.
-      // A kernel's duration is the life of its largest rectangle whatever the batch's size and the batches of a stream run one after the other, so a look from
-      // inside a walk (minNew > 0) takes a batch only when it is worth a launch; a look with nothing else to do takes whatever there is.
-      // (same-box A/B of these three and of the merge's first report, tools/r04/run38.sh: photo-noise 27.5-27.7 ms against 28.8-32.0 with "any size, looks every
-      //  8192 rectangles, first report at 4096", gradient 20.3-20.4 against 19.9-21.1)
-      constexpr size_t kWorthWithOneInFlight = 16384, kWorthFromInsideAWalk = 8192, kWalkPiece = 2048;
-      auto enqueue_published = [&](bool mayWait, size_t minNew = 0)
-      {
-        if (fin || queue.size() - head >= kInFlight) return;
-        size_t r0 = 0, r1 = 0;
-        {
-          std::unique_lock<std::mutex> lk(pipe.m);
-          if (mayWait) pipe.cv.wait(lk, [&] { return pipe.ready > issued || pipe.finished; });
-          if (pipe.ready > issued && (pipe.ready - issued >= minNew || pipe.finished)) { r0 = issued; r1 = pipe.ready - issued > kBatchRegions ? issued + kBatchRegions : pipe.ready; issued = r1; }
-          else if (pipe.ready > issued) {}
-          else fin = pipe.finished;
-        }
-        if (r1 <= r0) return;
-        Batch nb; nb.r0 = r0; nb.r1 = r1; nb.ev = evNext; evNext = (evNext + 1) % kInFlight;
-        if (storeTimed[nb.ev])
-        { // the slot comes round again: its previous batch's store kernels were enqueued kInFlight batches ago
-          float t = 0;
-          if (hipEventSynchronize(c->workTimers[4 * nb.ev + 3]) == hipSuccess && hipEventElapsedTime(&t, c->workTimers[4 * nb.ev + 2], c->workTimers[4 * nb.ev + 3]) == hipSuccess) kernelMs[1] += t;
-          storeTimed[nb.ev] = 0;
-        }
-        if (workerResult == limg_hip_success)
-        {
-          const size_t n = r1 - r0;
-          const BlockedParams q = params_of(nb);
-          hipStream_t bs = c->workStreams[nb.ev % kWorkStreams];
-          bool ok = hipMemcpyAsync((RegionDesc *)c->bRegions.p + r0, desc + r0, n * sizeof(RegionDesc), hipMemcpyHostToDevice, bs) == hipSuccess;
-          ok = ok && hipEventRecord(c->workTimers[4 * nb.ev], bs) == hipSuccess;
-          if (ok) { launch_blocked_order(q, bs); launch_blocked_fit_search(q, bs); ok = hipGetLastError() == hipSuccess; }
-          ok = ok && hipEventRecord(c->workTimers[4 * nb.ev + 1], bs) == hipSuccess;
-          ok = ok && hipMemcpyAsync(hOut + r0, (RegionOut *)c->bOut.p + r0, n * sizeof(RegionOut), hipMemcpyDeviceToHost, bs) == hipSuccess;
-          ok = ok && hipEventRecord(c->workEvents[nb.ev], bs) == hipSuccess;
-          if (!ok) workerResult = limg_hip_error_Generic;
-        }
-        queue.push_back(nb);
-      };
-      for (;;)
-      {
-        const clk::time_point w0 = clk::now();
-        enqueue_published(head == queue.size(), head == queue.size() ? 0 : kWorthWithOneInFlight); // (with a batch in flight to wait for and walk, small change accumulates meanwhile)
-        // 2. the oldest batch in flight: its shift words are (about to be) back
-        if (head < queue.size())
-        {
-          const Batch pending = queue[head++];
-          if (workerResult == limg_hip_success)
-          {
-            bool ok = hipEventSynchronize(c->workEvents[pending.ev]) == hipSuccess;
-            {
-              float t = 0;
-              if (ok && hipEventElapsedTime(&t, c->workTimers[4 * pending.ev], c->workTimers[4 * pending.ev + 1]) == hipSuccess) kernelMs[0] += t;
-            }
-            const clk::time_point w1 = clk::now();
-            // the dither chain (src/limg_internal.h:711, src/limg.cpp:1541-1551): one chain through all rectangles in creation order; a call over N
-            // pixels advances it by floor(N / 8) AES rounds + N % 8 PCG steps, so it is walked here -- for the chain VALUES only: every call's start value, pixel
-            // count and place in the noise buffer go up (20 bytes per call) and k_noise_expand_calls produces the byte every pixel adds on the device.  (Rounds
-            // 1-3 wrote the bytes here and uploaded them: 200 MB per 8192^2 image through this thread's store buffers and over PCIe.)
-            const size_t call0 = callCount;
-            // (kWalkPiece rectangles between two looks at what the merge has published: 0.1-0.6 ms of chain)
-            for (size_t w = pending.r0; ok && w < pending.r1; w += kWalkPiece)
-            {
-              const size_t n = pending.r1 - w < kWalkPiece ? pending.r1 - w : kWalkPiece;
-              chain = chain_walk_batch(chain, n, reinterpret_cast<const uint8_t *>(&hOut[w].shiftWord), sizeof(RegionOut), npx.data() + w, noiseBase + w, callState, callOff, callPx,
-                                       noiseOff, callCount, maxCalls, pcg);
-              if (w + n < pending.r1) enqueue_published(false, kWorthFromInsideAWalk);
-            }
-            const clk::time_point w2 = clk::now();
-            const BlockedParams q = params_of(pending);
-            const size_t nc = callCount - call0;
-            ok = ok && hipStreamWaitEvent(ss, c->workEvents[pending.ev], 0) == hipSuccess; // this batch's records and shift words are in bOut
-            ok = ok && hipEventRecord(c->workTimers[4 * pending.ev + 2], ss) == hipSuccess;
-            if (ok && nc)
-            {
-              ok = hipMemcpyAsync(dCallState + call0, callState + call0, nc * 8, hipMemcpyHostToDevice, ss) == hipSuccess &&
-                   hipMemcpyAsync(dCallOff + call0, callOff + call0, nc * 8, hipMemcpyHostToDevice, ss) == hipSuccess &&
-                   hipMemcpyAsync(dCallPx + call0, callPx + call0, nc * 4, hipMemcpyHostToDevice, ss) == hipSuccess;
-              if (ok) { launch_noise_expand_calls((uint8_t *)c->bNoise.p, dCallState + call0, dCallOff + call0, dCallPx + call0, nc, pcg, ss); ok = hipGetLastError() == hipSuccess; }
-            }
-            ok = ok && hipMemcpyAsync((unsigned long long *)c->bNoiseBase.p + pending.r0, noiseBase + pending.r0, (pending.r1 - pending.r0) * 8, hipMemcpyHostToDevice, ss) == hipSuccess;
-            if (ok) { launch_blocked_store(q, ss); ok = hipGetLastError() == hipSuccess; }
-            if (ok && hipEventRecord(c->workTimers[4 * pending.ev + 3], ss) == hipSuccess) storeTimed[pending.ev] = 1;
-            const clk::time_point w3 = clk::now();
-            busy[0] += ms(w0, w1); busy[1] += ms(w1, w2); busy[2] += ms(w2, w3);
-            if (!ok) workerResult = limg_hip_error_Generic;
-          }
-        }
-        if (fin && head == queue.size()) break;
-      }
-      for (hipStream_t st : c->workStreams)
-        if (hipStreamSynchronize(st) != hipSuccess && workerResult == limg_hip_success) workerResult = limg_hip_error_Generic;
-      if (hipStreamSynchronize(ss) != hipSuccess && workerResult == limg_hip_success) workerResult = limg_hip_error_Generic;
-      for (size_t i = 0; i < kInFlight; i++)
-        if (storeTimed[i])
-        {
-          float t = 0;
-          if (hipEventElapsedTime(&t, c->workTimers[4 * i + 2], c->workTimers[4 * i + 3]) == hipSuccess) kernelMs[1] += t;
-        }
-    });
-
-    // producer: the merge; its progress callback lays the finished rectangles out (pixel counts, scratch slices) and hands them over
-    size_t laid = 0;
-    uint64_t cap = 0;
-    const std::function<void(size_t)> progress = [&](size_t count) {
-      const std::vector<HostRegion> &regs = c->lastRegions;
-      for (size_t i = laid; i < count; i++)
-      {
-        const HostRegion &h = regs[i];
-        size_t xpx = (size_t)h.rx * kBlock, ypx = (size_t)h.ry * kBlock;
-        if (h.ox + h.rx == blocksX && (sizeX % kBlock)) xpx = xpx - kBlock + sizeX % kBlock;
-        if (h.oy + h.ry == blocksY && (sizeY % kBlock)) ypx = ypx - kBlock + sizeY % kBlock;
-        npx[i] = (uint32_t)(xpx * ypx);
-        desc[i] = { h.ox, h.oy, h.rx, h.ry, h.keep, (uint32_t)cap, { 0, 0 } };
-        cap += ((uint64_t)npx[i] + 3) & ~3ull;
-      }
-      laid = count;
-      { std::lock_guard<std::mutex> lk(pipe.m); pipe.ready = count; }
-      pipe.cv.notify_one();
-    };
-    bool mergeFailed = false;
-    try { blocked_merge(hRec, hBits, blocksX, blocksY, channels, c->lastRegions, &progress, &needSeedRow, hFlags, &needRecords); }
-    catch (...) { mergeFailed = true; } // out of host memory: the worker must still be released and joined
-    needSeedRow(blocksY - 1); // every band's copy is complete before the staging buffers can be reused
-    needRecords();
-    const clk::time_point t2 = clk::now();
-    { std::lock_guard<std::mutex> lk(pipe.m); pipe.finished = true; }
-    pipe.cv.notify_one();
-    worker.join();
+    Pipe pipe;
+    Merge merge{ j, pipe };
+    Worker worker{ j, pipe };
+    // the merge on this thread, the worker on one of its own -- or after the merge, on this thread, if the host refuses the thread: the merge never waits for it
+    run_on_threads(2, [&](unsigned t) { if (t == 0) merge.run(); else worker.run(); });
     const clk::time_point t5 = clk::now();
-    {
-      float a = 0, b = 0; // (both intervals ended before the merge's last band arrived)
-      const bool ok = hipEventElapsedTime(&a, frontTimers[0], frontTimers[1]) == hipSuccess && hipEventElapsedTime(&b, frontTimers[1], frontTimers[2]) == hipSuccess;
-      c->blockedKernelMs[0] = ok ? a : 0; c->blockedKernelMs[1] = ok ? b : 0;
-    }
-    c->blockedKernelMs[2] = kernelMs[0]; c->blockedKernelMs[3] = kernelMs[1];
-    c->blockedMs[0] = ms(t0, t1); c->blockedMs[1] = ms(t1, t2); c->blockedMs[2] = busy[0]; c->blockedMs[3] = busy[1]; c->blockedMs[4] = busy[2]; c->blockedMs[5] = ms(t0, t5);
-    if (mergeFailed) return limg_hip_error_MemoryAllocationFailure;
-    if (bandError) return limg_hip_error_Generic;
-    if (workerResult == limg_hip_success && c->opt.collect_stats)
-    { // src/limg.cpp:1561-1590 per rectangle: (8 - shift) bits for each of its pixels, and the pixels by shift
-      memset(c->statsHost, 0, sizeof(c->statsHost));
-      for (size_t i = 0; i < c->lastRegions.size(); i++)
-        for (int f = 0; f < 3; f++)
-        {
-          uint32_t sh = (hOut[i].shiftWord >> (8 * f)) & 0xFFu;
-          if (sh > 8) sh = 8;
-          c->statsHost[f] += (uint64_t)(8 - sh) * npx[i];
-          c->statsHost[3 + 9 * f + sh] += npx[i];
-        }
-      c->statsState = 2; c->statsPixels = (uint64_t)sizeX * sizeY;
-    }
-    return workerResult;
+    double a = 0, b = 0; // (both intervals ended before the merge's last band arrived)
+    const bool ok = add_elapsed(a, j.frontTimers[0], j.frontTimers[1]) && add_elapsed(b, j.frontTimers[1], j.frontTimers[2]);
+    c->blockedKernelMs[0] = ok ? a : 0; c->blockedKernelMs[1] = ok ? b : 0; c->blockedKernelMs[2] = worker.kernelMs[0]; c->blockedKernelMs[3] = worker.kernelMs[1];
+    c->blockedMs[0] = ms(t0, t1); c->blockedMs[1] = ms(t1, merge.end); c->blockedMs[2] = worker.busy[0]; c->blockedMs[3] = worker.busy[1]; c->blockedMs[4] = worker.busy[2];
+    c->blockedMs[5] = ms(t0, t5);
+    if (merge.failed) return limg_hip_error_MemoryAllocationFailure;
+    if (merge.bandError) return limg_hip_error_Generic;
+    if (worker.result == limg_hip_success && c->opt.collect_stats) collect_stats(j);
+    return worker.result;
   }
 
   limg_hip_result limg_hip_blocked_regions(limg_hip_context *c, limg_hip_region *pRegions, size_t capacity, size_t *pCount)
   {
     if (!c || !pCount) return limg_hip_error_ArgumentNull;
-    *pCount = c->lastRegions.size();
-    if (pRegions)
-      for (size_t i = 0; i < c->lastRegions.size() && i < capacity; i++) pRegions[i] = { c->lastRegions[i].ox, c->lastRegions[i].oy, c->lastRegions[i].rx, c->lastRegions[i].ry };
+    *pCount = copy_regions(c->lastRegions, pRegions, capacity);
     return limg_hip_success;
   }
 
@@ -487,24 +495,15 @@ extern "C"
     if ((r = c->in.ensure(px * 4)) != limg_hip_success) return r;
     if ((r = c->planes.ensure(stride * 13)) != limg_hip_success) return r;
     HIP_TRY(hipMemcpy(c->in.p, pIn, px * 4, hipMemcpyHostToDevice));
-    uint8_t *base = (uint8_t *)c->planes.p;
-    limg_hip_blocked_encode3d_info d;
-    memset(&d, 0, sizeof(d));
-    // 13 written planes, one `stride` each (the uint8 ones use a quarter of theirs)
-    void **hostp[13] = { (void **)&pInfo->pDecoded, (void **)&pInfo->pFactorsA, (void **)&pInfo->pFactorsB, (void **)&pInfo->pFactorsC, (void **)&pInfo->pBitsPerPixel,
-                         (void **)&pInfo->pShiftABCX, (void **)&pInfo->pColAMin, (void **)&pInfo->pColAMax, (void **)&pInfo->pColBMin, (void **)&pInfo->pColBMax,
-                         (void **)&pInfo->pColCMin, (void **)&pInfo->pColCMax, (void **)&pInfo->pBlockIndex };
-    void **devp[13] = { (void **)&d.pDecoded, (void **)&d.pFactorsA, (void **)&d.pFactorsB, (void **)&d.pFactorsC, (void **)&d.pBitsPerPixel, (void **)&d.pShiftABCX,
-                        (void **)&d.pColAMin, (void **)&d.pColAMax, (void **)&d.pColBMin, (void **)&d.pColBMax, (void **)&d.pColCMin, (void **)&d.pColCMax, (void **)&d.pBlockIndex };
-    const bool is8[13] = { false, true, true, true, true, false, false, false, false, false, false, false, false };
-    for (int i = 0; i < 13; i++)
-    {
-      if (!*hostp[i]) return limg_hip_error_ArgumentNull;
-      *devp[i] = base + stride * i;
-    }
+    if (!has_written_planes(*pInfo)) return limg_hip_error_ArgumentNull;
+    limg_hip_blocked_encode3d_info d = {};
+    size_t i = 0; // 13 written planes, one `stride` each (the uint8 ones use a quarter of theirs)
+    for_each_written_plane([&](auto m) { d.*m = (std::decay_t<decltype(d.*m)>)((uint8_t *)c->planes.p + stride * i++); });
     if ((r = limg_hip_blocked_encode3d_device(c, (const uint32_t *)c->in.p, sizeX, sizeY, hasAlpha, &d, errorFactor, fastBitCrushing, nullptr)) != limg_hip_success) return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    for (int i = 0; i < 13; i++) HIP_TRY(hipMemcpy(*hostp[i], *devp[i], is8[i] ? px : px * 4, hipMemcpyDeviceToHost));
+    hipError_t e = hipSuccess;
+    for_each_written_plane([&](auto m) { if (e == hipSuccess) e = hipMemcpy(pInfo->*m, d.*m, px * sizeof(*(d.*m)), hipMemcpyDeviceToHost); });
+    HIP_TRY(e);
     return limg_hip_success;
   }
 }

@@ -15,21 +15,10 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <functional>
-#include <vector>
-
-#include "../../include/limg_hip.h"
+#include "limg_hip_blocked_host.h"
 
 namespace limg_hip
 {
-  constexpr int kMatchLo = 5, kMatchHi = 12; // keep in sync with limg_hip_internal.h
-  constexpr int kMatchSide = kMatchLo + kMatchHi + 1;
-  constexpr int kMatchWords = (kMatchSide * kMatchSide + 63) / 64;
-
-  struct HostRegion { uint32_t ox, oy, rx, ry, keep; };
-
-  uint64_t chain_call(uint64_t h, unsigned n, uint8_t *noise, bool forceSoft, bool pcg); // limg_hip_noise.cpp (any n; `noise` holds n bytes)
-
   namespace
   {
     // limg_color_error_state_3d (src/limg_internal.h:426-452) with limg_dot's serial order (:357-366)
@@ -397,8 +386,4 @@ namespace limg_hip
         if (!m.used[(size_t)y * blocksX + x]) { out.push_back({ x, y, 1u, 1u, 1u }); tell(false); }
     tell(true);
   }
-
-  // One dither call over n pixels (src/limg.cpp:824-879 / :799-822), any n: floor(n / 8) AES rounds on {h, ~h}, then n % 8 PCG steps on the
-  // low 64 bits; writes n noise bytes (the byte pixel i ANDs with its dither mask) and returns the next chain value.
-  uint64_t chain_call_n(uint64_t h, size_t n, uint8_t *noise, bool pcg) { return chain_call(h, (unsigned)n, noise, false, pcg); }
 }

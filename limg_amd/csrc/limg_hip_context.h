@@ -116,14 +116,14 @@ struct limg_hip_context
   DevBuf bMatch, bRegions, bOut, bPx, bFac, bNoise, bNoiseBase; // merged-block encoder: similarity bits, region table / results, scratch (gathered pixels, factor bytes), noise
   HostBuf hFlags;
   HostBuf hRec, hBits, hDesc, hOut, hNoise, hNoiseBase;
-  hipStream_t workStream = nullptr; // the merged-block encoder's worker thread launches on its own stream
-  std::vector<hipStream_t> workStreams; // ... its fit + search batches round-robin on these
-  hipStream_t storeStream = nullptr; // ... and the noise expansion + store kernels of a batch on a second one
+  hipStream_t searchStream = nullptr; // the merged-block encoder's worker thread launches its fit + search batches on this stream
+  hipStream_t storeStream = nullptr;  // ... and the noise expansion + store kernels of a batch on a second one
   DevBuf bCalls;                     // per dither call of the merged-block encoder: chain value, noise offset, pixel count (host walk -> k_noise_expand_calls)
   std::vector<hipEvent_t> workEvents;        // one per batch of the merged-block encoder's worker that is in flight on the GPU
   hipStream_t copyStream = nullptr;      // copies of the similarity-bit bands, behind the kernels that produce them
   std::vector<hipEvent_t> bandEvents;
   std::vector<limg_hip::HostRegion> lastRegions;
+  std::vector<uint32_t> regionPx;            // ... and their pixel counts
   size_t lastBlocks = 0;                     // blocks of the last merged-block encode (what hBits / lastRegions describe)
   double blockedMs[6] = { 0, 0, 0, 0, 0, 0 };
   double blockedKernelMs[4] = { 0, 0, 0, 0 }; // the last merged-block encode, HIP events: pass 1 (k_fit_tpb) / the k_blocked_match launches / the k_blocked_fit_search launches /

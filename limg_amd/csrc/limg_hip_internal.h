@@ -5,11 +5,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <functional>
 #include <type_traits>
-#include <vector>
 
 #include "../../include/limg_hip.h"
+#include "limg_hip_blocked_host.h"
 
 namespace limg_hip
 {
@@ -137,14 +136,7 @@ namespace limg_hip
   void launch_chain_base(const unsigned long long *dCalls, int rank, int world, unsigned long long *dBase, uint32_t *dAborted, hipStream_t s);
 
   // ---- merged-block encoder (limg_hip_blocked.hip; reference: limg_blocked_encode3d_test, src/limg.cpp:1774-1885, :2329-2453) ----
-  // similarity bits are precomputed for candidate offsets dx, dy in [-kMatchLo, +kMatchHi] blocks around every seed: rectangles grow right / down from
-  // their seed (far), and up / left only in the second attempt from the centre third (near); measured on the synthetic workloads, this window answers
-  // 99.7 % of the merge's queries (the rest is evaluated on the host)
-  constexpr int kMatchLo = 5, kMatchHi = 12;
-  constexpr int kMatchSide = kMatchLo + kMatchHi + 1;   // 18
-  constexpr int kMatchCells = kMatchSide * kMatchSide;  // 324
-  constexpr int kMatchWords = (kMatchCells + 63) / 64;  // 6 x 64 bits per seed
-
+  // (the similarity window kMatch* and the host stages: limg_hip_blocked_host.h)
   struct RegionDesc // one rectangle of 8x8 blocks, in creation (= block index = dither chain) order
   {
     uint32_t ox, oy, rx, ry; // blocks
@@ -189,16 +181,6 @@ namespace limg_hip
   void launch_blocked_fit_search(const BlockedParams &p, hipStream_t s);
   void launch_blocked_store(const BlockedParams &p, hipStream_t s);
   void launch_blocked_order(const BlockedParams &p, hipStream_t s);
-
-  // host side of the merged-block encoder (limg_hip_blocked_host.cpp): the greedy raster merge and the dither chain walk
-  struct HostRegion { uint32_t ox, oy, rx, ry, keep; };
-  void blocked_merge(const limg_hip_block_record *pass1, const unsigned long long *matchBits, uint32_t blocksX, uint32_t blocksY, int channels, std::vector<HostRegion> &out,
-                     const std::function<void(size_t)> *progress = nullptr, const std::function<void(uint32_t)> *needSeedRow = nullptr, const uint8_t *seedFlags = nullptr,
-                     const std::function<void()> *needRecords = nullptr);
-  bool blocked_matches_host(int channels, const limg_hip_block_record &seed, const limg_hip_block_record &cand);
-  uint64_t chain_call_n(uint64_t h, size_t n, uint8_t *noise, bool pcg);
-  uint64_t chain_walk_batch(uint64_t h, size_t count, const uint8_t *shiftWords, size_t stride, const uint32_t *npx, unsigned long long *noiseBase, unsigned long long *callState,
-                            unsigned long long *callOff, uint32_t *callPx, uint64_t &noiseOff, size_t &callCount, size_t maxCalls, bool pcg); // limg_hip_noise.cpp
 
   void launch_stream_pack(const StreamParams &p, hipStream_t s);
   void launch_stream_decode(const DecodeParams &p, hipStream_t s);
