@@ -7,19 +7,28 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import lib_axis as L
 from oracle.bind import BLOCKED_WRITTEN
 
 pytestmark = pytest.mark.gpu
 GOLD = json.load(open(os.path.join(gu.G, "blocked.json")))
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    import limg_amd
-    g = limg_amd.LimgHip(0)
+def _gpu(lib):
+    g = L.open_context(lib)
     yield g
     g.check()
     g.close()
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    yield from _gpu("test")
+
+
+@pytest.fixture(scope="module")
+def gpu_product():
+    yield from _gpu("product")
 
 
 def _input(orc, e):
@@ -197,3 +206,6 @@ def test_large_first_order_and_vector_stores_change_nothing(gpu, oracle):
         assert np.array_equal(outs[(True, False)][k], want[k]), ("creation order", k)
         assert np.array_equal(outs[(False, True)][k], want[k]), ("one pixel per lane in the store kernel", k)
     gpu.check()
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

@@ -8,6 +8,8 @@ RCCL with more than one rank needs more than one GPU: unmeasured here (the drive
 import numpy as np
 import pytest
 
+import lib_axis as L
+from lib_axis import lib, lib_product  # noqa: F401  (fixtures: "test" / "product")
 from oracle.bind import PLANES
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +21,7 @@ def _np(planes):
 
 
 @pytest.mark.parametrize("kind,alpha,ranks", [("pn", True, 4), ("rg", True, 2), ("pn", False, 8)])
-def test_single_chain_across_emulated_ranks(oracle, kind, alpha, ranks):
+def test_single_chain_across_emulated_ranks(oracle, kind, alpha, ranks, lib):
     import torch
     import limg_amd
     from limg_amd import shard
@@ -28,7 +30,7 @@ def test_single_chain_across_emulated_ranks(oracle, kind, alpha, ranks):
     want = oracle.encode3d(img, alpha)  # pool_threads = 0: ONE chain over the whole image
     d_img = torch.from_numpy(img.view(np.int32)).cuda()
     rows = shard.strip_rows(H, ranks)
-    ctxs = [limg_amd.LimgHip(0) for _ in range(ranks)]
+    ctxs = [L.open_context(lib) for _ in range(ranks)]
     try:
         planes = [c.alloc_planes_device(W, y1 - y0) for c, (y0, y1) in zip(ctxs, rows)]
         calls = torch.zeros(ranks, dtype=torch.int64, device="cuda")
@@ -56,10 +58,10 @@ def test_single_chain_across_emulated_ranks(oracle, kind, alpha, ranks):
             c.close()
 
 
-def test_chain_entry_refuses_what_it_cannot_chain(oracle):
+def test_chain_entry_refuses_what_it_cannot_chain(oracle, lib):
     import torch
     import limg_amd
-    g = limg_amd.LimgHip(0)
+    g = L.open_context(lib)
     try:
         img = torch.zeros((20, 30), dtype=torch.int32, device="cuda")  # partial edge blocks: the chain position is not a table index
         planes = g.alloc_planes_device(30, 20)
@@ -82,12 +84,12 @@ def test_chain_entry_refuses_what_it_cannot_chain(oracle):
         g.close()
 
 
-def test_rccl_world_of_one(oracle):
+def test_rccl_world_of_one(oracle, lib):
     """The real RCCL through the C ABI with a communicator of one rank: id, init, the gather (degenerates to the local copy after the size all-gather),
     the single-chain encode (its all-gather is a copy), destroy.  Checks the dlopen path, the argument plumbing and the stream ordering."""
     import torch
     import limg_amd
-    g = limg_amd.LimgHip(0)
+    g = L.open_context(lib)
     try:
         g.comm_init(g.comm_unique_id(), 0, 1)
         W, H = 512, 128
@@ -115,26 +117,27 @@ def test_rccl_world_of_one(oracle):
         for k in PLANES:
             assert np.array_equal(got[k], want[k]), k
         g.check()
-        # abort rule: a rank whose E step failed (test hook) still joins the all-gather -- with a poison value -- and returns its error; the call comes back
-        # (no rank is left waiting), no plane is written, and the context reports the aborted chain once
-        for v in planes.values():
-            v.zero_()
-        g.set_options(test_fail_chain_phase1=True)
-        try:
+        if L.has_hooks(g):
+            # abort rule: a rank whose E step failed (test hook) still joins the all-gather -- with a poison value -- and returns its error; the call comes back
+            # (no rank is left waiting), no plane is written, and the context reports the aborted chain once
+            for v in planes.values():
+                v.zero_()
+            g.set_options(test_fail_chain_phase1=True)
+            try:
+                with pytest.raises(limg_amd.LimgHipError):
+                    g.encode3d_single_chain_device(d_img, True, planes, 0)
+            finally:
+                g.set_options()
+            torch.cuda.synchronize()
+            assert all(int(v.count_nonzero().item()) == 0 for v in planes.values())
             with pytest.raises(limg_amd.LimgHipError):
-                g.encode3d_single_chain_device(d_img, True, planes, 0)
-        finally:
-            g.set_options()
-        torch.cuda.synchronize()
-        assert all(int(v.count_nonzero().item()) == 0 for v in planes.values())
-        with pytest.raises(limg_amd.LimgHipError):
-            g.check()  # "a rank of the communicator aborted a single-chain encode"
-        g.check()      # sticky until reported once
-        g.encode3d_single_chain_device(d_img, True, planes, 0)  # and the context goes on working
-        torch.cuda.synchronize()
-        got = _np(planes)
-        for k in PLANES:
-            assert np.array_equal(got[k], want[k]), k
+                g.check()  # "a rank of the communicator aborted a single-chain encode"
+            g.check()      # sticky until reported once
+            g.encode3d_single_chain_device(d_img, True, planes, 0)  # and the context goes on working
+            torch.cuda.synchronize()
+            got = _np(planes)
+            for k in PLANES:
+                assert np.array_equal(got[k], want[k]), k
         g.comm_destroy()
         g.check()
     finally:
@@ -258,3 +261,6 @@ def test_rccl_two_ranks(tmp_path):
         pytest.skip("the two-rank RCCL job did not get its communicator up in 240 s on this node (rendezvous / fabric problem, not a result): " + " | ".join(o[-300:] for o in outs))
     assert not timed_out, ("two-rank RCCL job hung AFTER the communicator was up", [o[-600:] for o in outs])
     assert all(p.returncode == 0 for p in procs), outs
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

@@ -13,6 +13,9 @@ import time
 
 import pytest
 
+import lib_axis as L
+from lib_axis import lib, lib_product  # noqa: F401  (fixtures: "test" / "product")
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -27,13 +30,21 @@ def _planes_equal_count(torch, got, want):
     return bad
 
 
-@pytest.fixture(scope="module")
-def ctxs():
-    import limg_amd
-    gs = [limg_amd.LimgHip(0) for _ in range(4)]
+def _ctxs(lib):
+    gs = [L.open_context(lib) for _ in range(4)]
     yield gs
     for g in gs:
         g.close()
+
+
+@pytest.fixture(scope="module")
+def ctxs():
+    yield from _ctxs("test")
+
+
+@pytest.fixture(scope="module")
+def ctxs_product():
+    yield from _ctxs("product")
 
 
 @pytest.mark.parametrize("kind,W,H", [("photo_noise", 8192, 8192), ("random_gradient", 4096, 4096)])
@@ -194,14 +205,13 @@ def test_lookback_timeout_is_loud(ctxs):
         assert torch.equal(got[k], want[k]), k
 
 
-def test_width_ragged_encodes_on_three_threads(oracle):
+def test_width_ragged_encodes_on_three_threads(oracle, lib):
     """The width-ragged path blocks its calling thread (the host walks the dither chain while the GPU works around it in bands): a service runs it from several threads, each
     with its own context and stream.  Three threads x 4 encodes of a 2046 x 1024 image (banded pipeline: 256 x 128 blocks) and, on one of them, the pool-of-2 variant
     (parallel chain walks): every result equals the oracle's."""
     import threading
     import numpy as np
     import torch
-    import limg_amd
     from oracle.bind import PLANES
     W, H = 2046, 1024
     img = oracle.photo_noise(W, H, 61)
@@ -212,7 +222,7 @@ def test_width_ragged_encodes_on_three_threads(oracle):
     def work(k):
         try:
             torch.cuda.set_device(0)
-            g = limg_amd.LimgHip(0)
+            g = L.open_context(lib)
             st = torch.cuda.Stream()
             planes = g.alloc_planes_device(W, H)
             with torch.cuda.stream(st):
@@ -234,3 +244,6 @@ def test_width_ragged_encodes_on_three_threads(oracle):
     for t in th:
         t.join()
     assert not errs, errs
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import lib_axis as L
 from oracle.bind import BLOCKED_WRITTEN, PLANES
 
 pytestmark = pytest.mark.gpu
@@ -18,13 +19,21 @@ GOLD = json.load(open(os.path.join(gu.G, "fullsize.json")))
 KIND = {"pn": "photo_noise", "rg": "random_gradient"}
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    import limg_amd
-    g = limg_amd.LimgHip(0)
+def _gpu(lib):
+    g = L.open_context(lib)
     yield g
     g.check()
     g.close()
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    yield from _gpu("test")
+
+
+@pytest.fixture(scope="module")
+def gpu_product():
+    yield from _gpu("product")
 
 
 def _host(t):
@@ -175,3 +184,6 @@ def test_blocked_reference_hashes(gpu, oracle, name):
     assert psnr == pytest.approx(e["psnr"], abs=1e-9)
     del planes, img
     torch.cuda.empty_cache()
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

@@ -4,6 +4,8 @@ launches' gaps are 10-15 % of an encode).  Replays must reproduce the planes of 
 import numpy as np
 import pytest
 
+import lib_axis as L
+from lib_axis import lib, lib_product  # noqa: F401  (fixtures: "test" / "product")
 from oracle.bind import PLANES
 
 pytestmark = pytest.mark.gpu
@@ -14,10 +16,9 @@ def _host(planes):
     return {k: v.cpu().numpy().view(np.uint32 if v.dtype == torch.int32 else np.uint8) for k, v in planes.items()}
 
 
-def test_single_encode_in_a_hip_graph(oracle):
+def test_single_encode_in_a_hip_graph(oracle, lib):
     import torch
-    import limg_amd
-    g = limg_amd.LimgHip(0)
+    g = L.open_context(lib)
     try:
         W, H = 512, 64
         a, b = oracle.photo_noise(W, H, 71), oracle.random_gradient(W, H, 72, True)
@@ -43,12 +44,11 @@ def test_single_encode_in_a_hip_graph(oracle):
         g.close()
 
 
-def test_batch_pipeline_in_a_hip_graph(oracle):
+def test_batch_pipeline_in_a_hip_graph(oracle, lib):
     """17 images: the default rule runs them in sub-batches of 4 with the float stage of the next sub-batch on the context's second stream -- a fork / join inside the
     captured region."""
     import torch
-    import limg_amd
-    g = limg_amd.LimgHip(0)
+    g = L.open_context(lib)
     try:
         W, H, n = 256, 24, 17
         host = [oracle.photo_noise(W, H, 300 + i) for i in range(n)]
@@ -72,3 +72,6 @@ def test_batch_pipeline_in_a_hip_graph(oracle):
         g.check()
     finally:
         g.close()
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import lib_axis as L
 from oracle.bind import PLANES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,13 +21,22 @@ pytestmark = pytest.mark.gpu
 N = 24576
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    import limg_amd
-    g = limg_amd.LimgHip(0)  # a context of its own: its scratch (noise table 1.8 GB, records, park) goes with it
+def _gpu(lib):
+    g = L.open_context(lib)  # a context of its own: its scratch (noise table 1.8 GB, records, park) goes with it
     yield g
     g.check()
     g.close()
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    yield from _gpu("test")
+
+
+@pytest.fixture(scope="module")
+def gpu_product():
+    yield from _gpu("product")
+
 
 UNIFORM = ("pShiftABCX", "pColAMin", "pColAMax", "pColBMin", "pColBMax", "pColCMin", "pColCMax")
 
@@ -82,6 +92,8 @@ def test_image_beyond_the_dense_checkpoints(gpu, oracle):
         _band_equals_oracle(oracle, img, planes, 7 * rows, PLANES)
         del part, planes
         torch.cuda.empty_cache()
+        if not L.has_hooks(gpu):  # the rest compares with the whole-image ragged path: a test hook
+            return
         # A partial last block row 28 M calls into the chain: the fast path takes the chain value there from a far checkpoint (+ at most 65535 calls on foot); the
         # whole-image ragged path walks every call on the host.  Every plane equal -- which also checks the GPU-filled noise table against a host walk of the whole chain.
         H = N - 3
@@ -96,3 +108,6 @@ def test_image_beyond_the_dense_checkpoints(gpu, oracle):
     finally:
         gpu.set_options()
         torch.cuda.empty_cache()
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

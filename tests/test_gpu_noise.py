@@ -5,6 +5,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lib_axis as L
+from lib_axis import lib, lib_product  # noqa: F401  (fixtures: "test" / "product")
 from oracle.bind import PLANES
 
 pytestmark = pytest.mark.gpu
@@ -25,9 +27,8 @@ def _host_table(g, calls):
     return out
 
 
-def test_gpu_noise_table_equals_host_walk():
-    import limg_amd
-    g = limg_amd.LimgHip(0)
+def test_gpu_noise_table_equals_host_walk(lib):
+    g = L.open_context(lib)
     try:
         for calls in (1, 1023, 1024, 1025, 40 * 1024 + 77):  # whole, partial and single stretches of 1024 calls
             assert np.array_equal(_device_table(g, calls), _host_table(g, calls)), calls
@@ -54,13 +55,12 @@ def test_gpu_noise_table_equals_host_walk():
         g.close()
 
 
-def test_encode_with_host_built_table_is_identical(oracle):
+def test_encode_with_host_built_table_is_identical(oracle, lib):
     """A/B of the two ways the context gets its table (limg_hip_options.host_noise_table): every plane equal, and equal to the oracle."""
-    import limg_amd
     img = oracle.photo_noise(512, 136, 71)
     want = oracle.encode3d(img, True)
     for host in (False, True):
-        g = limg_amd.LimgHip(0)
+        g = L.open_context(lib)
         try:
             g.set_options(host_noise_table=host)
             got = g.encode3d(img, True)
@@ -69,3 +69,6 @@ def test_encode_with_host_built_table_is_identical(oracle):
         finally:
             g.check()
             g.close()
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

@@ -8,30 +8,40 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import lib_axis as L
+from lib_axis import lib, lib_product  # noqa: F401  (fixtures: "test" / "product")
 from oracle.bind import PLANES, REC_DTYPE
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module", params=["fused", "split", "legacy"])
-def gpu(request):
+def _gpu(mode, lib):
     """`fused`  = k_fit_tpb (float stage, one lane per block) + the persistent kernel (decoupled look-back for the dither chain) where they apply;
     `split`  = the three-launch path (fit+search, scan, dither+store) that ragged images always take;
     `legacy` = the float stage inside the persistent kernel's E step with lane == pixel (the round-1 mapping, still what images with partial blocks run)."""
-    import limg_amd
-    g = limg_amd.LimgHip(0)  # raises if the HIP library or the device is missing: no fallback
-    g.mode = request.param
+    g = L.open_context(lib)  # raises if the HIP library or the device is missing: no fallback
+    g.mode = mode
     plain = g.set_options
 
     def set_options(**kw):  # every options change inside a test keeps the fixture's mode
-        kw.setdefault("force_split", request.param == "split")
-        kw["legacy_float_stage"] = request.param == "legacy"
+        kw.setdefault("force_split", mode == "split")
+        kw["legacy_float_stage"] = mode == "legacy"
         plain(**kw)
     g.set_options = set_options
     g.set_options()
     yield g
     g.check()
     g.close()
+
+
+@pytest.fixture(scope="module", params=["fused", "split", "legacy"])
+def gpu(request):
+    yield from _gpu(request.param, "test")
+
+
+@pytest.fixture(scope="module", params=["fused", "split", "legacy"])
+def gpu_product(request):
+    yield from _gpu(request.param, "product")
 
 
 def _assert_planes(got, want, ctx):
@@ -113,11 +123,12 @@ def test_height_ragged_shapes(gpu, oracle, w, h, alpha):
     img = oracle.photo_noise(w, h, 31) if w != 512 else oracle.random_gradient(w, h, 31, True)
     want = oracle.encode3d(img, alpha)
     _assert_planes(gpu.encode3d(img, alpha), want, (w, h, alpha))
-    gpu.set_options(test_whole_image_ragged=True)
-    try:
-        _assert_planes(gpu.encode3d(img, alpha), want, (w, h, alpha, "whole-image path"))
-    finally:
-        gpu.set_options()
+    if L.has_hooks(gpu):  # the whole-image ragged path of `fused` is a test hook
+        gpu.set_options(test_whole_image_ragged=True)
+        try:
+            _assert_planes(gpu.encode3d(img, alpha), want, (w, h, alpha, "whole-image path"))
+        finally:
+            gpu.set_options()
     for pool in ((1, 2, 3) if h >= 100 else (1,) if h >= 16 else ()):
         _assert_planes(gpu.encode3d(img, alpha, pool_threads=pool), oracle.encode3d(img, alpha, pool_threads=pool), (w, h, alpha, "pool", pool))
     if h == 100:
@@ -169,15 +180,17 @@ def test_height_ragged_at_4096(gpu, oracle):
     a = gpu.alloc_planes_device(W, H)
     b = gpu.alloc_planes_device(W, H)
     gpu.encode3d_device(img, True, a)
-    gpu.set_options(test_whole_image_ragged=True)
-    try:
-        gpu.encode3d_device(img, True, b)
-    finally:
-        gpu.set_options()
+    if L.has_hooks(gpu):  # the whole-image ragged path (test hook) against the fast path + last row
+        gpu.set_options(test_whole_image_ragged=True)
+        try:
+            gpu.encode3d_device(img, True, b)
+        finally:
+            gpu.set_options()
     torch.cuda.synchronize()
     gpu.check()
-    for k in PLANES:
-        assert torch.equal(a[k], b[k]), k
+    if L.has_hooks(gpu):
+        for k in PLANES:
+            assert torch.equal(a[k], b[k]), k
     host = img.cpu().numpy().view(np.uint32)
     want = oracle.encode3d(host, True, worker_threads=8)
     for k in PLANES:
@@ -389,10 +402,9 @@ def test_compact_mode(gpu, oracle):
         assert np.array_equal((gsh >> (8 * i)) & 0xFF, want["shifts"][:, :, i])
 
 
-def test_two_contexts_on_two_threads(oracle):
+def test_two_contexts_on_two_threads(oracle, lib):
     """Contexts are independent: two host threads, each with its own context, encode different images at the same time (8x8 path and merged-block encoder)."""
     import threading
-    import limg_amd
     from oracle.bind import BLOCKED_WRITTEN
     imgs = [oracle.photo_noise(512, 256, 21), oracle.random_gradient(384, 264, 22, False)]
     want = [oracle.encode3d(i, True) for i in imgs]
@@ -401,7 +413,7 @@ def test_two_contexts_on_two_threads(oracle):
 
     def work(k):
         try:
-            g = limg_amd.LimgHip(0)
+            g = L.open_context(lib)
             for _ in range(5):
                 got = g.encode3d(imgs[k], True)
                 bad = [p for p in PLANES if not np.array_equal(got[p], want[k][p])]
@@ -640,3 +652,6 @@ def test_accurate_mode_at_4096(gpu, oracle):
         del planes, d_img
     gpu.check()
     torch.cuda.empty_cache()
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

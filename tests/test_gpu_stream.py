@@ -3,20 +3,29 @@ decode(encode(image)) against the pDecoded plane of the oracle (== the real refe
 import numpy as np
 import pytest
 
+import lib_axis as L
 from oracle import stream as S
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module", params=["fused", "split"])
-def gpu(request):
-    import limg_amd
-    g = limg_amd.LimgHip(0)
-    g.set_options(force_split=(request.param == "split"))
-    g.mode = request.param
+def _gpu(mode, lib):
+    g = L.open_context(lib)
+    g.set_options(force_split=(mode == "split"))
+    g.mode = mode
     yield g
     g.check()
     g.close()
+
+
+@pytest.fixture(scope="module", params=["fused", "split"])
+def gpu(request):
+    yield from _gpu(request.param, "test")
+
+
+@pytest.fixture(scope="module", params=["fused", "split"])
+def gpu_product(request):
+    yield from _gpu(request.param, "product")
 
 
 def _cases(oracle):
@@ -139,3 +148,6 @@ def test_device_decode_refuses_wrapping_header(gpu, oracle):
         gpu.check()
     assert int(out.abs().max()) == 0
     assert np.array_equal(gpu.decode_stream(st), gpu.encode3d(img, True)["pDecoded"])
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

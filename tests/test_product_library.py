@@ -1,6 +1,8 @@
-"""The PRODUCT library (limg_amd/liblimg_hip.so) as shipped: the rest of the suite runs on the test-hooks build (tests/conftest.py), so everything that must hold for
-the plain library is checked here -- it exports the whole ABI of include/limg_hip.h and nothing of include/limg_hip_test_hooks.h, carries no fault-injection
-parameter in its kernels, versions limg_hip_options by its size, and (GPU) produces the oracle's planes.  The reference has no such knobs at all (src/limg.h:27-48)."""
+"""The PRODUCT library (limg_amd/liblimg_hip.so) as shipped, beside the test-hooks build (liblimg_hip_test.so): it exports the whole ABI of include/limg_hip.h and
+nothing of include/limg_hip_test_hooks.h, carries no fault-injection parameter in its kernels (the kernel inventory: the same kernels in both builds, a shorter
+kernarg segment for exactly the EncodeParams kernels), versions limg_hip_options by its size, and (GPU) produces the oracle's planes and refuses the hooks.  The
+in-process GPU suite runs on both libraries (tests/lib_axis.py) and tests/test_gpu_library_identity.py compares them bit for bit; this file holds what is about the
+product library itself.  The reference has no such knobs at all (src/limg.h:27-48)."""
 import ctypes as C
 import os
 import re
@@ -85,6 +87,50 @@ def test_no_fault_injection_in_the_product_kernels(tmp_path):
         sizes[name] = found
     assert sizes["plain"].keys() == sizes["test"].keys()
     assert all(sizes["test"][k] - sizes["plain"][k] in (12, 16) for k in sizes["plain"]), sizes
+
+
+def _kernarg_sizes(lib, tmp_path, tag):
+    """{mangled kernel name: kernarg segment size} over every gfx950 code object of `lib`"""
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    if not os.path.exists(readelf):
+        pytest.skip("no llvm-readelf")
+    found = {}
+    for i, co in enumerate(_gfx950_code_objects(lib)):
+        f = tmp_path / ("%s_%d.co" % (tag, i))
+        f.write_bytes(co)
+        notes = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
+        for kern in notes.split("- .agpr_count:")[1:]:
+            nm = re.search(r"\.name:\s*(\S+)", kern)
+            sz = re.search(r"\.kernarg_segment_size:\s*(\d+)", kern)
+            if nm and sz:
+                assert nm.group(1) not in found, (lib, nm.group(1))
+                found[nm.group(1)] = int(sz.group(1))
+    assert found, "no kernel metadata in " + lib
+    return found
+
+
+# the kernels that take EncodeParams (limg_hip_internal.h), with their instantiation counts: the test build's struct carries three hook members more, so each of
+# these is a code object of its own in the product -- what tests/test_gpu_library_identity.py runs bit for bit against the test build
+ENCODE_PARAMS_KERNELS = {"k_encode_persistent": 16, "k_fit_search": 16, "k_fit_tpb": 8, "k_dither_store": 2, "k_strip_scan": 1}
+
+
+def test_kernel_inventory_of_the_two_builds(tmp_path):
+    """Every kernel of both libraries: the same set of names; a longer kernarg segment in the test build for exactly the EncodeParams kernels (16 bytes: three uint32 hook
+    members and the padding in front of the pointer after them); an equal one for every other kernel (stream, decode, noise, synth, compare, blocked, chain)."""
+    _built()
+    plain, test = _kernarg_sizes(PLAIN, tmp_path, "plain"), _kernarg_sizes(limg_amd.TEST_LIB_PATH, tmp_path, "test")
+    assert plain.keys() == test.keys(), sorted(set(plain) ^ set(test))
+    differ = {k for k in plain if plain[k] != test[k]}
+    takes = {k for k in plain if "12EncodeParams" in k}
+    assert differ == takes, (sorted(differ - takes), sorted(takes - differ))
+    assert all(test[k] - plain[k] == 16 for k in differ), {k: (plain[k], test[k]) for k in differ}
+    family = {k: re.search(r"\d(k_[a-z_]+)", k).group(1) for k in plain}  # (mangled: <length>k_name, then I... for template arguments or E)
+    families = {}
+    for k in differ:
+        families[family[k]] = families.get(family[k], 0) + 1
+    assert families == ENCODE_PARAMS_KERNELS, families
+    others = {family[k] for k in plain if k not in differ}
+    assert {"k_stream_pack", "k_stream_decode", "k_noise_fill", "k_synth_photo_noise", "k_blocked_store", "k_blocked_fit_search", "k_chain_base"} <= others, sorted(others)
 
 
 def test_default_options_honours_the_callers_size():

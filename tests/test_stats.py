@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import lib_axis as L
+from lib_axis import lib, lib_product  # noqa: F401  (fixtures: "test" / "product")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "stats.json")))
@@ -48,11 +50,11 @@ def test_stats_text_from_oracle_shifts(oracle, name):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(GOLD))
-def test_gpu_stats_equal_the_reference_text(oracle, name):
+def test_gpu_stats_equal_the_reference_text(oracle, name, lib):
     import limg_amd
     e = GOLD[name]
     img = _input(e, oracle)
-    g = limg_amd.LimgHip(0)
+    g = L.open_context(lib)
     try:
         with pytest.raises(limg_amd.LimgHipError):
             g.last_stats()  # nothing collected yet
@@ -76,16 +78,15 @@ def test_gpu_stats_equal_the_reference_text(oracle, name):
 
 
 @pytest.mark.gpu
-def test_gpu_stats_of_a_batch(oracle):
+def test_gpu_stats_of_a_batch(oracle, lib):
     """A batched encode's counters are those of its images together."""
     import torch
-    import limg_amd
     W, H = 256, 64
     host = [oracle.photo_noise(W, H, 50 + i) for i in range(3)]
     total = np.zeros(30, dtype=np.uint64)
     for h in host:
         total += _counters_from_shifts(oracle.encode3d(h, True, extras=True)["shifts"], W, H)
-    g = limg_amd.LimgHip(0)
+    g = L.open_context(lib)
     try:
         g.set_options(collect_stats=True)
         imgs = [torch.from_numpy(h.view(np.int32)).cuda() for h in host]
@@ -96,3 +97,6 @@ def test_gpu_stats_of_a_batch(oracle):
     finally:
         g.check()
         g.close()
+
+
+L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

@@ -3,20 +3,29 @@ whose byte offsets pass 2^32, a dither chain of ~50 M calls (beyond the embedded
 run of the whole image: (1) status clean, PSNR of the generator; (2) the first 64 rows equal the oracle on every plane (the chain starts at the seed); (3) a middle and the LAST
 64-row band equal the oracle on the chain-independent planes; (4) strip-restart encode (pool of 2 = 8 strips): strips 0 and 7 equal their standalone encodes on every plane
 (strip 7 lies behind the 4 GiB offset in every 32-bit plane); (5) N x (N - 2), a partial last block row ~50 M calls into the chain: the fast path (the chain value there from
-the far checkpoints + at most 65535 calls on foot) equals the whole-image ragged path (host walk over every call) on every plane; (6) the compact stream's round trip.  usage: python tools/huge_image_check.py [N]"""
+the far checkpoints + at most 65535 calls on foot) equals the whole-image ragged path (host walk over every call) on every plane -- a hook of the test build, so on that build
+only; (6) the compact stream's round trip.  usage: python tools/huge_image_check.py [N] [--lib test|product]  (default: the test build)"""
 import os
 import sys
 import time
 sys.path.insert(0, '.')
 import numpy as np
 import torch
-os.environ.setdefault("LIMG_HIP_LIB", "test")  # property (5) uses a hook of the test build
 import limg_amd
 from oracle.bind import Oracle, PLANES
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 32768
+args = sys.argv[1:]
+LIB = "test"
+if "--lib" in args:
+    i = args.index("--lib")
+    LIB = args[i + 1]
+    del args[i:i + 2]
+assert LIB in ("test", "product"), LIB
+N = int(args[0]) if args else 32768
 orc = Oracle()
-g = limg_amd.LimgHip(0)
+g = limg_amd.LimgHip(0, lib_path=limg_amd.TEST_LIB_PATH if LIB == "test" else os.path.join(limg_amd.HERE, "liblimg_hip.so"))
+assert g.has_test_hooks == (LIB == "test"), LIB
+print("library: %s" % LIB, flush=True)
 t = time.perf_counter()
 img = g.synth_device("photo_noise", N, N, seed=1)
 planes = g.alloc_planes_device(N, N)
@@ -69,16 +78,19 @@ print("stream round trip == pDecoded", flush=True)
 g.check()
 del planes
 torch.cuda.empty_cache()
-H = N - 2
-pa, pb = g.alloc_planes_device(N, H), g.alloc_planes_device(N, H)
-for name, whole, out in (("fast path + last row", False, pa), ("whole-image ragged path", True, pb)):
-    g.set_options(test_whole_image_ragged=whole)
-    for i in range(2):
-        torch.cuda.synchronize(); t = time.perf_counter()
-        g.encode3d_device(img[:H], True, out); torch.cuda.synchronize()
-        print("%d x %d, %s, encode %d: %.2f ms" % (N, H, name, i, (time.perf_counter() - t) * 1e3), flush=True)
-for k in PLANES:
-    assert torch.equal(pa[k], pb[k]), k
-print("%d x %d: fast path == whole-image ragged path on all %d planes" % (N, H, len(PLANES)), flush=True)
+if g.has_test_hooks:  # (5) needs the whole-image ragged hook
+    H = N - 2
+    pa, pb = g.alloc_planes_device(N, H), g.alloc_planes_device(N, H)
+    for name, whole, out in (("fast path + last row", False, pa), ("whole-image ragged path", True, pb)):
+        g.set_options(test_whole_image_ragged=whole)
+        for i in range(2):
+            torch.cuda.synchronize(); t = time.perf_counter()
+            g.encode3d_device(img[:H], True, out); torch.cuda.synchronize()
+            print("%d x %d, %s, encode %d: %.2f ms" % (N, H, name, i, (time.perf_counter() - t) * 1e3), flush=True)
+    for k in PLANES:
+        assert torch.equal(pa[k], pb[k]), k
+    print("%d x %d: fast path == whole-image ragged path on all %d planes" % (N, H, len(PLANES)), flush=True)
+else:
+    print("(5) not run: the product library has no whole-image ragged hook", flush=True)
 g.check(); g.close()
-print("huge image check ok: %d x %d" % (N, N))
+print("huge image check ok: %d x %d, %s library" % (N, N, LIB))
