@@ -90,7 +90,8 @@ typedef struct limg_hip_options
 typedef struct limg_hip_context limg_hip_context;
 
 /* Thread safety.  The reference is re-entrant (stack scratch only, src/limg.cpp:1890-1891).  Here a context owns device scratch, so:
- *   - the blocking HOST-pointer entries (limg_hip_encode3d, _encode3d_perf, _compare, _blocked_encode3d, _encode_stream, _decode_stream) take a mutex inside the
+ *   - the blocking HOST-pointer entries (limg_hip_encode3d, _encode3d_perf, _compare, _blocked_encode3d, _encode_stream, _decode_stream, _blocked_encode_stream,
+ *     _blocked_decode_stream) take a mutex inside the
  *     context: any number of threads may call them on one shared context at once (this is what the C++ shim's limg_encode3d_test & co. rely on); the calls run
  *     one after the other;
  *   - the asynchronous *_device entries enqueue kernels that use the context's scratch after the call has returned: use one context per HIP stream / thread
@@ -240,7 +241,7 @@ limg_hip_result limg_hip_blocked_timing(limg_hip_context *pCtx, double *pMs6);
 limg_hip_result limg_hip_blocked_match_bits(limg_hip_context *pCtx, uint64_t *pBits, size_t capacityWords, size_t *pWords);
 /* GPU time of the last merged-block encode's launches, from HIP events on the streams they run on: [0] pass 1 (the 8x8 path's float stage), [1] the similarity
  * kernels (16 bands, back to back), and summed over the worker's batches [2] the per-rectangle fit + search kernel, [3] chain-value upload + noise expansion +
- * dither/decode/store kernel.  (What the GPU side costs with no host in the way: bench.py's kernel-only rate of the merged-block encoder.) */
+ * dither/decode/store kernel -- after limg_hip_blocked_encode_stream*, which stores no plane: noise expansion + the stream's scan and pack kernels.  (What the GPU side costs with no host in the way: bench.py's kernel-only rate of the merged-block encoder.) */
 limg_hip_result limg_hip_blocked_kernel_timing(limg_hip_context *pCtx, double *pMs4);
 /* Host-only (no GPU touched): the block-similarity predicate `limg_encode_3d_matches` (src/limg.cpp:1137-1268) as the host merge evaluates it
  * for candidates outside the precomputed window; records in `limg_hip_block_record` layout. */
@@ -276,8 +277,8 @@ typedef struct limg_hip_stream_header
   uint32_t blocksX, blocksY;
   uint64_t payloadWords; /* 8-byte words after the block table */
   uint64_t totalBytes;   /* header + table + payload */
-  uint32_t flags;        /* bit 0: fast bit crushing, bit 1: PCG dither (informational) */
-  uint32_t reserved[3];
+  uint32_t flags;        /* bit 0: fast bit crushing, bit 1: PCG dither (informational); version 2: bit 2 = merged-block stream */
+  uint32_t reserved[3];  /* 0; version 2: [0] = rectangle count */
 } limg_hip_stream_header; /* 64 bytes */
 
 typedef struct limg_hip_stream_block
@@ -305,6 +306,62 @@ limg_hip_result limg_hip_encode_stream(limg_hip_context *pCtx, const uint32_t *p
 limg_hip_result limg_hip_decode_stream(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, uint32_t *pOut, size_t outPixels);
 /* Host-only: validates a header (first 64 bytes suffice) and reports the image shape. */
 limg_hip_result limg_hip_stream_info(const uint8_t *pStream, size_t streamBytes, size_t *pSizeX, size_t *pSizeY, int *pHasAlpha, size_t *pTotalBytes);
+
+/* ---- compact stream, version 2: the merged-block encoder's rectangles --------------------------------------------------------
+ * What limg_hip_blocked_encode3d computes -- the rectangles of merged 8x8 blocks, each with ONE record, ONE shift triple and its crushed factor values -- in the same
+ * "LMG3" container, so that decode(blocked_encode_stream(image)) equals the pDecoded plane of `limg_blocked_encode3d_test` bit for bit.  Version 1 streams and their
+ * entry points are unchanged; each decoder refuses the other version.  Layout, little endian, sections 8-byte aligned:
+ *   limg_hip_stream_header, version = 2 | limg_hip_stream_rect[R], creation order | payload (8-byte words)
+ * Header: the struct above with version = LIMG_HIP_STREAM_VERSION_BLOCKED, R in reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], bit 2 of `flags`
+ * (LIMG_HIP_STREAM_FLAG_MERGED) set, blocksX / blocksY as in version 1, totalBytes = 64 + 64 R + 8 payloadWords.
+ * Table: one 64-byte entry per rectangle in creation order (= block-index order = dither-chain order = the order of limg_hip_blocked_regions).  The six vectors are
+ * the rectangle's record (`limg_encode_3d_output` minus avg): the pass-1 fit of a single block that kept it, the re-fit over all its pixels otherwise.  `shift` as in
+ * version 1, escape rule included: factor k of a 4-channel rectangle at shift 8 whose alpha normal (lane 3 of max/mag minus min/offset) is non-zero keeps its raw
+ * 8-bit factor byte and sets bit 24 + k.  ox, oy, rx, ry in 8x8 blocks; every block of the image belongs to exactly one rectangle.
+ * Payload of rectangle r, at `payloadWord`: field A, then B, then C.  The rectangle covers n = wpx * hpx image pixels, wpx = 8 rx and hpx = 8 ry CLIPPED to the image
+ * (a rectangle that holds the last block column of an image with sizeX % 8 != 0 has wpx = 8 rx - 8 + sizeX % 8; likewise hpx).  A field of b = 8 - shift bits per
+ * pixel (b = 8 when escaped; no field at shift 8 without escape) takes ceil(n b / 64) words; pixel (yy, xx) of the rectangle, i = yy * wpx + xx, sits at bit i * b
+ * of the field (bit 0 = least significant bit of the first word's first byte) -- the index the reference's decoder uses (src/limg_decode.h).  Unused high bits of a
+ * field's last word are 0.  A value is the dithered factor >> shift (what pFactorsK holds, >> shift), or the un-dithered factor byte where escaped.
+ * On images of whole blocks n is a multiple of 64: a field is exactly n b / 64 words and every row piece of 8 pixels a run of b bytes. */
+#define LIMG_HIP_STREAM_VERSION_BLOCKED 2u
+#define LIMG_HIP_STREAM_RESERVED_RECTANGLES 0 /* index into limg_hip_stream_header::reserved: the rectangle count R of a version 2 stream */
+#define LIMG_HIP_STREAM_FLAG_MERGED 4u        /* limg_hip_stream_header::flags bit 2: merged-block stream */
+
+typedef struct limg_hip_stream_rect
+{
+  int16_t dirA_min[4], dirA_max[4], dirB_offset[4], dirB_mag[4], dirC_offset[4], dirC_mag[4];
+  uint32_t shift;       /* shiftA | shiftB << 8 | shiftC << 16 | rawEscapeMask << 24 */
+  uint32_t payloadWord; /* first payload word of this rectangle */
+  uint16_t ox, oy, rx, ry; /* origin and size in 8x8 blocks */
+} limg_hip_stream_rect; /* 64 bytes */
+
+/* Worst case (every block its own rectangle): 64 + blocks * 64 + blocks * 192 bytes; 0 where limg_hip_stream_bound is 0 or a dimension exceeds 65535 blocks. */
+size_t limg_hip_blocked_stream_bound(size_t sizeX, size_t sizeY);
+/* The merged-block encoder (same pipeline as limg_hip_blocked_encode3d_device up to its store step, float_mode always EXACT; forced_shift, dither_pcg and
+ * collect_stats are honoured) in a compact mode that stores no plane, followed by a device-side scan over the rectangles' field sizes (payloadWord, header, totalBytes)
+ * and the bit packer.  Argument and alignment rules of limg_hip_encode_stream_device: DEVICE pointers, pStream 16-byte aligned, capacity >= the bound; pBytes (host,
+ * may be NULL) makes the call wait for the stream.  limg_hip_blocked_regions / _timing / _kernel_timing describe this encode afterwards; the scan + pack kernels count
+ * into slot [3] of limg_hip_blocked_kernel_timing.  Context memory beyond that of limg_hip_blocked_encode3d_device: 4 bytes per block. */
+limg_hip_result limg_hip_blocked_encode_stream_device(limg_hip_context *pCtx, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream,
+                                                      size_t capacity, size_t *pBytes, uint32_t errorFactor, int fastBitCrushing, void *stream);
+/* DEVICE pointers (16-byte aligned), asynchronous.  Two launches: the rectangle table is validated and scattered into a block -> rectangle map (every rectangle inside
+ * the block grid, every block covered exactly once, R <= blocks, every payload offset inside the payload), then a raster decode.  A stream that fails any of it is
+ * refused as a whole -- pOut is not written -- and limg_hip_check_device_status reports limg_hip_error_InvalidParameter, once.  sizeX / sizeY must match the header. */
+limg_hip_result limg_hip_blocked_decode_stream_device(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, uint32_t *pOut, size_t sizeX, size_t sizeY,
+                                                      void *stream);
+/* HOST-pointer variants (blocking, under the context's mutex; *pBytes / limg_hip_error_OutOfBounds as limg_hip_encode_stream). */
+limg_hip_result limg_hip_blocked_encode_stream(limg_hip_context *pCtx, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                               size_t *pBytes, uint32_t errorFactor, int fastBitCrushing);
+limg_hip_result limg_hip_blocked_decode_stream(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, uint32_t *pOut, size_t outPixels);
+/* The version 2 stream of the context's LAST merged-block encode -- limg_hip_blocked_encode3d* (the planes) or limg_hip_blocked_encode_stream* -- without encoding
+ * again: that encode's rectangles, records, shift words, factor and noise bytes stay in the context until its next merged-block encode, and this call runs the scan and the
+ * packer over them (what tools/limg_hip_cli.cpp --blocked-stream writes next to the planes).  HOST pointer, blocking, under the context's mutex; the caller keeps other
+ * threads from encoding on the context in between.  limg_hip_error_InvalidParameter if there is no such encode; *pBytes / limg_hip_error_OutOfBounds as above. */
+limg_hip_result limg_hip_blocked_last_stream(limg_hip_context *pCtx, uint8_t *pStream, size_t capacity, size_t *pBytes);
+/* Host-only: validates a version 2 header (first 64 bytes suffice) and reports the image shape and the rectangle count.  limg_hip_stream_info refuses version 2. */
+limg_hip_result limg_hip_blocked_stream_info(const uint8_t *pStream, size_t streamBytes, size_t *pSizeX, size_t *pSizeY, int *pHasAlpha, size_t *pTotalBytes,
+                                             size_t *pRectangles);
 
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ---------------------------------------------------------------------------------
  * The reference's only parallelism is row strips over a std::thread pool (src/limg.cpp:2105-2138); across GPUs the same strips

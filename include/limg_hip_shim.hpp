@@ -178,10 +178,12 @@ inline limg_result limg_encode(const uint32_t *pIn, const size_t sizeX, const si
                                              fastBitCrushing ? 1 : 0);
 }
 
+// either version of the stream: version 1 (limg_encode) or version 2 (limg_blocked_encode)
 inline limg_result limg_decode_info(const uint8_t *pIn, const size_t size, size_t *pSizeX, size_t *pSizeY, bool *pHasAlpha)
 {
   int alpha = 0;
-  const limg_result r = (limg_result)limg_hip_stream_info(pIn, size, pSizeX, pSizeY, &alpha, nullptr);
+  limg_result r = (limg_result)limg_hip_stream_info(pIn, size, pSizeX, pSizeY, &alpha, nullptr);
+  if (r != limg_success) r = (limg_result)limg_hip_blocked_stream_info(pIn, size, pSizeX, pSizeY, &alpha, nullptr, nullptr);
   if (pHasAlpha) *pHasAlpha = alpha != 0;
   return r;
 }
@@ -191,6 +193,33 @@ inline limg_result limg_decode(const uint8_t *pIn, const size_t size, uint32_t *
   limg_hip_context *c = limg_hip_shim::context();
   if (!c) return limg_error_Generic;
   return (limg_result)limg_hip_decode_stream(c, pIn, size, pOut, outPixelCapacity);
+}
+
+// `limg_blocked_encode` / `limg_blocked_decode`: the same pair for what limg_blocked_encode3d_test computes (version 2 of the stream: rectangles of merged blocks):
+// limg_blocked_decode(limg_blocked_encode(image)) == the pDecoded plane of limg_blocked_encode3d_test, bit for bit.
+inline size_t limg_blocked_encode_bound(const size_t sizeX, const size_t sizeY) { return limg_hip_blocked_stream_bound(sizeX, sizeY); }
+
+inline limg_result limg_blocked_encode(const uint32_t *pIn, const size_t sizeX, const size_t sizeY, const bool hasAlpha, uint8_t *pOut, const size_t outCapacity, size_t *pOutSize,
+                                       const uint32_t errorFactor = 100, const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  return (limg_result)limg_hip_blocked_encode_stream(c, pIn, sizeX, sizeY, hasAlpha ? 1 : 0, pOut, outCapacity, pOutSize, errorFactor, fastBitCrushing ? 1 : 0);
+}
+
+// the stream of the LAST limg_blocked_encode3d_test / limg_blocked_encode of this process's context, without encoding again (single-threaded callers)
+inline limg_result limg_blocked_last_encode(uint8_t *pOut, const size_t outCapacity, size_t *pOutSize)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  return (limg_result)limg_hip_blocked_last_stream(c, pOut, outCapacity, pOutSize);
+}
+
+inline limg_result limg_blocked_decode(const uint8_t *pIn, const size_t size, uint32_t *pOut, const size_t outPixelCapacity)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  return (limg_result)limg_hip_blocked_decode_stream(c, pIn, size, pOut, outPixelCapacity);
 }
 
 #endif // LIMG_HIP_SHIM_HPP

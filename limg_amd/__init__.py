@@ -28,6 +28,8 @@ ABI_SYMBOLS = (
     "limg_hip_host_noise_table", "limg_hip_noise_table_device", "limg_hip_host_chain_call", "limg_hip_host_chain_checkpoints", "limg_hip_host_dense_checkpoints", "limg_hip_host_partition", "limg_hip_check_device_status",
     "limg_hip_stream_bound", "limg_hip_encode_stream_device", "limg_hip_decode_stream_device", "limg_hip_encode_stream", "limg_hip_decode_stream",
     "limg_hip_stream_info",
+    "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
+    "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
     "limg_hip_blocked_encode3d", "limg_hip_blocked_encode3d_device", "limg_hip_blocked_regions", "limg_hip_blocked_timing", "limg_hip_blocked_kernel_timing", "limg_hip_blocked_match_bits", "limg_hip_host_blocked_matches",
     "limg_hip_host_blocked_merge", "limg_hip_host_blocked_match_words", "limg_hip_host_blocked_match_bits",
     "limg_hip_comm_unique_id", "limg_hip_comm_init", "limg_hip_comm_destroy", "limg_hip_comm_info", "limg_hip_gather_stream", "limg_hip_encode3d_single_chain_device",
@@ -46,6 +48,12 @@ STREAM_HEADER_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u4"), ("sizeX", 
                                 ("blocksX", "<u4"), ("blocksY", "<u4"), ("payloadWords", "<u8"), ("totalBytes", "<u8"), ("flags", "<u4"), ("reserved", "<u4", 3)])
 STREAM_BLOCK_DTYPE = np.dtype([("dirA_min", "<i2", 4), ("dirA_max", "<i2", 4), ("dirB_offset", "<i2", 4), ("dirB_mag", "<i2", 4), ("dirC_offset", "<i2", 4),
                                ("dirC_mag", "<i2", 4), ("shift", "<u4"), ("payloadWord", "<u4")])
+
+# version 2 (merged-block) stream: the header is STREAM_HEADER_DTYPE with version = 2, reserved[0] = rectangle count, flags bit 2
+STREAM_VERSION_BLOCKED = 2
+STREAM_FLAG_MERGED = 4
+STREAM_RECT_DTYPE = np.dtype([("dirA_min", "<i2", 4), ("dirA_max", "<i2", 4), ("dirB_offset", "<i2", 4), ("dirB_mag", "<i2", 4), ("dirC_offset", "<i2", 4),
+                              ("dirC_mag", "<i2", 4), ("shift", "<u4"), ("payloadWord", "<u4"), ("ox", "<u2"), ("oy", "<u2"), ("rx", "<u2"), ("ry", "<u2")])
 
 RECORD_DTYPE = np.dtype([("avg", "<f4", 4), ("dirA_min", "<i2", 4), ("dirA_max", "<i2", 4), ("dirB_offset", "<i2", 4),
                          ("dirB_mag", "<i2", 4), ("dirC_offset", "<i2", 4), ("dirC_mag", "<i2", 4)])
@@ -175,6 +183,22 @@ def load_library(path=None):
     L.limg_hip_decode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     L.limg_hip_stream_info.restype = C.c_int
     L.limg_hip_stream_info.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    L.limg_hip_blocked_stream_bound.restype = C.c_size_t
+    L.limg_hip_blocked_stream_bound.argtypes = [C.c_size_t, C.c_size_t]
+    L.limg_hip_blocked_encode_stream_device.restype = C.c_int
+    L.limg_hip_blocked_encode_stream_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_uint32, C.c_int,
+                                                        C.c_void_p]
+    L.limg_hip_blocked_decode_stream_device.restype = C.c_int
+    L.limg_hip_blocked_decode_stream_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    L.limg_hip_blocked_encode_stream.restype = C.c_int
+    L.limg_hip_blocked_encode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_uint32, C.c_int]
+    L.limg_hip_blocked_decode_stream.restype = C.c_int
+    L.limg_hip_blocked_decode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.limg_hip_blocked_last_stream.restype = C.c_int
+    L.limg_hip_blocked_last_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.limg_hip_blocked_stream_info.restype = C.c_int
+    L.limg_hip_blocked_stream_info.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t),
+                                               C.POINTER(C.c_size_t)]
     L.limg_hip_comm_unique_id.restype = C.c_int
     L.limg_hip_comm_unique_id.argtypes = [C.c_void_p]
     L.limg_hip_comm_init.restype = C.c_int
@@ -213,6 +237,20 @@ def stream_info(stream, lib=None):
     sx, sy, tb, ha = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int(0)
     _check(lib.limg_hip_stream_info(_np_ptr(stream), stream.size, C.byref(sx), C.byref(sy), C.byref(ha), C.byref(tb)), "limg_hip_stream_info")
     return sx.value, sy.value, bool(ha.value), tb.value
+
+
+def blocked_stream_bound(w, h, lib=None):
+    """Worst-case size of a version 2 (merged-block) stream; host only."""
+    return (lib or load_library()).limg_hip_blocked_stream_bound(w, h)
+
+
+def blocked_stream_info(stream, lib=None):
+    """(sizeX, sizeY, hasAlpha, totalBytes, rectangles) of a version 2 (merged-block) stream held in a numpy uint8 array (host-only, no GPU touched)."""
+    lib = lib or load_library()
+    stream = np.ascontiguousarray(stream, dtype=np.uint8)
+    sx, sy, tb, nr, ha = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+    _check(lib.limg_hip_blocked_stream_info(_np_ptr(stream), stream.size, C.byref(sx), C.byref(sy), C.byref(ha), C.byref(tb), C.byref(nr)), "limg_hip_blocked_stream_info")
+    return sx.value, sy.value, bool(ha.value), tb.value, nr.value
 
 
 def host_gather_offsets(sizes, lib=None):
@@ -503,6 +541,60 @@ class LimgHip:
             out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
         _check(self.lib.limg_hip_decode_stream_device(self.ctx, C.c_void_p(stream.data_ptr()), int(nbytes), C.c_void_p(out.data_ptr()), w, h, self._stream()),
                "limg_hip_decode_stream_device")
+        return out
+
+    # ---- version 2 stream: what the merged-block encoder produced ----------------------------------------------------------------------
+    def blocked_stream_bound(self, w, h):
+        return self.lib.limg_hip_blocked_stream_bound(w, h)
+
+    def blocked_stream_info(self, stream):
+        return blocked_stream_info(stream, self.lib)
+
+    def blocked_encode_stream(self, img, has_alpha, error_factor=100, fast=True):
+        """host uint32 image -> version 2 stream bytes (numpy uint8); blocked_regions() / blocked_timing() describe this encode afterwards"""
+        img = np.ascontiguousarray(img, dtype=np.uint32)
+        h, w = img.shape
+        cap = self.blocked_stream_bound(w, h)
+        out = np.zeros(cap, dtype=np.uint8)
+        n = C.c_size_t(0)
+        _check(self.lib.limg_hip_blocked_encode_stream(self.ctx, _np_ptr(img), w, h, int(has_alpha), _np_ptr(out), cap, C.byref(n), error_factor, int(fast)),
+               "limg_hip_blocked_encode_stream")
+        return out[:n.value].copy()
+
+    def blocked_last_stream(self, w, h):
+        """the version 2 stream of this context's last merged-block encode (planes or stream), of a w x h image, without encoding again"""
+        cap = self.blocked_stream_bound(w, h)
+        out = np.zeros(cap, dtype=np.uint8)
+        n = C.c_size_t(0)
+        _check(self.lib.limg_hip_blocked_last_stream(self.ctx, _np_ptr(out), cap, C.byref(n)), "limg_hip_blocked_last_stream")
+        return out[:n.value].copy()
+
+    def blocked_decode_stream(self, stream):
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        w, h = blocked_stream_info(stream, self.lib)[:2]
+        out = np.zeros((h, w), dtype=np.uint32)
+        _check(self.lib.limg_hip_blocked_decode_stream(self.ctx, _np_ptr(stream), stream.size, _np_ptr(out), out.size), "limg_hip_blocked_decode_stream")
+        return out
+
+    def blocked_encode_stream_device(self, img, has_alpha, out=None, error_factor=100, fast=True, want_size=True):
+        """img: torch int32 CUDA (h, w) -> (torch uint8 CUDA stream buffer of worst-case size, bytes used or None)"""
+        import torch
+        h, w = img.shape
+        cap = self.blocked_stream_bound(w, h)
+        if out is None:
+            out = torch.empty(cap, dtype=torch.uint8, device=img.device)
+        n = C.c_size_t(0)
+        _check(self.lib.limg_hip_blocked_encode_stream_device(self.ctx, C.c_void_p(img.data_ptr()), w, h, int(has_alpha), C.c_void_p(out.data_ptr()), out.numel(),
+                                                              C.byref(n) if want_size else None, error_factor, int(fast), self._stream()),
+               "limg_hip_blocked_encode_stream_device")
+        return out, (n.value if want_size else None)
+
+    def blocked_decode_stream_device(self, stream, nbytes, w, h, out=None):
+        import torch
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
+        _check(self.lib.limg_hip_blocked_decode_stream_device(self.ctx, C.c_void_p(stream.data_ptr()), int(nbytes), C.c_void_p(out.data_ptr()), w, h, self._stream()),
+               "limg_hip_blocked_decode_stream_device")
         return out
 
     def check(self):

@@ -112,6 +112,7 @@ extern "C"
     if (c->storeStream) (void)hipStreamDestroy(c->storeStream);
     for (hipEvent_t e : c->workEvents) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->workTimers) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->packTimers) (void)hipEventDestroy(e);
     if (c->copyStream) (void)hipStreamDestroy(c->copyStream);
     for (hipEvent_t e : c->bandEvents) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);

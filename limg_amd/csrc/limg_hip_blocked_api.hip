@@ -43,6 +43,7 @@ namespace
     size_t sizeX, sizeY, blocks, maxCalls;
     uint32_t blocksX, blocksY, bandRows, nBands;
     int channels; bool pcg; // pcg: limg_hip_options.dither_pcg
+    bool compact;           // no plane is stored: the stream packer (limg_hip_blocked_stream_api.hip) takes the rectangles from the context's buffers
     BlockedParams bp;
     hipEvent_t *frontTimers; // begin of pass 1, its end = begin of the similarity kernels, their end
     // the context's pinned staging, and per dither call its chain value, noise offset and pixel count on the host (call*) and on the device (dCall*)
@@ -55,8 +56,9 @@ namespace
 
   // Set-up: the shape, and every field of BlockedParams that does not point into the context's buffers.
   limg_hip_result set_up(BlockedJob &j, limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_blocked_encode3d_info &info,
-                         uint32_t errorFactor, int fastBitCrushing, void *stream)
+                         uint32_t errorFactor, int fastBitCrushing, void *stream, bool compact)
   {
+    j.compact = compact;
     j.c = c; j.s = (hipStream_t)stream; j.sizeX = sizeX; j.sizeY = sizeY; j.channels = hasAlpha ? 4 : 3; j.pcg = c->opt.dither_pcg != 0;
     j.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); j.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
     j.blocks = (size_t)j.blocksX * j.blocksY; j.maxCalls = 3 * j.blocks;
@@ -312,7 +314,7 @@ namespace
         if (ok) { launch_noise_expand_calls((uint8_t *)c->bNoise.p, j.dCallState + call0, j.dCallOff + call0, j.dCallPx + call0, nc, j.pcg, ss); ok = hipGetLastError() == hipSuccess; }
       }
       ok = ok && hipMemcpyAsync((unsigned long long *)c->bNoiseBase.p + pending.r0, j.noiseBase + pending.r0, (pending.r1 - pending.r0) * 8, hipMemcpyHostToDevice, ss) == hipSuccess;
-      if (ok) { launch_blocked_store(params_of(pending), ss); ok = hipGetLastError() == hipSuccess; }
+      if (ok && !j.compact) { launch_blocked_store(params_of(pending), ss); ok = hipGetLastError() == hipSuccess; }
       if (ok && hipEventRecord(c->workTimers[4 * pending.ev + 3], ss) == hipSuccess) storeTimed[pending.ev] = true;
       const clk::time_point w3 = clk::now();
       busy[0] += ms(w0, w1); busy[1] += ms(w1, w2); busy[2] += ms(w2, w3);
@@ -409,12 +411,23 @@ extern "C"
                                                    uint32_t errorFactor, int fastBitCrushing, void *stream)
   {
     if (!c || !pIn || !pInfo || !has_written_planes(*pInfo)) return limg_hip_error_ArgumentNull;
+    return blocked_encode_device(c, pIn, sizeX, sizeY, hasAlpha, pInfo, errorFactor, fastBitCrushing, (hipStream_t)stream);
+  }
+}
+
+namespace limg_hip
+{
+  limg_hip_result blocked_encode_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_blocked_encode3d_info *pInfo,
+                                        uint32_t errorFactor, int fastBitCrushing, hipStream_t stream)
+  {
+    const limg_hip_blocked_encode3d_info noPlanes = {};
     if (sizeX == 0 || sizeY == 0 || sizeX > 0x7FFFFFF8ull || sizeY > 0x7FFFFFF8ull || sizeX * sizeY > 0x60000000ull) return limg_hip_error_InvalidParameter;
     HIP_TRY(hipSetDevice(c->device));
     const clk::time_point t0 = clk::now();
     BlockedJob j; limg_hip_result r;
-    if ((r = set_up(j, c, pIn, sizeX, sizeY, hasAlpha, *pInfo, errorFactor, fastBitCrushing, stream)) != limg_hip_success) return r;
+    if ((r = set_up(j, c, pIn, sizeX, sizeY, hasAlpha, pInfo ? *pInfo : noPlanes, errorFactor, fastBitCrushing, stream, pInfo == nullptr)) != limg_hip_success) return r;
     if ((r = ensure_resources(j)) != limg_hip_success) return r;
+    c->blockedScratchCap = j.bp.scratchCap; c->packTimed = false; c->lastBlocked.valid = false;
     // pass 1 (src/limg.cpp:1088-1119): every block's own fit = the 8x8 path's E step, records only
     EncodeExtra x1; x1.fitOnly = true;
     HIP_TRY(hipEventRecord(j.frontTimers[0], j.s));
@@ -436,8 +449,15 @@ extern "C"
     if (merge.failed) return limg_hip_error_MemoryAllocationFailure;
     if (merge.bandError) return limg_hip_error_Generic;
     if (worker.result == limg_hip_success && c->opt.collect_stats) collect_stats(j);
+    c->lastBlocked.sizeX = sizeX; c->lastBlocked.sizeY = sizeY; c->lastBlocked.channels = j.channels; c->lastBlocked.errorFactor = errorFactor;
+    c->lastBlocked.flags = (fastBitCrushing ? 1u : 0u) | (j.pcg ? 2u : 0u);
+    c->lastBlocked.valid = worker.result == limg_hip_success;
     return worker.result;
   }
+}
+
+extern "C"
+{
 
   limg_hip_result limg_hip_blocked_regions(limg_hip_context *c, limg_hip_region *pRegions, size_t capacity, size_t *pCount)
   {
@@ -466,6 +486,12 @@ extern "C"
   limg_hip_result limg_hip_blocked_kernel_timing(limg_hip_context *c, double *pMs4)
   {
     if (!c || !pMs4) return limg_hip_error_ArgumentNull;
+    if (c->packTimed)
+    { // a stream encode: its scan + pack kernels were enqueued behind the pipeline (limg_hip_blocked_stream_api.hip) and belong to slot [3]
+      float t = 0;
+      if (hipEventSynchronize(c->packTimers[1]) == hipSuccess && hipEventElapsedTime(&t, c->packTimers[0], c->packTimers[1]) == hipSuccess) c->blockedKernelMs[3] += t;
+      c->packTimed = false;
+    }
     memcpy(pMs4, c->blockedKernelMs, sizeof(c->blockedKernelMs));
     return limg_hip_success;
   }

@@ -1,0 +1,508 @@
+// limg_hip_blocked_stream.hip -- version 2 of the "LMG3" stream: the merged-block encoder's rectangles (format: include/limg_hip.h).
+//
+// Pack, after a compact-mode merged-block encode (blocked_encode_device with no planes), from what that leaves in the context: per rectangle its descriptor, record and
+// shift word, its pre-dither factor bytes and noise bytes, both region-major (pixel i = yy * wpx + xx of the rectangle at byte i: the order the stream wants).
+//   k_bstream_sizes<false>  per tile of 256 rectangles: payload words and 64-pixel runs
+//   k_bstream_scan          one workgroup: exclusive prefix over the tiles, the header
+//   k_bstream_sizes<true>   per rectangle: its first payload word and first run, its 64-byte table entry
+//   k_bstream_pack          lane = one RUN: 64 consecutive pixels of one rectangle, its three fields one after the other.  Rectangles are wildly uneven (a single
+//                           block up to thousands), runs are not: a lane finds its rectangle by bisection over the runs' prefix, reads 64 factor bytes (and 64 noise
+//                           bytes where the field is dithered) with four 16-byte loads, dithers and crushes them (k_blocked_store's arithmetic), squeezes every 8
+//                           values into b bytes with the mask-and-shift steps of k_stream_pack_strips and stores b 8-byte words.  Runs that are short (the tail of a
+//                           rectangle on an image with partial blocks) or not 16-byte aligned gather their bytes one by one -- same bytes out.
+// Decode:
+//   k_bstream_map           validates the table and scatters it into a block -> rectangle map: 64 rectangles per wave step, a lane claims the blocks of a small
+//                           rectangle itself (atomicCAS on ~0), the wave claims a large one together; the claimed blocks are counted
+//   k_bstream_decode        refuses unless every block was claimed and nothing was flagged; then lane = (block j = lane & 7, block row r = lane >> 3) over units of 8
+//                           consecutive blocks: the lane's 8 pixels are the bit run at ((y - 8 oy) * wpx + (x - 8 ox)) * b of each field of the block's rectangle; the
+//                           integer decode is k_blocked_store's (a16); a wave's stores are 8 row pieces of 256 contiguous bytes.
+// Nothing here reads through an offset the map kernel has not checked against the stream's size.
+#include "limg_hip_internal.h"
+
+namespace limg_hip
+{
+  namespace
+  {
+    constexpr int kRectTile = 256;
+    constexpr int kRectEntry = 64;
+    constexpr uint32_t kNoRect = 0xFFFFFFFFu;
+
+    __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+    __device__ __forceinline__ int mad_i24(int a, int b, int c) { int r; asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
+    // (1 << s) + bias(s), src/limg_bit_crush_simd.h:611-619 / src/limg_decode.h:172-178
+    __device__ __forceinline__ uint32_t shift_mul(uint32_t s) { return s < 4 ? (1u << s) : (s == 4 ? 17u : (s == 5 ? 36u : (s == 6 ? 85u : (s == 7 ? 255u : 256u)))); }
+
+    // pixels of a rectangle: 8 rx x 8 ry clipped to the image (src/limg.cpp:1722-1740)
+    __device__ __forceinline__ uint32_t rect_pixels(uint32_t sizeX, uint32_t sizeY, uint32_t blocksX, uint32_t blocksY, uint32_t ox, uint32_t oy, uint32_t rx, uint32_t ry, uint32_t &wpx)
+    {
+      uint32_t hpx = ry * kBlock;
+      wpx = rx * kBlock;
+      if (ox + rx == blocksX && (sizeX % kBlock)) wpx = wpx - kBlock + sizeX % kBlock;
+      if (oy + ry == blocksY && (sizeY % kBlock)) hpx = hpx - kBlock + sizeY % kBlock;
+      return wpx * hpx;
+    }
+
+    // bits per pixel of the three fields + raw-escape mask (bA | bB << 8 | bC << 16 | rawMask << 24) from the shift triple and the alpha lanes of the record's vectors
+    __device__ __forceinline__ uint32_t field_bits(uint32_t shiftWord, uint32_t alphaVaries3, uint32_t channels)
+    {
+      uint32_t r = 0;
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+      {
+        const uint32_t s = (shiftWord >> (8 * k)) & 0xFFu;
+        uint32_t b = s >= 8u ? 0u : 8u - s;
+        if (s >= 8u && channels == 4u && ((alphaVaries3 >> k) & 1u)) { b = 8u; r |= 1u << (24 + k); }
+        r |= b << (8 * k);
+      }
+      return r;
+    }
+    // the same from a table entry's shift word, whose bits 24..26 say which factors are escaped
+    __device__ __forceinline__ uint32_t entry_bits(uint32_t sw)
+    {
+      uint32_t r = 0;
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+      {
+        const uint32_t s = (sw >> (8 * k)) & 0xFFu;
+        r |= (s >= 8u ? (((sw >> (24 + k)) & 1u) ? 8u : 0u) : 8u - s) << (8 * k);
+      }
+      return r;
+    }
+    __device__ __forceinline__ uint32_t field_words(uint32_t n, uint32_t b) { return (uint32_t)(((unsigned long long)n * b + 63ull) >> 6); }
+    __device__ __forceinline__ uint32_t rect_words(uint32_t n, uint32_t bits) { return field_words(n, bits & 0xFFu) + field_words(n, (bits >> 8) & 0xFFu) + field_words(n, (bits >> 16) & 0xFFu); }
+
+    // ---- pack ------------------------------------------------------------------------------------------------------------------------
+    struct RectSize { uint32_t bits, words, runs, sw; };
+    __device__ __forceinline__ RectSize rect_size(const BlockedStreamParams &p, uint32_t r)
+    {
+      const RegionDesc R = p.regions[r];
+      const uint4 *rp = reinterpret_cast<const uint4 *>(p.out + r) + 1; // skip avg[4]: {dirA_min, dirA_max}, {dirB_offset, dirB_mag}, {dirC_offset, dirC_mag}
+      const uint4 v0 = rp[0], v1 = rp[1], v2 = rp[2];
+      const uint32_t varies = ((v0.y >> 16) != (v0.w >> 16) ? 1u : 0u) | ((v1.y >> 16) != (v1.w >> 16) ? 2u : 0u) | ((v2.y >> 16) != (v2.w >> 16) ? 4u : 0u);
+      RectSize o;
+      o.sw = p.out[r].shiftWord & 0xFFFFFFu;
+      o.bits = field_bits(o.sw, varies, p.channels);
+      uint32_t wpx;
+      const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, R.ox, R.oy, R.rx, R.ry, wpx);
+      o.words = rect_words(n, o.bits);
+      o.runs = (n + 63u) >> 6;
+      return o;
+    }
+
+    // ENTRIES = false: the tile's totals.  ENTRIES = true (after the scan): every rectangle's first payload word and first run, and its table entry.
+    template <bool ENTRIES>
+    __global__ __launch_bounds__(kRectTile) void k_bstream_sizes(const BlockedStreamParams p)
+    {
+      __shared__ uint32_t sWords[4], sRuns[4];
+      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+      const uint32_t r = blockIdx.x * kRectTile + tid;
+      RectSize z = { 0, 0, 0, 0 };
+      if (r < p.nRegions) z = rect_size(p, r);
+      uint32_t iw = z.words, ir = z.runs;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1)
+      {
+        const uint32_t uw = (uint32_t)__shfl_up((int)iw, off, 64), ur = (uint32_t)__shfl_up((int)ir, off, 64);
+        if (lane >= off) { iw += uw; ir += ur; }
+      }
+      if (lane == 63) { sWords[wave] = iw; sRuns[wave] = ir; }
+      __syncthreads();
+      if (!ENTRIES)
+      {
+        if (tid == 0) { p.tiles[2 * blockIdx.x] = sWords[0] + sWords[1] + sWords[2] + sWords[3]; p.tiles[2 * blockIdx.x + 1] = sRuns[0] + sRuns[1] + sRuns[2] + sRuns[3]; }
+        return;
+      }
+      uint32_t word = p.tiles[2 * blockIdx.x] + iw - z.words, run = p.tiles[2 * blockIdx.x + 1] + ir - z.runs;
+      for (int w = 0; w < wave; w++) { word += sWords[w]; run += sRuns[w]; }
+      if (r >= p.nRegions) return;
+      p.units[r] = run;
+      if (r + 1 == p.nRegions) p.units[r + 1] = run + z.runs;
+      const RegionDesc R = p.regions[r];
+      const uint4 *rp = reinterpret_cast<const uint4 *>(p.out + r) + 1;
+      uint4 *e = reinterpret_cast<uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)r * kRectEntry);
+      e[0] = rp[0]; e[1] = rp[1]; e[2] = rp[2];
+      e[3] = make_uint4(z.sw | (z.bits & 0xFF000000u), word, R.ox | (R.oy << 16), R.rx | (R.ry << 16));
+    }
+
+    // exclusive prefix of the tile totals in place (one workgroup) + the header
+    __global__ __launch_bounds__(1024) void k_bstream_scan(const BlockedStreamParams p)
+    {
+      __shared__ unsigned long long sW[16], sR[16];
+      __shared__ unsigned long long sCarryW, sCarryR;
+      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+      if (tid == 0) { sCarryW = 0; sCarryR = 0; }
+      __syncthreads();
+      for (uint32_t base = 0; base < p.nTiles; base += 1024)
+      {
+        const uint32_t i = base + tid;
+        const unsigned long long vw = i < p.nTiles ? p.tiles[2 * i] : 0u, vr = i < p.nTiles ? p.tiles[2 * i + 1] : 0u;
+        unsigned long long iw = vw, ir = vr;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1)
+        {
+          const unsigned long long uw = (unsigned long long)__shfl_up((long long)iw, off, 64), ur = (unsigned long long)__shfl_up((long long)ir, off, 64);
+          if (lane >= off) { iw += uw; ir += ur; }
+        }
+        if (lane == 63) { sW[wave] = iw; sR[wave] = ir; }
+        __syncthreads();
+        unsigned long long pw = sCarryW, pr = sCarryR;
+        for (int w = 0; w < wave; w++) { pw += sW[w]; pr += sR[w]; }
+        // payloadWord is 32 bits: the host refuses images whose worst-case payload would not fit (limg_hip_blocked_stream_bound); runs <= blocks
+        if (i < p.nTiles) { p.tiles[2 * i] = (uint32_t)(pw + iw - vw); p.tiles[2 * i + 1] = (uint32_t)(pr + ir - vr); }
+        __syncthreads();
+        if (tid == 1023) { sCarryW = pw + iw; sCarryR = pr + ir; }
+        __syncthreads();
+      }
+      if (tid == 0)
+      {
+        limg_hip_stream_header h;
+        h.magic = LIMG_HIP_STREAM_MAGIC; h.version = LIMG_HIP_STREAM_VERSION_BLOCKED;
+        h.sizeX = p.sizeX; h.sizeY = p.sizeY; h.channels = p.channels; h.errorFactor = p.errorFactor;
+        h.blocksX = p.blocksX; h.blocksY = p.blocksY;
+        h.payloadWords = sCarryW;
+        h.totalBytes = sizeof(limg_hip_stream_header) + (unsigned long long)p.nRegions * kRectEntry + sCarryW * 8ull;
+        h.flags = p.flags | LIMG_HIP_STREAM_FLAG_MERGED; h.reserved[0] = p.nRegions; h.reserved[1] = h.reserved[2] = 0;
+        *reinterpret_cast<limg_hip_stream_header *>(p.stream) = h;
+      }
+    }
+
+    // 64 bytes of a region-major array into 16 dwords: four 16-byte loads where the run is whole and aligned, else byte by byte (absent pixels read as 0)
+    __device__ __forceinline__ void load_run(const uint8_t *src, uint32_t count, uint32_t v[16])
+    {
+      if (count == 64u && (reinterpret_cast<uintptr_t>(src) & 15u) == 0)
+      {
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+        {
+          const uint4 t = reinterpret_cast<const uint4 *>(src)[q];
+          v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+        }
+        return;
+      }
+#pragma unroll
+      for (int q = 0; q < 16; q++)
+      {
+        uint32_t w = 0;
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+          if ((uint32_t)(4 * q + t) < count) w |= (uint32_t)src[4 * q + t] << (8 * t);
+        v[q] = w;
+      }
+    }
+
+    // 64 values of B bits, one per byte of v -> B words at dst (only the first `words` of them: a short run ends early)
+    template <int B>
+    __device__ __forceinline__ void squeeze_run(const uint32_t v[16], unsigned long long *dst, uint32_t words)
+    {
+      constexpr uint32_t m1 = (1u << B) - 1u, mPair = (m1 * 0x00010001u) << B;
+      unsigned long long w[B];
+#pragma unroll
+      for (int i = 0; i < B; i++) w[i] = 0;
+#pragma unroll
+      for (int r = 0; r < 8; r++)
+      { // 8 values -> 8 B bits = B bytes, at byte r B of the run's words (k_stream_pack_strips' squeeze_row, on values that sit in the LOW bits of their bytes)
+        uint32_t z[2];
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+        {
+          const uint32_t x = v[2 * r + h];
+          const uint32_t y = ((x >> (8 - B)) & mPair) | (x & 0x00FF00FFu & (m1 * 0x00010001u)); // v0 | v1 << B in the low half, v2 | v3 << B in the high half
+          z[h] = (y & 0xFFFFu) | ((y >> 16) << (2 * B));
+        }
+        const unsigned long long row = (unsigned long long)z[0] | ((unsigned long long)z[1] << (4 * B));
+        constexpr int kBits = 8 * B;
+        const int pos = r * kBits, idx = pos >> 6, sh = pos & 63;
+        w[idx] |= row << sh;
+        if (sh + kBits > 64) w[idx + 1] |= row >> (64 - sh);
+      }
+#pragma unroll
+      for (int i = 0; i < B; i++)
+        if ((uint32_t)i < words) dst[i] = w[i];
+    }
+
+    __global__ __launch_bounds__(256) void k_bstream_pack(const BlockedStreamParams p)
+    {
+      const uint32_t nRuns = p.units[p.nRegions];
+      unsigned long long *const payload = reinterpret_cast<unsigned long long *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)p.nRegions * kRectEntry);
+      for (uint32_t u = blockIdx.x * 256u + threadIdx.x; u < nRuns; u += gridDim.x * 256u)
+      {
+        // the rectangle of run u: the last r with units[r] <= u
+        uint32_t lo = 0, hi = p.nRegions - 1u;
+        while (lo < hi)
+        {
+          const uint32_t mid = (lo + hi + 1u) >> 1;
+          if (p.units[mid] <= u) lo = mid; else hi = mid - 1u;
+        }
+        const uint32_t r = lo, run = u - p.units[r];
+        const RegionDesc R = p.regions[r];
+        const uint4 e3 = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)r * kRectEntry)[3]; // (k_bstream_sizes<true> wrote it)
+        const uint32_t sw = e3.x, bits = entry_bits(sw);
+        uint32_t wpx;
+        const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, R.ox, R.oy, R.rx, R.ry, wpx);
+        const uint32_t i0 = run * 64u, count = min(64u, n - i0);
+        const uint8_t *nz = p.noise + p.noiseBase[r]; // the rectangle's dither calls back to back in A, B, C order, n bytes each
+        unsigned long long *field = payload + e3.y;
+#pragma unroll 1
+        for (int k = 0; k < 3; k++)
+        {
+          const uint32_t s = (sw >> (8 * k)) & 0xFFu, b = (bits >> (8 * k)) & 0xFFu;
+          const bool dithered = s != 0u && s < 8u;
+          const uint8_t *noise = nz;
+          if (dithered) nz += n;
+          if (b == 0u) continue;
+          uint32_t v[16];
+          load_run(p.scratchFac + (size_t)k * p.scratchCap + R.scratch + i0, count, v);
+          if (dithered)
+          { // src/limg.cpp:824-879 as k_blocked_store applies it: (noise & ditherSize) - ditherOffset, add, clamp, shift
+            uint32_t z[16];
+            load_run(noise + i0, count, z);
+            const int half = (int)(1u << (s - 1u));
+            const uint32_t m = (1u << s) - 1u;
+#pragma unroll
+            for (int q = 0; q < 16; q++)
+            {
+              uint32_t o = 0;
+#pragma unroll
+              for (int t = 0; t < 4; t++)
+              {
+                int x = (int)((v[q] >> (8 * t)) & 0xFFu) + ((int)((z[q] >> (8 * t)) & m) - half);
+                x = x < 0 ? 0 : (x > 255 ? 255 : x);
+                o |= ((uint32_t)x >> s) << (8 * t);
+              }
+              v[q] = o;
+            }
+            // (pixels beyond the rectangle's end read as factor 0, noise 0: 0 - half clamps to 0, so their bits stay 0)
+          }
+          unsigned long long *dst = field + (size_t)run * b;
+          const uint32_t words = field_words(count, b);
+          switch (b)
+          {
+          case 1: squeeze_run<1>(v, dst, words); break;
+          case 2: squeeze_run<2>(v, dst, words); break;
+          case 3: squeeze_run<3>(v, dst, words); break;
+          case 4: squeeze_run<4>(v, dst, words); break;
+          case 5: squeeze_run<5>(v, dst, words); break;
+          case 6: squeeze_run<6>(v, dst, words); break;
+          case 7: squeeze_run<7>(v, dst, words); break;
+          default: squeeze_run<8>(v, dst, words); break;
+          }
+          field += field_words(n, b);
+        }
+      }
+    }
+
+    // ---- decode ----------------------------------------------------------------------------------------------------------------------
+    __device__ __forceinline__ uint32_t ld_volatile(const uint32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+
+    __device__ __forceinline__ void refuse(const BlockedDecodeParams &p, uint32_t bit)
+    {
+      atomicOr(p.state + 1, 1u);
+      atomicOr(p.status, bit);
+    }
+
+    __global__ __launch_bounds__(256) void k_bstream_map(const BlockedDecodeParams p)
+    {
+      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+      const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
+      const unsigned long long payloadWords = h->payloadWords;
+      const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES];
+      const bool ok = h->magic == LIMG_HIP_STREAM_MAGIC && h->version == LIMG_HIP_STREAM_VERSION_BLOCKED && h->sizeX == p.sizeX && h->sizeY == p.sizeY &&
+                      h->blocksX == p.blocksX && h->blocksY == p.blocksY && (h->channels == 3 || h->channels == 4) && nRects >= 1u && nRects <= p.nBlocks &&
+                      payloadWords <= (unsigned long long)p.nBlocks * 24ull && // 3 fields x 8 words at most per block: bounds the sum below
+                      sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry + payloadWords * 8ull <= p.streamBytes;
+      if (!ok)
+      {
+        if (tid == 0 && blockIdx.x == 0) refuse(p, 1u);
+        return;
+      }
+      uint32_t claimed = 0;
+      for (uint32_t base = (blockIdx.x * 4u + (uint32_t)wave) * 64u; base < nRects; base += gridDim.x * 256u)
+      {
+        if (ld_volatile(p.state + 1) != 0u) break; // refused already (all lanes read the same word: wave-uniform)
+        const uint32_t r = base + (uint32_t)lane;
+        uint32_t ox = 0, oy = 0, rx = 0, ry = 0;
+        bool good = false;
+        if (r < nRects)
+        {
+          const uint4 e3 = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)r * kRectEntry)[3];
+          ox = e3.z & 0xFFFFu; oy = e3.z >> 16; rx = e3.w & 0xFFFFu; ry = e3.w >> 16;
+          const uint32_t sw = e3.x;
+          good = rx >= 1u && ry >= 1u && ox + rx <= p.blocksX && oy + ry <= p.blocksY && (sw & 0xFFu) <= 8u && ((sw >> 8) & 0xFFu) <= 8u && ((sw >> 16) & 0xFFu) <= 8u;
+          if (good)
+          {
+            uint32_t wpx;
+            const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, ox, oy, rx, ry, wpx);
+            good = (unsigned long long)e3.y + rect_words(n, entry_bits(sw)) <= payloadWords; // (a field is at most n / 8 + 1 words, three of them far below 2^32)
+          }
+          if (!good) refuse(p, 2u);
+        }
+        const uint32_t nb = good ? rx * ry : 0u;
+        bool clash = false;
+        if (nb >= 1u && nb <= 4u)
+        { // a small rectangle: its lane claims it
+          for (uint32_t i = 0; i < nb; i++)
+          {
+            const uint32_t dy = i / rx, dx = i - dy * rx;
+            if (atomicCAS(p.map + (size_t)(oy + dy) * p.blocksX + ox + dx, kNoRect, r) != kNoRect) { clash = true; break; }
+            claimed++;
+          }
+        }
+        // the large ones, one after the other, by the whole wave; a block that is taken already ends the rectangle (and the stream): the work is bounded by the blocks
+        unsigned long long big = __builtin_amdgcn_ballot_w64(nb > 4u);
+        while (big != 0ull && __builtin_amdgcn_ballot_w64(clash) == 0ull)
+        {
+          const int src = __builtin_ctzll(big);
+          big &= big - 1ull;
+          const uint32_t box = (uint32_t)__shfl((int)ox, src, 64), boy = (uint32_t)__shfl((int)oy, src, 64), brx = (uint32_t)__shfl((int)rx, src, 64),
+                         bnb = (uint32_t)__shfl((int)nb, src, 64);
+          for (uint32_t i0 = 0; i0 < bnb && __builtin_amdgcn_ballot_w64(clash) == 0ull; i0 += 64u)
+          {
+            const uint32_t i = i0 + (uint32_t)lane;
+            if (i < bnb)
+            {
+              const uint32_t dy = i / brx, dx = i - dy * brx;
+              if (atomicCAS(p.map + (size_t)(boy + dy) * p.blocksX + box + dx, kNoRect, base + (uint32_t)src) != kNoRect) clash = true;
+              else claimed++;
+            }
+          }
+        }
+        if (clash) refuse(p, 2u);
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) claimed += (uint32_t)__shfl_xor((int)claimed, off, 64);
+      if (lane == 0 && claimed) atomicAdd(p.state, claimed);
+    }
+
+    __global__ __launch_bounds__(256) void k_bstream_decode(const BlockedDecodeParams p)
+    {
+      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+      // the verdict of k_bstream_map: nothing flagged and every block claimed exactly once (claims never overlap, so the count says it)
+      if (ld_volatile(p.state + 1) != 0u || ld_volatile(p.state) != p.nBlocks)
+      {
+        if (tid == 0 && blockIdx.x == 0) atomicOr(p.status, 2u);
+        return;
+      }
+      const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
+      const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h->channels;
+      const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h->payloadWords * 8ull;
+      const uint32_t unitsX = (p.blocksX + 7u) / 8u, nUnits = unitsX * p.blocksY;
+      const uint32_t j = (uint32_t)lane & 7u, row = (uint32_t)lane >> 3;
+      const bool rowAligned = (p.sizeX & 3u) == 0;
+      for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u)
+      {
+        const uint32_t by = unit / unitsX, bx = (unit - by * unitsX) * 8u + j;
+        const uint32_t y = by * 8u + row, x0 = bx * 8u;
+        if (bx >= p.blocksX || y >= p.sizeY) continue;
+        const uint32_t rect = p.map[(size_t)by * p.blocksX + bx];
+        if (rect >= nRects) continue; // (cannot happen after the check above; a lane never indexes the table with anything else)
+        const uint4 *ep = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)rect * kRectEntry);
+        const uint4 e0 = ep[0], e1 = ep[1], e2 = ep[2], e3 = ep[3];
+        const uint32_t ev[12] = { e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w };
+        const uint32_t sw = e3.x, ox = e3.z & 0xFFFFu, oy = e3.z >> 16, rx = e3.w & 0xFFFFu, ry = e3.w >> 16;
+        uint32_t wpx;
+        const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, ox, oy, rx, ry, wpx);
+        const uint32_t cnt = min(8u, p.sizeX - x0);
+        const unsigned long long i0 = (unsigned long long)(y - oy * 8u) * wpx + (x0 - ox * 8u);
+        const uint32_t bits = entry_bits(sw);
+        // the lane's 8 values of each field: the bit run at i0 * b
+        unsigned long long packed[3];
+        uint32_t bb[3], shift[3];
+        unsigned long long fieldByte = tableEnd + (unsigned long long)e3.y * 8ull;
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+        {
+          const uint32_t b = (bits >> (8 * k)) & 0xFFu;
+          bb[k] = b; shift[k] = (sw >> (8 * k)) & 0xFFu;
+          packed[k] = 0;
+          if (b)
+          {
+            const unsigned long long bit = i0 * b, byte = fieldByte + (bit >> 3), at = byte & ~3ull;
+            const uint32_t sh = (uint32_t)(byte & 3ull) * 8u + (uint32_t)(bit & 7ull); // < 32
+            // three aligned dwords hold the run's 64 bits wherever it starts; the last may lie beyond the stream's end (never beyond the field's: it is not used then)
+            const uint32_t *wp = reinterpret_cast<const uint32_t *>(p.stream + at);
+            const uint32_t d0 = at + 4ull <= total ? wp[0] : 0u, d1 = at + 8ull <= total ? wp[1] : 0u, d2 = at + 12ull <= total ? wp[2] : 0u;
+            const unsigned long long lo = ((unsigned long long)d1 << 32) | d0;
+            packed[k] = sh ? ((lo >> sh) | ((unsigned long long)d2 << (64u - sh))) : lo;
+            fieldByte += (unsigned long long)field_words(n, b) * 8ull;
+          }
+        }
+        // the decoder's constants (src/limg_decode.h:139-196 / :40-101), as k_blocked_store prepares them
+        int nn[3][4], mc[3][4];
+#pragma unroll
+        for (int f = 0; f < 3; f++)
+#pragma unroll
+          for (int c = 0; c < 4; c++)
+          {
+            const int mnv = (int)(int16_t)(ev[f * 4 + (c >> 1)] >> (16 * (c & 1))), mxv = (int)(int16_t)(ev[f * 4 + 2 + (c >> 1)] >> (16 * (c & 1)));
+            int nv = mxv - mnv, m = mnv;
+            if (c < 3) { if (shift[f] > 7u) { nv = 0; if (f > 0) m = 0; } }
+            else if (channels == 3u) { nv = 0; m = 0xFFFF; }
+            nn[f][c] = nv;
+            mc[f][c] = (int)(((uint32_t)m << 8) + 128u);
+          }
+        const int mulA = (int)shift_mul(shift[0]), mulB = (int)shift_mul(shift[1]), mulC = (int)shift_mul(shift[2]);
+        uint32_t px[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+        {
+          const int dA = (int)((uint32_t)(packed[0] >> (i * bb[0])) & ((1u << bb[0]) - 1u)) * mulA;
+          const int dB = (int)((uint32_t)(packed[1] >> (i * bb[1])) & ((1u << bb[1]) - 1u)) * mulB;
+          const int dC = (int)((uint32_t)(packed[2] >> (i * bb[2])) & ((1u << bb[2]) - 1u)) * mulC;
+          uint32_t decoded = 0;
+#pragma unroll
+          for (int c = 0; c < 4; c++)
+          {
+            int est = (mad_i24(dA, nn[0][c], mc[0][c]) >> 8) + (mad_i24(dB, nn[1][c], mc[1][c]) >> 8) + (mad_i24(dC, nn[2][c], mc[2][c]) >> 8);
+            est = est < 0 ? 0 : (est > 255 ? 255 : est);
+            decoded |= (uint32_t)est << (8 * c);
+          }
+          px[i] = decoded;
+        }
+        uint32_t *dst = p.out + (size_t)y * p.sizeX + x0;
+        if (cnt == 8u && rowAligned)
+        { // a wave's stores: 8 row pieces of 8 x 32 contiguous bytes
+          reinterpret_cast<uint4 *>(dst)[0] = make_uint4(px[0], px[1], px[2], px[3]);
+          reinterpret_cast<uint4 *>(dst)[1] = make_uint4(px[4], px[5], px[6], px[7]);
+        }
+        else
+        {
+#pragma unroll
+          for (int i = 0; i < 8; i++)
+            if ((uint32_t)i < cnt) dst[i] = px[i];
+        }
+      }
+    }
+
+    int device_cus()
+    {
+      static int cus = 0;
+      if (!cus)
+      {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+      }
+      return cus;
+    }
+  }
+
+  void launch_blocked_stream_pack(const BlockedStreamParams &p, hipStream_t s)
+  {
+    if (p.nRegions == 0) return;
+    hipLaunchKernelGGL(k_bstream_sizes<false>, dim3(p.nTiles), dim3(kRectTile), 0, s, p);
+    hipLaunchKernelGGL(k_bstream_scan, dim3(1), dim3(1024), 0, s, p);
+    hipLaunchKernelGGL(k_bstream_sizes<true>, dim3(p.nTiles), dim3(kRectTile), 0, s, p);
+    // one lane per run of 64 pixels; an image has at most blocks + rectangles runs.  Eight workgroups of four waves per CU, striding
+    const uint64_t runsMax = (uint64_t)p.blocksX * p.blocksY + p.nRegions, need = (runsMax + 255u) / 256u, slots = (uint64_t)device_cus() * 8u;
+    hipLaunchKernelGGL(k_bstream_pack, dim3((uint32_t)(need < slots ? need : slots)), dim3(256), 0, s, p);
+  }
+
+  void launch_blocked_stream_decode(const BlockedDecodeParams &p, hipStream_t s)
+  {
+    const uint32_t slots = (uint32_t)device_cus() * 8u;
+    const uint32_t needMap = (p.nBlocks + 255u) / 256u; // at most nBlocks rectangles, 64 per wave
+    hipLaunchKernelGGL(k_bstream_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, p);
+    const uint32_t units = ((p.blocksX + 7u) / 8u) * p.blocksY, need = (units + 3u) / 4u;
+    hipLaunchKernelGGL(k_bstream_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, p);
+  }
+}

@@ -141,6 +141,14 @@ struct limg_hip_context
   uint32_t chainEf = 0;
   DevBuf commWords; // [0] this rank's value, [1] its chain base, [8 ...] the all-gathered values
   DevBuf streamFac, streamTiles, streamUnits, streamStatus, streamBuf; // stream packer: 3 factor planes, per-tile payload words; decode status word; host-entry staging
+  // version 2 stream of the merged-block encoder (limg_hip_blocked_stream_api.hip): per rectangle its first 64-pixel run, per tile of rectangles its totals; the
+  // decoder's block -> rectangle map and its per-call words
+  DevBuf bsUnits, bsTiles, bsMap, bsState;
+  size_t blockedScratchCap = 0;              // plane stride of bFac in the last merged-block encode (BlockedParams::scratchCap)
+  struct { size_t sizeX = 0, sizeY = 0; int channels = 0; uint32_t errorFactor = 0, flags = 0; bool valid = false; } lastBlocked; // ... its shape and stream flags; valid: it succeeded,
+                                             // so the context's buffers hold everything the stream packer reads (limg_hip_blocked_last_stream)
+  std::vector<hipEvent_t> packTimers;        // begin / end of the last stream encode's scan + pack kernels ...
+  bool packTimed = false;                    // ... which limg_hip_blocked_kernel_timing still has to add to slot [3]
   // optional per-kernel timing (bench): 4 events per encode, recorded on the caller's stream, read back in one go
   int persistentWorkgroups = 1280; // 5 x the device's CU count (set at init): the unit the launches scale (x 6 / 5 with the float stage in its own kernel)
   bool forceSplit = false; // options: run the three-kernel path even where the fused kernel applies (A/B, tests)
@@ -154,7 +162,7 @@ struct limg_hip_context
   {
     for (auto *b : { &c.records, &c.shifts, &c.stripCalls, &c.stripBase, &c.invN, &c.noise, &c.noiseDyn, &c.noiseStates, &c.noiseCk, &c.park, &c.batchTable, &c.stats,
                      &c.lookback, &c.accTable, &c.devStatus, &c.in, &c.planes, &c.hostWords, &c.cmp, &c.bFlags, &c.bBound, &c.bOrder, &c.bMatch, &c.bRegions, &c.bOut,
-                     &c.bPx, &c.bFac, &c.bNoise, &c.bNoiseBase, &c.bCalls, &c.commWords, &c.streamFac, &c.streamTiles, &c.streamUnits, &c.streamStatus, &c.streamBuf })
+                     &c.bPx, &c.bFac, &c.bNoise, &c.bNoiseBase, &c.bCalls, &c.commWords, &c.streamFac, &c.streamTiles, &c.streamUnits, &c.streamStatus, &c.streamBuf, &c.bsUnits, &c.bsTiles, &c.bsMap, &c.bsState })
       f(*b);
   }
 };
@@ -247,6 +255,13 @@ namespace limg_hip
   limg_hip_result encode_stats(const EncodeJob &e);
   // images with partial edge blocks (limg_hip_encode_ragged.hip): the split path's kernels around a dither chain the host walks
   limg_hip_result encode_ragged(EncodeJob &e);
+
+  // ---- the merged-block encoder's pipeline (limg_hip_blocked_api.hip) ----
+  // pInfo == nullptr is the COMPACT mode of the stream entry: no plane is stored.  When the call returns, every rectangle's descriptor (bRegions), record and shift word
+  // (bOut), pre-dither factor bytes (bFac, region-major, plane stride blockedScratchCap), noise bytes (bNoise) and noise offset (bNoiseBase) are complete in the
+  // context's buffers, which is what the stream packer reads.
+  limg_hip_result blocked_encode_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_blocked_encode3d_info *pInfo,
+                                        uint32_t errorFactor, int fastBitCrushing, hipStream_t stream);
 }
 
 #endif

@@ -182,6 +182,34 @@ namespace limg_hip
   void launch_blocked_store(const BlockedParams &p, hipStream_t s);
   void launch_blocked_order(const BlockedParams &p, hipStream_t s);
 
+  // ---- version 2 stream: the merged-block encoder's rectangles (limg_hip_blocked_stream.hip) ----
+  // Pack: from what a compact-mode merged-block encode leaves in the context (see blocked_encode_device).  The work unit is a RUN: 64 consecutive pixels (rectangle
+  // row-major order) of one rectangle, all three fields.
+  struct BlockedStreamParams
+  {
+    uint32_t sizeX, sizeY, blocksX, blocksY, channels, errorFactor, flags;
+    uint32_t nRegions, nTiles, scratchCap;
+    const RegionDesc *regions;
+    const RegionOut *out;
+    const unsigned long long *noiseBase;
+    const uint8_t *scratchFac, *noise;
+    uint8_t *stream;
+    uint32_t *units; // nRegions + 1: every rectangle's first run (exclusive prefix of ceil(n / 64)); [nRegions] = all runs
+    uint32_t *tiles; // per tile of 256 rectangles { payload words, runs }: totals, then (k_bstream_scan) their exclusive prefix
+  };
+  struct BlockedDecodeParams
+  {
+    uint32_t sizeX, sizeY, blocksX, blocksY, nBlocks;
+    const uint8_t *stream;
+    unsigned long long streamBytes;
+    uint32_t *out;
+    uint32_t *map;    // per block the rectangle that covers it (~0: none yet)
+    uint32_t *status; // the context's sticky stream status word: bit 0 header mismatch, bit 1 inconsistent table or payload offsets
+    uint32_t *state;  // this call's words (zeroed in front of it): [0] blocks claimed by the rectangles, [1] non-0 = the stream is refused
+  };
+  void launch_blocked_stream_pack(const BlockedStreamParams &p, hipStream_t s);
+  void launch_blocked_stream_decode(const BlockedDecodeParams &p, hipStream_t s);
+
   void launch_stream_pack(const StreamParams &p, hipStream_t s);
   void launch_stream_decode(const DecodeParams &p, hipStream_t s);
 

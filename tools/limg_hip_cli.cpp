@@ -12,7 +12,8 @@
 // fills is not written.  Extras: `--fixed-blocks` (single-file mode with `limg_encode3d_test`, fixed 8x8 blocks, instead), `--threads <T>`
 // (size of the pool whose strip partition the 8x8 path reproduces; default: limg_threading_max_threads()),
 // `--out-dir <dir>`, `--stream <file>` (also write the compact LMG3 stream of the 8x8 path and verify that it decodes to that path's image),
-// and the extra mode `limg_hip_cli --decode <file.lmg3> [<out.tga>]`.
+// `--blocked-stream <file>` (single-file merged-block mode: write the version 2 stream of that very encode and verify that it decodes to its image),
+// and the extra mode `limg_hip_cli --decode <file.lmg3> [<out.tga>]` (either version).
 #include <inttypes.h>
 #include <math.h>
 #include <stdio.h>
@@ -227,12 +228,12 @@ struct Options
   bool writeImages = true, fastBitCrushing = true, usePool = true, fixedBlocks = false;
   uint32_t errorFactor = 100;
   size_t repeat = 1, threads = 0;
-  std::string outDir = ".", streamPath;
+  std::string outDir = ".", streamPath, blockedStreamPath;
 };
 
 static const char *const kUsage =
     "Usage:\nlimg_hip_cli [<InputFile> | --] [--no-output | --error-factor <Factor> | --accurate-bit-crushing | --single-thread | --fixed-blocks | --threads <T> | --out-dir <dir> | "
-    "--stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n";
+    "--stream <file> | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n";
 
 static bool parse_number(const char *text, uint64_t &value)
 {
@@ -263,6 +264,7 @@ static bool parse_args(int argc, const char **argv, Options &o)
     else if (a == "--threads" && hasValue && parse_number(argv[i + 1], v)) { o.threads = (size_t)v; if (v == 0) o.usePool = false; i++; }
     else if (a == "--out-dir" && hasValue) o.outDir = argv[++i];
     else if (a == "--stream" && hasValue) o.streamPath = argv[++i];
+    else if (a == "--blocked-stream" && hasValue) o.blockedStreamPath = argv[++i];
     else if ((a == "--count" || a == "--") && hasValue)
     {
       if (!listMode) { printf("'%s' is only supported with input file '--', found '%s'.\n", a.c_str(), argv[1]); return false; }
@@ -379,6 +381,26 @@ static bool write_and_check_stream(const Options &o, const Image &img, limg_thre
   return same;
 }
 
+// `--blocked-stream`: the version 2 stream of the merged-block encode that has just run -- packed from what that encode left in the context, the image is not
+// encoded again -- checked against that encode's decoded image
+static bool write_and_check_blocked_stream(const Options &o, const Image &img, const std::vector<uint32_t> &decoded)
+{
+  std::vector<uint8_t> stream(limg_blocked_encode_bound(img.w, img.h));
+  size_t bytes = 0;
+  limg_result r = limg_blocked_last_encode(stream.data(), stream.size(), &bytes);
+  if (r != limg_success) FAIL(EXIT_FAILURE, "limg_blocked_last_encode failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
+  std::vector<uint32_t> again(img.count());
+  r = limg_blocked_decode(stream.data(), bytes, again.data(), again.size());
+  if (r != limg_success) FAIL(EXIT_FAILURE, "limg_blocked_decode failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
+  const bool same = memcmp(again.data(), decoded.data(), img.count() * 4) == 0;
+  printf("Merged-block stream: %" PRIu64 " bytes (%5.3f bits per pixel); decoding it %s the merged-block decoded image.\n", (uint64_t)bytes, bytes * 8.0 / img.count(),
+         same ? "reproduces" : "DOES NOT reproduce");
+  FILE *f = fopen(o.blockedStreamPath.c_str(), "wb");
+  if (!f || fwrite(stream.data(), 1, bytes, f) != bytes) FAIL(EXIT_FAILURE, "Failed to write '%s'.\n", o.blockedStreamPath.c_str());
+  fclose(f);
+  return same;
+}
+
 // single-file mode (src/main.cpp:235-267, :342-370): the merged-block encoder like upstream, or the fixed 8x8 path with --fixed-blocks
 static int run_single_file(const Options &o, limg_thread_pool *pool)
 {
@@ -404,6 +426,11 @@ static int run_single_file(const Options &o, limg_thread_pool *pool)
   printf("Elapsed Time: %f ms\n", seconds * 1e3);
   printf("Throughput: %f Mpx/s\n", img.count() * 1e-6 / seconds);
   if (result != limg_success) FAIL(EXIT_FAILURE, "Encode failed with exit code 0x%" PRIX32 ".\n", (uint32_t)result);
+  if (!o.blockedStreamPath.empty())
+  { // (first thing after the encode: it packs what that encode left in the context)
+    if (o.fixedBlocks) FAIL(EXIT_FAILURE, "'--blocked-stream' is the stream of the merged-block encoder; it cannot be combined with '--fixed-blocks'.\n");
+    if (!write_and_check_blocked_stream(o, img, p.decoded)) return EXIT_FAILURE;
+  }
   if (!o.fixedBlocks)
   { // upstream prints this from inside the library (src/limg.cpp:2433-2440)
     uint64_t bits = 0;
@@ -480,7 +507,8 @@ static int run_decode(int argc, const char **argv)
   limg_result r = limg_decode_info(stream.data(), stream.size(), &sx, &sy, &alpha);
   if (r != limg_success) FAIL(EXIT_FAILURE, "'%s' is not an LMG3 stream (0x%" PRIX32 ").\n", argv[2], (uint32_t)r);
   std::vector<uint32_t> image(sx * sy);
-  r = limg_decode(stream.data(), stream.size(), image.data(), image.size());
+  const bool merged = stream.size() >= sizeof(limg_hip_stream_header) && reinterpret_cast<const limg_hip_stream_header *>(stream.data())->version == LIMG_HIP_STREAM_VERSION_BLOCKED;
+  r = merged ? limg_blocked_decode(stream.data(), stream.size(), image.data(), image.size()) : limg_decode(stream.data(), stream.size(), image.data(), image.size());
   if (r != limg_success) FAIL(EXIT_FAILURE, "limg_decode failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
   printf("%" PRIu64 " x %" PRIu64 " pixels, %s.\n", (uint64_t)sx, (uint64_t)sy, alpha ? "RGBA" : "RGB");
   puts(write_tga(argc > 3 ? argv[3] : "limg_out.tga", sx, sy, 4, image.data()) ? "Wrote decoded file." : "Failed to write decoded file.");
