@@ -502,48 +502,59 @@ class LimgHip:
         _check(self.lib.limg_hip_blocked_kernel_timing(self.ctx, _np_ptr(ms)), "limg_hip_blocked_kernel_timing")
         return dict(zip(("pass1_kernel", "match_kernels", "fit_search_kernel", "expand_store_kernels"), ms.tolist()))
 
-    # ---- compact stream ("limg_encode" / "limg_decode") ----------------------------------------------------------------------------
+    # ---- compact stream ("limg_encode" / "limg_decode"): version 1 (8x8 blocks) and version 2 (what the merged-block encoder produced) ----------------
+    # The two versions' entries take the same arguments but for pool_threads (version 1 only): `name` is the entry, `opts` its arguments after the size pointer.
+    def _stream_call(self, name, *args):
+        _check(getattr(self.lib, name)(self.ctx, *args), name)
+
+    def _encode_stream(self, name, cap, img, has_alpha, opts):
+        img = np.ascontiguousarray(img, dtype=np.uint32)
+        h, w = img.shape
+        out = np.zeros(cap(w, h), dtype=np.uint8)
+        n = C.c_size_t(0)
+        self._stream_call(name, _np_ptr(img), w, h, int(has_alpha), _np_ptr(out), out.size, C.byref(n), *opts)
+        return out[:n.value].copy()
+
+    def _decode_stream(self, name, stream, w, h):
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        out = np.zeros((h, w), dtype=np.uint32)
+        self._stream_call(name, _np_ptr(stream), stream.size, _np_ptr(out), out.size)
+        return out
+
+    def _encode_stream_device(self, name, cap, img, has_alpha, out, want_size, opts):
+        import torch
+        h, w = img.shape
+        if out is None:
+            out = torch.empty(cap(w, h), dtype=torch.uint8, device=img.device)
+        n = C.c_size_t(0)
+        self._stream_call(name, C.c_void_p(img.data_ptr()), w, h, int(has_alpha), C.c_void_p(out.data_ptr()), out.numel(), C.byref(n) if want_size else None, *opts, self._stream())
+        return out, (n.value if want_size else None)
+
+    def _decode_stream_device(self, name, stream, nbytes, w, h, out):
+        import torch
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
+        self._stream_call(name, C.c_void_p(stream.data_ptr()), int(nbytes), C.c_void_p(out.data_ptr()), w, h, self._stream())
+        return out
+
     def stream_bound(self, w, h):
         return self.lib.limg_hip_stream_bound(w, h)
 
     def encode_stream(self, img, has_alpha, error_factor=100, pool_threads=0, fast=True):
         """host uint32 image -> stream bytes (numpy uint8)"""
-        img = np.ascontiguousarray(img, dtype=np.uint32)
-        h, w = img.shape
-        cap = self.stream_bound(w, h)
-        out = np.zeros(cap, dtype=np.uint8)
-        n = C.c_size_t(0)
-        _check(self.lib.limg_hip_encode_stream(self.ctx, _np_ptr(img), w, h, int(has_alpha), _np_ptr(out), cap, C.byref(n), error_factor, pool_threads, int(fast)), "limg_hip_encode_stream")
-        return out[:n.value].copy()
+        return self._encode_stream("limg_hip_encode_stream", self.stream_bound, img, has_alpha, (error_factor, pool_threads, int(fast)))
 
     def decode_stream(self, stream):
-        stream = np.ascontiguousarray(stream, dtype=np.uint8)
         w, h, _, _ = stream_info(stream, self.lib)
-        out = np.zeros((h, w), dtype=np.uint32)
-        _check(self.lib.limg_hip_decode_stream(self.ctx, _np_ptr(stream), stream.size, _np_ptr(out), out.size), "limg_hip_decode_stream")
-        return out
+        return self._decode_stream("limg_hip_decode_stream", stream, w, h)
 
     def encode_stream_device(self, img, has_alpha, out=None, error_factor=100, pool_threads=0, fast=True, want_size=True):
         """img: torch int32 CUDA (h, w) -> (torch uint8 CUDA stream buffer of worst-case size, bytes used or None)"""
-        import torch
-        h, w = img.shape
-        cap = self.stream_bound(w, h)
-        if out is None:
-            out = torch.empty(cap, dtype=torch.uint8, device=img.device)
-        n = C.c_size_t(0)
-        _check(self.lib.limg_hip_encode_stream_device(self.ctx, C.c_void_p(img.data_ptr()), w, h, int(has_alpha), C.c_void_p(out.data_ptr()), out.numel(),
-                                                      C.byref(n) if want_size else None, error_factor, pool_threads, int(fast), self._stream()), "limg_hip_encode_stream_device")
-        return out, (n.value if want_size else None)
+        return self._encode_stream_device("limg_hip_encode_stream_device", self.stream_bound, img, has_alpha, out, want_size, (error_factor, pool_threads, int(fast)))
 
     def decode_stream_device(self, stream, nbytes, w, h, out=None):
-        import torch
-        if out is None:
-            out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
-        _check(self.lib.limg_hip_decode_stream_device(self.ctx, C.c_void_p(stream.data_ptr()), int(nbytes), C.c_void_p(out.data_ptr()), w, h, self._stream()),
-               "limg_hip_decode_stream_device")
-        return out
+        return self._decode_stream_device("limg_hip_decode_stream_device", stream, nbytes, w, h, out)
 
-    # ---- version 2 stream: what the merged-block encoder produced ----------------------------------------------------------------------
     def blocked_stream_bound(self, w, h):
         return self.lib.limg_hip_blocked_stream_bound(w, h)
 
@@ -552,50 +563,25 @@ class LimgHip:
 
     def blocked_encode_stream(self, img, has_alpha, error_factor=100, fast=True):
         """host uint32 image -> version 2 stream bytes (numpy uint8); blocked_regions() / blocked_timing() describe this encode afterwards"""
-        img = np.ascontiguousarray(img, dtype=np.uint32)
-        h, w = img.shape
-        cap = self.blocked_stream_bound(w, h)
-        out = np.zeros(cap, dtype=np.uint8)
-        n = C.c_size_t(0)
-        _check(self.lib.limg_hip_blocked_encode_stream(self.ctx, _np_ptr(img), w, h, int(has_alpha), _np_ptr(out), cap, C.byref(n), error_factor, int(fast)),
-               "limg_hip_blocked_encode_stream")
-        return out[:n.value].copy()
+        return self._encode_stream("limg_hip_blocked_encode_stream", self.blocked_stream_bound, img, has_alpha, (error_factor, int(fast)))
 
     def blocked_last_stream(self, w, h):
         """the version 2 stream of this context's last merged-block encode (planes or stream), of a w x h image, without encoding again"""
-        cap = self.blocked_stream_bound(w, h)
-        out = np.zeros(cap, dtype=np.uint8)
+        out = np.zeros(self.blocked_stream_bound(w, h), dtype=np.uint8)
         n = C.c_size_t(0)
-        _check(self.lib.limg_hip_blocked_last_stream(self.ctx, _np_ptr(out), cap, C.byref(n)), "limg_hip_blocked_last_stream")
+        self._stream_call("limg_hip_blocked_last_stream", _np_ptr(out), out.size, C.byref(n))
         return out[:n.value].copy()
 
     def blocked_decode_stream(self, stream):
-        stream = np.ascontiguousarray(stream, dtype=np.uint8)
         w, h = blocked_stream_info(stream, self.lib)[:2]
-        out = np.zeros((h, w), dtype=np.uint32)
-        _check(self.lib.limg_hip_blocked_decode_stream(self.ctx, _np_ptr(stream), stream.size, _np_ptr(out), out.size), "limg_hip_blocked_decode_stream")
-        return out
+        return self._decode_stream("limg_hip_blocked_decode_stream", stream, w, h)
 
     def blocked_encode_stream_device(self, img, has_alpha, out=None, error_factor=100, fast=True, want_size=True):
         """img: torch int32 CUDA (h, w) -> (torch uint8 CUDA stream buffer of worst-case size, bytes used or None)"""
-        import torch
-        h, w = img.shape
-        cap = self.blocked_stream_bound(w, h)
-        if out is None:
-            out = torch.empty(cap, dtype=torch.uint8, device=img.device)
-        n = C.c_size_t(0)
-        _check(self.lib.limg_hip_blocked_encode_stream_device(self.ctx, C.c_void_p(img.data_ptr()), w, h, int(has_alpha), C.c_void_p(out.data_ptr()), out.numel(),
-                                                              C.byref(n) if want_size else None, error_factor, int(fast), self._stream()),
-               "limg_hip_blocked_encode_stream_device")
-        return out, (n.value if want_size else None)
+        return self._encode_stream_device("limg_hip_blocked_encode_stream_device", self.blocked_stream_bound, img, has_alpha, out, want_size, (error_factor, int(fast)))
 
     def blocked_decode_stream_device(self, stream, nbytes, w, h, out=None):
-        import torch
-        if out is None:
-            out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
-        _check(self.lib.limg_hip_blocked_decode_stream_device(self.ctx, C.c_void_p(stream.data_ptr()), int(nbytes), C.c_void_p(out.data_ptr()), w, h, self._stream()),
-               "limg_hip_blocked_decode_stream_device")
-        return out
+        return self._decode_stream_device("limg_hip_blocked_decode_stream_device", stream, nbytes, w, h, out)
 
     def check(self):
         _check(self.lib.limg_hip_check_device_status(self.ctx), "limg_hip_check_device_status")

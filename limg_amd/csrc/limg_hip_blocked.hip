@@ -728,6 +728,8 @@ namespace limg_hip
       const uint32_t shift[3] = { O.shiftWord & 0xFF, (O.shiftWord >> 8) & 0xFF, (O.shiftWord >> 16) & 0xFF };
 
       // block-uniform plane values (src/limg.cpp:1604-1627) and the decoder's constants (src/limg_decode.h:139-196 / :40-101)
+      // (the dither + crush and the a16 below are limg_hip_stream_format.h's dither_crush4 / a16_constants / a16_pixel written out: called through those, this kernel
+      //  compiles to a different schedule, and its slot of the merged-block encode measured 7 % slower on a 4096^2 gradient -- profiles/stream_core_ab.md)
       const int16_t *vec[6] = { rec.dirA_min, rec.dirA_max, rec.dirB_offset, rec.dirB_mag, rec.dirC_offset, rec.dirC_mag };
       uint32_t col[6];
 #pragma unroll

@@ -43,7 +43,7 @@ namespace
     size_t sizeX, sizeY, blocks, maxCalls;
     uint32_t blocksX, blocksY, bandRows, nBands;
     int channels; bool pcg; // pcg: limg_hip_options.dither_pcg
-    bool compact;           // no plane is stored: the stream packer (limg_hip_blocked_stream_api.hip) takes the rectangles from the context's buffers
+    bool compact;           // no plane is stored: the stream packer (limg_hip_stream_api.hip) takes the rectangles from the context's buffers
     BlockedParams bp;
     hipEvent_t *frontTimers; // begin of pass 1, its end = begin of the similarity kernels, their end
     // the context's pinned staging, and per dither call its chain value, noise offset and pixel count on the host (call*) and on the device (dCall*)
@@ -487,7 +487,7 @@ extern "C"
   {
     if (!c || !pMs4) return limg_hip_error_ArgumentNull;
     if (c->packTimed)
-    { // a stream encode: its scan + pack kernels were enqueued behind the pipeline (limg_hip_blocked_stream_api.hip) and belong to slot [3]
+    { // a stream encode: its scan + pack kernels were enqueued behind the pipeline (limg_hip_stream_api.hip) and belong to slot [3]
       float t = 0;
       if (hipEventSynchronize(c->packTimers[1]) == hipSuccess && hipEventElapsedTime(&t, c->packTimers[0], c->packTimers[1]) == hipSuccess) c->blockedKernelMs[3] += t;
       c->packTimed = false;

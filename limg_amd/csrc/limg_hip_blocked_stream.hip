@@ -3,11 +3,11 @@
 // Pack, after a compact-mode merged-block encode (blocked_encode_device with no planes), from what that leaves in the context: per rectangle its descriptor, record and
 // shift word, its pre-dither factor bytes and noise bytes, both region-major (pixel i = yy * wpx + xx of the rectangle at byte i: the order the stream wants).
 //   k_bstream_sizes<false>  per tile of 256 rectangles: payload words and 64-pixel runs
-//   k_bstream_scan          one workgroup: exclusive prefix over the tiles, the header
+//   k_stream_tile_scan<2>   one workgroup: exclusive prefix over the tiles, the header (limg_hip_stream_format.h, shared with version 1)
 //   k_bstream_sizes<true>   per rectangle: its first payload word and first run, its 64-byte table entry
 //   k_bstream_pack          lane = one RUN: 64 consecutive pixels of one rectangle, its three fields one after the other.  Rectangles are wildly uneven (a single
 //                           block up to thousands), runs are not: a lane finds its rectangle by bisection over the runs' prefix, reads 64 factor bytes (and 64 noise
-//                           bytes where the field is dithered) with four 16-byte loads, dithers and crushes them (k_blocked_store's arithmetic), squeezes every 8
+//                           bytes where the field is dithered) with four 16-byte loads, dithers and crushes them (dither_crush4, as k_blocked_store does), squeezes every 8
 //                           values into b bytes with the mask-and-shift steps of k_stream_pack_strips and stores b 8-byte words.  Runs that are short (the tail of a
 //                           rectangle on an image with partial blocks) or not 16-byte aligned gather their bytes one by one -- same bytes out.
 // Decode:
@@ -15,9 +15,9 @@
 //                           rectangle itself (atomicCAS on ~0), the wave claims a large one together; the claimed blocks are counted
 //   k_bstream_decode        refuses unless every block was claimed and nothing was flagged; then lane = (block j = lane & 7, block row r = lane >> 3) over units of 8
 //                           consecutive blocks: the lane's 8 pixels are the bit run at ((y - 8 oy) * wpx + (x - 8 ox)) * b of each field of the block's rectangle; the
-//                           integer decode is k_blocked_store's (a16); a wave's stores are 8 row pieces of 256 contiguous bytes.
+//                           integer decode is a16_constants / a16_pixel, as in k_blocked_store; a wave's stores are 8 row pieces of 256 contiguous bytes.
 // Nothing here reads through an offset the map kernel has not checked against the stream's size.
-#include "limg_hip_internal.h"
+#include "limg_hip_stream_format.h"
 
 namespace limg_hip
 {
@@ -26,11 +26,6 @@ namespace limg_hip
     constexpr int kRectTile = 256;
     constexpr int kRectEntry = 64;
     constexpr uint32_t kNoRect = 0xFFFFFFFFu;
-
-    __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-    __device__ __forceinline__ int mad_i24(int a, int b, int c) { int r; asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-    // (1 << s) + bias(s), src/limg_bit_crush_simd.h:611-619 / src/limg_decode.h:172-178
-    __device__ __forceinline__ uint32_t shift_mul(uint32_t s) { return s < 4 ? (1u << s) : (s == 4 ? 17u : (s == 5 ? 36u : (s == 6 ? 85u : (s == 7 ? 255u : 256u)))); }
 
     // pixels of a rectangle: 8 rx x 8 ry clipped to the image (src/limg.cpp:1722-1740)
     __device__ __forceinline__ uint32_t rect_pixels(uint32_t sizeX, uint32_t sizeY, uint32_t blocksX, uint32_t blocksY, uint32_t ox, uint32_t oy, uint32_t rx, uint32_t ry, uint32_t &wpx)
@@ -42,32 +37,6 @@ namespace limg_hip
       return wpx * hpx;
     }
 
-    // bits per pixel of the three fields + raw-escape mask (bA | bB << 8 | bC << 16 | rawMask << 24) from the shift triple and the alpha lanes of the record's vectors
-    __device__ __forceinline__ uint32_t field_bits(uint32_t shiftWord, uint32_t alphaVaries3, uint32_t channels)
-    {
-      uint32_t r = 0;
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-      {
-        const uint32_t s = (shiftWord >> (8 * k)) & 0xFFu;
-        uint32_t b = s >= 8u ? 0u : 8u - s;
-        if (s >= 8u && channels == 4u && ((alphaVaries3 >> k) & 1u)) { b = 8u; r |= 1u << (24 + k); }
-        r |= b << (8 * k);
-      }
-      return r;
-    }
-    // the same from a table entry's shift word, whose bits 24..26 say which factors are escaped
-    __device__ __forceinline__ uint32_t entry_bits(uint32_t sw)
-    {
-      uint32_t r = 0;
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-      {
-        const uint32_t s = (sw >> (8 * k)) & 0xFFu;
-        r |= (s >= 8u ? (((sw >> (24 + k)) & 1u) ? 8u : 0u) : 8u - s) << (8 * k);
-      }
-      return r;
-    }
     __device__ __forceinline__ uint32_t field_words(uint32_t n, uint32_t b) { return (uint32_t)(((unsigned long long)n * b + 63ull) >> 6); }
     __device__ __forceinline__ uint32_t rect_words(uint32_t n, uint32_t bits) { return field_words(n, bits & 0xFFu) + field_words(n, (bits >> 8) & 0xFFu) + field_words(n, (bits >> 16) & 0xFFu); }
 
@@ -77,11 +46,11 @@ namespace limg_hip
     {
       const RegionDesc R = p.regions[r];
       const uint4 *rp = reinterpret_cast<const uint4 *>(p.out + r) + 1; // skip avg[4]: {dirA_min, dirA_max}, {dirB_offset, dirB_mag}, {dirC_offset, dirC_mag}
-      const uint4 v0 = rp[0], v1 = rp[1], v2 = rp[2];
-      const uint32_t varies = ((v0.y >> 16) != (v0.w >> 16) ? 1u : 0u) | ((v1.y >> 16) != (v1.w >> 16) ? 2u : 0u) | ((v2.y >> 16) != (v2.w >> 16) ? 4u : 0u);
+      int mn3[3], mx3[3];
+      alpha_lanes(rp[0], rp[1], rp[2], mn3, mx3);
       RectSize o;
       o.sw = p.out[r].shiftWord & 0xFFFFFFu;
-      o.bits = field_bits(o.sw, varies, p.channels);
+      o.bits = field_bits(o.sw, mn3, mx3, (int)p.channels);
       uint32_t wpx;
       const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, R.ox, R.oy, R.rx, R.ry, wpx);
       o.words = rect_words(n, o.bits);
@@ -98,13 +67,7 @@ namespace limg_hip
       const uint32_t r = blockIdx.x * kRectTile + tid;
       RectSize z = { 0, 0, 0, 0 };
       if (r < p.nRegions) z = rect_size(p, r);
-      uint32_t iw = z.words, ir = z.runs;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1)
-      {
-        const uint32_t uw = (uint32_t)__shfl_up((int)iw, off, 64), ur = (uint32_t)__shfl_up((int)ir, off, 64);
-        if (lane >= off) { iw += uw; ir += ur; }
-      }
+      const uint32_t iw = wave_scan_inclusive(z.words, lane), ir = wave_scan_inclusive(z.runs, lane);
       if (lane == 63) { sWords[wave] = iw; sRuns[wave] = ir; }
       __syncthreads();
       if (!ENTRIES)
@@ -122,48 +85,6 @@ namespace limg_hip
       uint4 *e = reinterpret_cast<uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)r * kRectEntry);
       e[0] = rp[0]; e[1] = rp[1]; e[2] = rp[2];
       e[3] = make_uint4(z.sw | (z.bits & 0xFF000000u), word, R.ox | (R.oy << 16), R.rx | (R.ry << 16));
-    }
-
-    // exclusive prefix of the tile totals in place (one workgroup) + the header
-    __global__ __launch_bounds__(1024) void k_bstream_scan(const BlockedStreamParams p)
-    {
-      __shared__ unsigned long long sW[16], sR[16];
-      __shared__ unsigned long long sCarryW, sCarryR;
-      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-      if (tid == 0) { sCarryW = 0; sCarryR = 0; }
-      __syncthreads();
-      for (uint32_t base = 0; base < p.nTiles; base += 1024)
-      {
-        const uint32_t i = base + tid;
-        const unsigned long long vw = i < p.nTiles ? p.tiles[2 * i] : 0u, vr = i < p.nTiles ? p.tiles[2 * i + 1] : 0u;
-        unsigned long long iw = vw, ir = vr;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1)
-        {
-          const unsigned long long uw = (unsigned long long)__shfl_up((long long)iw, off, 64), ur = (unsigned long long)__shfl_up((long long)ir, off, 64);
-          if (lane >= off) { iw += uw; ir += ur; }
-        }
-        if (lane == 63) { sW[wave] = iw; sR[wave] = ir; }
-        __syncthreads();
-        unsigned long long pw = sCarryW, pr = sCarryR;
-        for (int w = 0; w < wave; w++) { pw += sW[w]; pr += sR[w]; }
-        // payloadWord is 32 bits: the host refuses images whose worst-case payload would not fit (limg_hip_blocked_stream_bound); runs <= blocks
-        if (i < p.nTiles) { p.tiles[2 * i] = (uint32_t)(pw + iw - vw); p.tiles[2 * i + 1] = (uint32_t)(pr + ir - vr); }
-        __syncthreads();
-        if (tid == 1023) { sCarryW = pw + iw; sCarryR = pr + ir; }
-        __syncthreads();
-      }
-      if (tid == 0)
-      {
-        limg_hip_stream_header h;
-        h.magic = LIMG_HIP_STREAM_MAGIC; h.version = LIMG_HIP_STREAM_VERSION_BLOCKED;
-        h.sizeX = p.sizeX; h.sizeY = p.sizeY; h.channels = p.channels; h.errorFactor = p.errorFactor;
-        h.blocksX = p.blocksX; h.blocksY = p.blocksY;
-        h.payloadWords = sCarryW;
-        h.totalBytes = sizeof(limg_hip_stream_header) + (unsigned long long)p.nRegions * kRectEntry + sCarryW * 8ull;
-        h.flags = p.flags | LIMG_HIP_STREAM_FLAG_MERGED; h.reserved[0] = p.nRegions; h.reserved[1] = h.reserved[2] = 0;
-        *reinterpret_cast<limg_hip_stream_header *>(p.stream) = h;
-      }
     }
 
     // 64 bytes of a region-major array into 16 dwords: four 16-byte loads where the run is whole and aligned, else byte by byte (absent pixels read as 0)
@@ -253,25 +174,11 @@ namespace limg_hip
           uint32_t v[16];
           load_run(p.scratchFac + (size_t)k * p.scratchCap + R.scratch + i0, count, v);
           if (dithered)
-          { // src/limg.cpp:824-879 as k_blocked_store applies it: (noise & ditherSize) - ditherOffset, add, clamp, shift
+          {
             uint32_t z[16];
             load_run(noise + i0, count, z);
-            const int half = (int)(1u << (s - 1u));
-            const uint32_t m = (1u << s) - 1u;
 #pragma unroll
-            for (int q = 0; q < 16; q++)
-            {
-              uint32_t o = 0;
-#pragma unroll
-              for (int t = 0; t < 4; t++)
-              {
-                int x = (int)((v[q] >> (8 * t)) & 0xFFu) + ((int)((z[q] >> (8 * t)) & m) - half);
-                x = x < 0 ? 0 : (x > 255 ? 255 : x);
-                o |= ((uint32_t)x >> s) << (8 * t);
-              }
-              v[q] = o;
-            }
-            // (pixels beyond the rectangle's end read as factor 0, noise 0: 0 - half clamps to 0, so their bits stay 0)
+            for (int q = 0; q < 16; q++) v[q] = dither_crush4(v[q], z[q], s); // (pixels beyond the rectangle's end read as factor 0, noise 0: their bits stay 0)
           }
           unsigned long long *dst = field + (size_t)run * b;
           const uint32_t words = field_words(count, b);
@@ -306,11 +213,7 @@ namespace limg_hip
       const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
       const unsigned long long payloadWords = h->payloadWords;
       const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES];
-      const bool ok = h->magic == LIMG_HIP_STREAM_MAGIC && h->version == LIMG_HIP_STREAM_VERSION_BLOCKED && h->sizeX == p.sizeX && h->sizeY == p.sizeY &&
-                      h->blocksX == p.blocksX && h->blocksY == p.blocksY && (h->channels == 3 || h->channels == 4) && nRects >= 1u && nRects <= p.nBlocks &&
-                      payloadWords <= (unsigned long long)p.nBlocks * 24ull && // 3 fields x 8 words at most per block: bounds the sum below
-                      sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry + payloadWords * 8ull <= p.streamBytes;
-      if (!ok)
+      if (!(nRects >= 1u && nRects <= p.nBlocks && stream_header_ok(h, LIMG_HIP_STREAM_VERSION_BLOCKED, kRectEntry, nRects, p)))
       {
         if (tid == 0 && blockIdx.x == 0) refuse(p, 1u);
         return;
@@ -426,38 +329,12 @@ namespace limg_hip
             fieldByte += (unsigned long long)field_words(n, b) * 8ull;
           }
         }
-        // the decoder's constants (src/limg_decode.h:139-196 / :40-101), as k_blocked_store prepares them
-        int nn[3][4], mc[3][4];
-#pragma unroll
-        for (int f = 0; f < 3; f++)
-#pragma unroll
-          for (int c = 0; c < 4; c++)
-          {
-            const int mnv = (int)(int16_t)(ev[f * 4 + (c >> 1)] >> (16 * (c & 1))), mxv = (int)(int16_t)(ev[f * 4 + 2 + (c >> 1)] >> (16 * (c & 1)));
-            int nv = mxv - mnv, m = mnv;
-            if (c < 3) { if (shift[f] > 7u) { nv = 0; if (f > 0) m = 0; } }
-            else if (channels == 3u) { nv = 0; m = 0xFFFF; }
-            nn[f][c] = nv;
-            mc[f][c] = (int)(((uint32_t)m << 8) + 128u);
-          }
-        const int mulA = (int)shift_mul(shift[0]), mulB = (int)shift_mul(shift[1]), mulC = (int)shift_mul(shift[2]);
+        const A16 k = a16_constants([&](int v, int c) { return (int)(int16_t)(ev[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, (int)channels);
         uint32_t px[8];
 #pragma unroll
         for (int i = 0; i < 8; i++)
-        {
-          const int dA = (int)((uint32_t)(packed[0] >> (i * bb[0])) & ((1u << bb[0]) - 1u)) * mulA;
-          const int dB = (int)((uint32_t)(packed[1] >> (i * bb[1])) & ((1u << bb[1]) - 1u)) * mulB;
-          const int dC = (int)((uint32_t)(packed[2] >> (i * bb[2])) & ((1u << bb[2]) - 1u)) * mulC;
-          uint32_t decoded = 0;
-#pragma unroll
-          for (int c = 0; c < 4; c++)
-          {
-            int est = (mad_i24(dA, nn[0][c], mc[0][c]) >> 8) + (mad_i24(dB, nn[1][c], mc[1][c]) >> 8) + (mad_i24(dC, nn[2][c], mc[2][c]) >> 8);
-            est = est < 0 ? 0 : (est > 255 ? 255 : est);
-            decoded |= (uint32_t)est << (8 * c);
-          }
-          px[i] = decoded;
-        }
+          px[i] = a16_pixel(k, (uint32_t)(packed[0] >> (i * bb[0])) & ((1u << bb[0]) - 1u), (uint32_t)(packed[1] >> (i * bb[1])) & ((1u << bb[1]) - 1u),
+                            (uint32_t)(packed[2] >> (i * bb[2])) & ((1u << bb[2]) - 1u));
         uint32_t *dst = p.out + (size_t)y * p.sizeX + x0;
         if (cnt == 8u && rowAligned)
         { // a wave's stores: 8 row pieces of 8 x 32 contiguous bytes
@@ -473,33 +350,24 @@ namespace limg_hip
       }
     }
 
-    int device_cus()
-    {
-      static int cus = 0;
-      if (!cus)
-      {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-      }
-      return cus;
-    }
   }
 
-  void launch_blocked_stream_pack(const BlockedStreamParams &p, hipStream_t s)
+  void launch_blocked_stream_pack(const BlockedStreamParams &p, int cus, hipStream_t s)
   {
     if (p.nRegions == 0) return;
     hipLaunchKernelGGL(k_bstream_sizes<false>, dim3(p.nTiles), dim3(kRectTile), 0, s, p);
-    hipLaunchKernelGGL(k_bstream_scan, dim3(1), dim3(1024), 0, s, p);
+    const StreamHeaderInfo info = { LIMG_HIP_STREAM_VERSION_BLOCKED, p.sizeX, p.sizeY, p.channels, p.errorFactor, p.blocksX, p.blocksY, p.flags | LIMG_HIP_STREAM_FLAG_MERGED,
+                                    p.nRegions, (uint32_t)kRectEntry, p.nRegions };
+    hipLaunchKernelGGL(k_stream_tile_scan<2>, dim3(1), dim3(1024), 0, s, p.tiles, p.nTiles, p.stream, info); // columns: payload words, runs (runs <= blocks)
     hipLaunchKernelGGL(k_bstream_sizes<true>, dim3(p.nTiles), dim3(kRectTile), 0, s, p);
     // one lane per run of 64 pixels; an image has at most blocks + rectangles runs.  Eight workgroups of four waves per CU, striding
-    const uint64_t runsMax = (uint64_t)p.blocksX * p.blocksY + p.nRegions, need = (runsMax + 255u) / 256u, slots = (uint64_t)device_cus() * 8u;
+    const uint64_t runsMax = (uint64_t)p.blocksX * p.blocksY + p.nRegions, need = (runsMax + 255u) / 256u, slots = (uint64_t)cus * 8u;
     hipLaunchKernelGGL(k_bstream_pack, dim3((uint32_t)(need < slots ? need : slots)), dim3(256), 0, s, p);
   }
 
-  void launch_blocked_stream_decode(const BlockedDecodeParams &p, hipStream_t s)
+  void launch_blocked_stream_decode(const BlockedDecodeParams &p, int cus, hipStream_t s)
   {
-    const uint32_t slots = (uint32_t)device_cus() * 8u;
+    const uint32_t slots = (uint32_t)cus * 8u;
     const uint32_t needMap = (p.nBlocks + 255u) / 256u; // at most nBlocks rectangles, 64 per wave
     hipLaunchKernelGGL(k_bstream_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, p);
     const uint32_t units = ((p.blocksX + 7u) / 8u) * p.blocksY, need = (units + 3u) / 4u;

@@ -141,7 +141,7 @@ struct limg_hip_context
   uint32_t chainEf = 0;
   DevBuf commWords; // [0] this rank's value, [1] its chain base, [8 ...] the all-gathered values
   DevBuf streamFac, streamTiles, streamUnits, streamStatus, streamBuf; // stream packer: 3 factor planes, per-tile payload words; decode status word; host-entry staging
-  // version 2 stream of the merged-block encoder (limg_hip_blocked_stream_api.hip): per rectangle its first 64-pixel run, per tile of rectangles its totals; the
+  // version 2 stream of the merged-block encoder (limg_hip_stream_api.hip): per rectangle its first 64-pixel run, per tile of rectangles its totals; the
   // decoder's block -> rectangle map and its per-call words
   DevBuf bsUnits, bsTiles, bsMap, bsState;
   size_t blockedScratchCap = 0;              // plane stride of bFac in the last merged-block encode (BlockedParams::scratchCap)

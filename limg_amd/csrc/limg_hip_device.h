@@ -1,11 +1,11 @@
 // limg_hip_device.h -- device helpers shared by the kernel files (limg_hip_kernels.hip and the headers it includes: 8x8 blocks; limg_hip_blocked.hip: merged regions):
-// wave64 reductions, the x86 float semantics of the reference's SSE path (DPPS order, RSQRTPS table, sign-normalised unit vectors), the generic
+// the wave / instruction helpers of limg_hip_wave.h, wave64 reductions, the x86 float semantics of the reference's SSE path (DPPS order, RSQRTPS table, sign-normalised unit vectors), the generic
 // 32-bit bit-crush trial (a9) and the literal shift searches (a10-a12).  Everything lives in an anonymous namespace: each including
 // translation unit gets its own copy (including the 4 KiB RSQRTPS table).  Reference file:line citations are at each function.
 #ifndef LIMG_HIP_DEVICE_H
 #define LIMG_HIP_DEVICE_H
 
-#include "limg_hip_internal.h"
+#include "limg_hip_wave.h"
 #include "limg_rsqrt_x86_table.h"
 
 #include <float.h>
@@ -19,14 +19,6 @@ namespace limg_hip
     enum : uint32_t { kZeroA = 1u, kZeroB = 2u, kZeroC = 4u, kValid = 8u };
 
     // ---- wave64 helpers -------------------------------------------------------------------------------------------
-    __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-    __device__ __forceinline__ void wave_lds_fence()
-    {
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-
     template <int CTRL, int ROWMASK>
     __device__ __forceinline__ int dpp(int oldv, int v) { return __builtin_amdgcn_update_dpp(oldv, v, CTRL, ROWMASK, 0xF, false); }
 
@@ -72,13 +64,6 @@ namespace limg_hip
     }
 
     // ---- integer stage ------------------------------------------------------------------------------------------------
-    // (1 << s) + decode_bias(s)  (src/limg_bit_crush_simd.h:611-619): 1,2,4,8,17,36,85,255,256
-    __device__ __forceinline__ uint32_t shift_mul(uint32_t s)
-    {
-      const uint64_t biasPacked = (1ull << 28) | (4ull << 35) | (21ull << 42) | (127ull << 49); // 7 bits per shift value
-      return (1u << s) + (uint32_t)((biasPacked >> (7 * s)) & 127u);
-    }
-
     struct RecU // wave-uniform integer view of a record for the reconstruct (RGB lanes only; alpha never reaches the trial error)
     {
       int nA[3], nB[3], nC[3], mA[3], mB[3], mC[3];
@@ -116,14 +101,6 @@ namespace limg_hip
       blockError = be;
       return !any_fail && ((uint64_t)be * 16ull < maxBlockN);
     }
-
-    // 24-bit integer multiplies (full rate; v_mul_lo_u32 is quarter rate).  Operands here always fit: see kRecordLimit.
-    __device__ __forceinline__ int mul_i24(int a, int b) { int r; asm("v_mul_i32_i24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-    __device__ __forceinline__ uint32_t mul_u24(uint32_t a, uint32_t b) { uint32_t r; asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-    // same with a wave-uniform factor straight from its SGPR (src0 of the VOP2 form): no v_mov to bring it into a VGPR first
-    __device__ __forceinline__ uint32_t mul_u24_uniform(uint32_t a, uint32_t uniformB) { uint32_t r; asm("v_mul_u32_u24 %0, %2, %1" : "=v"(r) : "v"(a), "s"(uniformB)); return r; }
-    __device__ __forceinline__ int med3_i32(int a, int b, int c) { int r; asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-    __device__ __forceinline__ int mad_i24(int a, int b, int c) { int r; asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 
     // a10-a12 search driver; everything in here is wave-uniform
     // BE = type of the block error (32 bits suffice for an 8x8 block; merged regions of any size use 64)

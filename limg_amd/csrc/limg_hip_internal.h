@@ -195,7 +195,7 @@ namespace limg_hip
     const uint8_t *scratchFac, *noise;
     uint8_t *stream;
     uint32_t *units; // nRegions + 1: every rectangle's first run (exclusive prefix of ceil(n / 64)); [nRegions] = all runs
-    uint32_t *tiles; // per tile of 256 rectangles { payload words, runs }: totals, then (k_bstream_scan) their exclusive prefix
+    uint32_t *tiles; // per tile of 256 rectangles { payload words, runs }: totals, then (k_stream_tile_scan<2>) their exclusive prefix
   };
   struct BlockedDecodeParams
   {
@@ -207,11 +207,12 @@ namespace limg_hip
     uint32_t *status; // the context's sticky stream status word: bit 0 header mismatch, bit 1 inconsistent table or payload offsets
     uint32_t *state;  // this call's words (zeroed in front of it): [0] blocks claimed by the rectangles, [1] non-0 = the stream is refused
   };
-  void launch_blocked_stream_pack(const BlockedStreamParams &p, hipStream_t s);
-  void launch_blocked_stream_decode(const BlockedDecodeParams &p, hipStream_t s);
+  // (cus: the device's compute units, as the context knows them -- limg_hip_context::persistentWorkgroups / 5; the persistent launches size themselves by it)
+  void launch_blocked_stream_pack(const BlockedStreamParams &p, int cus, hipStream_t s);
+  void launch_blocked_stream_decode(const BlockedDecodeParams &p, int cus, hipStream_t s);
 
   void launch_stream_pack(const StreamParams &p, hipStream_t s);
-  void launch_stream_decode(const DecodeParams &p, hipStream_t s);
+  void launch_stream_decode(const DecodeParams &p, int cus, hipStream_t s);
 
   void launch_synth_random_gradient(uint32_t *out, uint32_t w, uint32_t h, uint64_t seed, int opaque, uint32_t y0, hipStream_t s);
   void launch_synth_photo_noise(uint32_t *out, uint32_t w, uint32_t h, uint64_t seed, uint32_t y0, hipStream_t s);

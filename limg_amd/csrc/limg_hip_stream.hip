@@ -19,7 +19,7 @@
 // 8 pixels of one block row: 8 B of each factor plane, 32 B of the decoded image, b bytes of each payload field.
 // Decode: the same lane mapping, but persistent -- a wave strides over units of 64 blocks on its own, nothing synchronises
 // across waves (k_stream_decode).
-#include "limg_hip_internal.h"
+#include "limg_hip_stream_format.h"
 
 namespace limg_hip
 {
@@ -30,42 +30,6 @@ namespace limg_hip
     constexpr int kGroupBytes = 8 * 192; // payload of 8 blocks, worst case
     constexpr int kPackedLimit = 2700;   // |record value| up to which the packed decode's 16-bit terms are exact (limg_hip_search.h "a9, packed form": 3 * 2700 + 1 < 0x2000)
     typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
-
-    __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-    __device__ __forceinline__ int mad_i24(int a, int b, int c) { int r; asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-    __device__ __forceinline__ uint32_t mul_u24(uint32_t a, uint32_t b) { uint32_t r; asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-    __device__ __forceinline__ int med3_i32(int a, int b, int c) { int r; asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-    __device__ __forceinline__ int add3(int a, int b, int c) { int r; asm("v_add3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-    __device__ __forceinline__ uint32_t bfe(uint32_t v, uint32_t off, uint32_t width) { uint32_t r; asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(off), "v"(width)); return r; }
-    __device__ __forceinline__ uint32_t lshl_or(uint32_t a, uint32_t sh, uint32_t b) { uint32_t r; asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(sh), "v"(b)); return r; }
-    __device__ __forceinline__ void wave_lds_fence()
-    {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-
-    // (1 << s) + bias(s), src/limg_bit_crush_simd.h:611-619 / src/limg_decode.h:172-178
-    __device__ __forceinline__ uint32_t shift_mul(uint32_t s)
-    {
-      return s < 4 ? (1u << s) : (s == 4 ? 17u : (s == 5 ? 36u : (s == 6 ? 85u : (s == 7 ? 255u : 256u))));
-    }
-
-    // bits per pixel of the three factor fields + raw-escape mask: bA | bB << 8 | bC << 16 | rawMask << 24.
-    // mn3 / mx3: lane 3 (alpha) of dir{A,B,C}_{min|offset} / _{max|mag}.
-    __device__ __forceinline__ uint32_t field_bits(uint32_t shiftWord, const int mn3[3], const int mx3[3], int channels)
-    {
-      uint32_t r = 0;
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-      {
-        const uint32_t s = (shiftWord >> (8 * k)) & 0xFF;
-        uint32_t b = s >= 8 ? 0u : 8u - s;
-        if (s >= 8 && channels == 4 && mn3[k] != mx3[k]) { b = 8; r |= 1u << (24 + k); }
-        r |= b << (8 * k);
-      }
-      return r;
-    }
 
     __device__ __forceinline__ uint32_t words_of(uint32_t bits) { return (bits & 0xFF) + ((bits >> 8) & 0xFF) + ((bits >> 16) & 0xFF); }
 
@@ -80,8 +44,9 @@ namespace limg_hip
       uint32_t words = 0;
       if (g < p.nBlocks)
       {
-        const limg_hip_block_record &rec = p.records[g];
-        const int mn3[3] = { rec.dirA_min[3], rec.dirB_offset[3], rec.dirC_offset[3] }, mx3[3] = { rec.dirA_max[3], rec.dirB_mag[3], rec.dirC_mag[3] };
+        const uint4 *rp = reinterpret_cast<const uint4 *>(p.records + g) + 1; // skip avg[4]
+        int mn3[3], mx3[3];
+        alpha_lanes(rp[0], rp[1], rp[2], mn3, mx3);
         words = words_of(field_bits(p.shifts[g] & 0xFFFFFFu, mn3, mx3, (int)p.channels));
       }
 #pragma unroll
@@ -91,46 +56,10 @@ namespace limg_hip
       if (tid == 0) p.tileBase[blockIdx.x] = sWave[0] + sWave[1] + sWave[2] + sWave[3];
     }
 
-    // exclusive scan of the tile totals in place (one workgroup) + the header
-    __global__ __launch_bounds__(1024) void k_stream_scan(const StreamParams p)
+    // (between them: k_stream_tile_scan<1>, limg_hip_stream_format.h -- exclusive scan of the tile totals in place + the header)
+    __host__ __device__ inline StreamHeaderInfo header_info(const StreamParams &p)
     {
-      __shared__ unsigned long long sWave[16];
-      __shared__ unsigned long long sCarry;
-      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-      if (tid == 0) sCarry = 0;
-      __syncthreads();
-      for (uint32_t base = 0; base < p.nTiles; base += 1024)
-      {
-        const uint32_t i = base + tid;
-        const unsigned long long v = i < p.nTiles ? p.tileBase[i] : 0u;
-        unsigned long long incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1)
-        {
-          const unsigned long long up = (unsigned long long)__shfl_up((long long)incl, off, 64);
-          if (lane >= off) incl += up;
-        }
-        if (lane == 63) sWave[wave] = incl;
-        __syncthreads();
-        unsigned long long pre = sCarry;
-        for (int w = 0; w < wave; w++) pre += sWave[w];
-        // entry.payloadWord is 32 bits: the host refuses images whose worst-case payload would not fit (limg_hip_stream_bound)
-        if (i < p.nTiles) p.tileBase[i] = (uint32_t)(pre + incl - v);
-        __syncthreads();
-        if (tid == 1023) sCarry = pre + incl;
-        __syncthreads();
-      }
-      if (tid == 0)
-      {
-        limg_hip_stream_header h;
-        h.magic = LIMG_HIP_STREAM_MAGIC; h.version = LIMG_HIP_STREAM_VERSION;
-        h.sizeX = p.sizeX; h.sizeY = p.sizeY; h.channels = p.channels; h.errorFactor = p.errorFactor;
-        h.blocksX = p.blocksX; h.blocksY = p.blocksY;
-        h.payloadWords = sCarry;
-        h.totalBytes = sizeof(limg_hip_stream_header) + (unsigned long long)p.nBlocks * kEntry + sCarry * 8ull;
-        h.flags = p.flags; h.reserved[0] = h.reserved[1] = h.reserved[2] = 0;
-        *reinterpret_cast<limg_hip_stream_header *>(p.stream) = h;
-      }
+      return { LIMG_HIP_STREAM_VERSION, p.sizeX, p.sizeY, p.channels, p.errorFactor, p.blocksX, p.blocksY, p.flags, p.nBlocks, (uint32_t)kEntry, 0u };
     }
 
     __global__ __launch_bounds__(kTile) void k_stream_pack(const StreamParams p)
@@ -146,9 +75,9 @@ namespace limg_hip
       {
         const uint4 *rp = reinterpret_cast<const uint4 *>(p.records + g) + 1; // skip avg[4]
         const uint4 r0 = rp[0], r1 = rp[1], r2 = rp[2];                        // {dirA_min, dirA_max}, {dirB_offset, dirB_mag}, {dirC_offset, dirC_mag}
-        const int mn3[3] = { (int)(int16_t)(r0.y >> 16), (int)(int16_t)(r1.y >> 16), (int)(int16_t)(r2.y >> 16) };
-        const int mx3[3] = { (int)(int16_t)(r0.w >> 16), (int)(int16_t)(r1.w >> 16), (int)(int16_t)(r2.w >> 16) };
         const uint32_t sw = p.shifts[g] & 0xFFFFFFu;
+        int mn3[3], mx3[3];
+        alpha_lanes(r0, r1, r2, mn3, mx3);
         bits = field_bits(sw, mn3, mx3, (int)p.channels);
         words = words_of(bits);
         uint32_t *e = sEntry + tid * (kEntry / 4);
@@ -156,13 +85,7 @@ namespace limg_hip
         e[8] = r2.x; e[9] = r2.y; e[10] = r2.z; e[11] = r2.w;
         e[12] = sw | (bits & 0xFF000000u);
       }
-      uint32_t incl = words;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1)
-      {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
-        if (lane >= off) incl += up;
-      }
+      const uint32_t incl = wave_scan_inclusive(words, lane);
       if (lane == 63) sWave[wave] = incl;
       __syncthreads();
       uint32_t off = p.tileBase[tile] + incl - words;
@@ -307,13 +230,7 @@ namespace limg_hip
         if (wave == 0)
         { // exclusive prefix over the 128 partial sums (slab-major = strip order): a lane owns two neighbours
           const unsigned long long a0 = sPart[2 * lane], a1 = sPart[2 * lane + 1];
-          unsigned long long in2 = a0 + a1;
-#pragma unroll
-          for (int off = 1; off < 64; off <<= 1)
-          {
-            const unsigned long long up = (unsigned long long)__shfl_up((long long)in2, off, 64);
-            if (lane >= off) in2 += up;
-          }
+          const unsigned long long in2 = wave_scan_inclusive(a0 + a1, lane);
           const unsigned long long ex = in2 - a0 - a1;
           sPart[2 * lane] = ex; sPart[2 * lane + 1] = ex + a0;
           if (lane == 63) sRound = in2;
@@ -343,17 +260,7 @@ namespace limg_hip
         if (tid == 0) sCarry = carry + sRound;
         __syncthreads();
       }
-      if (tid == 0)
-      {
-        limg_hip_stream_header h;
-        h.magic = LIMG_HIP_STREAM_MAGIC; h.version = LIMG_HIP_STREAM_VERSION;
-        h.sizeX = p.sizeX; h.sizeY = p.sizeY; h.channels = p.channels; h.errorFactor = p.errorFactor;
-        h.blocksX = p.blocksX; h.blocksY = p.blocksY;
-        h.payloadWords = sCarry;
-        h.totalBytes = sizeof(limg_hip_stream_header) + (unsigned long long)p.nBlocks * kEntry + sCarry * 8ull;
-        h.flags = p.flags; h.reserved[0] = h.reserved[1] = h.reserved[2] = 0;
-        *reinterpret_cast<limg_hip_stream_header *>(p.stream) = h;
-      }
+      if (tid == 0) write_stream_header(p.stream, header_info(p), sCarry);
     }
 
     // 8 bytes (lo = pixels 0..3, hi = 4..7), each holding its value in the TOP b bits (sh = 8 - b; raw-escaped fields: b = 8) -> the 8 values in 8 b consecutive bits
@@ -398,8 +305,8 @@ namespace limg_hip
       if (strip >= p.nStrips) return;
       const uint32_t by = strip / p.stripsX, sx = strip - by * p.stripsX, bx = sx * 32u + (uint32_t)j;
       if (bx >= p.blocksX) return;
-      const int mn3[3] = { (int)(int16_t)(sm.r0.y >> 16), (int)(int16_t)(sm.r1.y >> 16), (int)(int16_t)(sm.r2.y >> 16) };
-      const int mx3[3] = { (int)(int16_t)(sm.r0.w >> 16), (int)(int16_t)(sm.r1.w >> 16), (int)(int16_t)(sm.r2.w >> 16) };
+      int mn3[3], mx3[3];
+      alpha_lanes(sm.r0, sm.r1, sm.r2, mn3, mx3);
       o.bits = field_bits(sm.sw, mn3, mx3, (int)p.channels);
 #pragma unroll
       for (int k = 0; k < 3; k++)
@@ -432,7 +339,7 @@ namespace limg_hip
         const uint32_t inStrip = min(32u, p.blocksX - sx * 32u);
         const uint32_t bits = rows.bits, words = words_of(bits);
         // exclusive prefix of the words over the strip's blocks (both halves compute it)
-        uint32_t incl = words;
+        uint32_t incl = words; // (wave_scan_inclusive over 32 lanes, written out: through a width parameter there this kernel's measured schedule changes)
 #pragma unroll
         for (int off = 1; off < 32; off <<= 1)
         {
@@ -596,11 +503,7 @@ namespace limg_hip
       // every wave validates the header it is about to trust (scalar loads; a mismatch raises the context's status word)
       const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
       const unsigned long long payloadWords = h->payloadWords;
-      const bool ok = h->magic == LIMG_HIP_STREAM_MAGIC && h->version == LIMG_HIP_STREAM_VERSION && h->sizeX == p.sizeX && h->sizeY == p.sizeY &&
-                      h->blocksX == p.blocksX && h->blocksY == p.blocksY && (h->channels == 3 || h->channels == 4) &&
-                      payloadWords <= (unsigned long long)p.nBlocks * 24ull && // 3 fields x 8 words at most per block: bounds the product below
-                      sizeof(limg_hip_stream_header) + (unsigned long long)p.nBlocks * kEntry + payloadWords * 8ull <= p.streamBytes;
-      if (!ok)
+      if (!stream_header_ok(h, LIMG_HIP_STREAM_VERSION, kEntry, p.nBlocks, p))
       {
         if (tid == 0) atomicOr(p.status, 1u);
         return;
@@ -622,7 +525,7 @@ namespace limg_hip
         const uint32_t inUnit = min(64u, p.nBlocks - unit * 64u);
         const uint32_t sw = e[12];
         // ---- 1. what the first payload request needs: field widths and offsets ----
-        {
+        { // (entry_bits(sw), written out: called through the function this kernel's hand-counted schedule changes)
           uint32_t bits = 0;
 #pragma unroll
           for (int f = 0; f < 3; f++)
@@ -699,7 +602,8 @@ namespace limg_hip
           for (int f = 0; f < 3; f++)
           {
             const uint32_t s = min((sw >> (8 * f)) & 0xFFu, 8u);
-            const int fmul = (int)shift_mul(s);
+            // (shift_mul(s) as a chain of selects, in place: with the packed-constant form of limg_hip_wave.h this kernel's hand-counted schedule changes)
+            const int fmul = (int)(s < 4 ? (1u << s) : (s == 4 ? 17u : (s == 5 ? 36u : (s == 6 ? 85u : (s == 7 ? 255u : 256u)))));
             mul |= (big ? (uint32_t)fmul : 1u) << (10 * f);
 #pragma unroll
             for (int c = 0; c < 4; c++)
@@ -847,21 +751,14 @@ namespace limg_hip
       return;
     }
     hipLaunchKernelGGL(k_stream_count, dim3(p.nTiles), dim3(kTile), 0, s, p);
-    hipLaunchKernelGGL(k_stream_scan, dim3(1), dim3(1024), 0, s, p);
+    hipLaunchKernelGGL(k_stream_tile_scan<1>, dim3(1), dim3(1024), 0, s, p.tileBase, p.nTiles, p.stream, header_info(p));
     hipLaunchKernelGGL(k_stream_pack, dim3(p.nTiles), dim3(kTile), 0, s, p);
   }
 
-  void launch_stream_decode(const DecodeParams &p, hipStream_t s)
+  void launch_stream_decode(const DecodeParams &p, int cus, hipStream_t s)
   {
     // persistent: one workgroup of four waves per residency slot (4 per CU), every wave strides over the units of 64 blocks
-    static int slots = 0;
-    if (!slots)
-    {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      slots = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount * 4 : 1024;
-    }
-    const uint32_t units = (p.nBlocks + 63u) / 64u, need = (units + 3u) / 4u;
-    hipLaunchKernelGGL(k_stream_decode, dim3(need < (uint32_t)slots ? need : (uint32_t)slots), dim3(kTile), 0, s, p);
+    const uint32_t units = (p.nBlocks + 63u) / 64u, need = (units + 3u) / 4u, slots = (uint32_t)cus * 4u;
+    hipLaunchKernelGGL(k_stream_decode, dim3(need < slots ? need : slots), dim3(kTile), 0, s, p);
   }
 }

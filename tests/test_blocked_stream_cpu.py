@@ -1,12 +1,13 @@
 """Version 2 of the "LMG3" stream (the merged-block encoder's rectangles) without a GPU: the host-only entries of the library, and the format text itself --
-tests/blocked_stream_ref.py packs the CPU oracle's merged-block encode into the container as include/limg_hip.h describes it and decodes it again; that round trip
+oracle/blocked_stream.py packs the CPU oracle's merged-block encode into the container as include/limg_hip.h describes it and decodes it again; that round trip
 equals the oracle's pDecoded, so the format carries everything a decoder needs, the raw-byte escape included."""
 import numpy as np
 import pytest
 
 import limg_amd
 
-import blocked_stream_ref as B
+from oracle import blocked_stream as B
+from blocked_stream_ref import small_cases, stream_flags
 
 
 @pytest.fixture(scope="module")
@@ -73,10 +74,10 @@ def test_abi_symbols(lib):
 def test_format_round_trip_on_the_cpu(lib, oracle):
     """decode(pack(oracle encode)) == the oracle's pDecoded over the small shape list and the option cases: the container as written in the header text is complete."""
     escaped = {}
-    for name, img, alpha, kw in B.small_cases(oracle):
+    for name, img, alpha, kw in small_cases(oracle):
         ch = 4 if alpha else 3
         want = oracle.blocked_encode3d(img, alpha, **kw)
-        stream, esc = B.pack(want, img, ch, oracle, error_factor=kw.get("error_factor", 100), flags=B.stream_flags(kw))
+        stream, esc = B.pack(want, img, ch, oracle, error_factor=kw.get("error_factor", 100), flags=stream_flags(kw))
         escaped[name] = esc
         h, w = img.shape
         assert limg_amd.blocked_stream_info(stream, lib) == (w, h, alpha, stream.size, len(want["regions"])), name

@@ -1,5 +1,5 @@
 """GPU parity of version 2 of the compact stream (the merged-block encoder's rectangles): the packer's bytes against the CPU restatement of the container
-(tests/blocked_stream_ref.py, written from the format text in include/limg_hip.h), the GPU decoder and an independent CPU decoder against the pDecoded plane of
+(oracle/blocked_stream.py, written from the format text in include/limg_hip.h), the GPU decoder and an independent CPU decoder against the pDecoded plane of
 the oracle's limg_blocked_encode3d_test, determinism, full-size images through the device entries, context memory, and malformed streams."""
 import numpy as np
 import pytest
@@ -7,7 +7,8 @@ import pytest
 import lib_axis as L
 from lib_axis import lib, lib_product  # noqa: F401  (fixtures: "test" / "product")
 import limg_amd
-import blocked_stream_ref as B
+from oracle import blocked_stream as B
+from blocked_stream_ref import small_cases, stream_flags
 
 pytestmark = pytest.mark.gpu
 
@@ -48,9 +49,9 @@ def _first_diffs(a, b):
 
 def test_bytes_roundtrip_and_independent_decode(gpu, oracle):
     saw_escape = False
-    for name, img, alpha, kw in B.small_cases(oracle):
+    for name, img, alpha, kw in small_cases(oracle):
         want = oracle.blocked_encode3d(img, alpha, **kw)
-        ref_stream, esc = B.pack(want, img, 4 if alpha else 3, oracle, error_factor=kw.get("error_factor", 100), flags=B.stream_flags(kw))
+        ref_stream, esc = B.pack(want, img, 4 if alpha else 3, oracle, error_factor=kw.get("error_factor", 100), flags=stream_flags(kw))
         got = _encode(gpu, img, alpha, kw)
         assert got.size == ref_stream.size, (name, got.size, ref_stream.size, _first_diffs(got, ref_stream))
         assert np.array_equal(got, ref_stream), (name, _first_diffs(got, ref_stream))
