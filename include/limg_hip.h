@@ -363,6 +363,40 @@ limg_hip_result limg_hip_blocked_last_stream(limg_hip_context *pCtx, uint8_t *pS
 limg_hip_result limg_hip_blocked_stream_info(const uint8_t *pStream, size_t streamBytes, size_t *pSizeX, size_t *pSizeY, int *pHasAlpha, size_t *pTotalBytes,
                                              size_t *pRectangles);
 
+/* ---- window decode: any pixel rectangle of a stream, either version -----------------------------------------------------------
+ * The table gives every block (version 1) or rectangle (version 2) its own payloadWord, so a region of the image decodes without the rest.
+ * Result: pOut[r * outStridePixels + c] = pixel (x0 + c, y0 + r) of what the version's full decoder writes, for 0 <= r < height, 0 <= c < width, bit for bit.
+ * NOTHING ELSE IS WRITTEN: not the outStridePixels - width pixels behind each row, not anything beyond the last row -- pOut may be a slice of a larger buffer
+ * (a tile atlas, a batch tensor).
+ * Window: any pixel rectangle inside the image; x0, y0, width, height need not be multiples of 8, and the window may cover the partial edge blocks of an image
+ * whose size is not in whole blocks.
+ * Errors, in this order: NULL context or pointer: limg_hip_error_ArgumentNull (before anything touches the device); width == 0, height == 0 or
+ * outStridePixels < width: limg_hip_error_InvalidParameter; a window that is not inside sizeX x sizeY: limg_hip_error_OutOfBounds.
+ * Alignment: pStream 16 bytes, as for the full decoders; pOut 4 bytes only.  A block row piece of 8 pixels leaves as two 16-byte stores where pOut is 16-byte aligned
+ * and outStridePixels and x0 are multiples of 4, otherwise as dword stores -- identical results.
+ * Validation: the header against the call's geometry and streamBytes, exactly as the full decoders.
+ *   Version 1: every table entry the window reads is checked as the full decoder checks its groups of 8 blocks: offsets in 64 bits, inside the payload, a
+ *   group's run no longer than 8 x 24 words.  A group that fails stores nothing (the other groups do), as in the full decoder.
+ *   Version 2: the WHOLE rectangle table is scanned (64 bytes per rectangle): every rectangle's geometry, shifts and payload extent are checked as by the full decoder,
+ *   and every block of the window must be claimed by exactly one rectangle.  Overlaps that lie wholly outside the window are NOT detected.  A stream that fails
+ *   is refused as a whole: nothing is written.
+ *   Either way limg_hip_check_device_status reports limg_hip_error_InvalidParameter, once.
+ * Cost: table entries and payload read, pixels stored and context memory are functions of the window's block range bx0 = x0 / 8 .. (x0 + width - 1) / 8 (likewise
+ * in y), not of the image -- with the one exception of version 2's table scan.  Version 2's block -> rectangle map covers the window's blocks only (4 bytes each).
+ * Thread safety as for the family: the _device forms are asynchronous on `stream` and want one context per HIP stream; the host forms block and take the context's mutex. */
+/* DEVICE pointers, asynchronous on `stream`.  sizeX / sizeY must match the header. */
+limg_hip_result limg_hip_decode_stream_window_device(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t x0, size_t y0,
+                                                     size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, void *stream);
+limg_hip_result limg_hip_blocked_decode_stream_window_device(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t x0,
+                                                             size_t y0, size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, void *stream);
+/* HOST pointers, blocking, under the context's mutex.  The image size comes from the header (limg_hip_stream_info / limg_hip_blocked_stream_info).  The whole stream
+ * is uploaded, the window is decoded into context staging (4 bytes per window pixel), the status is checked, and only then are the window's rows copied into the caller's
+ * stride: a refused stream leaves pOut untouched, in both versions. */
+limg_hip_result limg_hip_decode_stream_window(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,
+                                              uint32_t *pOut, size_t outStridePixels);
+limg_hip_result limg_hip_blocked_decode_stream_window(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,
+                                                      uint32_t *pOut, size_t outStridePixels);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ---------------------------------------------------------------------------------
  * The reference's only parallelism is row strips over a std::thread pool (src/limg.cpp:2105-2138); across GPUs the same strips
  * go one per rank.  Blocks are independent except for the dither chain, so the data path needs no collective in strip-restart mode (each strip

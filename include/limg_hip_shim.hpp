@@ -222,4 +222,15 @@ inline limg_result limg_blocked_decode(const uint8_t *pIn, const size_t size, ui
   return (limg_result)limg_hip_blocked_decode_stream(c, pIn, size, pOut, outPixelCapacity);
 }
 
+// A pixel rectangle of either version of the stream (as limg_decode_info accepts either): pOut[r * outStridePixels + c] = pixel (x + c, y + r) of what the version's
+// full decoder gives, and nothing else is written (limg_hip.h "window decode").
+inline limg_result limg_decode_window(const uint8_t *pIn, const size_t size, const size_t x, const size_t y, const size_t w, const size_t h, uint32_t *pOut, const size_t outStridePixels)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (limg_hip_blocked_stream_info(pIn, size, nullptr, nullptr, nullptr, nullptr, nullptr) == limg_hip_success)
+    return (limg_result)limg_hip_blocked_decode_stream_window(c, pIn, size, x, y, w, h, pOut, outStridePixels);
+  return (limg_result)limg_hip_decode_stream_window(c, pIn, size, x, y, w, h, pOut, outStridePixels);
+}
+
 #endif // LIMG_HIP_SHIM_HPP

@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "limg_hip_stream_info",
     "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
     "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
+    "limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device", "limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window",
     "limg_hip_blocked_encode3d", "limg_hip_blocked_encode3d_device", "limg_hip_blocked_regions", "limg_hip_blocked_timing", "limg_hip_blocked_kernel_timing", "limg_hip_blocked_match_bits", "limg_hip_host_blocked_matches",
     "limg_hip_host_blocked_merge", "limg_hip_host_blocked_match_words", "limg_hip_host_blocked_match_bits",
     "limg_hip_comm_unique_id", "limg_hip_comm_init", "limg_hip_comm_destroy", "limg_hip_comm_info", "limg_hip_gather_stream", "limg_hip_encode3d_single_chain_device",
@@ -194,6 +195,12 @@ def load_library(path=None):
     L.limg_hip_blocked_encode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_uint32, C.c_int]
     L.limg_hip_blocked_decode_stream.restype = C.c_int
     L.limg_hip_blocked_decode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    for name in ("limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device"):
+        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, sizeX, sizeY, x0, y0, width, height, out, outStridePixels, hipStream
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_size_t] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]
+    for name in ("limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window"):
+        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, x0, y0, width, height, out, outStridePixels
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_size_t] * 4 + [C.c_void_p, C.c_size_t]
     L.limg_hip_blocked_last_stream.restype = C.c_int
     L.limg_hip_blocked_last_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.limg_hip_blocked_stream_info.restype = C.c_int
@@ -582,6 +589,39 @@ class LimgHip:
 
     def blocked_decode_stream_device(self, stream, nbytes, w, h, out=None):
         return self._decode_stream_device("limg_hip_blocked_decode_stream_device", stream, nbytes, w, h, out)
+
+    # ---- window decode: any pixel rectangle of a stream (contract: include/limg_hip.h) ----
+    def _decode_stream_window(self, name, stream, x, y, w, h, out):
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        if out is None:
+            out = np.zeros((h, w), dtype=np.uint32)
+        assert out.dtype == np.uint32 and out.ndim == 2 and out.strides[1] == 4 and out.strides[0] % 4 == 0, "out: uint32 rows, pixels contiguous"
+        self._stream_call(name, _np_ptr(stream), stream.size, x, y, w, h, _np_ptr(out), out.strides[0] // 4)
+        return out
+
+    def _decode_stream_window_device(self, name, stream, nbytes, W, H, x, y, w, h, out, out_stride):
+        import torch
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
+        if out_stride is None:
+            out_stride = out.stride(0) if out.dim() == 2 else w
+        self._stream_call(name, C.c_void_p(stream.data_ptr()), int(nbytes), W, H, x, y, w, h, C.c_void_p(out.data_ptr()), int(out_stride), self._stream())
+        return out
+
+    def decode_stream_window(self, stream, x, y, w, h, out=None):
+        """host stream bytes -> pixels (x .. x + w - 1, y .. y + h - 1) as numpy uint32 (h, w); `out`: a uint32 view (rows may be strided) that receives them"""
+        return self._decode_stream_window("limg_hip_decode_stream_window", stream, x, y, w, h, out)
+
+    def blocked_decode_stream_window(self, stream, x, y, w, h, out=None):
+        return self._decode_stream_window("limg_hip_blocked_decode_stream_window", stream, x, y, w, h, out)
+
+    def decode_stream_window_device(self, stream, nbytes, W, H, x, y, w, h, out=None, out_stride=None):
+        """stream: torch uint8 CUDA tensor holding a stream of a W x H image; out: torch int32 CUDA tensor whose first element receives pixel (x, y), rows out_stride
+        pixels apart (default: out's own row stride); only the window's pixels are written.  Asynchronous on torch's current stream."""
+        return self._decode_stream_window_device("limg_hip_decode_stream_window_device", stream, nbytes, W, H, x, y, w, h, out, out_stride)
+
+    def blocked_decode_stream_window_device(self, stream, nbytes, W, H, x, y, w, h, out=None, out_stride=None):
+        return self._decode_stream_window_device("limg_hip_blocked_decode_stream_window_device", stream, nbytes, W, H, x, y, w, h, out, out_stride)
 
     def check(self):
         _check(self.lib.limg_hip_check_device_status(self.ctx), "limg_hip_check_device_status")

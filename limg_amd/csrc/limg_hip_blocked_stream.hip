@@ -24,22 +24,6 @@ namespace limg_hip
   namespace
   {
     constexpr int kRectTile = 256;
-    constexpr int kRectEntry = 64;
-    constexpr uint32_t kNoRect = 0xFFFFFFFFu;
-
-    // pixels of a rectangle: 8 rx x 8 ry clipped to the image (src/limg.cpp:1722-1740)
-    __device__ __forceinline__ uint32_t rect_pixels(uint32_t sizeX, uint32_t sizeY, uint32_t blocksX, uint32_t blocksY, uint32_t ox, uint32_t oy, uint32_t rx, uint32_t ry, uint32_t &wpx)
-    {
-      uint32_t hpx = ry * kBlock;
-      wpx = rx * kBlock;
-      if (ox + rx == blocksX && (sizeX % kBlock)) wpx = wpx - kBlock + sizeX % kBlock;
-      if (oy + ry == blocksY && (sizeY % kBlock)) hpx = hpx - kBlock + sizeY % kBlock;
-      return wpx * hpx;
-    }
-
-    __device__ __forceinline__ uint32_t field_words(uint32_t n, uint32_t b) { return (uint32_t)(((unsigned long long)n * b + 63ull) >> 6); }
-    __device__ __forceinline__ uint32_t rect_words(uint32_t n, uint32_t bits) { return field_words(n, bits & 0xFFu) + field_words(n, (bits >> 8) & 0xFFu) + field_words(n, (bits >> 16) & 0xFFu); }
-
     // ---- pack ------------------------------------------------------------------------------------------------------------------------
     struct RectSize { uint32_t bits, words, runs, sw; };
     __device__ __forceinline__ RectSize rect_size(const BlockedStreamParams &p, uint32_t r)
@@ -199,8 +183,6 @@ namespace limg_hip
     }
 
     // ---- decode ----------------------------------------------------------------------------------------------------------------------
-    __device__ __forceinline__ uint32_t ld_volatile(const uint32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-
     __device__ __forceinline__ void refuse(const BlockedDecodeParams &p, uint32_t bit)
     {
       atomicOr(p.state + 1, 1u);

@@ -211,6 +211,24 @@ namespace limg_hip
   void launch_blocked_stream_pack(const BlockedStreamParams &p, int cus, hipStream_t s);
   void launch_blocked_stream_decode(const BlockedDecodeParams &p, int cus, hipStream_t s);
 
+  // ---- window decode, both versions (limg_hip_stream_window.hip): a pixel rectangle of the image into a caller's stride ----
+  struct WindowDecodeParams
+  {
+    uint32_t sizeX, sizeY, blocksX, blocksY, nBlocks; // the image (what the header is checked against)
+    const uint8_t *stream;
+    unsigned long long streamBytes;
+    uint32_t x0, y0, width, height; // the window, pixels: inside the image, not empty
+    uint32_t bx0, by0, wbx, wby;    // ... and its block range: blocks bx0 .. bx0 + wbx - 1 of block rows by0 .. by0 + wby - 1
+    uint32_t *out;                  // pixel (x0 + c, y0 + r) at out[r * outStride + c]
+    unsigned long long outStride;
+    uint32_t vecOut;                // a block row piece that lies wholly inside the window may leave as two 16-byte stores (out 16-byte aligned, outStride % 4 == 0, x0 % 4 == 0)
+    uint32_t *map;                  // version 2: per block of the window the rectangle that covers it (~0: none yet)
+    uint32_t *status;               // the context's sticky stream status word, bits as in DecodeParams / BlockedDecodeParams
+    uint32_t *state;                // version 2: this call's words (zeroed in front of it): [0] window blocks claimed, [1] non-0 = the stream is refused
+  };
+  void launch_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s);
+  void launch_blocked_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s);
+
   void launch_stream_pack(const StreamParams &p, hipStream_t s);
   void launch_stream_decode(const DecodeParams &p, int cus, hipStream_t s);
 

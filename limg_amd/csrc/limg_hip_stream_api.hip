@@ -130,6 +130,55 @@ namespace
     c->packTimed = true;
     return pBytes ? stream_total_bytes(dStream, s, pBytes) : limg_hip_success;
   }
+
+  // ---- window decode: limg_hip_*decode_stream_window* (kernels: limg_hip_stream_window.hip) ----
+  // the checks and the parameters the two versions share; `bound`: the version's limg_hip_*stream_bound(sizeX, sizeY)
+  limg_hip_result window_params(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width,
+                                size_t height, uint32_t *pOut, size_t outStridePixels, hipStream_t s, WindowDecodeParams &wp)
+  {
+    if (width == 0 || height == 0 || outStridePixels < width || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
+    if (((uintptr_t)pStream & 15u) != 0 || ((uintptr_t)pOut & 3u) != 0) return limg_hip_error_InvalidParameter;
+    if (x0 >= sizeX || width > sizeX - x0 || y0 >= sizeY || height > sizeY - y0) return limg_hip_error_OutOfBounds;
+    HIP_TRY(hipSetDevice(c->device));
+    const limg_hip_result r = ensure_stream_status(c, s);
+    if (r != limg_hip_success) return r;
+    memset(&wp, 0, sizeof(wp));
+    wp.sizeX = (uint32_t)sizeX; wp.sizeY = (uint32_t)sizeY;
+    wp.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); wp.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
+    wp.nBlocks = wp.blocksX * wp.blocksY;
+    wp.stream = pStream; wp.streamBytes = streamBytes;
+    wp.x0 = (uint32_t)x0; wp.y0 = (uint32_t)y0; wp.width = (uint32_t)width; wp.height = (uint32_t)height;
+    wp.bx0 = (uint32_t)(x0 / kBlock); wp.by0 = (uint32_t)(y0 / kBlock);
+    wp.wbx = (uint32_t)((x0 + width - 1) / kBlock) - wp.bx0 + 1; wp.wby = (uint32_t)((y0 + height - 1) / kBlock) - wp.by0 + 1;
+    wp.out = pOut; wp.outStride = outStridePixels;
+    wp.vecOut = ((uintptr_t)pOut & 15u) == 0 && (outStridePixels & 3u) == 0 && (x0 & 3u) == 0;
+    wp.status = (uint32_t *)c->streamStatus.p;
+    return limg_hip_success;
+  }
+
+  // info(&sizeX, &sizeY, &total): the version's header check.  deviceDecode(dStream, total, sizeX, sizeY, dOut): into context staging at stride `width`; only a stream
+  // that passed reaches pOut
+  template <class INFO, class DECODE>
+  limg_hip_result decode_window_host(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height, uint32_t *pOut,
+                                     size_t outStridePixels, INFO &&info, DECODE &&deviceDecode)
+  {
+    if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    if (width == 0 || height == 0 || outStridePixels < width) return limg_hip_error_InvalidParameter;
+    size_t sizeX = 0, sizeY = 0, total = 0;
+    limg_hip_result r = info(&sizeX, &sizeY, &total);
+    if (r != limg_hip_success) return r;
+    if (total > streamBytes) return limg_hip_error_OutOfBounds;
+    if (x0 >= sizeX || width > sizeX - x0 || y0 >= sizeY || height > sizeY - y0) return limg_hip_error_OutOfBounds;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
+    if ((r = c->planes.ensure(width * height * 4)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice));
+    if ((r = deviceDecode((const uint8_t *)c->streamBuf.p, total, sizeX, sizeY, (uint32_t *)c->planes.p)) != limg_hip_success) return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy2D(pOut, outStridePixels * 4, c->planes.p, width * 4, width * 4, height, hipMemcpyDeviceToHost));
+    return limg_hip_success;
+  }
 }
 
 extern "C"
@@ -348,5 +397,59 @@ extern "C"
     return decode_stream_host(c, pStream, streamBytes, pOut, outPixels, sizeX, sizeY, total, [&](const uint8_t *dStream, size_t bytes, uint32_t *dOut, size_t w, size_t h) {
       return limg_hip_blocked_decode_stream_device(c, dStream, bytes, dOut, w, h, nullptr);
     });
+  }
+
+  // ---- window decode, both versions ----
+  limg_hip_result limg_hip_decode_stream_window_device(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t x0, size_t y0,
+                                                       size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, void *stream)
+  {
+    if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
+    hipStream_t s = (hipStream_t)stream;
+    WindowDecodeParams wp;
+    const limg_hip_result r = window_params(c, pStream, streamBytes, sizeX, sizeY, limg_hip_stream_bound(sizeX, sizeY), x0, y0, width, height, pOut, outStridePixels, s, wp);
+    if (r != limg_hip_success) return r;
+    if (streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
+    launch_stream_window_decode(wp, device_cus(c), s);
+    HIP_TRY(hipGetLastError());
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_window_device(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t x0, size_t y0,
+                                                               size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, void *stream)
+  {
+    if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
+    hipStream_t s = (hipStream_t)stream;
+    WindowDecodeParams wp;
+    limg_hip_result r = window_params(c, pStream, streamBytes, sizeX, sizeY, limg_hip_blocked_stream_bound(sizeX, sizeY), x0, y0, width, height, pOut, outStridePixels, s, wp);
+    if (r != limg_hip_success) return r;
+    const size_t mapBytes = (size_t)wp.wbx * wp.wby * 4; // the window's blocks, not the image's
+    if ((r = c->bsMap.ensure(mapBytes)) != limg_hip_success) return r;
+    if ((r = c->bsState.ensure(64)) != limg_hip_success) return r;
+    HIP_TRY(hipMemsetAsync(c->bsMap.p, 0xFF, mapBytes, s)); // no block has a rectangle yet
+    HIP_TRY(hipMemsetAsync(c->bsState.p, 0, 64, s));
+    wp.map = (uint32_t *)c->bsMap.p; wp.state = (uint32_t *)c->bsState.p;
+    launch_blocked_stream_window_decode(wp, device_cus(c), s);
+    HIP_TRY(hipGetLastError());
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_decode_stream_window(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,
+                                                uint32_t *pOut, size_t outStridePixels)
+  {
+    return decode_window_host(c, pStream, streamBytes, x0, y0, width, height, pOut, outStridePixels,
+                              [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); },
+                              [&](const uint8_t *dStream, size_t bytes, size_t w, size_t h, uint32_t *dOut) {
+                                return limg_hip_decode_stream_window_device(c, dStream, bytes, w, h, x0, y0, width, height, dOut, width, nullptr);
+                              });
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_window(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,
+                                                        uint32_t *pOut, size_t outStridePixels)
+  {
+    return decode_window_host(c, pStream, streamBytes, x0, y0, width, height, pOut, outStridePixels,
+                              [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); },
+                              [&](const uint8_t *dStream, size_t bytes, size_t w, size_t h, uint32_t *dOut) {
+                                return limg_hip_blocked_decode_stream_window_device(c, dStream, bytes, w, h, x0, y0, width, height, dOut, width, nullptr);
+                              });
   }
 }

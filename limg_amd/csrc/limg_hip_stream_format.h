@@ -1,7 +1,7 @@
 // limg_hip_stream_format.h -- the rules of the "LMG3" stream (include/limg_hip.h) that both versions share, on the device: field widths, the header (writer and check),
 // the one-workgroup scan over the packers' tile totals -- and, as named functions of the version 2 kernels (k_bstream_pack, k_bstream_decode), the dither + crush that
-// produces the stored values and the reference's decoder arithmetic (a16) in 32-bit terms.  Included by limg_hip_stream.hip (version 1: 8x8 blocks) and
-// limg_hip_blocked_stream.hip (version 2: rectangles).  k_blocked_store (limg_hip_blocked.hip) has the same dither and a16 written out in place (reason there); the
+// produces the stored values and the reference's decoder arithmetic (a16) in 32-bit terms, and version 2's rectangle geometry (pixels, field sizes).  Included by
+// limg_hip_stream.hip (version 1: 8x8 blocks), limg_hip_blocked_stream.hip (version 2: rectangles) and limg_hip_stream_window.hip (window decode of both).  k_blocked_store (limg_hip_blocked.hip) has the same dither and a16 written out in place (reason there); the
 // packed-form decoders (decode_row_packed, phase_f_rows) are a different algorithm for a16's result and live with their kernels.
 #ifndef LIMG_HIP_STREAM_FORMAT_H
 #define LIMG_HIP_STREAM_FORMAT_H
@@ -50,6 +50,26 @@ namespace limg_hip
       }
       return r;
     }
+
+    // ---- version 2: a rectangle's pixels and field sizes (both decoders of limg_hip_blocked_stream.hip and limg_hip_stream_window.hip, and the packer) ------------
+    constexpr int kRectEntry = 64;
+    constexpr uint32_t kNoRect = 0xFFFFFFFFu;
+
+    // pixels of a rectangle: 8 rx x 8 ry clipped to the image (src/limg.cpp:1722-1740)
+    __device__ __forceinline__ uint32_t rect_pixels(uint32_t sizeX, uint32_t sizeY, uint32_t blocksX, uint32_t blocksY, uint32_t ox, uint32_t oy, uint32_t rx, uint32_t ry, uint32_t &wpx)
+    {
+      uint32_t hpx = ry * kBlock;
+      wpx = rx * kBlock;
+      if (ox + rx == blocksX && (sizeX % kBlock)) wpx = wpx - kBlock + sizeX % kBlock;
+      if (oy + ry == blocksY && (sizeY % kBlock)) hpx = hpx - kBlock + sizeY % kBlock;
+      return wpx * hpx;
+    }
+
+    __device__ __forceinline__ uint32_t field_words(uint32_t n, uint32_t b) { return (uint32_t)(((unsigned long long)n * b + 63ull) >> 6); }
+    __device__ __forceinline__ uint32_t rect_words(uint32_t n, uint32_t bits) { return field_words(n, bits & 0xFFu) + field_words(n, (bits >> 8) & 0xFFu) + field_words(n, (bits >> 16) & 0xFFu); }
+
+    // a word another launch or another workgroup of this one may have written (the decoders' verdict words)
+    __device__ __forceinline__ uint32_t ld_volatile(const uint32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 
     // ---- header --------------------------------------------------------------------------------------------------------------------------
     // what a packer knows before its scan has run: everything but the payload's size

@@ -1,0 +1,326 @@
+// limg_hip_stream_window.hip -- window decode of the "LMG3" stream, both versions: any pixel rectangle of the image into a caller's stride (contract: include/limg_hip.h).
+//
+// The table gives every 8x8 block (version 1) or rectangle (version 2) its own payloadWord, so a window needs the entries and payload of its own block range
+// bx0 .. bx0 + wbx - 1, by0 .. by0 + wby - 1 only.  What is read, stored and kept in context memory scales with that range -- except version 2's table scan.
+//   k_stream_window_decode     version 1.  Persistent, lane = (block j = lane & 7, block row r = lane >> 3) over groups of 8 blocks like k_stream_decode, but the work
+//                              unit is a run of up to 64 consecutive blocks of ONE block row of the window: raster-consecutive blocks are what the packer lays down
+//                              back to back, so a group's payload is still one run that is validated as a run (offsets in 64 bits, inside the payload, no longer than
+//                              8 x 24 words) and fetched by the whole wave; across window rows the runs are far apart.  The next group's run is requested before
+//                              the current one is decoded.  A group that fails raises the status word and stores nothing.
+//   k_bstream_window_map       version 2.  Scans the WHOLE rectangle table (64 B per rectangle), checks every rectangle as k_bstream_map does and claims the blocks of
+//                              rectangle n window block range in a window-sized map; overlaps wholly outside the window are therefore not seen.
+//   k_bstream_window_decode    refuses unless every block of the window was claimed exactly once and nothing was flagged; then units of 8 consecutive blocks of a
+//                              window block row, as k_bstream_decode.
+// Both decode with a16_constants / a16_pixel (limg_hip_stream_format.h): the reference's decoder in 32-bit terms, exact for every record.  Of the full version 1
+// decoder's devices this file uses the next-run prefetch only: no counted wait (and so no store sink), no packed 16-bit decode, no per-block constants in LDS -- every
+// lane prepares the constants of its block itself.
+// Lanes whose image row or columns fall outside the window store nothing, or only the pixels inside it: nothing but the window's pixels is ever written.
+#include "limg_hip_stream_format.h"
+
+namespace limg_hip
+{
+  namespace
+  {
+    constexpr int kEntry = 56;
+    constexpr int kGroupBytes = 8 * 192; // payload of 8 blocks, worst case
+
+    __device__ __forceinline__ uint32_t words_of(uint32_t bits) { return (bits & 0xFF) + ((bits >> 8) & 0xFF) + ((bits >> 16) & 0xFF); }
+
+    // the lane's 8 pixels, columns x .. x + 7 of image row y, into the window: a piece wholly inside it as two 16-byte stores where the caller's buffer allows
+    // them, else pixel by pixel; the caller has checked that y is a row of the window
+    __device__ __forceinline__ void store_row_piece(const WindowDecodeParams &p, uint32_t x, uint32_t y, const uint32_t px[8])
+    {
+      uint32_t *row = p.out + (unsigned long long)(y - p.y0) * p.outStride;
+      if (p.vecOut && x >= p.x0 && x + 8u <= p.x0 + p.width)
+      {
+        uint4 *dst = reinterpret_cast<uint4 *>(row + (x - p.x0));
+        dst[0] = make_uint4(px[0], px[1], px[2], px[3]);
+        dst[1] = make_uint4(px[4], px[5], px[6], px[7]);
+        return;
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < 8u; i++)
+        if (x + i >= p.x0 && x + i < p.x0 + p.width) row[x + i - p.x0] = px[i];
+    }
+
+    __device__ __forceinline__ void decode_row(const A16 &k, const unsigned long long packed[3], const uint32_t bb[3], uint32_t px[8])
+    {
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+        px[i] = a16_pixel(k, (uint32_t)(packed[0] >> (i * bb[0])) & ((1u << bb[0]) - 1u), (uint32_t)(packed[1] >> (i * bb[1])) & ((1u << bb[1]) - 1u),
+                          (uint32_t)(packed[2] >> (i * bb[2])) & ((1u << bb[2]) - 1u));
+    }
+
+    // ---- version 1 -------------------------------------------------------------------------------------------------------------------
+    struct WindowWaveLds
+    {
+      uint32_t entry[64][kEntry / 4]; // the unit's table entries, lane == block of the unit
+      uint8_t stage[kGroupBytes + 16]; // the current group's payload run (+ what the 12-byte reads of a row's last field reach beyond it)
+    };
+
+    __global__ __launch_bounds__(256) void k_stream_window_decode(const WindowDecodeParams p)
+    {
+      __shared__ __align__(16) WindowWaveLds sW[4];
+      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+      WindowWaveLds &S = sW[wave];
+
+      const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
+      const unsigned long long payloadWords = h->payloadWords;
+      if (!stream_header_ok(h, LIMG_HIP_STREAM_VERSION, kEntry, p.nBlocks, p))
+      {
+        if (tid == 0 && blockIdx.x == 0) atomicOr(p.status, 1u);
+        return;
+      }
+      const int channels = (int)h->channels;
+      const uint2 *payload = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)p.nBlocks * kEntry);
+      const uint32_t unitsX = (p.wbx + 63u) / 64u, nUnits = unitsX * p.wby;
+      const uint32_t j = (uint32_t)lane & 7u, r = (uint32_t)lane >> 3;
+      unsigned long long *stage64 = reinterpret_cast<unsigned long long *>(S.stage);
+
+      for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u) // (wave-uniform; nothing below synchronises across waves)
+      {
+        const uint32_t urow = unit / unitsX, ucol = unit - urow * unitsX;
+        const uint32_t by = p.by0 + urow, bxUnit = p.bx0 + ucol * 64u, inUnit = min(64u, p.wbx - ucol * 64u);
+        const uint32_t y = by * 8u + r;
+        if ((uint32_t)lane < inUnit)
+        { // (block (bxUnit + lane, by) lies inside the block grid: the host has checked the window against the image; the table's extent: stream_header_ok)
+          const uint2 *ep = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + ((size_t)by * p.blocksX + bxUnit + (uint32_t)lane) * kEntry);
+#pragma unroll
+          for (int i = 0; i < kEntry / 8; i++) { const uint2 v = ep[i]; S.entry[lane][2 * i] = v.x; S.entry[lane][2 * i + 1] = v.y; }
+        }
+        wave_lds_fence();
+
+        // per group of 8 blocks: where its payload run lies, checked as k_stream_decode checks it
+        struct Group { uint32_t t, bw, myOff, off0, n; bool valid, any, ok; };
+        auto group_info = [&](uint32_t grp) {
+          Group G;
+          const uint32_t jb = grp * 8u;
+          G.any = jb < inUnit; // wave-uniform
+          G.t = jb + j; G.bw = 0; G.myOff = 0; G.off0 = 0; G.n = 0; G.valid = false; G.ok = false;
+          if (!G.any) return G;
+          const uint32_t nValid = min(8u, inUnit - jb);
+          G.valid = j < nValid;
+          G.bw = G.valid ? entry_bits(S.entry[G.t][12]) : 0u;
+          G.myOff = G.valid ? S.entry[G.t][13] : 0u;
+          G.off0 = S.entry[jb][13];
+          // all of this in 64 bits: offsets come from the (untrusted) stream, and 32-bit sums such as 0xFFFFFFF0 + 24 wrap to small values that pass
+          const unsigned long long myEnd = (unsigned long long)G.myOff + words_of(G.bw);
+          const uint32_t lastOff = (uint32_t)__shfl((int)G.myOff, (int)nValid - 1, 64), lastWords = (uint32_t)__shfl((int)words_of(G.bw), (int)nValid - 1, 64);
+          const unsigned long long endWord = (unsigned long long)lastOff + lastWords;
+          const bool sane = G.myOff >= G.off0 && myEnd <= endWord && endWord >= G.off0 && endWord - G.off0 <= (unsigned long long)(kGroupBytes / 8) && endWord <= payloadWords;
+          G.ok = __builtin_amdgcn_ballot_w64(G.valid && !sane) == 0;
+          G.n = G.ok ? (uint32_t)(endWord - G.off0) : 0u;
+          return G;
+        };
+        auto fetch = [&](const Group &G, uint2 buf[3]) {
+#pragma unroll
+          for (uint32_t i = 0; i < 3u; i++)
+          {
+            const uint32_t w = (uint32_t)lane + 64u * i;
+            buf[i] = w < G.n ? payload[(size_t)G.off0 + w] : make_uint2(0u, 0u); // (G.n: validated against the payload's size in group_info)
+          }
+        };
+
+        Group cur = group_info(0);
+        uint2 buf[3];
+        fetch(cur, buf);
+        for (uint32_t grp = 0; grp < 8u; grp++)
+        {
+          if (!cur.any) break; // wave-uniform
+          const Group G = cur;
+#pragma unroll
+          for (uint32_t i = 0; i < 3u; i++)
+          {
+            const uint32_t w = (uint32_t)lane + 64u * i;
+            if (w < G.n) stage64[w] = ((unsigned long long)buf[i].y << 32) | buf[i].x;
+          }
+          wave_lds_fence();
+          cur = group_info(grp + 1u);
+          fetch(cur, buf); // the next group's run, in flight while this one is decoded
+          if (!G.ok && lane == 0) atomicOr(p.status, 2u); // inconsistent offsets: the stream is refused and the group stores nothing
+          const uint32_t x = (bxUnit + G.t) * 8u;
+          if (G.valid && G.ok && y >= p.y0 && y < p.y0 + p.height && x + 8u > p.x0 && x < p.x0 + p.width)
+          {
+            const uint32_t *e = S.entry[G.t];
+            const uint32_t sw = e[12];
+            uint32_t fieldByte = (G.myOff - G.off0) * 8u, bb[3], shift[3];
+            unsigned long long packed[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+            {
+              const uint32_t b = (G.bw >> (8 * k)) & 0xFFu;
+              bb[k] = b; shift[k] = min((sw >> (8 * k)) & 0xFFu, 8u);
+              const uint32_t o = fieldByte + r * b; // a block row is b bytes of its field
+              const uint32_t *wp = reinterpret_cast<const uint32_t *>(S.stage + (o & ~3u));
+              const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
+              const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, o & 3u), hi = __builtin_amdgcn_alignbyte(d2, d1, o & 3u);
+              packed[k] = ((unsigned long long)hi << 32) | lo;
+              fieldByte += b * 8u;
+            }
+            const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(e[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, channels);
+            uint32_t px[8];
+            decode_row(k16, packed, bb, px);
+            store_row_piece(p, x, y, px);
+          }
+          wave_lds_fence(); // every lane is done reading this group's run
+        }
+        wave_lds_fence(); // ... and the unit's entries
+      }
+    }
+
+    // ---- version 2 -------------------------------------------------------------------------------------------------------------------
+    __device__ __forceinline__ void refuse(const WindowDecodeParams &p, uint32_t bit)
+    {
+      atomicOr(p.state + 1, 1u);
+      atomicOr(p.status, bit);
+    }
+
+    __global__ __launch_bounds__(256) void k_bstream_window_map(const WindowDecodeParams p)
+    {
+      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+      const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
+      const unsigned long long payloadWords = h->payloadWords;
+      const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES];
+      if (!(nRects >= 1u && nRects <= p.nBlocks && stream_header_ok(h, LIMG_HIP_STREAM_VERSION_BLOCKED, kRectEntry, nRects, p)))
+      {
+        if (tid == 0 && blockIdx.x == 0) refuse(p, 1u);
+        return;
+      }
+      const uint32_t bx1 = p.bx0 + p.wbx, by1 = p.by0 + p.wby;
+      uint32_t claimed = 0;
+      for (uint32_t base = (blockIdx.x * 4u + (uint32_t)wave) * 64u; base < nRects; base += gridDim.x * 256u)
+      {
+        if (ld_volatile(p.state + 1) != 0u) break; // refused already (all lanes read the same word: wave-uniform)
+        const uint32_t rect = base + (uint32_t)lane;
+        uint32_t ix0 = 0, iy0 = 0, iw = 0, ih = 0; // rectangle n window block range
+        if (rect < nRects)
+        {
+          const uint4 e3 = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)rect * kRectEntry)[3];
+          const uint32_t ox = e3.z & 0xFFFFu, oy = e3.z >> 16, rx = e3.w & 0xFFFFu, ry = e3.w >> 16, sw = e3.x;
+          bool good = rx >= 1u && ry >= 1u && ox + rx <= p.blocksX && oy + ry <= p.blocksY && (sw & 0xFFu) <= 8u && ((sw >> 8) & 0xFFu) <= 8u && ((sw >> 16) & 0xFFu) <= 8u;
+          if (good)
+          {
+            uint32_t wpx;
+            const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, ox, oy, rx, ry, wpx);
+            good = (unsigned long long)e3.y + rect_words(n, entry_bits(sw)) <= payloadWords; // (a field is at most n / 8 + 1 words, three of them far below 2^32)
+          }
+          if (!good) refuse(p, 2u);
+          else
+          {
+            ix0 = max(ox, p.bx0); iy0 = max(oy, p.by0);
+            const uint32_t ix1 = min(ox + rx, bx1), iy1 = min(oy + ry, by1);
+            if (ix1 > ix0 && iy1 > iy0) { iw = ix1 - ix0; ih = iy1 - iy0; }
+          }
+        }
+        const uint32_t nb = iw * ih;
+        bool clash = false;
+        if (nb >= 1u && nb <= 4u)
+        { // a small piece: its lane claims it
+          for (uint32_t i = 0; i < nb; i++)
+          {
+            const uint32_t dy = i / iw, dx = i - dy * iw;
+            if (atomicCAS(p.map + (size_t)(iy0 - p.by0 + dy) * p.wbx + (ix0 - p.bx0 + dx), kNoRect, rect) != kNoRect) { clash = true; break; }
+            claimed++;
+          }
+        }
+        // the large ones, one after the other, by the whole wave; a block that is taken already ends the rectangle (and the stream): the work is bounded by the window's blocks
+        unsigned long long big = __builtin_amdgcn_ballot_w64(nb > 4u);
+        while (big != 0ull && __builtin_amdgcn_ballot_w64(clash) == 0ull)
+        {
+          const int src = __builtin_ctzll(big);
+          big &= big - 1ull;
+          const uint32_t bx = (uint32_t)__shfl((int)ix0, src, 64), by = (uint32_t)__shfl((int)iy0, src, 64), bw = (uint32_t)__shfl((int)iw, src, 64),
+                         bnb = (uint32_t)__shfl((int)nb, src, 64);
+          for (uint32_t i0 = 0; i0 < bnb && __builtin_amdgcn_ballot_w64(clash) == 0ull; i0 += 64u)
+          {
+            const uint32_t i = i0 + (uint32_t)lane;
+            if (i < bnb)
+            {
+              const uint32_t dy = i / bw, dx = i - dy * bw;
+              if (atomicCAS(p.map + (size_t)(by - p.by0 + dy) * p.wbx + (bx - p.bx0 + dx), kNoRect, base + (uint32_t)src) != kNoRect) clash = true;
+              else claimed++;
+            }
+          }
+        }
+        if (clash) refuse(p, 2u);
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) claimed += (uint32_t)__shfl_xor((int)claimed, off, 64);
+      if (lane == 0 && claimed) atomicAdd(p.state, claimed);
+    }
+
+    __global__ __launch_bounds__(256) void k_bstream_window_decode(const WindowDecodeParams p)
+    {
+      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+      // the verdict of k_bstream_window_map: nothing flagged and every block of the window claimed exactly once (claims never overlap, so the count says it)
+      if (ld_volatile(p.state + 1) != 0u || ld_volatile(p.state) != p.wbx * p.wby)
+      {
+        if (tid == 0 && blockIdx.x == 0) atomicOr(p.status, 2u);
+        return;
+      }
+      const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
+      const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h->channels;
+      const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h->payloadWords * 8ull;
+      const uint32_t unitsX = (p.wbx + 7u) / 8u, nUnits = unitsX * p.wby;
+      const uint32_t j = (uint32_t)lane & 7u, row = (uint32_t)lane >> 3;
+      for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u)
+      {
+        const uint32_t urow = unit / unitsX, wbxi = (unit - urow * unitsX) * 8u + j; // the block's place in the window's block range
+        const uint32_t y = (p.by0 + urow) * 8u + row, x = (p.bx0 + wbxi) * 8u;
+        if (wbxi >= p.wbx || y < p.y0 || y >= p.y0 + p.height) continue;
+        const uint32_t rect = p.map[(size_t)urow * p.wbx + wbxi];
+        if (rect >= nRects) continue; // (cannot happen after the check above; a lane never indexes the table with anything else)
+        const uint4 *ep = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)rect * kRectEntry);
+        const uint4 e0 = ep[0], e1 = ep[1], e2 = ep[2], e3 = ep[3];
+        const uint32_t ev[12] = { e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w };
+        const uint32_t sw = e3.x, ox = e3.z & 0xFFFFu, oy = e3.z >> 16, rx = e3.w & 0xFFFFu, ry = e3.w >> 16;
+        uint32_t wpx;
+        const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, ox, oy, rx, ry, wpx);
+        const unsigned long long i0 = (unsigned long long)(y - oy * 8u) * wpx + (x - ox * 8u);
+        const uint32_t bits = entry_bits(sw);
+        // the lane's 8 values of each field: the bit run at i0 * b
+        unsigned long long packed[3];
+        uint32_t bb[3], shift[3];
+        unsigned long long fieldByte = tableEnd + (unsigned long long)e3.y * 8ull;
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+        {
+          const uint32_t b = (bits >> (8 * k)) & 0xFFu;
+          bb[k] = b; shift[k] = (sw >> (8 * k)) & 0xFFu;
+          packed[k] = 0;
+          if (b)
+          {
+            const unsigned long long bit = i0 * b, byte = fieldByte + (bit >> 3), at = byte & ~3ull;
+            const uint32_t sh = (uint32_t)(byte & 3ull) * 8u + (uint32_t)(bit & 7ull); // < 32
+            // three aligned dwords hold the run's 64 bits wherever it starts; the last may lie beyond the stream's end (never beyond the field's: it is not used then)
+            const uint32_t *wp = reinterpret_cast<const uint32_t *>(p.stream + at);
+            const uint32_t d0 = at + 4ull <= total ? wp[0] : 0u, d1 = at + 8ull <= total ? wp[1] : 0u, d2 = at + 12ull <= total ? wp[2] : 0u;
+            const unsigned long long lo = ((unsigned long long)d1 << 32) | d0;
+            packed[k] = sh ? ((lo >> sh) | ((unsigned long long)d2 << (64u - sh))) : lo;
+            fieldByte += (unsigned long long)field_words(n, b) * 8ull;
+          }
+        }
+        const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(ev[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, (int)channels);
+        uint32_t px[8];
+        decode_row(k16, packed, bb, px);
+        store_row_piece(p, x, y, px); // (columns beyond a partial last block column lie outside the image, so outside the window)
+      }
+    }
+  }
+
+  // persistent launches: a workgroup of four waves per residency slot at most (version 1: 4 per CU at its 100 vector registers; version 2: 8), every wave strides over its units
+  void launch_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s)
+  {
+    const uint32_t units = ((p.wbx + 63u) / 64u) * p.wby, need = (units + 3u) / 4u, slots = (uint32_t)cus * 4u;
+    hipLaunchKernelGGL(k_stream_window_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, p);
+  }
+
+  void launch_blocked_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s)
+  {
+    const uint32_t slots = (uint32_t)cus * 8u;
+    const uint32_t needMap = (p.nBlocks + 255u) / 256u; // at most nBlocks rectangles, 64 per wave
+    hipLaunchKernelGGL(k_bstream_window_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, p);
+    const uint32_t units = ((p.wbx + 7u) / 8u) * p.wby, need = (units + 3u) / 4u;
+    hipLaunchKernelGGL(k_bstream_window_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, p);
+  }
+}

@@ -13,7 +13,7 @@
 // (size of the pool whose strip partition the 8x8 path reproduces; default: limg_threading_max_threads()),
 // `--out-dir <dir>`, `--stream <file>` (also write the compact LMG3 stream of the 8x8 path and verify that it decodes to that path's image),
 // `--blocked-stream <file>` (single-file merged-block mode: write the version 2 stream of that very encode and verify that it decodes to its image),
-// and the extra mode `limg_hip_cli --decode <file.lmg3> [<out.tga>]` (either version).
+// and the extra mode `limg_hip_cli --decode <file.lmg3> [<out.tga>] [--window x,y,w,h]` (either version; with --window only that pixel rectangle is decoded).
 #include <inttypes.h>
 #include <math.h>
 #include <stdio.h>
@@ -233,7 +233,8 @@ struct Options
 
 static const char *const kUsage =
     "Usage:\nlimg_hip_cli [<InputFile> | --] [--no-output | --error-factor <Factor> | --accurate-bit-crushing | --single-thread | --fixed-blocks | --threads <T> | --out-dir <dir> | "
-    "--stream <file> | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n";
+    "--stream <file> | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n"
+    "limg_hip_cli --decode <file.lmg3> [<out.tga>] [--window x,y,w,h]\n";
 
 static bool parse_number(const char *text, uint64_t &value)
 {
@@ -496,22 +497,66 @@ static int run_benchmark_list(const Options &o, limg_thread_pool *pool)
   return EXIT_SUCCESS;
 }
 
-// extra mode: limg_hip_cli --decode <file.lmg3> [<out.tga>]   (limg_decode of a compact stream written by --stream)
+// extra mode: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--window x,y,w,h]   (limg_decode of a compact stream written by --stream or --blocked-stream; with
+// --window: limg_decode_window of that pixel rectangle only, a w x h image)
+static const char *const kDecodeUsage = "Usage: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--window x,y,w,h]\n";
+
+static bool parse_window(const char *text, size_t win[4])
+{
+  for (int i = 0; i < 4; i++)
+  {
+    char *end = nullptr;
+    if (*text < '0' || *text > '9') return false;
+    win[i] = (size_t)strtoull(text, &end, 10);
+    if (*end != (i < 3 ? ',' : '\0')) return false;
+    text = end + 1;
+  }
+  return true;
+}
+
 static int run_decode(int argc, const char **argv)
 {
-  if (argc < 3) FAIL(EXIT_FAILURE, "Usage: limg_hip_cli --decode <file.lmg3> [<out.tga>]\n");
+  const char *in = nullptr, *out = "limg_out.tga";
+  size_t win[4] = { 0, 0, 0, 0 };
+  bool window = false;
+  int positional = 0;
+  for (int i = 2; i < argc; i++)
+  {
+    if (!strcmp(argv[i], "--window"))
+    {
+      if (i + 1 >= argc || !parse_window(argv[++i], win)) FAIL(EXIT_FAILURE, "'--window' takes x,y,w,h in pixels.\n%s", kDecodeUsage);
+      window = true;
+    }
+    else if (positional == 0) { in = argv[i]; positional++; }
+    else if (positional == 1) { out = argv[i]; positional++; }
+    else FAIL(EXIT_FAILURE, "%s", kDecodeUsage);
+  }
+  if (!in) FAIL(EXIT_FAILURE, "%s", kDecodeUsage);
   std::vector<uint8_t> stream;
-  if (!read_file(argv[2], stream)) FAIL(EXIT_FAILURE, "Failed to read '%s'.\n", argv[2]);
+  if (!read_file(in, stream)) FAIL(EXIT_FAILURE, "Failed to read '%s'.\n", in);
   size_t sx = 0, sy = 0;
   bool alpha = false;
   limg_result r = limg_decode_info(stream.data(), stream.size(), &sx, &sy, &alpha);
-  if (r != limg_success) FAIL(EXIT_FAILURE, "'%s' is not an LMG3 stream (0x%" PRIX32 ").\n", argv[2], (uint32_t)r);
+  if (r != limg_success) FAIL(EXIT_FAILURE, "'%s' is not an LMG3 stream (0x%" PRIX32 ").\n", in, (uint32_t)r);
+  if (window)
+  {
+    if (win[2] == 0 || win[3] == 0 || win[0] >= sx || win[2] > sx - win[0] || win[1] >= sy || win[3] > sy - win[1])
+      FAIL(EXIT_FAILURE, "The window %" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 " is not inside the image (%" PRIu64 " x %" PRIu64 " pixels).\n", (uint64_t)win[0], (uint64_t)win[1],
+           (uint64_t)win[2], (uint64_t)win[3], (uint64_t)sx, (uint64_t)sy);
+    std::vector<uint32_t> image(win[2] * win[3]);
+    r = limg_decode_window(stream.data(), stream.size(), win[0], win[1], win[2], win[3], image.data(), win[2]);
+    if (r != limg_success) FAIL(EXIT_FAILURE, "limg_decode_window failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
+    printf("%" PRIu64 " x %" PRIu64 " pixels, %s; window %" PRIu64 " x %" PRIu64 " at (%" PRIu64 ", %" PRIu64 ").\n", (uint64_t)sx, (uint64_t)sy, alpha ? "RGBA" : "RGB", (uint64_t)win[2],
+           (uint64_t)win[3], (uint64_t)win[0], (uint64_t)win[1]);
+    puts(write_tga(out, win[2], win[3], 4, image.data()) ? "Wrote decoded file." : "Failed to write decoded file.");
+    return EXIT_SUCCESS;
+  }
   std::vector<uint32_t> image(sx * sy);
   const bool merged = stream.size() >= sizeof(limg_hip_stream_header) && reinterpret_cast<const limg_hip_stream_header *>(stream.data())->version == LIMG_HIP_STREAM_VERSION_BLOCKED;
   r = merged ? limg_blocked_decode(stream.data(), stream.size(), image.data(), image.size()) : limg_decode(stream.data(), stream.size(), image.data(), image.size());
   if (r != limg_success) FAIL(EXIT_FAILURE, "limg_decode failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
   printf("%" PRIu64 " x %" PRIu64 " pixels, %s.\n", (uint64_t)sx, (uint64_t)sy, alpha ? "RGBA" : "RGB");
-  puts(write_tga(argc > 3 ? argv[3] : "limg_out.tga", sx, sy, 4, image.data()) ? "Wrote decoded file." : "Failed to write decoded file.");
+  puts(write_tga(out, sx, sy, 4, image.data()) ? "Wrote decoded file." : "Failed to write decoded file.");
   return EXIT_SUCCESS;
 }
 
