@@ -397,6 +397,54 @@ limg_hip_result limg_hip_decode_stream_window(limg_hip_context *pCtx, const uint
 limg_hip_result limg_hip_blocked_decode_stream_window(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,
                                                       uint32_t *pOut, size_t outStridePixels);
 
+/* ---- batched window decode: many windows of many streams per call ---------------------------------------------------------------
+ * One window is a few workgroups: a 256 x 256 window fills a few percent of the device, and version 2 scans the whole rectangle table for it.  Callers that cut
+ * many tiles out of a stream, or one crop out of each of many streams, hand all of them to one call.
+ * Result: job i writes exactly what the single-window _device entry of that version writes for the same arguments, bit for bit, and nothing else: the rules above
+ * for the stride slack, the rows beyond the window, unaligned pOut and partial edge blocks hold per job, and so does the choice between 16-byte and dword stores.
+ * Jobs are independent: they may name different streams, image sizes and channel counts, and several may name the same stream.  Each entry takes ONE stream version;
+ * a job whose stream is the other version is a header mismatch for that job.  Output rectangles of different jobs that overlap are not checked: which job's pixels
+ * land there is unspecified.
+ * Errors, before anything touches the device: NULL context or pJobs / pWindows: limg_hip_error_ArgumentNull; count == 0: limg_hip_error_InvalidParameter; then the jobs
+ * in index order, each by the single-window entry's rules in its order.  The first failing job's error is returned and NOTHING IS ENQUEUED: no job writes anything, not
+ * even those before it.  A list whose summed window blocks or work units do not fit in 32 bits: limg_hip_error_InvalidParameter.
+ * Validation on the device: every job exactly as the single-window kernels validate it, and a refused job never changes what another job writes.
+ *   Version 1: a group of 8 blocks that fails stores nothing; the job's other groups are stored.
+ *   Version 2: a job whose stream's table fails anywhere, or whose window is not claimed exactly once, writes nothing.  Overlaps wholly outside a job's window do not
+ *   concern that job.
+ *   pJobStatus: DEVICE pointer to `count` words, or NULL.  Every call overwrites it for every job: 0 = decoded, otherwise the job's status bits (bit 0 header
+ *   mismatch, bit 1 table or payload inconsistent).  The context's sticky status is raised as well: limg_hip_check_device_status reports
+ *   limg_hip_error_InvalidParameter, once.
+ * Cost: version 1 is ONE kernel launch per call, version 2 TWO, whatever `count` is.  Table entries and payload read and pixels stored are the sums over the jobs'
+ * block ranges.  Version 2 scans each distinct stream's rectangle table ONCE per call: jobs with the same pStream, streamBytes, sizeX and sizeY form a group, a
+ * rectangle is checked once per group and offered to every window of the group.  Context memory: the job table (about 128 bytes per job), version 2's map (4 bytes
+ * per window block, summed over the jobs) and a few words of state per job -- per call in flight, four at most.
+ * Ordering: calls on one context and stream execute in order.  A call's job table lives in context-owned memory of its own until the call has run, so further calls
+ * may be issued before it has; the fifth call in flight waits on the host for the first.  These entries must not be used while `stream` is being captured into a graph. */
+typedef struct limg_hip_window /* one window and where it goes */
+{
+  size_t x0, y0, width, height; /* pixels, inside the image, not empty */
+  uint32_t *pOut;               /* pixel (x0 + c, y0 + r) at pOut[r * outStridePixels + c] */
+  size_t outStridePixels;
+} limg_hip_window;
+
+typedef struct limg_hip_window_job /* one window of one stream */
+{
+  const uint8_t *pStream; /* DEVICE, 16-byte aligned */
+  size_t streamBytes;
+  size_t sizeX, sizeY;    /* must match the stream's header */
+  limg_hip_window window; /* pOut: DEVICE, 4-byte aligned */
+} limg_hip_window_job;
+
+/* DEVICE pointers inside the jobs; pJobs itself is HOST memory and may be reused or freed when the call returns.  Asynchronous on `stream`. */
+limg_hip_result limg_hip_decode_stream_windows_device(limg_hip_context *pCtx, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream);
+limg_hip_result limg_hip_blocked_decode_stream_windows_device(limg_hip_context *pCtx, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream);
+/* HOST pointers, blocking, under the context's mutex: `count` windows of ONE stream.  The image size comes from the header; the stream is uploaded ONCE; all windows
+ * decode in one batched call into context staging (4 bytes per window pixel, summed); the status is checked, and only then is each window copied into its stride: a
+ * stream refused for any window leaves EVERY pOut untouched, in both versions. */
+limg_hip_result limg_hip_decode_stream_windows(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count);
+limg_hip_result limg_hip_blocked_decode_stream_windows(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ---------------------------------------------------------------------------------
  * The reference's only parallelism is row strips over a std::thread pool (src/limg.cpp:2105-2138); across GPUs the same strips
  * go one per rank.  Blocks are independent except for the dither chain, so the data path needs no collective in strip-restart mode (each strip

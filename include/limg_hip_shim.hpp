@@ -233,4 +233,15 @@ inline limg_result limg_decode_window(const uint8_t *pIn, const size_t size, con
   return (limg_result)limg_hip_decode_stream_window(c, pIn, size, x, y, w, h, pOut, outStridePixels);
 }
 
+// `count` windows of one stream of either version in one call: the stream is uploaded once and all windows decode in one batched launch (limg_hip.h "batched window
+// decode"); a stream refused for any window leaves every pOut untouched.
+inline limg_result limg_decode_windows(const uint8_t *pIn, const size_t size, const limg_hip_window *pWindows, const size_t count)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (limg_hip_blocked_stream_info(pIn, size, nullptr, nullptr, nullptr, nullptr, nullptr) == limg_hip_success)
+    return (limg_result)limg_hip_blocked_decode_stream_windows(c, pIn, size, pWindows, count);
+  return (limg_result)limg_hip_decode_stream_windows(c, pIn, size, pWindows, count);
+}
+
 #endif // LIMG_HIP_SHIM_HPP

@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
     "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
     "limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device", "limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window",
+    "limg_hip_decode_stream_windows_device", "limg_hip_blocked_decode_stream_windows_device", "limg_hip_decode_stream_windows", "limg_hip_blocked_decode_stream_windows",
     "limg_hip_blocked_encode3d", "limg_hip_blocked_encode3d_device", "limg_hip_blocked_regions", "limg_hip_blocked_timing", "limg_hip_blocked_kernel_timing", "limg_hip_blocked_match_bits", "limg_hip_host_blocked_matches",
     "limg_hip_host_blocked_merge", "limg_hip_host_blocked_match_words", "limg_hip_host_blocked_match_bits",
     "limg_hip_comm_unique_id", "limg_hip_comm_init", "limg_hip_comm_destroy", "limg_hip_comm_info", "limg_hip_gather_stream", "limg_hip_encode3d_single_chain_device",
@@ -70,6 +71,16 @@ class Info(C.Structure):
 
 class CompactOut(C.Structure):
     _fields_ = [("pRecords", C.c_void_p), ("pShifts", C.c_void_p)]
+
+
+class Window(C.Structure):
+    """limg_hip_window: one window and where it goes"""
+    _fields_ = [("x0", C.c_size_t), ("y0", C.c_size_t), ("width", C.c_size_t), ("height", C.c_size_t), ("pOut", C.c_void_p), ("outStridePixels", C.c_size_t)]
+
+
+class WindowJob(C.Structure):
+    """limg_hip_window_job: one window of one stream"""
+    _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", Window)]
 
 
 class Options(C.Structure):
@@ -201,6 +212,12 @@ def load_library(path=None):
     for name in ("limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window"):
         getattr(L, name).restype = C.c_int  # ctx, stream, bytes, x0, y0, width, height, out, outStridePixels
         getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_size_t] * 4 + [C.c_void_p, C.c_size_t]
+    for name in ("limg_hip_decode_stream_windows_device", "limg_hip_blocked_decode_stream_windows_device"):
+        getattr(L, name).restype = C.c_int  # ctx, jobs (host), count, jobStatus (device), hipStream
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    for name in ("limg_hip_decode_stream_windows", "limg_hip_blocked_decode_stream_windows"):
+        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     L.limg_hip_blocked_last_stream.restype = C.c_int
     L.limg_hip_blocked_last_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.limg_hip_blocked_stream_info.restype = C.c_int
@@ -622,6 +639,51 @@ class LimgHip:
 
     def blocked_decode_stream_window_device(self, stream, nbytes, W, H, x, y, w, h, out=None, out_stride=None):
         return self._decode_stream_window_device("limg_hip_blocked_decode_stream_window_device", stream, nbytes, W, H, x, y, w, h, out, out_stride)
+
+    # ---- batched window decode: many windows of many streams per call (contract: include/limg_hip.h) ----
+    def _decode_stream_windows_device(self, name, jobs, status):
+        import torch
+        table = (WindowJob * len(jobs))()
+        outs = []
+        for i, (stream, nbytes, W, H, x, y, w, h, out, out_stride) in enumerate(jobs):
+            if out is None:
+                out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
+            if out_stride is None:
+                out_stride = out.stride(0) if out.dim() == 2 else w
+            table[i] = WindowJob(stream.data_ptr(), int(nbytes), W, H, Window(x, y, w, h, out.data_ptr(), int(out_stride)))
+            outs.append(out)
+        self._stream_call(name, table, len(jobs), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
+        return outs
+
+    def _decode_stream_windows(self, name, stream, wins, outs):
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        outs = [None] * len(wins) if outs is None else list(outs)
+        table = (Window * len(wins))()
+        for i, (x, y, w, h) in enumerate(wins):
+            if outs[i] is None:
+                outs[i] = np.zeros((h, w), dtype=np.uint32)
+            out = outs[i]
+            assert out.dtype == np.uint32 and out.ndim == 2 and out.strides[1] == 4 and out.strides[0] % 4 == 0, "out: uint32 rows, pixels contiguous"
+            table[i] = Window(x, y, w, h, out.ctypes.data, out.strides[0] // 4)
+        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins))
+        return outs
+
+    def decode_stream_windows_device(self, jobs, status=None):
+        """jobs: (stream tensor, nbytes, W, H, x, y, w, h, out, out_stride) each, as the arguments of decode_stream_window_device (out=None allocates, out_stride=None is
+        out's own row stride); status: torch int32 CUDA tensor of len(jobs) words or None.  One launch for all of them, asynchronous on torch's current stream.
+        Returns the list of output tensors."""
+        return self._decode_stream_windows_device("limg_hip_decode_stream_windows_device", jobs, status)
+
+    def blocked_decode_stream_windows_device(self, jobs, status=None):
+        return self._decode_stream_windows_device("limg_hip_blocked_decode_stream_windows_device", jobs, status)
+
+    def decode_stream_windows(self, stream, wins, outs=None):
+        """host stream bytes, wins: (x, y, w, h) each -> the list of numpy uint32 (h, w) arrays; outs: per window a uint32 view that receives it (rows may be strided)
+        or None.  The stream is uploaded once."""
+        return self._decode_stream_windows("limg_hip_decode_stream_windows", stream, wins, outs)
+
+    def blocked_decode_stream_windows(self, stream, wins, outs=None):
+        return self._decode_stream_windows("limg_hip_blocked_decode_stream_windows", stream, wins, outs)
 
     def check(self):
         _check(self.lib.limg_hip_check_device_status(self.ctx), "limg_hip_check_device_status")

@@ -113,6 +113,11 @@ extern "C"
     for (hipEvent_t e : c->workEvents) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->workTimers) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->packTimers) (void)hipEventDestroy(e);
+    for (auto &slot : c->windowSlots)
+    {
+      slot.host.release();
+      if (slot.done) (void)hipEventDestroy(slot.done);
+    }
     if (c->copyStream) (void)hipStreamDestroy(c->copyStream);
     for (hipEvent_t e : c->bandEvents) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);

@@ -144,6 +144,13 @@ struct limg_hip_context
   // version 2 stream of the merged-block encoder (limg_hip_stream_api.hip): per rectangle its first 64-pixel run, per tile of rectangles its totals; the
   // decoder's block -> rectangle map and its per-call words
   DevBuf bsUnits, bsTiles, bsMap, bsState;
+  // batched window decode (limg_hip_*decode_stream_windows*): a call's job table -- and, version 2, its map and per-job state words -- lives in one slot of a small
+  // ring, so that a call issued before the previous one has run does not disturb it.  host: pinned, the table as the call builds it; dev: its copy, then state and map;
+  // done: recorded behind the call's last kernel and waited for on the host before the slot is used again.
+  struct WindowSlot { HostBuf host; DevBuf dev; hipEvent_t done = nullptr; bool busy = false; };
+  static constexpr unsigned kWindowSlots = 4;
+  WindowSlot windowSlots[kWindowSlots];
+  unsigned windowSlotNext = 0;
   size_t blockedScratchCap = 0;              // plane stride of bFac in the last merged-block encode (BlockedParams::scratchCap)
   struct { size_t sizeX = 0, sizeY = 0; int channels = 0; uint32_t errorFactor = 0, flags = 0; bool valid = false; } lastBlocked; // ... its shape and stream flags; valid: it succeeded,
                                              // so the context's buffers hold everything the stream packer reads (limg_hip_blocked_last_stream)
@@ -162,7 +169,8 @@ struct limg_hip_context
   {
     for (auto *b : { &c.records, &c.shifts, &c.stripCalls, &c.stripBase, &c.invN, &c.noise, &c.noiseDyn, &c.noiseStates, &c.noiseCk, &c.park, &c.batchTable, &c.stats,
                      &c.lookback, &c.accTable, &c.devStatus, &c.in, &c.planes, &c.hostWords, &c.cmp, &c.bFlags, &c.bBound, &c.bOrder, &c.bMatch, &c.bRegions, &c.bOut,
-                     &c.bPx, &c.bFac, &c.bNoise, &c.bNoiseBase, &c.bCalls, &c.commWords, &c.streamFac, &c.streamTiles, &c.streamUnits, &c.streamStatus, &c.streamBuf, &c.bsUnits, &c.bsTiles, &c.bsMap, &c.bsState })
+                     &c.bPx, &c.bFac, &c.bNoise, &c.bNoiseBase, &c.bCalls, &c.commWords, &c.streamFac, &c.streamTiles, &c.streamUnits, &c.streamStatus, &c.streamBuf, &c.bsUnits, &c.bsTiles, &c.bsMap, &c.bsState,
+                     &c.windowSlots[0].dev, &c.windowSlots[1].dev, &c.windowSlots[2].dev, &c.windowSlots[3].dev })
       f(*b);
   }
 };

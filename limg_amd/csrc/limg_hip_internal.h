@@ -229,6 +229,35 @@ namespace limg_hip
   void launch_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s);
   void launch_blocked_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s);
 
+  // ---- batched window decode (limg_hip_stream_window.hip): many windows of many streams per launch ----
+  // Jobs of one call that name the same stream (pointer, bytes, image size) form a GROUP: version 2 scans a group's rectangle table once and offers every
+  // rectangle to every window of the group.
+  struct WindowGroup
+  {
+    uint32_t sizeX, sizeY, blocksX, blocksY, nBlocks;
+    uint32_t firstJob, nJobs; // its jobs: groupJobs[firstJob .. firstJob + nJobs - 1]
+    uint32_t pad;
+    const uint8_t *stream;
+    unsigned long long streamBytes;
+  };
+  // The job table of one call, in device memory.  jobs[i]: what the single-window entry would have launched job i with, except that `map` is the job's slice of the
+  // call's concatenated map, `state` the job's own [claimed, refused] pair and `status` the context's sticky word.
+  struct WindowBatchParams
+  {
+    const WindowDecodeParams *jobs;
+    const uint32_t *unitBase; // count + 1: exclusive prefix of the jobs' decode units (version 1: runs of up to 64 blocks; version 2: of 8); [count] = totalUnits
+    uint32_t count, totalUnits;
+    uint32_t *status;         // the context's sticky stream status word
+    uint32_t *jobStatus;      // per job (may be NULL): 0 = decoded, else its status bits; zeroed in front of the launch
+    // version 2
+    const WindowGroup *groups;
+    const uint32_t *groupJobs;   // job indices, group after group
+    const uint32_t *groupItemBase; // nGroups + 1: exclusive prefix of ceil(nBlocks / 64), the map kernel's work items (64 rectangles each; R <= nBlocks)
+    uint32_t nGroups, totalItems;
+  };
+  void launch_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s);
+  void launch_blocked_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s);
+
   void launch_stream_pack(const StreamParams &p, hipStream_t s);
   void launch_stream_decode(const DecodeParams &p, int cus, hipStream_t s);
 

@@ -3,6 +3,8 @@
 // limg_hip_blocked_stream.hip.  Decode, header check and the host-pointer forms of each; what the two versions do alike is written once, in the namespace below.
 #include "limg_hip_context.h"
 
+#include <algorithm>
+
 using namespace limg_hip;
 
 namespace
@@ -132,16 +134,14 @@ namespace
   }
 
   // ---- window decode: limg_hip_*decode_stream_window* (kernels: limg_hip_stream_window.hip) ----
-  // the checks and the parameters the two versions share; `bound`: the version's limg_hip_*stream_bound(sizeX, sizeY)
-  limg_hip_result window_params(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width,
-                                size_t height, uint32_t *pOut, size_t outStridePixels, hipStream_t s, WindowDecodeParams &wp)
+  // the checks and the parameters the two versions share, without touching the device; `bound`: the version's limg_hip_*stream_bound(sizeX, sizeY).  status, map and
+  // state are the caller's to set.
+  limg_hip_result window_fill(const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width, size_t height,
+                              uint32_t *pOut, size_t outStridePixels, WindowDecodeParams &wp)
   {
     if (width == 0 || height == 0 || outStridePixels < width || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
     if (((uintptr_t)pStream & 15u) != 0 || ((uintptr_t)pOut & 3u) != 0) return limg_hip_error_InvalidParameter;
     if (x0 >= sizeX || width > sizeX - x0 || y0 >= sizeY || height > sizeY - y0) return limg_hip_error_OutOfBounds;
-    HIP_TRY(hipSetDevice(c->device));
-    const limg_hip_result r = ensure_stream_status(c, s);
-    if (r != limg_hip_success) return r;
     memset(&wp, 0, sizeof(wp));
     wp.sizeX = (uint32_t)sizeX; wp.sizeY = (uint32_t)sizeY;
     wp.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); wp.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
@@ -152,6 +152,16 @@ namespace
     wp.wbx = (uint32_t)((x0 + width - 1) / kBlock) - wp.bx0 + 1; wp.wby = (uint32_t)((y0 + height - 1) / kBlock) - wp.by0 + 1;
     wp.out = pOut; wp.outStride = outStridePixels;
     wp.vecOut = ((uintptr_t)pOut & 15u) == 0 && (outStridePixels & 3u) == 0 && (x0 & 3u) == 0;
+    return limg_hip_success;
+  }
+
+  limg_hip_result window_params(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width,
+                                size_t height, uint32_t *pOut, size_t outStridePixels, hipStream_t s, WindowDecodeParams &wp)
+  {
+    limg_hip_result r = window_fill(pStream, streamBytes, sizeX, sizeY, bound, x0, y0, width, height, pOut, outStridePixels, wp);
+    if (r != limg_hip_success) return r;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
     wp.status = (uint32_t *)c->streamStatus.p;
     return limg_hip_success;
   }
@@ -177,6 +187,179 @@ namespace
     if ((r = deviceDecode((const uint8_t *)c->streamBuf.p, total, sizeX, sizeY, (uint32_t *)c->planes.p)) != limg_hip_success) return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
     HIP_TRY(hipMemcpy2D(pOut, outStridePixels * 4, c->planes.p, width * 4, width * 4, height, hipMemcpyDeviceToHost));
+    return limg_hip_success;
+  }
+
+  // ---- batched window decode: limg_hip_*decode_stream_windows* (kernels: limg_hip_stream_window.hip) ----
+  size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+  // One call: every job checked on the host before anything touches the device, then the job table built in a pinned slot of the context's ring, copied on `s`,
+  // and the version's one (two) launches.  blocked: version 2.
+  limg_hip_result decode_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, hipStream_t s, bool blocked)
+  {
+    if (!c || !pJobs) return limg_hip_error_ArgumentNull;
+    if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    // pass 1: the single-window entry's checks, job by job in its order; the sums the table's layout needs
+    unsigned long long units = 0, blocks = 0;
+    WindowDecodeParams wp;
+    for (size_t i = 0; i < count; i++)
+    {
+      const limg_hip_window_job &j = pJobs[i];
+      if (!j.pStream || !j.window.pOut) return limg_hip_error_ArgumentNull;
+      const size_t bound = blocked ? limg_hip_blocked_stream_bound(j.sizeX, j.sizeY) : limg_hip_stream_bound(j.sizeX, j.sizeY);
+      const limg_hip_result r = window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height, j.window.pOut,
+                                            j.window.outStridePixels, wp);
+      if (r != limg_hip_success) return r;
+      if (!blocked && j.streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
+      units += (unsigned long long)((wp.wbx + (blocked ? 7u : 63u)) / (blocked ? 8u : 64u)) * wp.wby;
+      blocks += (unsigned long long)wp.wbx * wp.wby;
+    }
+    if (units > 0xFFFFFFFFull || blocks > 0xFFFFFFFFull) return limg_hip_error_InvalidParameter;
+
+    HIP_TRY(hipSetDevice(c->device));
+    limg_hip_result r;
+    if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
+    // the slot: [jobs | unitBase | groups | groupJobs | groupItemBase] is uploaded; [state | map] behind it exists on the device only (version 2)
+    const size_t oJobs = 0, oUnitBase = align16(oJobs + count * sizeof(WindowDecodeParams)), oGroups = align16(oUnitBase + (count + 1) * 4);
+    const size_t oGroupJobs = blocked ? align16(oGroups + count * sizeof(WindowGroup)) : oGroups, oItemBase = blocked ? align16(oGroupJobs + count * 4) : oGroups;
+    const size_t upload = blocked ? align16(oItemBase + (count + 1) * 4) : oGroups;
+    const size_t oState = upload, oMap = align16(oState + (blocked ? count * 8 : 0)), total = oMap + (blocked ? (size_t)blocks * 4 : 0);
+    limg_hip_context::WindowSlot &slot = c->windowSlots[c->windowSlotNext];
+    c->windowSlotNext = (c->windowSlotNext + 1) % limg_hip_context::kWindowSlots;
+    if (slot.busy)
+    { // the call that used this slot last: its copy has left the pinned table and its kernels are done with the device copy
+      HIP_TRY(hipEventSynchronize(slot.done));
+      slot.busy = false;
+    }
+    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    if ((r = slot.host.ensure(upload)) != limg_hip_success) return r;
+    if ((r = slot.dev.ensure(total)) != limg_hip_success) return r;
+    uint8_t *hb = (uint8_t *)slot.host.p, *db = (uint8_t *)slot.dev.p;
+    WindowDecodeParams *jobs = (WindowDecodeParams *)(hb + oJobs);
+    uint32_t *unitBase = (uint32_t *)(hb + oUnitBase);
+
+    // pass 2: the table (the checks of pass 1 cannot fail again)
+    uint32_t unitAt = 0, blockAt = 0;
+    for (size_t i = 0; i < count; i++)
+    {
+      const limg_hip_window_job &j = pJobs[i];
+      const size_t bound = blocked ? limg_hip_blocked_stream_bound(j.sizeX, j.sizeY) : limg_hip_stream_bound(j.sizeX, j.sizeY);
+      (void)window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height, j.window.pOut, j.window.outStridePixels, jobs[i]);
+      jobs[i].status = (uint32_t *)c->streamStatus.p;
+      if (blocked)
+      {
+        jobs[i].state = (uint32_t *)(db + oState) + 2 * i;
+        jobs[i].map = (uint32_t *)(db + oMap) + blockAt;
+      }
+      unitBase[i] = unitAt;
+      unitAt += ((jobs[i].wbx + (blocked ? 7u : 63u)) / (blocked ? 8u : 64u)) * jobs[i].wby;
+      blockAt += jobs[i].wbx * jobs[i].wby;
+    }
+    unitBase[count] = unitAt;
+    WindowBatchParams b;
+    memset(&b, 0, sizeof(b));
+    b.jobs = (const WindowDecodeParams *)(db + oJobs); b.unitBase = (const uint32_t *)(db + oUnitBase);
+    b.count = (uint32_t)count; b.totalUnits = unitAt;
+    b.status = (uint32_t *)c->streamStatus.p; b.jobStatus = pJobStatus;
+    if (blocked)
+    { // groups: the jobs sorted by stream (in place, in the table: no allocation), then one group per run of equal keys
+      WindowGroup *groups = (WindowGroup *)(hb + oGroups);
+      uint32_t *groupJobs = (uint32_t *)(hb + oGroupJobs), *itemBase = (uint32_t *)(hb + oItemBase);
+      for (size_t i = 0; i < count; i++) groupJobs[i] = (uint32_t)i;
+      auto less = [jobs](uint32_t x, uint32_t y) {
+        const WindowDecodeParams &a = jobs[x], &bb = jobs[y];
+        if (a.stream != bb.stream) return (uintptr_t)a.stream < (uintptr_t)bb.stream;
+        if (a.streamBytes != bb.streamBytes) return a.streamBytes < bb.streamBytes;
+        if (a.sizeX != bb.sizeX) return a.sizeX < bb.sizeX;
+        if (a.sizeY != bb.sizeY) return a.sizeY < bb.sizeY;
+        return x < y;
+      };
+      std::sort(groupJobs, groupJobs + count, less);
+      uint32_t nGroups = 0;
+      unsigned long long items = 0;
+      for (size_t i = 0; i < count; i++)
+      {
+        const WindowDecodeParams &a = jobs[groupJobs[i]];
+        if (i == 0 || a.stream != groups[nGroups - 1].stream || a.streamBytes != groups[nGroups - 1].streamBytes || a.sizeX != groups[nGroups - 1].sizeX ||
+            a.sizeY != groups[nGroups - 1].sizeY)
+        {
+          WindowGroup &g = groups[nGroups];
+          memset(&g, 0, sizeof(g));
+          g.sizeX = a.sizeX; g.sizeY = a.sizeY; g.blocksX = a.blocksX; g.blocksY = a.blocksY; g.nBlocks = a.nBlocks;
+          g.firstJob = (uint32_t)i; g.stream = a.stream; g.streamBytes = a.streamBytes;
+          itemBase[nGroups++] = (uint32_t)items;
+          items += (a.nBlocks + 63u) / 64u; // 64 rectangles per item, at most nBlocks rectangles
+        }
+        groups[nGroups - 1].nJobs++;
+      }
+      if (items > 0xFFFFFFFFull) return limg_hip_error_InvalidParameter;
+      itemBase[nGroups] = (uint32_t)items;
+      b.groups = (const WindowGroup *)(db + oGroups); b.groupJobs = (const uint32_t *)(db + oGroupJobs); b.groupItemBase = (const uint32_t *)(db + oItemBase);
+      b.nGroups = nGroups; b.totalItems = (uint32_t)items;
+    }
+    HIP_TRY(hipMemcpyAsync(db, hb, upload, hipMemcpyHostToDevice, s));
+    slot.busy = true; // from here on the slot is in flight, whatever fails below
+    if (blocked)
+    {
+      HIP_TRY(hipMemsetAsync(db + oState, 0, count * 8, s));
+      HIP_TRY(hipMemsetAsync(db + oMap, 0xFF, (size_t)blocks * 4, s)); // no block has a rectangle yet
+    }
+    if (pJobStatus) HIP_TRY(hipMemsetAsync(pJobStatus, 0, count * 4, s));
+    if (blocked) launch_blocked_stream_windows_decode(b, device_cus(c), s);
+    else launch_stream_windows_decode(b, device_cus(c), s);
+    const hipError_t launched = hipGetLastError();
+    HIP_TRY(hipEventRecord(slot.done, s));
+    HIP_TRY(launched);
+    return limg_hip_success;
+  }
+
+  // `count` windows of ONE host stream.  info(&sizeX, &sizeY, &total): the version's header check.
+  template <class INFO>
+  limg_hip_result decode_windows_host(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count, bool blocked, INFO &&info)
+  {
+    if (!c || !pStream || !pWindows) return limg_hip_error_ArgumentNull;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    for (size_t i = 0; i < count; i++)
+    {
+      const limg_hip_window &w = pWindows[i];
+      if (!w.pOut) return limg_hip_error_ArgumentNull;
+      if (w.width == 0 || w.height == 0 || w.outStridePixels < w.width) return limg_hip_error_InvalidParameter;
+    }
+    size_t sizeX = 0, sizeY = 0, total = 0;
+    limg_hip_result r = info(&sizeX, &sizeY, &total);
+    if (r != limg_hip_success) return r;
+    if (total > streamBytes) return limg_hip_error_OutOfBounds;
+    size_t pixels = 0; // staging: every window at its own width, on a 16-byte boundary
+    for (size_t i = 0; i < count; i++)
+    {
+      const limg_hip_window &w = pWindows[i];
+      if (w.x0 >= sizeX || w.width > sizeX - w.x0 || w.y0 >= sizeY || w.height > sizeY - w.y0) return limg_hip_error_OutOfBounds;
+      pixels += (w.width * w.height + 3) & ~(size_t)3;
+    }
+    limg_hip_window_job *jobs = new (std::nothrow) limg_hip_window_job[count];
+    if (!jobs) return limg_hip_error_MemoryAllocationFailure;
+    struct Free { limg_hip_window_job *p; ~Free() { delete[] p; } } freeJobs = { jobs };
+    HIP_TRY(hipSetDevice(c->device));
+    if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
+    if ((r = c->planes.ensure(pixels * 4)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice)); // once, for all windows
+    size_t at = 0;
+    for (size_t i = 0; i < count; i++)
+    {
+      const limg_hip_window &w = pWindows[i];
+      jobs[i].pStream = (const uint8_t *)c->streamBuf.p; jobs[i].streamBytes = total; jobs[i].sizeX = sizeX; jobs[i].sizeY = sizeY;
+      jobs[i].window = w;
+      jobs[i].window.pOut = (uint32_t *)c->planes.p + at; jobs[i].window.outStridePixels = w.width;
+      at += (w.width * w.height + 3) & ~(size_t)3;
+    }
+    if ((r = decode_windows_device(c, jobs, count, nullptr, nullptr, blocked)) != limg_hip_success) return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r; // a stream refused for any window: no pOut is touched
+    for (size_t i = 0; i < count; i++)
+    {
+      const limg_hip_window &w = pWindows[i];
+      HIP_TRY(hipMemcpy2D(w.pOut, w.outStridePixels * 4, jobs[i].window.pOut, w.width * 4, w.width * 4, w.height, hipMemcpyDeviceToHost));
+    }
     return limg_hip_success;
   }
 }
@@ -451,5 +634,28 @@ extern "C"
                               [&](const uint8_t *dStream, size_t bytes, size_t w, size_t h, uint32_t *dOut) {
                                 return limg_hip_blocked_decode_stream_window_device(c, dStream, bytes, w, h, x0, y0, width, height, dOut, width, nullptr);
                               });
+  }
+
+  // ---- batched window decode, both versions ----
+  limg_hip_result limg_hip_decode_stream_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
+  {
+    return decode_windows_device(c, pJobs, count, pJobStatus, (hipStream_t)stream, false);
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
+  {
+    return decode_windows_device(c, pJobs, count, pJobStatus, (hipStream_t)stream, true);
+  }
+
+  limg_hip_result limg_hip_decode_stream_windows(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count)
+  {
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, false,
+                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); });
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_windows(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count)
+  {
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, true,
+                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });
   }
 }

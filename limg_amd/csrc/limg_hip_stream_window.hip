@@ -15,6 +15,14 @@
 // decoder's devices this file uses the next-run prefetch only: no counted wait (and so no store sink), no packed 16-bit decode, no per-block constants in LDS -- every
 // lane prepares the constants of its block itself.
 // Lanes whose image row or columns fall outside the window store nothing, or only the pixels inside it: nothing but the window's pixels is ever written.
+//
+// Batched forms (limg_hip_*decode_stream_windows*): many windows of many streams per launch.  The per-unit bodies of the kernels above are __device__ functions
+// (window_unit, bwindow_unit, rect_ok, claim_pieces) that both forms call, so a job decodes exactly as its single-window call would.
+//   k_stream_windows_decode    version 1.  One persistent launch over the concatenated unit list of all jobs; a wave finds its unit's job by a wave-uniform binary
+//                              search over the exclusive prefix of unit counts and reads the job's WindowDecodeParams from the job table through scalar loads.
+//   k_bstream_windows_map      version 2.  Work item = (stream group, 64 rectangles): every rectangle is checked ONCE per group and its intersection claimed in the
+//                              map slice of every window of the group.  A bad rectangle or header refuses every job of the group, a clash the job it happened in.
+//   k_bstream_windows_decode   one launch over the concatenated 8-block units; a unit reads its job's verdict first.
 #include "limg_hip_stream_format.h"
 
 namespace limg_hip
@@ -58,6 +66,102 @@ namespace limg_hip
       uint8_t stage[kGroupBytes + 16]; // the current group's payload run (+ what the 12-byte reads of a row's last field reach beyond it)
     };
 
+    // One unit of version 1: up to 64 consecutive blocks of block row `unit / unitsX` of p's window, by one wave.  S: the wave's LDS; payload, payloadWords, channels:
+    // from the (checked) header; raise(bits): how the caller reports a group that fails.  Everything but `lane` is wave-uniform.
+    template <class RAISE>
+    __device__ __forceinline__ void window_unit(const WindowDecodeParams &p, WindowWaveLds &S, uint32_t unit, uint32_t unitsX, int channels, unsigned long long payloadWords,
+                                                const uint2 *payload, int lane, RAISE &&raise)
+    {
+      const uint32_t j = (uint32_t)lane & 7u, r = (uint32_t)lane >> 3;
+      unsigned long long *stage64 = reinterpret_cast<unsigned long long *>(S.stage);
+      const uint32_t urow = unit / unitsX, ucol = unit - urow * unitsX;
+      const uint32_t by = p.by0 + urow, bxUnit = p.bx0 + ucol * 64u, inUnit = min(64u, p.wbx - ucol * 64u);
+      const uint32_t y = by * 8u + r;
+      if ((uint32_t)lane < inUnit)
+      { // (block (bxUnit + lane, by) lies inside the block grid: the host has checked the window against the image; the table's extent: stream_header_ok)
+        const uint2 *ep = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + ((size_t)by * p.blocksX + bxUnit + (uint32_t)lane) * kEntry);
+#pragma unroll
+        for (int i = 0; i < kEntry / 8; i++) { const uint2 v = ep[i]; S.entry[lane][2 * i] = v.x; S.entry[lane][2 * i + 1] = v.y; }
+      }
+      wave_lds_fence();
+
+      // per group of 8 blocks: where its payload run lies, checked as k_stream_decode checks it
+      struct Group { uint32_t t, bw, myOff, off0, n; bool valid, any, ok; };
+      auto group_info = [&](uint32_t grp) {
+        Group G;
+        const uint32_t jb = grp * 8u;
+        G.any = jb < inUnit; // wave-uniform
+        G.t = jb + j; G.bw = 0; G.myOff = 0; G.off0 = 0; G.n = 0; G.valid = false; G.ok = false;
+        if (!G.any) return G;
+        const uint32_t nValid = min(8u, inUnit - jb);
+        G.valid = j < nValid;
+        G.bw = G.valid ? entry_bits(S.entry[G.t][12]) : 0u;
+        G.myOff = G.valid ? S.entry[G.t][13] : 0u;
+        G.off0 = S.entry[jb][13];
+        // all of this in 64 bits: offsets come from the (untrusted) stream, and 32-bit sums such as 0xFFFFFFF0 + 24 wrap to small values that pass
+        const unsigned long long myEnd = (unsigned long long)G.myOff + words_of(G.bw);
+        const uint32_t lastOff = (uint32_t)__shfl((int)G.myOff, (int)nValid - 1, 64), lastWords = (uint32_t)__shfl((int)words_of(G.bw), (int)nValid - 1, 64);
+        const unsigned long long endWord = (unsigned long long)lastOff + lastWords;
+        const bool sane = G.myOff >= G.off0 && myEnd <= endWord && endWord >= G.off0 && endWord - G.off0 <= (unsigned long long)(kGroupBytes / 8) && endWord <= payloadWords;
+        G.ok = __builtin_amdgcn_ballot_w64(G.valid && !sane) == 0;
+        G.n = G.ok ? (uint32_t)(endWord - G.off0) : 0u;
+        return G;
+      };
+      auto fetch = [&](const Group &G, uint2 buf[3]) {
+#pragma unroll
+        for (uint32_t i = 0; i < 3u; i++)
+        {
+          const uint32_t w = (uint32_t)lane + 64u * i;
+          buf[i] = w < G.n ? payload[(size_t)G.off0 + w] : make_uint2(0u, 0u); // (G.n: validated against the payload's size in group_info)
+        }
+      };
+
+      Group cur = group_info(0);
+      uint2 buf[3];
+      fetch(cur, buf);
+      for (uint32_t grp = 0; grp < 8u; grp++)
+      {
+        if (!cur.any) break; // wave-uniform
+        const Group G = cur;
+#pragma unroll
+        for (uint32_t i = 0; i < 3u; i++)
+        {
+          const uint32_t w = (uint32_t)lane + 64u * i;
+          if (w < G.n) stage64[w] = ((unsigned long long)buf[i].y << 32) | buf[i].x;
+        }
+        wave_lds_fence();
+        cur = group_info(grp + 1u);
+        fetch(cur, buf); // the next group's run, in flight while this one is decoded
+        if (!G.ok && lane == 0) raise(2u); // inconsistent offsets: the stream is refused and the group stores nothing
+        const uint32_t x = (bxUnit + G.t) * 8u;
+        if (G.valid && G.ok && y >= p.y0 && y < p.y0 + p.height && x + 8u > p.x0 && x < p.x0 + p.width)
+        {
+          const uint32_t *e = S.entry[G.t];
+          const uint32_t sw = e[12];
+          uint32_t fieldByte = (G.myOff - G.off0) * 8u, bb[3], shift[3];
+          unsigned long long packed[3];
+#pragma unroll
+          for (int k = 0; k < 3; k++)
+          {
+            const uint32_t b = (G.bw >> (8 * k)) & 0xFFu;
+            bb[k] = b; shift[k] = min((sw >> (8 * k)) & 0xFFu, 8u);
+            const uint32_t o = fieldByte + r * b; // a block row is b bytes of its field
+            const uint32_t *wp = reinterpret_cast<const uint32_t *>(S.stage + (o & ~3u));
+            const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
+            const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, o & 3u), hi = __builtin_amdgcn_alignbyte(d2, d1, o & 3u);
+            packed[k] = ((unsigned long long)hi << 32) | lo;
+            fieldByte += b * 8u;
+          }
+          const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(e[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, channels);
+          uint32_t px[8];
+          decode_row(k16, packed, bb, px);
+          store_row_piece(p, x, y, px);
+        }
+        wave_lds_fence(); // every lane is done reading this group's run
+      }
+      wave_lds_fence(); // ... and the unit's entries
+    }
+
     __global__ __launch_bounds__(256) void k_stream_window_decode(const WindowDecodeParams p)
     {
       __shared__ __align__(16) WindowWaveLds sW[4];
@@ -74,97 +178,68 @@ namespace limg_hip
       const int channels = (int)h->channels;
       const uint2 *payload = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)p.nBlocks * kEntry);
       const uint32_t unitsX = (p.wbx + 63u) / 64u, nUnits = unitsX * p.wby;
-      const uint32_t j = (uint32_t)lane & 7u, r = (uint32_t)lane >> 3;
-      unsigned long long *stage64 = reinterpret_cast<unsigned long long *>(S.stage);
-
       for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u) // (wave-uniform; nothing below synchronises across waves)
+        window_unit(p, S, unit, unitsX, channels, payloadWords, payload, lane, [&](uint32_t bits) { atomicOr(p.status, bits); });
+    }
+
+    // ---- batch: the job table ---------------------------------------------------------------------------------------------------------
+    // The job table is written before the launch and by no kernel: read through the constant address space, an entry at a wave-uniform index arrives by scalar loads in
+    // scalar registers, as the single-window kernels' arguments do.  The pointers inside it are device memory (the generic loads the compiler would otherwise emit
+    // for pointers it has read from memory are slower than global ones).
+    template <class T>
+    __device__ __forceinline__ T load_uniform(const T *q)
+    {
+      T v;
+      __builtin_memcpy(&v, (const __attribute__((address_space(4))) T *)(uintptr_t)q, sizeof(T));
+      return v;
+    }
+    template <class T>
+    __device__ __forceinline__ T *as_global(T *q) { return (T *)(__attribute__((address_space(1))) T *)q; }
+    __device__ __forceinline__ WindowDecodeParams load_job(const WindowBatchParams &b, uint32_t job)
+    {
+      WindowDecodeParams p = load_uniform(b.jobs + job);
+      p.stream = as_global(p.stream); p.out = as_global(p.out); p.map = as_global(p.map); p.state = as_global(p.state); p.status = as_global(p.status);
+      return p;
+    }
+
+    // The slot of `x` in an exclusive prefix of n + 1 entries: base[i] <= x < base[i + 1] (no slot is empty).  x is wave-uniform, so every load below is a scalar
+    // load and the index stays in scalar registers: a per-lane search would cost vector registers for nothing.
+    __device__ __forceinline__ uint32_t find_slot(const uint32_t *__restrict__ base, uint32_t n, uint32_t x)
+    {
+      uint32_t lo = 0, hi = n;
+      while (hi - lo > 1u)
       {
-        const uint32_t urow = unit / unitsX, ucol = unit - urow * unitsX;
-        const uint32_t by = p.by0 + urow, bxUnit = p.bx0 + ucol * 64u, inUnit = min(64u, p.wbx - ucol * 64u);
-        const uint32_t y = by * 8u + r;
-        if ((uint32_t)lane < inUnit)
-        { // (block (bxUnit + lane, by) lies inside the block grid: the host has checked the window against the image; the table's extent: stream_header_ok)
-          const uint2 *ep = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + ((size_t)by * p.blocksX + bxUnit + (uint32_t)lane) * kEntry);
-#pragma unroll
-          for (int i = 0; i < kEntry / 8; i++) { const uint2 v = ep[i]; S.entry[lane][2 * i] = v.x; S.entry[lane][2 * i + 1] = v.y; }
-        }
-        wave_lds_fence();
+        const uint32_t mid = (lo + hi) >> 1;
+        if (load_uniform(base + mid) <= x) lo = mid; else hi = mid;
+      }
+      return (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+    }
 
-        // per group of 8 blocks: where its payload run lies, checked as k_stream_decode checks it
-        struct Group { uint32_t t, bw, myOff, off0, n; bool valid, any, ok; };
-        auto group_info = [&](uint32_t grp) {
-          Group G;
-          const uint32_t jb = grp * 8u;
-          G.any = jb < inUnit; // wave-uniform
-          G.t = jb + j; G.bw = 0; G.myOff = 0; G.off0 = 0; G.n = 0; G.valid = false; G.ok = false;
-          if (!G.any) return G;
-          const uint32_t nValid = min(8u, inUnit - jb);
-          G.valid = j < nValid;
-          G.bw = G.valid ? entry_bits(S.entry[G.t][12]) : 0u;
-          G.myOff = G.valid ? S.entry[G.t][13] : 0u;
-          G.off0 = S.entry[jb][13];
-          // all of this in 64 bits: offsets come from the (untrusted) stream, and 32-bit sums such as 0xFFFFFFF0 + 24 wrap to small values that pass
-          const unsigned long long myEnd = (unsigned long long)G.myOff + words_of(G.bw);
-          const uint32_t lastOff = (uint32_t)__shfl((int)G.myOff, (int)nValid - 1, 64), lastWords = (uint32_t)__shfl((int)words_of(G.bw), (int)nValid - 1, 64);
-          const unsigned long long endWord = (unsigned long long)lastOff + lastWords;
-          const bool sane = G.myOff >= G.off0 && myEnd <= endWord && endWord >= G.off0 && endWord - G.off0 <= (unsigned long long)(kGroupBytes / 8) && endWord <= payloadWords;
-          G.ok = __builtin_amdgcn_ballot_w64(G.valid && !sane) == 0;
-          G.n = G.ok ? (uint32_t)(endWord - G.off0) : 0u;
-          return G;
-        };
-        auto fetch = [&](const Group &G, uint2 buf[3]) {
-#pragma unroll
-          for (uint32_t i = 0; i < 3u; i++)
-          {
-            const uint32_t w = (uint32_t)lane + 64u * i;
-            buf[i] = w < G.n ? payload[(size_t)G.off0 + w] : make_uint2(0u, 0u); // (G.n: validated against the payload's size in group_info)
-          }
-        };
+    // a job's status bits: the context's sticky word and the caller's per-job word
+    __device__ __forceinline__ void raise_job(const WindowBatchParams &b, uint32_t job, uint32_t bits)
+    {
+      atomicOr(b.status, bits);
+      if (b.jobStatus) atomicOr(b.jobStatus + job, bits);
+    }
 
-        Group cur = group_info(0);
-        uint2 buf[3];
-        fetch(cur, buf);
-        for (uint32_t grp = 0; grp < 8u; grp++)
-        {
-          if (!cur.any) break; // wave-uniform
-          const Group G = cur;
-#pragma unroll
-          for (uint32_t i = 0; i < 3u; i++)
-          {
-            const uint32_t w = (uint32_t)lane + 64u * i;
-            if (w < G.n) stage64[w] = ((unsigned long long)buf[i].y << 32) | buf[i].x;
-          }
-          wave_lds_fence();
-          cur = group_info(grp + 1u);
-          fetch(cur, buf); // the next group's run, in flight while this one is decoded
-          if (!G.ok && lane == 0) atomicOr(p.status, 2u); // inconsistent offsets: the stream is refused and the group stores nothing
-          const uint32_t x = (bxUnit + G.t) * 8u;
-          if (G.valid && G.ok && y >= p.y0 && y < p.y0 + p.height && x + 8u > p.x0 && x < p.x0 + p.width)
-          {
-            const uint32_t *e = S.entry[G.t];
-            const uint32_t sw = e[12];
-            uint32_t fieldByte = (G.myOff - G.off0) * 8u, bb[3], shift[3];
-            unsigned long long packed[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++)
-            {
-              const uint32_t b = (G.bw >> (8 * k)) & 0xFFu;
-              bb[k] = b; shift[k] = min((sw >> (8 * k)) & 0xFFu, 8u);
-              const uint32_t o = fieldByte + r * b; // a block row is b bytes of its field
-              const uint32_t *wp = reinterpret_cast<const uint32_t *>(S.stage + (o & ~3u));
-              const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
-              const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, o & 3u), hi = __builtin_amdgcn_alignbyte(d2, d1, o & 3u);
-              packed[k] = ((unsigned long long)hi << 32) | lo;
-              fieldByte += b * 8u;
-            }
-            const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(e[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, channels);
-            uint32_t px[8];
-            decode_row(k16, packed, bb, px);
-            store_row_piece(p, x, y, px);
-          }
-          wave_lds_fence(); // every lane is done reading this group's run
+    __global__ __launch_bounds__(256) void k_stream_windows_decode(const WindowBatchParams b)
+    {
+      __shared__ __align__(16) WindowWaveLds sW[4];
+      const int lane = lane_id();
+      const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      WindowWaveLds &S = sW[wave];
+      for (uint32_t unit = blockIdx.x * 4u + wave; unit < b.totalUnits; unit += gridDim.x * 4u) // (wave-uniform; nothing below synchronises across waves)
+      {
+        const uint32_t job = find_slot(b.unitBase, b.count, unit), first = load_uniform(b.unitBase + job);
+        const WindowDecodeParams p = load_job(b, job);
+        const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
+        if (!stream_header_ok(h, LIMG_HIP_STREAM_VERSION, kEntry, p.nBlocks, p))
+        { // every unit of the job takes this way: the job writes nothing; its first unit says so
+          if (unit == first && lane == 0) raise_job(b, job, 1u);
+          continue;
         }
-        wave_lds_fence(); // ... and the unit's entries
+        const uint2 *payload = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)p.nBlocks * kEntry);
+        window_unit(p, S, unit - first, (p.wbx + 63u) / 64u, (int)h->channels, h->payloadWords, payload, lane, [&](uint32_t bits) { raise_job(b, job, bits); });
       }
     }
 
@@ -173,6 +248,74 @@ namespace limg_hip
     {
       atomicOr(p.state + 1, 1u);
       atomicOr(p.status, bit);
+    }
+
+    // A rectangle's geometry, shifts and payload extent, as k_bstream_map checks them.  e3: the entry's last 16 bytes; G: the image (WindowDecodeParams / WindowGroup).
+    template <class G>
+    __device__ __forceinline__ bool rect_ok(const G &g, const uint4 e3, unsigned long long payloadWords)
+    {
+      const uint32_t ox = e3.z & 0xFFFFu, oy = e3.z >> 16, rx = e3.w & 0xFFFFu, ry = e3.w >> 16, sw = e3.x;
+      bool good = rx >= 1u && ry >= 1u && ox + rx <= g.blocksX && oy + ry <= g.blocksY && (sw & 0xFFu) <= 8u && ((sw >> 8) & 0xFFu) <= 8u && ((sw >> 16) & 0xFFu) <= 8u;
+      if (good)
+      {
+        uint32_t wpx;
+        const uint32_t n = rect_pixels(g.sizeX, g.sizeY, g.blocksX, g.blocksY, ox, oy, rx, ry, wpx);
+        good = (unsigned long long)e3.y + rect_words(n, entry_bits(sw)) <= payloadWords; // (a field is at most n / 8 + 1 words, three of them far below 2^32)
+      }
+      return good;
+    }
+
+    // rectangle (e3) n p's window block range -> ix0, iy0, iw, ih; iw = ih = 0 where they do not meet
+    __device__ __forceinline__ void rect_in_window(const WindowDecodeParams &p, const uint4 e3, uint32_t &ix0, uint32_t &iy0, uint32_t &iw, uint32_t &ih)
+    {
+      const uint32_t ox = e3.z & 0xFFFFu, oy = e3.z >> 16, rx = e3.w & 0xFFFFu, ry = e3.w >> 16;
+      ix0 = max(ox, p.bx0); iy0 = max(oy, p.by0); iw = 0; ih = 0;
+      const uint32_t ix1 = min(ox + rx, p.bx0 + p.wbx), iy1 = min(oy + ry, p.by0 + p.wby);
+      if (ix1 > ix0 && iy1 > iy0) { iw = ix1 - ix0; ih = iy1 - iy0; }
+    }
+
+    // The wave's 64 rectangles base .. base + 63, each lane's piece (rectangle n window block range; iw * ih = 0: none) claimed in p's window-sized map.  Returns whether
+    // the lane met a block that was taken already; `claimed` counts the lane's claims.
+    __device__ __forceinline__ bool claim_pieces(const WindowDecodeParams &p, uint32_t base, int lane, uint32_t ix0, uint32_t iy0, uint32_t iw, uint32_t ih, uint32_t &claimed)
+    {
+      const uint32_t rect = base + (uint32_t)lane, nb = iw * ih;
+      bool clash = false;
+      if (nb >= 1u && nb <= 4u)
+      { // a small piece: its lane claims it
+        for (uint32_t i = 0; i < nb; i++)
+        {
+          const uint32_t dy = i / iw, dx = i - dy * iw;
+          if (atomicCAS(p.map + (size_t)(iy0 - p.by0 + dy) * p.wbx + (ix0 - p.bx0 + dx), kNoRect, rect) != kNoRect) { clash = true; break; }
+          claimed++;
+        }
+      }
+      // the large ones, one after the other, by the whole wave; a block that is taken already ends the rectangle (and the stream): the work is bounded by the window's blocks
+      unsigned long long big = __builtin_amdgcn_ballot_w64(nb > 4u);
+      while (big != 0ull && __builtin_amdgcn_ballot_w64(clash) == 0ull)
+      {
+        const int src = __builtin_ctzll(big);
+        big &= big - 1ull;
+        const uint32_t bx = (uint32_t)__shfl((int)ix0, src, 64), by = (uint32_t)__shfl((int)iy0, src, 64), bw = (uint32_t)__shfl((int)iw, src, 64),
+                       bnb = (uint32_t)__shfl((int)nb, src, 64);
+        for (uint32_t i0 = 0; i0 < bnb && __builtin_amdgcn_ballot_w64(clash) == 0ull; i0 += 64u)
+        {
+          const uint32_t i = i0 + (uint32_t)lane;
+          if (i < bnb)
+          {
+            const uint32_t dy = i / bw, dx = i - dy * bw;
+            if (atomicCAS(p.map + (size_t)(by - p.by0 + dy) * p.wbx + (bx - p.bx0 + dx), kNoRect, base + (uint32_t)src) != kNoRect) clash = true;
+            else claimed++;
+          }
+        }
+      }
+      return clash;
+    }
+
+    __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+    {
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
+      return v;
     }
 
     __global__ __launch_bounds__(256) void k_bstream_window_map(const WindowDecodeParams p)
@@ -186,7 +329,6 @@ namespace limg_hip
         if (tid == 0 && blockIdx.x == 0) refuse(p, 1u);
         return;
       }
-      const uint32_t bx1 = p.bx0 + p.wbx, by1 = p.by0 + p.wby;
       uint32_t claimed = 0;
       for (uint32_t base = (blockIdx.x * 4u + (uint32_t)wave) * 64u; base < nRects; base += gridDim.x * 256u)
       {
@@ -196,57 +338,60 @@ namespace limg_hip
         if (rect < nRects)
         {
           const uint4 e3 = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)rect * kRectEntry)[3];
-          const uint32_t ox = e3.z & 0xFFFFu, oy = e3.z >> 16, rx = e3.w & 0xFFFFu, ry = e3.w >> 16, sw = e3.x;
-          bool good = rx >= 1u && ry >= 1u && ox + rx <= p.blocksX && oy + ry <= p.blocksY && (sw & 0xFFu) <= 8u && ((sw >> 8) & 0xFFu) <= 8u && ((sw >> 16) & 0xFFu) <= 8u;
-          if (good)
-          {
-            uint32_t wpx;
-            const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, ox, oy, rx, ry, wpx);
-            good = (unsigned long long)e3.y + rect_words(n, entry_bits(sw)) <= payloadWords; // (a field is at most n / 8 + 1 words, three of them far below 2^32)
-          }
-          if (!good) refuse(p, 2u);
-          else
-          {
-            ix0 = max(ox, p.bx0); iy0 = max(oy, p.by0);
-            const uint32_t ix1 = min(ox + rx, bx1), iy1 = min(oy + ry, by1);
-            if (ix1 > ix0 && iy1 > iy0) { iw = ix1 - ix0; ih = iy1 - iy0; }
-          }
+          if (!rect_ok(p, e3, payloadWords)) refuse(p, 2u);
+          else rect_in_window(p, e3, ix0, iy0, iw, ih);
         }
-        const uint32_t nb = iw * ih;
-        bool clash = false;
-        if (nb >= 1u && nb <= 4u)
-        { // a small piece: its lane claims it
-          for (uint32_t i = 0; i < nb; i++)
-          {
-            const uint32_t dy = i / iw, dx = i - dy * iw;
-            if (atomicCAS(p.map + (size_t)(iy0 - p.by0 + dy) * p.wbx + (ix0 - p.bx0 + dx), kNoRect, rect) != kNoRect) { clash = true; break; }
-            claimed++;
-          }
-        }
-        // the large ones, one after the other, by the whole wave; a block that is taken already ends the rectangle (and the stream): the work is bounded by the window's blocks
-        unsigned long long big = __builtin_amdgcn_ballot_w64(nb > 4u);
-        while (big != 0ull && __builtin_amdgcn_ballot_w64(clash) == 0ull)
-        {
-          const int src = __builtin_ctzll(big);
-          big &= big - 1ull;
-          const uint32_t bx = (uint32_t)__shfl((int)ix0, src, 64), by = (uint32_t)__shfl((int)iy0, src, 64), bw = (uint32_t)__shfl((int)iw, src, 64),
-                         bnb = (uint32_t)__shfl((int)nb, src, 64);
-          for (uint32_t i0 = 0; i0 < bnb && __builtin_amdgcn_ballot_w64(clash) == 0ull; i0 += 64u)
-          {
-            const uint32_t i = i0 + (uint32_t)lane;
-            if (i < bnb)
-            {
-              const uint32_t dy = i / bw, dx = i - dy * bw;
-              if (atomicCAS(p.map + (size_t)(by - p.by0 + dy) * p.wbx + (bx - p.bx0 + dx), kNoRect, base + (uint32_t)src) != kNoRect) clash = true;
-              else claimed++;
-            }
-          }
-        }
-        if (clash) refuse(p, 2u);
+        if (claim_pieces(p, base, lane, ix0, iy0, iw, ih, claimed)) refuse(p, 2u);
       }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) claimed += (uint32_t)__shfl_xor((int)claimed, off, 64);
+      claimed = wave_sum(claimed);
       if (lane == 0 && claimed) atomicAdd(p.state, claimed);
+    }
+
+    // One unit of version 2: 8 consecutive blocks of block row `unit / unitsX` of p's window, lane = (block j = lane & 7, row = lane >> 3).  nRects, channels, tableEnd,
+    // total: from the header the map kernel has checked; the caller has read the verdict.
+    __device__ __forceinline__ void bwindow_unit(const WindowDecodeParams &p, uint32_t unit, uint32_t unitsX, uint32_t nRects, uint32_t channels, unsigned long long tableEnd,
+                                                 unsigned long long total, int lane)
+    {
+      const uint32_t j = (uint32_t)lane & 7u, row = (uint32_t)lane >> 3;
+      const uint32_t urow = unit / unitsX, wbxi = (unit - urow * unitsX) * 8u + j; // the block's place in the window's block range
+      const uint32_t y = (p.by0 + urow) * 8u + row, x = (p.bx0 + wbxi) * 8u;
+      if (wbxi >= p.wbx || y < p.y0 || y >= p.y0 + p.height) return;
+      const uint32_t rect = p.map[(size_t)urow * p.wbx + wbxi];
+      if (rect >= nRects) return; // (cannot happen after the verdict; a lane never indexes the table with anything else)
+      const uint4 *ep = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)rect * kRectEntry);
+      const uint4 e0 = ep[0], e1 = ep[1], e2 = ep[2], e3 = ep[3];
+      const uint32_t ev[12] = { e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w };
+      const uint32_t sw = e3.x, ox = e3.z & 0xFFFFu, oy = e3.z >> 16, rx = e3.w & 0xFFFFu, ry = e3.w >> 16;
+      uint32_t wpx;
+      const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, ox, oy, rx, ry, wpx);
+      const unsigned long long i0 = (unsigned long long)(y - oy * 8u) * wpx + (x - ox * 8u);
+      const uint32_t bits = entry_bits(sw);
+      // the lane's 8 values of each field: the bit run at i0 * b
+      unsigned long long packed[3];
+      uint32_t bb[3], shift[3];
+      unsigned long long fieldByte = tableEnd + (unsigned long long)e3.y * 8ull;
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+      {
+        const uint32_t b = (bits >> (8 * k)) & 0xFFu;
+        bb[k] = b; shift[k] = (sw >> (8 * k)) & 0xFFu;
+        packed[k] = 0;
+        if (b)
+        {
+          const unsigned long long bit = i0 * b, byte = fieldByte + (bit >> 3), at = byte & ~3ull;
+          const uint32_t sh = (uint32_t)(byte & 3ull) * 8u + (uint32_t)(bit & 7ull); // < 32
+          // three aligned dwords hold the run's 64 bits wherever it starts; the last may lie beyond the stream's end (never beyond the field's: it is not used then)
+          const uint32_t *wp = reinterpret_cast<const uint32_t *>(p.stream + at);
+          const uint32_t d0 = at + 4ull <= total ? wp[0] : 0u, d1 = at + 8ull <= total ? wp[1] : 0u, d2 = at + 12ull <= total ? wp[2] : 0u;
+          const unsigned long long lo = ((unsigned long long)d1 << 32) | d0;
+          packed[k] = sh ? ((lo >> sh) | ((unsigned long long)d2 << (64u - sh))) : lo;
+          fieldByte += (unsigned long long)field_words(n, b) * 8ull;
+        }
+      }
+      const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(ev[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, (int)channels);
+      uint32_t px[8];
+      decode_row(k16, packed, bb, px);
+      store_row_piece(p, x, y, px); // (columns beyond a partial last block column lie outside the image, so outside the window)
     }
 
     __global__ __launch_bounds__(256) void k_bstream_window_decode(const WindowDecodeParams p)
@@ -262,48 +407,94 @@ namespace limg_hip
       const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h->channels;
       const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h->payloadWords * 8ull;
       const uint32_t unitsX = (p.wbx + 7u) / 8u, nUnits = unitsX * p.wby;
-      const uint32_t j = (uint32_t)lane & 7u, row = (uint32_t)lane >> 3;
-      for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u)
+      for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u) bwindow_unit(p, unit, unitsX, nRects, channels, tableEnd, total, lane);
+    }
+
+    // ---- version 2, batch ------------------------------------------------------------------------------------------------------------
+    // every job of the group is refused: a header that does not match or a rectangle that is malformed concerns all windows of the stream
+    __device__ __forceinline__ void refuse_group(const WindowBatchParams &b, const WindowGroup &g, uint32_t bit, int lane)
+    {
+      for (uint32_t jj = (uint32_t)lane; jj < g.nJobs; jj += 64u)
       {
-        const uint32_t urow = unit / unitsX, wbxi = (unit - urow * unitsX) * 8u + j; // the block's place in the window's block range
-        const uint32_t y = (p.by0 + urow) * 8u + row, x = (p.bx0 + wbxi) * 8u;
-        if (wbxi >= p.wbx || y < p.y0 || y >= p.y0 + p.height) continue;
-        const uint32_t rect = p.map[(size_t)urow * p.wbx + wbxi];
-        if (rect >= nRects) continue; // (cannot happen after the check above; a lane never indexes the table with anything else)
-        const uint4 *ep = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)rect * kRectEntry);
-        const uint4 e0 = ep[0], e1 = ep[1], e2 = ep[2], e3 = ep[3];
-        const uint32_t ev[12] = { e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w };
-        const uint32_t sw = e3.x, ox = e3.z & 0xFFFFu, oy = e3.z >> 16, rx = e3.w & 0xFFFFu, ry = e3.w >> 16;
-        uint32_t wpx;
-        const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, ox, oy, rx, ry, wpx);
-        const unsigned long long i0 = (unsigned long long)(y - oy * 8u) * wpx + (x - ox * 8u);
-        const uint32_t bits = entry_bits(sw);
-        // the lane's 8 values of each field: the bit run at i0 * b
-        unsigned long long packed[3];
-        uint32_t bb[3], shift[3];
-        unsigned long long fieldByte = tableEnd + (unsigned long long)e3.y * 8ull;
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-        {
-          const uint32_t b = (bits >> (8 * k)) & 0xFFu;
-          bb[k] = b; shift[k] = (sw >> (8 * k)) & 0xFFu;
-          packed[k] = 0;
-          if (b)
-          {
-            const unsigned long long bit = i0 * b, byte = fieldByte + (bit >> 3), at = byte & ~3ull;
-            const uint32_t sh = (uint32_t)(byte & 3ull) * 8u + (uint32_t)(bit & 7ull); // < 32
-            // three aligned dwords hold the run's 64 bits wherever it starts; the last may lie beyond the stream's end (never beyond the field's: it is not used then)
-            const uint32_t *wp = reinterpret_cast<const uint32_t *>(p.stream + at);
-            const uint32_t d0 = at + 4ull <= total ? wp[0] : 0u, d1 = at + 8ull <= total ? wp[1] : 0u, d2 = at + 12ull <= total ? wp[2] : 0u;
-            const unsigned long long lo = ((unsigned long long)d1 << 32) | d0;
-            packed[k] = sh ? ((lo >> sh) | ((unsigned long long)d2 << (64u - sh))) : lo;
-            fieldByte += (unsigned long long)field_words(n, b) * 8ull;
-          }
+        const uint32_t job = b.groupJobs[g.firstJob + jj];
+        atomicOr(b.jobs[job].state + 1, 1u);
+        if (b.jobStatus) atomicOr(b.jobStatus + job, bit);
+      }
+      if (lane == 0) atomicOr(b.status, bit);
+    }
+
+    __global__ __launch_bounds__(256) void k_bstream_windows_map(const WindowBatchParams b)
+    {
+      const int lane = lane_id();
+      const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      for (uint32_t item = blockIdx.x * 4u + wave; item < b.totalItems; item += gridDim.x * 4u) // (wave-uniform)
+      {
+        const uint32_t gi = find_slot(b.groupItemBase, b.nGroups, item);
+        WindowGroup g = load_uniform(b.groups + gi);
+        g.stream = as_global(g.stream);
+        const uint32_t base = (item - load_uniform(b.groupItemBase + gi)) * 64u;
+        const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(g.stream);
+        const unsigned long long payloadWords = h->payloadWords;
+        const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES];
+        if (!(nRects >= 1u && nRects <= g.nBlocks && stream_header_ok(h, LIMG_HIP_STREAM_VERSION_BLOCKED, kRectEntry, nRects, g)))
+        { // every item of the group takes this way: nothing of the table is read; the first item refuses the group's jobs
+          if (base == 0u) refuse_group(b, g, 1u, lane);
+          continue;
         }
-        const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(ev[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, (int)channels);
-        uint32_t px[8];
-        decode_row(k16, packed, bb, px);
-        store_row_piece(p, x, y, px); // (columns beyond a partial last block column lie outside the image, so outside the window)
+        if (base >= nRects) continue; // (the items cover nBlocks rectangles, the most a table may hold)
+        // the rectangle, checked once for the whole group
+        const uint32_t rect = base + (uint32_t)lane;
+        uint4 e3 = make_uint4(0u, 0u, 0u, 0u);
+        bool good = true;
+        if (rect < nRects)
+        {
+          e3 = reinterpret_cast<const uint4 *>(g.stream + sizeof(limg_hip_stream_header) + (size_t)rect * kRectEntry)[3];
+          good = rect_ok(g, e3, payloadWords);
+        }
+        if (__builtin_amdgcn_ballot_w64(!good) != 0ull)
+        {
+          refuse_group(b, g, 2u, lane);
+          continue;
+        }
+        // ... and offered to every window of the group (lanes beyond the table: e3 = 0 is a rectangle of no blocks)
+        for (uint32_t jj = 0; jj < g.nJobs; jj++)
+        {
+          const uint32_t job = load_uniform(b.groupJobs + g.firstJob + jj);
+          const WindowDecodeParams p = load_job(b, job);
+          if (ld_volatile(p.state + 1) != 0u) continue; // refused already: nothing of it will be decoded (wave-uniform)
+          uint32_t ix0, iy0, iw, ih;
+          rect_in_window(p, e3, ix0, iy0, iw, ih);
+          if (__builtin_amdgcn_ballot_w64(iw * ih != 0u) == 0ull) continue; // none of the 64 meets this window
+          uint32_t claimed = 0;
+          if (__builtin_amdgcn_ballot_w64(claim_pieces(p, base, lane, ix0, iy0, iw, ih, claimed)) != 0ull && lane == 0)
+          { // a clash refuses the job whose map it happened in
+            atomicOr(p.state + 1, 1u);
+            raise_job(b, job, 2u);
+          }
+          claimed = wave_sum(claimed);
+          if (lane == 0 && claimed) atomicAdd(p.state, claimed);
+        }
+      }
+    }
+
+    __global__ __launch_bounds__(256) void k_bstream_windows_decode(const WindowBatchParams b)
+    {
+      const int lane = lane_id();
+      const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      for (uint32_t unit = blockIdx.x * 4u + wave; unit < b.totalUnits; unit += gridDim.x * 4u) // (wave-uniform)
+      {
+        const uint32_t job = find_slot(b.unitBase, b.count, unit), first = load_uniform(b.unitBase + job);
+        const WindowDecodeParams p = load_job(b, job);
+        // the job's verdict from k_bstream_windows_map: nothing flagged and every block of its window claimed exactly once
+        if (ld_volatile(p.state + 1) != 0u || ld_volatile(p.state) != p.wbx * p.wby)
+        {
+          if (unit == first && lane == 0) raise_job(b, job, 2u);
+          continue;
+        }
+        const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
+        const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h->channels;
+        const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h->payloadWords * 8ull;
+        bwindow_unit(p, unit - first, (p.wbx + 7u) / 8u, nRects, channels, tableEnd, total, lane);
       }
     }
   }
@@ -322,5 +513,21 @@ namespace limg_hip
     hipLaunchKernelGGL(k_bstream_window_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, p);
     const uint32_t units = ((p.wbx + 7u) / 8u) * p.wby, need = (units + 3u) / 4u;
     hipLaunchKernelGGL(k_bstream_window_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, p);
+  }
+
+  // the batched forms: the grid comes from the call's totals, so many small windows fill the device that one of them would leave nearly empty
+  void launch_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s)
+  {
+    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u), slots = (uint32_t)cus * 4u;
+    hipLaunchKernelGGL(k_stream_windows_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, b);
+  }
+
+  void launch_blocked_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s)
+  {
+    const uint32_t slots = (uint32_t)cus * 8u;
+    const uint32_t needMap = b.totalItems / 4u + (b.totalItems % 4u ? 1u : 0u);
+    hipLaunchKernelGGL(k_bstream_windows_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, b);
+    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u);
+    hipLaunchKernelGGL(k_bstream_windows_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, b);
   }
 }
