@@ -1,4 +1,5 @@
-// limg_hip_blocked_stream.hip -- version 2 of the "LMG3" stream: the merged-block encoder's rectangles (format: include/limg_hip.h).
+// limg_hip_blocked_stream.hip -- version 2 of the "LMG3" stream: the merged-block encoder's rectangles (format: include/limg_hip.h).  The packer; every decode of this
+// version, the whole image included, is limg_hip_stream_window.hip.
 //
 // Pack, after a compact-mode merged-block encode (blocked_encode_device with no planes), from what that leaves in the context: per rectangle its descriptor, record and
 // shift word, its pre-dither factor bytes and noise bytes, both region-major (pixel i = yy * wpx + xx of the rectangle at byte i: the order the stream wants).
@@ -10,13 +11,6 @@
 //                           bytes where the field is dithered) with four 16-byte loads, dithers and crushes them (dither_crush4, as k_blocked_store does), squeezes every 8
 //                           values into b bytes with the mask-and-shift steps of k_stream_pack_strips and stores b 8-byte words.  Runs that are short (the tail of a
 //                           rectangle on an image with partial blocks) or not 16-byte aligned gather their bytes one by one -- same bytes out.
-// Decode:
-//   k_bstream_map           validates the table and scatters it into a block -> rectangle map: 64 rectangles per wave step, a lane claims the blocks of a small
-//                           rectangle itself (atomicCAS on ~0), the wave claims a large one together; the claimed blocks are counted
-//   k_bstream_decode        refuses unless every block was claimed and nothing was flagged; then lane = (block j = lane & 7, block row r = lane >> 3) over units of 8
-//                           consecutive blocks: the lane's 8 pixels are the bit run at ((y - 8 oy) * wpx + (x - 8 ox)) * b of each field of the block's rectangle; the
-//                           integer decode is a16_constants / a16_pixel, as in k_blocked_store; a wave's stores are 8 row pieces of 256 contiguous bytes.
-// Nothing here reads through an offset the map kernel has not checked against the stream's size.
 #include "limg_hip_stream_format.h"
 
 namespace limg_hip
@@ -181,157 +175,6 @@ namespace limg_hip
         }
       }
     }
-
-    // ---- decode ----------------------------------------------------------------------------------------------------------------------
-    __device__ __forceinline__ void refuse(const BlockedDecodeParams &p, uint32_t bit)
-    {
-      atomicOr(p.state + 1, 1u);
-      atomicOr(p.status, bit);
-    }
-
-    __global__ __launch_bounds__(256) void k_bstream_map(const BlockedDecodeParams p)
-    {
-      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-      const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
-      const unsigned long long payloadWords = h->payloadWords;
-      const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES];
-      if (!(nRects >= 1u && nRects <= p.nBlocks && stream_header_ok(h, LIMG_HIP_STREAM_VERSION_BLOCKED, kRectEntry, nRects, p)))
-      {
-        if (tid == 0 && blockIdx.x == 0) refuse(p, 1u);
-        return;
-      }
-      uint32_t claimed = 0;
-      for (uint32_t base = (blockIdx.x * 4u + (uint32_t)wave) * 64u; base < nRects; base += gridDim.x * 256u)
-      {
-        if (ld_volatile(p.state + 1) != 0u) break; // refused already (all lanes read the same word: wave-uniform)
-        const uint32_t r = base + (uint32_t)lane;
-        uint32_t ox = 0, oy = 0, rx = 0, ry = 0;
-        bool good = false;
-        if (r < nRects)
-        {
-          const uint4 e3 = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)r * kRectEntry)[3];
-          ox = e3.z & 0xFFFFu; oy = e3.z >> 16; rx = e3.w & 0xFFFFu; ry = e3.w >> 16;
-          const uint32_t sw = e3.x;
-          good = rx >= 1u && ry >= 1u && ox + rx <= p.blocksX && oy + ry <= p.blocksY && (sw & 0xFFu) <= 8u && ((sw >> 8) & 0xFFu) <= 8u && ((sw >> 16) & 0xFFu) <= 8u;
-          if (good)
-          {
-            uint32_t wpx;
-            const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, ox, oy, rx, ry, wpx);
-            good = (unsigned long long)e3.y + rect_words(n, entry_bits(sw)) <= payloadWords; // (a field is at most n / 8 + 1 words, three of them far below 2^32)
-          }
-          if (!good) refuse(p, 2u);
-        }
-        const uint32_t nb = good ? rx * ry : 0u;
-        bool clash = false;
-        if (nb >= 1u && nb <= 4u)
-        { // a small rectangle: its lane claims it
-          for (uint32_t i = 0; i < nb; i++)
-          {
-            const uint32_t dy = i / rx, dx = i - dy * rx;
-            if (atomicCAS(p.map + (size_t)(oy + dy) * p.blocksX + ox + dx, kNoRect, r) != kNoRect) { clash = true; break; }
-            claimed++;
-          }
-        }
-        // the large ones, one after the other, by the whole wave; a block that is taken already ends the rectangle (and the stream): the work is bounded by the blocks
-        unsigned long long big = __builtin_amdgcn_ballot_w64(nb > 4u);
-        while (big != 0ull && __builtin_amdgcn_ballot_w64(clash) == 0ull)
-        {
-          const int src = __builtin_ctzll(big);
-          big &= big - 1ull;
-          const uint32_t box = (uint32_t)__shfl((int)ox, src, 64), boy = (uint32_t)__shfl((int)oy, src, 64), brx = (uint32_t)__shfl((int)rx, src, 64),
-                         bnb = (uint32_t)__shfl((int)nb, src, 64);
-          for (uint32_t i0 = 0; i0 < bnb && __builtin_amdgcn_ballot_w64(clash) == 0ull; i0 += 64u)
-          {
-            const uint32_t i = i0 + (uint32_t)lane;
-            if (i < bnb)
-            {
-              const uint32_t dy = i / brx, dx = i - dy * brx;
-              if (atomicCAS(p.map + (size_t)(boy + dy) * p.blocksX + box + dx, kNoRect, base + (uint32_t)src) != kNoRect) clash = true;
-              else claimed++;
-            }
-          }
-        }
-        if (clash) refuse(p, 2u);
-      }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) claimed += (uint32_t)__shfl_xor((int)claimed, off, 64);
-      if (lane == 0 && claimed) atomicAdd(p.state, claimed);
-    }
-
-    __global__ __launch_bounds__(256) void k_bstream_decode(const BlockedDecodeParams p)
-    {
-      const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-      // the verdict of k_bstream_map: nothing flagged and every block claimed exactly once (claims never overlap, so the count says it)
-      if (ld_volatile(p.state + 1) != 0u || ld_volatile(p.state) != p.nBlocks)
-      {
-        if (tid == 0 && blockIdx.x == 0) atomicOr(p.status, 2u);
-        return;
-      }
-      const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
-      const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h->channels;
-      const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h->payloadWords * 8ull;
-      const uint32_t unitsX = (p.blocksX + 7u) / 8u, nUnits = unitsX * p.blocksY;
-      const uint32_t j = (uint32_t)lane & 7u, row = (uint32_t)lane >> 3;
-      const bool rowAligned = (p.sizeX & 3u) == 0;
-      for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u)
-      {
-        const uint32_t by = unit / unitsX, bx = (unit - by * unitsX) * 8u + j;
-        const uint32_t y = by * 8u + row, x0 = bx * 8u;
-        if (bx >= p.blocksX || y >= p.sizeY) continue;
-        const uint32_t rect = p.map[(size_t)by * p.blocksX + bx];
-        if (rect >= nRects) continue; // (cannot happen after the check above; a lane never indexes the table with anything else)
-        const uint4 *ep = reinterpret_cast<const uint4 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)rect * kRectEntry);
-        const uint4 e0 = ep[0], e1 = ep[1], e2 = ep[2], e3 = ep[3];
-        const uint32_t ev[12] = { e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w };
-        const uint32_t sw = e3.x, ox = e3.z & 0xFFFFu, oy = e3.z >> 16, rx = e3.w & 0xFFFFu, ry = e3.w >> 16;
-        uint32_t wpx;
-        const uint32_t n = rect_pixels(p.sizeX, p.sizeY, p.blocksX, p.blocksY, ox, oy, rx, ry, wpx);
-        const uint32_t cnt = min(8u, p.sizeX - x0);
-        const unsigned long long i0 = (unsigned long long)(y - oy * 8u) * wpx + (x0 - ox * 8u);
-        const uint32_t bits = entry_bits(sw);
-        // the lane's 8 values of each field: the bit run at i0 * b
-        unsigned long long packed[3];
-        uint32_t bb[3], shift[3];
-        unsigned long long fieldByte = tableEnd + (unsigned long long)e3.y * 8ull;
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-        {
-          const uint32_t b = (bits >> (8 * k)) & 0xFFu;
-          bb[k] = b; shift[k] = (sw >> (8 * k)) & 0xFFu;
-          packed[k] = 0;
-          if (b)
-          {
-            const unsigned long long bit = i0 * b, byte = fieldByte + (bit >> 3), at = byte & ~3ull;
-            const uint32_t sh = (uint32_t)(byte & 3ull) * 8u + (uint32_t)(bit & 7ull); // < 32
-            // three aligned dwords hold the run's 64 bits wherever it starts; the last may lie beyond the stream's end (never beyond the field's: it is not used then)
-            const uint32_t *wp = reinterpret_cast<const uint32_t *>(p.stream + at);
-            const uint32_t d0 = at + 4ull <= total ? wp[0] : 0u, d1 = at + 8ull <= total ? wp[1] : 0u, d2 = at + 12ull <= total ? wp[2] : 0u;
-            const unsigned long long lo = ((unsigned long long)d1 << 32) | d0;
-            packed[k] = sh ? ((lo >> sh) | ((unsigned long long)d2 << (64u - sh))) : lo;
-            fieldByte += (unsigned long long)field_words(n, b) * 8ull;
-          }
-        }
-        const A16 k = a16_constants([&](int v, int c) { return (int)(int16_t)(ev[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, (int)channels);
-        uint32_t px[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-          px[i] = a16_pixel(k, (uint32_t)(packed[0] >> (i * bb[0])) & ((1u << bb[0]) - 1u), (uint32_t)(packed[1] >> (i * bb[1])) & ((1u << bb[1]) - 1u),
-                            (uint32_t)(packed[2] >> (i * bb[2])) & ((1u << bb[2]) - 1u));
-        uint32_t *dst = p.out + (size_t)y * p.sizeX + x0;
-        if (cnt == 8u && rowAligned)
-        { // a wave's stores: 8 row pieces of 8 x 32 contiguous bytes
-          reinterpret_cast<uint4 *>(dst)[0] = make_uint4(px[0], px[1], px[2], px[3]);
-          reinterpret_cast<uint4 *>(dst)[1] = make_uint4(px[4], px[5], px[6], px[7]);
-        }
-        else
-        {
-#pragma unroll
-          for (int i = 0; i < 8; i++)
-            if ((uint32_t)i < cnt) dst[i] = px[i];
-        }
-      }
-    }
-
   }
 
   void launch_blocked_stream_pack(const BlockedStreamParams &p, int cus, hipStream_t s)
@@ -345,14 +188,5 @@ namespace limg_hip
     // one lane per run of 64 pixels; an image has at most blocks + rectangles runs.  Eight workgroups of four waves per CU, striding
     const uint64_t runsMax = (uint64_t)p.blocksX * p.blocksY + p.nRegions, need = (runsMax + 255u) / 256u, slots = (uint64_t)cus * 8u;
     hipLaunchKernelGGL(k_bstream_pack, dim3((uint32_t)(need < slots ? need : slots)), dim3(256), 0, s, p);
-  }
-
-  void launch_blocked_stream_decode(const BlockedDecodeParams &p, int cus, hipStream_t s)
-  {
-    const uint32_t slots = (uint32_t)cus * 8u;
-    const uint32_t needMap = (p.nBlocks + 255u) / 256u; // at most nBlocks rectangles, 64 per wave
-    hipLaunchKernelGGL(k_bstream_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, p);
-    const uint32_t units = ((p.blocksX + 7u) / 8u) * p.blocksY, need = (units + 3u) / 4u;
-    hipLaunchKernelGGL(k_bstream_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, p);
   }
 }

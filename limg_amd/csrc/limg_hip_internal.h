@@ -182,7 +182,7 @@ namespace limg_hip
   void launch_blocked_store(const BlockedParams &p, hipStream_t s);
   void launch_blocked_order(const BlockedParams &p, hipStream_t s);
 
-  // ---- version 2 stream: the merged-block encoder's rectangles (limg_hip_blocked_stream.hip) ----
+  // ---- version 2 stream: the merged-block encoder's rectangles (limg_hip_blocked_stream.hip; its decode, whole images included: the window decode below) ----
   // Pack: from what a compact-mode merged-block encode leaves in the context (see blocked_encode_device).  The work unit is a RUN: 64 consecutive pixels (rectangle
   // row-major order) of one rectangle, all three fields.
   struct BlockedStreamParams
@@ -197,19 +197,8 @@ namespace limg_hip
     uint32_t *units; // nRegions + 1: every rectangle's first run (exclusive prefix of ceil(n / 64)); [nRegions] = all runs
     uint32_t *tiles; // per tile of 256 rectangles { payload words, runs }: totals, then (k_stream_tile_scan<2>) their exclusive prefix
   };
-  struct BlockedDecodeParams
-  {
-    uint32_t sizeX, sizeY, blocksX, blocksY, nBlocks;
-    const uint8_t *stream;
-    unsigned long long streamBytes;
-    uint32_t *out;
-    uint32_t *map;    // per block the rectangle that covers it (~0: none yet)
-    uint32_t *status; // the context's sticky stream status word: bit 0 header mismatch, bit 1 inconsistent table or payload offsets
-    uint32_t *state;  // this call's words (zeroed in front of it): [0] blocks claimed by the rectangles, [1] non-0 = the stream is refused
-  };
   // (cus: the device's compute units, as the context knows them -- limg_hip_context::persistentWorkgroups / 5; the persistent launches size themselves by it)
   void launch_blocked_stream_pack(const BlockedStreamParams &p, int cus, hipStream_t s);
-  void launch_blocked_stream_decode(const BlockedDecodeParams &p, int cus, hipStream_t s);
 
   // ---- window decode, both versions (limg_hip_stream_window.hip): a pixel rectangle of the image into a caller's stride ----
   struct WindowDecodeParams
@@ -223,7 +212,7 @@ namespace limg_hip
     unsigned long long outStride;
     uint32_t vecOut;                // a block row piece that lies wholly inside the window may leave as two 16-byte stores (out 16-byte aligned, outStride % 4 == 0, x0 % 4 == 0)
     uint32_t *map;                  // version 2: per block of the window the rectangle that covers it (~0: none yet)
-    uint32_t *status;               // the context's sticky stream status word, bits as in DecodeParams / BlockedDecodeParams
+    uint32_t *status;               // the context's sticky stream status word, bits as in DecodeParams
     uint32_t *state;                // version 2: this call's words (zeroed in front of it): [0] window blocks claimed, [1] non-0 = the stream is refused
   };
   void launch_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s);

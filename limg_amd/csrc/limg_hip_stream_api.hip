@@ -166,6 +166,22 @@ namespace
     return limg_hip_success;
   }
 
+  // Version 2's one decode, the full image's and a window's: wp from window_params; the map of the window's blocks (not the image's) and the call's state words, then
+  // the two kernels
+  limg_hip_result blocked_window_decode(limg_hip_context *c, WindowDecodeParams &wp, hipStream_t s)
+  {
+    const size_t mapBytes = (size_t)wp.wbx * wp.wby * 4;
+    limg_hip_result r;
+    if ((r = c->bsMap.ensure(mapBytes)) != limg_hip_success) return r;
+    if ((r = c->bsState.ensure(64)) != limg_hip_success) return r;
+    HIP_TRY(hipMemsetAsync(c->bsMap.p, 0xFF, mapBytes, s)); // no block has a rectangle yet
+    HIP_TRY(hipMemsetAsync(c->bsState.p, 0, 64, s));
+    wp.map = (uint32_t *)c->bsMap.p; wp.state = (uint32_t *)c->bsState.p;
+    launch_blocked_stream_window_decode(wp, device_cus(c), s);
+    HIP_TRY(hipGetLastError());
+    return limg_hip_success;
+  }
+
   // info(&sizeX, &sizeY, &total): the version's header check.  deviceDecode(dStream, total, sizeX, sizeY, dOut): into context staging at stride `width`; only a stream
   // that passed reaches pOut
   template <class INFO, class DECODE>
@@ -528,24 +544,12 @@ extern "C"
     if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
     if (limg_hip_blocked_stream_bound(sizeX, sizeY) == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
     if (((uintptr_t)pStream & 15u) != 0 || ((uintptr_t)pOut & 15u) != 0) return limg_hip_error_InvalidParameter;
-    HIP_TRY(hipSetDevice(c->device));
+    // the whole image as a window: (0, 0, sizeX, sizeY) at stride sizeX
     hipStream_t s = (hipStream_t)stream;
-    BlockedDecodeParams dp;
-    memset(&dp, 0, sizeof(dp));
-    dp.sizeX = (uint32_t)sizeX; dp.sizeY = (uint32_t)sizeY;
-    dp.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); dp.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
-    dp.nBlocks = dp.blocksX * dp.blocksY;
-    limg_hip_result r;
-    if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
-    if ((r = c->bsMap.ensure((size_t)dp.nBlocks * 4)) != limg_hip_success) return r;
-    if ((r = c->bsState.ensure(64)) != limg_hip_success) return r;
-    HIP_TRY(hipMemsetAsync(c->bsMap.p, 0xFF, (size_t)dp.nBlocks * 4, s)); // no block has a rectangle yet
-    HIP_TRY(hipMemsetAsync(c->bsState.p, 0, 64, s));
-    dp.stream = pStream; dp.streamBytes = streamBytes; dp.out = pOut;
-    dp.map = (uint32_t *)c->bsMap.p; dp.status = (uint32_t *)c->streamStatus.p; dp.state = (uint32_t *)c->bsState.p;
-    launch_blocked_stream_decode(dp, device_cus(c), s);
-    HIP_TRY(hipGetLastError());
-    return limg_hip_success;
+    WindowDecodeParams wp;
+    const limg_hip_result r = window_params(c, pStream, streamBytes, sizeX, sizeY, limg_hip_blocked_stream_bound(sizeX, sizeY), 0, 0, sizeX, sizeY, pOut, sizeX, s, wp);
+    if (r != limg_hip_success) return r;
+    return blocked_window_decode(c, wp, s);
   }
 
   limg_hip_result limg_hip_blocked_stream_info(const uint8_t *pStream, size_t streamBytes, size_t *pSizeX, size_t *pSizeY, int *pHasAlpha, size_t *pTotalBytes, size_t *pRectangles)
@@ -603,17 +607,9 @@ extern "C"
     if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
     hipStream_t s = (hipStream_t)stream;
     WindowDecodeParams wp;
-    limg_hip_result r = window_params(c, pStream, streamBytes, sizeX, sizeY, limg_hip_blocked_stream_bound(sizeX, sizeY), x0, y0, width, height, pOut, outStridePixels, s, wp);
+    const limg_hip_result r = window_params(c, pStream, streamBytes, sizeX, sizeY, limg_hip_blocked_stream_bound(sizeX, sizeY), x0, y0, width, height, pOut, outStridePixels, s, wp);
     if (r != limg_hip_success) return r;
-    const size_t mapBytes = (size_t)wp.wbx * wp.wby * 4; // the window's blocks, not the image's
-    if ((r = c->bsMap.ensure(mapBytes)) != limg_hip_success) return r;
-    if ((r = c->bsState.ensure(64)) != limg_hip_success) return r;
-    HIP_TRY(hipMemsetAsync(c->bsMap.p, 0xFF, mapBytes, s)); // no block has a rectangle yet
-    HIP_TRY(hipMemsetAsync(c->bsState.p, 0, 64, s));
-    wp.map = (uint32_t *)c->bsMap.p; wp.state = (uint32_t *)c->bsState.p;
-    launch_blocked_stream_window_decode(wp, device_cus(c), s);
-    HIP_TRY(hipGetLastError());
-    return limg_hip_success;
+    return blocked_window_decode(c, wp, s);
   }
 
   limg_hip_result limg_hip_decode_stream_window(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,

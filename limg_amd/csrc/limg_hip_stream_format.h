@@ -1,7 +1,7 @@
 // limg_hip_stream_format.h -- the rules of the "LMG3" stream (include/limg_hip.h) that both versions share, on the device: field widths, the header (writer and check),
-// the one-workgroup scan over the packers' tile totals -- and, as named functions of the version 2 kernels (k_bstream_pack, k_bstream_decode), the dither + crush that
+// the one-workgroup scan over the packers' tile totals -- and, as named functions of the version 2 kernels (k_bstream_pack, k_bstream_window_decode), the dither + crush that
 // produces the stored values and the reference's decoder arithmetic (a16) in 32-bit terms, and version 2's rectangle geometry (pixels, field sizes).  Included by
-// limg_hip_stream.hip (version 1: 8x8 blocks), limg_hip_blocked_stream.hip (version 2: rectangles) and limg_hip_stream_window.hip (window decode of both).  k_blocked_store (limg_hip_blocked.hip) has the same dither and a16 written out in place (reason there); the
+// limg_hip_stream.hip (version 1: 8x8 blocks), limg_hip_blocked_stream.hip (version 2: its packer) and limg_hip_stream_window.hip (window decode of both; all of version 2's decode).  k_blocked_store (limg_hip_blocked.hip) has the same dither and a16 written out in place (reason there); the
 // packed-form decoders (decode_row_packed, phase_f_rows) are a different algorithm for a16's result and live with their kernels.
 #ifndef LIMG_HIP_STREAM_FORMAT_H
 #define LIMG_HIP_STREAM_FORMAT_H
@@ -92,7 +92,7 @@ namespace limg_hip
       *reinterpret_cast<limg_hip_stream_header *>(stream) = h;
     }
 
-    // The header a decoder is about to trust, against the call's own geometry and the size of the buffer it was handed.  P: DecodeParams / BlockedDecodeParams.
+    // The header a decoder is about to trust, against the call's own geometry and the size of the buffer it was handed.  P: DecodeParams / WindowDecodeParams / WindowGroup.
     template <class P>
     __device__ __forceinline__ bool stream_header_ok(const limg_hip_stream_header *h, uint32_t version, uint32_t entryBytes, uint32_t nEntries, const P &p)
     {

@@ -7,11 +7,16 @@
 //                              back to back, so a group's payload is still one run that is validated as a run (offsets in 64 bits, inside the payload, no longer than
 //                              8 x 24 words) and fetched by the whole wave; across window rows the runs are far apart.  The next group's run is requested before
 //                              the current one is decoded.  A group that fails raises the status word and stores nothing.
-//   k_bstream_window_map       version 2.  Scans the WHOLE rectangle table (64 B per rectangle), checks every rectangle as k_bstream_map does and claims the blocks of
-//                              rectangle n window block range in a window-sized map; overlaps wholly outside the window are therefore not seen.
+//   k_bstream_window_map       version 2.  Scans the WHOLE rectangle table (64 B per rectangle), 64 rectangles per wave step: checks every rectangle's geometry, shifts
+//                              and payload extent (rect_ok) and claims the blocks of rectangle n window block range in a window-sized block -> rectangle map
+//                              (atomicCAS on ~0): a lane claims a small piece itself, the wave claims a large one together; the claimed blocks are counted.
+//                              Overlaps wholly outside the window are therefore not seen.
 //   k_bstream_window_decode    refuses unless every block of the window was claimed exactly once and nothing was flagged; then units of 8 consecutive blocks of a
-//                              window block row, as k_bstream_decode.
-// Both decode with a16_constants / a16_pixel (limg_hip_stream_format.h): the reference's decoder in 32-bit terms, exact for every record.  Of the full version 1
+//                              window block row: the lane's 8 pixels are the bit run at ((y - 8 oy) * wpx + (x - 8 ox)) * b of each field of the block's rectangle;
+//                              a wave's stores are 8 row pieces of 256 contiguous bytes.  Nothing is read through an offset the map kernel has not checked against
+//                              the stream's size.
+// The full version 2 decode (limg_hip_blocked_decode_stream[_device]) is these two kernels on the window (0, 0, sizeX, sizeY) at stride sizeX: version 2 has no other decoder.
+// Both versions decode with a16_constants / a16_pixel (limg_hip_stream_format.h): the reference's decoder in 32-bit terms, exact for every record.  Of the full version 1
 // decoder's devices this file uses the next-run prefetch only: no counted wait (and so no store sink), no packed 16-bit decode, no per-block constants in LDS -- every
 // lane prepares the constants of its block itself.
 // Lanes whose image row or columns fall outside the window store nothing, or only the pixels inside it: nothing but the window's pixels is ever written.
@@ -250,7 +255,7 @@ namespace limg_hip
       atomicOr(p.status, bit);
     }
 
-    // A rectangle's geometry, shifts and payload extent, as k_bstream_map checks them.  e3: the entry's last 16 bytes; G: the image (WindowDecodeParams / WindowGroup).
+    // Whether a rectangle's geometry, shifts and payload extent are sound.  e3: the entry's last 16 bytes; G: the image (WindowDecodeParams / WindowGroup).
     template <class G>
     __device__ __forceinline__ bool rect_ok(const G &g, const uint4 e3, unsigned long long payloadWords)
     {
@@ -403,9 +408,11 @@ namespace limg_hip
         if (tid == 0 && blockIdx.x == 0) atomicOr(p.status, 2u);
         return;
       }
-      const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
-      const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h->channels;
-      const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h->payloadWords * 8ull;
+      // the header by scalar loads (no kernel of this call writes the stream): nRects, channels, tableEnd and total then stay in scalar registers through the loop.  As
+      // plain loads they came out as vector loads: 8 vector registers more, 71 in all, and 7 waves per SIMD where the launch counts on 8
+      const limg_hip_stream_header h = load_uniform(reinterpret_cast<const limg_hip_stream_header *>(p.stream));
+      const uint32_t nRects = h.reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h.channels;
+      const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h.payloadWords * 8ull;
       const uint32_t unitsX = (p.wbx + 7u) / 8u, nUnits = unitsX * p.wby;
       for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u) bwindow_unit(p, unit, unitsX, nRects, channels, tableEnd, total, lane);
     }

@@ -9,6 +9,7 @@ from lib_axis import lib, lib_product  # noqa: F401  (fixtures: "test" / "produc
 import limg_amd
 from oracle import blocked_stream as B
 from blocked_stream_ref import small_cases, stream_flags
+from window_cases import ERRORS, SENTINEL
 
 pytestmark = pytest.mark.gpu
 
@@ -231,6 +232,44 @@ def test_malformed_streams_on_the_device_entry(gpu, oracle):
         got = gpu.blocked_decode_stream_device(buf, good.size, w, h, out=out)
         gpu.check()
         assert np.array_equal(got.cpu().numpy().view(np.uint32), want), name
+
+
+def test_row_tail_of_half_a_block(gpu, oracle):
+    """sizeX % 4 == 0 but sizeX % 8 != 0 (no shape of small_cases has it): the last block column holds 4 pixels while every other column leaves as 16-byte stores.
+    Host and device entry against the oracle's pDecoded; the device entry writes nothing beyond the image's last pixel."""
+    import torch
+    for name, img, alpha in (("pn-12x9", oracle.photo_noise(12, 9, 5), True), ("pn-60x20", oracle.photo_noise(60, 20, 5), True),
+                             ("rg-20x8", oracle.random_gradient(20, 8, 5, True), False)):
+        h, w = img.shape
+        assert w % 4 == 0 and w % 8 != 0
+        want = oracle.blocked_encode3d(img, alpha)["pDecoded"]
+        st = gpu.blocked_encode_stream(img, alpha)
+        assert np.array_equal(gpu.blocked_decode_stream(st), want), name
+        out = torch.full((h * w + 16,), SENTINEL, dtype=torch.int32, device="cuda")
+        gpu.blocked_decode_stream_device(torch.from_numpy(st).cuda(), st.size, w, h, out=out)
+        torch.cuda.synchronize()
+        gpu.check()
+        got = out.cpu().numpy().view(np.uint32)
+        assert np.array_equal(got[:h * w].reshape(h, w), want), name
+        assert (got[h * w:] == SENTINEL).all(), name
+
+
+def test_argument_codes_of_the_device_entry(gpu, oracle):
+    """limg_hip_blocked_decode_stream_device's own checks, in its own order: NULL, then geometry and stream size, then the 16-byte alignment of BOTH pointers."""
+    import torch
+    st = gpu.blocked_encode_stream(oracle.photo_noise(64, 64, 3), True)
+    d = torch.from_numpy(st).cuda()
+    out = torch.empty((64, 64), dtype=torch.int32, device="cuda")
+    fn, s, ps, po = gpu.lib.limg_hip_blocked_decode_stream_device, gpu._stream(), d.data_ptr(), out.data_ptr()
+    assert ps % 16 == 0 and po % 16 == 0
+    for args, code in (((None, ps, st.size, po, 64, 64), "ArgumentNull"), ((gpu.ctx, None, st.size, po, 64, 64), "ArgumentNull"),
+                       ((gpu.ctx, ps, st.size, None, 64, 64), "ArgumentNull"), ((gpu.ctx, ps, st.size, po, 0, 64), "InvalidParameter"),
+                       ((gpu.ctx, ps, 32, po, 64, 64), "InvalidParameter"), ((gpu.ctx, ps, st.size, po + 4, 64, 64), "InvalidParameter"),
+                       ((gpu.ctx, ps + 8, st.size, po, 64, 64), "InvalidParameter")):
+        assert fn(*args, s) == ERRORS[code], (args[1:], code)
+    assert fn(gpu.ctx, ps, st.size, po, 64, 64, s) == 0
+    torch.cuda.synchronize()
+    gpu.check()
 
 
 L.product_twins(globals())

@@ -4,7 +4,7 @@
   python tools/window_decode_bench.py [--reps 7] [--warmup 2]
 
 For 8192^2 photo-noise and 4096^2 gradient, in version 1 and version 2 of the stream, it prints one JSON line with four variants:
-  (a) full       the existing full decoder (limg_hip_decode_stream_device / limg_hip_blocked_decode_stream_device)
+  (a) full       the full decode entry (limg_hip_decode_stream_device / limg_hip_blocked_decode_stream_device; version 2's runs the kernels of (b))
   (b) whole      the window entry with the window = the whole image
   (c) aligned    a 1024^2 block-aligned window at (1024, 2048)
   (d) unaligned  a 1000 x 1000 window at (123, 457) into an odd stride, pOut 4 bytes off a 16-byte boundary
