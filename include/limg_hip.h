@@ -307,6 +307,37 @@ limg_hip_result limg_hip_decode_stream(limg_hip_context *pCtx, const uint8_t *pS
 /* Host-only: validates a header (first 64 bytes suffice) and reports the image shape. */
 limg_hip_result limg_hip_stream_info(const uint8_t *pStream, size_t streamBytes, size_t *pSizeX, size_t *pSizeY, int *pHasAlpha, size_t *pTotalBytes);
 
+/* ---- batched stream encode: a list of images to version 1 streams in one call ---------------------------------------------------
+ * limg_hip_encode3d_batch_device puts a list of same-shape images through one float-stage grid and one persistent launch, so that ramp-up and drain are paid once per
+ * list; these entries do the same for the compact stream, which is what a caller who encodes a set of images keeps.
+ * Result: stream i is byte for byte what limg_hip_encode_stream_device writes for image i with the same arguments and options; every image starts its own dither chain
+ * (or chains: poolThreads means what it means there).  Nothing beyond `totalBytes` of a stream has a specified value.  All images have the shape sizeX x sizeY.
+ * Errors, in this order and before anything touches the device: NULL context, array or array element: limg_hip_error_ArgumentNull;
+ * limg_hip_stream_bound(sizeX, sizeY) == 0: limg_hip_error_InvalidParameter; capacityEach < that bound: limg_hip_error_OutOfBounds; (device form) any ppStreams[i] not
+ * 16-byte aligned: limg_hip_error_InvalidParameter, whichever i it is.  Then count == 0: limg_hip_success with nothing done, as limg_hip_encode3d_batch_device.  A
+ * refused call writes nothing.  Output buffers that overlap are not checked.
+ * pBytes (device form: host array of `count` entries, or NULL): when given, the call waits for the streams and fills all `count` sizes from ONE download of the headers'
+ * totalBytes, gathered on the device -- not one blocking copy per image.
+ * Options: forced_shift, dither_pcg, float_mode, collect_stats (limg_hip_last_stats: all images of the list together) and batch_sub_images are honoured exactly as by
+ * limg_hip_encode3d_batch_device.
+ * Cost: a list that fits one launch pair is that batch's launches (image table, float stage, persistent kernel -- or its pipeline of sub-batches) plus ONE scan launch
+ * (one workgroup per image: the strips' first payload words and the image's header) and ONE pack launch (min(strips of the list, 16 x CUs) persistent one-wave
+ * workgroups striding over the strips of all images), whatever `count` is; the streams' pointers travel to the device as kernel arguments of a small launch.
+ * One encode per image instead -- the same bytes -- for images with partial edge blocks, under force_split_kernels or legacy_float_stage, and for count == 1.
+ * Longer lists go in chunks by the rule of limg_hip_encode3d_batch_device (1 GiB of block records, 32-bit strip ids); a chunk of one image takes the single call.
+ * Context memory: per image OF A CHUNK 3 bytes per pixel of factor planes (limg_hip_context::streamFac, where the single call holds one image's), 4 bytes per work strip
+ * and the per-block scratch of the plane batch; 32 bytes per image of the list (the table) and, with pBytes, 8 more.  limg_hip_context_device_bytes reports all of it.
+ * Ordering: calls on one context and stream execute in order and may be issued back to back; ppIn / ppStreams may be freed when the call returns. */
+/* DEVICE pointers, asynchronous on `stream`.  ppIn / ppStreams are HOST arrays of `count` device pointers and may be freed when the call returns. */
+limg_hip_result limg_hip_encode_stream_batch_device(limg_hip_context *pCtx, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                    uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes /* host, count entries, or NULL */,
+                                                    uint32_t errorFactor, int poolThreads, int fastBitCrushing, void *stream);
+/* HOST pointers, blocking, under the context's mutex.  pBytes required.  Uploads the images, runs the device form into context staging (per image 4 bytes per pixel and
+ * the stream bound), checks the device status and downloads totalBytes of each stream -- not capacityEach. */
+limg_hip_result limg_hip_encode_stream_batch(limg_hip_context *pCtx, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                             uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes,
+                                             uint32_t errorFactor, int poolThreads, int fastBitCrushing);
+
 /* ---- compact stream, version 2: the merged-block encoder's rectangles --------------------------------------------------------
  * What limg_hip_blocked_encode3d computes -- the rectangles of merged 8x8 blocks, each with ONE record, ONE shift triple and its crushed factor values -- in the same
  * "LMG3" container, so that decode(blocked_encode_stream(image)) equals the pDecoded plane of `limg_blocked_encode3d_test` bit for bit.  Version 1 streams and their

@@ -178,6 +178,18 @@ inline limg_result limg_encode(const uint32_t *pIn, const size_t sizeX, const si
                                              fastBitCrushing ? 1 : 0);
 }
 
+// `count` images of one shape in one call (limg_hip.h "batched stream encode"): pOutSizes[i] bytes at ppOut[i] are what limg_encode writes for ppIn[i]; every ppOut[i]
+// has room for outCapacityEach >= limg_encode_bound(sizeX, sizeY) bytes
+inline limg_result limg_encode_batch(const uint32_t *const *ppIn, const size_t count, const size_t sizeX, const size_t sizeY, const bool hasAlpha, uint8_t *const *ppOut,
+                                     const size_t outCapacityEach, size_t *pOutSizes, const uint32_t errorFactor = 100, limg_thread_pool *pThreadPool = nullptr,
+                                     const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  return (limg_result)limg_hip_encode_stream_batch(c, count, ppIn, sizeX, sizeY, hasAlpha ? 1 : 0, ppOut, outCapacityEach, pOutSizes, errorFactor,
+                                                   limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0);
+}
+
 // either version of the stream: version 1 (limg_encode) or version 2 (limg_blocked_encode)
 inline limg_result limg_decode_info(const uint8_t *pIn, const size_t size, size_t *pSizeX, size_t *pSizeY, bool *pHasAlpha)
 {

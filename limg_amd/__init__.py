@@ -27,7 +27,7 @@ ABI_SYMBOLS = (
     "limg_hip_synth_photo_noise_device", "limg_hip_context_device_bytes", "limg_hip_version", "limg_hip_profile_begin", "limg_hip_profile_end",
     "limg_hip_host_noise_table", "limg_hip_noise_table_device", "limg_hip_host_chain_call", "limg_hip_host_chain_checkpoints", "limg_hip_host_dense_checkpoints", "limg_hip_host_partition", "limg_hip_check_device_status",
     "limg_hip_stream_bound", "limg_hip_encode_stream_device", "limg_hip_decode_stream_device", "limg_hip_encode_stream", "limg_hip_decode_stream",
-    "limg_hip_stream_info",
+    "limg_hip_stream_info", "limg_hip_encode_stream_batch_device", "limg_hip_encode_stream_batch",
     "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
     "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
     "limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device", "limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window",
@@ -195,6 +195,11 @@ def load_library(path=None):
     L.limg_hip_decode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     L.limg_hip_stream_info.restype = C.c_int
     L.limg_hip_stream_info.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    L.limg_hip_encode_stream_batch_device.restype = C.c_int  # ctx, count, ins (host array), sizeX, sizeY, hasAlpha, streams (host array), capacityEach, sizes, ef, pool, fast, hipStream
+    L.limg_hip_encode_stream_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_int,
+                                                      C.c_int, C.c_void_p]
+    L.limg_hip_encode_stream_batch.restype = C.c_int
+    L.limg_hip_encode_stream_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_int, C.c_int]
     L.limg_hip_blocked_stream_bound.restype = C.c_size_t
     L.limg_hip_blocked_stream_bound.argtypes = [C.c_size_t, C.c_size_t]
     L.limg_hip_blocked_encode_stream_device.restype = C.c_int
@@ -578,6 +583,41 @@ class LimgHip:
 
     def decode_stream_device(self, stream, nbytes, w, h, out=None):
         return self._decode_stream_device("limg_hip_decode_stream_device", stream, nbytes, w, h, out)
+
+    # ---- batched stream encode: a list of same-shape images, stream i = encode_stream of image i (contract: include/limg_hip.h) ----
+    def encode_stream_batch(self, imgs, has_alpha, error_factor=100, pool_threads=0, fast=True):
+        """host uint32 images of one shape -> list of stream bytes (numpy uint8), one batched call"""
+        imgs = [np.ascontiguousarray(i, dtype=np.uint32) for i in imgs]
+        n = len(imgs)
+        if n == 0:
+            self._stream_call("limg_hip_encode_stream_batch", 0, (C.c_void_p * 1)(), 8, 8, int(has_alpha), (C.c_void_p * 1)(), self.stream_bound(8, 8), (C.c_size_t * 1)(),
+                              error_factor, pool_threads, int(fast))
+            return []
+        h, w = imgs[0].shape
+        assert all(i.shape == (h, w) for i in imgs)
+        cap = self.stream_bound(w, h)
+        outs = [np.zeros(cap, dtype=np.uint8) for _ in range(n)]
+        sizes = (C.c_size_t * n)()
+        self._stream_call("limg_hip_encode_stream_batch", n, (C.c_void_p * n)(*[i.ctypes.data for i in imgs]), w, h, int(has_alpha),
+                          (C.c_void_p * n)(*[o.ctypes.data for o in outs]), cap, sizes, error_factor, pool_threads, int(fast))
+        return [o[:sizes[k]].copy() for k, o in enumerate(outs)]
+
+    def encode_stream_batch_device(self, imgs, has_alpha, outs=None, want_sizes=True, error_factor=100, pool_threads=0, fast=True):
+        """imgs: list of torch int32 CUDA tensors (h, w) of one shape -> (list of torch uint8 CUDA stream buffers of worst-case size, list of bytes used or None).
+        outs: the buffers to use (each at least stream_bound(w, h) bytes, the smallest is the capacity handed on).  Asynchronous on torch's current stream unless
+        want_sizes."""
+        import torch
+        n = len(imgs)
+        h, w = imgs[0].shape
+        assert all(tuple(i.shape) == (h, w) for i in imgs)
+        if outs is None:
+            outs = [torch.empty(self.stream_bound(w, h), dtype=torch.uint8, device=imgs[0].device) for _ in range(n)]
+        assert len(outs) == n
+        sizes = (C.c_size_t * n)()
+        self._stream_call("limg_hip_encode_stream_batch_device", n, (C.c_void_p * n)(*[i.data_ptr() for i in imgs]), w, h, int(has_alpha),
+                          (C.c_void_p * n)(*[o.data_ptr() for o in outs]), min(o.numel() for o in outs), sizes if want_sizes else None, error_factor, pool_threads, int(fast),
+                          self._stream())
+        return outs, ([int(v) for v in sizes] if want_sizes else None)
 
     def blocked_stream_bound(self, w, h):
         return self.lib.limg_hip_blocked_stream_bound(w, h)

@@ -141,6 +141,7 @@ struct limg_hip_context
   uint32_t chainEf = 0;
   DevBuf commWords; // [0] this rank's value, [1] its chain base, [8 ...] the all-gathered values
   DevBuf streamFac, streamTiles, streamUnits, streamStatus, streamBuf; // stream packer: 3 factor planes, per-tile payload words; decode status word; host-entry staging
+  DevBuf streamTable, streamSizes; // batched stream encode: one StreamImage per image of the list; the finished streams' sizes side by side (one download)
   // version 2 stream of the merged-block encoder (limg_hip_stream_api.hip): per rectangle its first 64-pixel run, per tile of rectangles its totals; the
   // decoder's block -> rectangle map and its per-call words
   DevBuf bsUnits, bsTiles, bsMap, bsState;
@@ -169,7 +170,7 @@ struct limg_hip_context
   {
     for (auto *b : { &c.records, &c.shifts, &c.stripCalls, &c.stripBase, &c.invN, &c.noise, &c.noiseDyn, &c.noiseStates, &c.noiseCk, &c.park, &c.batchTable, &c.stats,
                      &c.lookback, &c.accTable, &c.devStatus, &c.in, &c.planes, &c.hostWords, &c.cmp, &c.bFlags, &c.bBound, &c.bOrder, &c.bMatch, &c.bRegions, &c.bOut,
-                     &c.bPx, &c.bFac, &c.bNoise, &c.bNoiseBase, &c.bCalls, &c.commWords, &c.streamFac, &c.streamTiles, &c.streamUnits, &c.streamStatus, &c.streamBuf, &c.bsUnits, &c.bsTiles, &c.bsMap, &c.bsState,
+                     &c.bPx, &c.bFac, &c.bNoise, &c.bNoiseBase, &c.bCalls, &c.commWords, &c.streamFac, &c.streamTiles, &c.streamUnits, &c.streamStatus, &c.streamBuf, &c.streamTable, &c.streamSizes, &c.bsUnits, &c.bsTiles, &c.bsMap, &c.bsState,
                      &c.windowSlots[0].dev, &c.windowSlots[1].dev, &c.windowSlots[2].dev, &c.windowSlots[3].dev })
       f(*b);
   }
@@ -229,7 +230,8 @@ namespace limg_hip
     unsigned long long *dChainCalls = nullptr;
     const unsigned long long *dChainBase = nullptr;
     size_t chainBlocksBefore = 0;
-    // batch (host array of batchCount entries, batchCount > 1): the images of a batched encode -- same shape, whole 8x8 blocks, all 11 planes -- in one launch
+    // batch (host array of batchCount entries, batchCount > 1): the images of a batched encode -- same shape, whole 8x8 blocks, all 11 planes (or, from the batched
+    // stream encode, the three factor planes only: streamRaw, stripWords and both compact outputs set) -- in one launch
     // pair (or, limg_hip_options.batch_sub_images, a pipeline of launch pairs); dIn / dInfo are then those of image 0.  The caller has checked all of that.
     const ImageIO *batch = nullptr;
     size_t batchCount = 1;

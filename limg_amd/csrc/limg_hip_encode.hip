@@ -296,6 +296,7 @@ namespace
       q.batch = p.batch + i0; q.batchCount = (uint32_t)n;
       q.io = e.x.batch[i0]; // (what the kernels read when a sub-batch is a single image)
       q.records = p.records + i0 * imgBlocks; q.shifts = p.shifts + i0 * imgBlocks; q.invN = p.invN + i0 * imgBlocks * 4;
+      if (p.stripWords) q.stripWords = p.stripWords + i0 * imgStrips; // (a sub-batch numbers its strips from 0: its payload words land at the list's offsets, where the packer reads one list)
       uint8_t *lb = (uint8_t *)c->lookback.p + k * 16 + i0 * imgStrips * 8; // sub-batch k: its ticket, then the descriptors of its strips
       q.ticket = (uint32_t *)lb; q.desc = (unsigned long long *)(lb + 16);
       q.fitPrio = k == 0 ? 0 : fitPrio;
@@ -435,7 +436,10 @@ namespace limg_hip
     limg_hip_result r;
     if ((r = encode_params(e, dIn, compact, errorFactor, poolThreads, fast)) != limg_hip_success) return r;
     if (chainPhase == 0 && !x.inner && !c->statsAccumulate) c->statsState = 0;
-    if (batchCount > 1 && (!e.fused || !e.p.prefit || !fullPlanes)) return limg_hip_error_InvalidParameter; // (limg_hip_encode3d_batch_device sends such lists through one encode per image instead)
+    // a list in compact mode only as the batched stream encode hands it over: raw-escaped factor bytes, the strips' payload words, records and shift words all in
+    // raster arrays that run image after image (what its scan and packer read)
+    const bool compactList = !fullPlanes && x.streamRaw && x.stripWords && compact && compact->pRecords && compact->pShifts;
+    if (batchCount > 1 && (!e.fused || !e.p.prefit || (!fullPlanes && !compactList))) return limg_hip_error_InvalidParameter; // (limg_hip_encode3d_batch_device sends such lists through one encode per image instead)
     if (e.fused && (r = fused_scratch(e, compact)) != limg_hip_success) return r;
 
     const size_t subImages = sub_batch_images(e);

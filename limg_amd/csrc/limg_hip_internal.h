@@ -101,6 +101,24 @@ namespace limg_hip
     uint32_t stripsX, nStrips, nWaves;
   };
 
+  // batched stream pack (limg_hip_stream.hip): a chunk of `nImages` images of one shape, all of whole blocks, behind ONE compact-mode batched encode.  Records, shift
+  // words and the strips' payload words run image after image (image i owns strips [i * imageStrips, (i + 1) * imageStrips)); what differs per image -- its three
+  // factor planes (slices of the context's streamFac) and its stream -- is an entry of a device table, read with scalar loads where a strip uses it.
+  struct StreamImage
+  {
+    const uint8_t *fac[3];
+    uint8_t *stream;
+  };
+  struct StreamBatchParams
+  {
+    uint32_t sizeX, sizeY, blocksX, blocksY, nBlocks /* of one image */, channels, errorFactor, flags;
+    uint32_t stripsX, imageStrips, nImages, nStrips /* of all images */, nWaves;
+    const StreamImage *images;
+    const limg_hip_block_record *records;
+    const uint32_t *shifts;
+    uint32_t *stripWords;
+  };
+
   struct DecodeParams
   {
     uint32_t sizeX, sizeY, blocksX, blocksY, nBlocks;
@@ -248,6 +266,9 @@ namespace limg_hip
   void launch_blocked_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s);
 
   void launch_stream_pack(const StreamParams &p, hipStream_t s);
+  void launch_stream_pack_batch(const StreamBatchParams &b, hipStream_t s);                                                  // one scan launch + one pack launch, whatever nImages is
+  void launch_set_stream_table(StreamImage *dTable, const StreamImage *hTable, size_t count, hipStream_t s);                // as launch_set_batch_table: through kernel arguments
+  void launch_stream_gather_bytes(const StreamImage *dTable, size_t count, unsigned long long *dBytes, hipStream_t s);      // dBytes[i] = totalBytes of image i's header
   void launch_stream_decode(const DecodeParams &p, int cus, hipStream_t s);
 
   void launch_synth_random_gradient(uint32_t *out, uint32_t w, uint32_t h, uint64_t seed, int opaque, uint32_t y0, hipStream_t s);

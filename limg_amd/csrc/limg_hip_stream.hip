@@ -57,7 +57,8 @@ namespace limg_hip
     }
 
     // (between them: k_stream_tile_scan<1>, limg_hip_stream_format.h -- exclusive scan of the tile totals in place + the header)
-    __host__ __device__ inline StreamHeaderInfo header_info(const StreamParams &p)
+    template <class P> // StreamParams / StreamBatchParams
+    __host__ __device__ inline StreamHeaderInfo header_info(const P &p)
     {
       return { LIMG_HIP_STREAM_VERSION, p.sizeX, p.sizeY, p.channels, p.errorFactor, p.blocksX, p.blocksY, p.flags, p.nBlocks, (uint32_t)kEntry, 0u };
     }
@@ -179,15 +180,16 @@ namespace limg_hip
     // coalesced 16 bytes per lane (a thread that owned 32 CONSECUTIVE strips asked its CU's address unit for 64 lines per instruction: 11 us; the first form, one
     // slab per loop iteration with the loads inside the loop: 32 us) -- all 8 requested before anything is added; the 8 slabs' wave scans run side by side, the
     // 8 x 16 wave totals are turned into their exclusive prefix by one wave, two barriers per round.  8192^2 is one round.
-    __global__ __launch_bounds__(1024) void k_stream_scan_strips(const StreamParams p)
+    // (the body: the exclusive prefix over `nStrips` words in place, by the whole workgroup; returns their sum.  k_stream_scan_strips_batch runs it once per image.)
+    __device__ __forceinline__ unsigned long long scan_strips(uint32_t *const stripWords, const uint32_t nStrips)
     {
       __shared__ unsigned long long sPart[8 * 16]; // [slab][wave] totals, then their exclusive prefix
       __shared__ unsigned long long sCarry, sRound;
       const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
       if (tid == 0) sCarry = 0;
       __syncthreads();
-      const bool vec = (p.nStrips & 3u) == 0; // 16-byte accesses need whole groups of 4 (the buffer itself is 256-byte aligned)
-      for (uint32_t base = 0; base < p.nStrips; base += 32768)
+      const bool vec = (nStrips & 3u) == 0; // 16-byte accesses need whole groups of 4 (the buffer itself is 256-byte aligned)
+      for (uint32_t base = 0; base < nStrips; base += 32768)
       {
         uint32_t v[8][4];
 #pragma unroll
@@ -197,13 +199,13 @@ namespace limg_hip
           if (vec)
           {
             uint4 t = make_uint4(0, 0, 0, 0);
-            if (i0 < p.nStrips) t = *reinterpret_cast<const uint4 *>(p.stripWords + i0);
+            if (i0 < nStrips) t = *reinterpret_cast<const uint4 *>(stripWords + i0);
             v[q][0] = t.x; v[q][1] = t.y; v[q][2] = t.z; v[q][3] = t.w;
           }
           else
           {
 #pragma unroll
-            for (int k = 0; k < 4; k++) v[q][k] = i0 + k < p.nStrips ? p.stripWords[i0 + k] : 0u;
+            for (int k = 0; k < 4; k++) v[q][k] = i0 + k < nStrips ? stripWords[i0 + k] : 0u;
           }
         }
         // (a slab's 4096 strips hold at most 4096 x 32 x 24 words: 32 bits, and the wave scans are DPP adds -- eight 64-bit shuffle scans per wave went through the
@@ -246,21 +248,36 @@ namespace limg_hip
           const uint32_t e1 = e0 + v[q][0], e2 = e1 + v[q][1], e3 = e2 + v[q][2];
           if (vec)
           {
-            if (i0 < p.nStrips) *reinterpret_cast<uint4 *>(p.stripWords + i0) = make_uint4(e0, e1, e2, e3);
+            if (i0 < nStrips) *reinterpret_cast<uint4 *>(stripWords + i0) = make_uint4(e0, e1, e2, e3);
           }
           else
           {
             const uint32_t e[4] = { e0, e1, e2, e3 };
 #pragma unroll
             for (int k = 0; k < 4; k++)
-              if (i0 + k < p.nStrips) p.stripWords[i0 + k] = e[k];
+              if (i0 + k < nStrips) stripWords[i0 + k] = e[k];
           }
         }
         __syncthreads();
         if (tid == 0) sCarry = carry + sRound;
         __syncthreads();
       }
-      if (tid == 0) write_stream_header(p.stream, header_info(p), sCarry);
+      return sCarry;
+    }
+
+    __global__ __launch_bounds__(1024) void k_stream_scan_strips(const StreamParams p)
+    {
+      const unsigned long long total = scan_strips(p.stripWords, p.nStrips);
+      if (threadIdx.x == 0) write_stream_header(p.stream, header_info(p), total);
+    }
+
+    // A chunk of a batched stream encode: workgroup i is k_stream_scan_strips for image i -- the prefix restarts at 0 in its slice of the list, its header goes to its
+    // own stream.  A slice starts at i * imageStrips words: 16-byte aligned, as the 16-byte path (imageStrips % 4 == 0) needs, exactly where that path is taken.
+    __global__ __launch_bounds__(1024) void k_stream_scan_strips_batch(const StreamBatchParams b)
+    {
+      const uint32_t img = blockIdx.x;
+      const unsigned long long total = scan_strips(b.stripWords + (size_t)img * b.imageStrips, b.imageStrips);
+      if (threadIdx.x == 0) write_stream_header(b.images[img].stream, header_info(b), total);
     }
 
     // 8 bytes (lo = pixels 0..3, hi = 4..7), each holding its value in the TOP b bits (sh = 8 - b; raw-escaped fields: b = 8) -> the 8 values in 8 b consecutive bits
@@ -278,7 +295,8 @@ namespace limg_hip
     }
 
     struct StripSmall { uint4 r0, r1, r2; uint32_t sw, base; };
-    __device__ __forceinline__ void load_strip_small(const StreamParams &p, uint32_t strip, int j, StripSmall &o)
+    template <class P> // StreamParams, or the StripView of a batch's image
+    __device__ __forceinline__ void load_strip_small(const P &p, uint32_t strip, int j, StripSmall &o)
     {
       o.r0 = o.r1 = o.r2 = make_uint4(0, 0, 0, 0); o.sw = 0; o.base = 0;
       if (strip >= p.nStrips) return;
@@ -295,7 +313,8 @@ namespace limg_hip
 
     struct StripRows { uint2 raw[3][4]; uint32_t bits; };
     // field sizes of the lane's block + the request for its four rows of every field the block has
-    __device__ __forceinline__ void issue_strip_rows(const StreamParams &p, uint32_t strip, int j, int h, const StripSmall &sm, StripRows &o)
+    template <class P>
+    __device__ __forceinline__ void issue_strip_rows(const P &p, uint32_t strip, int j, int h, const StripSmall &sm, StripRows &o)
     {
       o.bits = 0;
 #pragma unroll
@@ -335,76 +354,100 @@ namespace limg_hip
         issue_strip_rows(p, strip + p.nWaves, j, h, nxt, rowsNext); // (waits for `nxt`, requested one iteration ago)
         StripSmall nxt2;
         load_strip_small(p, strip + 2u * p.nWaves, j, nxt2);
-        const uint32_t by = strip / p.stripsX, sx = strip - by * p.stripsX;
-        const uint32_t inStrip = min(32u, p.blocksX - sx * 32u);
-        const uint32_t bits = rows.bits, words = words_of(bits);
-        // exclusive prefix of the words over the strip's blocks (both halves compute it)
-        uint32_t incl = words; // (wave_scan_inclusive over 32 lanes, written out: through a width parameter there this kernel's measured schedule changes)
-#pragma unroll
-        for (int off = 1; off < 32; off <<= 1)
-        {
-          const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 32);
-          if (j >= off) incl += up;
-        }
-        const uint32_t total = (uint32_t)__shfl((int)incl, 31, 32);
-        const uint32_t excl = incl - words;
-        if (h == 0)
-        {
-          uint32_t *e = sEnt + j * 14;
-          *reinterpret_cast<uint2 *>(e + 0) = make_uint2(cur.r0.x, cur.r0.y); *reinterpret_cast<uint2 *>(e + 2) = make_uint2(cur.r0.z, cur.r0.w);
-          *reinterpret_cast<uint2 *>(e + 4) = make_uint2(cur.r1.x, cur.r1.y); *reinterpret_cast<uint2 *>(e + 6) = make_uint2(cur.r1.z, cur.r1.w);
-          *reinterpret_cast<uint2 *>(e + 8) = make_uint2(cur.r2.x, cur.r2.y); *reinterpret_cast<uint2 *>(e + 10) = make_uint2(cur.r2.z, cur.r2.w);
-          *reinterpret_cast<uint2 *>(e + 12) = make_uint2(cur.sw | (bits & 0xFF000000u), cur.base + excl);
-        }
-        {
-          uint32_t *field = sRun + 2u * excl; // dwords
-#pragma unroll
-          for (int k = 0; k < 3; k++)
-          {
-            const uint32_t b = (bits >> (8 * k)) & 0xFFu;
-            if (b == 0u) continue;
-            const uint32_t sh = 8u - b, m1 = (1u << b) - 1u, m4 = m1 * 0x01010101u, mPair = (m1 * 0x00010001u) << b;
-            uint32_t *dst = field + (uint32_t)h * b; // rows 4 h .. 4 h + 3 are bytes [4 h b, 4 h b + 4 b) of the field: b dwords
-            const uint32_t len0 = b < 4u ? b : 4u, len1 = b - len0; // a row goes in as its low (up to) 4 bytes, then the rest: never more than 3 + 4 bytes in acc
-            unsigned long long acc = 0;
-            uint32_t fill = 0; // bytes in acc (< 4 between appends)
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-            {
-              const unsigned long long v = squeeze_row(rows.raw[k][r].x, rows.raw[k][r].y, sh, b, m4, mPair);
-              acc |= (unsigned long long)(uint32_t)v << (8u * fill);
-              fill += len0;
-              if (fill >= 4u) { *dst++ = (uint32_t)acc; acc >>= 32; fill -= 4u; }
-              acc |= (unsigned long long)(uint32_t)(v >> 32) << (8u * fill);
-              fill += len1;
-              if (fill >= 4u) { *dst++ = (uint32_t)acc; acc >>= 32; fill -= 4u; }
-            }
-            field += 2u * b;
-          }
-        }
-        wave_lds_fence();
-        {
-          uint2 *edst = reinterpret_cast<uint2 *>(p.stream + sizeof(limg_hip_stream_header) + ((size_t)by * p.blocksX + sx * 32u) * kEntry);
-          const uint2 *esrc = reinterpret_cast<const uint2 *>(sEnt);
-          for (uint32_t i = lane; i < inStrip * (kEntry / 8); i += 64) edst[i] = esrc[i];
-          // the run in 16-byte stores: the payload area is 8-byte aligned, so a run that starts on an odd word sends that word ahead (the LDS side is then read at
-          // 8-byte alignment, which ds_read_b128 does not allow: two ds_read_b64)
-          uint2 *pdst = payload + (size_t)cur.base;
-          const uint2 *psrc = reinterpret_cast<const uint2 *>(sRun);
-          const uint32_t odd = (uint32_t)((reinterpret_cast<uintptr_t>(pdst) >> 3) & 1u) & (total ? 1u : 0u);
-          if (odd && lane == 0) pdst[0] = psrc[0];
-          const uint32_t pairs = (total - odd) >> 1;
-          uint4 *p4 = reinterpret_cast<uint4 *>(pdst + odd);
-          for (uint32_t i = lane; i < pairs; i += 64)
-          {
-            const uint2 a = psrc[odd + 2u * i], b2 = psrc[odd + 2u * i + 1u];
-            p4[i] = make_uint4(a.x, a.y, b2.x, b2.y);
-          }
-          if (((total - odd) & 1u) && lane == 0) pdst[total - 1u] = psrc[total - 1u];
-        }
-        wave_lds_fence(); // the run is read: the next strip may overwrite it
+#include "limg_hip_stream_pack_step.inc"
         cur = nxt; nxt = nxt2; rows = rowsNext;
       }
+    }
+
+    // ---- pack, strip form, a list of images (batched stream encode) ---------------------------------------------------------------------
+    // k_stream_pack_strips over the strips of ALL images of a chunk: the same persistent one-wave workgroups, the same two-deep pipeline, the same helpers -- one
+    // launch whose waves never drain between images.  What an image owns is seen through a StripView: its slices of the list's records, shift words and strip
+    // offsets, its factor planes and its stream (the latter two from the device table, scalar loads).  Strips i, i + 1 and i + 2 of one wave are nWaves apart in the
+    // list and may lie in three different images (always, where an image is one strip), so the pipeline carries the image of each strip in flight: it is found
+    // once per strip, where the strip enters the pipeline, from values that are uniform across the wave.
+    struct StripView
+    {
+      uint32_t nStrips, stripsX, blocksX, sizeX, channels; // nStrips: of the image; 0 = no such strip (past the end of the list: the helpers then request nothing)
+      const uint32_t *stripWords;
+      const limg_hip_block_record *records;
+      const uint32_t *shifts;
+      const uint8_t *fac[3];
+      uint8_t *stream;
+    };
+
+    // the view of the image that holds strip g of the list, and g's number inside it
+    __device__ __forceinline__ StripView strip_view(const StreamBatchParams &b, const uint32_t g, const uint32_t img, uint32_t &local)
+    {
+      StripView v;
+      v.stripsX = b.stripsX; v.blocksX = b.blocksX; v.sizeX = b.sizeX; v.channels = b.channels;
+      if (g >= b.nStrips)
+      {
+        v.nStrips = 0; v.stripWords = nullptr; v.records = nullptr; v.shifts = nullptr; v.fac[0] = v.fac[1] = v.fac[2] = nullptr; v.stream = nullptr;
+        local = 0;
+        return v;
+      }
+      // (the table was written by a launch that precedes this one on the stream and does not change while the kernel runs: constant address space, scalar loads)
+      typedef const __attribute__((address_space(4))) StreamImage KernImage;
+      KernImage *const im = (KernImage *)b.images + img;
+      v.nStrips = b.imageStrips;
+      v.stripWords = b.stripWords + (size_t)img * b.imageStrips;
+      v.records = b.records + (size_t)img * b.nBlocks;
+      v.shifts = b.shifts + (size_t)img * b.nBlocks;
+      v.fac[0] = im->fac[0]; v.fac[1] = im->fac[1]; v.fac[2] = im->fac[2];
+      v.stream = im->stream;
+      local = g - img * b.imageStrips;
+      return v;
+    }
+    __device__ __forceinline__ uint32_t strip_image(const StreamBatchParams &b, const uint32_t g) { return g < b.nStrips ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(g / b.imageStrips)) : 0u; }
+
+    __global__ __launch_bounds__(64) void k_stream_pack_strips_batch(const StreamBatchParams b)
+    {
+      __shared__ __align__(16) uint32_t sRun[32 * 48];   // the strip's payload, worst case (24 words per block)
+      __shared__ __align__(16) uint32_t sEnt[32 * 14];   // its entries
+      const int lane = lane_id(), j = lane & 31, h = lane >> 5;
+      StripSmall cur, nxt;
+      StripRows rows, rowsNext;
+      uint32_t imgCur = strip_image(b, blockIdx.x), imgNxt = strip_image(b, blockIdx.x + b.nWaves), local;
+      {
+        uint32_t localNext;
+        const StripView v = strip_view(b, blockIdx.x, imgCur, local), vn = strip_view(b, blockIdx.x + b.nWaves, imgNxt, localNext);
+        load_strip_small(v, local, j, cur);
+        load_strip_small(vn, localNext, j, nxt);
+        issue_strip_rows(v, local, j, h, cur, rows);
+      }
+      for (uint32_t g = blockIdx.x; g < b.nStrips; g += b.nWaves)
+      {
+        const StripView vn = strip_view(b, g + b.nWaves, imgNxt, local);
+        issue_strip_rows(vn, local, j, h, nxt, rowsNext); // (waits for `nxt`, requested one iteration ago)
+        const uint32_t imgNxt2 = strip_image(b, g + 2u * b.nWaves);
+        const StripView vn2 = strip_view(b, g + 2u * b.nWaves, imgNxt2, local);
+        StripSmall nxt2;
+        load_strip_small(vn2, local, j, nxt2);
+        {
+          const StripView p = strip_view(b, g, imgCur, local);
+          const uint32_t strip = local;
+          uint2 *const payload = reinterpret_cast<uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)b.nBlocks * kEntry);
+#include "limg_hip_stream_pack_step.inc"
+        }
+        cur = nxt; nxt = nxt2; rows = rowsNext;
+        imgCur = imgNxt; imgNxt = imgNxt2;
+      }
+    }
+
+    // the image table of a batched stream encode, through kernel arguments (as k_set_batch_table: stream-ordered, and the caller's host arrays may die right away)
+    struct StreamTableChunk { uint32_t n; StreamImage e[32]; };
+    __global__ void k_set_stream_table(StreamImage *dst, const StreamTableChunk chunk)
+    {
+      const uint32_t *src = reinterpret_cast<const uint32_t *>(chunk.e);
+      uint32_t *out = reinterpret_cast<uint32_t *>(dst);
+      for (uint32_t i = threadIdx.x; i < chunk.n * (uint32_t)(sizeof(StreamImage) / 4); i += blockDim.x) out[i] = src[i];
+    }
+
+    // the sizes of `count` finished streams side by side, for ONE download
+    __global__ void k_stream_gather_bytes(const StreamImage *images, uint32_t count, unsigned long long *bytes)
+    {
+      const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+      if (i < count) bytes[i] = reinterpret_cast<const limg_hip_stream_header *>(images[i].stream)->totalBytes;
     }
 
     // ---- decode ----------------------------------------------------------------------------------------------------------
@@ -753,6 +796,29 @@ namespace limg_hip
     hipLaunchKernelGGL(k_stream_count, dim3(p.nTiles), dim3(kTile), 0, s, p);
     hipLaunchKernelGGL(k_stream_tile_scan<1>, dim3(1), dim3(1024), 0, s, p.tileBase, p.nTiles, p.stream, header_info(p));
     hipLaunchKernelGGL(k_stream_pack, dim3(p.nTiles), dim3(kTile), 0, s, p);
+  }
+
+  void launch_stream_pack_batch(const StreamBatchParams &b, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_stream_scan_strips_batch, dim3(b.nImages), dim3(1024), 0, s, b);
+    hipLaunchKernelGGL(k_stream_pack_strips_batch, dim3(b.nWaves), dim3(64), 0, s, b);
+  }
+
+  void launch_set_stream_table(StreamImage *dTable, const StreamImage *hTable, size_t count, hipStream_t s)
+  {
+    for (size_t i0 = 0; i0 < count; i0 += 32)
+    {
+      StreamTableChunk ch;
+      ch.n = (uint32_t)(count - i0 < 32 ? count - i0 : 32);
+      for (uint32_t i = 0; i < ch.n; i++) ch.e[i] = hTable[i0 + i];
+      for (uint32_t i = ch.n; i < 32; i++) ch.e[i] = StreamImage{};
+      hipLaunchKernelGGL(k_set_stream_table, dim3(1), dim3(256), 0, s, dTable + i0, ch);
+    }
+  }
+
+  void launch_stream_gather_bytes(const StreamImage *dTable, size_t count, unsigned long long *dBytes, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_stream_gather_bytes, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, s, dTable, (uint32_t)count, dBytes);
   }
 
   void launch_stream_decode(const DecodeParams &p, int cus, hipStream_t s)

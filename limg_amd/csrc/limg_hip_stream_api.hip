@@ -4,6 +4,7 @@
 #include "limg_hip_context.h"
 
 #include <algorithm>
+#include <vector>
 
 using namespace limg_hip;
 
@@ -496,6 +497,138 @@ extern "C"
     return decode_stream_host(c, pStream, streamBytes, pOut, outPixels, sizeX, sizeY, total, [&](const uint8_t *dStream, size_t bytes, uint32_t *dOut, size_t w, size_t h) {
       return limg_hip_decode_stream_device(c, dStream, bytes, dOut, w, h, nullptr);
     });
+  }
+
+  // ---- batched stream encode: a list of same-shape images, stream i = limg_hip_encode_stream_device of image i ----
+  // Lists of whole-block images go chunk by chunk (the plane batch's rule) through ONE compact-mode batched encode -- records, shift words and the strips' payload
+  // words in the context's raster arrays, image after image; the factor planes in per-image slices of streamFac -- and one scan + one pack launch over the chunk.
+  limg_hip_result limg_hip_encode_stream_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                      uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, int poolThreads,
+                                                      int fastBitCrushing, void *stream)
+  {
+    if (!c || !ppIn || !ppStreams) return limg_hip_error_ArgumentNull;
+    for (size_t i = 0; i < count; i++)
+      if (!ppIn[i] || !ppStreams[i]) return limg_hip_error_ArgumentNull;
+    const size_t bound = limg_hip_stream_bound(sizeX, sizeY);
+    if (bound == 0) return limg_hip_error_InvalidParameter;
+    if (capacityEach < bound) return limg_hip_error_OutOfBounds;
+    for (size_t i = 0; i < count; i++)
+      if (((uintptr_t)ppStreams[i] & 15u) != 0) return limg_hip_error_InvalidParameter;
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t px = sizeX * sizeY, planeStride = (px + 255) & ~(size_t)255;
+    const size_t blocksX = (sizeX + kBlock - 1) / kBlock, blocksY = (sizeY + kBlock - 1) / kBlock, blocks = blocksX * blocksY;
+    const size_t stripsX = (blocksX + kStripBlocks - 1) / kStripBlocks, imageStrips = stripsX * blocksY;
+    // the plane batch's chunk rule (limg_hip_encode3d_batch_device): 1 GiB of records, 32-bit strip ids, the test hook
+    size_t chunk = (size_t)(1ull << 30) / (blocks * sizeof(limg_hip_block_record));
+    if (chunk * imageStrips > 0x7FFFFFFFull) chunk = 0x7FFFFFFFull / imageStrips;
+    if (chunk < 1) chunk = 1;
+    if (TOPT(c, batch_chunk) > 0) chunk = (size_t)TOPT(c, batch_chunk);
+    const bool ragged = (sizeX % kBlock) != 0 || (sizeY % kBlock) != 0;
+    const bool oneByOne = count == 1 || ragged || c->opt.legacy_float_stage != 0 || c->forceSplit;
+    const size_t most = oneByOne ? 1 : (count < chunk ? count : chunk); // images of the largest chunk
+    limg_hip_result r;
+    if ((r = c->streamTable.ensure(count * sizeof(StreamImage))) != limg_hip_success) return r;
+    if (most > 1)
+    { // everything a chunk needs, before the first launch: nothing is grown (and so freed) between the chunks of a list
+      if ((r = c->streamFac.ensure(most * planeStride * 3)) != limg_hip_success) return r;
+      if ((r = c->streamUnits.ensure(most * imageStrips * 4)) != limg_hip_success) return r;
+      if ((r = c->records.ensure(most * blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+      if ((r = c->shifts.ensure(most * blocks * 4)) != limg_hip_success) return r;
+    }
+    std::vector<StreamImage> images(count);
+    for (size_t i = 0; i < count; i++) images[i].stream = ppStreams[i];
+    std::vector<ImageIO> table;
+    r = limg_hip_success;
+    for (size_t i0 = 0; i0 < count && r == limg_hip_success;)
+    {
+      const size_t n = oneByOne ? 1 : (count - i0 < chunk ? count - i0 : chunk);
+      c->statsAccumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, as the plane batch
+      if (n == 1)
+      { // the single call (images with partial edge blocks, the split path, the float stage inside the encode kernel, a list or a last chunk of one image)
+        r = limg_hip_encode_stream_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, ppStreams[i0], capacityEach, nullptr, errorFactor, poolThreads, fastBitCrushing, stream);
+        if (r == limg_hip_success && pBytes && !oneByOne) launch_set_stream_table((StreamImage *)c->streamTable.p + i0, &images[i0], 1, s); // (for the sizes below)
+      }
+      else
+      {
+        table.assign(n, ImageIO{});
+        for (size_t i = 0; i < n; i++)
+        {
+          uint8_t *fac = (uint8_t *)c->streamFac.p + i * 3 * planeStride; // 256-byte aligned slices
+          table[i].in = ppIn[i0 + i];
+          table[i].info.pFactorsA = fac; table[i].info.pFactorsB = fac + planeStride; table[i].info.pFactorsC = fac + 2 * planeStride;
+          images[i0 + i].fac[0] = fac; images[i0 + i].fac[1] = fac + planeStride; images[i0 + i].fac[2] = fac + 2 * planeStride;
+        }
+        limg_hip_compact_out comp = { (limg_hip_block_record *)c->records.p, (uint32_t *)c->shifts.p };
+        EncodeExtra x;
+        x.batch = table.data(); x.batchCount = n;
+        x.streamRaw = true; x.stripWords = (uint32_t *)c->streamUnits.p;
+        if ((r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, &table[0].info, &comp, errorFactor, poolThreads, fastBitCrushing, s, x)) != limg_hip_success) break;
+        launch_set_stream_table((StreamImage *)c->streamTable.p + i0, &images[i0], n, s);
+        StreamBatchParams b;
+        memset(&b, 0, sizeof(b));
+        b.sizeX = (uint32_t)sizeX; b.sizeY = (uint32_t)sizeY; b.blocksX = (uint32_t)blocksX; b.blocksY = (uint32_t)blocksY; b.nBlocks = (uint32_t)blocks;
+        b.channels = hasAlpha ? 4 : 3; b.errorFactor = errorFactor; b.flags = (fastBitCrushing ? 1u : 0u) | (c->opt.dither_pcg ? 2u : 0u);
+        b.stripsX = (uint32_t)stripsX; b.imageStrips = (uint32_t)imageStrips; b.nImages = (uint32_t)n; b.nStrips = (uint32_t)(n * imageStrips);
+        const size_t slots = (size_t)device_cus(c) * 16; // as the single call: 16 one-wave workgroups per CU -- for the whole chunk
+        b.nWaves = (uint32_t)(n * imageStrips < slots ? n * imageStrips : slots);
+        b.images = (const StreamImage *)c->streamTable.p + i0;
+        b.records = comp.pRecords; b.shifts = comp.pShifts; b.stripWords = (uint32_t *)c->streamUnits.p;
+        mark(c, s);
+        launch_stream_pack_batch(b, s);
+        mark(c, s); mark(c, s); mark(c, s);
+        const hipError_t launched = hipGetLastError();
+        if (launched != hipSuccess) { c->statsAccumulate = false; HIP_TRY(launched); }
+      }
+      i0 += n;
+    }
+    c->statsAccumulate = false;
+    if (r != limg_hip_success || !pBytes) return r;
+    // the sizes: gathered from the headers on the device, ONE download
+    if ((r = c->streamSizes.ensure(count * 8)) != limg_hip_success) return r;
+    if (oneByOne) launch_set_stream_table((StreamImage *)c->streamTable.p, images.data(), count, s);
+    launch_stream_gather_bytes((const StreamImage *)c->streamTable.p, count, (unsigned long long *)c->streamSizes.p, s);
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned long long> sizes(count);
+    HIP_TRY(hipMemcpyAsync(sizes.data(), c->streamSizes.p, count * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < count; i++) pBytes[i] = (size_t)sizes[i];
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_encode_stream_batch(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                               uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, int poolThreads, int fastBitCrushing)
+  {
+    if (!c || !ppIn || !ppStreams || !pBytes) return limg_hip_error_ArgumentNull;
+    for (size_t i = 0; i < count; i++)
+      if (!ppIn[i] || !ppStreams[i]) return limg_hip_error_ArgumentNull;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    const size_t bound = limg_hip_stream_bound(sizeX, sizeY);
+    if (bound == 0) return limg_hip_error_InvalidParameter;
+    if (capacityEach < bound) return limg_hip_error_OutOfBounds;
+    if (count == 0) return limg_hip_success;
+    HIP_TRY(hipSetDevice(c->device));
+    // staging: the images side by side in `in`, the streams at worst-case size (rounded up to 256 bytes) side by side in streamBuf
+    const size_t px = sizeX * sizeY, slice = (bound + 255) & ~(size_t)255;
+    limg_hip_result r;
+    if ((r = c->in.ensure(count * px * 4)) != limg_hip_success) return r;
+    if ((r = c->streamBuf.ensure(count * slice)) != limg_hip_success) return r;
+    std::vector<const uint32_t *> dIn(count);
+    std::vector<uint8_t *> dStreams(count);
+    for (size_t i = 0; i < count; i++)
+    {
+      dIn[i] = (const uint32_t *)c->in.p + i * px;
+      dStreams[i] = (uint8_t *)c->streamBuf.p + i * slice;
+      HIP_TRY(hipMemcpy((void *)dIn[i], ppIn[i], px * 4, hipMemcpyHostToDevice));
+    }
+    if ((r = limg_hip_encode_stream_batch_device(c, count, dIn.data(), sizeX, sizeY, hasAlpha, dStreams.data(), slice, pBytes, errorFactor, poolThreads, fastBitCrushing,
+                                                 nullptr)) != limg_hip_success)
+      return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], dStreams[i], pBytes[i], hipMemcpyDeviceToHost)); // totalBytes of each, not the capacity
+    return limg_hip_success;
   }
 
   // ---- version 2: the merged-block encoder's rectangles ----
