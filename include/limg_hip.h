@@ -476,6 +476,61 @@ limg_hip_result limg_hip_blocked_decode_stream_windows_device(limg_hip_context *
 limg_hip_result limg_hip_decode_stream_windows(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count);
 limg_hip_result limg_hip_blocked_decode_stream_windows(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count);
 
+/* ---- batched window decode into planar float tensors ---------------------------------------------------------------------------
+ * The crop + normalise + layout step of an image loader, fused into the decode: every job's window leaves as `planes` planes of float32 or float16 instead of packed
+ * RGBA8, so a batch tensor N x C x h x w is filled by one call, without the RGBA intermediate and the pass over it.  One format per call, many jobs per call.
+ * Result: let P(x, y) be the pixel the version's full decoder writes.  Element (c, r, col) of job i, for c < planes, r < height, col < width, is
+ *     v = (float)((P(x0 + col, y0 + r) >> 8c) & 0xFF) * scale[c] + bias[c]
+ * evaluated in float32 as one multiply, then one add, each rounded on its own (no fused multiply-add); stored as is for LIMG_HIP_TENSOR_F32, converted with
+ * round-to-nearest-even for LIMG_HIP_TENSOR_F16.  numpy gives the same bits: (b.astype(float32) * float32(scale)) + float32(bias), then .astype(float16).
+ * NOTHING ELSE IS WRITTEN: not the rowStride - width elements behind a row, not the gap between planes, no plane at or beyond `planes`, nothing beyond the last row.
+ * Store width: a block row piece of 8 pixels that lies wholly inside the window leaves as 16-byte stores per plane -- two for F32 where pOut is 16-byte aligned and
+ * rowStride, planeStride and x0 are multiples of 4; one for F16 where pOut is 16-byte aligned and the three are multiples of 8 -- otherwise element by element, with
+ * identical results.
+ * Errors, before anything is enqueued, in this order: NULL context, pJobs / pWindows or pFormat: limg_hip_error_ArgumentNull; count == 0: limg_hip_error_InvalidParameter;
+ * an unknown `type`, or `planes` not 3 or 4: limg_hip_error_InvalidParameter; then the jobs in index order, each by the single-window entry's rules in its order, where
+ * rowStride < width or planeStride < (height - 1) * rowStride + width takes the place of outStridePixels < width, and pOut must be aligned to the element size
+ * (4 / 2 bytes).  The first failing job's error is returned and nothing is enqueued for any job.
+ * Everything else is the batched window decode's, unchanged: validation on the device and what a refused job or group stores, per version; pJobStatus and the sticky
+ * status; ONE launch for version 1 and TWO for version 2 whatever `count` is; version 2 scans each distinct stream's table once per call; ordering, the four calls
+ * in flight, and not during graph capture. */
+#define LIMG_HIP_TENSOR_F32 0u
+#define LIMG_HIP_TENSOR_F16 1u
+
+typedef struct limg_hip_tensor_format
+{
+  uint32_t type;   /* LIMG_HIP_TENSOR_F32 / LIMG_HIP_TENSOR_F16 */
+  uint32_t planes; /* 3 or 4: plane c holds byte c of the decoded pixel (R, G, B[, byte 3]) */
+  float scale[4], bias[4];
+} limg_hip_tensor_format;
+
+typedef struct limg_hip_tensor_window /* one window and where it goes */
+{
+  size_t x0, y0, width, height;  /* pixels, inside the image, not empty */
+  void *pOut;                    /* element (c, r, col) at pOut[c * planeStride + r * rowStride + col], in elements of the format's type */
+  size_t rowStride, planeStride; /* in elements */
+} limg_hip_tensor_window;
+
+typedef struct limg_hip_tensor_window_job /* one window of one stream */
+{
+  const uint8_t *pStream; /* DEVICE, 16-byte aligned */
+  size_t streamBytes;
+  size_t sizeX, sizeY;    /* must match the stream's header */
+  limg_hip_tensor_window window; /* pOut: DEVICE, aligned to the element size */
+} limg_hip_tensor_window_job;
+
+/* DEVICE pointers inside the jobs; pJobs and pFormat are HOST memory and may be reused or freed when the call returns.  Asynchronous on `stream`. */
+limg_hip_result limg_hip_decode_stream_windows_tensor_device(limg_hip_context *pCtx, const limg_hip_tensor_window_job *pJobs, size_t count,
+                                                             const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream);
+limg_hip_result limg_hip_blocked_decode_stream_windows_tensor_device(limg_hip_context *pCtx, const limg_hip_tensor_window_job *pJobs, size_t count,
+                                                                     const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream);
+/* HOST pointers, blocking, under the context's mutex: `count` windows of ONE stream, as limg_hip_decode_stream_windows.  Context staging takes planes x element size
+ * per window pixel, summed; a stream refused for any window leaves EVERY pOut untouched, in both versions. */
+limg_hip_result limg_hip_decode_stream_windows_tensor(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows,
+                                                      size_t count, const limg_hip_tensor_format *pFormat);
+limg_hip_result limg_hip_blocked_decode_stream_windows_tensor(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows,
+                                                              size_t count, const limg_hip_tensor_format *pFormat);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ---------------------------------------------------------------------------------
  * The reference's only parallelism is row strips over a std::thread pool (src/limg.cpp:2105-2138); across GPUs the same strips
  * go one per rank.  Blocks are independent except for the dither chain, so the data path needs no collective in strip-restart mode (each strip

@@ -256,4 +256,14 @@ inline limg_result limg_decode_windows(const uint8_t *pIn, const size_t size, co
   return (limg_result)limg_hip_decode_stream_windows(c, pIn, size, pWindows, count);
 }
 
+// ... into planar float tensors (limg_hip.h "batched window decode into planar float tensors"): element (c, r, col) of window i = byte c of the pixel * scale[c] + bias[c]
+inline limg_result limg_decode_windows_tensor(const uint8_t *pIn, const size_t size, const limg_hip_tensor_window *pWindows, const size_t count, const limg_hip_tensor_format *pFormat)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (limg_hip_blocked_stream_info(pIn, size, nullptr, nullptr, nullptr, nullptr, nullptr) == limg_hip_success)
+    return (limg_result)limg_hip_blocked_decode_stream_windows_tensor(c, pIn, size, pWindows, count, pFormat);
+  return (limg_result)limg_hip_decode_stream_windows_tensor(c, pIn, size, pWindows, count, pFormat);
+}
+
 #endif // LIMG_HIP_SHIM_HPP

@@ -32,6 +32,8 @@ ABI_SYMBOLS = (
     "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
     "limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device", "limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window",
     "limg_hip_decode_stream_windows_device", "limg_hip_blocked_decode_stream_windows_device", "limg_hip_decode_stream_windows", "limg_hip_blocked_decode_stream_windows",
+    "limg_hip_decode_stream_windows_tensor_device", "limg_hip_blocked_decode_stream_windows_tensor_device", "limg_hip_decode_stream_windows_tensor",
+    "limg_hip_blocked_decode_stream_windows_tensor",
     "limg_hip_blocked_encode3d", "limg_hip_blocked_encode3d_device", "limg_hip_blocked_regions", "limg_hip_blocked_timing", "limg_hip_blocked_kernel_timing", "limg_hip_blocked_match_bits", "limg_hip_host_blocked_matches",
     "limg_hip_host_blocked_merge", "limg_hip_host_blocked_match_words", "limg_hip_host_blocked_match_bits",
     "limg_hip_comm_unique_id", "limg_hip_comm_init", "limg_hip_comm_destroy", "limg_hip_comm_info", "limg_hip_gather_stream", "limg_hip_encode3d_single_chain_device",
@@ -81,6 +83,33 @@ class Window(C.Structure):
 class WindowJob(C.Structure):
     """limg_hip_window_job: one window of one stream"""
     _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", Window)]
+
+
+TENSOR_F32, TENSOR_F16 = 0, 1  # limg_hip_tensor_format.type
+
+
+class TensorFormat(C.Structure):
+    """limg_hip_tensor_format: element type, plane count and the per-channel scale / bias of the tensor entries"""
+    _fields_ = [("type", C.c_uint32), ("planes", C.c_uint32), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
+class TensorWindow(C.Structure):
+    """limg_hip_tensor_window: one window and the planes it goes to"""
+    _fields_ = [("x0", C.c_size_t), ("y0", C.c_size_t), ("width", C.c_size_t), ("height", C.c_size_t), ("pOut", C.c_void_p), ("rowStride", C.c_size_t),
+                ("planeStride", C.c_size_t)]
+
+
+class TensorWindowJob(C.Structure):
+    """limg_hip_tensor_window_job: one window of one stream"""
+    _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", TensorWindow)]
+
+
+def tensor_format(dtype, planes, scale, bias):
+    """dtype: "float32" / "float16" (or the numpy / torch dtype); scale, bias: one value per plane (a 4th is 1 / 0 where only three are given)"""
+    name = str(dtype).split(".")[-1].replace("'>", "")
+    assert name in ("float32", "float16"), dtype
+    scale, bias = list(scale) + [1.0] * (4 - len(scale)), list(bias) + [0.0] * (4 - len(bias))
+    return TensorFormat(TENSOR_F16 if name == "float16" else TENSOR_F32, planes, (C.c_float * 4)(*scale[:4]), (C.c_float * 4)(*bias[:4]))
 
 
 class Options(C.Structure):
@@ -223,6 +252,12 @@ def load_library(path=None):
     for name in ("limg_hip_decode_stream_windows", "limg_hip_blocked_decode_stream_windows"):
         getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count
         getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    for name in ("limg_hip_decode_stream_windows_tensor_device", "limg_hip_blocked_decode_stream_windows_tensor_device"):
+        getattr(L, name).restype = C.c_int  # ctx, jobs (host), count, format (host), jobStatus (device), hipStream
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name in ("limg_hip_decode_stream_windows_tensor", "limg_hip_blocked_decode_stream_windows_tensor"):
+        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count, format (host)
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     L.limg_hip_blocked_last_stream.restype = C.c_int
     L.limg_hip_blocked_last_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.limg_hip_blocked_stream_info.restype = C.c_int
@@ -724,6 +759,72 @@ class LimgHip:
 
     def blocked_decode_stream_windows(self, stream, wins, outs=None):
         return self._decode_stream_windows("limg_hip_blocked_decode_stream_windows", stream, wins, outs)
+
+    # ---- batched window decode into planar float tensors (contract: include/limg_hip.h) ----
+    def _decode_stream_windows_tensor_device(self, name, jobs, fmt, status):
+        import torch
+        dtype = torch.float16 if fmt.type == TENSOR_F16 else torch.float32
+        table = (TensorWindowJob * len(jobs))()
+        outs = []
+        for i, (stream, nbytes, W, H, x, y, w, h, out, row_stride, plane_stride) in enumerate(jobs):
+            if out is None:
+                out = torch.empty((fmt.planes, h, w), dtype=dtype, device=stream.device)
+            assert out.dtype == dtype, (out.dtype, dtype)
+            if row_stride is None:
+                row_stride = out.stride(1) if out.dim() == 3 else w
+            if plane_stride is None:
+                plane_stride = out.stride(0) if out.dim() == 3 else row_stride * h
+            table[i] = TensorWindowJob(stream.data_ptr(), int(nbytes), W, H, TensorWindow(x, y, w, h, out.data_ptr(), int(row_stride), int(plane_stride)))
+            outs.append(out)
+        self._stream_call(name, table, len(jobs), C.byref(fmt), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
+        return outs
+
+    def _decode_stream_windows_tensor(self, name, stream, wins, fmt, outs):
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        dtype = np.float16 if fmt.type == TENSOR_F16 else np.float32
+        eb = np.dtype(dtype).itemsize
+        outs = [None] * len(wins) if outs is None else list(outs)
+        table = (TensorWindow * len(wins))()
+        for i, (x, y, w, h) in enumerate(wins):
+            if outs[i] is None:
+                outs[i] = np.zeros((fmt.planes, h, w), dtype=dtype)
+            out = outs[i]
+            assert out.dtype == dtype and out.ndim == 3 and out.shape[0] >= fmt.planes and out.strides[2] == eb and out.strides[1] % eb == 0 and out.strides[0] % eb == 0, \
+                "out: (planes, h, w) of the format's type, elements of a row contiguous"
+            table[i] = TensorWindow(x, y, w, h, out.ctypes.data, out.strides[1] // eb, out.strides[0] // eb)
+        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins), C.byref(fmt))
+        return outs
+
+    def decode_stream_windows_tensor_device(self, jobs, fmt, status=None):
+        """jobs: (stream tensor, nbytes, W, H, x, y, w, h, out, row_stride, plane_stride) each; out: a torch CUDA tensor of fmt's type whose first element receives
+        element (0, 0, 0) of the window, rows row_stride and planes plane_stride elements apart (None: out's own strides; out=None allocates (planes, h, w)).
+        fmt: tensor_format(...).  status: torch int32 CUDA tensor of len(jobs) words or None.  One launch for all jobs, asynchronous on torch's current stream.
+        Returns the list of output tensors."""
+        return self._decode_stream_windows_tensor_device("limg_hip_decode_stream_windows_tensor_device", jobs, fmt, status)
+
+    def blocked_decode_stream_windows_tensor_device(self, jobs, fmt, status=None):
+        return self._decode_stream_windows_tensor_device("limg_hip_blocked_decode_stream_windows_tensor_device", jobs, fmt, status)
+
+    def decode_stream_windows_tensor(self, stream, wins, fmt, outs=None):
+        """host stream bytes, wins: (x, y, w, h) each -> the list of numpy (planes, h, w) arrays of fmt's type; outs: per window a view that receives it (rows and
+        planes may be strided) or None.  The stream is uploaded once."""
+        return self._decode_stream_windows_tensor("limg_hip_decode_stream_windows_tensor", stream, wins, fmt, outs)
+
+    def blocked_decode_stream_windows_tensor(self, stream, wins, fmt, outs=None):
+        return self._decode_stream_windows_tensor("limg_hip_blocked_decode_stream_windows_tensor", stream, wins, fmt, outs)
+
+    def decode_crops_device(self, jobs, h, w, dtype, scale, bias, planes=3, blocked=False, out=None):
+        """The loader step: jobs: (stream tensor, nbytes, W, H, x, y) each -- the h x w crop at (x, y) of each stream -> ONE contiguous (N, planes, h, w) torch tensor
+        of `dtype` (torch.float32 / torch.float16), element = byte * scale[c] + bias[c]; job i fills slice i.  out: the tensor to fill.  One call of the version's
+        tensor entry, asynchronous on torch's current stream."""
+        import torch
+        fmt = tensor_format(dtype, planes, scale, bias)
+        if out is None:
+            out = torch.empty((len(jobs), planes, h, w), dtype=dtype, device=jobs[0][0].device)
+        assert tuple(out.shape) == (len(jobs), planes, h, w) and out.is_contiguous() and out.dtype == dtype
+        table = [(stream, nbytes, W, H, x, y, w, h, out[i], w, h * w) for i, (stream, nbytes, W, H, x, y) in enumerate(jobs)]
+        (self.blocked_decode_stream_windows_tensor_device if blocked else self.decode_stream_windows_tensor_device)(table, fmt)
+        return out
 
     def check(self):
         _check(self.lib.limg_hip_check_device_status(self.ctx), "limg_hip_check_device_status")

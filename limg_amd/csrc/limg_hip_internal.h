@@ -232,6 +232,9 @@ namespace limg_hip
     uint32_t *map;                  // version 2: per block of the window the rectangle that covers it (~0: none yet)
     uint32_t *status;               // the context's sticky stream status word, bits as in DecodeParams
     uint32_t *state;                // version 2: this call's words (zeroed in front of it): [0] window blocks claimed, [1] non-0 = the stream is refused
+    // planar float output (the *_windows_tensor entries): `out` is then float / _Float16, element (c, r, col) at out[c * planeStride + r * outStride + col], and vecOut
+    // says that a piece wholly inside the window may leave as 16-byte stores per plane (out 16-byte aligned; outStride, planeStride and x0 multiples of 16 / element size)
+    unsigned long long planeStride;
   };
   void launch_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s);
   void launch_blocked_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s);
@@ -264,6 +267,9 @@ namespace limg_hip
   };
   void launch_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s);
   void launch_blocked_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s);
+  // ... into planar float tensors: the same job table (planeStride set, out / outStride / vecOut in elements of f.type), one format per launch
+  void launch_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s);
+  void launch_blocked_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s);
 
   void launch_stream_pack(const StreamParams &p, hipStream_t s);
   void launch_stream_pack_batch(const StreamBatchParams &b, hipStream_t s);                                                  // one scan launch + one pack launch, whatever nImages is

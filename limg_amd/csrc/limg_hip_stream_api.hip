@@ -4,6 +4,7 @@
 #include "limg_hip_context.h"
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 using namespace limg_hip;
@@ -135,14 +136,45 @@ namespace
   }
 
   // ---- window decode: limg_hip_*decode_stream_window* (kernels: limg_hip_stream_window.hip) ----
+  // Where a window's pixels go: packed RGBA8 (planes == 0: elemBytes 4, one element per pixel) or `planes` planes of float / _Float16 (the tensor entries).
+  struct WindowOut
+  {
+    void *p;
+    size_t rowStride, planeStride; // in elements
+    uint32_t elemBytes, planes;
+  };
+  WindowOut window_out(const limg_hip_window &w, const limg_hip_tensor_format *) { return { w.pOut, w.outStridePixels, 0, 4u, 0u }; }
+  WindowOut window_out(const limg_hip_tensor_window &w, const limg_hip_tensor_format *f)
+  {
+    return { w.pOut, w.rowStride, w.planeStride, f->type == LIMG_HIP_TENSOR_F16 ? 2u : 4u, f->planes };
+  }
+  bool tensor_format_ok(const limg_hip_tensor_format *f) { return (f->type == LIMG_HIP_TENSOR_F32 || f->type == LIMG_HIP_TENSOR_F16) && (f->planes == 3u || f->planes == 4u); }
+
+  // the window's size and the output's strides: what every window entry, device or host, checks first
+  limg_hip_result window_out_check(size_t width, size_t height, const WindowOut &o)
+  {
+    if (width == 0 || height == 0 || o.rowStride < width) return limg_hip_error_InvalidParameter;
+    if (o.planes)
+    { // planeStride >= (height - 1) * rowStride + width, without overflow
+      if (height > 1 && o.rowStride > ((size_t)-1 - width) / (height - 1)) return limg_hip_error_InvalidParameter;
+      if (o.planeStride < (height - 1) * o.rowStride + width) return limg_hip_error_InvalidParameter;
+    }
+    return limg_hip_success;
+  }
+  bool out_aligned(const WindowOut &o) { return ((uintptr_t)o.p & (o.elemBytes - 1u)) == 0; }
+  bool window_inside(size_t sizeX, size_t sizeY, size_t x0, size_t y0, size_t width, size_t height)
+  {
+    return !(x0 >= sizeX || width > sizeX - x0 || y0 >= sizeY || height > sizeY - y0);
+  }
+
   // the checks and the parameters the two versions share, without touching the device; `bound`: the version's limg_hip_*stream_bound(sizeX, sizeY).  status, map and
   // state are the caller's to set.
   limg_hip_result window_fill(const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width, size_t height,
-                              uint32_t *pOut, size_t outStridePixels, WindowDecodeParams &wp)
+                              const WindowOut &o, WindowDecodeParams &wp)
   {
-    if (width == 0 || height == 0 || outStridePixels < width || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
-    if (((uintptr_t)pStream & 15u) != 0 || ((uintptr_t)pOut & 3u) != 0) return limg_hip_error_InvalidParameter;
-    if (x0 >= sizeX || width > sizeX - x0 || y0 >= sizeY || height > sizeY - y0) return limg_hip_error_OutOfBounds;
+    if (window_out_check(width, height, o) != limg_hip_success || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
+    if (((uintptr_t)pStream & 15u) != 0 || !out_aligned(o)) return limg_hip_error_InvalidParameter;
+    if (!window_inside(sizeX, sizeY, x0, y0, width, height)) return limg_hip_error_OutOfBounds;
     memset(&wp, 0, sizeof(wp));
     wp.sizeX = (uint32_t)sizeX; wp.sizeY = (uint32_t)sizeY;
     wp.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); wp.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
@@ -151,15 +183,16 @@ namespace
     wp.x0 = (uint32_t)x0; wp.y0 = (uint32_t)y0; wp.width = (uint32_t)width; wp.height = (uint32_t)height;
     wp.bx0 = (uint32_t)(x0 / kBlock); wp.by0 = (uint32_t)(y0 / kBlock);
     wp.wbx = (uint32_t)((x0 + width - 1) / kBlock) - wp.bx0 + 1; wp.wby = (uint32_t)((y0 + height - 1) / kBlock) - wp.by0 + 1;
-    wp.out = pOut; wp.outStride = outStridePixels;
-    wp.vecOut = ((uintptr_t)pOut & 15u) == 0 && (outStridePixels & 3u) == 0 && (x0 & 3u) == 0;
+    wp.out = (uint32_t *)o.p; wp.outStride = o.rowStride; wp.planeStride = o.planeStride;
+    const size_t per = 16u / o.elemBytes; // elements per 16-byte store (planeStride is 0 for RGBA)
+    wp.vecOut = ((uintptr_t)o.p & 15u) == 0 && o.rowStride % per == 0 && o.planeStride % per == 0 && x0 % per == 0;
     return limg_hip_success;
   }
 
   limg_hip_result window_params(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width,
                                 size_t height, uint32_t *pOut, size_t outStridePixels, hipStream_t s, WindowDecodeParams &wp)
   {
-    limg_hip_result r = window_fill(pStream, streamBytes, sizeX, sizeY, bound, x0, y0, width, height, pOut, outStridePixels, wp);
+    limg_hip_result r = window_fill(pStream, streamBytes, sizeX, sizeY, bound, x0, y0, width, height, WindowOut{ pOut, outStridePixels, 0, 4u, 0u }, wp);
     if (r != limg_hip_success) return r;
     HIP_TRY(hipSetDevice(c->device));
     if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
@@ -211,21 +244,26 @@ namespace
   size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
   // One call: every job checked on the host before anything touches the device, then the job table built in a pinned slot of the context's ring, copied on `s`,
-  // and the version's one (two) launches.  blocked: version 2.
-  limg_hip_result decode_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, hipStream_t s, bool blocked)
+  // and the version's one (two) launches.  blocked: version 2.  JOB: limg_hip_window_job (packed RGBA8; pFormat is not looked at) or limg_hip_tensor_window_job
+  // (planes of pFormat's type): the same checks, table and launches but for where the pixels go.
+  template <class JOB>
+  limg_hip_result decode_windows_device(limg_hip_context *c, const JOB *pJobs, size_t count, const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, hipStream_t s,
+                                        bool blocked)
   {
-    if (!c || !pJobs) return limg_hip_error_ArgumentNull;
+    constexpr bool tensor = std::is_same<JOB, limg_hip_tensor_window_job>::value;
+    if (!c || !pJobs || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
     if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
     // pass 1: the single-window entry's checks, job by job in its order; the sums the table's layout needs
     unsigned long long units = 0, blocks = 0;
     WindowDecodeParams wp;
     for (size_t i = 0; i < count; i++)
     {
-      const limg_hip_window_job &j = pJobs[i];
+      const JOB &j = pJobs[i];
       if (!j.pStream || !j.window.pOut) return limg_hip_error_ArgumentNull;
       const size_t bound = blocked ? limg_hip_blocked_stream_bound(j.sizeX, j.sizeY) : limg_hip_stream_bound(j.sizeX, j.sizeY);
-      const limg_hip_result r = window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height, j.window.pOut,
-                                            j.window.outStridePixels, wp);
+      const limg_hip_result r = window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height,
+                                            window_out(j.window, pFormat), wp);
       if (r != limg_hip_success) return r;
       if (!blocked && j.streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
       units += (unsigned long long)((wp.wbx + (blocked ? 7u : 63u)) / (blocked ? 8u : 64u)) * wp.wby;
@@ -259,9 +297,9 @@ namespace
     uint32_t unitAt = 0, blockAt = 0;
     for (size_t i = 0; i < count; i++)
     {
-      const limg_hip_window_job &j = pJobs[i];
+      const JOB &j = pJobs[i];
       const size_t bound = blocked ? limg_hip_blocked_stream_bound(j.sizeX, j.sizeY) : limg_hip_stream_bound(j.sizeX, j.sizeY);
-      (void)window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height, j.window.pOut, j.window.outStridePixels, jobs[i]);
+      (void)window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height, window_out(j.window, pFormat), jobs[i]);
       jobs[i].status = (uint32_t *)c->streamStatus.p;
       if (blocked)
       {
@@ -322,7 +360,12 @@ namespace
       HIP_TRY(hipMemsetAsync(db + oMap, 0xFF, (size_t)blocks * 4, s)); // no block has a rectangle yet
     }
     if (pJobStatus) HIP_TRY(hipMemsetAsync(pJobStatus, 0, count * 4, s));
-    if (blocked) launch_blocked_stream_windows_decode(b, device_cus(c), s);
+    if (tensor)
+    {
+      if (blocked) launch_blocked_stream_windows_tensor(b, *pFormat, device_cus(c), s);
+      else launch_stream_windows_tensor(b, *pFormat, device_cus(c), s);
+    }
+    else if (blocked) launch_blocked_stream_windows_decode(b, device_cus(c), s);
     else launch_stream_windows_decode(b, device_cus(c), s);
     const hipError_t launched = hipGetLastError();
     HIP_TRY(hipEventRecord(slot.done, s));
@@ -330,52 +373,69 @@ namespace
     return limg_hip_success;
   }
 
-  // `count` windows of ONE host stream.  info(&sizeX, &sizeY, &total): the version's header check.
-  template <class INFO>
-  limg_hip_result decode_windows_host(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count, bool blocked, INFO &&info)
+  // the staged form of a window: densely packed in context memory
+  void stage_window(limg_hip_window &w, void *p) { w.pOut = (uint32_t *)p; w.outStridePixels = w.width; }
+  void stage_window(limg_hip_tensor_window &w, void *p) { w.pOut = p; w.rowStride = w.width; w.planeStride = w.width * w.height; }
+  template <class WIN> struct JobOf { typedef limg_hip_window_job type; };
+  template <> struct JobOf<limg_hip_tensor_window> { typedef limg_hip_tensor_window_job type; };
+
+  // `count` windows of ONE host stream.  info(&sizeX, &sizeY, &total): the version's header check.  WIN: limg_hip_window or limg_hip_tensor_window (with pFormat).
+  template <class WIN, class INFO>
+  limg_hip_result decode_windows_host(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const WIN *pWindows, size_t count,
+                                      const limg_hip_tensor_format *pFormat, bool blocked, INFO &&info)
   {
-    if (!c || !pStream || !pWindows) return limg_hip_error_ArgumentNull;
+    typedef typename JobOf<WIN>::type JOB;
+    constexpr bool tensor = std::is_same<WIN, limg_hip_tensor_window>::value;
+    if (!c || !pStream || !pWindows || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
     if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
     for (size_t i = 0; i < count; i++)
     {
-      const limg_hip_window &w = pWindows[i];
+      const WIN &w = pWindows[i];
       if (!w.pOut) return limg_hip_error_ArgumentNull;
-      if (w.width == 0 || w.height == 0 || w.outStridePixels < w.width) return limg_hip_error_InvalidParameter;
+      const limg_hip_result ok = window_out_check(w.width, w.height, window_out(w, pFormat));
+      if (ok != limg_hip_success) return ok;
+      if (tensor && !out_aligned(window_out(w, pFormat))) return limg_hip_error_InvalidParameter;
     }
     size_t sizeX = 0, sizeY = 0, total = 0;
     limg_hip_result r = info(&sizeX, &sizeY, &total);
     if (r != limg_hip_success) return r;
     if (total > streamBytes) return limg_hip_error_OutOfBounds;
-    size_t pixels = 0; // staging: every window at its own width, on a 16-byte boundary
+    const size_t eb = window_out(pWindows[0], pFormat).elemBytes, planes = tensor ? pFormat->planes : 1;
+    const size_t per = 16 / eb;
+    size_t elems = 0; // staging: every window at its own width (plane after plane), on a 16-byte boundary
     for (size_t i = 0; i < count; i++)
     {
-      const limg_hip_window &w = pWindows[i];
-      if (w.x0 >= sizeX || w.width > sizeX - w.x0 || w.y0 >= sizeY || w.height > sizeY - w.y0) return limg_hip_error_OutOfBounds;
-      pixels += (w.width * w.height + 3) & ~(size_t)3;
+      const WIN &w = pWindows[i];
+      if (!window_inside(sizeX, sizeY, w.x0, w.y0, w.width, w.height)) return limg_hip_error_OutOfBounds;
+      elems += (planes * w.width * w.height + per - 1) / per * per;
     }
-    limg_hip_window_job *jobs = new (std::nothrow) limg_hip_window_job[count];
+    JOB *jobs = new (std::nothrow) JOB[count];
     if (!jobs) return limg_hip_error_MemoryAllocationFailure;
-    struct Free { limg_hip_window_job *p; ~Free() { delete[] p; } } freeJobs = { jobs };
+    struct Free { JOB *p; ~Free() { delete[] p; } } freeJobs = { jobs };
     HIP_TRY(hipSetDevice(c->device));
     if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
-    if ((r = c->planes.ensure(pixels * 4)) != limg_hip_success) return r;
+    if ((r = c->planes.ensure(elems * eb)) != limg_hip_success) return r;
     HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice)); // once, for all windows
     size_t at = 0;
     for (size_t i = 0; i < count; i++)
     {
-      const limg_hip_window &w = pWindows[i];
+      const WIN &w = pWindows[i];
       jobs[i].pStream = (const uint8_t *)c->streamBuf.p; jobs[i].streamBytes = total; jobs[i].sizeX = sizeX; jobs[i].sizeY = sizeY;
       jobs[i].window = w;
-      jobs[i].window.pOut = (uint32_t *)c->planes.p + at; jobs[i].window.outStridePixels = w.width;
-      at += (w.width * w.height + 3) & ~(size_t)3;
+      stage_window(jobs[i].window, (uint8_t *)c->planes.p + at * eb);
+      at += (planes * w.width * w.height + per - 1) / per * per;
     }
-    if ((r = decode_windows_device(c, jobs, count, nullptr, nullptr, blocked)) != limg_hip_success) return r;
+    if ((r = decode_windows_device(c, jobs, count, pFormat, nullptr, nullptr, blocked)) != limg_hip_success) return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r; // a stream refused for any window: no pOut is touched
     for (size_t i = 0; i < count; i++)
     {
-      const limg_hip_window &w = pWindows[i];
-      HIP_TRY(hipMemcpy2D(w.pOut, w.outStridePixels * 4, jobs[i].window.pOut, w.width * 4, w.width * 4, w.height, hipMemcpyDeviceToHost));
+      const WIN &w = pWindows[i];
+      const WindowOut o = window_out(w, pFormat);
+      for (size_t pl = 0; pl < planes; pl++)
+        HIP_TRY(hipMemcpy2D((uint8_t *)o.p + pl * o.planeStride * eb, o.rowStride * eb, (const uint8_t *)jobs[i].window.pOut + pl * w.width * w.height * eb, w.width * eb,
+                            w.width * eb, w.height, hipMemcpyDeviceToHost));
     }
     return limg_hip_success;
   }
@@ -768,23 +828,50 @@ extern "C"
   // ---- batched window decode, both versions ----
   limg_hip_result limg_hip_decode_stream_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
   {
-    return decode_windows_device(c, pJobs, count, pJobStatus, (hipStream_t)stream, false);
+    return decode_windows_device(c, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, false);
   }
 
   limg_hip_result limg_hip_blocked_decode_stream_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
   {
-    return decode_windows_device(c, pJobs, count, pJobStatus, (hipStream_t)stream, true);
+    return decode_windows_device(c, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, true);
   }
 
   limg_hip_result limg_hip_decode_stream_windows(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count)
   {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, false,
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, nullptr, false,
                                [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); });
   }
 
   limg_hip_result limg_hip_blocked_decode_stream_windows(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count)
   {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, true,
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, nullptr, true,
+                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });
+  }
+
+  // ---- batched window decode into planar float tensors, both versions ----
+  limg_hip_result limg_hip_decode_stream_windows_tensor_device(limg_hip_context *c, const limg_hip_tensor_window_job *pJobs, size_t count, const limg_hip_tensor_format *pFormat,
+                                                               uint32_t *pJobStatus, void *stream)
+  {
+    return decode_windows_device(c, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream, false);
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_windows_tensor_device(limg_hip_context *c, const limg_hip_tensor_window_job *pJobs, size_t count,
+                                                                       const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
+  {
+    return decode_windows_device(c, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream, true);
+  }
+
+  limg_hip_result limg_hip_decode_stream_windows_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows, size_t count,
+                                                        const limg_hip_tensor_format *pFormat)
+  {
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, pFormat, false,
+                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); });
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_windows_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows,
+                                                                size_t count, const limg_hip_tensor_format *pFormat)
+  {
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, pFormat, true,
                                [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });
   }
 }

@@ -28,6 +28,11 @@
 //   k_bstream_windows_map      version 2.  Work item = (stream group, 64 rectangles): every rectangle is checked ONCE per group and its intersection claimed in the
 //                              map slice of every window of the group.  A bad rectangle or header refuses every job of the group, a clash the job it happened in.
 //   k_bstream_windows_decode   one launch over the concatenated 8-block units; a unit reads its job's verdict first.
+//
+// Tensor forms (limg_hip_*decode_stream_windows_tensor*): the batched kernels with another store.  How a lane's 8 decoded pixels leave is a policy of window_unit and
+// bwindow_unit: RgbaStore is the packed store of every kernel above; PlanarStore<T> (T = float / _Float16) writes byte c of each pixel as scale[c] * byte + bias[c]
+// into plane c, `planes` planes.  k_stream_windows_tensor<T> and k_bstream_windows_tensor<T> are k_stream_windows_decode and k_bstream_windows_decode with it;
+// k_bstream_windows_map never touches the output and serves both.  The format is a kernel argument: scale and bias stay in scalar registers.
 #include "limg_hip_stream_format.h"
 
 namespace limg_hip
@@ -41,20 +46,74 @@ namespace limg_hip
 
     // the lane's 8 pixels, columns x .. x + 7 of image row y, into the window: a piece wholly inside it as two 16-byte stores where the caller's buffer allows
     // them, else pixel by pixel; the caller has checked that y is a row of the window
-    __device__ __forceinline__ void store_row_piece(const WindowDecodeParams &p, uint32_t x, uint32_t y, const uint32_t px[8])
+    struct RgbaStore
     {
-      uint32_t *row = p.out + (unsigned long long)(y - p.y0) * p.outStride;
-      if (p.vecOut && x >= p.x0 && x + 8u <= p.x0 + p.width)
+      __device__ __forceinline__ void operator()(const WindowDecodeParams &p, uint32_t x, uint32_t y, const uint32_t px[8]) const
       {
-        uint4 *dst = reinterpret_cast<uint4 *>(row + (x - p.x0));
-        dst[0] = make_uint4(px[0], px[1], px[2], px[3]);
-        dst[1] = make_uint4(px[4], px[5], px[6], px[7]);
-        return;
-      }
+        uint32_t *row = p.out + (unsigned long long)(y - p.y0) * p.outStride;
+        if (p.vecOut && x >= p.x0 && x + 8u <= p.x0 + p.width)
+        {
+          uint4 *dst = reinterpret_cast<uint4 *>(row + (x - p.x0));
+          dst[0] = make_uint4(px[0], px[1], px[2], px[3]);
+          dst[1] = make_uint4(px[4], px[5], px[6], px[7]);
+          return;
+        }
 #pragma unroll
-      for (uint32_t i = 0; i < 8u; i++)
-        if (x + i >= p.x0 && x + i < p.x0 + p.width) row[x + i - p.x0] = px[i];
-    }
+        for (uint32_t i = 0; i < 8u; i++)
+          if (x + i >= p.x0 && x + i < p.x0 + p.width) row[x + i - p.x0] = px[i];
+      }
+    };
+
+    // The same 8 pixels into planes of T: plane c gets byte c of every pixel as (float)byte * scale[c] + bias[c] -- a multiply, then an add, each rounded on its own
+    // (the library is built without contraction) -- as it is (float) or rounded to nearest even (_Float16).  The inside / edge rule is RgbaStore's; a piece wholly
+    // inside leaves as 16 bytes per store, so the 8 lanes of a block row fill 256 (float, two stores) or 128 (_Float16, one) contiguous bytes of a plane row.
+    // The packed pixels are made opaque first: the compiler otherwise sees through the packing, keeps the 8 x 4 channel values of a16_pixel apart instead of the
+    // 8 pixels and needs 155 vector registers in version 1's kernel where the RGBA kernel has 99 -- a wave per SIMD less.  f: the call's format, wave-uniform.
+    typedef float float4v __attribute__((ext_vector_type(4)));
+    typedef _Float16 half8v __attribute__((ext_vector_type(8)));
+    template <class T>
+    struct PlanarStore
+    {
+      limg_hip_tensor_format f;
+      __device__ __forceinline__ void operator()(const WindowDecodeParams &p, uint32_t x, uint32_t y, const uint32_t px[8]) const
+      {
+        T *row = reinterpret_cast<T *>(p.out) + (unsigned long long)(y - p.y0) * p.outStride;
+        const bool whole = p.vecOut && x >= p.x0 && x + 8u <= p.x0 + p.width;
+        uint32_t q[8];
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++)
+        {
+          q[i] = px[i];
+          asm volatile("" : "+v"(q[i]));
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < 4u; c++)
+        {
+          if (c >= f.planes) break; // (wave-uniform)
+          float v[8];
+#pragma unroll
+          for (uint32_t i = 0; i < 8u; i++) v[i] = (float)((q[i] >> (8u * c)) & 0xFFu) * f.scale[c] + f.bias[c];
+          T *plane = row + (unsigned long long)c * p.planeStride;
+          if (whole)
+          {
+            if constexpr (sizeof(T) == 4)
+            {
+              float4v *dst = reinterpret_cast<float4v *>(plane + (x - p.x0));
+              dst[0] = float4v{ v[0], v[1], v[2], v[3] };
+              dst[1] = float4v{ v[4], v[5], v[6], v[7] };
+            }
+            else
+              *reinterpret_cast<half8v *>(plane + (x - p.x0)) = half8v{ (T)v[0], (T)v[1], (T)v[2], (T)v[3], (T)v[4], (T)v[5], (T)v[6], (T)v[7] };
+          }
+          else
+          {
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; i++)
+              if (x + i >= p.x0 && x + i < p.x0 + p.width) plane[x + i - p.x0] = (T)v[i];
+          }
+        }
+      }
+    };
 
     __device__ __forceinline__ void decode_row(const A16 &k, const unsigned long long packed[3], const uint32_t bb[3], uint32_t px[8])
     {
@@ -72,10 +131,10 @@ namespace limg_hip
     };
 
     // One unit of version 1: up to 64 consecutive blocks of block row `unit / unitsX` of p's window, by one wave.  S: the wave's LDS; payload, payloadWords, channels:
-    // from the (checked) header; raise(bits): how the caller reports a group that fails.  Everything but `lane` is wave-uniform.
-    template <class RAISE>
+    // from the (checked) header; raise(bits): how the caller reports a group that fails; store: how a lane's 8 pixels leave.  Everything but `lane` is wave-uniform.
+    template <class RAISE, class STORE>
     __device__ __forceinline__ void window_unit(const WindowDecodeParams &p, WindowWaveLds &S, uint32_t unit, uint32_t unitsX, int channels, unsigned long long payloadWords,
-                                                const uint2 *payload, int lane, RAISE &&raise)
+                                                const uint2 *payload, int lane, RAISE &&raise, const STORE &store)
     {
       const uint32_t j = (uint32_t)lane & 7u, r = (uint32_t)lane >> 3;
       unsigned long long *stage64 = reinterpret_cast<unsigned long long *>(S.stage);
@@ -160,7 +219,7 @@ namespace limg_hip
           const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(e[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, channels);
           uint32_t px[8];
           decode_row(k16, packed, bb, px);
-          store_row_piece(p, x, y, px);
+          store(p, x, y, px);
         }
         wave_lds_fence(); // every lane is done reading this group's run
       }
@@ -184,7 +243,7 @@ namespace limg_hip
       const uint2 *payload = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)p.nBlocks * kEntry);
       const uint32_t unitsX = (p.wbx + 63u) / 64u, nUnits = unitsX * p.wby;
       for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u) // (wave-uniform; nothing below synchronises across waves)
-        window_unit(p, S, unit, unitsX, channels, payloadWords, payload, lane, [&](uint32_t bits) { atomicOr(p.status, bits); });
+        window_unit(p, S, unit, unitsX, channels, payloadWords, payload, lane, [&](uint32_t bits) { atomicOr(p.status, bits); }, RgbaStore());
     }
 
     // ---- batch: the job table ---------------------------------------------------------------------------------------------------------
@@ -227,9 +286,9 @@ namespace limg_hip
       if (b.jobStatus) atomicOr(b.jobStatus + job, bits);
     }
 
-    __global__ __launch_bounds__(256) void k_stream_windows_decode(const WindowBatchParams b)
+    template <class STORE>
+    __device__ __forceinline__ void stream_windows_body(const WindowBatchParams &b, WindowWaveLds (&sW)[4], const STORE &store)
     {
-      __shared__ __align__(16) WindowWaveLds sW[4];
       const int lane = lane_id();
       const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
       WindowWaveLds &S = sW[wave];
@@ -244,8 +303,21 @@ namespace limg_hip
           continue;
         }
         const uint2 *payload = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)p.nBlocks * kEntry);
-        window_unit(p, S, unit - first, (p.wbx + 63u) / 64u, (int)h->channels, h->payloadWords, payload, lane, [&](uint32_t bits) { raise_job(b, job, bits); });
+        window_unit(p, S, unit - first, (p.wbx + 63u) / 64u, (int)h->channels, h->payloadWords, payload, lane, [&](uint32_t bits) { raise_job(b, job, bits); }, store);
       }
+    }
+
+    __global__ __launch_bounds__(256) void k_stream_windows_decode(const WindowBatchParams b)
+    {
+      __shared__ __align__(16) WindowWaveLds sW[4];
+      stream_windows_body(b, sW, RgbaStore());
+    }
+
+    template <class T>
+    __global__ __launch_bounds__(256) void k_stream_windows_tensor(const WindowBatchParams b, const limg_hip_tensor_format f)
+    {
+      __shared__ __align__(16) WindowWaveLds sW[4];
+      stream_windows_body(b, sW, PlanarStore<T>{ f });
     }
 
     // ---- version 2 -------------------------------------------------------------------------------------------------------------------
@@ -353,9 +425,10 @@ namespace limg_hip
     }
 
     // One unit of version 2: 8 consecutive blocks of block row `unit / unitsX` of p's window, lane = (block j = lane & 7, row = lane >> 3).  nRects, channels, tableEnd,
-    // total: from the header the map kernel has checked; the caller has read the verdict.
+    // total: from the header the map kernel has checked; the caller has read the verdict.  store: how a lane's 8 pixels leave.
+    template <class STORE>
     __device__ __forceinline__ void bwindow_unit(const WindowDecodeParams &p, uint32_t unit, uint32_t unitsX, uint32_t nRects, uint32_t channels, unsigned long long tableEnd,
-                                                 unsigned long long total, int lane)
+                                                 unsigned long long total, int lane, const STORE &store)
     {
       const uint32_t j = (uint32_t)lane & 7u, row = (uint32_t)lane >> 3;
       const uint32_t urow = unit / unitsX, wbxi = (unit - urow * unitsX) * 8u + j; // the block's place in the window's block range
@@ -396,7 +469,7 @@ namespace limg_hip
       const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(ev[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, (int)channels);
       uint32_t px[8];
       decode_row(k16, packed, bb, px);
-      store_row_piece(p, x, y, px); // (columns beyond a partial last block column lie outside the image, so outside the window)
+      store(p, x, y, px); // (columns beyond a partial last block column lie outside the image, so outside the window)
     }
 
     __global__ __launch_bounds__(256) void k_bstream_window_decode(const WindowDecodeParams p)
@@ -414,7 +487,7 @@ namespace limg_hip
       const uint32_t nRects = h.reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h.channels;
       const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h.payloadWords * 8ull;
       const uint32_t unitsX = (p.wbx + 7u) / 8u, nUnits = unitsX * p.wby;
-      for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u) bwindow_unit(p, unit, unitsX, nRects, channels, tableEnd, total, lane);
+      for (uint32_t unit = blockIdx.x * 4u + (uint32_t)wave; unit < nUnits; unit += gridDim.x * 4u) bwindow_unit(p, unit, unitsX, nRects, channels, tableEnd, total, lane, RgbaStore());
     }
 
     // ---- version 2, batch ------------------------------------------------------------------------------------------------------------
@@ -484,7 +557,8 @@ namespace limg_hip
       }
     }
 
-    __global__ __launch_bounds__(256) void k_bstream_windows_decode(const WindowBatchParams b)
+    template <class STORE>
+    __device__ __forceinline__ void bstream_windows_body(const WindowBatchParams &b, const STORE &store)
     {
       const int lane = lane_id();
       const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -501,9 +575,14 @@ namespace limg_hip
         const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
         const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h->channels;
         const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h->payloadWords * 8ull;
-        bwindow_unit(p, unit - first, (p.wbx + 7u) / 8u, nRects, channels, tableEnd, total, lane);
+        bwindow_unit(p, unit - first, (p.wbx + 7u) / 8u, nRects, channels, tableEnd, total, lane, store);
       }
     }
+
+    __global__ __launch_bounds__(256) void k_bstream_windows_decode(const WindowBatchParams b) { bstream_windows_body(b, RgbaStore()); }
+
+    template <class T>
+    __global__ __launch_bounds__(256) void k_bstream_windows_tensor(const WindowBatchParams b, const limg_hip_tensor_format f) { bstream_windows_body(b, PlanarStore<T>{ f }); }
   }
 
   // persistent launches: a workgroup of four waves per residency slot at most (version 1: 4 per CU at its 100 vector registers; version 2: 8), every wave strides over its units
@@ -536,5 +615,23 @@ namespace limg_hip
     hipLaunchKernelGGL(k_bstream_windows_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, b);
     const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u);
     hipLaunchKernelGGL(k_bstream_windows_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, b);
+  }
+
+  // the tensor forms: the same grids (f.type: checked by the host entry)
+  void launch_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s)
+  {
+    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u), slots = (uint32_t)cus * 4u;
+    if (f.type == LIMG_HIP_TENSOR_F16) hipLaunchKernelGGL(k_stream_windows_tensor<_Float16>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
+    else hipLaunchKernelGGL(k_stream_windows_tensor<float>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
+  }
+
+  void launch_blocked_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s)
+  {
+    const uint32_t slots = (uint32_t)cus * 8u;
+    const uint32_t needMap = b.totalItems / 4u + (b.totalItems % 4u ? 1u : 0u);
+    hipLaunchKernelGGL(k_bstream_windows_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, b);
+    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u);
+    if (f.type == LIMG_HIP_TENSOR_F16) hipLaunchKernelGGL(k_bstream_windows_tensor<_Float16>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
+    else hipLaunchKernelGGL(k_bstream_windows_tensor<float>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
   }
 }
