@@ -531,6 +531,85 @@ limg_hip_result limg_hip_decode_stream_windows_tensor(limg_hip_context *pCtx, co
 limg_hip_result limg_hip_blocked_decode_stream_windows_tensor(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows,
                                                               size_t count, const limg_hip_tensor_format *pFormat);
 
+/* ---- reduced-scale window decode: 1/2, 1/4, 1/8 windows, RGBA8 or planar float tensors -----------------------------------------
+ * What libjpeg's scale_num / 8 is to a JPEG: a loader that wants a 224 x 224 sample out of a 1792 x 1792 crop, or a viewer that wants level 3 of a pyramid, gets it
+ * from the decode itself, without the full-resolution intermediate and the pass that shrinks it.  Every job carries its own level log2Scale = L in {0, 1, 2, 3},
+ * k = 1 << L; the format and the encoder do not change.
+ * Reduced image: let P(x, y) be the pixel the version's full decoder writes for an image of sizeX x sizeY.  The level-L image has size RX = sizeX >> L, RY = sizeY >> L:
+ * trailing source columns and rows that do not fill a box are dropped.
+ * Reduced pixel: for each byte c = 0 .. 3 independently, with no alpha weighting,
+ *     Q_L(X, Y).byte[c] = (sum over 0 <= i, j < k of byte c of P(k X + i, k Y + j) + (k k >> 1)) >> 2L
+ * in integer arithmetic: the mean of the k x k box, round half up.  L = 0 is P itself.
+ * Window: x0, y0, width, height are in level-L coordinates, inside RX x RY, not empty, and need not be aligned to anything.
+ * RGBA form: pOut[r * outStridePixels + c] = Q_L(x0 + c, y0 + r).
+ * Tensor form: element (c, r, col) = (float)Q_L(x0 + col, y0 + r).byte[c] * scale[c] + bias[c], evaluated and rounded exactly as the tensor entries above state it: the
+ * result is their conversion applied to the RGBA form's result.
+ * NOTHING ELSE IS WRITTEN: per job the rules above for the stride slack, the gap between planes, planes at or beyond `planes` and the rows beyond the window.
+ * Store width: a reduced block row piece is 8 >> L pixels.  A piece of exactly 16 bytes -- level 1, RGBA8 or F32 -- that lies wholly inside the window leaves as one
+ * 16-byte store where pOut is 16-byte aligned and the strides and x0 (level coordinates) are multiples of 4; every other piece (level 1 F16, levels 2 and 3, pieces
+ * across the window's edge, other alignments) leaves element by element.  Level 0 jobs follow the rules of the entries above.  Identical results either way.
+ * Errors: the list and the order of the batched entries above (the tensor entries' for the tensor forms), plus: log2Scale > 3 is limg_hip_error_InvalidParameter,
+ * checked where the job's zero width or height is; a window that is not inside RX x RY is limg_hip_error_OutOfBounds -- any window when RX or RY is 0, that is on an
+ * image smaller than k.  The first failing job's error is returned and nothing is enqueued.
+ * Validation on the device, pJobStatus and the sticky status are the batched window decode's, stated on the job's source footprint (k x0, k y0, k width, k height):
+ * version 1: a group of 8 blocks that fails stores none of its output pixels, the job's other groups are stored; version 2: a job refused by the map kernel writes
+ * nothing.
+ * Cost and call rules, unchanged: ONE launch for version 1 and TWO for version 2 whatever `count` and whatever mix of levels; version 2 scans each distinct stream's
+ * table once per call; four calls in flight; not during graph capture.  Table entries and payload read are those of the footprint's block range; pixels stored are the
+ * window's (1 / 64 of the footprint's at level 3). */
+typedef struct limg_hip_scaled_window /* limg_hip_window and the level */
+{
+  size_t x0, y0, width, height; /* level-L pixels, inside (sizeX >> L) x (sizeY >> L), not empty */
+  uint32_t *pOut;               /* Q_L(x0 + c, y0 + r) at pOut[r * outStridePixels + c] */
+  size_t outStridePixels;
+  uint32_t log2Scale;           /* L: 0 .. 3 */
+} limg_hip_scaled_window;
+
+typedef struct limg_hip_scaled_window_job /* one window of one stream */
+{
+  const uint8_t *pStream; /* DEVICE, 16-byte aligned */
+  size_t streamBytes;
+  size_t sizeX, sizeY;    /* must match the stream's header */
+  limg_hip_scaled_window window; /* pOut: DEVICE, 4-byte aligned */
+} limg_hip_scaled_window_job;
+
+typedef struct limg_hip_scaled_tensor_window /* limg_hip_tensor_window and the level */
+{
+  size_t x0, y0, width, height;  /* level-L pixels, inside (sizeX >> L) x (sizeY >> L), not empty */
+  void *pOut;                    /* element (c, r, col) at pOut[c * planeStride + r * rowStride + col], in elements of the format's type */
+  size_t rowStride, planeStride; /* in elements */
+  uint32_t log2Scale;            /* L: 0 .. 3 */
+} limg_hip_scaled_tensor_window;
+
+typedef struct limg_hip_scaled_tensor_window_job /* one window of one stream */
+{
+  const uint8_t *pStream; /* DEVICE, 16-byte aligned */
+  size_t streamBytes;
+  size_t sizeX, sizeY;    /* must match the stream's header */
+  limg_hip_scaled_tensor_window window; /* pOut: DEVICE, aligned to the element size */
+} limg_hip_scaled_tensor_window_job;
+
+/* DEVICE pointers inside the jobs; pJobs and pFormat are HOST memory and may be reused or freed when the call returns.  Asynchronous on `stream`. */
+limg_hip_result limg_hip_decode_stream_windows_scaled_device(limg_hip_context *pCtx, const limg_hip_scaled_window_job *pJobs, size_t count, uint32_t *pJobStatus,
+                                                             void *stream);
+limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_device(limg_hip_context *pCtx, const limg_hip_scaled_window_job *pJobs, size_t count, uint32_t *pJobStatus,
+                                                                     void *stream);
+limg_hip_result limg_hip_decode_stream_windows_scaled_tensor_device(limg_hip_context *pCtx, const limg_hip_scaled_tensor_window_job *pJobs, size_t count,
+                                                                    const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream);
+limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor_device(limg_hip_context *pCtx, const limg_hip_scaled_tensor_window_job *pJobs, size_t count,
+                                                                            const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream);
+/* HOST pointers, blocking, under the context's mutex: `count` windows of ONE stream, every window at its own level -- all levels of a pyramid, or all tiles of one
+ * level, from one upload and one batched call.  Staging as in the host forms above, per reduced window pixel; a stream refused for any window leaves EVERY pOut untouched,
+ * in both versions. */
+limg_hip_result limg_hip_decode_stream_windows_scaled(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_window *pWindows,
+                                                      size_t count);
+limg_hip_result limg_hip_blocked_decode_stream_windows_scaled(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_window *pWindows,
+                                                              size_t count);
+limg_hip_result limg_hip_decode_stream_windows_scaled_tensor(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes,
+                                                             const limg_hip_scaled_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat);
+limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes,
+                                                                     const limg_hip_scaled_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ---------------------------------------------------------------------------------
  * The reference's only parallelism is row strips over a std::thread pool (src/limg.cpp:2105-2138); across GPUs the same strips
  * go one per rank.  Blocks are independent except for the dither chain, so the data path needs no collective in strip-restart mode (each strip

@@ -266,4 +266,25 @@ inline limg_result limg_decode_windows_tensor(const uint8_t *pIn, const size_t s
   return (limg_result)limg_hip_decode_stream_windows_tensor(c, pIn, size, pWindows, count, pFormat);
 }
 
+// ... at reduced scale (limg_hip.h "reduced-scale window decode"): every window carries its level log2Scale = 0 .. 3 and is stated in that level's coordinates; pixel
+// (X, Y) of level L is the rounded mean of the (1 << L)^2 box at ((X << L), (Y << L)).  All levels of a pyramid come from one upload and one batched call.
+inline limg_result limg_decode_windows_scaled(const uint8_t *pIn, const size_t size, const limg_hip_scaled_window *pWindows, const size_t count)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (limg_hip_blocked_stream_info(pIn, size, nullptr, nullptr, nullptr, nullptr, nullptr) == limg_hip_success)
+    return (limg_result)limg_hip_blocked_decode_stream_windows_scaled(c, pIn, size, pWindows, count);
+  return (limg_result)limg_hip_decode_stream_windows_scaled(c, pIn, size, pWindows, count);
+}
+
+inline limg_result limg_decode_windows_scaled_tensor(const uint8_t *pIn, const size_t size, const limg_hip_scaled_tensor_window *pWindows, const size_t count,
+                                                     const limg_hip_tensor_format *pFormat)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (limg_hip_blocked_stream_info(pIn, size, nullptr, nullptr, nullptr, nullptr, nullptr) == limg_hip_success)
+    return (limg_result)limg_hip_blocked_decode_stream_windows_scaled_tensor(c, pIn, size, pWindows, count, pFormat);
+  return (limg_result)limg_hip_decode_stream_windows_scaled_tensor(c, pIn, size, pWindows, count, pFormat);
+}
+
 #endif // LIMG_HIP_SHIM_HPP

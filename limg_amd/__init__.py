@@ -34,6 +34,9 @@ ABI_SYMBOLS = (
     "limg_hip_decode_stream_windows_device", "limg_hip_blocked_decode_stream_windows_device", "limg_hip_decode_stream_windows", "limg_hip_blocked_decode_stream_windows",
     "limg_hip_decode_stream_windows_tensor_device", "limg_hip_blocked_decode_stream_windows_tensor_device", "limg_hip_decode_stream_windows_tensor",
     "limg_hip_blocked_decode_stream_windows_tensor",
+    "limg_hip_decode_stream_windows_scaled_device", "limg_hip_blocked_decode_stream_windows_scaled_device", "limg_hip_decode_stream_windows_scaled_tensor_device",
+    "limg_hip_blocked_decode_stream_windows_scaled_tensor_device", "limg_hip_decode_stream_windows_scaled", "limg_hip_blocked_decode_stream_windows_scaled",
+    "limg_hip_decode_stream_windows_scaled_tensor", "limg_hip_blocked_decode_stream_windows_scaled_tensor",
     "limg_hip_blocked_encode3d", "limg_hip_blocked_encode3d_device", "limg_hip_blocked_regions", "limg_hip_blocked_timing", "limg_hip_blocked_kernel_timing", "limg_hip_blocked_match_bits", "limg_hip_host_blocked_matches",
     "limg_hip_host_blocked_merge", "limg_hip_host_blocked_match_words", "limg_hip_host_blocked_match_bits",
     "limg_hip_comm_unique_id", "limg_hip_comm_init", "limg_hip_comm_destroy", "limg_hip_comm_info", "limg_hip_gather_stream", "limg_hip_encode3d_single_chain_device",
@@ -102,6 +105,26 @@ class TensorWindow(C.Structure):
 class TensorWindowJob(C.Structure):
     """limg_hip_tensor_window_job: one window of one stream"""
     _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", TensorWindow)]
+
+
+class ScaledWindow(C.Structure):
+    """limg_hip_scaled_window: limg_hip_window and the level"""
+    _fields_ = Window._fields_ + [("log2Scale", C.c_uint32)]
+
+
+class ScaledWindowJob(C.Structure):
+    """limg_hip_scaled_window_job: one window of one stream"""
+    _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", ScaledWindow)]
+
+
+class ScaledTensorWindow(C.Structure):
+    """limg_hip_scaled_tensor_window: limg_hip_tensor_window and the level"""
+    _fields_ = TensorWindow._fields_ + [("log2Scale", C.c_uint32)]
+
+
+class ScaledTensorWindowJob(C.Structure):
+    """limg_hip_scaled_tensor_window_job: one window of one stream"""
+    _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", ScaledTensorWindow)]
 
 
 def tensor_format(dtype, planes, scale, bias):
@@ -256,6 +279,18 @@ def load_library(path=None):
         getattr(L, name).restype = C.c_int  # ctx, jobs (host), count, format (host), jobStatus (device), hipStream
         getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in ("limg_hip_decode_stream_windows_tensor", "limg_hip_blocked_decode_stream_windows_tensor"):
+        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count, format (host)
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    for name in ("limg_hip_decode_stream_windows_scaled_device", "limg_hip_blocked_decode_stream_windows_scaled_device"):
+        getattr(L, name).restype = C.c_int  # ctx, jobs (host), count, jobStatus (device), hipStream
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    for name in ("limg_hip_decode_stream_windows_scaled", "limg_hip_blocked_decode_stream_windows_scaled"):
+        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    for name in ("limg_hip_decode_stream_windows_scaled_tensor_device", "limg_hip_blocked_decode_stream_windows_scaled_tensor_device"):
+        getattr(L, name).restype = C.c_int  # ctx, jobs (host), count, format (host), jobStatus (device), hipStream
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name in ("limg_hip_decode_stream_windows_scaled_tensor", "limg_hip_blocked_decode_stream_windows_scaled_tensor"):
         getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count, format (host)
         getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     L.limg_hip_blocked_last_stream.restype = C.c_int
@@ -824,6 +859,109 @@ class LimgHip:
         assert tuple(out.shape) == (len(jobs), planes, h, w) and out.is_contiguous() and out.dtype == dtype
         table = [(stream, nbytes, W, H, x, y, w, h, out[i], w, h * w) for i, (stream, nbytes, W, H, x, y) in enumerate(jobs)]
         (self.blocked_decode_stream_windows_tensor_device if blocked else self.decode_stream_windows_tensor_device)(table, fmt)
+        return out
+
+    # ---- reduced-scale window decode: every job at its own level 0 .. 3, RGBA8 or tensors (contract: include/limg_hip.h) ----
+    def _decode_stream_windows_scaled_device(self, name, jobs, status):
+        import torch
+        table = (ScaledWindowJob * len(jobs))()
+        outs = []
+        for i, (stream, nbytes, W, H, level, x, y, w, h, out, out_stride) in enumerate(jobs):
+            if out is None:
+                out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
+            if out_stride is None:
+                out_stride = out.stride(0) if out.dim() == 2 else w
+            table[i] = ScaledWindowJob(stream.data_ptr(), int(nbytes), W, H, ScaledWindow(x, y, w, h, out.data_ptr(), int(out_stride), level))
+            outs.append(out)
+        self._stream_call(name, table, len(jobs), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
+        return outs
+
+    def _decode_stream_windows_scaled_tensor_device(self, name, jobs, fmt, status):
+        import torch
+        dtype = torch.float16 if fmt.type == TENSOR_F16 else torch.float32
+        table = (ScaledTensorWindowJob * len(jobs))()
+        outs = []
+        for i, (stream, nbytes, W, H, level, x, y, w, h, out, row_stride, plane_stride) in enumerate(jobs):
+            if out is None:
+                out = torch.empty((fmt.planes, h, w), dtype=dtype, device=stream.device)
+            assert out.dtype == dtype, (out.dtype, dtype)
+            if row_stride is None:
+                row_stride = out.stride(1) if out.dim() == 3 else w
+            if plane_stride is None:
+                plane_stride = out.stride(0) if out.dim() == 3 else row_stride * h
+            table[i] = ScaledTensorWindowJob(stream.data_ptr(), int(nbytes), W, H, ScaledTensorWindow(x, y, w, h, out.data_ptr(), int(row_stride), int(plane_stride), level))
+            outs.append(out)
+        self._stream_call(name, table, len(jobs), C.byref(fmt), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
+        return outs
+
+    def _decode_stream_windows_scaled(self, name, stream, wins, outs):
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        outs = [None] * len(wins) if outs is None else list(outs)
+        table = (ScaledWindow * len(wins))()
+        for i, (level, x, y, w, h) in enumerate(wins):
+            if outs[i] is None:
+                outs[i] = np.zeros((h, w), dtype=np.uint32)
+            out = outs[i]
+            assert out.dtype == np.uint32 and out.ndim == 2 and out.strides[1] == 4 and out.strides[0] % 4 == 0, "out: uint32 rows, pixels contiguous"
+            table[i] = ScaledWindow(x, y, w, h, out.ctypes.data, out.strides[0] // 4, level)
+        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins))
+        return outs
+
+    def _decode_stream_windows_scaled_tensor(self, name, stream, wins, fmt, outs):
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        dtype = np.float16 if fmt.type == TENSOR_F16 else np.float32
+        eb = np.dtype(dtype).itemsize
+        outs = [None] * len(wins) if outs is None else list(outs)
+        table = (ScaledTensorWindow * len(wins))()
+        for i, (level, x, y, w, h) in enumerate(wins):
+            if outs[i] is None:
+                outs[i] = np.zeros((fmt.planes, h, w), dtype=dtype)
+            out = outs[i]
+            assert out.dtype == dtype and out.ndim == 3 and out.shape[0] >= fmt.planes and out.strides[2] == eb and out.strides[1] % eb == 0 and out.strides[0] % eb == 0, \
+                "out: (planes, h, w) of the format's type, elements of a row contiguous"
+            table[i] = ScaledTensorWindow(x, y, w, h, out.ctypes.data, out.strides[1] // eb, out.strides[0] // eb, level)
+        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins), C.byref(fmt))
+        return outs
+
+    def decode_stream_windows_scaled_device(self, jobs, status=None):
+        """jobs: (stream tensor, nbytes, W, H, level, x, y, w, h, out, out_stride) each: the jobs of decode_stream_windows_device with the level 0 .. 3 behind the image
+        size; x, y, w, h are in that level's coordinates, inside (W >> level) x (H >> level).  One launch whatever the mix of levels."""
+        return self._decode_stream_windows_scaled_device("limg_hip_decode_stream_windows_scaled_device", jobs, status)
+
+    def blocked_decode_stream_windows_scaled_device(self, jobs, status=None):
+        return self._decode_stream_windows_scaled_device("limg_hip_blocked_decode_stream_windows_scaled_device", jobs, status)
+
+    def decode_stream_windows_scaled_tensor_device(self, jobs, fmt, status=None):
+        """jobs: (stream tensor, nbytes, W, H, level, x, y, w, h, out, row_stride, plane_stride) each, as decode_stream_windows_tensor_device with the level"""
+        return self._decode_stream_windows_scaled_tensor_device("limg_hip_decode_stream_windows_scaled_tensor_device", jobs, fmt, status)
+
+    def blocked_decode_stream_windows_scaled_tensor_device(self, jobs, fmt, status=None):
+        return self._decode_stream_windows_scaled_tensor_device("limg_hip_blocked_decode_stream_windows_scaled_tensor_device", jobs, fmt, status)
+
+    def decode_stream_windows_scaled(self, stream, wins, outs=None):
+        """host stream bytes, wins: (level, x, y, w, h) each -> the list of numpy uint32 (h, w) arrays; one upload and one batched call for all levels"""
+        return self._decode_stream_windows_scaled("limg_hip_decode_stream_windows_scaled", stream, wins, outs)
+
+    def blocked_decode_stream_windows_scaled(self, stream, wins, outs=None):
+        return self._decode_stream_windows_scaled("limg_hip_blocked_decode_stream_windows_scaled", stream, wins, outs)
+
+    def decode_stream_windows_scaled_tensor(self, stream, wins, fmt, outs=None):
+        """host stream bytes, wins: (level, x, y, w, h) each -> the list of numpy (planes, h, w) arrays of fmt's type"""
+        return self._decode_stream_windows_scaled_tensor("limg_hip_decode_stream_windows_scaled_tensor", stream, wins, fmt, outs)
+
+    def blocked_decode_stream_windows_scaled_tensor(self, stream, wins, fmt, outs=None):
+        return self._decode_stream_windows_scaled_tensor("limg_hip_blocked_decode_stream_windows_scaled_tensor", stream, wins, fmt, outs)
+
+    def decode_crops_scaled_device(self, jobs, h, w, dtype, scale, bias, planes=3, blocked=False, out=None):
+        """The loader step where every sample picks its own level: jobs: (stream tensor, nbytes, W, H, level, x, y) each -- the h x w crop at (x, y) of the stream's
+        level-`level` image -> ONE contiguous (N, planes, h, w) torch tensor of `dtype`, as decode_crops_device.  One call of the version's scaled tensor entry."""
+        import torch
+        fmt = tensor_format(dtype, planes, scale, bias)
+        if out is None:
+            out = torch.empty((len(jobs), planes, h, w), dtype=dtype, device=jobs[0][0].device)
+        assert tuple(out.shape) == (len(jobs), planes, h, w) and out.is_contiguous() and out.dtype == dtype
+        table = [(stream, nbytes, W, H, level, x, y, w, h, out[i], w, h * w) for i, (stream, nbytes, W, H, level, x, y) in enumerate(jobs)]
+        (self.blocked_decode_stream_windows_scaled_tensor_device if blocked else self.decode_stream_windows_scaled_tensor_device)(table, fmt)
         return out
 
     def check(self):

@@ -229,6 +229,9 @@ namespace limg_hip
     uint32_t *out;                  // pixel (x0 + c, y0 + r) at out[r * outStride + c]
     unsigned long long outStride;
     uint32_t vecOut;                // a block row piece that lies wholly inside the window may leave as two 16-byte stores (out 16-byte aligned, outStride % 4 == 0, x0 % 4 == 0)
+    uint32_t log2Scale;             // the *_scaled entries (0 everywhere else; it lies in what was padding, so the struct's layout is what it was): level L.  x0 .. wby above then
+                                    // describe the job's SOURCE FOOTPRINT, multiples of k = 1 << L; the output window is (x0 >> L, y0 >> L, width >> L, height >> L), whose pixel
+                                    // (x0 >> L, y0 >> L) goes to out[0]; vecOut is stated on x0 >> L
     uint32_t *map;                  // version 2: per block of the window the rectangle that covers it (~0: none yet)
     uint32_t *status;               // the context's sticky stream status word, bits as in DecodeParams
     uint32_t *state;                // version 2: this call's words (zeroed in front of it): [0] window blocks claimed, [1] non-0 = the stream is refused
@@ -270,6 +273,10 @@ namespace limg_hip
   // ... into planar float tensors: the same job table (planeStride set, out / outStride / vecOut in elements of f.type), one format per launch
   void launch_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s);
   void launch_blocked_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s);
+  // ... at reduced scale (the *_scaled entries): kernels of their own that honour every job's log2Scale; f: the tensor format, or NULL for packed RGBA8
+  void launch_stream_windows_scaled(const WindowBatchParams &b, const limg_hip_tensor_format *f, int cus, hipStream_t s);
+  void launch_blocked_stream_windows_scaled(const WindowBatchParams &b, const limg_hip_tensor_format *f, int cus, hipStream_t s);
+  static_assert(sizeof(WindowDecodeParams) == 128, "the job table's entry: log2Scale must not grow it");
 
   void launch_stream_pack(const StreamParams &p, hipStream_t s);
   void launch_stream_pack_batch(const StreamBatchParams &b, hipStream_t s);                                                  // one scan launch + one pack launch, whatever nImages is

@@ -148,6 +148,21 @@ namespace
   {
     return { w.pOut, w.rowStride, w.planeStride, f->type == LIMG_HIP_TENSOR_F16 ? 2u : 4u, f->planes };
   }
+  WindowOut window_out(const limg_hip_scaled_window &w, const limg_hip_tensor_format *) { return { w.pOut, w.outStridePixels, 0, 4u, 0u }; }
+  WindowOut window_out(const limg_hip_scaled_tensor_window &w, const limg_hip_tensor_format *f)
+  {
+    return { w.pOut, w.rowStride, w.planeStride, f->type == LIMG_HIP_TENSOR_F16 ? 2u : 4u, f->planes };
+  }
+  // the four window types: which go to planes, which carry a level (the others are level 0)
+  template <class WIN> struct WindowKind { static constexpr bool tensor = false, scaled = false; };
+  template <> struct WindowKind<limg_hip_tensor_window> { static constexpr bool tensor = true, scaled = false; };
+  template <> struct WindowKind<limg_hip_scaled_window> { static constexpr bool tensor = false, scaled = true; };
+  template <> struct WindowKind<limg_hip_scaled_tensor_window> { static constexpr bool tensor = true, scaled = true; };
+  template <class WIN> size_t window_level(const WIN &w)
+  {
+    if constexpr (WindowKind<WIN>::scaled) return w.log2Scale;
+    else return 0;
+  }
   bool tensor_format_ok(const limg_hip_tensor_format *f) { return (f->type == LIMG_HIP_TENSOR_F32 || f->type == LIMG_HIP_TENSOR_F16) && (f->planes == 3u || f->planes == 4u); }
 
   // the window's size and the output's strides: what every window entry, device or host, checks first
@@ -168,13 +183,16 @@ namespace
   }
 
   // the checks and the parameters the two versions share, without touching the device; `bound`: the version's limg_hip_*stream_bound(sizeX, sizeY).  status, map and
-  // state are the caller's to set.
+  // state are the caller's to set.  level: the scaled entries' log2Scale -- the window is then in level coordinates, inside (sizeX >> level) x (sizeY >> level), and wp
+  // gets its source footprint (x0 .. height times 1 << level: inside the image, so nothing overflows) with vecOut stated on the window itself.
   limg_hip_result window_fill(const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width, size_t height,
-                              const WindowOut &o, WindowDecodeParams &wp)
+                              const WindowOut &o, WindowDecodeParams &wp, size_t level = 0)
   {
-    if (window_out_check(width, height, o) != limg_hip_success || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
+    if (level > 3 || window_out_check(width, height, o) != limg_hip_success || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
     if (((uintptr_t)pStream & 15u) != 0 || !out_aligned(o)) return limg_hip_error_InvalidParameter;
-    if (!window_inside(sizeX, sizeY, x0, y0, width, height)) return limg_hip_error_OutOfBounds;
+    if (!window_inside(sizeX >> level, sizeY >> level, x0, y0, width, height)) return limg_hip_error_OutOfBounds;
+    const size_t outX0 = x0;
+    x0 <<= level; y0 <<= level; width <<= level; height <<= level;
     memset(&wp, 0, sizeof(wp));
     wp.sizeX = (uint32_t)sizeX; wp.sizeY = (uint32_t)sizeY;
     wp.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); wp.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
@@ -185,7 +203,8 @@ namespace
     wp.wbx = (uint32_t)((x0 + width - 1) / kBlock) - wp.bx0 + 1; wp.wby = (uint32_t)((y0 + height - 1) / kBlock) - wp.by0 + 1;
     wp.out = (uint32_t *)o.p; wp.outStride = o.rowStride; wp.planeStride = o.planeStride;
     const size_t per = 16u / o.elemBytes; // elements per 16-byte store (planeStride is 0 for RGBA)
-    wp.vecOut = ((uintptr_t)o.p & 15u) == 0 && o.rowStride % per == 0 && o.planeStride % per == 0 && x0 % per == 0;
+    wp.vecOut = ((uintptr_t)o.p & 15u) == 0 && o.rowStride % per == 0 && o.planeStride % per == 0 && outX0 % per == 0;
+    wp.log2Scale = (uint32_t)level;
     return limg_hip_success;
   }
 
@@ -245,12 +264,14 @@ namespace
 
   // One call: every job checked on the host before anything touches the device, then the job table built in a pinned slot of the context's ring, copied on `s`,
   // and the version's one (two) launches.  blocked: version 2.  JOB: limg_hip_window_job (packed RGBA8; pFormat is not looked at) or limg_hip_tensor_window_job
-  // (planes of pFormat's type): the same checks, table and launches but for where the pixels go.
+  // (planes of pFormat's type): the same checks, table and launches but for where the pixels go; their _scaled_ twins: the same again with the job's level handed to
+  // window_fill and the scaled kernels launched.
   template <class JOB>
   limg_hip_result decode_windows_device(limg_hip_context *c, const JOB *pJobs, size_t count, const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, hipStream_t s,
                                         bool blocked)
   {
-    constexpr bool tensor = std::is_same<JOB, limg_hip_tensor_window_job>::value;
+    typedef decltype(JOB::window) WIN;
+    constexpr bool tensor = WindowKind<WIN>::tensor, scaled = WindowKind<WIN>::scaled;
     if (!c || !pJobs || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
     if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
     if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
@@ -263,7 +284,7 @@ namespace
       if (!j.pStream || !j.window.pOut) return limg_hip_error_ArgumentNull;
       const size_t bound = blocked ? limg_hip_blocked_stream_bound(j.sizeX, j.sizeY) : limg_hip_stream_bound(j.sizeX, j.sizeY);
       const limg_hip_result r = window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height,
-                                            window_out(j.window, pFormat), wp);
+                                            window_out(j.window, pFormat), wp, window_level(j.window));
       if (r != limg_hip_success) return r;
       if (!blocked && j.streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
       units += (unsigned long long)((wp.wbx + (blocked ? 7u : 63u)) / (blocked ? 8u : 64u)) * wp.wby;
@@ -299,7 +320,8 @@ namespace
     {
       const JOB &j = pJobs[i];
       const size_t bound = blocked ? limg_hip_blocked_stream_bound(j.sizeX, j.sizeY) : limg_hip_stream_bound(j.sizeX, j.sizeY);
-      (void)window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height, window_out(j.window, pFormat), jobs[i]);
+      (void)window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height, window_out(j.window, pFormat), jobs[i],
+                        window_level(j.window));
       jobs[i].status = (uint32_t *)c->streamStatus.p;
       if (blocked)
       {
@@ -360,7 +382,12 @@ namespace
       HIP_TRY(hipMemsetAsync(db + oMap, 0xFF, (size_t)blocks * 4, s)); // no block has a rectangle yet
     }
     if (pJobStatus) HIP_TRY(hipMemsetAsync(pJobStatus, 0, count * 4, s));
-    if (tensor)
+    if (scaled)
+    {
+      if (blocked) launch_blocked_stream_windows_scaled(b, tensor ? pFormat : nullptr, device_cus(c), s);
+      else launch_stream_windows_scaled(b, tensor ? pFormat : nullptr, device_cus(c), s);
+    }
+    else if (tensor)
     {
       if (blocked) launch_blocked_stream_windows_tensor(b, *pFormat, device_cus(c), s);
       else launch_stream_windows_tensor(b, *pFormat, device_cus(c), s);
@@ -376,16 +403,21 @@ namespace
   // the staged form of a window: densely packed in context memory
   void stage_window(limg_hip_window &w, void *p) { w.pOut = (uint32_t *)p; w.outStridePixels = w.width; }
   void stage_window(limg_hip_tensor_window &w, void *p) { w.pOut = p; w.rowStride = w.width; w.planeStride = w.width * w.height; }
+  void stage_window(limg_hip_scaled_window &w, void *p) { w.pOut = (uint32_t *)p; w.outStridePixels = w.width; }
+  void stage_window(limg_hip_scaled_tensor_window &w, void *p) { w.pOut = p; w.rowStride = w.width; w.planeStride = w.width * w.height; }
   template <class WIN> struct JobOf { typedef limg_hip_window_job type; };
   template <> struct JobOf<limg_hip_tensor_window> { typedef limg_hip_tensor_window_job type; };
+  template <> struct JobOf<limg_hip_scaled_window> { typedef limg_hip_scaled_window_job type; };
+  template <> struct JobOf<limg_hip_scaled_tensor_window> { typedef limg_hip_scaled_tensor_window_job type; };
 
-  // `count` windows of ONE host stream.  info(&sizeX, &sizeY, &total): the version's header check.  WIN: limg_hip_window or limg_hip_tensor_window (with pFormat).
+  // `count` windows of ONE host stream.  info(&sizeX, &sizeY, &total): the version's header check.  WIN: limg_hip_window or limg_hip_tensor_window (with pFormat), or
+  // their _scaled_ twins: every window then carries its level and is stated, checked and staged in that level's coordinates.
   template <class WIN, class INFO>
   limg_hip_result decode_windows_host(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const WIN *pWindows, size_t count,
                                       const limg_hip_tensor_format *pFormat, bool blocked, INFO &&info)
   {
     typedef typename JobOf<WIN>::type JOB;
-    constexpr bool tensor = std::is_same<WIN, limg_hip_tensor_window>::value;
+    constexpr bool tensor = WindowKind<WIN>::tensor;
     if (!c || !pStream || !pWindows || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
     if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
@@ -394,6 +426,7 @@ namespace
     {
       const WIN &w = pWindows[i];
       if (!w.pOut) return limg_hip_error_ArgumentNull;
+      if (window_level(w) > 3) return limg_hip_error_InvalidParameter;
       const limg_hip_result ok = window_out_check(w.width, w.height, window_out(w, pFormat));
       if (ok != limg_hip_success) return ok;
       if (tensor && !out_aligned(window_out(w, pFormat))) return limg_hip_error_InvalidParameter;
@@ -408,7 +441,7 @@ namespace
     for (size_t i = 0; i < count; i++)
     {
       const WIN &w = pWindows[i];
-      if (!window_inside(sizeX, sizeY, w.x0, w.y0, w.width, w.height)) return limg_hip_error_OutOfBounds;
+      if (!window_inside(sizeX >> window_level(w), sizeY >> window_level(w), w.x0, w.y0, w.width, w.height)) return limg_hip_error_OutOfBounds;
       elems += (planes * w.width * w.height + per - 1) / per * per;
     }
     JOB *jobs = new (std::nothrow) JOB[count];
@@ -870,6 +903,57 @@ extern "C"
 
   limg_hip_result limg_hip_blocked_decode_stream_windows_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows,
                                                                 size_t count, const limg_hip_tensor_format *pFormat)
+  {
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, pFormat, true,
+                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });
+  }
+
+  // ---- reduced-scale window decode, both versions, RGBA8 and tensors: the job types with a level ----
+  limg_hip_result limg_hip_decode_stream_windows_scaled_device(limg_hip_context *c, const limg_hip_scaled_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
+  {
+    return decode_windows_device(c, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, false);
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_device(limg_hip_context *c, const limg_hip_scaled_window_job *pJobs, size_t count, uint32_t *pJobStatus,
+                                                                       void *stream)
+  {
+    return decode_windows_device(c, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, true);
+  }
+
+  limg_hip_result limg_hip_decode_stream_windows_scaled_tensor_device(limg_hip_context *c, const limg_hip_scaled_tensor_window_job *pJobs, size_t count,
+                                                                      const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
+  {
+    return decode_windows_device(c, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream, false);
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor_device(limg_hip_context *c, const limg_hip_scaled_tensor_window_job *pJobs, size_t count,
+                                                                              const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
+  {
+    return decode_windows_device(c, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream, true);
+  }
+
+  limg_hip_result limg_hip_decode_stream_windows_scaled(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_window *pWindows, size_t count)
+  {
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, nullptr, false,
+                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); });
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_window *pWindows,
+                                                                size_t count)
+  {
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, nullptr, true,
+                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });
+  }
+
+  limg_hip_result limg_hip_decode_stream_windows_scaled_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_tensor_window *pWindows,
+                                                               size_t count, const limg_hip_tensor_format *pFormat)
+  {
+    return decode_windows_host(c, pStream, streamBytes, pWindows, count, pFormat, false,
+                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); });
+  }
+
+  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes,
+                                                                       const limg_hip_scaled_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat)
   {
     return decode_windows_host(c, pStream, streamBytes, pWindows, count, pFormat, true,
                                [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });

@@ -33,6 +33,11 @@
 // bwindow_unit: RgbaStore is the packed store of every kernel above; PlanarStore<T> (T = float / _Float16) writes byte c of each pixel as scale[c] * byte + bias[c]
 // into plane c, `planes` planes.  k_stream_windows_tensor<T> and k_bstream_windows_tensor<T> are k_stream_windows_decode and k_bstream_windows_decode with it;
 // k_bstream_windows_map never touches the output and serves both.  The format is a kernel argument: scale and bias stay in scalar registers.
+//
+// Scaled forms (limg_hip_*decode_stream_windows_scaled*): the batched kernels with ScaledStore<RgbaStore> / ScaledStore<PlanarStore<T>>, kernels of their own
+// (k_stream_windows_scaled[_tensor<T>], k_bstream_windows_scaled[_tensor<T>]).  A job's level L rides in its WindowDecodeParams, whose window is then the SOURCE
+// footprint: units, validation and the map kernel see a plain window; only the store differs -- k x k box sums inside the 8x8 block (in the lane along x, across
+// the lanes 8, 16 and 32 away along y), rounded and stored by the lane of each box's first row.  Nothing is gathered across blocks (DESIGN.md says why).
 #include "limg_hip_stream_format.h"
 
 namespace limg_hip
@@ -111,6 +116,126 @@ namespace limg_hip
             for (uint32_t i = 0; i < 8u; i++)
               if (x + i >= p.x0 && x + i < p.x0 + p.width) plane[x + i - p.x0] = (T)v[i];
           }
+        }
+      }
+    };
+
+    // ---- reduced scale (the *_scaled entries): the job's level L, k = 1 << L -------------------------------------------------------------
+    // p describes the job's source footprint, multiples of k; output pixel (X, Y) is the rounded mean of the k x k box at (k X, k Y), byte by byte.  A box never leaves
+    // its 8x8 block: its columns are k of the lane's 8 pixels, its rows the same pixels of the lanes 8, 16 and 32 away (lane = block j + 8 * row).  Two bytes of a
+    // pixel travel per dword (bytes 0 / 2 in lo, 1 / 3 in hi): the largest sum, 64 * 255 + 32, fits in 16 bits.
+    // Lanes that exchange sums belong to one block and one row of boxes.  Which lanes reach a store is decided per block (its place in the unit and in the window's
+    // columns, its group's verdict) and per image row against the footprint's rows, which are whole boxes: such lanes are inside or outside together, so no read
+    // below names a lane that is not here.
+    // The partners: lane ^ 8 through DPP row_ror:8 (a rotation by 8 within the row of 16 lanes; it folds into the add: one instruction per dword), lane ^ 16 through
+    // __shfl_xor (ds_bpermute_b32, one address for all dwords), lane ^ 32 through v_permlane32_swap of the dword with a copy of itself: one half of each result
+    // register is the lane's own sum, the other the partner's (2 instructions per dword where __shfl_xor takes a ds_bpermute_b32, its wait and the add).
+    __device__ __forceinline__ uint32_t add_lane_xor8(uint32_t v) { return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128 /* row_ror:8 */, 0xF, 0xF, false); }
+    __device__ __forceinline__ uint32_t add_lane_xor16(uint32_t v) { return v + (uint32_t)__shfl_xor((int)v, 16, 64); }
+    __device__ __forceinline__ uint32_t add_lane_xor32(uint32_t v)
+    {
+      const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+      return (uint32_t)r[0] + (uint32_t)r[1];
+    }
+
+    // N = 8 >> L reduced pixels of output row Y, columns X .. X + N - 1, into the window.  Store width: a piece of exactly 16 bytes (level 1, RGBA8 and float) that lies
+    // wholly inside the window leaves as one 16-byte store where vecOut allows it (X is a multiple of 4 there); every other piece element by element.
+    template <uint32_t L>
+    __device__ __forceinline__ void store_reduced(const RgbaStore &, const WindowDecodeParams &p, uint32_t X, uint32_t Y, const uint32_t (&q)[8u >> L])
+    {
+      constexpr uint32_t N = 8u >> L;
+      const uint32_t X0 = p.x0 >> L, W = p.width >> L;
+      uint32_t *row = p.out + (unsigned long long)(Y - (p.y0 >> L)) * p.outStride;
+      if constexpr (N == 4u)
+        if (p.vecOut && X >= X0 && X + 4u <= X0 + W)
+        {
+          *reinterpret_cast<uint4 *>(row + (X - X0)) = make_uint4(q[0], q[1], q[2], q[3]);
+          return;
+        }
+#pragma unroll
+      for (uint32_t i = 0; i < N; i++)
+        if (X + i >= X0 && X + i < X0 + W) row[X + i - X0] = q[i];
+    }
+
+    template <uint32_t L, class T>
+    __device__ __forceinline__ void store_reduced(const PlanarStore<T> &s, const WindowDecodeParams &p, uint32_t X, uint32_t Y, const uint32_t (&q)[8u >> L])
+    {
+      constexpr uint32_t N = 8u >> L;
+      const uint32_t X0 = p.x0 >> L, W = p.width >> L;
+      T *row = reinterpret_cast<T *>(p.out) + (unsigned long long)(Y - (p.y0 >> L)) * p.outStride;
+      const bool whole = N == 4u && sizeof(T) == 4 && p.vecOut && X >= X0 && X + 4u <= X0 + W;
+#pragma unroll
+      for (uint32_t c = 0; c < 4u; c++)
+      {
+        if (c >= s.f.planes) break; // (wave-uniform)
+        float v[N];
+#pragma unroll
+        for (uint32_t i = 0; i < N; i++) v[i] = (float)((q[i] >> (8u * c)) & 0xFFu) * s.f.scale[c] + s.f.bias[c];
+        T *plane = row + (unsigned long long)c * p.planeStride;
+        if constexpr (N == 4u && sizeof(T) == 4)
+          if (whole)
+          {
+            *reinterpret_cast<float4v *>(plane + (X - X0)) = float4v{ v[0], v[1], v[2], v[3] };
+            continue;
+          }
+#pragma unroll
+        for (uint32_t i = 0; i < N; i++)
+          if (X + i >= X0 && X + i < X0 + W) plane[X + i - X0] = (T)v[i];
+      }
+    }
+
+    // the lane's 8 pixels of image row y -> its share of the sums of 8 >> L boxes; after the exchange every lane of a box row holds the whole sums, and the lane of
+    // the box's first row rounds (half up) and stores.  The pixels are made opaque first, as in PlanarStore and for its reason.
+    template <uint32_t L, class BASE>
+    __device__ __forceinline__ void reduce_and_store(const BASE &base, const WindowDecodeParams &p, uint32_t x, uint32_t y, const uint32_t px[8])
+    {
+      constexpr uint32_t k = 1u << L, N = 8u >> L, kHalf = ((k * k) >> 1) * 0x00010001u;
+      uint32_t lo[N], hi[N];
+#pragma unroll
+      for (uint32_t i = 0; i < N; i++)
+      {
+        lo[i] = 0; hi[i] = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < k; j++)
+        {
+          const uint32_t v = px[i * k + j];
+          lo[i] += v & 0x00FF00FFu; hi[i] += (v >> 8) & 0x00FF00FFu;
+        }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < N; i++)
+      {
+        lo[i] = add_lane_xor8(lo[i]); hi[i] = add_lane_xor8(hi[i]);
+        if constexpr (L >= 2u) { lo[i] = add_lane_xor16(lo[i]); hi[i] = add_lane_xor16(hi[i]); }
+        if constexpr (L >= 3u) { lo[i] = add_lane_xor32(lo[i]); hi[i] = add_lane_xor32(hi[i]); }
+      }
+      if (y & (k - 1u)) return; // not the box's first row: its sums have gone to the lane that is
+      uint32_t q[N];
+#pragma unroll
+      for (uint32_t i = 0; i < N; i++) q[i] = (((lo[i] + kHalf) >> (2u * L)) & 0x00FF00FFu) | ((((hi[i] + kHalf) >> (2u * L)) & 0x00FF00FFu) << 8);
+      store_reduced<L>(base, p, x >> L, y >> L, q);
+    }
+
+    // BASE (RgbaStore / PlanarStore<T>) at the job's level: a wave-uniform switch, level 0 is BASE itself
+    template <class BASE>
+    struct ScaledStore
+    {
+      BASE base;
+      __device__ __forceinline__ void operator()(const WindowDecodeParams &p, uint32_t x, uint32_t y, const uint32_t px[8]) const
+      {
+        uint32_t q[8];
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++)
+        {
+          q[i] = px[i];
+          asm volatile("" : "+v"(q[i]));
+        }
+        switch (p.log2Scale)
+        {
+        case 0u: base(p, x, y, q); break;
+        case 1u: reduce_and_store<1u>(base, p, x, y, q); break;
+        case 2u: reduce_and_store<2u>(base, p, x, y, q); break;
+        default: reduce_and_store<3u>(base, p, x, y, q); break; // (3: the host entry has refused everything else)
         }
       }
     };
@@ -318,6 +443,20 @@ namespace limg_hip
     {
       __shared__ __align__(16) WindowWaveLds sW[4];
       stream_windows_body(b, sW, PlanarStore<T>{ f });
+    }
+
+    // the *_scaled entries: the same bodies, every job stored at its own level
+    __global__ __launch_bounds__(256) void k_stream_windows_scaled(const WindowBatchParams b)
+    {
+      __shared__ __align__(16) WindowWaveLds sW[4];
+      stream_windows_body(b, sW, ScaledStore<RgbaStore>{ RgbaStore() });
+    }
+
+    template <class T>
+    __global__ __launch_bounds__(256) void k_stream_windows_scaled_tensor(const WindowBatchParams b, const limg_hip_tensor_format f)
+    {
+      __shared__ __align__(16) WindowWaveLds sW[4];
+      stream_windows_body(b, sW, ScaledStore<PlanarStore<T>>{ PlanarStore<T>{ f } });
     }
 
     // ---- version 2 -------------------------------------------------------------------------------------------------------------------
@@ -583,6 +722,15 @@ namespace limg_hip
 
     template <class T>
     __global__ __launch_bounds__(256) void k_bstream_windows_tensor(const WindowBatchParams b, const limg_hip_tensor_format f) { bstream_windows_body(b, PlanarStore<T>{ f }); }
+
+    // (8 workgroups per CU asked for: left alone the allocator takes 65 vector registers and 7 waves per SIMD; held to 64 it needs no scratch and runs the 8 the launch counts on)
+    __global__ __launch_bounds__(256, 8) void k_bstream_windows_scaled(const WindowBatchParams b) { bstream_windows_body(b, ScaledStore<RgbaStore>{ RgbaStore() }); }
+
+    template <class T>
+    __global__ __launch_bounds__(256, 8) void k_bstream_windows_scaled_tensor(const WindowBatchParams b, const limg_hip_tensor_format f)
+    {
+      bstream_windows_body(b, ScaledStore<PlanarStore<T>>{ PlanarStore<T>{ f } });
+    }
   }
 
   // persistent launches: a workgroup of four waves per residency slot at most (version 1: 4 per CU at its 100 vector registers; version 2: 8), every wave strides over its units
@@ -633,5 +781,27 @@ namespace limg_hip
     const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u);
     if (f.type == LIMG_HIP_TENSOR_F16) hipLaunchKernelGGL(k_bstream_windows_tensor<_Float16>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
     else hipLaunchKernelGGL(k_bstream_windows_tensor<float>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
+  }
+
+  // the scaled forms: the same grids again; version 2's map kernel works on the footprints and serves them as it is
+  void launch_stream_windows_scaled(const WindowBatchParams &b, const limg_hip_tensor_format *f, int cus, hipStream_t s)
+  {
+    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u), slots = (uint32_t)cus * 4u;
+    const dim3 grid(need < slots ? need : slots);
+    if (!f) hipLaunchKernelGGL(k_stream_windows_scaled, grid, dim3(256), 0, s, b);
+    else if (f->type == LIMG_HIP_TENSOR_F16) hipLaunchKernelGGL(k_stream_windows_scaled_tensor<_Float16>, grid, dim3(256), 0, s, b, *f);
+    else hipLaunchKernelGGL(k_stream_windows_scaled_tensor<float>, grid, dim3(256), 0, s, b, *f);
+  }
+
+  void launch_blocked_stream_windows_scaled(const WindowBatchParams &b, const limg_hip_tensor_format *f, int cus, hipStream_t s)
+  {
+    const uint32_t slots = (uint32_t)cus * 8u;
+    const uint32_t needMap = b.totalItems / 4u + (b.totalItems % 4u ? 1u : 0u);
+    hipLaunchKernelGGL(k_bstream_windows_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, b);
+    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u);
+    const dim3 grid(need < slots ? need : slots);
+    if (!f) hipLaunchKernelGGL(k_bstream_windows_scaled, grid, dim3(256), 0, s, b);
+    else if (f->type == LIMG_HIP_TENSOR_F16) hipLaunchKernelGGL(k_bstream_windows_scaled_tensor<_Float16>, grid, dim3(256), 0, s, b, *f);
+    else hipLaunchKernelGGL(k_bstream_windows_scaled_tensor<float>, grid, dim3(256), 0, s, b, *f);
   }
 }

@@ -13,7 +13,8 @@
 // (size of the pool whose strip partition the 8x8 path reproduces; default: limg_threading_max_threads()),
 // `--out-dir <dir>`, `--stream <file>` (also write the compact LMG3 stream of the 8x8 path and verify that it decodes to that path's image),
 // `--blocked-stream <file>` (single-file merged-block mode: write the version 2 stream of that very encode and verify that it decodes to its image),
-// and the extra mode `limg_hip_cli --decode <file.lmg3> [<out.tga>] [--window x,y,w,h]` (either version; with --window only that pixel rectangle is decoded).
+// and the extra mode `limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]` (either version; with --window only that pixel rectangle
+// is decoded; with --scale k the image reduced by k x k box means, the window then in the reduced image's coordinates).
 #include <inttypes.h>
 #include <math.h>
 #include <stdio.h>
@@ -234,7 +235,7 @@ struct Options
 static const char *const kUsage =
     "Usage:\nlimg_hip_cli [<InputFile> | --] [--no-output | --error-factor <Factor> | --accurate-bit-crushing | --single-thread | --fixed-blocks | --threads <T> | --out-dir <dir> | "
     "--stream <file> | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n"
-    "limg_hip_cli --decode <file.lmg3> [<out.tga>] [--window x,y,w,h]\n";
+    "limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n";
 
 static bool parse_number(const char *text, uint64_t &value)
 {
@@ -497,9 +498,10 @@ static int run_benchmark_list(const Options &o, limg_thread_pool *pool)
   return EXIT_SUCCESS;
 }
 
-// extra mode: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--window x,y,w,h]   (limg_decode of a compact stream written by --stream or --blocked-stream; with
-// --window: limg_decode_window of that pixel rectangle only, a w x h image)
-static const char *const kDecodeUsage = "Usage: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--window x,y,w,h]\n";
+// extra mode: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]   (limg_decode of a compact stream written by --stream or
+// --blocked-stream; with --window: limg_decode_window of that pixel rectangle only, a w x h image; with --scale k: limg_decode_windows_scaled at level log2 k -- the
+// image of (sizeX / k) x (sizeY / k) box means, or the --window of it, which is then in that image's coordinates)
+static const char *const kDecodeUsage = "Usage: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n";
 
 static bool parse_window(const char *text, size_t win[4])
 {
@@ -519,13 +521,19 @@ static int run_decode(int argc, const char **argv)
   const char *in = nullptr, *out = "limg_out.tga";
   size_t win[4] = { 0, 0, 0, 0 };
   bool window = false;
-  int positional = 0;
+  int positional = 0, level = -1; // level: log2 of --scale, -1 without it
   for (int i = 2; i < argc; i++)
   {
     if (!strcmp(argv[i], "--window"))
     {
       if (i + 1 >= argc || !parse_window(argv[++i], win)) FAIL(EXIT_FAILURE, "'--window' takes x,y,w,h in pixels.\n%s", kDecodeUsage);
       window = true;
+    }
+    else if (!strcmp(argv[i], "--scale"))
+    {
+      const char *v = i + 1 < argc ? argv[++i] : "";
+      level = !strcmp(v, "1") ? 0 : !strcmp(v, "2") ? 1 : !strcmp(v, "4") ? 2 : !strcmp(v, "8") ? 3 : -1;
+      if (level < 0) FAIL(EXIT_FAILURE, "'--scale' takes 1, 2, 4 or 8.\n%s", kDecodeUsage);
     }
     else if (positional == 0) { in = argv[i]; positional++; }
     else if (positional == 1) { out = argv[i]; positional++; }
@@ -538,6 +546,22 @@ static int run_decode(int argc, const char **argv)
   bool alpha = false;
   limg_result r = limg_decode_info(stream.data(), stream.size(), &sx, &sy, &alpha);
   if (r != limg_success) FAIL(EXIT_FAILURE, "'%s' is not an LMG3 stream (0x%" PRIX32 ").\n", in, (uint32_t)r);
+  if (level >= 0)
+  {
+    const size_t rx = sx >> level, ry = sy >> level;
+    if (!window) { win[0] = 0; win[1] = 0; win[2] = rx; win[3] = ry; }
+    if (win[2] == 0 || win[3] == 0 || win[0] >= rx || win[2] > rx - win[0] || win[1] >= ry || win[3] > ry - win[1])
+      FAIL(EXIT_FAILURE, "The window %" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 " is not inside the reduced image (%" PRIu64 " x %" PRIu64 " pixels at scale 1/%d).\n", (uint64_t)win[0],
+           (uint64_t)win[1], (uint64_t)win[2], (uint64_t)win[3], (uint64_t)rx, (uint64_t)ry, 1 << level);
+    std::vector<uint32_t> image(win[2] * win[3]);
+    limg_hip_scaled_window w = { win[0], win[1], win[2], win[3], image.data(), win[2], (uint32_t)level };
+    r = limg_decode_windows_scaled(stream.data(), stream.size(), &w, 1);
+    if (r != limg_success) FAIL(EXIT_FAILURE, "limg_decode_windows_scaled failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
+    printf("%" PRIu64 " x %" PRIu64 " pixels, %s; scale 1/%d: window %" PRIu64 " x %" PRIu64 " at (%" PRIu64 ", %" PRIu64 ") of %" PRIu64 " x %" PRIu64 ".\n", (uint64_t)sx, (uint64_t)sy,
+           alpha ? "RGBA" : "RGB", 1 << level, (uint64_t)win[2], (uint64_t)win[3], (uint64_t)win[0], (uint64_t)win[1], (uint64_t)rx, (uint64_t)ry);
+    puts(write_tga(out, win[2], win[3], 4, image.data()) ? "Wrote decoded file." : "Failed to write decoded file.");
+    return EXIT_SUCCESS;
+  }
   if (window)
   {
     if (win[2] == 0 || win[3] == 0 || win[0] >= sx || win[2] > sx - win[0] || win[1] >= sy || win[3] > sy - win[1])
