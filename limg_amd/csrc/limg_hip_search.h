@@ -113,19 +113,71 @@ namespace limg_hip
       return v;
     }
 
+    // ---- the hot subtree of that automaton as straight-line code (limg_search_hot.h, generated) ---------------------------------------------------------------
+    // A handful of the tree's states take most of the trials of every workload (tools/search_hot_paths.json).  For those the table walk is replaced by generated
+    // nested code: the triple of a state is static, so shift amounts and multipliers are literals (v_lshrrev_b32 with an inline constant issues at full rate, with
+    // an SGPR it does not), there is no table load, no wait and no change-mask test, and a term set is a named variable that a later state of the same path reuses
+    // where the table walk -- which keeps one set per factor -- builds it again.  Which sets stay live is the generator's decision (its parameter K), not a
+    // dynamic register index.  Whole blocks only: search_fast_automaton<true>.
+    struct TermSet { uint32_t rg; int b; };
+    // factors B and C at shift 8 contribute nothing (rebuild_B / rebuild_C): constant sets, no register
+    __device__ __forceinline__ constexpr TermSet terms_shift8(int factor) { return TermSet{ (uint32_t)term_bias(factor) * 0x10001u, 0 }; }
+    // make_terms for a literal shift S and its multiplier MUL == shift_mul(S): the same integers.  A factor is a byte (cvt_u8_rne_sat), so at shift 8 the
+    // re-expanded value is 0 and the terms are the additive constants; below shift 4 the multiplier is 1 << S and  (f >> S) << S  is one AND with an inline
+    // constant; otherwise the shift and the 24-bit multiply take their constants as immediates -- no SGPR, no scalar move.
+    template <uint32_t S, uint32_t MUL>
+    __device__ __forceinline__ TermSet hot_terms(const uint32_t f, const int n[3], const int m[3])
+    {
+      static_assert(S <= 8 && (S >= 4 || MUL == (1u << S)), "MUL is shift_mul(S)");
+      int t0, t1, t2;
+      if constexpr (S == 8) { t0 = m[0]; t1 = m[1]; t2 = m[2]; }
+      else
+      {
+        uint32_t d;
+        if constexpr (S < 4) d = f & ~((1u << S) - 1u);
+        else asm("v_mul_u32_u24 %0, %2, %1" : "=v"(d) : "v"(f >> S), "n"(MUL));
+        t0 = mad_i24((int)d, n[0], m[0]); t1 = mad_i24((int)d, n[1], m[1]); t2 = mad_i24((int)d, n[2], m[2]);
+      }
+      TermSet r;
+      r.rg = __builtin_amdgcn_perm((uint32_t)t1, (uint32_t)t0, 0x06050201u);
+      r.b = t2 >> 8;
+      return r;
+    }
+    // one trial of a whole block on three named sets (they become the cached ones): the trial core, the pixel check and -- only if no pixel fails -- the block sum.
+    // (Spelled as two branches to one label in the generated code instead, the compiler emits the same instructions: measured on the assembly.)
+    __device__ __forceinline__ bool hot_trial(TrialState &t, const TermSet &A, const TermSet &B, const TermSet &C, const uint32_t maxPixel32, const uint32_t blockLimit)
+    {
+      t.tA_RG = A.rg; t.tA_B = A.b; t.tB_RG = B.rg; t.tB_B = B.b; t.tC_RG = C.rg; t.tC_B = C.b;
+      const uint32_t err = trial_pixel_error<true>(t, true);
+      return __builtin_amdgcn_ballot_w64(err > maxPixel32) == 0ull && wave_sum(err) < blockLimit; // be * 16 < maxBlock * n, see phase E
+    }
+#include "limg_search_hot.h"
+
     template <bool FULL>
     __device__ __forceinline__ void search_fast_automaton(TrialState &t, const bool active, const uint32_t maxPixel32, const uint32_t blockLimit, uint32_t shift[3])
     {
       const SearchEntry *tab = d_search_tab;
-      asm volatile("" : "+s"(tab)); // opaque: otherwise the address is rematerialised (s_getpc + 2 adds) in every iteration
-      // entry 0 as immediates (the opaque base above would make reading it a memory round trip per block)
-      // its three factors are built here, unconditionally and with immediate operands (the loop then starts with nothing to rebuild): the cached terms need no
-      // initial value at all
-      constexpr uint32_t root[8] = LIMG_SEARCH_ROOT;
-      rebuild_A(t, root[0] & 31u, root[5]);
-      rebuild_B(t, root[3], root[6]);
-      rebuild_C(t, root[4], root[7]);
-      uint8s_t e = { root[0] & ~0xE0u, root[1], root[2], root[3], root[4], root[5], root[6], root[7] };
+      uint8s_t e;
+      if constexpr (FULL)
+      { // whole blocks: the generated hot subtree first; it ends the search itself or hands over the offset of the table entry to go on with (the state's three
+        // sets are the cached ones, and the entry names its changes against exactly that triple)
+        uint32_t off;
+        if (search_hot(t, maxPixel32, blockLimit, shift, off)) return;
+        asm volatile("" : "+s"(tab)); // opaque: otherwise the address is rematerialised (s_getpc + 2 adds) in every iteration
+        e = sload8(tab, off);
+      }
+      else
+      {
+        asm volatile("" : "+s"(tab)); // (as above)
+        // entry 0 as immediates (the opaque base above would make reading it a memory round trip per block)
+        // its three factors are built here, unconditionally and with immediate operands (the loop then starts with nothing to rebuild): the cached terms need no
+        // initial value at all
+        constexpr uint32_t root[8] = LIMG_SEARCH_ROOT;
+        rebuild_A(t, root[0] & 31u, root[5]);
+        rebuild_B(t, root[3], root[6]);
+        rebuild_C(t, root[4], root[7]);
+        e = uint8s_t{ root[0] & ~0xE0u, root[1], root[2], root[3], root[4], root[5], root[6], root[7] };
+      }
       while (!(e[0] >> 31))
       { // every field sits in an SGPR of its own: no extraction.  (e[0] & 31 is the shift amount as v_lshrrev_b32 reads it -- the mask costs nothing)
         if (e[0] & 0x20u) rebuild_A(t, e[0] & 31u, e[5]);

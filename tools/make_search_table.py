@@ -10,6 +10,11 @@ inlined copies of the trial inside nested uniform loops.
 `search_fast` below is a literal restatement of the upstream control flow as a generator (same loop-carried resets,
 uint8 counters never exceed 10 here); the table is produced by exhaustively exploring both outcomes of every trial and
 merging identical control states.  tests/test_host.py replays it against the golden trial tables of the real reference.
+
+The few states nearly every block visits (tools/search_hot_paths.json, from tools/search_hot_paths.py) are emitted a second time, as nested straight-line C++
+(limg_amd/csrc/limg_search_hot.h): the triple of a state is static there, so shifts and multipliers are literals, nothing is loaded, and a term set built
+earlier on the same path is reused instead of rebuilt.  `hot_walk` is the Python model of that code and of its hand-over to the table loop
+(tests/test_search_hot.py).
 """
 import os
 import sys
@@ -312,6 +317,177 @@ def walk(words, outcome):
 ENTRY_FMT = "{0x%08xu, 0x%04xu, 0x%04xu, %du, %du, %du, %du, %du}"
 ACC_ENTRY_FMT = "{0x%x,0x%x}"
 
+# ---- the hot subtree as straight-line code (limg_amd/csrc/limg_search_hot.h) -------------------------------------------------------------------------------------
+HOT_JSON = os.path.join(ROOT, "tools", "search_hot_paths.json")  # written by tools/search_hot_paths.py
+HOT_HEADER = os.path.join(ROOT, "limg_amd", "csrc", "limg_search_hot.h")
+HOT_K = None  # extra live term sets per factor beside the current one (None: no limit); the shipped value, see profiles/search_hot_ab.md
+
+
+def load_hot_paths(path=HOT_JSON):
+    import json
+    return json.load(open(path))["states"]
+
+
+def hot_tree(trans, paths, K=HOT_K):
+    """The hot subtree as the structure both the C++ emitter and `hot_walk` read.  node = dict(path, sid, triple, build = [(factor, shift, variable)] in factor order,
+    use = [variable of A, of B, of C] (None: factor B / C at shift 8, a constant set), edge = {True: e, False: e});
+    e = ("hot", node) | ("final", shifts) | ("exit", byte offset of the successor's table entry).
+    A variable is one built term set (make_terms: 7 VALU).  A state builds a set only if no live variable holds it; a set stays live into a child's subtree while
+    some hot state there uses it -- the current one always, of the others at most K per factor, those with the most visits (summed maximum over the settings) first."""
+    weight = {p: max(f.values()) for p, f in paths.items()}
+    sid_of = {"": 0}
+    for p in sorted(paths, key=len):
+        if p:
+            sid_of[p] = trans[sid_of[p[:-1]]][1 if p[-1] == "P" else 2]
+    assert all(trans[s][0] != "final" for s in sid_of.values())
+
+    def uses(p):  # {(factor, shift): visits} over the hot states at or below p
+        out = {}
+        for q in paths:
+            if q.startswith(p):
+                for f in range(3):
+                    s = trans[sid_of[q]][0][f]
+                    out[(f, s)] = out.get((f, s), 0.0) + weight[q]
+        return out
+
+    def make(p, live):
+        sid = sid_of[p]
+        tri = trans[sid][0]
+        node = dict(path=p, sid=sid, triple=tri, build=[], use=[], edge={})
+        for f in range(3):
+            s = tri[f]
+            if f > 0 and s > 7:
+                node["use"].append(None)
+                continue
+            if (f, s) not in live:
+                live[(f, s)] = "t%s%d_%d" % ("ABC"[f], s, sid)
+                node["build"].append((f, s, live[(f, s)]))
+            node["use"].append(live[(f, s)])
+        for ok in (True, False):
+            nxt = trans[sid][1 if ok else 2]
+            q = p + ("P" if ok else "F")
+            if q in paths:
+                want = uses(q)
+                keep = {}
+                for f in range(3):
+                    extra = sorted((k for k in live if k[0] == f and k in want and k[1] != trans[nxt][0][f]), key=lambda k: (-want[k], k[1]))
+                    for k in extra[:K]:
+                        keep[k] = live[k]
+                    cur = (f, trans[nxt][0][f])
+                    if cur in live:
+                        keep[cur] = live[cur]
+                node["edge"][ok] = ("hot", make(q, keep))
+            elif trans[nxt][0] == "final":
+                node["edge"][ok] = ("final", tuple(trans[nxt][1]))
+            else:
+                node["edge"][ok] = ("exit", nxt * ENTRY_BYTES)
+        return node
+
+    return make("", {})
+
+
+def hot_nodes(node):
+    yield node
+    for ok in (True, False):
+        if node["edge"][ok][0] == "hot":
+            yield from hot_nodes(node["edge"][ok][1])
+
+
+def hot_walk(outcomes, tree, words):
+    """Model of search_fast_automaton<true>: the generated straight-line code, then -- where it leaves -- the table loop from the offset it hands over, with the
+    state's three current sets as the cached ones.  `outcomes`: an iterator of pass / fail results, one per trial.  Returns (triples tried, final shifts, real builds).
+    Asserts what the kernel relies on: a used variable holds the set of the state's shift, and the table's change masks continue from the handed-over triple."""
+    it = iter(outcomes)
+    tried, builds, holds = [], 0, {}
+    node = tree
+    while True:
+        for f, s, var in node["build"]:
+            assert var not in holds
+            holds[var] = (f, s)
+            builds += 1
+        for f in range(3):
+            var, s = node["use"][f], node["triple"][f]
+            assert (f > 0 and s == 8) if var is None else holds[var] == (f, s), (node["path"], f)
+        tried.append(tuple(node["triple"]))
+        e = node["edge"][bool(next(it))]
+        if e[0] == "hot":
+            node = e[1]
+        elif e[0] == "final":
+            return tried, tuple(e[1]), builds
+        else:
+            break
+    cached = list(node["triple"])
+    assert e[1] % ENTRY_BYTES == 0
+    s = e[1] // ENTRY_BYTES
+    while not (words[s][0] >> 31):
+        w = words[s]
+        t = (w[0] & 31, w[3], w[4])
+        for k in range(3):
+            if (w[0] >> 5) & (1 << k):
+                cached[k] = t[k]
+                builds += 0 if (k > 0 and t[k] > 7) else 1
+        assert tuple(cached) == t, (s, cached, t)
+        tried.append(t)
+        s = (w[1] if next(it) else w[2]) // ENTRY_BYTES
+    w = words[s]
+    return tried, (w[0] & 31, w[3], w[4]), builds
+
+
+def emit_hot(tree, K=HOT_K):
+    """the text of limg_search_hot.h"""
+    out = []
+
+    def const_set(f):
+        return "terms_shift8(%d)" % f
+
+    def edge(e, node, ind):
+        pad = "  " * ind
+        a, b, c = node["triple"]
+        if e[0] == "final":
+            out.append("%s{ shift[0] = %du; shift[1] = %du; shift[2] = %du; return true; }" % (pad, e[1][0], e[1][1], e[1][2]))
+        elif e[0] == "exit":
+            out.append("%s{ t.cA = %du; t.cB = %du; t.cC = %du; off = 0x%04xu; return false; }" % (pad, a, b, c, e[1]))
+        else:
+            out.append("%s{" % pad)
+            state(e[1], ind + 1)
+            out.append("%s}" % pad)
+
+    def state(node, ind):
+        pad = "  " * ind
+        out.append('%s// state "%s": (%d, %d, %d)' % ((pad, node["path"]) + tuple(node["triple"])))
+        for f, s, var in node["build"]:
+            F = "ABC"[f]
+            out.append("%sconst TermSet %s = hot_terms<%du, %du>(t.f%s, t.n%s, t.m%s);" % (pad, var, s, MUL[s], F, F, F))
+        use = [v if v is not None else const_set(f) for f, v in enumerate(node["use"])]
+        out.append("%sif (hot_trial(t, %s, %s, %s, maxPixel32, blockLimit))" % (pad, use[0], use[1], use[2]))
+        edge(node["edge"][True], node, ind)
+        out.append("%selse" % pad)
+        edge(node["edge"][False], node, ind)
+
+    state(tree, 1)
+    nodes = list(hot_nodes(tree))
+    return """// GENERATED by tools/make_search_table.py from tools/search_hot_paths.json -- do not edit.
+// The hot subtree of the default shift search's decision automaton (limg_search_table.h) as nested straight-line code: %d states, %d term sets built, K = %s.
+// Per state the shift triple is static: a term set is a named variable, built with literal shift and multiplier only where no live variable holds it; then the
+// unchanged trial (hot_trial: trial core, pixel check, block sum).  An edge to a hot child continues inline, an edge to a final state yields its shifts, any other
+// edge leaves to the table loop with the successor's byte offset in `off` (the state's three sets are the cached ones in `t`).
+// Included by limg_hip_search.h, inside namespace limg_hip::(anonymous), after the helpers it is built from.
+#ifndef LIMG_SEARCH_HOT_H
+#define LIMG_SEARCH_HOT_H
+#define LIMG_SEARCH_HOT_STATES %d
+__device__ __forceinline__ bool search_hot(TrialState &t, const uint32_t maxPixel32, const uint32_t blockLimit, uint32_t shift[3], uint32_t &off)
+{
+%s
+}
+#endif
+""" % (len(nodes), sum(len(n["build"]) for n in nodes), "unlimited" if K is None else str(K), len(nodes), "\n".join(out))
+
+
+def write_hot(K=HOT_K, path=HOT_HEADER):
+    text = emit_hot(hot_tree(build(), load_hot_paths(), K), K)
+    open(path, "w").write(text)
+    print("wrote", path, text.count("// state"), "states")
+
 
 def main():
     trans = build()
@@ -352,6 +528,7 @@ def main():
     path = os.path.join(ROOT, "limg_amd", "csrc", "limg_search_table_accurate.h")
     open(path, "w").write(text)
     print("wrote", path, len(acc), "states")
+    write_hot()
 
 
 if __name__ == "__main__":
