@@ -127,6 +127,11 @@ class ScaledTensorWindowJob(C.Structure):
     _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", ScaledTensorWindow)]
 
 
+# (a level leads the window tuple, the pixels go to planes) -> the entry's window and job struct
+_WINDOW_TYPES = {(False, False): (Window, WindowJob), (False, True): (TensorWindow, TensorWindowJob),
+                 (True, False): (ScaledWindow, ScaledWindowJob), (True, True): (ScaledTensorWindow, ScaledTensorWindowJob)}
+
+
 def tensor_format(dtype, planes, scale, bias):
     """dtype: "float32" / "float16" (or the numpy / torch dtype); scale, bias: one value per plane (a 4th is 1 / 0 where only three are given)"""
     name = str(dtype).split(".")[-1].replace("'>", "")
@@ -263,36 +268,18 @@ def load_library(path=None):
     L.limg_hip_blocked_encode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_uint32, C.c_int]
     L.limg_hip_blocked_decode_stream.restype = C.c_int
     L.limg_hip_blocked_decode_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
-    for name in ("limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device"):
-        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, sizeX, sizeY, x0, y0, width, height, out, outStridePixels, hipStream
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_size_t] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]
-    for name in ("limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window"):
-        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, x0, y0, width, height, out, outStridePixels
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_size_t] * 4 + [C.c_void_p, C.c_size_t]
-    for name in ("limg_hip_decode_stream_windows_device", "limg_hip_blocked_decode_stream_windows_device"):
-        getattr(L, name).restype = C.c_int  # ctx, jobs (host), count, jobStatus (device), hipStream
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    for name in ("limg_hip_decode_stream_windows", "limg_hip_blocked_decode_stream_windows"):
-        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
-    for name in ("limg_hip_decode_stream_windows_tensor_device", "limg_hip_blocked_decode_stream_windows_tensor_device"):
-        getattr(L, name).restype = C.c_int  # ctx, jobs (host), count, format (host), jobStatus (device), hipStream
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-    for name in ("limg_hip_decode_stream_windows_tensor", "limg_hip_blocked_decode_stream_windows_tensor"):
-        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count, format (host)
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-    for name in ("limg_hip_decode_stream_windows_scaled_device", "limg_hip_blocked_decode_stream_windows_scaled_device"):
-        getattr(L, name).restype = C.c_int  # ctx, jobs (host), count, jobStatus (device), hipStream
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    for name in ("limg_hip_decode_stream_windows_scaled", "limg_hip_blocked_decode_stream_windows_scaled"):
-        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
-    for name in ("limg_hip_decode_stream_windows_scaled_tensor_device", "limg_hip_blocked_decode_stream_windows_scaled_tensor_device"):
-        getattr(L, name).restype = C.c_int  # ctx, jobs (host), count, format (host), jobStatus (device), hipStream
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-    for name in ("limg_hip_decode_stream_windows_scaled_tensor", "limg_hip_blocked_decode_stream_windows_scaled_tensor"):
-        getattr(L, name).restype = C.c_int  # ctx, stream, bytes, windows (host), count, format (host)
-        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    P, Z = C.c_void_p, C.c_size_t
+    for args, names in (  # the window entries, limg_hip_[blocked_]decode_stream_<name>: both versions of a name share its argument list
+            ([P, P, Z] + [Z] * 6 + [P, Z, P], ("window_device",)),  # ctx, stream, bytes, sizeX, sizeY, x0, y0, width, height, out, outStridePixels, hipStream
+            ([P, P, Z] + [Z] * 4 + [P, Z], ("window",)),  # ctx, stream, bytes, x0, y0, width, height, out, outStridePixels
+            ([P, P, Z, P, P], ("windows_device", "windows_scaled_device")),  # ctx, jobs (host), count, jobStatus (device), hipStream
+            ([P, P, Z, P, Z], ("windows", "windows_scaled")),  # ctx, stream, bytes, windows (host), count
+            ([P, P, Z, P, P, P], ("windows_tensor_device", "windows_scaled_tensor_device")),  # ctx, jobs (host), count, format (host), jobStatus (device), hipStream
+            ([P, P, Z, P, Z, P], ("windows_tensor", "windows_scaled_tensor"))):  # ctx, stream, bytes, windows (host), count, format (host)
+        for name in names:
+            for version in ("limg_hip_decode_stream_", "limg_hip_blocked_decode_stream_"):
+                getattr(L, version + name).restype = C.c_int
+                getattr(L, version + name).argtypes = args
     L.limg_hip_blocked_last_stream.restype = C.c_int
     L.limg_hip_blocked_last_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.limg_hip_blocked_stream_info.restype = C.c_int
@@ -750,219 +737,151 @@ class LimgHip:
     def blocked_decode_stream_window_device(self, stream, nbytes, W, H, x, y, w, h, out=None, out_stride=None):
         return self._decode_stream_window_device("limg_hip_blocked_decode_stream_window_device", stream, nbytes, W, H, x, y, w, h, out, out_stride)
 
-    # ---- batched window decode: many windows of many streams per call (contract: include/limg_hip.h) ----
-    def _decode_stream_windows_device(self, name, jobs, status):
+    # ---- batched window decode: many windows of many streams per call, into packed RGBA8 or planar float tensors, at full or reduced scale (contract: include/limg_hip.h).
+    # The two builders below make every entry's table; `scaled`: a level 0 .. 3 leads the window's (x, y, w, h) and ends its struct; fmt: the tensor format, None for RGBA8.
+    def _decode_windows_device(self, name, jobs, scaled, fmt, status):
         import torch
-        table = (WindowJob * len(jobs))()
+        planar = fmt is not None
+        win_t, job_t = _WINDOW_TYPES[scaled, planar]
+        dtype = torch.int32 if not planar else torch.float16 if fmt.type == TENSOR_F16 else torch.float32
+        table = (job_t * len(jobs))()
         outs = []
-        for i, (stream, nbytes, W, H, x, y, w, h, out, out_stride) in enumerate(jobs):
+        for i, job in enumerate(jobs):  # (a loader calls this per step with thousands of jobs: the four tuple layouts are unpacked by name, everything else is shared)
+            if planar:
+                if scaled:
+                    stream, nbytes, W, H, level, x, y, w, h, out, row, plane = job
+                else:
+                    stream, nbytes, W, H, x, y, w, h, out, row, plane = job
+            elif scaled:
+                stream, nbytes, W, H, level, x, y, w, h, out, row = job
+            else:
+                stream, nbytes, W, H, x, y, w, h, out, row = job
             if out is None:
-                out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
-            if out_stride is None:
-                out_stride = out.stride(0) if out.dim() == 2 else w
-            table[i] = WindowJob(stream.data_ptr(), int(nbytes), W, H, Window(x, y, w, h, out.data_ptr(), int(out_stride)))
+                out = torch.empty((fmt.planes, h, w) if planar else (h, w), dtype=dtype, device=stream.device)
+            if row is None:  # out's own strides where it has the window's shape, else densely packed
+                row = out.stride(-2) if out.dim() == 2 + planar else w
+            if planar:
+                assert out.dtype == dtype, (out.dtype, dtype)
+                if plane is None:
+                    plane = out.stride(0) if out.dim() == 3 else row * h
+                win = win_t(x, y, w, h, out.data_ptr(), int(row), int(plane))
+            else:
+                win = win_t(x, y, w, h, out.data_ptr(), int(row))
+            if scaled:
+                win.log2Scale = level
+            table[i] = job_t(stream.data_ptr(), int(nbytes), W, H, win)
             outs.append(out)
-        self._stream_call(name, table, len(jobs), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
+        self._stream_call(name, table, len(jobs), *([C.byref(fmt)] if planar else []), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
         return outs
 
-    def _decode_stream_windows(self, name, stream, wins, outs):
+    def _decode_windows_host(self, name, stream, wins, scaled, fmt, outs):
         stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        planar = fmt is not None
+        win_t = _WINDOW_TYPES[scaled, planar][0]
+        dtype = np.dtype(np.uint32 if not planar else np.float16 if fmt.type == TENSOR_F16 else np.float32)
+        eb = dtype.itemsize
         outs = [None] * len(wins) if outs is None else list(outs)
-        table = (Window * len(wins))()
-        for i, (x, y, w, h) in enumerate(wins):
+        table = (win_t * len(wins))()
+        for i, win in enumerate(wins):
+            x, y, w, h = win[scaled:]
             if outs[i] is None:
-                outs[i] = np.zeros((h, w), dtype=np.uint32)
+                outs[i] = np.zeros((fmt.planes, h, w) if planar else (h, w), dtype=dtype)
             out = outs[i]
-            assert out.dtype == np.uint32 and out.ndim == 2 and out.strides[1] == 4 and out.strides[0] % 4 == 0, "out: uint32 rows, pixels contiguous"
-            table[i] = Window(x, y, w, h, out.ctypes.data, out.strides[0] // 4)
-        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins))
+            if planar:
+                assert out.dtype == dtype and out.ndim == 3 and out.shape[0] >= fmt.planes and out.strides[2] == eb and out.strides[1] % eb == 0 and out.strides[0] % eb == 0, \
+                    "out: (planes, h, w) of the format's type, elements of a row contiguous"
+            else:
+                assert out.dtype == np.uint32 and out.ndim == 2 and out.strides[1] == 4 and out.strides[0] % 4 == 0, "out: uint32 rows, pixels contiguous"
+            table[i] = win_t(x, y, w, h, out.ctypes.data, *[s // eb for s in out.strides[-2::-1]], *win[:scaled])  # (strides: of the rows, then of the planes)
+        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins), *([C.byref(fmt)] if planar else []))
         return outs
 
     def decode_stream_windows_device(self, jobs, status=None):
         """jobs: (stream tensor, nbytes, W, H, x, y, w, h, out, out_stride) each, as the arguments of decode_stream_window_device (out=None allocates, out_stride=None is
         out's own row stride); status: torch int32 CUDA tensor of len(jobs) words or None.  One launch for all of them, asynchronous on torch's current stream.
         Returns the list of output tensors."""
-        return self._decode_stream_windows_device("limg_hip_decode_stream_windows_device", jobs, status)
+        return self._decode_windows_device("limg_hip_decode_stream_windows_device", jobs, False, None, status)
 
     def blocked_decode_stream_windows_device(self, jobs, status=None):
-        return self._decode_stream_windows_device("limg_hip_blocked_decode_stream_windows_device", jobs, status)
+        return self._decode_windows_device("limg_hip_blocked_decode_stream_windows_device", jobs, False, None, status)
 
     def decode_stream_windows(self, stream, wins, outs=None):
         """host stream bytes, wins: (x, y, w, h) each -> the list of numpy uint32 (h, w) arrays; outs: per window a uint32 view that receives it (rows may be strided)
         or None.  The stream is uploaded once."""
-        return self._decode_stream_windows("limg_hip_decode_stream_windows", stream, wins, outs)
+        return self._decode_windows_host("limg_hip_decode_stream_windows", stream, wins, False, None, outs)
 
     def blocked_decode_stream_windows(self, stream, wins, outs=None):
-        return self._decode_stream_windows("limg_hip_blocked_decode_stream_windows", stream, wins, outs)
-
-    # ---- batched window decode into planar float tensors (contract: include/limg_hip.h) ----
-    def _decode_stream_windows_tensor_device(self, name, jobs, fmt, status):
-        import torch
-        dtype = torch.float16 if fmt.type == TENSOR_F16 else torch.float32
-        table = (TensorWindowJob * len(jobs))()
-        outs = []
-        for i, (stream, nbytes, W, H, x, y, w, h, out, row_stride, plane_stride) in enumerate(jobs):
-            if out is None:
-                out = torch.empty((fmt.planes, h, w), dtype=dtype, device=stream.device)
-            assert out.dtype == dtype, (out.dtype, dtype)
-            if row_stride is None:
-                row_stride = out.stride(1) if out.dim() == 3 else w
-            if plane_stride is None:
-                plane_stride = out.stride(0) if out.dim() == 3 else row_stride * h
-            table[i] = TensorWindowJob(stream.data_ptr(), int(nbytes), W, H, TensorWindow(x, y, w, h, out.data_ptr(), int(row_stride), int(plane_stride)))
-            outs.append(out)
-        self._stream_call(name, table, len(jobs), C.byref(fmt), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
-        return outs
-
-    def _decode_stream_windows_tensor(self, name, stream, wins, fmt, outs):
-        stream = np.ascontiguousarray(stream, dtype=np.uint8)
-        dtype = np.float16 if fmt.type == TENSOR_F16 else np.float32
-        eb = np.dtype(dtype).itemsize
-        outs = [None] * len(wins) if outs is None else list(outs)
-        table = (TensorWindow * len(wins))()
-        for i, (x, y, w, h) in enumerate(wins):
-            if outs[i] is None:
-                outs[i] = np.zeros((fmt.planes, h, w), dtype=dtype)
-            out = outs[i]
-            assert out.dtype == dtype and out.ndim == 3 and out.shape[0] >= fmt.planes and out.strides[2] == eb and out.strides[1] % eb == 0 and out.strides[0] % eb == 0, \
-                "out: (planes, h, w) of the format's type, elements of a row contiguous"
-            table[i] = TensorWindow(x, y, w, h, out.ctypes.data, out.strides[1] // eb, out.strides[0] // eb)
-        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins), C.byref(fmt))
-        return outs
+        return self._decode_windows_host("limg_hip_blocked_decode_stream_windows", stream, wins, False, None, outs)
 
     def decode_stream_windows_tensor_device(self, jobs, fmt, status=None):
         """jobs: (stream tensor, nbytes, W, H, x, y, w, h, out, row_stride, plane_stride) each; out: a torch CUDA tensor of fmt's type whose first element receives
         element (0, 0, 0) of the window, rows row_stride and planes plane_stride elements apart (None: out's own strides; out=None allocates (planes, h, w)).
         fmt: tensor_format(...).  status: torch int32 CUDA tensor of len(jobs) words or None.  One launch for all jobs, asynchronous on torch's current stream.
         Returns the list of output tensors."""
-        return self._decode_stream_windows_tensor_device("limg_hip_decode_stream_windows_tensor_device", jobs, fmt, status)
+        return self._decode_windows_device("limg_hip_decode_stream_windows_tensor_device", jobs, False, fmt, status)
 
     def blocked_decode_stream_windows_tensor_device(self, jobs, fmt, status=None):
-        return self._decode_stream_windows_tensor_device("limg_hip_blocked_decode_stream_windows_tensor_device", jobs, fmt, status)
+        return self._decode_windows_device("limg_hip_blocked_decode_stream_windows_tensor_device", jobs, False, fmt, status)
 
     def decode_stream_windows_tensor(self, stream, wins, fmt, outs=None):
         """host stream bytes, wins: (x, y, w, h) each -> the list of numpy (planes, h, w) arrays of fmt's type; outs: per window a view that receives it (rows and
         planes may be strided) or None.  The stream is uploaded once."""
-        return self._decode_stream_windows_tensor("limg_hip_decode_stream_windows_tensor", stream, wins, fmt, outs)
+        return self._decode_windows_host("limg_hip_decode_stream_windows_tensor", stream, wins, False, fmt, outs)
 
     def blocked_decode_stream_windows_tensor(self, stream, wins, fmt, outs=None):
-        return self._decode_stream_windows_tensor("limg_hip_blocked_decode_stream_windows_tensor", stream, wins, fmt, outs)
+        return self._decode_windows_host("limg_hip_blocked_decode_stream_windows_tensor", stream, wins, False, fmt, outs)
+
+    def _decode_crops(self, jobs, scaled, h, w, dtype, scale, bias, planes, blocked, out):
+        import torch
+        fmt = tensor_format(dtype, planes, scale, bias)
+        if out is None:
+            out = torch.empty((len(jobs), planes, h, w), dtype=dtype, device=jobs[0][0].device)
+        assert tuple(out.shape) == (len(jobs), planes, h, w) and out.is_contiguous() and out.dtype == dtype
+        assert all(len(j) == 6 + scaled for j in jobs)
+        table = [(*j, w, h, out[i], w, h * w) for i, j in enumerate(jobs)]
+        getattr(self, ("blocked_" if blocked else "") + "decode_stream_windows_" + ("scaled_" if scaled else "") + "tensor_device")(table, fmt)
+        return out
 
     def decode_crops_device(self, jobs, h, w, dtype, scale, bias, planes=3, blocked=False, out=None):
         """The loader step: jobs: (stream tensor, nbytes, W, H, x, y) each -- the h x w crop at (x, y) of each stream -> ONE contiguous (N, planes, h, w) torch tensor
         of `dtype` (torch.float32 / torch.float16), element = byte * scale[c] + bias[c]; job i fills slice i.  out: the tensor to fill.  One call of the version's
         tensor entry, asynchronous on torch's current stream."""
-        import torch
-        fmt = tensor_format(dtype, planes, scale, bias)
-        if out is None:
-            out = torch.empty((len(jobs), planes, h, w), dtype=dtype, device=jobs[0][0].device)
-        assert tuple(out.shape) == (len(jobs), planes, h, w) and out.is_contiguous() and out.dtype == dtype
-        table = [(stream, nbytes, W, H, x, y, w, h, out[i], w, h * w) for i, (stream, nbytes, W, H, x, y) in enumerate(jobs)]
-        (self.blocked_decode_stream_windows_tensor_device if blocked else self.decode_stream_windows_tensor_device)(table, fmt)
-        return out
+        return self._decode_crops(jobs, False, h, w, dtype, scale, bias, planes, blocked, out)
 
     # ---- reduced-scale window decode: every job at its own level 0 .. 3, RGBA8 or tensors (contract: include/limg_hip.h) ----
-    def _decode_stream_windows_scaled_device(self, name, jobs, status):
-        import torch
-        table = (ScaledWindowJob * len(jobs))()
-        outs = []
-        for i, (stream, nbytes, W, H, level, x, y, w, h, out, out_stride) in enumerate(jobs):
-            if out is None:
-                out = torch.empty((h, w), dtype=torch.int32, device=stream.device)
-            if out_stride is None:
-                out_stride = out.stride(0) if out.dim() == 2 else w
-            table[i] = ScaledWindowJob(stream.data_ptr(), int(nbytes), W, H, ScaledWindow(x, y, w, h, out.data_ptr(), int(out_stride), level))
-            outs.append(out)
-        self._stream_call(name, table, len(jobs), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
-        return outs
-
-    def _decode_stream_windows_scaled_tensor_device(self, name, jobs, fmt, status):
-        import torch
-        dtype = torch.float16 if fmt.type == TENSOR_F16 else torch.float32
-        table = (ScaledTensorWindowJob * len(jobs))()
-        outs = []
-        for i, (stream, nbytes, W, H, level, x, y, w, h, out, row_stride, plane_stride) in enumerate(jobs):
-            if out is None:
-                out = torch.empty((fmt.planes, h, w), dtype=dtype, device=stream.device)
-            assert out.dtype == dtype, (out.dtype, dtype)
-            if row_stride is None:
-                row_stride = out.stride(1) if out.dim() == 3 else w
-            if plane_stride is None:
-                plane_stride = out.stride(0) if out.dim() == 3 else row_stride * h
-            table[i] = ScaledTensorWindowJob(stream.data_ptr(), int(nbytes), W, H, ScaledTensorWindow(x, y, w, h, out.data_ptr(), int(row_stride), int(plane_stride), level))
-            outs.append(out)
-        self._stream_call(name, table, len(jobs), C.byref(fmt), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
-        return outs
-
-    def _decode_stream_windows_scaled(self, name, stream, wins, outs):
-        stream = np.ascontiguousarray(stream, dtype=np.uint8)
-        outs = [None] * len(wins) if outs is None else list(outs)
-        table = (ScaledWindow * len(wins))()
-        for i, (level, x, y, w, h) in enumerate(wins):
-            if outs[i] is None:
-                outs[i] = np.zeros((h, w), dtype=np.uint32)
-            out = outs[i]
-            assert out.dtype == np.uint32 and out.ndim == 2 and out.strides[1] == 4 and out.strides[0] % 4 == 0, "out: uint32 rows, pixels contiguous"
-            table[i] = ScaledWindow(x, y, w, h, out.ctypes.data, out.strides[0] // 4, level)
-        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins))
-        return outs
-
-    def _decode_stream_windows_scaled_tensor(self, name, stream, wins, fmt, outs):
-        stream = np.ascontiguousarray(stream, dtype=np.uint8)
-        dtype = np.float16 if fmt.type == TENSOR_F16 else np.float32
-        eb = np.dtype(dtype).itemsize
-        outs = [None] * len(wins) if outs is None else list(outs)
-        table = (ScaledTensorWindow * len(wins))()
-        for i, (level, x, y, w, h) in enumerate(wins):
-            if outs[i] is None:
-                outs[i] = np.zeros((fmt.planes, h, w), dtype=dtype)
-            out = outs[i]
-            assert out.dtype == dtype and out.ndim == 3 and out.shape[0] >= fmt.planes and out.strides[2] == eb and out.strides[1] % eb == 0 and out.strides[0] % eb == 0, \
-                "out: (planes, h, w) of the format's type, elements of a row contiguous"
-            table[i] = ScaledTensorWindow(x, y, w, h, out.ctypes.data, out.strides[1] // eb, out.strides[0] // eb, level)
-        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins), C.byref(fmt))
-        return outs
-
     def decode_stream_windows_scaled_device(self, jobs, status=None):
         """jobs: (stream tensor, nbytes, W, H, level, x, y, w, h, out, out_stride) each: the jobs of decode_stream_windows_device with the level 0 .. 3 behind the image
         size; x, y, w, h are in that level's coordinates, inside (W >> level) x (H >> level).  One launch whatever the mix of levels."""
-        return self._decode_stream_windows_scaled_device("limg_hip_decode_stream_windows_scaled_device", jobs, status)
+        return self._decode_windows_device("limg_hip_decode_stream_windows_scaled_device", jobs, True, None, status)
 
     def blocked_decode_stream_windows_scaled_device(self, jobs, status=None):
-        return self._decode_stream_windows_scaled_device("limg_hip_blocked_decode_stream_windows_scaled_device", jobs, status)
+        return self._decode_windows_device("limg_hip_blocked_decode_stream_windows_scaled_device", jobs, True, None, status)
 
     def decode_stream_windows_scaled_tensor_device(self, jobs, fmt, status=None):
         """jobs: (stream tensor, nbytes, W, H, level, x, y, w, h, out, row_stride, plane_stride) each, as decode_stream_windows_tensor_device with the level"""
-        return self._decode_stream_windows_scaled_tensor_device("limg_hip_decode_stream_windows_scaled_tensor_device", jobs, fmt, status)
+        return self._decode_windows_device("limg_hip_decode_stream_windows_scaled_tensor_device", jobs, True, fmt, status)
 
     def blocked_decode_stream_windows_scaled_tensor_device(self, jobs, fmt, status=None):
-        return self._decode_stream_windows_scaled_tensor_device("limg_hip_blocked_decode_stream_windows_scaled_tensor_device", jobs, fmt, status)
+        return self._decode_windows_device("limg_hip_blocked_decode_stream_windows_scaled_tensor_device", jobs, True, fmt, status)
 
     def decode_stream_windows_scaled(self, stream, wins, outs=None):
         """host stream bytes, wins: (level, x, y, w, h) each -> the list of numpy uint32 (h, w) arrays; one upload and one batched call for all levels"""
-        return self._decode_stream_windows_scaled("limg_hip_decode_stream_windows_scaled", stream, wins, outs)
+        return self._decode_windows_host("limg_hip_decode_stream_windows_scaled", stream, wins, True, None, outs)
 
     def blocked_decode_stream_windows_scaled(self, stream, wins, outs=None):
-        return self._decode_stream_windows_scaled("limg_hip_blocked_decode_stream_windows_scaled", stream, wins, outs)
+        return self._decode_windows_host("limg_hip_blocked_decode_stream_windows_scaled", stream, wins, True, None, outs)
 
     def decode_stream_windows_scaled_tensor(self, stream, wins, fmt, outs=None):
         """host stream bytes, wins: (level, x, y, w, h) each -> the list of numpy (planes, h, w) arrays of fmt's type"""
-        return self._decode_stream_windows_scaled_tensor("limg_hip_decode_stream_windows_scaled_tensor", stream, wins, fmt, outs)
+        return self._decode_windows_host("limg_hip_decode_stream_windows_scaled_tensor", stream, wins, True, fmt, outs)
 
     def blocked_decode_stream_windows_scaled_tensor(self, stream, wins, fmt, outs=None):
-        return self._decode_stream_windows_scaled_tensor("limg_hip_blocked_decode_stream_windows_scaled_tensor", stream, wins, fmt, outs)
+        return self._decode_windows_host("limg_hip_blocked_decode_stream_windows_scaled_tensor", stream, wins, True, fmt, outs)
 
     def decode_crops_scaled_device(self, jobs, h, w, dtype, scale, bias, planes=3, blocked=False, out=None):
         """The loader step where every sample picks its own level: jobs: (stream tensor, nbytes, W, H, level, x, y) each -- the h x w crop at (x, y) of the stream's
         level-`level` image -> ONE contiguous (N, planes, h, w) torch tensor of `dtype`, as decode_crops_device.  One call of the version's scaled tensor entry."""
-        import torch
-        fmt = tensor_format(dtype, planes, scale, bias)
-        if out is None:
-            out = torch.empty((len(jobs), planes, h, w), dtype=dtype, device=jobs[0][0].device)
-        assert tuple(out.shape) == (len(jobs), planes, h, w) and out.is_contiguous() and out.dtype == dtype
-        table = [(stream, nbytes, W, H, level, x, y, w, h, out[i], w, h * w) for i, (stream, nbytes, W, H, level, x, y) in enumerate(jobs)]
-        (self.blocked_decode_stream_windows_scaled_tensor_device if blocked else self.decode_stream_windows_scaled_tensor_device)(table, fmt)
-        return out
+        return self._decode_crops(jobs, True, h, w, dtype, scale, bias, planes, blocked, out)
 
     def check(self):
         _check(self.lib.limg_hip_check_device_status(self.ctx), "limg_hip_check_device_status")

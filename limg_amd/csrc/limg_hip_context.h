@@ -142,7 +142,7 @@ struct limg_hip_context
   DevBuf commWords; // [0] this rank's value, [1] its chain base, [8 ...] the all-gathered values
   DevBuf streamFac, streamTiles, streamUnits, streamStatus, streamBuf; // stream packer: 3 factor planes, per-tile payload words; decode status word; host-entry staging
   DevBuf streamTable, streamSizes; // batched stream encode: one StreamImage per image of the list; the finished streams' sizes side by side (one download)
-  // version 2 stream of the merged-block encoder (limg_hip_stream_api.hip): per rectangle its first 64-pixel run, per tile of rectangles its totals; the
+  // version 2 stream of the merged-block encoder (limg_hip_stream_api.hip, limg_hip_stream_window_api.hip): per rectangle its first 64-pixel run, per tile of rectangles its totals; the
   // decoder's block -> rectangle map and its per-call words
   DevBuf bsUnits, bsTiles, bsMap, bsState;
   // batched window decode (limg_hip_*decode_stream_windows*): a call's job table -- and, version 2, its map and per-job state words -- lives in one slot of a small
@@ -216,6 +216,15 @@ namespace limg_hip
     for (unsigned t = 0; t < started; t++) pool[t].join();
     delete[] pool;
   }
+
+  // ---- what the stream entries (limg_hip_stream_api.hip) and the window entries (limg_hip_stream_window_api.hip) share ----
+  int device_cus(const limg_hip_context *c);
+  limg_hip_result ensure_stream_status(limg_hip_context *c, hipStream_t s); // the decoders' status word, zeroed on `s` when it is first made
+  // one RGBA8 window, checked without touching the device, as kernel parameters with the status word set; bound: the version's limg_hip_*stream_bound(sizeX, sizeY)
+  limg_hip_result window_params(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width,
+                                size_t height, uint32_t *pOut, size_t outStridePixels, hipStream_t s, WindowDecodeParams &wp);
+  // version 2's one decode, the full image's and a window's: wp from window_params
+  limg_hip_result blocked_window_decode(limg_hip_context *c, WindowDecodeParams &wp, hipStream_t s);
 
   // ---- the 8x8 encode (limg_hip_encode.hip, limg_hip_encode_ragged.hip) ----
   struct Partition { uint32_t chainCount, chainRows; };

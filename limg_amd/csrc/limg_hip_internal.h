@@ -268,14 +268,10 @@ namespace limg_hip
     const uint32_t *groupItemBase; // nGroups + 1: exclusive prefix of ceil(nBlocks / 64), the map kernel's work items (64 rectangles each; R <= nBlocks)
     uint32_t nGroups, totalItems;
   };
-  void launch_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s);
-  void launch_blocked_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s);
-  // ... into planar float tensors: the same job table (planeStride set, out / outStride / vecOut in elements of f.type), one format per launch
-  void launch_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s);
-  void launch_blocked_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s);
-  // ... at reduced scale (the *_scaled entries): kernels of their own that honour every job's log2Scale; f: the tensor format, or NULL for packed RGBA8
-  void launch_stream_windows_scaled(const WindowBatchParams &b, const limg_hip_tensor_format *f, int cus, hipStream_t s);
-  void launch_blocked_stream_windows_scaled(const WindowBatchParams &b, const limg_hip_tensor_format *f, int cus, hipStream_t s);
+  // f: NULL for packed RGBA8, else the planar float format of the launch (the same job table with planeStride set and out / outStride / vecOut in elements of f's
+  // type); scaled: the *_scaled entries' kernels, which honour every job's log2Scale -- a plain job table never goes to them
+  void launch_stream_windows(const WindowBatchParams &b, bool scaled, const limg_hip_tensor_format *f, int cus, hipStream_t s);
+  void launch_blocked_stream_windows(const WindowBatchParams &b, bool scaled, const limg_hip_tensor_format *f, int cus, hipStream_t s);
   static_assert(sizeof(WindowDecodeParams) == 128, "the job table's entry: log2Scale must not grow it");
 
   void launch_stream_pack(const StreamParams &p, hipStream_t s);

@@ -1,28 +1,28 @@
-// limg_hip_stream_api.hip -- the compact stream entries of the C ABI, both versions.  Version 1: 8x8 encode in compact mode + the packer of limg_hip_stream.hip.
-// Version 2: the merged-block encoder in compact mode (blocked_encode_device without planes, limg_hip_blocked_api.hip) + the scan and pack kernels of
-// limg_hip_blocked_stream.hip.  Decode, header check and the host-pointer forms of each; what the two versions do alike is written once, in the namespace below.
+// limg_hip_stream_api.hip -- the compact stream entries of the C ABI, both versions: encode, batched encode, whole-image decode, header check and the host-pointer
+// forms of each.  Version 1: 8x8 encode in compact mode + the packer of limg_hip_stream.hip.  Version 2: the merged-block encoder in compact mode
+// (blocked_encode_device without planes, limg_hip_blocked_api.hip) + the scan and pack kernels of limg_hip_blocked_stream.hip; its whole-image decode is a window
+// decode.  What the two versions do alike is written once, in the anonymous namespace below.  The window entries: limg_hip_stream_window_api.hip.
 #include "limg_hip_context.h"
 
-#include <algorithm>
-#include <type_traits>
 #include <vector>
 
 using namespace limg_hip;
 
+// ---- shared with limg_hip_stream_window_api.hip (declared in limg_hip_context.h) ----
+int limg_hip::device_cus(const limg_hip_context *c) { return c->persistentWorkgroups / 5; }
+
+// the status word the stream decoders share (limg_hip_check_device_status reads it), then the version 1 decode kernel's store sink (see DecodeParams::sink)
+limg_hip_result limg_hip::ensure_stream_status(limg_hip_context *c, hipStream_t s)
+{
+  if (c->streamStatus.p) return limg_hip_success;
+  const limg_hip_result r = c->streamStatus.ensure(256 + 2048);
+  if (r != limg_hip_success) return r;
+  HIP_TRY(hipMemsetAsync(c->streamStatus.p, 0, 8, s));
+  return limg_hip_success;
+}
+
 namespace
 {
-  int device_cus(const limg_hip_context *c) { return c->persistentWorkgroups / 5; }
-
-  // the status word the stream decoders share (limg_hip_check_device_status reads it), then the version 1 decode kernel's store sink (see DecodeParams::sink)
-  limg_hip_result ensure_stream_status(limg_hip_context *c, hipStream_t s)
-  {
-    if (c->streamStatus.p) return limg_hip_success;
-    const limg_hip_result r = c->streamStatus.ensure(256 + 2048);
-    if (r != limg_hip_success) return r;
-    HIP_TRY(hipMemsetAsync(c->streamStatus.p, 0, 8, s));
-    return limg_hip_success;
-  }
-
   // what the packer's scan left in the stream's header; waits for `s`
   limg_hip_result stream_total_bytes(const uint8_t *dStream, hipStream_t s, size_t *pBytes)
   {
@@ -133,344 +133,6 @@ namespace
     HIP_TRY(hipGetLastError());
     c->packTimed = true;
     return pBytes ? stream_total_bytes(dStream, s, pBytes) : limg_hip_success;
-  }
-
-  // ---- window decode: limg_hip_*decode_stream_window* (kernels: limg_hip_stream_window.hip) ----
-  // Where a window's pixels go: packed RGBA8 (planes == 0: elemBytes 4, one element per pixel) or `planes` planes of float / _Float16 (the tensor entries).
-  struct WindowOut
-  {
-    void *p;
-    size_t rowStride, planeStride; // in elements
-    uint32_t elemBytes, planes;
-  };
-  WindowOut window_out(const limg_hip_window &w, const limg_hip_tensor_format *) { return { w.pOut, w.outStridePixels, 0, 4u, 0u }; }
-  WindowOut window_out(const limg_hip_tensor_window &w, const limg_hip_tensor_format *f)
-  {
-    return { w.pOut, w.rowStride, w.planeStride, f->type == LIMG_HIP_TENSOR_F16 ? 2u : 4u, f->planes };
-  }
-  WindowOut window_out(const limg_hip_scaled_window &w, const limg_hip_tensor_format *) { return { w.pOut, w.outStridePixels, 0, 4u, 0u }; }
-  WindowOut window_out(const limg_hip_scaled_tensor_window &w, const limg_hip_tensor_format *f)
-  {
-    return { w.pOut, w.rowStride, w.planeStride, f->type == LIMG_HIP_TENSOR_F16 ? 2u : 4u, f->planes };
-  }
-  // the four window types: which go to planes, which carry a level (the others are level 0)
-  template <class WIN> struct WindowKind { static constexpr bool tensor = false, scaled = false; };
-  template <> struct WindowKind<limg_hip_tensor_window> { static constexpr bool tensor = true, scaled = false; };
-  template <> struct WindowKind<limg_hip_scaled_window> { static constexpr bool tensor = false, scaled = true; };
-  template <> struct WindowKind<limg_hip_scaled_tensor_window> { static constexpr bool tensor = true, scaled = true; };
-  template <class WIN> size_t window_level(const WIN &w)
-  {
-    if constexpr (WindowKind<WIN>::scaled) return w.log2Scale;
-    else return 0;
-  }
-  bool tensor_format_ok(const limg_hip_tensor_format *f) { return (f->type == LIMG_HIP_TENSOR_F32 || f->type == LIMG_HIP_TENSOR_F16) && (f->planes == 3u || f->planes == 4u); }
-
-  // the window's size and the output's strides: what every window entry, device or host, checks first
-  limg_hip_result window_out_check(size_t width, size_t height, const WindowOut &o)
-  {
-    if (width == 0 || height == 0 || o.rowStride < width) return limg_hip_error_InvalidParameter;
-    if (o.planes)
-    { // planeStride >= (height - 1) * rowStride + width, without overflow
-      if (height > 1 && o.rowStride > ((size_t)-1 - width) / (height - 1)) return limg_hip_error_InvalidParameter;
-      if (o.planeStride < (height - 1) * o.rowStride + width) return limg_hip_error_InvalidParameter;
-    }
-    return limg_hip_success;
-  }
-  bool out_aligned(const WindowOut &o) { return ((uintptr_t)o.p & (o.elemBytes - 1u)) == 0; }
-  bool window_inside(size_t sizeX, size_t sizeY, size_t x0, size_t y0, size_t width, size_t height)
-  {
-    return !(x0 >= sizeX || width > sizeX - x0 || y0 >= sizeY || height > sizeY - y0);
-  }
-
-  // the checks and the parameters the two versions share, without touching the device; `bound`: the version's limg_hip_*stream_bound(sizeX, sizeY).  status, map and
-  // state are the caller's to set.  level: the scaled entries' log2Scale -- the window is then in level coordinates, inside (sizeX >> level) x (sizeY >> level), and wp
-  // gets its source footprint (x0 .. height times 1 << level: inside the image, so nothing overflows) with vecOut stated on the window itself.
-  limg_hip_result window_fill(const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width, size_t height,
-                              const WindowOut &o, WindowDecodeParams &wp, size_t level = 0)
-  {
-    if (level > 3 || window_out_check(width, height, o) != limg_hip_success || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
-    if (((uintptr_t)pStream & 15u) != 0 || !out_aligned(o)) return limg_hip_error_InvalidParameter;
-    if (!window_inside(sizeX >> level, sizeY >> level, x0, y0, width, height)) return limg_hip_error_OutOfBounds;
-    const size_t outX0 = x0;
-    x0 <<= level; y0 <<= level; width <<= level; height <<= level;
-    memset(&wp, 0, sizeof(wp));
-    wp.sizeX = (uint32_t)sizeX; wp.sizeY = (uint32_t)sizeY;
-    wp.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); wp.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
-    wp.nBlocks = wp.blocksX * wp.blocksY;
-    wp.stream = pStream; wp.streamBytes = streamBytes;
-    wp.x0 = (uint32_t)x0; wp.y0 = (uint32_t)y0; wp.width = (uint32_t)width; wp.height = (uint32_t)height;
-    wp.bx0 = (uint32_t)(x0 / kBlock); wp.by0 = (uint32_t)(y0 / kBlock);
-    wp.wbx = (uint32_t)((x0 + width - 1) / kBlock) - wp.bx0 + 1; wp.wby = (uint32_t)((y0 + height - 1) / kBlock) - wp.by0 + 1;
-    wp.out = (uint32_t *)o.p; wp.outStride = o.rowStride; wp.planeStride = o.planeStride;
-    const size_t per = 16u / o.elemBytes; // elements per 16-byte store (planeStride is 0 for RGBA)
-    wp.vecOut = ((uintptr_t)o.p & 15u) == 0 && o.rowStride % per == 0 && o.planeStride % per == 0 && outX0 % per == 0;
-    wp.log2Scale = (uint32_t)level;
-    return limg_hip_success;
-  }
-
-  limg_hip_result window_params(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width,
-                                size_t height, uint32_t *pOut, size_t outStridePixels, hipStream_t s, WindowDecodeParams &wp)
-  {
-    limg_hip_result r = window_fill(pStream, streamBytes, sizeX, sizeY, bound, x0, y0, width, height, WindowOut{ pOut, outStridePixels, 0, 4u, 0u }, wp);
-    if (r != limg_hip_success) return r;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
-    wp.status = (uint32_t *)c->streamStatus.p;
-    return limg_hip_success;
-  }
-
-  // Version 2's one decode, the full image's and a window's: wp from window_params; the map of the window's blocks (not the image's) and the call's state words, then
-  // the two kernels
-  limg_hip_result blocked_window_decode(limg_hip_context *c, WindowDecodeParams &wp, hipStream_t s)
-  {
-    const size_t mapBytes = (size_t)wp.wbx * wp.wby * 4;
-    limg_hip_result r;
-    if ((r = c->bsMap.ensure(mapBytes)) != limg_hip_success) return r;
-    if ((r = c->bsState.ensure(64)) != limg_hip_success) return r;
-    HIP_TRY(hipMemsetAsync(c->bsMap.p, 0xFF, mapBytes, s)); // no block has a rectangle yet
-    HIP_TRY(hipMemsetAsync(c->bsState.p, 0, 64, s));
-    wp.map = (uint32_t *)c->bsMap.p; wp.state = (uint32_t *)c->bsState.p;
-    launch_blocked_stream_window_decode(wp, device_cus(c), s);
-    HIP_TRY(hipGetLastError());
-    return limg_hip_success;
-  }
-
-  // info(&sizeX, &sizeY, &total): the version's header check.  deviceDecode(dStream, total, sizeX, sizeY, dOut): into context staging at stride `width`; only a stream
-  // that passed reaches pOut
-  template <class INFO, class DECODE>
-  limg_hip_result decode_window_host(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height, uint32_t *pOut,
-                                     size_t outStridePixels, INFO &&info, DECODE &&deviceDecode)
-  {
-    if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
-    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    if (width == 0 || height == 0 || outStridePixels < width) return limg_hip_error_InvalidParameter;
-    size_t sizeX = 0, sizeY = 0, total = 0;
-    limg_hip_result r = info(&sizeX, &sizeY, &total);
-    if (r != limg_hip_success) return r;
-    if (total > streamBytes) return limg_hip_error_OutOfBounds;
-    if (x0 >= sizeX || width > sizeX - x0 || y0 >= sizeY || height > sizeY - y0) return limg_hip_error_OutOfBounds;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
-    if ((r = c->planes.ensure(width * height * 4)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice));
-    if ((r = deviceDecode((const uint8_t *)c->streamBuf.p, total, sizeX, sizeY, (uint32_t *)c->planes.p)) != limg_hip_success) return r;
-    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy2D(pOut, outStridePixels * 4, c->planes.p, width * 4, width * 4, height, hipMemcpyDeviceToHost));
-    return limg_hip_success;
-  }
-
-  // ---- batched window decode: limg_hip_*decode_stream_windows* (kernels: limg_hip_stream_window.hip) ----
-  size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-  // One call: every job checked on the host before anything touches the device, then the job table built in a pinned slot of the context's ring, copied on `s`,
-  // and the version's one (two) launches.  blocked: version 2.  JOB: limg_hip_window_job (packed RGBA8; pFormat is not looked at) or limg_hip_tensor_window_job
-  // (planes of pFormat's type): the same checks, table and launches but for where the pixels go; their _scaled_ twins: the same again with the job's level handed to
-  // window_fill and the scaled kernels launched.
-  template <class JOB>
-  limg_hip_result decode_windows_device(limg_hip_context *c, const JOB *pJobs, size_t count, const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, hipStream_t s,
-                                        bool blocked)
-  {
-    typedef decltype(JOB::window) WIN;
-    constexpr bool tensor = WindowKind<WIN>::tensor, scaled = WindowKind<WIN>::scaled;
-    if (!c || !pJobs || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
-    if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
-    if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
-    // pass 1: the single-window entry's checks, job by job in its order; the sums the table's layout needs
-    unsigned long long units = 0, blocks = 0;
-    WindowDecodeParams wp;
-    for (size_t i = 0; i < count; i++)
-    {
-      const JOB &j = pJobs[i];
-      if (!j.pStream || !j.window.pOut) return limg_hip_error_ArgumentNull;
-      const size_t bound = blocked ? limg_hip_blocked_stream_bound(j.sizeX, j.sizeY) : limg_hip_stream_bound(j.sizeX, j.sizeY);
-      const limg_hip_result r = window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height,
-                                            window_out(j.window, pFormat), wp, window_level(j.window));
-      if (r != limg_hip_success) return r;
-      if (!blocked && j.streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
-      units += (unsigned long long)((wp.wbx + (blocked ? 7u : 63u)) / (blocked ? 8u : 64u)) * wp.wby;
-      blocks += (unsigned long long)wp.wbx * wp.wby;
-    }
-    if (units > 0xFFFFFFFFull || blocks > 0xFFFFFFFFull) return limg_hip_error_InvalidParameter;
-
-    HIP_TRY(hipSetDevice(c->device));
-    limg_hip_result r;
-    if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
-    // the slot: [jobs | unitBase | groups | groupJobs | groupItemBase] is uploaded; [state | map] behind it exists on the device only (version 2)
-    const size_t oJobs = 0, oUnitBase = align16(oJobs + count * sizeof(WindowDecodeParams)), oGroups = align16(oUnitBase + (count + 1) * 4);
-    const size_t oGroupJobs = blocked ? align16(oGroups + count * sizeof(WindowGroup)) : oGroups, oItemBase = blocked ? align16(oGroupJobs + count * 4) : oGroups;
-    const size_t upload = blocked ? align16(oItemBase + (count + 1) * 4) : oGroups;
-    const size_t oState = upload, oMap = align16(oState + (blocked ? count * 8 : 0)), total = oMap + (blocked ? (size_t)blocks * 4 : 0);
-    limg_hip_context::WindowSlot &slot = c->windowSlots[c->windowSlotNext];
-    c->windowSlotNext = (c->windowSlotNext + 1) % limg_hip_context::kWindowSlots;
-    if (slot.busy)
-    { // the call that used this slot last: its copy has left the pinned table and its kernels are done with the device copy
-      HIP_TRY(hipEventSynchronize(slot.done));
-      slot.busy = false;
-    }
-    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    if ((r = slot.host.ensure(upload)) != limg_hip_success) return r;
-    if ((r = slot.dev.ensure(total)) != limg_hip_success) return r;
-    uint8_t *hb = (uint8_t *)slot.host.p, *db = (uint8_t *)slot.dev.p;
-    WindowDecodeParams *jobs = (WindowDecodeParams *)(hb + oJobs);
-    uint32_t *unitBase = (uint32_t *)(hb + oUnitBase);
-
-    // pass 2: the table (the checks of pass 1 cannot fail again)
-    uint32_t unitAt = 0, blockAt = 0;
-    for (size_t i = 0; i < count; i++)
-    {
-      const JOB &j = pJobs[i];
-      const size_t bound = blocked ? limg_hip_blocked_stream_bound(j.sizeX, j.sizeY) : limg_hip_stream_bound(j.sizeX, j.sizeY);
-      (void)window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, bound, j.window.x0, j.window.y0, j.window.width, j.window.height, window_out(j.window, pFormat), jobs[i],
-                        window_level(j.window));
-      jobs[i].status = (uint32_t *)c->streamStatus.p;
-      if (blocked)
-      {
-        jobs[i].state = (uint32_t *)(db + oState) + 2 * i;
-        jobs[i].map = (uint32_t *)(db + oMap) + blockAt;
-      }
-      unitBase[i] = unitAt;
-      unitAt += ((jobs[i].wbx + (blocked ? 7u : 63u)) / (blocked ? 8u : 64u)) * jobs[i].wby;
-      blockAt += jobs[i].wbx * jobs[i].wby;
-    }
-    unitBase[count] = unitAt;
-    WindowBatchParams b;
-    memset(&b, 0, sizeof(b));
-    b.jobs = (const WindowDecodeParams *)(db + oJobs); b.unitBase = (const uint32_t *)(db + oUnitBase);
-    b.count = (uint32_t)count; b.totalUnits = unitAt;
-    b.status = (uint32_t *)c->streamStatus.p; b.jobStatus = pJobStatus;
-    if (blocked)
-    { // groups: the jobs sorted by stream (in place, in the table: no allocation), then one group per run of equal keys
-      WindowGroup *groups = (WindowGroup *)(hb + oGroups);
-      uint32_t *groupJobs = (uint32_t *)(hb + oGroupJobs), *itemBase = (uint32_t *)(hb + oItemBase);
-      for (size_t i = 0; i < count; i++) groupJobs[i] = (uint32_t)i;
-      auto less = [jobs](uint32_t x, uint32_t y) {
-        const WindowDecodeParams &a = jobs[x], &bb = jobs[y];
-        if (a.stream != bb.stream) return (uintptr_t)a.stream < (uintptr_t)bb.stream;
-        if (a.streamBytes != bb.streamBytes) return a.streamBytes < bb.streamBytes;
-        if (a.sizeX != bb.sizeX) return a.sizeX < bb.sizeX;
-        if (a.sizeY != bb.sizeY) return a.sizeY < bb.sizeY;
-        return x < y;
-      };
-      std::sort(groupJobs, groupJobs + count, less);
-      uint32_t nGroups = 0;
-      unsigned long long items = 0;
-      for (size_t i = 0; i < count; i++)
-      {
-        const WindowDecodeParams &a = jobs[groupJobs[i]];
-        if (i == 0 || a.stream != groups[nGroups - 1].stream || a.streamBytes != groups[nGroups - 1].streamBytes || a.sizeX != groups[nGroups - 1].sizeX ||
-            a.sizeY != groups[nGroups - 1].sizeY)
-        {
-          WindowGroup &g = groups[nGroups];
-          memset(&g, 0, sizeof(g));
-          g.sizeX = a.sizeX; g.sizeY = a.sizeY; g.blocksX = a.blocksX; g.blocksY = a.blocksY; g.nBlocks = a.nBlocks;
-          g.firstJob = (uint32_t)i; g.stream = a.stream; g.streamBytes = a.streamBytes;
-          itemBase[nGroups++] = (uint32_t)items;
-          items += (a.nBlocks + 63u) / 64u; // 64 rectangles per item, at most nBlocks rectangles
-        }
-        groups[nGroups - 1].nJobs++;
-      }
-      if (items > 0xFFFFFFFFull) return limg_hip_error_InvalidParameter;
-      itemBase[nGroups] = (uint32_t)items;
-      b.groups = (const WindowGroup *)(db + oGroups); b.groupJobs = (const uint32_t *)(db + oGroupJobs); b.groupItemBase = (const uint32_t *)(db + oItemBase);
-      b.nGroups = nGroups; b.totalItems = (uint32_t)items;
-    }
-    HIP_TRY(hipMemcpyAsync(db, hb, upload, hipMemcpyHostToDevice, s));
-    slot.busy = true; // from here on the slot is in flight, whatever fails below
-    if (blocked)
-    {
-      HIP_TRY(hipMemsetAsync(db + oState, 0, count * 8, s));
-      HIP_TRY(hipMemsetAsync(db + oMap, 0xFF, (size_t)blocks * 4, s)); // no block has a rectangle yet
-    }
-    if (pJobStatus) HIP_TRY(hipMemsetAsync(pJobStatus, 0, count * 4, s));
-    if (scaled)
-    {
-      if (blocked) launch_blocked_stream_windows_scaled(b, tensor ? pFormat : nullptr, device_cus(c), s);
-      else launch_stream_windows_scaled(b, tensor ? pFormat : nullptr, device_cus(c), s);
-    }
-    else if (tensor)
-    {
-      if (blocked) launch_blocked_stream_windows_tensor(b, *pFormat, device_cus(c), s);
-      else launch_stream_windows_tensor(b, *pFormat, device_cus(c), s);
-    }
-    else if (blocked) launch_blocked_stream_windows_decode(b, device_cus(c), s);
-    else launch_stream_windows_decode(b, device_cus(c), s);
-    const hipError_t launched = hipGetLastError();
-    HIP_TRY(hipEventRecord(slot.done, s));
-    HIP_TRY(launched);
-    return limg_hip_success;
-  }
-
-  // the staged form of a window: densely packed in context memory
-  void stage_window(limg_hip_window &w, void *p) { w.pOut = (uint32_t *)p; w.outStridePixels = w.width; }
-  void stage_window(limg_hip_tensor_window &w, void *p) { w.pOut = p; w.rowStride = w.width; w.planeStride = w.width * w.height; }
-  void stage_window(limg_hip_scaled_window &w, void *p) { w.pOut = (uint32_t *)p; w.outStridePixels = w.width; }
-  void stage_window(limg_hip_scaled_tensor_window &w, void *p) { w.pOut = p; w.rowStride = w.width; w.planeStride = w.width * w.height; }
-  template <class WIN> struct JobOf { typedef limg_hip_window_job type; };
-  template <> struct JobOf<limg_hip_tensor_window> { typedef limg_hip_tensor_window_job type; };
-  template <> struct JobOf<limg_hip_scaled_window> { typedef limg_hip_scaled_window_job type; };
-  template <> struct JobOf<limg_hip_scaled_tensor_window> { typedef limg_hip_scaled_tensor_window_job type; };
-
-  // `count` windows of ONE host stream.  info(&sizeX, &sizeY, &total): the version's header check.  WIN: limg_hip_window or limg_hip_tensor_window (with pFormat), or
-  // their _scaled_ twins: every window then carries its level and is stated, checked and staged in that level's coordinates.
-  template <class WIN, class INFO>
-  limg_hip_result decode_windows_host(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const WIN *pWindows, size_t count,
-                                      const limg_hip_tensor_format *pFormat, bool blocked, INFO &&info)
-  {
-    typedef typename JobOf<WIN>::type JOB;
-    constexpr bool tensor = WindowKind<WIN>::tensor;
-    if (!c || !pStream || !pWindows || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
-    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
-    if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
-    for (size_t i = 0; i < count; i++)
-    {
-      const WIN &w = pWindows[i];
-      if (!w.pOut) return limg_hip_error_ArgumentNull;
-      if (window_level(w) > 3) return limg_hip_error_InvalidParameter;
-      const limg_hip_result ok = window_out_check(w.width, w.height, window_out(w, pFormat));
-      if (ok != limg_hip_success) return ok;
-      if (tensor && !out_aligned(window_out(w, pFormat))) return limg_hip_error_InvalidParameter;
-    }
-    size_t sizeX = 0, sizeY = 0, total = 0;
-    limg_hip_result r = info(&sizeX, &sizeY, &total);
-    if (r != limg_hip_success) return r;
-    if (total > streamBytes) return limg_hip_error_OutOfBounds;
-    const size_t eb = window_out(pWindows[0], pFormat).elemBytes, planes = tensor ? pFormat->planes : 1;
-    const size_t per = 16 / eb;
-    size_t elems = 0; // staging: every window at its own width (plane after plane), on a 16-byte boundary
-    for (size_t i = 0; i < count; i++)
-    {
-      const WIN &w = pWindows[i];
-      if (!window_inside(sizeX >> window_level(w), sizeY >> window_level(w), w.x0, w.y0, w.width, w.height)) return limg_hip_error_OutOfBounds;
-      elems += (planes * w.width * w.height + per - 1) / per * per;
-    }
-    JOB *jobs = new (std::nothrow) JOB[count];
-    if (!jobs) return limg_hip_error_MemoryAllocationFailure;
-    struct Free { JOB *p; ~Free() { delete[] p; } } freeJobs = { jobs };
-    HIP_TRY(hipSetDevice(c->device));
-    if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
-    if ((r = c->planes.ensure(elems * eb)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice)); // once, for all windows
-    size_t at = 0;
-    for (size_t i = 0; i < count; i++)
-    {
-      const WIN &w = pWindows[i];
-      jobs[i].pStream = (const uint8_t *)c->streamBuf.p; jobs[i].streamBytes = total; jobs[i].sizeX = sizeX; jobs[i].sizeY = sizeY;
-      jobs[i].window = w;
-      stage_window(jobs[i].window, (uint8_t *)c->planes.p + at * eb);
-      at += (planes * w.width * w.height + per - 1) / per * per;
-    }
-    if ((r = decode_windows_device(c, jobs, count, pFormat, nullptr, nullptr, blocked)) != limg_hip_success) return r;
-    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r; // a stream refused for any window: no pOut is touched
-    for (size_t i = 0; i < count; i++)
-    {
-      const WIN &w = pWindows[i];
-      const WindowOut o = window_out(w, pFormat);
-      for (size_t pl = 0; pl < planes; pl++)
-        HIP_TRY(hipMemcpy2D((uint8_t *)o.p + pl * o.planeStride * eb, o.rowStride * eb, (const uint8_t *)jobs[i].window.pOut + pl * w.width * w.height * eb, w.width * eb,
-                            w.width * eb, w.height, hipMemcpyDeviceToHost));
-    }
-    return limg_hip_success;
   }
 }
 
@@ -810,152 +472,5 @@ extern "C"
     return decode_stream_host(c, pStream, streamBytes, pOut, outPixels, sizeX, sizeY, total, [&](const uint8_t *dStream, size_t bytes, uint32_t *dOut, size_t w, size_t h) {
       return limg_hip_blocked_decode_stream_device(c, dStream, bytes, dOut, w, h, nullptr);
     });
-  }
-
-  // ---- window decode, both versions ----
-  limg_hip_result limg_hip_decode_stream_window_device(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t x0, size_t y0,
-                                                       size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, void *stream)
-  {
-    if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
-    hipStream_t s = (hipStream_t)stream;
-    WindowDecodeParams wp;
-    const limg_hip_result r = window_params(c, pStream, streamBytes, sizeX, sizeY, limg_hip_stream_bound(sizeX, sizeY), x0, y0, width, height, pOut, outStridePixels, s, wp);
-    if (r != limg_hip_success) return r;
-    if (streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
-    launch_stream_window_decode(wp, device_cus(c), s);
-    HIP_TRY(hipGetLastError());
-    return limg_hip_success;
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_window_device(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t x0, size_t y0,
-                                                               size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, void *stream)
-  {
-    if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
-    hipStream_t s = (hipStream_t)stream;
-    WindowDecodeParams wp;
-    const limg_hip_result r = window_params(c, pStream, streamBytes, sizeX, sizeY, limg_hip_blocked_stream_bound(sizeX, sizeY), x0, y0, width, height, pOut, outStridePixels, s, wp);
-    if (r != limg_hip_success) return r;
-    return blocked_window_decode(c, wp, s);
-  }
-
-  limg_hip_result limg_hip_decode_stream_window(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,
-                                                uint32_t *pOut, size_t outStridePixels)
-  {
-    return decode_window_host(c, pStream, streamBytes, x0, y0, width, height, pOut, outStridePixels,
-                              [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); },
-                              [&](const uint8_t *dStream, size_t bytes, size_t w, size_t h, uint32_t *dOut) {
-                                return limg_hip_decode_stream_window_device(c, dStream, bytes, w, h, x0, y0, width, height, dOut, width, nullptr);
-                              });
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_window(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,
-                                                        uint32_t *pOut, size_t outStridePixels)
-  {
-    return decode_window_host(c, pStream, streamBytes, x0, y0, width, height, pOut, outStridePixels,
-                              [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); },
-                              [&](const uint8_t *dStream, size_t bytes, size_t w, size_t h, uint32_t *dOut) {
-                                return limg_hip_blocked_decode_stream_window_device(c, dStream, bytes, w, h, x0, y0, width, height, dOut, width, nullptr);
-                              });
-  }
-
-  // ---- batched window decode, both versions ----
-  limg_hip_result limg_hip_decode_stream_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
-  {
-    return decode_windows_device(c, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, false);
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
-  {
-    return decode_windows_device(c, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, true);
-  }
-
-  limg_hip_result limg_hip_decode_stream_windows(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count)
-  {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, nullptr, false,
-                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); });
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_windows(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count)
-  {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, nullptr, true,
-                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });
-  }
-
-  // ---- batched window decode into planar float tensors, both versions ----
-  limg_hip_result limg_hip_decode_stream_windows_tensor_device(limg_hip_context *c, const limg_hip_tensor_window_job *pJobs, size_t count, const limg_hip_tensor_format *pFormat,
-                                                               uint32_t *pJobStatus, void *stream)
-  {
-    return decode_windows_device(c, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream, false);
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_windows_tensor_device(limg_hip_context *c, const limg_hip_tensor_window_job *pJobs, size_t count,
-                                                                       const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
-  {
-    return decode_windows_device(c, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream, true);
-  }
-
-  limg_hip_result limg_hip_decode_stream_windows_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows, size_t count,
-                                                        const limg_hip_tensor_format *pFormat)
-  {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, pFormat, false,
-                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); });
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_windows_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows,
-                                                                size_t count, const limg_hip_tensor_format *pFormat)
-  {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, pFormat, true,
-                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });
-  }
-
-  // ---- reduced-scale window decode, both versions, RGBA8 and tensors: the job types with a level ----
-  limg_hip_result limg_hip_decode_stream_windows_scaled_device(limg_hip_context *c, const limg_hip_scaled_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
-  {
-    return decode_windows_device(c, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, false);
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_device(limg_hip_context *c, const limg_hip_scaled_window_job *pJobs, size_t count, uint32_t *pJobStatus,
-                                                                       void *stream)
-  {
-    return decode_windows_device(c, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, true);
-  }
-
-  limg_hip_result limg_hip_decode_stream_windows_scaled_tensor_device(limg_hip_context *c, const limg_hip_scaled_tensor_window_job *pJobs, size_t count,
-                                                                      const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
-  {
-    return decode_windows_device(c, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream, false);
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor_device(limg_hip_context *c, const limg_hip_scaled_tensor_window_job *pJobs, size_t count,
-                                                                              const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
-  {
-    return decode_windows_device(c, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream, true);
-  }
-
-  limg_hip_result limg_hip_decode_stream_windows_scaled(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_window *pWindows, size_t count)
-  {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, nullptr, false,
-                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); });
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_window *pWindows,
-                                                                size_t count)
-  {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, nullptr, true,
-                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });
-  }
-
-  limg_hip_result limg_hip_decode_stream_windows_scaled_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_tensor_window *pWindows,
-                                                               size_t count, const limg_hip_tensor_format *pFormat)
-  {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, pFormat, false,
-                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(pStream, streamBytes, w, h, nullptr, total); });
-  }
-
-  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes,
-                                                                       const limg_hip_scaled_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat)
-  {
-    return decode_windows_host(c, pStream, streamBytes, pWindows, count, pFormat, true,
-                               [&](size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(pStream, streamBytes, w, h, nullptr, total, nullptr); });
   }
 }

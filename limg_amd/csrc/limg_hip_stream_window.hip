@@ -733,75 +733,50 @@ namespace limg_hip
     }
   }
 
-  // persistent launches: a workgroup of four waves per residency slot at most (version 1: 4 per CU at its 100 vector registers; version 2: 8), every wave strides over its units
+  // persistent launches: a workgroup of four waves per residency slot at most, every wave strides over its units.  slotsPerCu: 4 for version 1 (its 100 vector
+  // registers), 8 for version 2
+  static dim3 window_grid(uint32_t units, int cus, uint32_t slotsPerCu)
+  {
+    const uint32_t need = units / 4u + (units % 4u ? 1u : 0u), slots = (uint32_t)cus * slotsPerCu;
+    return dim3(need < slots ? need : slots);
+  }
+
   void launch_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s)
   {
-    const uint32_t units = ((p.wbx + 63u) / 64u) * p.wby, need = (units + 3u) / 4u, slots = (uint32_t)cus * 4u;
-    hipLaunchKernelGGL(k_stream_window_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_stream_window_decode, window_grid(((p.wbx + 63u) / 64u) * p.wby, cus, 4u), dim3(256), 0, s, p);
   }
 
   void launch_blocked_stream_window_decode(const WindowDecodeParams &p, int cus, hipStream_t s)
   {
-    const uint32_t slots = (uint32_t)cus * 8u;
-    const uint32_t needMap = (p.nBlocks + 255u) / 256u; // at most nBlocks rectangles, 64 per wave
-    hipLaunchKernelGGL(k_bstream_window_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, p);
-    const uint32_t units = ((p.wbx + 7u) / 8u) * p.wby, need = (units + 3u) / 4u;
-    hipLaunchKernelGGL(k_bstream_window_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_bstream_window_map, window_grid((p.nBlocks + 63u) / 64u, cus, 8u), dim3(256), 0, s, p); // at most nBlocks rectangles, 64 per wave
+    hipLaunchKernelGGL(k_bstream_window_decode, window_grid(((p.wbx + 7u) / 8u) * p.wby, cus, 8u), dim3(256), 0, s, p);
   }
 
-  // the batched forms: the grid comes from the call's totals, so many small windows fill the device that one of them would leave nearly empty
-  void launch_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s)
+  // the batched forms: the grid comes from the call's totals, so many small windows fill the device that one of them would leave nearly empty.  f: the tensor format
+  // (its type checked by the host entry), NULL for packed RGBA8; scaled: the job types with a level, which have kernels of their own whatever the levels are.
+  // (Templates are emitted in the order they are first named in: tensor before scaled, version 1 before 2, as the device code has had them so far.)
+  static void launch_windows_decode(bool rects, bool scaled, const limg_hip_tensor_format *f, const WindowBatchParams &b, dim3 grid, hipStream_t s)
   {
-    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u), slots = (uint32_t)cus * 4u;
-    hipLaunchKernelGGL(k_stream_windows_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, b);
+    const bool half = f && f->type == LIMG_HIP_TENSOR_F16;
+    if (!f) hipLaunchKernelGGL(!scaled ? (!rects ? k_stream_windows_decode : k_bstream_windows_decode) : (!rects ? k_stream_windows_scaled : k_bstream_windows_scaled), grid, dim3(256), 0, s, b);
+    else if (!scaled)
+      hipLaunchKernelGGL(!rects ? (half ? k_stream_windows_tensor<_Float16> : k_stream_windows_tensor<float>) : (half ? k_bstream_windows_tensor<_Float16> : k_bstream_windows_tensor<float>),
+                         grid, dim3(256), 0, s, b, *f);
+    else
+      hipLaunchKernelGGL(!rects ? (half ? k_stream_windows_scaled_tensor<_Float16> : k_stream_windows_scaled_tensor<float>)
+                                : (half ? k_bstream_windows_scaled_tensor<_Float16> : k_bstream_windows_scaled_tensor<float>),
+                         grid, dim3(256), 0, s, b, *f);
   }
 
-  void launch_blocked_stream_windows_decode(const WindowBatchParams &b, int cus, hipStream_t s)
+  void launch_stream_windows(const WindowBatchParams &b, bool scaled, const limg_hip_tensor_format *f, int cus, hipStream_t s)
   {
-    const uint32_t slots = (uint32_t)cus * 8u;
-    const uint32_t needMap = b.totalItems / 4u + (b.totalItems % 4u ? 1u : 0u);
-    hipLaunchKernelGGL(k_bstream_windows_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, b);
-    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u);
-    hipLaunchKernelGGL(k_bstream_windows_decode, dim3(need < slots ? need : slots), dim3(256), 0, s, b);
+    launch_windows_decode(false, scaled, f, b, window_grid(b.totalUnits, cus, 4u), s);
   }
 
-  // the tensor forms: the same grids (f.type: checked by the host entry)
-  void launch_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s)
+  // version 2: the map kernel first; it never touches the output, works on the footprints and so serves every form as it is
+  void launch_blocked_stream_windows(const WindowBatchParams &b, bool scaled, const limg_hip_tensor_format *f, int cus, hipStream_t s)
   {
-    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u), slots = (uint32_t)cus * 4u;
-    if (f.type == LIMG_HIP_TENSOR_F16) hipLaunchKernelGGL(k_stream_windows_tensor<_Float16>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
-    else hipLaunchKernelGGL(k_stream_windows_tensor<float>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
-  }
-
-  void launch_blocked_stream_windows_tensor(const WindowBatchParams &b, const limg_hip_tensor_format &f, int cus, hipStream_t s)
-  {
-    const uint32_t slots = (uint32_t)cus * 8u;
-    const uint32_t needMap = b.totalItems / 4u + (b.totalItems % 4u ? 1u : 0u);
-    hipLaunchKernelGGL(k_bstream_windows_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, b);
-    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u);
-    if (f.type == LIMG_HIP_TENSOR_F16) hipLaunchKernelGGL(k_bstream_windows_tensor<_Float16>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
-    else hipLaunchKernelGGL(k_bstream_windows_tensor<float>, dim3(need < slots ? need : slots), dim3(256), 0, s, b, f);
-  }
-
-  // the scaled forms: the same grids again; version 2's map kernel works on the footprints and serves them as it is
-  void launch_stream_windows_scaled(const WindowBatchParams &b, const limg_hip_tensor_format *f, int cus, hipStream_t s)
-  {
-    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u), slots = (uint32_t)cus * 4u;
-    const dim3 grid(need < slots ? need : slots);
-    if (!f) hipLaunchKernelGGL(k_stream_windows_scaled, grid, dim3(256), 0, s, b);
-    else if (f->type == LIMG_HIP_TENSOR_F16) hipLaunchKernelGGL(k_stream_windows_scaled_tensor<_Float16>, grid, dim3(256), 0, s, b, *f);
-    else hipLaunchKernelGGL(k_stream_windows_scaled_tensor<float>, grid, dim3(256), 0, s, b, *f);
-  }
-
-  void launch_blocked_stream_windows_scaled(const WindowBatchParams &b, const limg_hip_tensor_format *f, int cus, hipStream_t s)
-  {
-    const uint32_t slots = (uint32_t)cus * 8u;
-    const uint32_t needMap = b.totalItems / 4u + (b.totalItems % 4u ? 1u : 0u);
-    hipLaunchKernelGGL(k_bstream_windows_map, dim3(needMap < slots ? needMap : slots), dim3(256), 0, s, b);
-    const uint32_t need = b.totalUnits / 4u + (b.totalUnits % 4u ? 1u : 0u);
-    const dim3 grid(need < slots ? need : slots);
-    if (!f) hipLaunchKernelGGL(k_bstream_windows_scaled, grid, dim3(256), 0, s, b);
-    else if (f->type == LIMG_HIP_TENSOR_F16) hipLaunchKernelGGL(k_bstream_windows_scaled_tensor<_Float16>, grid, dim3(256), 0, s, b, *f);
-    else hipLaunchKernelGGL(k_bstream_windows_scaled_tensor<float>, grid, dim3(256), 0, s, b, *f);
+    hipLaunchKernelGGL(k_bstream_windows_map, window_grid(b.totalItems, cus, 8u), dim3(256), 0, s, b);
+    launch_windows_decode(true, scaled, f, b, window_grid(b.totalUnits, cus, 8u), s);
   }
 }

@@ -1,0 +1,432 @@
+// limg_hip_stream_window_api.hip -- the window decode entries of the C ABI (limg_hip_*decode_stream_window*; kernels: limg_hip_stream_window.hip): one window or a
+// table of them, into packed RGBA8 or planar float tensors, at full or reduced scale, from device or host memory, of either stream version.  Three things vary and each
+// is stated once: the stream version (StreamVersion: two constants), the public window struct (window_view / stage_window) and where the pixels go (WindowOut).
+// No kernel lives here.
+#include "limg_hip_context.h"
+
+#include <algorithm>
+#include <type_traits>
+
+using namespace limg_hip;
+
+namespace
+{
+  // ---- what the host needs to know about a stream version ----
+  struct StreamVersion
+  {
+    size_t (*bound)(size_t sizeX, size_t sizeY);                                                                        // limg_hip_*stream_bound
+    limg_hip_result (*info)(const uint8_t *pStream, size_t bytes, size_t *pSizeX, size_t *pSizeY, size_t *pTotalBytes); // the header check
+    uint32_t unitLog2; // a decode unit is a run of up to 64 (version 1) or 8 (version 2) blocks of one block row of the window: log2 of that width
+    bool rectangles;   // the table holds rectangles: decoding needs the block -> rectangle map, the state words and, batched, the stream groups
+    bool tableExtent;  // one entry per block: streamBytes >= header + nBlocks * entry is known, and checked, on the host
+  };
+  const StreamVersion kVersion1 = { limg_hip_stream_bound,
+                                    [](const uint8_t *p, size_t n, size_t *w, size_t *h, size_t *total) { return limg_hip_stream_info(p, n, w, h, nullptr, total); }, 6u, false, true };
+  const StreamVersion kVersion2 = { limg_hip_blocked_stream_bound,
+                                    [](const uint8_t *p, size_t n, size_t *w, size_t *h, size_t *total) { return limg_hip_blocked_stream_info(p, n, w, h, nullptr, total, nullptr); },
+                                    3u, true, false };
+  uint32_t window_units(const StreamVersion &v, const WindowDecodeParams &wp) { return ((wp.wbx + (1u << v.unitLog2) - 1u) >> v.unitLog2) * wp.wby; }
+
+  // ---- one view of a window ----
+  // Where a window's pixels go: packed RGBA8 (planes == 0: elemBytes 4, one element per pixel) or `planes` planes of float / _Float16 (the tensor entries).
+  struct WindowOut
+  {
+    void *p;
+    size_t rowStride, planeStride; // in elements
+    uint32_t elemBytes, planes;
+  };
+  // any of the four public window structs; level: the scaled ones' log2Scale (the others are level 0), the window is in that level's coordinates
+  struct WindowView
+  {
+    size_t x0, y0, width, height, level;
+    WindowOut out;
+  };
+  template <class WIN, class = void> struct IsPlanar : std::false_type {}; // limg_hip_[scaled_]tensor_window: rowStride and planeStride, pixels of the format's type
+  template <class WIN> struct IsPlanar<WIN, std::void_t<decltype(WIN::planeStride)>> : std::true_type {};
+  template <class WIN, class = void> struct IsScaled : std::false_type {}; // limg_hip_scaled_[tensor_]window: log2Scale
+  template <class WIN> struct IsScaled<WIN, std::void_t<decltype(WIN::log2Scale)>> : std::true_type {};
+
+  template <class WIN> WindowView window_view(const WIN &w, const limg_hip_tensor_format *f)
+  {
+    WindowView v = { w.x0, w.y0, w.width, w.height, 0, { w.pOut, 0, 0, 4u, 0u } };
+    if constexpr (IsPlanar<WIN>::value) v.out = { w.pOut, w.rowStride, w.planeStride, f->type == LIMG_HIP_TENSOR_F16 ? 2u : 4u, f->planes };
+    else v.out.rowStride = w.outStridePixels;
+    if constexpr (IsScaled<WIN>::value) v.level = w.log2Scale;
+    return v;
+  }
+  // ... and back: the staged form of a window, densely packed at `p`
+  template <class WIN> void stage_window(WIN &w, void *p)
+  {
+    w.pOut = (decltype(w.pOut))p;
+    if constexpr (IsPlanar<WIN>::value) { w.rowStride = w.width; w.planeStride = w.width * w.height; }
+    else w.outStridePixels = w.width;
+  }
+  WindowView rgba_view(size_t x0, size_t y0, size_t width, size_t height, uint32_t *pOut, size_t outStridePixels)
+  {
+    return { x0, y0, width, height, 0, { pOut, outStridePixels, 0, 4u, 0u } };
+  }
+  bool tensor_format_ok(const limg_hip_tensor_format *f) { return (f->type == LIMG_HIP_TENSOR_F32 || f->type == LIMG_HIP_TENSOR_F16) && (f->planes == 3u || f->planes == 4u); }
+
+  // the window's size and the output's strides: what every window entry, device or host, checks first
+  limg_hip_result window_out_check(size_t width, size_t height, const WindowOut &o)
+  {
+    if (width == 0 || height == 0 || o.rowStride < width) return limg_hip_error_InvalidParameter;
+    if (o.planes)
+    { // planeStride >= (height - 1) * rowStride + width, without overflow
+      if (height > 1 && o.rowStride > ((size_t)-1 - width) / (height - 1)) return limg_hip_error_InvalidParameter;
+      if (o.planeStride < (height - 1) * o.rowStride + width) return limg_hip_error_InvalidParameter;
+    }
+    return limg_hip_success;
+  }
+  bool out_aligned(const WindowOut &o) { return ((uintptr_t)o.p & (o.elemBytes - 1u)) == 0; }
+  bool window_inside(size_t sizeX, size_t sizeY, const WindowView &w)
+  {
+    return !(w.x0 >= sizeX || w.width > sizeX - w.x0 || w.y0 >= sizeY || w.height > sizeY - w.y0);
+  }
+
+  // the checks and the parameters the two versions share, without touching the device; `bound`: the version's limg_hip_*stream_bound(sizeX, sizeY).  status, map and
+  // state are the caller's to set.  A window at level > 0 lies inside (sizeX >> level) x (sizeY >> level), and wp gets its source footprint (x0 .. height times
+  // 1 << level: inside the image, so nothing overflows) with vecOut stated on the window itself.
+  limg_hip_result window_fill(const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, const WindowView &w, WindowDecodeParams &wp)
+  {
+    const WindowOut &o = w.out;
+    const size_t level = w.level;
+    if (level > 3 || window_out_check(w.width, w.height, o) != limg_hip_success || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
+    if (((uintptr_t)pStream & 15u) != 0 || !out_aligned(o)) return limg_hip_error_InvalidParameter;
+    if (!window_inside(sizeX >> level, sizeY >> level, w)) return limg_hip_error_OutOfBounds;
+    const size_t x0 = w.x0 << level, y0 = w.y0 << level, width = w.width << level, height = w.height << level;
+    memset(&wp, 0, sizeof(wp));
+    wp.sizeX = (uint32_t)sizeX; wp.sizeY = (uint32_t)sizeY;
+    wp.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); wp.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
+    wp.nBlocks = wp.blocksX * wp.blocksY;
+    wp.stream = pStream; wp.streamBytes = streamBytes;
+    wp.x0 = (uint32_t)x0; wp.y0 = (uint32_t)y0; wp.width = (uint32_t)width; wp.height = (uint32_t)height;
+    wp.bx0 = (uint32_t)(x0 / kBlock); wp.by0 = (uint32_t)(y0 / kBlock);
+    wp.wbx = (uint32_t)((x0 + width - 1) / kBlock) - wp.bx0 + 1; wp.wby = (uint32_t)((y0 + height - 1) / kBlock) - wp.by0 + 1;
+    wp.out = (uint32_t *)o.p; wp.outStride = o.rowStride; wp.planeStride = o.planeStride;
+    const size_t per = 16u / o.elemBytes; // elements per 16-byte store (planeStride is 0 for RGBA)
+    wp.vecOut = ((uintptr_t)o.p & 15u) == 0 && o.rowStride % per == 0 && o.planeStride % per == 0 && w.x0 % per == 0;
+    wp.log2Scale = (uint32_t)level;
+    return limg_hip_success;
+  }
+}
+
+limg_hip_result limg_hip::window_params(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0,
+                                        size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, hipStream_t s, WindowDecodeParams &wp)
+{
+  limg_hip_result r = window_fill(pStream, streamBytes, sizeX, sizeY, bound, rgba_view(x0, y0, width, height, pOut, outStridePixels), wp);
+  if (r != limg_hip_success) return r;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
+  wp.status = (uint32_t *)c->streamStatus.p;
+  return limg_hip_success;
+}
+
+// the map of the window's blocks (not the image's) and the call's state words, then the two kernels
+limg_hip_result limg_hip::blocked_window_decode(limg_hip_context *c, WindowDecodeParams &wp, hipStream_t s)
+{
+  const size_t mapBytes = (size_t)wp.wbx * wp.wby * 4;
+  limg_hip_result r;
+  if ((r = c->bsMap.ensure(mapBytes)) != limg_hip_success) return r;
+  if ((r = c->bsState.ensure(64)) != limg_hip_success) return r;
+  HIP_TRY(hipMemsetAsync(c->bsMap.p, 0xFF, mapBytes, s)); // no block has a rectangle yet
+  HIP_TRY(hipMemsetAsync(c->bsState.p, 0, 64, s));
+  wp.map = (uint32_t *)c->bsMap.p; wp.state = (uint32_t *)c->bsState.p;
+  launch_blocked_stream_window_decode(wp, device_cus(c), s);
+  HIP_TRY(hipGetLastError());
+  return limg_hip_success;
+}
+
+namespace
+{
+  // ---- one window: limg_hip_*decode_stream_window[_device] ----
+  limg_hip_result decode_window_device(limg_hip_context *c, const StreamVersion &v, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t x0, size_t y0,
+                                       size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, hipStream_t s)
+  {
+    if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
+    WindowDecodeParams wp;
+    const limg_hip_result r = window_params(c, pStream, streamBytes, sizeX, sizeY, v.bound(sizeX, sizeY), x0, y0, width, height, pOut, outStridePixels, s, wp);
+    if (r != limg_hip_success) return r;
+    if (v.rectangles) return blocked_window_decode(c, wp, s);
+    if (streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
+    launch_stream_window_decode(wp, device_cus(c), s);
+    HIP_TRY(hipGetLastError());
+    return limg_hip_success;
+  }
+
+  // the host form: the stream into context memory, the window into context staging at stride `width`; only a stream that passed reaches pOut
+  limg_hip_result decode_window_host(limg_hip_context *c, const StreamVersion &v, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,
+                                     uint32_t *pOut, size_t outStridePixels)
+  {
+    if (!c || !pStream || !pOut) return limg_hip_error_ArgumentNull;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    const WindowView w = rgba_view(x0, y0, width, height, pOut, outStridePixels);
+    limg_hip_result r = window_out_check(width, height, w.out);
+    if (r != limg_hip_success) return r;
+    size_t sizeX = 0, sizeY = 0, total = 0;
+    if ((r = v.info(pStream, streamBytes, &sizeX, &sizeY, &total)) != limg_hip_success) return r;
+    if (total > streamBytes || !window_inside(sizeX, sizeY, w)) return limg_hip_error_OutOfBounds;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
+    if ((r = c->planes.ensure(width * height * 4)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice));
+    if ((r = decode_window_device(c, v, (const uint8_t *)c->streamBuf.p, total, sizeX, sizeY, x0, y0, width, height, (uint32_t *)c->planes.p, width, nullptr)) != limg_hip_success)
+      return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy2D(pOut, outStridePixels * 4, c->planes.p, width * 4, width * 4, height, hipMemcpyDeviceToHost));
+    return limg_hip_success;
+  }
+
+  // ---- batched: limg_hip_*decode_stream_windows* ----
+  size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+  // One call: every job checked on the host before anything touches the device, then the job table built in a pinned slot of the context's ring, copied on `s`,
+  // and the version's one (two) launches.  JOB: any of the four public job types -- its window says whether the pixels go to planes of pFormat's type (else pFormat is
+  // not looked at) and whether it carries a level, which then selects the scaled kernels: the same checks, table and launches otherwise.
+  template <class JOB>
+  limg_hip_result decode_windows_device(limg_hip_context *c, const StreamVersion &v, const JOB *pJobs, size_t count, const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus,
+                                        hipStream_t s)
+  {
+    typedef decltype(JOB::window) WIN;
+    constexpr bool tensor = IsPlanar<WIN>::value, scaled = IsScaled<WIN>::value;
+    if (!c || !pJobs || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
+    if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
+    const bool rects = v.rectangles;
+    auto fill = [&v, pFormat](const JOB &j, WindowDecodeParams &wp) {
+      return window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, v.bound(j.sizeX, j.sizeY), window_view(j.window, pFormat), wp);
+    };
+    // pass 1: the single-window entry's checks, job by job in its order; the sums the table's layout needs
+    unsigned long long units = 0, blocks = 0;
+    WindowDecodeParams wp;
+    for (size_t i = 0; i < count; i++)
+    {
+      const JOB &j = pJobs[i];
+      if (!j.pStream || !j.window.pOut) return limg_hip_error_ArgumentNull;
+      const limg_hip_result r = fill(j, wp);
+      if (r != limg_hip_success) return r;
+      if (v.tableExtent && j.streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
+      units += window_units(v, wp);
+      blocks += (unsigned long long)wp.wbx * wp.wby;
+    }
+    if (units > 0xFFFFFFFFull || blocks > 0xFFFFFFFFull) return limg_hip_error_InvalidParameter;
+
+    HIP_TRY(hipSetDevice(c->device));
+    limg_hip_result r;
+    if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
+    // the slot: [jobs | unitBase | groups | groupJobs | groupItemBase] is uploaded; [state | map] behind it exists on the device only (version 2)
+    const size_t oJobs = 0, oUnitBase = align16(oJobs + count * sizeof(WindowDecodeParams)), oGroups = align16(oUnitBase + (count + 1) * 4);
+    const size_t oGroupJobs = rects ? align16(oGroups + count * sizeof(WindowGroup)) : oGroups, oItemBase = rects ? align16(oGroupJobs + count * 4) : oGroups;
+    const size_t upload = rects ? align16(oItemBase + (count + 1) * 4) : oGroups;
+    const size_t oState = upload, oMap = align16(oState + (rects ? count * 8 : 0)), total = oMap + (rects ? (size_t)blocks * 4 : 0);
+    limg_hip_context::WindowSlot &slot = c->windowSlots[c->windowSlotNext];
+    c->windowSlotNext = (c->windowSlotNext + 1) % limg_hip_context::kWindowSlots;
+    if (slot.busy)
+    { // the call that used this slot last: its copy has left the pinned table and its kernels are done with the device copy
+      HIP_TRY(hipEventSynchronize(slot.done));
+      slot.busy = false;
+    }
+    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    if ((r = slot.host.ensure(upload)) != limg_hip_success) return r;
+    if ((r = slot.dev.ensure(total)) != limg_hip_success) return r;
+    uint8_t *hb = (uint8_t *)slot.host.p, *db = (uint8_t *)slot.dev.p;
+    WindowDecodeParams *jobs = (WindowDecodeParams *)(hb + oJobs);
+    uint32_t *unitBase = (uint32_t *)(hb + oUnitBase);
+
+    // pass 2: the table (the checks of pass 1 cannot fail again)
+    uint32_t unitAt = 0, blockAt = 0;
+    for (size_t i = 0; i < count; i++)
+    {
+      (void)fill(pJobs[i], jobs[i]);
+      jobs[i].status = (uint32_t *)c->streamStatus.p;
+      if (rects)
+      {
+        jobs[i].state = (uint32_t *)(db + oState) + 2 * i;
+        jobs[i].map = (uint32_t *)(db + oMap) + blockAt;
+      }
+      unitBase[i] = unitAt;
+      unitAt += window_units(v, jobs[i]);
+      blockAt += jobs[i].wbx * jobs[i].wby;
+    }
+    unitBase[count] = unitAt;
+    WindowBatchParams b;
+    memset(&b, 0, sizeof(b));
+    b.jobs = (const WindowDecodeParams *)(db + oJobs); b.unitBase = (const uint32_t *)(db + oUnitBase);
+    b.count = (uint32_t)count; b.totalUnits = unitAt;
+    b.status = (uint32_t *)c->streamStatus.p; b.jobStatus = pJobStatus;
+    if (rects)
+    { // groups: the jobs sorted by stream (in place, in the table: no allocation), then one group per run of equal keys
+      WindowGroup *groups = (WindowGroup *)(hb + oGroups);
+      uint32_t *groupJobs = (uint32_t *)(hb + oGroupJobs), *itemBase = (uint32_t *)(hb + oItemBase);
+      for (size_t i = 0; i < count; i++) groupJobs[i] = (uint32_t)i;
+      auto less = [jobs](uint32_t x, uint32_t y) {
+        const WindowDecodeParams &a = jobs[x], &bb = jobs[y];
+        if (a.stream != bb.stream) return (uintptr_t)a.stream < (uintptr_t)bb.stream;
+        if (a.streamBytes != bb.streamBytes) return a.streamBytes < bb.streamBytes;
+        if (a.sizeX != bb.sizeX) return a.sizeX < bb.sizeX;
+        if (a.sizeY != bb.sizeY) return a.sizeY < bb.sizeY;
+        return x < y;
+      };
+      std::sort(groupJobs, groupJobs + count, less);
+      uint32_t nGroups = 0;
+      unsigned long long items = 0;
+      for (size_t i = 0; i < count; i++)
+      {
+        const WindowDecodeParams &a = jobs[groupJobs[i]];
+        if (i == 0 || a.stream != groups[nGroups - 1].stream || a.streamBytes != groups[nGroups - 1].streamBytes || a.sizeX != groups[nGroups - 1].sizeX ||
+            a.sizeY != groups[nGroups - 1].sizeY)
+        {
+          WindowGroup &g = groups[nGroups];
+          memset(&g, 0, sizeof(g));
+          g.sizeX = a.sizeX; g.sizeY = a.sizeY; g.blocksX = a.blocksX; g.blocksY = a.blocksY; g.nBlocks = a.nBlocks;
+          g.firstJob = (uint32_t)i; g.stream = a.stream; g.streamBytes = a.streamBytes;
+          itemBase[nGroups++] = (uint32_t)items;
+          items += (a.nBlocks + 63u) / 64u; // 64 rectangles per item, at most nBlocks rectangles
+        }
+        groups[nGroups - 1].nJobs++;
+      }
+      if (items > 0xFFFFFFFFull) return limg_hip_error_InvalidParameter;
+      itemBase[nGroups] = (uint32_t)items;
+      b.groups = (const WindowGroup *)(db + oGroups); b.groupJobs = (const uint32_t *)(db + oGroupJobs); b.groupItemBase = (const uint32_t *)(db + oItemBase);
+      b.nGroups = nGroups; b.totalItems = (uint32_t)items;
+    }
+    HIP_TRY(hipMemcpyAsync(db, hb, upload, hipMemcpyHostToDevice, s));
+    slot.busy = true; // from here on the slot is in flight, whatever fails below
+    if (rects)
+    {
+      HIP_TRY(hipMemsetAsync(db + oState, 0, count * 8, s));
+      HIP_TRY(hipMemsetAsync(db + oMap, 0xFF, (size_t)blocks * 4, s)); // no block has a rectangle yet
+    }
+    if (pJobStatus) HIP_TRY(hipMemsetAsync(pJobStatus, 0, count * 4, s));
+    (rects ? launch_blocked_stream_windows : launch_stream_windows)(b, scaled, tensor ? pFormat : nullptr, device_cus(c), s);
+    const hipError_t launched = hipGetLastError();
+    HIP_TRY(hipEventRecord(slot.done, s));
+    HIP_TRY(launched);
+    return limg_hip_success;
+  }
+
+  // `count` windows of ONE host stream, JOB as above: every window is stated, checked and staged in its level's coordinates
+  template <class JOB>
+  limg_hip_result decode_windows_host(limg_hip_context *c, const StreamVersion &v, const uint8_t *pStream, size_t streamBytes, const decltype(JOB::window) *pWindows, size_t count,
+                                      const limg_hip_tensor_format *pFormat)
+  {
+    constexpr bool tensor = IsPlanar<decltype(JOB::window)>::value;
+    if (!c || !pStream || !pWindows || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
+    for (size_t i = 0; i < count; i++)
+    {
+      const WindowView w = window_view(pWindows[i], pFormat);
+      if (!w.out.p) return limg_hip_error_ArgumentNull;
+      if (w.level > 3) return limg_hip_error_InvalidParameter;
+      const limg_hip_result ok = window_out_check(w.width, w.height, w.out);
+      if (ok != limg_hip_success) return ok;
+      if (tensor && !out_aligned(w.out)) return limg_hip_error_InvalidParameter;
+    }
+    size_t sizeX = 0, sizeY = 0, total = 0;
+    limg_hip_result r = v.info(pStream, streamBytes, &sizeX, &sizeY, &total);
+    if (r != limg_hip_success) return r;
+    if (total > streamBytes) return limg_hip_error_OutOfBounds;
+    const size_t eb = window_view(pWindows[0], pFormat).out.elemBytes, planes = tensor ? pFormat->planes : 1;
+    const size_t per = 16 / eb;
+    size_t elems = 0; // staging: every window at its own width (plane after plane), on a 16-byte boundary
+    for (size_t i = 0; i < count; i++)
+    {
+      const WindowView w = window_view(pWindows[i], pFormat);
+      if (!window_inside(sizeX >> w.level, sizeY >> w.level, w)) return limg_hip_error_OutOfBounds;
+      elems += (planes * w.width * w.height + per - 1) / per * per;
+    }
+    JOB *jobs = new (std::nothrow) JOB[count];
+    if (!jobs) return limg_hip_error_MemoryAllocationFailure;
+    struct Free { JOB *p; ~Free() { delete[] p; } } freeJobs = { jobs };
+    HIP_TRY(hipSetDevice(c->device));
+    if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
+    if ((r = c->planes.ensure(elems * eb)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice)); // once, for all windows
+    size_t at = 0;
+    for (size_t i = 0; i < count; i++)
+    {
+      jobs[i].pStream = (const uint8_t *)c->streamBuf.p; jobs[i].streamBytes = total; jobs[i].sizeX = sizeX; jobs[i].sizeY = sizeY;
+      jobs[i].window = pWindows[i];
+      stage_window(jobs[i].window, (uint8_t *)c->planes.p + at * eb);
+      at += (planes * pWindows[i].width * pWindows[i].height + per - 1) / per * per;
+    }
+    if ((r = decode_windows_device(c, v, jobs, count, pFormat, nullptr, nullptr)) != limg_hip_success) return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r; // a stream refused for any window: no pOut is touched
+    for (size_t i = 0; i < count; i++)
+    {
+      const WindowView w = window_view(pWindows[i], pFormat);
+      for (size_t pl = 0; pl < planes; pl++)
+        HIP_TRY(hipMemcpy2D((uint8_t *)w.out.p + pl * w.out.planeStride * eb, w.out.rowStride * eb, (const uint8_t *)jobs[i].window.pOut + pl * w.width * w.height * eb,
+                            w.width * eb, w.width * eb, w.height, hipMemcpyDeviceToHost));
+    }
+    return limg_hip_success;
+  }
+}
+
+// every entry: its version's constant, its job type, the caller's arguments
+extern "C"
+{
+  // ---- one window ----
+  limg_hip_result limg_hip_decode_stream_window_device(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t x0, size_t y0,
+                                                       size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, void *stream)
+  { return decode_window_device(c, kVersion1, pStream, streamBytes, sizeX, sizeY, x0, y0, width, height, pOut, outStridePixels, (hipStream_t)stream); }
+  limg_hip_result limg_hip_blocked_decode_stream_window_device(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t x0, size_t y0,
+                                                               size_t width, size_t height, uint32_t *pOut, size_t outStridePixels, void *stream)
+  { return decode_window_device(c, kVersion2, pStream, streamBytes, sizeX, sizeY, x0, y0, width, height, pOut, outStridePixels, (hipStream_t)stream); }
+  limg_hip_result limg_hip_decode_stream_window(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height, uint32_t *pOut,
+                                                size_t outStridePixels)
+  { return decode_window_host(c, kVersion1, pStream, streamBytes, x0, y0, width, height, pOut, outStridePixels); }
+  limg_hip_result limg_hip_blocked_decode_stream_window(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height,
+                                                        uint32_t *pOut, size_t outStridePixels)
+  { return decode_window_host(c, kVersion2, pStream, streamBytes, x0, y0, width, height, pOut, outStridePixels); }
+
+  // ---- batched, packed RGBA8 ----
+  limg_hip_result limg_hip_decode_stream_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion1, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_device(limg_hip_context *c, const limg_hip_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion2, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_decode_stream_windows(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count)
+  { return decode_windows_host<limg_hip_window_job>(c, kVersion1, pStream, streamBytes, pWindows, count, nullptr); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count)
+  { return decode_windows_host<limg_hip_window_job>(c, kVersion2, pStream, streamBytes, pWindows, count, nullptr); }
+
+  // ---- batched, planar float tensors ----
+  limg_hip_result limg_hip_decode_stream_windows_tensor_device(limg_hip_context *c, const limg_hip_tensor_window_job *pJobs, size_t count, const limg_hip_tensor_format *pFormat,
+                                                               uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion1, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_tensor_device(limg_hip_context *c, const limg_hip_tensor_window_job *pJobs, size_t count,
+                                                                       const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion2, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_decode_stream_windows_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows, size_t count,
+                                                        const limg_hip_tensor_format *pFormat)
+  { return decode_windows_host<limg_hip_tensor_window_job>(c, kVersion1, pStream, streamBytes, pWindows, count, pFormat); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_tensor_window *pWindows,
+                                                                size_t count, const limg_hip_tensor_format *pFormat)
+  { return decode_windows_host<limg_hip_tensor_window_job>(c, kVersion2, pStream, streamBytes, pWindows, count, pFormat); }
+
+  // ---- batched, reduced scale, RGBA8 and tensors: the job types with a level ----
+  limg_hip_result limg_hip_decode_stream_windows_scaled_device(limg_hip_context *c, const limg_hip_scaled_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion1, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_device(limg_hip_context *c, const limg_hip_scaled_window_job *pJobs, size_t count, uint32_t *pJobStatus,
+                                                                       void *stream)
+  { return decode_windows_device(c, kVersion2, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_decode_stream_windows_scaled(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_window *pWindows, size_t count)
+  { return decode_windows_host<limg_hip_scaled_window_job>(c, kVersion1, pStream, streamBytes, pWindows, count, nullptr); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_window *pWindows,
+                                                                size_t count)
+  { return decode_windows_host<limg_hip_scaled_window_job>(c, kVersion2, pStream, streamBytes, pWindows, count, nullptr); }
+  limg_hip_result limg_hip_decode_stream_windows_scaled_tensor_device(limg_hip_context *c, const limg_hip_scaled_tensor_window_job *pJobs, size_t count,
+                                                                      const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion1, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor_device(limg_hip_context *c, const limg_hip_scaled_tensor_window_job *pJobs, size_t count,
+                                                                              const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion2, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_decode_stream_windows_scaled_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_scaled_tensor_window *pWindows,
+                                                               size_t count, const limg_hip_tensor_format *pFormat)
+  { return decode_windows_host<limg_hip_scaled_tensor_window_job>(c, kVersion1, pStream, streamBytes, pWindows, count, pFormat); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes,
+                                                                       const limg_hip_scaled_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat)
+  { return decode_windows_host<limg_hip_scaled_tensor_window_job>(c, kVersion2, pStream, streamBytes, pWindows, count, pFormat); }
+}
