@@ -22,8 +22,8 @@ namespace limg_hip
     template <int CTRL, int ROWMASK>
     __device__ __forceinline__ int dpp(int oldv, int v) { return __builtin_amdgcn_update_dpp(oldv, v, CTRL, ROWMASK, 0xF, false); }
 
-    // integer sum over the wave; result is wave-uniform
-    __device__ __forceinline__ uint32_t wave_sum(uint32_t x)
+    // integer sum over the wave, left in the vector registers: lane 63 holds the total (the other lanes partial sums)
+    __device__ __forceinline__ uint32_t wave_sum_lane63(uint32_t x)
     {
       int v = (int)x;
       v += dpp<0xB1, 0xF>(0, v);  // quad_perm [1,0,3,2]
@@ -32,8 +32,23 @@ namespace limg_hip
       v += dpp<0x140, 0xF>(0, v); // row_mirror
       v += dpp<0x142, 0xA>(0, v); // row_bcast:15
       v += dpp<0x143, 0xC>(0, v); // row_bcast:31
-      return (uint32_t)__builtin_amdgcn_readlane(v, 63);
+      return (uint32_t)v;
     }
+
+    // integer sum over the wave; result is wave-uniform
+    __device__ __forceinline__ uint32_t wave_sum(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)wave_sum_lane63(x), 63); }
+
+    // sum(x) < limit over the wave, wave-uniform, without bringing the sum to an SGPR (v_readlane_b32 issues at quarter rate): one per-lane compare puts lane
+    // 63's verdict in bit 63 of the mask and the scalar side tests the sign of the mask's high word.  The high word is made opaque on purpose: left to itself the
+    // compiler widens the test to the 64-bit mask, which only the VALU can compare (v_cmp_lt_i64).  For callers that branch on the verdict; wave_sum stays for
+    // those that need the value.
+    __device__ __forceinline__ uint32_t wave_sum_below_mask(uint32_t x, uint32_t limit) // the verdict is the SIGN of the returned word
+    {
+      uint32_t hi = (uint32_t)(__builtin_amdgcn_ballot_w64(wave_sum_lane63(x) < limit) >> 32);
+      asm("" : "+s"(hi));
+      return hi;
+    }
+    __device__ __forceinline__ bool wave_sum_below(uint32_t x, uint32_t limit) { return (int)wave_sum_below_mask(x, limit) < 0; }
 
     __device__ __forceinline__ int sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
     __device__ __forceinline__ float sgprf(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }

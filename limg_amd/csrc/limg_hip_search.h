@@ -144,12 +144,19 @@ namespace limg_hip
       return r;
     }
     // one trial of a whole block on three named sets (they become the cached ones): the trial core, the pixel check and -- only if no pixel fails -- the block sum.
-    // (Spelled as two branches to one label in the generated code instead, the compiler emits the same instructions: measured on the assembly.)
+    // The two ways to fail reach one successor.  As a boolean (a && b, or two branches to one label in the generated code) that join travels as a lane-mask pair
+    // -- s_cselect_b64, s_andn2_b64 and a second branch: profiles/search_hot_ab.md -- so the outcome is one scalar WORD instead: 0 where a pixel fails, else the
+    // high word of the block sum's compare mask (wave_sum_below: lane 63's bit is its sign), opaque to the compiler behind the join.  A pixel failure is then its
+    // branch over the sum plus the common sign test, a sum failure the sign test alone.  (asm goto would leave only the branches; this compiler drops the asm of
+    // an asm goto on gfx950.)
     __device__ __forceinline__ bool hot_trial(TrialState &t, const TermSet &A, const TermSet &B, const TermSet &C, const uint32_t maxPixel32, const uint32_t blockLimit)
     {
       t.tA_RG = A.rg; t.tA_B = A.b; t.tB_RG = B.rg; t.tB_B = B.b; t.tC_RG = C.rg; t.tC_B = C.b;
       const uint32_t err = trial_pixel_error<true>(t, true);
-      return __builtin_amdgcn_ballot_w64(err > maxPixel32) == 0ull && wave_sum(err) < blockLimit; // be * 16 < maxBlock * n, see phase E
+      uint32_t verdict = 0u;
+      if (__builtin_amdgcn_ballot_w64(err > maxPixel32) == 0ull) verdict = wave_sum_below_mask(err, blockLimit); // be * 16 < maxBlock * n, see phase E
+      asm("" : "+s"(verdict));
+      return (int)verdict < 0;
     }
 #include "limg_search_hot.h"
 
@@ -185,9 +192,11 @@ namespace limg_hip
         if (e[0] & 0x80u) rebuild_C(t, e[4], e[7]);
         const uint32_t err = trial_pixel_error<FULL>(t, active);
         // two tails on purpose: a pixel failure (the common way to fail) needs no outcome flag, no select and no block sum
-        uint32_t off;
-        if (__builtin_amdgcn_ballot_w64(err > maxPixel32) != 0ull) off = e[2];
-        else off = (wave_sum(err) < blockLimit) ? e[1] : e[2]; // be * 16 < maxBlock * n, see phase E
+        uint32_t off = e[2];
+        if (__builtin_amdgcn_ballot_w64(err > maxPixel32) == 0ull)
+        {
+          if (wave_sum_below(err, blockLimit)) off = e[1]; // be * 16 < maxBlock * n, see phase E
+        }
         e = sload8(tab, off);
       }
       shift[0] = e[0] & 31u; shift[1] = e[3]; shift[2] = e[4];

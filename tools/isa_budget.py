@@ -168,7 +168,7 @@ def main():
     phases = [
         ("search: trial core (a9)", [fn("trial_pixel_error")]),
         ("search: factor rebuild (make_terms)", [fn("make_terms"), fn("rebuild_A"), fn("rebuild_B"), fn("rebuild_C")]),
-        ("search: block-error sum (wave_sum)", [fn("wave_sum")]),
+        ("search: block-error sum (wave_sum)", [fn("wave_sum"), fn("wave_sum_lane63"), fn("wave_sum_below_mask"), fn("wave_sum_below")]),
         ("search: automaton loop / entry load", [fn("search_fast_automaton"), fn("sload8")]),
         ("search: accurate automaton (other variant)", [fn("search_accurate_automaton")]),
         ("E: strip staging (pixels -> LDS)", [(kf, m_stage, m_prefit - 1)]),
@@ -192,7 +192,7 @@ def main():
     acc, ops = budget(instrs, phases, "unattributed")
     copies_trial = max(1, ops["search: trial core (a9)"]["v_dot2_u32_u16"])
     copies_rows = max(1, ops["F: dither + crushed bytes + decode terms (rows_factor)"]["v_add_u32_sdwa"] // 8)
-    copies_sum = max(1, ops["search: block-error sum (wave_sum)"]["v_readlane_b32"])
+    copies_sum = max(1, ops["search: block-error sum (wave_sum)"]["v_add_u32_dpp"] // 6)  # six butterfly stages per copy (the search's verdict form has no v_readlane_b32)
     copies_rebuild = max(1, ops["search: factor rebuild (make_terms)"]["v_perm_b32"])
     # (name) -> (copies, executions per block, note)
     T, R, S, Dz = args.trials, args.rebuilds, args.sums, args.dithers
