@@ -4,6 +4,9 @@
  * export limg_hip_set_test_options.  limg_amd/build.py compiles the same sources a second time with -DLIMG_HIP_TEST_HOOKS into limg_amd/liblimg_hip_test.so;
  * the test suite (tests/conftest.py) and A/B runs of the bench (LIMG_HIP_LIB=limg_amd/liblimg_hip_test.so) load that build, everything else -- bench.py, the C++
  * shim, the CLI, __graft_entry__.smoke() -- loads the plain library.  Everything include/limg_hip.h declares is exported by both.
+ *
+ * The test build also counts the GPU resources that are alive in the process (limg_hip_test_live_resources): what lets a test assert that closing a context gives
+ * back exactly what the context took.
  */
 #ifndef LIMG_HIP_TEST_HOOKS_H
 #define LIMG_HIP_TEST_HOOKS_H
@@ -41,6 +44,10 @@ typedef struct limg_hip_test_options
 void limg_hip_default_test_options_sized(limg_hip_test_options *pOptions, size_t structSize);
 static inline void limg_hip_default_test_options(limg_hip_test_options *pOptions) { limg_hip_default_test_options_sized(pOptions, sizeof(limg_hip_test_options)); }
 limg_hip_result limg_hip_set_test_options(limg_hip_context *pCtx, const limg_hip_test_options *pOptions);
+
+/* What the contexts of this process hold right now (limg_amd/csrc/limg_hip_owned.h): out[0] device buffers, [1] their bytes (the sum of limg_hip_context_device_bytes
+ * over the open contexts), [2] pinned host buffers, [3] streams, [4] events.  Counted where the HIP create call succeeded and where the destroy call is made. */
+void limg_hip_test_live_resources(uint64_t out[5]);
 
 #ifdef __cplusplus
 }

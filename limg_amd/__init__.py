@@ -42,7 +42,7 @@ ABI_SYMBOLS = (
     "limg_hip_comm_unique_id", "limg_hip_comm_init", "limg_hip_comm_destroy", "limg_hip_comm_info", "limg_hip_gather_stream", "limg_hip_encode3d_single_chain_device",
     "limg_hip_encode3d_chain_device", "limg_hip_host_gather_offsets", "limg_hip_host_chain_bases",
 )
-TEST_ABI_SYMBOLS = ("limg_hip_default_test_options_sized", "limg_hip_set_test_options")  # include/limg_hip_test_hooks.h: exported by liblimg_hip_test.so only
+TEST_ABI_SYMBOLS = ("limg_hip_default_test_options_sized", "limg_hip_set_test_options", "limg_hip_test_live_resources")  # include/limg_hip_test_hooks.h: exported by liblimg_hip_test.so only
 COMM_ID_BYTES = 128
 
 # limg_blocked_encode3d_info (src/limg.h:39-44), member order
@@ -174,6 +174,8 @@ def load_library(path=None):
         L.limg_hip_default_test_options_sized.argtypes = [C.c_void_p, C.c_size_t]
         L.limg_hip_set_test_options.restype = C.c_int
         L.limg_hip_set_test_options.argtypes = [C.c_void_p, C.c_void_p]
+        L.limg_hip_test_live_resources.restype = None
+        L.limg_hip_test_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     L.limg_hip_set_options.restype = C.c_int
     L.limg_hip_set_options.argtypes = [C.c_void_p, C.c_void_p]
     L.limg_hip_get_options.restype = C.c_int
@@ -314,6 +316,13 @@ def _check(r, what):
 
 def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def live_resources(lib):
+    """(device buffers, device bytes, pinned buffers, streams, events) that the contexts opened through `lib` hold right now.  Test build only (include/limg_hip_test_hooks.h)."""
+    out = (C.c_uint64 * 5)()
+    lib.limg_hip_test_live_resources(out)
+    return tuple(int(v) for v in out)
 
 
 def stream_info(stream, lib=None):

@@ -12,14 +12,9 @@ namespace limg_hip
 {
   void mark(limg_hip_context *c, hipStream_t stream)
   {
-    if (!c->profiling) return;
-    if (c->eventsUsed == c->events.size())
-    {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) return;
-      c->events.push_back(e);
-    }
-    (void)hipEventRecord(c->events[c->eventsUsed++], stream);
+    if (!c->enc.profiling) return;
+    if (c->enc.events.ensure(c->enc.eventsUsed + 1, hipEventDefault) != limg_hip_success) return;
+    (void)hipEventRecord(c->enc.events[c->enc.eventsUsed++], stream);
   }
 }
 
@@ -62,6 +57,11 @@ extern "C"
     c->topt = full;
     return limg_hip_success;
   }
+
+  void limg_hip_test_live_resources(uint64_t out[5])
+  {
+    for (int i = 0; out && i < limg_hip_live::kCounts; i++) out[i] = limg_hip_live::count[i].load();
+  }
 #endif
 
   limg_hip_result limg_hip_init(int device, limg_hip_context **ppCtx)
@@ -81,7 +81,7 @@ extern "C"
     if (!c) return limg_hip_error_MemoryAllocationFailure;
     c->device = device;
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->persistentWorkgroups = 5 * prop.multiProcessorCount;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->enc.persistentWorkgroups = 5 * prop.multiProcessorCount;
     limg_hip_default_options_sized(&c->opt, sizeof(c->opt));
 #ifdef LIMG_HIP_TEST_HOOKS
     limg_hip_default_test_options_sized(&c->topt, sizeof(c->topt));
@@ -93,35 +93,7 @@ extern "C"
   void limg_hip_shutdown(limg_hip_context **ppCtx)
   {
     if (!ppCtx || !*ppCtx) return;
-    limg_hip_context *c = *ppCtx;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    limg_hip_context::for_each_device_buffer(*c, [](DevBuf &b) { b.release(); });
-    HostBuf *hbufs[] = { &c->hFlags, &c->hRec, &c->hBits, &c->hDesc, &c->hOut, &c->hNoise, &c->hNoiseBase };
-    for (HostBuf *b : hbufs) b->release();
-    c->hStage.release(); // (the device is idle: hipDeviceSynchronize above)
-    if (c->hStageEvent) (void)hipEventDestroy(c->hStageEvent);
-    for (hipEvent_t e : c->raggedEvents) (void)hipEventDestroy(e);
-    if (c->fitStream) (void)hipStreamDestroy(c->fitStream);
-    if (c->hostStream) (void)hipStreamDestroy(c->hostStream);
-    if (c->hostCopyStream) (void)hipStreamDestroy(c->hostCopyStream);
-    for (hipEvent_t e : c->hostEvents) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->pipeEvents) (void)hipEventDestroy(e);
-    if (c->comm && rccl().ok) (void)rccl().CommDestroy(c->comm);
-    if (c->searchStream) (void)hipStreamDestroy(c->searchStream);
-    if (c->storeStream) (void)hipStreamDestroy(c->storeStream);
-    for (hipEvent_t e : c->workEvents) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->workTimers) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->packTimers) (void)hipEventDestroy(e);
-    for (auto &slot : c->windowSlots)
-    {
-      slot.host.release();
-      if (slot.done) (void)hipEventDestroy(slot.done);
-    }
-    if (c->copyStream) (void)hipStreamDestroy(c->copyStream);
-    for (hipEvent_t e : c->bandEvents) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
-    delete c;
+    delete *ppCtx; // (an idle device first: ~limg_hip_context)
     *ppCtx = nullptr;
   }
 
@@ -135,7 +107,6 @@ extern "C"
     memcpy(&full, o, n < sizeof(full) ? n : sizeof(full));
     full.struct_size = (uint32_t)sizeof(full);
     c->opt = full;
-    c->forceSplit = full.force_split_kernels != 0;
     return limg_hip_success;
   }
 
@@ -159,31 +130,31 @@ extern "C"
     if (!c) return limg_hip_error_ArgumentNull;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
-    if (c->devStatus.p)
+    if (c->enc.devStatus.p)
     {
       uint32_t word = 0;
-      HIP_TRY(hipMemcpy(&word, c->devStatus.p, 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&word, c->enc.devStatus.p, 4, hipMemcpyDeviceToHost));
       if (word != 0)
       {
-        HIP_TRY(hipMemset(c->devStatus.p, 0, 4)); // sticky until reported once
+        HIP_TRY(hipMemset(c->enc.devStatus.p, 0, 4)); // sticky until reported once
         fprintf(stderr, "limg_hip: look-back timeout in the fused encode kernel\n");
         return limg_hip_error_Generic;
       }
-      HIP_TRY(hipMemcpy(&word, (const uint8_t *)c->devStatus.p + 4, 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&word, (const uint8_t *)c->enc.devStatus.p + 4, 4, hipMemcpyDeviceToHost));
       if (word != 0)
       {
-        HIP_TRY(hipMemset((uint8_t *)c->devStatus.p + 4, 0, 4));
+        HIP_TRY(hipMemset((uint8_t *)c->enc.devStatus.p + 4, 0, 4));
         fprintf(stderr, "limg_hip: a rank of the communicator aborted a single-chain encode; this rank's planes of that encode were not written\n");
         return limg_hip_error_Generic;
       }
     }
-    if (c->streamStatus.p)
+    if (c->stream.status.p)
     {
       uint32_t word = 0;
-      HIP_TRY(hipMemcpy(&word, c->streamStatus.p, 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&word, c->stream.status.p, 4, hipMemcpyDeviceToHost));
       if (word != 0)
       {
-        HIP_TRY(hipMemset(c->streamStatus.p, 0, 4));
+        HIP_TRY(hipMemset(c->stream.status.p, 0, 4));
         fprintf(stderr, "limg_hip: stream refused by the decode kernel (%s)\n", (word & 1u) ? "header mismatch" : "inconsistent payload offsets");
         return limg_hip_error_InvalidParameter;
       }
@@ -195,24 +166,24 @@ extern "C"
   {
     if (!c || !pCounters30) return limg_hip_error_ArgumentNull;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry); // (the host-pointer entries write this state under the same lock)
-    if (c->statsState == 0) return limg_hip_error_InvalidParameter; // no encode with limg_hip_options.collect_stats since the last reset
-    if (c->statsState == 1)
+    if (c->stats.state == 0) return limg_hip_error_InvalidParameter; // no encode with limg_hip_options.collect_stats since the last reset
+    if (c->stats.state == 1)
     {
       HIP_TRY(hipSetDevice(c->device));
-      HIP_TRY(hipMemcpyAsync(c->statsHost, c->stats.p, 30 * 8, hipMemcpyDeviceToHost, c->statsStream));
-      HIP_TRY(hipStreamSynchronize(c->statsStream));
-      c->statsState = 2;
+      HIP_TRY(hipMemcpyAsync(c->stats.host, c->stats.counters.p, 30 * 8, hipMemcpyDeviceToHost, c->stats.stream));
+      HIP_TRY(hipStreamSynchronize(c->stats.stream));
+      c->stats.state = 2;
     }
-    memcpy(pCounters30, c->statsHost, 30 * 8);
-    if (pPixels) *pPixels = c->statsPixels;
+    memcpy(pCounters30, c->stats.host, 30 * 8);
+    if (pPixels) *pPixels = c->stats.pixels;
     return limg_hip_success;
   }
 
   limg_hip_result limg_hip_profile_begin(limg_hip_context *c)
   {
     if (!c) return limg_hip_error_ArgumentNull;
-    c->profiling = true;
-    c->eventsUsed = 0;
+    c->enc.profiling = true;
+    c->enc.eventsUsed = 0;
     return limg_hip_success;
   }
 
@@ -221,38 +192,34 @@ extern "C"
   int limg_hip_profile_end(limg_hip_context *c, float *pMs, int maxEncodes)
   {
     if (!c || !pMs) return -1;
-    c->profiling = false;
-    const int n = (int)(c->eventsUsed / 4);
+    c->enc.profiling = false;
+    const int n = (int)(c->enc.eventsUsed / 4);
     int written = 0;
     for (int i = 0; i < n && i < maxEncodes; i++, written++)
     {
-      if (hipEventSynchronize(c->events[4 * i + 3]) != hipSuccess) return -1;
+      if (hipEventSynchronize(c->enc.events[4 * i + 3]) != hipSuccess) return -1;
       for (int k = 0; k < 3; k++)
-        if (hipEventElapsedTime(&pMs[3 * i + k], c->events[4 * i + k], c->events[4 * i + k + 1]) != hipSuccess) return -1;
+        if (hipEventElapsedTime(&pMs[3 * i + k], c->enc.events[4 * i + k], c->enc.events[4 * i + k + 1]) != hipSuccess) return -1;
     }
-    c->eventsUsed = 0;
+    c->enc.eventsUsed = 0;
     return written;
   }
 
-
   size_t limg_hip_context_device_bytes(const limg_hip_context *c)
   {
-    if (!c) return 0;
-    size_t sum = 0;
-    limg_hip_context::for_each_device_buffer(*c, [&](const DevBuf &b) { sum += b.cap; });
-    return sum;
+    return c ? c->deviceBytes.load(std::memory_order_relaxed) : 0;
   }
 
   double limg_hip_compare_device(limg_hip_context *c, const uint32_t *a, const uint32_t *b, size_t sizeX, size_t sizeY, int hasAlpha, double *pMse, double *pMax, void *stream)
   {
     if (!c || !a || !b || sizeX == 0 || sizeY == 0) return NAN;
     if (hipSetDevice(c->device) != hipSuccess) return NAN;
-    if (c->cmp.ensure(8) != limg_hip_success) return NAN;
+    if (c->enc.cmp.ensure(8) != limg_hip_success) return NAN;
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(c->cmp.p, 0, 8, s) != hipSuccess) return NAN;
-    launch_compare(a, b, (uint64_t)sizeX * sizeY, hasAlpha ? 4 : 3, (unsigned long long *)c->cmp.p, s);
+    if (hipMemsetAsync(c->enc.cmp.p, 0, 8, s) != hipSuccess) return NAN;
+    launch_compare(a, b, (uint64_t)sizeX * sizeY, hasAlpha ? 4 : 3, (unsigned long long *)c->enc.cmp.p, s);
     unsigned long long err = 0;
-    if (hipMemcpyAsync(&err, c->cmp.p, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NAN;
+    if (hipMemcpyAsync(&err, c->enc.cmp.p, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NAN;
     // maxError = limg_color_error(min, max): red diff 255^2 >= 0x4000 => factors {3,4,2,3}
     const double maxError = 255.0 * 255.0 * (hasAlpha ? 12.0 : 9.0);
     const double mse = (double)err / (double)(sizeX * sizeY);
@@ -267,9 +234,9 @@ extern "C"
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
     if (hipSetDevice(c->device) != hipSuccess) return NAN;
     const size_t bytes = sizeX * sizeY * 4;
-    if (c->in.ensure(bytes) != limg_hip_success || c->planes.ensure(bytes) != limg_hip_success) return NAN;
-    if (hipMemcpy(c->in.p, a, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c->planes.p, b, bytes, hipMemcpyHostToDevice) != hipSuccess) return NAN;
-    return limg_hip_compare_device(c, (const uint32_t *)c->in.p, (const uint32_t *)c->planes.p, sizeX, sizeY, hasAlpha, pMse, pMax, nullptr);
+    if (c->host.in.ensure(bytes) != limg_hip_success || c->host.planes.ensure(bytes) != limg_hip_success) return NAN;
+    if (hipMemcpy(c->host.in.p, a, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c->host.planes.p, b, bytes, hipMemcpyHostToDevice) != hipSuccess) return NAN;
+    return limg_hip_compare_device(c, (const uint32_t *)c->host.in.p, (const uint32_t *)c->host.planes.p, sizeX, sizeY, hasAlpha, pMse, pMax, nullptr);
   }
 
   limg_hip_result limg_hip_synth_random_gradient_device(uint32_t *pOut, size_t width, size_t height, uint64_t seed, int opaque, size_t y0, void *stream)

@@ -85,10 +85,6 @@ namespace
     return limg_hip_success;
   }
 
-  limg_hip_result ensure_events(std::vector<hipEvent_t> &events, size_t n, unsigned flags)
-  { for (hipEvent_t e; events.size() < n; events.push_back(e)) HIP_TRY(hipEventCreateWithFlags(&e, flags)); return limg_hip_success; }
-  limg_hip_result ensure_stream(hipStream_t &stream) { if (!stream) HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); return limg_hip_success; }
-
   // Resources: every buffer, stream and event of the call, before anything is enqueued -- a failure leaves no work in flight.  Buffers are sized for the worst
   // case, so that nothing is reallocated while the pipeline runs.
   limg_hip_result ensure_resources(BlockedJob &j)
@@ -96,31 +92,32 @@ namespace
     limg_hip_context *c = j.c;
     const size_t blocks = j.blocks, maxCalls = j.maxCalls, px = j.sizeX * j.sizeY, capMax = j.bp.scratchCap;
     const bool bound = TOPT(c, blocked_no_bound) == 0;
-    limg_hip_result r = ensure_events(c->workTimers, 4 * kInFlight + 3, hipEventDefault);
+    limg_hip_result r = c->blocked.workTimers.ensure(4 * kInFlight + 3, hipEventDefault);
     auto need = [&r](auto &buf, size_t bytes) { if (r == limg_hip_success) r = buf.ensure(bytes); };
-    need(c->bMatch, blocks * kMatchWords * 8); need(c->bFlags, blocks); need(c->hFlags, blocks + 16); // (+ 16: the merge's scan reads 16 flags at a time)
-    if (bound) need(c->bBound, blocks * 16);
-    need(c->hRec, blocks * sizeof(limg_hip_block_record)); need(c->hBits, blocks * kMatchWords * 8);
-    if (r == limg_hip_success) r = ensure_events(c->bandEvents, 2 * kBands + 1, hipEventDisableTiming);
-    need(c->hDesc, blocks * sizeof(RegionDesc)); need(c->hOut, blocks * sizeof(RegionOut)); need(c->hNoiseBase, blocks * 8 + 8);
-    need(c->hNoise, maxCalls * 20 + 64); need(c->bCalls, maxCalls * 20 + 64); // per dither call 8 + 8 + 4 bytes
-    need(c->bRegions, blocks * sizeof(RegionDesc)); need(c->bOut, blocks * sizeof(RegionOut)); need(c->bNoiseBase, blocks * 8 + 8); need(c->bOrder, blocks * 4);
-    need(c->bNoise, 3 * px + 64); need(c->bPx, capMax * 4); need(c->bFac, capMax * 3);
-    for (hipStream_t *st : { &c->copyStream, &c->searchStream, &c->storeStream }) // (in this order: HIP maps streams to hardware queues in creation order)
-      if (r == limg_hip_success) r = ensure_stream(*st);
-    if (r == limg_hip_success) r = ensure_events(c->workEvents, kInFlight, hipEventDisableTiming);
+    need(c->blocked.match, blocks * kMatchWords * 8); need(c->blocked.flags, blocks); need(c->blocked.hFlags, blocks + 16); // (+ 16: the merge's scan reads 16 flags at a time)
+    if (bound) need(c->blocked.bound, blocks * 16);
+    need(c->blocked.hRec, blocks * sizeof(limg_hip_block_record)); need(c->blocked.hBits, blocks * kMatchWords * 8);
+    if (r == limg_hip_success) r = c->blocked.bandEvents.ensure(2 * kBands + 1, hipEventDisableTiming);
+    need(c->blocked.hDesc, blocks * sizeof(RegionDesc)); need(c->blocked.hOut, blocks * sizeof(RegionOut)); need(c->blocked.hNoiseBase, blocks * 8 + 8);
+    need(c->blocked.hNoise, maxCalls * 20 + 64); need(c->blocked.calls, maxCalls * 20 + 64); // per dither call 8 + 8 + 4 bytes
+    need(c->blocked.regions, blocks * sizeof(RegionDesc)); need(c->blocked.out, blocks * sizeof(RegionOut)); need(c->blocked.noiseBase, blocks * 8 + 8); need(c->blocked.order, blocks * 4);
+    need(c->blocked.noise, 3 * px + 64); need(c->blocked.px, capMax * 4); need(c->blocked.fac, capMax * 3);
+    hipStream_t made;
+    for (Stream *st : { &c->blocked.copyStream, &c->blocked.searchStream, &c->blocked.storeStream }) // (in this order: HIP maps streams to hardware queues in creation order)
+      if (r == limg_hip_success) r = st->get(made);
+    if (r == limg_hip_success) r = c->blocked.workEvents.ensure(kInFlight, hipEventDisableTiming);
     if (r != limg_hip_success) return r;
-    try { c->regionPx.resize(blocks); }
+    try { c->blocked.regionPx.resize(blocks); }
     catch (const std::bad_alloc &) { return limg_hip_error_MemoryAllocationFailure; }
-    j.npx = c->regionPx.data();
-    j.frontTimers = c->workTimers.data() + 4 * kInFlight;
-    j.hRec = (limg_hip_block_record *)c->hRec.p; j.hBits = (unsigned long long *)c->hBits.p; j.hFlags = (uint8_t *)c->hFlags.p;
-    j.desc = (RegionDesc *)c->hDesc.p; j.hOut = (RegionOut *)c->hOut.p; j.noiseBase = (unsigned long long *)c->hNoiseBase.p;
-    j.callState = (unsigned long long *)c->hNoise.p; j.callOff = j.callState + maxCalls; j.callPx = (uint32_t *)(j.callOff + maxCalls);
-    j.dCallState = (unsigned long long *)c->bCalls.p; j.dCallOff = j.dCallState + maxCalls; j.dCallPx = (uint32_t *)(j.dCallOff + maxCalls);
-    j.bp.matchBits = (unsigned long long *)c->bMatch.p; j.bp.matchFlags = (uint8_t *)c->bFlags.p;
-    if (bound) j.bp.matchBound = (float *)c->bBound.p;
-    j.bp.scratchPx = (uint32_t *)c->bPx.p; j.bp.scratchFac = (uint8_t *)c->bFac.p; j.bp.noise = (const uint8_t *)c->bNoise.p;
+    j.npx = c->blocked.regionPx.data();
+    j.frontTimers = c->blocked.workTimers.data() + 4 * kInFlight;
+    j.hRec = (limg_hip_block_record *)c->blocked.hRec.p; j.hBits = (unsigned long long *)c->blocked.hBits.p; j.hFlags = (uint8_t *)c->blocked.hFlags.p;
+    j.desc = (RegionDesc *)c->blocked.hDesc.p; j.hOut = (RegionOut *)c->blocked.hOut.p; j.noiseBase = (unsigned long long *)c->blocked.hNoiseBase.p;
+    j.callState = (unsigned long long *)c->blocked.hNoise.p; j.callOff = j.callState + maxCalls; j.callPx = (uint32_t *)(j.callOff + maxCalls);
+    j.dCallState = (unsigned long long *)c->blocked.calls.p; j.dCallOff = j.dCallState + maxCalls; j.dCallPx = (uint32_t *)(j.dCallOff + maxCalls);
+    j.bp.matchBits = (unsigned long long *)c->blocked.match.p; j.bp.matchFlags = (uint8_t *)c->blocked.flags.p;
+    if (bound) j.bp.matchBound = (float *)c->blocked.bound.p;
+    j.bp.scratchPx = (uint32_t *)c->blocked.px.p; j.bp.scratchFac = (uint8_t *)c->blocked.fac.p; j.bp.noise = (const uint8_t *)c->blocked.noise.p;
     return limg_hip_success;
   }
 
@@ -130,11 +127,11 @@ namespace
   {
     limg_hip_context *c = j.c;
     BlockedParams &bp = j.bp;
-    const hipStream_t s = j.s, cs = c->copyStream;
+    const hipStream_t s = j.s, cs = c->blocked.copyStream;
     // The records go to the host as well, but the merge reads them only for pairs outside the similarity window (a few dozen per image): their copy (64 MB for 8192^2,
     // 1.3 ms of PCIe) is queued BEHIND the first two bands' bits, and the merge waits for it when it first needs a record -- not before it starts.
     HIP_TRY(hipEventRecord(j.frontTimers[1], s));
-    c->lastBlocks = j.blocks;
+    c->blocked.lastBlocks = j.blocks;
     launch_blocked_bounds(bp, s);
     for (uint32_t b = 0; b < j.nBands; b++)
     {
@@ -142,20 +139,20 @@ namespace
       bp.seedBase = row0 * j.blocksX; bp.seedCount = rows * j.blocksX;
       launch_blocked_match(bp, s);
       HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(c->bandEvents[2 * b], s));
-      HIP_TRY(hipStreamWaitEvent(cs, c->bandEvents[2 * b], 0));
+      HIP_TRY(hipEventRecord(c->blocked.bandEvents[2 * b], s));
+      HIP_TRY(hipStreamWaitEvent(cs, c->blocked.bandEvents[2 * b], 0));
       HIP_TRY(hipMemcpyAsync(j.hBits + (size_t)bp.seedBase * kMatchWords, bp.matchBits + (size_t)bp.seedBase * kMatchWords, (size_t)bp.seedCount * kMatchWords * 8,
                              hipMemcpyDeviceToHost, cs));
       HIP_TRY(hipMemcpyAsync(j.hFlags + bp.seedBase, bp.matchFlags + bp.seedBase, bp.seedCount, hipMemcpyDeviceToHost, cs));
-      HIP_TRY(hipEventRecord(c->bandEvents[2 * b + 1], cs));
+      HIP_TRY(hipEventRecord(c->blocked.bandEvents[2 * b + 1], cs));
       if (b == 1 || (b == 0 && j.nBands == 1))
       {
-        HIP_TRY(hipMemcpyAsync(j.hRec, c->records.p, j.blocks * sizeof(limg_hip_block_record), hipMemcpyDeviceToHost, cs)); // (`cs` has waited for a band's kernel: pass 1 is long done)
-        HIP_TRY(hipEventRecord(c->bandEvents[2 * kBands], cs)); // "records are on the host"
+        HIP_TRY(hipMemcpyAsync(j.hRec, c->enc.records.p, j.blocks * sizeof(limg_hip_block_record), hipMemcpyDeviceToHost, cs)); // (`cs` has waited for a band's kernel: pass 1 is long done)
+        HIP_TRY(hipEventRecord(c->blocked.bandEvents[2 * kBands], cs)); // "records are on the host"
       }
     }
     HIP_TRY(hipEventRecord(j.frontTimers[2], s)); // (`s` holds nothing but the similarity kernels between the two timers: the copies run on `cs`)
-    HIP_TRY(hipEventSynchronize(c->bandEvents[1])); // the first band's bits: the merge can start
+    HIP_TRY(hipEventSynchronize(c->blocked.bandEvents[1])); // the first band's bits: the merge can start
     return limg_hip_success;
   }
 
@@ -173,17 +170,17 @@ namespace
     bool recordsHere = false, bandError = false, failed = false;
     size_t laid = 0; uint64_t cap = 0; // rectangles laid out, their scratch
     clk::time_point end;
-    void need_records() { if (!recordsHere && hipEventSynchronize(j.c->bandEvents[2 * kBands]) != hipSuccess) bandError = true; recordsHere = true; }
+    void need_records() { if (!recordsHere && hipEventSynchronize(j.c->blocked.bandEvents[2 * kBands]) != hipSuccess) bandError = true; recordsHere = true; }
     void need_seed_row(uint32_t row)
     {
       for (; bandsReady < j.nBands && row >= bandsReady * j.bandRows; bandsReady++)
-        if (hipEventSynchronize(j.c->bandEvents[2 * bandsReady + 1]) != hipSuccess) bandError = true;
+        if (hipEventSynchronize(j.c->blocked.bandEvents[2 * bandsReady + 1]) != hipSuccess) bandError = true;
     }
     void publish(size_t count)
     {
       for (size_t i = laid; i < count; i++)
       {
-        const HostRegion &h = j.c->lastRegions[i];
+        const HostRegion &h = j.c->blocked.lastRegions[i];
         size_t xpx = (size_t)h.rx * kBlock, ypx = (size_t)h.ry * kBlock;
         if (h.ox + h.rx == j.blocksX && (j.sizeX % kBlock)) xpx = xpx - kBlock + j.sizeX % kBlock;
         if (h.oy + h.ry == j.blocksY && (j.sizeY % kBlock)) ypx = ypx - kBlock + j.sizeY % kBlock;
@@ -202,7 +199,7 @@ namespace
         const std::function<void()> records = [this] { need_records(); };
         const std::function<void(uint32_t)> seedRow = [this](uint32_t row) { need_seed_row(row); };
         const std::function<void(size_t)> progress = [this](size_t count) { publish(count); };
-        blocked_merge(j.hRec, j.hBits, j.blocksX, j.blocksY, j.channels, j.c->lastRegions, &progress, &seedRow, j.hFlags, &records);
+        blocked_merge(j.hRec, j.hBits, j.blocksX, j.blocksY, j.channels, j.c->blocked.lastRegions, &progress, &seedRow, j.hFlags, &records);
       }
       catch (...) { failed = true; } // out of host memory: the worker must still be released
       need_seed_row(j.blocksY - 1); // every band's copy is complete before the staging buffers can be reused
@@ -244,9 +241,9 @@ namespace
     BlockedParams params_of(const Batch &b) const
     {
       BlockedParams q = j.bp;
-      q.regions = (const RegionDesc *)c->bRegions.p + b.r0; q.nRegions = (uint32_t)(b.r1 - b.r0); q.regionBase = (uint32_t)b.r0;
-      q.out = (RegionOut *)c->bOut.p + b.r0; q.noiseBase = (const unsigned long long *)c->bNoiseBase.p + b.r0;
-      q.order = (b.r1 - b.r0 >= kOrderFrom && TOPT(c, blocked_no_order) == 0) ? (uint32_t *)c->bOrder.p + b.r0 : nullptr; // (a small batch is one round of workgroups anyway)
+      q.regions = (const RegionDesc *)c->blocked.regions.p + b.r0; q.nRegions = (uint32_t)(b.r1 - b.r0); q.regionBase = (uint32_t)b.r0;
+      q.out = (RegionOut *)c->blocked.out.p + b.r0; q.noiseBase = (const unsigned long long *)c->blocked.noiseBase.p + b.r0;
+      q.order = (b.r1 - b.r0 >= kOrderFrom && TOPT(c, blocked_no_order) == 0) ? (uint32_t *)c->blocked.order.p + b.r0 : nullptr; // (a small batch is one round of workgroups anyway)
       return q;
     }
     // Everything the merge has published since the last look goes to the GPU as one batch.  mayWait: nothing is left to walk, so wait for the merge.
@@ -263,19 +260,19 @@ namespace
       if (r1 == r0) return;
       const Batch nb = { r0, r1, tail % kInFlight };
       if (storeTimed[nb.ev]) // the slot comes round again: its previous batch's store kernels were enqueued kInFlight batches ago
-        if (hipEventSynchronize(c->workTimers[4 * nb.ev + 3]) == hipSuccess) add_elapsed(kernelMs[1], c->workTimers[4 * nb.ev + 2], c->workTimers[4 * nb.ev + 3]);
+        if (hipEventSynchronize(c->blocked.workTimers[4 * nb.ev + 3]) == hipSuccess) add_elapsed(kernelMs[1], c->blocked.workTimers[4 * nb.ev + 2], c->blocked.workTimers[4 * nb.ev + 3]);
       storeTimed[nb.ev] = false;
       if (result == limg_hip_success)
       {
         const size_t n = r1 - r0;
         const BlockedParams q = params_of(nb);
-        const hipStream_t bs = c->searchStream;
-        bool ok = hipMemcpyAsync((RegionDesc *)c->bRegions.p + r0, j.desc + r0, n * sizeof(RegionDesc), hipMemcpyHostToDevice, bs) == hipSuccess;
-        ok = ok && hipEventRecord(c->workTimers[4 * nb.ev], bs) == hipSuccess;
+        const hipStream_t bs = c->blocked.searchStream;
+        bool ok = hipMemcpyAsync((RegionDesc *)c->blocked.regions.p + r0, j.desc + r0, n * sizeof(RegionDesc), hipMemcpyHostToDevice, bs) == hipSuccess;
+        ok = ok && hipEventRecord(c->blocked.workTimers[4 * nb.ev], bs) == hipSuccess;
         if (ok) { launch_blocked_order(q, bs); launch_blocked_fit_search(q, bs); ok = hipGetLastError() == hipSuccess; }
-        ok = ok && hipEventRecord(c->workTimers[4 * nb.ev + 1], bs) == hipSuccess;
-        ok = ok && hipMemcpyAsync(j.hOut + r0, (RegionOut *)c->bOut.p + r0, n * sizeof(RegionOut), hipMemcpyDeviceToHost, bs) == hipSuccess;
-        ok = ok && hipEventRecord(c->workEvents[nb.ev], bs) == hipSuccess;
+        ok = ok && hipEventRecord(c->blocked.workTimers[4 * nb.ev + 1], bs) == hipSuccess;
+        ok = ok && hipMemcpyAsync(j.hOut + r0, (RegionOut *)c->blocked.out.p + r0, n * sizeof(RegionOut), hipMemcpyDeviceToHost, bs) == hipSuccess;
+        ok = ok && hipEventRecord(c->blocked.workEvents[nb.ev], bs) == hipSuccess;
         if (!ok) result = limg_hip_error_Generic;
       }
       queue[tail++ % kInFlight] = nb;
@@ -285,8 +282,8 @@ namespace
     void walk_and_store(const Batch pending, clk::time_point w0)
     {
       if (result != limg_hip_success) return;
-      bool ok = hipEventSynchronize(c->workEvents[pending.ev]) == hipSuccess;
-      if (ok) add_elapsed(kernelMs[0], c->workTimers[4 * pending.ev], c->workTimers[4 * pending.ev + 1]);
+      bool ok = hipEventSynchronize(c->blocked.workEvents[pending.ev]) == hipSuccess;
+      if (ok) add_elapsed(kernelMs[0], c->blocked.workTimers[4 * pending.ev], c->blocked.workTimers[4 * pending.ev + 1]);
       const clk::time_point w1 = clk::now();
       // the dither chain (src/limg_internal.h:711, src/limg.cpp:1541-1551): one chain through all rectangles in creation order; a call over N
       // pixels advances it by floor(N / 8) AES rounds + N % 8 PCG steps, so it is walked here -- for the chain VALUES only: every call's start value, pixel
@@ -303,19 +300,19 @@ namespace
       }
       const clk::time_point w2 = clk::now();
       const size_t nc = callCount - call0;
-      const hipStream_t ss = c->storeStream; // noise expansion + store kernels of a batch: beside the next batch's fit + search kernel, not behind it
-      ok = ok && hipStreamWaitEvent(ss, c->workEvents[pending.ev], 0) == hipSuccess; // this batch's records and shift words are in bOut
-      ok = ok && hipEventRecord(c->workTimers[4 * pending.ev + 2], ss) == hipSuccess;
+      const hipStream_t ss = c->blocked.storeStream; // noise expansion + store kernels of a batch: beside the next batch's fit + search kernel, not behind it
+      ok = ok && hipStreamWaitEvent(ss, c->blocked.workEvents[pending.ev], 0) == hipSuccess; // this batch's records and shift words are in bOut
+      ok = ok && hipEventRecord(c->blocked.workTimers[4 * pending.ev + 2], ss) == hipSuccess;
       if (ok && nc)
       {
         ok = hipMemcpyAsync(j.dCallState + call0, j.callState + call0, nc * 8, hipMemcpyHostToDevice, ss) == hipSuccess &&
              hipMemcpyAsync(j.dCallOff + call0, j.callOff + call0, nc * 8, hipMemcpyHostToDevice, ss) == hipSuccess &&
              hipMemcpyAsync(j.dCallPx + call0, j.callPx + call0, nc * 4, hipMemcpyHostToDevice, ss) == hipSuccess;
-        if (ok) { launch_noise_expand_calls((uint8_t *)c->bNoise.p, j.dCallState + call0, j.dCallOff + call0, j.dCallPx + call0, nc, j.pcg, ss); ok = hipGetLastError() == hipSuccess; }
+        if (ok) { launch_noise_expand_calls((uint8_t *)c->blocked.noise.p, j.dCallState + call0, j.dCallOff + call0, j.dCallPx + call0, nc, j.pcg, ss); ok = hipGetLastError() == hipSuccess; }
       }
-      ok = ok && hipMemcpyAsync((unsigned long long *)c->bNoiseBase.p + pending.r0, j.noiseBase + pending.r0, (pending.r1 - pending.r0) * 8, hipMemcpyHostToDevice, ss) == hipSuccess;
+      ok = ok && hipMemcpyAsync((unsigned long long *)c->blocked.noiseBase.p + pending.r0, j.noiseBase + pending.r0, (pending.r1 - pending.r0) * 8, hipMemcpyHostToDevice, ss) == hipSuccess;
       if (ok && !j.compact) { launch_blocked_store(params_of(pending), ss); ok = hipGetLastError() == hipSuccess; }
-      if (ok && hipEventRecord(c->workTimers[4 * pending.ev + 3], ss) == hipSuccess) storeTimed[pending.ev] = true;
+      if (ok && hipEventRecord(c->blocked.workTimers[4 * pending.ev + 3], ss) == hipSuccess) storeTimed[pending.ev] = true;
       const clk::time_point w3 = clk::now();
       busy[0] += ms(w0, w1); busy[1] += ms(w1, w2); busy[2] += ms(w2, w3);
       if (!ok) result = limg_hip_error_Generic;
@@ -330,10 +327,10 @@ namespace
         if (head < tail) walk_and_store(queue[head++ % kInFlight], w0);
         if (fin && head == tail) break;
       }
-      if (hipStreamSynchronize(c->searchStream) != hipSuccess && result == limg_hip_success) result = limg_hip_error_Generic;
-      if (hipStreamSynchronize(c->storeStream) != hipSuccess && result == limg_hip_success) result = limg_hip_error_Generic;
+      if (hipStreamSynchronize(c->blocked.searchStream) != hipSuccess && result == limg_hip_success) result = limg_hip_error_Generic;
+      if (hipStreamSynchronize(c->blocked.storeStream) != hipSuccess && result == limg_hip_success) result = limg_hip_error_Generic;
       for (size_t i = 0; i < kInFlight; i++)
-        if (storeTimed[i]) add_elapsed(kernelMs[1], c->workTimers[4 * i + 2], c->workTimers[4 * i + 3]);
+        if (storeTimed[i]) add_elapsed(kernelMs[1], c->blocked.workTimers[4 * i + 2], c->blocked.workTimers[4 * i + 3]);
     }
   };
 
@@ -341,16 +338,16 @@ namespace
   void collect_stats(const BlockedJob &j)
   {
     limg_hip_context *c = j.c;
-    memset(c->statsHost, 0, sizeof(c->statsHost));
-    for (size_t i = 0; i < c->lastRegions.size(); i++)
+    memset(c->stats.host, 0, sizeof(c->stats.host));
+    for (size_t i = 0; i < c->blocked.lastRegions.size(); i++)
       for (int f = 0; f < 3; f++)
       {
         uint32_t sh = (j.hOut[i].shiftWord >> (8 * f)) & 0xFFu;
         if (sh > 8) sh = 8;
-        c->statsHost[f] += (uint64_t)(8 - sh) * j.npx[i];
-        c->statsHost[3 + 9 * f + sh] += j.npx[i];
+        c->stats.host[f] += (uint64_t)(8 - sh) * j.npx[i];
+        c->stats.host[3 + 9 * f + sh] += j.npx[i];
       }
-    c->statsState = 2; c->statsPixels = (uint64_t)j.sizeX * j.sizeY;
+    c->stats.state = 2; c->stats.pixels = (uint64_t)j.sizeX * j.sizeY;
   }
 }
 
@@ -427,13 +424,13 @@ namespace limg_hip
     BlockedJob j; limg_hip_result r;
     if ((r = set_up(j, c, pIn, sizeX, sizeY, hasAlpha, pInfo ? *pInfo : noPlanes, errorFactor, fastBitCrushing, stream, pInfo == nullptr)) != limg_hip_success) return r;
     if ((r = ensure_resources(j)) != limg_hip_success) return r;
-    c->blockedScratchCap = j.bp.scratchCap; c->packTimed = false; c->lastBlocked.valid = false;
+    c->blocked.scratchCap = j.bp.scratchCap; c->stream.packTimed = false; c->blocked.last.valid = false;
     // pass 1 (src/limg.cpp:1088-1119): every block's own fit = the 8x8 path's E step, records only
     EncodeExtra x1; x1.fitOnly = true;
     HIP_TRY(hipEventRecord(j.frontTimers[0], j.s));
     if ((r = encode_device(c, pIn, sizeX, sizeY, hasAlpha, nullptr, nullptr, errorFactor, 0, fastBitCrushing, j.s, x1)) != limg_hip_success) return r;
-    j.bp.pass1 = (const limg_hip_block_record *)c->records.p;
-    if ((r = similarity_bands(j)) != limg_hip_success) { (void)hipStreamSynchronize(c->copyStream); return r; } // (no copy into the pinned staging may outlive the call)
+    j.bp.pass1 = (const limg_hip_block_record *)c->enc.records.p;
+    if ((r = similarity_bands(j)) != limg_hip_success) { (void)hipStreamSynchronize(c->blocked.copyStream); return r; } // (no copy into the pinned staging may outlive the call)
     const clk::time_point t1 = clk::now();
     Pipe pipe;
     Merge merge{ j, pipe };
@@ -443,15 +440,15 @@ namespace limg_hip
     const clk::time_point t5 = clk::now();
     double a = 0, b = 0; // (both intervals ended before the merge's last band arrived)
     const bool ok = add_elapsed(a, j.frontTimers[0], j.frontTimers[1]) && add_elapsed(b, j.frontTimers[1], j.frontTimers[2]);
-    c->blockedKernelMs[0] = ok ? a : 0; c->blockedKernelMs[1] = ok ? b : 0; c->blockedKernelMs[2] = worker.kernelMs[0]; c->blockedKernelMs[3] = worker.kernelMs[1];
-    c->blockedMs[0] = ms(t0, t1); c->blockedMs[1] = ms(t1, merge.end); c->blockedMs[2] = worker.busy[0]; c->blockedMs[3] = worker.busy[1]; c->blockedMs[4] = worker.busy[2];
-    c->blockedMs[5] = ms(t0, t5);
+    c->blocked.kernelMs[0] = ok ? a : 0; c->blocked.kernelMs[1] = ok ? b : 0; c->blocked.kernelMs[2] = worker.kernelMs[0]; c->blocked.kernelMs[3] = worker.kernelMs[1];
+    c->blocked.ms[0] = ms(t0, t1); c->blocked.ms[1] = ms(t1, merge.end); c->blocked.ms[2] = worker.busy[0]; c->blocked.ms[3] = worker.busy[1]; c->blocked.ms[4] = worker.busy[2];
+    c->blocked.ms[5] = ms(t0, t5);
     if (merge.failed) return limg_hip_error_MemoryAllocationFailure;
     if (merge.bandError) return limg_hip_error_Generic;
     if (worker.result == limg_hip_success && c->opt.collect_stats) collect_stats(j);
-    c->lastBlocked.sizeX = sizeX; c->lastBlocked.sizeY = sizeY; c->lastBlocked.channels = j.channels; c->lastBlocked.errorFactor = errorFactor;
-    c->lastBlocked.flags = (fastBitCrushing ? 1u : 0u) | (j.pcg ? 2u : 0u);
-    c->lastBlocked.valid = worker.result == limg_hip_success;
+    c->blocked.last.sizeX = sizeX; c->blocked.last.sizeY = sizeY; c->blocked.last.channels = j.channels; c->blocked.last.errorFactor = errorFactor;
+    c->blocked.last.flags = (fastBitCrushing ? 1u : 0u) | (j.pcg ? 2u : 0u);
+    c->blocked.last.valid = worker.result == limg_hip_success;
     return worker.result;
   }
 }
@@ -462,14 +459,14 @@ extern "C"
   limg_hip_result limg_hip_blocked_regions(limg_hip_context *c, limg_hip_region *pRegions, size_t capacity, size_t *pCount)
   {
     if (!c || !pCount) return limg_hip_error_ArgumentNull;
-    *pCount = copy_regions(c->lastRegions, pRegions, capacity);
+    *pCount = copy_regions(c->blocked.lastRegions, pRegions, capacity);
     return limg_hip_success;
   }
 
   limg_hip_result limg_hip_blocked_timing(limg_hip_context *c, double *pMs6)
   {
     if (!c || !pMs6) return limg_hip_error_ArgumentNull;
-    memcpy(pMs6, c->blockedMs, sizeof(c->blockedMs));
+    memcpy(pMs6, c->blocked.ms, sizeof(c->blocked.ms));
     return limg_hip_success;
   }
 
@@ -477,22 +474,22 @@ extern "C"
   { // the similarity bits the last merged-block encode's merge worked from (they stay in the context's pinned staging buffer until the next encode)
     if (!c || !pWords) return limg_hip_error_ArgumentNull;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    const size_t words = c->lastBlocks * kMatchWords;
+    const size_t words = c->blocked.lastBlocks * kMatchWords;
     *pWords = words;
-    if (pBits && c->hBits.p) memcpy(pBits, c->hBits.p, (words < capacityWords ? words : capacityWords) * 8);
+    if (pBits && c->blocked.hBits.p) memcpy(pBits, c->blocked.hBits.p, (words < capacityWords ? words : capacityWords) * 8);
     return limg_hip_success;
   }
 
   limg_hip_result limg_hip_blocked_kernel_timing(limg_hip_context *c, double *pMs4)
   {
     if (!c || !pMs4) return limg_hip_error_ArgumentNull;
-    if (c->packTimed)
+    if (c->stream.packTimed)
     { // a stream encode: its scan + pack kernels were enqueued behind the pipeline (limg_hip_stream_api.hip) and belong to slot [3]
       float t = 0;
-      if (hipEventSynchronize(c->packTimers[1]) == hipSuccess && hipEventElapsedTime(&t, c->packTimers[0], c->packTimers[1]) == hipSuccess) c->blockedKernelMs[3] += t;
-      c->packTimed = false;
+      if (hipEventSynchronize(c->stream.packTimers[1]) == hipSuccess && hipEventElapsedTime(&t, c->stream.packTimers[0], c->stream.packTimers[1]) == hipSuccess) c->blocked.kernelMs[3] += t;
+      c->stream.packTimed = false;
     }
-    memcpy(pMs4, c->blockedKernelMs, sizeof(c->blockedKernelMs));
+    memcpy(pMs4, c->blocked.kernelMs, sizeof(c->blocked.kernelMs));
     return limg_hip_success;
   }
 
@@ -518,14 +515,14 @@ extern "C"
     HIP_TRY(hipSetDevice(c->device));
     const size_t px = sizeX * sizeY, stride = (px * 4 + 255) & ~(size_t)255;
     limg_hip_result r;
-    if ((r = c->in.ensure(px * 4)) != limg_hip_success) return r;
-    if ((r = c->planes.ensure(stride * 13)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(c->in.p, pIn, px * 4, hipMemcpyHostToDevice));
+    if ((r = c->host.in.ensure(px * 4)) != limg_hip_success) return r;
+    if ((r = c->host.planes.ensure(stride * 13)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->host.in.p, pIn, px * 4, hipMemcpyHostToDevice));
     if (!has_written_planes(*pInfo)) return limg_hip_error_ArgumentNull;
     limg_hip_blocked_encode3d_info d = {};
     size_t i = 0; // 13 written planes, one `stride` each (the uint8 ones use a quarter of theirs)
-    for_each_written_plane([&](auto m) { d.*m = (std::decay_t<decltype(d.*m)>)((uint8_t *)c->planes.p + stride * i++); });
-    if ((r = limg_hip_blocked_encode3d_device(c, (const uint32_t *)c->in.p, sizeX, sizeY, hasAlpha, &d, errorFactor, fastBitCrushing, nullptr)) != limg_hip_success) return r;
+    for_each_written_plane([&](auto m) { d.*m = (std::decay_t<decltype(d.*m)>)((uint8_t *)c->host.planes.p + stride * i++); });
+    if ((r = limg_hip_blocked_encode3d_device(c, (const uint32_t *)c->host.in.p, sizeX, sizeY, hasAlpha, &d, errorFactor, fastBitCrushing, nullptr)) != limg_hip_success) return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
     hipError_t e = hipSuccess;
     for_each_written_plane([&](auto m) { if (e == hipSuccess) e = hipMemcpy(pInfo->*m, d.*m, px * sizeof(*(d.*m)), hipMemcpyDeviceToHost); });

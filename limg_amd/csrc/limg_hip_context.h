@@ -4,6 +4,7 @@
 #define LIMG_HIP_CONTEXT_H
 
 #include "limg_hip_internal.h"
+#include "limg_hip_owned.h"
 #ifdef LIMG_HIP_TEST_HOOKS
 #include "../../include/limg_hip_test_hooks.h"
 #define TOPT(c, member) ((c)->topt.member)
@@ -13,57 +14,10 @@
 #include "limg_hip_rccl.h"
 
 #include <stddef.h>
-#include <stdio.h>
 #include <string.h>
 #include <new>
 #include <mutex>
 #include <thread>
-#include <vector>
-
-#define HIP_TRY(expr)                                                                                                     \
-  do                                                                                                                      \
-  {                                                                                                                       \
-    const hipError_t e_ = (expr);                                                                                         \
-    if (e_ != hipSuccess)                                                                                                 \
-    {                                                                                                                     \
-      fprintf(stderr, "limg_hip: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__);            \
-      return limg_hip_error_Generic;                                                                                      \
-    }                                                                                                                     \
-  } while (0)
-
-struct DevBuf
-{
-  void *p = nullptr;
-  size_t cap = 0;
-  limg_hip_result ensure(size_t bytes)
-  {
-    if (bytes <= cap) return limg_hip_success;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; return limg_hip_error_MemoryAllocationFailure; }
-    cap = bytes;
-    return limg_hip_success;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-// pinned host memory owned by the context (staging of the merged-block encoder's host stages: no zero fill, full-rate PCIe copies)
-struct HostBuf
-{
-  void *p = nullptr;
-  size_t cap = 0;
-  limg_hip_result ensure(size_t bytes)
-  {
-    if (bytes <= cap) return limg_hip_success;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 4; // grow with slack: sizes depend on the image content
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return limg_hip_error_MemoryAllocationFailure; }
-    cap = want;
-    return limg_hip_success;
-  }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
 
 struct limg_hip_context
 {
@@ -77,102 +31,135 @@ struct limg_hip_context
 #ifdef LIMG_HIP_TEST_HOOKS
   limg_hip_test_options topt; // liblimg_hip_test.so only (include/limg_hip_test_hooks.h)
 #endif
-  DevBuf records, shifts, stripCalls, stripBase; // per-block / per-strip scratch
-  DevBuf invN;                                   // per block 1 / |normal|^2 of the three factors (k_fit_tpb -> E step)
-  DevBuf noise;                                  // static dither noise table (full-block chains)
-  bool noisePcg = false;                         // which generator the table was built with
-  size_t noiseCount = 0;                         // entries generated so far
-  uint64_t noiseNext = limg_hip::kDitherSeed;           // chain value after the last generated entry
-  DevBuf noiseDyn;                               // data-dependent chains (images with partial blocks)
-  DevBuf noiseStates;                            // ... their per-call chain values + pixel counts as the host uploads them (k_noise_expand -> noiseDyn)
-  DevBuf noiseCk;                                // the chain checkpoints (limg_noise_checkpoints.h) on the device: the GPU fills the noise table from them
-  size_t noiseCkCount = 0;                       // ... how many dense values (every 1024th call) are there: the embedded ones, or more (ensure_checkpoints)
-  std::vector<uint64_t> noiseCkHost;             // ... and, once an image has reached beyond the embedded dense values, the host copy they were uploaded from
-  DevBuf park;                                   // persistent kernel: 2 x 8 KiB per workgroup
-  DevBuf batchTable;                             // batched encode: one ImageIO per image
-  hipStream_t fitStream = nullptr;               // batched encode in sub-batches: k_fit_tpb of sub-batch k + 1 runs here, next to the persistent kernel of sub-batch k
-  std::vector<hipEvent_t> pipeEvents;            // ... and the events that fork it from / join it to the caller's stream
-  HostBuf hStage;                                // pinned staging of the ragged paths' host step (shift words down; chain bases and noise up)
-  hipEvent_t hStageEvent = nullptr;              // ... recorded behind the last asynchronous H2D copy that reads it: waited for before it is written, grown or freed again
-  bool hStageBusy = false;
-  std::vector<hipEvent_t> raggedEvents;          // banded ragged encode: "the shift words of band b are down"
-  DevBuf stats;                                  // limg_hip_options.collect_stats: the reference's 3 + 27 bit counters of the last encode
-  hipStream_t statsStream = nullptr;
-  int statsState = 0;                            // 0 = none, 1 = on the device (8x8 path), 2 = in statsHost (merged-block encoder)
-  bool statsAccumulate = false;                  // a batched encode in several launch pairs: the pairs after the first add to the counters instead of restarting them
-  uint64_t statsHost[30] = { 0 };
-  uint64_t statsPixels = 0;
-  DevBuf lookback;                               // fused path: ticket (16 B) then one 8-byte descriptor per work strip
-  DevBuf accTable;                               // accurate search: automaton expanded to 32-byte entries (built on the first accurate encode)
-  DevBuf devStatus;                              // sticky look-back timeout word: never touched by the per-launch memset, cleared by limg_hip_check_device_status
-  DevBuf in, planes;                             // staging for the host-pointer entry points
-  hipStream_t hostCopyStream = nullptr;          // ... the downloads of the finished bands (second host thread)
-  hipStream_t hostStream = nullptr;              // ... in row bands: the bands' kernels run here, their events tell the download thread when a band is done
-  std::vector<hipEvent_t> hostEvents;
-  DevBuf hostWords;                              // ... per band its dither-call total and its chain base (one chain through the bands)
-  DevBuf cmp;                                    // 8-byte accumulator of limg_hip_compare
-  DevBuf bFlags, bBound;
-  DevBuf bOrder; // merged-block encoder: per batch the order its workgroups take the rectangles in
-  DevBuf bMatch, bRegions, bOut, bPx, bFac, bNoise, bNoiseBase; // merged-block encoder: similarity bits, region table / results, scratch (gathered pixels, factor bytes), noise
-  HostBuf hFlags;
-  HostBuf hRec, hBits, hDesc, hOut, hNoise, hNoiseBase;
-  hipStream_t searchStream = nullptr; // the merged-block encoder's worker thread launches its fit + search batches on this stream
-  hipStream_t storeStream = nullptr;  // ... and the noise expansion + store kernels of a batch on a second one
-  DevBuf bCalls;                     // per dither call of the merged-block encoder: chain value, noise offset, pixel count (host walk -> k_noise_expand_calls)
-  std::vector<hipEvent_t> workEvents;        // one per batch of the merged-block encoder's worker that is in flight on the GPU
-  hipStream_t copyStream = nullptr;      // copies of the similarity-bit bands, behind the kernels that produce them
-  std::vector<hipEvent_t> bandEvents;
-  std::vector<limg_hip::HostRegion> lastRegions;
-  std::vector<uint32_t> regionPx;            // ... and their pixel counts
-  size_t lastBlocks = 0;                     // blocks of the last merged-block encode (what hBits / lastRegions describe)
-  double blockedMs[6] = { 0, 0, 0, 0, 0, 0 };
-  double blockedKernelMs[4] = { 0, 0, 0, 0 }; // the last merged-block encode, HIP events: pass 1 (k_fit_tpb) / the k_blocked_match launches / the k_blocked_fit_search launches /
-                                             // the noise-expansion + store launches (the last two summed over the worker's batches)
-  std::vector<hipEvent_t> workTimers;        // [4 i .. 4 i + 3]: begin / end of batch slot i's fit + search kernel, begin / end of its expansion + store kernels;
-                                             // [4 kInFlight ..]: begin of pass 1, end of pass 1 = begin of the similarity kernels, their end
-  // multi-GPU (RCCL over xGMI): one communicator per context, created by limg_hip_comm_init
-  ncclComm_t comm = nullptr;
-  int commRank = 0, commWorld = 1;
-  // limg_hip_encode3d_chain_device: phase 2 is only valid right after phase 1 of the same strip (the context holds the intermediate results)
-  const void *chainIn = nullptr;
-  size_t chainX = 0, chainY = 0, chainBefore = 0;
-  const void *chainFac[3] = { nullptr, nullptr, nullptr }; // phase 1 left the pre-dither factor bytes in these planes
-  int chainAlpha = 0, chainFast = 0;
-  uint32_t chainEf = 0;
-  DevBuf commWords; // [0] this rank's value, [1] its chain base, [8 ...] the all-gathered values
-  DevBuf streamFac, streamTiles, streamUnits, streamStatus, streamBuf; // stream packer: 3 factor planes, per-tile payload words; decode status word; host-entry staging
-  DevBuf streamTable, streamSizes; // batched stream encode: one StreamImage per image of the list; the finished streams' sizes side by side (one download)
-  // version 2 stream of the merged-block encoder (limg_hip_stream_api.hip, limg_hip_stream_window_api.hip): per rectangle its first 64-pixel run, per tile of rectangles its totals; the
-  // decoder's block -> rectangle map and its per-call words
-  DevBuf bsUnits, bsTiles, bsMap, bsState;
-  // batched window decode (limg_hip_*decode_stream_windows*): a call's job table -- and, version 2, its map and per-job state words -- lives in one slot of a small
-  // ring, so that a call issued before the previous one has run does not disturb it.  host: pinned, the table as the call builds it; dev: its copy, then state and map;
-  // done: recorded behind the call's last kernel and waited for on the host before the slot is used again.
-  struct WindowSlot { HostBuf host; DevBuf dev; hipEvent_t done = nullptr; bool busy = false; };
-  static constexpr unsigned kWindowSlots = 4;
-  WindowSlot windowSlots[kWindowSlots];
-  unsigned windowSlotNext = 0;
-  size_t blockedScratchCap = 0;              // plane stride of bFac in the last merged-block encode (BlockedParams::scratchCap)
-  struct { size_t sizeX = 0, sizeY = 0; int channels = 0; uint32_t errorFactor = 0, flags = 0; bool valid = false; } lastBlocked; // ... its shape and stream flags; valid: it succeeded,
-                                             // so the context's buffers hold everything the stream packer reads (limg_hip_blocked_last_stream)
-  std::vector<hipEvent_t> packTimers;        // begin / end of the last stream encode's scan + pack kernels ...
-  bool packTimed = false;                    // ... which limg_hip_blocked_kernel_timing still has to add to slot [3]
-  // optional per-kernel timing (bench): 4 events per encode, recorded on the caller's stream, read back in one go
-  int persistentWorkgroups = 1280; // 5 x the device's CU count (set at init): the unit the launches scale (x 6 / 5 with the float stage in its own kernel)
-  bool forceSplit = false; // options: run the three-kernel path even where the fused kernel applies (A/B, tests)
-  bool profiling = false;
-  std::vector<hipEvent_t> events;
-  size_t eventsUsed = 0;
-
-  // every device buffer above, in ONE list: what limg_hip_shutdown frees and limg_hip_context_device_bytes counts (a buffer added to the context goes here)
-  template <class Ctx, class F>
-  static void for_each_device_buffer(Ctx &c, F &&f)
+  // Every buffer, stream and event below belongs to the member that names it (limg_hip_owned.h) and goes with it: limg_hip_shutdown is `delete`.  The members are
+  // grouped by the family of entries that uses them, each family's buffers next to the words that say what they hold.
+  typedef std::atomic<size_t> Bytes;
+  Bytes deviceBytes{ 0 }; // limg_hip_context_device_bytes: kept by the DevBufs themselves (declared before them, so it outlives them)
+  // ---- the 8x8 encode (limg_hip_encode.hip, limg_hip_encode_ragged.hip), compare, profiling ----
+  struct Encode
   {
-    for (auto *b : { &c.records, &c.shifts, &c.stripCalls, &c.stripBase, &c.invN, &c.noise, &c.noiseDyn, &c.noiseStates, &c.noiseCk, &c.park, &c.batchTable, &c.stats,
-                     &c.lookback, &c.accTable, &c.devStatus, &c.in, &c.planes, &c.hostWords, &c.cmp, &c.bFlags, &c.bBound, &c.bOrder, &c.bMatch, &c.bRegions, &c.bOut,
-                     &c.bPx, &c.bFac, &c.bNoise, &c.bNoiseBase, &c.bCalls, &c.commWords, &c.streamFac, &c.streamTiles, &c.streamUnits, &c.streamStatus, &c.streamBuf, &c.streamTable, &c.streamSizes, &c.bsUnits, &c.bsTiles, &c.bsMap, &c.bsState,
-                     &c.windowSlots[0].dev, &c.windowSlots[1].dev, &c.windowSlots[2].dev, &c.windowSlots[3].dev })
-      f(*b);
+    Bytes &n; // the context's deviceBytes, in every group: what its DevBufs count into
+    DevBuf records{ n }, shifts{ n }, stripCalls{ n }, stripBase{ n }; // per-block / per-strip scratch
+    DevBuf invN{ n }; // per block 1 / |normal|^2 of the three factors (k_fit_tpb -> E step)
+    DevBuf park{ n }; // persistent kernel: 2 x 8 KiB per workgroup
+    DevBuf batchTable{ n }; // batched encode: one ImageIO per image
+    Stream fitStream; // batched encode in sub-batches: k_fit_tpb of sub-batch k + 1 runs here, next to the persistent kernel of sub-batch k
+    Events pipeEvents; // ... and the events that fork it from / join it to the caller's stream
+    DevBuf lookback{ n }; // fused path: ticket (16 B) then one 8-byte descriptor per work strip
+    DevBuf accTable{ n }; // accurate search: automaton expanded to 32-byte entries (built on the first accurate encode)
+    DevBuf devStatus{ n }; // sticky look-back timeout word: never touched by the per-launch memset, cleared by limg_hip_check_device_status
+    DevBuf cmp{ n }; // 8-byte accumulator of limg_hip_compare
+    int persistentWorkgroups = 1280; // 5 x the device's CU count (set at init): the unit the launches scale (x 6 / 5 with the float stage in its own kernel)
+    // optional per-kernel timing (bench): 4 events per encode, recorded on the caller's stream, read back in one go
+    bool profiling = false;
+    Events events;
+    size_t eventsUsed = 0;
+  } enc{ deviceBytes };
+  // ---- the dither noise (limg_hip_noise_table.hip; dyn, states: limg_hip_encode_ragged.hip) ----
+  struct Noise
+  {
+    Bytes &n;
+    DevBuf table{ n }; // static dither noise table (full-block chains)
+    bool pcg = false; // which generator the table was built with
+    size_t count = 0; // entries generated so far
+    uint64_t next = limg_hip::kDitherSeed; // chain value after the last generated entry
+    DevBuf dyn{ n }; // data-dependent chains (images with partial blocks)
+    DevBuf states{ n }; // ... their per-call chain values + pixel counts as the host uploads them (k_noise_expand -> dyn)
+    DevBuf ck{ n }; // the chain checkpoints (limg_noise_checkpoints.h) on the device: the GPU fills the noise table from them
+    size_t ckCount = 0; // ... how many dense values (every 1024th call) are there: the embedded ones, or more (ensure_checkpoints)
+    std::vector<uint64_t> ckHost; // ... and, once an image has reached beyond the embedded dense values, the host copy they were uploaded from
+  } noise{ deviceBytes };
+  // ---- limg_hip_options.collect_stats: the reference's 3 + 27 bit counters of the last encode ----
+  struct Stats
+  {
+    Bytes &n;
+    DevBuf counters{ n };
+    hipStream_t stream = nullptr;
+    int state = 0;           // 0 = none, 1 = on the device (8x8 path), 2 = in `host` (merged-block encoder)
+    bool accumulate = false; // a batched encode in several launch pairs: the pairs after the first add to the counters instead of restarting them
+    uint64_t host[30] = { 0 };
+    uint64_t pixels = 0;
+  } stats{ deviceBytes };
+  // ---- a dither chain shared between GPUs (limg_hip_encode.hip, limg_hip_multi.hip) ----
+  struct Chain
+  {
+    Bytes &n;
+    // multi-GPU (RCCL over xGMI): one communicator per context, created by limg_hip_comm_init
+    ncclComm_t comm = nullptr;
+    int rank = 0, world = 1;
+    DevBuf words{ n }; // [0] this rank's value, [1] its chain base, [8 ...] the all-gathered values
+    // limg_hip_encode3d_chain_device: phase 2 is only valid right after phase 1 of the same strip (the context holds the intermediate results)
+    const void *in = nullptr;
+    size_t x = 0, y = 0, before = 0;
+    const void *fac[3] = { nullptr, nullptr, nullptr }; // phase 1 left the pre-dither factor bytes in these planes
+    int alpha = 0, fast = 0;
+    uint32_t ef = 0;
+  } chain{ deviceBytes };
+  // ---- staging of the host-pointer entry points (limg_hip_host_entry.hip and every family's host forms) and of the ragged paths' host step ----
+  struct Host
+  {
+    Bytes &n;
+    DevBuf in{ n }, planes{ n };
+    Stream copyStream;   // ... the downloads of the finished bands (second host thread)
+    Stream stream;       // ... in row bands: the bands' kernels run here, their events tell the download thread when a band is done
+    Events events;
+    DevBuf words{ n }; // ... per band its dither-call total and its chain base (one chain through the bands)
+    HostBuf stage;       // pinned staging of the ragged paths' host step (shift words down; chain bases and noise up)
+    Event stageEvent;    // ... recorded behind the last asynchronous H2D copy that reads it: waited for before it is written, grown or freed again
+    bool stageBusy = false;
+    Events raggedEvents; // banded ragged encode: "the shift words of band b are down"
+  } host{ deviceBytes };
+  // ---- the merged-block encoder (limg_hip_blocked_api.hip; the stream packer reads what its last encode left here) ----
+  struct Blocked
+  {
+    Bytes &n;
+    DevBuf flags{ n }, bound{ n };
+    DevBuf order{ n }; // per batch the order its workgroups take the rectangles in
+    DevBuf match{ n }, regions{ n }, out{ n }, px{ n }, fac{ n }, noise{ n }, noiseBase{ n }; // similarity bits, region table / results, scratch (gathered pixels, factor bytes), noise
+    DevBuf calls{ n }; // per dither call: chain value, noise offset, pixel count (host walk -> k_noise_expand_calls)
+    HostBuf hFlags, hRec, hBits, hDesc, hOut, hNoise, hNoiseBase;
+    Stream searchStream; // the worker thread launches its fit + search batches on this stream
+    Stream storeStream;  // ... and the noise expansion + store kernels of a batch on a second one
+    Stream copyStream;   // copies of the similarity-bit bands, behind the kernels that produce them
+    Events workEvents;   // one per batch of the worker that is in flight on the GPU
+    Events bandEvents;
+    std::vector<limg_hip::HostRegion> lastRegions;
+    std::vector<uint32_t> regionPx; // ... and their pixel counts
+    size_t lastBlocks = 0;          // blocks of the last encode (what hBits / lastRegions describe)
+    double ms[6] = { 0, 0, 0, 0, 0, 0 };
+    double kernelMs[4] = { 0, 0, 0, 0 }; // the last encode, HIP events: pass 1 (k_fit_tpb) / the k_blocked_match launches / the k_blocked_fit_search launches /
+                                         // the noise-expansion + store launches (the last two summed over the worker's batches)
+    Events workTimers; // [4 i .. 4 i + 3]: begin / end of batch slot i's fit + search kernel, begin / end of its expansion + store kernels;
+                       // [4 kInFlight ..]: begin of pass 1, end of pass 1 = begin of the similarity kernels, their end
+    size_t scratchCap = 0; // plane stride of `fac` in the last encode (BlockedParams::scratchCap)
+    struct { size_t sizeX = 0, sizeY = 0; int channels = 0; uint32_t errorFactor = 0, flags = 0; bool valid = false; } last; // ... its shape and stream flags; valid: it succeeded,
+                           // so the buffers hold everything the stream packer reads (limg_hip_blocked_last_stream)
+  } blocked{ deviceBytes };
+  // ---- the stream packers and decoders (limg_hip_stream_api.hip, limg_hip_stream_window_api.hip) ----
+  struct Streams
+  {
+    Bytes &n;
+    DevBuf fac{ n }, tiles{ n }, units{ n }, status{ n }, buf{ n }; // stream packer: 3 factor planes, per-tile payload words; decode status word; host-entry staging
+    DevBuf table{ n }, sizes{ n }; // batched stream encode: one StreamImage per image of the list; the finished streams' sizes side by side (one download)
+    // version 2 stream of the merged-block encoder: per rectangle its first 64-pixel run, per tile of rectangles its totals; the decoder's block -> rectangle map and
+    // its per-call words
+    DevBuf bsUnits{ n }, bsTiles{ n }, bsMap{ n }, bsState{ n };
+    Events packTimers;      // begin / end of the last stream encode's scan + pack kernels ...
+    bool packTimed = false; // ... which limg_hip_blocked_kernel_timing still has to add to blocked.kernelMs[3]
+  } stream{ deviceBytes };
+  // ---- batched window decode (limg_hip_*decode_stream_windows*): a call's job table -- and, version 2, its map and per-job state words -- lives in one slot of a
+  // small ring, so that a call issued before the previous one has run does not disturb it.  host: pinned, the table as the call builds it; dev: its copy, then state
+  // and map; done: recorded behind the call's last kernel and waited for on the host before the slot is used again.
+  struct WindowSlot { HostBuf host; DevBuf dev; Event done; bool busy = false; WindowSlot(Bytes &n) : dev(n) {} };
+  static constexpr unsigned kWindowSlots = 4;
+  struct { WindowSlot slots[kWindowSlots]; unsigned next = 0; } window{ { deviceBytes, deviceBytes, deviceBytes, deviceBytes } };
+
+  // limg_hip_shutdown: an idle device and no communicator, then the members release themselves
+  ~limg_hip_context()
+  {
+    (void)hipSetDevice(device);
+    (void)hipDeviceSynchronize();
+    if (chain.comm && limg_hip::rccl().ok) (void)limg_hip::rccl().CommDestroy(chain.comm);
   }
 };
 
@@ -276,9 +263,9 @@ namespace limg_hip
   limg_hip_result encode_ragged(EncodeJob &e);
 
   // ---- the merged-block encoder's pipeline (limg_hip_blocked_api.hip) ----
-  // pInfo == nullptr is the COMPACT mode of the stream entry: no plane is stored.  When the call returns, every rectangle's descriptor (bRegions), record and shift word
-  // (bOut), pre-dither factor bytes (bFac, region-major, plane stride blockedScratchCap), noise bytes (bNoise) and noise offset (bNoiseBase) are complete in the
-  // context's buffers, which is what the stream packer reads.
+  // pInfo == nullptr is the COMPACT mode of the stream entry: no plane is stored.  When the call returns, every rectangle's descriptor (regions), record and shift word
+  // (out), pre-dither factor bytes (fac, region-major, plane stride scratchCap), noise bytes (noise) and noise offset (noiseBase) are complete in the
+  // context's `blocked` buffers, which is what the stream packer reads.
   limg_hip_result blocked_encode_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_blocked_encode3d_info *pInfo,
                                         uint32_t errorFactor, int fastBitCrushing, hipStream_t stream);
 }

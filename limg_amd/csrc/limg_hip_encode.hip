@@ -33,11 +33,11 @@ namespace limg_hip
     const EncodeParams &p = e.p;
     if (!e.wantStats || e.x.inner) return limg_hip_success;
     limg_hip_result rs;
-    if ((rs = c->stats.ensure(30 * 8)) != limg_hip_success) return rs;
-    if (!c->statsAccumulate) HIP_TRY(hipMemsetAsync(c->stats.p, 0, 30 * 8, e.stream));
-    launch_shift_stats(p.shifts, p.blocksX, p.blocksY, p.blocksY * p.batchCount, p.sizeX, p.sizeY, (unsigned long long *)c->stats.p, e.stream);
-    c->statsStream = e.stream; c->statsState = 1;
-    c->statsPixels = (c->statsAccumulate ? c->statsPixels : 0) + (uint64_t)e.sizeX * e.sizeY * e.x.batchCount;
+    if ((rs = c->stats.counters.ensure(30 * 8)) != limg_hip_success) return rs;
+    if (!c->stats.accumulate) HIP_TRY(hipMemsetAsync(c->stats.counters.p, 0, 30 * 8, e.stream));
+    launch_shift_stats(p.shifts, p.blocksX, p.blocksY, p.blocksY * p.batchCount, p.sizeX, p.sizeY, (unsigned long long *)c->stats.counters.p, e.stream);
+    c->stats.stream = e.stream; c->stats.state = 1;
+    c->stats.pixels = (c->stats.accumulate ? c->stats.pixels : 0) + (uint64_t)e.sizeX * e.sizeY * e.x.batchCount;
     return limg_hip_success;
   }
 }
@@ -57,7 +57,7 @@ namespace
   // property of the edge -- with it the kernel needs no record of the shifts its cached terms were built for and no three compares per trial.
   limg_hip_result ensure_accurate_table(limg_hip_context *c)
   {
-    if (c->accTable.p) return limg_hip_success;
+    if (c->enc.accTable.p) return limg_hip_success;
     static const uint32_t compact[LIMG_SEARCH_ACC_STATES][2] = LIMG_SEARCH_ACC_TABLE_INIT;
     static const uint32_t mul[9] = { 1, 2, 4, 8, 17, 36, 85, 255, 256 }; // (1 << s) + decode_bias(s), src/limg_bit_crush_simd.h:611-619
     std::vector<uint32_t> wide((size_t)LIMG_SEARCH_ACC_STATES * 8);
@@ -85,21 +85,9 @@ namespace
         e[k] |= mask << 24;
       }
     }
-    limg_hip_result r = c->accTable.ensure(wide.size() * 4);
+    limg_hip_result r = c->enc.accTable.ensure(wide.size() * 4);
     if (r != limg_hip_success) return r;
-    if (hipMemcpy(c->accTable.p, wide.data(), wide.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { c->accTable.release(); return limg_hip_error_Generic; }
-    return limg_hip_success;
-  }
-
-  limg_hip_result ensure_pipe_events(limg_hip_context *c, size_t n)
-  {
-    if (!c->fitStream) HIP_TRY(hipStreamCreateWithFlags(&c->fitStream, hipStreamNonBlocking));
-    while (c->pipeEvents.size() < n)
-    {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      c->pipeEvents.push_back(e);
-    }
+    if (hipMemcpy(c->enc.accTable.p, wide.data(), wide.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { c->enc.accTable.release(); return limg_hip_error_Generic; }
     return limg_hip_success;
   }
 
@@ -134,7 +122,7 @@ namespace
     {
       limg_hip_result ra = ensure_accurate_table(c);
       if (ra != limg_hip_success) return ra;
-      p.accTable = (const uint32_t *)c->accTable.p;
+      p.accTable = (const uint32_t *)c->enc.accTable.p;
     }
     const bool forced = c->opt.forced_shift[0] >= 0 && c->opt.forced_shift[0] <= 8 && c->opt.forced_shift[1] >= 0 && c->opt.forced_shift[1] <= 8 &&
                         c->opt.forced_shift[2] >= 0 && c->opt.forced_shift[2] <= 8;
@@ -153,14 +141,14 @@ namespace
     const size_t blockOff = x.scratchRow0 * p.blocksX, stripOff = x.scratchRow0 * p.stripsX;
     limg_hip_result r;
     if (compact && compact->pRecords) p.records = compact->pRecords + blockOff;
-    else { if ((r = c->records.ensure(scratchBlocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r; p.records = (limg_hip_block_record *)c->records.p + blockOff; }
+    else { if ((r = c->enc.records.ensure(scratchBlocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r; p.records = (limg_hip_block_record *)c->enc.records.p + blockOff; }
     if (compact && compact->pShifts) p.shifts = compact->pShifts + blockOff;
-    else { if ((r = c->shifts.ensure(scratchBlocks * 4)) != limg_hip_success) return r; p.shifts = (uint32_t *)c->shifts.p + blockOff; }
-    if ((r = c->invN.ensure(scratchBlocks * 16)) != limg_hip_success) return r;
-    p.invN = (float *)c->invN.p + blockOff * 4;
-    if ((r = c->stripCalls.ensure(scratchStrips * 4)) != limg_hip_success) return r;
-    if ((r = c->stripBase.ensure(scratchStrips * 4)) != limg_hip_success) return r;
-    p.stripCalls = (uint32_t *)c->stripCalls.p + stripOff; p.stripBase = (uint32_t *)c->stripBase.p + stripOff;
+    else { if ((r = c->enc.shifts.ensure(scratchBlocks * 4)) != limg_hip_success) return r; p.shifts = (uint32_t *)c->enc.shifts.p + blockOff; }
+    if ((r = c->enc.invN.ensure(scratchBlocks * 16)) != limg_hip_success) return r;
+    p.invN = (float *)c->enc.invN.p + blockOff * 4;
+    if ((r = c->enc.stripCalls.ensure(scratchStrips * 4)) != limg_hip_success) return r;
+    if ((r = c->enc.stripBase.ensure(scratchStrips * 4)) != limg_hip_success) return r;
+    p.stripCalls = (uint32_t *)c->enc.stripCalls.p + stripOff; p.stripBase = (uint32_t *)c->enc.stripBase.p + stripOff;
     const bool fullPlanes = e.fullPlanes;
     p.storePlanes = dInfo != nullptr;
     p.fullPlanes = fullPlanes;
@@ -195,9 +183,9 @@ namespace
         p.vecFactors8 = p.vecFactors8 && ((((uintptr_t)batch[i].info.pFactorsA) | ((uintptr_t)batch[i].info.pFactorsB) | ((uintptr_t)batch[i].info.pFactorsC)) & 7u) == 0;
         p.vecFactors = p.vecFactors && ((((uintptr_t)batch[i].info.pFactorsA) | ((uintptr_t)batch[i].info.pFactorsB) | ((uintptr_t)batch[i].info.pFactorsC)) & 15u) == 0;
       }
-      if ((r = c->batchTable.ensure(batchCount * sizeof(ImageIO))) != limg_hip_success) return r;
-      launch_set_batch_table((ImageIO *)c->batchTable.p, batch, batchCount, e.stream); // through kernel arguments: stream-ordered, and the host array may die right away
-      p.batch = (const ImageIO *)c->batchTable.p;
+      if ((r = c->enc.batchTable.ensure(batchCount * sizeof(ImageIO))) != limg_hip_success) return r;
+      launch_set_batch_table((ImageIO *)c->enc.batchTable.p, batch, batchCount, e.stream); // through kernel arguments: stream-ordered, and the host array may die right away
+      p.batch = (const ImageIO *)c->enc.batchTable.p;
     }
 
     if (dInfo && !e.ragged)
@@ -206,8 +194,8 @@ namespace
       uint32_t maxRows = p.blocksY;
       if (pt.chainCount > 1 && (pt.chainCount - 1) * pt.chainRows < p.blocksY) maxRows = p.blocksY - (pt.chainCount - 1) * pt.chainRows; // the last chain takes the remainder, never fewer rows than the others
       if ((r = grow_noise_table(c, ((size_t)maxRows * p.blocksX + x.chainBlocksBefore) * 3, e.stream)) != limg_hip_success) return r;
-      p.noise = (const uint8_t *)c->noise.p;
-      p.noiseLast = (uint32_t)(c->noiseCount - 1);
+      p.noise = (const uint8_t *)c->noise.table.p;
+      p.noiseLast = (uint32_t)(c->noise.count - 1);
     }
 
     const int chainPhase = x.chainPhase;
@@ -216,7 +204,7 @@ namespace
     p.chainBase = chainPhase == 2 ? x.dChainBase : nullptr;
     // The float stage as its own launch, one lane per block (limg_hip_fit_tpb.hip), wherever every block is a whole 8x8: the E step then starts from the records.
     p.prefit = (!e.ragged && c->opt.legacy_float_stage == 0 && (((uintptr_t)p.records) & 15u) == 0) ? 1 : 0; // k_fit_tpb stores records 16 bytes at a time
-    e.fused = dInfo != nullptr && !e.ragged && (!c->forceSplit || batchCount > 1) && chainPhase == 0;
+    e.fused = dInfo != nullptr && !e.ragged && (c->opt.force_split_kernels == 0 || batchCount > 1) && chainPhase == 0;
     e.wantStats = c->opt.collect_stats != 0 && dInfo != nullptr && chainPhase == 0;
     return limg_hip_success;
   }
@@ -228,25 +216,25 @@ namespace
     limg_hip_context *const c = e.c;
     EncodeParams &p = e.p;
     limg_hip_result r;
-    if ((r = c->lookback.ensure(16 * (e.x.batchCount + 1) + e.strips * 8)) != limg_hip_success) return r; // (room for one ticket per sub-batch)
-    p.ticket = (uint32_t *)c->lookback.p;
-    p.desc = (unsigned long long *)((uint8_t *)c->lookback.p + 16);
+    if ((r = c->enc.lookback.ensure(16 * (e.x.batchCount + 1) + e.strips * 8)) != limg_hip_success) return r; // (room for one ticket per sub-batch)
+    p.ticket = (uint32_t *)c->enc.lookback.p;
+    p.desc = (unsigned long long *)((uint8_t *)c->enc.lookback.p + 16);
     p.zeroLookback = p.prefit ? 1 : 0;
-    if (!p.prefit) HIP_TRY(hipMemsetAsync(c->lookback.p, 0, 16 + e.strips * 8, e.stream));
-    if (!c->devStatus.p)
+    if (!p.prefit) HIP_TRY(hipMemsetAsync(c->enc.lookback.p, 0, 16 + e.strips * 8, e.stream));
+    if (!c->enc.devStatus.p)
     {
-      if ((r = c->devStatus.ensure(16)) != limg_hip_success) return r;
-      HIP_TRY(hipMemsetAsync(c->devStatus.p, 0, 16, e.stream));
+      if ((r = c->enc.devStatus.ensure(16)) != limg_hip_success) return r;
+      HIP_TRY(hipMemsetAsync(c->enc.devStatus.p, 0, 16, e.stream));
     }
-    p.timeout = (uint32_t *)c->devStatus.p;
+    p.timeout = (uint32_t *)c->enc.devStatus.p;
 #ifdef LIMG_HIP_TEST_HOOKS
     p.lookbackSpins = c->topt.lookback_spins > 0 ? (uint32_t)c->topt.lookback_spins : (1u << 22);
     p.testSkipStrip = c->topt.skip_publish_strip > 0 ? (uint32_t)c->topt.skip_publish_strip - 1u : ~0u;
     p.testBaseErrStrip = c->topt.base_error_strip > 0 ? (uint32_t)c->topt.base_error_strip - 1u : ~0u;
 #endif
     p.compactOut = compact != nullptr || e.wantStats; // the statistics are reduced from the raster-order shift words
-    if ((r = c->park.ensure((size_t)(c->persistentWorkgroups / 5 * 6) * 2 * 8192)) != limg_hip_success) return r; // 6 workgroups per CU: the kernel's launch bound
-    p.park = (uint8_t *)c->park.p;
+    if ((r = c->enc.park.ensure((size_t)(c->enc.persistentWorkgroups / 5 * 6) * 2 * 8192)) != limg_hip_success) return r; // 6 workgroups per CU: the kernel's launch bound
+    p.park = (uint8_t *)c->enc.park.p;
     return limg_hip_success;
   }
 
@@ -287,7 +275,9 @@ namespace
     const size_t firstSub = ((knobs >> 8) & 255u) && ((knobs >> 8) & 255u) < subImages ? (size_t)((knobs >> 8) & 255u) : subImages;
     const size_t nSub = 1 + (batchCount - firstSub + subImages - 1) / subImages;
     limg_hip_result r;
-    if ((r = ensure_pipe_events(c, 2 * nSub + 1)) != limg_hip_success) return r;
+    hipStream_t fs;
+    if ((r = c->enc.fitStream.get(fs)) != limg_hip_success) return r;
+    if ((r = c->enc.pipeEvents.ensure(2 * nSub + 1, hipEventDisableTiming)) != limg_hip_success) return r;
     const size_t imgBlocks = (size_t)p.blocksX * p.blocksY, imgStrips = (size_t)p.imageStrips;
     auto sub = [&](size_t k) -> EncodeParams
     {
@@ -297,13 +287,12 @@ namespace
       q.io = e.x.batch[i0]; // (what the kernels read when a sub-batch is a single image)
       q.records = p.records + i0 * imgBlocks; q.shifts = p.shifts + i0 * imgBlocks; q.invN = p.invN + i0 * imgBlocks * 4;
       if (p.stripWords) q.stripWords = p.stripWords + i0 * imgStrips; // (a sub-batch numbers its strips from 0: its payload words land at the list's offsets, where the packer reads one list)
-      uint8_t *lb = (uint8_t *)c->lookback.p + k * 16 + i0 * imgStrips * 8; // sub-batch k: its ticket, then the descriptors of its strips
+      uint8_t *lb = (uint8_t *)c->enc.lookback.p + k * 16 + i0 * imgStrips * 8; // sub-batch k: its ticket, then the descriptors of its strips
       q.ticket = (uint32_t *)lb; q.desc = (unsigned long long *)(lb + 16);
       q.fitPrio = k == 0 ? 0 : fitPrio;
       return q;
     };
-    hipStream_t fs = c->fitStream;
-    hipEvent_t *ev = c->pipeEvents.data(); // [0]: fork; [1 + 2 k]: k_fit_tpb of sub-batch k done; [2 + 2 k]: the persistent kernel of sub-batch k is next on `stream`
+    hipEvent_t *ev = c->enc.pipeEvents.data(); // [0]: fork; [1 + 2 k]: k_fit_tpb of sub-batch k done; [2 + 2 k]: the persistent kernel of sub-batch k is next on `stream`
     e.mark_if(1);
     HIP_TRY(hipEventRecord(ev[0], stream)); // everything the caller's stream holds so far (inputs, the image table, earlier encodes that use the scratch)
     HIP_TRY(hipStreamWaitEvent(fs, ev[0], 0));
@@ -320,7 +309,7 @@ namespace
         launch_fit_tpb(sub(k + 1), e.channels, fs);
         HIP_TRY(hipEventRecord(ev[3 + 2 * k], fs));
       }
-      launch_encode_persistent(sub(k), e.channels, c->persistentWorkgroups / 5 * (k + 1 < nSub ? wgOverlap : wg_per_cu(c, 6)), stream);
+      launch_encode_persistent(sub(k), e.channels, c->enc.persistentWorkgroups / 5 * (k + 1 < nSub ? wgOverlap : wg_per_cu(c, 6)), stream);
     }
     e.mark_if(1); e.mark_if(2);
     HIP_TRY(hipGetLastError());
@@ -337,7 +326,7 @@ namespace
       launch_fit_tpb(p, e.channels, e.stream);
     }
     e.mark_if(1);
-    launch_encode_persistent(p, e.channels, e.c->persistentWorkgroups / 5 * wg_per_cu(e.c, p.prefit ? 6 : 5), e.stream);
+    launch_encode_persistent(p, e.channels, e.c->enc.persistentWorkgroups / 5 * wg_per_cu(e.c, p.prefit ? 6 : 5), e.stream);
     e.mark_if(1);
     if (p.prefit) e.mark_if(2); else { e.mark_if(1); e.mark_if(2); } // 4 events per encode: with the float stage as its own launch the intervals are {k_fit_tpb, k_encode_persistent, -}
     HIP_TRY(hipGetLastError());
@@ -404,7 +393,7 @@ namespace limg_hip
     const int chainPhase = x.chainPhase;
     const size_t batchCount = x.batchCount;
     if (!c || !dIn) return limg_hip_error_ArgumentNull;
-    if (chainPhase == 0 && !x.inner) c->chainIn = nullptr; // the context's per-block scratch is about to be reused
+    if (chainPhase == 0 && !x.inner) c->chain.in = nullptr; // the context's per-block scratch is about to be reused
     if (sizeX == 0 || sizeY == 0 || sizeX > 0x7FFFFFF8ull || sizeY > 0x7FFFFFF8ull) return limg_hip_error_InvalidParameter;
     bool fullPlanes = true;
     if (dInfo)
@@ -422,7 +411,7 @@ namespace limg_hip
     const bool ragged = (sizeX % kBlock) != 0 || (sizeY % kBlock) != 0;
     // An image whose WIDTH is whole blocks but whose last block row is partial (BASELINE config 1's shape class: 1024 x 618): every block row but the last
     // is on the fast path (its dither chain is the seed's orbit, the noise table applies); only the last row needs the host to walk its chain.
-    if (ragged && sizeX % kBlock == 0 && sizeY > (size_t)kBlock && dInfo && chainPhase == 0 && batchCount == 1 && !x.inner && !x.fitOnly && !c->forceSplit &&
+    if (ragged && sizeX % kBlock == 0 && sizeY > (size_t)kBlock && dInfo && chainPhase == 0 && batchCount == 1 && !x.inner && !x.fitOnly && c->opt.force_split_kernels == 0 &&
         c->opt.legacy_float_stage == 0 && c->opt.dither_pcg == 0 && TOPT(c, whole_image_ragged) == 0)
     {
       if (((sizeX / kBlock) * ((sizeY + kBlock - 1) / kBlock)) * 3 <= checkpoint_reach())
@@ -435,7 +424,7 @@ namespace limg_hip
     e.fullPlanes = fullPlanes;
     limg_hip_result r;
     if ((r = encode_params(e, dIn, compact, errorFactor, poolThreads, fast)) != limg_hip_success) return r;
-    if (chainPhase == 0 && !x.inner && !c->statsAccumulate) c->statsState = 0;
+    if (chainPhase == 0 && !x.inner && !c->stats.accumulate) c->stats.state = 0;
     // a list in compact mode only as the batched stream encode hands it over: raw-escaped factor bytes, the strips' payload words, records and shift words all in
     // raster arrays that run image after image (what its scan and packer read)
     const bool compactList = !fullPlanes && x.streamRaw && x.stripWords && compact && compact->pRecords && compact->pShifts;
@@ -463,8 +452,8 @@ namespace
   {
     const size_t topY = (sizeY / kBlock) * kBlock, blocksX = sizeX / kBlock, blocksY = topY / kBlock + 1, stripsX = (blocksX + kStripBlocks - 1) / kStripBlocks;
     const Partition pt = partition(sizeY, poolThreads);
-    c->chainIn = nullptr;
-    c->statsState = 0;
+    c->chain.in = nullptr;
+    c->stats.state = 0;
     limg_hip_result r;
     EncodeExtra xt;
     xt.streamRaw = x.streamRaw; xt.inner = true; xt.marks = 1; xt.part = &pt; xt.scratchRows = blocksY;
@@ -483,16 +472,16 @@ namespace
     const Partition one = { 1, 0 };
     xb.part = &one;
     const bool sameChain = chain_of_row(pt, (uint32_t)blocksY - 1) == chain_of_row(pt, (uint32_t)blocksY - 2);
-    if (sameChain) xb.dPrevDesc = (const unsigned long long *)((const uint8_t *)c->lookback.p + 16) + ((blocksY - 1) * stripsX - 1);
+    if (sameChain) xb.dPrevDesc = (const unsigned long long *)((const uint8_t *)c->enc.lookback.p + 16) + ((blocksY - 1) * stripsX - 1);
     if ((r = encode_device(c, dIn + topY * sizeX, sizeX, sizeY - topY, hasAlpha, &low, compact, errorFactor, 0, fast, stream, xb)) != limg_hip_success) return r;
     mark(c, stream);
     if (c->opt.collect_stats != 0)
     {
-      if ((r = c->stats.ensure(30 * 8)) != limg_hip_success) return r;
-      HIP_TRY(hipMemsetAsync(c->stats.p, 0, 30 * 8, stream));
-      const uint32_t *shifts = (compact && compact->pShifts) ? compact->pShifts : (const uint32_t *)c->shifts.p;
-      launch_shift_stats(shifts, (uint32_t)blocksX, (uint32_t)blocksY, (uint32_t)blocksY, (uint32_t)sizeX, (uint32_t)sizeY, (unsigned long long *)c->stats.p, stream);
-      c->statsStream = stream; c->statsState = 1; c->statsPixels = (uint64_t)sizeX * sizeY;
+      if ((r = c->stats.counters.ensure(30 * 8)) != limg_hip_success) return r;
+      HIP_TRY(hipMemsetAsync(c->stats.counters.p, 0, 30 * 8, stream));
+      const uint32_t *shifts = (compact && compact->pShifts) ? compact->pShifts : (const uint32_t *)c->enc.shifts.p;
+      launch_shift_stats(shifts, (uint32_t)blocksX, (uint32_t)blocksY, (uint32_t)blocksY, (uint32_t)sizeX, (uint32_t)sizeY, (unsigned long long *)c->stats.counters.p, stream);
+      c->stats.stream = stream; c->stats.state = 1; c->stats.pixels = (uint64_t)sizeX * sizeY;
     }
     return limg_hip_success;
   }
@@ -544,13 +533,13 @@ extern "C"
     if (chunk * strips > 0x7FFFFFFFull) chunk = 0x7FFFFFFFull / strips; // strip ids are 32 bits
     if (chunk < 1) chunk = 1;
     if (TOPT(c, batch_chunk) > 0) chunk = (size_t)TOPT(c, batch_chunk);
-    const bool oneByOne = count == 1 || ragged || !full || c->opt.legacy_float_stage != 0 || c->forceSplit;
+    const bool oneByOne = count == 1 || ragged || !full || c->opt.legacy_float_stage != 0 || c->opt.force_split_kernels != 0;
     std::vector<ImageIO> table;
     limg_hip_result r = limg_hip_success;
     for (size_t i0 = 0; i0 < count && r == limg_hip_success;)
     {
       const size_t n = oneByOne ? 1 : (count - i0 < chunk ? count - i0 : chunk);
-      c->statsAccumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, however many launch pairs it took
+      c->stats.accumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, however many launch pairs it took
       if (n == 1) r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, &pInfos[i0], nullptr, errorFactor, poolThreads, fastBitCrushing, (hipStream_t)stream);
       else
       {
@@ -562,7 +551,7 @@ extern "C"
       }
       i0 += n;
     }
-    c->statsAccumulate = false;
+    c->stats.accumulate = false;
     return r;
   }
 
@@ -574,19 +563,19 @@ extern "C"
     if (!c || (phase == 1 && !pCallsDevice) || (phase == 2 && !pChainBaseDevice) || !pInfo) return limg_hip_error_ArgumentNull;
     // phase 2 continues the phase 1 the context holds: same strip, same planes (phase 1 left the pre-dither factor bytes in them), same parameters, and a noise
     // table that was sized for the same chain position
-    if (phase == 2 && (c->chainIn != pIn || c->chainX != sizeX || c->chainY != sizeY || c->chainFac[0] != pInfo->pFactorsA || c->chainFac[1] != pInfo->pFactorsB ||
-                       c->chainFac[2] != pInfo->pFactorsC || c->chainAlpha != (hasAlpha != 0) || c->chainEf != errorFactor || c->chainFast != (fastBitCrushing != 0) ||
-                       c->chainBefore != blocksBefore))
+    if (phase == 2 && (c->chain.in != pIn || c->chain.x != sizeX || c->chain.y != sizeY || c->chain.fac[0] != pInfo->pFactorsA || c->chain.fac[1] != pInfo->pFactorsB ||
+                       c->chain.fac[2] != pInfo->pFactorsC || c->chain.alpha != (hasAlpha != 0) || c->chain.ef != errorFactor || c->chain.fast != (fastBitCrushing != 0) ||
+                       c->chain.before != blocksBefore))
       return limg_hip_error_InvalidParameter; // no matching phase 1 pending
-    c->chainIn = nullptr;
+    c->chain.in = nullptr;
     EncodeExtra x;
     x.chainPhase = phase; x.dChainCalls = (unsigned long long *)pCallsDevice; x.dChainBase = (const unsigned long long *)pChainBaseDevice; x.chainBlocksBefore = blocksBefore;
     const limg_hip_result r = encode_device(c, pIn, sizeX, sizeY, hasAlpha, pInfo, nullptr, errorFactor, 0, fastBitCrushing, (hipStream_t)stream, x);
     if (r == limg_hip_success && phase == 1)
     {
-      c->chainIn = pIn; c->chainX = sizeX; c->chainY = sizeY; c->chainBefore = blocksBefore;
-      c->chainFac[0] = pInfo->pFactorsA; c->chainFac[1] = pInfo->pFactorsB; c->chainFac[2] = pInfo->pFactorsC;
-      c->chainAlpha = hasAlpha != 0; c->chainEf = errorFactor; c->chainFast = fastBitCrushing != 0;
+      c->chain.in = pIn; c->chain.x = sizeX; c->chain.y = sizeY; c->chain.before = blocksBefore;
+      c->chain.fac[0] = pInfo->pFactorsA; c->chain.fac[1] = pInfo->pFactorsB; c->chain.fac[2] = pInfo->pFactorsC;
+      c->chain.alpha = hasAlpha != 0; c->chain.ef = errorFactor; c->chain.fast = fastBitCrushing != 0;
     }
     return r;
   }

@@ -9,7 +9,7 @@ using namespace limg_hip;
 
 namespace
 {
-  // pinned staging of the ragged paths' host step (c->hStage): shift words | previous descriptor | strip bases | per call: chain value, pixel count (worst case:
+  // pinned staging of the ragged paths' host step (c->host.stage): shift words | previous descriptor | strip bases | per call: chain value, pixel count (worst case:
   // 3 calls per block)
   struct RaggedStage
   {
@@ -39,29 +39,30 @@ namespace
   limg_hip_result ensure_stage(EncodeJob &e)
   {
     limg_hip_context *const c = e.c;
-    if (c->hStageBusy) { HIP_TRY(hipEventSynchronize(c->hStageEvent)); c->hStageBusy = false; }
-    return c->hStage.ensure(RaggedStage(e.blocks, e.strips).bytes);
+    if (c->host.stageBusy) { HIP_TRY(hipEventSynchronize(c->host.stageEvent)); c->host.stageBusy = false; }
+    return c->host.stage.ensure(RaggedStage(e.blocks, e.strips).bytes);
   }
 
   // the staging buffer is the context's: the event marks the point where this encode's copies have read it (waited for by the next encode that uses it, on
-  // whatever stream, and by limg_hip_shutdown)
+  // whatever stream; the context goes only once the device is idle)
   limg_hip_result release_stage(EncodeJob &e)
   {
     limg_hip_context *const c = e.c;
-    if (!c->hStageEvent) HIP_TRY(hipEventCreateWithFlags(&c->hStageEvent, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->hStageEvent, e.stream));
-    c->hStageBusy = true;
+    const limg_hip_result r = c->host.stageEvent.ensure(hipEventDisableTiming);
+    if (r != limg_hip_success) return r;
+    HIP_TRY(hipEventRecord(c->host.stageEvent, e.stream));
+    c->host.stageBusy = true;
     return limg_hip_success;
   }
 
-  // device side: per dither call 64 noise bytes + the 9 bytes they are expanded from (c->noiseDyn, c->noiseStates); the F step reads the noise from there
+  // device side: per dither call 64 noise bytes + the 9 bytes they are expanded from (c->noise.dyn, c->noise.states); the F step reads the noise from there
   limg_hip_result size_noise_calls(EncodeJob &e, size_t calls)
   {
     limg_hip_context *const c = e.c;
     limg_hip_result r;
-    if ((r = c->noiseDyn.ensure((calls + 1) * 64)) != limg_hip_success) return r;
-    if ((r = c->noiseStates.ensure(calls * 9 + 16)) != limg_hip_success) return r;
-    e.p.noise = (const uint8_t *)c->noiseDyn.p;
+    if ((r = c->noise.dyn.ensure((calls + 1) * 64)) != limg_hip_success) return r;
+    if ((r = c->noise.states.ensure(calls * 9 + 16)) != limg_hip_success) return r;
+    e.p.noise = (const uint8_t *)c->noise.dyn.p;
     e.p.noiseLast = (uint32_t)calls; // (entry `calls` exists: the clamp of a call index cannot land outside the buffer)
     return limg_hip_success;
   }
@@ -71,11 +72,11 @@ namespace
   {
     limg_hip_context *const c = e.c;
     if (!n) return limg_hip_success;
-    unsigned long long *dStates = (unsigned long long *)c->noiseStates.p;
-    uint8_t *dPixels = (uint8_t *)c->noiseStates.p + calls * 8;
+    unsigned long long *dStates = (unsigned long long *)c->noise.states.p;
+    uint8_t *dPixels = (uint8_t *)c->noise.states.p + calls * 8;
     HIP_TRY(hipMemcpyAsync(dStates + call0, h.states + call0, n * 8, hipMemcpyHostToDevice, e.stream));
     HIP_TRY(hipMemcpyAsync(dPixels + call0, h.pixels + call0, n, hipMemcpyHostToDevice, e.stream));
-    launch_noise_expand((uint8_t *)c->noiseDyn.p + call0 * 64, dStates + call0, dPixels + call0, n, c->opt.dither_pcg != 0, e.stream);
+    launch_noise_expand((uint8_t *)c->noise.dyn.p + call0 * 64, dStates + call0, dPixels + call0, n, c->opt.dither_pcg != 0, e.stream);
     return limg_hip_success;
   }
 
@@ -126,20 +127,15 @@ namespace
     limg_hip_result r;
     e.mark_if(1); // split path intervals: {k_fit_tpb + k_fit_search, scan, k_dither_store}
     if ((r = ensure_stage(e)) != limg_hip_success) return r;
-    while (c->raggedEvents.size() < nBands)
-    {
-      hipEvent_t ev;
-      HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      c->raggedEvents.push_back(ev);
-    }
-    const RaggedStage h(e.blocks, e.strips, c->hStage.p);
+    if ((r = c->host.raggedEvents.ensure(nBands, hipEventDisableTiming)) != limg_hip_success) return r;
+    const RaggedStage h(e.blocks, e.strips, c->host.stage.p);
     for (uint32_t b = 0; b < nBands; b++)
     {
       const EncodeParams q = band_params(e, bandRows, b);
       launch_fit_search(q, e.channels, stream);
       const size_t off = (size_t)b * bandRows * p.blocksX;
       HIP_TRY(hipMemcpyAsync(h.shifts + off, p.shifts + off, (size_t)q.blocksY * p.blocksX * 4, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipEventRecord(c->raggedEvents[b], stream));
+      HIP_TRY(hipEventRecord(c->host.raggedEvents[b], stream));
     }
     e.mark_if(1);
     // sized for the worst case up front (3 calls per block): a band's calls go up while later bands are still being walked
@@ -151,7 +147,7 @@ namespace
     {
       EncodeParams q = band_params(e, bandRows, b);
       const uint32_t r0 = b * bandRows, r1 = r0 + q.blocksY;
-      HIP_TRY(hipEventSynchronize(c->raggedEvents[b])); // this band's shift words are down
+      HIP_TRY(hipEventSynchronize(c->host.raggedEvents[b])); // this band's shift words are down
       const size_t call0 = call;
       chain_walk_rows(hv, call, r0, r1, p.blocksX, p.stripsX, e.sizeX, e.sizeY, 1, 0, h.shifts, h.base, h.states, h.pixels, h.maxCalls, pcg);
       if ((r = upload_calls(e, h, h.maxCalls, call0, call - call0)) != limg_hip_success) return r;
@@ -191,7 +187,7 @@ namespace limg_hip
     }
     limg_hip_result r;
     if ((r = ensure_stage(e)) != limg_hip_success) return r;
-    const RaggedStage h(e.blocks, e.strips, c->hStage.p);
+    const RaggedStage h(e.blocks, e.strips, c->host.stage.p);
     const size_t blocks = e.blocks, maxCalls = h.maxCalls;
     const bool pcg = c->opt.dither_pcg != 0;
     HIP_TRY(hipMemcpyAsync(h.shifts, p.shifts, blocks * 4, hipMemcpyDeviceToHost, stream));

@@ -30,16 +30,10 @@ namespace
   // the banded paths' two streams (kernels, copies) and one event per band
   limg_hip_result band_streams(limg_hip_context *c, uint32_t nb)
   {
-    if (!c->hostStream) HIP_TRY(hipStreamCreateWithFlags(&c->hostStream, hipStreamNonBlocking));
-    if (!c->hostCopyStream) HIP_TRY(hipStreamCreateWithFlags(&c->hostCopyStream, hipStreamNonBlocking));
-    while (c->hostEvents.size() < nb)
-    {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      try { c->hostEvents.push_back(e); }
-      catch (...) { (void)hipEventDestroy(e); return limg_hip_error_MemoryAllocationFailure; } // (no exception may cross the extern "C" boundary)
-    }
-    return limg_hip_success;
+    hipStream_t s;
+    limg_hip_result r;
+    if ((r = c->host.stream.get(s)) != limg_hip_success || (r = c->host.copyStream.get(s)) != limg_hip_success) return r;
+    return c->host.events.ensure(nb, hipEventDisableTiming);
   }
 
   // The host-pointer entry in ROW BANDS: what every relinked caller of limg_encode3d_test hits moves 4 B/px up and 35 B/px down over PCIe, and
@@ -72,14 +66,14 @@ namespace
     else nb = even_bands(sizeY, bands);
     limg_hip_result r;
     if ((r = band_streams(c, nb)) != limg_hip_success) return r;
-    if ((r = c->hostWords.ensure((2 * 64 + 2) * 8)) != limg_hip_success) return r;
-    if (!c->devStatus.p)
+    if ((r = c->host.words.ensure((2 * 64 + 2) * 8)) != limg_hip_success) return r;
+    if (!c->enc.devStatus.p)
     {
-      if ((r = c->devStatus.ensure(16)) != limg_hip_success) return r;
-      HIP_TRY(hipMemset(c->devStatus.p, 0, 16));
+      if ((r = c->enc.devStatus.ensure(16)) != limg_hip_success) return r;
+      HIP_TRY(hipMemset(c->enc.devStatus.p, 0, 16));
     }
-    unsigned long long *dCalls = (unsigned long long *)c->hostWords.p, *dBase = dCalls + 64;
-    hipStream_t s = c->hostStream;
+    unsigned long long *dCalls = (unsigned long long *)c->host.words.p, *dBase = dCalls + 64;
+    hipStream_t s = c->host.stream;
     HIP_TRY(hipMemsetAsync(dCalls, 0, 2 * 64 * 8, s));
 
     // the downloads: a second host thread, band after band, as their events fire
@@ -96,16 +90,16 @@ namespace
           cv.wait(lk, [&] { return ready.load() > b || failed.load() != 0; });
         }
         if (failed.load() != 0) return;
-        if (hipEventSynchronize(c->hostEvents[b]) != hipSuccess) { failed = 1; return; }
+        if (hipEventSynchronize(c->host.events[b]) != hipSuccess) { failed = 1; return; }
         const size_t o = bands[b].y0 * sizeX, n = (bands[b].y1 - bands[b].y0) * sizeX;
         for (int i = 0; i < 11; i++)
         {
           const size_t es = i < 8 ? 4 : 1;
           // (on a stream of its own: blocking hipMemcpy calls of two threads share the null stream and run one after the other -- measured: every upload waited
           // for the download in front of it)
-          if (hipMemcpyAsync((uint8_t *)hp[i] + o * es, (const uint8_t *)dp[i] + o * es, n * es, hipMemcpyDeviceToHost, c->hostCopyStream) != hipSuccess) { failed = 1; return; }
+          if (hipMemcpyAsync((uint8_t *)hp[i] + o * es, (const uint8_t *)dp[i] + o * es, n * es, hipMemcpyDeviceToHost, c->host.copyStream) != hipSuccess) { failed = 1; return; }
         }
-        if (hipStreamSynchronize(c->hostCopyStream) != hipSuccess) { failed = 1; return; }
+        if (hipStreamSynchronize(c->host.copyStream) != hipSuccess) { failed = 1; return; }
       }
     };
     std::thread *copier = nullptr;
@@ -116,7 +110,7 @@ namespace
     for (uint32_t b = 0; b < nb && result == limg_hip_success && failed.load() == 0; b++)
     {
       const size_t y0 = bands[b].y0, rows = bands[b].y1 - y0, o = y0 * sizeX;
-      const uint32_t *dIn = (const uint32_t *)c->in.p + o;
+      const uint32_t *dIn = (const uint32_t *)c->host.in.p + o;
       if (hipMemcpyAsync((void *)dIn, pIn + o, rows * sizeX * 4, hipMemcpyHostToDevice, s) != hipSuccess) { result = limg_hip_error_Generic; break; }
       limg_hip_encode3d_info d;
       void **q = reinterpret_cast<void **>(&d);
@@ -128,11 +122,11 @@ namespace
         result = limg_hip_encode3d_chain_device(c, dIn, sizeX, rows, hasAlpha, &d, errorFactor, fastBitCrushing, 1, (uint64_t *)(dCalls + b), nullptr, before, s);
         if (result == limg_hip_success)
         {
-          launch_chain_base(dCalls, (int)b, (int)nb, dBase + b, (uint32_t *)c->devStatus.p + 1, s);
+          launch_chain_base(dCalls, (int)b, (int)nb, dBase + b, (uint32_t *)c->enc.devStatus.p + 1, s);
           result = limg_hip_encode3d_chain_device(c, dIn, sizeX, rows, hasAlpha, &d, errorFactor, fastBitCrushing, 2, nullptr, (const uint64_t *)(dBase + b), before, s);
         }
       }
-      if (result == limg_hip_success && hipEventRecord(c->hostEvents[b], s) != hipSuccess) result = limg_hip_error_Generic;
+      if (result == limg_hip_success && hipEventRecord(c->host.events[b], s) != hipSuccess) result = limg_hip_error_Generic;
       if (result != limg_hip_success) break;
       {
         std::lock_guard<std::mutex> lk(m);
@@ -141,7 +135,7 @@ namespace
       cv.notify_all();
       if (!copier)
       { // no second thread to be had: this band comes down here and now (the plain order, band-wise)
-        if (hipEventSynchronize(c->hostEvents[b]) != hipSuccess) { result = limg_hip_error_Generic; break; }
+        if (hipEventSynchronize(c->host.events[b]) != hipSuccess) { result = limg_hip_error_Generic; break; }
         for (int i = 0; i < 11; i++)
         {
           const size_t es = i < 8 ? 4 : 1;
@@ -173,13 +167,13 @@ namespace
     for (uint32_t b = 0; b < nb; b++)
     {
       const size_t rows = bands[b].y1 - bands[b].y0, o = bands[b].y0 * sizeX;
-      if (hipMemcpyAsync((uint32_t *)c->in.p + o, pIn + o, rows * sizeX * 4, hipMemcpyHostToDevice, c->hostCopyStream) != hipSuccess ||
-          hipEventRecord(c->hostEvents[b], c->hostCopyStream) != hipSuccess || hipStreamWaitEvent(c->hostStream, c->hostEvents[b], 0) != hipSuccess)
+      if (hipMemcpyAsync((uint32_t *)c->host.in.p + o, pIn + o, rows * sizeX * 4, hipMemcpyHostToDevice, c->host.copyStream) != hipSuccess ||
+          hipEventRecord(c->host.events[b], c->host.copyStream) != hipSuccess || hipStreamWaitEvent(c->host.stream, c->host.events[b], 0) != hipSuccess)
       {
         result = limg_hip_error_Generic;
         break;
       }
-      if ((result = encode_device(c, (const uint32_t *)c->in.p + o, sizeX, rows, hasAlpha, nullptr, nullptr, errorFactor, 0, fastBitCrushing, c->hostStream)) != limg_hip_success) break;
+      if ((result = encode_device(c, (const uint32_t *)c->host.in.p + o, sizeX, rows, hasAlpha, nullptr, nullptr, errorFactor, 0, fastBitCrushing, c->host.stream)) != limg_hip_success) break;
     }
     const limg_hip_result status = limg_hip_check_device_status(c); // (also waits for whatever is still enqueued: uploads from the caller's pIn among it)
     return result != limg_hip_success ? result : status;
@@ -200,10 +194,10 @@ extern "C"
     HIP_TRY(hipSetDevice(c->device));
     const size_t px = sizeX * sizeY;
     limg_hip_result r;
-    if ((r = c->in.ensure(px * 4)) != limg_hip_success) return r;
-    if ((r = c->planes.ensure(px * 35 + 11 * 256)) != limg_hip_success) return r;
+    if ((r = c->host.in.ensure(px * 4)) != limg_hip_success) return r;
+    if ((r = c->host.planes.ensure(px * 35 + 11 * 256)) != limg_hip_success) return r;
     limg_hip_encode3d_info d;
-    uint8_t *base = (uint8_t *)c->planes.p;
+    uint8_t *base = (uint8_t *)c->host.planes.p;
     void **dp = reinterpret_cast<void **>(&d);
     size_t off = 0;
     for (int i = 0; i < 11; i++)
@@ -215,10 +209,10 @@ extern "C"
     // (independent chains are the bands: at most 64 of them, at least 8 block rows each)
     const Partition pt = partition(sizeY, poolThreads);
     const bool chains = pt.chainCount > 1 && pt.chainRows != 0;
-    if (banded_host_entry(c, sizeX, sizeY) && !c->forceSplit && (!chains || (pt.chainCount <= 64 && pt.chainRows >= 8)))
+    if (banded_host_entry(c, sizeX, sizeY) && c->opt.force_split_kernels == 0 && (!chains || (pt.chainCount <= 64 && pt.chainRows >= 8)))
       return host_encode_banded(c, pIn, sizeX, sizeY, hasAlpha, hp, dp, errorFactor, poolThreads, fastBitCrushing);
-    HIP_TRY(hipMemcpy(c->in.p, pIn, px * 4, hipMemcpyHostToDevice));
-    if ((r = encode_device(c, (const uint32_t *)c->in.p, sizeX, sizeY, hasAlpha, &d, nullptr, errorFactor, poolThreads, fastBitCrushing, nullptr)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->host.in.p, pIn, px * 4, hipMemcpyHostToDevice));
+    if ((r = encode_device(c, (const uint32_t *)c->host.in.p, sizeX, sizeY, hasAlpha, &d, nullptr, errorFactor, poolThreads, fastBitCrushing, nullptr)) != limg_hip_success) return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
     for (int i = 0; i < 11; i++) HIP_TRY(hipMemcpy(hp[i], dp[i], i < 8 ? px * 4 : px, hipMemcpyDeviceToHost));
     return limg_hip_success;
@@ -233,11 +227,11 @@ extern "C"
     HIP_TRY(hipSetDevice(c->device));
     const size_t px = sizeX * sizeY;
     limg_hip_result r;
-    if ((r = c->in.ensure(px * 4)) != limg_hip_success) return r;
+    if ((r = c->host.in.ensure(px * 4)) != limg_hip_success) return r;
     if (banded_host_entry(c, sizeX, sizeY))
       return perf_banded(c, pIn, sizeX, sizeY, hasAlpha, errorFactor, fastBitCrushing);
-    HIP_TRY(hipMemcpy(c->in.p, pIn, px * 4, hipMemcpyHostToDevice));
-    if ((r = encode_device(c, (const uint32_t *)c->in.p, sizeX, sizeY, hasAlpha, nullptr, nullptr, errorFactor, poolThreads, fastBitCrushing, nullptr)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->host.in.p, pIn, px * 4, hipMemcpyHostToDevice));
+    if ((r = encode_device(c, (const uint32_t *)c->host.in.p, sizeX, sizeY, hasAlpha, nullptr, nullptr, errorFactor, poolThreads, fastBitCrushing, nullptr)) != limg_hip_success) return r;
     HIP_TRY(hipDeviceSynchronize());
     return limg_hip_success;
   }

@@ -31,20 +31,20 @@ extern "C"
   limg_hip_result limg_hip_comm_init(limg_hip_context *c, const uint8_t *pId, int rank, int worldSize)
   {
     if (!c || !pId) return limg_hip_error_ArgumentNull;
-    if (worldSize < 1 || rank < 0 || rank >= worldSize || c->comm) return limg_hip_error_InvalidParameter;
+    if (worldSize < 1 || rank < 0 || rank >= worldSize || c->chain.comm) return limg_hip_error_InvalidParameter;
     if (!rccl().ok) return limg_hip_error_Generic;
     HIP_TRY(hipSetDevice(c->device));
     ncclUniqueId id;
     memcpy(&id, pId, sizeof(id));
-    NCCL_TRY(rccl().CommInitRank(&c->comm, worldSize, id, rank));
-    c->commRank = rank; c->commWorld = worldSize;
-    limg_hip_result r2 = c->commWords.ensure((8 + 2 * (size_t)worldSize) * 8); // [0] own value, [1] chain base, [2..3] own (size, capacity), [8 ...] gathered
+    NCCL_TRY(rccl().CommInitRank(&c->chain.comm, worldSize, id, rank));
+    c->chain.rank = rank; c->chain.world = worldSize;
+    limg_hip_result r2 = c->chain.words.ensure((8 + 2 * (size_t)worldSize) * 8); // [0] own value, [1] chain base, [2..3] own (size, capacity), [8 ...] gathered
     if (r2 != limg_hip_success) return r2;
-    HIP_TRY(hipMemset(c->commWords.p, 0, (8 + 2 * (size_t)worldSize) * 8));
-    if (!c->devStatus.p)
+    HIP_TRY(hipMemset(c->chain.words.p, 0, (8 + 2 * (size_t)worldSize) * 8));
+    if (!c->enc.devStatus.p)
     { // the sticky status words (look-back timeout, aborted chain) exist from here on: the single-chain entry must not have to allocate on its error path
-      if ((r2 = c->devStatus.ensure(16)) != limg_hip_success) return r2;
-      HIP_TRY(hipMemset(c->devStatus.p, 0, 16));
+      if ((r2 = c->enc.devStatus.ensure(16)) != limg_hip_success) return r2;
+      HIP_TRY(hipMemset(c->enc.devStatus.p, 0, 16));
     }
     return limg_hip_success;
   }
@@ -54,11 +54,11 @@ extern "C"
   limg_hip_result limg_hip_comm_info(limg_hip_context *c, int *pRank, int *pRanks, int *pRcclVersion)
   {
     if (!c) return limg_hip_error_ArgumentNull;
-    if (!c->comm) return limg_hip_error_InvalidParameter;
+    if (!c->chain.comm) return limg_hip_error_InvalidParameter;
     if (!rccl().ok || !rccl().CommCount || !rccl().CommUserRank || !rccl().GetVersion) return limg_hip_error_Generic;
     int v = 0;
-    if (pRanks) NCCL_TRY(rccl().CommCount(c->comm, pRanks));
-    if (pRank) NCCL_TRY(rccl().CommUserRank(c->comm, pRank));
+    if (pRanks) NCCL_TRY(rccl().CommCount(c->chain.comm, pRanks));
+    if (pRank) NCCL_TRY(rccl().CommUserRank(c->chain.comm, pRank));
     if (pRcclVersion) { NCCL_TRY(rccl().GetVersion(&v)); *pRcclVersion = v; }
     return limg_hip_success;
   }
@@ -66,12 +66,12 @@ extern "C"
   limg_hip_result limg_hip_comm_destroy(limg_hip_context *c)
   {
     if (!c) return limg_hip_error_ArgumentNull;
-    if (c->comm)
+    if (c->chain.comm)
     {
       HIP_TRY(hipSetDevice(c->device));
       HIP_TRY(hipDeviceSynchronize());
-      NCCL_TRY(rccl().CommDestroy(c->comm));
-      c->comm = nullptr; c->commRank = 0; c->commWorld = 1;
+      NCCL_TRY(rccl().CommDestroy(c->chain.comm));
+      c->chain.comm = nullptr; c->chain.rank = 0; c->chain.world = 1;
     }
     return limg_hip_success;
   }
@@ -105,20 +105,20 @@ extern "C"
                                          void *stream)
   {
     if (!c || !pStream) return limg_hip_error_ArgumentNull;
-    if (!c->comm) return limg_hip_error_InvalidParameter;
-    if (root < 0 || root >= c->commWorld) return limg_hip_error_InvalidParameter;
-    const bool isRoot = c->commRank == root;
+    if (!c->chain.comm) return limg_hip_error_InvalidParameter;
+    if (root < 0 || root >= c->chain.world) return limg_hip_error_InvalidParameter;
+    const bool isRoot = c->chain.rank == root;
     if (isRoot && (!pGathered || !pOffsets)) return limg_hip_error_ArgumentNull;
     if (isRoot && ((uintptr_t)pGathered & 15u) != 0) return limg_hip_error_InvalidParameter;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const int world = c->commWorld;
-    unsigned long long *words = (unsigned long long *)c->commWords.p;
+    const int world = c->chain.world;
+    unsigned long long *words = (unsigned long long *)c->chain.words.p;
     // 1. every rank learns every size AND the root's capacity: one 16-byte all-gather.  Whether the pieces fit is then decided by every rank from the same
     //    numbers -- a root that alone found its buffer too small would leave its peers' sends unmatched
     const unsigned long long mine[2] = { (unsigned long long)streamBytes, isRoot ? (unsigned long long)capacity : 0ull };
     HIP_TRY(hipMemcpyAsync(words + 2, mine, 16, hipMemcpyHostToDevice, s));
-    NCCL_TRY(rccl().AllGather(words + 2, words + 8, 2, ncclUint64, c->comm, s));
+    NCCL_TRY(rccl().AllGather(words + 2, words + 8, 2, ncclUint64, c->chain.comm, s));
     std::vector<uint64_t> pairs(2 * (size_t)world), sizes(world), offs(world + 1);
     HIP_TRY(hipMemcpyAsync(pairs.data(), words + 8, (size_t)world * 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -131,10 +131,10 @@ extern "C"
     if (isRoot)
     {
       for (int r = 0; r < world && posted == ncclSuccess; r++)
-        if (r != root && sizes[r]) posted = rccl().Recv(pGathered + offs[r], sizes[r], ncclUint8, r, c->comm, s);
+        if (r != root && sizes[r]) posted = rccl().Recv(pGathered + offs[r], sizes[r], ncclUint8, r, c->chain.comm, s);
     }
     else if (streamBytes)
-      posted = rccl().Send(pStream, streamBytes, ncclUint8, root, c->comm, s);
+      posted = rccl().Send(pStream, streamBytes, ncclUint8, root, c->chain.comm, s);
     const ncclResult_t closed = rccl().GroupEnd();
     NCCL_TRY(posted);
     NCCL_TRY(closed);
@@ -151,10 +151,10 @@ extern "C"
                                                         uint32_t errorFactor, int fastBitCrushing, size_t blocksBefore, void *stream)
   {
     if (!c) return limg_hip_error_ArgumentNull;
-    if (!c->comm) return limg_hip_error_InvalidParameter; // no communicator: nobody is waiting for this rank
+    if (!c->chain.comm) return limg_hip_error_InvalidParameter; // no communicator: nobody is waiting for this rank
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long *words = (unsigned long long *)c->commWords.p;
+    unsigned long long *words = (unsigned long long *)c->chain.words.p;
     limg_hip_result r;
     // E step + scan: this strip's dither calls land in words[0] ...  (bad arguments on this rank are a phase-1 failure like any other: see the abort rule)
     if (!pIn || !pInfo) r = limg_hip_error_ArgumentNull;
@@ -167,8 +167,8 @@ extern "C"
     const limg_hip_result phase1 = r;
     if (phase1 != limg_hip_success) HIP_TRY(hipMemsetAsync(words, 0xFF, 8, s));
     // ... one 8-byte all-gather, the exclusive prefix over the ranks before this one on the device (stream-ordered, no host round trip) ...
-    NCCL_TRY(rccl().AllGather(words, words + 8, 1, ncclUint64, c->comm, s));
-    launch_chain_base(words + 8, c->commRank, c->commWorld, words + 1, (uint32_t *)c->devStatus.p + 1, s);
+    NCCL_TRY(rccl().AllGather(words, words + 8, 1, ncclUint64, c->chain.comm, s));
+    launch_chain_base(words + 8, c->chain.rank, c->chain.world, words + 1, (uint32_t *)c->enc.devStatus.p + 1, s);
     if (phase1 != limg_hip_success) return phase1;
     // ... and the F step indexes the noise stream from there: the 8-GPU result equals the single-threaded reference's (src/limg.cpp:1893, :2110)
     return limg_hip_encode3d_chain_device(c, pIn, sizeX, stripRows, hasAlpha, pInfo, errorFactor, fastBitCrushing, 2, nullptr, (const uint64_t *)(words + 1), blocksBefore, s);

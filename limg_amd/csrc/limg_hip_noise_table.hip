@@ -51,7 +51,7 @@ namespace limg_hip
     return true;
   }
 
-  // Dense chain checkpoints covering dither calls [0, calls) on the device (c->noiseCk): the embedded table once per context, more when an image reaches beyond it
+  // Dense chain checkpoints covering dither calls [0, calls) on the device (c->noise.ck): the embedded table once per context, more when an image reaches beyond it
   // (more than 5.59 M blocks: the missing values come from the far table, dense_checkpoints_host).  Blocking copies: whichever stream fills a noise table later
   // finds them there (an asynchronous copy on the first caller's stream would order nothing for a second stream), and a failed copy leaves no buffer behind that
   // later encodes would trust.  (A buffer that grows is freed first: hipFree waits for the fill kernels that may still read it.)
@@ -61,14 +61,14 @@ namespace limg_hip
     const uint64_t *ck = noise_checkpoints_host(&ckCount, &ckEvery);
     size_t need = (calls + ckEvery - 1) / ckEvery;
     if (need < ckCount) need = ckCount;
-    if (c->noiseCk.p && need <= c->noiseCkCount) return limg_hip_success;
+    if (c->noise.ck.p && need <= c->noise.ckCount) return limg_hip_success;
     if (calls > checkpoint_reach()) return limg_hip_error_InvalidParameter;
     const uint64_t *src = ck;
     if (need > ckCount)
     {
       try
       {
-        std::vector<uint64_t> &v = c->noiseCkHost;
+        std::vector<uint64_t> &v = c->noise.ckHost;
         if (v.empty()) v.assign(ck, ck + ckCount);
         const size_t have = v.size();
         if (need > have)
@@ -78,26 +78,26 @@ namespace limg_hip
         }
         src = v.data();
       }
-      catch (...) { c->noiseCkHost.clear(); return limg_hip_error_MemoryAllocationFailure; }
+      catch (...) { c->noise.ckHost.clear(); return limg_hip_error_MemoryAllocationFailure; }
     }
     limg_hip_result r;
-    c->noiseCkCount = 0;
-    if ((r = c->noiseCk.ensure(need * 8)) != limg_hip_success) return r;
-    if (hipMemcpy(c->noiseCk.p, src, need * 8, hipMemcpyHostToDevice) != hipSuccess)
+    c->noise.ckCount = 0;
+    if ((r = c->noise.ck.ensure(need * 8)) != limg_hip_success) return r;
+    if (hipMemcpy(c->noise.ck.p, src, need * 8, hipMemcpyHostToDevice) != hipSuccess)
     {
-      c->noiseCk.release();
+      c->noise.ck.release();
       fprintf(stderr, "limg_hip: upload of the dither chain checkpoints failed\n");
       return limg_hip_error_Generic;
     }
-    c->noiseCkCount = need;
+    c->noise.ckCount = need;
     return limg_hip_success;
   }
 
   limg_hip_result grow_noise_table(limg_hip_context *c, size_t entries, hipStream_t stream)
   {
     const bool pcg = c->opt.dither_pcg != 0;
-    if (pcg != c->noisePcg) c->noiseCount = 0;
-    if (entries <= c->noiseCount) return limg_hip_success;
+    if (pcg != c->noise.pcg) c->noise.count = 0;
+    if (entries <= c->noise.count) return limg_hip_success;
     const size_t want = ((entries + kNoiseChunk - 1) / kNoiseChunk) * kNoiseChunk;
     if (!pcg && want <= checkpoint_reach() && c->opt.host_noise_table == 0)
     { // the AES stream, on the GPU from the embedded chain checkpoints (limg_hip_noise_gpu.hip): stream-ordered, ~1 ms, nothing crosses PCIe but the 128 KiB of
@@ -107,11 +107,11 @@ namespace limg_hip
       limg_hip_result r;
       if ((r = ensure_checkpoints(c, want)) != limg_hip_success) return r;
       HIP_TRY(hipStreamSynchronize(stream)); // earlier encodes on this stream may still read the table that is about to be replaced
-      if ((r = c->noise.ensure(want * 64)) != limg_hip_success) return r;
-      launch_noise_fill((uint8_t *)c->noise.p, (const uint64_t *)c->noiseCk.p, want, stream);
+      if ((r = c->noise.table.ensure(want * 64)) != limg_hip_success) return r;
+      launch_noise_fill((uint8_t *)c->noise.table.p, (const uint64_t *)c->noise.ck.p, want, stream);
       HIP_TRY(hipGetLastError());
-      c->noiseCount = want;
-      c->noisePcg = false;
+      c->noise.count = want;
+      c->noise.pcg = false;
       return limg_hip_success;
     }
     // PCG dither (a test / fallback mode), tables beyond the far checkpoints' reach (2^27 calls: images of more than 44.7 M blocks) or limg_hip_options.host_noise_table:
@@ -120,12 +120,12 @@ namespace limg_hip
     uint64_t h = kDitherSeed;
     h = fill_noise_table(h, host.data(), want, pcg);
     HIP_TRY(hipStreamSynchronize(stream));
-    const limg_hip_result r = c->noise.ensure(want * 64);
+    const limg_hip_result r = c->noise.table.ensure(want * 64);
     if (r != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(c->noise.p, host.data(), want * 64, hipMemcpyHostToDevice));
-    c->noiseCount = want;
-    c->noisePcg = pcg;
-    c->noiseNext = h;
+    HIP_TRY(hipMemcpy(c->noise.table.p, host.data(), want * 64, hipMemcpyHostToDevice));
+    c->noise.count = want;
+    c->noise.pcg = pcg;
+    c->noise.next = h;
     return limg_hip_success;
   }
 
@@ -155,7 +155,7 @@ extern "C"
     HIP_TRY(hipSetDevice(c->device));
     limg_hip_result r;
     if ((r = ensure_checkpoints(c, calls)) != limg_hip_success) return r;
-    launch_noise_fill(pOutDevice, (const uint64_t *)c->noiseCk.p, calls, (hipStream_t)stream);
+    launch_noise_fill(pOutDevice, (const uint64_t *)c->noise.ck.p, calls, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return limg_hip_success;
   }

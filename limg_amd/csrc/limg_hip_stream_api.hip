@@ -9,15 +9,15 @@
 using namespace limg_hip;
 
 // ---- shared with limg_hip_stream_window_api.hip (declared in limg_hip_context.h) ----
-int limg_hip::device_cus(const limg_hip_context *c) { return c->persistentWorkgroups / 5; }
+int limg_hip::device_cus(const limg_hip_context *c) { return c->enc.persistentWorkgroups / 5; }
 
 // the status word the stream decoders share (limg_hip_check_device_status reads it), then the version 1 decode kernel's store sink (see DecodeParams::sink)
 limg_hip_result limg_hip::ensure_stream_status(limg_hip_context *c, hipStream_t s)
 {
-  if (c->streamStatus.p) return limg_hip_success;
-  const limg_hip_result r = c->streamStatus.ensure(256 + 2048);
+  if (c->stream.status.p) return limg_hip_success;
+  const limg_hip_result r = c->stream.status.ensure(256 + 2048);
   if (r != limg_hip_success) return r;
-  HIP_TRY(hipMemsetAsync(c->streamStatus.p, 0, 8, s));
+  HIP_TRY(hipMemsetAsync(c->stream.status.p, 0, 8, s));
   return limg_hip_success;
 }
 
@@ -56,12 +56,12 @@ namespace
   }
 
   // ---- host-pointer forms: upload, the version's device entry on the null stream, status, download ----
-  // the stream in the context's streamBuf to the caller: *pBytes says what it takes even where `capacity` is too small
+  // the stream in the context's stream.buf to the caller: *pBytes says what it takes even where `capacity` is too small
   limg_hip_result download_stream(limg_hip_context *c, size_t bytes, uint8_t *pStream, size_t capacity, size_t *pBytes)
   {
     *pBytes = bytes;
     if (bytes > capacity) return limg_hip_error_OutOfBounds;
-    HIP_TRY(hipMemcpy(pStream, c->streamBuf.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pStream, c->stream.buf.p, bytes, hipMemcpyDeviceToHost));
     return limg_hip_success;
   }
 
@@ -74,11 +74,11 @@ namespace
     HIP_TRY(hipSetDevice(c->device));
     limg_hip_result r;
     const size_t px = sizeX * sizeY;
-    if ((r = c->in.ensure(px * 4)) != limg_hip_success) return r;
-    if ((r = c->streamBuf.ensure(bound)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(c->in.p, pIn, px * 4, hipMemcpyHostToDevice));
+    if ((r = c->host.in.ensure(px * 4)) != limg_hip_success) return r;
+    if ((r = c->stream.buf.ensure(bound)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->host.in.p, pIn, px * 4, hipMemcpyHostToDevice));
     size_t bytes = 0;
-    if ((r = deviceEncode((const uint32_t *)c->in.p, (uint8_t *)c->streamBuf.p, bound, &bytes)) != limg_hip_success) return r;
+    if ((r = deviceEncode((const uint32_t *)c->host.in.p, (uint8_t *)c->stream.buf.p, bound, &bytes)) != limg_hip_success) return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
     return download_stream(c, bytes, pStream, capacity, pBytes);
   }
@@ -91,12 +91,12 @@ namespace
     if (total > streamBytes || sizeX * sizeY > outPixels) return limg_hip_error_OutOfBounds;
     HIP_TRY(hipSetDevice(c->device));
     limg_hip_result r;
-    if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
-    if ((r = c->planes.ensure(sizeX * sizeY * 4)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice));
-    if ((r = deviceDecode((const uint8_t *)c->streamBuf.p, total, (uint32_t *)c->planes.p, sizeX, sizeY)) != limg_hip_success) return r;
+    if ((r = c->stream.buf.ensure(total + 16)) != limg_hip_success) return r;
+    if ((r = c->host.planes.ensure(sizeX * sizeY * 4)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->stream.buf.p, pStream, total, hipMemcpyHostToDevice));
+    if ((r = deviceDecode((const uint8_t *)c->stream.buf.p, total, (uint32_t *)c->host.planes.p, sizeX, sizeY)) != limg_hip_success) return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(pOut, c->planes.p, sizeX * sizeY * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pOut, c->host.planes.p, sizeX * sizeY * 4, hipMemcpyDeviceToHost));
     return limg_hip_success;
   }
 
@@ -106,32 +106,31 @@ namespace
   {
     const size_t blocks = ((sizeX + kBlock - 1) / kBlock) * ((sizeY + kBlock - 1) / kBlock);
     limg_hip_result r;
-    if ((r = c->bsUnits.ensure((blocks + 1) * 4)) != limg_hip_success) return r;
-    if ((r = c->bsTiles.ensure(((blocks + 255) / 256) * 8)) != limg_hip_success) return r;
-    for (hipEvent_t e; c->packTimers.size() < 2; c->packTimers.push_back(e)) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDefault));
-    return limg_hip_success;
+    if ((r = c->stream.bsUnits.ensure((blocks + 1) * 4)) != limg_hip_success) return r;
+    if ((r = c->stream.bsTiles.ensure(((blocks + 255) / 256) * 8)) != limg_hip_success) return r;
+    return c->stream.packTimers.ensure(2, hipEventDefault);
   }
 
   // The stream of the context's last merged-block encode, from what that left in the context's buffers (blocked_encode_device: with or without planes, the store step
   // does not change them): scan + pack on `s`.  pBytes (host, may be NULL) makes the call wait.
   limg_hip_result pack_last(limg_hip_context *c, uint8_t *dStream, size_t *pBytes, hipStream_t s)
   {
-    const size_t sizeX = c->lastBlocked.sizeX, sizeY = c->lastBlocked.sizeY;
-    const size_t blocksX = (sizeX + kBlock - 1) / kBlock, blocksY = (sizeY + kBlock - 1) / kBlock, blocks = blocksX * blocksY, nRegions = c->lastRegions.size();
-    if (!c->lastBlocked.valid || nRegions == 0 || nRegions > blocks) return limg_hip_error_Generic;
+    const size_t sizeX = c->blocked.last.sizeX, sizeY = c->blocked.last.sizeY;
+    const size_t blocksX = (sizeX + kBlock - 1) / kBlock, blocksY = (sizeY + kBlock - 1) / kBlock, blocks = blocksX * blocksY, nRegions = c->blocked.lastRegions.size();
+    if (!c->blocked.last.valid || nRegions == 0 || nRegions > blocks) return limg_hip_error_Generic;
     BlockedStreamParams sp;
     memset(&sp, 0, sizeof(sp));
     sp.sizeX = (uint32_t)sizeX; sp.sizeY = (uint32_t)sizeY; sp.blocksX = (uint32_t)blocksX; sp.blocksY = (uint32_t)blocksY;
-    sp.channels = (uint32_t)c->lastBlocked.channels; sp.errorFactor = c->lastBlocked.errorFactor; sp.flags = c->lastBlocked.flags;
-    sp.nRegions = (uint32_t)nRegions; sp.nTiles = (uint32_t)((nRegions + 255) / 256); sp.scratchCap = (uint32_t)c->blockedScratchCap;
-    sp.regions = (const RegionDesc *)c->bRegions.p; sp.out = (const RegionOut *)c->bOut.p; sp.noiseBase = (const unsigned long long *)c->bNoiseBase.p;
-    sp.scratchFac = (const uint8_t *)c->bFac.p; sp.noise = (const uint8_t *)c->bNoise.p;
-    sp.stream = dStream; sp.units = (uint32_t *)c->bsUnits.p; sp.tiles = (uint32_t *)c->bsTiles.p;
-    HIP_TRY(hipEventRecord(c->packTimers[0], s));
+    sp.channels = (uint32_t)c->blocked.last.channels; sp.errorFactor = c->blocked.last.errorFactor; sp.flags = c->blocked.last.flags;
+    sp.nRegions = (uint32_t)nRegions; sp.nTiles = (uint32_t)((nRegions + 255) / 256); sp.scratchCap = (uint32_t)c->blocked.scratchCap;
+    sp.regions = (const RegionDesc *)c->blocked.regions.p; sp.out = (const RegionOut *)c->blocked.out.p; sp.noiseBase = (const unsigned long long *)c->blocked.noiseBase.p;
+    sp.scratchFac = (const uint8_t *)c->blocked.fac.p; sp.noise = (const uint8_t *)c->blocked.noise.p;
+    sp.stream = dStream; sp.units = (uint32_t *)c->stream.bsUnits.p; sp.tiles = (uint32_t *)c->stream.bsTiles.p;
+    HIP_TRY(hipEventRecord(c->stream.packTimers[0], s));
     launch_blocked_stream_pack(sp, device_cus(c), s);
-    HIP_TRY(hipEventRecord(c->packTimers[1], s));
+    HIP_TRY(hipEventRecord(c->stream.packTimers[1], s));
     HIP_TRY(hipGetLastError());
-    c->packTimed = true;
+    c->stream.packTimed = true;
     return pBytes ? stream_total_bytes(dStream, s, pBytes) : limg_hip_success;
   }
 }
@@ -160,21 +159,21 @@ extern "C"
     const size_t blocksX = (sizeX + kBlock - 1) / kBlock, blocksY = (sizeY + kBlock - 1) / kBlock, blocks = blocksX * blocksY;
     const size_t tiles = (blocks + 255) / 256;
     limg_hip_result r;
-    if ((r = c->streamFac.ensure(planeStride * 3)) != limg_hip_success) return r;
+    if ((r = c->stream.fac.ensure(planeStride * 3)) != limg_hip_success) return r;
     // strip form of the packer (images of whole blocks): the encode kernel leaves one payload-word count per work strip (limg_hip_stream.hip)
     const size_t stripsX = (blocksX + kStripBlocks - 1) / kStripBlocks, nStrips = stripsX * blocksY;
-    const bool stripForm = (sizeX % kBlock) == 0 && (sizeY % kBlock) == 0 && !c->forceSplit;
-    if ((r = c->streamTiles.ensure(tiles * 4)) != limg_hip_success) return r;
-    if (stripForm && (r = c->streamUnits.ensure(nStrips * 4)) != limg_hip_success) return r;
-    if ((r = c->records.ensure(blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
-    if ((r = c->shifts.ensure(blocks * 4)) != limg_hip_success) return r;
+    const bool stripForm = (sizeX % kBlock) == 0 && (sizeY % kBlock) == 0 && c->opt.force_split_kernels == 0;
+    if ((r = c->stream.tiles.ensure(tiles * 4)) != limg_hip_success) return r;
+    if (stripForm && (r = c->stream.units.ensure(nStrips * 4)) != limg_hip_success) return r;
+    if ((r = c->enc.records.ensure(blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+    if ((r = c->enc.shifts.ensure(blocks * 4)) != limg_hip_success) return r;
     limg_hip_encode3d_info info;
     memset(&info, 0, sizeof(info));
-    info.pFactorsA = (uint8_t *)c->streamFac.p; info.pFactorsB = info.pFactorsA + planeStride; info.pFactorsC = info.pFactorsB + planeStride;
-    limg_hip_compact_out comp = { (limg_hip_block_record *)c->records.p, (uint32_t *)c->shifts.p };
+    info.pFactorsA = (uint8_t *)c->stream.fac.p; info.pFactorsB = info.pFactorsA + planeStride; info.pFactorsC = info.pFactorsB + planeStride;
+    limg_hip_compact_out comp = { (limg_hip_block_record *)c->enc.records.p, (uint32_t *)c->enc.shifts.p };
     EncodeExtra xs;
     xs.streamRaw = true;
-    xs.stripWords = stripForm ? (uint32_t *)c->streamUnits.p : nullptr;
+    xs.stripWords = stripForm ? (uint32_t *)c->stream.units.p : nullptr;
     if ((r = encode_device(c, pIn, sizeX, sizeY, hasAlpha, &info, &comp, errorFactor, poolThreads, fastBitCrushing, s, xs)) != limg_hip_success) return r;
 
     StreamParams sp;
@@ -184,10 +183,10 @@ extern "C"
     sp.flags = (fastBitCrushing ? 1u : 0u) | (c->opt.dither_pcg ? 2u : 0u);
     sp.fac[0] = info.pFactorsA; sp.fac[1] = info.pFactorsB; sp.fac[2] = info.pFactorsC;
     sp.records = comp.pRecords; sp.shifts = comp.pShifts;
-    sp.stream = pStream; sp.tileBase = (uint32_t *)c->streamTiles.p;
+    sp.stream = pStream; sp.tileBase = (uint32_t *)c->stream.tiles.p;
     if (stripForm)
     {
-      sp.stripWords = (uint32_t *)c->streamUnits.p;
+      sp.stripWords = (uint32_t *)c->stream.units.p;
       sp.stripsX = (uint32_t)stripsX; sp.nStrips = (uint32_t)nStrips;
       const size_t slots = (size_t)device_cus(c) * 16; // 16 one-wave workgroups per CU (128 vector registers each: 4 per SIMD)
       sp.nWaves = (uint32_t)(nStrips < slots ? nStrips : slots);
@@ -214,7 +213,7 @@ extern "C"
     dp.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); dp.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
     dp.nBlocks = dp.blocksX * dp.blocksY;
     if (streamBytes < sizeof(limg_hip_stream_header) + (size_t)dp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
-    dp.stream = pStream; dp.streamBytes = streamBytes; dp.out = pOut; dp.status = (uint32_t *)c->streamStatus.p; dp.sink = (uint32_t *)((uint8_t *)c->streamStatus.p + 256);
+    dp.stream = pStream; dp.streamBytes = streamBytes; dp.out = pOut; dp.status = (uint32_t *)c->stream.status.p; dp.sink = (uint32_t *)((uint8_t *)c->stream.status.p + 256);
     mark(c, s);
     launch_stream_decode(dp, device_cus(c), s);
     mark(c, s); mark(c, s); mark(c, s);
@@ -256,7 +255,7 @@ extern "C"
 
   // ---- batched stream encode: a list of same-shape images, stream i = limg_hip_encode_stream_device of image i ----
   // Lists of whole-block images go chunk by chunk (the plane batch's rule) through ONE compact-mode batched encode -- records, shift words and the strips' payload
-  // words in the context's raster arrays, image after image; the factor planes in per-image slices of streamFac -- and one scan + one pack launch over the chunk.
+  // words in the context's raster arrays, image after image; the factor planes in per-image slices of stream.fac -- and one scan + one pack launch over the chunk.
   limg_hip_result limg_hip_encode_stream_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
                                                       uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, int poolThreads,
                                                       int fastBitCrushing, void *stream)
@@ -282,16 +281,16 @@ extern "C"
     if (chunk < 1) chunk = 1;
     if (TOPT(c, batch_chunk) > 0) chunk = (size_t)TOPT(c, batch_chunk);
     const bool ragged = (sizeX % kBlock) != 0 || (sizeY % kBlock) != 0;
-    const bool oneByOne = count == 1 || ragged || c->opt.legacy_float_stage != 0 || c->forceSplit;
+    const bool oneByOne = count == 1 || ragged || c->opt.legacy_float_stage != 0 || c->opt.force_split_kernels != 0;
     const size_t most = oneByOne ? 1 : (count < chunk ? count : chunk); // images of the largest chunk
     limg_hip_result r;
-    if ((r = c->streamTable.ensure(count * sizeof(StreamImage))) != limg_hip_success) return r;
+    if ((r = c->stream.table.ensure(count * sizeof(StreamImage))) != limg_hip_success) return r;
     if (most > 1)
     { // everything a chunk needs, before the first launch: nothing is grown (and so freed) between the chunks of a list
-      if ((r = c->streamFac.ensure(most * planeStride * 3)) != limg_hip_success) return r;
-      if ((r = c->streamUnits.ensure(most * imageStrips * 4)) != limg_hip_success) return r;
-      if ((r = c->records.ensure(most * blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
-      if ((r = c->shifts.ensure(most * blocks * 4)) != limg_hip_success) return r;
+      if ((r = c->stream.fac.ensure(most * planeStride * 3)) != limg_hip_success) return r;
+      if ((r = c->stream.units.ensure(most * imageStrips * 4)) != limg_hip_success) return r;
+      if ((r = c->enc.records.ensure(most * blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+      if ((r = c->enc.shifts.ensure(most * blocks * 4)) != limg_hip_success) return r;
     }
     std::vector<StreamImage> images(count);
     for (size_t i = 0; i < count; i++) images[i].stream = ppStreams[i];
@@ -300,28 +299,28 @@ extern "C"
     for (size_t i0 = 0; i0 < count && r == limg_hip_success;)
     {
       const size_t n = oneByOne ? 1 : (count - i0 < chunk ? count - i0 : chunk);
-      c->statsAccumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, as the plane batch
+      c->stats.accumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, as the plane batch
       if (n == 1)
       { // the single call (images with partial edge blocks, the split path, the float stage inside the encode kernel, a list or a last chunk of one image)
         r = limg_hip_encode_stream_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, ppStreams[i0], capacityEach, nullptr, errorFactor, poolThreads, fastBitCrushing, stream);
-        if (r == limg_hip_success && pBytes && !oneByOne) launch_set_stream_table((StreamImage *)c->streamTable.p + i0, &images[i0], 1, s); // (for the sizes below)
+        if (r == limg_hip_success && pBytes && !oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], 1, s); // (for the sizes below)
       }
       else
       {
         table.assign(n, ImageIO{});
         for (size_t i = 0; i < n; i++)
         {
-          uint8_t *fac = (uint8_t *)c->streamFac.p + i * 3 * planeStride; // 256-byte aligned slices
+          uint8_t *fac = (uint8_t *)c->stream.fac.p + i * 3 * planeStride; // 256-byte aligned slices
           table[i].in = ppIn[i0 + i];
           table[i].info.pFactorsA = fac; table[i].info.pFactorsB = fac + planeStride; table[i].info.pFactorsC = fac + 2 * planeStride;
           images[i0 + i].fac[0] = fac; images[i0 + i].fac[1] = fac + planeStride; images[i0 + i].fac[2] = fac + 2 * planeStride;
         }
-        limg_hip_compact_out comp = { (limg_hip_block_record *)c->records.p, (uint32_t *)c->shifts.p };
+        limg_hip_compact_out comp = { (limg_hip_block_record *)c->enc.records.p, (uint32_t *)c->enc.shifts.p };
         EncodeExtra x;
         x.batch = table.data(); x.batchCount = n;
-        x.streamRaw = true; x.stripWords = (uint32_t *)c->streamUnits.p;
+        x.streamRaw = true; x.stripWords = (uint32_t *)c->stream.units.p;
         if ((r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, &table[0].info, &comp, errorFactor, poolThreads, fastBitCrushing, s, x)) != limg_hip_success) break;
-        launch_set_stream_table((StreamImage *)c->streamTable.p + i0, &images[i0], n, s);
+        launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], n, s);
         StreamBatchParams b;
         memset(&b, 0, sizeof(b));
         b.sizeX = (uint32_t)sizeX; b.sizeY = (uint32_t)sizeY; b.blocksX = (uint32_t)blocksX; b.blocksY = (uint32_t)blocksY; b.nBlocks = (uint32_t)blocks;
@@ -329,25 +328,25 @@ extern "C"
         b.stripsX = (uint32_t)stripsX; b.imageStrips = (uint32_t)imageStrips; b.nImages = (uint32_t)n; b.nStrips = (uint32_t)(n * imageStrips);
         const size_t slots = (size_t)device_cus(c) * 16; // as the single call: 16 one-wave workgroups per CU -- for the whole chunk
         b.nWaves = (uint32_t)(n * imageStrips < slots ? n * imageStrips : slots);
-        b.images = (const StreamImage *)c->streamTable.p + i0;
-        b.records = comp.pRecords; b.shifts = comp.pShifts; b.stripWords = (uint32_t *)c->streamUnits.p;
+        b.images = (const StreamImage *)c->stream.table.p + i0;
+        b.records = comp.pRecords; b.shifts = comp.pShifts; b.stripWords = (uint32_t *)c->stream.units.p;
         mark(c, s);
         launch_stream_pack_batch(b, s);
         mark(c, s); mark(c, s); mark(c, s);
         const hipError_t launched = hipGetLastError();
-        if (launched != hipSuccess) { c->statsAccumulate = false; HIP_TRY(launched); }
+        if (launched != hipSuccess) { c->stats.accumulate = false; HIP_TRY(launched); }
       }
       i0 += n;
     }
-    c->statsAccumulate = false;
+    c->stats.accumulate = false;
     if (r != limg_hip_success || !pBytes) return r;
     // the sizes: gathered from the headers on the device, ONE download
-    if ((r = c->streamSizes.ensure(count * 8)) != limg_hip_success) return r;
-    if (oneByOne) launch_set_stream_table((StreamImage *)c->streamTable.p, images.data(), count, s);
-    launch_stream_gather_bytes((const StreamImage *)c->streamTable.p, count, (unsigned long long *)c->streamSizes.p, s);
+    if ((r = c->stream.sizes.ensure(count * 8)) != limg_hip_success) return r;
+    if (oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p, images.data(), count, s);
+    launch_stream_gather_bytes((const StreamImage *)c->stream.table.p, count, (unsigned long long *)c->stream.sizes.p, s);
     HIP_TRY(hipGetLastError());
     std::vector<unsigned long long> sizes(count);
-    HIP_TRY(hipMemcpyAsync(sizes.data(), c->streamSizes.p, count * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(sizes.data(), c->stream.sizes.p, count * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (size_t i = 0; i < count; i++) pBytes[i] = (size_t)sizes[i];
     return limg_hip_success;
@@ -365,17 +364,17 @@ extern "C"
     if (capacityEach < bound) return limg_hip_error_OutOfBounds;
     if (count == 0) return limg_hip_success;
     HIP_TRY(hipSetDevice(c->device));
-    // staging: the images side by side in `in`, the streams at worst-case size (rounded up to 256 bytes) side by side in streamBuf
+    // staging: the images side by side in host.in, the streams at worst-case size (rounded up to 256 bytes) side by side in stream.buf
     const size_t px = sizeX * sizeY, slice = (bound + 255) & ~(size_t)255;
     limg_hip_result r;
-    if ((r = c->in.ensure(count * px * 4)) != limg_hip_success) return r;
-    if ((r = c->streamBuf.ensure(count * slice)) != limg_hip_success) return r;
+    if ((r = c->host.in.ensure(count * px * 4)) != limg_hip_success) return r;
+    if ((r = c->stream.buf.ensure(count * slice)) != limg_hip_success) return r;
     std::vector<const uint32_t *> dIn(count);
     std::vector<uint8_t *> dStreams(count);
     for (size_t i = 0; i < count; i++)
     {
-      dIn[i] = (const uint32_t *)c->in.p + i * px;
-      dStreams[i] = (uint8_t *)c->streamBuf.p + i * slice;
+      dIn[i] = (const uint32_t *)c->host.in.p + i * px;
+      dStreams[i] = (uint8_t *)c->stream.buf.p + i * slice;
       HIP_TRY(hipMemcpy((void *)dIn[i], ppIn[i], px * 4, hipMemcpyHostToDevice));
     }
     if ((r = limg_hip_encode_stream_batch_device(c, count, dIn.data(), sizeX, sizeY, hasAlpha, dStreams.data(), slice, pBytes, errorFactor, poolThreads, fastBitCrushing,
@@ -415,15 +414,15 @@ extern "C"
   {
     if (!c || !pStream || !pBytes) return limg_hip_error_ArgumentNull;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    if (!c->lastBlocked.valid) return limg_hip_error_InvalidParameter; // no merged-block encode on this context, or the last one failed
-    const size_t bound = limg_hip_blocked_stream_bound(c->lastBlocked.sizeX, c->lastBlocked.sizeY);
+    if (!c->blocked.last.valid) return limg_hip_error_InvalidParameter; // no merged-block encode on this context, or the last one failed
+    const size_t bound = limg_hip_blocked_stream_bound(c->blocked.last.sizeX, c->blocked.last.sizeY);
     if (bound == 0) return limg_hip_error_InvalidParameter;
     HIP_TRY(hipSetDevice(c->device));
     limg_hip_result r;
-    if ((r = ensure_pack_resources(c, c->lastBlocked.sizeX, c->lastBlocked.sizeY)) != limg_hip_success) return r;
-    if ((r = c->streamBuf.ensure(bound)) != limg_hip_success) return r;
+    if ((r = ensure_pack_resources(c, c->blocked.last.sizeX, c->blocked.last.sizeY)) != limg_hip_success) return r;
+    if ((r = c->stream.buf.ensure(bound)) != limg_hip_success) return r;
     size_t bytes = 0;
-    if ((r = pack_last(c, (uint8_t *)c->streamBuf.p, &bytes, nullptr)) != limg_hip_success) return r;
+    if ((r = pack_last(c, (uint8_t *)c->stream.buf.p, &bytes, nullptr)) != limg_hip_success) return r;
     return download_stream(c, bytes, pStream, capacity, pBytes);
   }
 

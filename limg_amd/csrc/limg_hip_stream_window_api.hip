@@ -118,7 +118,7 @@ limg_hip_result limg_hip::window_params(limg_hip_context *c, const uint8_t *pStr
   if (r != limg_hip_success) return r;
   HIP_TRY(hipSetDevice(c->device));
   if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
-  wp.status = (uint32_t *)c->streamStatus.p;
+  wp.status = (uint32_t *)c->stream.status.p;
   return limg_hip_success;
 }
 
@@ -127,11 +127,11 @@ limg_hip_result limg_hip::blocked_window_decode(limg_hip_context *c, WindowDecod
 {
   const size_t mapBytes = (size_t)wp.wbx * wp.wby * 4;
   limg_hip_result r;
-  if ((r = c->bsMap.ensure(mapBytes)) != limg_hip_success) return r;
-  if ((r = c->bsState.ensure(64)) != limg_hip_success) return r;
-  HIP_TRY(hipMemsetAsync(c->bsMap.p, 0xFF, mapBytes, s)); // no block has a rectangle yet
-  HIP_TRY(hipMemsetAsync(c->bsState.p, 0, 64, s));
-  wp.map = (uint32_t *)c->bsMap.p; wp.state = (uint32_t *)c->bsState.p;
+  if ((r = c->stream.bsMap.ensure(mapBytes)) != limg_hip_success) return r;
+  if ((r = c->stream.bsState.ensure(64)) != limg_hip_success) return r;
+  HIP_TRY(hipMemsetAsync(c->stream.bsMap.p, 0xFF, mapBytes, s)); // no block has a rectangle yet
+  HIP_TRY(hipMemsetAsync(c->stream.bsState.p, 0, 64, s));
+  wp.map = (uint32_t *)c->stream.bsMap.p; wp.state = (uint32_t *)c->stream.bsState.p;
   launch_blocked_stream_window_decode(wp, device_cus(c), s);
   HIP_TRY(hipGetLastError());
   return limg_hip_success;
@@ -167,13 +167,13 @@ namespace
     if ((r = v.info(pStream, streamBytes, &sizeX, &sizeY, &total)) != limg_hip_success) return r;
     if (total > streamBytes || !window_inside(sizeX, sizeY, w)) return limg_hip_error_OutOfBounds;
     HIP_TRY(hipSetDevice(c->device));
-    if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
-    if ((r = c->planes.ensure(width * height * 4)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice));
-    if ((r = decode_window_device(c, v, (const uint8_t *)c->streamBuf.p, total, sizeX, sizeY, x0, y0, width, height, (uint32_t *)c->planes.p, width, nullptr)) != limg_hip_success)
+    if ((r = c->stream.buf.ensure(total + 16)) != limg_hip_success) return r;
+    if ((r = c->host.planes.ensure(width * height * 4)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->stream.buf.p, pStream, total, hipMemcpyHostToDevice));
+    if ((r = decode_window_device(c, v, (const uint8_t *)c->stream.buf.p, total, sizeX, sizeY, x0, y0, width, height, (uint32_t *)c->host.planes.p, width, nullptr)) != limg_hip_success)
       return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy2D(pOut, outStridePixels * 4, c->planes.p, width * 4, width * 4, height, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(pOut, outStridePixels * 4, c->host.planes.p, width * 4, width * 4, height, hipMemcpyDeviceToHost));
     return limg_hip_success;
   }
 
@@ -219,14 +219,14 @@ namespace
     const size_t oGroupJobs = rects ? align16(oGroups + count * sizeof(WindowGroup)) : oGroups, oItemBase = rects ? align16(oGroupJobs + count * 4) : oGroups;
     const size_t upload = rects ? align16(oItemBase + (count + 1) * 4) : oGroups;
     const size_t oState = upload, oMap = align16(oState + (rects ? count * 8 : 0)), total = oMap + (rects ? (size_t)blocks * 4 : 0);
-    limg_hip_context::WindowSlot &slot = c->windowSlots[c->windowSlotNext];
-    c->windowSlotNext = (c->windowSlotNext + 1) % limg_hip_context::kWindowSlots;
+    limg_hip_context::WindowSlot &slot = c->window.slots[c->window.next];
+    c->window.next = (c->window.next + 1) % limg_hip_context::kWindowSlots;
     if (slot.busy)
     { // the call that used this slot last: its copy has left the pinned table and its kernels are done with the device copy
       HIP_TRY(hipEventSynchronize(slot.done));
       slot.busy = false;
     }
-    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    if ((r = slot.done.ensure(hipEventDisableTiming)) != limg_hip_success) return r;
     if ((r = slot.host.ensure(upload)) != limg_hip_success) return r;
     if ((r = slot.dev.ensure(total)) != limg_hip_success) return r;
     uint8_t *hb = (uint8_t *)slot.host.p, *db = (uint8_t *)slot.dev.p;
@@ -238,7 +238,7 @@ namespace
     for (size_t i = 0; i < count; i++)
     {
       (void)fill(pJobs[i], jobs[i]);
-      jobs[i].status = (uint32_t *)c->streamStatus.p;
+      jobs[i].status = (uint32_t *)c->stream.status.p;
       if (rects)
       {
         jobs[i].state = (uint32_t *)(db + oState) + 2 * i;
@@ -253,7 +253,7 @@ namespace
     memset(&b, 0, sizeof(b));
     b.jobs = (const WindowDecodeParams *)(db + oJobs); b.unitBase = (const uint32_t *)(db + oUnitBase);
     b.count = (uint32_t)count; b.totalUnits = unitAt;
-    b.status = (uint32_t *)c->streamStatus.p; b.jobStatus = pJobStatus;
+    b.status = (uint32_t *)c->stream.status.p; b.jobStatus = pJobStatus;
     if (rects)
     { // groups: the jobs sorted by stream (in place, in the table: no allocation), then one group per run of equal keys
       WindowGroup *groups = (WindowGroup *)(hb + oGroups);
@@ -341,15 +341,15 @@ namespace
     if (!jobs) return limg_hip_error_MemoryAllocationFailure;
     struct Free { JOB *p; ~Free() { delete[] p; } } freeJobs = { jobs };
     HIP_TRY(hipSetDevice(c->device));
-    if ((r = c->streamBuf.ensure(total + 16)) != limg_hip_success) return r;
-    if ((r = c->planes.ensure(elems * eb)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(c->streamBuf.p, pStream, total, hipMemcpyHostToDevice)); // once, for all windows
+    if ((r = c->stream.buf.ensure(total + 16)) != limg_hip_success) return r;
+    if ((r = c->host.planes.ensure(elems * eb)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->stream.buf.p, pStream, total, hipMemcpyHostToDevice)); // once, for all windows
     size_t at = 0;
     for (size_t i = 0; i < count; i++)
     {
-      jobs[i].pStream = (const uint8_t *)c->streamBuf.p; jobs[i].streamBytes = total; jobs[i].sizeX = sizeX; jobs[i].sizeY = sizeY;
+      jobs[i].pStream = (const uint8_t *)c->stream.buf.p; jobs[i].streamBytes = total; jobs[i].sizeX = sizeX; jobs[i].sizeY = sizeY;
       jobs[i].window = pWindows[i];
-      stage_window(jobs[i].window, (uint8_t *)c->planes.p + at * eb);
+      stage_window(jobs[i].window, (uint8_t *)c->host.planes.p + at * eb);
       at += (planes * pWindows[i].width * pWindows[i].height + per - 1) / per * per;
     }
     if ((r = decode_windows_device(c, v, jobs, count, pFormat, nullptr, nullptr)) != limg_hip_success) return r;

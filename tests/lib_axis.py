@@ -29,6 +29,10 @@ HOOK_ONLY = {
     "test_gpu_fullsize.py::test_one_strip_base_error_is_caught": "base_error_strip hook: the sensitivity of the hash pin to one wrong chain base",
     "test_gpu_blocked.py::test_similarity_bits_equal_host_evaluation_with_and_without_the_bound": "blocked_no_bound hook: A/B of the match kernel's bounds",
     "test_gpu_blocked.py::test_large_first_order_and_vector_stores_change_nothing": "blocked_no_order / blocked_no_vec_store hooks: A/B of the store ordering",
+    "test_gpu_context_resources.py::test_every_family_then_close": "limg_hip_test_live_resources hook: the counts of live GPU resources, which the product does not keep",
+    "test_gpu_context_resources.py::test_two_contexts": "limg_hip_test_live_resources hook: the counts of live GPU resources, which the product does not keep",
+    "test_gpu_context_resources.py::test_unused_context": "limg_hip_test_live_resources hook: the counts of live GPU resources, which the product does not keep",
+    "test_gpu_context_resources.py::test_open_encode_close_cycles": "limg_hip_test_live_resources hook: the counts of live GPU resources, which the product does not keep",
 }
 
 # GPU tests without the axis because they do not encode in this process on a library of their choosing: they start programs that load the product themselves, or
