@@ -44,13 +44,6 @@ namespace limg_hip
 
 namespace
 {
-  uint32_t chain_of_row(const Partition &pt, uint32_t row)
-  {
-    if (pt.chainCount <= 1 || pt.chainRows == 0) return 0;
-    const uint32_t c = row / pt.chainRows;
-    return c < pt.chainCount - 1 ? c : pt.chainCount - 1;
-  }
-
   // The accurate search's automaton (tools/make_search_table.py, src/limg_bit_crush.h:668-830) in the form the kernel's scalar loads want: 8 dwords per state,
   // every field in a dword of its own = { a | phase2 << 5 | final << 31, byte offset on pass, byte offset on fail, b, c, mul(a), mul(b), mul(c) }.  Bits 24..26 of the two
   // offsets say which factors' shifts the SUCCESSOR's triple changes against this state's (A, B, C): a state of this DAG has several predecessors, so the change mask is a
@@ -471,7 +464,7 @@ namespace
     xb.streamRaw = x.streamRaw; xb.inner = true; xb.marks = 0; xb.scratchRow0 = blocksY - 1; xb.scratchRows = blocksY;
     const Partition one = { 1, 0 };
     xb.part = &one;
-    const bool sameChain = chain_of_row(pt, (uint32_t)blocksY - 1) == chain_of_row(pt, (uint32_t)blocksY - 2);
+    const bool sameChain = chain_of_row(pt.chainCount, pt.chainRows, (uint32_t)blocksY - 1) == chain_of_row(pt.chainCount, pt.chainRows, (uint32_t)blocksY - 2);
     if (sameChain) xb.dPrevDesc = (const unsigned long long *)((const uint8_t *)c->enc.lookback.p + 16) + ((blocksY - 1) * stripsX - 1);
     if ((r = encode_device(c, dIn + topY * sizeX, sizeX, sizeY - topY, hasAlpha, &low, compact, errorFactor, 0, fast, stream, xb)) != limg_hip_success) return r;
     mark(c, stream);

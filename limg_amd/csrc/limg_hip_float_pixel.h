@@ -1,5 +1,6 @@
-// limg_hip_float_pixel.h -- parts of the E step's lane == pixel float stage (a4-a6), which images with partial edge blocks keep: the per-block LDS state
-// (BlkF, and the phase-E view BlkE that overlays it) and the pixel-order direction sums (serial_sums2).  Phases A-D themselves are inline in fit_search_strip.
+// limg_hip_float_pixel.h -- the E step's lane == pixel float stage (a4-a6), which images with partial edge blocks keep: the per-block LDS state (BlkF, and the
+// phase-E view BlkE that overlays it), what every stage of the E step knows of its strip (EStrip, block_geom, block_pixel) and the pixel-order direction sums
+// (serial_sums2).  Phases A-D themselves are inline in fit_search_strip: as a function of their own they cost the instances that run them 5 % (see there).
 // Included by limg_hip_kernels.hip only, which stays one translation unit (its per-source compile flags cover this code).
 #ifndef LIMG_HIP_FLOAT_PIXEL_H
 #define LIMG_HIP_FLOAT_PIXEL_H
@@ -32,6 +33,42 @@ namespace limg_hip
     };
     static_assert(sizeof(BlkE) <= 120, "BlkE must fit the dead float-stage fields");
     static_assert(sizeof(BlkF) == 192, "BlkF layout");
+
+    // What every stage of the E step (fit_search_strip, limg_hip_kernels.hip) knows of its work strip: geometry (wave-uniform), the thread, the LDS areas.
+    // The stages take it BY VALUE: a stage is optimised on its own before it is inlined, and behind a reference every LDS store in it might alias these fields
+    // (measured on the compiler's metadata: by reference the split path's lane == pixel instances take 2 more VGPRs).
+    struct EStrip
+    {
+      uint32_t strip, by, byS; // the strip's place in its block row, its block row in the image, and in the per-block scratch arrays (records, shift words)
+      uint32_t x0, y0, stripW, ry; // pixels: origin, width and rows inside the image
+      int tid, lane, wave;
+      uint32_t *pix;   // [8 rows][kRowDw] the strip's pixels
+      float *V;        // the parked contributions of the float stage (all waves); later the factor-byte staging area
+      BlkF *blk;       // [kStripBlocks]
+      uint32_t *calls; // 4 per-wave call counts + the phase-E block queue
+      int *trialc;     // PREFIT: [kStripBlocks][kTrialConstDw]
+    };
+
+    // geometry of block sb of the strip (wave-uniform): its width and pixel count; false: past the image's right edge
+    template <class P>
+    __device__ __forceinline__ bool block_geom(const P &p, const EStrip g, const uint32_t sb, uint32_t &rx, uint32_t &n)
+    {
+      const uint32_t bx = g.strip * kStripBlocks + sb;
+      if (bx >= p.blocksX) { rx = 0; n = 0; return false; }
+      rx = min(p.sizeX - bx * kBlock, (uint32_t)kBlock);
+      n = rx * g.ry;
+      return true;
+    }
+
+    // lane == pixel: the lane's pixel of block sb (0 for lanes past the block's n pixels) and its position inside the block
+    __device__ __forceinline__ uint32_t block_pixel(const EStrip g, const uint32_t sb, const uint32_t rx, const uint32_t n, uint32_t &lx, uint32_t &ly)
+    {
+      const int lane = g.lane;
+      if (rx == 8) { lx = lane & 7; ly = lane >> 3; }
+      else { const uint32_t l = (uint32_t)lane < n ? (uint32_t)lane : 0u; ly = l / rx; lx = l - ly * rx; }
+      const uint32_t px = g.pix[ly * kRowDw + sb * kBlock + lx];
+      return (uint32_t)lane < n ? px : 0u;
+    }
 
     enum : int { kDirA = 0, kDirB = 1, kDirC = 2 };
     constexpr int kBatch = 4; // blocks per wave whose pass contributions are parked at a time

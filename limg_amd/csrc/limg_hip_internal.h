@@ -19,6 +19,17 @@ namespace limg_hip
   constexpr int kBlocksPerWave = 8; // kStripBlocks / kWaves: a wave's blocks in the E step's float stage and the F step
   constexpr uint64_t kDitherSeed = 0xCA7F00D15BADF00DULL; // reference: src/limg.cpp:1893
 
+  // The dither chain partition (reference: src/limg.cpp:2114-2134) in block rows, stated once for the host and the kernels: chain c (< chainCount - 1) owns block
+  // rows [c * chainRows, (c + 1) * chainRows), the last chain owns the rest; chainCount <= 1 or chainRows == 0 is one chain.
+  __host__ __device__ inline uint32_t chain_of_row(uint32_t chainCount, uint32_t chainRows, uint32_t row)
+  {
+    if (chainCount <= 1 || chainRows == 0) return 0u;
+    const uint32_t c = row / chainRows;
+    return c < chainCount - 1 ? c : chainCount - 1;
+  }
+  // ... and the first block row of the chain that `row` belongs to (its strips' look-back ends there; the row above is no predecessor of its blocks)
+  __host__ __device__ inline uint32_t chain_head_row(uint32_t chainCount, uint32_t chainRows, uint32_t row) { return chain_of_row(chainCount, chainRows, row) * chainRows; }
+
   // The caller's pointers of one image: input pixels and the 11 output planes.  A batched encode (limg_hip_encode3d_batch_device) holds one of these per image
   // in a device table; the kernels read them with scalar loads where they use them.
   struct ImageIO

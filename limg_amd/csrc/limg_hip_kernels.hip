@@ -32,12 +32,16 @@
 //     chains at once instead of a 64-step dependent chain per block;
 //   * correctly rounded division (hipcc default), once per batch and lane-parallel; round-to-nearest-even conversions.
 //
-// This file holds the E step (fit_search_strip), the split path's scan, the F step (dither_store_strip), the kernels and their launchers.  The parts
-// they are built from live in headers that only this file includes, so that all of it stays one translation unit under this file's compile flags:
+// This file holds the E step -- its stages (request_prefit_records / take_prefit_records, stage_strip_pixels, phase_e_view, pixel_factors, finish_block,
+// publish_strip, park_or_store_factors) and fit_search_strip, which calls them in order around the strip's block queue and keeps the lane == pixel float stage and
+// the search's set-up inline --, the split path's scan, the F step
+// (dither_store_strip), the kernels and their launchers.  The parts they are built from live in headers that only this file includes, so that all of it stays one
+// translation unit under this file's compile flags:
 //   limg_hip_search.h      the packed trial, the two search automata, the generic-path search
-//   limg_hip_phase_f.h     the F step's parts: LDS areas, preparation, plane stores, the rows / pixels phases, first dither calls
-//   limg_hip_float_pixel.h the lane == pixel float stage's per-block state and direction sums
+//   limg_hip_phase_f.h     the F step's parts: LDS areas, the factor-plane copy, preparation, plane stores, the rows / pixels phases, first dither calls
+//   limg_hip_float_pixel.h the E step's view of its strip (EStrip), the per-block LDS state, and the lane == pixel float stage's direction sums (serial_sums2)
 //   limg_hip_lookback.h    the decoupled look-back over the per-strip dither-call counts
+// The dither chain partition (which chain a block row belongs to, which row heads it) is chain_of_row / chain_head_row in limg_hip_internal.h, shared with the host.
 #include "limg_hip_search.h"
 #include "limg_hip_phase_f.h"
 #include "limg_hip_float_pixel.h"
@@ -76,59 +80,40 @@ namespace limg_hip
     // parked results of one strip (persistent kernel): pre-dither factor bytes, records (int16 part), shift words
     constexpr int kParkFac = 0, kParkRec = 6144, kParkShift = 6144 + 1536, kParkBytes = 8192;
 
-    // PREFIT: the float stage already ran in k_fit_tpb (limg_hip_fit_tpb.hip, one lane per block); this step loads the records and goes on with phase E.
-    // id: the strip's number in ticket / look-back order (all images of a batch); local: its number inside its image (geometry); rowBase: the image's first
-    // block row in the per-block scratch arrays; head0: the id of the image's first strip
-    // ACC: the accurate search (fastBitCrushing == false) instead of the default one -- a kernel variant of its own, so that neither search's registers and code
-    // weigh on the other
-    template <int CH, bool PERSIST, bool FAST, bool PREFIT, bool ACC, class P, class IO>
-    __device__ __forceinline__ void fit_search_strip(const P &p, const IO &io, const uint32_t id, const uint32_t local, const uint32_t rowBase, const uint32_t head0, uint8_t *lds,
-                                                     uint8_t *park, const int tid)
+    // ---- the E step's stages, in the order fit_search_strip calls them (tools/isa_budget.py attributes the kernel's instructions to them by function) ----------
+
+    // E: record load + flags (PREFIT), first half.  The records of the wave's 8 blocks as k_fit_tpb left them (16 dwords per block: avg, then the 24 int16; 16 lanes
+    // per block) are REQUESTED here, next to the strip's pixels, and used behind the barrier below: one memory round trip per strip instead of two.  Round 4, same-box A/B (tools/r04/run19.sh): persistent
+    // kernel 1.079-1.085 -> 1.054-1.059 ms on 8192^2 photo-noise, config 4 15.01-15.13 -> 14.46-14.65 ms.  (The same idea for the F step -- the strip's own look-back
+    // descriptor and the first window requested before the parked data -- costs 4 spilled registers and was measured 0.5-1 % slower: not kept.)
+    template <class P>
+    __device__ __forceinline__ void request_prefit_records(const P &p, const EStrip g, uint32_t recVal[2])
     {
-      // the 4 KiB RSQRTPS table is read straight from global memory (it lives in the CU's vector L1): keeping a copy in LDS would
-      // cost the fifth workgroup per CU
-      const unsigned short *s_rsq = d_rsqrt_x86_tab;
-      uint32_t *s_strip = reinterpret_cast<uint32_t *>(lds + kLdsStrip);
-      constexpr LdsLayout LL = lds_layout<PREFIT>();
-      float *s_V = reinterpret_cast<float *>(lds + LL.v);
-      BlkF *s_blk = reinterpret_cast<BlkF *>(lds + LL.blk);
-      uint32_t *s_calls = reinterpret_cast<uint32_t *>(lds + LL.calls);
-      int *s_trialc = reinterpret_cast<int *>(lds + LL.trialc);
-
-      const int lane = tid & 63, wave = tid >> 6;
-      const uint32_t strip = local % p.stripsX, by = local / p.stripsX;
-      const uint32_t byS = rowBase + by; // block row in the per-block scratch arrays (records, shift words)
-      const uint32_t x0 = strip * (kStripBlocks * kBlock), y0 = by * kBlock;
-      const uint32_t stripW = min(p.sizeX - x0, (uint32_t)(kStripBlocks * kBlock)); // pixels
-      const uint32_t ry = min(p.sizeY - y0, (uint32_t)kBlock);
-
-      // PREFIT: the records of the wave's 8 blocks as k_fit_tpb left them (16 dwords per block: avg, then the 24 int16; 16 lanes per block) are REQUESTED here, next to
-      // the strip's pixels, and used behind the barrier below: one memory round trip per strip instead of two.  Round 4, same-box A/B (tools/r04/run19.sh): persistent
-      // kernel 1.079-1.085 -> 1.054-1.059 ms on 8192^2 photo-noise, config 4 15.01-15.13 -> 14.46-14.65 ms.  (The same idea for the F step -- the strip's own look-back
-      // descriptor and the first window requested before the parked data -- costs 4 spilled registers and was measured 0.5-1 % slower: not kept.)
-      uint32_t recVal[2] = { 0u, 0u };
-      if (PREFIT)
-      {
 #pragma unroll
-        for (int r = 0; r < 2; r++)
-        {
-          const int b = r * 4 + (lane >> 4), w = lane & 15;
-          const uint32_t bx = strip * kStripBlocks + wave * kBlocksPerWave + b;
-          if (bx < p.blocksX) recVal[r] = w >= 4 ? reinterpret_cast<const uint32_t *>(p.records + (size_t)byS * p.blocksX + bx)[w] // (the averages in words 0..3 are not needed here)
-                                                 : reinterpret_cast<const uint32_t *>(p.invN)[((size_t)byS * p.blocksX + bx) * 4 + w];      // 1 / |n|^2 of A, B, C from k_fit_tpb
-        }
+      for (int r = 0; r < 2; r++)
+      {
+        const int b = r * 4 + (g.lane >> 4), w = g.lane & 15;
+        const uint32_t bx = g.strip * kStripBlocks + g.wave * kBlocksPerWave + b;
+        if (bx < p.blocksX) recVal[r] = w >= 4 ? reinterpret_cast<const uint32_t *>(p.records + (size_t)g.byS * p.blocksX + bx)[w] // (the averages in words 0..3 are not needed here)
+                                               : reinterpret_cast<const uint32_t *>(p.invN)[((size_t)g.byS * p.blocksX + bx) * 4 + w];      // 1 / |n|^2 of A, B, C from k_fit_tpb
       }
-      // ---- stage: the strip's pixel rows into LDS (the rsqrt table is loaded by the caller) ----------------------------
+    }
+
+    // E: strip staging -- the strip's pixel rows into LDS (the rsqrt table is read from global memory where it is used)
+    template <class P, class IO>
+    __device__ __forceinline__ void stage_strip_pixels(const P &p, const IO &io, const EStrip g)
+    {
+      const int tid = g.tid;
       if (p.vecIn)
       {
 #pragma unroll
         for (int pass = 0; pass < 2; pass++)
         {
           const uint32_t row = pass * 4 + (tid >> 6), col = (tid & 63) * 4; // 4 px per lane
-          if (row < ry && col < stripW)
+          if (row < g.ry && col < g.stripW)
           {
-            const uint4 v = *reinterpret_cast<const uint4 *>(io.in + (size_t)(y0 + row) * p.sizeX + x0 + col); // (as a non-temporal load: measured, no difference -- tools/r05/ab_nt_loads.sh)
-            *reinterpret_cast<uint4 *>(&s_strip[row * kRowDw + col]) = v;
+            const uint4 v = *reinterpret_cast<const uint4 *>(io.in + (size_t)(g.y0 + row) * p.sizeX + g.x0 + col); // (as a non-temporal load: measured, no difference -- tools/r05/ab_nt_loads.sh)
+            *reinterpret_cast<uint4 *>(&g.pix[row * kRowDw + col]) = v;
           }
         }
       }
@@ -137,51 +122,210 @@ namespace limg_hip
         for (uint32_t i = tid; i < 8 * 256; i += kThreads)
         {
           const uint32_t row = i >> 8, col = i & 255;
-          if (row < ry && col < stripW) s_strip[row * kRowDw + col] = io.in[(size_t)(y0 + row) * p.sizeX + x0 + col];
+          if (row < g.ry && col < g.stripW) g.pix[row * kRowDw + col] = io.in[(size_t)(g.y0 + row) * p.sizeX + g.x0 + col];
         }
       }
-      __syncthreads();
+    }
 
-      float *V = s_V + wave * kBatch * kVDw;
-      BlkF *blk = s_blk + wave * kBlocksPerWave;
-
-      // per-block geometry (wave-uniform)
-      auto geom = [&](int b, uint32_t &rx, uint32_t &n) -> bool
-      {
-        const uint32_t bx = strip * kStripBlocks + wave * kBlocksPerWave + b;
-        if (bx >= p.blocksX) { rx = 0; n = 0; return false; }
-        rx = min(p.sizeX - bx * kBlock, (uint32_t)kBlock);
-        n = rx * ry;
-        return true;
-      };
-
-      if (PREFIT)
-      {
-        // the records requested above: into the phase-E view, the park slot, and the range flags
+    // E: record load + flags (PREFIT), second half -- the records requested above: into the phase-E view, the park slot, and the range flags
+    template <bool PERSIST, class P>
+    __device__ __forceinline__ void take_prefit_records(const P &p, const EStrip g, const uint32_t recVal[2], uint8_t *park)
+    {
+      BlkF *blk = g.blk + g.wave * kBlocksPerWave;
 #pragma unroll
-        for (int r = 0; r < 2; r++)
-        {
-          const int b = r * 4 + (lane >> 4), w = lane & 15;
-          const uint32_t sb = wave * kBlocksPerWave + b, bx = strip * kStripBlocks + sb;
-          const uint32_t val = recVal[r];
-          if (w < 3) reinterpret_cast<BlkE *>(&blk[b])->invN[w] = __uint_as_float(val); // its place in the phase-E view (nothing else of the float-stage fields is live with PREFIT)
-          if (w >= 4)
-          {
-            reinterpret_cast<uint32_t *>(blk[b].rec)[w - 4] = val;
-            if (PERSIST) reinterpret_cast<uint32_t *>(park + kParkRec)[sb * 12 + (w - 4)] = val;
-          }
-          const int lo = (int)(int16_t)(val & 0xFFFFu), hi = (int)(int16_t)(val >> 16);
-          uint32_t big = (w >= 4 && (lo > p.recordLimit || lo < -p.recordLimit || hi > p.recordLimit || hi < -p.recordLimit)) ? 1u : 0u;
-          big |= (uint32_t)dpp<0xB1, 0xF>(0, (int)big);  // OR over the block's 16 lanes (one DPP row)
-          big |= (uint32_t)dpp<0x4E, 0xF>(0, (int)big);
-          big |= (uint32_t)dpp<0x141, 0xF>(0, (int)big);
-          big |= (uint32_t)dpp<0x140, 0xF>(0, (int)big);
-          if (w == 0) { blk[b].flags = (bx < p.blocksX ? kValid : 0u) | (big ? kBig : 0u); blk[b].n = bx < p.blocksX ? 64u : 0u; }
-        }
-        wave_lds_fence();
-      }
-      else
+      for (int r = 0; r < 2; r++)
       {
+        const int b = r * 4 + (g.lane >> 4), w = g.lane & 15;
+        const uint32_t sb = g.wave * kBlocksPerWave + b, bx = g.strip * kStripBlocks + sb;
+        const uint32_t val = recVal[r];
+        if (w < 3) reinterpret_cast<BlkE *>(&blk[b])->invN[w] = __uint_as_float(val); // its place in the phase-E view (nothing else of the float-stage fields is live with PREFIT)
+        if (w >= 4)
+        {
+          reinterpret_cast<uint32_t *>(blk[b].rec)[w - 4] = val;
+          if (PERSIST) reinterpret_cast<uint32_t *>(park + kParkRec)[sb * 12 + (w - 4)] = val;
+        }
+        const int lo = (int)(int16_t)(val & 0xFFFFu), hi = (int)(int16_t)(val >> 16);
+        uint32_t big = (w >= 4 && (lo > p.recordLimit || lo < -p.recordLimit || hi > p.recordLimit || hi < -p.recordLimit)) ? 1u : 0u;
+        big |= (uint32_t)dpp<0xB1, 0xF>(0, (int)big);  // OR over the block's 16 lanes (one DPP row)
+        big |= (uint32_t)dpp<0x4E, 0xF>(0, (int)big);
+        big |= (uint32_t)dpp<0x141, 0xF>(0, (int)big);
+        big |= (uint32_t)dpp<0x140, 0xF>(0, (int)big);
+        if (w == 0) { blk[b].flags = (bx < p.blocksX ? kValid : 0u) | (big ? kBig : 0u); blk[b].n = bx < p.blocksX ? 64u : 0u; }
+      }
+      wave_lds_fence();
+    }
+
+    // E: phase-E view + trial constants (a7).  The view overlays the dead float-stage fields: float normals / offsets and 1 / |n|^2 in the serial limg_dot
+    // order (src/limg_internal.h:426-452).  One lane per (block, factor, channel): 96 of 128 lane slots.
+    template <int CH, bool FAST, bool PREFIT>
+    __device__ __forceinline__ void phase_e_view(const EStrip g)
+    {
+      const int lane = g.lane;
+      BlkF *blk = g.blk + g.wave * kBlocksPerWave;
+      float nrm[2], off[2], invn[2];
+#pragma unroll
+      for (int r = 0; r < 2; r++)
+      {
+        const int idx = min(r * 64 + lane, 95);
+        const int b = idx / 12, fc = idx - b * 12, f = fc >> 2, c = fc & 3;
+        const int lo = blk[b].rec[f * 8 + c], hi = blk[b].rec[f * 8 + 4 + c];
+        nrm[r] = (float)(hi - lo); off[r] = (float)lo;
+        if (PREFIT) { invn[r] = 0.0f; continue; } // k_fit_tpb left 1 / |n|^2 with the record
+        const float sq = nrm[r] * nrm[r];
+        const float s0 = __int_as_float(dpp<0x00, 0xF>(0, __float_as_int(sq))), s1 = __int_as_float(dpp<0x55, 0xF>(0, __float_as_int(sq)));
+        const float s2 = __int_as_float(dpp<0xAA, 0xF>(0, __float_as_int(sq))), s3 = __int_as_float(dpp<0xFF, 0xF>(0, __float_as_int(sq)));
+        float s = ((0.0f + s0) + s1) + s2;
+        if (CH == 4) s = s + s3;
+        const bool nz = (s0 != 0.0f) || (s1 != 0.0f) || (s2 != 0.0f) || (CH == 4 && s3 != 0.0f);
+        invn[r] = nz ? (FAST ? __builtin_amdgcn_rcpf(s) : 1.0f / s) : 0.0f;
+      }
+      wave_lds_fence(); // every lane has read what it needs of the float-stage fields before the overlay is written
+#pragma unroll
+      for (int r = 0; r < 2; r++)
+      {
+        const int idx = r * 64 + lane;
+        if (idx < 96)
+        {
+          const int b = idx / 12, fc = idx - b * 12, f = fc >> 2, c = fc & 3;
+          BlkE *e = reinterpret_cast<BlkE *>(&blk[b]);
+          e->nrm[f][slot_of(c)] = nrm[r]; e->off[f][slot_of(c)] = off[r]; // slot order x0 x2 x1 x3, see V4
+          if (!PREFIT && c == 0) e->invN[f] = invn[r];
+          if (PREFIT && c < 3)
+          { // the packed trial's integer operands (negated, see "a9, packed form"), once per block here instead of per lane in phase E
+            int *tc = g.trialc + (g.wave * kBlocksPerWave + b) * kTrialConstDw;
+            tc[f * 3 + c] = -(int)nrm[r];
+            tc[9 + f * 3 + c] = term_const(f, c, (int)off[r]);
+          }
+        }
+      }
+    }
+
+    // E: per-pixel factors, a8 (src/limg_factorization.h:149-197): fa = ((px - Amin) . nA) * invA, est = Amin + nA * fa, fb from px - est - Boff, ...
+    template <int CH, bool FAST>
+    __device__ __forceinline__ void pixel_factors(const BlkE *be, const uint32_t px, uint32_t &fA, uint32_t &fB, uint32_t &fC)
+    {
+      const V4 pv = px_to_v4(px);
+      const V4 nA = ld4(be->nrm[0]), mnA = ld4(be->off[0]);
+      const float fa = dp4<CH, FAST>(pv - mnA, nA) * be->invN[0];
+      fA = cvt_u8_rne_sat(255.0f * fa);
+      const V4 nB = ld4(be->nrm[1]), ofB = ld4(be->off[1]);
+      V4 est = mnA + nA * fa;
+      const float fb = dp4<CH, FAST>((pv - est) - ofB, nB) * be->invN[1];
+      fB = cvt_u8_rne_sat(255.0f * fb);
+      const V4 nC = ld4(be->nrm[2]), ofC = ld4(be->off[2]);
+      est = est + nB * fb;
+      const float fc = dp4<CH, FAST>((pv - est) - ofC, nC) * be->invN[2];
+      fC = cvt_u8_rne_sat(255.0f * fc);
+    }
+
+
+    // E: block epilogue -- the block's dither calls and payload words into the wave's counter, its shift word to the park slot / the raster-order array, its
+    // factor bytes to the staging area ([3 planes][8 rows][256 px] at the F step's strides)
+    template <int CH, bool PERSIST, class P>
+    __device__ __forceinline__ void finish_block(const P &p, const EStrip g, const uint32_t sb, const uint32_t bx, const BlkF *blkE, const uint32_t shift[3], const uint32_t fA,
+                                                 const uint32_t fB, const uint32_t fC, const bool active, const uint32_t o, uint8_t *park, uint8_t *stage, uint32_t &waveCalls)
+    {
+      // dither calls this block will make (src/limg.cpp:1951-1958)
+      // a shift of 1..7 dithers (one call), 0 and 8 do not; as scalar arithmetic -- ((s & 7) + 7) >> 3 -- because a boolean would go through a lane mask and a vector select
+      const uint32_t calls = (((shift[0] & 7u) + 7u) >> 3) + (((shift[1] & 7u) + 7u) >> 3) + (((shift[2] & 7u) + 7u) >> 3);
+      waveCalls += calls;
+      if (p.stripWords)
+      { // stream mode: the block's payload size in 8-byte words rides in bits 8.. of the same per-wave counter (calls of a strip stay below 256): a field of 8 - shift
+        // bits per pixel is that many words; a factor at shift 8 has none unless its alpha normal is non-zero (raw-byte escape, limg_hip_stream.hip)
+        uint32_t words = 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+        {
+          const uint32_t sk = shift[k];
+          if (sk < 8u) words += 8u - sk;
+          else if (CH == 4 && sgpr((int)blkE->rec[8 * k + 3]) != sgpr((int)blkE->rec[8 * k + 7])) words += 8u;
+        }
+        waveCalls += words << 8;
+      }
+
+      const size_t bi = (size_t)g.byS * p.blocksX + bx;
+      const uint32_t word = shift[0] | (shift[1] << 8) | (shift[2] << 16) | (calls << 24);
+      if (g.lane == 0)
+      {
+        if (!PERSIST || p.compactOut) p.shifts[bi] = word;
+        if (PERSIST) reinterpret_cast<uint32_t *>(park + kParkShift)[sb] = word;
+      }
+      if (p.storePlanes && active) { stage[o] = (uint8_t)fA; stage[kFacPlane + o] = (uint8_t)fB; stage[2 * kFacPlane + o] = (uint8_t)fC; }
+    }
+
+    // E: strip epilogue, the strip's dither-call count (thread 0, behind the barrier that follows the block loop): to the look-back descriptor or to k_strip_scan
+    template <bool PERSIST, class P>
+    __device__ __forceinline__ void publish_strip(const P &p, const EStrip g, const uint32_t id, const uint32_t head0)
+    {
+      const uint32_t aggAll = g.calls[0] + g.calls[1] + g.calls[2] + g.calls[3];
+      const uint32_t agg = aggAll & 0xFFu; // (bits 8..: the strip's payload words, stream mode)
+      if (p.stripWords) p.stripWords[id] = aggAll >> 8;
+      if (PERSIST)
+      { // publish the count; if the predecessor's inclusive count is already there, publish ours as inclusive right away
+        const uint32_t headId = head0 + chain_head_row(p.chainCount, p.chainRows, g.by) * p.stripsX;
+#ifdef LIMG_HIP_TEST_HOOKS
+        if (id == p.testSkipStrip) {} // (test build: a strip that never publishes)
+        else
+#endif
+        if (id == headId) desc_store(p.desc + id, kDescInclusive, agg);
+        else
+        {
+          const unsigned long long d = desc_load(p.desc + id - 1);
+          if ((uint32_t)(d >> 32) == kDescInclusive) desc_store(p.desc + id, kDescInclusive, (uint32_t)d == kBasePoison ? kBasePoison : (uint32_t)d + agg);
+          else desc_store(p.desc + id, kDescAggregate, agg);
+        }
+      }
+      else p.stripCalls[id] = agg;
+    }
+
+    // E: strip epilogue, the strip's pre-dither factor bytes: parked (persistent kernel: private, L2-resident scratch; same workgroup reads them back) or stored to
+    // the caller's factor planes (split path: rewritten in place by k_dither_store)
+    template <bool PERSIST, class P, class IO>
+    __device__ __forceinline__ void park_or_store_factors(const P &p, const IO &io, const EStrip g, uint8_t *park, uint8_t *stage)
+    {
+      if (PERSIST)
+        for (int i = g.tid; i < 384; i += kThreads) reinterpret_cast<uint4 *>(park + kParkFac)[i] = *reinterpret_cast<const uint4 *>(stage + (i >> 4) * kFacRow + (i & 15) * 16); // 24 rows of 256 bytes
+      else if (p.storePlanes) copy_factor_planes<true>(p, io, stage, g.x0, g.y0, g.stripW, g.ry, g.tid);
+    }
+
+    // PREFIT: the float stage already ran in k_fit_tpb (limg_hip_fit_tpb.hip, one lane per block); this step loads the records and goes on with phase E.
+    // id: the strip's number in ticket / look-back order (all images of a batch); local: its number inside its image (geometry); rowBase: the image's first
+    // block row in the per-block scratch arrays; head0: the id of the image's first strip
+    // ACC: the accurate search (fastBitCrushing == false) instead of the default one -- a kernel variant of its own, so that neither search's registers and code
+    // weigh on the other
+    // Two parts stay INLINE here, measured (profiles/e_step_stages_ab.md): as functions of their own (float_stage_pixel, search_block) the lane == pixel float stage and
+    // the search's set-up left the persistent kernel's lane == pixel instances with 11-46 more spilled SGPRs and 1.1-1.8 KB more code, `--legacy-float-stage` 5.3 %
+    // slower, and four k_fit_search instances with 2-4 more VGPRs; either one alone as a function does the same.
+    template <int CH, bool PERSIST, bool FAST, bool PREFIT, bool ACC, class P, class IO>
+    __device__ __forceinline__ void fit_search_strip(const P &p, const IO &io, const uint32_t id, const uint32_t local, const uint32_t rowBase, const uint32_t head0, uint8_t *lds,
+                                                     uint8_t *park, const int tid)
+    {
+      constexpr LdsLayout LL = lds_layout<PREFIT>();
+      EStrip g;
+      g.tid = tid; g.lane = tid & 63; g.wave = tid >> 6;
+      g.strip = local % p.stripsX; g.by = local / p.stripsX; g.byS = rowBase + g.by;
+      g.x0 = g.strip * (kStripBlocks * kBlock); g.y0 = g.by * kBlock;
+      g.stripW = min(p.sizeX - g.x0, (uint32_t)(kStripBlocks * kBlock)); g.ry = min(p.sizeY - g.y0, (uint32_t)kBlock);
+      g.pix = reinterpret_cast<uint32_t *>(lds + kLdsStrip); g.V = reinterpret_cast<float *>(lds + LL.v); g.blk = reinterpret_cast<BlkF *>(lds + LL.blk);
+      g.calls = reinterpret_cast<uint32_t *>(lds + LL.calls); g.trialc = reinterpret_cast<int *>(lds + LL.trialc);
+      const int lane = g.lane;
+
+      uint32_t recVal[2] = { 0u, 0u };
+      if (PREFIT) request_prefit_records(p, g, recVal);
+      stage_strip_pixels(p, io, g);
+      __syncthreads();
+      if (PREFIT) take_prefit_records<PERSIST>(p, g, recVal, park);
+      else
+      { // the lane == pixel float stage (a4-a6), inline: see the note above this function
+      // the 4 KiB RSQRTPS table is read straight from global memory (it lives in the CU's vector L1): keeping a copy in LDS would
+      // cost the fifth workgroup per CU
+      const unsigned short *s_rsq = d_rsqrt_x86_tab;
+      const int lane = g.lane, wave = g.wave;
+      const uint32_t strip = g.strip, by = g.by, byS = g.byS;
+      float *V = g.V + wave * kBatch * kVDw;
+      BlkF *blk = g.blk + wave * kBlocksPerWave;
+      auto geom = [&](int b, uint32_t &rx, uint32_t &n) -> bool { return block_geom(p, g, wave * kBlocksPerWave + b, rx, n); }; // per-block geometry (wave-uniform)
+
       // The float stage runs in batches of kBatch blocks per wave: the parked contributions of one batch are what limits the
       // workgroups per CU (LDS), and 4 blocks x 4 waves keep it at 5 workgroups per CU.
       // Per-block values of the batch stay in registers across the phases (the loops over i are fully unrolled).
@@ -207,10 +351,7 @@ namespace limg_hip
         }
         const uint32_t sb = wave * kBlocksPerWave + b;
         uint32_t lx, ly;
-        if (rx == 8) { lx = lane & 7; ly = lane >> 3; }
-        else { const uint32_t l = (uint32_t)lane < n ? (uint32_t)lane : 0u; ly = l / rx; lx = l - ly * rx; }
-        uint32_t px = s_strip[ly * kRowDw + sb * kBlock + lx];
-        px = (uint32_t)lane < n ? px : 0u;
+        const uint32_t px = block_pixel(g, sb, rx, n, lx, ly);
         px8[i] = px;
         const V4 pf = px_to_v4(px);
         uint32_t pxs = px;
@@ -220,9 +361,7 @@ namespace limg_hip
           // block in raster order is its left neighbour, or the last block of the row above for a one-block-wide image.  The first block of a strip
           // has no predecessor (uninitialised stack upstream): nothing is added then.
           const uint32_t bxx = strip * kStripBlocks + sb;
-          uint32_t chainStart = 0;
-          if (p.chainCount > 1 && p.chainRows != 0) chainStart = min(by / p.chainRows, p.chainCount - 1) * p.chainRows;
-          const bool hasPrev = bxx > 0 || by > chainStart;
+          const bool hasPrev = bxx > 0 || by > chain_head_row(p.chainCount, p.chainRows, by);
           if (hasPrev && (uint32_t)lane >= n && lane < 4)
           {
             const uint32_t pbx = bxx > 0 ? bxx - 1 : p.blocksX - 1, pby = bxx > 0 ? by : by - 1;
@@ -415,53 +554,15 @@ namespace limg_hip
           if (PERSIST && w >= 4) reinterpret_cast<uint32_t *>(park + kParkRec)[sb * 12 + (w - 4)] = val;
         }
       }
-      } // !PREFIT
-      if (!PERSIST && p.fitOnly) return; // pass 1 of the merged-block encoder: the records are all it needs (uniform for the workgroup)
-      // phase-E view (overlays the dead float-stage fields): float normals / offsets and 1 / |n|^2 in the serial limg_dot
-      // order (src/limg_internal.h:426-452).  One lane per (block, factor, channel): 96 of 128 lane slots.
-      {
-        float nrm[2], off[2], invn[2];
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-        {
-          const int idx = min(r * 64 + lane, 95);
-          const int b = idx / 12, fc = idx - b * 12, f = fc >> 2, c = fc & 3;
-          const int lo = blk[b].rec[f * 8 + c], hi = blk[b].rec[f * 8 + 4 + c];
-          nrm[r] = (float)(hi - lo); off[r] = (float)lo;
-          if (PREFIT) { invn[r] = 0.0f; continue; } // k_fit_tpb left 1 / |n|^2 with the record
-          const float sq = nrm[r] * nrm[r];
-          const float s0 = __int_as_float(dpp<0x00, 0xF>(0, __float_as_int(sq))), s1 = __int_as_float(dpp<0x55, 0xF>(0, __float_as_int(sq)));
-          const float s2 = __int_as_float(dpp<0xAA, 0xF>(0, __float_as_int(sq))), s3 = __int_as_float(dpp<0xFF, 0xF>(0, __float_as_int(sq)));
-          float s = ((0.0f + s0) + s1) + s2;
-          if (CH == 4) s = s + s3;
-          const bool nz = (s0 != 0.0f) || (s1 != 0.0f) || (s2 != 0.0f) || (CH == 4 && s3 != 0.0f);
-          invn[r] = nz ? (FAST ? __builtin_amdgcn_rcpf(s) : 1.0f / s) : 0.0f;
-        }
-        wave_lds_fence(); // every lane has read what it needs of the float-stage fields before the overlay is written
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-        {
-          const int idx = r * 64 + lane;
-          if (idx < 96)
-          {
-            const int b = idx / 12, fc = idx - b * 12, f = fc >> 2, c = fc & 3;
-            BlkE *e = reinterpret_cast<BlkE *>(&blk[b]);
-            e->nrm[f][slot_of(c)] = nrm[r]; e->off[f][slot_of(c)] = off[r]; // slot order x0 x2 x1 x3, see V4
-            if (!PREFIT && c == 0) e->invN[f] = invn[r];
-            if (PREFIT && c < 3)
-            { // the packed trial's integer operands (negated, see "a9, packed form"), once per block here instead of per lane in phase E
-              int *tc = s_trialc + (wave * kBlocksPerWave + b) * kTrialConstDw;
-              tc[f * 3 + c] = -(int)nrm[r];
-              tc[9 + f * 3 + c] = term_const(f, c, (int)off[r]);
-            }
-          }
-        }
+    
       }
-      uint32_t *s_queue = s_calls + 4;
+      if (!PERSIST && p.fitOnly) return; // pass 1 of the merged-block encoder: the records are all it needs (uniform for the workgroup)
+      phase_e_view<CH, FAST, PREFIT>(g);
+      uint32_t *s_queue = g.calls + 4;
       if (tid == 0) *s_queue = 0;
       __syncthreads(); // all waves are done with V: wave 0's V region becomes the factor-byte staging area
 
-      uint8_t *stage = reinterpret_cast<uint8_t *>(s_V); // [3 planes][8 rows][256 px]
+      uint8_t *stage = reinterpret_cast<uint8_t *>(g.V); // [3 planes][8 rows][256 px]
       uint32_t waveCalls = 0;
       // (No zeroing of the parked shift words of blocks past the right edge here: with the dynamic queue below another wave may already have parked a real
       //  word for a block of this wave's range by the time this wave gets to issue such a store -- a rare lost update, found in round 2.  The F step masks
@@ -479,39 +580,16 @@ namespace limg_hip
         if (sb >= (uint32_t)kStripBlocks) break;
         uint32_t qv = 0;
         if (lane == 0) qv = atomicAdd(s_queue, 1u); // the next block's index arrives while this one is searched
-        const uint32_t bx = strip * kStripBlocks + sb;
-        if (bx >= p.blocksX) { sbNext = (uint32_t)sgpr((int)qv); continue; }
-        const uint32_t rx = min(p.sizeX - bx * kBlock, (uint32_t)kBlock), n = rx * ry;
-        BlkF *const blkE = s_blk + sb;
-        uint32_t lx, ly;
-        if (rx == 8) { lx = lane & 7; ly = lane >> 3; }
-        else { const uint32_t l = (uint32_t)lane < n ? (uint32_t)lane : 0u; ly = l / rx; lx = l - ly * rx; }
-        uint32_t px = s_strip[ly * kRowDw + sb * kBlock + lx];
+        uint32_t rx, n, lx, ly;
+        if (!block_geom(p, g, sb, rx, n)) { sbNext = (uint32_t)sgpr((int)qv); continue; }
+        const BlkF *const blkE = g.blk + sb;
         const bool active = (uint32_t)lane < n;
-        px = active ? px : 0u;
-        const BlkE *be = reinterpret_cast<const BlkE *>(blkE);
-
-        uint32_t fA, fB, fC;
-        { // a8 (src/limg_factorization.h:149-197): fa = ((px - Amin) . nA) * invA, est = Amin + nA * fa, fb from px - est - Boff, ...
-          const V4 pv = px_to_v4(px);
-          const V4 nA = ld4(be->nrm[0]), mnA = ld4(be->off[0]);
-          const float fa = dp4<CH, FAST>(pv - mnA, nA) * be->invN[0];
-          fA = cvt_u8_rne_sat(255.0f * fa);
-          const V4 nB = ld4(be->nrm[1]), ofB = ld4(be->off[1]);
-          V4 est = mnA + nA * fa;
-          const float fb = dp4<CH, FAST>((pv - est) - ofB, nB) * be->invN[1];
-          fB = cvt_u8_rne_sat(255.0f * fb);
-          const V4 nC = ld4(be->nrm[2]), ofC = ld4(be->off[2]);
-          est = est + nB * fb;
-          const float fc = dp4<CH, FAST>((pv - est) - ofC, nC) * be->invN[2];
-          fC = cvt_u8_rne_sat(255.0f * fc);
-        }
-
-        uint32_t shift[3] = { 0, 0, 0 };
-        if (p.forced[0] >= 0)
-        {
-          shift[0] = (uint32_t)p.forced[0]; shift[1] = (uint32_t)p.forced[1]; shift[2] = (uint32_t)p.forced[2];
-        }
+        const uint32_t px = block_pixel(g, sb, rx, n, lx, ly);
+        uint32_t fA, fB, fC, shift[3] = { 0, 0, 0 };
+        pixel_factors<CH, FAST>(reinterpret_cast<const BlkE *>(blkE), px, fA, fB, fC);
+        // the shift search of the block (a10-a12), inline (see the note above this function): limits, the packed trial's state, then one of the two automata or, for a
+        // record out of the packed trial's range, the generic search
+        if (p.forced[0] >= 0) { shift[0] = (uint32_t)p.forced[0]; shift[1] = (uint32_t)p.forced[1]; shift[2] = (uint32_t)p.forced[2]; }
         else if (p.crushBits)
         {
           const uint64_t maxBlockN = p.maxBlock * (uint64_t)n;
@@ -534,7 +612,7 @@ namespace limg_hip
             t.pxBlo = t.pxB - 255;
             if (PREFIT)
             { // uniform values, kept in VGPRs (they are operands of v_mad_i32_i24); prepared lane-parallel with the phase-E view above
-              const int *tc = s_trialc + sb * kTrialConstDw;
+              const int *tc = g.trialc + sb * kTrialConstDw;
 #pragma unroll
               for (int c = 0; c < 3; c++)
               {
@@ -575,97 +653,14 @@ namespace limg_hip
             shift[0] = packed & 0xFF; shift[1] = (packed >> 8) & 0xFF; shift[2] = (packed >> 16) & 0xFF;
           }
         }
-
-        // dither calls this block will make (src/limg.cpp:1951-1958)
-        // a shift of 1..7 dithers (one call), 0 and 8 do not; as scalar arithmetic -- ((s & 7) + 7) >> 3 -- because a boolean would go through a lane mask and a vector select
-        const uint32_t calls = (((shift[0] & 7u) + 7u) >> 3) + (((shift[1] & 7u) + 7u) >> 3) + (((shift[2] & 7u) + 7u) >> 3);
-        waveCalls += calls;
-        if (p.stripWords)
-        { // stream mode: the block's payload size in 8-byte words rides in bits 8.. of the same per-wave counter (calls of a strip stay below 256): a field of 8 - shift
-          // bits per pixel is that many words; a factor at shift 8 has none unless its alpha normal is non-zero (raw-byte escape, limg_hip_stream.hip)
-          uint32_t words = 0;
-#pragma unroll
-          for (int k = 0; k < 3; k++)
-          {
-            const uint32_t sk = shift[k];
-            if (sk < 8u) words += 8u - sk;
-            else if (CH == 4 && sgpr((int)blkE->rec[8 * k + 3]) != sgpr((int)blkE->rec[8 * k + 7])) words += 8u;
-          }
-          waveCalls += words << 8;
-        }
-
-        const size_t bi = (size_t)byS * p.blocksX + bx;
-        const uint32_t word = shift[0] | (shift[1] << 8) | (shift[2] << 16) | (calls << 24);
-        if (lane == 0)
-        {
-          if (!PERSIST || p.compactOut) p.shifts[bi] = word;
-          if (PERSIST) reinterpret_cast<uint32_t *>(park + kParkShift)[sb] = word;
-        }
-        if (p.storePlanes && active)
-        {
-          const uint32_t o = ly * kFacRow + sb * kBlock + lx;
-          stage[o] = (uint8_t)fA; stage[kFacPlane + o] = (uint8_t)fB; stage[2 * kFacPlane + o] = (uint8_t)fC;
-        }
+    
+        finish_block<CH, PERSIST>(p, g, sb, g.strip * kStripBlocks + sb, blkE, shift, fA, fB, fC, active, ly * kFacRow + sb * kBlock + lx, park, stage, waveCalls);
         sbNext = (uint32_t)sgpr((int)qv);
       }
-      if (lane == 0) s_calls[wave] = waveCalls;
+      if (lane == 0) g.calls[g.wave] = waveCalls;
       __syncthreads();
-      if (tid == 0)
-      {
-        const uint32_t aggAll = s_calls[0] + s_calls[1] + s_calls[2] + s_calls[3];
-        const uint32_t agg = aggAll & 0xFFu; // (bits 8..: the strip's payload words, stream mode)
-        if (p.stripWords) p.stripWords[id] = aggAll >> 8;
-        if (PERSIST)
-        { // publish the count; if the predecessor's inclusive count is already there, publish ours as inclusive right away
-          uint32_t headId = head0;
-          if (p.chainCount > 1 && p.chainRows != 0)
-          {
-            uint32_t c = by / p.chainRows;
-            c = c < p.chainCount - 1 ? c : p.chainCount - 1;
-            headId = head0 + c * p.chainRows * p.stripsX;
-          }
-#ifdef LIMG_HIP_TEST_HOOKS
-          if (id == p.testSkipStrip) {} // (test build: a strip that never publishes)
-          else
-#endif
-          if (id == headId) desc_store(p.desc + id, kDescInclusive, agg);
-          else
-          {
-            const unsigned long long d = desc_load(p.desc + id - 1);
-            if ((uint32_t)(d >> 32) == kDescInclusive) desc_store(p.desc + id, kDescInclusive, (uint32_t)d == kBasePoison ? kBasePoison : (uint32_t)d + agg);
-            else desc_store(p.desc + id, kDescAggregate, agg);
-          }
-        }
-        else p.stripCalls[id] = agg;
-      }
-      if (PERSIST)
-      { // park the pre-dither factor bytes (private, L2-resident scratch; same workgroup reads them back)
-        for (int i = tid; i < 384; i += kThreads) reinterpret_cast<uint4 *>(park + kParkFac)[i] = *reinterpret_cast<const uint4 *>(stage + (i >> 4) * kFacRow + (i & 15) * 16); // 24 rows of 256 bytes
-        return;
-      }
-
-      // ---- pre-dither factor bytes -> the caller's factor planes (rewritten in place by k_dither_store) -------------
-      if (p.storePlanes)
-      {
-        uint8_t *planes[3] = { io.info.pFactorsA, io.info.pFactorsB, io.info.pFactorsC };
-        if (p.vecFactors)
-        {
-          for (int i = tid; i < 384; i += kThreads)
-          {
-            const int pl = i >> 7, row = (i & 127) >> 4, col = (i & 15) * 16;
-            if ((uint32_t)row < ry && (uint32_t)col < stripW)
-              *reinterpret_cast<uint4 *>(planes[pl] + (size_t)(y0 + row) * p.sizeX + x0 + col) = *reinterpret_cast<const uint4 *>(stage + pl * kFacPlane + row * kFacRow + col);
-          }
-        }
-        else
-        {
-          for (int i = tid; i < 3 * 2048; i += kThreads)
-          {
-            const int pl = i >> 11, row = (i & 2047) >> 8, col = i & 255;
-            if ((uint32_t)row < ry && (uint32_t)col < stripW) planes[pl][(size_t)(y0 + row) * p.sizeX + x0 + col] = stage[pl * kFacPlane + row * kFacRow + col];
-          }
-        }
-      }
+      if (tid == 0) publish_strip<PERSIST>(p, g, id, head0);
+      park_or_store_factors<PERSIST>(p, io, g, park, stage);
     }
 
     // =====================================================================================================================
@@ -679,13 +674,7 @@ namespace limg_hip
       const uint32_t per = (total + 1023u) / 1024u;
       const uint32_t t = threadIdx.x;
       const uint32_t begin = min(t * per, total), end = min(begin + per, total);
-      auto chain_of = [&](uint32_t e) -> uint32_t
-      {
-        const uint32_t row = e / p.stripsX;
-        if (p.chainCount <= 1 || p.chainRows == 0) return 0u;
-        const uint32_t c = row / p.chainRows;
-        return c < p.chainCount - 1 ? c : p.chainCount - 1;
-      };
+      auto chain_of = [&](uint32_t e) -> uint32_t { return chain_of_row(p.chainCount, p.chainRows, e / p.stripsX); };
       auto is_head = [&](uint32_t e) -> bool { return e == 0 || chain_of(e) != chain_of(e - 1); };
 
       uint32_t sum = 0, flag = 0;
@@ -736,7 +725,6 @@ namespace limg_hip
       const uint32_t stripW = min(p.sizeX - x0, (uint32_t)(kStripBlocks * kBlock));
       const uint32_t ry = min(p.sizeY - y0, (uint32_t)kBlock);
       const uint32_t nBlocks = min(p.blocksX - strip * kStripBlocks, (uint32_t)kStripBlocks);
-      const uint8_t *planesIn[3] = { io.info.pFactorsA, io.info.pFactorsB, io.info.pFactorsC };
       const StripLds L = carve_phase_f(fbase, s_rec, 24);
 
       if (PERSIST)
@@ -750,23 +738,7 @@ namespace limg_hip
       }
       else
       {
-        if (p.vecFactors)
-        {
-          for (int i = tid; i < 384; i += kThreads)
-          {
-            const int pl = i >> 7, row = (i & 127) >> 4, col = (i & 15) * 16;
-            if ((uint32_t)row < ry && (uint32_t)col < stripW)
-              *reinterpret_cast<uint4 *>(L.fac + pl * kFacPlane + row * kFacRow + col) = *reinterpret_cast<const uint4 *>(planesIn[pl] + (size_t)(y0 + row) * p.sizeX + x0 + col);
-          }
-        }
-        else
-        {
-          for (int i = tid; i < 3 * 2048; i += kThreads)
-          {
-            const int pl = i >> 11, row = (i & 2047) >> 8, col = i & 255;
-            if ((uint32_t)row < ry && (uint32_t)col < stripW) L.fac[pl * kFacPlane + row * kFacRow + col] = planesIn[pl][(size_t)(y0 + row) * p.sizeX + x0 + col];
-          }
-        }
+        copy_factor_planes<false>(p, io, L.fac, x0, y0, stripW, ry, tid);
         // records (12 dwords of int16 per block) and shift words
         for (int i = tid; i < kStripBlocks * 12; i += kThreads)
         {
@@ -790,13 +762,7 @@ namespace limg_hip
         uint32_t base;
         if (PERSIST)
         {
-          uint32_t headId = head0;
-          if (p.chainCount > 1 && p.chainRows != 0)
-          {
-            uint32_t c = by / p.chainRows;
-            c = c < p.chainCount - 1 ? c : p.chainCount - 1;
-            headId = head0 + c * p.chainRows * p.stripsX;
-          }
+          const uint32_t headId = head0 + chain_head_row(p.chainCount, p.chainRows, by) * p.stripsX;
           const uint32_t w = lane < kStripBlocks ? L.shift[lane] : 0u;
           const uint32_t agg = wave_sum(w >> 24);
           const unsigned long long own = desc_load(p.desc + id);

@@ -15,6 +15,28 @@ namespace limg_hip
     // (at a stride of 256 all rows of a block share two banks).
     constexpr int kFacRow = 320, kFacPlane = 8 * kFacRow, kFacBytes = 3 * kFacPlane;
 
+    // The strip's factor bytes between that LDS area and the caller's three factor planes, by the whole workgroup: TO_PLANES the E step's pre-dither bytes (split
+    // path) and the ragged F step's final ones, !TO_PLANES the split path's F step taking the pre-dither bytes back.  16 bytes per lane where p.vecFactors allows.
+    template <bool TO_PLANES, class P, class IO>
+    __device__ __forceinline__ void copy_factor_planes(const P &p, const IO &io, uint8_t *fac, const uint32_t x0, const uint32_t y0, const uint32_t stripW, const uint32_t ry, const int tid)
+    {
+      uint8_t *planes[3] = { io.info.pFactorsA, io.info.pFactorsB, io.info.pFactorsC };
+      auto piece = [&](auto *g, auto *l) { if (TO_PLANES) *g = *l; else *l = *g; }; // g: in the plane, l: in LDS
+      if (p.vecFactors)
+        for (int i = tid; i < 384; i += kThreads)
+        {
+          const int pl = i >> 7, row = (i & 127) >> 4, col = (i & 15) * 16;
+          if ((uint32_t)row < ry && (uint32_t)col < stripW)
+            piece(reinterpret_cast<uint4 *>(planes[pl] + (size_t)(y0 + row) * p.sizeX + x0 + col), reinterpret_cast<uint4 *>(fac + pl * kFacPlane + row * kFacRow + col));
+        }
+      else
+        for (int i = tid; i < 3 * 2048; i += kThreads)
+        {
+          const int pl = i >> 11, row = (i & 2047) >> 8, col = i & 255;
+          if ((uint32_t)row < ry && (uint32_t)col < stripW) piece(planes[pl] + (size_t)(y0 + row) * p.sizeX + x0 + col, fac + pl * kFacPlane + row * kFacRow + col);
+        }
+    }
+
     // LDS areas of phase F.  In the fused kernel they overlay the (then dead) parked-contribution area of k_fit_search.
     struct StripLds
     {
@@ -503,27 +525,7 @@ namespace limg_hip
           for (uint32_t row = 0; row < ry; row++) io.info.pDecoded[(size_t)(y0 + row) * p.sizeX + wx0 + lane] = dec[row * 64 + lane];
       }
       __syncthreads(); // the three factor planes are stored strip-wide: 16 bytes per lane, whole rows of 256 bytes
-      {
-        const uint32_t stripW = min(p.sizeX - x0, (uint32_t)(kStripBlocks * kBlock));
-        uint8_t *planes8[3] = { io.info.pFactorsA, io.info.pFactorsB, io.info.pFactorsC };
-        if (p.vecFactors)
-        {
-          for (int i = tid; i < 384; i += kThreads)
-          {
-            const int pl = i >> 7, row = (i & 127) >> 4, col = (i & 15) * 16;
-            if ((uint32_t)row < ry && (uint32_t)col < stripW)
-              *reinterpret_cast<uint4 *>(planes8[pl] + (size_t)(y0 + row) * p.sizeX + x0 + col) = *reinterpret_cast<const uint4 *>(out + pl * kFacPlane + row * kFacRow + col);
-          }
-        }
-        else
-        {
-          for (int i = tid; i < 3 * 2048; i += kThreads)
-          {
-            const int pl = i >> 11, row = (i & 2047) >> 8, col = i & 255;
-            if ((uint32_t)row < ry && (uint32_t)col < stripW) planes8[pl][(size_t)(y0 + row) * p.sizeX + x0 + col] = out[pl * kFacPlane + row * kFacRow + col];
-          }
-        }
-      }
+      copy_factor_planes<true>(p, io, out, x0, y0, min(p.sizeX - x0, (uint32_t)(kStripBlocks * kBlock)), ry, tid);
     }
 
     // exclusive prefix of the dither-call counts of the strip's 32 blocks (wave 0), on top of the strip's base

@@ -2,7 +2,8 @@
 """Per-phase instruction budget of the encode kernels, from the compiler's own assembly (hipcc -S -gline-tables-only) of the sources as they stand.
 
 Every instruction of a kernel is attributed to a PHASE through its inlined-at chain (the .loc comments): the innermost frame that lies inside one of the phase
-functions below decides.  A phase's static count is divided by the number of inlined copies the kernel holds of it (the search loop exists twice -- whole blocks and
+functions below decides.  The encode kernel's phases are functions and nothing else -- the E step's stages (fit_search_strip's callees), the search's and the F step's
+parts --, so a reworded comment cannot move a phase; only k_fit_tpb, one function of its own, is still cut by source markers.  A phase's static count is divided by the number of inlined copies the kernel holds of it (the search loop exists twice -- whole blocks and
 blocks with masked lanes --, the F step's per-factor body six times ...), which gives the instructions of ONE execution; the last column multiplies by how often a
 block executes the phase.  The dynamic totals (rocprofv3 SQ_INSTS_VALU / _SALU / _LDS per kernel, split path: one kernel per step) are printed next to the sums.
 
@@ -137,8 +138,6 @@ def main():
     ap.add_argument("--sums", type=float, default=10.0, help="block-error sums per block (trials that no pixel fails)")
     ap.add_argument("--dithers", type=float, default=2.2, help="dithered factors per block (shifts 1..7)")
     args = ap.parse_args()
-    K = os.path.join(CSRC, "limg_hip_kernels.hip")
-    kf = "limg_hip_kernels.hip"
     funcs = {}  # name -> (file, first line, last line)
     for f in ENCODE_FILES:
         for name, (a, b) in function_ranges(os.path.join(CSRC, f)).items():
@@ -147,17 +146,6 @@ def main():
     def fn(name):
         return funcs[name]
 
-    # sub-ranges of fit_search_strip by markers in the source
-    e1 = funcs["fit_search_strip"][2]
-    m_stage = marker(K, "// ---- stage: the strip's pixel rows into LDS")
-    m_prefit = marker(K, "the records of the wave's 8 blocks as k_fit_tpb left them")
-    m_float = marker(K, "// The float stage runs in batches of kBatch blocks per wave")
-    m_view = marker(K, "// phase-E view (overlays the dead float-stage fields)")
-    m_phaseE = marker(K, "// ---- phase E: per-pixel factors (a8) + shift search (a10-a12)")
-    m_a8 = marker(K, "{ // a8 (src/limg_factorization.h:149-197)")
-    m_shift = marker(K, "uint32_t shift[3] = { 0, 0, 0 };", after=m_a8)
-    m_calls = marker(K, "// dither calls this block will make (src/limg.cpp:1951-1958)")
-    m_after = marker(K, "if (lane == 0) s_calls[wave] = waveCalls;")
     asm = assemble("limg_hip_kernels.hip")
     asm_fit = assemble("limg_hip_fit_tpb.hip")
     print("# Per-phase instruction budget of the encode path (generated by tools/isa_budget.py from the assembly of the committed sources)\n")
@@ -171,14 +159,14 @@ def main():
         ("search: block-error sum (wave_sum)", [fn("wave_sum"), fn("wave_sum_lane63"), fn("wave_sum_below_mask"), fn("wave_sum_below")]),
         ("search: automaton loop / entry load", [fn("search_fast_automaton"), fn("sload8")]),
         ("search: accurate automaton (other variant)", [fn("search_accurate_automaton")]),
-        ("E: strip staging (pixels -> LDS)", [(kf, m_stage, m_prefit - 1)]),
-        ("E: record load + flags (PREFIT)", [(kf, m_prefit, m_float - 1)]),
-        ("E: lane == pixel float stage (other variant)", [(kf, m_float, m_view - 1), fn("serial_sums2")]),
-        ("E: phase-E view + trial constants (a7)", [(kf, m_view, m_phaseE - 1)]),
-        ("E: per-pixel factors (a8)", [(kf, m_a8, m_shift - 1)]),
-        ("E: block loop, trial set-up", [(kf, m_phaseE, m_a8 - 1), (kf, m_shift, m_calls - 1)]),
-        ("E: block epilogue (shift word, factor bytes -> LDS)", [(kf, m_calls, m_after - 1)]),
-        ("E: strip epilogue (descriptor, park)", [(kf, m_after, e1)]),
+        ("E: strip staging (pixels -> LDS)", [fn("stage_strip_pixels")]),
+        ("E: record load + flags (PREFIT)", [fn("request_prefit_records"), fn("take_prefit_records")]),
+        ("E: lane == pixel float stage (other variant)", [fn("serial_sums2")]),  # (phases A-D are inline in fit_search_strip: in the variants that have them they count under its row)
+        ("E: phase-E view + trial constants (a7)", [fn("phase_e_view")]),
+        ("E: per-pixel factors (a8)", [fn("pixel_factors")]),
+        ("E: block loop, trial set-up", [fn("fit_search_strip"), fn("block_geom"), fn("block_pixel")]),  # (the orchestrator itself: strip geometry, the block queue, the search's set-up)
+        ("E: block epilogue (shift word, factor bytes -> LDS)", [fn("finish_block")]),
+        ("E: strip epilogue (descriptor, park)", [fn("publish_strip"), fn("park_or_store_factors")]),
         ("F: prepare (plane constants, decode constants, flags)", [fn("phase_f_prepare")]),
         ("F: 7 uniform planes' stores", [fn("phase_f_store_const")]),
         ("F: chain position (look-back, first calls)", [fn("lookback_base"), fn("phase_f_first_calls"), fn("desc_load"), fn("desc_store")]),
