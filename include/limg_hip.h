@@ -338,6 +338,60 @@ limg_hip_result limg_hip_encode_stream_batch(limg_hip_context *pCtx, size_t coun
                                              uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes,
                                              uint32_t errorFactor, int poolThreads, int fastBitCrushing);
 
+/* ---- stream encode to a byte budget: size probe and error-factor search (version 1 streams) -----------------------------------------
+ * errorFactor is the stream's only rate knob.  A stream is 64 + 56 blocks + 8 x (payload words) bytes, and the payload words follow from the blocks' records -- which do
+ * not depend on errorFactor -- and their shift triples, which depend on it through errorFactor / 2 only.  So the size at an error factor is the float stage once and,
+ * per error factor, the per-pixel factors and the shift search of every block with the field widths summed (k_rate_probe): no dither, no decode, no plane, no packer.
+ *
+ * limg_hip_stream_sizes*: pBytes[i] = the totalBytes limg_hip_encode_stream* reports for the same image, arguments and options at errorFactor pErrorFactors[i]; any
+ * value is allowed (0, odd ones).  The records are computed once; there is one probe launch per entry and ONE download.  pErrorFactors and pBytes are HOST arrays of
+ * `count` entries in both forms.  Errors, in this order and before anything touches the device: NULL context, image or array: limg_hip_error_ArgumentNull;
+ * limg_hip_stream_bound(sizeX, sizeY) == 0: limg_hip_error_InvalidParameter.  Then count == 0: limg_hip_success with nothing done.
+ *
+ * limg_hip_encode_stream_budget*: the stream of limg_hip_encode_stream* at an error factor chosen for maxBytes.  The search runs over h = errorFactor / 2 between
+ * minErrorFactor / 2 and maxErrorFactor / 2 (0 means 2 and 1024) and is this algorithm, with size(h) the stream's length at errorFactor 2 h:
+ *     if size(hHi) > maxBytes:          errorFactor = maxErrorFactor, withinBudget = 0       (the call still succeeds and writes that stream)
+ *     elif size(hLo) <= maxBytes:       errorFactor = minErrorFactor, withinBudget = 1
+ *     else bisect with size(lo) > maxBytes >= size(hi) until hi - lo == 1:  errorFactor = 2 hi, withinBudget = 1
+ * With withinBudget = 1 the stream is never longer than maxBytes (only measured values are returned).  The size is NOT monotone in errorFactor (the shift search is
+ * greedy), so errorFactor is the smallest that fits only where it happens to be; a budget may even be refused that some error factor below maxErrorFactor would meet.
+ * probes: sizes measured, at most 2 + ceil(log2(hHi - hLo)).  The stream written is byte for byte limg_hip_encode_stream_device's at pResult->errorFactor, and
+ * pResult->bytes its totalBytes.  pResult (host): set struct_size to sizeof(limg_hip_budget_result) before the call.
+ * Errors: those of limg_hip_encode_stream_device in its order, pResult counted among the pointers; then an odd bound, a bound below 2, minErrorFactor >
+ * maxErrorFactor, maxBytes == 0 or a struct_size below the struct's: limg_hip_error_InvalidParameter.  All before anything touches the device; a refused call writes
+ * nothing.
+ * The device forms enqueue all probes at once -- the thresholds of the next probe are written on the device (k_rate_step, the search of limg_hip_rate_step.h) -- wait
+ * ONCE for the 48-byte state, and then encode.  They SYNCHRONISE `stream`, so they cannot be captured into a graph.
+ * Fallback: images with partial edge blocks, force_split_kernels, legacy_float_stage and fastBitCrushing == 0 have no probe kernel; each size is then one ordinary
+ * stream encode (budget: into the caller's buffer; sizes: into context staging of the stream bound) whose totalBytes is read back, driven by the same search function:
+ * the same results, one wait per size.
+ * Options: forced_shift (a flat size curve), dither_pcg and float_mode are honoured as by limg_hip_encode_stream_device.
+ * Context memory: 48 + 24 + 8 bytes of state and counter, and 12 bytes per entry of a sizes list, besides what a stream encode of the image holds. */
+typedef struct limg_hip_budget_result
+{
+  uint32_t struct_size;  /* in: sizeof(limg_hip_budget_result) */
+  uint32_t errorFactor;  /* the error factor the stream was encoded with */
+  uint32_t probes;       /* sizes the search measured */
+  uint32_t withinBudget; /* 1: bytes <= maxBytes */
+  uint64_t bytes;        /* the stream's totalBytes */
+} limg_hip_budget_result; /* 24 bytes */
+
+/* DEVICE image, asynchronous probes, ONE wait for the sizes. */
+limg_hip_result limg_hip_stream_sizes_device(limg_hip_context *pCtx, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const uint32_t *pErrorFactors,
+                                             size_t count, size_t *pBytes, int poolThreads, int fastBitCrushing, void *stream);
+/* HOST image, blocking, under the context's mutex. */
+limg_hip_result limg_hip_stream_sizes(limg_hip_context *pCtx, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const uint32_t *pErrorFactors, size_t count,
+                                      size_t *pBytes, int poolThreads, int fastBitCrushing);
+/* DEVICE pointers (pIn, pStream: 16-byte aligned, capacity >= limg_hip_stream_bound); waits for `stream`. */
+limg_hip_result limg_hip_encode_stream_budget_device(limg_hip_context *pCtx, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream,
+                                                     size_t capacity, size_t maxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads,
+                                                     int fastBitCrushing, limg_hip_budget_result *pResult, void *stream);
+/* HOST pointers, blocking, under the context's mutex.  capacity may be below the bound: pResult is filled, and limg_hip_error_OutOfBounds returned with nothing written
+ * to pStream, where pResult->bytes > capacity. */
+limg_hip_result limg_hip_encode_stream_budget(limg_hip_context *pCtx, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                              size_t maxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                              limg_hip_budget_result *pResult);
+
 /* ---- compact stream, version 2: the merged-block encoder's rectangles --------------------------------------------------------
  * What limg_hip_blocked_encode3d computes -- the rectangles of merged 8x8 blocks, each with ONE record, ONE shift triple and its crushed factor values -- in the same
  * "LMG3" container, so that decode(blocked_encode_stream(image)) equals the pDecoded plane of `limg_blocked_encode3d_test` bit for bit.  Version 1 streams and their

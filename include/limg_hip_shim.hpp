@@ -178,6 +178,26 @@ inline limg_result limg_encode(const uint32_t *pIn, const size_t sizeX, const si
                                              fastBitCrushing ? 1 : 0);
 }
 
+// limg_encode to a byte budget (limg_hip.h "stream encode to a byte budget"): the stream of limg_encode at the error factor a search over
+// [minErrorFactor, maxErrorFactor] (even, 0 = 2 / 1024) chose for maxBytes.  *pErrorFactor, *pOutSize: what was chosen and what it takes; *pWithinBudget (may be NULL):
+// false where even maxErrorFactor's stream is longer than maxBytes -- that stream is then what is written, and the call succeeds; *pProbes (may be NULL): sizes measured.
+inline limg_result limg_encode_budget(const uint32_t *pIn, const size_t sizeX, const size_t sizeY, const bool hasAlpha, uint8_t *pOut, const size_t outCapacity, size_t *pOutSize,
+                                      const size_t maxBytes, uint32_t *pErrorFactor, bool *pWithinBudget = nullptr, uint32_t *pProbes = nullptr,
+                                      const uint32_t minErrorFactor = 0, const uint32_t maxErrorFactor = 0, limg_thread_pool *pThreadPool = nullptr, const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (!pOutSize || !pErrorFactor) return limg_error_ArgumentNull;
+  limg_hip_budget_result res = { sizeof(limg_hip_budget_result), 0, 0, 0, 0 };
+  const limg_result r = (limg_result)limg_hip_encode_stream_budget(c, pIn, sizeX, sizeY, hasAlpha ? 1 : 0, pOut, outCapacity, maxBytes, minErrorFactor, maxErrorFactor,
+                                                                   limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0, &res);
+  if (r != limg_success && r != limg_error_OutOfBounds) return r;
+  *pOutSize = (size_t)res.bytes; *pErrorFactor = res.errorFactor;
+  if (pWithinBudget) *pWithinBudget = res.withinBudget != 0;
+  if (pProbes) *pProbes = res.probes;
+  return r;
+}
+
 // `count` images of one shape in one call (limg_hip.h "batched stream encode"): pOutSizes[i] bytes at ppOut[i] are what limg_encode writes for ppIn[i]; every ppOut[i]
 // has room for outCapacityEach >= limg_encode_bound(sizeX, sizeY) bytes
 inline limg_result limg_encode_batch(const uint32_t *const *ppIn, const size_t count, const size_t sizeX, const size_t sizeY, const bool hasAlpha, uint8_t *const *ppOut,

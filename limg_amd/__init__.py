@@ -28,6 +28,7 @@ ABI_SYMBOLS = (
     "limg_hip_host_noise_table", "limg_hip_noise_table_device", "limg_hip_host_chain_call", "limg_hip_host_chain_checkpoints", "limg_hip_host_dense_checkpoints", "limg_hip_host_partition", "limg_hip_check_device_status",
     "limg_hip_stream_bound", "limg_hip_encode_stream_device", "limg_hip_decode_stream_device", "limg_hip_encode_stream", "limg_hip_decode_stream",
     "limg_hip_stream_info", "limg_hip_encode_stream_batch_device", "limg_hip_encode_stream_batch",
+    "limg_hip_stream_sizes_device", "limg_hip_stream_sizes", "limg_hip_encode_stream_budget_device", "limg_hip_encode_stream_budget",
     "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
     "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
     "limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device", "limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window",
@@ -138,6 +139,11 @@ def tensor_format(dtype, planes, scale, bias):
     assert name in ("float32", "float16"), dtype
     scale, bias = list(scale) + [1.0] * (4 - len(scale)), list(bias) + [0.0] * (4 - len(bias))
     return TensorFormat(TENSOR_F16 if name == "float16" else TENSOR_F32, planes, (C.c_float * 4)(*scale[:4]), (C.c_float * 4)(*bias[:4]))
+
+
+class BudgetResult(C.Structure):
+    """limg_hip_budget_result: what a budgeted stream encode chose"""
+    _fields_ = [("struct_size", C.c_uint32), ("errorFactor", C.c_uint32), ("probes", C.c_uint32), ("withinBudget", C.c_uint32), ("bytes", C.c_uint64)]
 
 
 class Options(C.Structure):
@@ -259,6 +265,16 @@ def load_library(path=None):
                                                       C.c_int, C.c_void_p]
     L.limg_hip_encode_stream_batch.restype = C.c_int
     L.limg_hip_encode_stream_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_int, C.c_int]
+    L.limg_hip_stream_sizes_device.restype = C.c_int  # ctx, in, sizeX, sizeY, hasAlpha, error factors (host), count, sizes (host), pool, fast, hipStream
+    L.limg_hip_stream_sizes_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.limg_hip_stream_sizes.restype = C.c_int
+    L.limg_hip_stream_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
+    L.limg_hip_encode_stream_budget_device.restype = C.c_int  # ctx, in, sizeX, sizeY, hasAlpha, stream, capacity, maxBytes, min ef, max ef, pool, fast, result, hipStream
+    L.limg_hip_encode_stream_budget_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int,
+                                                       C.c_int, C.c_void_p, C.c_void_p]
+    L.limg_hip_encode_stream_budget.restype = C.c_int
+    L.limg_hip_encode_stream_budget.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                                C.c_void_p]
     L.limg_hip_blocked_stream_bound.restype = C.c_size_t
     L.limg_hip_blocked_stream_bound.argtypes = [C.c_size_t, C.c_size_t]
     L.limg_hip_blocked_encode_stream_device.restype = C.c_int
@@ -649,6 +665,45 @@ class LimgHip:
 
     def decode_stream_device(self, stream, nbytes, w, h, out=None):
         return self._decode_stream_device("limg_hip_decode_stream_device", stream, nbytes, w, h, out)
+
+    # ---- stream sizes and the encode to a byte budget (contract: include/limg_hip.h) ----
+    def stream_sizes(self, img, has_alpha, error_factors, pool_threads=0, fast=True):
+        """host uint32 image -> [len(encode_stream(img, ..., error_factor=ef)) for ef in error_factors], without encoding"""
+        img = np.ascontiguousarray(img, dtype=np.uint32)
+        h, w = img.shape
+        n = len(error_factors)
+        efs, sizes = (C.c_uint32 * max(n, 1))(*error_factors), (C.c_size_t * max(n, 1))()
+        self._stream_call("limg_hip_stream_sizes", _np_ptr(img), w, h, int(has_alpha), efs, n, sizes, pool_threads, int(fast))
+        return [int(v) for v in sizes[:n]]
+
+    def stream_sizes_device(self, img, has_alpha, error_factors, pool_threads=0, fast=True):
+        """img: torch int32 CUDA (h, w); waits for torch's current stream"""
+        h, w = img.shape
+        n = len(error_factors)
+        efs, sizes = (C.c_uint32 * max(n, 1))(*error_factors), (C.c_size_t * max(n, 1))()
+        self._stream_call("limg_hip_stream_sizes_device", C.c_void_p(img.data_ptr()), w, h, int(has_alpha), efs, n, sizes, pool_threads, int(fast), self._stream())
+        return [int(v) for v in sizes[:n]]
+
+    def encode_stream_budget(self, img, has_alpha, max_bytes, min_error_factor=0, max_error_factor=0, pool_threads=0, fast=True):
+        """host uint32 image -> (stream bytes (numpy uint8), BudgetResult): the stream of encode_stream at the error factor the search chose for max_bytes"""
+        img = np.ascontiguousarray(img, dtype=np.uint32)
+        h, w = img.shape
+        out = np.zeros(self.stream_bound(w, h), dtype=np.uint8)
+        res = BudgetResult(C.sizeof(BudgetResult))
+        self._stream_call("limg_hip_encode_stream_budget", _np_ptr(img), w, h, int(has_alpha), _np_ptr(out), out.size, int(max_bytes), min_error_factor, max_error_factor,
+                          pool_threads, int(fast), C.byref(res))
+        return out[:res.bytes].copy(), res
+
+    def encode_stream_budget_device(self, img, has_alpha, max_bytes, min_error_factor=0, max_error_factor=0, out=None, pool_threads=0, fast=True):
+        """img: torch int32 CUDA (h, w) -> (torch uint8 CUDA stream buffer of worst-case size, BudgetResult); waits for torch's current stream"""
+        import torch
+        h, w = img.shape
+        if out is None:
+            out = torch.empty(self.stream_bound(w, h), dtype=torch.uint8, device=img.device)
+        res = BudgetResult(C.sizeof(BudgetResult))
+        self._stream_call("limg_hip_encode_stream_budget_device", C.c_void_p(img.data_ptr()), w, h, int(has_alpha), C.c_void_p(out.data_ptr()), out.numel(), int(max_bytes),
+                          min_error_factor, max_error_factor, pool_threads, int(fast), C.byref(res), self._stream())
+        return out, res
 
     # ---- batched stream encode: a list of same-shape images, stream i = encode_stream of image i (contract: include/limg_hip.h) ----
     def encode_stream_batch(self, imgs, has_alpha, error_factor=100, pool_threads=0, fast=True):

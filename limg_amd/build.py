@@ -16,13 +16,14 @@ TEST_FLAGS = ["-DLIMG_HIP_TEST_HOOKS"]
 SOURCES = ["limg_hip_kernels.hip", "limg_hip_fit_tpb.hip", "limg_hip_stream.hip", "limg_hip_blocked.hip", "limg_hip_synth.hip", "limg_hip_noise_gpu.hip",
            "limg_hip_api.hip", "limg_hip_noise_table.hip", "limg_hip_encode.hip", "limg_hip_encode_ragged.hip", "limg_hip_host_entry.hip", "limg_hip_stream_api.hip",
            "limg_hip_blocked_api.hip", "limg_hip_multi.hip", "limg_hip_noise.cpp", "limg_hip_blocked_host.cpp", "limg_hip_blocked_stream.hip", "limg_hip_stream_window.hip",
-           "limg_hip_stream_window_api.hip"]
+           "limg_hip_stream_window_api.hip", "limg_hip_rate.hip"]
 # the library exports the C ABI of include/limg_hip.h (limg_hip_*) and nothing else: the host units' shared internals and the C++ runtime's template instances stay local
 EXPORTS = os.path.join(CSRC, "limg_hip.map")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 # per-source extras.  limg_hip_kernels.hip: every atomic in it is issued by one lane (block queue, ticket, look-back descriptors); LLVM's atomic optimizer would still
 # wrap each in its wave-aggregation prologue (v_mbcnt x 2, compare, s_bcnt1, broadcast, add) -- five vector instructions per 8x8 block for nothing
 SOURCE_FLAGS = {"limg_hip_kernels.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
+                "limg_hip_rate.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],  # (the same block queue; its one global atomic per workgroup is thread 0's)
                 # k_stream_decode: LLVM reports one `#pragma unroll` it did not honour (a transformation-ordering note, no particular loop: every loop over a register
                 # array IS unrolled -- the kernel has no scratch, which tests/test_decode_isa.py asserts on the compiled assembly)
                 "limg_hip_stream.hip": ["-Wno-pass-failed"]}

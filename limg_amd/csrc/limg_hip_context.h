@@ -140,6 +140,7 @@ struct limg_hip_context
   {
     Bytes &n;
     DevBuf fac{ n }, tiles{ n }, units{ n }, status{ n }, buf{ n }; // stream packer: 3 factor planes, per-tile payload words; decode status word; host-entry staging
+    DevBuf rateState{ n }, rateCounter{ n }, rateList{ n }; // size probe (limg_hip_rate.hip): RateDevice; the payload-word counter; the list form's error factors, then its sizes
     DevBuf table{ n }, sizes{ n }; // batched stream encode: one StreamImage per image of the list; the finished streams' sizes side by side (one download)
     // version 2 stream of the merged-block encoder: per rectangle its first 64-pixel run, per tile of rectangles its totals; the decoder's block -> rectangle map and
     // its per-call words
@@ -221,6 +222,8 @@ namespace limg_hip
   struct EncodeExtra
   {
     bool streamRaw = false, fitOnly = false;
+    bool fitFloatMode = false;      // fitOnly: the records in the context's float mode, as a stream encode's k_fit_tpb leaves them (the size probe); false: always the
+                                    // exact float stage (pass 1 of the merged-block encoder)
     uint32_t *stripWords = nullptr; // stream mode, images of whole blocks: per work strip the payload words of its blocks (EncodeParams::stripWords)
     int chainPhase = 0; // 0 = whole encode; 1 = E step + scan only (writes *dChainCalls); 2 = F step only (reads *dChainBase).  1 and 2 always take the split path.
     unsigned long long *dChainCalls = nullptr;

@@ -120,7 +120,7 @@ namespace
     const bool forced = c->opt.forced_shift[0] >= 0 && c->opt.forced_shift[0] <= 8 && c->opt.forced_shift[1] >= 0 && c->opt.forced_shift[1] <= 8 &&
                         c->opt.forced_shift[2] >= 0 && c->opt.forced_shift[2] <= 8;
     for (int i = 0; i < 3; i++) p.forced[i] = forced ? c->opt.forced_shift[i] : -1;
-    p.floatFast = (c->opt.float_mode == 1 && !x.fitOnly) ? 1 : 0;
+    p.floatFast = (c->opt.float_mode == 1 && (!x.fitOnly || x.fitFloatMode)) ? 1 : 0;
     p.recordLimit = TOPT(c, record_limit) > 0 ? TOPT(c, record_limit) - 1 : 2700; // see term_bias in limg_hip_search.h: 3 * 2700 + 1 < 0x2000
     const Partition pt = e.pt = x.part ? *x.part : partition(sizeY, poolThreads);
     p.chainCount = pt.chainCount; p.chainRows = pt.chainRows;

@@ -1,7 +1,7 @@
 // limg_hip_float_pixel.h -- the E step's lane == pixel float stage (a4-a6), which images with partial edge blocks keep: the per-block LDS state (BlkF, and the
 // phase-E view BlkE that overlays it), what every stage of the E step knows of its strip (EStrip, block_geom, block_pixel) and the pixel-order direction sums
 // (serial_sums2).  Phases A-D themselves are inline in fit_search_strip: as a function of their own they cost the instances that run them 5 % (see there).
-// Included by limg_hip_kernels.hip only, which stays one translation unit (its per-source compile flags cover this code).
+// Included through limg_hip_phase_e.h by limg_hip_kernels.hip and limg_hip_rate.hip, each one translation unit (the same per-source compile flags cover this code).
 #ifndef LIMG_HIP_FLOAT_PIXEL_H
 #define LIMG_HIP_FLOAT_PIXEL_H
 

@@ -9,6 +9,7 @@
 
 #include "../../include/limg_hip.h"
 #include "limg_hip_blocked_host.h"
+#include "limg_hip_rate_step.h"
 
 namespace limg_hip
 {
@@ -290,6 +291,36 @@ namespace limg_hip
   void launch_set_stream_table(StreamImage *dTable, const StreamImage *hTable, size_t count, hipStream_t s);                // as launch_set_batch_table: through kernel arguments
   void launch_stream_gather_bytes(const StreamImage *dTable, size_t count, unsigned long long *dBytes, hipStream_t s);      // dBytes[i] = totalBytes of image i's header
   void launch_stream_decode(const DecodeParams &p, int cus, hipStream_t s);
+
+  // ---- the stream's size probe (limg_hip_rate.hip) ----
+  // What the probes of one call read on the device and the step kernel between them writes: the search (limg_hip_rate_step.h) or the position in a list of error
+  // factors, and the thresholds of the error factor being measured.
+  struct RateDevice
+  {
+    RateState search;
+    uint32_t listNext;       // list form: the entry the next step kernel fills
+    uint32_t maxPixel32, blockLimitFull, crushBits; // as EncodeParams
+    uint64_t maxBlock;
+  };
+  // k_rate_probe's arguments: the same in both builds (no test-hook member; the test build's record_limit travels in recordLimit, as in EncodeParams).  The members the
+  // E step's stages read carry EncodeParams' names.
+  struct RateProbeParams
+  {
+    struct { const uint32_t *in; } io;
+    uint32_t sizeX, sizeY, blocksX, blocksY, stripsX;
+    int32_t vecIn;
+    int32_t recordLimit;
+    int32_t forced[3];
+    const limg_hip_block_record *records; // k_fit_tpb's
+    const float *invN;
+    const RateDevice *state;
+    unsigned long long *counter;          // the payload words of the error factor being measured, summed over the strips
+  };
+  void launch_rate_begin(RateDevice *dState, unsigned long long *dCounter, const RateState &first, uint32_t firstErrorFactor, hipStream_t s);
+  // fixedBytes: header + table.  dList == nullptr: the search; else the list form (dListBytes[i] = the size at dList[i])
+  void launch_rate_step(RateDevice *dState, unsigned long long *dCounter, uint64_t fixedBytes, const uint32_t *dList, unsigned long long *dListBytes, uint32_t listCount,
+                        hipStream_t s);
+  void launch_rate_probe(const RateProbeParams &p, int channels, bool floatFast, hipStream_t s);
 
   void launch_synth_random_gradient(uint32_t *out, uint32_t w, uint32_t h, uint64_t seed, int opaque, uint32_t y0, hipStream_t s);
   void launch_synth_photo_noise(uint32_t *out, uint32_t w, uint32_t h, uint64_t seed, uint32_t y0, hipStream_t s);

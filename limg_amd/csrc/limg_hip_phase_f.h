@@ -1,5 +1,5 @@
 // limg_hip_phase_f.h -- the F step of one work strip: dither (a13), plane stores (a15), decode (a16), first dither calls.
-// Included by limg_hip_kernels.hip only, which stays one translation unit (its per-source compile flags cover this code).
+// Included through limg_hip_phase_e.h by limg_hip_kernels.hip and limg_hip_rate.hip, each one translation unit (the same per-source compile flags cover this code).
 #ifndef LIMG_HIP_PHASE_F_H
 #define LIMG_HIP_PHASE_F_H
 

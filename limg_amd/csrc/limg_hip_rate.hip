@@ -1,0 +1,167 @@
+// limg_hip_rate.hip -- the LMG3 stream's size probe: how long the version 1 stream of an image would be at an error factor, without encoding it.
+//
+// A stream is 64 + 56 blocks + 8 W bytes, W = the blocks' payload words; a block's words follow from its shift triple and its record's alpha lanes alone (field_bits,
+// limg_hip_stream_format.h).  The records do not depend on the error factor and the shift triple depends on it only through the two thresholds, so one k_fit_tpb
+// (the `fitOnly` route of encode_device) serves any number of probes, and a probe is the E step's front half -- strip staging, record load, phase-E view, per-pixel
+// factors, the shift search (limg_hip_phase_e.h, limg_hip_search.h) -- with W summed instead of anything stored: no noise table, no look-back, no F step, no planes.
+//
+// k_rate_probe: one workgroup per work strip (32 blocks), wave = block, lane = pixel, as the E step.  Images of whole 8x8 blocks, the default search, records from
+// k_fit_tpb.  The thresholds come from a small device-resident state, not from the kernel arguments, and a one-thread k_rate_step between two probes turns the
+// counted words into the next thresholds: a list of error factors (limg_hip_stream_sizes*) or the search of limg_hip_rate_step.h (limg_hip_encode_stream_budget*).  So
+// all launches of a call are enqueued at once, with no host round trip between them; probes behind the end of a search return at once.
+// Progress: no workgroup waits for another one -- no look-back, no spin, no ticket; a workgroup's only global write is one 64-bit atomic add.
+#include "limg_hip_phase_e.h"
+
+namespace limg_hip
+{
+  namespace
+  {
+    // thresholds and flags of an error factor, as encode_params (limg_hip_encode.hip) states them (src/limg.cpp:2186-2212)
+    __device__ __forceinline__ void set_thresholds(RateDevice *d, uint32_t errorFactor)
+    {
+      const uint64_t maxPixel = (uint64_t)0x6 * (errorFactor / 2) * 7, maxBlock = (uint64_t)0x4 * (errorFactor / 2) * 7;
+      const uint64_t lim = (maxBlock * 64ull + 15ull) >> 4;
+      d->maxPixel32 = maxPixel > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxPixel;
+      d->blockLimitFull = lim > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim;
+      d->maxBlock = maxBlock;
+      d->crushBits = errorFactor != 0 ? 1u : 0u;
+    }
+
+    // in front of a call's first probe: the search's state (or the list's position), the first thresholds, an empty counter
+    __global__ void k_rate_begin(RateDevice *d, unsigned long long *counter, const RateState first, const uint32_t firstErrorFactor)
+    {
+      d->search = first;
+      d->listNext = 0u;
+      set_thresholds(d, firstErrorFactor);
+      *counter = 0ull;
+    }
+
+    // between two probes.  list == nullptr: the search takes the size just counted (rate_step) and names the next error factor, 2 h; otherwise the size goes to
+    // listBytes[i] and the list's next entry is set up.
+    __global__ void k_rate_step(RateDevice *d, unsigned long long *counter, const unsigned long long fixedBytes, const uint32_t *list, unsigned long long *listBytes,
+                                const uint32_t listCount)
+    {
+      const unsigned long long bytes = fixedBytes + 8ull * *counter;
+      *counter = 0ull;
+      if (list)
+      {
+        const uint32_t i = d->listNext;
+        if (i >= listCount) return;
+        listBytes[i] = bytes;
+        d->listNext = i + 1u;
+        if (i + 1u < listCount) set_thresholds(d, list[i + 1u]);
+        return;
+      }
+      if (d->search.done) return;
+      rate_step(d->search, bytes);
+      if (!d->search.done) set_thresholds(d, 2u * d->search.next);
+    }
+
+    template <int CH, bool FAST>
+    __global__ __launch_bounds__(kThreads, 6) void k_rate_probe(const RateProbeParams p)
+    {
+      constexpr LdsLayout LL = lds_layout<true>();
+      __shared__ __attribute__((aligned(16))) uint8_t lds[LL.total];
+      const RateDevice *const st = p.state;
+      if (st->search.done) return; // (uniform: the step kernel in front of this launch wrote it)
+      const uint32_t maxPixel32 = (uint32_t)sgpr((int)st->maxPixel32), blockLimit = (uint32_t)sgpr((int)st->blockLimitFull), crushBits = (uint32_t)sgpr((int)st->crushBits);
+      const int tid = (int)threadIdx.x;
+      EStrip g;
+      g.tid = tid; g.lane = tid & 63; g.wave = tid >> 6;
+      g.strip = blockIdx.x % p.stripsX; g.by = blockIdx.x / p.stripsX; g.byS = g.by;
+      g.x0 = g.strip * (kStripBlocks * kBlock); g.y0 = g.by * kBlock;
+      g.stripW = min(p.sizeX - g.x0, (uint32_t)(kStripBlocks * kBlock)); g.ry = (uint32_t)kBlock; // whole blocks
+      g.pix = reinterpret_cast<uint32_t *>(lds + kLdsStrip); g.V = reinterpret_cast<float *>(lds + LL.v); g.blk = reinterpret_cast<BlkF *>(lds + LL.blk);
+      g.calls = reinterpret_cast<uint32_t *>(lds + LL.calls); g.trialc = reinterpret_cast<int *>(lds + LL.trialc);
+      const int lane = g.lane;
+
+      uint32_t recVal[2] = { 0u, 0u };
+      request_prefit_records(p, g, recVal);
+      stage_strip_pixels(p, p.io, g);
+      __syncthreads();
+      take_prefit_records<false>(p, g, recVal, nullptr);
+      phase_e_view<CH, FAST, true>(g);
+      uint32_t *s_queue = g.calls + 4;
+      if (tid == 0) *s_queue = 0;
+      __syncthreads();
+
+      // the strip's blocks from a queue, as phase E hands them out: the number of trials differs from block to block
+      uint32_t waveWords = 0; // scalar
+      auto grab = [&]() -> uint32_t { uint32_t v = 0; if (lane == 0) v = atomicAdd(s_queue, 1u); return (uint32_t)sgpr((int)v); };
+      uint32_t sbNext = grab();
+#pragma unroll 1
+      for (;;)
+      {
+        const uint32_t sb = sbNext;
+        if (sb >= (uint32_t)kStripBlocks) break;
+        uint32_t qv = 0;
+        if (lane == 0) qv = atomicAdd(s_queue, 1u);
+        uint32_t rx, n, lx, ly;
+        if (!block_geom(p, g, sb, rx, n)) { sbNext = (uint32_t)sgpr((int)qv); continue; }
+        const BlkF *const blkE = g.blk + sb;
+        uint32_t shift[3] = { 0, 0, 0 };
+        if (p.forced[0] >= 0) { shift[0] = (uint32_t)p.forced[0]; shift[1] = (uint32_t)p.forced[1]; shift[2] = (uint32_t)p.forced[2]; }
+        else if (crushBits)
+        {
+          const uint32_t px = block_pixel(g, sb, rx, n, lx, ly);
+          uint32_t fA, fB, fC;
+          pixel_factors<CH, FAST>(reinterpret_cast<const BlkE *>(blkE), px, fA, fB, fC);
+          if (!((uint32_t)sgpr((int)blkE->flags) & kBig))
+          { // the packed trial's state, as fit_search_strip sets it up for a whole block with the trial constants of phase_e_view
+            TrialState t;
+            t.fA = fA; t.fB = fB; t.fC = fC;
+            const uint32_t R = px & 0xFF, G = (px >> 8) & 0xFF;
+            t.hiRG = (R + 0x8000u) | ((G + 0x8000u) << 16);
+            t.loRG = (R + 0x8000u - 255u) | ((G + 0x8000u - 255u) << 16);
+            t.pxB = (int)((px >> 16) & 0xFF);
+            t.pxBlo = t.pxB - 255;
+            const int *tc = g.trialc + sb * kTrialConstDw;
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+            {
+              t.nA[c] = tc[c]; t.nB[c] = tc[3 + c]; t.nC[c] = tc[6 + c];
+              t.mA[c] = tc[9 + c]; t.mB[c] = tc[12 + c]; t.mC[c] = tc[15 + c];
+            }
+            t.mA[0] += (int)(R << 8); t.mA[1] += (int)(G << 8); t.mA[2] += t.pxB << 8;
+            search_fast_automaton<true>(t, true, maxPixel32, blockLimit, shift);
+          }
+          else
+          { // a record out of the packed trial's range: the generic 32-bit search, as phase E
+            const uint32_t packed = (uint32_t)sgpr((int)search_generic(px, fA, fB, fC, blkE->rec, true, maxPixel32, st->maxBlock * 64ull, true));
+            shift[0] = packed & 0xFF; shift[1] = (packed >> 8) & 0xFF; shift[2] = (packed >> 16) & 0xFF;
+          }
+        }
+        // the block's payload words (finish_block's count; field_bits, limg_hip_stream_format.h): a field of 8 - shift bits per pixel is that many 8-byte words; a
+        // factor at shift 8 has none unless its alpha normal is non-zero (raw-byte escape)
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+        {
+          const uint32_t sk = shift[k];
+          if (sk < 8u) waveWords += 8u - sk;
+          else if (CH == 4 && sgpr((int)blkE->rec[8 * k + 3]) != sgpr((int)blkE->rec[8 * k + 7])) waveWords += 8u;
+        }
+        sbNext = (uint32_t)sgpr((int)qv);
+      }
+      if (lane == 0) g.calls[g.wave] = waveWords;
+      __syncthreads();
+      if (tid == 0) atomicAdd(p.counter, (unsigned long long)(g.calls[0] + g.calls[1] + g.calls[2] + g.calls[3])); // <= 32 blocks x 24 words
+    }
+  } // namespace
+
+  void launch_rate_begin(RateDevice *dState, unsigned long long *dCounter, const RateState &first, uint32_t firstErrorFactor, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_rate_begin, dim3(1), dim3(1), 0, s, dState, dCounter, first, firstErrorFactor);
+  }
+
+  void launch_rate_step(RateDevice *dState, unsigned long long *dCounter, uint64_t fixedBytes, const uint32_t *dList, unsigned long long *dListBytes, uint32_t listCount,
+                        hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_rate_step, dim3(1), dim3(1), 0, s, dState, dCounter, (unsigned long long)fixedBytes, dList, dListBytes, listCount);
+  }
+
+  void launch_rate_probe(const RateProbeParams &p, int channels, bool floatFast, hipStream_t s)
+  {
+    const dim3 grid(p.stripsX * p.blocksY), block(kThreads);
+    with_flags([&](auto rgba, auto fast) { hipLaunchKernelGGL((k_rate_probe<rgba ? 4 : 3, fast>), grid, block, 0, s, p); }, channels == 4, floatFast);
+  }
+} // namespace limg_hip

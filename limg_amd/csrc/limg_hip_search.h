@@ -1,5 +1,5 @@
 // limg_hip_search.h -- the E step's shift search (a9-a12): the packed 16-bit trial, the fast and the accurate search automata, and the generic-path search.
-// Included by limg_hip_kernels.hip only, which stays one translation unit (its per-source compile flags cover this code).
+// Included through limg_hip_phase_e.h by limg_hip_kernels.hip and limg_hip_rate.hip, each one translation unit (the same per-source compile flags cover this code).
 #ifndef LIMG_HIP_SEARCH_H
 #define LIMG_HIP_SEARCH_H
 

@@ -100,6 +100,50 @@ namespace
     return limg_hip_success;
   }
 
+  // ---- size probe and budget search (kernels: limg_hip_rate.hip; the search: limg_hip_rate_step.h) ----
+  // the probe kernel's domain: whole 8x8 blocks, the persistent path's float stage (k_fit_tpb), the default search
+  bool rate_probe_applies(const limg_hip_context *c, size_t sizeX, size_t sizeY, int fast)
+  {
+    return (sizeX % kBlock) == 0 && (sizeY % kBlock) == 0 && c->opt.force_split_kernels == 0 && c->opt.legacy_float_stage == 0 && fast != 0;
+  }
+
+  uint64_t stream_fixed_bytes(size_t sizeX, size_t sizeY)
+  {
+    return sizeof(limg_hip_stream_header) + (uint64_t)((sizeX + kBlock - 1) / kBlock) * ((sizeY + kBlock - 1) / kBlock) * sizeof(limg_hip_stream_block);
+  }
+
+  // The records of k_fit_tpb (the `fitOnly` route, which the merged-block encoder's pass 1 also takes) and the probe's parameters on them; the state and the counter.
+  limg_hip_result rate_probe_setup(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, int poolThreads, hipStream_t s, RateProbeParams &rp)
+  {
+    limg_hip_result r;
+    if ((r = c->stream.rateState.ensure(sizeof(RateDevice))) != limg_hip_success) return r;
+    if ((r = c->stream.rateCounter.ensure(8)) != limg_hip_success) return r;
+    EncodeExtra x;
+    x.fitOnly = true; x.fitFloatMode = true;
+    if ((r = encode_device(c, dIn, sizeX, sizeY, hasAlpha, nullptr, nullptr, 0, poolThreads, 1, s, x)) != limg_hip_success) return r;
+    memset(&rp, 0, sizeof(rp));
+    rp.io.in = dIn;
+    rp.sizeX = (uint32_t)sizeX; rp.sizeY = (uint32_t)sizeY; rp.blocksX = (uint32_t)(sizeX / kBlock); rp.blocksY = (uint32_t)(sizeY / kBlock);
+    rp.stripsX = (rp.blocksX + kStripBlocks - 1) / kStripBlocks;
+    rp.vecIn = (sizeX % 4 == 0) && (((uintptr_t)dIn) & 15u) == 0; // as encode_params
+    rp.recordLimit = TOPT(c, record_limit) > 0 ? TOPT(c, record_limit) - 1 : 2700;
+    const bool forced = c->opt.forced_shift[0] >= 0 && c->opt.forced_shift[0] <= 8 && c->opt.forced_shift[1] >= 0 && c->opt.forced_shift[1] <= 8 &&
+                        c->opt.forced_shift[2] >= 0 && c->opt.forced_shift[2] <= 8;
+    for (int i = 0; i < 3; i++) rp.forced[i] = forced ? c->opt.forced_shift[i] : -1;
+    rp.records = (const limg_hip_block_record *)c->enc.records.p; rp.invN = (const float *)c->enc.invN.p;
+    rp.state = (const RateDevice *)c->stream.rateState.p; rp.counter = (unsigned long long *)c->stream.rateCounter.p;
+    return limg_hip_success;
+  }
+
+  // minErrorFactor / maxErrorFactor / maxBytes / pResult of the budget entries -> the bounds of h = errorFactor / 2
+  limg_hip_result budget_bounds(size_t maxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, const limg_hip_budget_result *pResult, uint32_t &hLo, uint32_t &hHi)
+  {
+    const uint32_t lo = minErrorFactor ? minErrorFactor : 2u, hi = maxErrorFactor ? maxErrorFactor : 1024u;
+    if ((lo & 1u) || (hi & 1u) || lo < 2u || hi < 2u || lo > hi || maxBytes == 0 || pResult->struct_size < sizeof(limg_hip_budget_result)) return limg_hip_error_InvalidParameter;
+    hLo = lo / 2u; hHi = hi / 2u;
+    return limg_hip_success;
+  }
+
   // ---- version 2 ----
   // the packer's scratch for the worst case (every block its own rectangle): 4 bytes per block and 8 per 256 blocks; the two timing events
   limg_hip_result ensure_pack_resources(limg_hip_context *c, size_t sizeX, size_t sizeY)
@@ -250,6 +294,130 @@ extern "C"
     if (r != limg_hip_success) return r;
     return decode_stream_host(c, pStream, streamBytes, pOut, outPixels, sizeX, sizeY, total, [&](const uint8_t *dStream, size_t bytes, uint32_t *dOut, size_t w, size_t h) {
       return limg_hip_decode_stream_device(c, dStream, bytes, dOut, w, h, nullptr);
+    });
+  }
+
+  // ---- size probe and budget search (contract: include/limg_hip.h) ----
+  limg_hip_result limg_hip_stream_sizes_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const uint32_t *pErrorFactors, size_t count,
+                                               size_t *pBytes, int poolThreads, int fastBitCrushing, void *stream)
+  {
+    if (!c || !pIn || !pErrorFactors || !pBytes) return limg_hip_error_ArgumentNull;
+    const size_t bound = limg_hip_stream_bound(sizeX, sizeY);
+    if (bound == 0) return limg_hip_error_InvalidParameter;
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    limg_hip_result r;
+    if (!rate_probe_applies(c, sizeX, sizeY, fastBitCrushing))
+    { // one ordinary stream encode per entry, into context staging
+      if ((r = c->stream.buf.ensure(bound)) != limg_hip_success) return r;
+      for (size_t i = 0; i < count; i++)
+        if ((r = limg_hip_encode_stream_device(c, pIn, sizeX, sizeY, hasAlpha, (uint8_t *)c->stream.buf.p, bound, &pBytes[i], pErrorFactors[i], poolThreads, fastBitCrushing,
+                                               stream)) != limg_hip_success)
+          return r;
+      return limg_hip_success;
+    }
+    if ((r = c->stream.rateList.ensure(count * 12)) != limg_hip_success) return r;
+    RateProbeParams rp;
+    if ((r = rate_probe_setup(c, pIn, sizeX, sizeY, hasAlpha, poolThreads, s, rp)) != limg_hip_success) return r;
+    unsigned long long *dBytes = (unsigned long long *)c->stream.rateList.p;
+    uint32_t *dList = (uint32_t *)(dBytes + count);
+    std::vector<uint32_t> list(pErrorFactors, pErrorFactors + count); // (the caller's array may be pageable and may die when the call returns)
+    HIP_TRY(hipMemcpyAsync(dList, list.data(), count * 4, hipMemcpyHostToDevice, s));
+    launch_rate_begin((RateDevice *)c->stream.rateState.p, rp.counter, rate_begin(0, 0, 0), list[0], s);
+    for (size_t i = 0; i < count; i++)
+    {
+      launch_rate_probe(rp, hasAlpha ? 4 : 3, c->opt.float_mode == 1, s);
+      launch_rate_step((RateDevice *)c->stream.rateState.p, rp.counter, stream_fixed_bytes(sizeX, sizeY), dList, dBytes, (uint32_t)count, s);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned long long> sizes(count);
+    HIP_TRY(hipMemcpyAsync(sizes.data(), dBytes, count * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (also: `list` is no longer read)
+    for (size_t i = 0; i < count; i++) pBytes[i] = (size_t)sizes[i];
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_stream_sizes(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const uint32_t *pErrorFactors, size_t count,
+                                        size_t *pBytes, int poolThreads, int fastBitCrushing)
+  {
+    if (!c || !pIn || !pErrorFactors || !pBytes) return limg_hip_error_ArgumentNull;
+    if (limg_hip_stream_bound(sizeX, sizeY) == 0) return limg_hip_error_InvalidParameter;
+    if (count == 0) return limg_hip_success;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    HIP_TRY(hipSetDevice(c->device));
+    limg_hip_result r;
+    if ((r = c->host.in.ensure(sizeX * sizeY * 4)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->host.in.p, pIn, sizeX * sizeY * 4, hipMemcpyHostToDevice));
+    if ((r = limg_hip_stream_sizes_device(c, (const uint32_t *)c->host.in.p, sizeX, sizeY, hasAlpha, pErrorFactors, count, pBytes, poolThreads, fastBitCrushing, nullptr)) !=
+        limg_hip_success)
+      return r;
+    return limg_hip_check_device_status(c);
+  }
+
+  limg_hip_result limg_hip_encode_stream_budget_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                                       size_t maxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                       limg_hip_budget_result *pResult, void *stream)
+  {
+    if (!c || !pIn || !pStream || !pResult) return limg_hip_error_ArgumentNull;
+    const size_t bound = limg_hip_stream_bound(sizeX, sizeY);
+    if (bound == 0) return limg_hip_error_InvalidParameter;
+    if (capacity < bound) return limg_hip_error_OutOfBounds;
+    if (((uintptr_t)pStream & 15u) != 0) return limg_hip_error_InvalidParameter;
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = budget_bounds(maxBytes, minErrorFactor, maxErrorFactor, pResult, hLo, hHi)) != limg_hip_success) return r;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    RateState st = rate_begin(hLo, hHi, maxBytes);
+    size_t bytes = 0;
+    bool written = false; // pStream holds the stream at the result
+    if (rate_probe_applies(c, sizeX, sizeY, fastBitCrushing))
+    { // every launch the search can need, enqueued at once; those behind its end return at once
+      RateProbeParams rp;
+      if ((r = rate_probe_setup(c, pIn, sizeX, sizeY, hasAlpha, poolThreads, s, rp)) != limg_hip_success) return r;
+      launch_rate_begin((RateDevice *)c->stream.rateState.p, rp.counter, st, 2u * st.next, s);
+      for (uint32_t i = 0, n = rate_max_probes(hLo, hHi); i < n; i++)
+      {
+        launch_rate_probe(rp, hasAlpha ? 4 : 3, c->opt.float_mode == 1, s);
+        launch_rate_step((RateDevice *)c->stream.rateState.p, rp.counter, stream_fixed_bytes(sizeX, sizeY), nullptr, nullptr, 0, s);
+      }
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&st, c->stream.rateState.p, sizeof(st), hipMemcpyDeviceToHost, s)); // (RateDevice starts with the search's state)
+      HIP_TRY(hipStreamSynchronize(s));
+      if (!st.done) return limg_hip_error_Generic;
+    }
+    else
+      while (!st.done)
+      { // the same search, a whole stream encode per size
+        const uint32_t h = st.next;
+        if ((r = limg_hip_encode_stream_device(c, pIn, sizeX, sizeY, hasAlpha, pStream, capacity, &bytes, 2u * h, poolThreads, fastBitCrushing, stream)) != limg_hip_success) return r;
+        rate_step(st, bytes);
+        written = st.done && st.next == h;
+      }
+    if (!written && (r = limg_hip_encode_stream_device(c, pIn, sizeX, sizeY, hasAlpha, pStream, capacity, &bytes, 2u * st.next, poolThreads, fastBitCrushing, stream)) != limg_hip_success)
+      return r;
+    pResult->errorFactor = 2u * st.next; pResult->probes = st.probes; pResult->withinBudget = st.within; pResult->bytes = bytes;
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_encode_stream_budget(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                                size_t maxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                limg_hip_budget_result *pResult)
+  {
+    if (!c || !pIn || !pStream || !pResult) return limg_hip_error_ArgumentNull;
+    if (limg_hip_stream_bound(sizeX, sizeY) == 0) return limg_hip_error_InvalidParameter;
+    uint32_t hLo, hHi;
+    const limg_hip_result ok = budget_bounds(maxBytes, minErrorFactor, maxErrorFactor, pResult, hLo, hHi);
+    if (ok != limg_hip_success) return ok;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    size_t bytes = 0;
+    return encode_stream_host(c, pIn, sizeX, sizeY, pStream, capacity, &bytes, limg_hip_stream_bound(sizeX, sizeY), [&](const uint32_t *dIn, uint8_t *dStream, size_t bound, size_t *n) {
+      const limg_hip_result r = limg_hip_encode_stream_budget_device(c, dIn, sizeX, sizeY, hasAlpha, dStream, bound, maxBytes, minErrorFactor, maxErrorFactor, poolThreads,
+                                                                     fastBitCrushing, pResult, nullptr);
+      if (r == limg_hip_success) *n = (size_t)pResult->bytes;
+      return r;
     });
   }
 

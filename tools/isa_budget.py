@@ -22,7 +22,7 @@ sys.path.insert(0, ROOT)
 from limg_amd.build import CSRC, compile_line  # noqa: E402  (the objects' own compile line)
 
 # the encode path's device code: limg_hip_kernels.hip and the headers only it includes, then the helpers it shares with the other kernel files
-ENCODE_FILES = ["limg_hip_kernels.hip", "limg_hip_search.h", "limg_hip_phase_f.h", "limg_hip_float_pixel.h", "limg_hip_lookback.h", "limg_hip_device.h"]
+ENCODE_FILES = ["limg_hip_kernels.hip", "limg_hip_phase_e.h", "limg_hip_search.h", "limg_hip_phase_f.h", "limg_hip_float_pixel.h", "limg_hip_lookback.h", "limg_hip_device.h"]
 
 
 def function_ranges(path):

@@ -230,11 +230,13 @@ struct Options
   uint32_t errorFactor = 100;
   size_t repeat = 1, threads = 0;
   std::string outDir = ".", streamPath, blockedStreamPath;
+  uint64_t maxBytes = 0;                                // `--max-bytes`: `--stream` is encoded to this byte budget
+  uint32_t minErrorFactor = 0, maxErrorFactor = 0;      // ... its search range (0: the library's defaults, 2 and 1024)
 };
 
 static const char *const kUsage =
     "Usage:\nlimg_hip_cli [<InputFile> | --] [--no-output | --error-factor <Factor> | --accurate-bit-crushing | --single-thread | --fixed-blocks | --threads <T> | --out-dir <dir> | "
-    "--stream <file> | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n"
+    "--stream <file> [--max-bytes <N> [--min-error-factor <A>] [--max-error-factor <B>]] | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n"
     "limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n";
 
 static bool parse_number(const char *text, uint64_t &value)
@@ -267,6 +269,9 @@ static bool parse_args(int argc, const char **argv, Options &o)
     else if (a == "--out-dir" && hasValue) o.outDir = argv[++i];
     else if (a == "--stream" && hasValue) o.streamPath = argv[++i];
     else if (a == "--blocked-stream" && hasValue) o.blockedStreamPath = argv[++i];
+    else if (a == "--max-bytes" && hasValue && parse_number(argv[i + 1], v)) { o.maxBytes = v; i++; }
+    else if (a == "--min-error-factor" && hasValue && parse_number(argv[i + 1], v)) { o.minErrorFactor = (uint32_t)v; i++; }
+    else if (a == "--max-error-factor" && hasValue && parse_number(argv[i + 1], v)) { o.maxErrorFactor = (uint32_t)v; i++; }
     else if ((a == "--count" || a == "--") && hasValue)
     {
       if (!listMode) { printf("'%s' is only supported with input file '--', found '%s'.\n", a.c_str(), argv[1]); return false; }
@@ -282,6 +287,11 @@ static bool parse_args(int argc, const char **argv, Options &o)
     if (o.files.empty()) { printf("No files given after '--'.\n"); return false; }
     o.writeImages = false;
     o.mode = (o.files.size() == 1 && o.repeat > 1) ? Options::BenchmarkOneFile : Options::BenchmarkList;
+  }
+  if ((o.maxBytes || o.minErrorFactor || o.maxErrorFactor) && (o.streamPath.empty() || !o.maxBytes))
+  {
+    printf("'--max-bytes' is the byte budget of '--stream'; '--min-error-factor' / '--max-error-factor' bound its search.\n");
+    return false;
   }
   if (o.threads == 0 && o.usePool) o.threads = limg_threading_max_threads() ? limg_threading_max_threads() : 1;
   return true;
@@ -355,12 +365,26 @@ static void write_planes(const Options &o, const Image &img, Planes &p)
   write_tga(d + "limg_block_idx.tga", img.w, img.h, 4, p.blockIndex.data());
 }
 
-// `--stream`: the compact stream belongs to the fixed-8x8 path, so its decode is checked against that path's image
+// `--stream`: the compact stream belongs to the fixed-8x8 path, so its decode is checked against that path's image.  With `--max-bytes` the error factor is the one
+// limg_encode_budget chooses for that many bytes ('--error-factor' then only applies to the planes), and the check is against the 8x8 path at that error factor.
 static bool write_and_check_stream(const Options &o, const Image &img, limg_thread_pool *pool, const std::vector<uint32_t> *fixedDecoded)
 {
   std::vector<uint8_t> stream(limg_encode_bound(img.w, img.h));
   size_t bytes = 0;
-  limg_result r = limg_encode(img.px.data(), img.w, img.h, img.hasAlpha, stream.data(), stream.size(), &bytes, o.errorFactor, pool, o.fastBitCrushing);
+  uint32_t errorFactor = o.errorFactor;
+  limg_result r;
+  if (o.maxBytes)
+  {
+    bool within = false;
+    uint32_t probes = 0;
+    r = limg_encode_budget(img.px.data(), img.w, img.h, img.hasAlpha, stream.data(), stream.size(), &bytes, (size_t)o.maxBytes, &errorFactor, &within, &probes,
+                           o.minErrorFactor, o.maxErrorFactor, pool, o.fastBitCrushing);
+    if (r != limg_success) FAIL(EXIT_FAILURE, "limg_encode_budget failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
+    printf("Budget: %" PRIu64 " bytes; error factor %" PRIu32 " after %" PRIu32 " size probes; %" PRIu64 " bytes; budget %s.\n", o.maxBytes, errorFactor, probes,
+           (uint64_t)bytes, within ? "met" : "NOT met");
+    if (errorFactor != o.errorFactor) fixedDecoded = nullptr; // (the planes were encoded at '--error-factor')
+  }
+  else r = limg_encode(img.px.data(), img.w, img.h, img.hasAlpha, stream.data(), stream.size(), &bytes, o.errorFactor, pool, o.fastBitCrushing);
   if (r != limg_success) FAIL(EXIT_FAILURE, "limg_encode failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
   std::vector<uint32_t> again(img.count());
   r = limg_decode(stream.data(), bytes, again.data(), again.size());
@@ -370,7 +394,7 @@ static bool write_and_check_stream(const Options &o, const Image &img, limg_thre
   {
     Planes tmp(img.count());
     limg_encode3d_info fi = tmp.fixed_info();
-    r = limg_encode3d_test(img.px.data(), img.w, img.h, img.hasAlpha, &fi, o.errorFactor, pool, o.fastBitCrushing);
+    r = limg_encode3d_test(img.px.data(), img.w, img.h, img.hasAlpha, &fi, errorFactor, pool, o.fastBitCrushing);
     if (r != limg_success) FAIL(EXIT_FAILURE, "limg_encode3d_test failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
     own.swap(tmp.decoded);
     fixedDecoded = &own;
