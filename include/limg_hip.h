@@ -392,6 +392,48 @@ limg_hip_result limg_hip_encode_stream_budget(limg_hip_context *pCtx, const uint
                                               size_t maxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
                                               limg_hip_budget_result *pResult);
 
+/* ---- budgeted stream encode of a list: one search per image, the probes of all images in the same launches ------------------------
+ * "Compress these `count` same-shape images to at most pMaxBytes[i] bytes each": the product of the batched stream encode and the budget entries above.
+ * Result, for every i: pResults[i] holds exactly what limg_hip_encode_stream_budget_device puts in *pResult for image i with maxBytes = pMaxBytes[i] and the same
+ * bounds, arguments and options; ppStreams[i] is byte for byte limg_hip_encode_stream_device's stream at pResults[i].errorFactor.
+ * Independence: every image runs its own search (rate_begin / rate_step of the algorithm above); one image's outcome -- refused, met at the lower bound, bisected --
+ * never touches another's.  minErrorFactor / maxErrorFactor are shared by the list; the budgets are per image.  pMaxBytes and pResults are HOST arrays of `count`
+ * entries in both forms; set struct_size in EVERY pResults[i] before the call.
+ * Errors, all before anything touches the device -- a refused call writes nothing to any stream or result -- in this order: (1) those of
+ * limg_hip_encode_stream_batch_device in its order, pMaxBytes and pResults counted among the pointers; (2) the bound rules above (odd, below 2, min > max):
+ * limg_hip_error_InvalidParameter; (3) any pMaxBytes[i] == 0 or any struct_size below the struct's: limg_hip_error_InvalidParameter, whichever i it is; (4) count == 0:
+ * limg_hip_success with nothing done.
+ * Cost: lists go chunk by chunk by the rule of limg_hip_encode3d_batch_device (1 GiB of block records, 32-bit strip ids).  Per chunk: the image table and ONE k_fit_tpb
+ * grid over all its images (records in the context's float mode), one k_rate_begin_batch per 64 images, then 2 + ceil(log2(hHi - hLo)) pairs of k_rate_probe_batch
+ * (one workgroup per image and work strip; the workgroups of an image whose search is over return at their first load) and k_rate_step_batch, ONE copy of the chunk's
+ * states and ONE wait -- whatever the chunk's length: for 64 images over the default bounds 2 table launches, the float stage, one begin and 22 probe / step launches
+ * with one wait, where 64 single calls are 64 x 24 launches and 64 waits.  Then the chunk's images are grouped by the error factor their searches chose: a group of two or more is one limg_hip_encode_stream_batch_device, a group of
+ * one is one limg_hip_encode_stream_device.  pResults[i].bytes is the size the probe measured at the result, which is the stream's totalBytes: no wait follows the
+ * encodes.  A chunk of one image takes the single call.
+ * Synchronisation: the device form SYNCHRONISES `stream` once per chunk, for that chunk's search states; it cannot be captured into a graph.  The streams themselves
+ * are complete in stream order behind the call.
+ * Fallback: where the single call has no probe kernel (partial edge blocks, force_split_kernels, legacy_float_stage, fastBitCrushing == 0) and for count == 1 the call
+ * is the loop of single budget calls: the same results by construction.
+ * Options: as the single call.  limg_hip_last_stats after these entries is that of the last group encoded.
+ * Context memory, besides what limg_hip_encode_stream_batch_device holds for the longest chunk: 72 bytes of state (sizeof RateDevice: the 48-byte search state, the list
+ * position and the thresholds) + 8 bytes of counter = 80 bytes per image of the longest chunk (streamRateState, streamRateCounter); the probes read the images through
+ * the batched encode's own table (96 bytes per image of a chunk, no second table).  limg_hip_context_device_bytes reports all of it.
+ * Out of scope: per-image error factors inside ONE persistent launch (the thresholds are kernel arguments of the encode kernel, so the final encodes batch only over
+ * images that chose the same error factor); a batched limg_hip_stream_sizes; lists of mixed shapes; version 2 streams; the CLI, which encodes one file. */
+/* DEVICE pointers; ppIn / ppStreams are HOST arrays of `count` device pointers (streams 16-byte aligned, capacityEach >= limg_hip_stream_bound) and, as pMaxBytes, may
+ * be freed when the call returns.  Waits for `stream`. */
+limg_hip_result limg_hip_encode_stream_budget_batch_device(limg_hip_context *pCtx, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                           uint8_t *const *ppStreams, size_t capacityEach, const size_t *pMaxBytes /* host, count */,
+                                                           uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                           limg_hip_budget_result *pResults /* host, count, struct_size set in each */, void *stream);
+/* HOST images and HOST stream buffers, blocking, under the context's mutex.  Uploads the list, runs the device form into context staging (as
+ * limg_hip_encode_stream_batch) and downloads pResults[i].bytes of each stream.  capacityEach may be below the bound: where it is below some pResults[i].bytes, all
+ * results are filled, NO stream is written and limg_hip_error_OutOfBounds is returned -- the single host call's rule. */
+limg_hip_result limg_hip_encode_stream_budget_batch(limg_hip_context *pCtx, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                    uint8_t *const *ppStreams, size_t capacityEach, const size_t *pMaxBytes /* host, count */,
+                                                    uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                    limg_hip_budget_result *pResults /* host, count, struct_size set in each */);
+
 /* ---- compact stream, version 2: the merged-block encoder's rectangles --------------------------------------------------------
  * What limg_hip_blocked_encode3d computes -- the rectangles of merged 8x8 blocks, each with ONE record, ONE shift triple and its crushed factor values -- in the same
  * "LMG3" container, so that decode(blocked_encode_stream(image)) equals the pDecoded plane of `limg_blocked_encode3d_test` bit for bit.  Version 1 streams and their

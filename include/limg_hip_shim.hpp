@@ -210,6 +210,32 @@ inline limg_result limg_encode_batch(const uint32_t *const *ppIn, const size_t c
                                                    limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0);
 }
 
+// limg_encode_batch to byte budgets (limg_hip.h "budgeted stream encode of a list"): image i gets the stream limg_encode_budget writes for it with pMaxBytes[i], every
+// image on a search of its own over the shared [minErrorFactor, maxErrorFactor].  pOutSizes[i], pErrorFactors[i]: what was chosen and what it takes; pWithinBudget[i],
+// pProbes[i] (arrays of `count`, may be NULL) as limg_encode_budget's.  outCapacityEach below some pOutSizes[i]: limg_error_OutOfBounds with all sizes filled and
+// nothing written to any ppOut[i].
+inline limg_result limg_encode_budget_batch(const uint32_t *const *ppIn, const size_t count, const size_t sizeX, const size_t sizeY, const bool hasAlpha, uint8_t *const *ppOut,
+                                            const size_t outCapacityEach, size_t *pOutSizes, const size_t *pMaxBytes, uint32_t *pErrorFactors, bool *pWithinBudget = nullptr,
+                                            uint32_t *pProbes = nullptr, const uint32_t minErrorFactor = 0, const uint32_t maxErrorFactor = 0,
+                                            limg_thread_pool *pThreadPool = nullptr, const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (!pOutSizes || !pErrorFactors) return limg_error_ArgumentNull;
+  const limg_hip_budget_result blank = { sizeof(limg_hip_budget_result), 0, 0, 0, 0 };
+  std::vector<limg_hip_budget_result> res(count ? count : 1, blank);
+  const limg_result r = (limg_result)limg_hip_encode_stream_budget_batch(c, count, ppIn, sizeX, sizeY, hasAlpha ? 1 : 0, ppOut, outCapacityEach, pMaxBytes, minErrorFactor,
+                                                                         maxErrorFactor, limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0, res.data());
+  if (r != limg_success && r != limg_error_OutOfBounds) return r;
+  for (size_t i = 0; i < count; i++)
+  {
+    pOutSizes[i] = (size_t)res[i].bytes; pErrorFactors[i] = res[i].errorFactor;
+    if (pWithinBudget) pWithinBudget[i] = res[i].withinBudget != 0;
+    if (pProbes) pProbes[i] = res[i].probes;
+  }
+  return r;
+}
+
 // either version of the stream: version 1 (limg_encode) or version 2 (limg_blocked_encode)
 inline limg_result limg_decode_info(const uint8_t *pIn, const size_t size, size_t *pSizeX, size_t *pSizeY, bool *pHasAlpha)
 {

@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "limg_hip_stream_bound", "limg_hip_encode_stream_device", "limg_hip_decode_stream_device", "limg_hip_encode_stream", "limg_hip_decode_stream",
     "limg_hip_stream_info", "limg_hip_encode_stream_batch_device", "limg_hip_encode_stream_batch",
     "limg_hip_stream_sizes_device", "limg_hip_stream_sizes", "limg_hip_encode_stream_budget_device", "limg_hip_encode_stream_budget",
+    "limg_hip_encode_stream_budget_batch_device", "limg_hip_encode_stream_budget_batch",
     "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
     "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
     "limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device", "limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window",
@@ -275,6 +276,12 @@ def load_library(path=None):
     L.limg_hip_encode_stream_budget.restype = C.c_int
     L.limg_hip_encode_stream_budget.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
                                                 C.c_void_p]
+    L.limg_hip_encode_stream_budget_batch_device.restype = C.c_int  # ctx, count, ins, sizeX, sizeY, hasAlpha, streams, capacityEach, budgets (host), min ef, max ef, pool, fast, results, hipStream
+    L.limg_hip_encode_stream_budget_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
+                                                             C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.limg_hip_encode_stream_budget_batch.restype = C.c_int
+    L.limg_hip_encode_stream_budget_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                      C.c_int, C.c_int, C.c_void_p]
     L.limg_hip_blocked_stream_bound.restype = C.c_size_t
     L.limg_hip_blocked_stream_bound.argtypes = [C.c_size_t, C.c_size_t]
     L.limg_hip_blocked_encode_stream_device.restype = C.c_int
@@ -739,6 +746,53 @@ class LimgHip:
                           (C.c_void_p * n)(*[o.data_ptr() for o in outs]), min(o.numel() for o in outs), sizes if want_sizes else None, error_factor, pool_threads, int(fast),
                           self._stream())
         return outs, ([int(v) for v in sizes] if want_sizes else None)
+
+    # ---- budgeted stream encode of a list: result i = encode_stream_budget of image i with its budget (contract: include/limg_hip.h) ----
+    @staticmethod
+    def _budget_list(max_bytes, n):
+        budgets = [int(max_bytes)] * n if np.isscalar(max_bytes) else [int(b) for b in max_bytes]
+        assert len(budgets) == n
+        results = (BudgetResult * max(n, 1))()
+        for r in results:
+            r.struct_size = C.sizeof(BudgetResult)
+        return (C.c_size_t * max(n, 1))(*budgets), results
+
+    def encode_stream_budget_batch(self, imgs, has_alpha, max_bytes, min_error_factor=0, max_error_factor=0, pool_threads=0, fast=True):
+        """host uint32 images of one shape, max_bytes an int or one per image -> (list of stream bytes (numpy uint8), list of BudgetResult), one batched call"""
+        imgs = [np.ascontiguousarray(i, dtype=np.uint32) for i in imgs]
+        n = len(imgs)
+        budgets, results = self._budget_list(max_bytes, n)
+        if n == 0:
+            self._stream_call("limg_hip_encode_stream_budget_batch", 0, (C.c_void_p * 1)(), 8, 8, int(has_alpha), (C.c_void_p * 1)(), self.stream_bound(8, 8), budgets,
+                              min_error_factor, max_error_factor, pool_threads, int(fast), results)
+            return [], []
+        h, w = imgs[0].shape
+        assert all(i.shape == (h, w) for i in imgs)
+        cap = self.stream_bound(w, h)
+        outs = [np.zeros(cap, dtype=np.uint8) for _ in range(n)]
+        self._stream_call("limg_hip_encode_stream_budget_batch", n, (C.c_void_p * n)(*[i.ctypes.data for i in imgs]), w, h, int(has_alpha),
+                          (C.c_void_p * n)(*[o.ctypes.data for o in outs]), cap, budgets, min_error_factor, max_error_factor, pool_threads, int(fast), results)
+        return [o[:results[k].bytes].copy() for k, o in enumerate(outs)], list(results)
+
+    def encode_stream_budget_batch_device(self, imgs, has_alpha, max_bytes, min_error_factor=0, max_error_factor=0, outs=None, pool_threads=0, fast=True):
+        """imgs: list of torch int32 CUDA tensors (h, w) of one shape, max_bytes an int or one per image -> (list of torch uint8 CUDA stream buffers of worst-case size,
+        list of BudgetResult).  outs: the buffers to use (each at least stream_bound(w, h) bytes).  Waits for torch's current stream."""
+        import torch
+        n = len(imgs)
+        budgets, results = self._budget_list(max_bytes, n)
+        if n == 0:
+            self._stream_call("limg_hip_encode_stream_budget_batch_device", 0, (C.c_void_p * 1)(), 8, 8, int(has_alpha), (C.c_void_p * 1)(), self.stream_bound(8, 8), budgets,
+                              min_error_factor, max_error_factor, pool_threads, int(fast), results, self._stream())
+            return [], []
+        h, w = imgs[0].shape
+        assert all(tuple(i.shape) == (h, w) for i in imgs)
+        if outs is None:
+            outs = [torch.empty(self.stream_bound(w, h), dtype=torch.uint8, device=imgs[0].device) for _ in range(n)]
+        assert len(outs) == n
+        self._stream_call("limg_hip_encode_stream_budget_batch_device", n, (C.c_void_p * n)(*[i.data_ptr() for i in imgs]), w, h, int(has_alpha),
+                          (C.c_void_p * n)(*[o.data_ptr() for o in outs]), min(o.numel() for o in outs), budgets, min_error_factor, max_error_factor, pool_threads,
+                          int(fast), results, self._stream())
+        return outs, list(results)
 
     def blocked_stream_bound(self, w, h):
         return self.lib.limg_hip_blocked_stream_bound(w, h)

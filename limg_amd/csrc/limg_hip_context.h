@@ -232,6 +232,7 @@ namespace limg_hip
     // batch (host array of batchCount entries, batchCount > 1): the images of a batched encode -- same shape, whole 8x8 blocks, all 11 planes (or, from the batched
     // stream encode, the three factor planes only: streamRaw, stripWords and both compact outputs set) -- in one launch
     // pair (or, limg_hip_options.batch_sub_images, a pipeline of launch pairs); dIn / dInfo are then those of image 0.  The caller has checked all of that.
+    // With fitOnly (no planes at all): k_fit_tpb's one grid over the list, records and invN image after image in the context's scratch -- the budgeted list's probes.
     const ImageIO *batch = nullptr;
     size_t batchCount = 1;
     // ---- a sub-image of a larger encode (the two parts of an image whose last block row is partial: encode_height_ragged) ----

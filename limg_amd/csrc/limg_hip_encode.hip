@@ -421,7 +421,9 @@ namespace limg_hip
     // a list in compact mode only as the batched stream encode hands it over: raw-escaped factor bytes, the strips' payload words, records and shift words all in
     // raster arrays that run image after image (what its scan and packer read)
     const bool compactList = !fullPlanes && x.streamRaw && x.stripWords && compact && compact->pRecords && compact->pShifts;
-    if (batchCount > 1 && (!e.fused || !e.p.prefit || (!fullPlanes && !compactList))) return limg_hip_error_InvalidParameter; // (limg_hip_encode3d_batch_device sends such lists through one encode per image instead)
+    // ... or for its records alone (the size probes of a budgeted list): k_fit_tpb's batched grid and nothing else
+    const bool fitList = e.p.fitOnly && e.p.prefit && !ragged && chainPhase == 0;
+    if (batchCount > 1 && !fitList && (!e.fused || !e.p.prefit || (!fullPlanes && !compactList))) return limg_hip_error_InvalidParameter; // (limg_hip_encode3d_batch_device sends such lists through one encode per image instead)
     if (e.fused && (r = fused_scratch(e, compact)) != limg_hip_success) return r;
 
     const size_t subImages = sub_batch_images(e);

@@ -321,6 +321,27 @@ namespace limg_hip
   void launch_rate_step(RateDevice *dState, unsigned long long *dCounter, uint64_t fixedBytes, const uint32_t *dList, unsigned long long *dListBytes, uint32_t listCount,
                         hipStream_t s);
   void launch_rate_probe(const RateProbeParams &p, int channels, bool floatFast, hipStream_t s);
+  // The list form (limg_hip_encode_stream_budget_batch*): `nImages` images of one shape, each on a search of its own.  states[i] / counters[i] are image i's; the
+  // records and invN of k_fit_tpb's batched grid run image after image (image i owns block rows [i * blocksY, (i + 1) * blocksY)); image i's pixels are batch[i].in,
+  // an entry of the batched encode's device table.  The members the E step's stages read carry EncodeParams' names.
+  struct RateProbeBatchParams
+  {
+    const ImageIO *batch;
+    uint32_t nImages, imageStrips;
+    uint32_t sizeX, sizeY, blocksX, blocksY, stripsX;
+    int32_t vecIn;
+    int32_t recordLimit;
+    int32_t forced[3];
+    const limg_hip_block_record *records;
+    const float *invN;
+    const RateDevice *states;
+    unsigned long long *counters;
+  };
+  struct RateBudgetChunk { uint32_t n; unsigned long long maxBytes[64]; }; // k_rate_begin_batch's budgets, as kernel arguments
+  // hMaxBytes: HOST array of `count` budgets (may die when the call returns); every search runs over [hLo, hHi]
+  void launch_rate_begin_batch(RateDevice *dStates, unsigned long long *dCounters, const uint64_t *hMaxBytes, size_t count, uint32_t hLo, uint32_t hHi, hipStream_t s);
+  void launch_rate_step_batch(RateDevice *dStates, unsigned long long *dCounters, uint32_t nImages, uint64_t fixedBytes, hipStream_t s);
+  void launch_rate_probe_batch(const RateProbeBatchParams &p, int channels, bool floatFast, hipStream_t s);
 
   void launch_synth_random_gradient(uint32_t *out, uint32_t w, uint32_t h, uint64_t seed, int opaque, uint32_t y0, hipStream_t s);
   void launch_synth_photo_noise(uint32_t *out, uint32_t w, uint32_t h, uint64_t seed, uint32_t y0, hipStream_t s);

@@ -10,6 +10,10 @@
 // counted words into the next thresholds: a list of error factors (limg_hip_stream_sizes*) or the search of limg_hip_rate_step.h (limg_hip_encode_stream_budget*).  So
 // all launches of a call are enqueued at once, with no host round trip between them; probes behind the end of a search return at once.
 // Progress: no workgroup waits for another one -- no look-back, no spin, no ticket; a workgroup's only global write is one 64-bit atomic add.
+//
+// The *_batch kernels are the same three for a LIST of same-shape images (limg_hip_encode_stream_budget_batch*): one RateDevice and one counter per image, one probe
+// workgroup per (image, work strip) over records that run image after image, every image on a search of its own.  The probe's body is written once
+// (rate_probe_strip) and takes what differs -- the image's pixels, state, counter and its block rows in the records -- as arguments.
 #include "limg_hip_phase_e.h"
 
 namespace limg_hip
@@ -57,18 +61,19 @@ namespace limg_hip
       if (!d->search.done) set_thresholds(d, 2u * d->search.next);
     }
 
-    template <int CH, bool FAST>
-    __global__ __launch_bounds__(kThreads, 6) void k_rate_probe(const RateProbeParams p)
+    // One work strip's probe: strip `strip` of block row `by` of the image whose pixels are io.in; byS: that row in p.records / p.invN.  P: RateProbeParams or
+    // RateProbeBatchParams; everything but `lane`-derived values is wave-uniform.
+    template <int CH, bool FAST, class P, class IO>
+    __device__ __forceinline__ void rate_probe_strip(const P &p, const IO &io, const RateDevice *const st, unsigned long long *const counter, uint8_t *const lds,
+                                                     const uint32_t strip, const uint32_t by, const uint32_t byS)
     {
       constexpr LdsLayout LL = lds_layout<true>();
-      __shared__ __attribute__((aligned(16))) uint8_t lds[LL.total];
-      const RateDevice *const st = p.state;
       if (st->search.done) return; // (uniform: the step kernel in front of this launch wrote it)
       const uint32_t maxPixel32 = (uint32_t)sgpr((int)st->maxPixel32), blockLimit = (uint32_t)sgpr((int)st->blockLimitFull), crushBits = (uint32_t)sgpr((int)st->crushBits);
       const int tid = (int)threadIdx.x;
       EStrip g;
       g.tid = tid; g.lane = tid & 63; g.wave = tid >> 6;
-      g.strip = blockIdx.x % p.stripsX; g.by = blockIdx.x / p.stripsX; g.byS = g.by;
+      g.strip = strip; g.by = by; g.byS = byS;
       g.x0 = g.strip * (kStripBlocks * kBlock); g.y0 = g.by * kBlock;
       g.stripW = min(p.sizeX - g.x0, (uint32_t)(kStripBlocks * kBlock)); g.ry = (uint32_t)kBlock; // whole blocks
       g.pix = reinterpret_cast<uint32_t *>(lds + kLdsStrip); g.V = reinterpret_cast<float *>(lds + LL.v); g.blk = reinterpret_cast<BlkF *>(lds + LL.blk);
@@ -77,7 +82,7 @@ namespace limg_hip
 
       uint32_t recVal[2] = { 0u, 0u };
       request_prefit_records(p, g, recVal);
-      stage_strip_pixels(p, p.io, g);
+      stage_strip_pixels(p, io, g);
       __syncthreads();
       take_prefit_records<false>(p, g, recVal, nullptr);
       phase_e_view<CH, FAST, true>(g);
@@ -144,7 +149,51 @@ namespace limg_hip
       }
       if (lane == 0) g.calls[g.wave] = waveWords;
       __syncthreads();
-      if (tid == 0) atomicAdd(p.counter, (unsigned long long)(g.calls[0] + g.calls[1] + g.calls[2] + g.calls[3])); // <= 32 blocks x 24 words
+      if (tid == 0) atomicAdd(counter, (unsigned long long)(g.calls[0] + g.calls[1] + g.calls[2] + g.calls[3])); // <= 32 blocks x 24 words
+    }
+
+    template <int CH, bool FAST>
+    __global__ __launch_bounds__(kThreads, 6) void k_rate_probe(const RateProbeParams p)
+    {
+      __shared__ __attribute__((aligned(16))) uint8_t lds[lds_layout<true>().total];
+      rate_probe_strip<CH, FAST>(p, p.io, p.state, p.counter, lds, blockIdx.x % p.stripsX, blockIdx.x / p.stripsX, blockIdx.x / p.stripsX);
+    }
+
+    // ---- a list of images: one search per image ----
+    // thread i: image i's search over [hLo, hHi] for its budget, the thresholds of its first probe (2 hHi), an empty counter
+    __global__ void k_rate_begin_batch(RateDevice *d, unsigned long long *counters, const RateBudgetChunk budgets, const uint32_t hLo, const uint32_t hHi)
+    {
+      const uint32_t i = threadIdx.x;
+      if (i >= budgets.n) return;
+      d[i].search = rate_begin(hLo, hHi, budgets.maxBytes[i]);
+      d[i].listNext = 0u;
+      set_thresholds(d + i, 2u * hHi);
+      counters[i] = 0ull;
+    }
+
+    // thread i: k_rate_step's search form for image i
+    __global__ void k_rate_step_batch(RateDevice *d, unsigned long long *counters, const uint32_t nImages, const unsigned long long fixedBytes)
+    {
+      const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+      if (i >= nImages) return;
+      const unsigned long long bytes = fixedBytes + 8ull * counters[i];
+      counters[i] = 0ull;
+      if (d[i].search.done) return;
+      rate_step(d[i].search, bytes);
+      if (!d[i].search.done) set_thresholds(d + i, 2u * d[i].search.next);
+    }
+
+    // One workgroup per (image, work strip); the image index is wave-uniform, and the image's pixels come from its entry of the device table through the constant
+    // address space (scalar loads, as the persistent kernel's io_of).  A workgroup of an image whose search is over returns at its first load.
+    template <int CH, bool FAST>
+    __global__ __launch_bounds__(kThreads, 6) void k_rate_probe_batch(const RateProbeBatchParams p)
+    {
+      __shared__ __attribute__((aligned(16))) uint8_t lds[lds_layout<true>().total];
+      const uint32_t img = blockIdx.x / p.imageStrips, local = blockIdx.x - img * p.imageStrips; // (the grid is nImages * imageStrips workgroups)
+      typedef const __attribute__((address_space(4))) ImageIO KernIO;
+      KernIO *const io = (KernIO *)p.batch + img;
+      const uint32_t by = local / p.stripsX;
+      rate_probe_strip<CH, FAST>(p, *io, p.states + img, p.counters + img, lds, local - by * p.stripsX, by, img * p.blocksY + by);
     }
   } // namespace
 
@@ -163,5 +212,27 @@ namespace limg_hip
   {
     const dim3 grid(p.stripsX * p.blocksY), block(kThreads);
     with_flags([&](auto rgba, auto fast) { hipLaunchKernelGGL((k_rate_probe<rgba ? 4 : 3, fast>), grid, block, 0, s, p); }, channels == 4, floatFast);
+  }
+
+  void launch_rate_begin_batch(RateDevice *dStates, unsigned long long *dCounters, const uint64_t *hMaxBytes, size_t count, uint32_t hLo, uint32_t hHi, hipStream_t s)
+  {
+    for (size_t i0 = 0; i0 < count; i0 += 64)
+    { // the budgets through kernel arguments: stream-ordered, and the host array may die right away
+      RateBudgetChunk ch;
+      ch.n = (uint32_t)(count - i0 < 64 ? count - i0 : 64);
+      for (uint32_t i = 0; i < 64; i++) ch.maxBytes[i] = i < ch.n ? (unsigned long long)hMaxBytes[i0 + i] : 0ull;
+      hipLaunchKernelGGL(k_rate_begin_batch, dim3(1), dim3(64), 0, s, dStates + i0, dCounters + i0, ch, hLo, hHi);
+    }
+  }
+
+  void launch_rate_step_batch(RateDevice *dStates, unsigned long long *dCounters, uint32_t nImages, uint64_t fixedBytes, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_rate_step_batch, dim3((nImages + 63u) / 64u), dim3(64), 0, s, dStates, dCounters, nImages, (unsigned long long)fixedBytes);
+  }
+
+  void launch_rate_probe_batch(const RateProbeBatchParams &p, int channels, bool floatFast, hipStream_t s)
+  {
+    const dim3 grid(p.nImages * p.imageStrips), block(kThreads);
+    with_flags([&](auto rgba, auto fast) { hipLaunchKernelGGL((k_rate_probe_batch<rgba ? 4 : 3, fast>), grid, block, 0, s, p); }, channels == 4, floatFast);
   }
 } // namespace limg_hip

@@ -4,6 +4,7 @@
 // decode.  What the two versions do alike is written once, in the anonymous namespace below.  The window entries: limg_hip_stream_window_api.hip.
 #include "limg_hip_context.h"
 
+#include <algorithm>
 #include <vector>
 
 using namespace limg_hip;
@@ -141,6 +142,19 @@ namespace
     const uint32_t lo = minErrorFactor ? minErrorFactor : 2u, hi = maxErrorFactor ? maxErrorFactor : 1024u;
     if ((lo & 1u) || (hi & 1u) || lo < 2u || hi < 2u || lo > hi || maxBytes == 0 || pResult->struct_size < sizeof(limg_hip_budget_result)) return limg_hip_error_InvalidParameter;
     hLo = lo / 2u; hHi = hi / 2u;
+    return limg_hip_success;
+  }
+
+  // ... of the list entries: the bound rules first (they hold for an empty list too), then every image's budget and result
+  limg_hip_result budget_list_checks(size_t count, const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, const limg_hip_budget_result *pResults,
+                                     uint32_t &hLo, uint32_t &hHi)
+  {
+    limg_hip_budget_result whole;
+    whole.struct_size = sizeof(whole);
+    const limg_hip_result r = budget_bounds(1, minErrorFactor, maxErrorFactor, &whole, hLo, hHi);
+    if (r != limg_hip_success) return r;
+    for (size_t i = 0; i < count; i++)
+      if (pMaxBytes[i] == 0 || pResults[i].struct_size < sizeof(limg_hip_budget_result)) return limg_hip_error_InvalidParameter;
     return limg_hip_success;
   }
 
@@ -550,6 +564,179 @@ extern "C"
       return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
     for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], dStreams[i], pBytes[i], hipMemcpyDeviceToHost)); // totalBytes of each, not the capacity
+    return limg_hip_success;
+  }
+
+  // ---- budgeted stream encode of a list: result i = limg_hip_encode_stream_budget_device of image i with pMaxBytes[i] (contract: include/limg_hip.h) ----
+  // Chunk by chunk (the plane batch's rule): the records of the chunk from ONE k_fit_tpb grid, one search state and one counter per image, the whole chunk's searches
+  // as 1 + 2 x rate_max_probes launches and ONE wait; then one stream encode per distinct error factor the searches chose.
+  limg_hip_result limg_hip_encode_stream_budget_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                             uint8_t *const *ppStreams, size_t capacityEach, const size_t *pMaxBytes, uint32_t minErrorFactor,
+                                                             uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults, void *stream)
+  {
+    if (!c || !ppIn || !ppStreams || !pMaxBytes || !pResults) return limg_hip_error_ArgumentNull;
+    for (size_t i = 0; i < count; i++)
+      if (!ppIn[i] || !ppStreams[i]) return limg_hip_error_ArgumentNull;
+    const size_t bound = limg_hip_stream_bound(sizeX, sizeY);
+    if (bound == 0) return limg_hip_error_InvalidParameter;
+    if (capacityEach < bound) return limg_hip_error_OutOfBounds;
+    for (size_t i = 0; i < count; i++)
+      if (((uintptr_t)ppStreams[i] & 15u) != 0) return limg_hip_error_InvalidParameter;
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = budget_list_checks(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    auto single = [&](size_t i) {
+      return limg_hip_encode_stream_budget_device(c, ppIn[i], sizeX, sizeY, hasAlpha, ppStreams[i], capacityEach, pMaxBytes[i], minErrorFactor, maxErrorFactor, poolThreads,
+                                                  fastBitCrushing, &pResults[i], stream);
+    };
+    if (count == 1 || !rate_probe_applies(c, sizeX, sizeY, fastBitCrushing))
+    { // no probe kernel (or nothing to share): the loop of single calls
+      for (size_t i = 0; i < count; i++)
+        if ((r = single(i)) != limg_hip_success) return r;
+      return limg_hip_success;
+    }
+    const size_t blocksX = sizeX / kBlock, blocksY = sizeY / kBlock, blocks = blocksX * blocksY;
+    const size_t stripsX = (blocksX + kStripBlocks - 1) / kStripBlocks, imageStrips = stripsX * blocksY;
+    // the plane batch's chunk rule (limg_hip_encode3d_batch_device): 1 GiB of records, 32-bit strip ids, the test hook
+    size_t chunk = (size_t)(1ull << 30) / (blocks * sizeof(limg_hip_block_record));
+    if (chunk * imageStrips > 0x7FFFFFFFull) chunk = 0x7FFFFFFFull / imageStrips;
+    if (chunk < 1) chunk = 1;
+    if (TOPT(c, batch_chunk) > 0) chunk = (size_t)TOPT(c, batch_chunk);
+    const size_t most = count < chunk ? count : chunk;
+    if (most > 1)
+    {
+      if ((r = c->stream.rateState.ensure(most * sizeof(RateDevice))) != limg_hip_success) return r;
+      if ((r = c->stream.rateCounter.ensure(most * 8)) != limg_hip_success) return r;
+    }
+    const uint32_t probes = rate_max_probes(hLo, hHi);
+    std::vector<ImageIO> table;
+    std::vector<uint64_t> budgets;
+    std::vector<RateDevice> states;
+    std::vector<uint32_t> order; // the chunk's images sorted by the h their searches chose
+    std::vector<const uint32_t *> groupIn;
+    std::vector<uint8_t *> groupOut;
+    for (size_t i0 = 0; i0 < count;)
+    {
+      const size_t n = count - i0 < chunk ? count - i0 : chunk;
+      if (n == 1)
+      { // a chunk (or a last chunk) of one image
+        if ((r = single(i0)) != limg_hip_success) return r;
+        i0++;
+        continue;
+      }
+      // 1. the chunk's records in the context's float mode, image after image in enc.records: k_fit_tpb's one grid; encode_params puts the image table on the device
+      table.assign(n, ImageIO{});
+      budgets.resize(n);
+      bool vecIn = sizeX % 4 == 0;
+      for (size_t i = 0; i < n; i++)
+      {
+        table[i].in = ppIn[i0 + i];
+        budgets[i] = (uint64_t)pMaxBytes[i0 + i];
+        vecIn = vecIn && (((uintptr_t)ppIn[i0 + i]) & 15u) == 0; // as encode_params: 16-byte loads only if every image of the chunk allows them
+      }
+      EncodeExtra x;
+      x.fitOnly = true; x.fitFloatMode = true;
+      x.batch = table.data(); x.batchCount = n;
+      if ((r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, nullptr, nullptr, 0, poolThreads, 1, s, x)) != limg_hip_success) return r;
+      // 2. the searches: begin, then every launch any of them can need; probes of an image whose search is over return at once
+      RateProbeBatchParams bp;
+      memset(&bp, 0, sizeof(bp));
+      bp.batch = (const ImageIO *)c->enc.batchTable.p;
+      bp.nImages = (uint32_t)n; bp.imageStrips = (uint32_t)imageStrips;
+      bp.sizeX = (uint32_t)sizeX; bp.sizeY = (uint32_t)sizeY; bp.blocksX = (uint32_t)blocksX; bp.blocksY = (uint32_t)blocksY; bp.stripsX = (uint32_t)stripsX;
+      bp.vecIn = vecIn ? 1 : 0;
+      bp.recordLimit = TOPT(c, record_limit) > 0 ? TOPT(c, record_limit) - 1 : 2700;
+      const bool forced = c->opt.forced_shift[0] >= 0 && c->opt.forced_shift[0] <= 8 && c->opt.forced_shift[1] >= 0 && c->opt.forced_shift[1] <= 8 &&
+                          c->opt.forced_shift[2] >= 0 && c->opt.forced_shift[2] <= 8;
+      for (int i = 0; i < 3; i++) bp.forced[i] = forced ? c->opt.forced_shift[i] : -1;
+      bp.records = (const limg_hip_block_record *)c->enc.records.p; bp.invN = (const float *)c->enc.invN.p;
+      RateDevice *const dStates = (RateDevice *)c->stream.rateState.p;
+      unsigned long long *const dCounters = (unsigned long long *)c->stream.rateCounter.p;
+      bp.states = dStates; bp.counters = dCounters;
+      launch_rate_begin_batch(dStates, dCounters, budgets.data(), n, hLo, hHi, s);
+      for (uint32_t i = 0; i < probes; i++)
+      {
+        launch_rate_probe_batch(bp, hasAlpha ? 4 : 3, c->opt.float_mode == 1, s);
+        launch_rate_step_batch(dStates, dCounters, (uint32_t)n, stream_fixed_bytes(sizeX, sizeY), s);
+      }
+      HIP_TRY(hipGetLastError());
+      states.resize(n);
+      HIP_TRY(hipMemcpyAsync(states.data(), dStates, n * sizeof(RateDevice), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      for (size_t i = 0; i < n; i++)
+        if (!states[i].search.done) return limg_hip_error_Generic;
+      // 3. the final encodes: the thresholds are kernel arguments of the persistent kernel, so one (batched) stream encode per distinct h
+      order.resize(n);
+      for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return states[a].search.next < states[b].search.next; });
+      for (size_t g0 = 0; g0 < n;)
+      {
+        const uint32_t h = states[order[g0]].search.next;
+        size_t g1 = g0;
+        groupIn.clear(); groupOut.clear();
+        for (; g1 < n && states[order[g1]].search.next == h; g1++) { groupIn.push_back(ppIn[i0 + order[g1]]); groupOut.push_back(ppStreams[i0 + order[g1]]); }
+        if (g1 - g0 == 1) r = limg_hip_encode_stream_device(c, groupIn[0], sizeX, sizeY, hasAlpha, groupOut[0], capacityEach, nullptr, 2u * h, poolThreads, fastBitCrushing, stream);
+        else r = limg_hip_encode_stream_batch_device(c, g1 - g0, groupIn.data(), sizeX, sizeY, hasAlpha, groupOut.data(), capacityEach, nullptr, 2u * h, poolThreads,
+                                                     fastBitCrushing, stream);
+        if (r != limg_hip_success) return r;
+        g0 = g1;
+      }
+      for (size_t i = 0; i < n; i++)
+      { // bytes: what the probe measured at the result -- the packer's totalBytes
+        const RateState &st = states[i].search;
+        limg_hip_budget_result &res = pResults[i0 + i];
+        res.errorFactor = 2u * st.next; res.probes = st.probes; res.withinBudget = st.within; res.bytes = st.bestBytes;
+      }
+      i0 += n;
+    }
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_encode_stream_budget_batch(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                      uint8_t *const *ppStreams, size_t capacityEach, const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor,
+                                                      int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults)
+  {
+    if (!c || !ppIn || !ppStreams || !pMaxBytes || !pResults) return limg_hip_error_ArgumentNull;
+    for (size_t i = 0; i < count; i++)
+      if (!ppIn[i] || !ppStreams[i]) return limg_hip_error_ArgumentNull;
+    const size_t bound = limg_hip_stream_bound(sizeX, sizeY);
+    if (bound == 0) return limg_hip_error_InvalidParameter;
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = budget_list_checks(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    HIP_TRY(hipSetDevice(c->device));
+    // staging as limg_hip_encode_stream_batch: the images side by side in host.in, the streams at worst-case size side by side in stream.buf
+    const size_t px = sizeX * sizeY, slice = (bound + 255) & ~(size_t)255;
+    if ((r = c->host.in.ensure(count * px * 4)) != limg_hip_success) return r;
+    if ((r = c->stream.buf.ensure(count * slice)) != limg_hip_success) return r;
+    std::vector<const uint32_t *> dIn(count);
+    std::vector<uint8_t *> dStreams(count);
+    for (size_t i = 0; i < count; i++)
+    {
+      dIn[i] = (const uint32_t *)c->host.in.p + i * px;
+      dStreams[i] = (uint8_t *)c->stream.buf.p + i * slice;
+      HIP_TRY(hipMemcpy((void *)dIn[i], ppIn[i], px * 4, hipMemcpyHostToDevice));
+    }
+    std::vector<limg_hip_budget_result> results(count);
+    for (size_t i = 0; i < count; i++) { memset(&results[i], 0, sizeof(results[i])); results[i].struct_size = sizeof(limg_hip_budget_result); }
+    if ((r = limg_hip_encode_stream_budget_batch_device(c, count, dIn.data(), sizeX, sizeY, hasAlpha, dStreams.data(), slice, pMaxBytes, minErrorFactor, maxErrorFactor,
+                                                        poolThreads, fastBitCrushing, results.data(), nullptr)) != limg_hip_success)
+      return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    bool fits = true;
+    for (size_t i = 0; i < count; i++)
+    { // (the caller's struct_size may be larger than ours: only the members are written)
+      pResults[i].errorFactor = results[i].errorFactor; pResults[i].probes = results[i].probes; pResults[i].withinBudget = results[i].withinBudget; pResults[i].bytes = results[i].bytes;
+      fits = fits && results[i].bytes <= capacityEach;
+    }
+    if (!fits) return limg_hip_error_OutOfBounds; // the single host call's rule: the results say what each stream takes, no stream is written
+    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], dStreams[i], (size_t)results[i].bytes, hipMemcpyDeviceToHost));
     return limg_hip_success;
   }
 
