@@ -706,6 +706,102 @@ limg_hip_result limg_hip_decode_stream_windows_scaled_tensor(limg_hip_context *p
 limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes,
                                                                      const limg_hip_scaled_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat);
 
+/* ---- resized window decode: any source rectangle to any output size, inside the decode ------------------------------------------
+ * RandomResizedCrop plus horizontal flip of a training loader, a thumbnail or a viewer tile of a given pixel size: every job names a SOURCE rectangle in
+ * full-resolution pixels (x0, y0, width, height: inside the image, not empty) and writes outWidth x outHeight pixels, smaller or larger than the rectangle and with
+ * an aspect ratio of its own; flags bit 0 (LIMG_HIP_RESIZE_FLIP_X) mirrors the output horizontally, every other bit must be 0.
+ * Level: log2Scale is L = 0 .. 3, or LIMG_HIP_RESIZE_AUTO: the largest L <= 3 with (width >> L) >= outWidth and (height >> L) >= outHeight, 0 if there is none -- the
+ * deepest box level that still leaves at least one level pixel per output pixel on both axes.
+ * Result: let Q_L be the level-L image of the reduced-scale entries above (byte-wise box mean of the full decode, round half up, RX = sizeX >> L, RY = sizeY >> L).
+ * Per axis (x shown; y is the same with y0, height, outHeight, RY and no flip), for output column X, in integers -- the product in unsigned 64 bits, floor division,
+ * arithmetic shifts on signed 64 bits afterwards:
+ *     Xs  = flip ? outWidth - 1 - X : X
+ *     c16 = (x0 << 16) + (((2 Xs + 1) * width) << 15) / outWidth      sample centre, full resolution, 16.16
+ *     u16 = (c16 >> L) - 32768                                        in level-L pixel-centre coordinates
+ *     i0  = u16 >> 16 ;  f = ((u16 & 0xFFFF) + 128) >> 8              f in 0 .. 256
+ *     lo  = x0 >> L ;  hi = min((x0 + width - 1) >> L, RX - 1)
+ *     a   = clamp(i0, lo, hi) ;  b = clamp(i0 + 1, lo, hi)
+ * With (a, b, f) of the column and (ya, yb, g) of the row, per byte c:
+ *     top = Q_L(a, ya)[c] * (256 - f) + Q_L(b, ya)[c] * f
+ *     bot = Q_L(a, yb)[c] * (256 - f) + Q_L(b, yb)[c] * f
+ *     R(X, Y)[c] = (top * (256 - g) + bot * g + 32768) >> 16
+ * that is align_corners = false bilinear on the level-L image, clamped to the level pixels the rectangle touches, with no alpha weighting.  Consequences: with
+ * outWidth == width, outHeight == height, L = 0 and no flip R is the window itself, bit for bit; with x0, y0, width, height multiples of k = 1 << L and
+ * outWidth == width / k, outHeight == height / k it is that window of Q_L (and AUTO picks that L); the flip is exactly the column reversal.  Against exact bilinear
+ * interpolation at level 0 the result deviates by less than 1.52 byte steps (weights rounded to 1 / 256: 1 / 512 plus two floors of 2^-16 per axis, 0.5 for the end).
+ * RGBA form: pOut[Y * outStridePixels + X] = R(X, Y).  Tensor form: the tensor entries' conversion applied to R's bytes (one multiply, one add, no fused multiply-add,
+ * round-to-nearest-even to F16).  NOTHING ELSE IS WRITTEN, by the rules of the entries above.  Stores are element by element; 64 consecutive elements of an output
+ * row leave together.
+ * Errors, before anything is enqueued: the list and the order of the reduced-scale entries; log2Scale > 3 and not LIMG_HIP_RESIZE_AUTO, a flag bit other than bit 0,
+ * outWidth or outHeight of 0 or above 32768: limg_hip_error_InvalidParameter, checked where a zero width or height is; the stride rules are stated on outWidth and
+ * outHeight; a source rectangle that is not inside the image: limg_hip_error_OutOfBounds; an explicit level with (x0 >> L) > RX - 1 or (y0 >> L) > RY - 1 -- a
+ * rectangle that starts in the trailing columns or rows the level drops, or any rectangle when RX or RY is 0 -- limg_hip_error_OutOfBounds (AUTO cannot get there).
+ * The first failing job's error is returned and nothing is enqueued.
+ * Validation on the device, pJobStatus and the sticky status are the batched window decode's, stated on the job's footprint (the level pixels lo .. hi of both axes,
+ * times k).  Version 2: a job refused by the map kernel writes nothing.  Version 1: a job whose header fails writes nothing; where a group of 8 blocks fails the
+ * job's status gets bit 1 and the output pixels with a tap in that group are unspecified (they lie inside the job's output rectangle); every output pixel whose four
+ * taps lie in sound groups is correct, and other jobs are unaffected.
+ * Cost and call rules: ONE launch for version 1 and TWO for version 2 whatever the count, the mix of levels, the sizes and the flips; version 2 scans each distinct
+ * stream's table once per call; four calls in flight; not during graph capture.  There is no full-resolution and no crop-sized intermediate in device memory: a
+ * workgroup decodes an output tile's footprint into on-chip memory and resamples from there (blocks on a tile's border are decoded by both neighbours).  Context
+ * memory per job: the batched entries' and 64 bytes more. */
+#define LIMG_HIP_RESIZE_AUTO 0xFFFFFFFFu
+#define LIMG_HIP_RESIZE_FLIP_X 1u
+
+typedef struct limg_hip_resized_window
+{
+  size_t x0, y0, width, height; /* SOURCE rectangle, full-resolution pixels, inside the image, not empty */
+  uint32_t *pOut;               /* R(X, Y) at pOut[Y * outStridePixels + X] */
+  size_t outStridePixels;       /* >= outWidth */
+  size_t outWidth, outHeight;   /* 1 .. 32768 */
+  uint32_t log2Scale, flags;    /* L: 0 .. 3 or LIMG_HIP_RESIZE_AUTO; LIMG_HIP_RESIZE_FLIP_X */
+} limg_hip_resized_window;
+
+typedef struct limg_hip_resized_window_job /* one window of one stream */
+{
+  const uint8_t *pStream; /* DEVICE, 16-byte aligned */
+  size_t streamBytes;
+  size_t sizeX, sizeY;    /* must match the stream's header */
+  limg_hip_resized_window window; /* pOut: DEVICE, 4-byte aligned */
+} limg_hip_resized_window_job;
+
+typedef struct limg_hip_resized_tensor_window
+{
+  size_t x0, y0, width, height;  /* SOURCE rectangle, full-resolution pixels, inside the image, not empty */
+  void *pOut;                    /* element (c, Y, X) at pOut[c * planeStride + Y * rowStride + X], in elements of the format's type */
+  size_t rowStride, planeStride; /* in elements: rowStride >= outWidth, planeStride >= (outHeight - 1) * rowStride + outWidth */
+  size_t outWidth, outHeight;    /* 1 .. 32768 */
+  uint32_t log2Scale, flags;     /* L: 0 .. 3 or LIMG_HIP_RESIZE_AUTO; LIMG_HIP_RESIZE_FLIP_X */
+} limg_hip_resized_tensor_window;
+
+typedef struct limg_hip_resized_tensor_window_job /* one window of one stream */
+{
+  const uint8_t *pStream; /* DEVICE, 16-byte aligned */
+  size_t streamBytes;
+  size_t sizeX, sizeY;    /* must match the stream's header */
+  limg_hip_resized_tensor_window window; /* pOut: DEVICE, aligned to the element size */
+} limg_hip_resized_tensor_window_job;
+
+/* DEVICE pointers inside the jobs; pJobs and pFormat are HOST memory and may be reused or freed when the call returns.  Asynchronous on `stream`. */
+limg_hip_result limg_hip_decode_stream_windows_resized_device(limg_hip_context *pCtx, const limg_hip_resized_window_job *pJobs, size_t count, uint32_t *pJobStatus,
+                                                              void *stream);
+limg_hip_result limg_hip_blocked_decode_stream_windows_resized_device(limg_hip_context *pCtx, const limg_hip_resized_window_job *pJobs, size_t count, uint32_t *pJobStatus,
+                                                                      void *stream);
+limg_hip_result limg_hip_decode_stream_windows_resized_tensor_device(limg_hip_context *pCtx, const limg_hip_resized_tensor_window_job *pJobs, size_t count,
+                                                                     const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream);
+limg_hip_result limg_hip_blocked_decode_stream_windows_resized_tensor_device(limg_hip_context *pCtx, const limg_hip_resized_tensor_window_job *pJobs, size_t count,
+                                                                             const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream);
+/* HOST pointers, blocking, under the context's mutex: `count` windows of ONE stream from one upload and one batched call.  Staging as in the host forms above, per
+ * OUTPUT pixel (outWidth x outHeight); a stream refused for any window leaves EVERY pOut untouched, in both versions. */
+limg_hip_result limg_hip_decode_stream_windows_resized(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_resized_window *pWindows,
+                                                       size_t count);
+limg_hip_result limg_hip_blocked_decode_stream_windows_resized(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_resized_window *pWindows,
+                                                               size_t count);
+limg_hip_result limg_hip_decode_stream_windows_resized_tensor(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes,
+                                                              const limg_hip_resized_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat);
+limg_hip_result limg_hip_blocked_decode_stream_windows_resized_tensor(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes,
+                                                                      const limg_hip_resized_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ---------------------------------------------------------------------------------
  * The reference's only parallelism is row strips over a std::thread pool (src/limg.cpp:2105-2138); across GPUs the same strips
  * go one per rank.  Blocks are independent except for the dither chain, so the data path needs no collective in strip-restart mode (each strip

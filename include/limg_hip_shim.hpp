@@ -333,4 +333,25 @@ inline limg_result limg_decode_windows_scaled_tensor(const uint8_t *pIn, const s
   return (limg_result)limg_hip_decode_stream_windows_scaled_tensor(c, pIn, size, pWindows, count, pFormat);
 }
 
+// ... resized (limg_hip.h "resized window decode"): every window names a source rectangle in full-resolution pixels and the size of its output, which is resampled
+// bilinearly from the level log2Scale = 0 .. 3 or LIMG_HIP_RESIZE_AUTO and mirrored where flags has LIMG_HIP_RESIZE_FLIP_X: a thumbnail, a viewer tile, a loader's sample.
+inline limg_result limg_decode_windows_resized(const uint8_t *pIn, const size_t size, const limg_hip_resized_window *pWindows, const size_t count)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (limg_hip_blocked_stream_info(pIn, size, nullptr, nullptr, nullptr, nullptr, nullptr) == limg_hip_success)
+    return (limg_result)limg_hip_blocked_decode_stream_windows_resized(c, pIn, size, pWindows, count);
+  return (limg_result)limg_hip_decode_stream_windows_resized(c, pIn, size, pWindows, count);
+}
+
+inline limg_result limg_decode_windows_resized_tensor(const uint8_t *pIn, const size_t size, const limg_hip_resized_tensor_window *pWindows, const size_t count,
+                                                      const limg_hip_tensor_format *pFormat)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (limg_hip_blocked_stream_info(pIn, size, nullptr, nullptr, nullptr, nullptr, nullptr) == limg_hip_success)
+    return (limg_result)limg_hip_blocked_decode_stream_windows_resized_tensor(c, pIn, size, pWindows, count, pFormat);
+  return (limg_result)limg_hip_decode_stream_windows_resized_tensor(c, pIn, size, pWindows, count, pFormat);
+}
+
 #endif // LIMG_HIP_SHIM_HPP

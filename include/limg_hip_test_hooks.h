@@ -39,6 +39,8 @@ typedef struct limg_hip_test_options
   int32_t blocked_no_order;   /* A/B, non-0: the merged-block encoder's per-rectangle launches take the rectangles in creation order instead of large-first
                                  (k_blocked_order, limg_hip_blocked.hip).  Same planes either way */
   int32_t blocked_no_vec_store; /* A/B, non-0: the merged-block encoder's store kernel keeps one pixel per lane (what images with partial edge blocks always use) */
+  int32_t resize_tile_pixels; /* N > 0: the resized window entries plan their output tiles for a tile of N level pixels (at least 4, at most the kernel's capacity),
+                                 so that small jobs split into several tiles on both axes.  The HOST plans with it: the kernels are the product's.  Same pixels */
 } limg_hip_test_options;
 
 void limg_hip_default_test_options_sized(limg_hip_test_options *pOptions, size_t structSize);

@@ -39,6 +39,9 @@ ABI_SYMBOLS = (
     "limg_hip_decode_stream_windows_scaled_device", "limg_hip_blocked_decode_stream_windows_scaled_device", "limg_hip_decode_stream_windows_scaled_tensor_device",
     "limg_hip_blocked_decode_stream_windows_scaled_tensor_device", "limg_hip_decode_stream_windows_scaled", "limg_hip_blocked_decode_stream_windows_scaled",
     "limg_hip_decode_stream_windows_scaled_tensor", "limg_hip_blocked_decode_stream_windows_scaled_tensor",
+    "limg_hip_decode_stream_windows_resized_device", "limg_hip_blocked_decode_stream_windows_resized_device", "limg_hip_decode_stream_windows_resized_tensor_device",
+    "limg_hip_blocked_decode_stream_windows_resized_tensor_device", "limg_hip_decode_stream_windows_resized", "limg_hip_blocked_decode_stream_windows_resized",
+    "limg_hip_decode_stream_windows_resized_tensor", "limg_hip_blocked_decode_stream_windows_resized_tensor",
     "limg_hip_blocked_encode3d", "limg_hip_blocked_encode3d_device", "limg_hip_blocked_regions", "limg_hip_blocked_timing", "limg_hip_blocked_kernel_timing", "limg_hip_blocked_match_bits", "limg_hip_host_blocked_matches",
     "limg_hip_host_blocked_merge", "limg_hip_host_blocked_match_words", "limg_hip_host_blocked_match_bits",
     "limg_hip_comm_unique_id", "limg_hip_comm_init", "limg_hip_comm_destroy", "limg_hip_comm_info", "limg_hip_gather_stream", "limg_hip_encode3d_single_chain_device",
@@ -129,6 +132,29 @@ class ScaledTensorWindowJob(C.Structure):
     _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", ScaledTensorWindow)]
 
 
+RESIZE_AUTO, RESIZE_FLIP_X = 0xFFFFFFFF, 1  # limg_hip_resized_*window.log2Scale / .flags
+
+
+class ResizedWindow(C.Structure):
+    """limg_hip_resized_window: a source rectangle, the output's size, the level (0 .. 3 or RESIZE_AUTO) and the flags"""
+    _fields_ = Window._fields_ + [("outWidth", C.c_size_t), ("outHeight", C.c_size_t), ("log2Scale", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ResizedWindowJob(C.Structure):
+    """limg_hip_resized_window_job: one window of one stream"""
+    _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", ResizedWindow)]
+
+
+class ResizedTensorWindow(C.Structure):
+    """limg_hip_resized_tensor_window: the same into planes"""
+    _fields_ = TensorWindow._fields_ + [("outWidth", C.c_size_t), ("outHeight", C.c_size_t), ("log2Scale", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ResizedTensorWindowJob(C.Structure):
+    """limg_hip_resized_tensor_window_job: one window of one stream"""
+    _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", ResizedTensorWindow)]
+
+
 # (a level leads the window tuple, the pixels go to planes) -> the entry's window and job struct
 _WINDOW_TYPES = {(False, False): (Window, WindowJob), (False, True): (TensorWindow, TensorWindowJob),
                  (True, False): (ScaledWindow, ScaledWindowJob), (True, True): (ScaledTensorWindow, ScaledTensorWindowJob)}
@@ -157,7 +183,7 @@ class TestOptions(C.Structure):
     """include/limg_hip_test_hooks.h -- liblimg_hip_test.so only"""
     _fields_ = [("struct_size", C.c_uint32), ("record_limit", C.c_int32), ("batch_chunk", C.c_int32), ("wg_per_cu", C.c_int32), ("whole_image_ragged", C.c_int32),
                 ("pipeline", C.c_int32), ("fail_chain_phase1", C.c_int32), ("blocked_no_bound", C.c_int32), ("lookback_spins", C.c_int32), ("base_error_strip", C.c_int32),
-                ("skip_publish_strip", C.c_int32), ("blocked_no_order", C.c_int32), ("blocked_no_vec_store", C.c_int32)]
+                ("skip_publish_strip", C.c_int32), ("blocked_no_order", C.c_int32), ("blocked_no_vec_store", C.c_int32), ("resize_tile_pixels", C.c_int32)]
 
 
 def load_library(path=None):
@@ -297,10 +323,10 @@ def load_library(path=None):
     for args, names in (  # the window entries, limg_hip_[blocked_]decode_stream_<name>: both versions of a name share its argument list
             ([P, P, Z] + [Z] * 6 + [P, Z, P], ("window_device",)),  # ctx, stream, bytes, sizeX, sizeY, x0, y0, width, height, out, outStridePixels, hipStream
             ([P, P, Z] + [Z] * 4 + [P, Z], ("window",)),  # ctx, stream, bytes, x0, y0, width, height, out, outStridePixels
-            ([P, P, Z, P, P], ("windows_device", "windows_scaled_device")),  # ctx, jobs (host), count, jobStatus (device), hipStream
-            ([P, P, Z, P, Z], ("windows", "windows_scaled")),  # ctx, stream, bytes, windows (host), count
-            ([P, P, Z, P, P, P], ("windows_tensor_device", "windows_scaled_tensor_device")),  # ctx, jobs (host), count, format (host), jobStatus (device), hipStream
-            ([P, P, Z, P, Z, P], ("windows_tensor", "windows_scaled_tensor"))):  # ctx, stream, bytes, windows (host), count, format (host)
+            ([P, P, Z, P, P], ("windows_device", "windows_scaled_device", "windows_resized_device")),  # ctx, jobs (host), count, jobStatus (device), hipStream
+            ([P, P, Z, P, Z], ("windows", "windows_scaled", "windows_resized")),  # ctx, stream, bytes, windows (host), count
+            ([P, P, Z, P, P, P], ("windows_tensor_device", "windows_scaled_tensor_device", "windows_resized_tensor_device")),  # ctx, jobs (host), count, format (host), jobStatus (device), hipStream
+            ([P, P, Z, P, Z, P], ("windows_tensor", "windows_scaled_tensor", "windows_resized_tensor"))):  # ctx, stream, bytes, windows (host), count, format (host)
         for name in names:
             for version in ("limg_hip_decode_stream_", "limg_hip_blocked_decode_stream_"):
                 getattr(L, version + name).restype = C.c_int
@@ -1000,6 +1026,101 @@ class LimgHip:
         """The loader step where every sample picks its own level: jobs: (stream tensor, nbytes, W, H, level, x, y) each -- the h x w crop at (x, y) of the stream's
         level-`level` image -> ONE contiguous (N, planes, h, w) torch tensor of `dtype`, as decode_crops_device.  One call of the version's scaled tensor entry."""
         return self._decode_crops(jobs, True, h, w, dtype, scale, bias, planes, blocked, out)
+
+    # ---- resized window decode: any source rectangle to any output size, bilinear on a box level, optionally mirrored (contract: include/limg_hip.h) ----
+    def _decode_resized_device(self, name, jobs, fmt, status):
+        import torch
+        planar = fmt is not None
+        win_t, job_t = (ResizedTensorWindow, ResizedTensorWindowJob) if planar else (ResizedWindow, ResizedWindowJob)
+        dtype = torch.int32 if not planar else torch.float16 if fmt.type == TENSOR_F16 else torch.float32
+        table = (job_t * len(jobs))()
+        outs = []
+        for i, job in enumerate(jobs):
+            if planar:
+                stream, nbytes, W, H, level, flags, x, y, sw, sh, ow, oh, out, row, plane = job
+            else:
+                stream, nbytes, W, H, level, flags, x, y, sw, sh, ow, oh, out, row = job
+            if out is None:
+                out = torch.empty((fmt.planes, oh, ow) if planar else (oh, ow), dtype=dtype, device=stream.device)
+            if row is None:
+                row = out.stride(-2) if out.dim() == 2 + planar else ow
+            level = RESIZE_AUTO if level is None else level
+            if planar:
+                assert out.dtype == dtype, (out.dtype, dtype)
+                if plane is None:
+                    plane = out.stride(0) if out.dim() == 3 else row * oh
+                win = win_t(x, y, sw, sh, out.data_ptr(), int(row), int(plane), ow, oh, level, flags)
+            else:
+                win = win_t(x, y, sw, sh, out.data_ptr(), int(row), ow, oh, level, flags)
+            table[i] = job_t(stream.data_ptr(), int(nbytes), W, H, win)
+            outs.append(out)
+        self._stream_call(name, table, len(jobs), *([C.byref(fmt)] if planar else []), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
+        return outs
+
+    def _decode_resized_host(self, name, stream, wins, fmt, outs):
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        planar = fmt is not None
+        win_t = ResizedTensorWindow if planar else ResizedWindow
+        dtype = np.dtype(np.uint32 if not planar else np.float16 if fmt.type == TENSOR_F16 else np.float32)
+        eb = dtype.itemsize
+        outs = [None] * len(wins) if outs is None else list(outs)
+        table = (win_t * len(wins))()
+        for i, (level, flags, x, y, sw, sh, ow, oh) in enumerate(wins):
+            if outs[i] is None:
+                outs[i] = np.zeros((fmt.planes, oh, ow) if planar else (oh, ow), dtype=dtype)
+            out = outs[i]
+            if planar:
+                assert out.dtype == dtype and out.ndim == 3 and out.shape[0] >= fmt.planes and out.strides[2] == eb and out.strides[1] % eb == 0 and out.strides[0] % eb == 0, \
+                    "out: (planes, h, w) of the format's type, elements of a row contiguous"
+            else:
+                assert out.dtype == np.uint32 and out.ndim == 2 and out.strides[1] == 4 and out.strides[0] % 4 == 0, "out: uint32 rows, pixels contiguous"
+            table[i] = win_t(x, y, sw, sh, out.ctypes.data, *[s // eb for s in out.strides[-2::-1]], ow, oh, RESIZE_AUTO if level is None else level, flags)
+        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins), *([C.byref(fmt)] if planar else []))
+        return outs
+
+    def decode_stream_windows_resized_device(self, jobs, status=None):
+        """jobs: (stream tensor, nbytes, W, H, level, flags, x, y, sw, sh, ow, oh, out, out_stride) each: the source rectangle (x, y, sw, sh) of the W x H image,
+        full-resolution pixels, as ow x oh pixels; level 0 .. 3 or None (RESIZE_AUTO); flags: RESIZE_FLIP_X or 0.  out=None allocates (oh, ow) int32.  One launch."""
+        return self._decode_resized_device("limg_hip_decode_stream_windows_resized_device", jobs, None, status)
+
+    def blocked_decode_stream_windows_resized_device(self, jobs, status=None):
+        return self._decode_resized_device("limg_hip_blocked_decode_stream_windows_resized_device", jobs, None, status)
+
+    def decode_stream_windows_resized_tensor_device(self, jobs, fmt, status=None):
+        """jobs: (stream tensor, nbytes, W, H, level, flags, x, y, sw, sh, ow, oh, out, row_stride, plane_stride) each, into planes of fmt's type"""
+        return self._decode_resized_device("limg_hip_decode_stream_windows_resized_tensor_device", jobs, fmt, status)
+
+    def blocked_decode_stream_windows_resized_tensor_device(self, jobs, fmt, status=None):
+        return self._decode_resized_device("limg_hip_blocked_decode_stream_windows_resized_tensor_device", jobs, fmt, status)
+
+    def decode_stream_windows_resized(self, stream, wins, outs=None):
+        """host stream bytes, wins: (level, flags, x, y, sw, sh, ow, oh) each -> the list of numpy uint32 (oh, ow) arrays; one upload and one batched call"""
+        return self._decode_resized_host("limg_hip_decode_stream_windows_resized", stream, wins, None, outs)
+
+    def blocked_decode_stream_windows_resized(self, stream, wins, outs=None):
+        return self._decode_resized_host("limg_hip_blocked_decode_stream_windows_resized", stream, wins, None, outs)
+
+    def decode_stream_windows_resized_tensor(self, stream, wins, fmt, outs=None):
+        """host stream bytes, wins: (level, flags, x, y, sw, sh, ow, oh) each -> the list of numpy (planes, oh, ow) arrays of fmt's type"""
+        return self._decode_resized_host("limg_hip_decode_stream_windows_resized_tensor", stream, wins, fmt, outs)
+
+    def blocked_decode_stream_windows_resized_tensor(self, stream, wins, fmt, outs=None):
+        return self._decode_resized_host("limg_hip_blocked_decode_stream_windows_resized_tensor", stream, wins, fmt, outs)
+
+    def decode_crops_resized_device(self, jobs, h, w, dtype, scale, bias, planes=3, blocked=False, out=None, level=None):
+        """RandomResizedCrop + flip + normalise + layout in one call: jobs: (stream tensor, nbytes, W, H, x, y, sw, sh[, flip]) each -- the source rectangle
+        (x, y, sw, sh) of each stream resampled to h x w, mirrored where flip is true -> ONE contiguous (N, planes, h, w) torch tensor of `dtype`, element =
+        byte * scale[c] + bias[c]; job i fills slice i.  level: 0 .. 3 for every job, or None: each job's deepest level that keeps a level pixel per output pixel.
+        out: the tensor to fill.  One call of the version's resized tensor entry, asynchronous on torch's current stream."""
+        import torch
+        fmt = tensor_format(dtype, planes, scale, bias)
+        if out is None:
+            out = torch.empty((len(jobs), planes, h, w), dtype=dtype, device=jobs[0][0].device)
+        assert tuple(out.shape) == (len(jobs), planes, h, w) and out.is_contiguous() and out.dtype == dtype
+        assert all(len(j) in (8, 9) for j in jobs)
+        table = [(*j[:4], level, RESIZE_FLIP_X if len(j) == 9 and j[8] else 0, *j[4:8], w, h, out[i], w, h * w) for i, j in enumerate(jobs)]
+        getattr(self, ("blocked_" if blocked else "") + "decode_stream_windows_resized_tensor_device")(table, fmt)
+        return out
 
     def check(self):
         _check(self.lib.limg_hip_check_device_status(self.ctx), "limg_hip_check_device_status")

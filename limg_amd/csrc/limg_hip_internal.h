@@ -286,6 +286,58 @@ namespace limg_hip
   void launch_blocked_stream_windows(const WindowBatchParams &b, bool scaled, const limg_hip_tensor_format *f, int cus, hipStream_t s);
   static_assert(sizeof(WindowDecodeParams) == 128, "the job table's entry: log2Scale must not grow it");
 
+  // ---- resized window decode (the *_resized entries): any source rectangle to any output size, bilinear on the level-L image (contract: include/limg_hip.h) ----
+  // The work item is an output TILE of a job: one workgroup decodes the tile's level-L footprint into an LDS tile and resamples from it.  jobs[i] of the batch table
+  // describes, as for a scaled job, the job's SOURCE FOOTPRINT at level L (the level pixels [lo, hi] of both axes times k, log2Scale = L; `out`, outStride and
+  // planeStride are the output's); what does not fit into that entry is the job's ResizeJob in a second table of the same ring slot.
+  constexpr uint32_t kResizeTilePixels = 4096; // capacity of the LDS tile in level-L pixels (16 KiB; DESIGN.md 4c says why)
+  constexpr uint32_t kResizeTileEdge = 64;     // a tile is at most 64 output columns (one per lane of a wave) and 64 output rows
+  struct ResizeJob
+  {
+    uint32_t outW, outH;         // the output's size
+    uint32_t x0, y0, srcW, srcH; // the source rectangle, full-resolution pixels
+    uint32_t flags;              // LIMG_HIP_RESIZE_FLIP_X
+    uint32_t tileW, tileH;       // a tile's output size (the last tile of a row / column may be smaller); its level-L footprint holds at most kResizeTilePixels
+    uint32_t tilesX;             // tiles per row of tiles
+    uint32_t stepR, pad0;        // four output rows further the y axis' numerator is (srcH << 18) larger: that step's remainder and quotient by outH, so a lane
+    unsigned long long stepQ;    // that walks down its rows divides once
+    uint32_t pad[2];
+  };
+  static_assert(sizeof(ResizeJob) == 64, "the second per-job table's entry");
+  struct WindowResizeParams
+  {
+    WindowBatchParams b;
+    const ResizeJob *resize;  // count entries
+    const uint32_t *tileBase; // count + 1: exclusive prefix of the jobs' tile counts; [count] = totalTiles
+    uint32_t totalTiles;
+  };
+  // One axis of the contract's formula: output index X (already mirrored where the job flips) of `out` -> taps a, b (level-L pixels, clamped to [lo, hi]) and the
+  // weight f = 0 .. 256 of b.  num / out is the only division; the kernel takes it once per lane and steps the quotient (resize_axis_q + resize_taps).
+  struct ResizeTaps { uint32_t a, b, f; };
+  __host__ __device__ inline ResizeTaps resize_taps(unsigned long long c16, uint32_t L, uint32_t lo, uint32_t hi)
+  {
+    const long long u16 = (long long)(c16 >> L) - 32768;
+    const long long i0 = u16 >> 16, l = (long long)lo, h = (long long)hi;
+    ResizeTaps t;
+    t.f = (uint32_t)(((u16 & 0xFFFF) + 128) >> 8);
+    t.a = (uint32_t)(i0 < l ? l : i0 > h ? h : i0);
+    t.b = (uint32_t)(i0 + 1 < l ? l : i0 + 1 > h ? h : i0 + 1);
+    return t;
+  }
+  __host__ __device__ inline ResizeTaps resize_axis(uint32_t X, uint32_t s0, uint32_t len, uint32_t out, uint32_t L, uint32_t lo, uint32_t hi)
+  {
+    return resize_taps(((unsigned long long)s0 << 16) + ((((unsigned long long)(2u * X + 1u) * len) << 15) / out), L, lo, hi);
+  }
+  // the level pixels an axis of a job may touch: lo = s0 >> L, hi = min((s0 + len - 1) >> L, R - 1) with R the level image's size (the caller has checked lo <= R - 1)
+  __host__ __device__ inline uint32_t resize_hi(uint32_t s0, uint32_t len, uint32_t L, uint32_t size)
+  {
+    const uint32_t e = (s0 + len - 1u) >> L, r = (size >> L) - 1u;
+    return e < r ? e : r;
+  }
+  // v1 / v2 launch: f NULL = packed RGBA8
+  void launch_stream_windows_resized(const WindowResizeParams &r, const limg_hip_tensor_format *f, int cus, hipStream_t s);
+  void launch_blocked_stream_windows_resized(const WindowResizeParams &r, const limg_hip_tensor_format *f, int cus, hipStream_t s);
+
   void launch_stream_pack(const StreamParams &p, hipStream_t s);
   void launch_stream_pack_batch(const StreamBatchParams &b, hipStream_t s);                                                  // one scan launch + one pack launch, whatever nImages is
   void launch_set_stream_table(StreamImage *dTable, const StreamImage *hTable, size_t count, hipStream_t s);                // as launch_set_batch_table: through kernel arguments

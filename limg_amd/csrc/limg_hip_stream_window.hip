@@ -38,6 +38,11 @@
 // (k_stream_windows_scaled[_tensor<T>], k_bstream_windows_scaled[_tensor<T>]).  A job's level L rides in its WindowDecodeParams, whose window is then the SOURCE
 // footprint: units, validation and the map kernel see a plain window; only the store differs -- k x k box sums inside the 8x8 block (in the lane along x, across
 // the lanes 8, 16 and 32 away along y), rounded and stored by the lane of each box's first row.  Nothing is gathered across blocks (DESIGN.md says why).
+//
+// Resized forms (limg_hip_*decode_stream_windows_resized*): the one thing a store policy cannot do, a filter whose taps cross 8x8 blocks, as a kernel stage of its own.
+// The work item is an output TILE of a job and belongs to a whole workgroup (k_stream_windows_resized[_tensor<T>], k_bstream_windows_resized[_tensor<T>]): its waves
+// run the unit bodies above over the tile's level-L footprint with ScaledStore<TileStore> -- into an LDS tile instead of the output --, synchronise, and resample
+// bilinearly from LDS by the contract's integer formula.  A second per-job table (ResizeJob) carries what WindowDecodeParams has no room for.
 #include "limg_hip_stream_format.h"
 
 namespace limg_hip
@@ -182,6 +187,30 @@ namespace limg_hip
         for (uint32_t i = 0; i < N; i++)
           if (X + i >= X0 && X + i < X0 + W) plane[X + i - X0] = (T)v[i];
       }
+    }
+
+    // The resized entries' base policy: level-L pixels into the workgroup's LDS tile, which holds the level pixels fx0 .. fx0 + fw - 1 of the level rows fy0 .. fy0 + fh - 1
+    // at pitch fw.  Pixels outside the tile are dropped (X - fx0 wraps to a large value left of it); the level-0 operator does the same for the lane's 8 pixels.
+    struct TileStore
+    {
+      uint32_t *tile;
+      uint32_t fx0, fy0, fw, fh;
+      __device__ __forceinline__ void put(uint32_t X, uint32_t Y, uint32_t v) const
+      {
+        if (X - fx0 < fw && Y - fy0 < fh) tile[(Y - fy0) * fw + (X - fx0)] = v;
+      }
+      __device__ __forceinline__ void operator()(const WindowDecodeParams &, uint32_t x, uint32_t y, const uint32_t px[8]) const
+      {
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++) put(x + i, y, px[i]);
+      }
+    };
+
+    template <uint32_t L>
+    __device__ __forceinline__ void store_reduced(const TileStore &s, const WindowDecodeParams &, uint32_t X, uint32_t Y, const uint32_t (&q)[8u >> L])
+    {
+#pragma unroll
+      for (uint32_t i = 0; i < (8u >> L); i++) s.put(X + i, Y, q[i]);
     }
 
     // the lane's 8 pixels of image row y -> its share of the sums of 8 >> L boxes; after the exchange every lane of a box row holds the whole sums, and the lane of
@@ -731,6 +760,153 @@ namespace limg_hip
     {
       bstream_windows_body(b, ScaledStore<PlanarStore<T>>{ PlanarStore<T>{ f } });
     }
+
+    // ---- resized, both versions ------------------------------------------------------------------------------------------------------------
+    // Work item = an output tile of a job, by one workgroup: (1) its four waves decode the job's units that meet the tile's level-L footprint with the unit bodies
+    // above, stored by ScaledStore<TileStore> into the LDS tile; (2) barrier; (3) lane = output column, wave = every fourth output row: the four taps as dword reads
+    // from the tile, bytes two per dword half horizontally (255 * 256 fits 16 bits), one per dword vertically, and one store per output element -- a wave's store is
+    // 64 consecutive elements of an output row.  The unit bodies get a LOCAL copy of the job's parameters whose pixel clip is the tile's footprint in whole k x k boxes
+    // (so the lane partners of the reduction stay on the same branches); block range, map, state and status stay the job's, and with them the unit numbering, every
+    // validation and version 2's map indexing.
+    struct RgbaOut
+    {
+      __device__ __forceinline__ void operator()(const WindowDecodeParams &p, uint32_t X, uint32_t Y, uint32_t px) const { p.out[(unsigned long long)Y * p.outStride + X] = px; }
+    };
+    template <class T>
+    struct PlanarOut
+    {
+      limg_hip_tensor_format f;
+      __device__ __forceinline__ void operator()(const WindowDecodeParams &p, uint32_t X, uint32_t Y, uint32_t px) const
+      {
+        T *at = reinterpret_cast<T *>(p.out) + (unsigned long long)Y * p.outStride + X;
+#pragma unroll
+        for (uint32_t c = 0; c < 4u; c++)
+        {
+          if (c >= f.planes) break; // (wave-uniform)
+          at[(unsigned long long)c * p.planeStride] = (T)((float)((px >> (8u * c)) & 0xFFu) * f.scale[c] + f.bias[c]);
+        }
+      }
+    };
+
+    template <bool RECTS, class OUT>
+    __device__ __forceinline__ void resized_body(const WindowResizeParams &r, uint32_t *tile, WindowWaveLds *sW, const OUT &out)
+    {
+      const int lane = lane_id();
+      const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      for (uint32_t t = blockIdx.x; t < r.totalTiles; t += gridDim.x) // (workgroup-uniform, and so is every `continue` below: no wave misses a barrier)
+      {
+        const uint32_t job = find_slot(r.tileBase, r.b.count, t), first = load_uniform(r.tileBase + job);
+        const WindowDecodeParams p = load_job(r.b, job);
+        const ResizeJob rj = load_uniform(r.resize + job);
+        const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
+        if constexpr (!RECTS)
+        {
+          if (!stream_header_ok(h, LIMG_HIP_STREAM_VERSION, kEntry, p.nBlocks, p))
+          { // every tile of the job takes this way: the job writes nothing; its first tile says so
+            if (t == first && threadIdx.x == 0) raise_job(r.b, job, 1u);
+            continue;
+          }
+        }
+        else if (ld_volatile(p.state + 1) != 0u || ld_volatile(p.state) != p.wbx * p.wby)
+        { // the job's verdict from k_bstream_windows_map
+          if (t == first && threadIdx.x == 0) raise_job(r.b, job, 2u);
+          continue;
+        }
+        // the tile: output columns X0 .. X0 + tw - 1 of rows Y0 .. Y0 + th - 1, and the level pixels its first and last column and row tap
+        const uint32_t L = p.log2Scale, flip = rj.flags & LIMG_HIP_RESIZE_FLIP_X;
+        const uint32_t ti = t - first, ty = ti / rj.tilesX, tx = ti - ty * rj.tilesX;
+        const uint32_t X0 = tx * rj.tileW, Y0 = ty * rj.tileH, tw = min(rj.tileW, rj.outW - X0), th = min(rj.tileH, rj.outH - Y0);
+        const uint32_t lox = p.x0 >> L, hix = lox + (p.width >> L) - 1u, loy = p.y0 >> L, hiy = loy + (p.height >> L) - 1u;
+        const ResizeTaps xA = resize_axis(flip ? rj.outW - 1u - X0 : X0, rj.x0, rj.srcW, rj.outW, L, lox, hix);
+        const ResizeTaps xB = resize_axis(flip ? rj.outW - X0 - tw : X0 + tw - 1u, rj.x0, rj.srcW, rj.outW, L, lox, hix);
+        const ResizeTaps yA = resize_axis(Y0, rj.y0, rj.srcH, rj.outH, L, loy, hiy), yB = resize_axis(Y0 + th - 1u, rj.y0, rj.srcH, rj.outH, L, loy, hiy);
+        const uint32_t fx0 = min(xA.a, xB.a), fw = max(xA.b, xB.b) - fx0 + 1u, fy0 = yA.a, fh = yB.b - fy0 + 1u;
+        if (fw * fh > kResizeTilePixels || tw > 64u) continue; // (the host has planned the tiles so that this cannot happen; nothing is ever stored beyond the tile)
+
+        WindowDecodeParams lp = p;
+        lp.x0 = fx0 << L; lp.width = fw << L; lp.y0 = fy0 << L; lp.height = fh << L;
+        const ScaledStore<TileStore> store{ TileStore{ tile, fx0, fy0, fw, fh } };
+        constexpr uint32_t kUnit = RECTS ? 3u : 6u; // log2 of a unit's width in blocks
+        const uint32_t unitsX = (p.wbx + (1u << kUnit) - 1u) >> kUnit;
+        const uint32_t ua = ((lp.x0 >> 3) - p.bx0) >> kUnit, nuc = ((((lp.x0 + lp.width - 1u) >> 3) - p.bx0) >> kUnit) - ua + 1u;
+        const uint32_t bya = (lp.y0 >> 3) - p.by0, nU = nuc * (((lp.y0 + lp.height - 1u) >> 3) - p.by0 - bya + 1u);
+        if constexpr (!RECTS)
+        {
+          const uint2 *payload = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)p.nBlocks * kEntry);
+          const int channels = (int)h->channels;
+          const unsigned long long payloadWords = h->payloadWords;
+          for (uint32_t i = wave; i < nU; i += 4u) // (wave-uniform)
+          {
+            const uint32_t ur = i / nuc;
+            window_unit(lp, sW[wave], (bya + ur) * unitsX + ua + (i - ur * nuc), unitsX, channels, payloadWords, payload, lane, [&](uint32_t bits) { raise_job(r.b, job, bits); }, store);
+          }
+        }
+        else
+        {
+          const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h->channels;
+          const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h->payloadWords * 8ull;
+          for (uint32_t i = wave; i < nU; i += 4u)
+          {
+            const uint32_t ur = i / nuc;
+            bwindow_unit(lp, (bya + ur) * unitsX + ua + (i - ur * nuc), unitsX, nRects, channels, tableEnd, total, lane, store);
+          }
+        }
+        __syncthreads();
+
+        if ((uint32_t)lane < tw)
+        {
+          const uint32_t X = X0 + (uint32_t)lane;
+          const ResizeTaps cx = resize_axis(flip ? rj.outW - 1u - X : X, rj.x0, rj.srcW, rj.outW, L, lox, hix);
+          const uint32_t ca = cx.a - fx0, cb = cx.b - fx0, f = cx.f, nf = 256u - f;
+          // the y axis' quotient for the wave's first row, then stepped four rows at a time with the job's (stepQ, stepR)
+          const unsigned long long num = ((unsigned long long)(2u * (Y0 + wave) + 1u) * rj.srcH) << 15;
+          unsigned long long q = num / rj.outH;
+          uint32_t rem = (uint32_t)(num - q * rj.outH);
+          for (uint32_t Y = Y0 + wave; Y < Y0 + th; Y += 4u)
+          {
+            const ResizeTaps cy = resize_taps(((unsigned long long)rj.y0 << 16) + q, L, loy, hiy);
+            const uint32_t *ra = tile + (cy.a - fy0) * fw, *rb = tile + (cy.b - fy0) * fw;
+            const uint32_t p00 = ra[ca], p01 = ra[cb], p10 = rb[ca], p11 = rb[cb], g = cy.f, ng = 256u - g;
+            const uint32_t tlo = (p00 & 0x00FF00FFu) * nf + (p01 & 0x00FF00FFu) * f, thi = ((p00 >> 8) & 0x00FF00FFu) * nf + ((p01 >> 8) & 0x00FF00FFu) * f;
+            const uint32_t blo = (p10 & 0x00FF00FFu) * nf + (p11 & 0x00FF00FFu) * f, bhi = ((p10 >> 8) & 0x00FF00FFu) * nf + ((p11 >> 8) & 0x00FF00FFu) * f;
+            const uint32_t b0 = ((tlo & 0xFFFFu) * ng + (blo & 0xFFFFu) * g + 32768u) >> 16, b2 = ((tlo >> 16) * ng + (blo >> 16) * g + 32768u) >> 16;
+            const uint32_t b1 = ((thi & 0xFFFFu) * ng + (bhi & 0xFFFFu) * g + 32768u) >> 16, b3 = ((thi >> 16) * ng + (bhi >> 16) * g + 32768u) >> 16;
+            out(p, X, Y, b0 | (b1 << 8) | (b2 << 16) | (b3 << 24));
+            q += rj.stepQ; rem += rj.stepR;
+            if (rem >= rj.outH) { rem -= rj.outH; q++; }
+          }
+        }
+        __syncthreads(); // the tile is free for the next one
+      }
+    }
+
+    __global__ __launch_bounds__(256) void k_stream_windows_resized(const WindowResizeParams r)
+    {
+      __shared__ __align__(16) WindowWaveLds sW[4];
+      __shared__ __align__(16) uint32_t sTile[kResizeTilePixels];
+      resized_body<false>(r, sTile, sW, RgbaOut());
+    }
+
+    template <class T>
+    __global__ __launch_bounds__(256) void k_stream_windows_resized_tensor(const WindowResizeParams r, const limg_hip_tensor_format f)
+    {
+      __shared__ __align__(16) WindowWaveLds sW[4];
+      __shared__ __align__(16) uint32_t sTile[kResizeTilePixels];
+      resized_body<false>(r, sTile, sW, PlanarOut<T>{ f });
+    }
+
+    __global__ __launch_bounds__(256) void k_bstream_windows_resized(const WindowResizeParams r)
+    {
+      __shared__ __align__(16) uint32_t sTile[kResizeTilePixels];
+      resized_body<true>(r, sTile, nullptr, RgbaOut());
+    }
+
+    template <class T>
+    __global__ __launch_bounds__(256) void k_bstream_windows_resized_tensor(const WindowResizeParams r, const limg_hip_tensor_format f)
+    {
+      __shared__ __align__(16) uint32_t sTile[kResizeTilePixels];
+      resized_body<true>(r, sTile, nullptr, PlanarOut<T>{ f });
+    }
   }
 
   // persistent launches: a workgroup of four waves per residency slot at most, every wave strides over its units.  slotsPerCu: 4 for version 1 (its 100 vector
@@ -778,5 +954,27 @@ namespace limg_hip
   {
     hipLaunchKernelGGL(k_bstream_windows_map, window_grid(b.totalItems, cus, 8u), dim3(256), 0, s, b);
     launch_windows_decode(true, scaled, f, b, window_grid(b.totalUnits, cus, 8u), s);
+  }
+
+  // the resized forms: a workgroup per output tile, persistent over the call's tiles.  Residency slots per CU: 4 for version 1 (111 vector registers; 4 x (4
+  // WindowWaveLds + the 16 KiB tile) = 144 KiB of the CU's 160), 6 for version 2 (73 vector registers; 6 x 16 KiB)
+  static void launch_windows_resized(bool rects, const limg_hip_tensor_format *f, const WindowResizeParams &r, int cus, hipStream_t s)
+  {
+    const uint32_t slots = (uint32_t)cus * (rects ? 6u : 4u);
+    const dim3 grid(r.totalTiles < slots ? r.totalTiles : slots);
+    const bool half = f && f->type == LIMG_HIP_TENSOR_F16;
+    if (!f) hipLaunchKernelGGL(!rects ? k_stream_windows_resized : k_bstream_windows_resized, grid, dim3(256), 0, s, r);
+    else
+      hipLaunchKernelGGL(!rects ? (half ? k_stream_windows_resized_tensor<_Float16> : k_stream_windows_resized_tensor<float>)
+                                : (half ? k_bstream_windows_resized_tensor<_Float16> : k_bstream_windows_resized_tensor<float>),
+                         grid, dim3(256), 0, s, r, *f);
+  }
+
+  void launch_stream_windows_resized(const WindowResizeParams &r, const limg_hip_tensor_format *f, int cus, hipStream_t s) { launch_windows_resized(false, f, r, cus, s); }
+
+  void launch_blocked_stream_windows_resized(const WindowResizeParams &r, const limg_hip_tensor_format *f, int cus, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_bstream_windows_map, window_grid(r.b.totalItems, cus, 8u), dim3(256), 0, s, r.b);
+    launch_windows_resized(true, f, r, cus, s);
   }
 }

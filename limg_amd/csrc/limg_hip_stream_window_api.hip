@@ -36,15 +36,22 @@ namespace
     uint32_t elemBytes, planes;
   };
   // any of the four public window structs; level: the scaled ones' log2Scale (the others are level 0), the window is in that level's coordinates
+  // ... or of the two resized ones: x0 .. height is then the SOURCE rectangle in full-resolution pixels, level may be LIMG_HIP_RESIZE_AUTO, and the output has a
+  // size of its own
   struct WindowView
   {
     size_t x0, y0, width, height, level;
     WindowOut out;
+    bool resized;
+    size_t outW, outH;
+    uint32_t flags;
   };
   template <class WIN, class = void> struct IsPlanar : std::false_type {}; // limg_hip_[scaled_]tensor_window: rowStride and planeStride, pixels of the format's type
   template <class WIN> struct IsPlanar<WIN, std::void_t<decltype(WIN::planeStride)>> : std::true_type {};
   template <class WIN, class = void> struct IsScaled : std::false_type {}; // limg_hip_scaled_[tensor_]window: log2Scale
   template <class WIN> struct IsScaled<WIN, std::void_t<decltype(WIN::log2Scale)>> : std::true_type {};
+  template <class WIN, class = void> struct IsResized : std::false_type {}; // limg_hip_resized_[tensor_]window: outWidth, outHeight, flags
+  template <class WIN> struct IsResized<WIN, std::void_t<decltype(WIN::outWidth)>> : std::true_type {};
 
   template <class WIN> WindowView window_view(const WIN &w, const limg_hip_tensor_format *f)
   {
@@ -52,14 +59,17 @@ namespace
     if constexpr (IsPlanar<WIN>::value) v.out = { w.pOut, w.rowStride, w.planeStride, f->type == LIMG_HIP_TENSOR_F16 ? 2u : 4u, f->planes };
     else v.out.rowStride = w.outStridePixels;
     if constexpr (IsScaled<WIN>::value) v.level = w.log2Scale;
+    if constexpr (IsResized<WIN>::value) { v.resized = true; v.outW = w.outWidth; v.outH = w.outHeight; v.flags = w.flags; }
     return v;
   }
   // ... and back: the staged form of a window, densely packed at `p`
   template <class WIN> void stage_window(WIN &w, void *p)
   {
     w.pOut = (decltype(w.pOut))p;
-    if constexpr (IsPlanar<WIN>::value) { w.rowStride = w.width; w.planeStride = w.width * w.height; }
-    else w.outStridePixels = w.width;
+    size_t width = w.width, height = w.height;
+    if constexpr (IsResized<WIN>::value) { width = w.outWidth; height = w.outHeight; }
+    if constexpr (IsPlanar<WIN>::value) { w.rowStride = width; w.planeStride = width * height; }
+    else w.outStridePixels = width;
   }
   WindowView rgba_view(size_t x0, size_t y0, size_t width, size_t height, uint32_t *pOut, size_t outStridePixels)
   {
@@ -84,17 +94,52 @@ namespace
     return !(w.x0 >= sizeX || w.width > sizeX - w.x0 || w.y0 >= sizeY || w.height > sizeY - w.y0);
   }
 
+  // ---- the same three checks for any view: a resized one states its strides on the output's size and carries a level that may be AUTO ----
+  size_t out_width(const WindowView &w) { return w.resized ? w.outW : w.width; }
+  size_t out_height(const WindowView &w) { return w.resized ? w.outH : w.height; }
+  // what is checked where a zero width is
+  limg_hip_result view_size_check(const WindowView &w)
+  {
+    if (!w.resized) return w.level > 3 ? limg_hip_error_InvalidParameter : window_out_check(w.width, w.height, w.out);
+    if ((w.level > 3 && w.level != LIMG_HIP_RESIZE_AUTO) || (w.flags & ~LIMG_HIP_RESIZE_FLIP_X) != 0 || w.width == 0 || w.height == 0) return limg_hip_error_InvalidParameter;
+    if (w.outW == 0 || w.outW > 32768 || w.outH == 0 || w.outH > 32768) return limg_hip_error_InvalidParameter;
+    return window_out_check(w.outW, w.outH, w.out);
+  }
+  // a resized view's level: AUTO is the deepest level that leaves at least one level pixel per output pixel on both axes
+  uint32_t resize_level(const WindowView &w)
+  {
+    if (w.level != LIMG_HIP_RESIZE_AUTO) return (uint32_t)w.level;
+    uint32_t L = 0;
+    while (L < 3 && (w.width >> (L + 1)) >= w.outW && (w.height >> (L + 1)) >= w.outH) L++;
+    return L;
+  }
+  // scaled: the window inside the level's image; resized: the rectangle inside the image, and its first column and row among those the level keeps
+  bool view_inside(size_t sizeX, size_t sizeY, const WindowView &w)
+  {
+    if (!w.resized) return window_inside(sizeX >> w.level, sizeY >> w.level, w);
+    if (!window_inside(sizeX, sizeY, w)) return false;
+    const uint32_t L = resize_level(w);
+    const size_t RX = sizeX >> L, RY = sizeY >> L;
+    return RX != 0 && RY != 0 && (w.x0 >> L) <= RX - 1 && (w.y0 >> L) <= RY - 1;
+  }
+
   // the checks and the parameters the two versions share, without touching the device; `bound`: the version's limg_hip_*stream_bound(sizeX, sizeY).  status, map and
   // state are the caller's to set.  A window at level > 0 lies inside (sizeX >> level) x (sizeY >> level), and wp gets its source footprint (x0 .. height times
   // 1 << level: inside the image, so nothing overflows) with vecOut stated on the window itself.
   limg_hip_result window_fill(const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, const WindowView &w, WindowDecodeParams &wp)
   {
     const WindowOut &o = w.out;
-    const size_t level = w.level;
-    if (level > 3 || window_out_check(w.width, w.height, o) != limg_hip_success || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
+    if (view_size_check(w) != limg_hip_success || bound == 0 || streamBytes < sizeof(limg_hip_stream_header)) return limg_hip_error_InvalidParameter;
     if (((uintptr_t)pStream & 15u) != 0 || !out_aligned(o)) return limg_hip_error_InvalidParameter;
-    if (!window_inside(sizeX >> level, sizeY >> level, w)) return limg_hip_error_OutOfBounds;
-    const size_t x0 = w.x0 << level, y0 = w.y0 << level, width = w.width << level, height = w.height << level;
+    if (!view_inside(sizeX, sizeY, w)) return limg_hip_error_OutOfBounds;
+    const size_t level = w.resized ? resize_level(w) : w.level;
+    size_t x0 = w.x0 << level, y0 = w.y0 << level, width = w.width << level, height = w.height << level;
+    if (w.resized)
+    { // the footprint: the level pixels lo .. hi of both axes, in full-resolution pixels
+      const size_t lox = w.x0 >> level, loy = w.y0 >> level;
+      const size_t hix = resize_hi((uint32_t)w.x0, (uint32_t)w.width, (uint32_t)level, (uint32_t)sizeX), hiy = resize_hi((uint32_t)w.y0, (uint32_t)w.height, (uint32_t)level, (uint32_t)sizeY);
+      x0 = lox << level; y0 = loy << level; width = (hix - lox + 1) << level; height = (hiy - loy + 1) << level;
+    }
     memset(&wp, 0, sizeof(wp));
     wp.sizeX = (uint32_t)sizeX; wp.sizeY = (uint32_t)sizeY;
     wp.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock); wp.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
@@ -105,7 +150,7 @@ namespace
     wp.wbx = (uint32_t)((x0 + width - 1) / kBlock) - wp.bx0 + 1; wp.wby = (uint32_t)((y0 + height - 1) / kBlock) - wp.by0 + 1;
     wp.out = (uint32_t *)o.p; wp.outStride = o.rowStride; wp.planeStride = o.planeStride;
     const size_t per = 16u / o.elemBytes; // elements per 16-byte store (planeStride is 0 for RGBA)
-    wp.vecOut = ((uintptr_t)o.p & 15u) == 0 && o.rowStride % per == 0 && o.planeStride % per == 0 && w.x0 % per == 0;
+    wp.vecOut = !w.resized && ((uintptr_t)o.p & 15u) == 0 && o.rowStride % per == 0 && o.planeStride % per == 0 && w.x0 % per == 0; // (resized: one element per store)
     wp.log2Scale = (uint32_t)level;
     return limg_hip_success;
   }
@@ -180,6 +225,40 @@ namespace
   // ---- batched: limg_hip_*decode_stream_windows* ----
   size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
+  // A resized job's output tiles: the largest tiles, at most kResizeTileEdge on a side, whose level-L footprint -- the taps of a tile's first and last output column
+  // and row, by the kernel's own arithmetic -- holds at most `cap` level pixels for EVERY tile of the job; the side with the wider footprint shrinks by an eighth until it does.
+  // A tile of one output pixel taps 2 x 2 at most, so the search ends (cap >= 4).  wp: the job's filled parameters (its footprint and level).
+  void plan_tiles(const WindowView &w, const WindowDecodeParams &wp, uint32_t cap, ResizeJob &rj)
+  {
+    const uint32_t L = wp.log2Scale, lox = wp.x0 >> L, hix = lox + (wp.width >> L) - 1u, loy = wp.y0 >> L, hiy = loy + (wp.height >> L) - 1u;
+    memset(&rj, 0, sizeof(rj));
+    rj.outW = (uint32_t)w.outW; rj.outH = (uint32_t)w.outH;
+    rj.x0 = (uint32_t)w.x0; rj.y0 = (uint32_t)w.y0; rj.srcW = (uint32_t)w.width; rj.srcH = (uint32_t)w.height;
+    rj.flags = w.flags;
+    const unsigned long long step = (unsigned long long)rj.srcH << 18;
+    rj.stepQ = step / rj.outH; rj.stepR = (uint32_t)(step % rj.outH);
+    // the widest footprint of a tile of `t` outputs along an axis (a mirrored axis cuts its tiles from the other end)
+    auto span = [L](uint32_t out, uint32_t t, bool flip, uint32_t s0, uint32_t len, uint32_t lo, uint32_t hi) {
+      uint32_t worst = 0;
+      for (uint32_t X0 = 0; X0 < out; X0 += t)
+      {
+        const uint32_t n = std::min(t, out - X0), first = flip ? out - X0 - n : X0;
+        worst = std::max(worst, resize_axis(first + n - 1u, s0, len, out, L, lo, hi).b - resize_axis(first, s0, len, out, L, lo, hi).a + 1u);
+      }
+      return worst;
+    };
+    uint32_t tw = std::min(rj.outW, kResizeTileEdge), th = std::min(rj.outH, kResizeTileEdge);
+    for (;;)
+    {
+      const uint32_t fw = span(rj.outW, tw, (rj.flags & LIMG_HIP_RESIZE_FLIP_X) != 0, rj.x0, rj.srcW, lox, hix), fh = span(rj.outH, th, false, rj.y0, rj.srcH, loy, hiy);
+      if ((unsigned long long)fw * fh <= cap) break;
+      if ((fw >= fh && tw > 1u) || th == 1u) tw -= std::max(1u, tw / 8u);
+      else th -= std::max(1u, th / 8u);
+    }
+    rj.tileW = tw; rj.tileH = th; rj.tilesX = (rj.outW + tw - 1u) / tw;
+  }
+  unsigned long long tile_count(const ResizeJob &rj) { return (unsigned long long)rj.tilesX * ((rj.outH + rj.tileH - 1u) / rj.tileH); }
+
   // One call: every job checked on the host before anything touches the device, then the job table built in a pinned slot of the context's ring, copied on `s`,
   // and the version's one (two) launches.  JOB: any of the four public job types -- its window says whether the pixels go to planes of pFormat's type (else pFormat is
   // not looked at) and whether it carries a level, which then selects the scaled kernels: the same checks, table and launches otherwise.
@@ -188,7 +267,7 @@ namespace
                                         hipStream_t s)
   {
     typedef decltype(JOB::window) WIN;
-    constexpr bool tensor = IsPlanar<WIN>::value, scaled = IsScaled<WIN>::value;
+    constexpr bool tensor = IsPlanar<WIN>::value, scaled = IsScaled<WIN>::value, resized = IsResized<WIN>::value;
     if (!c || !pJobs || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
     if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
     if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
@@ -197,8 +276,11 @@ namespace
       return window_fill(j.pStream, j.streamBytes, j.sizeX, j.sizeY, v.bound(j.sizeX, j.sizeY), window_view(j.window, pFormat), wp);
     };
     // pass 1: the single-window entry's checks, job by job in its order; the sums the table's layout needs
-    unsigned long long units = 0, blocks = 0;
+    unsigned long long units = 0, blocks = 0, tiles = 0;
+    // (the resized entries) the tile capacity the host plans with: the kernel's, or the test build's smaller one
+    const uint32_t tileCap = TOPT(c, resize_tile_pixels) > 0 ? std::max(4u, std::min((uint32_t)TOPT(c, resize_tile_pixels), kResizeTilePixels)) : kResizeTilePixels;
     WindowDecodeParams wp;
+    ResizeJob rj;
     for (size_t i = 0; i < count; i++)
     {
       const JOB &j = pJobs[i];
@@ -208,16 +290,23 @@ namespace
       if (v.tableExtent && j.streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
       units += window_units(v, wp);
       blocks += (unsigned long long)wp.wbx * wp.wby;
+      if (resized)
+      {
+        plan_tiles(window_view(j.window, pFormat), wp, tileCap, rj);
+        tiles += tile_count(rj);
+      }
     }
-    if (units > 0xFFFFFFFFull || blocks > 0xFFFFFFFFull) return limg_hip_error_InvalidParameter;
+    if (units > 0xFFFFFFFFull || blocks > 0xFFFFFFFFull || tiles > 0xFFFFFFFFull) return limg_hip_error_InvalidParameter;
 
     HIP_TRY(hipSetDevice(c->device));
     limg_hip_result r;
     if ((r = ensure_stream_status(c, s)) != limg_hip_success) return r;
-    // the slot: [jobs | unitBase | groups | groupJobs | groupItemBase] is uploaded; [state | map] behind it exists on the device only (version 2)
+    // the slot: [jobs | unitBase | groups | groupJobs | groupItemBase | resize | tileBase] is uploaded (the last two: the resized entries' second per-job table and
+    // the prefix of its tile counts); [state | map] behind it exists on the device only (version 2)
     const size_t oJobs = 0, oUnitBase = align16(oJobs + count * sizeof(WindowDecodeParams)), oGroups = align16(oUnitBase + (count + 1) * 4);
     const size_t oGroupJobs = rects ? align16(oGroups + count * sizeof(WindowGroup)) : oGroups, oItemBase = rects ? align16(oGroupJobs + count * 4) : oGroups;
-    const size_t upload = rects ? align16(oItemBase + (count + 1) * 4) : oGroups;
+    const size_t oResize = rects ? align16(oItemBase + (count + 1) * 4) : oGroups, oTileBase = resized ? align16(oResize + count * sizeof(ResizeJob)) : oResize;
+    const size_t upload = resized ? align16(oTileBase + (count + 1) * 4) : oResize;
     const size_t oState = upload, oMap = align16(oState + (rects ? count * 8 : 0)), total = oMap + (rects ? (size_t)blocks * 4 : 0);
     limg_hip_context::WindowSlot &slot = c->window.slots[c->window.next];
     c->window.next = (c->window.next + 1) % limg_hip_context::kWindowSlots;
@@ -234,10 +323,18 @@ namespace
     uint32_t *unitBase = (uint32_t *)(hb + oUnitBase);
 
     // pass 2: the table (the checks of pass 1 cannot fail again)
-    uint32_t unitAt = 0, blockAt = 0;
+    uint32_t unitAt = 0, blockAt = 0, tileAt = 0;
+    ResizeJob *resize = (ResizeJob *)(hb + oResize);
+    uint32_t *tileBase = (uint32_t *)(hb + oTileBase);
     for (size_t i = 0; i < count; i++)
     {
       (void)fill(pJobs[i], jobs[i]);
+      if (resized)
+      {
+        plan_tiles(window_view(pJobs[i].window, pFormat), jobs[i], tileCap, resize[i]);
+        tileBase[i] = tileAt;
+        tileAt += (uint32_t)tile_count(resize[i]);
+      }
       jobs[i].status = (uint32_t *)c->stream.status.p;
       if (rects)
       {
@@ -249,6 +346,7 @@ namespace
       blockAt += jobs[i].wbx * jobs[i].wby;
     }
     unitBase[count] = unitAt;
+    if (resized) tileBase[count] = tileAt;
     WindowBatchParams b;
     memset(&b, 0, sizeof(b));
     b.jobs = (const WindowDecodeParams *)(db + oJobs); b.unitBase = (const uint32_t *)(db + oUnitBase);
@@ -298,7 +396,13 @@ namespace
       HIP_TRY(hipMemsetAsync(db + oMap, 0xFF, (size_t)blocks * 4, s)); // no block has a rectangle yet
     }
     if (pJobStatus) HIP_TRY(hipMemsetAsync(pJobStatus, 0, count * 4, s));
-    (rects ? launch_blocked_stream_windows : launch_stream_windows)(b, scaled, tensor ? pFormat : nullptr, device_cus(c), s);
+    if (resized)
+    { // a workgroup per output tile; version 2's map kernel first, as it is
+      const WindowResizeParams rp = { b, (const ResizeJob *)(db + oResize), (const uint32_t *)(db + oTileBase), tileAt };
+      (rects ? launch_blocked_stream_windows_resized : launch_stream_windows_resized)(rp, tensor ? pFormat : nullptr, device_cus(c), s);
+    }
+    else
+      (rects ? launch_blocked_stream_windows : launch_stream_windows)(b, scaled, tensor ? pFormat : nullptr, device_cus(c), s);
     const hipError_t launched = hipGetLastError();
     HIP_TRY(hipEventRecord(slot.done, s));
     HIP_TRY(launched);
@@ -319,8 +423,7 @@ namespace
     {
       const WindowView w = window_view(pWindows[i], pFormat);
       if (!w.out.p) return limg_hip_error_ArgumentNull;
-      if (w.level > 3) return limg_hip_error_InvalidParameter;
-      const limg_hip_result ok = window_out_check(w.width, w.height, w.out);
+      const limg_hip_result ok = view_size_check(w);
       if (ok != limg_hip_success) return ok;
       if (tensor && !out_aligned(w.out)) return limg_hip_error_InvalidParameter;
     }
@@ -334,8 +437,8 @@ namespace
     for (size_t i = 0; i < count; i++)
     {
       const WindowView w = window_view(pWindows[i], pFormat);
-      if (!window_inside(sizeX >> w.level, sizeY >> w.level, w)) return limg_hip_error_OutOfBounds;
-      elems += (planes * w.width * w.height + per - 1) / per * per;
+      if (!view_inside(sizeX, sizeY, w)) return limg_hip_error_OutOfBounds;
+      elems += (planes * out_width(w) * out_height(w) + per - 1) / per * per;
     }
     JOB *jobs = new (std::nothrow) JOB[count];
     if (!jobs) return limg_hip_error_MemoryAllocationFailure;
@@ -350,16 +453,18 @@ namespace
       jobs[i].pStream = (const uint8_t *)c->stream.buf.p; jobs[i].streamBytes = total; jobs[i].sizeX = sizeX; jobs[i].sizeY = sizeY;
       jobs[i].window = pWindows[i];
       stage_window(jobs[i].window, (uint8_t *)c->host.planes.p + at * eb);
-      at += (planes * pWindows[i].width * pWindows[i].height + per - 1) / per * per;
+      const WindowView w = window_view(pWindows[i], pFormat);
+      at += (planes * out_width(w) * out_height(w) + per - 1) / per * per;
     }
     if ((r = decode_windows_device(c, v, jobs, count, pFormat, nullptr, nullptr)) != limg_hip_success) return r;
     if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r; // a stream refused for any window: no pOut is touched
     for (size_t i = 0; i < count; i++)
     {
       const WindowView w = window_view(pWindows[i], pFormat);
+      const size_t ow = out_width(w), oh = out_height(w);
       for (size_t pl = 0; pl < planes; pl++)
-        HIP_TRY(hipMemcpy2D((uint8_t *)w.out.p + pl * w.out.planeStride * eb, w.out.rowStride * eb, (const uint8_t *)jobs[i].window.pOut + pl * w.width * w.height * eb,
-                            w.width * eb, w.width * eb, w.height, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy2D((uint8_t *)w.out.p + pl * w.out.planeStride * eb, w.out.rowStride * eb, (const uint8_t *)jobs[i].window.pOut + pl * ow * oh * eb, ow * eb, ow * eb, oh,
+                            hipMemcpyDeviceToHost));
     }
     return limg_hip_success;
   }
@@ -429,4 +534,28 @@ extern "C"
   limg_hip_result limg_hip_blocked_decode_stream_windows_scaled_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes,
                                                                        const limg_hip_scaled_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat)
   { return decode_windows_host<limg_hip_scaled_tensor_window_job>(c, kVersion2, pStream, streamBytes, pWindows, count, pFormat); }
+
+  // ---- batched, resized, RGBA8 and tensors: the job types with a source rectangle and an output size ----
+  limg_hip_result limg_hip_decode_stream_windows_resized_device(limg_hip_context *c, const limg_hip_resized_window_job *pJobs, size_t count, uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion1, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_resized_device(limg_hip_context *c, const limg_hip_resized_window_job *pJobs, size_t count, uint32_t *pJobStatus,
+                                                                        void *stream)
+  { return decode_windows_device(c, kVersion2, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_decode_stream_windows_resized(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_resized_window *pWindows, size_t count)
+  { return decode_windows_host<limg_hip_resized_window_job>(c, kVersion1, pStream, streamBytes, pWindows, count, nullptr); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_resized(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_resized_window *pWindows,
+                                                                 size_t count)
+  { return decode_windows_host<limg_hip_resized_window_job>(c, kVersion2, pStream, streamBytes, pWindows, count, nullptr); }
+  limg_hip_result limg_hip_decode_stream_windows_resized_tensor_device(limg_hip_context *c, const limg_hip_resized_tensor_window_job *pJobs, size_t count,
+                                                                       const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion1, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_resized_tensor_device(limg_hip_context *c, const limg_hip_resized_tensor_window_job *pJobs, size_t count,
+                                                                               const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion2, pJobs, count, pFormat, pJobStatus, (hipStream_t)stream); }
+  limg_hip_result limg_hip_decode_stream_windows_resized_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_resized_tensor_window *pWindows,
+                                                                size_t count, const limg_hip_tensor_format *pFormat)
+  { return decode_windows_host<limg_hip_resized_tensor_window_job>(c, kVersion1, pStream, streamBytes, pWindows, count, pFormat); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_resized_tensor(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes,
+                                                                        const limg_hip_resized_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat)
+  { return decode_windows_host<limg_hip_resized_tensor_window_job>(c, kVersion2, pStream, streamBytes, pWindows, count, pFormat); }
 }

@@ -14,7 +14,8 @@
 // `--out-dir <dir>`, `--stream <file>` (also write the compact LMG3 stream of the 8x8 path and verify that it decodes to that path's image),
 // `--blocked-stream <file>` (single-file merged-block mode: write the version 2 stream of that very encode and verify that it decodes to its image),
 // and the extra mode `limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]` (either version; with --window only that pixel rectangle
-// is decoded; with --scale k the image reduced by k x k box means, the window then in the reduced image's coordinates).
+// is decoded; with --scale k the image reduced by k x k box means, the window then in the reduced image's coordinates; with --resize WxH the image or the window,
+// stated in full-resolution pixels, resampled to W x H pixels, mirrored with --flip).
 #include <inttypes.h>
 #include <math.h>
 #include <stdio.h>
@@ -237,7 +238,8 @@ struct Options
 static const char *const kUsage =
     "Usage:\nlimg_hip_cli [<InputFile> | --] [--no-output | --error-factor <Factor> | --accurate-bit-crushing | --single-thread | --fixed-blocks | --threads <T> | --out-dir <dir> | "
     "--stream <file> [--max-bytes <N> [--min-error-factor <A>] [--max-error-factor <B>]] | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n"
-    "limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n";
+    "limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n"
+    "limg_hip_cli --decode <file.lmg3> [<out.tga>] --resize WxH [--window x,y,w,h] [--flip]\n";
 
 static bool parse_number(const char *text, uint64_t &value)
 {
@@ -525,7 +527,10 @@ static int run_benchmark_list(const Options &o, limg_thread_pool *pool)
 // extra mode: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]   (limg_decode of a compact stream written by --stream or
 // --blocked-stream; with --window: limg_decode_window of that pixel rectangle only, a w x h image; with --scale k: limg_decode_windows_scaled at level log2 k -- the
 // image of (sizeX / k) x (sizeY / k) box means, or the --window of it, which is then in that image's coordinates)
-static const char *const kDecodeUsage = "Usage: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n";
+// with --resize WxH: limg_decode_windows_resized -- the image, or the --window of it (full-resolution pixels), resampled bilinearly to W x H pixels from the deepest
+// box level that keeps a level pixel per output pixel, mirrored with --flip
+static const char *const kDecodeUsage = "Usage: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n"
+                                        "       limg_hip_cli --decode <file.lmg3> [<out.tga>] --resize WxH [--window x,y,w,h] [--flip]\n";
 
 static bool parse_window(const char *text, size_t win[4])
 {
@@ -544,7 +549,8 @@ static int run_decode(int argc, const char **argv)
 {
   const char *in = nullptr, *out = "limg_out.tga";
   size_t win[4] = { 0, 0, 0, 0 };
-  bool window = false;
+  bool window = false, resize = false, flip = false;
+  size_t outW = 0, outH = 0; // --resize
   int positional = 0, level = -1; // level: log2 of --scale, -1 without it
   for (int i = 2; i < argc; i++)
   {
@@ -559,17 +565,44 @@ static int run_decode(int argc, const char **argv)
       level = !strcmp(v, "1") ? 0 : !strcmp(v, "2") ? 1 : !strcmp(v, "4") ? 2 : !strcmp(v, "8") ? 3 : -1;
       if (level < 0) FAIL(EXIT_FAILURE, "'--scale' takes 1, 2, 4 or 8.\n%s", kDecodeUsage);
     }
+    else if (!strcmp(argv[i], "--resize"))
+    {
+      const char *v = i + 1 < argc ? argv[++i] : "";
+      char *end = nullptr;
+      outW = (*v >= '0' && *v <= '9') ? (size_t)strtoull(v, &end, 10) : 0;
+      outH = (end && *end == 'x' && end[1] >= '0' && end[1] <= '9') ? (size_t)strtoull(end + 1, &end, 10) : 0;
+      if (outW == 0 || outH == 0 || outW > 32768 || outH > 32768 || *end != '\0') FAIL(EXIT_FAILURE, "'--resize' takes WxH in pixels, 1 to 32768 each.\n%s", kDecodeUsage);
+      resize = true;
+    }
+    else if (!strcmp(argv[i], "--flip")) flip = true;
     else if (positional == 0) { in = argv[i]; positional++; }
     else if (positional == 1) { out = argv[i]; positional++; }
     else FAIL(EXIT_FAILURE, "%s", kDecodeUsage);
   }
   if (!in) FAIL(EXIT_FAILURE, "%s", kDecodeUsage);
+  if (resize && level >= 0) FAIL(EXIT_FAILURE, "'--resize' chooses its level itself: it does not go with '--scale'.\n%s", kDecodeUsage);
+  if (flip && !resize) FAIL(EXIT_FAILURE, "'--flip' goes with '--resize'.\n%s", kDecodeUsage);
   std::vector<uint8_t> stream;
   if (!read_file(in, stream)) FAIL(EXIT_FAILURE, "Failed to read '%s'.\n", in);
   size_t sx = 0, sy = 0;
   bool alpha = false;
   limg_result r = limg_decode_info(stream.data(), stream.size(), &sx, &sy, &alpha);
   if (r != limg_success) FAIL(EXIT_FAILURE, "'%s' is not an LMG3 stream (0x%" PRIX32 ").\n", in, (uint32_t)r);
+  if (resize)
+  {
+    if (!window) { win[0] = 0; win[1] = 0; win[2] = sx; win[3] = sy; }
+    if (win[2] == 0 || win[3] == 0 || win[0] >= sx || win[2] > sx - win[0] || win[1] >= sy || win[3] > sy - win[1])
+      FAIL(EXIT_FAILURE, "The window %" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 " is not inside the image (%" PRIu64 " x %" PRIu64 " pixels).\n", (uint64_t)win[0], (uint64_t)win[1],
+           (uint64_t)win[2], (uint64_t)win[3], (uint64_t)sx, (uint64_t)sy);
+    std::vector<uint32_t> image(outW * outH);
+    limg_hip_resized_window w = { win[0], win[1], win[2], win[3], image.data(), outW, outW, outH, LIMG_HIP_RESIZE_AUTO, flip ? LIMG_HIP_RESIZE_FLIP_X : 0u };
+    r = limg_decode_windows_resized(stream.data(), stream.size(), &w, 1);
+    if (r != limg_success) FAIL(EXIT_FAILURE, "limg_decode_windows_resized failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
+    printf("%" PRIu64 " x %" PRIu64 " pixels, %s; window %" PRIu64 " x %" PRIu64 " at (%" PRIu64 ", %" PRIu64 ") resized to %" PRIu64 " x %" PRIu64 "%s.\n", (uint64_t)sx, (uint64_t)sy,
+           alpha ? "RGBA" : "RGB", (uint64_t)win[2], (uint64_t)win[3], (uint64_t)win[0], (uint64_t)win[1], (uint64_t)outW, (uint64_t)outH, flip ? ", mirrored" : "");
+    puts(write_tga(out, outW, outH, 4, image.data()) ? "Wrote decoded file." : "Failed to write decoded file.");
+    return EXIT_SUCCESS;
+  }
   if (level >= 0)
   {
     const size_t rx = sx >> level, ry = sy >> level;
