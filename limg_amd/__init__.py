@@ -738,40 +738,42 @@ class LimgHip:
                           min_error_factor, max_error_factor, pool_threads, int(fast), C.byref(res), self._stream())
         return out, res
 
-    # ---- batched stream encode: a list of same-shape images, stream i = encode_stream of image i (contract: include/limg_hip.h) ----
+    # ---- the list entries of the stream encode family (contract: include/limg_hip.h) ----
+    def _stream_list(self, name, imgs, has_alpha, outs, rest, device):
+        """One call of list entry `name`: the pointer arrays of the images (device: torch int32 CUDA tensors, else host arrays) and of the stream buffers (`outs`, or made
+        here at the worst-case size), the smallest buffer as the capacity, then the entry's own arguments `rest`.  An empty list is a call too, of 8 x 8 images.  -> outs"""
+        if not device:
+            imgs = [np.ascontiguousarray(i, dtype=np.uint32) for i in imgs]
+        n = len(imgs)
+        h, w = tuple(imgs[0].shape) if n else (8, 8)
+        assert all(tuple(i.shape) == (h, w) for i in imgs)
+        bound = self.stream_bound(w, h)
+        if outs is None and device:
+            import torch
+            outs = [torch.empty(bound, dtype=torch.uint8, device=imgs[0].device) for _ in range(n)]
+        elif outs is None:
+            outs = [np.zeros(bound, dtype=np.uint8) for _ in range(n)]
+        assert len(outs) == n
+        ptr = (lambda t: t.data_ptr()) if device else (lambda a: a.ctypes.data)
+        cap = min([o.numel() if device else o.size for o in outs], default=bound)
+        self._stream_call(name, n, (C.c_void_p * max(n, 1))(*map(ptr, imgs)), w, h, int(has_alpha), (C.c_void_p * max(n, 1))(*map(ptr, outs)), cap, *rest,
+                          *([self._stream()] if device else []))
+        return outs
+
+    # ---- batched stream encode: a list of same-shape images, stream i = encode_stream of image i ----
     def encode_stream_batch(self, imgs, has_alpha, error_factor=100, pool_threads=0, fast=True):
         """host uint32 images of one shape -> list of stream bytes (numpy uint8), one batched call"""
-        imgs = [np.ascontiguousarray(i, dtype=np.uint32) for i in imgs]
-        n = len(imgs)
-        if n == 0:
-            self._stream_call("limg_hip_encode_stream_batch", 0, (C.c_void_p * 1)(), 8, 8, int(has_alpha), (C.c_void_p * 1)(), self.stream_bound(8, 8), (C.c_size_t * 1)(),
-                              error_factor, pool_threads, int(fast))
-            return []
-        h, w = imgs[0].shape
-        assert all(i.shape == (h, w) for i in imgs)
-        cap = self.stream_bound(w, h)
-        outs = [np.zeros(cap, dtype=np.uint8) for _ in range(n)]
-        sizes = (C.c_size_t * n)()
-        self._stream_call("limg_hip_encode_stream_batch", n, (C.c_void_p * n)(*[i.ctypes.data for i in imgs]), w, h, int(has_alpha),
-                          (C.c_void_p * n)(*[o.ctypes.data for o in outs]), cap, sizes, error_factor, pool_threads, int(fast))
+        sizes = (C.c_size_t * max(len(imgs), 1))()
+        outs = self._stream_list("limg_hip_encode_stream_batch", imgs, has_alpha, None, (sizes, error_factor, pool_threads, int(fast)), False)
         return [o[:sizes[k]].copy() for k, o in enumerate(outs)]
 
     def encode_stream_batch_device(self, imgs, has_alpha, outs=None, want_sizes=True, error_factor=100, pool_threads=0, fast=True):
         """imgs: list of torch int32 CUDA tensors (h, w) of one shape -> (list of torch uint8 CUDA stream buffers of worst-case size, list of bytes used or None).
         outs: the buffers to use (each at least stream_bound(w, h) bytes, the smallest is the capacity handed on).  Asynchronous on torch's current stream unless
         want_sizes."""
-        import torch
-        n = len(imgs)
-        h, w = imgs[0].shape
-        assert all(tuple(i.shape) == (h, w) for i in imgs)
-        if outs is None:
-            outs = [torch.empty(self.stream_bound(w, h), dtype=torch.uint8, device=imgs[0].device) for _ in range(n)]
-        assert len(outs) == n
-        sizes = (C.c_size_t * n)()
-        self._stream_call("limg_hip_encode_stream_batch_device", n, (C.c_void_p * n)(*[i.data_ptr() for i in imgs]), w, h, int(has_alpha),
-                          (C.c_void_p * n)(*[o.data_ptr() for o in outs]), min(o.numel() for o in outs), sizes if want_sizes else None, error_factor, pool_threads, int(fast),
-                          self._stream())
-        return outs, ([int(v) for v in sizes] if want_sizes else None)
+        sizes = (C.c_size_t * max(len(imgs), 1))()
+        outs = self._stream_list("limg_hip_encode_stream_batch_device", imgs, has_alpha, outs, (sizes if want_sizes else None, error_factor, pool_threads, int(fast)), True)
+        return outs, ([int(v) for v in sizes[:len(imgs)]] if want_sizes else None)
 
     # ---- budgeted stream encode of a list: result i = encode_stream_budget of image i with its budget (contract: include/limg_hip.h) ----
     @staticmethod
@@ -785,40 +787,16 @@ class LimgHip:
 
     def encode_stream_budget_batch(self, imgs, has_alpha, max_bytes, min_error_factor=0, max_error_factor=0, pool_threads=0, fast=True):
         """host uint32 images of one shape, max_bytes an int or one per image -> (list of stream bytes (numpy uint8), list of BudgetResult), one batched call"""
-        imgs = [np.ascontiguousarray(i, dtype=np.uint32) for i in imgs]
-        n = len(imgs)
-        budgets, results = self._budget_list(max_bytes, n)
-        if n == 0:
-            self._stream_call("limg_hip_encode_stream_budget_batch", 0, (C.c_void_p * 1)(), 8, 8, int(has_alpha), (C.c_void_p * 1)(), self.stream_bound(8, 8), budgets,
-                              min_error_factor, max_error_factor, pool_threads, int(fast), results)
-            return [], []
-        h, w = imgs[0].shape
-        assert all(i.shape == (h, w) for i in imgs)
-        cap = self.stream_bound(w, h)
-        outs = [np.zeros(cap, dtype=np.uint8) for _ in range(n)]
-        self._stream_call("limg_hip_encode_stream_budget_batch", n, (C.c_void_p * n)(*[i.ctypes.data for i in imgs]), w, h, int(has_alpha),
-                          (C.c_void_p * n)(*[o.ctypes.data for o in outs]), cap, budgets, min_error_factor, max_error_factor, pool_threads, int(fast), results)
-        return [o[:results[k].bytes].copy() for k, o in enumerate(outs)], list(results)
+        budgets, results = self._budget_list(max_bytes, len(imgs))
+        outs = self._stream_list("limg_hip_encode_stream_budget_batch", imgs, has_alpha, None, (budgets, min_error_factor, max_error_factor, pool_threads, int(fast), results), False)
+        return [o[:results[k].bytes].copy() for k, o in enumerate(outs)], results[:len(imgs)]
 
     def encode_stream_budget_batch_device(self, imgs, has_alpha, max_bytes, min_error_factor=0, max_error_factor=0, outs=None, pool_threads=0, fast=True):
         """imgs: list of torch int32 CUDA tensors (h, w) of one shape, max_bytes an int or one per image -> (list of torch uint8 CUDA stream buffers of worst-case size,
         list of BudgetResult).  outs: the buffers to use (each at least stream_bound(w, h) bytes).  Waits for torch's current stream."""
-        import torch
-        n = len(imgs)
-        budgets, results = self._budget_list(max_bytes, n)
-        if n == 0:
-            self._stream_call("limg_hip_encode_stream_budget_batch_device", 0, (C.c_void_p * 1)(), 8, 8, int(has_alpha), (C.c_void_p * 1)(), self.stream_bound(8, 8), budgets,
-                              min_error_factor, max_error_factor, pool_threads, int(fast), results, self._stream())
-            return [], []
-        h, w = imgs[0].shape
-        assert all(tuple(i.shape) == (h, w) for i in imgs)
-        if outs is None:
-            outs = [torch.empty(self.stream_bound(w, h), dtype=torch.uint8, device=imgs[0].device) for _ in range(n)]
-        assert len(outs) == n
-        self._stream_call("limg_hip_encode_stream_budget_batch_device", n, (C.c_void_p * n)(*[i.data_ptr() for i in imgs]), w, h, int(has_alpha),
-                          (C.c_void_p * n)(*[o.data_ptr() for o in outs]), min(o.numel() for o in outs), budgets, min_error_factor, max_error_factor, pool_threads,
-                          int(fast), results, self._stream())
-        return outs, list(results)
+        budgets, results = self._budget_list(max_bytes, len(imgs))
+        outs = self._stream_list("limg_hip_encode_stream_budget_batch_device", imgs, has_alpha, outs, (budgets, min_error_factor, max_error_factor, pool_threads, int(fast), results), True)
+        return outs, results[:len(imgs)]
 
     def blocked_stream_bound(self, w, h):
         return self.lib.limg_hip_blocked_stream_bound(w, h)

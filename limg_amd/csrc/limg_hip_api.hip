@@ -1,6 +1,6 @@
 // limg_hip_api.hip -- host side of liblimg_hip.so: context life cycle, options, device status, statistics, profiling, compare and synthesis entries of the C ABI
-// (include/limg_hip.h).  The encode paths live in limg_hip_encode.hip (8x8 path), limg_hip_host_entry.hip (host pointers), limg_hip_stream_api.hip (compact stream),
-// limg_hip_blocked_api.hip (merged-block encoder) and limg_hip_multi.hip (RCCL); the noise table in limg_hip_noise_table.hip.
+// (include/limg_hip.h).  The encode paths live in limg_hip_encode.hip (8x8 path), limg_hip_host_entry.hip (host pointers), limg_hip_stream_api.hip and
+// limg_hip_stream_encode_api.hip (compact stream; version 1's encode family), limg_hip_blocked_api.hip (merged-block encoder) and limg_hip_multi.hip (RCCL); the noise table in limg_hip_noise_table.hip.
 // Mirrors the reference's driver (src/limg.cpp:2175-2265 threshold/flag setup, :2105-2138 strip partition).
 #include "limg_hip_context.h"
 

@@ -68,13 +68,10 @@ namespace
     BlockedParams &bp = j.bp;
     memset(&bp, 0, sizeof(bp));
     bp.in = pIn; bp.sizeX = (uint32_t)sizeX; bp.sizeY = (uint32_t)sizeY; bp.blocksX = j.blocksX; bp.blocksY = j.blocksY; bp.channels = (uint32_t)j.channels;
-    const uint64_t maxPixel = (uint64_t)0x6 * (errorFactor / 2) * 7, maxBlock = (uint64_t)0x4 * (errorFactor / 2) * 7; // src/limg.cpp:2343-2368, same values as the 8x8 path
-    bp.maxPixel32 = maxPixel > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxPixel;
-    bp.maxBlock = maxBlock;
-    bp.crushBits = errorFactor != 0; bp.fast = fastBitCrushing != 0;
-    const bool forced = c->opt.forced_shift[0] >= 0 && c->opt.forced_shift[0] <= 8 && c->opt.forced_shift[1] >= 0 && c->opt.forced_shift[1] <= 8 &&
-                        c->opt.forced_shift[2] >= 0 && c->opt.forced_shift[2] <= 8;
-    for (int i = 0; i < 3; i++) bp.forced[i] = forced ? c->opt.forced_shift[i] : -1;
+    const Thresholds t = thresholds(errorFactor); // src/limg.cpp:2343-2368, same values as the 8x8 path
+    bp.maxPixel32 = t.maxPixel32; bp.maxBlock = t.maxBlock;
+    bp.crushBits = (int32_t)t.crushBits; bp.fast = fastBitCrushing != 0;
+    forced_shifts(c->opt.forced_shift, bp.forced);
     bp.info = info;
     bp.scratchCap = (uint32_t)capMax;
     // k_blocked_store's 4-pixels-per-lane form: whole blocks (every rectangle row is a multiple of 8 pixels, every scratch / noise offset a multiple of 4) and planes

@@ -135,7 +135,7 @@ struct limg_hip_context
     struct { size_t sizeX = 0, sizeY = 0; int channels = 0; uint32_t errorFactor = 0, flags = 0; bool valid = false; } last; // ... its shape and stream flags; valid: it succeeded,
                            // so the buffers hold everything the stream packer reads (limg_hip_blocked_last_stream)
   } blocked{ deviceBytes };
-  // ---- the stream packers and decoders (limg_hip_stream_api.hip, limg_hip_stream_window_api.hip) ----
+  // ---- the stream packers and decoders (limg_hip_stream_api.hip, limg_hip_stream_encode_api.hip, limg_hip_stream_window_api.hip) ----
   struct Streams
   {
     Bytes &n;
@@ -205,8 +205,33 @@ namespace limg_hip
     delete[] pool;
   }
 
-  // ---- what the stream entries (limg_hip_stream_api.hip) and the window entries (limg_hip_stream_window_api.hip) share ----
+  // |record value| above which a block takes the generic 32-bit trial: EncodeParams::recordLimit and the probes' (see term_bias in limg_hip_search.h: 3 * 2700 + 1 < 0x2000)
+  inline int32_t record_limit(const limg_hip_context *c) { return TOPT(c, record_limit) > 0 ? TOPT(c, record_limit) - 1 : 2700; }
+  // images of one shape per launch pair (list_chunk, limg_hip_encode_rules.h) with the test build's batch_chunk; blocks, strips: of one image
+  inline size_t list_chunk(const limg_hip_context *c, size_t blocks, size_t strips) { return list_chunk(blocks, strips, TOPT(c, batch_chunk) > 0 ? (size_t)TOPT(c, batch_chunk) : 0); }
+
+  // ---- what the stream entries (limg_hip_stream_api.hip: shared parts, header checks, decode, version 2; limg_hip_stream_encode_api.hip: the version 1 encode family)
+  // and the window entries (limg_hip_stream_window_api.hip) share; defined in limg_hip_stream_api.hip ----
   int device_cus(const limg_hip_context *c);
+  limg_hip_result stream_total_bytes(const uint8_t *dStream, hipStream_t s, size_t *pBytes); // what the packer's scan left in the stream's header; waits for `s`
+  limg_hip_result download_stream(limg_hip_context *c, size_t bytes, uint8_t *pStream, size_t capacity, size_t *pBytes); // stream.buf to the caller; *pBytes = bytes even where `capacity` is too small
+  // a host-pointer encode: upload, deviceEncode(dIn, dStream, bound, &bytes) on the null stream, status, download.  bound: the version's limg_hip_*stream_bound
+  template <class ENCODE>
+  limg_hip_result encode_stream_host(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, uint8_t *pStream, size_t capacity, size_t *pBytes, size_t bound,
+                                     ENCODE &&deviceEncode)
+  {
+    if (bound == 0) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    limg_hip_result r;
+    const size_t px = sizeX * sizeY;
+    if ((r = c->host.in.ensure(px * 4)) != limg_hip_success) return r;
+    if ((r = c->stream.buf.ensure(bound)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->host.in.p, pIn, px * 4, hipMemcpyHostToDevice));
+    size_t bytes = 0;
+    if ((r = deviceEncode((const uint32_t *)c->host.in.p, (uint8_t *)c->stream.buf.p, bound, &bytes)) != limg_hip_success) return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    return download_stream(c, bytes, pStream, capacity, pBytes);
+  }
   limg_hip_result ensure_stream_status(limg_hip_context *c, hipStream_t s); // the decoders' status word, zeroed on `s` when it is first made
   // one RGBA8 window, checked without touching the device, as kernel parameters with the status word set; bound: the version's limg_hip_*stream_bound(sizeX, sizeY)
   limg_hip_result window_params(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, size_t bound, size_t x0, size_t y0, size_t width,

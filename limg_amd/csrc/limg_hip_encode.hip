@@ -103,12 +103,9 @@ namespace
     p.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock);
     p.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
     p.stripsX = (p.blocksX + kStripBlocks - 1) / kStripBlocks;
-    // thresholds and flags, src/limg.cpp:2186-2212
-    const uint64_t maxPixel = (uint64_t)0x6 * (errorFactor / 2) * 7, maxBlock = (uint64_t)0x4 * (errorFactor / 2) * 7;
-    p.maxPixel32 = maxPixel > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxPixel;
-    p.maxBlock = maxBlock;
-    { const uint64_t lim = (maxBlock * 64ull + 15ull) >> 4; p.blockLimitFull = lim > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim; }
-    p.crushBits = errorFactor != 0;
+    // thresholds and flags (limg_hip_encode_rules.h)
+    const Thresholds t = thresholds(errorFactor);
+    p.maxPixel32 = t.maxPixel32; p.maxBlock = t.maxBlock; p.blockLimitFull = t.blockLimitFull; p.crushBits = (int32_t)t.crushBits;
     p.fast = fast != 0;
     p.accTable = nullptr;
     if (!p.fast && p.crushBits)
@@ -117,11 +114,9 @@ namespace
       if (ra != limg_hip_success) return ra;
       p.accTable = (const uint32_t *)c->enc.accTable.p;
     }
-    const bool forced = c->opt.forced_shift[0] >= 0 && c->opt.forced_shift[0] <= 8 && c->opt.forced_shift[1] >= 0 && c->opt.forced_shift[1] <= 8 &&
-                        c->opt.forced_shift[2] >= 0 && c->opt.forced_shift[2] <= 8;
-    for (int i = 0; i < 3; i++) p.forced[i] = forced ? c->opt.forced_shift[i] : -1;
+    forced_shifts(c->opt.forced_shift, p.forced);
     p.floatFast = (c->opt.float_mode == 1 && (!x.fitOnly || x.fitFloatMode)) ? 1 : 0;
-    p.recordLimit = TOPT(c, record_limit) > 0 ? TOPT(c, record_limit) - 1 : 2700; // see term_bias in limg_hip_search.h: 3 * 2700 + 1 < 0x2000
+    p.recordLimit = record_limit(c);
     const Partition pt = e.pt = x.part ? *x.part : partition(sizeY, poolThreads);
     p.chainCount = pt.chainCount; p.chainRows = pt.chainRows;
 
@@ -523,11 +518,7 @@ extern "C"
     }
     const bool ragged = (sizeX % kBlock) != 0 || (sizeY % kBlock) != 0;
     const size_t blocks = ((sizeX + kBlock - 1) / kBlock) * ((sizeY + kBlock - 1) / kBlock), strips = ((sizeX + kBlock * kStripBlocks - 1) / (kBlock * kStripBlocks)) * ((sizeY + kBlock - 1) / kBlock);
-    // per-block scratch of a launch pair is bounded (1 GiB of records): longer lists go in several launch pairs
-    size_t chunk = (size_t)(1ull << 30) / (blocks * sizeof(limg_hip_block_record));
-    if (chunk * strips > 0x7FFFFFFFull) chunk = 0x7FFFFFFFull / strips; // strip ids are 32 bits
-    if (chunk < 1) chunk = 1;
-    if (TOPT(c, batch_chunk) > 0) chunk = (size_t)TOPT(c, batch_chunk);
+    const size_t chunk = list_chunk(c, blocks, strips); // longer lists go in several launch pairs
     const bool oneByOne = count == 1 || ragged || !full || c->opt.legacy_float_stage != 0 || c->opt.force_split_kernels != 0;
     std::vector<ImageIO> table;
     limg_hip_result r = limg_hip_success;

@@ -1,0 +1,59 @@
+// limg_hip_encode_rules.h -- three rules of the 8x8 encode that the host units and one kernel file state alike, each written ONCE for the host and the device:
+// the bit-crush thresholds of an error factor (encode_params, the merged-block encoder's set_up, k_rate_begin / k_rate_step), the forced shift triple (every
+// parameter block with a `forced` member) and the images of one launch pair of a list (limg_hip_encode3d_batch_device, the batched and the budgeted stream
+// encode).  A host compiler builds it on its own (tests/helpers/encode_rules_check.cpp).  Plain C++: no HIP types, no library.
+#ifndef LIMG_HIP_ENCODE_RULES_H
+#define LIMG_HIP_ENCODE_RULES_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/limg_hip.h" // limg_hip_block_record: what a block of a launch pair costs
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define LIMG_RULES_HD __host__ __device__
+#else
+#define LIMG_RULES_HD
+#endif
+
+namespace limg_hip
+{
+  // thresholds and flags of an error factor, src/limg.cpp:2186-2212 (the merged-block encoder: 2343-2368, the same values)
+  struct Thresholds
+  {
+    uint32_t maxPixel32;     // min(maxPixelBitCrushError, 2^32 - 1)
+    uint32_t blockLimitFull; // min(ceil(maxBlock * 64 / 16), 2^32 - 1): what a full block's error sum is compared with (be * 16 < maxBlock * n)
+    uint64_t maxBlock;       // maxBlockBitCrushError
+    uint32_t crushBits;
+  };
+  LIMG_RULES_HD inline Thresholds thresholds(uint32_t errorFactor)
+  {
+    const uint64_t maxPixel = (uint64_t)0x6 * (errorFactor / 2) * 7, maxBlock = (uint64_t)0x4 * (errorFactor / 2) * 7;
+    const uint64_t lim = (maxBlock * 64ull + 15ull) >> 4;
+    Thresholds t;
+    t.maxPixel32 = maxPixel > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxPixel;
+    t.blockLimitFull = lim > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim;
+    t.maxBlock = maxBlock;
+    t.crushBits = errorFactor != 0 ? 1u : 0u;
+    return t;
+  }
+
+  // limg_hip_options.forced_shift -> the kernels' `forced`: the triple if all three are in 0..8, else {-1, -1, -1} (the shift search runs)
+  LIMG_RULES_HD inline void forced_shifts(const int32_t forced_shift[3], int32_t forced[3])
+  {
+    const bool all = forced_shift[0] >= 0 && forced_shift[0] <= 8 && forced_shift[1] >= 0 && forced_shift[1] <= 8 && forced_shift[2] >= 0 && forced_shift[2] <= 8;
+    for (int i = 0; i < 3; i++) forced[i] = all ? forced_shift[i] : -1;
+  }
+
+  // Images of one shape that go into ONE launch pair: the per-block scratch of a launch pair is bounded (1 GiB of records) and strip ids are 32 bits; at least one.
+  // hook: the test build's batch_chunk, 0 = none.  blocks, strips: of one image, both > 0.
+  LIMG_RULES_HD inline size_t list_chunk(size_t blocks, size_t strips, size_t hook)
+  {
+    if (hook > 0) return hook;
+    size_t chunk = (size_t)(1ull << 30) / (blocks * sizeof(limg_hip_block_record));
+    if (chunk * strips > 0x7FFFFFFFull) chunk = 0x7FFFFFFFull / strips;
+    return chunk < 1 ? 1 : chunk;
+  }
+}
+
+#endif

@@ -10,6 +10,7 @@
 #include "../../include/limg_hip.h"
 #include "limg_hip_blocked_host.h"
 #include "limg_hip_rate_step.h"
+#include "limg_hip_encode_rules.h"
 
 namespace limg_hip
 {

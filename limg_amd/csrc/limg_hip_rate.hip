@@ -20,15 +20,11 @@ namespace limg_hip
 {
   namespace
   {
-    // thresholds and flags of an error factor, as encode_params (limg_hip_encode.hip) states them (src/limg.cpp:2186-2212)
+    // thresholds and flags of an error factor: the rule encode_params (limg_hip_encode.hip) applies on the host (limg_hip_encode_rules.h)
     __device__ __forceinline__ void set_thresholds(RateDevice *d, uint32_t errorFactor)
     {
-      const uint64_t maxPixel = (uint64_t)0x6 * (errorFactor / 2) * 7, maxBlock = (uint64_t)0x4 * (errorFactor / 2) * 7;
-      const uint64_t lim = (maxBlock * 64ull + 15ull) >> 4;
-      d->maxPixel32 = maxPixel > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxPixel;
-      d->blockLimitFull = lim > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim;
-      d->maxBlock = maxBlock;
-      d->crushBits = errorFactor != 0 ? 1u : 0u;
+      const Thresholds t = thresholds(errorFactor);
+      d->maxPixel32 = t.maxPixel32; d->blockLimitFull = t.blockLimitFull; d->maxBlock = t.maxBlock; d->crushBits = t.crushBits;
     }
 
     // in front of a call's first probe: the search's state (or the list's position), the first thresholds, an empty counter

@@ -1,5 +1,5 @@
 // limg_hip_rate_step.h -- the search of the budgeted stream encode (limg_hip_encode_stream_budget*) as ONE function for the host and the device: k_rate_step
-// (limg_hip_rate.hip) calls it between two size probes, the fallback host loop (limg_hip_stream_api.hip) between two stream encodes, and a host compiler builds it on
+// (limg_hip_rate.hip) calls it between two size probes, the fallback host loop (limg_hip_stream_encode_api.hip) between two stream encodes, and a host compiler builds it on
 // its own (tests/helpers/rate_step_check.cpp).  Plain C++: no HIP types, no library.
 //
 // The search runs over h = errorFactor / 2 (the thresholds depend on errorFactor through errorFactor / 2 only) in [hLo, hHi] and asks for size(h), the stream's

@@ -1,0 +1,523 @@
+// limg_hip_stream_encode_api.hip -- the version 1 stream's encode family of the C ABI: limg_hip_encode_stream, limg_hip_encode_stream_batch, limg_hip_stream_sizes,
+// limg_hip_encode_stream_budget and limg_hip_encode_stream_budget_batch, each with its _device form.  The 8x8 encode in compact mode + the packer of
+// limg_hip_stream.hip; the size probe's kernels are limg_hip_rate.hip, the search limg_hip_rate_step.h.  What the ten entries do alike -- a call's shape, the argument
+// checks, a list's staging, the probe's parameters, the searches' enqueue, the results -- is written once, in the anonymous namespace below.  No kernel is defined here.
+#include "limg_hip_context.h"
+
+#include <algorithm>
+#include <vector>
+
+using namespace limg_hip;
+
+namespace
+{
+  // ---- a call's shape: everything the entries derive from (sizeX, sizeY) ----
+  struct StreamShape
+  {
+    size_t sizeX, sizeY, px, planeStride, blocksX, blocksY, blocks, tiles, stripsX, strips, bound;
+    uint64_t fixedBytes; // header + table: a stream is this + 8 x its payload words
+    bool whole;          // whole 8x8 blocks: the strip form of the packer, the batched kernels, the probe
+    StreamShape(size_t x, size_t y)
+      : sizeX(x), sizeY(y), px(x * y), planeStride((px + 255) & ~(size_t)255), blocksX((x + kBlock - 1) / kBlock), blocksY((y + kBlock - 1) / kBlock), blocks(blocksX * blocksY),
+        tiles((blocks + 255) / 256), stripsX((blocksX + kStripBlocks - 1) / kStripBlocks), strips(stripsX * blocksY), bound(limg_hip_stream_bound(x, y)),
+        fixedBytes(sizeof(limg_hip_stream_header) + (uint64_t)blocks * sizeof(limg_hip_stream_block)), whole((x % kBlock) == 0 && (y % kBlock) == 0) {}
+  };
+
+  // lists in one launch pair and the probe kernel: whole blocks, the persistent path's float stage (k_fit_tpb) -- and, the probe, the default search
+  bool batch_applies(const limg_hip_context *c, const StreamShape &sh) { return sh.whole && c->opt.force_split_kernels == 0 && c->opt.legacy_float_stage == 0; }
+  bool rate_probe_applies(const limg_hip_context *c, const StreamShape &sh, int fast) { return batch_applies(c, sh) && fast != 0; }
+
+  // ---- argument checks, in the contract's order (include/limg_hip.h) ----
+  // The single entries.  pointers: the entry's other pointers are all there.  dStream: a device form's stream buffer, which must hold the bound and be 16-byte aligned.
+  limg_hip_result check_single(const void *c, const void *pIn, bool pointers, const StreamShape &sh, const uint8_t *dStream = nullptr, size_t capacity = 0)
+  {
+    if (!c || !pIn || !pointers) return limg_hip_error_ArgumentNull;
+    if (sh.bound == 0) return limg_hip_error_InvalidParameter;
+    if (dStream && capacity < sh.bound) return limg_hip_error_OutOfBounds;
+    if (((uintptr_t)dStream & 15u) != 0) return limg_hip_error_InvalidParameter;
+    return limg_hip_success;
+  }
+  // The list entries; the element checks hold for the `count` elements there are.  deviceStreams: ppStreams are device buffers (16-byte aligned).
+  limg_hip_result check_list(const void *c, bool pointers, size_t count, const uint32_t *const *ppIn, uint8_t *const *ppStreams, const StreamShape &sh, size_t capacityEach,
+                             bool deviceStreams)
+  {
+    if (!c || !ppIn || !ppStreams || !pointers) return limg_hip_error_ArgumentNull;
+    for (size_t i = 0; i < count; i++)
+      if (!ppIn[i] || !ppStreams[i]) return limg_hip_error_ArgumentNull;
+    if (sh.bound == 0) return limg_hip_error_InvalidParameter;
+    if (capacityEach < sh.bound) return limg_hip_error_OutOfBounds;
+    for (size_t i = 0; deviceStreams && i < count; i++)
+      if (((uintptr_t)ppStreams[i] & 15u) != 0) return limg_hip_error_InvalidParameter;
+    return limg_hip_success;
+  }
+
+  // minErrorFactor / maxErrorFactor of the budget entries -> the bounds of h = errorFactor / 2, then the `count` budgets and results (the bound rules hold for an empty list too)
+  limg_hip_result check_budgets(size_t count, const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, const limg_hip_budget_result *pResults, uint32_t &hLo,
+                                uint32_t &hHi)
+  {
+    const uint32_t lo = minErrorFactor ? minErrorFactor : 2u, hi = maxErrorFactor ? maxErrorFactor : 1024u;
+    if ((lo & 1u) || (hi & 1u) || lo < 2u || hi < 2u || lo > hi) return limg_hip_error_InvalidParameter;
+    for (size_t i = 0; i < count; i++)
+      if (pMaxBytes[i] == 0 || pResults[i].struct_size < sizeof(limg_hip_budget_result)) return limg_hip_error_InvalidParameter;
+    hLo = lo / 2u; hHi = hi / 2u;
+    return limg_hip_success;
+  }
+
+  // (the caller's struct_size may be larger than ours: only the members are written)
+  void fill_result(limg_hip_budget_result &res, uint32_t ef, uint32_t probes, uint32_t within, uint64_t bytes) { res.errorFactor = ef; res.probes = probes; res.withinBudget = within; res.bytes = bytes; }
+
+  // `count` sizes the device holds as 64-bit words -> the caller's size_t: ONE download, waits for `s`
+  limg_hip_result download_sizes(const void *dSizes, size_t count, size_t *pBytes, hipStream_t s)
+  {
+    std::vector<unsigned long long> sizes(count);
+    HIP_TRY(hipMemcpyAsync(sizes.data(), dSizes, count * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < count; i++) pBytes[i] = (size_t)sizes[i];
+    return limg_hip_success;
+  }
+
+  // ---- the packers' set-up, single and batched ----
+  uint32_t stream_flags(const limg_hip_context *c, int fast) { return (fast ? 1u : 0u) | (c->opt.dither_pcg ? 2u : 0u); }
+  // the strip form's grid: 16 one-wave workgroups per CU (128 vector registers each: 4 per SIMD), no more than there are strips
+  uint32_t pack_waves(const limg_hip_context *c, size_t strips)
+  {
+    const size_t slots = (size_t)device_cus(c) * 16;
+    return (uint32_t)(strips < slots ? strips : slots);
+  }
+
+  // ---- host forms of the list entries: the images side by side in host.in, the streams at worst-case size (rounded up to 256 bytes) side by side in stream.buf ----
+  struct StagedList { std::vector<const uint32_t *> in; std::vector<uint8_t *> streams; size_t slice; };
+  limg_hip_result stage_list(limg_hip_context *c, const StreamShape &sh, size_t count, const uint32_t *const *ppIn, StagedList &l)
+  {
+    HIP_TRY(hipSetDevice(c->device));
+    l.slice = (sh.bound + 255) & ~(size_t)255;
+    limg_hip_result r;
+    if ((r = c->host.in.ensure(count * sh.px * 4)) != limg_hip_success) return r;
+    if ((r = c->stream.buf.ensure(count * l.slice)) != limg_hip_success) return r;
+    l.in.resize(count); l.streams.resize(count);
+    for (size_t i = 0; i < count; i++)
+    {
+      l.in[i] = (const uint32_t *)c->host.in.p + i * sh.px;
+      l.streams[i] = (uint8_t *)c->stream.buf.p + i * l.slice;
+      HIP_TRY(hipMemcpy((void *)l.in[i], ppIn[i], sh.px * 4, hipMemcpyHostToDevice));
+    }
+    return limg_hip_success;
+  }
+
+  // ---- size probe and budget search (kernels: limg_hip_rate.hip; the search: limg_hip_rate_step.h) ----
+  // The probes of n images of one shape: one state and one counter per image, the probe kernel's parameters.  n == 1: the single-image kernels, n > 1: the _batch ones.
+  struct Probe
+  {
+    size_t n; int channels; bool floatFast; uint64_t fixedBytes;
+    RateDevice *states; unsigned long long *counters;
+    RateProbeParams one; RateProbeBatchParams many;
+    void launch(hipStream_t s) const { if (n == 1) launch_rate_probe(one, channels, floatFast, s); else launch_rate_probe_batch(many, channels, floatFast, s); }
+  };
+
+  // what RateProbeParams and RateProbeBatchParams name alike.  aligned: every image of the launch starts 16-byte aligned
+  template <class P>
+  void fill_probe(P &p, const limg_hip_context *c, const StreamShape &sh, bool aligned)
+  {
+    memset(&p, 0, sizeof(p));
+    p.sizeX = (uint32_t)sh.sizeX; p.sizeY = (uint32_t)sh.sizeY; p.blocksX = (uint32_t)sh.blocksX; p.blocksY = (uint32_t)sh.blocksY; p.stripsX = (uint32_t)sh.stripsX;
+    p.vecIn = (sh.sizeX % 4 == 0) && aligned; // as encode_params: 16-byte loads only if every image allows them
+    p.recordLimit = record_limit(c);
+    forced_shifts(c->opt.forced_shift, p.forced);
+    p.records = (const limg_hip_block_record *)c->enc.records.p; p.invN = (const float *)c->enc.invN.p;
+  }
+
+  // The records of k_fit_tpb in the context's float mode (the `fitOnly` route, which the merged-block encoder's pass 1 also takes), image after image in enc.records
+  // from ONE grid -- encode_params puts a list's image table on the device --, and the probe on them.
+  limg_hip_result probe_setup(limg_hip_context *c, const StreamShape &sh, const uint32_t *const *ppIn, size_t n, int hasAlpha, int poolThreads, hipStream_t s, Probe &pr)
+  {
+    limg_hip_result r;
+    if ((r = c->stream.rateState.ensure(n * sizeof(RateDevice))) != limg_hip_success) return r;
+    if ((r = c->stream.rateCounter.ensure(n * 8)) != limg_hip_success) return r;
+    std::vector<ImageIO> table(n > 1 ? n : 0);
+    bool aligned = true;
+    for (size_t i = 0; i < n; i++) { aligned = aligned && (((uintptr_t)ppIn[i]) & 15u) == 0; if (n > 1) table[i].in = ppIn[i]; }
+    EncodeExtra x;
+    x.fitOnly = true; x.fitFloatMode = true;
+    if (n > 1) { x.batch = table.data(); x.batchCount = n; }
+    if ((r = encode_device(c, ppIn[0], sh.sizeX, sh.sizeY, hasAlpha, nullptr, nullptr, 0, poolThreads, 1, s, x)) != limg_hip_success) return r;
+    pr.n = n; pr.channels = hasAlpha ? 4 : 3; pr.floatFast = c->opt.float_mode == 1; pr.fixedBytes = sh.fixedBytes;
+    pr.states = (RateDevice *)c->stream.rateState.p; pr.counters = (unsigned long long *)c->stream.rateCounter.p;
+    fill_probe(pr.one, c, sh, aligned);
+    pr.one.io.in = ppIn[0]; pr.one.state = pr.states; pr.one.counter = pr.counters;
+    fill_probe(pr.many, c, sh, aligned);
+    pr.many.batch = (const ImageIO *)c->enc.batchTable.p; pr.many.nImages = (uint32_t)n; pr.many.imageStrips = (uint32_t)sh.strips;
+    pr.many.states = pr.states; pr.many.counters = pr.counters;
+    return limg_hip_success;
+  }
+
+  // The searches of n images over [hLo, hHi], image i's for budgets[i]: begin, then every launch any of them can need, enqueued at once -- probes behind the end of
+  // an image's search return at once --, ONE download of the states and ONE wait.  hStates: n, host.
+  limg_hip_result run_searches(limg_hip_context *c, const StreamShape &sh, const uint32_t *const *ppIn, const size_t *budgets, size_t n, uint32_t hLo, uint32_t hHi,
+                               int hasAlpha, int poolThreads, hipStream_t s, RateDevice *hStates)
+  {
+    Probe pr;
+    const limg_hip_result r = probe_setup(c, sh, ppIn, n, hasAlpha, poolThreads, s, pr);
+    if (r != limg_hip_success) return r;
+    if (n == 1) launch_rate_begin(pr.states, pr.counters, rate_begin(hLo, hHi, budgets[0]), 2u * hHi, s);
+    else launch_rate_begin_batch(pr.states, pr.counters, budgets, n, hLo, hHi, s);
+    for (uint32_t i = 0, probes = rate_max_probes(hLo, hHi); i < probes; i++)
+    {
+      pr.launch(s);
+      if (n == 1) launch_rate_step(pr.states, pr.counters, pr.fixedBytes, nullptr, nullptr, 0, s);
+      else launch_rate_step_batch(pr.states, pr.counters, (uint32_t)n, pr.fixedBytes, s);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hStates, pr.states, n * sizeof(RateDevice), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; i++)
+      if (!hStates[i].search.done) return limg_hip_error_Generic;
+    return limg_hip_success;
+  }
+}
+
+extern "C"
+{
+  limg_hip_result limg_hip_encode_stream_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                                size_t *pBytes, uint32_t errorFactor, int poolThreads, int fastBitCrushing, void *stream)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    limg_hip_result r;
+    if ((r = check_single(c, pIn, pStream != nullptr, sh, pStream, capacity)) != limg_hip_success) return r;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((r = c->stream.fac.ensure(sh.planeStride * 3)) != limg_hip_success) return r;
+    // strip form of the packer (images of whole blocks): the encode kernel leaves one payload-word count per work strip (limg_hip_stream.hip)
+    const bool stripForm = sh.whole && c->opt.force_split_kernels == 0;
+    if ((r = c->stream.tiles.ensure(sh.tiles * 4)) != limg_hip_success) return r;
+    if (stripForm && (r = c->stream.units.ensure(sh.strips * 4)) != limg_hip_success) return r;
+    if ((r = c->enc.records.ensure(sh.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+    if ((r = c->enc.shifts.ensure(sh.blocks * 4)) != limg_hip_success) return r;
+    limg_hip_encode3d_info info;
+    memset(&info, 0, sizeof(info));
+    info.pFactorsA = (uint8_t *)c->stream.fac.p; info.pFactorsB = info.pFactorsA + sh.planeStride; info.pFactorsC = info.pFactorsB + sh.planeStride;
+    limg_hip_compact_out comp = { (limg_hip_block_record *)c->enc.records.p, (uint32_t *)c->enc.shifts.p };
+    EncodeExtra xs;
+    xs.streamRaw = true; xs.stripWords = stripForm ? (uint32_t *)c->stream.units.p : nullptr;
+    if ((r = encode_device(c, pIn, sizeX, sizeY, hasAlpha, &info, &comp, errorFactor, poolThreads, fastBitCrushing, s, xs)) != limg_hip_success) return r;
+
+    StreamParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.sizeX = (uint32_t)sizeX; sp.sizeY = (uint32_t)sizeY; sp.blocksX = (uint32_t)sh.blocksX; sp.blocksY = (uint32_t)sh.blocksY;
+    sp.nBlocks = (uint32_t)sh.blocks; sp.nTiles = (uint32_t)sh.tiles; sp.channels = hasAlpha ? 4 : 3; sp.errorFactor = errorFactor;
+    sp.flags = stream_flags(c, fastBitCrushing);
+    sp.fac[0] = info.pFactorsA; sp.fac[1] = info.pFactorsB; sp.fac[2] = info.pFactorsC;
+    sp.records = comp.pRecords; sp.shifts = comp.pShifts;
+    sp.stream = pStream; sp.tileBase = (uint32_t *)c->stream.tiles.p;
+    if (stripForm)
+    {
+      sp.stripWords = (uint32_t *)c->stream.units.p;
+      sp.stripsX = (uint32_t)sh.stripsX; sp.nStrips = (uint32_t)sh.strips;
+      sp.nWaves = pack_waves(c, sh.strips);
+    }
+    mark(c, s);
+    launch_stream_pack(sp, s);
+    mark(c, s); mark(c, s); mark(c, s);
+    HIP_TRY(hipGetLastError());
+    return pBytes ? stream_total_bytes(pStream, s, pBytes) : limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_encode_stream(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity, size_t *pBytes,
+                                         uint32_t errorFactor, int poolThreads, int fastBitCrushing)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    const limg_hip_result ok = check_single(c, pIn, pStream && pBytes, sh);
+    if (ok != limg_hip_success) return ok;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    return encode_stream_host(c, pIn, sizeX, sizeY, pStream, capacity, pBytes, sh.bound, [&](const uint32_t *dIn, uint8_t *dStream, size_t bound, size_t *bytes) {
+      return limg_hip_encode_stream_device(c, dIn, sizeX, sizeY, hasAlpha, dStream, bound, bytes, errorFactor, poolThreads, fastBitCrushing, nullptr);
+    });
+  }
+
+  // ---- size probe and budget search (contract: include/limg_hip.h) ----
+  limg_hip_result limg_hip_stream_sizes_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const uint32_t *pErrorFactors, size_t count,
+                                               size_t *pBytes, int poolThreads, int fastBitCrushing, void *stream)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    limg_hip_result r;
+    if ((r = check_single(c, pIn, pErrorFactors && pBytes, sh)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!rate_probe_applies(c, sh, fastBitCrushing))
+    { // one ordinary stream encode per entry, into context staging
+      if ((r = c->stream.buf.ensure(sh.bound)) != limg_hip_success) return r;
+      for (size_t i = 0; i < count; i++)
+        if ((r = limg_hip_encode_stream_device(c, pIn, sizeX, sizeY, hasAlpha, (uint8_t *)c->stream.buf.p, sh.bound, &pBytes[i], pErrorFactors[i], poolThreads, fastBitCrushing,
+                                               stream)) != limg_hip_success)
+          return r;
+      return limg_hip_success;
+    }
+    if ((r = c->stream.rateList.ensure(count * 12)) != limg_hip_success) return r;
+    Probe pr;
+    if ((r = probe_setup(c, sh, &pIn, 1, hasAlpha, poolThreads, s, pr)) != limg_hip_success) return r;
+    unsigned long long *dBytes = (unsigned long long *)c->stream.rateList.p;
+    uint32_t *dList = (uint32_t *)(dBytes + count);
+    std::vector<uint32_t> list(pErrorFactors, pErrorFactors + count); // (the caller's array may be pageable and may die when the call returns)
+    HIP_TRY(hipMemcpyAsync(dList, list.data(), count * 4, hipMemcpyHostToDevice, s));
+    launch_rate_begin(pr.states, pr.counters, rate_begin(0, 0, 0), list[0], s);
+    for (size_t i = 0; i < count; i++)
+    {
+      pr.launch(s);
+      launch_rate_step(pr.states, pr.counters, pr.fixedBytes, dList, dBytes, (uint32_t)count, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return download_sizes(dBytes, count, pBytes, s); // (its wait also: `list` is no longer read)
+  }
+
+  limg_hip_result limg_hip_stream_sizes(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const uint32_t *pErrorFactors, size_t count,
+                                        size_t *pBytes, int poolThreads, int fastBitCrushing)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    limg_hip_result r;
+    if ((r = check_single(c, pIn, pErrorFactors && pBytes, sh)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((r = c->host.in.ensure(sh.px * 4)) != limg_hip_success) return r;
+    HIP_TRY(hipMemcpy(c->host.in.p, pIn, sh.px * 4, hipMemcpyHostToDevice));
+    r = limg_hip_stream_sizes_device(c, (const uint32_t *)c->host.in.p, sizeX, sizeY, hasAlpha, pErrorFactors, count, pBytes, poolThreads, fastBitCrushing, nullptr);
+    return r != limg_hip_success ? r : limg_hip_check_device_status(c);
+  }
+
+  limg_hip_result limg_hip_encode_stream_budget_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                                       size_t maxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                       limg_hip_budget_result *pResult, void *stream)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = check_single(c, pIn, pStream && pResult, sh, pStream, capacity)) != limg_hip_success) return r;
+    if ((r = check_budgets(1, &maxBytes, minErrorFactor, maxErrorFactor, pResult, hLo, hHi)) != limg_hip_success) return r;
+    HIP_TRY(hipSetDevice(c->device));
+    RateDevice search;
+    RateState &st = search.search = rate_begin(hLo, hHi, maxBytes);
+    size_t bytes = 0;
+    bool written = false; // pStream holds the stream at the result
+    if (rate_probe_applies(c, sh, fastBitCrushing) &&
+        (r = run_searches(c, sh, &pIn, &maxBytes, 1, hLo, hHi, hasAlpha, poolThreads, (hipStream_t)stream, &search)) != limg_hip_success)
+      return r;
+    while (!st.done)
+    { // no probe kernel (behind one the search is over): the same search, a whole stream encode per size
+      const uint32_t h = st.next;
+      if ((r = limg_hip_encode_stream_device(c, pIn, sizeX, sizeY, hasAlpha, pStream, capacity, &bytes, 2u * h, poolThreads, fastBitCrushing, stream)) != limg_hip_success) return r;
+      rate_step(st, bytes);
+      written = st.done && st.next == h;
+    }
+    // bytes: the final encode's, from its header
+    if (!written && (r = limg_hip_encode_stream_device(c, pIn, sizeX, sizeY, hasAlpha, pStream, capacity, &bytes, 2u * st.next, poolThreads, fastBitCrushing, stream)) != limg_hip_success)
+      return r;
+    fill_result(*pResult, 2u * st.next, st.probes, st.within, bytes);
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_encode_stream_budget(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                                size_t maxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                limg_hip_budget_result *pResult)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    uint32_t hLo, hHi;
+    limg_hip_result ok;
+    if ((ok = check_single(c, pIn, pStream && pResult, sh)) != limg_hip_success) return ok;
+    if ((ok = check_budgets(1, &maxBytes, minErrorFactor, maxErrorFactor, pResult, hLo, hHi)) != limg_hip_success) return ok;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    size_t bytes = 0;
+    return encode_stream_host(c, pIn, sizeX, sizeY, pStream, capacity, &bytes, sh.bound, [&](const uint32_t *dIn, uint8_t *dStream, size_t bound, size_t *n) {
+      const limg_hip_result r = limg_hip_encode_stream_budget_device(c, dIn, sizeX, sizeY, hasAlpha, dStream, bound, maxBytes, minErrorFactor, maxErrorFactor, poolThreads,
+                                                                     fastBitCrushing, pResult, nullptr);
+      if (r == limg_hip_success) *n = (size_t)pResult->bytes;
+      return r;
+    });
+  }
+
+  // ---- batched stream encode: a list of same-shape images, stream i = limg_hip_encode_stream_device of image i ----
+  // Lists of whole-block images go chunk by chunk (the plane batch's rule) through ONE compact-mode batched encode -- records, shift words and the strips' payload
+  // words in the context's raster arrays, image after image; the factor planes in per-image slices of stream.fac -- and one scan + one pack launch over the chunk.
+  limg_hip_result limg_hip_encode_stream_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                      uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, int poolThreads,
+                                                      int fastBitCrushing, void *stream)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    limg_hip_result r;
+    if ((r = check_list(c, true, count, ppIn, ppStreams, sh, capacityEach, true)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t chunk = list_chunk(c, sh.blocks, sh.strips);
+    const bool oneByOne = count == 1 || !batch_applies(c, sh);
+    const size_t most = oneByOne ? 1 : (count < chunk ? count : chunk); // images of the largest chunk
+    if ((r = c->stream.table.ensure(count * sizeof(StreamImage))) != limg_hip_success) return r;
+    if (most > 1)
+    { // everything a chunk needs, before the first launch: nothing is grown (and so freed) between the chunks of a list
+      if ((r = c->stream.fac.ensure(most * sh.planeStride * 3)) != limg_hip_success) return r;
+      if ((r = c->stream.units.ensure(most * sh.strips * 4)) != limg_hip_success) return r;
+      if ((r = c->enc.records.ensure(most * sh.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+      if ((r = c->enc.shifts.ensure(most * sh.blocks * 4)) != limg_hip_success) return r;
+    }
+    std::vector<StreamImage> images(count);
+    for (size_t i = 0; i < count; i++) images[i].stream = ppStreams[i];
+    std::vector<ImageIO> table;
+    for (size_t i0 = 0; i0 < count && r == limg_hip_success;)
+    {
+      const size_t n = oneByOne ? 1 : (count - i0 < chunk ? count - i0 : chunk);
+      c->stats.accumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, as the plane batch
+      if (n == 1)
+      { // the single call (images with partial edge blocks, the split path, the float stage inside the encode kernel, a list or a last chunk of one image)
+        r = limg_hip_encode_stream_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, ppStreams[i0], capacityEach, nullptr, errorFactor, poolThreads, fastBitCrushing, stream);
+        if (r == limg_hip_success && pBytes && !oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], 1, s); // (for the sizes below)
+      }
+      else
+      {
+        table.assign(n, ImageIO{});
+        for (size_t i = 0; i < n; i++)
+        {
+          uint8_t *fac = (uint8_t *)c->stream.fac.p + i * 3 * sh.planeStride; // 256-byte aligned slices
+          table[i].in = ppIn[i0 + i];
+          table[i].info.pFactorsA = fac; table[i].info.pFactorsB = fac + sh.planeStride; table[i].info.pFactorsC = fac + 2 * sh.planeStride;
+          images[i0 + i].fac[0] = fac; images[i0 + i].fac[1] = fac + sh.planeStride; images[i0 + i].fac[2] = fac + 2 * sh.planeStride;
+        }
+        limg_hip_compact_out comp = { (limg_hip_block_record *)c->enc.records.p, (uint32_t *)c->enc.shifts.p };
+        EncodeExtra x;
+        x.batch = table.data(); x.batchCount = n;
+        x.streamRaw = true; x.stripWords = (uint32_t *)c->stream.units.p;
+        if ((r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, &table[0].info, &comp, errorFactor, poolThreads, fastBitCrushing, s, x)) != limg_hip_success) break;
+        launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], n, s);
+        StreamBatchParams b;
+        memset(&b, 0, sizeof(b));
+        b.sizeX = (uint32_t)sizeX; b.sizeY = (uint32_t)sizeY; b.blocksX = (uint32_t)sh.blocksX; b.blocksY = (uint32_t)sh.blocksY; b.nBlocks = (uint32_t)sh.blocks;
+        b.channels = hasAlpha ? 4 : 3; b.errorFactor = errorFactor; b.flags = stream_flags(c, fastBitCrushing);
+        b.stripsX = (uint32_t)sh.stripsX; b.imageStrips = (uint32_t)sh.strips; b.nImages = (uint32_t)n; b.nStrips = (uint32_t)(n * sh.strips);
+        b.nWaves = pack_waves(c, n * sh.strips); // as the single call -- for the whole chunk
+        b.images = (const StreamImage *)c->stream.table.p + i0;
+        b.records = comp.pRecords; b.shifts = comp.pShifts; b.stripWords = (uint32_t *)c->stream.units.p;
+        mark(c, s);
+        launch_stream_pack_batch(b, s);
+        mark(c, s); mark(c, s); mark(c, s);
+        const hipError_t launched = hipGetLastError();
+        if (launched != hipSuccess) { c->stats.accumulate = false; HIP_TRY(launched); }
+      }
+      i0 += n;
+    }
+    c->stats.accumulate = false;
+    if (r != limg_hip_success || !pBytes) return r;
+    // the sizes: gathered from the headers on the device
+    if ((r = c->stream.sizes.ensure(count * 8)) != limg_hip_success) return r;
+    if (oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p, images.data(), count, s);
+    launch_stream_gather_bytes((const StreamImage *)c->stream.table.p, count, (unsigned long long *)c->stream.sizes.p, s);
+    HIP_TRY(hipGetLastError());
+    return download_sizes(c->stream.sizes.p, count, pBytes, s);
+  }
+
+  limg_hip_result limg_hip_encode_stream_batch(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                               uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, int poolThreads, int fastBitCrushing)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    limg_hip_result r;
+    if ((r = check_list(c, pBytes != nullptr, count, ppIn, ppStreams, sh, capacityEach, false)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    StagedList l;
+    if ((r = stage_list(c, sh, count, ppIn, l)) != limg_hip_success) return r;
+    if ((r = limg_hip_encode_stream_batch_device(c, count, l.in.data(), sizeX, sizeY, hasAlpha, l.streams.data(), l.slice, pBytes, errorFactor, poolThreads, fastBitCrushing,
+                                                 nullptr)) != limg_hip_success)
+      return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], l.streams[i], pBytes[i], hipMemcpyDeviceToHost)); // totalBytes of each, not the capacity
+    return limg_hip_success;
+  }
+
+  // ---- budgeted stream encode of a list: result i = limg_hip_encode_stream_budget_device of image i with pMaxBytes[i] (contract: include/limg_hip.h) ----
+  // Chunk by chunk (the plane batch's rule): the records of the chunk from ONE k_fit_tpb grid, one search state and one counter per image, the whole chunk's searches
+  // as 1 + 2 x rate_max_probes launches and ONE wait; then one stream encode per distinct error factor the searches chose.
+  limg_hip_result limg_hip_encode_stream_budget_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                             uint8_t *const *ppStreams, size_t capacityEach, const size_t *pMaxBytes, uint32_t minErrorFactor,
+                                                             uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults, void *stream)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = check_list(c, pMaxBytes && pResults, count, ppIn, ppStreams, sh, capacityEach, true)) != limg_hip_success) return r;
+    if ((r = check_budgets(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    auto single = [&](size_t i) {
+      return limg_hip_encode_stream_budget_device(c, ppIn[i], sizeX, sizeY, hasAlpha, ppStreams[i], capacityEach, pMaxBytes[i], minErrorFactor, maxErrorFactor, poolThreads,
+                                                  fastBitCrushing, &pResults[i], stream);
+    };
+    // no probe kernel (or nothing to share): the loop of single calls, which a chunk (or a last chunk) of one image takes too
+    const size_t chunk = count == 1 || !rate_probe_applies(c, sh, fastBitCrushing) ? 1 : list_chunk(c, sh.blocks, sh.strips);
+    std::vector<RateDevice> states;
+    std::vector<uint32_t> order; // the chunk's images sorted by the h their searches chose
+    std::vector<const uint32_t *> groupIn;
+    std::vector<uint8_t *> groupOut;
+    for (size_t i0 = 0; i0 < count;)
+    {
+      const size_t n = count - i0 < chunk ? count - i0 : chunk;
+      if (n == 1)
+      {
+        if ((r = single(i0++)) != limg_hip_success) return r;
+        continue;
+      }
+      // 1. + 2. the chunk's records and its searches
+      states.resize(n);
+      if ((r = run_searches(c, sh, ppIn + i0, pMaxBytes + i0, n, hLo, hHi, hasAlpha, poolThreads, (hipStream_t)stream, states.data())) != limg_hip_success) return r;
+      // 3. the final encodes: the thresholds are kernel arguments of the persistent kernel, so one (batched) stream encode per distinct h
+      order.resize(n);
+      for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return states[a].search.next < states[b].search.next; });
+      for (size_t g0 = 0; g0 < n;)
+      {
+        const uint32_t h = states[order[g0]].search.next;
+        size_t g1 = g0;
+        groupIn.clear(); groupOut.clear();
+        for (; g1 < n && states[order[g1]].search.next == h; g1++) { groupIn.push_back(ppIn[i0 + order[g1]]); groupOut.push_back(ppStreams[i0 + order[g1]]); }
+        if (g1 - g0 == 1) r = limg_hip_encode_stream_device(c, groupIn[0], sizeX, sizeY, hasAlpha, groupOut[0], capacityEach, nullptr, 2u * h, poolThreads, fastBitCrushing, stream);
+        else r = limg_hip_encode_stream_batch_device(c, g1 - g0, groupIn.data(), sizeX, sizeY, hasAlpha, groupOut.data(), capacityEach, nullptr, 2u * h, poolThreads,
+                                                     fastBitCrushing, stream);
+        if (r != limg_hip_success) return r;
+        g0 = g1;
+      }
+      for (size_t i = 0; i < n; i++) // bytes: what the probe measured at the result -- the packer's totalBytes
+        fill_result(pResults[i0 + i], 2u * states[i].search.next, states[i].search.probes, states[i].search.within, states[i].search.bestBytes);
+      i0 += n;
+    }
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_encode_stream_budget_batch(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                      uint8_t *const *ppStreams, size_t capacityEach, const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor,
+                                                      int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = check_list(c, pMaxBytes && pResults, count, ppIn, ppStreams, sh, SIZE_MAX, false)) != limg_hip_success) return r; // (capacityEach: the rule below)
+    if ((r = check_budgets(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    StagedList l;
+    if ((r = stage_list(c, sh, count, ppIn, l)) != limg_hip_success) return r;
+    std::vector<limg_hip_budget_result> results(count);
+    for (size_t i = 0; i < count; i++) { memset(&results[i], 0, sizeof(results[i])); results[i].struct_size = sizeof(limg_hip_budget_result); }
+    if ((r = limg_hip_encode_stream_budget_batch_device(c, count, l.in.data(), sizeX, sizeY, hasAlpha, l.streams.data(), l.slice, pMaxBytes, minErrorFactor, maxErrorFactor,
+                                                        poolThreads, fastBitCrushing, results.data(), nullptr)) != limg_hip_success)
+      return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    bool fits = true;
+    for (size_t i = 0; i < count; i++)
+    {
+      fill_result(pResults[i], results[i].errorFactor, results[i].probes, results[i].withinBudget, results[i].bytes);
+      fits = fits && results[i].bytes <= capacityEach;
+    }
+    if (!fits) return limg_hip_error_OutOfBounds; // the single host call's rule: the results say what each stream takes, no stream is written
+    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], l.streams[i], (size_t)results[i].bytes, hipMemcpyDeviceToHost));
+    return limg_hip_success;
+  }
+}

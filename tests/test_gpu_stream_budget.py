@@ -200,6 +200,32 @@ def test_device_forms_and_back_to_back(gpu, oracle, images):
     assert n == want_b.size and np.array_equal(plain[:n].cpu().numpy(), want_b)
 
 
+def test_probe_on_a_misaligned_image(gpu, images):
+    """The probe's dword-load path.  Its domain is whole blocks, so the width is always a multiple of 4 and only an image that starts 4-byte but not 16-byte aligned
+    takes it: the pixels of the 264 x 24 image at element 1 of a tensor one element longer.  Sizes, the search's result and the stream must be exactly those of the
+    aligned tensor, which the tests above tie to the oracle."""
+    import torch
+    img = images["264x24"]
+    aligned = torch.from_numpy(img.view(np.int32)).cuda()
+    moved = torch.empty(img.size + 1, dtype=torch.int32, device="cuda")[1:].view(24, 264)
+    moved.copy_(aligned)
+    assert aligned.data_ptr() % 16 == 0 and moved.data_ptr() % 16 == 4 and moved.is_contiguous()
+    efs = [2, 100, 1024]
+    want = gpu.stream_sizes_device(aligned, True, efs)
+    got = gpu.stream_sizes_device(moved, True, efs)
+    print(want, got)
+    assert got == want and want[2] < want[0]
+    budget = (want[0] + want[2]) // 2
+    oa, ra = gpu.encode_stream_budget_device(aligned, True, budget)
+    ob, rb = gpu.encode_stream_budget_device(moved, True, budget)
+    torch.cuda.synchronize()
+    gpu.check()
+    ta, tb = ((r.errorFactor, r.withinBudget, r.probes, r.bytes) for r in (ra, rb))
+    print(budget, ta, tb)
+    assert tb == ta and ra.withinBudget == 1 and ra.probes > 2 and 2 < ra.errorFactor <= 1024, "a bisected budget"
+    assert torch.equal(ob[:rb.bytes], oa[:ra.bytes])
+
+
 def test_errors(gpu):
     """the contract's refusals, in its order, each before anything touches the device: the output buffer keeps its pattern, the result its values"""
     import torch

@@ -233,6 +233,25 @@ def test_device_form_back_to_back(gpu, oracle, five):
         assert np.array_equal(plain[i][:n[i]].cpu().numpy(), gpu.encode_stream(img, True, error_factor=100)), i
 
 
+def test_one_misaligned_image_in_the_list(gpu, five):
+    """The probe's dword-load path.  The probe's domain is whole blocks, so the width is always a multiple of 4 and only an image that starts 4-byte but not 16-byte
+    aligned takes it -- and with it every image of its chunk.  Three images, the middle one at element 1 of a tensor one element longer: results and streams must be
+    exactly those of the call on the aligned tensors, which the tests above tie to the oracle."""
+    import torch
+    aligned = [torch.from_numpy(i.view(np.int32)).cuda() for i in five[0][:3]]
+    moved = torch.empty(W * H + 1, dtype=torch.int32, device="cuda")[1:].view(H, W)
+    moved.copy_(aligned[1])
+    assert all(t.data_ptr() % 16 == 0 for t in aligned) and moved.data_ptr() % 16 == 4 and moved.is_contiguous()
+    oa, ra = gpu.encode_stream_budget_batch_device(aligned, True, 11500, 2, 128)
+    ob, rb = gpu.encode_stream_budget_batch_device([aligned[0], moved, aligned[2]], True, 11500, 2, 128)
+    torch.cuda.synchronize()
+    gpu.check()
+    print([_tuple(r) for r in ra], [_tuple(r) for r in rb])
+    assert [_tuple(r) for r in rb] == [_tuple(r) for r in ra] and {_outcome(r, 2) for r in ra} == {"refused", "bisected"}
+    for i in range(3):
+        assert torch.equal(ob[i][:rb[i].bytes], oa[i][:ra[i].bytes]), i
+
+
 def _results(n, struct_size=None):
     rs = (limg_amd.BudgetResult * n)()
     for r in rs:
