@@ -338,6 +338,30 @@ limg_hip_result limg_hip_encode_stream_batch(limg_hip_context *pCtx, size_t coun
                                              uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes,
                                              uint32_t errorFactor, int poolThreads, int fastBitCrushing);
 
+/* ---- ... each image at its own error factor ---------------------------------------------------------------------------------------------
+ * "This list, each image at its own quality": the batched stream encode above with pErrorFactors[i] (HOST array of `count` entries in both forms; may be freed when the
+ * call returns) in the place of errorFactor.
+ * Result: stream i is byte for byte what limg_hip_encode_stream_device writes for image i at errorFactor = pErrorFactors[i] with the same arguments and options.  Any
+ * value is allowed, 0 and odd ones included; stream i's header carries pErrorFactors[i] as given, as the single call's does.
+ * Errors: those of limg_hip_encode_stream_batch_device, in its order, pErrorFactors counted among the pointers; then count == 0: limg_hip_success with nothing done.  A
+ * refused call writes nothing.  pBytes, options (forced_shift, dither_pcg, float_mode, collect_stats, batch_sub_images), chunks and ordering: as that entry.
+ * Cost: the shared-factor call's launches -- one float-stage grid, the persistent launch (k_encode_list_rated in the place of k_encode_persistent: the same loop, which
+ * fetches its image's bit-crush thresholds from a device table once per work strip, with scalar loads, where the other reads kernel arguments) or its pipeline of
+ * sub-batches, one scan, one pack -- plus one small launch per 64 images of a chunk that writes the threshold table from the factors, which travel as its kernel
+ * arguments.  That is one launch pair per chunk however many distinct factors the list holds, where the calls above need one encode per distinct factor.
+ * Fallback, the same bytes: images with partial edge blocks, force_split_kernels, legacy_float_stage, fastBitCrushing == 0 (the accurate search has no such kernel) and
+ * count == 1 go through the entries above, the images grouped by error factor -- one limg_hip_encode_stream_batch_device per factor that two or more images share, one
+ * limg_hip_encode_stream_device per factor of one image; a last chunk of one image takes the single call.
+ * Context memory: what limg_hip_encode_stream_batch_device holds, and 32 bytes per image of the longest chunk for the threshold table. */
+/* DEVICE pointers, asynchronous on `stream`.  ppIn / ppStreams / pErrorFactors are HOST arrays of `count` entries and may be freed when the call returns. */
+limg_hip_result limg_hip_encode_stream_batch_ef_device(limg_hip_context *pCtx, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                       uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes /* host, count entries, or NULL */,
+                                                       const uint32_t *pErrorFactors /* host, count */, int poolThreads, int fastBitCrushing, void *stream);
+/* HOST pointers, blocking, under the context's mutex.  pBytes required.  As limg_hip_encode_stream_batch. */
+limg_hip_result limg_hip_encode_stream_batch_ef(limg_hip_context *pCtx, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, const uint32_t *pErrorFactors, int poolThreads,
+                                                int fastBitCrushing);
+
 /* ---- stream encode to a byte budget: size probe and error-factor search (version 1 streams) -----------------------------------------
  * errorFactor is the stream's only rate knob.  A stream is 64 + 56 blocks + 8 x (payload words) bytes, and the payload words follow from the blocks' records -- which do
  * not depend on errorFactor -- and their shift triples, which depend on it through errorFactor / 2 only.  So the size at an error factor is the float stage once and,
@@ -407,19 +431,21 @@ limg_hip_result limg_hip_encode_stream_budget(limg_hip_context *pCtx, const uint
  * grid over all its images (records in the context's float mode), one k_rate_begin_batch per 64 images, then 2 + ceil(log2(hHi - hLo)) pairs of k_rate_probe_batch
  * (one workgroup per image and work strip; the workgroups of an image whose search is over return at their first load) and k_rate_step_batch, ONE copy of the chunk's
  * states and ONE wait -- whatever the chunk's length: for 64 images over the default bounds 2 table launches, the float stage, one begin and 22 probe / step launches
- * with one wait, where 64 single calls are 64 x 24 launches and 64 waits.  Then the chunk's images are grouped by the error factor their searches chose: a group of two or more is one limg_hip_encode_stream_batch_device, a group of
- * one is one limg_hip_encode_stream_device.  pResults[i].bytes is the size the probe measured at the result, which is the stream's totalBytes: no wait follows the
+ * with one wait, where 64 single calls are 64 x 24 launches and 64 waits.  Then the chunk is encoded ONCE, every image at the error factor its search chose: one
+ * limg_hip_encode_stream_batch_ef_device -- a threshold-table launch, one launch pair, scan and pack, whatever the searches chose -- or, where all chose the same value,
+ * one limg_hip_encode_stream_batch_device.  pResults[i].bytes is the size the probe measured at the result, which is the stream's totalBytes: no wait follows the
  * encodes.  A chunk of one image takes the single call.
  * Synchronisation: the device form SYNCHRONISES `stream` once per chunk, for that chunk's search states; it cannot be captured into a graph.  The streams themselves
  * are complete in stream order behind the call.
  * Fallback: where the single call has no probe kernel (partial edge blocks, force_split_kernels, legacy_float_stage, fastBitCrushing == 0) and for count == 1 the call
  * is the loop of single budget calls: the same results by construction.
- * Options: as the single call.  limg_hip_last_stats after these entries is that of the last group encoded.
+ * Options: as the single call.  limg_hip_last_stats after these entries is that of the last encode issued: the last chunk, all its images together.
  * Context memory, besides what limg_hip_encode_stream_batch_device holds for the longest chunk: 72 bytes of state (sizeof RateDevice: the 48-byte search state, the list
  * position and the thresholds) + 8 bytes of counter = 80 bytes per image of the longest chunk (streamRateState, streamRateCounter); the probes read the images through
- * the batched encode's own table (96 bytes per image of a chunk, no second table).  limg_hip_context_device_bytes reports all of it.
- * Out of scope: per-image error factors inside ONE persistent launch (the thresholds are kernel arguments of the encode kernel, so the final encodes batch only over
- * images that chose the same error factor); a batched limg_hip_stream_sizes; lists of mixed shapes; version 2 streams; the CLI, which encodes one file. */
+ * the batched encode's own table (96 bytes per image of a chunk, no second table), and the final encode's threshold table (32 bytes per image) lies in the chunk's
+ * search states, which are on the host by then: no memory of its own.  limg_hip_context_device_bytes reports all of it.
+ * Out of scope: a batched limg_hip_stream_sizes; lists of mixed shapes; version 2 streams; the accurate search with per-image error factors in one launch (it takes
+ * the grouped fallback of limg_hip_encode_stream_batch_ef_device); the CLI, which encodes one file. */
 /* DEVICE pointers; ppIn / ppStreams are HOST arrays of `count` device pointers (streams 16-byte aligned, capacityEach >= limg_hip_stream_bound) and, as pMaxBytes, may
  * be freed when the call returns.  Waits for `stream`. */
 limg_hip_result limg_hip_encode_stream_budget_batch_device(limg_hip_context *pCtx, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,

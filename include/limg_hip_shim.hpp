@@ -210,6 +210,18 @@ inline limg_result limg_encode_batch(const uint32_t *const *ppIn, const size_t c
                                                    limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0);
 }
 
+// limg_encode_batch with one error factor per image (limg_hip.h "each image at its own error factor"): pOutSizes[i] bytes at ppOut[i] are what limg_encode writes
+// for ppIn[i] at pErrorFactors[i]
+inline limg_result limg_encode_batch_ef(const uint32_t *const *ppIn, const size_t count, const size_t sizeX, const size_t sizeY, const bool hasAlpha, uint8_t *const *ppOut,
+                                        const size_t outCapacityEach, size_t *pOutSizes, const uint32_t *pErrorFactors, limg_thread_pool *pThreadPool = nullptr,
+                                        const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  return (limg_result)limg_hip_encode_stream_batch_ef(c, count, ppIn, sizeX, sizeY, hasAlpha ? 1 : 0, ppOut, outCapacityEach, pOutSizes, pErrorFactors,
+                                                      limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0);
+}
+
 // limg_encode_batch to byte budgets (limg_hip.h "budgeted stream encode of a list"): image i gets the stream limg_encode_budget writes for it with pMaxBytes[i], every
 // image on a search of its own over the shared [minErrorFactor, maxErrorFactor].  pOutSizes[i], pErrorFactors[i]: what was chosen and what it takes; pWithinBudget[i],
 // pProbes[i] (arrays of `count`, may be NULL) as limg_encode_budget's.  outCapacityEach below some pOutSizes[i]: limg_error_OutOfBounds with all sizes filled and

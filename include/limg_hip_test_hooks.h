@@ -31,7 +31,9 @@ typedef struct limg_hip_test_options
   int32_t fail_chain_phase1;  /* non-0: limg_hip_encode3d_single_chain_device behaves as if this rank's E step had failed (abort rule in limg_hip.h) */
   int32_t blocked_no_bound;   /* non-0: the merged-block encoder's similarity kernel evaluates the 27-colour loop for every pair its early exits leave open, without
                                  the certain-match / certain-failure bounds in front of it (limg_hip_blocked.hip).  Same bits either way */
-  int32_t lookback_spins;     /* N > 0: bound of one look-back wait of the persistent kernel, in polls (the product's bound is 2^22, seconds) */
+  int32_t lookback_spins;     /* N > 0: bound of one look-back wait of the persistent kernel, in polls (the product's bound is 2^22, seconds).  This hook,
+                                 base_error_strip and skip_publish_strip reach k_encode_persistent only: k_encode_list_rated (limg_hip_encode_stream_batch_ef*, and
+                                 through it the budgeted list's final encodes) has the same kernel arguments in both builds and always runs with the product's values */
   int32_t base_error_strip;   /* N > 0: work strip N - 1 of the persistent kernel dithers from a chain position that is off by one dither call (every other strip is
                                  unaffected): the smallest possible look-back error, which the full-size reference hashes must catch (tests/test_gpu_fullsize.py) */
   int32_t skip_publish_strip; /* N > 0: work strip N - 1 of the persistent kernel never publishes its dither-call count, i.e. the look-back of every later strip of its

@@ -27,7 +27,7 @@ ABI_SYMBOLS = (
     "limg_hip_synth_photo_noise_device", "limg_hip_context_device_bytes", "limg_hip_version", "limg_hip_profile_begin", "limg_hip_profile_end",
     "limg_hip_host_noise_table", "limg_hip_noise_table_device", "limg_hip_host_chain_call", "limg_hip_host_chain_checkpoints", "limg_hip_host_dense_checkpoints", "limg_hip_host_partition", "limg_hip_check_device_status",
     "limg_hip_stream_bound", "limg_hip_encode_stream_device", "limg_hip_decode_stream_device", "limg_hip_encode_stream", "limg_hip_decode_stream",
-    "limg_hip_stream_info", "limg_hip_encode_stream_batch_device", "limg_hip_encode_stream_batch",
+    "limg_hip_stream_info", "limg_hip_encode_stream_batch_device", "limg_hip_encode_stream_batch", "limg_hip_encode_stream_batch_ef_device", "limg_hip_encode_stream_batch_ef",
     "limg_hip_stream_sizes_device", "limg_hip_stream_sizes", "limg_hip_encode_stream_budget_device", "limg_hip_encode_stream_budget",
     "limg_hip_encode_stream_budget_batch_device", "limg_hip_encode_stream_budget_batch",
     "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
@@ -292,6 +292,11 @@ def load_library(path=None):
                                                       C.c_int, C.c_void_p]
     L.limg_hip_encode_stream_batch.restype = C.c_int
     L.limg_hip_encode_stream_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_int, C.c_int]
+    L.limg_hip_encode_stream_batch_ef_device.restype = C.c_int  # as limg_hip_encode_stream_batch_device, ef: host array of `count` uint32
+    L.limg_hip_encode_stream_batch_ef_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int,
+                                                         C.c_int, C.c_void_p]
+    L.limg_hip_encode_stream_batch_ef.restype = C.c_int
+    L.limg_hip_encode_stream_batch_ef.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.limg_hip_stream_sizes_device.restype = C.c_int  # ctx, in, sizeX, sizeY, hasAlpha, error factors (host), count, sizes (host), pool, fast, hipStream
     L.limg_hip_stream_sizes_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.limg_hip_stream_sizes.restype = C.c_int
@@ -773,6 +778,25 @@ class LimgHip:
         want_sizes."""
         sizes = (C.c_size_t * max(len(imgs), 1))()
         outs = self._stream_list("limg_hip_encode_stream_batch_device", imgs, has_alpha, outs, (sizes if want_sizes else None, error_factor, pool_threads, int(fast)), True)
+        return outs, ([int(v) for v in sizes[:len(imgs)]] if want_sizes else None)
+
+    # ---- ... each image at its own error factor: stream i = encode_stream of image i at error_factors[i] ----
+    @staticmethod
+    def _factor_list(error_factors, n):
+        assert len(error_factors) == n
+        return (C.c_uint32 * max(n, 1))(*[int(e) for e in error_factors])
+
+    def encode_stream_batch_ef(self, imgs, has_alpha, error_factors, pool_threads=0, fast=True):
+        """host uint32 images of one shape, one error factor per image -> list of stream bytes (numpy uint8), one batched call"""
+        sizes = (C.c_size_t * max(len(imgs), 1))()
+        outs = self._stream_list("limg_hip_encode_stream_batch_ef", imgs, has_alpha, None, (sizes, self._factor_list(error_factors, len(imgs)), pool_threads, int(fast)), False)
+        return [o[:sizes[k]].copy() for k, o in enumerate(outs)]
+
+    def encode_stream_batch_ef_device(self, imgs, has_alpha, error_factors, outs=None, want_sizes=True, pool_threads=0, fast=True):
+        """encode_stream_batch_device with one error factor per image (error_factors: host sequence of len(imgs))"""
+        sizes = (C.c_size_t * max(len(imgs), 1))()
+        outs = self._stream_list("limg_hip_encode_stream_batch_ef_device", imgs, has_alpha, outs,
+                                 (sizes if want_sizes else None, self._factor_list(error_factors, len(imgs)), pool_threads, int(fast)), True)
         return outs, ([int(v) for v in sizes[:len(imgs)]] if want_sizes else None)
 
     # ---- budgeted stream encode of a list: result i = encode_stream_budget of image i with its budget (contract: include/limg_hip.h) ----

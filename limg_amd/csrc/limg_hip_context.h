@@ -141,6 +141,7 @@ struct limg_hip_context
     Bytes &n;
     DevBuf fac{ n }, tiles{ n }, units{ n }, status{ n }, buf{ n }; // stream packer: 3 factor planes, per-tile payload words; decode status word; host-entry staging
     DevBuf rateState{ n }, rateCounter{ n }, rateList{ n }; // size probe (limg_hip_rate.hip): RateDevice; the payload-word counter; the list form's error factors, then its sizes
+    DevBuf rated{ n }; // batched stream encode with one error factor per image: one RatedImage (32 bytes) per image of a chunk, the threshold table
     DevBuf table{ n }, sizes{ n }; // batched stream encode: one StreamImage per image of the list; the finished streams' sizes side by side (one download)
     // version 2 stream of the merged-block encoder: per rectangle its first 64-pixel run, per tile of rectangles its totals; the decoder's block -> rectangle map and
     // its per-call words
@@ -260,6 +261,11 @@ namespace limg_hip
     // With fitOnly (no planes at all): k_fit_tpb's one grid over the list, records and invN image after image in the context's scratch -- the budgeted list's probes.
     const ImageIO *batch = nullptr;
     size_t batchCount = 1;
+    // errorFactors (host array of batchCount entries, or NULL): image i of a compact-mode stream list at its own error factor -- k_encode_list_rated instead of the
+    // persistent kernel, the `errorFactor` argument unused.  Whole blocks, k_fit_tpb's float stage, the default search; anything else is refused.
+    // ratedTable: device memory of the caller's for batchCount RatedImage entries, which this call fills from errorFactors on its stream.
+    const uint32_t *errorFactors = nullptr;
+    RatedImage *ratedTable = nullptr;
     // ---- a sub-image of a larger encode (the two parts of an image whose last block row is partial: encode_height_ragged) ----
     bool inner = false;            // part of a larger encode: no statistics launch of its own, no reset of the context's chain / statistics state
     int marks = 2;                 // profiling events: 2 = all four, 1 = all but the last, 0 = none
@@ -285,6 +291,7 @@ namespace limg_hip
     int channels;
     bool ragged, fullPlanes, fused, wantStats;
     size_t blocks, strips; // of all images of the launch
+    const RatedImage *rated = nullptr; // x.errorFactors as the device's threshold table: the persistent launches are k_encode_list_rated's
     void mark_if(int level) const { if (x.marks >= level) mark(c, stream); } // profiling events: x.marks says which of an encode's four this call records
   };
   limg_hip_result encode_stats(const EncodeJob &e);

@@ -174,6 +174,11 @@ namespace
       if ((r = c->enc.batchTable.ensure(batchCount * sizeof(ImageIO))) != limg_hip_success) return r;
       launch_set_batch_table((ImageIO *)c->enc.batchTable.p, batch, batchCount, e.stream); // through kernel arguments: stream-ordered, and the host array may die right away
       p.batch = (const ImageIO *)c->enc.batchTable.p;
+      if (x.errorFactors && x.ratedTable)
+      { // one error factor per image: the thresholds go to the caller's table, by the same kind of launch as the image table
+        launch_set_rated_table(x.ratedTable, x.errorFactors, batchCount, e.stream);
+        e.rated = x.ratedTable;
+      }
     }
 
     if (dInfo && !e.ragged)
@@ -249,6 +254,26 @@ namespace
     return 0;
   }
 
+  // The persistent launch of a job, or of the sub-batch q of it that starts at image i0 of the list: k_encode_persistent, or -- a list with one error factor per
+  // image -- k_encode_list_rated on the same scratch, with the threshold table offset as the image table is.
+  void launch_persistent(const EncodeJob &e, const EncodeParams &q, size_t i0, int workgroups)
+  {
+    if (!e.rated) { launch_encode_persistent(q, e.channels, workgroups, e.stream); return; }
+    RatedListParams r;
+    memset(&r, 0, sizeof(r));
+    r.batch = q.batch; r.rated = e.rated + i0;
+    r.batchCount = q.batchCount; r.imageStrips = q.imageStrips;
+    r.sizeX = q.sizeX; r.sizeY = q.sizeY; r.blocksX = q.blocksX; r.blocksY = q.blocksY; r.stripsX = q.stripsX;
+    for (int k = 0; k < 3; k++) r.forced[k] = q.forced[k];
+    r.recordLimit = q.recordLimit;
+    r.chainCount = q.chainCount; r.chainRows = q.chainRows;
+    r.records = q.records; r.invN = q.invN; r.shifts = q.shifts; r.stripWords = q.stripWords;
+    r.noise = q.noise; r.noiseLast = q.noiseLast;
+    r.vecIn = q.vecIn; r.vecFactors = q.vecFactors; r.vecFactors8 = q.vecFactors8;
+    r.desc = q.desc; r.ticket = q.ticket; r.timeout = q.timeout; r.park = q.park;
+    launch_encode_list_rated(r, e.channels, q.floatFast != 0, workgroups, e.stream);
+  }
+
   limg_hip_result encode_sub_batches(EncodeJob &e, size_t subImages)
   {
     limg_hip_context *const c = e.c;
@@ -297,7 +322,7 @@ namespace
         launch_fit_tpb(sub(k + 1), e.channels, fs);
         HIP_TRY(hipEventRecord(ev[3 + 2 * k], fs));
       }
-      launch_encode_persistent(sub(k), e.channels, c->enc.persistentWorkgroups / 5 * (k + 1 < nSub ? wgOverlap : wg_per_cu(c, 6)), stream);
+      launch_persistent(e, sub(k), k == 0 ? 0 : firstSub + (k - 1) * subImages, c->enc.persistentWorkgroups / 5 * (k + 1 < nSub ? wgOverlap : wg_per_cu(c, 6)));
     }
     e.mark_if(1); e.mark_if(2);
     HIP_TRY(hipGetLastError());
@@ -314,7 +339,7 @@ namespace
       launch_fit_tpb(p, e.channels, e.stream);
     }
     e.mark_if(1);
-    launch_encode_persistent(p, e.channels, e.c->enc.persistentWorkgroups / 5 * wg_per_cu(e.c, p.prefit ? 6 : 5), e.stream);
+    launch_persistent(e, p, 0, e.c->enc.persistentWorkgroups / 5 * wg_per_cu(e.c, p.prefit ? 6 : 5));
     e.mark_if(1);
     if (p.prefit) e.mark_if(2); else { e.mark_if(1); e.mark_if(2); } // 4 events per encode: with the float stage as its own launch the intervals are {k_fit_tpb, k_encode_persistent, -}
     HIP_TRY(hipGetLastError());
@@ -419,6 +444,8 @@ namespace limg_hip
     // ... or for its records alone (the size probes of a budgeted list): k_fit_tpb's batched grid and nothing else
     const bool fitList = e.p.fitOnly && e.p.prefit && !ragged && chainPhase == 0;
     if (batchCount > 1 && !fitList && (!e.fused || !e.p.prefit || (!fullPlanes && !compactList))) return limg_hip_error_InvalidParameter; // (limg_hip_encode3d_batch_device sends such lists through one encode per image instead)
+    // ... each at its own error factor (x.errorFactors): that compact list, and the one kernel there is for it
+    if (x.errorFactors && (!e.rated || batchCount <= 1 || !compactList || !e.fused || !e.p.prefit || !fast || chainPhase != 0)) return limg_hip_error_InvalidParameter;
     if (e.fused && (r = fused_scratch(e, compact)) != limg_hip_success) return r;
 
     const size_t subImages = sub_batch_images(e);

@@ -99,6 +99,53 @@ namespace limg_hip
     int32_t vecDecoded; // pDecoded may be stored 16 bytes per lane (sizeX % 4 == 0 and 16-byte aligned)
   };
 
+  // ---- a list whose images each carry their own error factor (limg_hip_encode_stream_batch_ef*, k_encode_list_rated) ----
+  // Image i's bit-crush thresholds and flags (thresholds(), limg_hip_encode_rules.h) and the error factor its stream's header carries: an entry of a device table
+  // next to the ImageIO table, read once per work strip with scalar loads.  The members carry EncodeParams' names: fit_search_strip takes its limits from `lim`,
+  // which is the parameter block itself in every other kernel.
+  struct RatedImage
+  {
+    uint32_t maxPixel32, blockLimitFull;
+    uint64_t maxBlock;
+    int32_t crushBits;
+    uint32_t errorFactor;
+    uint32_t pad[2];
+  };
+  static_assert(sizeof(RatedImage) == 32, "one entry of the threshold table");
+
+  // k_encode_list_rated's arguments: the persistent kernel's loop over a list in compact stream mode (float stage by k_fit_tpb, default search), the thresholds per
+  // image.  What the shared stages read carries EncodeParams' names; what that mode fixes is a constant here, and so are the look-back's test hooks: the kernarg
+  // segment is the same in both builds (as RateProbeParams), and the test build's record_limit travels in recordLimit.
+  struct RatedListParams
+  {
+    const ImageIO *batch;      // one entry per image of THIS launch (a sub-batch's slice of the list's table)
+    const RatedImage *rated;   // ... and its thresholds, offset alike
+    uint32_t batchCount, imageStrips;
+    uint32_t sizeX, sizeY, blocksX, blocksY, stripsX;
+    int32_t forced[3];
+    int32_t recordLimit;
+    uint32_t chainCount, chainRows;
+    limg_hip_block_record *records;
+    float *invN;
+    uint32_t *shifts;
+    uint32_t *stripWords;
+    const uint8_t *noise;
+    uint32_t noiseLast;
+    int32_t vecIn, vecFactors, vecFactors8;
+    unsigned long long *desc;
+    uint32_t *ticket;
+    uint32_t *timeout;
+    uint8_t *park;
+    // compact stream mode, whole blocks, one dither chain partition per image, nothing of the split path or of a chain shared between GPUs
+    static constexpr int32_t storePlanes = 1, fullPlanes = 0, compactOut = 1, streamRaw = 1, fitOnly = 0, vecPlanes = 0, vecDecoded = 0;
+    static constexpr uint32_t *stripCalls = nullptr, *stripBase = nullptr;
+    static constexpr const unsigned long long *chainBase = nullptr;
+    static constexpr const uint32_t *accTable = nullptr;
+#ifdef LIMG_HIP_TEST_HOOKS // the three look-back hooks do not reach this kernel (include/limg_hip_test_hooks.h): the product's values
+    static constexpr uint32_t lookbackSpins = 1u << 22, testBaseErrStrip = ~0u, testSkipStrip = ~0u;
+#endif
+  };
+
   // stream pack (limg_hip_stream.hip): from the compact outputs of an encode (factor planes, records, shift words)
   struct StreamParams
   {
@@ -130,6 +177,7 @@ namespace limg_hip
     const limg_hip_block_record *records;
     const uint32_t *shifts;
     uint32_t *stripWords;
+    const RatedImage *rated; // NULL: every header carries errorFactor; else image i's carries rated[i].errorFactor (a list with one error factor per image)
   };
 
   struct DecodeParams
@@ -161,6 +209,8 @@ namespace limg_hip
   void launch_fit_tpb(const EncodeParams &p, int channels, hipStream_t s);
   void launch_fit_search(const EncodeParams &p, int channels, hipStream_t s);
   void launch_encode_persistent(const EncodeParams &p, int channels, int workgroups, hipStream_t s);
+  void launch_encode_list_rated(const RatedListParams &p, int channels, bool floatFast, int workgroups, hipStream_t s);
+  void launch_set_rated_table(RatedImage *dTable, const uint32_t *hErrorFactors, size_t count, hipStream_t s); // hErrorFactors: HOST array (may die when the call returns), 64 per launch
   void launch_strip_scan(const EncodeParams &p, hipStream_t s);
   void launch_dither_store(const EncodeParams &p, int channels, hipStream_t s);
   void launch_shift_stats(const uint32_t *dShifts, uint32_t blocksX, uint32_t blocksY, uint32_t rows, uint32_t sizeX, uint32_t sizeY, unsigned long long *dOut30, hipStream_t s);

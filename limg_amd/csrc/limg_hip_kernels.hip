@@ -13,7 +13,8 @@
 //
 // Kernels: k_encode_persistent (one launch per image -- or per list of images of one shape, limg_hip_encode3d_batch_device: the tickets
 // then run through the strips of image 0, image 1, ... --: every workgroup loops over work strips, E step of a new strip then the
-// F step of the strip it fitted one iteration earlier) and the three-launch split path k_fit_search / k_strip_scan /
+// F step of the strip it fitted one iteration earlier), k_encode_list_rated (the same loop, limg_hip_persistent_loop.inc, for a list in compact stream mode whose
+// images each carry their own error factor: the search's limits per work strip from a device table) and the three-launch split path k_fit_search / k_strip_scan /
 // k_dither_store (images with partial edge blocks, whose chain has to be walked on the host; `_perf` mode; A/B testing).
 // For images made of whole blocks the float stage (channel sums, direction fit, extrema, record) runs before them as its own
 // kernel with one lane per block (k_fit_tpb, limg_hip_fit_tpb.hip; template parameter PREFIT here): the E step then starts from
@@ -131,11 +132,12 @@ namespace limg_hip
     // block row in the per-block scratch arrays; head0: the id of the image's first strip
     // ACC: the accurate search (fastBitCrushing == false) instead of the default one -- a kernel variant of its own, so that neither search's registers and code
     // weigh on the other
+    // lim: where the search's limits (maxPixel32, blockLimitFull, maxBlock, crushBits) come from -- `p` itself, or the image's entry of a threshold table (k_encode_list_rated)
     // Two parts stay INLINE here, measured (profiles/e_step_stages_ab.md): as functions of their own (float_stage_pixel, search_block) the lane == pixel float stage and
     // the search's set-up left the persistent kernel's lane == pixel instances with 11-46 more spilled SGPRs and 1.1-1.8 KB more code, `--legacy-float-stage` 5.3 %
     // slower, and four k_fit_search instances with 2-4 more VGPRs; either one alone as a function does the same.
-    template <int CH, bool PERSIST, bool FAST, bool PREFIT, bool ACC, class P, class IO>
-    __device__ __forceinline__ void fit_search_strip(const P &p, const IO &io, const uint32_t id, const uint32_t local, const uint32_t rowBase, const uint32_t head0, uint8_t *lds,
+    template <int CH, bool PERSIST, bool FAST, bool PREFIT, bool ACC, class P, class LIM, class IO>
+    __device__ __forceinline__ void fit_search_strip(const P &p, const LIM &lim, const IO &io, const uint32_t id, const uint32_t local, const uint32_t rowBase, const uint32_t head0, uint8_t *lds,
                                                      uint8_t *park, const int tid)
     {
       constexpr LdsLayout LL = lds_layout<PREFIT>();
@@ -428,11 +430,11 @@ namespace limg_hip
         // the shift search of the block (a10-a12), inline (see the note above this function): limits, the packed trial's state, then one of the two automata or, for a
         // record out of the packed trial's range, the generic search
         if (p.forced[0] >= 0) { shift[0] = (uint32_t)p.forced[0]; shift[1] = (uint32_t)p.forced[1]; shift[2] = (uint32_t)p.forced[2]; }
-        else if (p.crushBits)
+        else if (lim.crushBits)
         {
-          const uint64_t maxBlockN = p.maxBlock * (uint64_t)n;
+          const uint64_t maxBlockN = lim.maxBlock * (uint64_t)n;
           // be * 16 < maxBlock * n  <=>  be < ceil(maxBlock * n / 16); clamped to 32 bits (be itself never gets near 2^32).  Full blocks: from the host.
-          uint32_t blockLimit = p.blockLimitFull;
+          uint32_t blockLimit = lim.blockLimitFull;
           if (n != 64)
           {
             const uint64_t lim64 = (maxBlockN + 15ull) >> 4;
@@ -474,20 +476,20 @@ namespace limg_hip
             //  instructions per block)
             if (!ACC)
             {
-              if (n == 64) search_fast_automaton<true>(t, true, p.maxPixel32, blockLimit, shift);
-              else search_fast_automaton<false>(t, active, p.maxPixel32, blockLimit, shift);
+              if (n == 64) search_fast_automaton<true>(t, true, lim.maxPixel32, blockLimit, shift);
+              else search_fast_automaton<false>(t, active, lim.maxPixel32, blockLimit, shift);
             }
             else
             {
-              if (n == 64) search_accurate_automaton<true>(t, true, p.maxPixel32, blockLimit, p.accTable, shift);
-              else search_accurate_automaton<false>(t, active, p.maxPixel32, blockLimit, p.accTable, shift);
+              if (n == 64) search_accurate_automaton<true>(t, true, lim.maxPixel32, blockLimit, p.accTable, shift);
+              else search_accurate_automaton<false>(t, active, lim.maxPixel32, blockLimit, p.accTable, shift);
             }
           }
           else
           {
             // out-of-range record (never produced by a fit of byte pixels; kept so that no input can break exactness):
             // generic 32-bit trial, deliberately a real call so that none of it is speculated into the common path
-            const uint32_t packed = (uint32_t)sgpr((int)search_generic(px, fA, fB, fC, blkE->rec, active, p.maxPixel32, maxBlockN, !ACC)); // uniform: keeps the shift triple (and the bookkeeping below) on the scalar unit for the common path too
+            const uint32_t packed = (uint32_t)sgpr((int)search_generic(px, fA, fB, fC, blkE->rec, active, lim.maxPixel32, maxBlockN, !ACC)); // uniform: keeps the shift triple (and the bookkeeping below) on the scalar unit for the common path too
             shift[0] = packed & 0xFF; shift[1] = (packed >> 8) & 0xFF; shift[2] = (packed >> 16) & 0xFF;
           }
         }
@@ -633,7 +635,7 @@ namespace limg_hip
     __global__ __launch_bounds__(kThreads) void k_fit_search(const EncodeParams p)
     {
       __shared__ __attribute__((aligned(16))) uint8_t s_lds[lds_layout<PREFIT>().total];
-      fit_search_strip<CH, false, FAST, PREFIT, ACC>(p, p.io, blockIdx.x, blockIdx.x, 0u, 0u, s_lds, nullptr, (int)threadIdx.x);
+      fit_search_strip<CH, false, FAST, PREFIT, ACC>(p, p, p.io, blockIdx.x, blockIdx.x, 0u, 0u, s_lds, nullptr, (int)threadIdx.x);
     }
 
     template <int CH>
@@ -655,68 +657,39 @@ namespace limg_hip
     // drift apart, E and F steps of different workgroups overlap on every CU.
     // Progress: a look-back only waits for strips with smaller tickets; those were drawn earlier by workgroups that are running, and an E step never waits
     // (see "decoupled look-back" above: no strip id is ever derived from blockIdx).
+    // The loop itself: limg_hip_persistent_loop.inc, one text for this kernel and for k_encode_list_rated below.
     template <int CH, bool FAST, bool PREFIT, bool ACC>
     __global__ __launch_bounds__(kThreads, PREFIT ? 6 : 5) void k_encode_persistent(const EncodeParams p)
     {
       __shared__ __attribute__((aligned(16))) uint8_t s_lds[lds_layout<PREFIT>().total];
       __shared__ uint32_t s_ticket;
-      const int tid = (int)threadIdx.x;
-      const uint32_t S = p.imageStrips * p.batchCount; // the strips of all images of a batch, image after image
-      uint8_t *park = p.park + (size_t)blockIdx.x * 2 * kParkBytes;
-      uint32_t prev = 0xFFFFFFFFu, prevImg = 0, slot = 0;
-      // The two steps read the parameters straight from the kernel-argument segment, through a pointer the compiler cannot see through from one step to the
-      // next: a field is then fetched (one scalar load, scalar-cache hit) where a step uses it.  Read from `p`, all ~70 dwords are loaded once before the
-      // loop and kept alive across it -- more SGPRs than there are, so the compiler parks them in VGPR lanes and pays a quarter-rate v_readlane per use.
       typedef const __attribute__((address_space(4))) EncodeParams KernArgs;
-      KernArgs *const kargs = (KernArgs *)__builtin_amdgcn_kernarg_segment_ptr();
       // the caller's pointers of the image a strip belongs to: the kernel arguments themselves for a single image, an entry of the device table for a batch (same
       // address space, same scalar loads).  The table was written by a copy that precedes this launch on the stream and is not modified while the kernel runs.
       typedef const __attribute__((address_space(4))) ImageIO KernIO;
       auto io_of = [](KernArgs *a, uint32_t img) -> KernIO * { return a->batchCount > 1 ? (KernIO *)a->batch + img : &a->io; };
-      // All workgroups start their first E step together, so their first F steps (latency-bound, little vector work) coincide too, and it takes a few iterations
-      // of data-dependent search lengths before the E and F steps of a CU's six workgroups interleave.  Workgroups are dealt out to the 256 CUs residency slot
-      // by slot, so slot k (= blockIdx.x / 256) starts k * 3.4 us late: measured -0.5 % on the kernel, and harmless where the placement differs.
-      for (uint32_t i = 0; i < (blockIdx.x >> 8); i++) __builtin_amdgcn_s_sleep(127);
-      __builtin_amdgcn_s_setprio(kPrioE);
-      for (;;)
-      {
-        __syncthreads(); // the previous step's LDS use is over (and the rsqrt table is in place)
-        // EVERY strip id is drawn from the ticket, the first one included: a workgroup that holds id t is resident, and so is the holder of every id < t (it drew
-        // earlier).  Round 4 let workgroup i take strip i without asking (one atomic round trip less per workgroup): with a second persistent kernel on the GPU
-        // (another context's stream) a resident workgroup then waited for strips of workgroups that were never dispatched, and both kernels spun into the
-        // look-back's bound.  Never derive a strip id from blockIdx.
-        if (tid == 0) s_ticket = atomicAdd(p.ticket, 1u);
-        __syncthreads();
-        const uint32_t t = (uint32_t)sgpr((int)s_ticket);
-        int tid_e = tid;
-        asm volatile("" : "+v"(tid_e));
-        KernArgs *pe = kargs;
-        asm volatile("" : "+s"(pe));
-        uint32_t img = 0;
-        if (t < S)
-        {
-          if (pe->batchCount > 1) img = t / pe->imageStrips; // once per strip, on the scalar unit
-          const uint32_t head0 = img * pe->imageStrips;
-          fit_search_strip<CH, true, FAST, PREFIT, ACC>(*pe, *io_of(pe, img), t, t - head0, img * pe->blocksY, head0, s_lds, park + slot * kParkBytes, tid_e);
-        }
-        if (prev != 0xFFFFFFFFu)
-        {
-          __syncthreads();
-          int tid_f = tid;
-          asm volatile("" : "+v"(tid_f));
-          KernArgs *pf = kargs;
-          asm volatile("" : "+s"(pf));
-          // The F step is latency-bound with little vector work, the E step is what keeps the vector unit busy: E-step waves get the issue priority (s_setprio),
-          // F-step waves take the slots they leave.  Measured: -2.5 % on the kernel (the other way round: +0.8 %).
-          __builtin_amdgcn_s_setprio(0);
-          const uint32_t head0 = prevImg * pf->imageStrips;
-          dither_store_strip<CH, true>(*pf, *io_of(pf, prevImg), prev, prev - head0, prevImg * pf->blocksY, head0, s_lds + kLdsStrip, park + (slot ^ 1u) * kParkBytes, tid_f);
-          __builtin_amdgcn_s_setprio(kPrioE);
-        }
-        if (t >= S) break;
-        prev = t; prevImg = img;
-        slot ^= 1u;
-      }
+#define LIMG_LOOP_LIMITS(a, img) (*(a)) /* one error factor: the limits are kernel arguments */
+#include "limg_hip_persistent_loop.inc"
+#undef LIMG_LOOP_LIMITS
+    }
+
+    // A list whose images each carry their own error factor (limg_hip_encode_stream_batch_ef*): the same loop in compact stream mode behind k_fit_tpb, default search.
+    // Once per strip the E step fetches its image's entry of the threshold table with scalar loads, as it fetches the image's pointers: the limits stay on the
+    // scalar unit, no lane holds a threshold.  The F step needs none of them.  The table, like the ImageIO table, was written by a launch that precedes this one on
+    // the stream and is not modified while the kernel runs.
+    template <int CH, bool FAST>
+    __global__ __launch_bounds__(kThreads, 6) void k_encode_list_rated(const RatedListParams p)
+    {
+      constexpr bool PREFIT = true, ACC = false;
+      __shared__ __attribute__((aligned(16))) uint8_t s_lds[lds_layout<PREFIT>().total];
+      __shared__ uint32_t s_ticket;
+      typedef const __attribute__((address_space(4))) RatedListParams KernArgs;
+      typedef const __attribute__((address_space(4))) ImageIO KernIO;
+      typedef const __attribute__((address_space(4))) RatedImage KernLimits;
+      auto io_of = [](KernArgs *a, uint32_t img) -> KernIO * { return (KernIO *)a->batch + img; }; // (a sub-batch of one image reads the table too)
+#define LIMG_LOOP_LIMITS(a, img) (*((KernLimits *)(a)->rated + (img)))
+#include "limg_hip_persistent_loop.inc"
+#undef LIMG_LOOP_LIMITS
     }
   } // namespace
 
@@ -740,6 +713,41 @@ namespace limg_hip
     const uint32_t strips = p.imageStrips * p.batchCount;
     const dim3 grid(strips < (uint32_t)workgroups ? strips : (uint32_t)workgroups), block(kThreads);
     with_encode_variant(p, channels, [&](auto CH, auto FAST, auto PREFIT, auto ACC) { hipLaunchKernelGGL((k_encode_persistent<CH, FAST, PREFIT, ACC>), grid, block, 0, s, p); });
+  }
+
+  namespace
+  {
+    // the threshold table of a list with one error factor per image: the factors travel inside kernel arguments (as k_set_batch_table's pointers: stream-ordered, and
+    // the caller's array may die right away); thread i turns image i's into its entry by the rule every encode uses (thresholds, limg_hip_encode_rules.h)
+    struct RatedChunk { uint32_t n; uint32_t errorFactor[64]; };
+    __global__ void k_set_rated_table(RatedImage *dst, const RatedChunk chunk)
+    {
+      const uint32_t i = threadIdx.x;
+      if (i >= chunk.n) return;
+      const Thresholds t = thresholds(chunk.errorFactor[i]);
+      RatedImage e;
+      e.maxPixel32 = t.maxPixel32; e.blockLimitFull = t.blockLimitFull; e.maxBlock = t.maxBlock; e.crushBits = (int32_t)t.crushBits;
+      e.errorFactor = chunk.errorFactor[i]; e.pad[0] = 0u; e.pad[1] = 0u;
+      dst[i] = e;
+    }
+  }
+
+  void launch_set_rated_table(RatedImage *dTable, const uint32_t *hErrorFactors, size_t count, hipStream_t s)
+  {
+    for (size_t i0 = 0; i0 < count; i0 += 64)
+    {
+      RatedChunk ch;
+      ch.n = (uint32_t)(count - i0 < 64 ? count - i0 : 64);
+      for (uint32_t i = 0; i < 64; i++) ch.errorFactor[i] = i < ch.n ? hErrorFactors[i0 + i] : 0u;
+      hipLaunchKernelGGL(k_set_rated_table, dim3(1), dim3(64), 0, s, dTable + i0, ch);
+    }
+  }
+
+  void launch_encode_list_rated(const RatedListParams &p, int channels, bool floatFast, int workgroups, hipStream_t s)
+  {
+    const uint32_t strips = p.imageStrips * p.batchCount;
+    const dim3 grid(strips < (uint32_t)workgroups ? strips : (uint32_t)workgroups), block(kThreads);
+    with_flags([&](auto rgba, auto fast) { hipLaunchKernelGGL((k_encode_list_rated<rgba ? 4 : 3, fast>), grid, block, 0, s, p); }, channels == 4, floatFast);
   }
 
   namespace

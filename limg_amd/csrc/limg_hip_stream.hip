@@ -277,7 +277,12 @@ namespace limg_hip
     {
       const uint32_t img = blockIdx.x;
       const unsigned long long total = scan_strips(b.stripWords + (size_t)img * b.imageStrips, b.imageStrips);
-      if (threadIdx.x == 0) write_stream_header(b.images[img].stream, header_info(b), total);
+      if (threadIdx.x == 0)
+      {
+        StreamHeaderInfo h = header_info(b);
+        if (b.rated) h.errorFactor = b.rated[img].errorFactor; // a list with one error factor per image: the header carries the image's own
+        write_stream_header(b.images[img].stream, h, total);
+      }
     }
 
     // 8 bytes (lo = pixels 0..3, hi = 4..7), each holding its value in the TOP b bits (sh = 8 - b; raw-escaped fields: b = 8) -> the 8 values in 8 b consecutive bits

@@ -1,6 +1,6 @@
-// limg_hip_stream_encode_api.hip -- the version 1 stream's encode family of the C ABI: limg_hip_encode_stream, limg_hip_encode_stream_batch, limg_hip_stream_sizes,
+// limg_hip_stream_encode_api.hip -- the version 1 stream's encode family of the C ABI: limg_hip_encode_stream, limg_hip_encode_stream_batch, limg_hip_encode_stream_batch_ef, limg_hip_stream_sizes,
 // limg_hip_encode_stream_budget and limg_hip_encode_stream_budget_batch, each with its _device form.  The 8x8 encode in compact mode + the packer of
-// limg_hip_stream.hip; the size probe's kernels are limg_hip_rate.hip, the search limg_hip_rate_step.h.  What the ten entries do alike -- a call's shape, the argument
+// limg_hip_stream.hip; the size probe's kernels are limg_hip_rate.hip, the search limg_hip_rate_step.h.  What the twelve entries do alike -- a call's shape, the argument
 // checks, a list's staging, the probe's parameters, the searches' enqueue, the results -- is written once, in the anonymous namespace below.  No kernel is defined here.
 #include "limg_hip_context.h"
 
@@ -175,6 +175,148 @@ namespace
   }
 }
 
+namespace
+{
+  // ---- a list of same-shape images to streams: what the batch entries do, with one error factor (efs == NULL) or one per image (efs: host, count) ----
+  // The images of [0, n) sorted by error factor, one existing call per distinct value -- the single call for a group of one, the shared-factor batch otherwise:
+  // what a list with one factor per image falls back to where k_encode_list_rated does not apply.  The same bytes.
+  limg_hip_result encode_grouped(limg_hip_context *c, size_t n, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *const *ppStreams,
+                                 size_t capacityEach, const uint32_t *efs, int poolThreads, int fastBitCrushing, void *stream)
+  {
+    std::vector<uint32_t> order(n); // the images sorted by their error factor
+    std::vector<const uint32_t *> groupIn;
+    std::vector<uint8_t *> groupOut;
+    for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return efs[a] < efs[b]; });
+    limg_hip_result r = limg_hip_success;
+    for (size_t g0 = 0; g0 < n;)
+    {
+      const uint32_t ef = efs[order[g0]];
+      size_t g1 = g0;
+      groupIn.clear(); groupOut.clear();
+      for (; g1 < n && efs[order[g1]] == ef; g1++) { groupIn.push_back(ppIn[order[g1]]); groupOut.push_back(ppStreams[order[g1]]); }
+      if (g1 - g0 == 1) r = limg_hip_encode_stream_device(c, groupIn[0], sizeX, sizeY, hasAlpha, groupOut[0], capacityEach, nullptr, ef, poolThreads, fastBitCrushing, stream);
+      else r = limg_hip_encode_stream_batch_device(c, g1 - g0, groupIn.data(), sizeX, sizeY, hasAlpha, groupOut.data(), capacityEach, nullptr, ef, poolThreads, fastBitCrushing,
+                                                   stream);
+      if (r != limg_hip_success) return r;
+      g0 = g1;
+    }
+    return r;
+  }
+
+  // Lists of whole-block images go chunk by chunk (the plane batch's rule) through ONE compact-mode batched encode -- records, shift words and the strips' payload
+  // words in the context's raster arrays, image after image; the factor planes in per-image slices of stream.fac -- and one scan + one pack launch over the chunk.
+  // With efs the chunk's encode is k_encode_list_rated's (thresholds per image from a device table) and the scan writes every header's own error factor.
+  // pointers: the entry's other pointers (pErrorFactors) are there.  ratedStorage: device memory for the threshold table of a chunk (32 bytes per image) where the
+  // caller has some to spare -- the budgeted list's search states, which its searches are done with --, else the context's own (stream.rated).
+  limg_hip_result stream_list_device(limg_hip_context *c, bool pointers, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                     uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, const uint32_t *efs, int poolThreads,
+                                     int fastBitCrushing, void *stream, RatedImage *ratedStorage = nullptr)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    limg_hip_result r;
+    if ((r = check_list(c, pointers, count, ppIn, ppStreams, sh, capacityEach, true)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t chunk = list_chunk(c, sh.blocks, sh.strips);
+    // one factor per image outside the rated kernel's reach (partial edge blocks, the split path, the float stage inside the encode kernel, the accurate search, a
+    // list of one): one existing call per distinct factor
+    const bool grouped = efs && (count == 1 || !batch_applies(c, sh) || fastBitCrushing == 0);
+    const bool oneByOne = grouped || count == 1 || !batch_applies(c, sh);
+    const size_t most = oneByOne ? 1 : (count < chunk ? count : chunk); // images of the largest chunk
+    if ((r = c->stream.table.ensure(count * sizeof(StreamImage))) != limg_hip_success) return r;
+    if (most > 1)
+    { // everything a chunk needs, before the first launch: nothing is grown (and so freed) between the chunks of a list
+      if ((r = c->stream.fac.ensure(most * sh.planeStride * 3)) != limg_hip_success) return r;
+      if ((r = c->stream.units.ensure(most * sh.strips * 4)) != limg_hip_success) return r;
+      if ((r = c->enc.records.ensure(most * sh.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+      if ((r = c->enc.shifts.ensure(most * sh.blocks * 4)) != limg_hip_success) return r;
+      if (efs && !ratedStorage)
+      {
+        if ((r = c->stream.rated.ensure(most * sizeof(RatedImage))) != limg_hip_success) return r;
+        ratedStorage = (RatedImage *)c->stream.rated.p;
+      }
+    }
+    std::vector<StreamImage> images(count);
+    for (size_t i = 0; i < count; i++) images[i].stream = ppStreams[i];
+    std::vector<ImageIO> table;
+    if (grouped) r = encode_grouped(c, count, ppIn, sizeX, sizeY, hasAlpha, ppStreams, capacityEach, efs, poolThreads, fastBitCrushing, stream);
+    for (size_t i0 = 0; !grouped && i0 < count && r == limg_hip_success;)
+    {
+      const size_t n = oneByOne ? 1 : (count - i0 < chunk ? count - i0 : chunk);
+      c->stats.accumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, as the plane batch
+      if (n == 1)
+      { // the single call (images with partial edge blocks, the split path, the float stage inside the encode kernel, a list or a last chunk of one image)
+        r = limg_hip_encode_stream_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, ppStreams[i0], capacityEach, nullptr, efs ? efs[i0] : errorFactor, poolThreads, fastBitCrushing,
+                                          stream);
+        if (r == limg_hip_success && pBytes && !oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], 1, s); // (for the sizes below)
+      }
+      else
+      {
+        table.assign(n, ImageIO{});
+        for (size_t i = 0; i < n; i++)
+        {
+          uint8_t *fac = (uint8_t *)c->stream.fac.p + i * 3 * sh.planeStride; // 256-byte aligned slices
+          table[i].in = ppIn[i0 + i];
+          table[i].info.pFactorsA = fac; table[i].info.pFactorsB = fac + sh.planeStride; table[i].info.pFactorsC = fac + 2 * sh.planeStride;
+          images[i0 + i].fac[0] = fac; images[i0 + i].fac[1] = fac + sh.planeStride; images[i0 + i].fac[2] = fac + 2 * sh.planeStride;
+        }
+        limg_hip_compact_out comp = { (limg_hip_block_record *)c->enc.records.p, (uint32_t *)c->enc.shifts.p };
+        EncodeExtra x;
+        x.batch = table.data(); x.batchCount = n;
+        x.streamRaw = true; x.stripWords = (uint32_t *)c->stream.units.p;
+        if (efs) { x.errorFactors = efs + i0; x.ratedTable = ratedStorage; }
+        if ((r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, &table[0].info, &comp, efs ? efs[i0] : errorFactor, poolThreads, fastBitCrushing, s, x)) != limg_hip_success) break;
+        launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], n, s);
+        StreamBatchParams b;
+        memset(&b, 0, sizeof(b));
+        b.sizeX = (uint32_t)sizeX; b.sizeY = (uint32_t)sizeY; b.blocksX = (uint32_t)sh.blocksX; b.blocksY = (uint32_t)sh.blocksY; b.nBlocks = (uint32_t)sh.blocks;
+        b.channels = hasAlpha ? 4 : 3; b.errorFactor = errorFactor; b.flags = stream_flags(c, fastBitCrushing);
+        b.stripsX = (uint32_t)sh.stripsX; b.imageStrips = (uint32_t)sh.strips; b.nImages = (uint32_t)n; b.nStrips = (uint32_t)(n * sh.strips);
+        b.nWaves = pack_waves(c, n * sh.strips); // as the single call -- for the whole chunk
+        b.images = (const StreamImage *)c->stream.table.p + i0;
+        b.records = comp.pRecords; b.shifts = comp.pShifts; b.stripWords = (uint32_t *)c->stream.units.p;
+        b.rated = efs ? ratedStorage : nullptr; // (the chunk's table, as the encode just wrote it)
+        mark(c, s);
+        launch_stream_pack_batch(b, s);
+        mark(c, s); mark(c, s); mark(c, s);
+        const hipError_t launched = hipGetLastError();
+        if (launched != hipSuccess) { c->stats.accumulate = false; HIP_TRY(launched); }
+      }
+      i0 += n;
+    }
+    c->stats.accumulate = false;
+    if (r != limg_hip_success || !pBytes) return r;
+    // the sizes: gathered from the headers on the device
+    if ((r = c->stream.sizes.ensure(count * 8)) != limg_hip_success) return r;
+    if (oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p, images.data(), count, s);
+    launch_stream_gather_bytes((const StreamImage *)c->stream.table.p, count, (unsigned long long *)c->stream.sizes.p, s);
+    HIP_TRY(hipGetLastError());
+    return download_sizes(c->stream.sizes.p, count, pBytes, s);
+  }
+
+  // the host form: upload, stream_list_device on the null stream, status, the streams down at their own sizes
+  limg_hip_result stream_list_host(limg_hip_context *c, bool pointers, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                   uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, const uint32_t *efs, int poolThreads, int fastBitCrushing)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    limg_hip_result r;
+    if ((r = check_list(c, pointers && pBytes != nullptr, count, ppIn, ppStreams, sh, capacityEach, false)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    StagedList l;
+    if ((r = stage_list(c, sh, count, ppIn, l)) != limg_hip_success) return r;
+    if ((r = stream_list_device(c, true, count, l.in.data(), sizeX, sizeY, hasAlpha, l.streams.data(), l.slice, pBytes, errorFactor, efs, poolThreads, fastBitCrushing, nullptr)) !=
+        limg_hip_success)
+      return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], l.streams[i], pBytes[i], hipMemcpyDeviceToHost)); // totalBytes of each, not the capacity
+    return limg_hip_success;
+  }
+}
+
 extern "C"
 {
   limg_hip_result limg_hip_encode_stream_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
@@ -335,106 +477,39 @@ extern "C"
     });
   }
 
-  // ---- batched stream encode: a list of same-shape images, stream i = limg_hip_encode_stream_device of image i ----
-  // Lists of whole-block images go chunk by chunk (the plane batch's rule) through ONE compact-mode batched encode -- records, shift words and the strips' payload
-  // words in the context's raster arrays, image after image; the factor planes in per-image slices of stream.fac -- and one scan + one pack launch over the chunk.
+  // ---- batched stream encode: a list of same-shape images, stream i = limg_hip_encode_stream_device of image i (stream_list_device / stream_list_host above) ----
   limg_hip_result limg_hip_encode_stream_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
                                                       uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, int poolThreads,
                                                       int fastBitCrushing, void *stream)
   {
-    const StreamShape sh(sizeX, sizeY);
-    limg_hip_result r;
-    if ((r = check_list(c, true, count, ppIn, ppStreams, sh, capacityEach, true)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const size_t chunk = list_chunk(c, sh.blocks, sh.strips);
-    const bool oneByOne = count == 1 || !batch_applies(c, sh);
-    const size_t most = oneByOne ? 1 : (count < chunk ? count : chunk); // images of the largest chunk
-    if ((r = c->stream.table.ensure(count * sizeof(StreamImage))) != limg_hip_success) return r;
-    if (most > 1)
-    { // everything a chunk needs, before the first launch: nothing is grown (and so freed) between the chunks of a list
-      if ((r = c->stream.fac.ensure(most * sh.planeStride * 3)) != limg_hip_success) return r;
-      if ((r = c->stream.units.ensure(most * sh.strips * 4)) != limg_hip_success) return r;
-      if ((r = c->enc.records.ensure(most * sh.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
-      if ((r = c->enc.shifts.ensure(most * sh.blocks * 4)) != limg_hip_success) return r;
-    }
-    std::vector<StreamImage> images(count);
-    for (size_t i = 0; i < count; i++) images[i].stream = ppStreams[i];
-    std::vector<ImageIO> table;
-    for (size_t i0 = 0; i0 < count && r == limg_hip_success;)
-    {
-      const size_t n = oneByOne ? 1 : (count - i0 < chunk ? count - i0 : chunk);
-      c->stats.accumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, as the plane batch
-      if (n == 1)
-      { // the single call (images with partial edge blocks, the split path, the float stage inside the encode kernel, a list or a last chunk of one image)
-        r = limg_hip_encode_stream_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, ppStreams[i0], capacityEach, nullptr, errorFactor, poolThreads, fastBitCrushing, stream);
-        if (r == limg_hip_success && pBytes && !oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], 1, s); // (for the sizes below)
-      }
-      else
-      {
-        table.assign(n, ImageIO{});
-        for (size_t i = 0; i < n; i++)
-        {
-          uint8_t *fac = (uint8_t *)c->stream.fac.p + i * 3 * sh.planeStride; // 256-byte aligned slices
-          table[i].in = ppIn[i0 + i];
-          table[i].info.pFactorsA = fac; table[i].info.pFactorsB = fac + sh.planeStride; table[i].info.pFactorsC = fac + 2 * sh.planeStride;
-          images[i0 + i].fac[0] = fac; images[i0 + i].fac[1] = fac + sh.planeStride; images[i0 + i].fac[2] = fac + 2 * sh.planeStride;
-        }
-        limg_hip_compact_out comp = { (limg_hip_block_record *)c->enc.records.p, (uint32_t *)c->enc.shifts.p };
-        EncodeExtra x;
-        x.batch = table.data(); x.batchCount = n;
-        x.streamRaw = true; x.stripWords = (uint32_t *)c->stream.units.p;
-        if ((r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, &table[0].info, &comp, errorFactor, poolThreads, fastBitCrushing, s, x)) != limg_hip_success) break;
-        launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], n, s);
-        StreamBatchParams b;
-        memset(&b, 0, sizeof(b));
-        b.sizeX = (uint32_t)sizeX; b.sizeY = (uint32_t)sizeY; b.blocksX = (uint32_t)sh.blocksX; b.blocksY = (uint32_t)sh.blocksY; b.nBlocks = (uint32_t)sh.blocks;
-        b.channels = hasAlpha ? 4 : 3; b.errorFactor = errorFactor; b.flags = stream_flags(c, fastBitCrushing);
-        b.stripsX = (uint32_t)sh.stripsX; b.imageStrips = (uint32_t)sh.strips; b.nImages = (uint32_t)n; b.nStrips = (uint32_t)(n * sh.strips);
-        b.nWaves = pack_waves(c, n * sh.strips); // as the single call -- for the whole chunk
-        b.images = (const StreamImage *)c->stream.table.p + i0;
-        b.records = comp.pRecords; b.shifts = comp.pShifts; b.stripWords = (uint32_t *)c->stream.units.p;
-        mark(c, s);
-        launch_stream_pack_batch(b, s);
-        mark(c, s); mark(c, s); mark(c, s);
-        const hipError_t launched = hipGetLastError();
-        if (launched != hipSuccess) { c->stats.accumulate = false; HIP_TRY(launched); }
-      }
-      i0 += n;
-    }
-    c->stats.accumulate = false;
-    if (r != limg_hip_success || !pBytes) return r;
-    // the sizes: gathered from the headers on the device
-    if ((r = c->stream.sizes.ensure(count * 8)) != limg_hip_success) return r;
-    if (oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p, images.data(), count, s);
-    launch_stream_gather_bytes((const StreamImage *)c->stream.table.p, count, (unsigned long long *)c->stream.sizes.p, s);
-    HIP_TRY(hipGetLastError());
-    return download_sizes(c->stream.sizes.p, count, pBytes, s);
+    return stream_list_device(c, true, count, ppIn, sizeX, sizeY, hasAlpha, ppStreams, capacityEach, pBytes, errorFactor, nullptr, poolThreads, fastBitCrushing, stream);
   }
 
   limg_hip_result limg_hip_encode_stream_batch(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
                                                uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, int poolThreads, int fastBitCrushing)
   {
-    const StreamShape sh(sizeX, sizeY);
-    limg_hip_result r;
-    if ((r = check_list(c, pBytes != nullptr, count, ppIn, ppStreams, sh, capacityEach, false)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    StagedList l;
-    if ((r = stage_list(c, sh, count, ppIn, l)) != limg_hip_success) return r;
-    if ((r = limg_hip_encode_stream_batch_device(c, count, l.in.data(), sizeX, sizeY, hasAlpha, l.streams.data(), l.slice, pBytes, errorFactor, poolThreads, fastBitCrushing,
-                                                 nullptr)) != limg_hip_success)
-      return r;
-    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], l.streams[i], pBytes[i], hipMemcpyDeviceToHost)); // totalBytes of each, not the capacity
-    return limg_hip_success;
+    return stream_list_host(c, true, count, ppIn, sizeX, sizeY, hasAlpha, ppStreams, capacityEach, pBytes, errorFactor, nullptr, poolThreads, fastBitCrushing);
+  }
+
+  // ... and each image at its own error factor: stream i = limg_hip_encode_stream_device of image i at pErrorFactors[i]
+  limg_hip_result limg_hip_encode_stream_batch_ef_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                         uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, const uint32_t *pErrorFactors, int poolThreads,
+                                                         int fastBitCrushing, void *stream)
+  {
+    return stream_list_device(c, pErrorFactors != nullptr, count, ppIn, sizeX, sizeY, hasAlpha, ppStreams, capacityEach, pBytes, 0, pErrorFactors, poolThreads, fastBitCrushing,
+                              stream);
+  }
+
+  limg_hip_result limg_hip_encode_stream_batch_ef(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                  uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, const uint32_t *pErrorFactors, int poolThreads,
+                                                  int fastBitCrushing)
+  {
+    return stream_list_host(c, pErrorFactors != nullptr, count, ppIn, sizeX, sizeY, hasAlpha, ppStreams, capacityEach, pBytes, 0, pErrorFactors, poolThreads, fastBitCrushing);
   }
 
   // ---- budgeted stream encode of a list: result i = limg_hip_encode_stream_budget_device of image i with pMaxBytes[i] (contract: include/limg_hip.h) ----
   // Chunk by chunk (the plane batch's rule): the records of the chunk from ONE k_fit_tpb grid, one search state and one counter per image, the whole chunk's searches
-  // as 1 + 2 x rate_max_probes launches and ONE wait; then one stream encode per distinct error factor the searches chose.
+  // as 1 + 2 x rate_max_probes launches and ONE wait; then the chunk's stream encode at the error factors the searches chose, as one list.
   limg_hip_result limg_hip_encode_stream_budget_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
                                                              uint8_t *const *ppStreams, size_t capacityEach, const size_t *pMaxBytes, uint32_t minErrorFactor,
                                                              uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults, void *stream)
@@ -454,9 +529,7 @@ extern "C"
     // no probe kernel (or nothing to share): the loop of single calls, which a chunk (or a last chunk) of one image takes too
     const size_t chunk = count == 1 || !rate_probe_applies(c, sh, fastBitCrushing) ? 1 : list_chunk(c, sh.blocks, sh.strips);
     std::vector<RateDevice> states;
-    std::vector<uint32_t> order; // the chunk's images sorted by the h their searches chose
-    std::vector<const uint32_t *> groupIn;
-    std::vector<uint8_t *> groupOut;
+    std::vector<uint32_t> efs; // the error factors the chunk's searches chose
     for (size_t i0 = 0; i0 < count;)
     {
       const size_t n = count - i0 < chunk ? count - i0 : chunk;
@@ -468,22 +541,16 @@ extern "C"
       // 1. + 2. the chunk's records and its searches
       states.resize(n);
       if ((r = run_searches(c, sh, ppIn + i0, pMaxBytes + i0, n, hLo, hHi, hasAlpha, poolThreads, (hipStream_t)stream, states.data())) != limg_hip_success) return r;
-      // 3. the final encodes: the thresholds are kernel arguments of the persistent kernel, so one (batched) stream encode per distinct h
-      order.resize(n);
-      for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return states[a].search.next < states[b].search.next; });
-      for (size_t g0 = 0; g0 < n;)
-      {
-        const uint32_t h = states[order[g0]].search.next;
-        size_t g1 = g0;
-        groupIn.clear(); groupOut.clear();
-        for (; g1 < n && states[order[g1]].search.next == h; g1++) { groupIn.push_back(ppIn[i0 + order[g1]]); groupOut.push_back(ppStreams[i0 + order[g1]]); }
-        if (g1 - g0 == 1) r = limg_hip_encode_stream_device(c, groupIn[0], sizeX, sizeY, hasAlpha, groupOut[0], capacityEach, nullptr, 2u * h, poolThreads, fastBitCrushing, stream);
-        else r = limg_hip_encode_stream_batch_device(c, g1 - g0, groupIn.data(), sizeX, sizeY, hasAlpha, groupOut.data(), capacityEach, nullptr, 2u * h, poolThreads,
-                                                     fastBitCrushing, stream);
-        if (r != limg_hip_success) return r;
-        g0 = g1;
-      }
+      // 3. the final encodes, in ONE launch pair + scan + pack whatever the searches chose: the chunk at the chosen factors, thresholds per image (where all chose
+      // the same value: the shared-factor batch, whose thresholds are kernel arguments)
+      efs.resize(n);
+      bool same = true;
+      for (size_t i = 0; i < n; i++) { efs[i] = 2u * states[i].search.next; same = same && efs[i] == efs[0]; }
+      // (the threshold table -- 32 bytes per image -- in the chunk's search states -- 72 per image --, which are on the host by now: no context memory of its own)
+      static_assert(sizeof(RatedImage) <= sizeof(RateDevice), "the threshold table fits the search states");
+      if ((r = stream_list_device(c, true, n, ppIn + i0, sizeX, sizeY, hasAlpha, ppStreams + i0, capacityEach, nullptr, efs[0], same ? nullptr : efs.data(), poolThreads,
+                                  fastBitCrushing, stream, (RatedImage *)c->stream.rateState.p)) != limg_hip_success)
+        return r;
       for (size_t i = 0; i < n; i++) // bytes: what the probe measured at the result -- the packer's totalBytes
         fill_result(pResults[i0 + i], 2u * states[i].search.next, states[i].search.probes, states[i].search.within, states[i].search.bestBytes);
       i0 += n;

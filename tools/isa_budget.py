@@ -90,7 +90,7 @@ def kernel_instructions(asm, kernel_substr):
             on = False
             continue
         if re.match(r"\s*\.loc\s", line):
-            frames = [(os.path.basename(f), int(l)) for f, l in re.findall(r"([A-Za-z_0-9./]+\.(?:hip|h)):(\d+):\d+", line)]
+            frames = [(os.path.basename(f), int(l)) for f, l in re.findall(r"([A-Za-z_0-9./]+\.(?:hip|h|inc)):(\d+):\d+", line)]
             continue
         m = re.match(r"\s+([a-z_0-9]+)(\s|$)", line)
         if not m or line.strip().startswith((".", ";")):
@@ -174,7 +174,7 @@ def main():
         ("F: row set-up, clamp + pack, stores (phase_f_rows)", [fn("phase_f_rows")]),
         ("F: lane == pixel pixels phase (ragged images only)", [fn("phase_f_pixels")]),
         ("F: strip load (park -> LDS), rest of dither_store_strip", [fn("dither_store_strip")]),
-        ("persistent loop (ticket, barriers)", [fn("k_encode_persistent")]),
+        ("persistent loop (ticket, barriers)", [fn("k_encode_persistent"), ("limg_hip_persistent_loop.inc", 1, 1 << 30)]),  # (the loop's text: included into the kernel)
     ]
     instrs = kernel_instructions(asm, "k_encode_persistentILi4ELb0ELb1ELb0E")
     acc, ops = budget(instrs, phases, "unattributed")
