@@ -38,6 +38,17 @@ namespace limg_hip
     return t;
   }
 
+  // The packed trial weights a pixel's squared differences (2, 4, 3) while dR^2 < 0x4000 and (3, 4, 2) otherwise (src/limg_bit_crush_simd.h; trial_pixel_error,
+  // limg_hip_search.h).  Below a pixel limit of 0x8000 the second form never decides anything, and a launch whose host knows the limit takes a trial without it:
+  //  * a pixel with dR^2 >= 0x4000 has the error 3 dR^2 + 4 dG^2 + 2 dB^2 >= 49152, and its first-form value 2 dR^2 + 4 dG^2 + 3 dB^2 is >= 32768: with
+  //    maxPixel32 <= 32767 it fails the pixel test (err > maxPixel32) under either form;
+  //  * a pixel with dR^2 < 0x4000 has the same value under both.
+  // So the pixel-failure ballot of a trial is the same; the block sum is only read where no pixel failed, i.e. where every pixel has dR^2 < 0x4000 and every
+  // summand is the same, so the sum verdict and every block error the accurate search compares are the same too.  The bound is tight: at a limit of 32768 the
+  // pixel (|dR|, |dG|, |dB|) = (128, 0, 0) passes under the first form (32768) and fails under the second (49152).  maxPixel32 = 42 * (errorFactor / 2) stays
+  // below 0x8000 exactly for errorFactor <= 1561 (1562: 32802).  tests/test_red_select_cpu.py walks all 256^3 difference triples.
+  LIMG_RULES_HD inline bool red_select_dead(uint32_t maxPixel32) { return maxPixel32 < 0x8000u; }
+
   // limg_hip_options.forced_shift -> the kernels' `forced`: the triple if all three are in 0..8, else {-1, -1, -1} (the shift search runs)
   LIMG_RULES_HD inline void forced_shifts(const int32_t forced_shift[3], int32_t forced[3])
   {

@@ -136,7 +136,7 @@ namespace limg_hip
     // Two parts stay INLINE here, measured (profiles/e_step_stages_ab.md): as functions of their own (float_stage_pixel, search_block) the lane == pixel float stage and
     // the search's set-up left the persistent kernel's lane == pixel instances with 11-46 more spilled SGPRs and 1.1-1.8 KB more code, `--legacy-float-stage` 5.3 %
     // slower, and four k_fit_search instances with 2-4 more VGPRs; either one alone as a function does the same.
-    template <int CH, bool PERSIST, bool FAST, bool PREFIT, bool ACC, class P, class LIM, class IO>
+    template <int CH, bool PERSIST, bool FAST, bool PREFIT, bool ACC, bool NOSEL, class P, class LIM, class IO>
     __device__ __forceinline__ void fit_search_strip(const P &p, const LIM &lim, const IO &io, const uint32_t id, const uint32_t local, const uint32_t rowBase, const uint32_t head0, uint8_t *lds,
                                                      uint8_t *park, const int tid)
     {
@@ -476,13 +476,13 @@ namespace limg_hip
             //  instructions per block)
             if (!ACC)
             {
-              if (n == 64) search_fast_automaton<true>(t, true, lim.maxPixel32, blockLimit, shift);
-              else search_fast_automaton<false>(t, active, lim.maxPixel32, blockLimit, shift);
+              if (n == 64) search_fast_automaton<true, NOSEL>(t, true, lim.maxPixel32, blockLimit, shift);
+              else search_fast_automaton<false, NOSEL>(t, active, lim.maxPixel32, blockLimit, shift);
             }
             else
             {
-              if (n == 64) search_accurate_automaton<true>(t, true, lim.maxPixel32, blockLimit, p.accTable, shift);
-              else search_accurate_automaton<false>(t, active, lim.maxPixel32, blockLimit, p.accTable, shift);
+              if (n == 64) search_accurate_automaton<true, NOSEL>(t, true, lim.maxPixel32, blockLimit, p.accTable, shift);
+              else search_accurate_automaton<false, NOSEL>(t, active, lim.maxPixel32, blockLimit, p.accTable, shift);
             }
           }
           else
@@ -631,11 +631,16 @@ namespace limg_hip
     }
 
     // ---- kernels ---------------------------------------------------------------------------------------------------------
+    // The trial's form (NOSEL: without the red-weight select, trial_pixel_error) follows from the launch's pixel limit by red_select_dead (limg_hip_encode_rules.h).
+    // The limit is a kernel argument of these kernels, so each instance holds its step for both forms and takes one of them with ONE scalar branch per workgroup, at
+    // the top of the kernel: nothing is decided per strip, block or trial, and inside either side the form is a template argument all the way down.  (Not a further
+    // template argument of the kernels: the set of kernel instances that take EncodeParams is pinned, tests/test_product_library.py.)
     template <int CH, bool FAST, bool PREFIT, bool ACC>
     __global__ __launch_bounds__(kThreads) void k_fit_search(const EncodeParams p)
     {
       __shared__ __attribute__((aligned(16))) uint8_t s_lds[lds_layout<PREFIT>().total];
-      fit_search_strip<CH, false, FAST, PREFIT, ACC>(p, p, p.io, blockIdx.x, blockIdx.x, 0u, 0u, s_lds, nullptr, (int)threadIdx.x);
+      if (red_select_dead(p.maxPixel32)) fit_search_strip<CH, false, FAST, PREFIT, ACC, true>(p, p, p.io, blockIdx.x, blockIdx.x, 0u, 0u, s_lds, nullptr, (int)threadIdx.x);
+      else fit_search_strip<CH, false, FAST, PREFIT, ACC, false>(p, p, p.io, blockIdx.x, blockIdx.x, 0u, 0u, s_lds, nullptr, (int)threadIdx.x);
     }
 
     template <int CH>
@@ -657,7 +662,7 @@ namespace limg_hip
     // drift apart, E and F steps of different workgroups overlap on every CU.
     // Progress: a look-back only waits for strips with smaller tickets; those were drawn earlier by workgroups that are running, and an E step never waits
     // (see "decoupled look-back" above: no strip id is ever derived from blockIdx).
-    // The loop itself: limg_hip_persistent_loop.inc, one text for this kernel and for k_encode_list_rated below.
+    // The loop itself: limg_hip_persistent_loop.inc, one text for this kernel -- once per form of the trial, see k_fit_search -- and for k_encode_list_rated below.
     template <int CH, bool FAST, bool PREFIT, bool ACC>
     __global__ __launch_bounds__(kThreads, PREFIT ? 6 : 5) void k_encode_persistent(const EncodeParams p)
     {
@@ -669,7 +674,16 @@ namespace limg_hip
       typedef const __attribute__((address_space(4))) ImageIO KernIO;
       auto io_of = [](KernArgs *a, uint32_t img) -> KernIO * { return a->batchCount > 1 ? (KernIO *)a->batch + img : &a->io; };
 #define LIMG_LOOP_LIMITS(a, img) (*(a)) /* one error factor: the limits are kernel arguments */
+      if (red_select_dead(p.maxPixel32))
+      {
+        constexpr bool NOSEL = true;
 #include "limg_hip_persistent_loop.inc"
+      }
+      else
+      {
+        constexpr bool NOSEL = false;
+#include "limg_hip_persistent_loop.inc"
+      }
 #undef LIMG_LOOP_LIMITS
     }
 
@@ -680,7 +694,7 @@ namespace limg_hip
     template <int CH, bool FAST>
     __global__ __launch_bounds__(kThreads, 6) void k_encode_list_rated(const RatedListParams p)
     {
-      constexpr bool PREFIT = true, ACC = false;
+      constexpr bool PREFIT = true, ACC = false, NOSEL = false; // (the limits differ from image to image, in device memory: the trial keeps its select)
       __shared__ __attribute__((aligned(16))) uint8_t s_lds[lds_layout<PREFIT>().total];
       __shared__ uint32_t s_ticket;
       typedef const __attribute__((address_space(4))) RatedListParams KernArgs;

@@ -1,7 +1,7 @@
 // limg_hip_persistent_loop.inc -- the persistent encode kernels' loop (limg_hip_kernels.hip), included as the BODY of k_encode_persistent and of k_encode_list_rated:
 // one text for both.  Not a function: called through one (the image's pointers and limits as callables) k_encode_persistent's instances came out with another
 // schedule than the one they were measured with; included, their code is instruction for instruction what it was when the loop stood in the kernel.
-// From the enclosing scope: CH, FAST, PREFIT, ACC; p (the kernel's parameter block); KernArgs (its type in the constant address space); s_lds, s_ticket;
+// From the enclosing scope: CH, FAST, PREFIT, ACC, NOSEL; p (the kernel's parameter block); KernArgs (its type in the constant address space); s_lds, s_ticket;
 // io_of(a, img): the caller's pointers of image `img` of the launch; LIMG_LOOP_LIMITS(a, img): where the E step's search takes its limits from.
       const int tid = (int)threadIdx.x;
       const uint32_t S = p.imageStrips * p.batchCount; // the strips of all images of a batch, image after image
@@ -35,7 +35,7 @@
         {
           if (pe->batchCount > 1) img = t / pe->imageStrips; // once per strip, on the scalar unit
           const uint32_t head0 = img * pe->imageStrips;
-          fit_search_strip<CH, true, FAST, PREFIT, ACC>(*pe, LIMG_LOOP_LIMITS(pe, img), *io_of(pe, img), t, t - head0, img * pe->blocksY, head0, s_lds, park + slot * kParkBytes, tid_e);
+          fit_search_strip<CH, true, FAST, PREFIT, ACC, NOSEL>(*pe, LIMG_LOOP_LIMITS(pe, img), *io_of(pe, img), t, t - head0, img * pe->blocksY, head0, s_lds, park + slot * kParkBytes, tid_e);
         }
         if (prev != 0xFFFFFFFFu)
         {

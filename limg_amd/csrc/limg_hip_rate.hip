@@ -124,7 +124,7 @@ namespace limg_hip
               t.mA[c] = tc[9 + c]; t.mB[c] = tc[12 + c]; t.mC[c] = tc[15 + c];
             }
             t.mA[0] += (int)(R << 8); t.mA[1] += (int)(G << 8); t.mA[2] += t.pxB << 8;
-            search_fast_automaton<true>(t, true, maxPixel32, blockLimit, shift);
+            search_fast_automaton<true, false>(t, true, maxPixel32, blockLimit, shift); // (the limits come from device memory: the trial keeps its red-weight select)
           }
           else
           { // a record out of the packed trial's range: the generic 32-bit search, as phase E

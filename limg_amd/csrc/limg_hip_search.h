@@ -27,7 +27,7 @@ namespace limg_hip
     //    16-bit number -- one plain 32-bit add3 then adds the halves independently -- and the biases sum to 0x8000: the sum is the difference in OFFSET BINARY, which
     //    unsigned v_pk_max / v_pk_min clamp correctly against bounds biased the same way, and whose square modulo 2^16 is the square of the difference itself
     //    ((e + 0x8000)^2 = e^2 + 0x10000 e + 2^30, |e| <= 255).  So the bias is never removed;
-    //  * the weighted squared error is one v_dot2_u32_u16, one select and one shift-add.
+    //  * the weighted squared error is one v_dot2_u32_u16, one select and one shift-add; without the select where the launch's pixel limit makes it dead (NOSEL).
     // Valid while every term stays inside (-0x2000, 0x2000): a term is (d * n + (min << 8) + 128) >> 8 with d <= 255 and n = max - min, so
     // |term| <= |min| + |n| + 1 <= 3 L + 1 when every record value is at most L in magnitude: L = p.recordLimit = 2700 (3 * 2700 + 1 = 8101 < 8192).  Then every
     // biased half lies in (0, 0x5100) and three of them sum to less than 65536 (no carry between the halves or out of the register).  A fit of byte pixels cannot
@@ -77,8 +77,9 @@ namespace limg_hip
       t.cC = sC;
     }
 
-    // the trial proper on the cached terms: clamp, differences, weighted squared error per pixel
-    template <bool FULL>
+    // the trial proper on the cached terms: clamp, differences, weighted squared error per pixel.  NOSEL: the form without the red-weight select, for launches whose
+    // pixel limit makes it dead (red_select_dead, limg_hip_encode_rules.h: same ballot, same sums); chosen per launch, a template argument all the way down
+    template <bool FULL, bool NOSEL>
     __device__ __forceinline__ uint32_t trial_pixel_error(const TrialState &t, const bool active)
     {
       const uint32_t dRG = t.tA_RG + t.tB_RG + t.tC_RG; // (R - estimate + 0x8000) | (G - estimate + 0x8000) << 16: no carry crosses the halves
@@ -89,12 +90,21 @@ namespace limg_hip
       int dB = med3_i32(dBraw, t.pxBlo, t.pxB); // clamp(px - S, px - 255, px)
       const ushort2_t sq = eu * eu; // (d + 0x8000)^2 mod 2^16 == d^2 <= 65025
       const uint32_t sqB = (uint32_t)mul_i24(dB, dB);
-      // weights (R, G, B) = (2, 4, 3) while dR^2 < 0x4000, else (3, 4, 2)  ==  2 * (dR^2 + 2 dG^2 + dB^2) + (dB^2 or dR^2): one dot product with constant weights,
-      // one select (the red square is picked out of the packed pair by the select's operand modifier), one shift-add
-      const bool low_red = sq.x < 0x4000;
-      const uint32_t half = __builtin_amdgcn_udot2(sq, __builtin_bit_cast(ushort2_t, 0x00020001u), sqB, false);
-      const uint32_t extra = low_red ? sqB : (__builtin_bit_cast(uint32_t, sq) & 0xFFFFu);
-      uint32_t err = (half << 1) + extra;
+      uint32_t err;
+      if constexpr (NOSEL)
+      { // weights (2, 4, 3) for every pixel: one dot product that also adds dB^2 once, one shift-add for the other two
+        const uint32_t h = __builtin_amdgcn_udot2(sq, __builtin_bit_cast(ushort2_t, 0x00040002u), sqB, false);
+        err = (sqB << 1) + h;
+      }
+      else
+      {
+        // weights (R, G, B) = (2, 4, 3) while dR^2 < 0x4000, else (3, 4, 2)  ==  2 * (dR^2 + 2 dG^2 + dB^2) + (dB^2 or dR^2): one dot product with constant
+        // weights, one select (the red square is picked out of the packed pair by the select's operand modifier), one shift-add
+        const bool low_red = sq.x < 0x4000;
+        const uint32_t half = __builtin_amdgcn_udot2(sq, __builtin_bit_cast(ushort2_t, 0x00020001u), sqB, false);
+        const uint32_t extra = low_red ? sqB : (__builtin_bit_cast(uint32_t, sq) & 0xFFFFu);
+        err = (half << 1) + extra;
+      }
       if (!FULL) err = active ? err : 0u;
       return err;
     }
@@ -149,10 +159,11 @@ namespace limg_hip
     // high word of the block sum's compare mask (wave_sum_below: lane 63's bit is its sign), opaque to the compiler behind the join.  A pixel failure is then its
     // branch over the sum plus the common sign test, a sum failure the sign test alone.  (asm goto would leave only the branches; this compiler drops the asm of
     // an asm goto on gfx950.)
+    template <bool NOSEL>
     __device__ __forceinline__ bool hot_trial(TrialState &t, const TermSet &A, const TermSet &B, const TermSet &C, const uint32_t maxPixel32, const uint32_t blockLimit)
     {
       t.tA_RG = A.rg; t.tA_B = A.b; t.tB_RG = B.rg; t.tB_B = B.b; t.tC_RG = C.rg; t.tC_B = C.b;
-      const uint32_t err = trial_pixel_error<true>(t, true);
+      const uint32_t err = trial_pixel_error<true, NOSEL>(t, true);
       uint32_t verdict = 0u;
       if (__builtin_amdgcn_ballot_w64(err > maxPixel32) == 0ull) verdict = wave_sum_below_mask(err, blockLimit); // be * 16 < maxBlock * n, see phase E
       asm("" : "+s"(verdict));
@@ -160,7 +171,7 @@ namespace limg_hip
     }
 #include "limg_search_hot.h"
 
-    template <bool FULL>
+    template <bool FULL, bool NOSEL>
     __device__ __forceinline__ void search_fast_automaton(TrialState &t, const bool active, const uint32_t maxPixel32, const uint32_t blockLimit, uint32_t shift[3])
     {
       const SearchEntry *tab = d_search_tab;
@@ -169,7 +180,7 @@ namespace limg_hip
       { // whole blocks: the generated hot subtree first; it ends the search itself or hands over the offset of the table entry to go on with (the state's three
         // sets are the cached ones, and the entry names its changes against exactly that triple)
         uint32_t off;
-        if (search_hot(t, maxPixel32, blockLimit, shift, off)) return;
+        if (search_hot<NOSEL>(t, maxPixel32, blockLimit, shift, off)) return;
         asm volatile("" : "+s"(tab)); // opaque: otherwise the address is rematerialised (s_getpc + 2 adds) in every iteration
         e = sload8(tab, off);
       }
@@ -190,7 +201,7 @@ namespace limg_hip
         if (e[0] & 0x20u) rebuild_A(t, e[0] & 31u, e[5]);
         if (e[0] & 0x40u) rebuild_B(t, e[3], e[6]);
         if (e[0] & 0x80u) rebuild_C(t, e[4], e[7]);
-        const uint32_t err = trial_pixel_error<FULL>(t, active);
+        const uint32_t err = trial_pixel_error<FULL, NOSEL>(t, active);
         // two tails on purpose: a pixel failure (the common way to fail) needs no outcome flag, no select and no block sum
         uint32_t off = e[2];
         if (__builtin_amdgcn_ballot_w64(err > maxPixel32) == 0ull)
@@ -207,7 +218,7 @@ namespace limg_hip
     // the block errors decide stays here: a passing phase-1 trial becomes the result; a passing phase-2 trial only if its error is below the best so far
     // (src/limg_bit_crush.h:774-826; `have` is always set by then).  A state has several predecessors, so the factors to rebuild come from comparing with the cached
     // shifts (t.cA..cC).
-    template <bool FULL>
+    template <bool FULL, bool NOSEL>
     __device__ __forceinline__ void search_accurate_automaton(TrialState &t, const bool active, const uint32_t maxPixel32, const uint32_t blockLimit, const uint32_t *table,
                                                               uint32_t shift[3])
     {
@@ -235,7 +246,7 @@ namespace limg_hip
         if (mask & 1u) rebuild_A(t, a, e[5]);
         if (mask & 2u) rebuild_B(t, e[3], e[6]);
         if (mask & 4u) rebuild_C(t, e[4], e[7]);
-        const uint32_t err = trial_pixel_error<FULL>(t, active);
+        const uint32_t err = trial_pixel_error<FULL, NOSEL>(t, active);
         uint32_t off = e[2];
         if (__builtin_amdgcn_ballot_w64(err > maxPixel32) == 0ull)
         {

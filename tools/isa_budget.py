@@ -75,8 +75,9 @@ def assemble(src):
     return out
 
 
-def kernel_instructions(asm, kernel_substr):
-    """[(opcode, [(file, line) frames innermost first])] of one kernel"""
+def kernel_instructions(asm, kernel_substr, labels=None, operands=None):
+    """[(opcode, [(file, line) frames innermost first])] of one kernel; `labels` (a dict) receives label -> index of the first instruction behind it, `operands`
+    (a list) the operand text of every instruction"""
     on = False
     frames = []
     out = []
@@ -92,11 +93,33 @@ def kernel_instructions(asm, kernel_substr):
         if re.match(r"\s*\.loc\s", line):
             frames = [(os.path.basename(f), int(l)) for f, l in re.findall(r"([A-Za-z_0-9./]+\.(?:hip|h|inc)):(\d+):\d+", line)]
             continue
+        if labels is not None and re.match(r"^\.LBB\w+:", line):
+            labels[line.split(":")[0]] = len(out)
+            continue
         m = re.match(r"\s+([a-z_0-9]+)(\s|$)", line)
         if not m or line.strip().startswith((".", ";")):
             continue
         out.append((m.group(1), frames))
+        if operands is not None:
+            operands.append(line.split(";")[0].strip()[len(m.group(1)):].strip())
     return out
+
+
+def one_trial_form(instrs, labels, operands):
+    """k_encode_persistent holds its loop twice, once per form of the trial (with and without the red-weight select: red_select_dead, limg_hip_encode_rules.h), and
+    picks one with the first scalar branch of the kernel, on the pixel limit against 0x7fff.  The two copies are contiguous in the assembly and the branch's target
+    label is where the second begins: -> (the instructions of the copy WITHOUT the select -- the headline's, with the few instructions in front of the branch --, the
+    other copy's count).  The copy without the select is told by its trials: v_dot2_u32_u16 with no v_cndmask_b32_sdwa."""
+    at = next(i for i, (op, _) in enumerate(instrs) if op.startswith("s_cmp") and operands[i].endswith("0x7fff"))
+    br = next(i for i in range(at, at + 8) if instrs[i][0].startswith("s_cbranch_scc"))
+    cut = labels[operands[br].split()[-1]]
+    assert cut > br, "the branch on the pixel limit goes forward"
+    parts = [instrs[:br + 1] + instrs[br + 1:cut], instrs[:br + 1] + instrs[cut:]]
+    sel = [sum(op == "v_cndmask_b32_sdwa" for op, _ in part) for part in parts]
+    dots = [sum(op == "v_dot2_u32_u16" for op, _ in part) for part in parts]
+    assert dots[0] == dots[1] and min(sel) * 4 < max(sel), (dots, sel)
+    keep = 0 if sel[0] < sel[1] else 1
+    return parts[keep], len(parts[1 - keep]) - (br + 1)
 
 
 def kind(op):
@@ -176,7 +199,11 @@ def main():
         ("F: strip load (park -> LDS), rest of dither_store_strip", [fn("dither_store_strip")]),
         ("persistent loop (ticket, barriers)", [fn("k_encode_persistent"), ("limg_hip_persistent_loop.inc", 1, 1 << 30)]),  # (the loop's text: included into the kernel)
     ]
-    instrs = kernel_instructions(asm, "k_encode_persistentILi4ELb0ELb1ELb0E")
+    labels, operands = {}, []
+    instrs = kernel_instructions(asm, "k_encode_persistentILi4ELb0ELb1ELb0E", labels, operands)
+    instrs, other_copy = one_trial_form(instrs, labels, operands)
+    print("The kernel holds its loop once per form of the trial; the table below is the copy the headline's pixel limit takes, without the red-weight select (%d instructions; the"
+          " other copy: %d).\n" % (len(instrs), other_copy))
     acc, ops = budget(instrs, phases, "unattributed")
     copies_trial = max(1, ops["search: trial core (a9)"]["v_dot2_u32_u16"])
     copies_rows = max(1, ops["F: dither + crushed bytes + decode terms (rows_factor)"]["v_add_u32_sdwa"] // 8)

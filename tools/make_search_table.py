@@ -459,7 +459,7 @@ def emit_hot(tree, K=HOT_K):
             F = "ABC"[f]
             out.append("%sconst TermSet %s = hot_terms<%du, %du>(t.f%s, t.n%s, t.m%s);" % (pad, var, s, MUL[s], F, F, F))
         use = [v if v is not None else const_set(f) for f, v in enumerate(node["use"])]
-        out.append("%sif (hot_trial(t, %s, %s, %s, maxPixel32, blockLimit))" % (pad, use[0], use[1], use[2]))
+        out.append("%sif (hot_trial<NOSEL>(t, %s, %s, %s, maxPixel32, blockLimit))" % (pad, use[0], use[1], use[2]))
         edge(node["edge"][True], node, ind)
         out.append("%selse" % pad)
         edge(node["edge"][False], node, ind)
@@ -470,11 +470,13 @@ def emit_hot(tree, K=HOT_K):
 // The hot subtree of the default shift search's decision automaton (limg_search_table.h) as nested straight-line code: %d states, %d term sets built, K = %s.
 // Per state the shift triple is static: a term set is a named variable, built with literal shift and multiplier only where no live variable holds it; then the
 // unchanged trial (hot_trial: trial core, pixel check, block sum).  An edge to a hot child continues inline, an edge to a final state yields its shifts, any other
-// edge leaves to the table loop with the successor's byte offset in `off` (the state's three sets are the cached ones in `t`).
+// edge leaves to the table loop with the successor's byte offset in `off` (the state's three sets are the cached ones in `t`).  NOSEL: the trial's form
+// (trial_pixel_error), passed through.
 // Included by limg_hip_search.h, inside namespace limg_hip::(anonymous), after the helpers it is built from.
 #ifndef LIMG_SEARCH_HOT_H
 #define LIMG_SEARCH_HOT_H
 #define LIMG_SEARCH_HOT_STATES %d
+template <bool NOSEL>
 __device__ __forceinline__ bool search_hot(TrialState &t, const uint32_t maxPixel32, const uint32_t blockLimit, uint32_t shift[3], uint32_t &off)
 {
 %s
