@@ -88,6 +88,14 @@ class Oracle:
         L.limg_oracle_blocked_matches.restype = C.c_int
         L.limg_oracle_blocked_matches.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
 
+        L.limg_oracle_set_event_sink.argtypes = [C.c_void_p]
+        L.limg_oracle_event_layout.restype = C.c_size_t
+        L.limg_oracle_event_layout.argtypes = [C.c_void_p]
+
+    def count_events(self):
+        """`with oracle.count_events() as ev:` -- the fits and factor calls made inside count into ev (an Events); the sink is off again afterwards."""
+        return Events(self)
+
     def config(self, error_factor=100, fast=True, float_mode=FLOAT_X86, dither_mode=DITHER_AES, pool_threads=0, worker_threads=1, forced_shift=None):
         cfg = Config()
         cfg.error_factor, cfg.fast_bit_crush, cfg.float_mode, cfg.dither_mode = error_factor, int(fast), float_mode, dither_mode
@@ -198,6 +206,65 @@ class Oracle:
     def photo_noise(self, w, h, seed=1):
         out = np.zeros((h, w), dtype=np.uint32)
         self.lib.limg_oracle_synth_photo_noise(_ptr(out), w, h, seed)
+        return out
+
+
+EV_CONTEXTS = ("whole", "partial", "tiny", "region")  # n == 64, 4 <= n < 64, n < 4, n > 64
+EV_PASS = ("skip", "flip", "noflip", "bias_decides")  # x pass 1..3
+EV_TIE_CLASSES = ("lt2", "2to8", "ge8")
+EV_SINGLE = ("dirA_zero_flat", "dirA_zero_nonflat", "dirB_zero", "dirC_zero", "dirC_nan", "rec_indefinite", "rec_tie",
+             "nzA_false", "nzB_false", "nzC_false", "fac_below", "fac_above", "fac_tie")
+
+
+class Events:
+    """The oracle's event sink (limg_oracle.h) as a context manager.  A counted event is a CELL, named "<event>/<context>/<channels>":
+    skip.p1 .. bias_decides.p3, tie.p<pass>.<min lane><max lane>.<class>, the EV_SINGLE names; the RSQRTPS table index and exponent counters are arrays."""
+
+    def __init__(self, oracle):
+        lay = (C.c_size_t * 8)()
+        oracle.lib.limg_oracle_event_layout(lay)
+        self.TIE, self.RSQ_INDEX, self.RSQ_EXP, self.FIT, self.CELL, total, contexts = list(lay)[:7]
+        assert contexts == len(EV_CONTEXTS) and total == contexts * 2 * self.CELL and self.CELL == self.FIT + len(EV_SINGLE), list(lay)
+        assert self.TIE == 3 * len(EV_PASS) and self.RSQ_INDEX == self.TIE + 144 and self.RSQ_EXP == self.RSQ_INDEX + 3 * 2048 and self.FIT == self.RSQ_EXP + 3 * 256
+        self.lib = oracle.lib
+        self.counters = np.zeros(total, dtype=np.uint64)
+
+    def __enter__(self):
+        self.lib.limg_oracle_set_event_sink(_ptr(self.counters))
+        return self
+
+    def __exit__(self, *exc):
+        self.lib.limg_oracle_set_event_sink(None)
+
+    def cell(self, context, channels):
+        i = (EV_CONTEXTS.index(context) * 2 + (channels == 4)) * self.CELL
+        return self.counters[i:i + self.CELL]
+
+    def rsq_index(self, context, channels, pass_=1):
+        return self.cell(context, channels)[self.RSQ_INDEX + (pass_ - 1) * 2048:self.RSQ_INDEX + pass_ * 2048]
+
+    def rsq_exp(self, context, channels, pass_=1):
+        return self.cell(context, channels)[self.RSQ_EXP + (pass_ - 1) * 256:self.RSQ_EXP + pass_ * 256]
+
+    def min_exponent(self, context, channels):
+        """the smallest biased exponent fed to RSQRTPS in any pass (None: no call)"""
+        e = self.cell(context, channels)[self.RSQ_EXP:self.RSQ_EXP + 3 * 256].reshape(3, 256).sum(axis=0)
+        return int(np.flatnonzero(e)[0]) if e.any() else None
+
+    def names(self):
+        """the names of one cell's scalar events, in counter order (the index and exponent arrays left out) -> [(name, offset)]"""
+        out = [("%s.p%d" % (e, p + 1), 3 * k + p) for k, e in enumerate(EV_PASS) for p in range(3)]
+        out += [("tie.p%d.%d%d.%s" % (p + 1, a, b, c), self.TIE + ((p * 4 + a) * 4 + b) * 3 + k) for p in range(3) for a in range(4) for b in range(4)
+                for k, c in enumerate(EV_TIE_CLASSES)]
+        return out + [(e, self.FIT + k) for k, e in enumerate(EV_SINGLE)]
+
+    def cells(self):
+        """{"<event>/<context>/<channels>": count} of every scalar event counted at least once"""
+        out = {}
+        for ctx in EV_CONTEXTS:
+            for ch in (3, 4):
+                c = self.cell(ctx, ch)
+                out.update({"%s/%s/%d" % (name, ctx, ch): int(c[o]) for name, o in self.names() if c[o]})
         return out
 
 

@@ -46,6 +46,42 @@ static inline int32_t cvtps(float x)
   return (int32_t)lrintf(x);
 }
 
+/* ------------------------------------------------------------------------------------------------------------------ */
+/* event sink (limg_oracle.h): counts only, reads what the functions below compute anyway */
+static uint64_t *g_event_sink = NULL;
+
+void limg_oracle_set_event_sink(uint64_t *counters) { __atomic_store_n(&g_event_sink, counters, __ATOMIC_SEQ_CST); }
+
+size_t limg_oracle_event_layout(size_t out[8])
+{
+  out[0] = LIMG_ORACLE_EV_TIE; out[1] = LIMG_ORACLE_EV_RSQ_INDEX; out[2] = LIMG_ORACLE_EV_RSQ_EXP; out[3] = LIMG_ORACLE_EV_FIT;
+  out[4] = LIMG_ORACLE_EV_CELL; out[5] = LIMG_ORACLE_EV_TOTAL; out[6] = LIMG_ORACLE_EV_CONTEXTS; out[7] = 0;
+  return 8;
+}
+
+/* the (context, channels) cell of a fit over n pixels, NULL when the sink is off */
+static inline uint64_t *ev_cell(size_t n, int channels)
+{
+  uint64_t *sink = __atomic_load_n(&g_event_sink, __ATOMIC_RELAXED);
+  if (!sink) return NULL;
+  const int ctx = n == 64 ? LIMG_ORACLE_EV_CTX_WHOLE : (n > 64 ? LIMG_ORACLE_EV_CTX_REGION : (n < 4 ? LIMG_ORACLE_EV_CTX_TINY : LIMG_ORACLE_EV_CTX_PARTIAL));
+  return sink + (size_t)(ctx * 2 + (channels == 4)) * LIMG_ORACLE_EV_CELL;
+}
+
+static inline void ev_add(uint64_t *ev, int event) { __atomic_fetch_add(&ev[event], 1, __ATOMIC_RELAXED); }
+
+/* cvtps of a record field / a factor, counted: `indefinite` may be -1 (not counted) */
+static inline int32_t cvtps_ev(float x, uint64_t *ev, int indefinite, int tie)
+{
+  const int32_t r = cvtps(x);
+  if (ev)
+  {
+    if (r == INT32_MIN) { if (indefinite >= 0) ev_add(ev, indefinite); }
+    else if (x - floorf(x) == 0.5f) ev_add(ev, tie);
+  }
+  return r;
+}
+
 /* DPPS with mask 0xFF (4 ch) / 0x7F (3 ch): (x0y0 + x1y1) + (x2y2 + x3y3), products rounded individually */
 static inline float dpps(const float a[4], const float b[4], int channels)
 {
@@ -62,10 +98,13 @@ static inline void px_to_float(uint32_t px, float out[4])
 /* The "sign-normalised unit vector" step shared by all direction passes
  * (src/limg_factorization.h:411-428 / 605-623 and the two analogous blocks per function).
  * Returns 0 when every lane of d is zero (pixel skipped). */
-static int unit_contribution(const float d[4], int channels, float out[4])
+static int unit_contribution(const float d[4], int channels, float out[4], uint64_t *ev, int pass)
 {
   if (d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f && d[3] == 0.0f)
+  {
+    if (ev) ev_add(ev, LIMG_ORACLE_EV_SKIP + pass);
     return 0;
+  }
   /* preferenceBias = _mm_set_ps(0, 1e, 2e, 3e): lane0 = 3*eps ... lane3 = 0 (:393 / :589) */
   static const float bias[4] = { FLT_EPSILON * 3, FLT_EPSILON * 2, FLT_EPSILON * 1, 0.0f };
   float mb[4], xb[4];
@@ -74,8 +113,28 @@ static int unit_contribution(const float d[4], int channels, float out[4])
   const float half_max0 = maxps(xb[0], xb[2]), half_max1 = maxps(xb[1], xb[3]);
   const float abs_min = fabsf(minps(half_min0, half_min1));
   const float mx = maxps(half_max0, half_max1);
-  float inv = limg_oracle_rsqrt_x86(dpps(d, d, channels));
+  const float dd = dpps(d, d, channels);
+  float inv = limg_oracle_rsqrt_x86(dd);
   if (abs_min > mx) inv = u2f(f2u(inv) ^ 0x80000000u);
+  if (ev)
+  {
+    const int flip = abs_min > mx;
+    const float m = minps(minps(d[0], d[2]), minps(d[1], d[3])), M = maxps(maxps(d[0], d[2]), maxps(d[1], d[3]));
+    ev_add(ev, (flip ? LIMG_ORACLE_EV_FLIP : LIMG_ORACLE_EV_NOFLIP) + pass);
+    if ((fabsf(m) > M) != flip) ev_add(ev, LIMG_ORACLE_EV_BIAS_DECIDES + pass);
+    if (-m == M)
+    {
+      int lm = -1, lM = -1;
+      for (int i = 3; i >= 0; i--) { if (d[i] == m) lm = i; if (d[i] == M) lM = i; }
+      if (lm >= 0 && lM >= 0) ev_add(ev, LIMG_ORACLE_EV_TIE + ((pass * 4 + lm) * 4 + lM) * 3 + (M < 2.0f ? 0 : (M < 8.0f ? 1 : 2)));
+    }
+    if (dd == dd)
+    {
+      const uint32_t b = f2u(dd);
+      ev_add(ev, LIMG_ORACLE_EV_RSQ_INDEX + pass * 2048 + (int)((((b >> 23) & 1) ? 0u : 1024u) + ((b >> 13) & 0x3FFu)));
+      ev_add(ev, LIMG_ORACLE_EV_RSQ_EXP + pass * 256 + (int)((b >> 23) & 0xFF));
+    }
+  }
   for (int i = 0; i < 4; i++) out[i] = d[i] * inv;
   return 1;
 }
@@ -139,6 +198,8 @@ void limg_oracle_block_fit_gathered(const uint32_t *px, size_t n, size_t sum_n, 
   int *valid = (int *)malloc(cap * sizeof(int));
   float dirA[4] = { 0, 0, 0, 0 }, dirB[4] = { 0, 0, 0, 0 }, dirC[4] = { 0, 0, 0, 0 };
   float minA = 0, maxA = 0, minB = 0, maxB = 0, minC = 0, maxC = 0;
+  uint64_t *ev = ev_cell(n, channels);
+  int contributed = 0;
 
   for (size_t i = 0; i < n; i++) px_to_float(px[i], pxf[i]);
 
@@ -148,7 +209,8 @@ void limg_oracle_block_fit_gathered(const uint32_t *px, size_t n, size_t sum_n, 
     float d[4];
     for (int c = 0; c < 4; c++) d[c] = pxf[i][c] - avg[c];
     if (channels == 3) d[3] = 0.0f; /* zero_alpha */
-    valid[i] = unit_contribution(d, channels, contrib[i]);
+    valid[i] = unit_contribution(d, channels, contrib[i], ev, 0);
+    contributed |= valid[i];
   }
   sum_contributions(contrib, valid, n, float_mode, dirA);
   for (int c = 0; c < 4; c++) dirA[c] = dirA[c] * inv_count;
@@ -167,7 +229,7 @@ void limg_oracle_block_fit_gathered(const uint32_t *px, size_t n, size_t sum_n, 
       maxA = maxps(maxA, fA);
       for (int c = 0; c < 4; c++) { est[i][c] = avg[c] + fA * dirA[c]; e[c] = pxf[i][c] - est[i][c]; }
       if (channels == 3) e[3] = 0.0f;
-      valid[i] = unit_contribution(e, channels, contrib[i]);
+      valid[i] = unit_contribution(e, channels, contrib[i], ev, 1);
     }
     sum_contributions(contrib, valid, n, float_mode, dirB);
     for (int c = 0; c < 4; c++) dirB[c] = dirB[c] * inv_count;
@@ -188,7 +250,7 @@ void limg_oracle_block_fit_gathered(const uint32_t *px, size_t n, size_t sum_n, 
         minB = minps(minB, fB);
         maxB = maxps(maxB, fB);
         for (int c = 0; c < 4; c++) { est[i][c] = est[i][c] + fB * dirB[c]; e[c] = pxf[i][c] - est[i][c]; }
-        valid[i] = unit_contribution(e, 4, contrib[i]);
+        valid[i] = unit_contribution(e, 4, contrib[i], ev, 2);
       }
       sum_contributions(contrib, valid, n, float_mode, dirC);
       for (int c = 0; c < 4; c++) dirC[c] = dirC[c] * inv_count;
@@ -233,19 +295,46 @@ void limg_oracle_block_fit_gathered(const uint32_t *px, size_t n, size_t sum_n, 
     }
   }
 
+  if (ev)
+  {
+    const int zA = dirA[0] == 0.0f && dirA[1] == 0.0f && dirA[2] == 0.0f && dirA[3] == 0.0f;
+    const int zB = dirB[0] == 0.0f && dirB[1] == 0.0f && dirB[2] == 0.0f && dirB[3] == 0.0f;
+    const int zC = dirC[0] == 0.0f && dirC[1] == 0.0f && dirC[2] == 0.0f && dirC[3] == 0.0f;
+    int nanC = 0;
+    for (int c = 0; c < channels; c++) nanC |= dirC[c] != dirC[c];
+    if (zA) ev_add(ev, contributed ? LIMG_ORACLE_EV_DIRA_ZERO_NONFLAT : LIMG_ORACLE_EV_DIRA_ZERO_FLAT);
+    else
+    {
+      if (zB) ev_add(ev, LIMG_ORACLE_EV_DIRB_ZERO);
+      else if (zC) ev_add(ev, LIMG_ORACLE_EV_DIRC_ZERO);
+      if (nanC) ev_add(ev, LIMG_ORACLE_EV_DIRC_NAN);
+    }
+  }
+
   /* :764-790 / :545-575 -- cvtps2dq then truncation to int16 */
   memset(out, 0, sizeof(*out));
   for (int c = 0; c < channels; c++)
   {
+    const int ind = LIMG_ORACLE_EV_REC_INDEFINITE, tie = LIMG_ORACLE_EV_REC_TIE;
     out->avg[c] = avg[c];
-    out->dirA_min[c] = (int16_t)cvtps(avg[c] + minA * dirA[c]);
-    out->dirA_max[c] = (int16_t)cvtps(avg[c] + maxA * dirA[c]);
-    out->dirB_offset[c] = (int16_t)cvtps(minB * dirB[c]);
-    out->dirB_mag[c] = (int16_t)cvtps(maxB * dirB[c]);
-    out->dirC_offset[c] = (int16_t)cvtps(minC * dirC[c]);
-    out->dirC_mag[c] = (int16_t)cvtps(maxC * dirC[c]);
+    out->dirA_min[c] = (int16_t)cvtps_ev(avg[c] + minA * dirA[c], ev, ind, tie);
+    out->dirA_max[c] = (int16_t)cvtps_ev(avg[c] + maxA * dirA[c], ev, ind, tie);
+    out->dirB_offset[c] = (int16_t)cvtps_ev(minB * dirB[c], ev, ind, tie);
+    out->dirB_mag[c] = (int16_t)cvtps_ev(maxB * dirB[c], ev, ind, tie);
+    out->dirC_offset[c] = (int16_t)cvtps_ev(minC * dirC[c], ev, ind, tie);
+    out->dirC_mag[c] = (int16_t)cvtps_ev(maxC * dirC[c], ev, ind, tie);
   }
   free(contrib); free(pxf); free(est); free(valid);
+}
+
+/* cvtps2dq of 255 f, then the clamp to a byte (src/limg_factorization.h:176,185,194 / :126,135,144) */
+static inline uint8_t factor_byte(float f, uint64_t *ev)
+{
+  int32_t q = cvtps_ev(255.0f * f, ev, -1, LIMG_ORACLE_EV_FAC_TIE);
+  if (ev && q < 0) ev_add(ev, LIMG_ORACLE_EV_FAC_BELOW);
+  if (ev && q > 0xFF) ev_add(ev, LIMG_ORACLE_EV_FAC_ABOVE);
+  q = q < 0xFF ? q : 0xFF; q = q > 0 ? q : 0;
+  return (uint8_t)q;
 }
 
 /* a7: src/limg_internal.h:426-452;  a8: src/limg_factorization.h:149-197 (4 ch) / :98-147 (3 ch) */
@@ -262,6 +351,13 @@ void limg_oracle_block_factors(const uint32_t *px, size_t n, int channels, const
     nzA |= nA[c] != 0; nzB |= nB[c] != 0; nzC |= nC[c] != 0;
     mnA[c] = (float)rec->dirA_min[c]; ofB[c] = (float)rec->dirB_offset[c]; ofC[c] = (float)rec->dirC_offset[c];
   }
+  uint64_t *ev = ev_cell(n, channels);
+  if (ev)
+  {
+    if (!nzA) ev_add(ev, LIMG_ORACLE_EV_NZA_FALSE);
+    if (!nzB) ev_add(ev, LIMG_ORACLE_EV_NZB_FALSE);
+    if (!nzC) ev_add(ev, LIMG_ORACLE_EV_NZC_FALSE);
+  }
   /* limg_dot: serial ((0 + n0*n0) + n1*n1) + ... (src/limg_internal.h:357-366) */
   float invA = 0, invB = 0, invC = 0;
   if (nzA) { float s = 0; for (int c = 0; c < channels; c++) s += nA[c] * nA[c]; invA = 1.0f / s; }
@@ -274,16 +370,13 @@ void limg_oracle_block_factors(const uint32_t *px, size_t n, int channels, const
     px_to_float(px[i], col);
     for (int c = 0; c < 4; c++) t[c] = col[c] - mnA[c];
     const float fa = dpps(t, nA, channels) * invA;
-    int32_t q = cvtps(255.0f * fa); q = q < 0xFF ? q : 0xFF; q = q > 0 ? q : 0;
-    A[i] = (uint8_t)q;
+    A[i] = factor_byte(fa, ev);
     for (int c = 0; c < 4; c++) { est[c] = mnA[c] + nA[c] * fa; t[c] = (col[c] - est[c]) - ofB[c]; }
     const float fb = dpps(t, nB, channels) * invB;
-    q = cvtps(255.0f * fb); q = q < 0xFF ? q : 0xFF; q = q > 0 ? q : 0;
-    B[i] = (uint8_t)q;
+    B[i] = factor_byte(fb, ev);
     for (int c = 0; c < 4; c++) { est[c] = est[c] + nB[c] * fb; t[c] = (col[c] - est[c]) - ofC[c]; }
     const float fc = dpps(t, nC, channels) * invC;
-    q = cvtps(255.0f * fc); q = q < 0xFF ? q : 0xFF; q = q > 0 ? q : 0;
-    C[i] = (uint8_t)q;
+    C[i] = factor_byte(fc, ev);
   }
 }
 

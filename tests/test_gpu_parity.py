@@ -9,6 +9,7 @@ import pytest
 
 import golden_util as gu
 import lib_axis as L
+from float_edge_inputs import degenerate_blocks_image
 from lib_axis import lib, lib_product  # noqa: F401  (fixtures: "test" / "product")
 from oracle.bind import PLANES, REC_DTYPE
 
@@ -260,17 +261,7 @@ def test_generic_trial_path(gpu, oracle, alpha, fast, limit):
 
 def test_degenerate_blocks(gpu, oracle):
     """flat blocks (dirA == 0), single-line blocks (dirB == 0), planes (dirC noise), extreme values."""
-    img = np.zeros((16, 256), dtype=np.uint32)
-    img[:, :] = 0xFF804020
-    x = np.arange(256, dtype=np.uint32)[None, :]
-    y = np.arange(16, dtype=np.uint32)[:, None]
-    img[0:8, 8:16] = ((10 + 20 * (x[:, 8:16] - 8)) | ((200 - 10 * (x[:, 8:16] - 8)) << 8) | ((50 + 5 * (x[:, 8:16] - 8)) << 16) | (255 << 24))
-    img[0:8, 16:24] = ((10 + 20 * (x[:, 16:24] - 16)) | ((30 + 25 * y[0:8]) << 8) | ((50 + 5 * (x[:, 16:24] - 16) + 3 * y[0:8]) << 16) | (255 << 24)).astype(np.uint32)
-    img[0:8, 24:32] = 0
-    img[0:8, 32:40] = 0xFFFFFFFF
-    img[0:8, 40:48] = np.where((x[:, 40:48] + y[0:8]) % 2 == 0, 0, 0xFFFFFFFF).astype(np.uint32)
-    rng = np.random.default_rng(3)
-    img[8:16, :] = rng.integers(0, 2**32, (8, 256), dtype=np.uint32)
+    img = degenerate_blocks_image()
     for alpha in (True, False):
         _assert_planes(gpu.encode3d(img, alpha), oracle.encode3d(img, alpha), alpha)
 
