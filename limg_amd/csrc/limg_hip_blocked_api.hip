@@ -415,7 +415,7 @@ namespace limg_hip
                                         uint32_t errorFactor, int fastBitCrushing, hipStream_t stream)
   {
     const limg_hip_blocked_encode3d_info noPlanes = {};
-    if (sizeX == 0 || sizeY == 0 || sizeX > 0x7FFFFFF8ull || sizeY > 0x7FFFFFF8ull || sizeX * sizeY > 0x60000000ull) return limg_hip_error_InvalidParameter;
+    if (!EncodeShape(sizeX, sizeY).valid || sizeX * sizeY > 0x60000000ull) return limg_hip_error_InvalidParameter;
     HIP_TRY(hipSetDevice(c->device));
     const clk::time_point t0 = clk::now();
     BlockedJob j; limg_hip_result r;

@@ -4,6 +4,7 @@
 #define LIMG_HIP_CONTEXT_H
 
 #include "limg_hip_internal.h"
+#include "limg_hip_encode_plan.h"
 #include "limg_hip_owned.h"
 #ifdef LIMG_HIP_TEST_HOOKS
 #include "../../include/limg_hip_test_hooks.h"
@@ -185,6 +186,19 @@ namespace limg_hip
 
   // ---- profiling (limg_hip_api.hip) ----
   void mark(limg_hip_context *c, hipStream_t stream);
+  // limg_hip_profile_end reads the events in groups of four, so whatever brackets its kernels records a fixed number of them -- its quota (an encode:
+  // EncodePlan::marks; a packer or decoder: 4).  mark() records one at each real boundary while the quota lasts; close() records what is left of it where the
+  // stream stands.  More than the quota cannot be recorded, and a closed timeline has recorded exactly its quota.
+  class Timeline
+  {
+    limg_hip_context *c;
+    hipStream_t stream;
+    int left;
+  public:
+    Timeline(limg_hip_context *c, hipStream_t stream, int quota) : c(c), stream(stream), left(quota) {}
+    void mark() { if (left > 0) { left--; limg_hip::mark(c, stream); } }
+    void close() { while (left > 0) mark(); }
+  };
 
   // work(0) .. work(n - 1), each on a host thread of its own where the host lets us start one.  A thread that cannot be created (EAGAIN under a pid / thread limit) or a
   // pool that cannot be allocated must neither leave joinable threads behind (their destructor calls std::terminate) nor send an exception across the extern "C"
@@ -240,9 +254,8 @@ namespace limg_hip
   // version 2's one decode, the full image's and a window's: wp from window_params
   limg_hip_result blocked_window_decode(limg_hip_context *c, WindowDecodeParams &wp, hipStream_t s);
 
-  // ---- the 8x8 encode (limg_hip_encode.hip, limg_hip_encode_ragged.hip) ----
-  struct Partition { uint32_t chainCount, chainRows; };
-  Partition partition(size_t sizeY, int poolThreads); // src/limg.cpp:2114-2134 in block rows
+  // ---- the 8x8 encode (limg_hip_encode.hip, limg_hip_encode_ragged.hip; its decisions: limg_hip_encode_plan.h) ----
+  static_assert(kShapeBlock == (size_t)kBlock && kShapeStripBlocks == (size_t)kStripBlocks, "limg_hip_encode_plan.h counts the kernels' blocks and strips");
 
   // What the public entries add to the plain (single image, whole encode) call.
   struct EncodeExtra
@@ -268,7 +281,7 @@ namespace limg_hip
     RatedImage *ratedTable = nullptr;
     // ---- a sub-image of a larger encode (the two parts of an image whose last block row is partial: encode_height_ragged) ----
     bool inner = false;            // part of a larger encode: no statistics launch of its own, no reset of the context's chain / statistics state
-    int marks = 2;                 // profiling events: 2 = all four, 1 = all but the last, 0 = none
+    bool innerLast = false;        // ... its last block row: no profiling event (the rows above record three, the whole call the fourth)
     const Partition *part = nullptr; // the dither-chain partition of the WHOLE image (a sub-image cannot derive it from its own height)
     size_t scratchRow0 = 0;        // this sub-image's first block row in the per-block scratch (and in the caller's compact outputs)
     size_t scratchRows = 0;        // block rows the scratch must hold (0: this call's own)
@@ -286,15 +299,14 @@ namespace limg_hip
     const EncodeExtra &x;
     const limg_hip_encode3d_info *dInfo;
     size_t sizeX, sizeY;
+    const EncodePlan &plan;
+    Timeline tl; // the path marks its real boundaries, encode_device closes it
     EncodeParams p;
     Partition pt;
     int channels;
-    bool ragged, fullPlanes, fused, wantStats;
     size_t blocks, strips; // of all images of the launch
     const RatedImage *rated = nullptr; // x.errorFactors as the device's threshold table: the persistent launches are k_encode_list_rated's
-    void mark_if(int level) const { if (x.marks >= level) mark(c, stream); } // profiling events: x.marks says which of an encode's four this call records
   };
-  limg_hip_result encode_stats(const EncodeJob &e);
   // images with partial edge blocks (limg_hip_encode_ragged.hip): the split path's kernels around a dither chain the host walks
   limg_hip_result encode_ragged(EncodeJob &e);
 

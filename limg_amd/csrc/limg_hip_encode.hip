@@ -1,49 +1,30 @@
 // limg_hip_encode.hip -- the 8x8 encode: its parameters, the launch paths of an image of whole blocks (fused, sub-batch pipeline, chain phases, split) and the
-// dispatcher that picks one (encode_device); the *_device, batch, chain and stats entries of the C ABI.  Images with partial edge blocks: limg_hip_encode_ragged.hip.
-// Mirrors the reference's driver (src/limg.cpp:2175-2265 threshold/flag setup, :2105-2138 strip partition).
+// dispatcher that runs the one the plan names (encode_device; the decisions: limg_hip_encode_plan.h); the *_device, batch, chain and stats entries of the C ABI.
+// Images with partial edge blocks: limg_hip_encode_ragged.hip.  Mirrors the reference's driver (src/limg.cpp:2175-2265 threshold/flag setup).
 #include "limg_hip_context.h"
 #include "limg_search_table_accurate.h"
 
 using namespace limg_hip;
 
-namespace limg_hip
-{
-  // src/limg.cpp:2114-2134 in block rows
-  Partition partition(size_t sizeY, int poolThreads)
-  {
-    Partition pt = { 1, 0 };
-    if (poolThreads <= 0) return pt;
-    size_t thread_count = (size_t)poolThreads * 4;
-    size_t y_range = ((sizeY / kBlock) / thread_count) * kBlock;
-    if (y_range == 0)
-    {
-      thread_count = (size_t)poolThreads;
-      y_range = ((sizeY / kBlock) / thread_count) * kBlock;
-    }
-    if (y_range == 0) return pt; // every strip but the last is empty
-    pt.chainCount = (uint32_t)thread_count;
-    pt.chainRows = (uint32_t)(y_range / kBlock);
-    return pt;
-  }
-
-  // the reference's "Average Block Bits" counters (src/limg.cpp:1971-1999) of this encode, left on the device for limg_hip_last_stats
-  limg_hip_result encode_stats(const EncodeJob &e)
-  {
-    limg_hip_context *const c = e.c;
-    const EncodeParams &p = e.p;
-    if (!e.wantStats || e.x.inner) return limg_hip_success;
-    limg_hip_result rs;
-    if ((rs = c->stats.counters.ensure(30 * 8)) != limg_hip_success) return rs;
-    if (!c->stats.accumulate) HIP_TRY(hipMemsetAsync(c->stats.counters.p, 0, 30 * 8, e.stream));
-    launch_shift_stats(p.shifts, p.blocksX, p.blocksY, p.blocksY * p.batchCount, p.sizeX, p.sizeY, (unsigned long long *)c->stats.counters.p, e.stream);
-    c->stats.stream = e.stream; c->stats.state = 1;
-    c->stats.pixels = (c->stats.accumulate ? c->stats.pixels : 0) + (uint64_t)e.sizeX * e.sizeY * e.x.batchCount;
-    return limg_hip_success;
-  }
-}
-
 namespace
 {
+  // the reference's "Average Block Bits" counters (src/limg.cpp:1971-1999) of this encode, left on the device for limg_hip_last_stats
+  limg_hip_result encode_stats(const EncodeJob &e, const limg_hip_compact_out *compact)
+  {
+    limg_hip_context *const c = e.c;
+    if (!e.plan.wantStats || e.x.inner) return limg_hip_success;
+    const EncodeShape sh(e.sizeX, e.sizeY);
+    const bool add = c->stats.accumulate && e.plan.path != kPathHeightRagged; // (an image of that path restarts the counters of a list)
+    const uint32_t *shifts = (compact && compact->pShifts) ? compact->pShifts : (const uint32_t *)c->enc.shifts.p;
+    limg_hip_result rs;
+    if ((rs = c->stats.counters.ensure(30 * 8)) != limg_hip_success) return rs;
+    if (!add) HIP_TRY(hipMemsetAsync(c->stats.counters.p, 0, 30 * 8, e.stream));
+    launch_shift_stats(shifts, (uint32_t)sh.blocksX, (uint32_t)sh.blocksY, (uint32_t)(sh.blocksY * e.x.batchCount), (uint32_t)e.sizeX, (uint32_t)e.sizeY, (unsigned long long *)c->stats.counters.p, e.stream);
+    c->stats.stream = e.stream; c->stats.state = 1;
+    c->stats.pixels = (add ? c->stats.pixels : 0) + (uint64_t)e.sizeX * e.sizeY * e.x.batchCount;
+    return limg_hip_success;
+  }
+
   // The accurate search's automaton (tools/make_search_table.py, src/limg_bit_crush.h:668-830) in the form the kernel's scalar loads want: 8 dwords per state,
   // every field in a dword of its own = { a | phase2 << 5 | final << 31, byte offset on pass, byte offset on fail, b, c, mul(a), mul(b), mul(c) }.  Bits 24..26 of the two
   // offsets say which factors' shifts the SUCCESSOR's triple changes against this state's (A, B, C): a state of this DAG has several predecessors, so the change mask is a
@@ -84,25 +65,22 @@ namespace
     return limg_hip_success;
   }
 
-  limg_hip_result encode_height_ragged(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *dInfo,
-                                       const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast, hipStream_t stream, const EncodeExtra &x);
-
-  // The whole 8x8 encode's EncodeParams: geometry, thresholds and flags, the per-block / per-strip scratch, the vector-access flags, the batch table and the noise
-  // table; then the chain-phase arguments and which kernels apply (e.fused, p.prefit).
-  limg_hip_result encode_params(EncodeJob &e, const uint32_t *dIn, const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast)
+  // The whole 8x8 encode's EncodeParams: geometry, thresholds and flags as the plan has them, the per-block / per-strip scratch, the vector-access flags, the batch
+  // table, the noise table and the chain-phase arguments.  It fills and allocates; it decides nothing.
+  limg_hip_result encode_params(EncodeJob &e, const uint32_t *dIn, const limg_hip_compact_out *compact, uint32_t errorFactor, int fast)
   {
     limg_hip_context *const c = e.c;
     const EncodeExtra &x = e.x;
+    const EncodePlan &plan = e.plan;
     const limg_hip_encode3d_info *const dInfo = e.dInfo;
-    const size_t sizeX = e.sizeX, sizeY = e.sizeY, batchCount = x.batchCount;
+    const size_t sizeX = e.sizeX, batchCount = x.batchCount;
     const ImageIO *const batch = x.batch;
+    const EncodeShape sh(sizeX, e.sizeY);
     EncodeParams &p = e.p;
     memset(&p, 0, sizeof(p));
     p.io.in = dIn;
-    p.sizeX = (uint32_t)sizeX; p.sizeY = (uint32_t)sizeY;
-    p.blocksX = (uint32_t)((sizeX + kBlock - 1) / kBlock);
-    p.blocksY = (uint32_t)((sizeY + kBlock - 1) / kBlock);
-    p.stripsX = (p.blocksX + kStripBlocks - 1) / kStripBlocks;
+    p.sizeX = (uint32_t)sizeX; p.sizeY = (uint32_t)e.sizeY;
+    p.blocksX = (uint32_t)sh.blocksX; p.blocksY = (uint32_t)sh.blocksY; p.stripsX = (uint32_t)sh.stripsX;
     // thresholds and flags (limg_hip_encode_rules.h)
     const Thresholds t = thresholds(errorFactor);
     p.maxPixel32 = t.maxPixel32; p.maxBlock = t.maxBlock; p.blockLimitFull = t.blockLimitFull; p.crushBits = (int32_t)t.crushBits;
@@ -115,14 +93,14 @@ namespace
       p.accTable = (const uint32_t *)c->enc.accTable.p;
     }
     forced_shifts(c->opt.forced_shift, p.forced);
-    p.floatFast = (c->opt.float_mode == 1 && (!x.fitOnly || x.fitFloatMode)) ? 1 : 0;
+    p.floatFast = plan.floatFast ? 1 : 0;
     p.recordLimit = record_limit(c);
-    const Partition pt = e.pt = x.part ? *x.part : partition(sizeY, poolThreads);
+    const Partition pt = e.pt;
     p.chainCount = pt.chainCount; p.chainRows = pt.chainRows;
 
     p.batchCount = (uint32_t)batchCount;
-    p.imageStrips = p.stripsX * p.blocksY;
-    e.blocks = (size_t)p.blocksX * p.blocksY * batchCount; e.strips = (size_t)p.stripsX * p.blocksY * batchCount;
+    p.imageStrips = (uint32_t)sh.strips;
+    e.blocks = sh.blocks * batchCount; e.strips = sh.strips * batchCount;
     // the per-block / per-strip scratch: sized for the larger encode this call may be a part of, addressed from this part's first block row
     const size_t scratchRows = x.scratchRows > (size_t)p.blocksY * batchCount ? x.scratchRows : (size_t)p.blocksY * batchCount;
     const size_t scratchBlocks = scratchRows * p.blocksX, scratchStrips = scratchRows * p.stripsX;
@@ -137,40 +115,17 @@ namespace
     if ((r = c->enc.stripCalls.ensure(scratchStrips * 4)) != limg_hip_success) return r;
     if ((r = c->enc.stripBase.ensure(scratchStrips * 4)) != limg_hip_success) return r;
     p.stripCalls = (uint32_t *)c->enc.stripCalls.p + stripOff; p.stripBase = (uint32_t *)c->enc.stripBase.p + stripOff;
-    const bool fullPlanes = e.fullPlanes;
-    p.storePlanes = dInfo != nullptr;
-    p.fullPlanes = fullPlanes;
-    p.streamRaw = x.streamRaw && !fullPlanes;
-    p.stripWords = (x.streamRaw && !fullPlanes) ? x.stripWords : nullptr;
-    p.fitOnly = x.fitOnly && !dInfo;
+    p.storePlanes = plan.storePlanes;
+    p.fullPlanes = plan.fullPlanes;
+    p.streamRaw = plan.streamRaw;
+    p.stripWords = plan.streamRaw ? x.stripWords : nullptr;
+    p.fitOnly = plan.fitOnly;
+    p.prefit = plan.prefit ? 1 : 0;
     if (dInfo) p.io.info = *dInfo;
-    // 16-byte vector access straight on caller pointers only where the address is 16-byte aligned for every row: sliced or offset
-    // device pointers take the dword paths
-    p.vecIn = (sizeX % 4 == 0) && (((uintptr_t)dIn) & 15u) == 0;
-    p.vecPlanes = 0;
-    if (dInfo && fullPlanes && sizeX % 4 == 0)
-    {
-      uintptr_t bits = 0;
-      const void *const *pp = reinterpret_cast<const void *const *>(dInfo);
-      for (int i = 1; i < 8; i++) bits |= (uintptr_t)pp[i]; // pShiftABCX .. pColCMax
-      p.vecPlanes = (bits & 15u) == 0;
-    }
-    p.vecFactors8 = dInfo && (sizeX % 8 == 0) && ((((uintptr_t)dInfo->pFactorsA) | ((uintptr_t)dInfo->pFactorsB) | ((uintptr_t)dInfo->pFactorsC)) & 7u) == 0;
-    p.vecDecoded = dInfo && fullPlanes && (sizeX % 4 == 0) && (((uintptr_t)dInfo->pDecoded) & 15u) == 0;
-    p.vecFactors = dInfo && (sizeX % 16 == 0) && ((((uintptr_t)dInfo->pFactorsA) | ((uintptr_t)dInfo->pFactorsB) | ((uintptr_t)dInfo->pFactorsC)) & 15u) == 0;
+    VecAccess vec = vec_access(dIn, dInfo, sizeX, plan.fullPlanes);
     if (batchCount > 1)
     { // the 16-byte access paths only if every image of the batch allows them; the table goes to the device behind whatever the stream still holds
-      for (size_t i = 1; i < batchCount; i++)
-      {
-        uintptr_t bits = 0;
-        const void *const *pp = reinterpret_cast<const void *const *>(&batch[i].info);
-        for (int k = 1; k < 8; k++) bits |= (uintptr_t)pp[k];
-        p.vecPlanes = p.vecPlanes && (bits & 15u) == 0;
-        p.vecIn = p.vecIn && (((uintptr_t)batch[i].in) & 15u) == 0;
-        p.vecDecoded = p.vecDecoded && (((uintptr_t)batch[i].info.pDecoded) & 15u) == 0;
-        p.vecFactors8 = p.vecFactors8 && ((((uintptr_t)batch[i].info.pFactorsA) | ((uintptr_t)batch[i].info.pFactorsB) | ((uintptr_t)batch[i].info.pFactorsC)) & 7u) == 0;
-        p.vecFactors = p.vecFactors && ((((uintptr_t)batch[i].info.pFactorsA) | ((uintptr_t)batch[i].info.pFactorsB) | ((uintptr_t)batch[i].info.pFactorsC)) & 15u) == 0;
-      }
+      for (size_t i = 1; i < batchCount; i++) vec &= vec_access(batch[i].in, dInfo ? &batch[i].info : nullptr, sizeX, plan.fullPlanes);
       if ((r = c->enc.batchTable.ensure(batchCount * sizeof(ImageIO))) != limg_hip_success) return r;
       launch_set_batch_table((ImageIO *)c->enc.batchTable.p, batch, batchCount, e.stream); // through kernel arguments: stream-ordered, and the host array may die right away
       p.batch = (const ImageIO *)c->enc.batchTable.p;
@@ -180,8 +135,9 @@ namespace
         e.rated = x.ratedTable;
       }
     }
+    p.vecIn = vec.in; p.vecPlanes = vec.planes; p.vecFactors8 = vec.factors8; p.vecDecoded = vec.decoded; p.vecFactors = vec.factors;
 
-    if (dInfo && !e.ragged)
+    if (dInfo && sh.whole)
     {
       // longest chain, in blocks: every block makes at most 3 dither calls
       uint32_t maxRows = p.blocksY;
@@ -190,15 +146,8 @@ namespace
       p.noise = (const uint8_t *)c->noise.table.p;
       p.noiseLast = (uint32_t)(c->noise.count - 1);
     }
-
-    const int chainPhase = x.chainPhase;
-    if (chainPhase != 0 && (e.ragged || !dInfo || poolThreads != 0)) return limg_hip_error_InvalidParameter; // a chain shared between GPUs: whole 8x8 blocks, one chain
-    p.chainCallsOut = chainPhase == 1 ? x.dChainCalls : nullptr;
-    p.chainBase = chainPhase == 2 ? x.dChainBase : nullptr;
-    // The float stage as its own launch, one lane per block (limg_hip_fit_tpb.hip), wherever every block is a whole 8x8: the E step then starts from the records.
-    p.prefit = (!e.ragged && c->opt.legacy_float_stage == 0 && (((uintptr_t)p.records) & 15u) == 0) ? 1 : 0; // k_fit_tpb stores records 16 bytes at a time
-    e.fused = dInfo != nullptr && !e.ragged && (c->opt.force_split_kernels == 0 || batchCount > 1) && chainPhase == 0;
-    e.wantStats = c->opt.collect_stats != 0 && dInfo != nullptr && chainPhase == 0;
+    p.chainCallsOut = x.chainPhase == 1 ? x.dChainCalls : nullptr;
+    p.chainBase = x.chainPhase == 2 ? x.dChainBase : nullptr;
     return limg_hip_success;
   }
 
@@ -225,7 +174,7 @@ namespace
     p.testSkipStrip = c->topt.skip_publish_strip > 0 ? (uint32_t)c->topt.skip_publish_strip - 1u : ~0u;
     p.testBaseErrStrip = c->topt.base_error_strip > 0 ? (uint32_t)c->topt.base_error_strip - 1u : ~0u;
 #endif
-    p.compactOut = compact != nullptr || e.wantStats; // the statistics are reduced from the raster-order shift words
+    p.compactOut = compact != nullptr || e.plan.wantStats; // the statistics are reduced from the raster-order shift words
     if ((r = c->enc.park.ensure((size_t)(c->enc.persistentWorkgroups / 5 * 6) * 2 * 8192)) != limg_hip_success) return r; // 6 workgroups per CU: the kernel's launch bound
     p.park = (uint8_t *)c->enc.park.p;
     return limg_hip_success;
@@ -237,21 +186,6 @@ namespace
   {
     const int t = TOPT(c, wg_per_cu);
     return (t >= 1 && t < deflt) ? t : deflt;
-  }
-
-  // A list of images as a PIPELINE of launch pairs (limg_hip_options.batch_sub_images): k_fit_tpb of sub-batch k + 1 runs on a stream of the context's own next to
-  // the persistent kernel of sub-batch k.  On content with short searches (BASELINE configs 2 / 4: ~2 trials per block) the persistent kernel waits for its plane
-  // stores a third of the time while k_fit_tpb is pure vector work: side by side they fill each other's gaps.  The persistent kernel leaves the float stage room
-  // to be resident: 5 workgroups per CU instead of 6 (at 6 x 80 VGPRs nothing else fits on a SIMD) for every sub-batch but the last.
-  // Measured on 4096^2 random-gradient lists (profiles/archive/r04_pipeline_sweep.md): 64 images 66.5 -> 73.3 Gpixel/s in sub-batches of 8 (4: 70.9, 16: 71.9); 16 images
-  // +3.5 % in sub-batches of 4; 8 images and fewer: nothing to gain (the lone first float stage and the 5-workgroup launches cost what the overlap saves).
-  size_t sub_batch_images(const EncodeJob &e)
-  {
-    const limg_hip_options &o = e.c->opt;
-    if (!e.fused || e.x.batchCount <= 1 || !e.p.prefit) return 0;
-    if (o.batch_sub_images > 0) return (size_t)o.batch_sub_images;
-    if (o.batch_sub_images == 0) return e.x.batchCount >= 32 ? 8 : (e.x.batchCount >= 16 ? 4 : 0);
-    return 0;
   }
 
   // The persistent launch of a job, or of the sub-batch q of it that starts at image i0 of the list: k_encode_persistent, or -- a list with one error factor per
@@ -274,8 +208,16 @@ namespace
     launch_encode_list_rated(r, e.channels, q.floatFast != 0, workgroups, e.stream);
   }
 
-  limg_hip_result encode_sub_batches(EncodeJob &e, size_t subImages)
+  // A list of images as a PIPELINE of launch pairs (limg_hip_options.batch_sub_images): k_fit_tpb of sub-batch k + 1 runs on a stream of the context's own next to
+  // the persistent kernel of sub-batch k.  On content with short searches (BASELINE configs 2 / 4: ~2 trials per block) the persistent kernel waits for its plane
+  // stores a third of the time while k_fit_tpb is pure vector work: side by side they fill each other's gaps.  The persistent kernel leaves the float stage room
+  // to be resident: 5 workgroups per CU instead of 6 (at 6 x 80 VGPRs nothing else fits on a SIMD) for every sub-batch but the last.
+  // Measured on 4096^2 random-gradient lists (profiles/archive/r04_pipeline_sweep.md): 64 images 66.5 -> 73.3 Gpixel/s in sub-batches of 8 (4: 70.9, 16: 71.9); 16 images
+  // +3.5 % in sub-batches of 4; 8 images and fewer: nothing to gain (the lone first float stage and the 5-workgroup launches cost what the overlap saves).
+  // Timeline: {k_fit_tpb of the first sub-batch -- the only float-stage work that runs alone --, the rest, -}.
+  limg_hip_result encode_sub_batches(EncodeJob &e)
   {
+    const size_t subImages = e.plan.subImages;
     limg_hip_context *const c = e.c;
     const EncodeParams &p = e.p;
     const size_t batchCount = e.x.batchCount;
@@ -306,7 +248,7 @@ namespace
       return q;
     };
     hipEvent_t *ev = c->enc.pipeEvents.data(); // [0]: fork; [1 + 2 k]: k_fit_tpb of sub-batch k done; [2 + 2 k]: the persistent kernel of sub-batch k is next on `stream`
-    e.mark_if(1);
+    e.tl.mark();
     HIP_TRY(hipEventRecord(ev[0], stream)); // everything the caller's stream holds so far (inputs, the image table, earlier encodes that use the scratch)
     HIP_TRY(hipStreamWaitEvent(fs, ev[0], 0));
     launch_fit_tpb(sub(0), e.channels, fs);
@@ -314,7 +256,7 @@ namespace
     for (size_t k = 0; k < nSub; k++)
     {
       HIP_TRY(hipStreamWaitEvent(stream, ev[1 + 2 * k], 0));
-      if (k == 0) e.mark_if(1); // (k_fit_tpb of the first sub-batch: the only float-stage work that runs alone)
+      if (k == 0) e.tl.mark();
       if (k + 1 < nSub)
       {
         HIP_TRY(hipEventRecord(ev[2 + 2 * k], stream));
@@ -324,183 +266,136 @@ namespace
       }
       launch_persistent(e, sub(k), k == 0 ? 0 : firstSub + (k - 1) * subImages, c->enc.persistentWorkgroups / 5 * (k + 1 < nSub ? wgOverlap : wg_per_cu(c, 6)));
     }
-    e.mark_if(1); e.mark_if(2);
-    HIP_TRY(hipGetLastError());
-    return encode_stats(e);
-  }
-
-  // k_fit_tpb (where the float stage is its own launch) + the persistent kernel: E step, look-back scan and F step of every strip in one launch
-  limg_hip_result encode_fused(EncodeJob &e)
-  {
-    const EncodeParams &p = e.p;
-    if (p.prefit)
-    {
-      e.mark_if(1);
-      launch_fit_tpb(p, e.channels, e.stream);
-    }
-    e.mark_if(1);
-    launch_persistent(e, p, 0, e.c->enc.persistentWorkgroups / 5 * wg_per_cu(e.c, p.prefit ? 6 : 5));
-    e.mark_if(1);
-    if (p.prefit) e.mark_if(2); else { e.mark_if(1); e.mark_if(2); } // 4 events per encode: with the float stage as its own launch the intervals are {k_fit_tpb, k_encode_persistent, -}
-    HIP_TRY(hipGetLastError());
-    return encode_stats(e);
-  }
-
-  // phase 2 of a chain encode: the E step and the scan of this very image ran in phase 1 -- records, shift words, strip bases and the pre-dither factor bytes are
-  // where they left them
-  limg_hip_result encode_chain_phase2(EncodeJob &e)
-  {
-    mark(e.c, e.stream); // a chain encode records 4 events over its two phases: intervals {E step + scan, exchange between the phases, F step}
-    launch_dither_store(e.p, e.channels, e.stream);
-    mark(e.c, e.stream);
-    HIP_TRY(hipGetLastError());
+    e.tl.mark();
     return limg_hip_success;
   }
 
-  // The split path on an image of whole blocks: [k_fit_tpb] + k_fit_search, the strip scan, k_dither_store.  Also pass 1 of the merged-block encoder (records only),
-  // `_perf` (nothing to store) and phase 1 of a chain encode (E step + scan).
-  limg_hip_result encode_split(EncodeJob &e)
+  // k_fit_tpb (where the float stage is its own launch) + the persistent kernel: E step, look-back scan and F step of every strip in one launch.
+  // Timeline: {k_fit_tpb, k_encode_persistent, -}; with the float stage inside the kernel {k_encode_persistent, -, -}.
+  void encode_fused(EncodeJob &e)
   {
     const EncodeParams &p = e.p;
     if (p.prefit)
     {
-      e.mark_if(1);
+      e.tl.mark();
       launch_fit_tpb(p, e.channels, e.stream);
-      if (p.fitOnly)
-      { // pass 1 of the merged-block encoder: the records are all it wants
-        e.mark_if(1); e.mark_if(1); e.mark_if(2);
-        HIP_TRY(hipGetLastError());
-        return limg_hip_success;
-      }
     }
-    else e.mark_if(1); // split path intervals: {k_fit_tpb + k_fit_search, scan, k_dither_store}
-    launch_fit_search(p, e.channels, e.stream);
-    if (e.x.chainPhase != 1) e.mark_if(1);
-    if (!e.dInfo)
-    {
-      e.mark_if(1); e.mark_if(2);
-      HIP_TRY(hipGetLastError());
-      return limg_hip_success; // `_perf` behaviour: nothing to dither into, nothing to store
-    }
-    launch_strip_scan(p, e.stream);
-    if (e.x.chainPhase == 1)
-    {
-      mark(e.c, e.stream);
-      HIP_TRY(hipGetLastError());
-      return limg_hip_success;
-    }
-    e.mark_if(1);
-    launch_dither_store(p, e.channels, e.stream);
-    e.mark_if(2);
-    HIP_TRY(hipGetLastError());
-    return encode_stats(e);
+    e.tl.mark();
+    launch_persistent(e, p, 0, e.c->enc.persistentWorkgroups / 5 * wg_per_cu(e.c, p.prefit ? 6 : 5));
+    e.tl.mark();
   }
-}
 
-namespace limg_hip
-{
-  // One 8x8 encode, whichever of its paths applies.
-  limg_hip_result encode_device(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *dInfo,
-                                const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast, hipStream_t stream, const EncodeExtra &x)
+  // phase 2 of a chain encode: the E step and the scan of this very image ran in phase 1 -- records, shift words, strip bases and the pre-dither factor bytes are
+  // where they left them.  A chain encode's timeline runs over its two phases, two events each: {E step + scan, exchange between the phases, F step}.
+  void encode_chain_phase2(EncodeJob &e)
   {
-    const int chainPhase = x.chainPhase;
-    const size_t batchCount = x.batchCount;
-    if (!c || !dIn) return limg_hip_error_ArgumentNull;
-    if (chainPhase == 0 && !x.inner) c->chain.in = nullptr; // the context's per-block scratch is about to be reused
-    if (sizeX == 0 || sizeY == 0 || sizeX > 0x7FFFFFF8ull || sizeY > 0x7FFFFFF8ull) return limg_hip_error_InvalidParameter;
-    bool fullPlanes = true;
-    if (dInfo)
-    {
-      // either all 11 planes, or (compact mode) only the three factor planes with the eight uint32 planes all NULL
-      const void *const *pp = reinterpret_cast<const void *const *>(dInfo);
-      int n32 = 0;
-      for (int i = 0; i < 8; i++) n32 += pp[i] != nullptr;
-      for (int i = 8; i < 11; i++)
-        if (!pp[i]) return limg_hip_error_ArgumentNull;
-      if (n32 != 0 && n32 != 8) return limg_hip_error_ArgumentNull;
-      fullPlanes = n32 == 8;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    const bool ragged = (sizeX % kBlock) != 0 || (sizeY % kBlock) != 0;
-    // An image whose WIDTH is whole blocks but whose last block row is partial (BASELINE config 1's shape class: 1024 x 618): every block row but the last
-    // is on the fast path (its dither chain is the seed's orbit, the noise table applies); only the last row needs the host to walk its chain.
-    if (ragged && sizeX % kBlock == 0 && sizeY > (size_t)kBlock && dInfo && chainPhase == 0 && batchCount == 1 && !x.inner && !x.fitOnly && c->opt.force_split_kernels == 0 &&
-        c->opt.legacy_float_stage == 0 && c->opt.dither_pcg == 0 && TOPT(c, whole_image_ragged) == 0)
-    {
-      if (((sizeX / kBlock) * ((sizeY + kBlock - 1) / kBlock)) * 3 <= checkpoint_reach())
-        return encode_height_ragged(c, dIn, sizeX, sizeY, hasAlpha, dInfo, compact, errorFactor, poolThreads, fast, stream, x);
-    }
-
-    EncodeJob e = { c, stream, x, dInfo, sizeX, sizeY };
-    e.channels = hasAlpha ? 4 : 3;
-    e.ragged = ragged;
-    e.fullPlanes = fullPlanes;
-    limg_hip_result r;
-    if ((r = encode_params(e, dIn, compact, errorFactor, poolThreads, fast)) != limg_hip_success) return r;
-    if (chainPhase == 0 && !x.inner && !c->stats.accumulate) c->stats.state = 0;
-    // a list in compact mode only as the batched stream encode hands it over: raw-escaped factor bytes, the strips' payload words, records and shift words all in
-    // raster arrays that run image after image (what its scan and packer read)
-    const bool compactList = !fullPlanes && x.streamRaw && x.stripWords && compact && compact->pRecords && compact->pShifts;
-    // ... or for its records alone (the size probes of a budgeted list): k_fit_tpb's batched grid and nothing else
-    const bool fitList = e.p.fitOnly && e.p.prefit && !ragged && chainPhase == 0;
-    if (batchCount > 1 && !fitList && (!e.fused || !e.p.prefit || (!fullPlanes && !compactList))) return limg_hip_error_InvalidParameter; // (limg_hip_encode3d_batch_device sends such lists through one encode per image instead)
-    // ... each at its own error factor (x.errorFactors): that compact list, and the one kernel there is for it
-    if (x.errorFactors && (!e.rated || batchCount <= 1 || !compactList || !e.fused || !e.p.prefit || !fast || chainPhase != 0)) return limg_hip_error_InvalidParameter;
-    if (e.fused && (r = fused_scratch(e, compact)) != limg_hip_success) return r;
-
-    const size_t subImages = sub_batch_images(e);
-    if (subImages > 0 && subImages < batchCount) return encode_sub_batches(e, subImages); // a list of images as a pipeline of launch pairs
-    if (e.fused) return encode_fused(e);                                                    // [k_fit_tpb +] the persistent kernel
-    if (chainPhase == 2) return encode_chain_phase2(e);                                     // k_dither_store behind a chain encode's phase 1
-    if (!ragged) return encode_split(e);                                                    // [k_fit_tpb +] k_fit_search, scan, k_dither_store
-    return encode_ragged(e);                                                                // k_fit_search, the host's chain walk, k_dither_store
+    e.tl.mark();
+    launch_dither_store(e.p, e.channels, e.stream);
   }
-}
 
-namespace
-{
+  // The split path on an image of whole blocks: [k_fit_tpb] + k_fit_search, the strip scan, k_dither_store.  Also pass 1 of the merged-block encoder (records only),
+  // `_perf` (nothing to dither into, nothing to store) and phase 1 of a chain encode (E step + scan).  Timeline: {k_fit_tpb + k_fit_search, scan, k_dither_store}.
+  void encode_split(EncodeJob &e)
+  {
+    const EncodeParams &p = e.p;
+    e.tl.mark();
+    if (p.prefit) launch_fit_tpb(p, e.channels, e.stream);
+    if (p.prefit && p.fitOnly) return; // pass 1 of the merged-block encoder: the records are all it wants
+    launch_fit_search(p, e.channels, e.stream);
+    if (e.x.chainPhase != 1) e.tl.mark();
+    if (!e.dInfo) return;
+    launch_strip_scan(p, e.stream);
+    if (e.x.chainPhase == 1) return;
+    e.tl.mark();
+    launch_dither_store(p, e.channels, e.stream);
+  }
+
   // sizeX % 8 == 0, sizeY % 8 != 0, at least two block rows (reference: the rx x ry gather of src/limg.cpp:1899-1905 only ever sees ry < 8 in the last block row,
   // and a dither call over 8 ry pixels is ry AES rounds, :824-879): the block rows above the last one are an image of whole blocks -- k_fit_tpb + persistent kernel
   // with the chain partition of the WHOLE image -- and the last row goes through the split path's kernels as a one-row sub-image whose chain starts where the
   // persistent kernel's last strip left it: that call count is the low word of the strip's look-back descriptor, and the chain value there comes from the embedded
   // checkpoints (at most 1023 calls on foot).  The host's share is then one block row: blocksX shift words down, <= 3 blocksX calls of ry rounds, their noise up.
-  limg_hip_result encode_height_ragged(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *dInfo,
-                                       const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast, hipStream_t stream, const EncodeExtra &x)
+  // Timeline: the rows above record three events, the last row none, this call the fourth.
+  limg_hip_result encode_height_ragged(const EncodeJob &e, const uint32_t *dIn, int hasAlpha, const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast)
   {
-    const size_t topY = (sizeY / kBlock) * kBlock, blocksX = sizeX / kBlock, blocksY = topY / kBlock + 1, stripsX = (blocksX + kStripBlocks - 1) / kStripBlocks;
-    const Partition pt = partition(sizeY, poolThreads);
+    limg_hip_context *const c = e.c;
+    const EncodeShape sh(e.sizeX, e.sizeY);
+    const size_t sizeX = e.sizeX, topY = (sh.blocksY - 1) * kBlock;
     c->chain.in = nullptr;
     c->stats.state = 0;
     limg_hip_result r;
     EncodeExtra xt;
-    xt.streamRaw = x.streamRaw; xt.inner = true; xt.marks = 1; xt.part = &pt; xt.scratchRows = blocksY;
-    if ((r = encode_device(c, dIn, sizeX, topY, hasAlpha, dInfo, compact, errorFactor, poolThreads, fast, stream, xt)) != limg_hip_success) return r;
+    xt.streamRaw = e.x.streamRaw; xt.inner = true; xt.part = &e.pt; xt.scratchRows = sh.blocksY;
+    if ((r = encode_device(c, dIn, sizeX, topY, hasAlpha, e.dInfo, compact, errorFactor, poolThreads, fast, e.stream, xt)) != limg_hip_success) return r;
     // the last block row
-    limg_hip_encode3d_info low = *dInfo;
-    {
-      const size_t skip = topY * sizeX; // pixels above the last block row, in every plane
-      uint32_t **words[] = { &low.pDecoded, &low.pShiftABCX, &low.pColAMin, &low.pColAMax, &low.pColBMin, &low.pColBMax, &low.pColCMin, &low.pColCMax };
-      uint8_t **bytes[] = { &low.pFactorsA, &low.pFactorsB, &low.pFactorsC };
-      for (uint32_t **p : words) if (*p) *p += skip;
-      for (uint8_t **p : bytes) if (*p) *p += skip;
-    }
+    limg_hip_encode3d_info low = *e.dInfo;
+    advance_planes(low, topY * sizeX); // pixels above the last block row, in every plane
     EncodeExtra xb;
-    xb.streamRaw = x.streamRaw; xb.inner = true; xb.marks = 0; xb.scratchRow0 = blocksY - 1; xb.scratchRows = blocksY;
+    xb.streamRaw = e.x.streamRaw; xb.inner = xb.innerLast = true; xb.scratchRow0 = sh.blocksY - 1; xb.scratchRows = sh.blocksY;
     const Partition one = { 1, 0 };
     xb.part = &one;
-    const bool sameChain = chain_of_row(pt.chainCount, pt.chainRows, (uint32_t)blocksY - 1) == chain_of_row(pt.chainCount, pt.chainRows, (uint32_t)blocksY - 2);
-    if (sameChain) xb.dPrevDesc = (const unsigned long long *)((const uint8_t *)c->enc.lookback.p + 16) + ((blocksY - 1) * stripsX - 1);
-    if ((r = encode_device(c, dIn + topY * sizeX, sizeX, sizeY - topY, hasAlpha, &low, compact, errorFactor, 0, fast, stream, xb)) != limg_hip_success) return r;
-    mark(c, stream);
-    if (c->opt.collect_stats != 0)
+    const bool sameChain = chain_of_row(e.pt.chainCount, e.pt.chainRows, (uint32_t)sh.blocksY - 1) == chain_of_row(e.pt.chainCount, e.pt.chainRows, (uint32_t)sh.blocksY - 2);
+    if (sameChain) xb.dPrevDesc = (const unsigned long long *)((const uint8_t *)c->enc.lookback.p + 16) + ((sh.blocksY - 1) * sh.stripsX - 1);
+    return encode_device(c, dIn + topY * sizeX, sizeX, e.sizeY - topY, hasAlpha, &low, compact, errorFactor, 0, fast, e.stream, xb);
+  }
+}
+
+namespace limg_hip
+{
+  // One 8x8 encode, whichever of its paths applies: the facts, the plan (limg_hip_encode_plan.h), its refusal if there is one -- before anything is grown or
+  // enqueued --, the parameters, the plan's path.
+  limg_hip_result encode_device(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *dInfo,
+                                const limg_hip_compact_out *compact, uint32_t errorFactor, int poolThreads, int fast, hipStream_t stream, const EncodeExtra &x)
+  {
+    EncodeFacts f = {};
+    f.nullArgument = !c || !dIn;
+    f.sizeX = sizeX; f.sizeY = sizeY;
+    f.planes = plane_set(dInfo);
+    f.callerRecords = compact && compact->pRecords; f.callerShifts = compact && compact->pShifts;
+    f.recordsAligned = compact && (((uintptr_t)compact->pRecords) & 15u) == 0;
+    f.poolThreads = poolThreads; f.fast = fast != 0;
+    f.part = x.part ? *x.part : partition(sizeY, poolThreads);
+    f.chainPhase = x.chainPhase; f.batchCount = x.batchCount;
+    f.inner = x.inner; f.innerLast = x.innerLast; f.fitOnly = x.fitOnly; f.fitFloatMode = x.fitFloatMode; f.streamRaw = x.streamRaw;
+    f.stripWords = x.stripWords != nullptr; f.errorFactors = x.errorFactors != nullptr; f.ratedTable = x.ratedTable != nullptr; f.dPrevDesc = x.dPrevDesc != nullptr;
+    if (c)
     {
-      if ((r = c->stats.counters.ensure(30 * 8)) != limg_hip_success) return r;
-      HIP_TRY(hipMemsetAsync(c->stats.counters.p, 0, 30 * 8, stream));
-      const uint32_t *shifts = (compact && compact->pShifts) ? compact->pShifts : (const uint32_t *)c->enc.shifts.p;
-      launch_shift_stats(shifts, (uint32_t)blocksX, (uint32_t)blocksY, (uint32_t)blocksY, (uint32_t)sizeX, (uint32_t)sizeY, (unsigned long long *)c->stats.counters.p, stream);
-      c->stats.stream = stream; c->stats.state = 1; c->stats.pixels = (uint64_t)sizeX * sizeY;
+      const limg_hip_options &o = c->opt;
+      f.force_split_kernels = o.force_split_kernels; f.legacy_float_stage = o.legacy_float_stage; f.dither_pcg = o.dither_pcg; f.float_mode = o.float_mode;
+      f.collect_stats = o.collect_stats; f.batch_sub_images = o.batch_sub_images; f.ragged_bands = o.ragged_bands;
+      f.whole_image_ragged = TOPT(c, whole_image_ragged);
     }
-    return limg_hip_success;
+    f.checkpoint_reach = checkpoint_reach();
+    const EncodePlan plan = encode_plan(f);
+    // what a call that is no part of a larger one resets, as far as it gets: the context's per-block scratch is about to be reused, its statistics are about to be stale
+    const bool outer = x.chainPhase == 0 && !x.inner;
+    if (outer && plan.verdict > kRefusedNull) c->chain.in = nullptr;
+    if (outer && plan.verdict > kRefusedChain && !c->stats.accumulate) c->stats.state = 0;
+    if (plan.code != limg_hip_success) return plan.code;
+    HIP_TRY(hipSetDevice(c->device));
+
+    EncodeJob e = { c, stream, x, dInfo, sizeX, sizeY, plan, Timeline(c, stream, plan.marks) };
+    e.channels = hasAlpha ? 4 : 3;
+    e.pt = f.part;
+    limg_hip_result r = limg_hip_success;
+    if (plan.path != kPathHeightRagged)
+    {
+      if ((r = encode_params(e, dIn, compact, errorFactor, fast)) != limg_hip_success) return r;
+      if (plan.fused && (r = fused_scratch(e, compact)) != limg_hip_success) return r;
+    }
+    switch (plan.path)
+    {
+      case kPathHeightRagged: r = encode_height_ragged(e, dIn, hasAlpha, compact, errorFactor, poolThreads, fast); break;
+      case kPathSubBatches: r = encode_sub_batches(e); break;
+      case kPathFused: encode_fused(e); break;
+      case kPathChainPhase2: encode_chain_phase2(e); break;
+      case kPathSplit: encode_split(e); break;
+      case kPathRagged: r = encode_ragged(e); break;
+    }
+    if (r != limg_hip_success) return r;
+    e.tl.close();
+    HIP_TRY(hipGetLastError());
+    return encode_stats(e, compact);
   }
 }
 
@@ -530,23 +425,18 @@ extern "C"
   {
     if (!c || !ppIn || !pInfos) return limg_hip_error_ArgumentNull;
     if (count == 0) return limg_hip_success;
-    if (sizeX == 0 || sizeY == 0 || sizeX > 0x7FFFFFF8ull || sizeY > 0x7FFFFFF8ull) return limg_hip_error_InvalidParameter;
+    const EncodeShape sh(sizeX, sizeY);
+    if (!sh.valid) return limg_hip_error_InvalidParameter;
     bool full = true;
     for (size_t i = 0; i < count; i++)
     {
       if (!ppIn[i]) return limg_hip_error_ArgumentNull;
-      const void *const *pp = reinterpret_cast<const void *const *>(&pInfos[i]);
-      for (int k = 8; k < 11; k++)
-        if (!pp[k]) return limg_hip_error_ArgumentNull;
-      int n32 = 0;
-      for (int k = 0; k < 8; k++) n32 += pp[k] != nullptr;
-      if (n32 != 0 && n32 != 8) return limg_hip_error_ArgumentNull;
-      full = full && n32 == 8;
+      const PlaneSet planes = plane_set(&pInfos[i]);
+      if (planes == kPlanesInvalid) return limg_hip_error_ArgumentNull;
+      full = full && planes == kPlanesFull;
     }
-    const bool ragged = (sizeX % kBlock) != 0 || (sizeY % kBlock) != 0;
-    const size_t blocks = ((sizeX + kBlock - 1) / kBlock) * ((sizeY + kBlock - 1) / kBlock), strips = ((sizeX + kBlock * kStripBlocks - 1) / (kBlock * kStripBlocks)) * ((sizeY + kBlock - 1) / kBlock);
-    const size_t chunk = list_chunk(c, blocks, strips); // longer lists go in several launch pairs
-    const bool oneByOne = count == 1 || ragged || !full || c->opt.legacy_float_stage != 0 || c->opt.force_split_kernels != 0;
+    const size_t chunk = list_chunk(c, sh.blocks, sh.strips); // longer lists go in several launch pairs
+    const bool oneByOne = count == 1 || !full || !list_in_one_pair(sh, c->opt);
     std::vector<ImageIO> table;
     limg_hip_result r = limg_hip_success;
     for (size_t i0 = 0; i0 < count && r == limg_hip_success;)

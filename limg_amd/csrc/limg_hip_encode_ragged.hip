@@ -80,24 +80,6 @@ namespace
     return limg_hip_success;
   }
 
-  // How many bands of block rows the E step runs in.  The walk is the floor of this class -- ~26 ms for 8190 x 8192, one dependent AESDEC chain -- so everything
-  // else is taken off its path: the E step runs in BANDS of block rows whose shift words come back band by band (the walk starts when the first band is down and
-  // runs under the rest of the E step), and the F step of a band is launched as soon as its chain values are up (it runs under the walk of the next band).  Only
-  // for one chain (poolThreads == 0): independent chains are walked in parallel instead.
-  // (an explicit band count is honoured from 2 x 2 blocks on -- tests and the fuzz tool; a band must not be one block wide: the corner block of fewer than four
-  //  pixels sums its LEFT neighbour's pixels, which for a one-block-wide image would be the row above, in another band)
-  uint32_t band_count(const EncodeJob &e)
-  {
-    const limg_hip_options &o = e.c->opt;
-    const EncodeParams &p = e.p;
-    uint32_t nBands = 1;
-    if (e.dInfo && !e.x.dPrevDesc && e.pt.chainCount <= 1 && o.ragged_bands >= 0 && p.blocksX >= 2 && p.blocksY >= 2 && (o.ragged_bands > 0 || (p.blocksX >= 32 && p.blocksY >= 64)))
-      nBands = o.ragged_bands > 0 ? (uint32_t)o.ragged_bands : 16u;
-    if (nBands > p.blocksY / 2) nBands = p.blocksY / 2 ? p.blocksY / 2 : 1;
-    if (nBands > 64) nBands = 64;
-    return nBands;
-  }
-
   // band b of a banded encode as a sub-image: pointers advanced, block rows counted from its top
   EncodeParams band_params(const EncodeJob &e, uint32_t bandRows, uint32_t b)
   {
@@ -106,10 +88,7 @@ namespace
     const uint32_t r0 = b * bandRows, r1 = r0 + bandRows < p.blocksY ? r0 + bandRows : p.blocksY;
     const size_t y0 = (size_t)r0 * kBlock, skip = y0 * e.sizeX;
     q.io.in = p.io.in + skip;
-    uint32_t **words[] = { &q.io.info.pDecoded, &q.io.info.pShiftABCX, &q.io.info.pColAMin, &q.io.info.pColAMax, &q.io.info.pColBMin, &q.io.info.pColBMax, &q.io.info.pColCMin, &q.io.info.pColCMax };
-    uint8_t **bytes[] = { &q.io.info.pFactorsA, &q.io.info.pFactorsB, &q.io.info.pFactorsC };
-    for (uint32_t **w : words) if (*w) *w += skip;
-    for (uint8_t **w : bytes) if (*w) *w += skip;
+    advance_planes(q.io.info, skip);
     q.sizeY = (uint32_t)(((size_t)r1 * kBlock < e.sizeY ? (size_t)r1 * kBlock : e.sizeY) - y0);
     q.blocksY = r1 - r0;
     q.imageStrips = q.stripsX * q.blocksY;
@@ -118,14 +97,16 @@ namespace
     return q;
   }
 
-  // ---- one chain, walked band by band under the E step; every band's F step under the walk of the next ----
-  limg_hip_result encode_ragged_banded(EncodeJob &e, uint32_t nBands, uint32_t bandRows)
+  // ---- one chain, walked band by band under the E step; every band's F step under the walk of the next (when: encode_plan) ----
+  // Timeline: {E step of all bands, the walk with the other bands' F steps under it, the last band's F step}
+  limg_hip_result encode_ragged_banded(EncodeJob &e)
   {
+    const uint32_t nBands = e.plan.bands, bandRows = e.plan.bandRows;
     limg_hip_context *const c = e.c;
     const EncodeParams &p = e.p;
     const hipStream_t stream = e.stream;
     limg_hip_result r;
-    e.mark_if(1); // split path intervals: {k_fit_tpb + k_fit_search, scan, k_dither_store}
+    e.tl.mark();
     if ((r = ensure_stage(e)) != limg_hip_success) return r;
     if ((r = c->host.raggedEvents.ensure(nBands, hipEventDisableTiming)) != limg_hip_success) return r;
     const RaggedStage h(e.blocks, e.strips, c->host.stage.p);
@@ -137,7 +118,7 @@ namespace
       HIP_TRY(hipMemcpyAsync(h.shifts + off, p.shifts + off, (size_t)q.blocksY * p.blocksX * 4, hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipEventRecord(c->host.raggedEvents[b], stream));
     }
-    e.mark_if(1);
+    e.tl.mark();
     // sized for the worst case up front (3 calls per block): a band's calls go up while later bands are still being walked
     if ((r = size_noise_calls(e, h.maxCalls)) != limg_hip_success) return r;
     const bool pcg = c->opt.dither_pcg != 0;
@@ -153,13 +134,10 @@ namespace
       if ((r = upload_calls(e, h, h.maxCalls, call0, call - call0)) != limg_hip_success) return r;
       HIP_TRY(hipMemcpyAsync(p.stripBase + (size_t)r0 * p.stripsX, h.base + (size_t)r0 * p.stripsX, (size_t)q.blocksY * p.stripsX * 4, hipMemcpyHostToDevice, stream));
       q.noise = p.noise; q.noiseLast = p.noiseLast;
-      if (b + 1 == nBands) e.mark_if(1); // intervals of a banded encode: {E step of all bands, the walk with the other bands' F steps under it, the last band's F step}
+      if (b + 1 == nBands) e.tl.mark();
       launch_dither_store(q, e.channels, stream);
     }
-    if ((r = release_stage(e)) != limg_hip_success) return r;
-    e.mark_if(2);
-    HIP_TRY(hipGetLastError());
-    return encode_stats(e);
+    return release_stage(e);
   }
 }
 
@@ -171,20 +149,12 @@ namespace limg_hip
     const EncodeParams &p = e.p;
     const Partition &pt = e.pt;
     const hipStream_t stream = e.stream;
-    uint32_t nBands = band_count(e);
-    const uint32_t bandRows = (p.blocksY + nBands - 1) / nBands;
-    nBands = (p.blocksY + bandRows - 1) / bandRows;
-    if (nBands > 1) return encode_ragged_banded(e, nBands, bandRows);
+    if (e.plan.bands > 1) return encode_ragged_banded(e);
 
-    e.mark_if(1); // split path intervals: {k_fit_tpb + k_fit_search, scan, k_dither_store}
+    e.tl.mark(); // the split path's timeline: {k_fit_search, the walk, k_dither_store}
     launch_fit_search(p, e.channels, stream);
-    e.mark_if(1);
-    if (!e.dInfo)
-    {
-      e.mark_if(1); e.mark_if(2);
-      HIP_TRY(hipGetLastError());
-      return limg_hip_success; // `_perf` behaviour: nothing to dither into, nothing to store
-    }
+    e.tl.mark();
+    if (!e.dInfo) return limg_hip_success; // `_perf` behaviour: nothing to dither into, nothing to store
     limg_hip_result r;
     if ((r = ensure_stage(e)) != limg_hip_success) return r;
     const RaggedStage h(e.blocks, e.strips, c->host.stage.p);
@@ -252,10 +222,8 @@ namespace limg_hip
     if ((r = upload_calls(e, h, calls, 0, totalCalls)) != limg_hip_success) return r;
     HIP_TRY(hipMemcpyAsync(p.stripBase, h.base, e.strips * 4, hipMemcpyHostToDevice, stream));
     if ((r = release_stage(e)) != limg_hip_success) return r;
-    e.mark_if(1);
+    e.tl.mark();
     launch_dither_store(p, e.channels, stream);
-    e.mark_if(2);
-    HIP_TRY(hipGetLastError());
-    return encode_stats(e);
+    return limg_hip_success;
   }
 }

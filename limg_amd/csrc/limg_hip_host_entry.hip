@@ -112,9 +112,8 @@ namespace
       const size_t y0 = bands[b].y0, rows = bands[b].y1 - y0, o = y0 * sizeX;
       const uint32_t *dIn = (const uint32_t *)c->host.in.p + o;
       if (hipMemcpyAsync((void *)dIn, pIn + o, rows * sizeX * 4, hipMemcpyHostToDevice, s) != hipSuccess) { result = limg_hip_error_Generic; break; }
-      limg_hip_encode3d_info d;
-      void **q = reinterpret_cast<void **>(&d);
-      for (int i = 0; i < 11; i++) q[i] = (uint8_t *)dp[i] + o * (i < 8 ? 4 : 1);
+      limg_hip_encode3d_info d = *reinterpret_cast<const limg_hip_encode3d_info *>(dp);
+      advance_planes(d, o);
       if (chains) result = encode_device(c, dIn, sizeX, rows, hasAlpha, &d, nullptr, errorFactor, 0, fastBitCrushing, s);
       else
       {

@@ -117,8 +117,9 @@ extern "C"
 {
   size_t limg_hip_stream_bound(size_t sizeX, size_t sizeY)
   {
-    if (sizeX == 0 || sizeY == 0 || sizeX > 0x7FFFFFF8ull || sizeY > 0x7FFFFFF8ull) return 0;
-    const size_t blocks = ((sizeX + kBlock - 1) / kBlock) * ((sizeY + kBlock - 1) / kBlock);
+    const EncodeShape sh(sizeX, sizeY);
+    if (!sh.valid) return 0;
+    const size_t blocks = sh.blocks;
     if (blocks * 24 > 0xFFFFFFFFull) return 0; // entry.payloadWord is 32 bits
     return sizeof(limg_hip_stream_header) + blocks * sizeof(limg_hip_stream_block) + blocks * 192;
   }
@@ -139,9 +140,10 @@ extern "C"
     dp.nBlocks = dp.blocksX * dp.blocksY;
     if (streamBytes < sizeof(limg_hip_stream_header) + (size_t)dp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
     dp.stream = pStream; dp.streamBytes = streamBytes; dp.out = pOut; dp.status = (uint32_t *)c->stream.status.p; dp.sink = (uint32_t *)((uint8_t *)c->stream.status.p + 256);
-    mark(c, s);
+    Timeline tl(c, s, 4);
+    tl.mark();
     launch_stream_decode(dp, device_cus(c), s);
-    mark(c, s); mark(c, s); mark(c, s);
+    tl.close();
     HIP_TRY(hipGetLastError());
     return limg_hip_success;
   }

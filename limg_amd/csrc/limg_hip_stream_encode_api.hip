@@ -12,19 +12,17 @@ using namespace limg_hip;
 namespace
 {
   // ---- a call's shape: everything the entries derive from (sizeX, sizeY) ----
-  struct StreamShape
+  struct StreamShape : EncodeShape // blocks and strips; whole: the strip form of the packer, the batched kernels, the probe
   {
-    size_t sizeX, sizeY, px, planeStride, blocksX, blocksY, blocks, tiles, stripsX, strips, bound;
+    size_t px, planeStride, tiles, bound;
     uint64_t fixedBytes; // header + table: a stream is this + 8 x its payload words
-    bool whole;          // whole 8x8 blocks: the strip form of the packer, the batched kernels, the probe
     StreamShape(size_t x, size_t y)
-      : sizeX(x), sizeY(y), px(x * y), planeStride((px + 255) & ~(size_t)255), blocksX((x + kBlock - 1) / kBlock), blocksY((y + kBlock - 1) / kBlock), blocks(blocksX * blocksY),
-        tiles((blocks + 255) / 256), stripsX((blocksX + kStripBlocks - 1) / kStripBlocks), strips(stripsX * blocksY), bound(limg_hip_stream_bound(x, y)),
-        fixedBytes(sizeof(limg_hip_stream_header) + (uint64_t)blocks * sizeof(limg_hip_stream_block)), whole((x % kBlock) == 0 && (y % kBlock) == 0) {}
+      : EncodeShape(x, y), px(x * y), planeStride((px + 255) & ~(size_t)255), tiles((blocks + 255) / 256), bound(limg_hip_stream_bound(x, y)),
+        fixedBytes(sizeof(limg_hip_stream_header) + (uint64_t)blocks * sizeof(limg_hip_stream_block)) {}
   };
 
-  // lists in one launch pair and the probe kernel: whole blocks, the persistent path's float stage (k_fit_tpb) -- and, the probe, the default search
-  bool batch_applies(const limg_hip_context *c, const StreamShape &sh) { return sh.whole && c->opt.force_split_kernels == 0 && c->opt.legacy_float_stage == 0; }
+  // lists in one launch pair and the probe kernel: list_in_one_pair -- and, the probe, the default search
+  bool batch_applies(const limg_hip_context *c, const StreamShape &sh) { return list_in_one_pair(sh, c->opt); }
   bool rate_probe_applies(const limg_hip_context *c, const StreamShape &sh, int fast) { return batch_applies(c, sh) && fast != 0; }
 
   // ---- argument checks, in the contract's order (include/limg_hip.h) ----
@@ -114,13 +112,13 @@ namespace
     void launch(hipStream_t s) const { if (n == 1) launch_rate_probe(one, channels, floatFast, s); else launch_rate_probe_batch(many, channels, floatFast, s); }
   };
 
-  // what RateProbeParams and RateProbeBatchParams name alike.  aligned: every image of the launch starts 16-byte aligned
+  // what RateProbeParams and RateProbeBatchParams name alike.  vecIn: 16-byte loads, which every image of the launch allows (vec_access)
   template <class P>
-  void fill_probe(P &p, const limg_hip_context *c, const StreamShape &sh, bool aligned)
+  void fill_probe(P &p, const limg_hip_context *c, const StreamShape &sh, bool vecIn)
   {
     memset(&p, 0, sizeof(p));
     p.sizeX = (uint32_t)sh.sizeX; p.sizeY = (uint32_t)sh.sizeY; p.blocksX = (uint32_t)sh.blocksX; p.blocksY = (uint32_t)sh.blocksY; p.stripsX = (uint32_t)sh.stripsX;
-    p.vecIn = (sh.sizeX % 4 == 0) && aligned; // as encode_params: 16-byte loads only if every image allows them
+    p.vecIn = vecIn;
     p.recordLimit = record_limit(c);
     forced_shifts(c->opt.forced_shift, p.forced);
     p.records = (const limg_hip_block_record *)c->enc.records.p; p.invN = (const float *)c->enc.invN.p;
@@ -134,17 +132,17 @@ namespace
     if ((r = c->stream.rateState.ensure(n * sizeof(RateDevice))) != limg_hip_success) return r;
     if ((r = c->stream.rateCounter.ensure(n * 8)) != limg_hip_success) return r;
     std::vector<ImageIO> table(n > 1 ? n : 0);
-    bool aligned = true;
-    for (size_t i = 0; i < n; i++) { aligned = aligned && (((uintptr_t)ppIn[i]) & 15u) == 0; if (n > 1) table[i].in = ppIn[i]; }
+    VecAccess vec = vec_access(ppIn[0], nullptr, sh.sizeX, false);
+    for (size_t i = 0; i < n; i++) { vec &= vec_access(ppIn[i], nullptr, sh.sizeX, false); if (n > 1) table[i].in = ppIn[i]; }
     EncodeExtra x;
     x.fitOnly = true; x.fitFloatMode = true;
     if (n > 1) { x.batch = table.data(); x.batchCount = n; }
     if ((r = encode_device(c, ppIn[0], sh.sizeX, sh.sizeY, hasAlpha, nullptr, nullptr, 0, poolThreads, 1, s, x)) != limg_hip_success) return r;
     pr.n = n; pr.channels = hasAlpha ? 4 : 3; pr.floatFast = c->opt.float_mode == 1; pr.fixedBytes = sh.fixedBytes;
     pr.states = (RateDevice *)c->stream.rateState.p; pr.counters = (unsigned long long *)c->stream.rateCounter.p;
-    fill_probe(pr.one, c, sh, aligned);
+    fill_probe(pr.one, c, sh, vec.in);
     pr.one.io.in = ppIn[0]; pr.one.state = pr.states; pr.one.counter = pr.counters;
-    fill_probe(pr.many, c, sh, aligned);
+    fill_probe(pr.many, c, sh, vec.in);
     pr.many.batch = (const ImageIO *)c->enc.batchTable.p; pr.many.nImages = (uint32_t)n; pr.many.imageStrips = (uint32_t)sh.strips;
     pr.many.states = pr.states; pr.many.counters = pr.counters;
     return limg_hip_success;
@@ -279,9 +277,10 @@ namespace
         b.images = (const StreamImage *)c->stream.table.p + i0;
         b.records = comp.pRecords; b.shifts = comp.pShifts; b.stripWords = (uint32_t *)c->stream.units.p;
         b.rated = efs ? ratedStorage : nullptr; // (the chunk's table, as the encode just wrote it)
-        mark(c, s);
+        Timeline tl(c, s, 4); // {scan + pack of the chunk, -, -}
+        tl.mark();
         launch_stream_pack_batch(b, s);
-        mark(c, s); mark(c, s); mark(c, s);
+        tl.close();
         const hipError_t launched = hipGetLastError();
         if (launched != hipSuccess) { c->stats.accumulate = false; HIP_TRY(launched); }
       }
@@ -356,9 +355,10 @@ extern "C"
       sp.stripsX = (uint32_t)sh.stripsX; sp.nStrips = (uint32_t)sh.strips;
       sp.nWaves = pack_waves(c, sh.strips);
     }
-    mark(c, s);
+    Timeline tl(c, s, 4); // {scan + pack, -, -}
+    tl.mark();
     launch_stream_pack(sp, s);
-    mark(c, s); mark(c, s); mark(c, s);
+    tl.close();
     HIP_TRY(hipGetLastError());
     return pBytes ? stream_total_bytes(pStream, s, pBytes) : limg_hip_success;
   }
