@@ -460,6 +460,69 @@ limg_hip_result limg_hip_encode_stream_budget_batch(limg_hip_context *pCtx, size
                                                     uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
                                                     limg_hip_budget_result *pResults /* host, count, struct_size set in each */);
 
+/* ---- stream encode to a quality target: error-factor search on the stream's measured error (version 1 streams) ----------------------
+ * The budget entries answer "at most N bytes"; these answer "at least this good": the stream of limg_hip_encode_stream* at the COARSEST error factor the search finds whose
+ * error sum against its own image -- limg_hip_decode_stream_windows_error over the whole image, mse * pixels of limg_hip_compare(image, decode(stream)) -- is at most
+ * maxErrorSum.  For a PSNR target pass limg_hip_error_sum_for_psnr(sizeX, sizeY, hasAlpha, dB): "PSNR >= dB" is then the exact integer comparison errorSum <= limit.
+ * The search runs over h = errorFactor / 2 between minErrorFactor / 2 and maxErrorFactor / 2 (even bounds; 0 means 2 and 1024) and is this algorithm, with E(h) the error
+ * sum of the stream at errorFactor 2 h (limg_hip_quality_step.h: the budget search on the mirrored axis hLo + hHi - h, with E in the size's place):
+ *     if E(hLo) > maxErrorSum:          errorFactor = minErrorFactor, withinTarget = 0       (not even the finest allowed value reaches the target; the call still
+ *                                                                                             succeeds and writes that stream)
+ *     elif E(hHi) <= maxErrorSum:       errorFactor = maxErrorFactor, withinTarget = 1
+ *     else bisect with E(lo) <= maxErrorSum < E(hi), mid = hi - (hi - lo) / 2, until hi - lo == 1:  errorFactor = 2 lo, withinTarget = 1
+ * Every value is asked for once (hLo == hHi asks once); probes is at most 2 + ceil(log2(hHi - hLo)).  With withinTarget = 1 the result is a value whose error was MEASURED
+ * and found to meet the limit.  E is NOT monotone in errorFactor (the shift search is greedy and the dither differs between error factors), so errorFactor is the largest
+ * that meets the limit only on curves that happen to rise monotonically: the search may return a finer stream than the coarsest that would do.
+ * The stream written is byte for byte limg_hip_encode_stream_device's at pResult->errorFactor, pResult->bytes its totalBytes and pResult->errorSum its E.  maxErrorSum == 0
+ * is allowed: it asks for a lossless image.  pResult (host): set struct_size to sizeof(limg_hip_quality_result) before the call; the budget result's rule.
+ * Each probe is ONE ordinary stream encode into the caller's buffer -- so every shape, option and search the stream encode accepts works here, there is no fallback
+ * class --, ONE error launch over the whole image and ONE 8-byte download.  The device form therefore WAITS for `stream` once per probe (and once more for the size) and
+ * cannot be captured into a graph.  Where the last probe was not the result, the result's stream is encoded once more.
+ * Errors: those of limg_hip_encode_stream[_device] in its order, pResult counted among the pointers; then an odd bound, a bound below 2, minErrorFactor > maxErrorFactor or
+ * a struct_size below the struct's: limg_hip_error_InvalidParameter.  All before anything touches the device; a refused call writes nothing.
+ * Context memory: 8 bytes per image of the call besides what the stream encode and one batched window call hold.
+ * Follow-up, not here: a device-stepped search that enqueues all probes at once needs the encode's thresholds from a device table for a single image too (the list
+ * encode has one); error at reduced levels; version 2 streams; lists of mixed shapes; other metrics. */
+typedef struct limg_hip_quality_result
+{
+  uint32_t struct_size;  /* in: sizeof(limg_hip_quality_result) */
+  uint32_t errorFactor;  /* the error factor the stream was encoded with */
+  uint32_t probes;       /* error sums the search measured */
+  uint32_t withinTarget; /* 1: errorSum <= maxErrorSum */
+  uint64_t bytes;        /* the stream's totalBytes */
+  uint64_t errorSum;     /* the stream's error sum against the image */
+} limg_hip_quality_result; /* 32 bytes */
+
+/* DEVICE pointers (pIn, pStream: 16-byte aligned, capacity >= limg_hip_stream_bound); waits for `stream`. */
+limg_hip_result limg_hip_encode_stream_quality_device(limg_hip_context *pCtx, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream,
+                                                      size_t capacity, uint64_t maxErrorSum, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads,
+                                                      int fastBitCrushing, limg_hip_quality_result *pResult, void *stream);
+/* HOST pointers, blocking, under the context's mutex.  capacity may be below the bound: pResult is filled, and limg_hip_error_OutOfBounds returned with nothing written
+ * to pStream, where pResult->bytes > capacity. */
+limg_hip_result limg_hip_encode_stream_quality(limg_hip_context *pCtx, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                               uint64_t maxErrorSum, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                               limg_hip_quality_result *pResult);
+/* A list of `count` same-shape images: pResults[i] and ppStreams[i] are exactly the single call's for image i with maxErrorSum = pMaxErrorSums[i] and the same bounds,
+ * arguments and options; one image's outcome never touches another's.  Per round the images whose search is not over are encoded at their own next value by ONE
+ * limg_hip_encode_stream_batch_ef_device call, measured by ONE error launch and stepped behind ONE download: a list costs at most 2 + ceil(log2(hHi - hLo)) rounds, plus
+ * at most one final list encode for the images whose buffer does not hold their result's stream, and one download of the sizes -- whatever its length.  A list of one is
+ * the single call.  pMaxErrorSums and pResults are HOST arrays of `count` entries in both forms; set struct_size in EVERY pResults[i].
+ * Errors, all before anything touches the device -- a refused call writes nothing to any stream or result -- in this order: (1) those of
+ * limg_hip_encode_stream_batch_device in its order, pMaxErrorSums and pResults counted among the pointers; (2) the bound rules above: limg_hip_error_InvalidParameter;
+ * (3) any struct_size below the struct's: limg_hip_error_InvalidParameter; (4) count == 0: limg_hip_success with nothing done.
+ * DEVICE pointers; ppIn / ppStreams are HOST arrays of `count` device pointers (streams 16-byte aligned, capacityEach >= limg_hip_stream_bound).  Waits for `stream` once
+ * per round. */
+limg_hip_result limg_hip_encode_stream_quality_batch_device(limg_hip_context *pCtx, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                            uint8_t *const *ppStreams, size_t capacityEach, const uint64_t *pMaxErrorSums /* host, count */,
+                                                            uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                            limg_hip_quality_result *pResults /* host, count, struct_size set in each */, void *stream);
+/* HOST images and HOST stream buffers, blocking, under the context's mutex.  capacityEach may be below the bound: where it is below some pResults[i].bytes, all results are
+ * filled, NO stream is written and limg_hip_error_OutOfBounds is returned -- the single host call's rule. */
+limg_hip_result limg_hip_encode_stream_quality_batch(limg_hip_context *pCtx, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                     uint8_t *const *ppStreams, size_t capacityEach, const uint64_t *pMaxErrorSums /* host, count */,
+                                                     uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                     limg_hip_quality_result *pResults /* host, count, struct_size set in each */);
+
 /* ---- compact stream, version 2: the merged-block encoder's rectangles --------------------------------------------------------
  * What limg_hip_blocked_encode3d computes -- the rectangles of merged 8x8 blocks, each with ONE record, ONE shift triple and its crushed factor values -- in the same
  * "LMG3" container, so that decode(blocked_encode_stream(image)) equals the pDecoded plane of `limg_blocked_encode3d_test` bit for bit.  Version 1 streams and their
@@ -597,6 +660,65 @@ limg_hip_result limg_hip_blocked_decode_stream_windows_device(limg_hip_context *
  * stream refused for any window leaves EVERY pOut untouched, in both versions. */
 limg_hip_result limg_hip_decode_stream_windows(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count);
 limg_hip_result limg_hip_blocked_decode_stream_windows(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count);
+
+/* ---- stream error inside the decode: a window of a stream against an original, without the decoded image ------------------------
+ * "How good is this stream?" -- the reference's answer is limg_compare, the perceptual RGB(A) PSNR of its tool -- used to take a full decode (4 bytes per pixel stored)
+ * and limg_hip_compare_device (8 bytes per pixel read).  These entries are the batched window decode with a sink instead of a store: the decoded pixels never leave the
+ * registers, the original's pixels are read where the decoded ones would have been written, and one integer per job is all that is written.
+ * Result: let P(x, y) be the pixel the version's full decoder writes and O(x, y) = pOriginal[(y - y0) * originalStridePixels + (x - x0)].  pErrorSums[i] is the sum over
+ * the window's pixels of the reference's colour error between P and O, exactly what limg_hip_compare_device adds per pixel: with the byte differences r, g, b, a
+ *     r^2 * (r^2 < 0x4000 ? 2 : 3) + g^2 * 4 + b^2 * (r^2 < 0x4000 ? 3 : 2) + (a^2 * 3 where the STREAM's header says 4 channels)
+ * It is an exact integer sum, so it does not depend on the order the device adds in; over the window (0, 0, sizeX, sizeY) it is mse * sizeX * sizeY of
+ * limg_hip_compare(original, decode(stream)) with hasAlpha = (channels == 4), and "PSNR >= target" is pErrorSums[i] <= limg_hip_error_sum_for_psnr(...).
+ * The call zeroes the `count` sums on `stream` in front of its launch.  NOTHING ELSE IS WRITTEN: no decoded pixel, no scratch image; the originals are only read, and
+ * only at the window's pixels (never in the stride slack).  Load width: a block row piece of 8 pixels that lies wholly inside the window is read as two 16-byte loads
+ * where pOriginal is 16-byte aligned and originalStridePixels and x0 are multiples of 4, else pixel by pixel -- the store rule of the batched window decode.
+ * Full scale only: there is no level and no resize.
+ * Jobs, checks and refusals are the batched window decode's: jobs are independent and may name different streams; every job is checked on the host, in index order and by
+ * the single-window entry's rules in its order, with pOriginal in pOut's place (NULL: limg_hip_error_ArgumentNull; not 4-byte aligned or originalStridePixels < width:
+ * limg_hip_error_InvalidParameter; a window outside the image: limg_hip_error_OutOfBounds), NULL pErrorSums counting as a NULL pointer of the call and count == 0 as
+ * limg_hip_error_InvalidParameter; a refused call enqueues nothing and leaves the sums untouched.  Each entry takes ONE stream version.
+ * Validation on the device is the window decode's.  A job that is refused there (bit 0 header mismatch, bit 1 table entry or payload extent inconsistent) raises
+ * pJobStatus[i] and the context's sticky status; what it contributes to its own sum is then unspecified (version 1 leaves out the groups of 8 blocks that failed,
+ * version 2 the whole job) and pErrorSums[i] is MEANINGLESS.  No other job's sum changes.
+ * Cost: version 1 is ONE kernel launch per call, version 2 TWO (k_bstream_windows_map as it is), and one memset.  A wave adds its lanes' sums up once per work unit
+ * and issues one 64-bit atomic per run of units of the same job; the runs its loop ends in leave with those of its workgroup's other waves, one atomic per job.  Memory read: the windows' table entries and payload and 4 bytes per window pixel of the originals.
+ * Ordering and context memory: the batched window decode's (the job table in the ring of four slots); these entries must not be used while `stream` is being captured. */
+typedef struct limg_hip_error_window /* one window and the original it is compared with */
+{
+  size_t x0, y0, width, height; /* pixels, inside the image, not empty */
+  const uint32_t *pOriginal;    /* the original's pixel for image pixel (x0 + c, y0 + r) at pOriginal[r * originalStridePixels + c]; read only */
+  size_t originalStridePixels;  /* >= width */
+} limg_hip_error_window;
+
+typedef struct limg_hip_error_window_job /* one window of one stream */
+{
+  const uint8_t *pStream; /* DEVICE, 16-byte aligned */
+  size_t streamBytes;
+  size_t sizeX, sizeY;    /* must match the stream's header */
+  limg_hip_error_window window; /* pOriginal: DEVICE, 4-byte aligned */
+} limg_hip_error_window_job;
+
+/* DEVICE pointers inside the jobs and for pErrorSums (count x uint64_t) and pJobStatus (count words, or NULL); pJobs itself is HOST memory and may be reused or freed when
+ * the call returns.  Asynchronous on `stream`. */
+limg_hip_result limg_hip_decode_stream_windows_error_device(limg_hip_context *pCtx, const limg_hip_error_window_job *pJobs, size_t count, uint64_t *pErrorSums,
+                                                            uint32_t *pJobStatus, void *stream);
+limg_hip_result limg_hip_blocked_decode_stream_windows_error_device(limg_hip_context *pCtx, const limg_hip_error_window_job *pJobs, size_t count, uint64_t *pErrorSums,
+                                                                    uint32_t *pJobStatus, void *stream);
+/* HOST pointers, blocking, under the context's mutex: `count` windows of ONE stream.  The image size comes from the header; the stream is uploaded ONCE; every window's
+ * original is staged densely (4 bytes per window pixel, summed); the status is checked before any sum is handed back: a stream refused for any window leaves pErrorSums
+ * (host, count) untouched, in both versions. */
+limg_hip_result limg_hip_decode_stream_windows_error(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_error_window *pWindows, size_t count,
+                                                     uint64_t *pErrorSums);
+limg_hip_result limg_hip_blocked_decode_stream_windows_error(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const limg_hip_error_window *pWindows,
+                                                             size_t count, uint64_t *pErrorSums);
+/* The whole image: HOST pointers, blocking; takes either stream version by its header.  Returns the value, *pMse and *pMax (either may be NULL) of
+ * limg_hip_compare(pOriginal, decode(pStream), sizeX, sizeY, channels == 4) with the size and channel count of the header; `pixels` must be sizeX * sizeY.  NaN on any
+ * refusal (a NULL pointer, a header that is not a stream's, pixels that do not match, a stream refused on the device). */
+double limg_hip_stream_compare(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, const uint32_t *pOriginal, size_t pixels, double *pMse, double *pMax);
+/* Host only, no context: floor(255^2 * (hasAlpha ? 12 : 9) * sizeX * sizeY / 10^(psnr / 10)), the largest error sum whose PSNR by limg_hip_compare_device's constants is
+ * at least `psnr` dB.  0 for a NaN or an empty size; saturates at UINT64_MAX (psnr = -inf). */
+uint64_t limg_hip_error_sum_for_psnr(size_t sizeX, size_t sizeY, int hasAlpha, double psnr);
 
 /* ---- batched window decode into planar float tensors ---------------------------------------------------------------------------
  * The crop + normalise + layout step of an image loader, fused into the decode: every job's window leaves as `planes` planes of float32 or float16 instead of packed

@@ -11,6 +11,7 @@
 #define LIMG_HIP_SHIM_HPP
 
 #include <inttypes.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -243,6 +244,72 @@ inline limg_result limg_encode_budget_batch(const uint32_t *const *ppIn, const s
   {
     pOutSizes[i] = (size_t)res[i].bytes; pErrorFactors[i] = res[i].errorFactor;
     if (pWithinBudget) pWithinBudget[i] = res[i].withinBudget != 0;
+    if (pProbes) pProbes[i] = res[i].probes;
+  }
+  return r;
+}
+
+// limg_compare of an image with a stream's decode, without the decoded image (limg_hip.h "stream error inside the decode"): the value, *pMeanSquaredError and
+// *pMaxPossibleSquaredError of limg_compare(pOriginal, limg_decode(pIn), ...) with the size and channel count of the stream's header; either stream version.
+// `pixels`: of pOriginal, which must be the header's sizeX * sizeY.  NaN where the stream is refused.
+inline double limg_compare_stream(const uint8_t *pIn, const size_t size, const uint32_t *pOriginal, const size_t pixels, double *pMeanSquaredError = nullptr,
+                                  double *pMaxPossibleSquaredError = nullptr)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return NAN;
+  return limg_hip_stream_compare(c, pIn, size, pOriginal, pixels, pMeanSquaredError, pMaxPossibleSquaredError);
+}
+
+// limg_encode to a quality target (limg_hip.h "stream encode to a quality target"): the stream of limg_encode at the coarsest error factor a search over
+// [minErrorFactor, maxErrorFactor] (even, 0 = 2 / 1024) finds whose limg_compare PSNR against pIn is at least minPsnr dB.  *pErrorFactor, *pOutSize: what was chosen and
+// what it takes; *pPsnr (may be NULL): the PSNR of the stream written; *pWithinTarget (may be NULL): false where even minErrorFactor's stream misses the target -- that
+// stream is then what is written, and the call succeeds; *pProbes (may be NULL): errors measured.  A NaN minPsnr: limg_error_InvalidParameter.
+inline limg_result limg_encode_quality(const uint32_t *pIn, const size_t sizeX, const size_t sizeY, const bool hasAlpha, uint8_t *pOut, const size_t outCapacity, size_t *pOutSize,
+                                       const double minPsnr, uint32_t *pErrorFactor, double *pPsnr = nullptr, bool *pWithinTarget = nullptr, uint32_t *pProbes = nullptr,
+                                       const uint32_t minErrorFactor = 0, const uint32_t maxErrorFactor = 0, limg_thread_pool *pThreadPool = nullptr, const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (!pOutSize || !pErrorFactor) return limg_error_ArgumentNull;
+  if (minPsnr != minPsnr) return limg_error_InvalidParameter; // NaN names no target (limg_hip_error_sum_for_psnr would make it 0, the lossless one)
+  limg_hip_quality_result res = { sizeof(limg_hip_quality_result), 0, 0, 0, 0, 0 };
+  const limg_result r = (limg_result)limg_hip_encode_stream_quality(c, pIn, sizeX, sizeY, hasAlpha ? 1 : 0, pOut, outCapacity,
+                                                                    limg_hip_error_sum_for_psnr(sizeX, sizeY, hasAlpha ? 1 : 0, minPsnr), minErrorFactor, maxErrorFactor,
+                                                                    limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0, &res);
+  if (r != limg_success && r != limg_error_OutOfBounds) return r;
+  *pOutSize = (size_t)res.bytes; *pErrorFactor = res.errorFactor;
+  if (pPsnr) *pPsnr = 10.0 * log10(255.0 * 255.0 * (hasAlpha ? 12.0 : 9.0) * (double)sizeX * (double)sizeY / (double)res.errorSum); // limg_compare's, from the sum
+  if (pWithinTarget) *pWithinTarget = res.withinTarget != 0;
+  if (pProbes) *pProbes = res.probes;
+  return r;
+}
+
+// limg_encode_quality of `count` images of one shape in one call: image i gets the stream limg_encode_quality writes for it with pMinPsnr[i], every image on a search
+// of its own over the shared [minErrorFactor, maxErrorFactor].  pOutSizes[i], pErrorFactors[i]: what was chosen and what it takes; pPsnr[i], pWithinTarget[i],
+// pProbes[i] (arrays of `count`, may be NULL) as limg_encode_quality's.  outCapacityEach below some pOutSizes[i]: limg_error_OutOfBounds with all sizes filled and
+// nothing written to any ppOut[i].
+inline limg_result limg_encode_quality_batch(const uint32_t *const *ppIn, const size_t count, const size_t sizeX, const size_t sizeY, const bool hasAlpha, uint8_t *const *ppOut,
+                                             const size_t outCapacityEach, size_t *pOutSizes, const double *pMinPsnr, uint32_t *pErrorFactors, double *pPsnr = nullptr,
+                                             bool *pWithinTarget = nullptr, uint32_t *pProbes = nullptr, const uint32_t minErrorFactor = 0, const uint32_t maxErrorFactor = 0,
+                                             limg_thread_pool *pThreadPool = nullptr, const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (!pOutSizes || !pErrorFactors || !pMinPsnr) return limg_error_ArgumentNull;
+  for (size_t i = 0; i < count; i++)
+    if (pMinPsnr[i] != pMinPsnr[i]) return limg_error_InvalidParameter; // NaN names no target, as in limg_encode_quality
+  const limg_hip_quality_result blank = { sizeof(limg_hip_quality_result), 0, 0, 0, 0, 0 };
+  std::vector<limg_hip_quality_result> res(count ? count : 1, blank);
+  std::vector<uint64_t> limits(count ? count : 1, 0);
+  for (size_t i = 0; i < count; i++) limits[i] = limg_hip_error_sum_for_psnr(sizeX, sizeY, hasAlpha ? 1 : 0, pMinPsnr[i]);
+  const limg_result r = (limg_result)limg_hip_encode_stream_quality_batch(c, count, ppIn, sizeX, sizeY, hasAlpha ? 1 : 0, ppOut, outCapacityEach, limits.data(), minErrorFactor,
+                                                                          maxErrorFactor, limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0, res.data());
+  if (r != limg_success && r != limg_error_OutOfBounds) return r;
+  for (size_t i = 0; i < count; i++)
+  {
+    pOutSizes[i] = (size_t)res[i].bytes; pErrorFactors[i] = res[i].errorFactor;
+    if (pPsnr) pPsnr[i] = 10.0 * log10(255.0 * 255.0 * (hasAlpha ? 12.0 : 9.0) * (double)sizeX * (double)sizeY / (double)res[i].errorSum);
+    if (pWithinTarget) pWithinTarget[i] = res[i].withinTarget != 0;
     if (pProbes) pProbes[i] = res[i].probes;
   }
   return r;

@@ -30,10 +30,13 @@ ABI_SYMBOLS = (
     "limg_hip_stream_info", "limg_hip_encode_stream_batch_device", "limg_hip_encode_stream_batch", "limg_hip_encode_stream_batch_ef_device", "limg_hip_encode_stream_batch_ef",
     "limg_hip_stream_sizes_device", "limg_hip_stream_sizes", "limg_hip_encode_stream_budget_device", "limg_hip_encode_stream_budget",
     "limg_hip_encode_stream_budget_batch_device", "limg_hip_encode_stream_budget_batch",
+    "limg_hip_encode_stream_quality_device", "limg_hip_encode_stream_quality", "limg_hip_encode_stream_quality_batch_device", "limg_hip_encode_stream_quality_batch",
     "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
     "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
     "limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device", "limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window",
     "limg_hip_decode_stream_windows_device", "limg_hip_blocked_decode_stream_windows_device", "limg_hip_decode_stream_windows", "limg_hip_blocked_decode_stream_windows",
+    "limg_hip_decode_stream_windows_error_device", "limg_hip_blocked_decode_stream_windows_error_device", "limg_hip_decode_stream_windows_error",
+    "limg_hip_blocked_decode_stream_windows_error", "limg_hip_stream_compare", "limg_hip_error_sum_for_psnr",
     "limg_hip_decode_stream_windows_tensor_device", "limg_hip_blocked_decode_stream_windows_tensor_device", "limg_hip_decode_stream_windows_tensor",
     "limg_hip_blocked_decode_stream_windows_tensor",
     "limg_hip_decode_stream_windows_scaled_device", "limg_hip_blocked_decode_stream_windows_scaled_device", "limg_hip_decode_stream_windows_scaled_tensor_device",
@@ -91,6 +94,16 @@ class Window(C.Structure):
 class WindowJob(C.Structure):
     """limg_hip_window_job: one window of one stream"""
     _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", Window)]
+
+
+class ErrorWindow(C.Structure):
+    """limg_hip_error_window: one window and the original it is compared with"""
+    _fields_ = [("x0", C.c_size_t), ("y0", C.c_size_t), ("width", C.c_size_t), ("height", C.c_size_t), ("pOriginal", C.c_void_p), ("originalStridePixels", C.c_size_t)]
+
+
+class ErrorWindowJob(C.Structure):
+    """limg_hip_error_window_job: one window of one stream"""
+    _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("sizeX", C.c_size_t), ("sizeY", C.c_size_t), ("window", ErrorWindow)]
 
 
 TENSOR_F32, TENSOR_F16 = 0, 1  # limg_hip_tensor_format.type
@@ -171,6 +184,11 @@ def tensor_format(dtype, planes, scale, bias):
 class BudgetResult(C.Structure):
     """limg_hip_budget_result: what a budgeted stream encode chose"""
     _fields_ = [("struct_size", C.c_uint32), ("errorFactor", C.c_uint32), ("probes", C.c_uint32), ("withinBudget", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+class QualityResult(C.Structure):
+    """limg_hip_quality_result: what a stream encode to a quality target chose"""
+    _fields_ = [("struct_size", C.c_uint32), ("errorFactor", C.c_uint32), ("probes", C.c_uint32), ("withinTarget", C.c_uint32), ("bytes", C.c_uint64), ("errorSum", C.c_uint64)]
 
 
 class Options(C.Structure):
@@ -313,6 +331,22 @@ def load_library(path=None):
     L.limg_hip_encode_stream_budget_batch.restype = C.c_int
     L.limg_hip_encode_stream_budget_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32,
                                                       C.c_int, C.c_int, C.c_void_p]
+    L.limg_hip_encode_stream_quality_device.restype = C.c_int  # ctx, in, sizeX, sizeY, hasAlpha, stream, capacity, maxErrorSum, min ef, max ef, pool, fast, result, hipStream
+    L.limg_hip_encode_stream_quality_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int,
+                                                        C.c_int, C.c_void_p, C.c_void_p]
+    L.limg_hip_encode_stream_quality.restype = C.c_int
+    L.limg_hip_encode_stream_quality.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                                 C.c_void_p]
+    L.limg_hip_encode_stream_quality_batch_device.restype = C.c_int  # ctx, count, ins, sizeX, sizeY, hasAlpha, streams, capacityEach, limits (host), min ef, max ef, pool, fast, results, hipStream
+    L.limg_hip_encode_stream_quality_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
+                                                              C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.limg_hip_encode_stream_quality_batch.restype = C.c_int
+    L.limg_hip_encode_stream_quality_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                       C.c_int, C.c_int, C.c_void_p]
+    L.limg_hip_stream_compare.restype = C.c_double  # ctx, stream, bytes, original, pixels, mse, max
+    L.limg_hip_stream_compare.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.limg_hip_error_sum_for_psnr.restype = C.c_uint64
+    L.limg_hip_error_sum_for_psnr.argtypes = [C.c_size_t, C.c_size_t, C.c_int, C.c_double]
     L.limg_hip_blocked_stream_bound.restype = C.c_size_t
     L.limg_hip_blocked_stream_bound.argtypes = [C.c_size_t, C.c_size_t]
     L.limg_hip_blocked_encode_stream_device.restype = C.c_int
@@ -330,6 +364,8 @@ def load_library(path=None):
             ([P, P, Z] + [Z] * 4 + [P, Z], ("window",)),  # ctx, stream, bytes, x0, y0, width, height, out, outStridePixels
             ([P, P, Z, P, P], ("windows_device", "windows_scaled_device", "windows_resized_device")),  # ctx, jobs (host), count, jobStatus (device), hipStream
             ([P, P, Z, P, Z], ("windows", "windows_scaled", "windows_resized")),  # ctx, stream, bytes, windows (host), count
+            ([P, P, Z, P, P, P], ("windows_error_device",)),  # ctx, jobs (host), count, errorSums (device), jobStatus (device), hipStream
+            ([P, P, Z, P, Z, P], ("windows_error",)),  # ctx, stream, bytes, windows (host), count, errorSums (host)
             ([P, P, Z, P, P, P], ("windows_tensor_device", "windows_scaled_tensor_device", "windows_resized_tensor_device")),  # ctx, jobs (host), count, format (host), jobStatus (device), hipStream
             ([P, P, Z, P, Z, P], ("windows_tensor", "windows_scaled_tensor", "windows_resized_tensor"))):  # ctx, stream, bytes, windows (host), count, format (host)
         for name in names:
@@ -822,6 +858,50 @@ class LimgHip:
         outs = self._stream_list("limg_hip_encode_stream_budget_batch_device", imgs, has_alpha, outs, (budgets, min_error_factor, max_error_factor, pool_threads, int(fast), results), True)
         return outs, results[:len(imgs)]
 
+    # ---- stream encode to a quality target: the coarsest error factor the search finds whose error sum meets the limit (contract: include/limg_hip.h) ----
+    def encode_stream_quality(self, img, has_alpha, max_error_sum, min_error_factor=0, max_error_factor=0, pool_threads=0, fast=True):
+        """host uint32 image -> (stream bytes (numpy uint8), QualityResult): the stream of encode_stream at the error factor the search chose for max_error_sum"""
+        img = np.ascontiguousarray(img, dtype=np.uint32)
+        h, w = img.shape
+        out = np.zeros(self.stream_bound(w, h), dtype=np.uint8)
+        res = QualityResult(C.sizeof(QualityResult))
+        self._stream_call("limg_hip_encode_stream_quality", _np_ptr(img), w, h, int(has_alpha), _np_ptr(out), out.size, int(max_error_sum), min_error_factor, max_error_factor,
+                          pool_threads, int(fast), C.byref(res))
+        return out[:res.bytes].copy(), res
+
+    def encode_stream_quality_device(self, img, has_alpha, max_error_sum, min_error_factor=0, max_error_factor=0, out=None, pool_threads=0, fast=True):
+        """img: torch int32 CUDA (h, w) -> (torch uint8 CUDA stream buffer of worst-case size, QualityResult); waits for torch's current stream once per probe"""
+        import torch
+        h, w = img.shape
+        if out is None:
+            out = torch.empty(self.stream_bound(w, h), dtype=torch.uint8, device=img.device)
+        res = QualityResult(C.sizeof(QualityResult))
+        self._stream_call("limg_hip_encode_stream_quality_device", C.c_void_p(img.data_ptr()), w, h, int(has_alpha), C.c_void_p(out.data_ptr()), out.numel(), int(max_error_sum),
+                          min_error_factor, max_error_factor, pool_threads, int(fast), C.byref(res), self._stream())
+        return out, res
+
+    @staticmethod
+    def _quality_list(max_error_sums, n):
+        limits = [int(max_error_sums)] * n if np.isscalar(max_error_sums) else [int(b) for b in max_error_sums]
+        assert len(limits) == n
+        results = (QualityResult * max(n, 1))()
+        for r in results:
+            r.struct_size = C.sizeof(QualityResult)
+        return (C.c_uint64 * max(n, 1))(*limits), results
+
+    def encode_stream_quality_batch(self, imgs, has_alpha, max_error_sums, min_error_factor=0, max_error_factor=0, pool_threads=0, fast=True):
+        """host uint32 images of one shape, max_error_sums an int or one per image -> (list of stream bytes (numpy uint8), list of QualityResult), one batched call"""
+        limits, results = self._quality_list(max_error_sums, len(imgs))
+        outs = self._stream_list("limg_hip_encode_stream_quality_batch", imgs, has_alpha, None, (limits, min_error_factor, max_error_factor, pool_threads, int(fast), results), False)
+        return [o[:results[k].bytes].copy() for k, o in enumerate(outs)], results[:len(imgs)]
+
+    def encode_stream_quality_batch_device(self, imgs, has_alpha, max_error_sums, min_error_factor=0, max_error_factor=0, outs=None, pool_threads=0, fast=True):
+        """imgs: list of torch int32 CUDA tensors (h, w) of one shape, max_error_sums an int or one per image -> (list of torch uint8 CUDA stream buffers of worst-case
+        size, list of QualityResult).  outs: the buffers to use (each at least stream_bound(w, h) bytes).  Waits for torch's current stream once per round."""
+        limits, results = self._quality_list(max_error_sums, len(imgs))
+        outs = self._stream_list("limg_hip_encode_stream_quality_batch_device", imgs, has_alpha, outs, (limits, min_error_factor, max_error_factor, pool_threads, int(fast), results), True)
+        return outs, results[:len(imgs)]
+
     def blocked_stream_bound(self, w, h):
         return self.lib.limg_hip_blocked_stream_bound(w, h)
 
@@ -958,6 +1038,57 @@ class LimgHip:
 
     def blocked_decode_stream_windows(self, stream, wins, outs=None):
         return self._decode_windows_host("limg_hip_blocked_decode_stream_windows", stream, wins, False, None, outs)
+
+    # ---- stream error inside the decode: windows of streams against originals, a sum per job and no decoded pixel (contract: include/limg_hip.h) ----
+    def _decode_windows_error_device(self, name, jobs, sums, status):
+        import torch
+        table = (ErrorWindowJob * len(jobs))()
+        for i, (stream, nbytes, W, H, x, y, w, h, original, stride) in enumerate(jobs):
+            if stride is None:  # original's own row stride where it has the window's shape, else densely packed
+                stride = original.stride(0) if original.dim() == 2 else w
+            table[i] = ErrorWindowJob(stream.data_ptr(), int(nbytes), W, H, ErrorWindow(x, y, w, h, original.data_ptr(), int(stride)))
+        if sums is None:
+            sums = torch.empty(len(jobs), dtype=torch.int64, device=jobs[0][0].device)
+        self._stream_call(name, table, len(jobs), C.c_void_p(sums.data_ptr()), C.c_void_p(status.data_ptr()) if status is not None else None, self._stream())
+        return sums
+
+    def _decode_windows_error_host(self, name, stream, wins, originals):
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        table = (ErrorWindow * len(wins))()
+        for i, ((x, y, w, h), o) in enumerate(zip(wins, originals)):
+            assert o.dtype == np.uint32 and o.ndim == 2 and o.shape == (h, w) and o.strides[1] == 4 and o.strides[0] % 4 == 0, "original: uint32 (h, w), pixels contiguous"
+            table[i] = ErrorWindow(x, y, w, h, o.ctypes.data, o.strides[0] // 4)
+        sums = (C.c_uint64 * max(len(wins), 1))()
+        self._stream_call(name, _np_ptr(stream), stream.size, table, len(wins), sums)
+        return [int(v) for v in sums[:len(wins)]]
+
+    def decode_stream_windows_error_device(self, jobs, sums=None, status=None):
+        """jobs: (stream tensor, nbytes, W, H, x, y, w, h, original, original_stride) each; original: a torch int32 CUDA tensor whose first element is the original's pixel
+        for image pixel (x, y), rows original_stride pixels apart (None: its own row stride).  sums: torch int64 CUDA tensor of len(jobs) (None allocates); status as in
+        decode_stream_windows_device.  One launch, asynchronous on torch's current stream; nothing but `sums` (and `status`) is written.  Returns sums."""
+        return self._decode_windows_error_device("limg_hip_decode_stream_windows_error_device", jobs, sums, status)
+
+    def blocked_decode_stream_windows_error_device(self, jobs, sums=None, status=None):
+        return self._decode_windows_error_device("limg_hip_blocked_decode_stream_windows_error_device", jobs, sums, status)
+
+    def decode_stream_windows_error(self, stream, wins, originals):
+        """host stream bytes, wins: (x, y, w, h) each, originals: per window a uint32 (h, w) view (rows may be strided) -> the list of error sums (int)"""
+        return self._decode_windows_error_host("limg_hip_decode_stream_windows_error", stream, wins, originals)
+
+    def blocked_decode_stream_windows_error(self, stream, wins, originals):
+        return self._decode_windows_error_host("limg_hip_blocked_decode_stream_windows_error", stream, wins, originals)
+
+    def stream_compare(self, stream, original):
+        """host stream bytes of either version against the host uint32 original -> (psnr, mse) of compare(original, decode_stream(stream)), without the decoded image"""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        original = np.ascontiguousarray(original, dtype=np.uint32)
+        mse, mx = C.c_double(), C.c_double()
+        p = self.lib.limg_hip_stream_compare(self.ctx, _np_ptr(stream), stream.size, _np_ptr(original), original.size, C.byref(mse), C.byref(mx))
+        return p, mse.value
+
+    def error_sum_for_psnr(self, w, h, has_alpha, psnr):
+        """the largest error sum over w x h pixels whose PSNR is at least `psnr` dB: what the quality entries take as their limit"""
+        return int(self.lib.limg_hip_error_sum_for_psnr(w, h, int(has_alpha), float(psnr)))
 
     def decode_stream_windows_tensor_device(self, jobs, fmt, status=None):
         """jobs: (stream tensor, nbytes, W, H, x, y, w, h, out, row_stride, plane_stride) each; out: a torch CUDA tensor of fmt's type whose first element receives

@@ -144,6 +144,7 @@ struct limg_hip_context
     DevBuf rateState{ n }, rateCounter{ n }, rateList{ n }; // size probe (limg_hip_rate.hip): RateDevice; the payload-word counter; the list form's error factors, then its sizes
     DevBuf rated{ n }; // batched stream encode with one error factor per image: one RatedImage (32 bytes) per image of a chunk, the threshold table
     DevBuf table{ n }, sizes{ n }; // batched stream encode: one StreamImage per image of the list; the finished streams' sizes side by side (one download)
+    DevBuf errorSums{ n }; // stream encode to a quality target: one error sum per image of a round (one download)
     // version 2 stream of the merged-block encoder: per rectangle its first 64-pixel run, per tile of rectangles its totals; the decoder's block -> rectangle map and
     // its per-call words
     DevBuf bsUnits{ n }, bsTiles{ n }, bsMap{ n }, bsState{ n };

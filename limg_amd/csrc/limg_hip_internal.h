@@ -330,11 +330,16 @@ namespace limg_hip
     const uint32_t *groupJobs;   // job indices, group after group
     const uint32_t *groupItemBase; // nGroups + 1: exclusive prefix of ceil(nBlocks / 64), the map kernel's work items (64 rectangles each; R <= nBlocks)
     uint32_t nGroups, totalItems;
+    // the error entries (NULL everywhere else): per job the sum of the per-pixel colour error over its window, device memory, zeroed in front of the launch; the jobs'
+    // `out` / outStride / vecOut then describe the ORIGINAL the window is compared with, which is only read
+    unsigned long long *errorSums;
   };
   // f: NULL for packed RGBA8, else the planar float format of the launch (the same job table with planeStride set and out / outStride / vecOut in elements of f's
   // type); scaled: the *_scaled entries' kernels, which honour every job's log2Scale -- a plain job table never goes to them
   void launch_stream_windows(const WindowBatchParams &b, bool scaled, const limg_hip_tensor_format *f, int cus, hipStream_t s);
   void launch_blocked_stream_windows(const WindowBatchParams &b, bool scaled, const limg_hip_tensor_format *f, int cus, hipStream_t s);
+  void launch_stream_windows_error(const WindowBatchParams &b, int cus, hipStream_t s);
+  void launch_blocked_stream_windows_error(const WindowBatchParams &b, int cus, hipStream_t s);
   static_assert(sizeof(WindowDecodeParams) == 128, "the job table's entry: log2Scale must not grow it");
 
   // ---- resized window decode (the *_resized entries): any source rectangle to any output size, bilinear on the level-L image (contract: include/limg_hip.h) ----

@@ -1,8 +1,11 @@
 // limg_hip_stream_encode_api.hip -- the version 1 stream's encode family of the C ABI: limg_hip_encode_stream, limg_hip_encode_stream_batch, limg_hip_encode_stream_batch_ef, limg_hip_stream_sizes,
-// limg_hip_encode_stream_budget and limg_hip_encode_stream_budget_batch, each with its _device form.  The 8x8 encode in compact mode + the packer of
-// limg_hip_stream.hip; the size probe's kernels are limg_hip_rate.hip, the search limg_hip_rate_step.h.  What the twelve entries do alike -- a call's shape, the argument
-// checks, a list's staging, the probe's parameters, the searches' enqueue, the results -- is written once, in the anonymous namespace below.  No kernel is defined here.
+// limg_hip_encode_stream_budget, limg_hip_encode_stream_budget_batch, limg_hip_encode_stream_quality and limg_hip_encode_stream_quality_batch, each with its _device
+// form.  The 8x8 encode in compact mode + the packer of limg_hip_stream.hip; the size probe's kernels are limg_hip_rate.hip, the search limg_hip_rate_step.h; the quality
+// entries measure with the error windows of limg_hip_stream_window_api.hip and search with limg_hip_quality_step.h.  What the sixteen entries do alike -- a call's shape,
+// the argument checks, a list's staging, the probe's parameters, the searches' enqueue, the results -- is written once, in the anonymous namespace below.  No kernel is
+// defined here.
 #include "limg_hip_context.h"
+#include "limg_hip_quality_step.h"
 
 #include <algorithm>
 #include <vector>
@@ -49,20 +52,25 @@ namespace
     return limg_hip_success;
   }
 
-  // minErrorFactor / maxErrorFactor of the budget entries -> the bounds of h = errorFactor / 2, then the `count` budgets and results (the bound rules hold for an empty list too)
-  limg_hip_result check_budgets(size_t count, const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, const limg_hip_budget_result *pResults, uint32_t &hLo,
-                                uint32_t &hHi)
+  // minErrorFactor / maxErrorFactor of the search entries -> the bounds of h = errorFactor / 2, then the `count` results (RESULT: the budget or the quality entries')
+  // and the budgets -- pMaxBytes == NULL: the quality entries, whose limit may be 0 (the bound rules hold for an empty list too)
+  template <class RESULT>
+  limg_hip_result check_search(size_t count, const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, const RESULT *pResults, uint32_t &hLo, uint32_t &hHi)
   {
     const uint32_t lo = minErrorFactor ? minErrorFactor : 2u, hi = maxErrorFactor ? maxErrorFactor : 1024u;
     if ((lo & 1u) || (hi & 1u) || lo < 2u || hi < 2u || lo > hi) return limg_hip_error_InvalidParameter;
     for (size_t i = 0; i < count; i++)
-      if (pMaxBytes[i] == 0 || pResults[i].struct_size < sizeof(limg_hip_budget_result)) return limg_hip_error_InvalidParameter;
+      if ((pMaxBytes && pMaxBytes[i] == 0) || pResults[i].struct_size < sizeof(RESULT)) return limg_hip_error_InvalidParameter;
     hLo = lo / 2u; hHi = hi / 2u;
     return limg_hip_success;
   }
 
   // (the caller's struct_size may be larger than ours: only the members are written)
   void fill_result(limg_hip_budget_result &res, uint32_t ef, uint32_t probes, uint32_t within, uint64_t bytes) { res.errorFactor = ef; res.probes = probes; res.withinBudget = within; res.bytes = bytes; }
+  void fill_result(limg_hip_quality_result &res, uint32_t ef, uint32_t probes, uint32_t within, uint64_t bytes, uint64_t errorSum)
+  {
+    res.errorFactor = ef; res.probes = probes; res.withinTarget = within; res.bytes = bytes; res.errorSum = errorSum;
+  }
 
   // `count` sizes the device holds as 64-bit words -> the caller's size_t: ONE download, waits for `s`
   limg_hip_result download_sizes(const void *dSizes, size_t count, size_t *pBytes, hipStream_t s)
@@ -175,6 +183,18 @@ namespace
 
 namespace
 {
+  // The sizes of `count` finished streams, gathered from their headers on the device: ONE download, waits for `s`.  images: the list (its `stream` members), which goes
+  // into the context's table (stream.table, `count` entries) first; NULL: the table names the streams already.
+  limg_hip_result list_bytes(limg_hip_context *c, const StreamImage *images, size_t count, size_t *pBytes, hipStream_t s)
+  {
+    limg_hip_result r;
+    if ((r = c->stream.sizes.ensure(count * 8)) != limg_hip_success) return r;
+    if (images) launch_set_stream_table((StreamImage *)c->stream.table.p, images, count, s);
+    launch_stream_gather_bytes((const StreamImage *)c->stream.table.p, count, (unsigned long long *)c->stream.sizes.p, s);
+    HIP_TRY(hipGetLastError());
+    return download_sizes(c->stream.sizes.p, count, pBytes, s);
+  }
+
   // ---- a list of same-shape images to streams: what the batch entries do, with one error factor (efs == NULL) or one per image (efs: host, count) ----
   // The images of [0, n) sorted by error factor, one existing call per distinct value -- the single call for a group of one, the shared-factor batch otherwise:
   // what a list with one factor per image falls back to where k_encode_list_rated does not apply.  The same bytes.
@@ -288,12 +308,7 @@ namespace
     }
     c->stats.accumulate = false;
     if (r != limg_hip_success || !pBytes) return r;
-    // the sizes: gathered from the headers on the device
-    if ((r = c->stream.sizes.ensure(count * 8)) != limg_hip_success) return r;
-    if (oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p, images.data(), count, s);
-    launch_stream_gather_bytes((const StreamImage *)c->stream.table.p, count, (unsigned long long *)c->stream.sizes.p, s);
-    HIP_TRY(hipGetLastError());
-    return download_sizes(c->stream.sizes.p, count, pBytes, s);
+    return list_bytes(c, oneByOne ? images.data() : nullptr, count, pBytes, s);
   }
 
   // the host form: upload, stream_list_device on the null stream, status, the streams down at their own sizes
@@ -435,7 +450,7 @@ extern "C"
     uint32_t hLo, hHi;
     limg_hip_result r;
     if ((r = check_single(c, pIn, pStream && pResult, sh, pStream, capacity)) != limg_hip_success) return r;
-    if ((r = check_budgets(1, &maxBytes, minErrorFactor, maxErrorFactor, pResult, hLo, hHi)) != limg_hip_success) return r;
+    if ((r = check_search(1, &maxBytes, minErrorFactor, maxErrorFactor, pResult, hLo, hHi)) != limg_hip_success) return r;
     HIP_TRY(hipSetDevice(c->device));
     RateDevice search;
     RateState &st = search.search = rate_begin(hLo, hHi, maxBytes);
@@ -466,7 +481,7 @@ extern "C"
     uint32_t hLo, hHi;
     limg_hip_result ok;
     if ((ok = check_single(c, pIn, pStream && pResult, sh)) != limg_hip_success) return ok;
-    if ((ok = check_budgets(1, &maxBytes, minErrorFactor, maxErrorFactor, pResult, hLo, hHi)) != limg_hip_success) return ok;
+    if ((ok = check_search(1, &maxBytes, minErrorFactor, maxErrorFactor, pResult, hLo, hHi)) != limg_hip_success) return ok;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
     size_t bytes = 0;
     return encode_stream_host(c, pIn, sizeX, sizeY, pStream, capacity, &bytes, sh.bound, [&](const uint32_t *dIn, uint8_t *dStream, size_t bound, size_t *n) {
@@ -518,7 +533,7 @@ extern "C"
     uint32_t hLo, hHi;
     limg_hip_result r;
     if ((r = check_list(c, pMaxBytes && pResults, count, ppIn, ppStreams, sh, capacityEach, true)) != limg_hip_success) return r;
-    if ((r = check_budgets(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    if ((r = check_search(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
     if (count == 0) return limg_hip_success;
     if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
     HIP_TRY(hipSetDevice(c->device));
@@ -566,7 +581,7 @@ extern "C"
     uint32_t hLo, hHi;
     limg_hip_result r;
     if ((r = check_list(c, pMaxBytes && pResults, count, ppIn, ppStreams, sh, SIZE_MAX, false)) != limg_hip_success) return r; // (capacityEach: the rule below)
-    if ((r = check_budgets(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    if ((r = check_search(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
     if (count == 0) return limg_hip_success;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
     StagedList l;
@@ -581,6 +596,158 @@ extern "C"
     for (size_t i = 0; i < count; i++)
     {
       fill_result(pResults[i], results[i].errorFactor, results[i].probes, results[i].withinBudget, results[i].bytes);
+      fits = fits && results[i].bytes <= capacityEach;
+    }
+    if (!fits) return limg_hip_error_OutOfBounds; // the single host call's rule: the results say what each stream takes, no stream is written
+    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], l.streams[i], (size_t)results[i].bytes, hipMemcpyDeviceToHost));
+    return limg_hip_success;
+  }
+}
+
+// ---- stream encode to a quality target (contract: include/limg_hip.h; the search: limg_hip_quality_step.h) ----
+namespace
+{
+  // The searches of n images over [hLo, hHi], image i's for limits[i], round by round: the images whose search is not over are encoded at their own next value by ONE
+  // limg_hip_encode_stream_batch_ef_device call (a list of one: the single stream encode) into their own buffers, measured against their own pixels by ONE error
+  // launch over the whole images and stepped behind ONE download of the round's sums, which waits for `stream`.  Then at most one more list encode, for the images
+  // whose buffer does not hold the stream of their result, and the streams' sizes from their headers.  The arguments have been checked.
+  limg_hip_result quality_searches(limg_hip_context *c, const StreamShape &sh, size_t n, const uint32_t *const *ppIn, int hasAlpha, uint8_t *const *ppStreams, size_t capacityEach,
+                                   const uint64_t *limits, uint32_t hLo, uint32_t hHi, int poolThreads, int fastBitCrushing, limg_hip_quality_result *pResults, void *stream)
+  {
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    limg_hip_result r;
+    if ((r = c->stream.errorSums.ensure(n * 8)) != limg_hip_success) return r;
+    if ((r = c->stream.table.ensure(n * sizeof(StreamImage))) != limg_hip_success) return r;
+    std::vector<QualityState> st(n);
+    std::vector<uint32_t> held(n, 0u); // the h whose stream image i's buffer holds (0: none yet)
+    for (size_t i = 0; i < n; i++) st[i] = quality_begin(hLo, hHi, limits[i]);
+    std::vector<size_t> active;
+    std::vector<const uint32_t *> in;
+    std::vector<uint8_t *> out;
+    std::vector<uint32_t> efs;
+    std::vector<limg_hip_error_window_job> jobs;
+    std::vector<unsigned long long> sums;
+    // the images of `active` at 2 x their search's next value (where it is over: at the result)
+    auto encode_active = [&]() {
+      in.clear(); out.clear(); efs.clear();
+      for (size_t i : active) { in.push_back(ppIn[i]); out.push_back(ppStreams[i]); efs.push_back(2u * quality_next(st[i])); held[i] = quality_next(st[i]); }
+      return limg_hip_encode_stream_batch_ef_device(c, active.size(), in.data(), sh.sizeX, sh.sizeY, hasAlpha, out.data(), capacityEach, nullptr, efs.data(), poolThreads,
+                                                    fastBitCrushing, stream);
+    };
+    for (uint32_t round = 0, most = rate_max_probes(hLo, hHi); round <= most; round++)
+    {
+      active.clear();
+      for (size_t i = 0; i < n; i++)
+        if (!quality_done(st[i])) active.push_back(i);
+      if (active.empty()) break;
+      if (round == most) return limg_hip_error_Generic; // (cannot happen: no search asks for more)
+      if ((r = encode_active()) != limg_hip_success) return r;
+      jobs.clear();
+      for (size_t i : active)
+      { // (streamBytes: the buffer's size -- the stream's own length is in its header, on the device)
+        const limg_hip_error_window_job j = { ppStreams[i], capacityEach, sh.sizeX, sh.sizeY, { 0, 0, sh.sizeX, sh.sizeY, ppIn[i], sh.sizeX } };
+        jobs.push_back(j);
+      }
+      if ((r = limg_hip_decode_stream_windows_error_device(c, jobs.data(), jobs.size(), (uint64_t *)c->stream.errorSums.p, nullptr, stream)) != limg_hip_success) return r;
+      sums.resize(active.size());
+      HIP_TRY(hipMemcpyAsync(sums.data(), c->stream.errorSums.p, active.size() * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      for (size_t k = 0; k < active.size(); k++) quality_step(st[active[k]], sums[k]);
+    }
+    active.clear();
+    for (size_t i = 0; i < n; i++)
+      if (held[i] != quality_next(st[i])) active.push_back(i);
+    if (!active.empty() && (r = encode_active()) != limg_hip_success) return r;
+    // bytes: the totalBytes of the streams the buffers hold now
+    std::vector<StreamImage> images(n);
+    std::vector<size_t> bytes(n);
+    for (size_t i = 0; i < n; i++) images[i].stream = ppStreams[i];
+    if ((r = list_bytes(c, images.data(), n, bytes.data(), s)) != limg_hip_success) return r;
+    for (size_t i = 0; i < n; i++)
+      fill_result(pResults[i], 2u * quality_next(st[i]), quality_probes(st[i]), quality_within(st[i]), bytes[i], quality_error_sum(st[i]));
+    return limg_hip_success;
+  }
+
+  // fresh results for a host form's device call, which the caller's are filled from afterwards (its struct_size may be larger than ours)
+  std::vector<limg_hip_quality_result> own_results(size_t count)
+  {
+    std::vector<limg_hip_quality_result> results(count);
+    for (size_t i = 0; i < count; i++) { memset(&results[i], 0, sizeof(results[i])); results[i].struct_size = sizeof(limg_hip_quality_result); }
+    return results;
+  }
+}
+
+extern "C"
+{
+  limg_hip_result limg_hip_encode_stream_quality_device(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                                        uint64_t maxErrorSum, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                        limg_hip_quality_result *pResult, void *stream)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = check_single(c, pIn, pStream && pResult, sh, pStream, capacity)) != limg_hip_success) return r;
+    if ((r = check_search(1, nullptr, minErrorFactor, maxErrorFactor, pResult, hLo, hHi)) != limg_hip_success) return r;
+    return quality_searches(c, sh, 1, &pIn, hasAlpha, &pStream, capacity, &maxErrorSum, hLo, hHi, poolThreads, fastBitCrushing, pResult, stream);
+  }
+
+  limg_hip_result limg_hip_encode_stream_quality(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *pStream, size_t capacity,
+                                                 uint64_t maxErrorSum, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                 limg_hip_quality_result *pResult)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    uint32_t hLo, hHi;
+    limg_hip_result ok;
+    if ((ok = check_single(c, pIn, pStream && pResult, sh)) != limg_hip_success) return ok;
+    if ((ok = check_search(1, nullptr, minErrorFactor, maxErrorFactor, pResult, hLo, hHi)) != limg_hip_success) return ok;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    size_t bytes = 0;
+    return encode_stream_host(c, pIn, sizeX, sizeY, pStream, capacity, &bytes, sh.bound, [&](const uint32_t *dIn, uint8_t *dStream, size_t bound, size_t *n) {
+      const limg_hip_result r = limg_hip_encode_stream_quality_device(c, dIn, sizeX, sizeY, hasAlpha, dStream, bound, maxErrorSum, minErrorFactor, maxErrorFactor, poolThreads,
+                                                                      fastBitCrushing, pResult, nullptr);
+      if (r == limg_hip_success) *n = (size_t)pResult->bytes;
+      return r;
+    });
+  }
+
+  // ---- ... of a list: result i = limg_hip_encode_stream_quality_device of image i with pMaxErrorSums[i] ----
+  limg_hip_result limg_hip_encode_stream_quality_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                              uint8_t *const *ppStreams, size_t capacityEach, const uint64_t *pMaxErrorSums, uint32_t minErrorFactor,
+                                                              uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing, limg_hip_quality_result *pResults, void *stream)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = check_list(c, pMaxErrorSums && pResults, count, ppIn, ppStreams, sh, capacityEach, true)) != limg_hip_success) return r;
+    if ((r = check_search(count, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    return quality_searches(c, sh, count, ppIn, hasAlpha, ppStreams, capacityEach, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults, stream);
+  }
+
+  limg_hip_result limg_hip_encode_stream_quality_batch(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                                       uint8_t *const *ppStreams, size_t capacityEach, const uint64_t *pMaxErrorSums, uint32_t minErrorFactor,
+                                                       uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing, limg_hip_quality_result *pResults)
+  {
+    const StreamShape sh(sizeX, sizeY);
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = check_list(c, pMaxErrorSums && pResults, count, ppIn, ppStreams, sh, SIZE_MAX, false)) != limg_hip_success) return r; // (capacityEach: the rule below)
+    if ((r = check_search(count, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    StagedList l;
+    if ((r = stage_list(c, sh, count, ppIn, l)) != limg_hip_success) return r;
+    std::vector<limg_hip_quality_result> results = own_results(count);
+    if ((r = limg_hip_encode_stream_quality_batch_device(c, count, l.in.data(), sizeX, sizeY, hasAlpha, l.streams.data(), l.slice, pMaxErrorSums, minErrorFactor, maxErrorFactor,
+                                                         poolThreads, fastBitCrushing, results.data(), nullptr)) != limg_hip_success)
+      return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    bool fits = true;
+    for (size_t i = 0; i < count; i++)
+    {
+      fill_result(pResults[i], results[i].errorFactor, results[i].probes, results[i].withinTarget, results[i].bytes, results[i].errorSum);
       fits = fits && results[i].bytes <= capacityEach;
     }
     if (!fits) return limg_hip_error_OutOfBounds; // the single host call's rule: the results say what each stream takes, no stream is written

@@ -43,7 +43,15 @@
 // The work item is an output TILE of a job and belongs to a whole workgroup (k_stream_windows_resized[_tensor<T>], k_bstream_windows_resized[_tensor<T>]): its waves
 // run the unit bodies above over the tile's level-L footprint with ScaledStore<TileStore> -- into an LDS tile instead of the output --, synchronise, and resample
 // bilinearly from LDS by the contract's integer formula.  A second per-job table (ResizeJob) carries what WindowDecodeParams has no room for.
+//
+// Error forms (limg_hip_*decode_stream_windows_error*): the batched kernels with a policy that stores nothing.  ErrorSink reads the ORIGINAL's 8 pixels where RgbaStore
+// would write the decoded ones (p.out / outStride / vecOut then describe the original; the loads are requested before the lane's decode arithmetic) and adds the
+// reference's per-pixel colour error -- k_compare's integer sum (limg_hip_synth.hip) -- to the lane's 32-bit partial.  ErrorTotal, the bodies' second policy, reduces
+// the partials once per unit into a wave-uniform 64-bit total and adds that to the job's sum with one device-scope atomic when the wave's job changes; where the
+// waves' loops end, the four waves of a workgroup hand their totals to one thread through 48 bytes of LDS (ErrorEnd), which adds them with one atomic per job.  k_stream_windows_error / k_bstream_windows_error; k_bstream_windows_map serves them as it is.
 #include "limg_hip_stream_format.h"
+
+#include <type_traits>
 
 namespace limg_hip
 {
@@ -124,6 +132,151 @@ namespace limg_hip
         }
       }
     };
+
+    // ---- the error forms: nothing is stored -----------------------------------------------------------------------------------------------
+    // What the error bodies keep per wave.  lane: the lane's partial of the current unit -- 8 pixels are below 2^23 (12 x 255^2 x 8), the at most 8 rows a lane decodes
+    // in a version 1 unit below 2^26 and a whole unit of 64 blocks below 2^32 (12 x 255^2 x 4096), so 32 bits hold every sum inside a unit.  total, job: the sum of
+    // the units since the last flush and the job they belong to, wave-uniform (scalar registers).  alpha: the current job's header says 4 channels.
+    // ErrorEnd: where the four waves of a workgroup leave what they hold when their loops end, so that one of them adds it to the sums.  Every atomic of a whole-image
+    // call names one address, where they are served one after the other, and the waves' loops end together: left to each wave, thousands of them queue up behind the
+    // kernel's last unit (profiles/stream_error.md).
+    struct ErrorEnd { unsigned long long total[4]; uint32_t job[4]; };
+    struct ErrorTotal
+    {
+      static constexpr bool kKeepsJob = true; // (version 2's body)
+      unsigned long long *sums;
+      ErrorEnd &end;
+      uint32_t lane = 0, job = 0;
+      unsigned long long total = 0;
+      bool alpha = false;
+      // one 64-bit device-scope atomic for all units of `job` since the last one
+      __device__ __forceinline__ void flush()
+      {
+        if (total != 0ull && lane_id() == 0) atomicAdd(sums + job, total);
+        total = 0ull;
+      }
+      __device__ __forceinline__ void begin_unit(uint32_t unitJob, uint32_t channels)
+      {
+        if (unitJob != job) flush(); // (wave-uniform)
+        job = unitJob; alpha = channels == 4u;
+      }
+      // every lane is here (the unit bodies' branches have joined): the partials' sum within each row of 16 lanes through DPP, the four rows' through scalar reads
+      __device__ __forceinline__ void end_unit()
+      {
+        uint32_t v = lane;
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1 /* quad_perm:[1,0,3,2] */, 0xF, 0xF, false);
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E /* quad_perm:[2,3,0,1] */, 0xF, 0xF, false);
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141 /* row_half_mirror */, 0xF, 0xF, false);
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140 /* row_mirror */, 0xF, 0xF, false);
+        total += (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
+                 (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+        lane = 0;
+      }
+      // the wave's loop has ended, and so will every other wave's of the workgroup (no wave leaves a body early): the four totals, those of one job added up, by
+      // thread 0 with at most four atomics -- one where the workgroup ended inside one job
+      __device__ __forceinline__ void finish()
+      {
+        const uint32_t wave = threadIdx.x >> 6;
+        if (lane_id() == 0) { end.total[wave] = total; end.job[wave] = job; }
+        __syncthreads();
+        if (threadIdx.x == 0)
+          for (uint32_t w = 0; w < 4u; w++)
+          {
+            unsigned long long t = end.total[w];
+            if (t == 0ull) continue;
+            for (uint32_t v = w + 1u; v < 4u; v++)
+              if (end.job[v] == end.job[w]) { t += end.total[v]; end.total[v] = 0ull; }
+            atomicAdd(sums + end.job[w], t);
+          }
+        total = 0ull;
+      }
+    };
+    // the bodies' second policy for every kernel that stores: nothing to keep
+    struct NoTotal
+    {
+      static constexpr bool kKeepsJob = false;
+      __device__ __forceinline__ void begin_unit(uint32_t, uint32_t) const {}
+      __device__ __forceinline__ void end_unit() const {}
+      __device__ __forceinline__ void finish() const {}
+    };
+
+    // The original's 8 pixels beside the lane's decoded ones, columns x .. x + 7 of image row y; p.out is the ORIGINAL, read only, and the inside / edge rule is
+    // RgbaStore's: a piece wholly inside the window arrives as two 16-byte loads where the original's pointer, stride and x0 allow them (vecOut), else pixel by pixel,
+    // and only pixels inside the window are read or counted.
+    struct ErrorSink
+    {
+      ErrorTotal &t;
+      struct Loaded { uint32_t px[8]; uint32_t inside; }; // inside: bit i = pixel i lies in the window
+      // requested before the lane's decode arithmetic, which then runs while the loads are in flight; the caller has checked that y is a row of the window
+      __device__ __forceinline__ Loaded load(const WindowDecodeParams &p, uint32_t x, uint32_t y) const
+      {
+        Loaded o;
+        const uint32_t *row = p.out + (unsigned long long)(y - p.y0) * p.outStride;
+        if (p.vecOut && x >= p.x0 && x + 8u <= p.x0 + p.width)
+        {
+          const uint4 *src = reinterpret_cast<const uint4 *>(row + (x - p.x0));
+          const uint4 a = src[0], b = src[1];
+          o.px[0] = a.x; o.px[1] = a.y; o.px[2] = a.z; o.px[3] = a.w; o.px[4] = b.x; o.px[5] = b.y; o.px[6] = b.z; o.px[7] = b.w;
+          o.inside = 0xFFu;
+          return o;
+        }
+        o.inside = 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++)
+        {
+          const bool in = x + i >= p.x0 && x + i < p.x0 + p.width;
+          o.px[i] = in ? row[x + i - p.x0] : 0u;
+          o.inside |= in ? 1u << i : 0u;
+        }
+        return o;
+      }
+      // k_compare's sum per pixel: red^2 x (2 | 3) + green^2 x 4 + blue^2 x (3 | 2) + alpha^2 x 3, the weights swapped where red^2 >= 0x4000, alpha in 4-channel streams only.
+      // Two channels at a time: the even bytes (red, blue) and the odd bytes (green, alpha) of both pixels as pairs of 16-bit values, their differences and the
+      // differences' squares (at most 255^2: 16 bits hold them) as packed 16-bit operations, each pair weighted and added by one dot product.  ALL: every pixel lies in
+      // the window; else a pixel outside it is compared with itself.
+      typedef short short2v __attribute__((ext_vector_type(2)));
+      typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
+      template <bool ALL>
+      __device__ __forceinline__ uint32_t row_error(const uint32_t dd[8], const Loaded &o) const
+      {
+        constexpr uint32_t kOdd = 0x0C030C01u; // v_perm_b32: bytes 1 and 3 into bytes 0 and 2, zeros between them
+        const ushort2v wOdd = __builtin_bit_cast(ushort2v, t.alpha ? 0x00030004u : 0x00000004u); // (wave-uniform)
+        uint32_t sum = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++)
+        {
+          const uint32_t d = dd[i], q = ALL || ((o.inside >> i) & 1u) ? o.px[i] : d;
+          const short2v even = __builtin_bit_cast(short2v, d & 0x00FF00FFu) - __builtin_bit_cast(short2v, q & 0x00FF00FFu);
+          const short2v odd = __builtin_bit_cast(short2v, __builtin_amdgcn_perm(d, d, kOdd)) - __builtin_bit_cast(short2v, __builtin_amdgcn_perm(q, q, kOdd));
+          const ushort2v sqEven = __builtin_bit_cast(ushort2v, even * even), sqOdd = __builtin_bit_cast(ushort2v, odd * odd);
+          const bool low = (__builtin_bit_cast(uint32_t, sqEven) & 0xC000u) == 0u; // red^2 < 0x4000
+          sum = __builtin_amdgcn_udot2(sqEven, __builtin_bit_cast(ushort2v, low ? 0x00030002u : 0x00020003u), sum, false);
+          sum = __builtin_amdgcn_udot2(sqOdd, wOdd, sum, false);
+        }
+        return sum;
+      }
+      __device__ __forceinline__ void operator()(const WindowDecodeParams &, uint32_t, uint32_t, const uint32_t px[8], const Loaded &o) const
+      {
+        uint32_t dd[8];
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++)
+        {
+          dd[i] = px[i];
+          asm volatile("" : "+v"(dd[i])); // (the packed pixels, as in PlanarStore and for its reason)
+        }
+        t.lane += o.inside == 0xFFu ? row_error<true>(dd, o) : row_error<false>(dd, o);
+      }
+    };
+
+    // What a unit body does around a lane's decode: before_decode where the lane knows its pixels' place, after_decode with the decoded pixels.  Every store policy has
+    // nothing to do before and stores after; ErrorSink requests the original first.
+    struct Nothing {};
+    template <class STORE>
+    __device__ __forceinline__ Nothing before_decode(const STORE &, const WindowDecodeParams &, uint32_t, uint32_t) { return Nothing(); }
+    __device__ __forceinline__ ErrorSink::Loaded before_decode(const ErrorSink &s, const WindowDecodeParams &p, uint32_t x, uint32_t y) { return s.load(p, x, y); }
+    template <class STORE>
+    __device__ __forceinline__ void after_decode(const STORE &store, const WindowDecodeParams &p, uint32_t x, uint32_t y, const uint32_t px[8], const Nothing &) { store(p, x, y, px); }
+    __device__ __forceinline__ void after_decode(const ErrorSink &s, const WindowDecodeParams &p, uint32_t x, uint32_t y, const uint32_t px[8], const ErrorSink::Loaded &o) { s(p, x, y, px, o); }
 
     // ---- reduced scale (the *_scaled entries): the job's level L, k = 1 << L -------------------------------------------------------------
     // p describes the job's source footprint, multiples of k; output pixel (X, Y) is the rounded mean of the k x k box at (k X, k Y), byte by byte.  A box never leaves
@@ -354,6 +507,7 @@ namespace limg_hip
         const uint32_t x = (bxUnit + G.t) * 8u;
         if (G.valid && G.ok && y >= p.y0 && y < p.y0 + p.height && x + 8u > p.x0 && x < p.x0 + p.width)
         {
+          const auto before = before_decode(store, p, x, y);
           const uint32_t *e = S.entry[G.t];
           const uint32_t sw = e[12];
           uint32_t fieldByte = (G.myOff - G.off0) * 8u, bb[3], shift[3];
@@ -373,7 +527,7 @@ namespace limg_hip
           const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(e[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, channels);
           uint32_t px[8];
           decode_row(k16, packed, bb, px);
-          store(p, x, y, px);
+          after_decode(store, p, x, y, px, before);
         }
         wave_lds_fence(); // every lane is done reading this group's run
       }
@@ -440,8 +594,9 @@ namespace limg_hip
       if (b.jobStatus) atomicOr(b.jobStatus + job, bits);
     }
 
-    template <class STORE>
-    __device__ __forceinline__ void stream_windows_body(const WindowBatchParams &b, WindowWaveLds (&sW)[4], const STORE &store)
+    // total: what the body keeps across its units (NoTotal; the error kernel's ErrorTotal, which its ErrorSink adds to)
+    template <class STORE, class TOTAL = NoTotal>
+    __device__ __forceinline__ void stream_windows_body(const WindowBatchParams &b, WindowWaveLds (&sW)[4], const STORE &store, TOTAL &&total = TOTAL())
     {
       const int lane = lane_id();
       const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -457,8 +612,11 @@ namespace limg_hip
           continue;
         }
         const uint2 *payload = reinterpret_cast<const uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)p.nBlocks * kEntry);
+        total.begin_unit(job, h->channels);
         window_unit(p, S, unit - first, (p.wbx + 63u) / 64u, (int)h->channels, h->payloadWords, payload, lane, [&](uint32_t bits) { raise_job(b, job, bits); }, store);
+        total.end_unit();
       }
+      total.finish();
     }
 
     __global__ __launch_bounds__(256) void k_stream_windows_decode(const WindowBatchParams b)
@@ -486,6 +644,15 @@ namespace limg_hip
     {
       __shared__ __align__(16) WindowWaveLds sW[4];
       stream_windows_body(b, sW, ScaledStore<PlanarStore<T>>{ PlanarStore<T>{ f } });
+    }
+
+    // the *_error entries: the same body, the jobs' sums instead of their pixels (b.errorSums: zeroed in front of the launch)
+    __global__ __launch_bounds__(256) void k_stream_windows_error(const WindowBatchParams b)
+    {
+      __shared__ __align__(16) WindowWaveLds sW[4];
+      __shared__ ErrorEnd sEnd;
+      ErrorTotal t{ as_global(b.errorSums), sEnd };
+      stream_windows_body(b, sW, ErrorSink{ t }, t);
     }
 
     // ---- version 2 -------------------------------------------------------------------------------------------------------------------
@@ -634,10 +801,13 @@ namespace limg_hip
           fieldByte += (unsigned long long)field_words(n, b) * 8ull;
         }
       }
+      // (behind the last load of the chain map -> entry -> payload: loads return in order, so anything requested ahead of the chain would have to arrive before its
+      // next link could be read, and the chain's links come from the cache where the original comes from memory)
+      const auto before = before_decode(store, p, x, y);
       const A16 k16 = a16_constants([&](int v, int c) { return (int)(int16_t)(ev[2 * v + (c >> 1)] >> (16 * (c & 1))); }, shift, (int)channels);
       uint32_t px[8];
       decode_row(k16, packed, bb, px);
-      store(p, x, y, px); // (columns beyond a partial last block column lie outside the image, so outside the window)
+      after_decode(store, p, x, y, px, before); // (columns beyond a partial last block column lie outside the image, so outside the window)
     }
 
     __global__ __launch_bounds__(256) void k_bstream_window_decode(const WindowDecodeParams p)
@@ -725,26 +895,53 @@ namespace limg_hip
       }
     }
 
-    template <class STORE>
-    __device__ __forceinline__ void bstream_windows_body(const WindowBatchParams &b, const STORE &store)
+    // TOTAL::kKeepsJob (the error kernel): a job is typically a whole image, thousands of consecutive units, so what a unit needs to know about its job -- the table
+    // entry, the verdict, the header -- is kept in scalar registers while the wave's units stay inside the job's range first .. end - 1 and read once per run of them
+    // (the header by scalar loads, as k_bstream_window_decode reads it); the kernels that store look everything up per unit, as they did.  (GPU time of
+    // k_bstream_windows_error with the per-unit lookup instead: profiles/stream_error.md, "Version 2's error kernel".)
+    template <class STORE, class TOTAL = NoTotal>
+    __device__ __forceinline__ void bstream_windows_body(const WindowBatchParams &b, const STORE &store, TOTAL &&total = TOTAL())
     {
+      constexpr bool keeps = std::remove_reference_t<TOTAL>::kKeepsJob;
       const int lane = lane_id();
       const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      uint32_t job = 0, first = 0, end = 0, nRects = 0, channels = 0;
+      unsigned long long tableEnd = 0, streamEnd = 0;
+      bool refused = false;
+      WindowDecodeParams p;
       for (uint32_t unit = blockIdx.x * 4u + wave; unit < b.totalUnits; unit += gridDim.x * 4u) // (wave-uniform)
       {
-        const uint32_t job = find_slot(b.unitBase, b.count, unit), first = load_uniform(b.unitBase + job);
-        const WindowDecodeParams p = load_job(b, job);
-        // the job's verdict from k_bstream_windows_map: nothing flagged and every block of its window claimed exactly once
-        if (ld_volatile(p.state + 1) != 0u || ld_volatile(p.state) != p.wbx * p.wby)
+        if (!keeps || unit < first || unit >= end)
+        {
+          job = find_slot(b.unitBase, b.count, unit); first = load_uniform(b.unitBase + job);
+          if constexpr (keeps) end = load_uniform(b.unitBase + job + 1u);
+          p = load_job(b, job);
+          // the job's verdict from k_bstream_windows_map: nothing flagged and every block of its window claimed exactly once
+          refused = ld_volatile(p.state + 1) != 0u || ld_volatile(p.state) != p.wbx * p.wby;
+          if constexpr (keeps)
+            if (!refused)
+            {
+              const limg_hip_stream_header h = load_uniform(reinterpret_cast<const limg_hip_stream_header *>(p.stream));
+              nRects = h.reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES]; channels = h.channels;
+              tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry; streamEnd = tableEnd + h.payloadWords * 8ull;
+            }
+        }
+        if (refused)
         {
           if (unit == first && lane == 0) raise_job(b, job, 2u);
           continue;
         }
-        const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
-        const uint32_t nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES], channels = h->channels;
-        const unsigned long long tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry, total = tableEnd + h->payloadWords * 8ull;
-        bwindow_unit(p, unit - first, (p.wbx + 7u) / 8u, nRects, channels, tableEnd, total, lane, store);
+        if constexpr (!keeps)
+        {
+          const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(p.stream);
+          nRects = h->reserved[LIMG_HIP_STREAM_RESERVED_RECTANGLES]; channels = h->channels;
+          tableEnd = sizeof(limg_hip_stream_header) + (unsigned long long)nRects * kRectEntry; streamEnd = tableEnd + h->payloadWords * 8ull;
+        }
+        total.begin_unit(job, channels);
+        bwindow_unit(p, unit - first, (p.wbx + 7u) / 8u, nRects, channels, tableEnd, streamEnd, lane, store);
+        total.end_unit();
       }
+      total.finish();
     }
 
     __global__ __launch_bounds__(256) void k_bstream_windows_decode(const WindowBatchParams b) { bstream_windows_body(b, RgbaStore()); }
@@ -759,6 +956,14 @@ namespace limg_hip
     __global__ __launch_bounds__(256, 8) void k_bstream_windows_scaled_tensor(const WindowBatchParams b, const limg_hip_tensor_format f)
     {
       bstream_windows_body(b, ScaledStore<PlanarStore<T>>{ PlanarStore<T>{ f } });
+    }
+
+    // (70 vector registers, 7 waves per SIMD as k_bstream_windows_decode's 66; held to 64 for the eighth it would spill two of them to scratch)
+    __global__ __launch_bounds__(256) void k_bstream_windows_error(const WindowBatchParams b)
+    {
+      __shared__ ErrorEnd sEnd;
+      ErrorTotal t{ as_global(b.errorSums), sEnd };
+      bstream_windows_body(b, ErrorSink{ t }, t);
     }
 
     // ---- resized, both versions ------------------------------------------------------------------------------------------------------------
@@ -954,6 +1159,20 @@ namespace limg_hip
   {
     hipLaunchKernelGGL(k_bstream_windows_map, window_grid(b.totalItems, cus, 8u), dim3(256), 0, s, b);
     launch_windows_decode(true, scaled, f, b, window_grid(b.totalUnits, cus, 8u), s);
+  }
+
+  // the error forms: the batched launches with the error kernels (b.errorSums set, zeroed on `s` in front of this)
+  void launch_stream_windows_error(const WindowBatchParams &b, int cus, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_stream_windows_error, window_grid(b.totalUnits, cus, 4u), dim3(256), 0, s, b);
+  }
+
+  void launch_blocked_stream_windows_error(const WindowBatchParams &b, int cus, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_bstream_windows_map, window_grid(b.totalItems, cus, 8u), dim3(256), 0, s, b);
+    // 7 residency slots per CU, what the kernel's 70 vector registers allow: an eighth workgroup per CU would start only when one of the seven has ended and run its
+    // units as a second round behind them
+    hipLaunchKernelGGL(k_bstream_windows_error, window_grid(b.totalUnits, cus, 7u), dim3(256), 0, s, b);
   }
 
   // the resized forms: a workgroup per output tile, persistent over the call's tiles.  Residency slots per CU: 4 for version 1 (111 vector registers; 4 x (4

@@ -1,8 +1,12 @@
 // limg_hip_stream_window_api.hip -- the window decode entries of the C ABI (limg_hip_*decode_stream_window*; kernels: limg_hip_stream_window.hip): one window or a
 // table of them, into packed RGBA8 or planar float tensors, at full or reduced scale, from device or host memory, of either stream version.  Three things vary and each
 // is stated once: the stream version (StreamVersion: two constants), the public window struct (window_view / stage_window) and where the pixels go (WindowOut).
+// The error entries (limg_hip_*decode_stream_windows_error*, limg_hip_stream_compare, limg_hip_error_sum_for_psnr) are the batched RGBA8 entries with a window whose
+// pixels come from the caller -- the original the decode is compared with -- and a sum per job as the only thing written.
 // No kernel lives here.
 #include "limg_hip_context.h"
+
+#include <math.h>
 
 #include <algorithm>
 #include <type_traits>
@@ -52,11 +56,20 @@ namespace
   template <class WIN> struct IsScaled<WIN, std::void_t<decltype(WIN::log2Scale)>> : std::true_type {};
   template <class WIN, class = void> struct IsResized : std::false_type {}; // limg_hip_resized_[tensor_]window: outWidth, outHeight, flags
   template <class WIN> struct IsResized<WIN, std::void_t<decltype(WIN::outWidth)>> : std::true_type {};
+  template <class WIN, class = void> struct IsError : std::false_type {}; // limg_hip_error_window: pOriginal and its stride where the others have pOut -- read, never written
+  template <class WIN> struct IsError<WIN, std::void_t<decltype(WIN::pOriginal)>> : std::true_type {};
 
+  // the window's pixels: the output of every entry but the error ones, whose window names the original
+  template <class WIN> void *window_pixels(const WIN &w)
+  {
+    if constexpr (IsError<WIN>::value) return (void *)w.pOriginal;
+    else return (void *)w.pOut;
+  }
   template <class WIN> WindowView window_view(const WIN &w, const limg_hip_tensor_format *f)
   {
-    WindowView v = { w.x0, w.y0, w.width, w.height, 0, { w.pOut, 0, 0, 4u, 0u } };
+    WindowView v = { w.x0, w.y0, w.width, w.height, 0, { window_pixels(w), 0, 0, 4u, 0u } };
     if constexpr (IsPlanar<WIN>::value) v.out = { w.pOut, w.rowStride, w.planeStride, f->type == LIMG_HIP_TENSOR_F16 ? 2u : 4u, f->planes };
+    else if constexpr (IsError<WIN>::value) v.out.rowStride = w.originalStridePixels;
     else v.out.rowStride = w.outStridePixels;
     if constexpr (IsScaled<WIN>::value) v.level = w.log2Scale;
     if constexpr (IsResized<WIN>::value) { v.resized = true; v.outW = w.outWidth; v.outH = w.outHeight; v.flags = w.flags; }
@@ -65,11 +78,15 @@ namespace
   // ... and back: the staged form of a window, densely packed at `p`
   template <class WIN> void stage_window(WIN &w, void *p)
   {
-    w.pOut = (decltype(w.pOut))p;
     size_t width = w.width, height = w.height;
     if constexpr (IsResized<WIN>::value) { width = w.outWidth; height = w.outHeight; }
-    if constexpr (IsPlanar<WIN>::value) { w.rowStride = width; w.planeStride = width * height; }
-    else w.outStridePixels = width;
+    if constexpr (IsError<WIN>::value) { w.pOriginal = (const uint32_t *)p; w.originalStridePixels = width; }
+    else
+    {
+      w.pOut = (decltype(w.pOut))p;
+      if constexpr (IsPlanar<WIN>::value) { w.rowStride = width; w.planeStride = width * height; }
+      else w.outStridePixels = width;
+    }
   }
   WindowView rgba_view(size_t x0, size_t y0, size_t width, size_t height, uint32_t *pOut, size_t outStridePixels)
   {
@@ -261,14 +278,15 @@ namespace
 
   // One call: every job checked on the host before anything touches the device, then the job table built in a pinned slot of the context's ring, copied on `s`,
   // and the version's one (two) launches.  JOB: any of the four public job types -- its window says whether the pixels go to planes of pFormat's type (else pFormat is
-  // not looked at) and whether it carries a level, which then selects the scaled kernels: the same checks, table and launches otherwise.
+  // not looked at) and whether it carries a level, which then selects the scaled kernels: the same checks, table and launches otherwise.  The error job type: its
+  // window names the original, which is checked as an output is and never written; pErrorSums (device, count) is zeroed on `s` and is all the launch writes.
   template <class JOB>
   limg_hip_result decode_windows_device(limg_hip_context *c, const StreamVersion &v, const JOB *pJobs, size_t count, const limg_hip_tensor_format *pFormat, uint32_t *pJobStatus,
-                                        hipStream_t s)
+                                        hipStream_t s, uint64_t *pErrorSums = nullptr)
   {
     typedef decltype(JOB::window) WIN;
-    constexpr bool tensor = IsPlanar<WIN>::value, scaled = IsScaled<WIN>::value, resized = IsResized<WIN>::value;
-    if (!c || !pJobs || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
+    constexpr bool tensor = IsPlanar<WIN>::value, scaled = IsScaled<WIN>::value, resized = IsResized<WIN>::value, error = IsError<WIN>::value;
+    if (!c || !pJobs || (tensor && !pFormat) || (error && !pErrorSums)) return limg_hip_error_ArgumentNull;
     if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
     if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
     const bool rects = v.rectangles;
@@ -284,7 +302,7 @@ namespace
     for (size_t i = 0; i < count; i++)
     {
       const JOB &j = pJobs[i];
-      if (!j.pStream || !j.window.pOut) return limg_hip_error_ArgumentNull;
+      if (!j.pStream || !window_pixels(j.window)) return limg_hip_error_ArgumentNull;
       const limg_hip_result r = fill(j, wp);
       if (r != limg_hip_success) return r;
       if (v.tableExtent && j.streamBytes < sizeof(limg_hip_stream_header) + (size_t)wp.nBlocks * sizeof(limg_hip_stream_block)) return limg_hip_error_OutOfBounds;
@@ -352,6 +370,7 @@ namespace
     b.jobs = (const WindowDecodeParams *)(db + oJobs); b.unitBase = (const uint32_t *)(db + oUnitBase);
     b.count = (uint32_t)count; b.totalUnits = unitAt;
     b.status = (uint32_t *)c->stream.status.p; b.jobStatus = pJobStatus;
+    b.errorSums = (unsigned long long *)pErrorSums;
     if (rects)
     { // groups: the jobs sorted by stream (in place, in the table: no allocation), then one group per run of equal keys
       WindowGroup *groups = (WindowGroup *)(hb + oGroups);
@@ -396,7 +415,12 @@ namespace
       HIP_TRY(hipMemsetAsync(db + oMap, 0xFF, (size_t)blocks * 4, s)); // no block has a rectangle yet
     }
     if (pJobStatus) HIP_TRY(hipMemsetAsync(pJobStatus, 0, count * 4, s));
-    if (resized)
+    if (error)
+    {
+      HIP_TRY(hipMemsetAsync(pErrorSums, 0, count * 8, s));
+      (rects ? launch_blocked_stream_windows_error : launch_stream_windows_error)(b, device_cus(c), s);
+    }
+    else if (resized)
     { // a workgroup per output tile; version 2's map kernel first, as it is
       const WindowResizeParams rp = { b, (const ResizeJob *)(db + oResize), (const uint32_t *)(db + oTileBase), tileAt };
       (rects ? launch_blocked_stream_windows_resized : launch_stream_windows_resized)(rp, tensor ? pFormat : nullptr, device_cus(c), s);
@@ -409,13 +433,14 @@ namespace
     return limg_hip_success;
   }
 
-  // `count` windows of ONE host stream, JOB as above: every window is stated, checked and staged in its level's coordinates
+  // `count` windows of ONE host stream, JOB as above: every window is stated, checked and staged in its level's coordinates.  The error job type: the staged windows
+  // are the originals, which go UP in front of the call, and what comes down behind the status check are the `count` sums (pErrorSums, host), staged behind them.
   template <class JOB>
   limg_hip_result decode_windows_host(limg_hip_context *c, const StreamVersion &v, const uint8_t *pStream, size_t streamBytes, const decltype(JOB::window) *pWindows, size_t count,
-                                      const limg_hip_tensor_format *pFormat)
+                                      const limg_hip_tensor_format *pFormat, uint64_t *pErrorSums = nullptr)
   {
-    constexpr bool tensor = IsPlanar<decltype(JOB::window)>::value;
-    if (!c || !pStream || !pWindows || (tensor && !pFormat)) return limg_hip_error_ArgumentNull;
+    constexpr bool tensor = IsPlanar<decltype(JOB::window)>::value, error = IsError<decltype(JOB::window)>::value;
+    if (!c || !pStream || !pWindows || (tensor && !pFormat) || (error && !pErrorSums)) return limg_hip_error_ArgumentNull;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
     if (count == 0 || count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
     if (tensor && !tensor_format_ok(pFormat)) return limg_hip_error_InvalidParameter;
@@ -445,8 +470,9 @@ namespace
     struct Free { JOB *p; ~Free() { delete[] p; } } freeJobs = { jobs };
     HIP_TRY(hipSetDevice(c->device));
     if ((r = c->stream.buf.ensure(total + 16)) != limg_hip_success) return r;
-    if ((r = c->host.planes.ensure(elems * eb)) != limg_hip_success) return r;
+    if ((r = c->host.planes.ensure(elems * eb + (error ? count * 8 : 0))) != limg_hip_success) return r;
     HIP_TRY(hipMemcpy(c->stream.buf.p, pStream, total, hipMemcpyHostToDevice)); // once, for all windows
+    uint64_t *dSums = error ? (uint64_t *)((uint8_t *)c->host.planes.p + elems * eb) : nullptr; // (elems * eb is a multiple of 16)
     size_t at = 0;
     for (size_t i = 0; i < count; i++)
     {
@@ -454,16 +480,22 @@ namespace
       jobs[i].window = pWindows[i];
       stage_window(jobs[i].window, (uint8_t *)c->host.planes.p + at * eb);
       const WindowView w = window_view(pWindows[i], pFormat);
+      if (error) HIP_TRY(hipMemcpy2D(window_pixels(jobs[i].window), w.width * 4, w.out.p, w.out.rowStride * 4, w.width * 4, w.height, hipMemcpyHostToDevice));
       at += (planes * out_width(w) * out_height(w) + per - 1) / per * per;
     }
-    if ((r = decode_windows_device(c, v, jobs, count, pFormat, nullptr, nullptr)) != limg_hip_success) return r;
-    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r; // a stream refused for any window: no pOut is touched
+    if ((r = decode_windows_device(c, v, jobs, count, pFormat, nullptr, nullptr, dSums)) != limg_hip_success) return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r; // a stream refused for any window: no pOut (no sum) is touched
+    if (error)
+    { // (the copy waits for the null stream's kernels)
+      HIP_TRY(hipMemcpy(pErrorSums, dSums, count * 8, hipMemcpyDeviceToHost));
+      return limg_hip_success;
+    }
     for (size_t i = 0; i < count; i++)
     {
       const WindowView w = window_view(pWindows[i], pFormat);
       const size_t ow = out_width(w), oh = out_height(w);
       for (size_t pl = 0; pl < planes; pl++)
-        HIP_TRY(hipMemcpy2D((uint8_t *)w.out.p + pl * w.out.planeStride * eb, w.out.rowStride * eb, (const uint8_t *)jobs[i].window.pOut + pl * ow * oh * eb, ow * eb, ow * eb, oh,
+        HIP_TRY(hipMemcpy2D((uint8_t *)w.out.p + pl * w.out.planeStride * eb, w.out.rowStride * eb, (const uint8_t *)window_pixels(jobs[i].window) + pl * ow * oh * eb, ow * eb, ow * eb, oh,
                             hipMemcpyDeviceToHost));
     }
     return limg_hip_success;
@@ -496,6 +528,49 @@ extern "C"
   { return decode_windows_host<limg_hip_window_job>(c, kVersion1, pStream, streamBytes, pWindows, count, nullptr); }
   limg_hip_result limg_hip_blocked_decode_stream_windows(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_window *pWindows, size_t count)
   { return decode_windows_host<limg_hip_window_job>(c, kVersion2, pStream, streamBytes, pWindows, count, nullptr); }
+
+  // ---- batched, the error against an original instead of the pixels ----
+  limg_hip_result limg_hip_decode_stream_windows_error_device(limg_hip_context *c, const limg_hip_error_window_job *pJobs, size_t count, uint64_t *pErrorSums, uint32_t *pJobStatus,
+                                                              void *stream)
+  { return decode_windows_device(c, kVersion1, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, pErrorSums); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_error_device(limg_hip_context *c, const limg_hip_error_window_job *pJobs, size_t count, uint64_t *pErrorSums,
+                                                                      uint32_t *pJobStatus, void *stream)
+  { return decode_windows_device(c, kVersion2, pJobs, count, nullptr, pJobStatus, (hipStream_t)stream, pErrorSums); }
+  limg_hip_result limg_hip_decode_stream_windows_error(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_error_window *pWindows, size_t count,
+                                                       uint64_t *pErrorSums)
+  { return decode_windows_host<limg_hip_error_window_job>(c, kVersion1, pStream, streamBytes, pWindows, count, nullptr, pErrorSums); }
+  limg_hip_result limg_hip_blocked_decode_stream_windows_error(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const limg_hip_error_window *pWindows,
+                                                               size_t count, uint64_t *pErrorSums)
+  { return decode_windows_host<limg_hip_error_window_job>(c, kVersion2, pStream, streamBytes, pWindows, count, nullptr, pErrorSums); }
+
+  // the whole image of a host stream of either version against a host original: limg_hip_compare(original, decode) without the decode
+  double limg_hip_stream_compare(limg_hip_context *c, const uint8_t *pStream, size_t streamBytes, const uint32_t *pOriginal, size_t pixels, double *pMse, double *pMax)
+  {
+    if (!c || !pStream || !pOriginal || streamBytes < sizeof(limg_hip_stream_header)) return NAN;
+    uint32_t version; // (the caller's bytes need no alignment)
+    memcpy(&version, pStream + offsetof(limg_hip_stream_header, version), sizeof(version));
+    const bool rects = version == LIMG_HIP_STREAM_VERSION_BLOCKED;
+    size_t sizeX = 0, sizeY = 0;
+    int hasAlpha = 0;
+    if ((rects ? limg_hip_blocked_stream_info(pStream, streamBytes, &sizeX, &sizeY, &hasAlpha, nullptr, nullptr)
+               : limg_hip_stream_info(pStream, streamBytes, &sizeX, &sizeY, &hasAlpha, nullptr)) != limg_hip_success || sizeX * sizeY != pixels)
+      return NAN;
+    const limg_hip_error_window whole = { 0, 0, sizeX, sizeY, pOriginal, sizeX };
+    uint64_t err = 0;
+    if (decode_windows_host<limg_hip_error_window_job>(c, rects ? kVersion2 : kVersion1, pStream, streamBytes, &whole, 1, nullptr, &err) != limg_hip_success) return NAN;
+    const double maxError = 255.0 * 255.0 * (hasAlpha ? 12.0 : 9.0), mse = (double)err / (double)pixels; // limg_hip_compare_device's constants
+    if (pMse) *pMse = mse;
+    if (pMax) *pMax = maxError;
+    return 10.0 * log10(maxError / mse);
+  }
+
+  // the largest error sum whose PSNR over sizeX x sizeY pixels is still `psnr` dB: PSNR >= psnr <=> errorSum <= this
+  uint64_t limg_hip_error_sum_for_psnr(size_t sizeX, size_t sizeY, int hasAlpha, double psnr)
+  {
+    if (psnr != psnr || sizeX == 0 || sizeY == 0) return 0;
+    const double v = floor(255.0 * 255.0 * (hasAlpha ? 12.0 : 9.0) * (double)sizeX * (double)sizeY / pow(10.0, psnr / 10.0));
+    return v >= 18446744073709551616.0 ? UINT64_MAX : v > 0.0 ? (uint64_t)v : 0;
+  }
 
   // ---- batched, planar float tensors ----
   limg_hip_result limg_hip_decode_stream_windows_tensor_device(limg_hip_context *c, const limg_hip_tensor_window_job *pJobs, size_t count, const limg_hip_tensor_format *pFormat,

@@ -233,13 +233,16 @@ struct Options
   std::string outDir = ".", streamPath, blockedStreamPath;
   uint64_t maxBytes = 0;                                // `--max-bytes`: `--stream` is encoded to this byte budget
   uint32_t minErrorFactor = 0, maxErrorFactor = 0;      // ... its search range (0: the library's defaults, 2 and 1024)
+  bool hasMinPsnr = false;                              // `--min-psnr`: `--stream` is encoded to this quality target, over the same search range
+  double minPsnr = 0;
 };
 
 static const char *const kUsage =
     "Usage:\nlimg_hip_cli [<InputFile> | --] [--no-output | --error-factor <Factor> | --accurate-bit-crushing | --single-thread | --fixed-blocks | --threads <T> | --out-dir <dir> | "
-    "--stream <file> [--max-bytes <N> [--min-error-factor <A>] [--max-error-factor <B>]] | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n"
+    "--stream <file> [--max-bytes <N> | --min-psnr <dB> [--min-error-factor <A>] [--max-error-factor <B>]] | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n"
     "limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n"
-    "limg_hip_cli --decode <file.lmg3> [<out.tga>] --resize WxH [--window x,y,w,h] [--flip]\n";
+    "limg_hip_cli --decode <file.lmg3> [<out.tga>] --resize WxH [--window x,y,w,h] [--flip]\n"
+    "limg_hip_cli --decode <file.lmg3> --compare <original image>\n";
 
 static bool parse_number(const char *text, uint64_t &value)
 {
@@ -272,6 +275,13 @@ static bool parse_args(int argc, const char **argv, Options &o)
     else if (a == "--stream" && hasValue) o.streamPath = argv[++i];
     else if (a == "--blocked-stream" && hasValue) o.blockedStreamPath = argv[++i];
     else if (a == "--max-bytes" && hasValue && parse_number(argv[i + 1], v)) { o.maxBytes = v; i++; }
+    else if (a == "--min-psnr" && hasValue)
+    {
+      char *end = nullptr;
+      o.minPsnr = strtod(argv[++i], &end);
+      if (end == argv[i] || *end != '\0' || !(o.minPsnr == o.minPsnr)) { printf("'--min-psnr' takes a number of dB.\n"); return false; }
+      o.hasMinPsnr = true;
+    }
     else if (a == "--min-error-factor" && hasValue && parse_number(argv[i + 1], v)) { o.minErrorFactor = (uint32_t)v; i++; }
     else if (a == "--max-error-factor" && hasValue && parse_number(argv[i + 1], v)) { o.maxErrorFactor = (uint32_t)v; i++; }
     else if ((a == "--count" || a == "--") && hasValue)
@@ -290,7 +300,12 @@ static bool parse_args(int argc, const char **argv, Options &o)
     o.writeImages = false;
     o.mode = (o.files.size() == 1 && o.repeat > 1) ? Options::BenchmarkOneFile : Options::BenchmarkList;
   }
-  if ((o.maxBytes || o.minErrorFactor || o.maxErrorFactor) && (o.streamPath.empty() || !o.maxBytes))
+  if (o.hasMinPsnr && (o.streamPath.empty() || o.maxBytes))
+  {
+    printf("'--min-psnr' is the quality target of '--stream' (and does not go with '--max-bytes'); '--min-error-factor' / '--max-error-factor' bound its search.\n");
+    return false;
+  }
+  if (!o.hasMinPsnr && (o.maxBytes || o.minErrorFactor || o.maxErrorFactor) && (o.streamPath.empty() || !o.maxBytes))
   {
     printf("'--max-bytes' is the byte budget of '--stream'; '--min-error-factor' / '--max-error-factor' bound its search.\n");
     return false;
@@ -368,7 +383,8 @@ static void write_planes(const Options &o, const Image &img, Planes &p)
 }
 
 // `--stream`: the compact stream belongs to the fixed-8x8 path, so its decode is checked against that path's image.  With `--max-bytes` the error factor is the one
-// limg_encode_budget chooses for that many bytes ('--error-factor' then only applies to the planes), and the check is against the 8x8 path at that error factor.
+// limg_encode_budget chooses for that many bytes ('--error-factor' then only applies to the planes), and the check is against the 8x8 path at that error factor;
+// with `--min-psnr` the one limg_encode_quality chooses for that many dB, the same way.
 static bool write_and_check_stream(const Options &o, const Image &img, limg_thread_pool *pool, const std::vector<uint32_t> *fixedDecoded)
 {
   std::vector<uint8_t> stream(limg_encode_bound(img.w, img.h));
@@ -384,6 +400,18 @@ static bool write_and_check_stream(const Options &o, const Image &img, limg_thre
     if (r != limg_success) FAIL(EXIT_FAILURE, "limg_encode_budget failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
     printf("Budget: %" PRIu64 " bytes; error factor %" PRIu32 " after %" PRIu32 " size probes; %" PRIu64 " bytes; budget %s.\n", o.maxBytes, errorFactor, probes,
            (uint64_t)bytes, within ? "met" : "NOT met");
+    if (errorFactor != o.errorFactor) fixedDecoded = nullptr; // (the planes were encoded at '--error-factor')
+  }
+  else if (o.hasMinPsnr)
+  {
+    bool within = false;
+    uint32_t probes = 0;
+    double psnr = 0;
+    r = limg_encode_quality(img.px.data(), img.w, img.h, img.hasAlpha, stream.data(), stream.size(), &bytes, o.minPsnr, &errorFactor, &psnr, &within, &probes,
+                            o.minErrorFactor, o.maxErrorFactor, pool, o.fastBitCrushing);
+    if (r != limg_success) FAIL(EXIT_FAILURE, "limg_encode_quality failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
+    printf("Quality: %.2f dB; error factor %" PRIu32 " after %" PRIu32 " error probes; %" PRIu64 " bytes; PSNR %.4f dB; target %s.\n", o.minPsnr, errorFactor, probes,
+           (uint64_t)bytes, psnr, within ? "met" : "NOT met");
     if (errorFactor != o.errorFactor) fixedDecoded = nullptr; // (the planes were encoded at '--error-factor')
   }
   else r = limg_encode(img.px.data(), img.w, img.h, img.hasAlpha, stream.data(), stream.size(), &bytes, o.errorFactor, pool, o.fastBitCrushing);
@@ -529,8 +557,10 @@ static int run_benchmark_list(const Options &o, limg_thread_pool *pool)
 // image of (sizeX / k) x (sizeY / k) box means, or the --window of it, which is then in that image's coordinates)
 // with --resize WxH: limg_decode_windows_resized -- the image, or the --window of it (full-resolution pixels), resampled bilinearly to W x H pixels from the deepest
 // box level that keeps a level pixel per output pixel, mirrored with --flip
+// with --compare <original image>: limg_compare_stream -- the reference's PSNR line for the stream against that image, and no image is decoded or written
 static const char *const kDecodeUsage = "Usage: limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n"
-                                        "       limg_hip_cli --decode <file.lmg3> [<out.tga>] --resize WxH [--window x,y,w,h] [--flip]\n";
+                                        "       limg_hip_cli --decode <file.lmg3> [<out.tga>] --resize WxH [--window x,y,w,h] [--flip]\n"
+                                        "       limg_hip_cli --decode <file.lmg3> --compare <original image>\n";
 
 static bool parse_window(const char *text, size_t win[4])
 {
@@ -547,7 +577,7 @@ static bool parse_window(const char *text, size_t win[4])
 
 static int run_decode(int argc, const char **argv)
 {
-  const char *in = nullptr, *out = "limg_out.tga";
+  const char *in = nullptr, *out = "limg_out.tga", *original = nullptr; // original: --compare
   size_t win[4] = { 0, 0, 0, 0 };
   bool window = false, resize = false, flip = false;
   size_t outW = 0, outH = 0; // --resize
@@ -575,6 +605,11 @@ static int run_decode(int argc, const char **argv)
       resize = true;
     }
     else if (!strcmp(argv[i], "--flip")) flip = true;
+    else if (!strcmp(argv[i], "--compare"))
+    {
+      if (i + 1 >= argc) FAIL(EXIT_FAILURE, "'--compare' takes the original image.\n%s", kDecodeUsage);
+      original = argv[++i];
+    }
     else if (positional == 0) { in = argv[i]; positional++; }
     else if (positional == 1) { out = argv[i]; positional++; }
     else FAIL(EXIT_FAILURE, "%s", kDecodeUsage);
@@ -582,12 +617,26 @@ static int run_decode(int argc, const char **argv)
   if (!in) FAIL(EXIT_FAILURE, "%s", kDecodeUsage);
   if (resize && level >= 0) FAIL(EXIT_FAILURE, "'--resize' chooses its level itself: it does not go with '--scale'.\n%s", kDecodeUsage);
   if (flip && !resize) FAIL(EXIT_FAILURE, "'--flip' goes with '--resize'.\n%s", kDecodeUsage);
+  if (original && (resize || level >= 0 || window || positional > 1)) FAIL(EXIT_FAILURE, "'--compare' measures the whole stream at full scale and writes no image.\n%s", kDecodeUsage);
   std::vector<uint8_t> stream;
   if (!read_file(in, stream)) FAIL(EXIT_FAILURE, "Failed to read '%s'.\n", in);
   size_t sx = 0, sy = 0;
   bool alpha = false;
   limg_result r = limg_decode_info(stream.data(), stream.size(), &sx, &sy, &alpha);
   if (r != limg_success) FAIL(EXIT_FAILURE, "'%s' is not an LMG3 stream (0x%" PRIX32 ").\n", in, (uint32_t)r);
+  if (original)
+  {
+    Image img;
+    load_or_die(original, img);
+    if (img.w != sx || img.h != sy)
+      FAIL(EXIT_FAILURE, "'%s' is %" PRIu64 " x %" PRIu64 " pixels, the stream %" PRIu64 " x %" PRIu64 ".\n", original, (uint64_t)img.w, (uint64_t)img.h, (uint64_t)sx, (uint64_t)sy);
+    double mse = 0, maxError = 0;
+    const double psnr = limg_compare_stream(stream.data(), stream.size(), img.px.data(), img.count(), &mse, &maxError);
+    if (psnr != psnr) FAIL(EXIT_FAILURE, "limg_compare_stream refused '%s'.\n", in);
+    printf("%" PRIu64 " x %" PRIu64 " pixels, %s.\n", (uint64_t)sx, (uint64_t)sy, alpha ? "RGBA" : "RGB");
+    printf("\nImage Perceptual RGB(A) PSNR: %4.2f dB (mean: %5.3f => %7.5f%% | sqrt: %5.3f%%)\n\n", psnr, mse, (mse / maxError) * 100.0, (sqrt(mse) / sqrt(maxError)) * 100.0);
+    return EXIT_SUCCESS;
+  }
   if (resize)
   {
     if (!window) { win[0] = 0; win[1] = 0; win[2] = sx; win[3] = sy; }
