@@ -444,7 +444,8 @@ limg_hip_result limg_hip_encode_stream_budget(limg_hip_context *pCtx, const uint
  * position and the thresholds) + 8 bytes of counter = 80 bytes per image of the longest chunk (streamRateState, streamRateCounter); the probes read the images through
  * the batched encode's own table (96 bytes per image of a chunk, no second table), and the final encode's threshold table (32 bytes per image) lies in the chunk's
  * search states, which are on the host by then: no memory of its own.  limg_hip_context_device_bytes reports all of it.
- * Out of scope: a batched limg_hip_stream_sizes; lists of mixed shapes; version 2 streams; the accurate search with per-image error factors in one launch (it takes
+ * Out of scope: a batched limg_hip_stream_sizes; budgeted lists of mixed shapes (the plain list of mixed shapes: limg_hip_encode_stream_list below); version 2 streams;
+ * the accurate search with per-image error factors in one launch (it takes
  * the grouped fallback of limg_hip_encode_stream_batch_ef_device); the CLI, which encodes one file. */
 /* DEVICE pointers; ppIn / ppStreams are HOST arrays of `count` device pointers (streams 16-byte aligned, capacityEach >= limg_hip_stream_bound) and, as pMaxBytes, may
  * be freed when the call returns.  Waits for `stream`. */
@@ -482,7 +483,7 @@ limg_hip_result limg_hip_encode_stream_budget_batch(limg_hip_context *pCtx, size
  * a struct_size below the struct's: limg_hip_error_InvalidParameter.  All before anything touches the device; a refused call writes nothing.
  * Context memory: 8 bytes per image of the call besides what the stream encode and one batched window call hold.
  * Follow-up, not here: a device-stepped search that enqueues all probes at once needs the encode's thresholds from a device table for a single image too (the list
- * encode has one); error at reduced levels; version 2 streams; lists of mixed shapes; other metrics. */
+ * encode has one); error at reduced levels; version 2 streams; other metrics.  (Lists of mixed shapes: limg_hip_encode_stream_quality_list below.) */
 typedef struct limg_hip_quality_result
 {
   uint32_t struct_size;  /* in: sizeof(limg_hip_quality_result) */
@@ -522,6 +523,62 @@ limg_hip_result limg_hip_encode_stream_quality_batch(limg_hip_context *pCtx, siz
                                                      uint8_t *const *ppStreams, size_t capacityEach, const uint64_t *pMaxErrorSums /* host, count */,
                                                      uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
                                                      limg_hip_quality_result *pResults /* host, count, struct_size set in each */);
+
+/* ---- stream encode of a list of MIXED shapes in one launch pair -----------------------------------------------------------------------
+ * The list entries above take one sizeX x sizeY for the whole list.  These take one item per image -- its pixels, its stream buffer, its own size and its own
+ * error factor -- and put the images that can share launches through ONE float-stage grid, ONE persistent launch, ONE scan and ONE pack per chunk, whatever the
+ * number of distinct shapes (the decode side's counterpart: limg_hip_decode_stream_windows*, which takes any mix of streams).
+ * Result: stream i is byte for byte what limg_hip_encode_stream_device writes for (pIn, sizeX, sizeY, hasAlpha, errorFactor) of item i under the same options, and
+ * pBytes[i] is its totalBytes.  The result for an item does not depend on its position in the list or on what else is in the list.  Every image starts its own
+ * dither chain(s); poolThreads means for each image what it means for the single call.
+ * pItems is a HOST array of `count` items in both forms and may be freed or overwritten when the call returns.  itemSize = sizeof(limg_hip_stream_list_item) versions
+ * the struct as struct_size does elsewhere.
+ * Errors, all before anything touches the device -- a refused call writes nothing -- in this order: (1) NULL context or pItems (host form: or pBytes):
+ * limg_hip_error_ArgumentNull; (2) itemSize below the struct's: limg_hip_error_InvalidParameter; (3) per item, the FIRST offending item in list order decides, and
+ * within an item: NULL pIn or pStream: limg_hip_error_ArgumentNull; sizeX or sizeY 0, or limg_hip_stream_bound(sizeX, sizeY) == 0 (the single call's size bound):
+ * limg_hip_error_InvalidParameter; (device form) pStream not 16-byte aligned: limg_hip_error_InvalidParameter; (device form) capacity below that bound:
+ * limg_hip_error_OutOfBounds; reserved != 0: limg_hip_error_InvalidParameter; (4) count == 0: limg_hip_success with nothing done.
+ * Options: forced_shift, dither_pcg, float_mode and collect_stats (limg_hip_last_stats: all images of the list together) are honoured as by
+ * limg_hip_encode_stream_batch_ef_device.  batch_sub_images does NOT apply to the mixed route -- a chunk is one launch pair -- and the bytes do not depend on it.
+ * Routing: an item is ELIGIBLE for the shared launches when both its sizes are multiples of 8, fastBitCrushing != 0, and force_split_kernels and legacy_float_stage
+ * are off (what k_encode_list_rated asks).  Ineligible items take limg_hip_encode_stream_device, inside the same call and on the same stream: the same bytes.  Where
+ * all eligible items share one shape they go to limg_hip_encode_stream_batch_ef_device's route as it is (a list of one item included).  Otherwise they go chunk by
+ * chunk -- the plane batch's rule (1 GiB of block records, 32-bit strip ids) counted in blocks and strips SUMMED over the images; a chunk that holds one item takes
+ * the single call -- and per chunk the call issues: the tables (kernel arguments of small launches, 3 KiB each), k_fit_tpb_list, k_encode_list_mixed,
+ * k_stream_scan_strips_list, k_stream_pack_strips_list; with pBytes one gather launch and ONE download per call.
+ * Context memory: what limg_hip_encode_stream_batch_ef_device holds for a chunk of the same blocks, strips and pixels (every image's factor planes are 3 slices of
+ * sizeX x sizeY bytes, each rounded up to 256), and per image of the longest chunk 64 + 96 + 32 + 32 bytes of tables, 160 for its view (the persistent kernel's parameters as that image's own launch would have them) and
+ * 8 for the two prefixes.  limg_hip_context_device_bytes reports all of it.
+ * Ordering: calls on one context and stream execute in order and may be issued back to back without a wait.
+ * Out of scope: the budgeted list for mixed shapes; a mixed-shape plane batch; the accurate search in the shared launch; version 2 streams; the CLI. */
+typedef struct limg_hip_stream_list_item
+{
+  const uint32_t *pIn;      /* image i */
+  uint8_t        *pStream;  /* its stream buffer */
+  uint64_t        capacity; /* of pStream */
+  uint32_t        sizeX, sizeY;
+  uint32_t        errorFactor;
+  uint32_t        reserved; /* 0 */
+} limg_hip_stream_list_item;  /* 40 bytes */
+
+/* DEVICE pointers in the items (pStream 16-byte aligned, capacity >= limg_hip_stream_bound(sizeX, sizeY)), asynchronous on `stream`; with pBytes it waits. */
+limg_hip_result limg_hip_encode_stream_list_device(limg_hip_context *pCtx, size_t count, const limg_hip_stream_list_item *pItems /* host */, size_t itemSize, int hasAlpha,
+                                                   size_t *pBytes /* host, count entries, or NULL */, int poolThreads, int fastBitCrushing, void *stream);
+/* HOST pointers in the items, blocking, under the context's mutex.  pBytes required.  A capacity may be below the bound: where some item's capacity is below that
+ * stream's totalBytes, all `count` sizes are reported, NO stream is written and limg_hip_error_OutOfBounds is returned. */
+limg_hip_result limg_hip_encode_stream_list(limg_hip_context *pCtx, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha, size_t *pBytes,
+                                            int poolThreads, int fastBitCrushing);
+/* ... to a quality target: the same items (each item's errorFactor is ignored), pResults[i] and stream i exactly limg_hip_encode_stream_quality_device's for item i
+ * with maxErrorSum = pMaxErrorSums[i].  The rounds of limg_hip_encode_stream_quality_batch_device, each round's encode one limg_hip_encode_stream_list_device call; the
+ * error launch takes jobs of any shape as it is.  Errors: (1) - (3) above, pMaxErrorSums and pResults counted among the pointers; then the bound rules and struct_size
+ * of limg_hip_encode_stream_quality_batch_device; then count == 0.  The device form waits for `stream` once per round. */
+limg_hip_result limg_hip_encode_stream_quality_list_device(limg_hip_context *pCtx, size_t count, const limg_hip_stream_list_item *pItems /* host */, size_t itemSize,
+                                                           int hasAlpha, const uint64_t *pMaxErrorSums /* host, count */, uint32_t minErrorFactor, uint32_t maxErrorFactor,
+                                                           int poolThreads, int fastBitCrushing, limg_hip_quality_result *pResults /* host, count */, void *stream);
+/* HOST pointers in the items, blocking; the capacity rule of limg_hip_encode_stream_list with pResults[i].bytes. */
+limg_hip_result limg_hip_encode_stream_quality_list(limg_hip_context *pCtx, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
+                                                    const uint64_t *pMaxErrorSums, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                    limg_hip_quality_result *pResults);
 
 /* ---- compact stream, version 2: the merged-block encoder's rectangles --------------------------------------------------------
  * What limg_hip_blocked_encode3d computes -- the rectangles of merged 8x8 blocks, each with ONE record, ONE shift triple and its crushed factor values -- in the same

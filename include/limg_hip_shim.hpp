@@ -315,6 +315,62 @@ inline limg_result limg_encode_quality_batch(const uint32_t *const *ppIn, const 
   return r;
 }
 
+// limg_encode of `count` images of ANY shapes in one call (limg_hip.h "stream encode of a list of mixed shapes"): pOutSizes[i] bytes at ppOut[i] are what limg_encode
+// writes for ppIn[i] (pSizesX[i] x pSizesY[i]) at pErrorFactors[i].  pOutCapacities[i] below some pOutSizes[i]: limg_error_OutOfBounds with all sizes filled and nothing
+// written to any ppOut[i].
+inline limg_result limg_encode_list(const uint32_t *const *ppIn, const size_t count, const size_t *pSizesX, const size_t *pSizesY, const bool hasAlpha, uint8_t *const *ppOut,
+                                    const size_t *pOutCapacities, size_t *pOutSizes, const uint32_t *pErrorFactors, limg_thread_pool *pThreadPool = nullptr,
+                                    const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (!ppIn || !pSizesX || !pSizesY || !ppOut || !pOutCapacities || !pErrorFactors) return limg_error_ArgumentNull;
+  std::vector<limg_hip_stream_list_item> items(count ? count : 1);
+  for (size_t i = 0; i < count; i++)
+  {
+    if (pSizesX[i] > 0xFFFFFFFFull || pSizesY[i] > 0xFFFFFFFFull) return limg_error_InvalidParameter;
+    const limg_hip_stream_list_item it = { ppIn[i], ppOut[i], (uint64_t)pOutCapacities[i], (uint32_t)pSizesX[i], (uint32_t)pSizesY[i], pErrorFactors[i], 0u };
+    items[i] = it;
+  }
+  return (limg_result)limg_hip_encode_stream_list(c, count, items.data(), sizeof(limg_hip_stream_list_item), hasAlpha ? 1 : 0, pOutSizes, limg_hip_shim::pool_threads(pThreadPool),
+                                                  fastBitCrushing ? 1 : 0);
+}
+
+// limg_encode_quality of `count` images of ANY shapes in one call: image i gets the stream limg_encode_quality writes for it with pMinPsnr[i]; the outputs as
+// limg_encode_quality_batch's, the capacities per image as limg_encode_list's.
+inline limg_result limg_encode_quality_list(const uint32_t *const *ppIn, const size_t count, const size_t *pSizesX, const size_t *pSizesY, const bool hasAlpha,
+                                            uint8_t *const *ppOut, const size_t *pOutCapacities, size_t *pOutSizes, const double *pMinPsnr, uint32_t *pErrorFactors,
+                                            double *pPsnr = nullptr, bool *pWithinTarget = nullptr, uint32_t *pProbes = nullptr, const uint32_t minErrorFactor = 0,
+                                            const uint32_t maxErrorFactor = 0, limg_thread_pool *pThreadPool = nullptr, const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (!ppIn || !pSizesX || !pSizesY || !ppOut || !pOutCapacities || !pOutSizes || !pErrorFactors || !pMinPsnr) return limg_error_ArgumentNull;
+  const limg_hip_quality_result blank = { sizeof(limg_hip_quality_result), 0, 0, 0, 0, 0 };
+  std::vector<limg_hip_quality_result> res(count ? count : 1, blank);
+  std::vector<uint64_t> limits(count ? count : 1, 0);
+  std::vector<limg_hip_stream_list_item> items(count ? count : 1);
+  for (size_t i = 0; i < count; i++)
+  {
+    if (pMinPsnr[i] != pMinPsnr[i]) return limg_error_InvalidParameter; // NaN names no target, as in limg_encode_quality
+    if (pSizesX[i] > 0xFFFFFFFFull || pSizesY[i] > 0xFFFFFFFFull) return limg_error_InvalidParameter;
+    const limg_hip_stream_list_item it = { ppIn[i], ppOut[i], (uint64_t)pOutCapacities[i], (uint32_t)pSizesX[i], (uint32_t)pSizesY[i], 0u, 0u };
+    items[i] = it;
+    limits[i] = limg_hip_error_sum_for_psnr(pSizesX[i], pSizesY[i], hasAlpha ? 1 : 0, pMinPsnr[i]);
+  }
+  const limg_result r = (limg_result)limg_hip_encode_stream_quality_list(c, count, items.data(), sizeof(limg_hip_stream_list_item), hasAlpha ? 1 : 0, limits.data(), minErrorFactor,
+                                                                         maxErrorFactor, limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0, res.data());
+  if (r != limg_success && r != limg_error_OutOfBounds) return r;
+  for (size_t i = 0; i < count; i++)
+  {
+    pOutSizes[i] = (size_t)res[i].bytes; pErrorFactors[i] = res[i].errorFactor;
+    if (pPsnr) pPsnr[i] = 10.0 * log10(255.0 * 255.0 * (hasAlpha ? 12.0 : 9.0) * (double)pSizesX[i] * (double)pSizesY[i] / (double)res[i].errorSum);
+    if (pWithinTarget) pWithinTarget[i] = res[i].withinTarget != 0;
+    if (pProbes) pProbes[i] = res[i].probes;
+  }
+  return r;
+}
+
 // either version of the stream: version 1 (limg_encode) or version 2 (limg_blocked_encode)
 inline limg_result limg_decode_info(const uint8_t *pIn, const size_t size, size_t *pSizeX, size_t *pSizeY, bool *pHasAlpha)
 {

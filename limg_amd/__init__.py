@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "limg_hip_stream_sizes_device", "limg_hip_stream_sizes", "limg_hip_encode_stream_budget_device", "limg_hip_encode_stream_budget",
     "limg_hip_encode_stream_budget_batch_device", "limg_hip_encode_stream_budget_batch",
     "limg_hip_encode_stream_quality_device", "limg_hip_encode_stream_quality", "limg_hip_encode_stream_quality_batch_device", "limg_hip_encode_stream_quality_batch",
+    "limg_hip_encode_stream_list_device", "limg_hip_encode_stream_list", "limg_hip_encode_stream_quality_list_device", "limg_hip_encode_stream_quality_list",
     "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
     "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
     "limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device", "limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window",
@@ -191,6 +192,12 @@ class QualityResult(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("errorFactor", C.c_uint32), ("probes", C.c_uint32), ("withinTarget", C.c_uint32), ("bytes", C.c_uint64), ("errorSum", C.c_uint64)]
 
 
+class StreamListItem(C.Structure):
+    """limg_hip_stream_list_item: one image of a list of mixed shapes -- its pixels, its stream buffer and capacity, its size and its error factor"""
+    _fields_ = [("pIn", C.c_void_p), ("pStream", C.c_void_p), ("capacity", C.c_uint64), ("sizeX", C.c_uint32), ("sizeY", C.c_uint32), ("errorFactor", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class Options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("forced_shift", C.c_int32 * 3), ("force_split_kernels", C.c_int32), ("dither_pcg", C.c_int32), ("float_mode", C.c_int32),
                 ("legacy_float_stage", C.c_int32), ("collect_stats", C.c_int32), ("host_noise_table", C.c_int32), ("batch_sub_images", C.c_int32), ("ragged_bands", C.c_int32),
@@ -343,6 +350,15 @@ def load_library(path=None):
     L.limg_hip_encode_stream_quality_batch.restype = C.c_int
     L.limg_hip_encode_stream_quality_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32,
                                                        C.c_int, C.c_int, C.c_void_p]
+    L.limg_hip_encode_stream_list_device.restype = C.c_int  # ctx, count, items (host), itemSize, hasAlpha, bytes (host or NULL), pool, fast, hipStream
+    L.limg_hip_encode_stream_list_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.limg_hip_encode_stream_list.restype = C.c_int
+    L.limg_hip_encode_stream_list.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    L.limg_hip_encode_stream_quality_list_device.restype = C.c_int  # ctx, count, items, itemSize, hasAlpha, limits (host), min ef, max ef, pool, fast, results, hipStream
+    L.limg_hip_encode_stream_quality_list_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                                             C.c_void_p]
+    L.limg_hip_encode_stream_quality_list.restype = C.c_int
+    L.limg_hip_encode_stream_quality_list.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
     L.limg_hip_stream_compare.restype = C.c_double  # ctx, stream, bytes, original, pixels, mse, max
     L.limg_hip_stream_compare.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.limg_hip_error_sum_for_psnr.restype = C.c_uint64
@@ -900,6 +916,70 @@ class LimgHip:
         size, list of QualityResult).  outs: the buffers to use (each at least stream_bound(w, h) bytes).  Waits for torch's current stream once per round."""
         limits, results = self._quality_list(max_error_sums, len(imgs))
         outs = self._stream_list("limg_hip_encode_stream_quality_batch_device", imgs, has_alpha, outs, (limits, min_error_factor, max_error_factor, pool_threads, int(fast), results), True)
+        return outs, results[:len(imgs)]
+
+    # ---- a list of MIXED shapes: stream i = encode_stream of image i at error_factors[i], the images that can share launches in one launch pair per chunk ----
+    def _stream_items(self, imgs, error_factors, outs, device):
+        """the item array of a mixed-shape list entry: images of any shapes (device: torch int32 CUDA tensors, else host arrays), the stream buffers (`outs`, or made
+        here at each image's worst-case size) -> (imgs, outs, ctypes array of StreamListItem); all three must stay alive until the call has returned"""
+        if not device:
+            imgs = [np.ascontiguousarray(i, dtype=np.uint32) for i in imgs]
+        n = len(imgs)
+        efs = [int(error_factors)] * n if np.isscalar(error_factors) else [int(e) for e in error_factors]
+        assert len(efs) == n
+        if outs is None and device:
+            import torch
+            outs = [torch.empty(self.stream_bound(i.shape[1], i.shape[0]), dtype=torch.uint8, device=i.device) for i in imgs]
+        elif outs is None:
+            outs = [np.zeros(self.stream_bound(i.shape[1], i.shape[0]), dtype=np.uint8) for i in imgs]
+        assert len(outs) == n
+        ptr = (lambda t: t.data_ptr()) if device else (lambda a: a.ctypes.data)
+        items = (StreamListItem * max(n, 1))()
+        for k in range(n):
+            items[k] = StreamListItem(ptr(imgs[k]), ptr(outs[k]), outs[k].numel() if device else outs[k].size, imgs[k].shape[1], imgs[k].shape[0], efs[k], 0)
+        return imgs, outs, items
+
+    def encode_stream_list(self, imgs, has_alpha, error_factors, pool_threads=0, fast=True):
+        """host uint32 images of ANY shapes, one error factor per image (or one int for all) -> list of stream bytes (numpy uint8), one call"""
+        imgs, outs, items = self._stream_items(imgs, error_factors, None, False)
+        sizes = (C.c_size_t * max(len(imgs), 1))()
+        self._stream_call("limg_hip_encode_stream_list", len(imgs), items, C.sizeof(StreamListItem), int(has_alpha), sizes, pool_threads, int(fast))
+        return [o[:sizes[k]].copy() for k, o in enumerate(outs)]
+
+    def encode_stream_list_device(self, imgs, has_alpha, error_factors, outs=None, want_sizes=True, pool_threads=0, fast=True):
+        """imgs: list of torch int32 CUDA tensors (h, w) of ANY shapes -> (list of torch uint8 CUDA stream buffers, each of its image's worst-case size, list of bytes
+        used or None).  outs: the buffers to use (each at least its image's stream_bound).  Asynchronous on torch's current stream unless want_sizes."""
+        imgs, outs, items = self._stream_items(imgs, error_factors, outs, True)
+        sizes = (C.c_size_t * max(len(imgs), 1))()
+        self._stream_call("limg_hip_encode_stream_list_device", len(imgs), items, C.sizeof(StreamListItem), int(has_alpha), sizes if want_sizes else None, pool_threads, int(fast),
+                          self._stream())
+        return outs, ([int(v) for v in sizes[:len(imgs)]] if want_sizes else None)
+
+    def _quality_limits(self, imgs, has_alpha, max_error_sums, min_psnr):
+        """the limits of a mixed-shape quality list: max_error_sums (an int or one per image), or -- min_psnr, a float or one per image -- error_sum_for_psnr per image"""
+        if min_psnr is None:
+            return max_error_sums
+        assert max_error_sums is None
+        targets = [float(min_psnr)] * len(imgs) if np.isscalar(min_psnr) else [float(t) for t in min_psnr]
+        assert len(targets) == len(imgs)
+        return [self.error_sum_for_psnr(i.shape[1], i.shape[0], has_alpha, t) for i, t in zip(imgs, targets)]
+
+    def encode_stream_quality_list(self, imgs, has_alpha, max_error_sums=None, min_error_factor=0, max_error_factor=0, pool_threads=0, fast=True, min_psnr=None):
+        """host uint32 images of ANY shapes, max_error_sums an int or one per image (or min_psnr= in dB, through error_sum_for_psnr per image) -> (list of stream bytes
+        (numpy uint8), list of QualityResult), one call"""
+        limits, results = self._quality_list(self._quality_limits(imgs, has_alpha, max_error_sums, min_psnr), len(imgs))
+        imgs, outs, items = self._stream_items(imgs, 0, None, False)
+        self._stream_call("limg_hip_encode_stream_quality_list", len(imgs), items, C.sizeof(StreamListItem), int(has_alpha), limits, min_error_factor, max_error_factor, pool_threads,
+                          int(fast), results)
+        return [o[:results[k].bytes].copy() for k, o in enumerate(outs)], results[:len(imgs)]
+
+    def encode_stream_quality_list_device(self, imgs, has_alpha, max_error_sums=None, min_error_factor=0, max_error_factor=0, outs=None, pool_threads=0, fast=True, min_psnr=None):
+        """imgs: list of torch int32 CUDA tensors (h, w) of ANY shapes -> (list of torch uint8 CUDA stream buffers, list of QualityResult).  Waits for torch's current
+        stream once per round."""
+        limits, results = self._quality_list(self._quality_limits(imgs, has_alpha, max_error_sums, min_psnr), len(imgs))
+        imgs, outs, items = self._stream_items(imgs, 0, outs, True)
+        self._stream_call("limg_hip_encode_stream_quality_list_device", len(imgs), items, C.sizeof(StreamListItem), int(has_alpha), limits, min_error_factor, max_error_factor,
+                          pool_threads, int(fast), results, self._stream())
         return outs, results[:len(imgs)]
 
     def blocked_stream_bound(self, w, h):

@@ -145,6 +145,7 @@ struct limg_hip_context
     DevBuf rated{ n }; // batched stream encode with one error factor per image: one RatedImage (32 bytes) per image of a chunk, the threshold table
     DevBuf table{ n }, sizes{ n }; // batched stream encode: one StreamImage per image of the list; the finished streams' sizes side by side (one download)
     DevBuf errorSums{ n }; // stream encode to a quality target: one error sum per image of a round (one download)
+    DevBuf listTable{ n }; // stream encode of a list of mixed shapes: a chunk's tables side by side -- per image its view, ListImage, ImageIO, RatedImage, StreamImage, two prefix words
     // version 2 stream of the merged-block encoder: per rectangle its first 64-pixel run, per tile of rectangles its totals; the decoder's block -> rectangle map and
     // its per-call words
     DevBuf bsUnits{ n }, bsTiles{ n }, bsMap{ n }, bsState{ n };

@@ -16,6 +16,8 @@
 // distinct banks).  17 KiB per wave.  The passes re-read the pixels from LDS (2 x ds_read_b128 per row).
 #include "limg_hip_device.h"
 
+#include <string.h>
+
 namespace limg_hip
 {
   namespace
@@ -72,20 +74,9 @@ namespace limg_hip
       if (p.fitPrio == 3) __builtin_amdgcn_s_setprio(3);
       else if (p.fitPrio == 2) __builtin_amdgcn_s_setprio(2);
       else if (p.fitPrio == 1) __builtin_amdgcn_s_setprio(1);
-      if (!FAST)
-      {
-        const uint4 *src = reinterpret_cast<const uint4 *>(d_rsqrt_x86_tab);
-        for (int i = (int)threadIdx.x; i < 256; i += 64 * kTpbWaves)
-        {
-          const uint4 v = src[i]; // entries 8 i .. 8 i + 7
-          const uint32_t q[4] = { v.x, v.y, v.z, v.w };
-          uint32_t *dst = s_tab + ((8 * i) ^ 0x400);
-#pragma unroll
-          for (int k = 0; k < 4; k++) { dst[2 * k] = (q[k] & 0xFFFFu) << 11; dst[2 * k + 1] = (q[k] >> 16) << 11; }
-        }
-        __syncthreads();
-      }
-      const unsigned short *tab = reinterpret_cast<const unsigned short *>(s_tab);
+#define LIMG_FIT_TPB_TABLE
+#include "limg_hip_fit_tpb_body.inc"
+#undef LIMG_FIT_TPB_TABLE
       uint32_t *s_px = s_pxAll[wave];
       const uint32_t unitsX = (p.blocksX + 63u) / 64u;
       const uint32_t unitId = blockIdx.x * kTpbWaves + wave;
@@ -101,216 +92,96 @@ namespace limg_hip
         if (unitId == 0 && lane < 4) p.ticket[lane] = 0u;
       }
 
-      // ---- stage the 8 pixel rows (coalesced 16 bytes per lane) into the block-major layout ----
-      if (!DIRECT)
-      {
-      if (p.vecIn)
-      {
-#pragma unroll
-        for (int row = 0; row < 8; row++)
-          for (uint32_t col = (uint32_t)lane * 4u; col < widthPx; col += 256u)
-          {
-            const uint4 v = *reinterpret_cast<const uint4 *>(pin + (size_t)(y0 + row) * p.sizeX + x0 + col);
-            *reinterpret_cast<uint4 *>(&s_px[(col >> 3) * kTpbStride + row * 8 + (col & 7u)]) = v;
-          }
-      }
-      else
-      {
-        for (int row = 0; row < 8; row++)
-          for (uint32_t col = (uint32_t)lane; col < widthPx; col += 64u)
-            s_px[(col >> 3) * kTpbStride + row * 8 + (col & 7u)] = pin[(size_t)(y0 + row) * p.sizeX + x0 + col];
-      }
-      }
-      wave_lds_fence();
-      if ((uint32_t)lane >= nBlocks) return;
-      const uint32_t *my = DIRECT ? pin + (size_t)y0 * p.sizeX + x0 + lane * 8 : s_px + lane * kTpbStride;
-      const uint32_t pitch = DIRECT ? p.sizeX : 8u;
+#include "limg_hip_fit_tpb_body.inc"
+    }
 
-      // ---- a4: channel sums (src/limg.cpp:466-497); two channels per 32-bit accumulator, 64 * 255 < 2^16 ----
-      uint32_t s02 = 0, s13 = 0;
-#pragma unroll
-      for (int r = 0; r < 8; r++)
+    // ---- the float stage of a list whose images differ in shape (limg_hip_encode_stream_list*; layout: limg_hip_list_plan.h) ----
+    // The same body over the chunk's concatenated unit list.  A unit is up to 64 adjacent blocks of one block row of ONE image; which image, a wave finds by a
+    // binary search over the unit prefix (wave-uniform, scalar loads), and what the body reads of `p` is that image's: its width, its pixels, and its slice of
+    // the records and invN, offset to its first block.  The tables were written by launches that precede this one on the stream: constant address space.
+    struct FitUnitView
+    {
+      uint32_t sizeX, blocksX;
+      int32_t vecIn;
+      limg_hip_block_record *records;
+      float *invN;
+    };
+    // (entry of a uint32 prefix of n entries that holds x: base[i] <= x < base[i + 1])
+    __device__ __forceinline__ uint32_t find_prefix(const uint32_t *base, uint32_t n, uint32_t x)
+    {
+      const __attribute__((address_space(4))) uint32_t *b = (const __attribute__((address_space(4))) uint32_t *)(uintptr_t)base;
+      uint32_t lo = 0, hi = n;
+      while (hi - lo > 1u)
       {
-        const uint4 u = *reinterpret_cast<const uint4 *>(my + r * pitch), w = *reinterpret_cast<const uint4 *>(my + r * pitch + 4);
-        const uint32_t q[8] = { u.x, u.y, u.z, u.w, w.x, w.y, w.z, w.w };
-#pragma unroll
-        for (int i = 0; i < 8; i++) { s02 += q[i] & 0x00FF00FFu; s13 += (q[i] >> 8) & 0x00FF00FFu; }
+        const uint32_t mid = (lo + hi) >> 1;
+        if (b[mid] <= x) lo = mid; else hi = mid;
       }
-      const float inv_count = 0.015625f;
-      V4 avg;
-      avg.a = float2_t{ (float)(int)(s02 & 0xFFFF), (float)(int)(s02 >> 16) } * inv_count;
-      avg.b = float2_t{ (float)(int)(s13 & 0xFFFF), CH == 4 ? (float)(int)(s13 >> 16) : 0.0f } * inv_count;
-      const V4 zero4 = { float2_t{ 0.0f, 0.0f }, float2_t{ 0.0f, 0.0f } };
+      return (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+    }
 
-      // the epilogue of a direction sum: dir = sum / N, 1 / (dir . dir) in DPPS order, all-zero test (== serial_sums2 of limg_hip_float_pixel.h)
-      auto finish_dir = [&](const V4 &acc, V4 &dir, float &inv, bool &zero)
-      {
-        dir = acc * inv_count;
-        const float pp = dp4<CH>(dir, dir); // plain products even in FAST mode: the lane == pixel path does the same
-        zero = dir.a.x == 0.0f && dir.a.y == 0.0f && dir.b.x == 0.0f && dir.b.y == 0.0f;
-        inv = FAST ? __builtin_amdgcn_rcpf(pp) : 1.0f / pp;
-      };
-
-      // ---- pass 1 (src/limg_factorization.h:602-628): sign-normalised unit vectors of px - avg, summed in pixel order ----
-      V4 dirA, dirB = zero4, dirC = zero4, est0 = zero4;
-      float invA, invB = 0.0f, invC = 0.0f;
-      bool zeroA, zeroB = true, zeroC = true;
-      float mm[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-      {
-        V4 acc = zero4;
-        for_rows(my, pitch, [&](const int, const uint32_t (&q)[8])
-        {
-#pragma unroll
-          for (int i = 0; i < 8; i++)
-          {
-            V4 d = px_to_v4(q[i]) - avg;
-            mask_alpha<CH>(d);
-            acc = acc + unit4<CH, FAST, true, true>(tab, d, true);
-          }
-        });
-        finish_dir(acc, dirA, invA, zeroA);
+    template <int CH, bool FAST, bool DIRECT>
+    __global__ __launch_bounds__(64 * tpb_waves<DIRECT>(), DIRECT ? 5 : 1) void k_fit_tpb_list(const FitListParams lp)
+    {
+      constexpr int kTpbWaves = tpb_waves<DIRECT>();
+      __shared__ __attribute__((aligned(16))) uint32_t s_pxAll[kTpbWaves][DIRECT ? 4 : 64 * kTpbStride];
+      __shared__ __attribute__((aligned(16))) uint32_t s_tab[FAST ? 4 : 2048];
+      const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+#define LIMG_FIT_TPB_TABLE
+#include "limg_hip_fit_tpb_body.inc"
+#undef LIMG_FIT_TPB_TABLE
+      uint32_t *s_px = s_pxAll[wave];
+      const uint32_t unitId = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kTpbWaves + wave));
+      if (unitId >= lp.nUnits) return; // whole wave; after the only barrier
+      const uint32_t img = find_prefix(lp.firstUnit, lp.nImages, unitId);
+      typedef const __attribute__((address_space(4))) ListImage KernImage;
+      typedef const __attribute__((address_space(4))) ImageIO KernIO;
+      KernImage *const im = (KernImage *)(uintptr_t)lp.images + img;
+      const uint32_t unitsX = (im->blocksX + 63u) / 64u, localUnit = unitId - im->firstUnit;
+      const uint32_t unit = localUnit % unitsX, by = localUnit / unitsX, byS = by; // (the image's slices start at its first block: its rows count from 0)
+      const uint32_t *const pin = (const uint32_t *)(const __attribute__((address_space(1))) uint32_t *)((KernIO *)(uintptr_t)lp.batch + img)->in;
+      FitUnitView p;
+      p.sizeX = im->sizeX; p.blocksX = im->blocksX; p.vecIn = (im->vec & kListVecIn) ? 1 : 0;
+      p.records = lp.records + im->firstBlock; p.invN = lp.invN + 4 * im->firstBlock;
+      const uint32_t bx0 = unit * 64u, x0 = bx0 * kBlock, y0 = by * kBlock;
+      const uint32_t nBlocks = min(p.blocksX - bx0, 64u), widthPx = nBlocks * kBlock;
+      { // this wave's 64 blocks are two work strips of the persistent launch that follows: their look-back descriptors, and (once) the ticket
+        const uint32_t stripsX = im->stripsX;
+        if ((uint32_t)lane < 2u && unit * 2u + (uint32_t)lane < stripsX) lp.desc[(size_t)im->firstStrip + (size_t)by * stripsX + unit * 2u + (uint32_t)lane] = 0ull;
+        if (unitId == 0 && lane < 4) lp.ticket[lane] = 0u;
       }
 
-      // ---- pass 2 (:652-688): factor A extrema, residual -> second direction ----
-      if (!zeroA)
-      {
-        V4 acc = zero4;
-        float mn = 0.0f, mx = 0.0f; // upstream starts them at 0 (:633-634)
-        for_rows(my, pitch, [&](const int, const uint32_t (&q)[8])
-        {
-#pragma unroll
-          for (int i = 0; i < 8; i++)
-          {
-            const V4 pf = px_to_v4(q[i]);
-            const float fA = dp4<CH, FAST>(pf - avg, dirA) * invA;
-            mn = vmin(mn, fA); mx = vmax(mx, fA);
-            V4 e = pf - (avg + dirA * fA);
-            mask_alpha<CH>(e);
-            acc = acc + unit4<CH, FAST, true, true>(tab, e, true);
-          }
-        });
-        mm[0] = mn; mm[1] = mx;
-        finish_dir(acc, dirB, invB, zeroB);
-      }
+#include "limg_hip_fit_tpb_body.inc"
+    }
+  }
 
-      // ---- pass 3 ----
-      if (!zeroA && !zeroB)
-      {
-        float mnB = FLT_MAX, mxB = -FLT_MAX;
-        if (CH == 4)
-        { // :701-738: factor B extrema, residual -> third direction; the A+B estimate of pixel 0 is what pass 4 measures every pixel against (:748-758)
-          V4 acc = zero4;
-          for_rows(my, pitch, [&](const int r, const uint32_t (&q)[8])
-          {
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-            {
-              const V4 pf = px_to_v4(q[i]);
-              const float fA = dp4<CH, FAST>(pf - avg, dirA) * invA; // recomputed, same operations => same bits as pass 2's
-              const V4 estA = avg + dirA * fA;
-              const float fB = dp4<CH, FAST>(pf - estA, dirB) * invB;
-              mnB = vmin(mnB, fB); mxB = vmax(mxB, fB);
-              const V4 estB = estA + dirB * fB;
-              if (r == 0 && i == 0) est0 = estB;
-              acc = acc + unit4<CH, FAST, true, true>(tab, pf - estB, true);
-            }
-          });
-          mm[2] = mnB; mm[3] = mxB;
-          finish_dir(acc, dirC, invC, zeroC);
-          // ---- pass 4 (:748-758) ----
-          if (!zeroC)
-          {
-            float mnC = FLT_MAX, mxC = -FLT_MAX;
-            for_rows(my, pitch, [&](const int, const uint32_t (&q)[8])
-            {
-#pragma unroll
-              for (int i = 0; i < 8; i++)
-              {
-                const float fC = dp4<CH, FAST>(px_to_v4(q[i]) - est0, dirC) * invC;
-                mnC = vmin(mnC, fC); mxC = vmax(mxC, fC);
-              }
-            });
-            mm[4] = mnC; mm[5] = mxC;
-          }
-        }
-        else
-        { // 3 channels (:498-541): dirC = dirA x dirB, B and C extrema in one pass; slots: a = (x0, x2), b = (x1, x3)
-          dirC.a.x = dirA.b.x * dirB.a.y - dirA.a.y * dirB.b.x; // A1 B2 - A2 B1
-          dirC.b.x = dirA.a.y * dirB.a.x - dirA.a.x * dirB.a.y; // A2 B0 - A0 B2
-          dirC.a.y = dirA.a.x * dirB.b.x - dirA.b.x * dirB.a.x; // A0 B1 - A1 B0
-          dirC.b.y = 0.0f;
-          zeroC = dirC.a.x == 0.0f && dirC.b.x == 0.0f && dirC.a.y == 0.0f;
-          if (!zeroC) invC = FAST ? __builtin_amdgcn_rcpf(dp4<CH, FAST>(dirC, dirC)) : 1.0f / dp4<CH, FAST>(dirC, dirC);
-          float mnC = zeroC ? 0.0f : FLT_MAX, mxC = zeroC ? 0.0f : -FLT_MAX;
-          for_rows(my, pitch, [&](const int, const uint32_t (&q)[8])
-          {
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-            {
-              const V4 pf = px_to_v4(q[i]);
-              const float fA = dp4<CH, FAST>(pf - avg, dirA) * invA;
-              const V4 estA = avg + dirA * fA;
-              const float fB = dp4<CH, FAST>(pf - estA, dirB) * invB;
-              mnB = vmin(mnB, fB); mxB = vmax(mxB, fB);
-              if (!zeroC)
-              {
-                const V4 e = pf - (estA + dirB * fB);
-                const float fC = dp4<CH, FAST>(e, dirC) * invC;
-                mnC = vmin(mnC, fC); mxC = vmax(mxC, fC);
-              }
-            }
-          });
-          mm[2] = mnB; mm[3] = mxB; mm[4] = mnC; mm[5] = mxC;
-        }
-      }
+  void launch_fit_tpb_list(const FitListParams &p, int channels, bool floatFast, bool direct, hipStream_t s)
+  {
+    with_flags([&](auto rgba, auto FAST, auto DIRECT)
+               { hipLaunchKernelGGL((k_fit_tpb_list<rgba ? 4 : 3, FAST, DIRECT>), dim3((p.nUnits + tpb_waves<DIRECT>() - 1) / tpb_waves<DIRECT>()), dim3(64 * tpb_waves<DIRECT>()), 0, s, p); },
+               channels == 4, floatFast, direct);
+  }
 
-      // ---- record (src/limg_factorization.h:764-790): avg + extreme * dir for A, extreme * dir for B and C, round to nearest even, int16 ----
-      const bool deadA = zeroA, deadB = zeroA || zeroB, deadC = zeroA || zeroB || zeroC;
-      auto comp = [](const V4 &v, int c) -> float { return c == 0 ? v.a.x : (c == 1 ? v.b.x : (c == 2 ? v.a.y : v.b.y)); };
-      uint32_t words[16];
-#pragma unroll
-      for (int c = 0; c < 4; c++) words[c] = __float_as_uint(comp(avg, c));
-      // Factor by factor, so that nothing but the factor's eight values is live: the record's int16 pairs, and -- a7 (limg_init_color_error_state_3d,
-      // src/limg_internal.h:426-452) -- 1 / (n . n) of the INTEGER normal max - min in the serial limg_dot order, 0 for an all-zero normal.  Here that is three
-      // divisions per 64 blocks; in the E step (lane == pixel, one lane per (block, factor, channel)) it was four DPP broadcasts and a correctly rounded division per
-      // lane and strip: ~7 vector instructions per block.
-      float inv[3];
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-      {
-        const bool dead = r == 0 ? deadA : (r == 1 ? deadB : deadC);
-        const V4 &dir = r == 0 ? dirA : (r == 1 ? dirB : dirC);
-        int16_t lo[4], hi[4];
-        float sum = 0.0f;
-        bool nz = false;
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-        {
-          float dv = comp(dir, c), mLo = mm[2 * r], mHi = mm[2 * r + 1];
-          if (dead) { mLo = 0.0f; mHi = 0.0f; dv = 0.0f; }
-          float vLo = mLo * dv, vHi = mHi * dv;
-          if (r == 0) { vLo = comp(avg, c) + vLo; vHi = comp(avg, c) + vHi; }
-          int qLo = cvt_rne(vLo), qHi = cvt_rne(vHi);
-          if (CH == 3 && c == 3) { qLo = 0; qHi = 0; }
-          lo[c] = (int16_t)qLo; hi[c] = (int16_t)qHi;
-          if (CH == 4 || c < 3)
-          {
-            const float n = (float)((int)hi[c] - (int)lo[c]);
-            const float sq = n * n;
-            sum = sum + sq; // ((0 + s0) + s1) + s2 (+ s3)
-            nz = nz || sq != 0.0f;
-          }
-        }
-        inv[r] = nz ? (FAST ? __builtin_amdgcn_rcpf(sum) : 1.0f / sum) : 0.0f;
-        words[4 + 4 * r] = (uint32_t)(uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-        words[5 + 4 * r] = (uint32_t)(uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-        words[6 + 4 * r] = (uint32_t)(uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-        words[7 + 4 * r] = (uint32_t)(uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-      }
-      uint4 *dst = reinterpret_cast<uint4 *>(p.records + (size_t)byS * p.blocksX + bx0 + lane);
-#pragma unroll
-      for (int i = 0; i < 4; i++) dst[i] = make_uint4(words[4 * i], words[4 * i + 1], words[4 * i + 2], words[4 * i + 3]);
-      reinterpret_cast<float4 *>(p.invN)[(size_t)byS * p.blocksX + bx0 + lane] = make_float4(inv[0], inv[1], inv[2], 0.0f);
+  namespace
+  {
+    // any table of a list call, as 32-bit words through kernel arguments (as k_set_batch_table: stream-ordered, and the host array may die right away)
+    struct WordChunk { uint32_t n; uint32_t w[768]; };
+    static_assert(sizeof(WordChunk) <= 3584, "kernel-argument segment");
+    __global__ void k_set_words(uint32_t *dst, const WordChunk chunk)
+    {
+      for (uint32_t i = threadIdx.x; i < chunk.n; i += blockDim.x) dst[i] = chunk.w[i];
+    }
+  }
+
+  void launch_set_words(void *dDst, const void *hSrc, size_t bytes, hipStream_t s)
+  {
+    const size_t words = bytes / 4;
+    for (size_t i0 = 0; i0 < words; i0 += 768)
+    {
+      WordChunk ch;
+      ch.n = (uint32_t)(words - i0 < 768 ? words - i0 : 768);
+      memset(ch.w, 0, sizeof(ch.w));
+      memcpy(ch.w, (const uint32_t *)hSrc + i0, (size_t)ch.n * 4);
+      hipLaunchKernelGGL(k_set_words, dim3(1), dim3(256), 0, s, (uint32_t *)dDst + i0, ch);
     }
   }
 

@@ -11,6 +11,7 @@
 #include "limg_hip_blocked_host.h"
 #include "limg_hip_rate_step.h"
 #include "limg_hip_encode_rules.h"
+#include "limg_hip_list_plan.h"
 
 namespace limg_hip
 {
@@ -146,6 +147,49 @@ namespace limg_hip
 #endif
   };
 
+  // ---- a list whose images differ in SHAPE (limg_hip_encode_stream_list*; the layout: limg_hip_list_plan.h) ----
+  // One chunk's images are concatenated: strip ids, look-back descriptors and payload words run through all of them, records / invN / shift words image after
+  // image from each image's firstBlock.  Four device tables share the image index: ListImage (geometry and slice starts), ImageIO, RatedImage and -- the persistent
+  // kernel's -- one RatedListParams per image, the VIEW its stages read in place of the kernel arguments: that image's geometry, flags and chain partition, and
+  // records / invN / shifts already offset to its first block (so the stages' rowBase is 0); desc, stripWords, noise and timeout are the launch's own in every view.
+  struct StreamImage;
+  static_assert(sizeof(RatedListParams) == 160 && sizeof(ImageIO) == 96, "the per-image table entries include/limg_hip.h states");
+  // k_fit_tpb_list's arguments: no hook member, the kernarg segment is the same in both builds.
+  struct FitListParams
+  {
+    const ListImage *images;
+    const ImageIO *batch;
+    const uint32_t *firstUnit; // nImages: exclusive prefix of the images' float-stage units
+    uint32_t nImages, nUnits;
+    limg_hip_block_record *records;
+    float *invN;
+    unsigned long long *desc;  // the persistent launch's look-back descriptors and ticket, which this grid clears on its way (as EncodeParams::zeroLookback)
+    uint32_t *ticket;
+  };
+  // k_encode_list_mixed's arguments
+  struct MixedListParams
+  {
+    const RatedListParams *views; // per image
+    const ImageIO *batch;
+    const RatedImage *rated;
+    const uint32_t *firstStrip;   // nImages: exclusive prefix of the images' work strips
+    uint32_t nImages, nStrips;
+    uint32_t *ticket;
+    uint8_t *park;
+  };
+  // the list's scan + pack (limg_hip_stream.hip)
+  struct StreamListParams
+  {
+    const ListImage *images;
+    const StreamImage *streams;   // per image: its three factor planes and its stream
+    const RatedImage *rated;      // ... and the error factor its header carries
+    const uint32_t *firstStrip;
+    uint32_t nImages, nStrips, nWaves, channels, flags;
+    const limg_hip_block_record *records;
+    const uint32_t *shifts;
+    uint32_t *stripWords;
+  };
+
   // stream pack (limg_hip_stream.hip): from the compact outputs of an encode (factor planes, records, shift words)
   struct StreamParams
   {
@@ -210,6 +254,10 @@ namespace limg_hip
   void launch_fit_search(const EncodeParams &p, int channels, hipStream_t s);
   void launch_encode_persistent(const EncodeParams &p, int channels, int workgroups, hipStream_t s);
   void launch_encode_list_rated(const RatedListParams &p, int channels, bool floatFast, int workgroups, hipStream_t s);
+  void launch_fit_tpb_list(const FitListParams &p, int channels, bool floatFast, bool direct, hipStream_t s);
+  void launch_encode_list_mixed(const MixedListParams &p, int channels, bool floatFast, int workgroups, hipStream_t s);
+  void launch_stream_pack_list(const StreamListParams &b, hipStream_t s);                  // one scan launch + one pack launch, whatever the shapes are
+  void launch_set_words(void *dDst, const void *hSrc, size_t bytes, hipStream_t s);          // hSrc: HOST memory (may die when the call returns), through kernel arguments; bytes % 4 == 0
   void launch_set_rated_table(RatedImage *dTable, const uint32_t *hErrorFactors, size_t count, hipStream_t s); // hErrorFactors: HOST array (may die when the call returns), 64 per launch
   void launch_strip_scan(const EncodeParams &p, hipStream_t s);
   void launch_dither_store(const EncodeParams &p, int channels, hipStream_t s);

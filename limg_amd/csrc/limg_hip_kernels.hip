@@ -674,6 +674,12 @@ namespace limg_hip
       typedef const __attribute__((address_space(4))) ImageIO KernIO;
       auto io_of = [](KernArgs *a, uint32_t img) -> KernIO * { return a->batchCount > 1 ? (KernIO *)a->batch + img : &a->io; };
 #define LIMG_LOOP_LIMITS(a, img) (*(a)) /* one error factor: the limits are kernel arguments */
+// (a list of one shape: the image of a strip by a division, its strips and block rows image after image, the kernel arguments as every image's view)
+#define LIMG_LOOP_STRIPS (p.imageStrips * p.batchCount)
+#define LIMG_LOOP_FIND_IMAGE(a, t, img) if ((a)->batchCount > 1) img = (t) / (a)->imageStrips;
+#define LIMG_LOOP_HEAD0(a, img) ((img) * (a)->imageStrips)
+#define LIMG_LOOP_ROWBASE(a, img) ((img) * (a)->blocksY)
+#define LIMG_LOOP_VIEW(a, img) (a)
       if (red_select_dead(p.maxPixel32))
       {
         constexpr bool NOSEL = true;
@@ -703,7 +709,57 @@ namespace limg_hip
       auto io_of = [](KernArgs *a, uint32_t img) -> KernIO * { return (KernIO *)a->batch + img; }; // (a sub-batch of one image reads the table too)
 #define LIMG_LOOP_LIMITS(a, img) (*((KernLimits *)(a)->rated + (img)))
 #include "limg_hip_persistent_loop.inc"
+    }
+#undef LIMG_LOOP_STRIPS
+#undef LIMG_LOOP_FIND_IMAGE
+#undef LIMG_LOOP_HEAD0
+#undef LIMG_LOOP_ROWBASE
+#undef LIMG_LOOP_VIEW
+
+    // A list whose images differ in SHAPE (limg_hip_encode_stream_list*; layout: limg_hip_list_plan.h): the same loop over the chunk's concatenated strips.  The image
+    // of a strip comes from a wave-uniform binary search over the strip prefix; what the stages read as `p` is that image's VIEW, an entry of a device table with
+    // RatedListParams' layout (its geometry, flags, chain partition, and records / invN / shifts offset to its first block: rowBase is 0), fetched with scalar
+    // loads where a stage uses a field, exactly as the siblings fetch kernel arguments.  The F step of the previous strip reads the previous image's view by its
+    // index.  Ticket, look-back (bounded, poisoning on a time-out) and park slots are those of the siblings; desc, stripWords, noise and timeout are the launch's
+    // own in every view and indexed by the global strip id.
+    __device__ __forceinline__ uint32_t find_strip_image(const uint32_t *base, uint32_t n, uint32_t x)
+    {
+      const __attribute__((address_space(4))) uint32_t *b = (const __attribute__((address_space(4))) uint32_t *)(uintptr_t)base;
+      uint32_t lo = 0, hi = n;
+      while (hi - lo > 1u)
+      {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (b[mid] <= x) lo = mid; else hi = mid;
+      }
+      return (uint32_t)sgpr((int)lo);
+    }
+
+    template <int CH, bool FAST>
+    __global__ __launch_bounds__(kThreads, 6) void k_encode_list_mixed(const MixedListParams p)
+    {
+      constexpr bool PREFIT = true, ACC = false, NOSEL = false;
+      __shared__ __attribute__((aligned(16))) uint8_t s_lds[lds_layout<PREFIT>().total];
+      __shared__ uint32_t s_ticket;
+      typedef const __attribute__((address_space(4))) MixedListParams KernArgs;
+      typedef const __attribute__((address_space(4))) RatedListParams KernView;
+      typedef const __attribute__((address_space(4))) ImageIO KernIO;
+      typedef const __attribute__((address_space(4))) RatedImage KernLimits;
+      typedef const __attribute__((address_space(4))) uint32_t KernWord;
+      auto io_of = [](KernArgs *a, uint32_t img) -> KernIO * { return (KernIO *)(uintptr_t)a->batch + img; };
+#define LIMG_LOOP_STRIPS (p.nStrips)
+#define LIMG_LOOP_FIND_IMAGE(a, t, img) img = find_strip_image((a)->firstStrip, (a)->nImages, (t));
+#define LIMG_LOOP_HEAD0(a, img) (((KernWord *)(uintptr_t)(a)->firstStrip)[img])
+#define LIMG_LOOP_ROWBASE(a, img) 0u
+#define LIMG_LOOP_VIEW(a, img) ((KernView *)(uintptr_t)(a)->views + (img))
 #undef LIMG_LOOP_LIMITS
+#define LIMG_LOOP_LIMITS(a, img) (*((KernLimits *)(uintptr_t)(a)->rated + (img)))
+#include "limg_hip_persistent_loop.inc"
+#undef LIMG_LOOP_LIMITS
+#undef LIMG_LOOP_STRIPS
+#undef LIMG_LOOP_FIND_IMAGE
+#undef LIMG_LOOP_HEAD0
+#undef LIMG_LOOP_ROWBASE
+#undef LIMG_LOOP_VIEW
     }
   } // namespace
 
@@ -762,6 +818,12 @@ namespace limg_hip
     const uint32_t strips = p.imageStrips * p.batchCount;
     const dim3 grid(strips < (uint32_t)workgroups ? strips : (uint32_t)workgroups), block(kThreads);
     with_flags([&](auto rgba, auto fast) { hipLaunchKernelGGL((k_encode_list_rated<rgba ? 4 : 3, fast>), grid, block, 0, s, p); }, channels == 4, floatFast);
+  }
+
+  void launch_encode_list_mixed(const MixedListParams &p, int channels, bool floatFast, int workgroups, hipStream_t s)
+  {
+    const dim3 grid(p.nStrips < (uint32_t)workgroups ? p.nStrips : (uint32_t)workgroups), block(kThreads);
+    with_flags([&](auto rgba, auto fast) { hipLaunchKernelGGL((k_encode_list_mixed<rgba ? 4 : 3, fast>), grid, block, 0, s, p); }, channels == 4, floatFast);
   }
 
   namespace

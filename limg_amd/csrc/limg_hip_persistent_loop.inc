@@ -1,10 +1,13 @@
-// limg_hip_persistent_loop.inc -- the persistent encode kernels' loop (limg_hip_kernels.hip), included as the BODY of k_encode_persistent and of k_encode_list_rated:
-// one text for both.  Not a function: called through one (the image's pointers and limits as callables) k_encode_persistent's instances came out with another
+// limg_hip_persistent_loop.inc -- the persistent encode kernels' loop (limg_hip_kernels.hip), included as the BODY of k_encode_persistent, of k_encode_list_rated and
+// of k_encode_list_mixed: one text for all three.  Not a function: called through one (the image's pointers and limits as callables) k_encode_persistent's instances came out with another
 // schedule than the one they were measured with; included, their code is instruction for instruction what it was when the loop stood in the kernel.
 // From the enclosing scope: CH, FAST, PREFIT, ACC, NOSEL; p (the kernel's parameter block); KernArgs (its type in the constant address space); s_lds, s_ticket;
-// io_of(a, img): the caller's pointers of image `img` of the launch; LIMG_LOOP_LIMITS(a, img): where the E step's search takes its limits from.
+// io_of(a, img): the caller's pointers of image `img` of the launch; LIMG_LOOP_LIMITS(a, img): where the E step's search takes its limits from;
+// LIMG_LOOP_STRIPS: the strips of the launch (from p); LIMG_LOOP_FIND_IMAGE(a, t, img): the statement that sets img to the image of strip t (img is 0 before it);
+// LIMG_LOOP_HEAD0(a, img), LIMG_LOOP_ROWBASE(a, img): that image's first strip id and its first block row in the per-block scratch; LIMG_LOOP_VIEW(a, img): the
+// parameter block the stages read for a strip of that image -- the kernel arguments themselves, or the image's own view (k_encode_list_mixed).
       const int tid = (int)threadIdx.x;
-      const uint32_t S = p.imageStrips * p.batchCount; // the strips of all images of a batch, image after image
+      const uint32_t S = LIMG_LOOP_STRIPS; // the strips of all images of a batch, image after image
       uint8_t *park = p.park + (size_t)blockIdx.x * 2 * kParkBytes;
       uint32_t prev = 0xFFFFFFFFu, prevImg = 0, slot = 0;
       // The two steps read the parameters straight from the kernel-argument segment, through a pointer the compiler cannot see through from one step to the
@@ -33,9 +36,9 @@
         uint32_t img = 0;
         if (t < S)
         {
-          if (pe->batchCount > 1) img = t / pe->imageStrips; // once per strip, on the scalar unit
-          const uint32_t head0 = img * pe->imageStrips;
-          fit_search_strip<CH, true, FAST, PREFIT, ACC, NOSEL>(*pe, LIMG_LOOP_LIMITS(pe, img), *io_of(pe, img), t, t - head0, img * pe->blocksY, head0, s_lds, park + slot * kParkBytes, tid_e);
+          LIMG_LOOP_FIND_IMAGE(pe, t, img) // once per strip, on the scalar unit
+          const uint32_t head0 = LIMG_LOOP_HEAD0(pe, img);
+          fit_search_strip<CH, true, FAST, PREFIT, ACC, NOSEL>(*LIMG_LOOP_VIEW(pe, img), LIMG_LOOP_LIMITS(pe, img), *io_of(pe, img), t, t - head0, LIMG_LOOP_ROWBASE(pe, img), head0, s_lds, park + slot * kParkBytes, tid_e);
         }
         if (prev != 0xFFFFFFFFu)
         {
@@ -47,8 +50,9 @@
           // The F step is latency-bound with little vector work, the E step is what keeps the vector unit busy: E-step waves get the issue priority (s_setprio),
           // F-step waves take the slots they leave.  Measured: -2.5 % on the kernel (the other way round: +0.8 %).
           __builtin_amdgcn_s_setprio(0);
-          const uint32_t head0 = prevImg * pf->imageStrips;
-          dither_store_strip<CH, true>(*pf, *io_of(pf, prevImg), prev, prev - head0, prevImg * pf->blocksY, head0, s_lds + kLdsStrip, park + (slot ^ 1u) * kParkBytes, tid_f);
+          const uint32_t head0 = LIMG_LOOP_HEAD0(pf, prevImg);
+          // (the view of the previous strip's image is fetched again here, by prevImg: nothing of it is carried across the E step)
+          dither_store_strip<CH, true>(*LIMG_LOOP_VIEW(pf, prevImg), *io_of(pf, prevImg), prev, prev - head0, LIMG_LOOP_ROWBASE(pf, prevImg), head0, s_lds + kLdsStrip, park + (slot ^ 1u) * kParkBytes, tid_f);
           __builtin_amdgcn_s_setprio(kPrioE);
         }
         if (t >= S) break;

@@ -180,7 +180,9 @@ namespace limg_hip
     // coalesced 16 bytes per lane (a thread that owned 32 CONSECUTIVE strips asked its CU's address unit for 64 lines per instruction: 11 us; the first form, one
     // slab per loop iteration with the loads inside the loop: 32 us) -- all 8 requested before anything is added; the 8 slabs' wave scans run side by side, the
     // 8 x 16 wave totals are turned into their exclusive prefix by one wave, two barriers per round.  8192^2 is one round.
-    // (the body: the exclusive prefix over `nStrips` words in place, by the whole workgroup; returns their sum.  k_stream_scan_strips_batch runs it once per image.)
+    // (the body: the exclusive prefix over `nStrips` words in place, by the whole workgroup; returns their sum.  k_stream_scan_strips_batch runs it once per image.
+    //  ALIGNED: the slice starts on a multiple of 4 words -- everywhere but in a list of mixed shapes, k_stream_scan_strips_list)
+    template <bool ALIGNED = true>
     __device__ __forceinline__ unsigned long long scan_strips(uint32_t *const stripWords, const uint32_t nStrips)
     {
       __shared__ unsigned long long sPart[8 * 16]; // [slab][wave] totals, then their exclusive prefix
@@ -188,7 +190,7 @@ namespace limg_hip
       const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
       if (tid == 0) sCarry = 0;
       __syncthreads();
-      const bool vec = (nStrips & 3u) == 0; // 16-byte accesses need whole groups of 4 (the buffer itself is 256-byte aligned)
+      const bool vec = ALIGNED && (nStrips & 3u) == 0; // 16-byte accesses need whole groups of 4 (the buffer itself is 256-byte aligned)
       for (uint32_t base = 0; base < nStrips; base += 32768)
       {
         uint32_t v[8][4];
@@ -432,6 +434,103 @@ namespace limg_hip
           const StripView p = strip_view(b, g, imgCur, local);
           const uint32_t strip = local;
           uint2 *const payload = reinterpret_cast<uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)b.nBlocks * kEntry);
+#include "limg_hip_stream_pack_step.inc"
+        }
+        cur = nxt; nxt = nxt2; rows = rowsNext;
+        imgCur = imgNxt; imgNxt = imgNxt2;
+      }
+    }
+
+    // ---- scan + pack, strip form, a list whose images differ in shape (limg_hip_encode_stream_list*; layout: limg_hip_list_plan.h) --------------------------
+    // The chunk's strips are concatenated; image i owns [firstStrip, firstStrip + strips) of the payload-word array and the blocks from firstBlock of the records and
+    // shift words.  What a strip's image is, a wave finds by a binary search over the strip prefix (uniform across the wave); its geometry, planes and stream come
+    // from the device tables (constant address space, scalar loads).
+    typedef const __attribute__((address_space(4))) ListImage KernListImage;
+    __device__ __forceinline__ uint32_t list_strip_image(const StreamListParams &b, const uint32_t g)
+    {
+      if (g >= b.nStrips) return 0u;
+      const __attribute__((address_space(4))) uint32_t *base = (const __attribute__((address_space(4))) uint32_t *)(uintptr_t)b.firstStrip;
+      uint32_t lo = 0, hi = b.nImages;
+      while (hi - lo > 1u)
+      {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (base[mid] <= g) lo = mid; else hi = mid;
+      }
+      return (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+    }
+
+    // Workgroup i is k_stream_scan_strips for image i: the prefix restarts at 0 in its slice, its header (its own size and error factor) goes to its own stream.
+    // A slice starts wherever the images in front of it end: the 16-byte path runs only where the slice's START is a multiple of 4 strips as well as its length.
+    __global__ __launch_bounds__(1024) void k_stream_scan_strips_list(const StreamListParams b)
+    {
+      const uint32_t img = blockIdx.x;
+      KernListImage *const im = (KernListImage *)(uintptr_t)b.images + img;
+      const uint32_t first = im->firstStrip, strips = im->strips;
+      uint32_t *const slice = b.stripWords + first;
+      const unsigned long long total = (first & 3u) == 0 ? scan_strips<true>(slice, strips) : scan_strips<false>(slice, strips);
+      if (threadIdx.x == 0)
+      {
+        const StreamHeaderInfo h = { LIMG_HIP_STREAM_VERSION, im->sizeX, im->sizeY, b.channels, b.rated[img].errorFactor, im->blocksX, im->blocksY, b.flags, im->nBlocks, (uint32_t)kEntry, 0u };
+        write_stream_header(b.streams[img].stream, h, total);
+      }
+    }
+
+    // the view of the image that holds strip g of the chunk, g's number inside it, and the image's block count (where its payload area starts)
+    __device__ __forceinline__ StripView strip_view(const StreamListParams &b, const uint32_t g, const uint32_t img, uint32_t &local, uint32_t &nBlocks)
+    {
+      StripView v;
+      v.channels = b.channels;
+      if (g >= b.nStrips)
+      {
+        v.stripsX = 1u; v.blocksX = 0u; v.sizeX = 0u;
+        v.nStrips = 0; v.stripWords = nullptr; v.records = nullptr; v.shifts = nullptr; v.fac[0] = v.fac[1] = v.fac[2] = nullptr; v.stream = nullptr;
+        local = 0; nBlocks = 0;
+        return v;
+      }
+      typedef const __attribute__((address_space(4))) StreamImage KernImage;
+      KernListImage *const li = (KernListImage *)(uintptr_t)b.images + img;
+      KernImage *const im = (KernImage *)(uintptr_t)b.streams + img;
+      v.stripsX = li->stripsX; v.blocksX = li->blocksX; v.sizeX = li->sizeX;
+      v.nStrips = li->strips;
+      v.stripWords = b.stripWords + li->firstStrip;
+      v.records = b.records + li->firstBlock;
+      v.shifts = b.shifts + li->firstBlock;
+      v.fac[0] = im->fac[0]; v.fac[1] = im->fac[1]; v.fac[2] = im->fac[2];
+      v.stream = im->stream;
+      local = g - li->firstStrip;
+      nBlocks = li->nBlocks;
+      return v;
+    }
+
+    // k_stream_pack_strips_batch's loop; the StripView of each of the three strips in flight is built from THAT strip's image: its row pitch, blocksX, records base
+    // (16 one-wave workgroups per CU is what pack_waves launches: 4 waves per SIMD, 128 vector registers -- asked for, since this kernel's per-image views cost two more)
+    __global__ __launch_bounds__(64, 4) void k_stream_pack_strips_list(const StreamListParams b)
+    {
+      __shared__ __align__(16) uint32_t sRun[32 * 48];   // the strip's payload, worst case (24 words per block)
+      __shared__ __align__(16) uint32_t sEnt[32 * 14];   // its entries
+      const int lane = lane_id(), j = lane & 31, h = lane >> 5;
+      StripSmall cur, nxt;
+      StripRows rows, rowsNext;
+      uint32_t imgCur = list_strip_image(b, blockIdx.x), imgNxt = list_strip_image(b, blockIdx.x + b.nWaves), local, nBlocks;
+      {
+        uint32_t localNext;
+        const StripView v = strip_view(b, blockIdx.x, imgCur, local, nBlocks), vn = strip_view(b, blockIdx.x + b.nWaves, imgNxt, localNext, nBlocks);
+        load_strip_small(v, local, j, cur);
+        load_strip_small(vn, localNext, j, nxt);
+        issue_strip_rows(v, local, j, h, cur, rows);
+      }
+      for (uint32_t g = blockIdx.x; g < b.nStrips; g += b.nWaves)
+      {
+        const StripView vn = strip_view(b, g + b.nWaves, imgNxt, local, nBlocks);
+        issue_strip_rows(vn, local, j, h, nxt, rowsNext); // (waits for `nxt`, requested one iteration ago)
+        const uint32_t imgNxt2 = list_strip_image(b, g + 2u * b.nWaves);
+        const StripView vn2 = strip_view(b, g + 2u * b.nWaves, imgNxt2, local, nBlocks);
+        StripSmall nxt2;
+        load_strip_small(vn2, local, j, nxt2);
+        {
+          const StripView p = strip_view(b, g, imgCur, local, nBlocks);
+          const uint32_t strip = local;
+          uint2 *const payload = reinterpret_cast<uint2 *>(p.stream + sizeof(limg_hip_stream_header) + (size_t)nBlocks * kEntry);
 #include "limg_hip_stream_pack_step.inc"
         }
         cur = nxt; nxt = nxt2; rows = rowsNext;
@@ -801,6 +900,12 @@ namespace limg_hip
     hipLaunchKernelGGL(k_stream_count, dim3(p.nTiles), dim3(kTile), 0, s, p);
     hipLaunchKernelGGL(k_stream_tile_scan<1>, dim3(1), dim3(1024), 0, s, p.tileBase, p.nTiles, p.stream, header_info(p));
     hipLaunchKernelGGL(k_stream_pack, dim3(p.nTiles), dim3(kTile), 0, s, p);
+  }
+
+  void launch_stream_pack_list(const StreamListParams &b, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_stream_scan_strips_list, dim3(b.nImages), dim3(1024), 0, s, b);
+    hipLaunchKernelGGL(k_stream_pack_strips_list, dim3(b.nWaves), dim3(64), 0, s, b);
   }
 
   void launch_stream_pack_batch(const StreamBatchParams &b, hipStream_t s)

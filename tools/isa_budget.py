@@ -295,8 +295,8 @@ def main():
         print("\n(no PMC file: %r)" % (e,))
 
     # ---- k_fit_tpb
-    F = os.path.join(CSRC, "limg_hip_fit_tpb.hip")
-    ff = "limg_hip_fit_tpb.hip"
+    F = os.path.join(CSRC, "limg_hip_fit_tpb_body.inc")  # the kernel's body: one text for k_fit_tpb and k_fit_tpb_list
+    ff = "limg_hip_fit_tpb_body.inc"
     p1 = marker(F, "// ---- pass 1 (src/limg_factorization.h:602-628)")
     p2 = marker(F, "// ---- pass 2 (:652-688)")
     p3 = marker(F, "// ---- pass 3 ----")
@@ -304,7 +304,7 @@ def main():
     p3c = marker(F, "{ // 3 channels (:498-541)")
     prec = marker(F, "// ---- record (src/limg_factorization.h:764-790)")
     psum = marker(F, "// ---- a4: channel sums (src/limg.cpp:466-497)")
-    fend = function_ranges(F)["k_fit_tpb"][1]
+    fend = sum(1 for _ in open(F))
     phases = [
         ("a4 channel sums", [(ff, psum, p1 - 1)]),
         ("pass 1 (unit vectors of px - avg)", [(ff, p1, p2 - 1)]),
