@@ -204,6 +204,11 @@ uint64_t limg_hip_host_chain_checkpoints(size_t calls, size_t every, uint64_t *p
  *                              embedded tables alone: the dense one where it reaches, the far one + 65536 calls on foot per far value (host threads) beyond;
  *                              limg_hip_error_OutOfBounds beyond 2^27 calls.  Equal to limg_hip_host_chain_checkpoints' serial walk (tests/test_host.py). */
 limg_hip_result limg_hip_host_dense_checkpoints(size_t first, size_t count, uint64_t *pOut);
+/*  limg_hip_host_accurate_table: the accurate shift search's automaton in the expanded form a context uploads on its first accurate encode -- the same routine fills
+ *                              both: 8 dwords per state = { a | phase2 << 5 | final << 31, byte offset of the next entry on pass, on fail, b, c, mul(a), mul(b),
+ *                              mul(c) }, bits 24..26 of either offset = which factors (A, B, C) the successor's triple changes against this state's.  `dwords` must be
+ *                              the table's size, 8 x its state count (18878 states: 151024), else limg_hip_error_InvalidParameter. */
+limg_hip_result limg_hip_host_accurate_table(uint32_t *pOut, size_t dwords);
 
 /* ---- merged-block encoder ----------------------------------------------------------------------------------------------------------
  * Replaces `limg_blocked_encode3d_test` (src/limg.h:46, src/limg.cpp:2329-2453), what the reference's CLI runs on a single file

@@ -25,7 +25,7 @@ ABI_SYMBOLS = (
     "limg_hip_encode3d_stats", "limg_hip_blocked_encode3d_stats",
     "limg_hip_encode3d_device", "limg_hip_encode3d_batch_device", "limg_hip_last_stats", "limg_hip_compare", "limg_hip_compare_device", "limg_hip_synth_random_gradient_device",
     "limg_hip_synth_photo_noise_device", "limg_hip_context_device_bytes", "limg_hip_version", "limg_hip_profile_begin", "limg_hip_profile_end",
-    "limg_hip_host_noise_table", "limg_hip_noise_table_device", "limg_hip_host_chain_call", "limg_hip_host_chain_checkpoints", "limg_hip_host_dense_checkpoints", "limg_hip_host_partition", "limg_hip_check_device_status",
+    "limg_hip_host_noise_table", "limg_hip_noise_table_device", "limg_hip_host_chain_call", "limg_hip_host_chain_checkpoints", "limg_hip_host_dense_checkpoints", "limg_hip_host_accurate_table", "limg_hip_host_partition", "limg_hip_check_device_status",
     "limg_hip_stream_bound", "limg_hip_encode_stream_device", "limg_hip_decode_stream_device", "limg_hip_encode_stream", "limg_hip_decode_stream",
     "limg_hip_stream_info", "limg_hip_encode_stream_batch_device", "limg_hip_encode_stream_batch", "limg_hip_encode_stream_batch_ef_device", "limg_hip_encode_stream_batch_ef",
     "limg_hip_stream_sizes_device", "limg_hip_stream_sizes", "limg_hip_encode_stream_budget_device", "limg_hip_encode_stream_budget",
@@ -276,6 +276,8 @@ def load_library(path=None):
     L.limg_hip_host_chain_checkpoints.argtypes = [C.c_size_t, C.c_size_t, C.c_void_p, C.c_int]
     L.limg_hip_host_dense_checkpoints.restype = C.c_int
     L.limg_hip_host_dense_checkpoints.argtypes = [C.c_size_t, C.c_size_t, C.c_void_p]
+    L.limg_hip_host_accurate_table.restype = C.c_int
+    L.limg_hip_host_accurate_table.argtypes = [C.c_void_p, C.c_size_t]
     L.limg_hip_host_partition.restype = C.c_int
     L.limg_hip_host_partition.argtypes = [C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.limg_hip_context_device_bytes.restype = C.c_size_t
@@ -469,6 +471,15 @@ def host_chain_bases(calls, lib=None):
     calls = np.ascontiguousarray(calls, dtype=np.uint64)
     out = np.zeros(calls.size, dtype=np.uint64)
     _check(lib.limg_hip_host_chain_bases(_np_ptr(calls), calls.size, _np_ptr(out)), "limg_hip_host_chain_bases")
+    return out
+
+
+def host_accurate_table(states, lib=None):
+    """The accurate shift search's automaton as a context uploads it: (states, 8) uint32, `states` = LIMG_SEARCH_ACC_STATES (the library refuses any other size);
+    host only."""
+    lib = lib or load_library()
+    out = np.zeros((states, 8), dtype=np.uint32)
+    _check(lib.limg_hip_host_accurate_table(_np_ptr(out), out.size), "limg_hip_host_accurate_table")
     return out
 
 

@@ -29,12 +29,13 @@ namespace
   // every field in a dword of its own = { a | phase2 << 5 | final << 31, byte offset on pass, byte offset on fail, b, c, mul(a), mul(b), mul(c) }.  Bits 24..26 of the two
   // offsets say which factors' shifts the SUCCESSOR's triple changes against this state's (A, B, C): a state of this DAG has several predecessors, so the change mask is a
   // property of the edge -- with it the kernel needs no record of the shifts its cached terms were built for and no three compares per trial.
-  limg_hip_result ensure_accurate_table(limg_hip_context *c)
+  // The one expansion: what the context uploads and what limg_hip_host_accurate_table hands out (tests/test_search_tables.py checks every entry and edge of it).
+  constexpr size_t kAccTableDwords = (size_t)LIMG_SEARCH_ACC_STATES * 8;
+  void expand_accurate_table(uint32_t *wide /* kAccTableDwords */)
   {
-    if (c->enc.accTable.p) return limg_hip_success;
     static const uint32_t compact[LIMG_SEARCH_ACC_STATES][2] = LIMG_SEARCH_ACC_TABLE_INIT;
     static const uint32_t mul[9] = { 1, 2, 4, 8, 17, 36, 85, 255, 256 }; // (1 << s) + decode_bias(s), src/limg_bit_crush_simd.h:611-619
-    std::vector<uint32_t> wide((size_t)LIMG_SEARCH_ACC_STATES * 8);
+    memset(wide, 0, kAccTableDwords * 4);
     for (size_t i = 0; i < (size_t)LIMG_SEARCH_ACC_STATES; i++)
     {
       const uint32_t w0 = compact[i][0], w1 = compact[i][1];
@@ -59,6 +60,13 @@ namespace
         e[k] |= mask << 24;
       }
     }
+  }
+
+  limg_hip_result ensure_accurate_table(limg_hip_context *c)
+  {
+    if (c->enc.accTable.p) return limg_hip_success;
+    std::vector<uint32_t> wide(kAccTableDwords);
+    expand_accurate_table(wide.data());
     limg_hip_result r = c->enc.accTable.ensure(wide.size() * 4);
     if (r != limg_hip_success) return r;
     if (hipMemcpy(c->enc.accTable.p, wide.data(), wide.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { c->enc.accTable.release(); return limg_hip_error_Generic; }
@@ -407,6 +415,14 @@ extern "C"
     const Partition pt = partition(sizeY, poolThreads);
     *pChainCount = pt.chainCount;
     *pChainBlockRows = pt.chainRows;
+    return limg_hip_success;
+  }
+
+  limg_hip_result limg_hip_host_accurate_table(uint32_t *pOut, size_t dwords)
+  {
+    if (!pOut) return limg_hip_error_ArgumentNull;
+    if (dwords != kAccTableDwords) return limg_hip_error_InvalidParameter;
+    expand_accurate_table(pOut);
     return limg_hip_success;
   }
 

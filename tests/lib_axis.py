@@ -25,6 +25,7 @@ TWIN_SUFFIX = "_product"
 # GPU tests that run on the test build only: each one is about a hook of include/limg_hip_test_hooks.h as a whole (the product has none to set).
 HOOK_ONLY = {
     "test_gpu_parity.py::test_generic_trial_path": "record_limit hook: sends blocks through the generic 32-bit trial, which byte pixels never reach",
+    "test_gpu_search_tables.py::test_generic_trial_accurate": "record_limit hook: the accurate search's literal loops behind the generic 32-bit trial",
     "test_gpu_concurrency.py::test_lookback_timeout_is_loud": "lookback_spins / skip_publish_strip hooks: a strip that never publishes",
     "test_gpu_fullsize.py::test_one_strip_base_error_is_caught": "base_error_strip hook: the sensitivity of the hash pin to one wrong chain base",
     "test_gpu_blocked.py::test_similarity_bits_equal_host_evaluation_with_and_without_the_bound": "blocked_no_bound hook: A/B of the match kernel's bounds",

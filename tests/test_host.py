@@ -139,10 +139,9 @@ def test_search_automaton_replays_reference_searches():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_search_table as mst
-    words = mst.encode(mst.build())
+    words = mst.encode(mst.build())  # (the committed header is exactly these words: tests/test_search_tables.py)
     hdr = open(os.path.join(ROOT, "limg_amd", "csrc", "limg_search_table.h")).read()
     assert "LIMG_SEARCH_STATES %d" % len(words) in hdr
-    assert all(mst.ENTRY_FMT % w in hdr for w in words[:50] + words[-50:])
     z = gu.blocks()
     for bi in range(int(z["count"])):
         for ch in (4, 3):
@@ -154,15 +153,14 @@ def test_search_automaton_replays_reference_searches():
 
 def test_accurate_search_automaton_replays_reference_searches():
     """The accurate search's automaton (tools/make_search_table.py -> limg_search_table_accurate.h, expanded by the library for the kernel) driven by the real
-    reference's trial outcomes and block errors (tests/golden/blocks.npz) ends at the real reference's accurate-search result; the committed header is what the
-    generator produces."""
+    reference's trial outcomes and block errors (tests/golden/blocks.npz) ends at the real reference's accurate-search result.  (The committed header is exactly
+    what the generator produces: tests/test_search_tables.py.)"""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_search_table as mst
     words = mst.encode_accurate(mst.build_accurate())
     hdr = open(os.path.join(ROOT, "limg_amd", "csrc", "limg_search_table_accurate.h")).read()
     assert "LIMG_SEARCH_ACC_STATES %d" % len(words) in hdr
-    assert all(mst.ACC_ENTRY_FMT % w in hdr for w in words[:60] + words[len(words) // 2: len(words) // 2 + 60] + words[-60:])
     z = gu.blocks()
     longest = 0
     for bi in range(int(z["count"])):

@@ -229,7 +229,8 @@ def build_accurate():
 
 def encode_accurate(trans):
     """compact entry = (a | b << 4 | c << 8 | phase2 << 12 | final << 31,  next on pass | next on fail << 16) -- state indices; the library expands it at context
-    creation into the 32-byte form the kernel reads (limg_hip_encode.hip ensure_accurate_table)."""
+    creation into the 32-byte form the kernel reads (limg_hip_encode.hip expand_accurate_table; limg_hip_host_accurate_table hands the same expansion out, and
+    tests/test_search_tables.py checks every entry and edge mask of it against `trans`)."""
     assert len(trans) < 65536
     words = []
     for t in trans:
@@ -491,11 +492,14 @@ def write_hot(K=HOT_K, path=HOT_HEADER):
     print("wrote", path, text.count("// state"), "states")
 
 
-def main():
-    trans = build()
-    words = encode(trans)
+TABLE_HEADER = os.path.join(ROOT, "limg_amd", "csrc", "limg_search_table.h")
+ACC_HEADER = os.path.join(ROOT, "limg_amd", "csrc", "limg_search_table_accurate.h")
+
+
+def emit_table(words):
+    """the text of limg_search_table.h"""
     body = ",\n".join("  " + ", ".join(ENTRY_FMT % w for w in words[i:i + 2]) for i in range(0, len(words), 2))
-    text = """// GENERATED by tools/make_search_table.py -- do not edit.
+    return """// GENERATED by tools/make_search_table.py -- do not edit.
 // Decision automaton of the reference's default shift search (src/limg_bit_crush.h:331-392, :502-614): %d states.
 // entry (8 dwords) = { a | changed << 5 | final << 31,  byte offset of the next entry on pass,  byte offset of the next entry on fail,  b,  c,  mul(a), mul(b), mul(c) };
 // changed = which shifts (bit 0 A, 1 B, 2 C) this entry's triple changes against its (only) predecessor's; state 0 is the start; a final entry carries the
@@ -509,12 +513,12 @@ def main():
 }
 #endif
 """ % (len(words), len(words), ", ".join("0x%xu" % v for v in words[0]), body.replace("\n", " \\\n"))
-    path = os.path.join(ROOT, "limg_amd", "csrc", "limg_search_table.h")
-    open(path, "w").write(text)
-    print("wrote", path, len(words), "states")
-    acc = encode_accurate(build_accurate())
+
+
+def emit_accurate(acc):
+    """the text of limg_search_table_accurate.h"""
     body = ",\n".join(" " + ",".join(ACC_ENTRY_FMT % w for w in acc[i:i + 12]) for i in range(0, len(acc), 12))
-    text = """// GENERATED by tools/make_search_table.py -- do not edit.
+    return """// GENERATED by tools/make_search_table.py -- do not edit.
 // Decision automaton of the reference's ACCURATE shift search (src/limg_bit_crush.h:668-830): %d states (a DAG; state 0 is the start).
 // compact entry = { a | b << 4 | c << 8 | phase2 << 12 | final << 31,  next state on pass | next state on fail << 16 }.  Which trials run depends on pass / fail only;
 // a passing phase-1 trial becomes the result, a passing phase-2 trial only if its block error is below the best so far.  Host-side data: expanded into 32-byte entries
@@ -527,9 +531,15 @@ def main():
 }
 #endif
 """ % (len(acc), len(acc), body.replace("\n", " \\\n"))
-    path = os.path.join(ROOT, "limg_amd", "csrc", "limg_search_table_accurate.h")
-    open(path, "w").write(text)
-    print("wrote", path, len(acc), "states")
+
+
+def main():
+    words = encode(build())
+    open(TABLE_HEADER, "w").write(emit_table(words))
+    print("wrote", TABLE_HEADER, len(words), "states")
+    acc = encode_accurate(build_accurate())
+    open(ACC_HEADER, "w").write(emit_accurate(acc))
+    print("wrote", ACC_HEADER, len(acc), "states")
     write_hot()
 
 
