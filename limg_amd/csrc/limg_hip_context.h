@@ -312,6 +312,23 @@ namespace limg_hip
   // images with partial edge blocks (limg_hip_encode_ragged.hip): the split path's kernels around a dither chain the host walks
   limg_hip_result encode_ragged(EncodeJob &e);
 
+  // the sticky status words (look-back timeout, aborted chain: enc.devStatus), zeroed on `stream` when they are first made
+  limg_hip_result ensure_device_status(limg_hip_context *c, hipStream_t stream);
+  // the persistent kernel's scratch whatever its parameters: `tickets` (>= 2) tickets of 16 bytes, a look-back descriptor per work strip, the status words, the park slots
+  struct PersistentScratch { uint32_t *ticket; unsigned long long *desc; uint32_t *timeout; uint8_t *park; };
+  limg_hip_result persistent_scratch(limg_hip_context *c, size_t strips, size_t tickets, hipStream_t stream, PersistentScratch &ps);
+
+  // ---- one chunk of a stream-encode list of mixed shapes (limg_hip_list_plan.h) as a route of the 8x8 encode ----
+  static_assert(sizeof(RatedListParams) == 160 && sizeof(ListImage) == 64 && sizeof(ImageIO) == 96 && sizeof(RatedImage) == 32 && sizeof(StreamImage) == 32,
+                "the entry sizes tests/test_list_plan_cpu.py asks the table layout for");
+  inline ChunkTables chunk_tables(size_t n) { return ChunkTables(n, { sizeof(RatedListParams), sizeof(ListImage), sizeof(ImageIO), sizeof(RatedImage), sizeof(StreamImage), 4, 4 }); }
+  struct ListChunkImage { const uint32_t *in; size_t sizeX, sizeY; uint32_t errorFactor; uint8_t *fac[3]; }; // whole blocks (list_item_eligible); fac: its three factor planes
+  // The n > 1 images through ONE float-stage grid and ONE persistent launch in compact stream mode, image i at its own error factor: records, invN and shift words
+  // in the context's per-block scratch (grown by the caller) and the strips' payload words in stripWords, image after image; then the statistics.  hostTables: the host copy of the
+  // chunk's table block (chunk_tables(n).bytes, zeroed, the caller's StreamImage entries written): every other part is filled here, ONE upload to devTables.
+  limg_hip_result encode_list_chunk(limg_hip_context *c, const ListChunkImage *images, size_t n, int hasAlpha, int poolThreads, uint32_t *stripWords, uint8_t *hostTables,
+                                    uint8_t *devTables, hipStream_t stream, ListChunkTotals &totals);
+
   // ---- the merged-block encoder's pipeline (limg_hip_blocked_api.hip) ----
   // pInfo == nullptr is the COMPACT mode of the stream entry: no plane is stored.  When the call returns, every rectangle's descriptor (regions), record and shift word
   // (out), pre-dither factor bytes (fac, region-major, plane stride scratchCap), noise bytes (noise) and noise offset (noiseBase) are complete in the

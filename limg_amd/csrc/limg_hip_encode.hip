@@ -9,6 +9,17 @@ using namespace limg_hip;
 namespace
 {
   // the reference's "Average Block Bits" counters (src/limg.cpp:1971-1999) of this encode, left on the device for limg_hip_last_stats
+  // `rows` block rows of shift words of images of shape sh, `pixels` in all; add: on top of what the counters hold
+  limg_hip_result shift_stats(limg_hip_context *c, const uint32_t *shifts, const EncodeShape &sh, size_t rows, uint64_t pixels, bool add, hipStream_t stream)
+  {
+    limg_hip_result rs;
+    if ((rs = c->stats.counters.ensure(30 * 8)) != limg_hip_success) return rs;
+    if (!add) HIP_TRY(hipMemsetAsync(c->stats.counters.p, 0, 30 * 8, stream));
+    launch_shift_stats(shifts, (uint32_t)sh.blocksX, (uint32_t)sh.blocksY, (uint32_t)rows, (uint32_t)sh.sizeX, (uint32_t)sh.sizeY, (unsigned long long *)c->stats.counters.p, stream);
+    c->stats.stream = stream; c->stats.state = 1;
+    c->stats.pixels = (add ? c->stats.pixels : 0) + pixels;
+    return limg_hip_success;
+  }
   limg_hip_result encode_stats(const EncodeJob &e, const limg_hip_compact_out *compact)
   {
     limg_hip_context *const c = e.c;
@@ -16,13 +27,7 @@ namespace
     const EncodeShape sh(e.sizeX, e.sizeY);
     const bool add = c->stats.accumulate && e.plan.path != kPathHeightRagged; // (an image of that path restarts the counters of a list)
     const uint32_t *shifts = (compact && compact->pShifts) ? compact->pShifts : (const uint32_t *)c->enc.shifts.p;
-    limg_hip_result rs;
-    if ((rs = c->stats.counters.ensure(30 * 8)) != limg_hip_success) return rs;
-    if (!add) HIP_TRY(hipMemsetAsync(c->stats.counters.p, 0, 30 * 8, e.stream));
-    launch_shift_stats(shifts, (uint32_t)sh.blocksX, (uint32_t)sh.blocksY, (uint32_t)(sh.blocksY * e.x.batchCount), (uint32_t)e.sizeX, (uint32_t)e.sizeY, (unsigned long long *)c->stats.counters.p, e.stream);
-    c->stats.stream = e.stream; c->stats.state = 1;
-    c->stats.pixels = (add ? c->stats.pixels : 0) + (uint64_t)e.sizeX * e.sizeY * e.x.batchCount;
-    return limg_hip_success;
+    return shift_stats(c, shifts, sh, sh.blocksY * e.x.batchCount, (uint64_t)e.sizeX * e.sizeY * e.x.batchCount, add, e.stream);
   }
 
   // The accurate search's automaton (tools/make_search_table.py, src/limg_bit_crush.h:668-830) in the form the kernel's scalar loads want: 8 dwords per state,
@@ -166,25 +171,17 @@ namespace
     limg_hip_context *const c = e.c;
     EncodeParams &p = e.p;
     limg_hip_result r;
-    if ((r = c->enc.lookback.ensure(16 * (e.x.batchCount + 1) + e.strips * 8)) != limg_hip_success) return r; // (room for one ticket per sub-batch)
-    p.ticket = (uint32_t *)c->enc.lookback.p;
-    p.desc = (unsigned long long *)((uint8_t *)c->enc.lookback.p + 16);
+    PersistentScratch ps;
+    if ((r = persistent_scratch(c, e.strips, e.x.batchCount + 1, e.stream, ps)) != limg_hip_success) return r; // (room for one ticket per sub-batch)
+    p.ticket = ps.ticket; p.desc = ps.desc; p.timeout = ps.timeout; p.park = ps.park;
     p.zeroLookback = p.prefit ? 1 : 0;
-    if (!p.prefit) HIP_TRY(hipMemsetAsync(c->enc.lookback.p, 0, 16 + e.strips * 8, e.stream));
-    if (!c->enc.devStatus.p)
-    {
-      if ((r = c->enc.devStatus.ensure(16)) != limg_hip_success) return r;
-      HIP_TRY(hipMemsetAsync(c->enc.devStatus.p, 0, 16, e.stream));
-    }
-    p.timeout = (uint32_t *)c->enc.devStatus.p;
+    if (!p.prefit) HIP_TRY(hipMemsetAsync(p.ticket, 0, 16 + e.strips * 8, e.stream));
 #ifdef LIMG_HIP_TEST_HOOKS
     p.lookbackSpins = c->topt.lookback_spins > 0 ? (uint32_t)c->topt.lookback_spins : (1u << 22);
     p.testSkipStrip = c->topt.skip_publish_strip > 0 ? (uint32_t)c->topt.skip_publish_strip - 1u : ~0u;
     p.testBaseErrStrip = c->topt.base_error_strip > 0 ? (uint32_t)c->topt.base_error_strip - 1u : ~0u;
 #endif
     p.compactOut = compact != nullptr || e.plan.wantStats; // the statistics are reduced from the raster-order shift words
-    if ((r = c->enc.park.ensure((size_t)(c->enc.persistentWorkgroups / 5 * 6) * 2 * 8192)) != limg_hip_success) return r; // 6 workgroups per CU: the kernel's launch bound
-    p.park = (uint8_t *)c->enc.park.p;
     return limg_hip_success;
   }
 
@@ -196,23 +193,34 @@ namespace
     return (t >= 1 && t < deflt) ? t : deflt;
   }
 
+  // k_encode_list_rated's arguments -- and a view of k_encode_list_mixed's table -- for `batchCount` images of shape sh from the table entries batch / rated on: geometry and partition,
+  // the arrays from those images' first block and strip, the 16-byte access flags, the look-back; forced shifts, record limit and the noise table (grown before this) as the context has them.
+  RatedListParams rated_list_params(const limg_hip_context *c, const EncodeShape &sh, const Partition &pt, const ImageIO *batch, const RatedImage *rated, uint32_t batchCount,
+                                    limg_hip_block_record *records, float *invN, uint32_t *shifts, uint32_t *stripWords, const VecAccess &vec, const PersistentScratch &ps)
+  {
+    RatedListParams r;
+    memset(&r, 0, sizeof(r));
+    r.batch = batch; r.rated = rated;
+    r.batchCount = batchCount; r.imageStrips = (uint32_t)sh.strips;
+    r.sizeX = (uint32_t)sh.sizeX; r.sizeY = (uint32_t)sh.sizeY; r.blocksX = (uint32_t)sh.blocksX; r.blocksY = (uint32_t)sh.blocksY; r.stripsX = (uint32_t)sh.stripsX;
+    forced_shifts(c->opt.forced_shift, r.forced);
+    r.recordLimit = record_limit(c);
+    r.chainCount = pt.chainCount; r.chainRows = pt.chainRows;
+    r.records = records; r.invN = invN; r.shifts = shifts; r.stripWords = stripWords;
+    r.noise = (const uint8_t *)c->noise.table.p; r.noiseLast = (uint32_t)(c->noise.count - 1);
+    r.vecIn = vec.in; r.vecFactors = vec.factors; r.vecFactors8 = vec.factors8;
+    r.desc = ps.desc; r.ticket = ps.ticket; r.timeout = ps.timeout; r.park = ps.park;
+    return r;
+  }
+
   // The persistent launch of a job, or of the sub-batch q of it that starts at image i0 of the list: k_encode_persistent, or -- a list with one error factor per
   // image -- k_encode_list_rated on the same scratch, with the threshold table offset as the image table is.
   void launch_persistent(const EncodeJob &e, const EncodeParams &q, size_t i0, int workgroups)
   {
     if (!e.rated) { launch_encode_persistent(q, e.channels, workgroups, e.stream); return; }
-    RatedListParams r;
-    memset(&r, 0, sizeof(r));
-    r.batch = q.batch; r.rated = e.rated + i0;
-    r.batchCount = q.batchCount; r.imageStrips = q.imageStrips;
-    r.sizeX = q.sizeX; r.sizeY = q.sizeY; r.blocksX = q.blocksX; r.blocksY = q.blocksY; r.stripsX = q.stripsX;
-    for (int k = 0; k < 3; k++) r.forced[k] = q.forced[k];
-    r.recordLimit = q.recordLimit;
-    r.chainCount = q.chainCount; r.chainRows = q.chainRows;
-    r.records = q.records; r.invN = q.invN; r.shifts = q.shifts; r.stripWords = q.stripWords;
-    r.noise = q.noise; r.noiseLast = q.noiseLast;
-    r.vecIn = q.vecIn; r.vecFactors = q.vecFactors; r.vecFactors8 = q.vecFactors8;
-    r.desc = q.desc; r.ticket = q.ticket; r.timeout = q.timeout; r.park = q.park;
+    const PersistentScratch ps = { q.ticket, q.desc, q.timeout, q.park };
+    const VecAccess vec = { q.vecIn != 0, false, q.vecFactors8 != 0, false, q.vecFactors != 0 };
+    const RatedListParams r = rated_list_params(e.c, EncodeShape(q.sizeX, q.sizeY), { q.chainCount, q.chainRows }, q.batch, e.rated + i0, q.batchCount, q.records, q.invN, q.shifts, q.stripWords, vec, ps);
     launch_encode_list_rated(r, e.channels, q.floatFast != 0, workgroups, e.stream);
   }
 
@@ -350,6 +358,88 @@ namespace
 
 namespace limg_hip
 {
+  limg_hip_result ensure_device_status(limg_hip_context *c, hipStream_t stream)
+  {
+    if (c->enc.devStatus.p) return limg_hip_success;
+    const limg_hip_result r = c->enc.devStatus.ensure(16);
+    if (r == limg_hip_success) HIP_TRY(hipMemsetAsync(c->enc.devStatus.p, 0, 16, stream));
+    return r;
+  }
+
+  limg_hip_result persistent_scratch(limg_hip_context *c, size_t strips, size_t tickets, hipStream_t stream, PersistentScratch &ps)
+  {
+    limg_hip_result r;
+    if ((r = c->enc.lookback.ensure(16 * tickets + strips * 8)) != limg_hip_success) return r;
+    if ((r = ensure_device_status(c, stream)) != limg_hip_success) return r;
+    if ((r = c->enc.park.ensure((size_t)(c->enc.persistentWorkgroups / 5 * 6) * 2 * 8192)) != limg_hip_success) return r; // 6 workgroups per CU: the kernel's launch bound
+    ps = { (uint32_t *)c->enc.lookback.p, (unsigned long long *)((uint8_t *)c->enc.lookback.p + 16), (uint32_t *)c->enc.devStatus.p, (uint8_t *)c->enc.park.p };
+    return limg_hip_success;
+  }
+
+  limg_hip_result encode_list_chunk(limg_hip_context *c, const ListChunkImage *images, size_t n, int hasAlpha, int poolThreads, uint32_t *stripWords, uint8_t *hostTables,
+                                    uint8_t *devTables, hipStream_t stream, ListChunkTotals &totals)
+  {
+    // what an outer call resets (encode_device): the context's per-block scratch is reused -- no chain encode's phase 1 is pending any more --, its statistics are stale
+    c->chain.in = nullptr;
+    if (!c->stats.accumulate) c->stats.state = 0;
+    const ChunkTables T = chunk_tables(n);
+    RatedListParams *const views = (RatedListParams *)(hostTables + T.views);
+    ListImage *const list = (ListImage *)(hostTables + T.images);
+    ImageIO *const io = (ImageIO *)(hostTables + T.io);
+    RatedImage *const rated = (RatedImage *)(hostTables + T.rated);
+    uint32_t *const firstStrip = (uint32_t *)(hostTables + T.firstStrip), *const firstUnit = (uint32_t *)(hostTables + T.firstUnit);
+    const ImageIO *const dIo = (const ImageIO *)(devTables + T.io);
+    const RatedImage *const dRated = (const RatedImage *)(devTables + T.rated);
+    ListChunkTotals &tot = totals = {};
+    for (size_t i = 0; i < n; i++)
+    {
+      const ListChunkImage &im = images[i];
+      list[i] = list_image(tot, im.sizeX, im.sizeY, poolThreads, im.in, im.fac);
+      firstStrip[i] = list[i].firstStrip; firstUnit[i] = list[i].firstUnit;
+      io[i].in = im.in; io[i].info.pFactorsA = im.fac[0]; io[i].info.pFactorsB = im.fac[1]; io[i].info.pFactorsC = im.fac[2];
+      const Thresholds t = thresholds(im.errorFactor);
+      rated[i].maxPixel32 = t.maxPixel32; rated[i].blockLimitFull = t.blockLimitFull; rated[i].maxBlock = t.maxBlock; rated[i].crushBits = (int32_t)t.crushBits; rated[i].errorFactor = im.errorFactor;
+    }
+    limg_hip_result r;
+    if ((r = grow_noise_table(c, (size_t)tot.noiseCalls, stream)) != limg_hip_success) return r; // the largest per-chain need of any image: every image starts at the seed
+    PersistentScratch ps;
+    if ((r = persistent_scratch(c, tot.strips, 2, stream, ps)) != limg_hip_success) return r;
+    limg_hip_block_record *const records = (limg_hip_block_record *)c->enc.records.p;
+    float *const invN = (float *)c->enc.invN.p;
+    uint32_t *const shifts = (uint32_t *)c->enc.shifts.p;
+    for (size_t i = 0; i < n; i++)
+    { // the view of image i: RatedListParams as its own launch would have them, the per-block arrays from its first block
+      const ListImage &im = list[i];
+      const VecAccess vec = { (im.vec & kListVecIn) != 0, false, (im.vec & kListVecFactors8) != 0, false, (im.vec & kListVecFactors) != 0 };
+      views[i] = rated_list_params(c, EncodeShape(im.sizeX, im.sizeY), { im.chainCount, im.chainRows }, dIo + i, dRated + i, 1, records + im.firstBlock, invN + 4 * im.firstBlock, shifts + im.firstBlock,
+                                   stripWords, vec, ps);
+    }
+    launch_set_words(devTables, hostTables, T.bytes, stream); // through kernel arguments: stream-ordered, the host copy may die right away
+    const bool floatFast = c->opt.float_mode == 1;
+    const int channels = hasAlpha ? 4 : 3;
+    FitListParams f; MixedListParams m;
+    memset(&f, 0, sizeof(f)); memset(&m, 0, sizeof(m));
+    f.images = (const ListImage *)(devTables + T.images); f.batch = dIo; f.firstUnit = (const uint32_t *)(devTables + T.firstUnit);
+    f.nImages = (uint32_t)n; f.nUnits = tot.units;
+    f.records = records; f.invN = invN; f.desc = ps.desc; f.ticket = ps.ticket;
+    m.views = (const RatedListParams *)(devTables + T.views); m.batch = dIo; m.rated = dRated; m.firstStrip = (const uint32_t *)(devTables + T.firstStrip);
+    m.nImages = (uint32_t)n; m.nStrips = tot.strips; m.ticket = ps.ticket; m.park = ps.park;
+    Timeline tl(c, stream, 4); // {k_fit_tpb_list, k_encode_list_mixed, -}
+    tl.mark();
+    launch_fit_tpb_list(f, channels, floatFast, tot.vecInAll, stream);
+    tl.mark();
+    launch_encode_list_mixed(m, channels, floatFast, c->enc.persistentWorkgroups / 5 * wg_per_cu(c, 6), stream);
+    tl.mark();
+    tl.close();
+    // limg_hip_last_stats: the counters of every image of the chunk, added up (and to what the call's earlier parts left)
+    for (size_t i = 0; c->opt.collect_stats && i < n; i++)
+      if ((r = shift_stats(c, shifts + list[i].firstBlock, EncodeShape(list[i].sizeX, list[i].sizeY), list[i].blocksY, (uint64_t)list[i].sizeX * list[i].sizeY, c->stats.accumulate || i > 0,
+                           stream)) != limg_hip_success)
+        return r;
+    HIP_TRY(hipGetLastError());
+    return limg_hip_success;
+  }
+
   // One 8x8 encode, whichever of its paths applies: the facts, the plan (limg_hip_encode_plan.h), its refusal if there is one -- before anything is grown or
   // enqueued --, the parameters, the plan's path.
   limg_hip_result encode_device(limg_hip_context *c, const uint32_t *dIn, size_t sizeX, size_t sizeY, int hasAlpha, const limg_hip_encode3d_info *dInfo,

@@ -67,13 +67,9 @@ namespace
     limg_hip_result r;
     if ((r = band_streams(c, nb)) != limg_hip_success) return r;
     if ((r = c->host.words.ensure((2 * 64 + 2) * 8)) != limg_hip_success) return r;
-    if (!c->enc.devStatus.p)
-    {
-      if ((r = c->enc.devStatus.ensure(16)) != limg_hip_success) return r;
-      HIP_TRY(hipMemset(c->enc.devStatus.p, 0, 16));
-    }
     unsigned long long *dCalls = (unsigned long long *)c->host.words.p, *dBase = dCalls + 64;
     hipStream_t s = c->host.stream;
+    if ((r = ensure_device_status(c, s)) != limg_hip_success) return r;
     HIP_TRY(hipMemsetAsync(dCalls, 0, 2 * 64 * 8, s));
 
     // the downloads: a second host thread, band after band, as their events fire

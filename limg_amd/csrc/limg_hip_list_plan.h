@@ -99,6 +99,46 @@ namespace limg_hip
     t.blocks += sh.blocks; t.strips += (uint32_t)sh.strips; t.units += list_units(sh);
     return e;
   }
+
+  // one of an image's three factor planes in the chunk's scratch: 256-byte aligned slices
+  inline size_t list_plane_stride(size_t sizeX, size_t sizeY) { return (sizeX * sizeY + 255) & ~(size_t)255; }
+
+  // ---- the tables of one chunk of n images, side by side in one device block: where each part starts (16-byte aligned), given the bytes of one entry of each part:
+  // the image's view (RatedListParams), its ListImage, ImageIO, RatedImage, StreamImage and its two prefix words ----
+  struct ChunkEntrySizes { size_t view, image, io, rated, stream, firstStrip, firstUnit; };
+  struct ChunkTables
+  {
+    size_t views, images, io, rated, streams, firstStrip, firstUnit, bytes;
+    ChunkTables(size_t n, const ChunkEntrySizes &e)
+    {
+      auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+      views = 0; images = up(views + n * e.view); io = up(images + n * e.image); rated = up(io + n * e.io);
+      streams = up(rated + n * e.rated); firstStrip = up(streams + n * e.stream); firstUnit = up(firstStrip + n * e.firstStrip); bytes = up(firstUnit + n * e.firstUnit);
+    }
+  };
+
+  // ---- what the largest chunk of a list asks of the scratch: the chunks of more than one image (list_chunk_end; one image alone takes the single call), each
+  // member the maximum over them -- everything is grown once, before the first launch.  facBytes[i]: image i's three factor planes ----
+  struct ListNeeds { size_t images; uint64_t blocks, strips; size_t facBytes; };
+  inline ListNeeds list_needs(const uint64_t *blocks, const uint64_t *strips, const size_t *facBytes, size_t count, size_t hook)
+  {
+    ListNeeds most = {};
+    for (size_t i0 = 0; i0 < count;)
+    {
+      const size_t i1 = list_chunk_end(blocks, strips, count, i0, hook);
+      if (i1 - i0 > 1)
+      {
+        ListNeeds n = { i1 - i0, 0, 0, 0 };
+        for (size_t i = i0; i < i1; i++) { n.blocks += blocks[i]; n.strips += strips[i]; n.facBytes += facBytes[i]; }
+        if (n.images > most.images) most.images = n.images;
+        if (n.blocks > most.blocks) most.blocks = n.blocks;
+        if (n.strips > most.strips) most.strips = n.strips;
+        if (n.facBytes > most.facBytes) most.facBytes = n.facBytes;
+      }
+      i0 = i1;
+    }
+    return most;
+  }
 }
 
 #endif

@@ -40,12 +40,10 @@ extern "C"
     c->chain.rank = rank; c->chain.world = worldSize;
     limg_hip_result r2 = c->chain.words.ensure((8 + 2 * (size_t)worldSize) * 8); // [0] own value, [1] chain base, [2..3] own (size, capacity), [8 ...] gathered
     if (r2 != limg_hip_success) return r2;
+    // the sticky status words (look-back timeout, aborted chain) exist from here on: the single-chain entry must not have to allocate on its error path.  On the
+    // null stream, in front of the blocking memset: both are done when this returns
+    if ((r2 = ensure_device_status(c, nullptr)) != limg_hip_success) return r2;
     HIP_TRY(hipMemset(c->chain.words.p, 0, (8 + 2 * (size_t)worldSize) * 8));
-    if (!c->enc.devStatus.p)
-    { // the sticky status words (look-back timeout, aborted chain) exist from here on: the single-chain entry must not have to allocate on its error path
-      if ((r2 = c->enc.devStatus.ensure(16)) != limg_hip_success) return r2;
-      HIP_TRY(hipMemset(c->enc.devStatus.p, 0, 16));
-    }
     return limg_hip_success;
   }
 

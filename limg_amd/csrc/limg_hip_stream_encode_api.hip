@@ -91,22 +91,81 @@ namespace
     return (uint32_t)(strips < slots ? strips : slots);
   }
 
-  // ---- host forms of the list entries: the images side by side in host.in, the streams at worst-case size (rounded up to 256 bytes) side by side in stream.buf ----
-  struct StagedList { std::vector<const uint32_t *> in; std::vector<uint8_t *> streams; size_t slice; };
-  limg_hip_result stage_list(limg_hip_context *c, const StreamShape &sh, size_t count, const uint32_t *const *ppIn, StagedList &l)
+  // ---- a list, whichever way it came: items.  A same-shape list (ppIn, ppStreams, one shape, capacityEach) as items, and items as the arrays a same-shape entry takes ----
+  typedef limg_hip_stream_list_item ListItem;
+  std::vector<ListItem> as_items(size_t n, const uint32_t *const *ppIn, uint8_t *const *ppStreams, size_t capacityEach, size_t sizeX, size_t sizeY)
+  {
+    std::vector<ListItem> items(n);
+    for (size_t i = 0; i < n; i++) items[i] = { ppIn[i], ppStreams[i], (uint64_t)capacityEach, (uint32_t)sizeX, (uint32_t)sizeY, 0u, 0u };
+    return items;
+  }
+  struct ItemArrays
+  {
+    std::vector<const uint32_t *> in;
+    std::vector<uint8_t *> streams;
+    std::vector<uint32_t> efs;
+    size_t capacityEach = SIZE_MAX; // the smallest of the items'
+    explicit ItemArrays(const std::vector<ListItem> &items)
+    {
+      for (const ListItem &it : items) { in.push_back(it.pIn); streams.push_back(it.pStream); efs.push_back(it.errorFactor); capacityEach = std::min(capacityEach, (size_t)it.capacity); }
+    }
+  };
+
+  // ---- host forms of the list entries.  Staging: the images side by side in host.in, the streams at worst-case size side by side in stream.buf, every slice
+  // rounded up to 256 bytes; `staged`: the items with both pointers and the capacity replaced ----
+  limg_hip_result stage_items(limg_hip_context *c, const std::vector<ListItem> &items, std::vector<ListItem> &staged)
   {
     HIP_TRY(hipSetDevice(c->device));
-    l.slice = (sh.bound + 255) & ~(size_t)255;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    staged = items;
+    size_t inBytes = 0, outBytes = 0;
+    for (ListItem &it : staged) { it.capacity = up(limg_hip_stream_bound(it.sizeX, it.sizeY)); inBytes += up((size_t)it.sizeX * it.sizeY * 4); outBytes += (size_t)it.capacity; }
     limg_hip_result r;
-    if ((r = c->host.in.ensure(count * sh.px * 4)) != limg_hip_success) return r;
-    if ((r = c->stream.buf.ensure(count * l.slice)) != limg_hip_success) return r;
-    l.in.resize(count); l.streams.resize(count);
-    for (size_t i = 0; i < count; i++)
+    if ((r = c->host.in.ensure(inBytes)) != limg_hip_success) return r;
+    if ((r = c->stream.buf.ensure(outBytes)) != limg_hip_success) return r;
+    size_t inAt = 0, outAt = 0;
+    for (size_t i = 0; i < items.size(); i++)
     {
-      l.in[i] = (const uint32_t *)c->host.in.p + i * sh.px;
-      l.streams[i] = (uint8_t *)c->stream.buf.p + i * l.slice;
-      HIP_TRY(hipMemcpy((void *)l.in[i], ppIn[i], sh.px * 4, hipMemcpyHostToDevice));
+      const size_t px4 = (size_t)items[i].sizeX * items[i].sizeY * 4;
+      staged[i].pIn = (const uint32_t *)((const uint8_t *)c->host.in.p + inAt);
+      staged[i].pStream = (uint8_t *)c->stream.buf.p + outAt;
+      HIP_TRY(hipMemcpy((void *)staged[i].pIn, items[i].pIn, px4, hipMemcpyHostToDevice));
+      inAt += up(px4); outAt += (size_t)staged[i].capacity;
     }
+    return limg_hip_success;
+  }
+
+  // fresh results for a host form's device call, which the caller's are filled from afterwards (its struct_size may be larger than ours)
+  template <class RESULT>
+  std::vector<RESULT> own_results(size_t count)
+  {
+    std::vector<RESULT> results(count);
+    for (size_t i = 0; i < count; i++) { memset(&results[i], 0, sizeof(results[i])); results[i].struct_size = sizeof(RESULT); }
+    return results;
+  }
+
+  // what the device call left for image i, to the caller -> the bytes of its stream.  The entries without a search report sizes.
+  size_t report(size_t *to, const size_t *from, size_t i) { to[i] = from[i]; return from[i]; }
+  size_t report(limg_hip_budget_result *to, const limg_hip_budget_result *from, size_t i)
+  { fill_result(to[i], from[i].errorFactor, from[i].probes, from[i].withinBudget, from[i].bytes); return (size_t)from[i].bytes; }
+  size_t report(limg_hip_quality_result *to, const limg_hip_quality_result *from, size_t i)
+  { fill_result(to[i], from[i].errorFactor, from[i].probes, from[i].withinTarget, from[i].bytes, from[i].errorSum); return (size_t)from[i].bytes; }
+  // A host form (its arguments have been checked): the staging, deviceCall(staged) on the null stream -- it leaves image i's result in own[i] --, the device status, every image's result
+  // to the caller, OutOfBounds -- all reported, no stream written: the single host call's rule -- where a stream is larger than its item's capacity, then each stream down at its own size.
+  template <class RESULT, class CALL>
+  limg_hip_result host_list(limg_hip_context *c, const std::vector<ListItem> &items, const RESULT *own, RESULT *pResults, CALL &&deviceCall)
+  {
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    std::vector<ListItem> staged;
+    limg_hip_result r;
+    if ((r = stage_items(c, items, staged)) != limg_hip_success) return r;
+    if ((r = deviceCall(staged)) != limg_hip_success) return r;
+    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
+    std::vector<size_t> bytes(items.size());
+    bool fits = true;
+    for (size_t i = 0; i < items.size(); i++) { bytes[i] = report(pResults, own, i); fits = fits && bytes[i] <= items[i].capacity; }
+    if (!fits) return limg_hip_error_OutOfBounds;
+    for (size_t i = 0; i < items.size(); i++) HIP_TRY(hipMemcpy(items[i].pStream, staged[i].pStream, bytes[i], hipMemcpyDeviceToHost));
     return limg_hip_success;
   }
 
@@ -311,7 +370,7 @@ namespace
     return list_bytes(c, oneByOne ? images.data() : nullptr, count, pBytes, s);
   }
 
-  // the host form: upload, stream_list_device on the null stream, status, the streams down at their own sizes
+  // the host form: upload, stream_list_device on the null stream, status, the streams down at their own sizes (capacityEach holds the bound: every stream fits)
   limg_hip_result stream_list_host(limg_hip_context *c, bool pointers, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
                                    uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, const uint32_t *efs, int poolThreads, int fastBitCrushing)
   {
@@ -319,15 +378,10 @@ namespace
     limg_hip_result r;
     if ((r = check_list(c, pointers && pBytes != nullptr, count, ppIn, ppStreams, sh, capacityEach, false)) != limg_hip_success) return r;
     if (count == 0) return limg_hip_success;
-    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    StagedList l;
-    if ((r = stage_list(c, sh, count, ppIn, l)) != limg_hip_success) return r;
-    if ((r = stream_list_device(c, true, count, l.in.data(), sizeX, sizeY, hasAlpha, l.streams.data(), l.slice, pBytes, errorFactor, efs, poolThreads, fastBitCrushing, nullptr)) !=
-        limg_hip_success)
-      return r;
-    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], l.streams[i], pBytes[i], hipMemcpyDeviceToHost)); // totalBytes of each, not the capacity
-    return limg_hip_success;
+    return host_list(c, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY), pBytes, pBytes, [&](const std::vector<ListItem> &staged) {
+      const ItemArrays a(staged);
+      return stream_list_device(c, true, count, a.in.data(), sizeX, sizeY, hasAlpha, a.streams.data(), a.capacityEach, pBytes, errorFactor, efs, poolThreads, fastBitCrushing, nullptr);
+    });
   }
 }
 
@@ -583,24 +637,12 @@ extern "C"
     if ((r = check_list(c, pMaxBytes && pResults, count, ppIn, ppStreams, sh, SIZE_MAX, false)) != limg_hip_success) return r; // (capacityEach: the rule below)
     if ((r = check_search(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
     if (count == 0) return limg_hip_success;
-    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    StagedList l;
-    if ((r = stage_list(c, sh, count, ppIn, l)) != limg_hip_success) return r;
-    std::vector<limg_hip_budget_result> results(count);
-    for (size_t i = 0; i < count; i++) { memset(&results[i], 0, sizeof(results[i])); results[i].struct_size = sizeof(limg_hip_budget_result); }
-    if ((r = limg_hip_encode_stream_budget_batch_device(c, count, l.in.data(), sizeX, sizeY, hasAlpha, l.streams.data(), l.slice, pMaxBytes, minErrorFactor, maxErrorFactor,
-                                                        poolThreads, fastBitCrushing, results.data(), nullptr)) != limg_hip_success)
-      return r;
-    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    bool fits = true;
-    for (size_t i = 0; i < count; i++)
-    {
-      fill_result(pResults[i], results[i].errorFactor, results[i].probes, results[i].withinBudget, results[i].bytes);
-      fits = fits && results[i].bytes <= capacityEach;
-    }
-    if (!fits) return limg_hip_error_OutOfBounds; // the single host call's rule: the results say what each stream takes, no stream is written
-    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], l.streams[i], (size_t)results[i].bytes, hipMemcpyDeviceToHost));
-    return limg_hip_success;
+    std::vector<limg_hip_budget_result> results = own_results<limg_hip_budget_result>(count);
+    return host_list(c, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY), results.data(), pResults, [&](const std::vector<ListItem> &staged) {
+      const ItemArrays a(staged);
+      return limg_hip_encode_stream_budget_batch_device(c, count, a.in.data(), sizeX, sizeY, hasAlpha, a.streams.data(), a.capacityEach, pMaxBytes, minErrorFactor, maxErrorFactor,
+                                                        poolThreads, fastBitCrushing, results.data(), nullptr);
+    });
   }
 }
 
@@ -625,22 +667,20 @@ namespace
     std::vector<uint32_t> held(n, 0u); // the h whose stream image i's buffer holds (0: none yet)
     for (size_t i = 0; i < n; i++) st[i] = quality_begin(hLo, hHi, limits[i]);
     std::vector<size_t> active;
-    std::vector<const uint32_t *> in;
-    std::vector<uint8_t *> out;
-    std::vector<uint32_t> efs;
     std::vector<limg_hip_stream_list_item> list;
     std::vector<limg_hip_error_window_job> jobs;
     std::vector<unsigned long long> sums;
     // the images of `active` at 2 x their search's next value (where it is over: at the result)
     auto encode_active = [&]() {
-      in.clear(); out.clear(); efs.clear(); list.clear();
+      list.clear();
       for (size_t i : active)
       {
-        in.push_back(items[i].pIn); out.push_back(items[i].pStream); efs.push_back(2u * quality_next(st[i])); held[i] = quality_next(st[i]);
-        list.push_back(items[i]); list.back().errorFactor = efs.back(); list.back().reserved = 0;
+        held[i] = quality_next(st[i]);
+        list.push_back(items[i]); list.back().errorFactor = 2u * held[i]; list.back().reserved = 0;
       }
       if (mixed) return limg_hip_encode_stream_list_device(c, list.size(), list.data(), sizeof(limg_hip_stream_list_item), hasAlpha, nullptr, poolThreads, fastBitCrushing, stream);
-      return limg_hip_encode_stream_batch_ef_device(c, active.size(), in.data(), items[0].sizeX, items[0].sizeY, hasAlpha, out.data(), (size_t)items[0].capacity, nullptr, efs.data(),
+      const ItemArrays a(list);
+      return limg_hip_encode_stream_batch_ef_device(c, list.size(), a.in.data(), items[0].sizeX, items[0].sizeY, hasAlpha, a.streams.data(), a.capacityEach, nullptr, a.efs.data(),
                                                     poolThreads, fastBitCrushing, stream);
     };
     for (uint32_t round = 0, most = rate_max_probes(hLo, hHi); round <= most; round++)
@@ -678,20 +718,14 @@ namespace
     return limg_hip_success;
   }
 
-  // fresh results for a host form's device call, which the caller's are filled from afterwards (its struct_size may be larger than ours)
-  std::vector<limg_hip_quality_result> own_results(size_t count)
+  // the host form of both list entries (the arguments have been checked)
+  limg_hip_result quality_list_host(limg_hip_context *c, const std::vector<ListItem> &items, bool mixed, int hasAlpha, const uint64_t *limits, uint32_t hLo, uint32_t hHi,
+                                    int poolThreads, int fastBitCrushing, limg_hip_quality_result *pResults)
   {
-    std::vector<limg_hip_quality_result> results(count);
-    for (size_t i = 0; i < count; i++) { memset(&results[i], 0, sizeof(results[i])); results[i].struct_size = sizeof(limg_hip_quality_result); }
-    return results;
-  }
-
-  // a same-shape list as items (what quality_searches reads)
-  std::vector<limg_hip_stream_list_item> as_items(size_t n, const uint32_t *const *ppIn, uint8_t *const *ppStreams, size_t capacityEach, size_t sizeX, size_t sizeY)
-  {
-    std::vector<limg_hip_stream_list_item> items(n);
-    for (size_t i = 0; i < n; i++) items[i] = { ppIn[i], ppStreams[i], (uint64_t)capacityEach, (uint32_t)sizeX, (uint32_t)sizeY, 0u, 0u };
-    return items;
+    std::vector<limg_hip_quality_result> results = own_results<limg_hip_quality_result>(items.size());
+    return host_list(c, items, results.data(), pResults, [&](const std::vector<ListItem> &staged) {
+      return quality_searches(c, staged.size(), staged.data(), mixed, hasAlpha, limits, hLo, hHi, poolThreads, fastBitCrushing, results.data(), nullptr);
+    });
   }
 }
 
@@ -754,31 +788,14 @@ extern "C"
     if ((r = check_list(c, pMaxErrorSums && pResults, count, ppIn, ppStreams, sh, SIZE_MAX, false)) != limg_hip_success) return r; // (capacityEach: the rule below)
     if ((r = check_search(count, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
     if (count == 0) return limg_hip_success;
-    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    StagedList l;
-    if ((r = stage_list(c, sh, count, ppIn, l)) != limg_hip_success) return r;
-    std::vector<limg_hip_quality_result> results = own_results(count);
-    if ((r = limg_hip_encode_stream_quality_batch_device(c, count, l.in.data(), sizeX, sizeY, hasAlpha, l.streams.data(), l.slice, pMaxErrorSums, minErrorFactor, maxErrorFactor,
-                                                         poolThreads, fastBitCrushing, results.data(), nullptr)) != limg_hip_success)
-      return r;
-    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    bool fits = true;
-    for (size_t i = 0; i < count; i++)
-    {
-      fill_result(pResults[i], results[i].errorFactor, results[i].probes, results[i].withinTarget, results[i].bytes, results[i].errorSum);
-      fits = fits && results[i].bytes <= capacityEach;
-    }
-    if (!fits) return limg_hip_error_OutOfBounds; // the single host call's rule: the results say what each stream takes, no stream is written
-    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(ppStreams[i], l.streams[i], (size_t)results[i].bytes, hipMemcpyDeviceToHost));
-    return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    return quality_list_host(c, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY), false, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults);
   }
 }
 
 // ---- stream encode of a list of mixed shapes (contract: include/limg_hip.h; the layout: limg_hip_list_plan.h) ----
 namespace
 {
-  typedef limg_hip_stream_list_item ListItem;
-
   // The items as the caller's array holds them (itemSize apart), checked in the contract's order.  deviceForm: the streams are device buffers.
   limg_hip_result check_items(const void *c, bool pointers, size_t count, const ListItem *pItems, size_t itemSize, bool deviceForm, std::vector<ListItem> &items)
   {
@@ -799,118 +816,38 @@ namespace
     return limg_hip_success;
   }
 
-  // the tables of one chunk, side by side in stream.listTable (every part 16-byte aligned)
-  struct ChunkTables
+  // One chunk of eligible items of more than one shape: the images' factor planes in slices of stream.fac, the chunk's table block with this layer's part of it
+  // (the StreamImage entries), the encode layer's launch pair on them (encode_list_chunk), ONE scan, ONE pack.  Everything it needs has been grown by the caller.
+  limg_hip_result mixed_chunk(limg_hip_context *c, const ListItem *its, size_t n, int hasAlpha, int poolThreads, int fastBitCrushing, hipStream_t s)
   {
-    size_t views, images, io, rated, streams, firstStrip, firstUnit, bytes;
-    explicit ChunkTables(size_t n)
-    {
-      auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-      views = 0; images = up(views + n * sizeof(RatedListParams)); io = up(images + n * sizeof(ListImage)); rated = up(io + n * sizeof(ImageIO));
-      streams = up(rated + n * sizeof(RatedImage)); firstStrip = up(streams + n * sizeof(StreamImage)); firstUnit = up(firstStrip + n * 4); bytes = up(firstUnit + n * 4);
-    }
-  };
-
-  // One chunk of eligible items of more than one shape: the tables, ONE float-stage grid, ONE persistent launch, ONE scan, ONE pack.  Everything it needs has
-  // been grown by the caller.  its: the chunk's items.
-  limg_hip_result mixed_chunk(limg_hip_context *c, const ListItem *const *its, size_t n, int hasAlpha, int poolThreads, int fastBitCrushing, hipStream_t s)
-  {
-    const ChunkTables T(n);
+    const ChunkTables T = chunk_tables(n);
     std::vector<uint8_t> host(T.bytes, 0);
     uint8_t *const dev = (uint8_t *)c->stream.listTable.p;
-    RatedListParams *views = (RatedListParams *)(host.data() + T.views);
-    ListImage *images = (ListImage *)(host.data() + T.images);
-    ImageIO *io = (ImageIO *)(host.data() + T.io);
-    RatedImage *rated = (RatedImage *)(host.data() + T.rated);
     StreamImage *streams = (StreamImage *)(host.data() + T.streams);
-    uint32_t *firstStrip = (uint32_t *)(host.data() + T.firstStrip), *firstUnit = (uint32_t *)(host.data() + T.firstUnit);
-    ListChunkTotals tot = {};
+    std::vector<ListChunkImage> images(n);
     size_t facAt = 0;
     for (size_t i = 0; i < n; i++)
     {
-      const ListItem &it = *its[i];
-      const size_t planeStride = ((size_t)it.sizeX * it.sizeY + 255) & ~(size_t)255; // 256-byte aligned slices
-      uint8_t *fac[3];
-      for (int k = 0; k < 3; k++) { fac[k] = (uint8_t *)c->stream.fac.p + facAt; facAt += planeStride; }
-      images[i] = list_image(tot, it.sizeX, it.sizeY, poolThreads, it.pIn, fac);
-      firstStrip[i] = images[i].firstStrip; firstUnit[i] = images[i].firstUnit;
-      io[i].in = it.pIn; io[i].info.pFactorsA = fac[0]; io[i].info.pFactorsB = fac[1]; io[i].info.pFactorsC = fac[2];
-      streams[i].fac[0] = fac[0]; streams[i].fac[1] = fac[1]; streams[i].fac[2] = fac[2]; streams[i].stream = it.pStream;
-      const Thresholds t = thresholds(it.errorFactor);
-      rated[i].maxPixel32 = t.maxPixel32; rated[i].blockLimitFull = t.blockLimitFull; rated[i].maxBlock = t.maxBlock; rated[i].crushBits = (int32_t)t.crushBits;
-      rated[i].errorFactor = it.errorFactor;
+      const ListItem &it = its[i];
+      images[i].in = it.pIn; images[i].sizeX = it.sizeX; images[i].sizeY = it.sizeY; images[i].errorFactor = it.errorFactor;
+      for (int k = 0; k < 3; k++) { streams[i].fac[k] = images[i].fac[k] = (uint8_t *)c->stream.fac.p + facAt; facAt += list_plane_stride(it.sizeX, it.sizeY); }
+      streams[i].stream = it.pStream;
     }
-    limg_hip_result r;
-    if ((r = grow_noise_table(c, (size_t)tot.noiseCalls, s)) != limg_hip_success) return r; // the largest per-chain need of any image: every image starts at the seed
-    uint32_t *const ticket = (uint32_t *)c->enc.lookback.p;
-    unsigned long long *const desc = (unsigned long long *)((uint8_t *)c->enc.lookback.p + 16);
-    for (size_t i = 0; i < n; i++)
-    { // the view of image i: RatedListParams as its own launch would have them, the per-block arrays from its first block
-      RatedListParams &v = views[i];
-      const ListImage &im = images[i];
-      v.batch = (const ImageIO *)(dev + T.io) + i; v.rated = (const RatedImage *)(dev + T.rated) + i;
-      v.batchCount = 1; v.imageStrips = im.strips;
-      v.sizeX = im.sizeX; v.sizeY = im.sizeY; v.blocksX = im.blocksX; v.blocksY = im.blocksY; v.stripsX = im.stripsX;
-      forced_shifts(c->opt.forced_shift, v.forced);
-      v.recordLimit = record_limit(c);
-      v.chainCount = im.chainCount; v.chainRows = im.chainRows;
-      v.records = (limg_hip_block_record *)c->enc.records.p + im.firstBlock; v.invN = (float *)c->enc.invN.p + 4 * im.firstBlock; v.shifts = (uint32_t *)c->enc.shifts.p + im.firstBlock;
-      v.stripWords = (uint32_t *)c->stream.units.p;
-      v.noise = (const uint8_t *)c->noise.table.p; v.noiseLast = (uint32_t)(c->noise.count - 1);
-      v.vecIn = (im.vec & kListVecIn) != 0; v.vecFactors = (im.vec & kListVecFactors) != 0; v.vecFactors8 = (im.vec & kListVecFactors8) != 0;
-      v.desc = desc; v.ticket = ticket; v.timeout = (uint32_t *)c->enc.devStatus.p; v.park = (uint8_t *)c->enc.park.p;
-    }
-    launch_set_words(dev, host.data(), T.bytes, s); // through kernel arguments: stream-ordered, `host` may die right away
-
-    const bool floatFast = c->opt.float_mode == 1;
-    const int channels = hasAlpha ? 4 : 3;
-    FitListParams f;
-    memset(&f, 0, sizeof(f));
-    f.images = (const ListImage *)(dev + T.images); f.batch = (const ImageIO *)(dev + T.io); f.firstUnit = (const uint32_t *)(dev + T.firstUnit);
-    f.nImages = (uint32_t)n; f.nUnits = tot.units;
-    f.records = (limg_hip_block_record *)c->enc.records.p; f.invN = (float *)c->enc.invN.p;
-    f.desc = desc; f.ticket = ticket;
-    MixedListParams m;
-    memset(&m, 0, sizeof(m));
-    m.views = (const RatedListParams *)(dev + T.views); m.batch = f.batch; m.rated = (const RatedImage *)(dev + T.rated); m.firstStrip = (const uint32_t *)(dev + T.firstStrip);
-    m.nImages = (uint32_t)n; m.nStrips = tot.strips;
-    m.ticket = ticket; m.park = (uint8_t *)c->enc.park.p;
-    const int perCu = TOPT(c, wg_per_cu) >= 1 && TOPT(c, wg_per_cu) < 6 ? TOPT(c, wg_per_cu) : 6; // (never above the launch bound the park slots are sized for)
-    {
-      Timeline tl(c, s, 4); // {k_fit_tpb_list, k_encode_list_mixed, -}
-      tl.mark();
-      launch_fit_tpb_list(f, channels, floatFast, tot.vecInAll, s);
-      tl.mark();
-      launch_encode_list_mixed(m, channels, floatFast, c->enc.persistentWorkgroups / 5 * perCu, s);
-      tl.mark();
-      tl.close();
-    }
+    uint32_t *const stripWords = (uint32_t *)c->stream.units.p;
+    ListChunkTotals tot;
+    const limg_hip_result r = encode_list_chunk(c, images.data(), n, hasAlpha, poolThreads, stripWords, host.data(), dev, s, tot);
+    if (r != limg_hip_success) return r;
     StreamListParams b;
     memset(&b, 0, sizeof(b));
-    b.images = f.images; b.streams = (const StreamImage *)(dev + T.streams); b.rated = m.rated; b.firstStrip = m.firstStrip;
+    b.images = (const ListImage *)(dev + T.images); b.streams = (const StreamImage *)(dev + T.streams); b.rated = (const RatedImage *)(dev + T.rated); b.firstStrip = (const uint32_t *)(dev + T.firstStrip);
     b.nImages = (uint32_t)n; b.nStrips = tot.strips; b.nWaves = pack_waves(c, tot.strips);
-    b.channels = (uint32_t)channels; b.flags = stream_flags(c, fastBitCrushing);
-    b.records = f.records; b.shifts = (const uint32_t *)c->enc.shifts.p; b.stripWords = (uint32_t *)c->stream.units.p;
-    {
-      Timeline tl(c, s, 4); // {scan + pack of the chunk, -, -}
-      tl.mark();
-      launch_stream_pack_list(b, s);
-      tl.close();
-    }
+    b.channels = hasAlpha ? 4u : 3u; b.flags = stream_flags(c, fastBitCrushing);
+    b.records = (const limg_hip_block_record *)c->enc.records.p; b.shifts = (const uint32_t *)c->enc.shifts.p; b.stripWords = stripWords;
+    Timeline tl(c, s, 4); // {scan + pack of the chunk, -, -}
+    tl.mark();
+    launch_stream_pack_list(b, s);
+    tl.close();
     HIP_TRY(hipGetLastError());
-    if (c->opt.collect_stats)
-    { // limg_hip_last_stats: the counters of every image of the chunk, added up (and to what the call's earlier parts left)
-      if ((r = c->stats.counters.ensure(30 * 8)) != limg_hip_success) return r;
-      if (!c->stats.accumulate) { HIP_TRY(hipMemsetAsync(c->stats.counters.p, 0, 30 * 8, s)); c->stats.pixels = 0; }
-      for (size_t i = 0; i < n; i++)
-      {
-        const ListImage &im = images[i];
-        launch_shift_stats((const uint32_t *)c->enc.shifts.p + im.firstBlock, im.blocksX, im.blocksY, im.blocksY, im.sizeX, im.sizeY, (unsigned long long *)c->stats.counters.p, s);
-        c->stats.pixels += (uint64_t)im.sizeX * im.sizeY;
-      }
-      c->stats.stream = s; c->stats.state = 1;
-      HIP_TRY(hipGetLastError());
-    }
     return limg_hip_success;
   }
 
@@ -923,10 +860,10 @@ namespace
     if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    std::vector<const ListItem *> shared, alone;
-    for (const ListItem &it : items) (list_item_eligible(it.sizeX, it.sizeY, fastBitCrushing, c->opt) ? shared : alone).push_back(&it);
+    std::vector<ListItem> shared, alone;
+    for (const ListItem &it : items) (list_item_eligible(it.sizeX, it.sizeY, fastBitCrushing, c->opt) ? shared : alone).push_back(it);
     bool oneShape = true;
-    for (const ListItem *it : shared) oneShape = oneShape && it->sizeX == shared[0]->sizeX && it->sizeY == shared[0]->sizeY;
+    for (const ListItem &it : shared) oneShape = oneShape && it.sizeX == shared[0].sizeX && it.sizeY == shared[0].sizeY;
     limg_hip_result r = limg_hip_success;
     if ((r = c->stream.table.ensure(count * sizeof(StreamImage))) != limg_hip_success) return r;
     bool first = true; // limg_hip_last_stats: all images of the list together, whichever way each went
@@ -934,19 +871,11 @@ namespace
       c->stats.accumulate = !first; first = false;
       return limg_hip_encode_stream_device(c, it.pIn, it.sizeX, it.sizeY, hasAlpha, it.pStream, (size_t)it.capacity, nullptr, it.errorFactor, poolThreads, fastBitCrushing, stream);
     };
-    if (shared.size() == 1) r = single(*shared[0]);
+    if (shared.size() == 1) r = single(shared[0]);
     else if (!shared.empty() && oneShape)
     { // the same-shape list, as it is: limg_hip_encode_stream_batch_ef_device's route
-      std::vector<const uint32_t *> in;
-      std::vector<uint8_t *> out;
-      std::vector<uint32_t> efs;
-      size_t capacityEach = SIZE_MAX;
-      for (const ListItem *it : shared)
-      {
-        in.push_back(it->pIn); out.push_back(it->pStream); efs.push_back(it->errorFactor);
-        if (it->capacity < capacityEach) capacityEach = (size_t)it->capacity;
-      }
-      r = stream_list_device(c, true, shared.size(), in.data(), shared[0]->sizeX, shared[0]->sizeY, hasAlpha, out.data(), capacityEach, nullptr, 0, efs.data(), poolThreads,
+      const ItemArrays a(shared);
+      r = stream_list_device(c, true, shared.size(), a.in.data(), shared[0].sizeX, shared[0].sizeY, hasAlpha, a.streams.data(), a.capacityEach, nullptr, 0, a.efs.data(), poolThreads,
                              fastBitCrushing, stream);
       first = false;
     }
@@ -954,89 +883,39 @@ namespace
     {
       // the chunks, and everything the largest of them needs, before the first launch: nothing is grown (and so freed) between the chunks of a list
       std::vector<uint64_t> blocks(shared.size()), strips(shared.size());
-      for (size_t i = 0; i < shared.size(); i++) { const EncodeShape sh(shared[i]->sizeX, shared[i]->sizeY); blocks[i] = sh.blocks; strips[i] = sh.strips; }
+      std::vector<size_t> fac(shared.size());
+      for (size_t i = 0; i < shared.size(); i++) { const EncodeShape sh(shared[i].sizeX, shared[i].sizeY); blocks[i] = sh.blocks; strips[i] = sh.strips; fac[i] = 3 * list_plane_stride(sh.sizeX, sh.sizeY); }
       const size_t hook = TOPT(c, batch_chunk) > 0 ? (size_t)TOPT(c, batch_chunk) : 0;
-      size_t mostN = 0, mostFac = 0;
-      uint64_t mostBlocks = 0, mostStrips = 0;
-      for (size_t i0 = 0; i0 < shared.size();)
+      const ListNeeds most = list_needs(blocks.data(), strips.data(), fac.data(), shared.size(), hook);
+      if (most.images > 1)
       {
-        const size_t i1 = list_chunk_end(blocks.data(), strips.data(), shared.size(), i0, hook);
-        if (i1 - i0 > 1)
-        {
-          uint64_t b = 0, st = 0;
-          size_t fac = 0;
-          for (size_t i = i0; i < i1; i++) { b += blocks[i]; st += strips[i]; fac += 3 * ((((size_t)shared[i]->sizeX * shared[i]->sizeY) + 255) & ~(size_t)255); }
-          if (i1 - i0 > mostN) mostN = i1 - i0;
-          if (b > mostBlocks) mostBlocks = b;
-          if (st > mostStrips) mostStrips = st;
-          if (fac > mostFac) mostFac = fac;
-        }
-        i0 = i1;
-      }
-      if (mostN > 1)
-      {
-        if ((r = c->stream.listTable.ensure(ChunkTables(mostN).bytes)) != limg_hip_success) return r;
-        if ((r = c->stream.fac.ensure(mostFac)) != limg_hip_success) return r;
-        if ((r = c->stream.units.ensure((size_t)mostStrips * 4)) != limg_hip_success) return r;
-        if ((r = c->enc.records.ensure((size_t)mostBlocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
-        if ((r = c->enc.shifts.ensure((size_t)mostBlocks * 4)) != limg_hip_success) return r;
-        if ((r = c->enc.invN.ensure((size_t)mostBlocks * 16)) != limg_hip_success) return r;
-        if ((r = c->enc.lookback.ensure(32 + (size_t)mostStrips * 8)) != limg_hip_success) return r;
-        if ((r = c->enc.park.ensure((size_t)(c->enc.persistentWorkgroups / 5 * 6) * 2 * 8192)) != limg_hip_success) return r; // 6 workgroups per CU: the kernel's launch bound
-        if (!c->enc.devStatus.p)
-        {
-          if ((r = c->enc.devStatus.ensure(16)) != limg_hip_success) return r;
-          HIP_TRY(hipMemsetAsync(c->enc.devStatus.p, 0, 16, s));
-        }
+        PersistentScratch ps;
+        if ((r = c->stream.listTable.ensure(chunk_tables(most.images).bytes)) != limg_hip_success) return r;
+        if ((r = c->stream.fac.ensure(most.facBytes)) != limg_hip_success) return r;
+        if ((r = c->stream.units.ensure((size_t)most.strips * 4)) != limg_hip_success) return r;
+        if ((r = c->enc.records.ensure((size_t)most.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+        if ((r = c->enc.shifts.ensure((size_t)most.blocks * 4)) != limg_hip_success) return r;
+        if ((r = c->enc.invN.ensure((size_t)most.blocks * 16)) != limg_hip_success) return r;
+        if ((r = persistent_scratch(c, (size_t)most.strips, 2, s, ps)) != limg_hip_success) return r;
       }
       for (size_t i0 = 0; i0 < shared.size() && r == limg_hip_success;)
       {
         const size_t i1 = list_chunk_end(blocks.data(), strips.data(), shared.size(), i0, hook);
-        if (i1 - i0 == 1) r = single(*shared[i0]); // a chunk that holds one item: the single call
+        if (i1 - i0 == 1) r = single(shared[i0]); // a chunk that holds one item: the single call
         else
         {
-          c->chain.in = nullptr; // (the context's per-block scratch is reused: no chain encode's phase 1 is pending any more)
           c->stats.accumulate = !first; first = false;
-          if (!c->stats.accumulate) c->stats.state = 0;
           r = mixed_chunk(c, &shared[i0], i1 - i0, hasAlpha, poolThreads, fastBitCrushing, s);
         }
         i0 = i1;
       }
     }
-    for (size_t i = 0; i < alone.size() && r == limg_hip_success; i++) r = single(*alone[i]);
+    for (size_t i = 0; i < alone.size() && r == limg_hip_success; i++) r = single(alone[i]);
     c->stats.accumulate = false;
     if (r != limg_hip_success || !pBytes) return r;
     std::vector<StreamImage> images(count);
     for (size_t i = 0; i < count; i++) images[i].stream = items[i].pStream;
     return list_bytes(c, images.data(), count, pBytes, s);
-  }
-
-  // a host form's staging: the images side by side in host.in, the streams at worst-case size (rounded up to 256 bytes) side by side in stream.buf; `staged`:
-  // the items with both pointers replaced
-  limg_hip_result stage_items(limg_hip_context *c, const std::vector<ListItem> &items, std::vector<ListItem> &staged)
-  {
-    HIP_TRY(hipSetDevice(c->device));
-    size_t inBytes = 0, outBytes = 0;
-    for (const ListItem &it : items)
-    {
-      inBytes += (((size_t)it.sizeX * it.sizeY * 4) + 255) & ~(size_t)255;
-      outBytes += (limg_hip_stream_bound(it.sizeX, it.sizeY) + 255) & ~(size_t)255;
-    }
-    limg_hip_result r;
-    if ((r = c->host.in.ensure(inBytes)) != limg_hip_success) return r;
-    if ((r = c->stream.buf.ensure(outBytes)) != limg_hip_success) return r;
-    staged = items;
-    size_t inAt = 0, outAt = 0;
-    for (size_t i = 0; i < items.size(); i++)
-    {
-      const size_t px4 = (size_t)items[i].sizeX * items[i].sizeY * 4, bound = limg_hip_stream_bound(items[i].sizeX, items[i].sizeY);
-      staged[i].pIn = (const uint32_t *)((const uint8_t *)c->host.in.p + inAt);
-      staged[i].pStream = (uint8_t *)c->stream.buf.p + outAt;
-      staged[i].capacity = (bound + 255) & ~(size_t)255;
-      HIP_TRY(hipMemcpy((void *)staged[i].pIn, items[i].pIn, px4, hipMemcpyHostToDevice));
-      inAt += (px4 + 255) & ~(size_t)255; outAt += (size_t)staged[i].capacity;
-    }
-    return limg_hip_success;
   }
 }
 
@@ -1053,20 +932,13 @@ extern "C"
   limg_hip_result limg_hip_encode_stream_list(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha, size_t *pBytes,
                                               int poolThreads, int fastBitCrushing)
   {
-    std::vector<ListItem> items, staged;
-    limg_hip_result r;
-    if ((r = check_items(c, pBytes != nullptr, count, pItems, itemSize, false, items)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    if ((r = stage_items(c, items, staged)) != limg_hip_success) return r;
+    std::vector<ListItem> items;
+    const limg_hip_result r = check_items(c, pBytes != nullptr, count, pItems, itemSize, false, items);
+    if (r != limg_hip_success || count == 0) return r;
     std::vector<size_t> bytes(count);
-    if ((r = stream_items_device(c, staged, hasAlpha, bytes.data(), poolThreads, fastBitCrushing, nullptr)) != limg_hip_success) return r;
-    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    bool fits = true;
-    for (size_t i = 0; i < count; i++) { pBytes[i] = bytes[i]; fits = fits && bytes[i] <= items[i].capacity; }
-    if (!fits) return limg_hip_error_OutOfBounds; // all sizes are reported, no stream is written
-    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(items[i].pStream, staged[i].pStream, bytes[i], hipMemcpyDeviceToHost)); // totalBytes of each, not the capacity
-    return limg_hip_success;
+    return host_list(c, items, bytes.data(), pBytes, [&](const std::vector<ListItem> &staged) {
+      return stream_items_device(c, staged, hasAlpha, bytes.data(), poolThreads, fastBitCrushing, nullptr);
+    });
   }
 
   limg_hip_result limg_hip_encode_stream_quality_list_device(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
@@ -1087,25 +959,12 @@ extern "C"
                                                       const uint64_t *pMaxErrorSums, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
                                                       limg_hip_quality_result *pResults)
   {
-    std::vector<ListItem> items, staged;
+    std::vector<ListItem> items;
     uint32_t hLo, hHi;
     limg_hip_result r;
     if ((r = check_items(c, pMaxErrorSums && pResults, count, pItems, itemSize, false, items)) != limg_hip_success) return r;
     if ((r = check_search(count, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
     if (count == 0) return limg_hip_success;
-    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    if ((r = stage_items(c, items, staged)) != limg_hip_success) return r;
-    std::vector<limg_hip_quality_result> results = own_results(count);
-    if ((r = quality_searches(c, count, staged.data(), true, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, results.data(), nullptr)) != limg_hip_success) return r;
-    if ((r = limg_hip_check_device_status(c)) != limg_hip_success) return r;
-    bool fits = true;
-    for (size_t i = 0; i < count; i++)
-    {
-      fill_result(pResults[i], results[i].errorFactor, results[i].probes, results[i].withinTarget, results[i].bytes, results[i].errorSum);
-      fits = fits && results[i].bytes <= items[i].capacity;
-    }
-    if (!fits) return limg_hip_error_OutOfBounds; // the results say what each stream takes, no stream is written
-    for (size_t i = 0; i < count; i++) HIP_TRY(hipMemcpy(items[i].pStream, staged[i].pStream, (size_t)results[i].bytes, hipMemcpyDeviceToHost));
-    return limg_hip_success;
+    return quality_list_host(c, items, true, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults);
   }
 }

@@ -4,6 +4,9 @@
 //                                                       chainCount chainRows vec", then "| blocks strips units noiseCalls vecInAll"
 //   E <w> <h> <fast> <split> <legacy>                   eligibility -> 0 / 1
 //   C <hook> <n> { <blocks> <strips> } x n              chunk boundaries with synthetic counts (no memory) -> the end of every chunk
+//   T <n> <view> <image> <io> <rated> <stream> <firstStrip> <firstUnit>   the table block of a chunk of n images with these entry sizes -> the seven offsets, bytes
+//   N <hook> <n> { <blocks> <strips> <facBytes> } x n   what the largest chunk needs -> "images blocks strips facBytes"
+//   P <w> <h>                                           one factor plane's slice -> bytes
 #include "../../limg_amd/csrc/limg_hip_list_plan.h"
 
 #include <stdio.h>
@@ -69,6 +72,30 @@ int main()
         i0 = i1;
       }
       puts(out.str().c_str());
+    }
+    else if (q == 'T')
+    {
+      size_t n = 0;
+      ChunkEntrySizes e = {};
+      in >> n >> e.view >> e.image >> e.io >> e.rated >> e.stream >> e.firstStrip >> e.firstUnit;
+      const ChunkTables t(n, e);
+      printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", t.views, t.images, t.io, t.rated, t.streams, t.firstStrip, t.firstUnit, t.bytes);
+    }
+    else if (q == 'N')
+    {
+      size_t hook = 0, n = 0;
+      in >> hook >> n;
+      std::vector<uint64_t> blocks(n), strips(n);
+      std::vector<size_t> fac(n);
+      for (size_t i = 0; i < n; i++) in >> blocks[i] >> strips[i] >> fac[i];
+      const ListNeeds m = list_needs(blocks.data(), strips.data(), fac.data(), n, hook);
+      printf("%zu %llu %llu %zu\n", m.images, (unsigned long long)m.blocks, (unsigned long long)m.strips, m.facBytes);
+    }
+    else if (q == 'P')
+    {
+      unsigned long long w = 0, h = 0;
+      in >> w >> h;
+      printf("%zu\n", list_plane_stride((size_t)w, (size_t)h));
     }
     else puts("?");
   }

@@ -379,4 +379,22 @@ def test_collect_stats(gpu, oracle, lists):
     assert p == pixels == sum(i.size for i in imgs) and np.array_equal(c, total), (c, total)
 
 
+def test_list_ends_a_pending_chain_phase(gpu):
+    """the mixed chunk reuses the context's per-block scratch as any outer encode does: a chain encode's phase 1 that was pending is gone, and its phase 2 is
+    refused (InvalidParameter) instead of running the F step on the list's records"""
+    import torch
+    strip = torch.zeros((16, 256), dtype=torch.int32, device="cuda")
+    planes = gpu.alloc_planes_device(256, 16)
+    calls, base = torch.zeros(1, dtype=torch.int64, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
+    gpu.encode3d_chain_device(strip, True, planes, 1, calls=calls)
+    gpu.encode3d_chain_device(strip, True, planes, 2, base=base)  # (with nothing in between, the same arguments are accepted)
+    gpu.encode3d_chain_device(strip, True, planes, 1, calls=calls)
+    imgs = [torch.zeros((h, w), dtype=torch.int32, device="cuda") for w, h in ((256, 8), (8, 8))]  # two eligible shapes: one chunk through the shared launches
+    gpu.encode_stream_list_device(imgs, True, [100, 37])
+    with pytest.raises(limg_amd.LimgHipError, match="limg_hip_result 101"):
+        gpu.encode3d_chain_device(strip, True, planes, 2, base=base)
+    torch.cuda.synchronize()
+    gpu.check()
+
+
 L.product_twins(globals())  # test_x_product: the same tests on the product library (tests/lib_axis.py)

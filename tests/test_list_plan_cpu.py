@@ -1,7 +1,8 @@
 """limg_amd/csrc/limg_hip_list_plan.h -- the layout of a stream-encode list of mixed shapes: per image its blocks, strips, float-stage units and where each starts,
 its OWN 16-byte access flags and dither-chain partition; per chunk the totals, the noise need (the maximum over the images, not the sum), the chunk boundaries and
-eligibility -- without a GPU: tests/helpers/list_plan_check.cpp is built by the host compiler alone (under the undefined-behaviour sanitizer) and prints the header's
-answers, which are compared with the rules restated here on the lists tests/test_gpu_stream_list.py encodes."""
+eligibility; the layout of a chunk's table block and what a list grows before its first launch -- without a GPU: tests/helpers/list_plan_check.cpp is built by
+the host compiler alone (under the undefined-behaviour sanitizer) and prints the header's answers, which are compared with the rules restated here on the lists
+tests/test_gpu_stream_list.py encodes."""
 import os
 import shutil
 import subprocess
@@ -159,3 +160,53 @@ def test_chunk_boundaries(ask):
         assert ends == chunk_ends(b, s, hook), (hook, b, s, line)
         assert ends[-1] == len(b) and all(e1 > e0 for e0, e1 in zip([0] + ends, ends))
     assert [int(x) for x in got[0].split()] == [3, 6, 7] and [int(x) for x in got[2].split()] == [2, 3, 4, 5, 6, 7] and [int(x) for x in got[3].split()] == [2, 3, 4, 5]
+
+
+ENTRY_SIZES = (160, 64, 96, 32, 32, 4, 4)  # view, ListImage, ImageIO, RatedImage, StreamImage, two prefix words (limg_hip_context.h asserts each sizeof)
+
+
+def test_table_layout(ask):
+    """a chunk's table block with the real entry sizes: every part starts on a 16-byte boundary, no two parts overlap, `bytes` covers them all"""
+    ns = (1, 2, 3, 64, 65)
+    got = ask(["T %d " % n + " ".join(str(e) for e in ENTRY_SIZES) for n in ns])
+    for n, line in zip(ns, got):
+        v = [int(x) for x in line.split()]
+        assert len(v) == 8, line
+        offsets, total = v[:7], v[7]
+        assert all(o % 16 == 0 for o in offsets) and total % 16 == 0, (n, line)
+        spans = sorted((o, o + n * e) for o, e in zip(offsets, ENTRY_SIZES))
+        assert spans[0][0] == 0 and all(a1 <= b0 for (_, a1), (b0, _) in zip(spans, spans[1:])), (n, spans)
+        assert spans[-1][1] <= total < spans[-1][1] + 16, (n, spans, total)
+        assert offsets == sorted(offsets), (n, line)  # the order the device code is given: views, images, io, rated, streams, the prefix words
+
+
+def needs(blocks, strips, fac, hook):
+    """the largest chunk of more than one image, member by member"""
+    most, i0 = [0, 0, 0, 0], 0
+    for i1 in chunk_ends(blocks, strips, hook):
+        if i1 - i0 > 1:
+            most = [max(most[0], i1 - i0), max(most[1], sum(blocks[i0:i1])), max(most[2], sum(strips[i0:i1])), max(most[3], sum(fac[i0:i1]))]
+        i0 = i1
+    return tuple(most)
+
+
+def test_needs(ask):
+    """what a list grows before its first launch: on the `edges` and `sixty_six` lists of tests/test_gpu_stream_list.py, whole and in chunks of three, and on a
+    synthetic list whose chunks break on the 1 GiB of block records (the members' maxima come from different chunks)"""
+    small = ((264, 24), (8, 8), (256, 8), (24, 40), (512, 32))
+    cases = []
+    for shapes in (LISTS["edges"], tuple(small[i % 5] for i in range(66))):
+        planes = [int(x) for x in ask(["P %d %d" % s for s in shapes])]
+        assert planes == [(w * h + 255) // 256 * 256 for w, h in shapes]
+        blocks = [(w // 8) * (h // 8) for w, h in shapes]
+        strips = [((w // 8 + 31) // 32) * (h // 8) for w, h in shapes]
+        for hook in (0, 3):
+            cases.append((hook, blocks, strips, [3 * p for p in planes]))
+    M = (1 << 30) // 64
+    cases.append((0, [M // 2, M // 2, 1, M, 1, M + 5, 1, 1, 1], [70, 70, 1, 1, 1, 1, 9, 9, 1], [100, 100, 1, 1, 1, 1, 50, 50, 200]))
+    cases.append((1, [4, 4, 4], [1, 1, 1], [256, 256, 256]))  # every chunk one image: nothing to grow
+    got = ask(["N %d %d " % (hook, len(b)) + " ".join("%d %d %d" % t for t in zip(b, s, f)) for hook, b, s, f in cases])
+    for line, (hook, b, s, f) in zip(got, cases):
+        assert tuple(int(x) for x in line.split()) == needs(b, s, f, hook), (hook, b, s, f, line)
+    assert got[0].split()[0] == "7" and got[1].split()[0] == "3" and got[2].split()[0] == "66" and got[3].split()[0] == "3"
+    assert [int(x) for x in got[4].split()] == [3, M, 140, 300] and got[5].split() == ["0"] * 4
