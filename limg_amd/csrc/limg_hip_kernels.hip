@@ -82,12 +82,20 @@ namespace limg_hip
         waveCalls += words << 8;
       }
 
-      const size_t bi = (size_t)g.byS * p.blocksX + bx;
       const uint32_t word = shift[0] | (shift[1] << 8) | (shift[2] << 16) | (calls << 24);
       if (g.lane == 0)
       {
-        if (!PERSIST || p.compactOut) p.shifts[bi] = word;
-        if (PERSIST) reinterpret_cast<uint32_t *>(park + kParkShift)[sb] = word;
+        if (!PERSIST) p.shifts[(size_t)g.byS * p.blocksX + bx] = word;
+        else
+        {
+          if (p.compactOut)
+          { // (the row's first index is worked out here, where it is stored to: hoisted out of the block loop its two words would sit in VGPR lanes across the search)
+            uint32_t byS = g.byS;
+            asm volatile("" : "+s"(byS));
+            p.shifts[(size_t)byS * p.blocksX + bx] = word;
+          }
+          reinterpret_cast<uint32_t *>(park + kParkShift)[sb] = word;
+        }
       }
       if (p.storePlanes && active) { stage[o] = (uint8_t)fA; stage[kFacPlane + o] = (uint8_t)fB; stage[2 * kFacPlane + o] = (uint8_t)fC; }
     }
@@ -125,6 +133,16 @@ namespace limg_hip
       if (PERSIST)
         for (int i = g.tid; i < 384; i += kThreads) reinterpret_cast<uint4 *>(park + kParkFac)[i] = *reinterpret_cast<const uint4 *>(stage + (i >> 4) * kFacRow + (i & 15) * 16); // 24 rows of 256 bytes
       else if (p.storePlanes) copy_factor_planes<true>(p, io, stage, g.x0, g.y0, g.stripW, g.ry, g.tid);
+    }
+
+    // the parameter block behind a pointer the compiler cannot follow (persistent kernels: p lies in the kernel-argument segment or a device table): what is read
+    // through the result is fetched again, with scalar loads, instead of being kept from an earlier read
+    template <class P>
+    __device__ __forceinline__ const P &reread_params(const P &p)
+    {
+      const P *q = &p;
+      asm volatile("" : "+s"(q));
+      return *q;
     }
 
     // PREFIT: the float stage already ran in k_fit_tpb (limg_hip_fit_tpb.hip, one lane per block); this step loads the records and goes on with phase E.
@@ -403,6 +421,13 @@ namespace limg_hip
       __syncthreads(); // all waves are done with V: wave 0's V region becomes the factor-byte staging area
 
       uint8_t *stage = reinterpret_cast<uint8_t *>(g.V); // [3 planes][8 rows][256 px]
+      if (PERSIST)
+      { // from here on the park slot is known by ONE address, the one the block loop stores its shift words to: the strip's epilogue goes back from it, instead of
+        // the slot's base and the offsets it was made of staying live across the search
+        park += kParkShift;
+        asm volatile("" : "+s"(park));
+        park -= kParkShift;
+      }
       uint32_t waveCalls = 0;
       // (No zeroing of the parked shift words of blocks past the right edge here: with the dynamic queue below another wave may already have parked a real
       //  word for a block of this wave's range by the time this wave gets to issue such a store -- a rare lost update, found in round 2.  The F step masks
@@ -420,8 +445,10 @@ namespace limg_hip
         if (sb >= (uint32_t)kStripBlocks) break;
         uint32_t qv = 0;
         if (lane == 0) qv = atomicAdd(s_queue, 1u); // the next block's index arrives while this one is searched
-        uint32_t rx, n, lx, ly;
-        if (!block_geom(p, g, sb, rx, n)) { sbNext = (uint32_t)sgpr((int)qv); continue; }
+        // (the persistent kernels run images of whole blocks only -- encode_plan: fused => !ragged --: a block that exists there has its 64 pixels, and the search's
+        //  form for blocks with masked lanes is not instantiated)
+        uint32_t rx = kBlock, n = kBlock * kBlock, lx, ly;
+        if (PERSIST ? g.strip * kStripBlocks + sb >= p.blocksX : !block_geom(p, g, sb, rx, n)) { sbNext = (uint32_t)sgpr((int)qv); continue; }
         const BlkF *const blkE = g.blk + sb;
         const bool active = (uint32_t)lane < n;
         const uint32_t px = block_pixel(g, sb, rx, n, lx, ly);
@@ -432,12 +459,11 @@ namespace limg_hip
         if (p.forced[0] >= 0) { shift[0] = (uint32_t)p.forced[0]; shift[1] = (uint32_t)p.forced[1]; shift[2] = (uint32_t)p.forced[2]; }
         else if (lim.crushBits)
         {
-          const uint64_t maxBlockN = lim.maxBlock * (uint64_t)n;
           // be * 16 < maxBlock * n  <=>  be < ceil(maxBlock * n / 16); clamped to 32 bits (be itself never gets near 2^32).  Full blocks: from the host.
           uint32_t blockLimit = lim.blockLimitFull;
           if (n != 64)
           {
-            const uint64_t lim64 = (maxBlockN + 15ull) >> 4;
+            const uint64_t lim64 = (lim.maxBlock * (uint64_t)n + 15ull) >> 4;
             blockLimit = (uint32_t)sgpr((int)(lim64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim64));
           }
           const bool big = ((uint32_t)sgpr((int)blkE->flags) & kBig) != 0;
@@ -489,6 +515,8 @@ namespace limg_hip
           {
             // out-of-range record (never produced by a fit of byte pixels; kept so that no input can break exactness):
             // generic 32-bit trial, deliberately a real call so that none of it is speculated into the common path
+            // (persistent kernels: the block limit is fetched here, where this rare path needs it, not held across every block's search)
+            const uint64_t maxBlockN = (PERSIST ? reread_params(lim).maxBlock : lim.maxBlock) * (uint64_t)n;
             const uint32_t packed = (uint32_t)sgpr((int)search_generic(px, fA, fB, fC, blkE->rec, active, lim.maxPixel32, maxBlockN, !ACC)); // uniform: keeps the shift triple (and the bookkeeping below) on the scalar unit for the common path too
             shift[0] = packed & 0xFF; shift[1] = (packed >> 8) & 0xFF; shift[2] = (packed >> 16) & 0xFF;
           }
@@ -499,6 +527,17 @@ namespace limg_hip
       }
       if (lane == 0) g.calls[g.wave] = waveCalls;
       __syncthreads();
+      if (PERSIST)
+      { // The strip's epilogue starts over from the parameter block, the thread id and the strip's block row: what the set-up above worked out of them (fields of
+        // p, lane masks, addresses) would otherwise stay live across the block loop, where the search leaves no scalar register free, and be parked in VGPR lanes.
+        const P &ps = reread_params(p);
+        EStrip ge = g;
+        asm volatile("" : "+v"(ge.tid));
+        asm volatile("" : "+s"(ge.by));
+        if (ge.tid == 0) publish_strip<true>(ps, ge, id, head0);
+        park_or_store_factors<true>(ps, io, ge, park, stage);
+        return;
+      }
       if (tid == 0) publish_strip<PERSIST>(p, g, id, head0);
       park_or_store_factors<PERSIST>(p, io, g, park, stage);
     }
@@ -675,7 +714,7 @@ namespace limg_hip
       auto io_of = [](KernArgs *a, uint32_t img) -> KernIO * { return a->batchCount > 1 ? (KernIO *)a->batch + img : &a->io; };
 #define LIMG_LOOP_LIMITS(a, img) (*(a)) /* one error factor: the limits are kernel arguments */
 // (a list of one shape: the image of a strip by a division, its strips and block rows image after image, the kernel arguments as every image's view)
-#define LIMG_LOOP_STRIPS (p.imageStrips * p.batchCount)
+#define LIMG_LOOP_STRIPS(a) ((a)->imageStrips * (a)->batchCount)
 #define LIMG_LOOP_FIND_IMAGE(a, t, img) if ((a)->batchCount > 1) img = (t) / (a)->imageStrips;
 #define LIMG_LOOP_HEAD0(a, img) ((img) * (a)->imageStrips)
 #define LIMG_LOOP_ROWBASE(a, img) ((img) * (a)->blocksY)
@@ -746,7 +785,7 @@ namespace limg_hip
       typedef const __attribute__((address_space(4))) RatedImage KernLimits;
       typedef const __attribute__((address_space(4))) uint32_t KernWord;
       auto io_of = [](KernArgs *a, uint32_t img) -> KernIO * { return (KernIO *)(uintptr_t)a->batch + img; };
-#define LIMG_LOOP_STRIPS (p.nStrips)
+#define LIMG_LOOP_STRIPS(a) ((a)->nStrips)
 #define LIMG_LOOP_FIND_IMAGE(a, t, img) img = find_strip_image((a)->firstStrip, (a)->nImages, (t));
 #define LIMG_LOOP_HEAD0(a, img) (((KernWord *)(uintptr_t)(a)->firstStrip)[img])
 #define LIMG_LOOP_ROWBASE(a, img) 0u

@@ -3,16 +3,16 @@
 // schedule than the one they were measured with; included, their code is instruction for instruction what it was when the loop stood in the kernel.
 // From the enclosing scope: CH, FAST, PREFIT, ACC, NOSEL; p (the kernel's parameter block); KernArgs (its type in the constant address space); s_lds, s_ticket;
 // io_of(a, img): the caller's pointers of image `img` of the launch; LIMG_LOOP_LIMITS(a, img): where the E step's search takes its limits from;
-// LIMG_LOOP_STRIPS: the strips of the launch (from p); LIMG_LOOP_FIND_IMAGE(a, t, img): the statement that sets img to the image of strip t (img is 0 before it);
+// LIMG_LOOP_STRIPS(a): the strips of the launch; LIMG_LOOP_FIND_IMAGE(a, t, img): the statement that sets img to the image of strip t (img is 0 before it);
 // LIMG_LOOP_HEAD0(a, img), LIMG_LOOP_ROWBASE(a, img): that image's first strip id and its first block row in the per-block scratch; LIMG_LOOP_VIEW(a, img): the
 // parameter block the stages read for a strip of that image -- the kernel arguments themselves, or the image's own view (k_encode_list_mixed).
       const int tid = (int)threadIdx.x;
-      const uint32_t S = LIMG_LOOP_STRIPS; // the strips of all images of a batch, image after image
-      uint8_t *park = p.park + (size_t)blockIdx.x * 2 * kParkBytes;
       uint32_t prev = 0xFFFFFFFFu, prevImg = 0, slot = 0;
       // The two steps read the parameters straight from the kernel-argument segment, through a pointer the compiler cannot see through from one step to the
       // next: a field is then fetched (one scalar load, scalar-cache hit) where a step uses it.  Read from `p`, all ~70 dwords are loaded once before the
       // loop and kept alive across it -- more SGPRs than there are, so the compiler parks them in VGPR lanes and pays a quarter-rate v_readlane per use.
+      // The same holds for what the loop itself needs of them -- the ticket, the number of strips, the workgroup's park slots: each is fetched where it is used,
+      // and the only words carried from one iteration to the next are prev, prevImg and slot.
       KernArgs *const kargs = (KernArgs *)__builtin_amdgcn_kernarg_segment_ptr();
       // All workgroups start their first E step together, so their first F steps (latency-bound, little vector work) coincide too, and it takes a few iterations
       // of data-dependent search lengths before the E and F steps of a CU's six workgroups interleave.  Workgroups are dealt out to the 256 CUs residency slot
@@ -22,23 +22,27 @@
       for (;;)
       {
         __syncthreads(); // the previous step's LDS use is over (and the rsqrt table is in place)
-        // EVERY strip id is drawn from the ticket, the first one included: a workgroup that holds id t is resident, and so is the holder of every id < t (it drew
-        // earlier).  Round 4 let workgroup i take strip i without asking (one atomic round trip less per workgroup): with a second persistent kernel on the GPU
-        // (another context's stream) a resident workgroup then waited for strips of workgroups that were never dispatched, and both kernels spun into the
-        // look-back's bound (VERDICT r04).  Never derive a strip id from blockIdx.
-        if (tid == 0) s_ticket = atomicAdd(p.ticket, 1u);
-        __syncthreads();
-        const uint32_t t = (uint32_t)sgpr((int)s_ticket);
         int tid_e = tid;
         asm volatile("" : "+v"(tid_e));
         KernArgs *pe = kargs;
         asm volatile("" : "+s"(pe));
+        // EVERY strip id is drawn from the ticket, the first one included: a workgroup that holds id t is resident, and so is the holder of every id < t (it drew
+        // earlier).  Round 4 let workgroup i take strip i without asking (one atomic round trip less per workgroup): with a second persistent kernel on the GPU
+        // (another context's stream) a resident workgroup then waited for strips of workgroups that were never dispatched, and both kernels spun into the
+        // look-back's bound (VERDICT r04).  Never derive a strip id from blockIdx.
+        if (tid_e == 0) s_ticket = atomicAdd(pe->ticket, 1u);
+        __syncthreads();
+        const uint32_t t = (uint32_t)sgpr((int)s_ticket);
+        // (t < S as one scalar word, compared in the statement itself: as a boolean it is carried across both steps as two lane masks)
+        uint32_t more;
+        asm volatile("s_cmp_lt_u32 %1, %2\n\ts_cselect_b32 %0, 1, 0" : "=s"(more) : "s"(t), "s"(LIMG_LOOP_STRIPS(pe)) : "scc");
         uint32_t img = 0;
-        if (t < S)
+        if (more)
         {
           LIMG_LOOP_FIND_IMAGE(pe, t, img) // once per strip, on the scalar unit
           const uint32_t head0 = LIMG_LOOP_HEAD0(pe, img);
-          fit_search_strip<CH, true, FAST, PREFIT, ACC, NOSEL>(*LIMG_LOOP_VIEW(pe, img), LIMG_LOOP_LIMITS(pe, img), *io_of(pe, img), t, t - head0, LIMG_LOOP_ROWBASE(pe, img), head0, s_lds, park + slot * kParkBytes, tid_e);
+          uint8_t *park = pe->park + (blockIdx.x * 2u + slot) * (uint32_t)kParkBytes; // (a 32-bit offset: the grid is a few workgroups per CU)
+          fit_search_strip<CH, true, FAST, PREFIT, ACC, NOSEL>(*LIMG_LOOP_VIEW(pe, img), LIMG_LOOP_LIMITS(pe, img), *io_of(pe, img), t, t - head0, LIMG_LOOP_ROWBASE(pe, img), head0, s_lds, park, tid_e);
         }
         if (prev != 0xFFFFFFFFu)
         {
@@ -51,11 +55,13 @@
           // F-step waves take the slots they leave.  Measured: -2.5 % on the kernel (the other way round: +0.8 %).
           __builtin_amdgcn_s_setprio(0);
           const uint32_t head0 = LIMG_LOOP_HEAD0(pf, prevImg);
+          const uint8_t *park = pf->park + (blockIdx.x * 2u + (slot ^ 1u)) * (uint32_t)kParkBytes;
           // (the view of the previous strip's image is fetched again here, by prevImg: nothing of it is carried across the E step)
-          dither_store_strip<CH, true>(*LIMG_LOOP_VIEW(pf, prevImg), *io_of(pf, prevImg), prev, prev - head0, LIMG_LOOP_ROWBASE(pf, prevImg), head0, s_lds + kLdsStrip, park + (slot ^ 1u) * kParkBytes, tid_f);
+          dither_store_strip<CH, true>(*LIMG_LOOP_VIEW(pf, prevImg), *io_of(pf, prevImg), prev, prev - head0, LIMG_LOOP_ROWBASE(pf, prevImg), head0, s_lds + kLdsStrip, park, tid_f);
           __builtin_amdgcn_s_setprio(kPrioE);
         }
-        if (t >= S) break;
+        asm volatile("" : "+s"(more)); // (tested again as a word: the test above is not kept as a lane mask)
+        if (!more) break;
         prev = t; prevImg = img;
         slot ^= 1u;
       }

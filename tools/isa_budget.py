@@ -75,12 +75,14 @@ def assemble(src):
     return out
 
 
-def kernel_instructions(asm, kernel_substr, labels=None, operands=None):
+def kernel_instructions(asm, kernel_substr, labels=None, operands=None, depths=None):
     """[(opcode, [(file, line) frames innermost first])] of one kernel; `labels` (a dict) receives label -> index of the first instruction behind it, `operands`
-    (a list) the operand text of every instruction"""
+    (a list) the operand text of every instruction, `depths` (a list) the loop depth of its basic block as the assembly's block comments give it (`Depth=N`; 0
+    outside every loop)"""
     on = False
     frames = []
     out = []
+    depth = 0
     for line in open(asm):
         if re.match(r"^_Z.*:", line):
             on = kernel_substr in line
@@ -93,8 +95,11 @@ def kernel_instructions(asm, kernel_substr, labels=None, operands=None):
         if re.match(r"\s*\.loc\s", line):
             frames = [(os.path.basename(f), int(l)) for f, l in re.findall(r"([A-Za-z_0-9./]+\.(?:hip|h|inc)):(\d+):\d+", line)]
             continue
-        if labels is not None and re.match(r"^\.LBB\w+:", line):
-            labels[line.split(":")[0]] = len(out)
+        if re.match(r"^(\.LBB\w+:|; %bb\.\d+:)", line):  # a basic block begins: its loop depth is in the comment, or it is in no loop
+            d = re.search(r"Depth=(\d+)", line)
+            depth = int(d.group(1)) if d else 0
+            if labels is not None and line.startswith(".LBB"):
+                labels[line.split(":")[0]] = len(out)
             continue
         m = re.match(r"\s+([a-z_0-9]+)(\s|$)", line)
         if not m or line.strip().startswith((".", ";")):
@@ -102,14 +107,16 @@ def kernel_instructions(asm, kernel_substr, labels=None, operands=None):
         out.append((m.group(1), frames))
         if operands is not None:
             operands.append(line.split(";")[0].strip()[len(m.group(1)):].strip())
+        if depths is not None:
+            depths.append(depth)
     return out
 
 
-def one_trial_form(instrs, labels, operands):
+def one_trial_form(instrs, labels, operands, depths):
     """k_encode_persistent holds its loop twice, once per form of the trial (with and without the red-weight select: red_select_dead, limg_hip_encode_rules.h), and
     picks one with the first scalar branch of the kernel, on the pixel limit against 0x7fff.  The two copies are contiguous in the assembly and the branch's target
     label is where the second begins: -> (the instructions of the copy WITHOUT the select -- the headline's, with the few instructions in front of the branch --, the
-    other copy's count).  The copy without the select is told by its trials: v_dot2_u32_u16 with no v_cndmask_b32_sdwa."""
+    other copy's count, the kept instructions' loop depths).  The copy without the select is told by its trials: v_dot2_u32_u16 with no v_cndmask_b32_sdwa."""
     at = next(i for i, (op, _) in enumerate(instrs) if op.startswith("s_cmp") and operands[i].endswith("0x7fff"))
     br = next(i for i in range(at, at + 8) if instrs[i][0].startswith("s_cbranch_scc"))
     cut = labels[operands[br].split()[-1]]
@@ -119,7 +126,7 @@ def one_trial_form(instrs, labels, operands):
     dots = [sum(op == "v_dot2_u32_u16" for op, _ in part) for part in parts]
     assert dots[0] == dots[1] and min(sel) * 4 < max(sel), (dots, sel)
     keep = 0 if sel[0] < sel[1] else 1
-    return parts[keep], len(parts[1 - keep]) - (br + 1)
+    return parts[keep], len(parts[1 - keep]) - (br + 1), depths[:cut] if keep == 0 else depths[:br + 1] + depths[cut:]
 
 
 def kind(op):
@@ -134,11 +141,22 @@ def kind(op):
     return "other"
 
 
-def budget(instrs, phases, default):
+# the quarter- and half-rate bookkeeping of the per-strip path (profiles/strip_scalars.md): SGPRs parked in VGPR lanes (and the source's own lane reads: sgpr(),
+# wave sums), and the 64-bit vector add every `v[a:b], off` address costs
+LANE_OPS = {"v_readlane_b32": "lane_r", "v_writelane_b32": "lane_w", "v_lshl_add_u64": "add64"}
+
+
+def by_depth(counter, key):
+    """'3@1 2@2': how many of `key` a phase holds at each loop depth (depth 0: outside the persistent loop; 1: once per strip and wave; 2: per block, or a copy loop)"""
+    return " ".join("%d@%d" % (n, d) for (k, d), n in sorted(counter.items()) if k == key) or "-"
+
+
+def budget(instrs, phases, default, depths=None, lanes=None):
+    """`lanes` (a dict, with `depths`) receives phase -> Counter of (LANE_OPS class, loop depth)"""
     acc = collections.OrderedDict((name, collections.Counter()) for name, _ in phases)
     acc[default] = collections.Counter()
     ops = collections.defaultdict(collections.Counter)
-    for op, frames in instrs:
+    for i, (op, frames) in enumerate(instrs):
         hit = default
         for f, l in frames:
             for name, ranges in phases:
@@ -149,6 +167,8 @@ def budget(instrs, phases, default):
                 break
         acc[hit][kind(op)] += 1
         ops[hit][op] += 1
+        if lanes is not None and op in LANE_OPS:
+            lanes.setdefault(hit, collections.Counter())[(LANE_OPS[op], depths[i])] += 1
     return acc, ops
 
 
@@ -199,12 +219,14 @@ def main():
         ("F: strip load (park -> LDS), rest of dither_store_strip", [fn("dither_store_strip")]),
         ("persistent loop (ticket, barriers)", [fn("k_encode_persistent"), ("limg_hip_persistent_loop.inc", 1, 1 << 30)]),  # (the loop's text: included into the kernel)
     ]
-    labels, operands = {}, []
-    instrs = kernel_instructions(asm, "k_encode_persistentILi4ELb0ELb1ELb0E", labels, operands)
-    instrs, other_copy = one_trial_form(instrs, labels, operands)
+    labels, operands, depths = {}, [], []
+    instrs = kernel_instructions(asm, "k_encode_persistentILi4ELb0ELb1ELb0E", labels, operands, depths)
+    instrs, other_copy, depths = one_trial_form(instrs, labels, operands, depths)
+    assert len(depths) == len(instrs)
     print("The kernel holds its loop once per form of the trial; the table below is the copy the headline's pixel limit takes, without the red-weight select (%d instructions; the"
           " other copy: %d).\n" % (len(instrs), other_copy))
-    acc, ops = budget(instrs, phases, "unattributed")
+    lanes = {}
+    acc, ops = budget(instrs, phases, "unattributed", depths, lanes)
     copies_trial = max(1, ops["search: trial core (a9)"]["v_dot2_u32_u16"])
     copies_rows = max(1, ops["F: dither + crushed bytes + decode terms (rows_factor)"]["v_add_u32_sdwa"] // 8)
     copies_sum = max(1, ops["search: block-error sum (wave_sum)"]["v_add_u32_dpp"] // 6)  # six butterfly stages per copy (the search's verdict form has no v_readlane_b32)
@@ -236,8 +258,10 @@ def main():
         "unattributed": (1, 1.0 / 8, "compiler-generated (address arithmetic, spills): per wave and strip assumed"),
     }
     print("## k_encode_persistent<4, false, true, false>\n")
-    print("| phase | static VALU / SALU / LDS / VMEM | copies | one execution: VALU / SALU / LDS | executions per block | per block: VALU / SALU / LDS |")
-    print("|---|---|---|---|---|---|")
+    print("The last three columns count, statically and by the loop depth of their basic block (`n@depth`; depth 0 is outside the persistent loop, 1 runs once per strip and wave,")
+    print("2 and deeper per block or per pass of a copy loop), the lane reads and writes -- spilled SGPRs and the source's own `sgpr()` / wave-sum reads -- and the 64-bit vector adds.\n")
+    print("| phase | static VALU / SALU / LDS / VMEM | copies | one execution: VALU / SALU / LDS | executions per block | per block: VALU / SALU / LDS | v_readlane_b32 | v_writelane_b32 | v_lshl_add_u64 |")
+    print("|---|---|---|---|---|---|---|---|---|")
     tot = collections.Counter()
     for name, c in acc.items():
         copies, per_block, note = how[name]
@@ -245,9 +269,13 @@ def main():
         pb = {k: one[k] * per_block for k in one}
         for k in pb:
             tot[k] += pb[k]
-        print("| %s | %d / %d / %d / %d | %d | %.1f / %.1f / %.1f | %.3g (%s) | %.1f / %.1f / %.1f |" % (name, c["valu"], c["salu"], c["lds"], c["vmem"], copies, one["valu"], one["salu"], one["lds"],
-                                                                                              per_block, note, pb["valu"], pb["salu"], pb["lds"]))
-    print("| **sum** | | | | | **%.0f / %.0f / %.0f** |" % (tot["valu"], tot["salu"], tot["lds"]))
+        ln = lanes.get(name, collections.Counter())
+        print("| %s | %d / %d / %d / %d | %d | %.1f / %.1f / %.1f | %.3g (%s) | %.1f / %.1f / %.1f | %s | %s | %s |" % (name, c["valu"], c["salu"], c["lds"], c["vmem"], copies, one["valu"], one["salu"], one["lds"],
+              per_block, note, pb["valu"], pb["salu"], pb["lds"], by_depth(ln, "lane_r"), by_depth(ln, "lane_w"), by_depth(ln, "add64")))
+    allp = collections.Counter()
+    for ln in lanes.values():
+        allp.update(ln)
+    print("| **sum** | | | | | **%.0f / %.0f / %.0f** | %s | %s | %s |" % (tot["valu"], tot["salu"], tot["lds"], by_depth(allp, "lane_r"), by_depth(allp, "lane_w"), by_depth(allp, "add64")))
     # ---- reconciliation with MEASURED aggregates (tools/isa_calibrate.py: errorFactor sweep + search bypassed) ----
     print("\nThe static columns count every instruction of a phase's code, whichever way its branches go.  For straight-line vector code that is what executes; for scalar code it")
     print("is an UPPER BOUND -- guards (`if (e[0] & 0x20) rebuild_A`), both tails of the trial, both copies of the search loop, the generic-path and alpha branches of the F step")

@@ -10,6 +10,7 @@
 // v_mfma_f32_4x4x1_16b_f32 with B == 1.0 give bit for bit the serial sum ((acc + a0) + a1) + ..., in k order, denormals included.
 //
 // build: hipcc --offload-arch=gfx950 -O2 tools/valu_ceiling.hip -o gpurun_out/valu_ceiling   (run on the GPU box; prints JSON lines)
+// usage: valu_ceiling [iterations [text ...]]: with texts, only the rows whose name contains one of them
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -22,10 +23,11 @@
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(2); } } while (0)
 
 enum Op : int { OP_ADD_U32, OP_FMA_F32, OP_ADD_F32, OP_MUL_F32, OP_MAD_I24, OP_PK_ADD_U16, OP_PK_MUL_U16, OP_PK_FMA_F32, OP_PK_ADD_F32, OP_DOT2_U16, OP_PERM, OP_MED3, OP_ADD3,
-                OP_MUL_LO_U32, OP_CVT_UBYTE, OP_ADD_DPP, OP_MOV_DPP, OP_MIN_F32, OP_LSHL_OR, OP_BFE, OP_CNDMASK, OP_RCP_F32, OP_PERMLANE32_SWAP, OP_CNDMASK_SGPR, OP_ADD_F32_DEP, OP_MAD_I24_DEP, OP_PK_ADD_DEP, OP_MIX_TRIAL, OP_SUB_F32, OP_MAX_F32, OP_FMAC_F32, OP_AND, OP_OR, OP_XOR, OP_LSHL, OP_LSHR, OP_ASHR, OP_SUB_U32, OP_MIN_U32, OP_MUL_U24, OP_MUL_I24, OP_MOV, OP_CVT_F32_I32, OP_CVT_I32_F32, OP_RNDNE, OP_PK_MUL_F32, OP_CMP_CNDMASK, OP_ADD_U32_SGPR, OP_MAD_I24_SGPR, OP_RSQ_F32, OP_READLANE, OP_MFMA_16x16x4, OP_MFMA_4x4x1, OP_COUNT };
+                OP_MUL_LO_U32, OP_CVT_UBYTE, OP_ADD_DPP, OP_MOV_DPP, OP_MIN_F32, OP_LSHL_OR, OP_BFE, OP_CNDMASK, OP_RCP_F32, OP_PERMLANE32_SWAP, OP_CNDMASK_SGPR, OP_ADD_F32_DEP, OP_MAD_I24_DEP, OP_PK_ADD_DEP, OP_MIX_TRIAL, OP_SUB_F32, OP_MAX_F32, OP_FMAC_F32, OP_AND, OP_OR, OP_XOR, OP_LSHL, OP_LSHR, OP_ASHR, OP_SUB_U32, OP_MIN_U32, OP_MUL_U24, OP_MUL_I24, OP_MOV, OP_CVT_F32_I32, OP_CVT_I32_F32, OP_RNDNE, OP_PK_MUL_F32, OP_CMP_CNDMASK, OP_ADD_U32_SGPR, OP_MAD_I24_SGPR, OP_RSQ_F32, OP_READLANE, OP_MFMA_16x16x4, OP_MFMA_4x4x1, OP_LSHL_ADD_U64, OP_LSHL_ADD_U64_SBASE, OP_READFIRSTLANE, OP_STORE_X4_VADDR64, OP_STORE_X4_SBASE, OP_COUNT };
 static const char *kOpName[OP_COUNT] = { "v_add_u32", "v_fma_f32", "v_add_f32", "v_mul_f32", "v_mad_i32_i24", "v_pk_add_u16", "v_pk_mul_lo_u16", "v_pk_fma_f32", "v_pk_add_f32", "v_dot2_u32_u16",
                                          "v_perm_b32", "v_med3_i32", "v_add3_u32", "v_mul_lo_u32", "v_cvt_f32_ubyte0", "v_add_f32_dpp(row_shr:1)", "v_mov_b32_dpp(quad_perm)", "v_min_f32", "v_lshl_or_b32",
-                                         "v_bfe_u32", "v_cndmask_b32", "v_rcp_f32", "v_permlane32_swap", "v_cndmask_b32(sgpr mask)", "v_add_f32 dependent chain", "v_mad_i32_i24 dependent chain", "v_pk_add_u16 dependent chain", "trial-like mix (mad24,perm,pk_add,add_u32)", "v_sub_f32", "v_max_f32", "v_fmac_f32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_lshlrev_b32", "v_lshrrev_b32", "v_ashrrev_i32", "v_sub_u32", "v_min_u32", "v_mul_u32_u24", "v_mul_i32_i24", "v_mov_b32", "v_cvt_f32_i32", "v_cvt_i32_f32", "v_rndne_f32", "v_pk_mul_f32", "v_cmp_lt_u32+v_cndmask_b32(vcc) pair (per instruction)", "v_add_u32(sgpr operand)", "v_mad_i32_i24(sgpr operand)", "v_rsq_f32", "v_readlane_b32+v_writelane_b32 pair (per instruction)", "v_mfma_f32_16x16x4_f32", "v_mfma_f32_4x4x1_16b_f32" };
+                                         "v_bfe_u32", "v_cndmask_b32", "v_rcp_f32", "v_permlane32_swap", "v_cndmask_b32(sgpr mask)", "v_add_f32 dependent chain", "v_mad_i32_i24 dependent chain", "v_pk_add_u16 dependent chain", "trial-like mix (mad24,perm,pk_add,add_u32)", "v_sub_f32", "v_max_f32", "v_fmac_f32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_lshlrev_b32", "v_lshrrev_b32", "v_ashrrev_i32", "v_sub_u32", "v_min_u32", "v_mul_u32_u24", "v_mul_i32_i24", "v_mov_b32", "v_cvt_f32_i32", "v_cvt_i32_f32", "v_rndne_f32", "v_pk_mul_f32", "v_cmp_lt_u32+v_cndmask_b32(vcc) pair (per instruction)", "v_add_u32(sgpr operand)", "v_mad_i32_i24(sgpr operand)", "v_rsq_f32", "v_readlane_b32+v_writelane_b32 pair (per instruction)", "v_mfma_f32_16x16x4_f32", "v_mfma_f32_4x4x1_16b_f32", "v_lshl_add_u64", "v_lshl_add_u64(sgpr base)", "v_readfirstlane_b32",
+                                         "global_store_dwordx4 v[addr:addr+1], off", "global_store_dwordx4 v_offset, s[base:base+1]" };
 
 typedef float float2_t __attribute__((ext_vector_type(2)));
 typedef float float4_t __attribute__((ext_vector_type(4)));
@@ -46,6 +48,15 @@ __global__ __launch_bounds__(256) void k_stream(uint32_t *out, unsigned long lon
   const unsigned long long mask = 0x5555AAAA3333CCCCull ^ seed;
   float fb = 1.0000001f, fc = 1e-9f;
   float2_t pb = { 1.0000001f, 0.9999999f }, pc = { 1e-9f, 1e-9f };
+  // 64-bit operands of the address-arithmetic rows, and the two address forms of a 16-byte store: every lane stores to its own 16 bytes of `out` (the host
+  // allocates 16 bytes per thread), over and over -- the lines stay in the L2
+  unsigned long long q[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) q[i] = (unsigned long long)seed * (i + 1) + threadIdx.x;
+  const unsigned long long qb = ((unsigned long long)seed << 20) | threadIdx.x;
+  const unsigned long long sinkBase = (unsigned long long)(uintptr_t)out;
+  const uint32_t sinkOff = (blockIdx.x * blockDim.x + threadIdx.x) * 16u;
+  const unsigned long long sinkAddr = sinkBase + sinkOff;
   __syncthreads();
   const unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
   const unsigned long long t0 = __builtin_amdgcn_s_memtime();
@@ -104,7 +115,12 @@ __global__ __launch_bounds__(256) void k_stream(uint32_t *out, unsigned long lon
     else if (OP == OP_RSQ_F32) asm volatile("v_rsq_f32 %0, %0" : "+v"(a[i])); \
     else if (OP == OP_READLANE) { uint32_t t_; asm volatile("v_readlane_b32 %0, %1, 3\n\tv_writelane_b32 %1, %0, 5" : "=&s"(t_), "+v"(a[i])); } \
     else if (OP == OP_MFMA_16x16x4) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(m[i & 3]) : "v"(fb), "v"(fc));    \
-    else if (OP == OP_MFMA_4x4x1) asm volatile("v_mfma_f32_4x4x1_16b_f32 %0, %1, %2, %0" : "+v"(m[i & 3]) : "v"(fb), "v"(fc));
+    else if (OP == OP_MFMA_4x4x1) asm volatile("v_mfma_f32_4x4x1_16b_f32 %0, %1, %2, %0" : "+v"(m[i & 3]) : "v"(fb), "v"(fc));    \
+    else if (OP == OP_LSHL_ADD_U64) asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(q[i]) : "v"(qb));                           \
+    else if (OP == OP_LSHL_ADD_U64_SBASE) asm volatile("v_lshl_add_u64 %0, %1, 0, %0" : "+v"(q[i]) : "s"(sinkBase));               \
+    else if (OP == OP_READFIRSTLANE) { uint32_t t_; asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(t_) : "v"(a[i])); }           \
+    else if (OP == OP_STORE_X4_VADDR64) asm volatile("global_store_dwordx4 %0, %1, off" : : "v"(sinkAddr), "v"(m[i & 3]) : "memory"); \
+    else if (OP == OP_STORE_X4_SBASE) asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"(sinkOff), "v"(m[i & 3]), "s"(sinkBase) : "memory");
     REP16(X) REP16(X) REP16(X) REP16(X)
 #undef X
   }
@@ -112,7 +128,7 @@ __global__ __launch_bounds__(256) void k_stream(uint32_t *out, unsigned long lon
   const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
   uint32_t r = 0;
 #pragma unroll
-  for (int i = 0; i < 16; i++) r ^= a[i] ^ __float_as_uint(p[i].x) ^ __float_as_uint(p[i].y);
+  for (int i = 0; i < 16; i++) r ^= a[i] ^ __float_as_uint(p[i].x) ^ __float_as_uint(p[i].y) ^ (uint32_t)q[i] ^ (uint32_t)(q[i] >> 32);
 #pragma unroll
   for (int i = 0; i < 4; i++) r ^= __float_as_uint(m[i].x) ^ __float_as_uint(m[i].y) ^ __float_as_uint(m[i].z) ^ __float_as_uint(m[i].w);
   out[blockIdx.x * blockDim.x + threadIdx.x] = r;
@@ -221,13 +237,15 @@ static int check_mfma(bool wide, int steps, int kind, int *orderOut)
 int main(int argc, char **argv)
 {
   int iters = argc > 1 ? atoi(argv[1]) : 5000;
+  const bool only = argc > 2; // rows whose name contains one of argv[2..], and no MFMA numerics check
+  auto wanted = [&](const char *name) { for (int i = 2; i < argc; i++) if (strstr(name, argv[i])) return true; return !only; };
   hipDeviceProp_t prop;
   CK(hipGetDeviceProperties(&prop, 0));
   const int cus = prop.multiProcessorCount;
   printf("{\"device\": \"%s\", \"cus\": %d, \"clock_khz\": %d}\n", prop.name, cus, prop.clockRate);
 
   // ---- numerics of the f32 matrix instructions as ordered sums ----
-  for (int wide = 1; wide >= 0; wide--)
+  for (int wide = 1; wide >= 0 && !only; wide--)
     for (int kind = 0; kind < 5; kind++)
     {
       int order = 0, bad = 0;
@@ -240,7 +258,8 @@ int main(int argc, char **argv)
   fill(tab, std::make_integer_sequence<int, OP_COUNT>{});
   uint32_t *out; unsigned long long *cyc;
   const int maxBlocks = cus * 8;
-  CK(hipMalloc(&out, (size_t)maxBlocks * 256 * 4)); CK(hipMalloc(&cyc, (size_t)maxBlocks * 4 * 32));
+  CK(hipMalloc(&out, (size_t)maxBlocks * 256 * 16)); // 16 bytes per thread: the store rows' target
+  CK(hipMalloc(&cyc, (size_t)maxBlocks * 4 * 32));
   std::vector<unsigned long long> hc((size_t)maxBlocks * 16);
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   const int wavesPerSimd[] = { 1, 2, 4, 5, 8 };
@@ -248,7 +267,8 @@ int main(int argc, char **argv)
     for (int w : wavesPerSimd)
     {
       const int blocks = cus * w; // 256 threads = 4 waves = one per SIMD; w workgroups per CU
-      const int it = (op == OP_MFMA_16x16x4) ? iters / 8 : ((op == OP_MFMA_4x4x1 || op == OP_CNDMASK) ? iters / 4 : iters);
+      if (!wanted(kOpName[op])) continue;
+      const int it = (op == OP_MFMA_16x16x4 || op == OP_STORE_X4_VADDR64 || op == OP_STORE_X4_SBASE) ? iters / 8 : ((op == OP_MFMA_4x4x1 || op == OP_CNDMASK) ? iters / 4 : iters);
       hipLaunchKernelGGL(tab[op], dim3(blocks), dim3(256), 0, 0, out, cyc, it / 4, 12345u); // warm-up
       CK(hipDeviceSynchronize());
       CK(hipEventRecord(e0));
