@@ -449,8 +449,7 @@ limg_hip_result limg_hip_encode_stream_budget(limg_hip_context *pCtx, const uint
  * position and the thresholds) + 8 bytes of counter = 80 bytes per image of the longest chunk (streamRateState, streamRateCounter); the probes read the images through
  * the batched encode's own table (96 bytes per image of a chunk, no second table), and the final encode's threshold table (32 bytes per image) lies in the chunk's
  * search states, which are on the host by then: no memory of its own.  limg_hip_context_device_bytes reports all of it.
- * Out of scope: a batched limg_hip_stream_sizes; budgeted lists of mixed shapes (the plain list of mixed shapes: limg_hip_encode_stream_list below); version 2 streams;
- * the accurate search with per-image error factors in one launch (it takes
+ * Out of scope: version 2 streams; the accurate search with per-image error factors in one launch (it takes
  * the grouped fallback of limg_hip_encode_stream_batch_ef_device); the CLI, which encodes one file. */
 /* DEVICE pointers; ppIn / ppStreams are HOST arrays of `count` device pointers (streams 16-byte aligned, capacityEach >= limg_hip_stream_bound) and, as pMaxBytes, may
  * be freed when the call returns.  Waits for `stream`. */
@@ -555,7 +554,7 @@ limg_hip_result limg_hip_encode_stream_quality_batch(limg_hip_context *pCtx, siz
  * sizeX x sizeY bytes, each rounded up to 256), and per image of the longest chunk 64 + 96 + 32 + 32 bytes of tables, 160 for its view (the persistent kernel's parameters as that image's own launch would have them) and
  * 8 for the two prefixes.  limg_hip_context_device_bytes reports all of it.
  * Ordering: calls on one context and stream execute in order and may be issued back to back without a wait.
- * Out of scope: the budgeted list for mixed shapes; a mixed-shape plane batch; the accurate search in the shared launch; version 2 streams; the CLI. */
+ * Out of scope: a mixed-shape plane batch; the accurate search in the shared launch; version 2 streams; the CLI. */
 typedef struct limg_hip_stream_list_item
 {
   const uint32_t *pIn;      /* image i */
@@ -584,6 +583,52 @@ limg_hip_result limg_hip_encode_stream_quality_list_device(limg_hip_context *pCt
 limg_hip_result limg_hip_encode_stream_quality_list(limg_hip_context *pCtx, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
                                                     const uint64_t *pMaxErrorSums, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
                                                     limg_hip_quality_result *pResults);
+
+/* ---- byte budget and size probe for a list of MIXED shapes --------------------------------------------------------------------------
+ * limg_hip_encode_stream_budget_list*: pResults[i] and stream i are exactly limg_hip_encode_stream_budget_device's for item i with maxBytes = pMaxBytes[i] and the same
+ * bounds, arguments and options; each item's errorFactor is ignored.  Every image runs its own search; the result for an item does not depend on its position in the
+ * list or on what else is in the list.  pMaxBytes and pResults are HOST arrays of `count` entries in both forms; set struct_size in EVERY pResults[i].
+ * Errors, all before anything touches the device -- a refused call writes nothing to any stream or result -- in this order: rules (1) to (3) of
+ * limg_hip_encode_stream_list_device, pMaxBytes and pResults counted among the pointers; then the bound rules (odd, below 2, min > max), any pMaxBytes[i] == 0 and any
+ * struct_size below the struct's, as limg_hip_encode_stream_budget_batch_device states them: limg_hip_error_InvalidParameter; then count == 0: limg_hip_success with
+ * nothing done.
+ * limg_hip_stream_sizes_list*: pBytes[i * factorCount + k] = the totalBytes limg_hip_encode_stream* reports for item i at pErrorFactors[k], without encoding; any factor
+ * value is allowed.  Of an item only pIn, sizeX, sizeY and reserved (0) are read: pStream may be NULL, capacity and errorFactor are ignored.  pErrorFactors (factorCount
+ * entries) and pBytes (count * factorCount) are HOST arrays in both forms.  Errors: the item rules above without those on pStream and capacity, pErrorFactors and pBytes
+ * counted among the pointers; then factorCount == 0 or count == 0: limg_hip_success with nothing done.
+ * Routing: eligibility is limg_hip_encode_stream_list's, the chunks are its chunks.  Per chunk of more than one eligible item the call issues the chunk's tables and ONE
+ * k_fit_tpb_list grid (records in the context's float mode, image after image; no noise table, no park slots), one k_rate_begin_batch per 64 images, and then
+ *   budget: 2 + ceil(log2(hHi - hLo)) pairs of k_rate_probe_list -- one workgroup per work strip of the chunk, the strip's image by the binary search of
+ *           k_encode_list_mixed, its geometry from its table entry; the workgroups of an image whose search is over return at their first load -- and k_rate_step_batch
+ *           with the chunk's image table (image i's fixed bytes are 64 + 56 x its own blocks), ONE copy of the chunk's states and ONE wait; then the chunk goes through
+ *           limg_hip_encode_stream_list_device's route with each item's errorFactor replaced by the one its search chose.  pResults[i].bytes is the size the probe
+ *           measured at the result, which is the stream's totalBytes.
+ *   sizes:  factorCount pairs of k_rate_probe_list and the step's list form, ONE download of the chunk's count x factorCount sizes and ONE wait.
+ * An ineligible item, and a chunk that holds one item, takes limg_hip_encode_stream_budget_device (sizes: limg_hip_stream_sizes_device, which has its own fallback) inside
+ * the same call and on the same stream.  Eligible items that all share one shape take limg_hip_encode_stream_budget_batch_device's route with the smallest capacity as
+ * capacityEach: the same results.
+ * Ordering: as limg_hip_encode_stream_list_device.  The device forms SYNCHRONISE `stream` once per chunk (and once per single call) and cannot be captured into a graph.
+ * Options: as the single calls.  limg_hip_last_stats after the budget entries is that of the last encode issued.
+ * Context memory, on top of what the mixed-list encode of the same chunk holds: sizeof(RateDevice) + 8 = 80 bytes per image of the longest chunk (state and counter);
+ * for the sizes list, which holds the probe's share of that encode only (tables, records, invN, look-back words), 8 x factorCount bytes per image of the longest chunk
+ * plus 4 x factorCount.  limg_hip_context_device_bytes reports all of it.
+ * Note: the chunk's final encode runs its own float stage, as the same-shape budgeted list's does; reusing the probe's records there is a follow-up.  Out of scope as
+ * well: the CLI; version 2 streams; the accurate search in the shared launches; a mixed-shape plane batch. */
+/* DEVICE pointers in the items (pStream 16-byte aligned, capacity >= limg_hip_stream_bound(sizeX, sizeY)); waits for `stream`. */
+limg_hip_result limg_hip_encode_stream_budget_list_device(limg_hip_context *pCtx, size_t count, const limg_hip_stream_list_item *pItems /* host */, size_t itemSize,
+                                                          int hasAlpha, const size_t *pMaxBytes /* host, count */, uint32_t minErrorFactor, uint32_t maxErrorFactor,
+                                                          int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults /* host, count */, void *stream);
+/* HOST pointers in the items, blocking; the capacity rule of limg_hip_encode_stream_list with pResults[i].bytes. */
+limg_hip_result limg_hip_encode_stream_budget_list(limg_hip_context *pCtx, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
+                                                   const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                   limg_hip_budget_result *pResults);
+/* DEVICE images; waits for `stream`. */
+limg_hip_result limg_hip_stream_sizes_list_device(limg_hip_context *pCtx, size_t count, const limg_hip_stream_list_item *pItems /* host */, size_t itemSize, int hasAlpha,
+                                                  const uint32_t *pErrorFactors /* host, factorCount */, size_t factorCount, size_t *pBytes /* host, count * factorCount */,
+                                                  int poolThreads, int fastBitCrushing, void *stream);
+/* HOST images, blocking, under the context's mutex. */
+limg_hip_result limg_hip_stream_sizes_list(limg_hip_context *pCtx, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
+                                           const uint32_t *pErrorFactors, size_t factorCount, size_t *pBytes, int poolThreads, int fastBitCrushing);
 
 /* ---- compact stream, version 2: the merged-block encoder's rectangles --------------------------------------------------------
  * What limg_hip_blocked_encode3d computes -- the rectangles of merged 8x8 blocks, each with ONE record, ONE shift triple and its crushed factor values -- in the same

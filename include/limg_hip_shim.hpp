@@ -371,6 +371,57 @@ inline limg_result limg_encode_quality_list(const uint32_t *const *ppIn, const s
   return r;
 }
 
+// limg_encode_budget of `count` images of ANY shapes in one call (limg_hip.h "byte budget and size probe for a list of mixed shapes"): image i gets the stream
+// limg_encode_budget writes for it with pMaxBytes[i]; the outputs as limg_encode_budget_batch's, the capacities per image as limg_encode_list's.
+inline limg_result limg_encode_budget_list(const uint32_t *const *ppIn, const size_t count, const size_t *pSizesX, const size_t *pSizesY, const bool hasAlpha,
+                                           uint8_t *const *ppOut, const size_t *pOutCapacities, size_t *pOutSizes, const size_t *pMaxBytes, uint32_t *pErrorFactors,
+                                           bool *pWithinBudget = nullptr, uint32_t *pProbes = nullptr, const uint32_t minErrorFactor = 0, const uint32_t maxErrorFactor = 0,
+                                           limg_thread_pool *pThreadPool = nullptr, const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (!ppIn || !pSizesX || !pSizesY || !ppOut || !pOutCapacities || !pOutSizes || !pErrorFactors || !pMaxBytes) return limg_error_ArgumentNull;
+  const limg_hip_budget_result blank = { sizeof(limg_hip_budget_result), 0, 0, 0, 0 };
+  std::vector<limg_hip_budget_result> res(count ? count : 1, blank);
+  std::vector<limg_hip_stream_list_item> items(count ? count : 1);
+  for (size_t i = 0; i < count; i++)
+  {
+    if (pSizesX[i] > 0xFFFFFFFFull || pSizesY[i] > 0xFFFFFFFFull) return limg_error_InvalidParameter;
+    const limg_hip_stream_list_item it = { ppIn[i], ppOut[i], (uint64_t)pOutCapacities[i], (uint32_t)pSizesX[i], (uint32_t)pSizesY[i], 0u, 0u };
+    items[i] = it;
+  }
+  const limg_result r = (limg_result)limg_hip_encode_stream_budget_list(c, count, items.data(), sizeof(limg_hip_stream_list_item), hasAlpha ? 1 : 0, pMaxBytes, minErrorFactor,
+                                                                        maxErrorFactor, limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0, res.data());
+  if (r != limg_success && r != limg_error_OutOfBounds) return r;
+  for (size_t i = 0; i < count; i++)
+  {
+    pOutSizes[i] = (size_t)res[i].bytes; pErrorFactors[i] = res[i].errorFactor;
+    if (pWithinBudget) pWithinBudget[i] = res[i].withinBudget != 0;
+    if (pProbes) pProbes[i] = res[i].probes;
+  }
+  return r;
+}
+
+// The sizes limg_encode would give `count` images of ANY shapes at each of `factorCount` error factors, without encoding: pOutSizes[i * factorCount + k] for image i
+// at pErrorFactors[k].
+inline limg_result limg_stream_sizes_list(const uint32_t *const *ppIn, const size_t count, const size_t *pSizesX, const size_t *pSizesY, const bool hasAlpha,
+                                          const uint32_t *pErrorFactors, const size_t factorCount, size_t *pOutSizes, limg_thread_pool *pThreadPool = nullptr,
+                                          const bool fastBitCrushing = true)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  if (!ppIn || !pSizesX || !pSizesY || !pErrorFactors || !pOutSizes) return limg_error_ArgumentNull;
+  std::vector<limg_hip_stream_list_item> items(count ? count : 1);
+  for (size_t i = 0; i < count; i++)
+  {
+    if (pSizesX[i] > 0xFFFFFFFFull || pSizesY[i] > 0xFFFFFFFFull) return limg_error_InvalidParameter;
+    const limg_hip_stream_list_item it = { ppIn[i], nullptr, 0u, (uint32_t)pSizesX[i], (uint32_t)pSizesY[i], 0u, 0u };
+    items[i] = it;
+  }
+  return (limg_result)limg_hip_stream_sizes_list(c, count, items.data(), sizeof(limg_hip_stream_list_item), hasAlpha ? 1 : 0, pErrorFactors, factorCount, pOutSizes,
+                                                 limg_hip_shim::pool_threads(pThreadPool), fastBitCrushing ? 1 : 0);
+}
+
 // either version of the stream: version 1 (limg_encode) or version 2 (limg_blocked_encode)
 inline limg_result limg_decode_info(const uint8_t *pIn, const size_t size, size_t *pSizeX, size_t *pSizeY, bool *pHasAlpha)
 {

@@ -32,6 +32,7 @@ ABI_SYMBOLS = (
     "limg_hip_encode_stream_budget_batch_device", "limg_hip_encode_stream_budget_batch",
     "limg_hip_encode_stream_quality_device", "limg_hip_encode_stream_quality", "limg_hip_encode_stream_quality_batch_device", "limg_hip_encode_stream_quality_batch",
     "limg_hip_encode_stream_list_device", "limg_hip_encode_stream_list", "limg_hip_encode_stream_quality_list_device", "limg_hip_encode_stream_quality_list",
+    "limg_hip_encode_stream_budget_list_device", "limg_hip_encode_stream_budget_list", "limg_hip_stream_sizes_list_device", "limg_hip_stream_sizes_list",
     "limg_hip_blocked_stream_bound", "limg_hip_blocked_encode_stream_device", "limg_hip_blocked_decode_stream_device", "limg_hip_blocked_encode_stream",
     "limg_hip_blocked_decode_stream", "limg_hip_blocked_stream_info", "limg_hip_blocked_last_stream",
     "limg_hip_decode_stream_window_device", "limg_hip_blocked_decode_stream_window_device", "limg_hip_decode_stream_window", "limg_hip_blocked_decode_stream_window",
@@ -361,6 +362,15 @@ def load_library(path=None):
                                                              C.c_void_p]
     L.limg_hip_encode_stream_quality_list.restype = C.c_int
     L.limg_hip_encode_stream_quality_list.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
+    L.limg_hip_encode_stream_budget_list_device.restype = C.c_int  # ctx, count, items, itemSize, hasAlpha, budgets (host), min ef, max ef, pool, fast, results, hipStream
+    L.limg_hip_encode_stream_budget_list_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                                            C.c_void_p]
+    L.limg_hip_encode_stream_budget_list.restype = C.c_int
+    L.limg_hip_encode_stream_budget_list.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
+    L.limg_hip_stream_sizes_list_device.restype = C.c_int  # ctx, count, items, itemSize, hasAlpha, error factors (host), factorCount, sizes (host), pool, fast, hipStream
+    L.limg_hip_stream_sizes_list_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.limg_hip_stream_sizes_list.restype = C.c_int
+    L.limg_hip_stream_sizes_list.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     L.limg_hip_stream_compare.restype = C.c_double  # ctx, stream, bytes, original, pixels, mse, max
     L.limg_hip_stream_compare.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.limg_hip_error_sum_for_psnr.restype = C.c_uint64
@@ -992,6 +1002,45 @@ class LimgHip:
         self._stream_call("limg_hip_encode_stream_quality_list_device", len(imgs), items, C.sizeof(StreamListItem), int(has_alpha), limits, min_error_factor, max_error_factor,
                           pool_threads, int(fast), results, self._stream())
         return outs, results[:len(imgs)]
+
+    # ---- ... to a byte budget per image, and the sizes of every image at a list of error factors (contract: include/limg_hip.h) ----
+    def encode_stream_budget_list(self, imgs, has_alpha, max_bytes, min_error_factor=0, max_error_factor=0, pool_threads=0, fast=True):
+        """host uint32 images of ANY shapes, max_bytes an int or one per image -> (list of stream bytes (numpy uint8), list of BudgetResult), one call"""
+        budgets, results = self._budget_list(max_bytes, len(imgs))
+        imgs, outs, items = self._stream_items(imgs, 0, None, False)
+        self._stream_call("limg_hip_encode_stream_budget_list", len(imgs), items, C.sizeof(StreamListItem), int(has_alpha), budgets, min_error_factor, max_error_factor, pool_threads,
+                          int(fast), results)
+        return [o[:results[k].bytes].copy() for k, o in enumerate(outs)], results[:len(imgs)]
+
+    def encode_stream_budget_list_device(self, imgs, has_alpha, max_bytes, min_error_factor=0, max_error_factor=0, outs=None, pool_threads=0, fast=True):
+        """imgs: list of torch int32 CUDA tensors (h, w) of ANY shapes, max_bytes an int or one per image -> (list of torch uint8 CUDA stream buffers, each of its
+        image's worst-case size, list of BudgetResult).  Waits for torch's current stream once per chunk."""
+        budgets, results = self._budget_list(max_bytes, len(imgs))
+        imgs, outs, items = self._stream_items(imgs, 0, outs, True)
+        self._stream_call("limg_hip_encode_stream_budget_list_device", len(imgs), items, C.sizeof(StreamListItem), int(has_alpha), budgets, min_error_factor, max_error_factor,
+                          pool_threads, int(fast), results, self._stream())
+        return outs, results[:len(imgs)]
+
+    def _sizes_list(self, name, imgs, has_alpha, error_factors, pool_threads, fast, device):
+        """one call of a sizes-list entry: items without stream buffers (pStream NULL, capacity 0) -> numpy uint64 (len(imgs), len(error_factors))"""
+        if not device:
+            imgs = [np.ascontiguousarray(i, dtype=np.uint32) for i in imgs]
+        n, m = len(imgs), len(error_factors)
+        ptr = (lambda t: t.data_ptr()) if device else (lambda a: a.ctypes.data)
+        items = (StreamListItem * max(n, 1))()
+        for k in range(n):
+            items[k] = StreamListItem(ptr(imgs[k]), None, 0, imgs[k].shape[1], imgs[k].shape[0], 0, 0)
+        efs, sizes = (C.c_uint32 * max(m, 1))(*[int(e) for e in error_factors]), (C.c_size_t * max(n * m, 1))()
+        self._stream_call(name, n, items, C.sizeof(StreamListItem), int(has_alpha), efs, m, sizes, pool_threads, int(fast), *([self._stream()] if device else []))
+        return np.array(sizes[:n * m], dtype=np.uint64).reshape(n, m)
+
+    def stream_sizes_list(self, imgs, has_alpha, error_factors, pool_threads=0, fast=True):
+        """host uint32 images of ANY shapes -> array [i, k] = len(encode_stream(imgs[i], ..., error_factor=error_factors[k])), without encoding"""
+        return self._sizes_list("limg_hip_stream_sizes_list", imgs, has_alpha, error_factors, pool_threads, fast, False)
+
+    def stream_sizes_list_device(self, imgs, has_alpha, error_factors, pool_threads=0, fast=True):
+        """imgs: list of torch int32 CUDA tensors (h, w) of ANY shapes; waits for torch's current stream"""
+        return self._sizes_list("limg_hip_stream_sizes_list_device", imgs, has_alpha, error_factors, pool_threads, fast, True)
 
     def blocked_stream_bound(self, w, h):
         return self.lib.limg_hip_blocked_stream_bound(w, h)

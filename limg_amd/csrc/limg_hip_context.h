@@ -326,8 +326,11 @@ namespace limg_hip
   // The n > 1 images through ONE float-stage grid and ONE persistent launch in compact stream mode, image i at its own error factor: records, invN and shift words
   // in the context's per-block scratch (grown by the caller) and the strips' payload words in stripWords, image after image; then the statistics.  hostTables: the host copy of the
   // chunk's table block (chunk_tables(n).bytes, zeroed, the caller's StreamImage entries written): every other part is filled here, ONE upload to devTables.
+  // fitOnly (the meaning of EncodeExtra's fitOnly + fitFloatMode for a mixed chunk): the tables and k_fit_tpb_list alone, in the context's float mode -- records and invN
+  // image after image from each image's firstBlock, which is what the chunk's size probes read (k_rate_probe_list).  No noise table, no park slots, no statistics; of
+  // the tables the views stay zero; images[i].fac and stripWords may be NULL, nothing reads the thresholds of images[i].errorFactor.
   limg_hip_result encode_list_chunk(limg_hip_context *c, const ListChunkImage *images, size_t n, int hasAlpha, int poolThreads, uint32_t *stripWords, uint8_t *hostTables,
-                                    uint8_t *devTables, hipStream_t stream, ListChunkTotals &totals);
+                                    uint8_t *devTables, hipStream_t stream, ListChunkTotals &totals, bool fitOnly = false);
 
   // ---- the merged-block encoder's pipeline (limg_hip_blocked_api.hip) ----
   // pInfo == nullptr is the COMPACT mode of the stream entry: no plane is stored.  When the call returns, every rectangle's descriptor (regions), record and shift word

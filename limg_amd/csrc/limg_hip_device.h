@@ -53,6 +53,20 @@ namespace limg_hip
     __device__ __forceinline__ int sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
     __device__ __forceinline__ float sgprf(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
+    // The image that holds work strip x of a mixed-shape chunk (layout: limg_hip_list_plan.h): base[i] <= x < base[i + 1] over the chunk's strip prefix of n
+    // entries.  Wave-uniform, scalar loads: the table was written by a launch that precedes the caller's on the stream.  k_encode_list_mixed and k_rate_probe_list.
+    __device__ __forceinline__ uint32_t find_strip_image(const uint32_t *base, uint32_t n, uint32_t x)
+    {
+      const __attribute__((address_space(4))) uint32_t *b = (const __attribute__((address_space(4))) uint32_t *)(uintptr_t)base;
+      uint32_t lo = 0, hi = n;
+      while (hi - lo > 1u)
+      {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (b[mid] <= x) lo = mid; else hi = mid;
+      }
+      return (uint32_t)sgpr((int)lo);
+    }
+
     // ---- x86 float semantics --------------------------------------------------------------------------------------
     // DPPS 0xFF / 0x7F
     template <int CH>

@@ -377,7 +377,7 @@ namespace limg_hip
   }
 
   limg_hip_result encode_list_chunk(limg_hip_context *c, const ListChunkImage *images, size_t n, int hasAlpha, int poolThreads, uint32_t *stripWords, uint8_t *hostTables,
-                                    uint8_t *devTables, hipStream_t stream, ListChunkTotals &totals)
+                                    uint8_t *devTables, hipStream_t stream, ListChunkTotals &totals, bool fitOnly)
   {
     // what an outer call resets (encode_device): the context's per-block scratch is reused -- no chain encode's phase 1 is pending any more --, its statistics are stale
     c->chain.in = nullptr;
@@ -401,13 +401,21 @@ namespace limg_hip
       rated[i].maxPixel32 = t.maxPixel32; rated[i].blockLimitFull = t.blockLimitFull; rated[i].maxBlock = t.maxBlock; rated[i].crushBits = (int32_t)t.crushBits; rated[i].errorFactor = im.errorFactor;
     }
     limg_hip_result r;
-    if ((r = grow_noise_table(c, (size_t)tot.noiseCalls, stream)) != limg_hip_success) return r; // the largest per-chain need of any image: every image starts at the seed
-    PersistentScratch ps;
-    if ((r = persistent_scratch(c, tot.strips, 2, stream, ps)) != limg_hip_success) return r;
+    PersistentScratch ps = {};
+    if (fitOnly)
+    { // no noise table, and of the persistent launch's scratch only what the fit grid clears on its way: the ticket and the look-back descriptors
+      if ((r = c->enc.lookback.ensure(16 * 2 + (size_t)tot.strips * 8)) != limg_hip_success) return r;
+      ps.ticket = (uint32_t *)c->enc.lookback.p; ps.desc = (unsigned long long *)((uint8_t *)c->enc.lookback.p + 16);
+    }
+    else
+    {
+      if ((r = grow_noise_table(c, (size_t)tot.noiseCalls, stream)) != limg_hip_success) return r; // the largest per-chain need of any image: every image starts at the seed
+      if ((r = persistent_scratch(c, tot.strips, 2, stream, ps)) != limg_hip_success) return r;
+    }
     limg_hip_block_record *const records = (limg_hip_block_record *)c->enc.records.p;
     float *const invN = (float *)c->enc.invN.p;
     uint32_t *const shifts = (uint32_t *)c->enc.shifts.p;
-    for (size_t i = 0; i < n; i++)
+    for (size_t i = 0; !fitOnly && i < n; i++)
     { // the view of image i: RatedListParams as its own launch would have them, the per-block arrays from its first block
       const ListImage &im = list[i];
       const VecAccess vec = { (im.vec & kListVecIn) != 0, false, (im.vec & kListVecFactors8) != 0, false, (im.vec & kListVecFactors) != 0 };
@@ -424,10 +432,16 @@ namespace limg_hip
     f.records = records; f.invN = invN; f.desc = ps.desc; f.ticket = ps.ticket;
     m.views = (const RatedListParams *)(devTables + T.views); m.batch = dIo; m.rated = dRated; m.firstStrip = (const uint32_t *)(devTables + T.firstStrip);
     m.nImages = (uint32_t)n; m.nStrips = tot.strips; m.ticket = ps.ticket; m.park = ps.park;
-    Timeline tl(c, stream, 4); // {k_fit_tpb_list, k_encode_list_mixed, -}
+    Timeline tl(c, stream, 4); // {k_fit_tpb_list, k_encode_list_mixed, -}; fitOnly: {k_fit_tpb_list, -, -}
     tl.mark();
     launch_fit_tpb_list(f, channels, floatFast, tot.vecInAll, stream);
     tl.mark();
+    if (fitOnly)
+    { // the records and invN are all the caller wants (the size probes of the chunk): in the context's float mode, as the full form leaves them
+      tl.close();
+      HIP_TRY(hipGetLastError());
+      return limg_hip_success;
+    }
     launch_encode_list_mixed(m, channels, floatFast, c->enc.persistentWorkgroups / 5 * wg_per_cu(c, 6), stream);
     tl.mark();
     tl.close();

@@ -494,10 +494,32 @@ namespace limg_hip
     unsigned long long *counters;
   };
   struct RateBudgetChunk { uint32_t n; unsigned long long maxBytes[64]; }; // k_rate_begin_batch's budgets, as kernel arguments
-  // hMaxBytes: HOST array of `count` budgets (may die when the call returns); every search runs over [hLo, hHi]
-  void launch_rate_begin_batch(RateDevice *dStates, unsigned long long *dCounters, const uint64_t *hMaxBytes, size_t count, uint32_t hLo, uint32_t hHi, hipStream_t s);
-  void launch_rate_step_batch(RateDevice *dStates, unsigned long long *dCounters, uint32_t nImages, uint64_t fixedBytes, hipStream_t s);
+  // hMaxBytes: HOST array of `count` budgets (may die when the call returns); every search runs over [hLo, hHi].  dList: the call measures a list of error factors
+  // (device memory; hMaxBytes may then be NULL): no search, the thresholds of dList[0]
+  void launch_rate_begin_batch(RateDevice *dStates, unsigned long long *dCounters, const uint64_t *hMaxBytes, size_t count, uint32_t hLo, uint32_t hHi, hipStream_t s,
+                               const uint32_t *dList = nullptr);
+  // dImages: the ListImage table of a chunk of mixed shapes -- image i's fixed bytes are those of its own block count, fixedBytes is not read.  dList: the list form,
+  // image i's size at dList[k] goes to dListBytes[i * listCount + k]
+  void launch_rate_step_batch(RateDevice *dStates, unsigned long long *dCounters, uint32_t nImages, uint64_t fixedBytes, hipStream_t s, const ListImage *dImages = nullptr,
+                              const uint32_t *dList = nullptr, unsigned long long *dListBytes = nullptr, uint32_t listCount = 0);
   void launch_rate_probe_batch(const RateProbeBatchParams &p, int channels, bool floatFast, hipStream_t s);
+  // A chunk of images of MIXED shapes (limg_hip_encode_stream_budget_list*, limg_hip_stream_sizes_list*): the chunk's tables as encode_list_chunk puts them on the
+  // device, records and invN of k_fit_tpb_list image after image from each image's firstBlock, states[i] / counters[i] image i's.  One workgroup per work strip of
+  // the chunk.  No hook member: the kernarg segment is the same in both builds.
+  struct RateProbeListParams
+  {
+    const ListImage *images;
+    const ImageIO *batch;
+    const uint32_t *firstStrip; // nImages: exclusive prefix of the images' work strips
+    uint32_t nImages, nStrips;
+    int32_t recordLimit;
+    int32_t forced[3];
+    const limg_hip_block_record *records;
+    const float *invN;
+    const RateDevice *states;
+    unsigned long long *counters;
+  };
+  void launch_rate_probe_list(const RateProbeListParams &p, int channels, bool floatFast, hipStream_t s);
 
   void launch_synth_random_gradient(uint32_t *out, uint32_t w, uint32_t h, uint64_t seed, int opaque, uint32_t y0, hipStream_t s);
   void launch_synth_photo_noise(uint32_t *out, uint32_t w, uint32_t h, uint64_t seed, uint32_t y0, hipStream_t s);

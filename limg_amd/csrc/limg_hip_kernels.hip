@@ -760,19 +760,7 @@ namespace limg_hip
     // RatedListParams' layout (its geometry, flags, chain partition, and records / invN / shifts offset to its first block: rowBase is 0), fetched with scalar
     // loads where a stage uses a field, exactly as the siblings fetch kernel arguments.  The F step of the previous strip reads the previous image's view by its
     // index.  Ticket, look-back (bounded, poisoning on a time-out) and park slots are those of the siblings; desc, stripWords, noise and timeout are the launch's
-    // own in every view and indexed by the global strip id.
-    __device__ __forceinline__ uint32_t find_strip_image(const uint32_t *base, uint32_t n, uint32_t x)
-    {
-      const __attribute__((address_space(4))) uint32_t *b = (const __attribute__((address_space(4))) uint32_t *)(uintptr_t)base;
-      uint32_t lo = 0, hi = n;
-      while (hi - lo > 1u)
-      {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (b[mid] <= x) lo = mid; else hi = mid;
-      }
-      return (uint32_t)sgpr((int)lo);
-    }
-
+    // own in every view and indexed by the global strip id.  (find_strip_image: limg_hip_device.h, shared with the size probe of a mixed list.)
     template <int CH, bool FAST>
     __global__ __launch_bounds__(kThreads, 6) void k_encode_list_mixed(const MixedListParams p)
     {

@@ -14,6 +14,11 @@
 // The *_batch kernels are the same three for a LIST of same-shape images (limg_hip_encode_stream_budget_batch*): one RateDevice and one counter per image, one probe
 // workgroup per (image, work strip) over records that run image after image, every image on a search of its own.  The probe's body is written once
 // (rate_probe_strip) and takes what differs -- the image's pixels, state, counter and its block rows in the records -- as arguments.
+//
+// The *_list forms are the same for a chunk of images that differ in SHAPE (limg_hip_encode_stream_budget_list*, limg_hip_stream_sizes_list*; the chunk's layout:
+// limg_hip_list_plan.h, its records: k_fit_tpb_list).  k_rate_probe_list: one workgroup per work strip of the chunk; the strip's image by the binary search over the
+// strip prefix that k_encode_list_mixed uses, that image's geometry, access flag and slice starts from its ListImage entry (scalar loads, once per workgroup) as the
+// view rate_probe_strip reads in place of the kernel arguments.  The begin and step kernels of a list take the ListImage table too: an image's fixed bytes are its own.
 #include "limg_hip_phase_e.h"
 
 namespace limg_hip
@@ -36,10 +41,10 @@ namespace limg_hip
       *counter = 0ull;
     }
 
-    // between two probes.  list == nullptr: the search takes the size just counted (rate_step) and names the next error factor, 2 h; otherwise the size goes to
-    // listBytes[i] and the list's next entry is set up.
-    __global__ void k_rate_step(RateDevice *d, unsigned long long *counter, const unsigned long long fixedBytes, const uint32_t *list, unsigned long long *listBytes,
-                                const uint32_t listCount)
+    // between two probes, one image.  bytes from words: a stream is its fixed bytes (header + table) + 8 x the payload words just counted.  list == nullptr: the
+    // search takes that size (rate_step) and names the next error factor, 2 h; otherwise the size goes to listBytes[i] and the list's next entry is set up.
+    __device__ __forceinline__ void rate_step_image(RateDevice *d, unsigned long long *counter, const unsigned long long fixedBytes, const uint32_t *list,
+                                                    unsigned long long *listBytes, const uint32_t listCount)
     {
       const unsigned long long bytes = fixedBytes + 8ull * *counter;
       *counter = 0ull;
@@ -55,6 +60,12 @@ namespace limg_hip
       if (d->search.done) return;
       rate_step(d->search, bytes);
       if (!d->search.done) set_thresholds(d, 2u * d->search.next);
+    }
+
+    __global__ void k_rate_step(RateDevice *d, unsigned long long *counter, const unsigned long long fixedBytes, const uint32_t *list, unsigned long long *listBytes,
+                                const uint32_t listCount)
+    {
+      rate_step_image(d, counter, fixedBytes, list, listBytes, listCount);
     }
 
     // One work strip's probe: strip `strip` of block row `by` of the image whose pixels are io.in; byS: that row in p.records / p.invN.  P: RateProbeParams or
@@ -156,27 +167,27 @@ namespace limg_hip
     }
 
     // ---- a list of images: one search per image ----
-    // thread i: image i's search over [hLo, hHi] for its budget, the thresholds of its first probe (2 hHi), an empty counter
-    __global__ void k_rate_begin_batch(RateDevice *d, unsigned long long *counters, const RateBudgetChunk budgets, const uint32_t hLo, const uint32_t hHi)
+    // thread i: image i's search over [hLo, hHi] for its budget, the thresholds of its first probe (2 hHi), an empty counter.  list: the call measures a list of
+    // error factors instead (limg_hip_stream_sizes_list*): no search, the thresholds of the list's first entry.
+    __global__ void k_rate_begin_batch(RateDevice *d, unsigned long long *counters, const RateBudgetChunk budgets, const uint32_t hLo, const uint32_t hHi, const uint32_t *list)
     {
       const uint32_t i = threadIdx.x;
       if (i >= budgets.n) return;
       d[i].search = rate_begin(hLo, hHi, budgets.maxBytes[i]);
       d[i].listNext = 0u;
-      set_thresholds(d + i, 2u * hHi);
+      set_thresholds(d + i, list ? list[0] : 2u * hHi);
       counters[i] = 0ull;
     }
 
-    // thread i: k_rate_step's search form for image i
-    __global__ void k_rate_step_batch(RateDevice *d, unsigned long long *counters, const uint32_t nImages, const unsigned long long fixedBytes)
+    // thread i: the step of image i.  images == nullptr: a list of one shape, fixedBytes is every image's; else a chunk of mixed shapes, whose image i has the fixed
+    // bytes of its own block count (header + table: limg_hip_stream_header, limg_hip_stream_block).  list: the list form, image i's sizes at listBytes[i * listCount + k].
+    __global__ void k_rate_step_batch(RateDevice *d, unsigned long long *counters, const uint32_t nImages, const unsigned long long fixedBytes, const ListImage *images,
+                                      const uint32_t *list, unsigned long long *listBytes, const uint32_t listCount)
     {
       const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
       if (i >= nImages) return;
-      const unsigned long long bytes = fixedBytes + 8ull * counters[i];
-      counters[i] = 0ull;
-      if (d[i].search.done) return;
-      rate_step(d[i].search, bytes);
-      if (!d[i].search.done) set_thresholds(d + i, 2u * d[i].search.next);
+      const unsigned long long fixed = images ? sizeof(limg_hip_stream_header) + (unsigned long long)images[i].nBlocks * sizeof(limg_hip_stream_block) : fixedBytes;
+      rate_step_image(d + i, counters + i, fixed, list, list ? listBytes + (size_t)i * listCount : nullptr, listCount);
     }
 
     // One workgroup per (image, work strip); the image index is wave-uniform, and the image's pixels come from its entry of the device table through the constant
@@ -190,6 +201,41 @@ namespace limg_hip
       KernIO *const io = (KernIO *)p.batch + img;
       const uint32_t by = local / p.stripsX;
       rate_probe_strip<CH, FAST>(p, *io, p.states + img, p.counters + img, lds, local - by * p.stripsX, by, img * p.blocksY + by);
+    }
+
+    // ---- a chunk of images of mixed shapes ----
+    // what rate_probe_strip reads as `p`, built from one image's ListImage entry: records and invN start at the image's first block, so its rows count from 0
+    struct RateProbeView
+    {
+      uint32_t sizeX, sizeY, blocksX, blocksY, stripsX;
+      int32_t vecIn;
+      int32_t recordLimit;
+      int32_t forced[3];
+      const limg_hip_block_record *records;
+      const float *invN;
+    };
+
+    // One workgroup per work strip of the chunk (the grid is the chunk's strip total).  Everything of the view is wave-uniform and comes through the constant address
+    // space: the tables were written by launches that precede this one on the stream.  A workgroup of an image whose search is over returns at its first load.
+    template <int CH, bool FAST>
+    __global__ __launch_bounds__(kThreads, 6) void k_rate_probe_list(const RateProbeListParams p)
+    {
+      __shared__ __attribute__((aligned(16))) uint8_t lds[lds_layout<true>().total];
+      typedef const __attribute__((address_space(4))) ListImage KernImage;
+      typedef const __attribute__((address_space(4))) ImageIO KernIO;
+      if (blockIdx.x >= p.nStrips) return;
+      const uint32_t img = find_strip_image(p.firstStrip, p.nImages, blockIdx.x);
+      if (p.states[img].search.done) return;
+      KernImage *const im = (KernImage *)(uintptr_t)p.images + img;
+      KernIO *const io = (KernIO *)(uintptr_t)p.batch + img;
+      RateProbeView v;
+      v.sizeX = im->sizeX; v.sizeY = im->sizeY; v.blocksX = im->blocksX; v.blocksY = im->blocksY; v.stripsX = im->stripsX;
+      v.vecIn = (im->vec & kListVecIn) ? 1 : 0; // of THIS image
+      v.recordLimit = p.recordLimit;
+      v.forced[0] = p.forced[0]; v.forced[1] = p.forced[1]; v.forced[2] = p.forced[2];
+      v.records = p.records + im->firstBlock; v.invN = p.invN + 4 * im->firstBlock;
+      const uint32_t local = blockIdx.x - im->firstStrip, by = local / v.stripsX;
+      rate_probe_strip<CH, FAST>(v, *io, p.states + img, p.counters + img, lds, local - by * v.stripsX, by, by);
     }
   } // namespace
 
@@ -210,25 +256,34 @@ namespace limg_hip
     with_flags([&](auto rgba, auto fast) { hipLaunchKernelGGL((k_rate_probe<rgba ? 4 : 3, fast>), grid, block, 0, s, p); }, channels == 4, floatFast);
   }
 
-  void launch_rate_begin_batch(RateDevice *dStates, unsigned long long *dCounters, const uint64_t *hMaxBytes, size_t count, uint32_t hLo, uint32_t hHi, hipStream_t s)
+  void launch_rate_begin_batch(RateDevice *dStates, unsigned long long *dCounters, const uint64_t *hMaxBytes, size_t count, uint32_t hLo, uint32_t hHi, hipStream_t s,
+                               const uint32_t *dList)
   {
     for (size_t i0 = 0; i0 < count; i0 += 64)
     { // the budgets through kernel arguments: stream-ordered, and the host array may die right away
       RateBudgetChunk ch;
       ch.n = (uint32_t)(count - i0 < 64 ? count - i0 : 64);
-      for (uint32_t i = 0; i < 64; i++) ch.maxBytes[i] = i < ch.n ? (unsigned long long)hMaxBytes[i0 + i] : 0ull;
-      hipLaunchKernelGGL(k_rate_begin_batch, dim3(1), dim3(64), 0, s, dStates + i0, dCounters + i0, ch, hLo, hHi);
+      for (uint32_t i = 0; i < 64; i++) ch.maxBytes[i] = hMaxBytes && i < ch.n ? (unsigned long long)hMaxBytes[i0 + i] : 0ull;
+      hipLaunchKernelGGL(k_rate_begin_batch, dim3(1), dim3(64), 0, s, dStates + i0, dCounters + i0, ch, hLo, hHi, dList);
     }
   }
 
-  void launch_rate_step_batch(RateDevice *dStates, unsigned long long *dCounters, uint32_t nImages, uint64_t fixedBytes, hipStream_t s)
+  void launch_rate_step_batch(RateDevice *dStates, unsigned long long *dCounters, uint32_t nImages, uint64_t fixedBytes, hipStream_t s, const ListImage *dImages,
+                              const uint32_t *dList, unsigned long long *dListBytes, uint32_t listCount)
   {
-    hipLaunchKernelGGL(k_rate_step_batch, dim3((nImages + 63u) / 64u), dim3(64), 0, s, dStates, dCounters, nImages, (unsigned long long)fixedBytes);
+    hipLaunchKernelGGL(k_rate_step_batch, dim3((nImages + 63u) / 64u), dim3(64), 0, s, dStates, dCounters, nImages, (unsigned long long)fixedBytes, dImages, dList, dListBytes,
+                       listCount);
   }
 
   void launch_rate_probe_batch(const RateProbeBatchParams &p, int channels, bool floatFast, hipStream_t s)
   {
     const dim3 grid(p.nImages * p.imageStrips), block(kThreads);
     with_flags([&](auto rgba, auto fast) { hipLaunchKernelGGL((k_rate_probe_batch<rgba ? 4 : 3, fast>), grid, block, 0, s, p); }, channels == 4, floatFast);
+  }
+
+  void launch_rate_probe_list(const RateProbeListParams &p, int channels, bool floatFast, hipStream_t s)
+  {
+    const dim3 grid(p.nStrips), block(kThreads);
+    with_flags([&](auto rgba, auto fast) { hipLaunchKernelGGL((k_rate_probe_list<rgba ? 4 : 3, fast>), grid, block, 0, s, p); }, channels == 4, floatFast);
   }
 } // namespace limg_hip

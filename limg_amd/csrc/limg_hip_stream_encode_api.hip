@@ -1,7 +1,7 @@
 // limg_hip_stream_encode_api.hip -- the version 1 stream's encode family of the C ABI: limg_hip_encode_stream, limg_hip_encode_stream_batch, limg_hip_encode_stream_batch_ef, limg_hip_stream_sizes,
 // limg_hip_encode_stream_budget, limg_hip_encode_stream_budget_batch, limg_hip_encode_stream_quality, limg_hip_encode_stream_quality_batch, limg_hip_encode_stream_list
-// (a list of mixed shapes) and limg_hip_encode_stream_quality_list, each with its _device form.  The 8x8 encode in compact mode + the packer of limg_hip_stream.hip; the size probe's kernels are limg_hip_rate.hip, the search limg_hip_rate_step.h; the quality
-// entries measure with the error windows of limg_hip_stream_window_api.hip and search with limg_hip_quality_step.h.  What the twenty entries do alike -- a call's shape,
+// (a list of mixed shapes), limg_hip_encode_stream_quality_list, limg_hip_encode_stream_budget_list and limg_hip_stream_sizes_list, each with its _device form.  The 8x8 encode in compact mode + the packer of limg_hip_stream.hip; the size probe's kernels are limg_hip_rate.hip, the search limg_hip_rate_step.h; the quality
+// entries measure with the error windows of limg_hip_stream_window_api.hip and search with limg_hip_quality_step.h.  What the twenty-four entries do alike -- a call's shape,
 // the argument checks, a list's staging, the probe's parameters, the searches' enqueue, the results -- is written once, in the anonymous namespace below.  No kernel is
 // defined here.
 #include "limg_hip_context.h"
@@ -14,6 +14,8 @@ using namespace limg_hip;
 
 namespace
 {
+  typedef limg_hip_stream_list_item ListItem;
+
   // ---- a call's shape: everything the entries derive from (sizeX, sizeY) ----
   struct StreamShape : EncodeShape // blocks and strips; whole: the strip form of the packer, the batched kernels, the probe
   {
@@ -92,7 +94,6 @@ namespace
   }
 
   // ---- a list, whichever way it came: items.  A same-shape list (ppIn, ppStreams, one shape, capacityEach) as items, and items as the arrays a same-shape entry takes ----
-  typedef limg_hip_stream_list_item ListItem;
   std::vector<ListItem> as_items(size_t n, const uint32_t *const *ppIn, uint8_t *const *ppStreams, size_t capacityEach, size_t sizeX, size_t sizeY)
   {
     std::vector<ListItem> items(n);
@@ -113,25 +114,35 @@ namespace
 
   // ---- host forms of the list entries.  Staging: the images side by side in host.in, the streams at worst-case size side by side in stream.buf, every slice
   // rounded up to 256 bytes; `staged`: the items with both pointers and the capacity replaced ----
-  limg_hip_result stage_items(limg_hip_context *c, const std::vector<ListItem> &items, std::vector<ListItem> &staged)
+  size_t stage_up(size_t v) { return (v + 255) & ~(size_t)255; }
+  // the images alone (the sizes list, which writes no stream): `staged` = the items with pIn replaced
+  limg_hip_result stage_inputs(limg_hip_context *c, const std::vector<ListItem> &items, std::vector<ListItem> &staged)
   {
     HIP_TRY(hipSetDevice(c->device));
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     staged = items;
-    size_t inBytes = 0, outBytes = 0;
-    for (ListItem &it : staged) { it.capacity = up(limg_hip_stream_bound(it.sizeX, it.sizeY)); inBytes += up((size_t)it.sizeX * it.sizeY * 4); outBytes += (size_t)it.capacity; }
-    limg_hip_result r;
-    if ((r = c->host.in.ensure(inBytes)) != limg_hip_success) return r;
-    if ((r = c->stream.buf.ensure(outBytes)) != limg_hip_success) return r;
-    size_t inAt = 0, outAt = 0;
+    size_t inBytes = 0;
+    for (const ListItem &it : items) inBytes += stage_up((size_t)it.sizeX * it.sizeY * 4);
+    const limg_hip_result r = c->host.in.ensure(inBytes);
+    if (r != limg_hip_success) return r;
+    size_t inAt = 0;
     for (size_t i = 0; i < items.size(); i++)
     {
       const size_t px4 = (size_t)items[i].sizeX * items[i].sizeY * 4;
       staged[i].pIn = (const uint32_t *)((const uint8_t *)c->host.in.p + inAt);
-      staged[i].pStream = (uint8_t *)c->stream.buf.p + outAt;
       HIP_TRY(hipMemcpy((void *)staged[i].pIn, items[i].pIn, px4, hipMemcpyHostToDevice));
-      inAt += up(px4); outAt += (size_t)staged[i].capacity;
+      inAt += stage_up(px4);
     }
+    return limg_hip_success;
+  }
+  limg_hip_result stage_items(limg_hip_context *c, const std::vector<ListItem> &items, std::vector<ListItem> &staged)
+  {
+    limg_hip_result r;
+    if ((r = stage_inputs(c, items, staged)) != limg_hip_success) return r;
+    size_t outBytes = 0;
+    for (ListItem &it : staged) { it.capacity = stage_up(limg_hip_stream_bound(it.sizeX, it.sizeY)); outBytes += (size_t)it.capacity; }
+    if ((r = c->stream.buf.ensure(outBytes)) != limg_hip_success) return r;
+    size_t outAt = 0;
+    for (ListItem &it : staged) { it.pStream = (uint8_t *)c->stream.buf.p + outAt; outAt += (size_t)it.capacity; }
     return limg_hip_success;
   }
 
@@ -170,13 +181,27 @@ namespace
   }
 
   // ---- size probe and budget search (kernels: limg_hip_rate.hip; the search: limg_hip_rate_step.h) ----
-  // The probes of n images of one shape: one state and one counter per image, the probe kernel's parameters.  n == 1: the single-image kernels, n > 1: the _batch ones.
+  // The probes of n images: one state and one counter per image, the probe kernel's parameters.  One shape: n == 1 the single-image kernels, n > 1 the _batch ones.
+  // images != NULL: a chunk of mixed shapes, the _list probe and the _batch begin and step with the chunk's ListImage table (fixedBytes is then every image's own).
   struct Probe
   {
     size_t n; int channels; bool floatFast; uint64_t fixedBytes;
     RateDevice *states; unsigned long long *counters;
     RateProbeParams one; RateProbeBatchParams many;
-    void launch(hipStream_t s) const { if (n == 1) launch_rate_probe(one, channels, floatFast, s); else launch_rate_probe_batch(many, channels, floatFast, s); }
+    const ListImage *images = nullptr; RateProbeListParams list;
+    bool single() const { return n == 1 && !images; }
+    void launch(hipStream_t s) const
+    {
+      if (images) launch_rate_probe_list(list, channels, floatFast, s);
+      else if (n == 1) launch_rate_probe(one, channels, floatFast, s);
+      else launch_rate_probe_batch(many, channels, floatFast, s);
+    }
+    // between two probes; dList: the list form (sizes at dBytes, image after image)
+    void step(hipStream_t s, const uint32_t *dList = nullptr, unsigned long long *dBytes = nullptr, uint32_t listCount = 0) const
+    {
+      if (single()) launch_rate_step(states, counters, fixedBytes, dList, dBytes, listCount, s);
+      else launch_rate_step_batch(states, counters, (uint32_t)n, fixedBytes, s, images, dList, dBytes, listCount);
+    }
   };
 
   // what RateProbeParams and RateProbeBatchParams name alike.  vecIn: 16-byte loads, which every image of the launch allows (vec_access)
@@ -215,21 +240,44 @@ namespace
     return limg_hip_success;
   }
 
-  // The searches of n images over [hLo, hHi], image i's for budgets[i]: begin, then every launch any of them can need, enqueued at once -- probes behind the end of
-  // an image's search return at once --, ONE download of the states and ONE wait.  hStates: n, host.
-  limg_hip_result run_searches(limg_hip_context *c, const StreamShape &sh, const uint32_t *const *ppIn, const size_t *budgets, size_t n, uint32_t hLo, uint32_t hHi,
-                               int hasAlpha, int poolThreads, hipStream_t s, RateDevice *hStates)
+  // The probe of a chunk of n > 1 images of mixed shapes (eligible items: list_item_eligible): the chunk's tables and k_fit_tpb_list alone (encode_list_chunk's fitOnly
+  // form) -- records and invN image after image from each image's firstBlock --, and k_rate_probe_list on them.  Everything it needs has been grown by the caller
+  // (grow_list_probe).
+  limg_hip_result list_probe_setup(limg_hip_context *c, const ListItem *its, size_t n, int hasAlpha, int poolThreads, hipStream_t s, Probe &pr)
   {
-    Probe pr;
-    const limg_hip_result r = probe_setup(c, sh, ppIn, n, hasAlpha, poolThreads, s, pr);
+    const ChunkTables T = chunk_tables(n);
+    std::vector<uint8_t> host(T.bytes, 0);
+    uint8_t *const dev = (uint8_t *)c->stream.listTable.p;
+    std::vector<ListChunkImage> images(n);
+    for (size_t i = 0; i < n; i++) images[i] = { its[i].pIn, its[i].sizeX, its[i].sizeY, 0u, { nullptr, nullptr, nullptr } };
+    ListChunkTotals tot;
+    const limg_hip_result r = encode_list_chunk(c, images.data(), n, hasAlpha, poolThreads, nullptr, host.data(), dev, s, tot, true);
     if (r != limg_hip_success) return r;
-    if (n == 1) launch_rate_begin(pr.states, pr.counters, rate_begin(hLo, hHi, budgets[0]), 2u * hHi, s);
+    pr.n = n; pr.channels = hasAlpha ? 4 : 3; pr.floatFast = c->opt.float_mode == 1; pr.fixedBytes = 0;
+    pr.states = (RateDevice *)c->stream.rateState.p; pr.counters = (unsigned long long *)c->stream.rateCounter.p;
+    pr.images = (const ListImage *)(dev + T.images);
+    RateProbeListParams &p = pr.list;
+    memset(&p, 0, sizeof(p));
+    p.images = pr.images; p.batch = (const ImageIO *)(dev + T.io); p.firstStrip = (const uint32_t *)(dev + T.firstStrip);
+    p.nImages = (uint32_t)n; p.nStrips = tot.strips;
+    p.recordLimit = record_limit(c);
+    forced_shifts(c->opt.forced_shift, p.forced);
+    p.records = (const limg_hip_block_record *)c->enc.records.p; p.invN = (const float *)c->enc.invN.p;
+    p.states = pr.states; p.counters = pr.counters;
+    return limg_hip_success;
+  }
+
+  // The searches of pr's n images over [hLo, hHi], image i's for budgets[i]: begin, then every launch any of them can need, enqueued at once -- probes behind the end of
+  // an image's search return at once --, ONE download of the states and ONE wait.  hStates: n, host.
+  limg_hip_result run_searches(const Probe &pr, const size_t *budgets, uint32_t hLo, uint32_t hHi, hipStream_t s, RateDevice *hStates)
+  {
+    const size_t n = pr.n;
+    if (pr.single()) launch_rate_begin(pr.states, pr.counters, rate_begin(hLo, hHi, budgets[0]), 2u * hHi, s);
     else launch_rate_begin_batch(pr.states, pr.counters, budgets, n, hLo, hHi, s);
     for (uint32_t i = 0, probes = rate_max_probes(hLo, hHi); i < probes; i++)
     {
       pr.launch(s);
-      if (n == 1) launch_rate_step(pr.states, pr.counters, pr.fixedBytes, nullptr, nullptr, 0, s);
-      else launch_rate_step_batch(pr.states, pr.counters, (uint32_t)n, pr.fixedBytes, s);
+      pr.step(s);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hStates, pr.states, n * sizeof(RateDevice), hipMemcpyDeviceToHost, s));
@@ -237,6 +285,14 @@ namespace
     for (size_t i = 0; i < n; i++)
       if (!hStates[i].search.done) return limg_hip_error_Generic;
     return limg_hip_success;
+  }
+  // ... of n images of one shape
+  limg_hip_result run_searches(limg_hip_context *c, const StreamShape &sh, const uint32_t *const *ppIn, const size_t *budgets, size_t n, uint32_t hLo, uint32_t hHi,
+                               int hasAlpha, int poolThreads, hipStream_t s, RateDevice *hStates)
+  {
+    Probe pr;
+    const limg_hip_result r = probe_setup(c, sh, ppIn, n, hasAlpha, poolThreads, s, pr);
+    return r != limg_hip_success ? r : run_searches(pr, budgets, hLo, hHi, s, hStates);
   }
 }
 
@@ -475,7 +531,7 @@ extern "C"
     for (size_t i = 0; i < count; i++)
     {
       pr.launch(s);
-      launch_rate_step(pr.states, pr.counters, pr.fixedBytes, dList, dBytes, (uint32_t)count, s);
+      pr.step(s, dList, dBytes, (uint32_t)count);
     }
     HIP_TRY(hipGetLastError());
     return download_sizes(dBytes, count, pBytes, s); // (its wait also: `list` is no longer read)
@@ -796,8 +852,10 @@ extern "C"
 // ---- stream encode of a list of mixed shapes (contract: include/limg_hip.h; the layout: limg_hip_list_plan.h) ----
 namespace
 {
-  // The items as the caller's array holds them (itemSize apart), checked in the contract's order.  deviceForm: the streams are device buffers.
-  limg_hip_result check_items(const void *c, bool pointers, size_t count, const ListItem *pItems, size_t itemSize, bool deviceForm, std::vector<ListItem> &items)
+  // The items as the caller's array holds them (itemSize apart), checked in the contract's order.  deviceForm: the streams are device buffers.  streams == false:
+  // the call writes no stream (the sizes list) -- pStream and capacity are not read.
+  limg_hip_result check_items(const void *c, bool pointers, size_t count, const ListItem *pItems, size_t itemSize, bool deviceForm, std::vector<ListItem> &items,
+                              bool streams = true)
   {
     if (!c || !pItems || !pointers) return limg_hip_error_ArgumentNull;
     if (itemSize < sizeof(ListItem)) return limg_hip_error_InvalidParameter;
@@ -806,11 +864,11 @@ namespace
     {
       memcpy(&items[i], (const uint8_t *)pItems + i * itemSize, sizeof(ListItem));
       const ListItem &it = items[i];
-      if (!it.pIn || !it.pStream) return limg_hip_error_ArgumentNull;
+      if (!it.pIn || (streams && !it.pStream)) return limg_hip_error_ArgumentNull;
       const size_t bound = (it.sizeX && it.sizeY) ? limg_hip_stream_bound(it.sizeX, it.sizeY) : 0;
       if (bound == 0) return limg_hip_error_InvalidParameter;
-      if (deviceForm && ((uintptr_t)it.pStream & 15u) != 0) return limg_hip_error_InvalidParameter;
-      if (deviceForm && it.capacity < bound) return limg_hip_error_OutOfBounds;
+      if (streams && deviceForm && ((uintptr_t)it.pStream & 15u) != 0) return limg_hip_error_InvalidParameter;
+      if (streams && deviceForm && it.capacity < bound) return limg_hip_error_OutOfBounds;
       if (it.reserved != 0) return limg_hip_error_InvalidParameter;
     }
     return limg_hip_success;
@@ -919,6 +977,163 @@ namespace
   }
 }
 
+// ---- the byte budget and the size probe for a list of mixed shapes (contract: include/limg_hip.h; kernels: k_rate_probe_list and the _batch begin / step with the
+// chunk's ListImage table, limg_hip_rate.hip) ----
+namespace
+{
+  // The eligible items of a list as the mixed routes walk them: which they are, their blocks and strips, and what the largest chunk of more than one item needs.
+  struct ListRoute
+  {
+    std::vector<size_t> shared, alone; // indices into the list
+    std::vector<ListItem> items;       // the eligible items, in list order
+    std::vector<uint64_t> blocks, strips;
+    size_t hook;
+    ListNeeds most;
+    bool oneShape = true;
+    ListRoute(const limg_hip_context *c, const std::vector<ListItem> &all, int fastBitCrushing)
+    {
+      for (size_t i = 0; i < all.size(); i++) (list_item_eligible(all[i].sizeX, all[i].sizeY, fastBitCrushing, c->opt) ? shared : alone).push_back(i);
+      for (size_t i : shared)
+      {
+        const EncodeShape sh(all[i].sizeX, all[i].sizeY);
+        items.push_back(all[i]); blocks.push_back(sh.blocks); strips.push_back(sh.strips);
+        oneShape = oneShape && all[i].sizeX == items[0].sizeX && all[i].sizeY == items[0].sizeY;
+      }
+      hook = TOPT(c, batch_chunk) > 0 ? (size_t)TOPT(c, batch_chunk) : 0;
+      const std::vector<size_t> noPlanes(items.size(), 0);
+      most = list_needs(blocks.data(), strips.data(), noPlanes.data(), items.size(), hook);
+    }
+    size_t chunk_end(size_t i0) const { return list_chunk_end(blocks.data(), strips.data(), items.size(), i0, hook); }
+  };
+
+  // everything the probes of the route's largest chunk need, before the first launch: the tables, the fit grid's records, invN and look-back words, one state and one
+  // counter per image
+  limg_hip_result grow_list_probe(limg_hip_context *c, const ListRoute &route)
+  {
+    const ListNeeds &most = route.most;
+    if (most.images < 2) return limg_hip_success;
+    limg_hip_result r;
+    if ((r = c->stream.listTable.ensure(chunk_tables(most.images).bytes)) != limg_hip_success) return r;
+    if ((r = c->enc.records.ensure((size_t)most.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+    if ((r = c->enc.invN.ensure((size_t)most.blocks * 16)) != limg_hip_success) return r;
+    if ((r = c->enc.lookback.ensure(16 * 2 + (size_t)most.strips * 8)) != limg_hip_success) return r;
+    if ((r = c->stream.rateState.ensure(most.images * sizeof(RateDevice))) != limg_hip_success) return r;
+    return c->stream.rateCounter.ensure(most.images * 8);
+  }
+
+  // The whole route of the budgeted list (the arguments have been checked): result i and stream i the single budget call's for item i.  Eligible items of more than
+  // one shape go chunk by chunk -- the chunk's records from ONE k_fit_tpb_list grid, its searches as 1 + 2 x rate_max_probes launches with ONE download and ONE wait,
+  // then the chunk through the mixed-list encode at the error factors the searches chose (that encode runs its own float stage: reusing the probe's records is a
+  // follow-up) --; a chunk of one item, and every ineligible item, takes the single call on the same stream; eligible items of ONE shape take the same-shape list.
+  limg_hip_result budget_items_device(limg_hip_context *c, const std::vector<ListItem> &items, int hasAlpha, const size_t *pMaxBytes, uint32_t minErrorFactor,
+                                      uint32_t maxErrorFactor, uint32_t hLo, uint32_t hHi, int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults, void *stream)
+  {
+    const size_t count = items.size();
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const ListRoute route(c, items, fastBitCrushing);
+    auto single = [&](size_t i) {
+      const ListItem &it = items[i];
+      return limg_hip_encode_stream_budget_device(c, it.pIn, it.sizeX, it.sizeY, hasAlpha, it.pStream, (size_t)it.capacity, pMaxBytes[i], minErrorFactor, maxErrorFactor, poolThreads,
+                                                  fastBitCrushing, &pResults[i], stream);
+    };
+    limg_hip_result r = limg_hip_success;
+    const size_t n = route.items.size();
+    std::vector<size_t> budgets(n);
+    for (size_t k = 0; k < n; k++) budgets[k] = pMaxBytes[route.shared[k]];
+    if (n == 1) r = single(route.shared[0]);
+    else if (n > 1 && route.oneShape)
+    { // the same-shape list, as it is: limg_hip_encode_stream_budget_batch_device with the smallest capacity
+      const ItemArrays a(route.items);
+      std::vector<limg_hip_budget_result> own = own_results<limg_hip_budget_result>(n);
+      r = limg_hip_encode_stream_budget_batch_device(c, n, a.in.data(), route.items[0].sizeX, route.items[0].sizeY, hasAlpha, a.streams.data(), a.capacityEach, budgets.data(),
+                                                     minErrorFactor, maxErrorFactor, poolThreads, fastBitCrushing, own.data(), stream);
+      for (size_t k = 0; r == limg_hip_success && k < n; k++) report(pResults + route.shared[k], own.data() + k, 0);
+    }
+    else if (n > 1)
+    {
+      if ((r = grow_list_probe(c, route)) != limg_hip_success) return r;
+      std::vector<RateDevice> states;
+      std::vector<ListItem> chosen;
+      for (size_t i0 = 0; i0 < n && r == limg_hip_success;)
+      {
+        const size_t i1 = route.chunk_end(i0), m = i1 - i0;
+        if (m == 1) r = single(route.shared[i0]); // a chunk that holds one item: the single call
+        else
+        {
+          Probe pr;
+          states.resize(m);
+          if ((r = list_probe_setup(c, &route.items[i0], m, hasAlpha, poolThreads, s, pr)) != limg_hip_success) break;
+          if ((r = run_searches(pr, &budgets[i0], hLo, hHi, s, states.data())) != limg_hip_success) break;
+          chosen.assign(route.items.begin() + i0, route.items.begin() + i1);
+          for (size_t k = 0; k < m; k++) { chosen[k].errorFactor = 2u * states[k].search.next; chosen[k].reserved = 0; }
+          if ((r = stream_items_device(c, chosen, hasAlpha, nullptr, poolThreads, fastBitCrushing, stream)) != limg_hip_success) break;
+          for (size_t k = 0; k < m; k++) // bytes: what the probe measured at the result -- the packer's totalBytes
+            fill_result(pResults[route.shared[i0 + k]], 2u * states[k].search.next, states[k].search.probes, states[k].search.within, states[k].search.bestBytes);
+        }
+        i0 = i1;
+      }
+    }
+    for (size_t k = 0; k < route.alone.size() && r == limg_hip_success; k++) r = single(route.alone[k]);
+    return r;
+  }
+
+  // The sizes of every item at every factor (the arguments have been checked; factorCount > 0): pBytes[i * factorCount + k].  The eligible items go chunk by chunk,
+  // whatever their shapes: ONE k_fit_tpb_list grid, one begin, factorCount pairs of k_rate_probe_list and the list form of the step, ONE download and ONE wait per
+  // chunk.  A chunk of one item and every ineligible item take limg_hip_stream_sizes_device, which has its own fallback.
+  limg_hip_result sizes_items_device(limg_hip_context *c, const std::vector<ListItem> &items, int hasAlpha, const uint32_t *pErrorFactors, size_t factorCount, size_t *pBytes,
+                                     int poolThreads, int fastBitCrushing, void *stream)
+  {
+    const size_t count = items.size();
+    if (count > 0x7FFFFFFFull || factorCount > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const ListRoute route(c, items, fastBitCrushing);
+    auto single = [&](size_t i) {
+      return limg_hip_stream_sizes_device(c, items[i].pIn, items[i].sizeX, items[i].sizeY, hasAlpha, pErrorFactors, factorCount, pBytes + i * factorCount, poolThreads, fastBitCrushing,
+                                          stream);
+    };
+    limg_hip_result r = limg_hip_success;
+    const size_t n = route.items.size();
+    if (route.most.images > 1)
+    {
+      if ((r = grow_list_probe(c, route)) != limg_hip_success) return r;
+      if ((r = c->stream.rateList.ensure(route.most.images * factorCount * 8 + factorCount * 4)) != limg_hip_success) return r;
+    }
+    const std::vector<uint32_t> list(pErrorFactors, pErrorFactors + factorCount); // (the caller's array may be pageable and may die when the call returns)
+    std::vector<size_t> sizes;
+    for (size_t i0 = 0; i0 < n && r == limg_hip_success;)
+    {
+      const size_t i1 = route.chunk_end(i0), m = i1 - i0;
+      if (m == 1) r = single(route.shared[i0]);
+      else
+      {
+        Probe pr;
+        if ((r = list_probe_setup(c, &route.items[i0], m, hasAlpha, poolThreads, s, pr)) != limg_hip_success) break;
+        unsigned long long *dBytes = (unsigned long long *)c->stream.rateList.p;
+        uint32_t *dList = (uint32_t *)(dBytes + m * factorCount);
+        HIP_TRY(hipMemcpyAsync(dList, list.data(), factorCount * 4, hipMemcpyHostToDevice, s));
+        launch_rate_begin_batch(pr.states, pr.counters, nullptr, m, 0, 0, s, dList);
+        for (size_t k = 0; k < factorCount; k++)
+        {
+          pr.launch(s);
+          pr.step(s, dList, dBytes, (uint32_t)factorCount);
+        }
+        HIP_TRY(hipGetLastError());
+        sizes.resize(m * factorCount);
+        if ((r = download_sizes(dBytes, m * factorCount, sizes.data(), s)) != limg_hip_success) break; // (its wait also: `list` is no longer read by this chunk)
+        for (size_t k = 0; k < m; k++)
+          for (size_t f = 0; f < factorCount; f++) pBytes[route.shared[i0 + k] * factorCount + f] = sizes[k * factorCount + f];
+      }
+      i0 = i1;
+    }
+    for (size_t k = 0; k < route.alone.size() && r == limg_hip_success; k++) r = single(route.alone[k]);
+    return r;
+  }
+}
+
 extern "C"
 {
   limg_hip_result limg_hip_encode_stream_list_device(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha, size_t *pBytes,
@@ -966,5 +1181,57 @@ extern "C"
     if ((r = check_search(count, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
     if (count == 0) return limg_hip_success;
     return quality_list_host(c, items, true, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults);
+  }
+
+  // ---- ... to a byte budget per item, and the sizes of every item at a list of error factors (budget_items_device / sizes_items_device above) ----
+  limg_hip_result limg_hip_encode_stream_budget_list_device(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
+                                                            const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                            limg_hip_budget_result *pResults, void *stream)
+  {
+    std::vector<ListItem> items;
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = check_items(c, pMaxBytes && pResults, count, pItems, itemSize, true, items)) != limg_hip_success) return r;
+    if ((r = check_search(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    return budget_items_device(c, items, hasAlpha, pMaxBytes, minErrorFactor, maxErrorFactor, hLo, hHi, poolThreads, fastBitCrushing, pResults, stream);
+  }
+
+  limg_hip_result limg_hip_encode_stream_budget_list(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
+                                                     const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
+                                                     limg_hip_budget_result *pResults)
+  {
+    std::vector<ListItem> items;
+    uint32_t hLo, hHi;
+    limg_hip_result r;
+    if ((r = check_items(c, pMaxBytes && pResults, count, pItems, itemSize, false, items)) != limg_hip_success) return r;
+    if ((r = check_search(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
+    if (count == 0) return limg_hip_success;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    std::vector<limg_hip_budget_result> results = own_results<limg_hip_budget_result>(count);
+    return host_list(c, items, results.data(), pResults, [&](const std::vector<ListItem> &staged) {
+      return budget_items_device(c, staged, hasAlpha, pMaxBytes, minErrorFactor, maxErrorFactor, hLo, hHi, poolThreads, fastBitCrushing, results.data(), nullptr);
+    });
+  }
+
+  limg_hip_result limg_hip_stream_sizes_list_device(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
+                                                    const uint32_t *pErrorFactors, size_t factorCount, size_t *pBytes, int poolThreads, int fastBitCrushing, void *stream)
+  {
+    std::vector<ListItem> items;
+    const limg_hip_result r = check_items(c, pErrorFactors && pBytes, count, pItems, itemSize, true, items, false);
+    if (r != limg_hip_success || count == 0 || factorCount == 0) return r;
+    return sizes_items_device(c, items, hasAlpha, pErrorFactors, factorCount, pBytes, poolThreads, fastBitCrushing, stream);
+  }
+
+  limg_hip_result limg_hip_stream_sizes_list(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
+                                             const uint32_t *pErrorFactors, size_t factorCount, size_t *pBytes, int poolThreads, int fastBitCrushing)
+  {
+    std::vector<ListItem> items, staged;
+    limg_hip_result r = check_items(c, pErrorFactors && pBytes, count, pItems, itemSize, false, items, false);
+    if (r != limg_hip_success || count == 0 || factorCount == 0) return r;
+    if (count > 0x7FFFFFFFull || factorCount > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
+    if ((r = stage_inputs(c, items, staged)) != limg_hip_success) return r;
+    r = sizes_items_device(c, staged, hasAlpha, pErrorFactors, factorCount, pBytes, poolThreads, fastBitCrushing, nullptr);
+    return r != limg_hip_success ? r : limg_hip_check_device_status(c);
   }
 }
