@@ -225,7 +225,8 @@ namespace limg_hip
   // |record value| above which a block takes the generic 32-bit trial: EncodeParams::recordLimit and the probes' (see term_bias in limg_hip_search.h: 3 * 2700 + 1 < 0x2000)
   inline int32_t record_limit(const limg_hip_context *c) { return TOPT(c, record_limit) > 0 ? TOPT(c, record_limit) - 1 : 2700; }
   // images of one shape per launch pair (list_chunk, limg_hip_encode_rules.h) with the test build's batch_chunk; blocks, strips: of one image
-  inline size_t list_chunk(const limg_hip_context *c, size_t blocks, size_t strips) { return list_chunk(blocks, strips, TOPT(c, batch_chunk) > 0 ? (size_t)TOPT(c, batch_chunk) : 0); }
+  inline size_t batch_hook(const limg_hip_context *c) { return TOPT(c, batch_chunk) > 0 ? (size_t)TOPT(c, batch_chunk) : 0; }
+  inline size_t list_chunk(const limg_hip_context *c, size_t blocks, size_t strips) { return list_chunk(blocks, strips, batch_hook(c)); }
 
   // ---- what the stream entries (limg_hip_stream_api.hip: shared parts, header checks, decode, version 2; limg_hip_stream_encode_api.hip: the version 1 encode family)
   // and the window entries (limg_hip_stream_window_api.hip) share; defined in limg_hip_stream_api.hip ----

@@ -57,12 +57,13 @@ namespace limg_hip
   }
 
   // Images of one shape that go into ONE launch pair: the per-block scratch of a launch pair is bounded (1 GiB of records) and strip ids are 32 bits; at least one.
-  // hook: the test build's batch_chunk, 0 = none.  blocks, strips: of one image, both > 0.
+  // hook: the test build's batch_chunk, 0 = none -- fewer images per pair, never more than the bounds allow.  blocks, strips: of one image, both > 0.  These are the
+  // chunks list_chunk_end (limg_hip_list_plan.h) gives on a list of that one shape: tests/test_list_plan_cpu.py.
   LIMG_RULES_HD inline size_t list_chunk(size_t blocks, size_t strips, size_t hook)
   {
-    if (hook > 0) return hook;
     size_t chunk = (size_t)(1ull << 30) / (blocks * sizeof(limg_hip_block_record));
     if (chunk * strips > 0x7FFFFFFFull) chunk = 0x7FFFFFFFull / strips;
+    if (hook > 0 && hook < chunk) chunk = hook;
     return chunk < 1 ? 1 : chunk;
   }
 }

@@ -1,14 +1,19 @@
 // limg_hip_list_plan.h -- the layout of a stream-encode list whose images differ in shape (limg_hip_encode_stream_list*), stated ONCE for the host route and the
 // kernels that walk it: which items may share the launches, where an image's blocks, strips and float-stage units start in the chunk's concatenated arrays, the
-// 16-byte access flags and the dither-chain partition of THAT image, a chunk's totals and its noise need, and where a chunk ends.  A host compiler builds it on
-// its own (tests/helpers/list_plan_check.cpp).  Plain C++: no HIP types, no library.
+// 16-byte access flags and the dither-chain partition of THAT image, a chunk's totals and its noise need, and where a chunk ends -- and the ROUTE of every list
+// entry of the stream encode family, same-shape or mixed (list_route: which items go through which launches, in which order, and what the largest chunk needs).  A
+// host compiler builds it on its own (tests/helpers/list_plan_check.cpp).  Plain C++: no HIP types, nothing but the standard library.
 #ifndef LIMG_HIP_LIST_PLAN_H
 #define LIMG_HIP_LIST_PLAN_H
 
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "limg_hip_encode_plan.h"
+#include "limg_hip_encode_rules.h"
 
 namespace limg_hip
 {
@@ -62,7 +67,8 @@ namespace limg_hip
   };
 
   // Where the chunk that starts at image i0 ends: the plane batch's rule (1 GiB of block records, 32-bit strip ids, the test build's batch_chunk = images per
-  // chunk) counted in blocks and strips SUMMED over the images; at least one image.  blocks[i], strips[i]: of image i, both > 0.
+  // chunk) counted in blocks and strips SUMMED over the images; at least one image.  blocks[i], strips[i]: of image i, both > 0.  On images of ONE shape its chunks
+  // are those of list_chunk (limg_hip_encode_rules.h), `list_chunk(blocks, strips, hook)` images each: tests/test_list_plan_cpu.py.
   inline size_t list_chunk_end(const uint64_t *blocks, const uint64_t *strips, size_t count, size_t i0, size_t hook)
   {
     const uint64_t maxBlocks = (1ull << 30) / sizeof(limg_hip_block_record), maxStrips = 0x7FFFFFFFull;
@@ -117,27 +123,172 @@ namespace limg_hip
     }
   };
 
-  // ---- what the largest chunk of a list asks of the scratch: the chunks of more than one image (list_chunk_end; one image alone takes the single call), each
-  // member the maximum over them -- everything is grown once, before the first launch.  facBytes[i]: image i's three factor planes ----
+  // ---- what the largest chunk of a list asks of the scratch: over the steps of more than one image (one image alone takes the single call), each member the
+  // maximum over them -- everything is grown once, before the first launch.  facBytes: the images' three factor planes each ----
   struct ListNeeds { size_t images; uint64_t blocks, strips; size_t facBytes; };
+  inline void list_needs_max(ListNeeds &most, const ListNeeds &n)
+  {
+    if (n.images > most.images) most.images = n.images;
+    if (n.blocks > most.blocks) most.blocks = n.blocks;
+    if (n.strips > most.strips) most.strips = n.strips;
+    if (n.facBytes > most.facBytes) most.facBytes = n.facBytes;
+  }
+  // ... of the chunks list_chunk_end cuts a list of eligible items into (what list_route's `most` is for a mixed-shape encode).  facBytes[i]: image i's planes
   inline ListNeeds list_needs(const uint64_t *blocks, const uint64_t *strips, const size_t *facBytes, size_t count, size_t hook)
   {
     ListNeeds most = {};
     for (size_t i0 = 0; i0 < count;)
     {
       const size_t i1 = list_chunk_end(blocks, strips, count, i0, hook);
-      if (i1 - i0 > 1)
-      {
-        ListNeeds n = { i1 - i0, 0, 0, 0 };
-        for (size_t i = i0; i < i1; i++) { n.blocks += blocks[i]; n.strips += strips[i]; n.facBytes += facBytes[i]; }
-        if (n.images > most.images) most.images = n.images;
-        if (n.blocks > most.blocks) most.blocks = n.blocks;
-        if (n.strips > most.strips) most.strips = n.strips;
-        if (n.facBytes > most.facBytes) most.facBytes = n.facBytes;
-      }
+      ListNeeds n = { i1 - i0, 0, 0, 0 };
+      for (size_t i = i0; i < i1; i++) { n.blocks += blocks[i]; n.strips += strips[i]; n.facBytes += facBytes[i]; }
+      if (n.images > 1) list_needs_max(most, n);
       i0 = i1;
     }
     return most;
+  }
+
+  // ---- the route of a list: which launches its items take, in which order.  ONE pure function for every list entry of the stream encode family; the entries'
+  // walkers (limg_hip_stream_encode_api.hip) grow what `most` says and loop over the steps, and decide nothing ----
+  enum ListJob { kListShared, kListOwn, kListBudget, kListSizes }; // encode at one factor / at each item's own; search each item's factor for a budget; the sizes at a list of factors
+  enum ListStepKind
+  {
+    kStepSingle, // one item through the single call of the job
+    kStepSame,   // n > 1 items of one shape in one launch pair (budget: behind one shared probe grid and the searches on it)
+    kStepMixed   // n > 1 eligible items, whatever their shapes, in the mixed launches (encode_list_chunk; budget and sizes: the list probe on its fit grid)
+  };
+  // blocks and strips are inputs of their own (not derived from the shape here), as list_chunk_end takes them: synthetic counts can be asked about without memory
+  struct ListPlanItem { size_t sizeX, sizeY; uint64_t blocks, strips; size_t facBytes; bool eligible; uint32_t errorFactor; }; // facBytes: its three factor planes
+  inline ListPlanItem list_plan_item(size_t sizeX, size_t sizeY, uint32_t errorFactor, int fastBitCrushing, const limg_hip_options &o)
+  {
+    const EncodeShape sh(sizeX, sizeY);
+    return { sizeX, sizeY, sh.blocks, sh.strips, 3 * list_plane_stride(sizeX, sizeY), list_item_eligible(sizeX, sizeY, fastBitCrushing, o), errorFactor };
+  }
+  struct ListStep
+  {
+    ListStepKind kind;
+    bool own;     // kStepSame of an encode: each image at its own factor (k_encode_list_rated); false: the chunk shares one
+    bool restart; // limg_hip_last_stats starts over with this step (the first; on the sorted route the first of every factor's group); the others add to it
+    size_t first, count; // its items: order[first, first + count)
+  };
+  struct ListPlan
+  {
+    std::vector<size_t> order; // item indices, step after step: every item once
+    std::vector<ListStep> steps;
+    ListNeeds most = {};   // of the steps of more than one item, member by member; facBytes: the encodes only (a probe writes no factor plane)
+    bool mixed = false;    // there are kStepMixed steps (then there is no kStepSame)
+    bool rated = false;    // there are own-factor chunks: a threshold table of most.images entries
+    bool inPlace = false;  // a same-shape encode cut in list order: step after step leaves its items' entries of the streams' table, entry i = item i
+  };
+
+  // The rules, each once.  same_shape / budget_same take items of ONE shape (by index); list_route below names which entry takes which.
+  struct ListRouter
+  {
+    const ListPlanItem *items; ListJob job; int fast; const limg_hip_options &opt; size_t hook;
+    ListPlan plan;
+    bool restart = true;
+
+    void step(ListStepKind kind, bool own, const size_t *idx, size_t n)
+    {
+      plan.steps.push_back({ kind, n > 1 && own, restart, plan.order.size(), n });
+      plan.order.insert(plan.order.end(), idx, idx + n);
+      restart = false;
+      if (n < 2) return;
+      ListNeeds need = { n, 0, 0, 0 };
+      for (size_t i = 0; i < n; i++)
+      {
+        const ListPlanItem &it = items[idx[i]];
+        need.blocks += it.blocks; need.strips += it.strips;
+        if (job == kListShared || job == kListOwn) need.facBytes += it.facBytes;
+      }
+      list_needs_max(plan.most, need);
+      plan.mixed = plan.mixed || kind == kStepMixed;
+      plan.rated = plan.rated || (kind == kStepSame && own);
+    }
+    bool pair(const std::vector<size_t> &idx) const { return list_in_one_pair(EncodeShape(items[idx[0]].sizeX, items[idx[0]].sizeY), opt); }
+    // `chunk` images per step, in the order of idx; a (last) chunk of one is a single
+    void chunks_of(const std::vector<size_t> &idx, size_t chunk, bool own)
+    {
+      for (size_t i0 = 0, n; i0 < idx.size(); i0 += n)
+      {
+        n = idx.size() - i0 < chunk ? idx.size() - i0 : chunk;
+        step(n == 1 ? kStepSingle : kStepSame, own, &idx[i0], n);
+      }
+    }
+    // An encode of images of one shape, at a shared factor or (own) each at its own.  Own factors outside k_encode_list_rated's reach -- a list of one, no launch
+    // pair (partial edge blocks, the split path, the float stage inside the encode kernel), the accurate search --: sorted by factor (stable), every distinct value
+    // as a shared-factor list of its own.  Else singles in list order where there is no launch pair (or one image), else chunks of list_chunk -- a shared-factor list
+    // takes them under the accurate search too.  -> the list was cut in list order by the chunk rule (ListPlan::inPlace)
+    bool same_shape(std::vector<size_t> idx, bool own)
+    {
+      const size_t n = idx.size();
+      const bool pairs = n > 1 && pair(idx);
+      if (own && (!pairs || fast == 0))
+      {
+        std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return items[a].errorFactor < items[b].errorFactor; });
+        for (size_t g0 = 0, g1; g0 < n; g0 = g1)
+        {
+          for (g1 = g0; g1 < n && items[idx[g1]].errorFactor == items[idx[g0]].errorFactor;) g1++;
+          restart = true;
+          same_shape(std::vector<size_t>(idx.begin() + g0, idx.begin() + g1), false);
+        }
+        return false;
+      }
+      chunks_of(idx, pairs ? list_chunk((size_t)items[idx[0]].blocks, (size_t)items[idx[0]].strips, hook) : 1, own);
+      return pairs;
+    }
+    // The budget searches of images of one shape: chunks of list_chunk behind one shared probe grid each where the probe applies and there is something to share, else
+    // the single budget call each.  A chunk's final encode is same_shape on that chunk, at a shared factor where all its searches chose one value, else at own factors.
+    void budget_same(const std::vector<size_t> &idx)
+    {
+      const bool probes = idx.size() > 1 && pair(idx) && fast != 0;
+      chunks_of(idx, probes ? list_chunk((size_t)items[idx[0]].blocks, (size_t)items[idx[0]].strips, hook) : 1, false);
+    }
+    // An items entry.  The eligible items first, in list order: one alone is a single; of one shape (not the sizes: their probe takes any shapes as they come) the
+    // same-shape rule of the job; else chunks of list_chunk_end, a chunk of one being a single.  Then the others as singles, in list order.  The final encode of a
+    // budget's mixed chunk is this route (kListOwn) of that chunk.
+    void items_form(size_t count)
+    {
+      std::vector<size_t> shared, alone;
+      for (size_t i = 0; i < count; i++) (items[i].eligible ? shared : alone).push_back(i);
+      bool oneShape = job != kListSizes;
+      for (size_t i : shared) oneShape = oneShape && items[i].sizeX == items[shared[0]].sizeX && items[i].sizeY == items[shared[0]].sizeY;
+      if (shared.size() == 1) step(kStepSingle, false, &shared[0], 1);
+      else if (!shared.empty() && oneShape)
+      {
+        if (job == kListBudget) budget_same(shared);
+        else same_shape(shared, true);
+      }
+      else
+      {
+        std::vector<uint64_t> blocks, strips;
+        for (size_t i : shared) { blocks.push_back(items[i].blocks); strips.push_back(items[i].strips); }
+        for (size_t i0 = 0, i1; i0 < shared.size(); i0 = i1)
+        {
+          i1 = list_chunk_end(blocks.data(), strips.data(), shared.size(), i0, hook);
+          step(i1 - i0 == 1 ? kStepSingle : kStepMixed, true, &shared[i0], i1 - i0);
+        }
+      }
+      for (size_t i : alone) step(kStepSingle, false, &i, 1);
+    }
+  };
+
+  // sameShape: a same-shape entry (limg_hip_encode_stream_batch*, _budget_batch: one shape for the whole list; there is no such entry for the sizes), else an items
+  // entry (limg_hip_encode_stream_list, _budget_list, limg_hip_stream_sizes_list; their items carry own factors: not kListShared).  opt: what list_in_one_pair reads.
+  // hook: the test build's batch_chunk, 0 = none.
+  inline ListPlan list_route(const ListPlanItem *items, size_t count, ListJob job, bool sameShape, int fastBitCrushing, const limg_hip_options &opt, size_t hook)
+  {
+    ListRouter r = { items, job, fastBitCrushing, opt, hook };
+    if (count == 0) return r.plan;
+    if (!sameShape) r.items_form(count);
+    else
+    {
+      std::vector<size_t> all(count);
+      for (size_t i = 0; i < count; i++) all[i] = i;
+      if (job == kListBudget) r.budget_same(all);
+      else r.plan.inPlace = r.same_shape(all, job == kListOwn);
+    }
+    return r.plan;
   }
 }
 

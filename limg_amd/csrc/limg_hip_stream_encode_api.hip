@@ -2,8 +2,9 @@
 // limg_hip_encode_stream_budget, limg_hip_encode_stream_budget_batch, limg_hip_encode_stream_quality, limg_hip_encode_stream_quality_batch, limg_hip_encode_stream_list
 // (a list of mixed shapes), limg_hip_encode_stream_quality_list, limg_hip_encode_stream_budget_list and limg_hip_stream_sizes_list, each with its _device form.  The 8x8 encode in compact mode + the packer of limg_hip_stream.hip; the size probe's kernels are limg_hip_rate.hip, the search limg_hip_rate_step.h; the quality
 // entries measure with the error windows of limg_hip_stream_window_api.hip and search with limg_hip_quality_step.h.  What the twenty-four entries do alike -- a call's shape,
-// the argument checks, a list's staging, the probe's parameters, the searches' enqueue, the results -- is written once, in the anonymous namespace below.  No kernel is
-// defined here.
+// the argument checks and how a list entry opens, a list's staging, the probe's parameters, the searches' enqueue, the results -- is written once, in the anonymous
+// namespace below.  Which launches a list takes is decided in limg_hip_list_plan.h (list_route) and nowhere here: encode_list, budget_list and sizes_list walk its
+// steps.  No kernel is defined here.
 #include "limg_hip_context.h"
 #include "limg_hip_quality_step.h"
 
@@ -26,9 +27,8 @@ namespace
         fixedBytes(sizeof(limg_hip_stream_header) + (uint64_t)blocks * sizeof(limg_hip_stream_block)) {}
   };
 
-  // lists in one launch pair and the probe kernel: list_in_one_pair -- and, the probe, the default search
-  bool batch_applies(const limg_hip_context *c, const StreamShape &sh) { return list_in_one_pair(sh, c->opt); }
-  bool rate_probe_applies(const limg_hip_context *c, const StreamShape &sh, int fast) { return batch_applies(c, sh) && fast != 0; }
+  // the probe kernel of one image: where a list goes in one launch pair (list_in_one_pair), under the default search
+  bool rate_probe_applies(const limg_hip_context *c, const StreamShape &sh, int fast) { return list_in_one_pair(sh, c->opt) && fast != 0; }
 
   // ---- argument checks, in the contract's order (include/limg_hip.h) ----
   // The single entries.  pointers: the entry's other pointers are all there.  dStream: a device form's stream buffer, which must hold the bound and be 16-byte aligned.
@@ -67,6 +67,42 @@ namespace
     return limg_hip_success;
   }
 
+  // The items as the caller's array holds them (itemSize apart), checked in the contract's order.  deviceForm: the streams are device buffers.  streams == false:
+  // the call writes no stream (the sizes list) -- pStream and capacity are not read.
+  limg_hip_result check_items(const void *c, bool pointers, size_t count, const ListItem *pItems, size_t itemSize, bool deviceForm, std::vector<ListItem> &items,
+                              bool streams = true)
+  {
+    if (!c || !pItems || !pointers) return limg_hip_error_ArgumentNull;
+    if (itemSize < sizeof(ListItem)) return limg_hip_error_InvalidParameter;
+    items.resize(count);
+    for (size_t i = 0; i < count; i++)
+    {
+      memcpy(&items[i], (const uint8_t *)pItems + i * itemSize, sizeof(ListItem));
+      const ListItem &it = items[i];
+      if (!it.pIn || (streams && !it.pStream)) return limg_hip_error_ArgumentNull;
+      const size_t bound = (it.sizeX && it.sizeY) ? limg_hip_stream_bound(it.sizeX, it.sizeY) : 0;
+      if (bound == 0) return limg_hip_error_InvalidParameter;
+      if (streams && deviceForm && ((uintptr_t)it.pStream & 15u) != 0) return limg_hip_error_InvalidParameter;
+      if (streams && deviceForm && it.capacity < bound) return limg_hip_error_OutOfBounds;
+      if (it.reserved != 0) return limg_hip_error_InvalidParameter;
+    }
+    return limg_hip_success;
+  }
+
+  // ---- how every list entry opens: the list's own checks (check_list / check_items, its form's rule), the search's (search(count) -> its result; no_search where
+  // there is none), then an empty list -- success with nothing done -- and a count beyond 31 bits.  go: the entry has work to do; else it returns the result ----
+  limg_hip_result no_search(size_t) { return limg_hip_success; }
+  template <class SEARCH>
+  limg_hip_result open_list(limg_hip_result listChecks, size_t count, SEARCH &&search, bool &go)
+  {
+    go = false;
+    limg_hip_result r = listChecks;
+    if (r != limg_hip_success || (r = search(count)) != limg_hip_success || count == 0) return r;
+    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    go = true;
+    return limg_hip_success;
+  }
+
   // (the caller's struct_size may be larger than ours: only the members are written)
   void fill_result(limg_hip_budget_result &res, uint32_t ef, uint32_t probes, uint32_t within, uint64_t bytes) { res.errorFactor = ef; res.probes = probes; res.withinBudget = within; res.bytes = bytes; }
   void fill_result(limg_hip_quality_result &res, uint32_t ef, uint32_t probes, uint32_t within, uint64_t bytes, uint64_t errorSum)
@@ -94,10 +130,12 @@ namespace
   }
 
   // ---- a list, whichever way it came: items.  A same-shape list (ppIn, ppStreams, one shape, capacityEach) as items, and items as the arrays a same-shape entry takes ----
-  std::vector<ListItem> as_items(size_t n, const uint32_t *const *ppIn, uint8_t *const *ppStreams, size_t capacityEach, size_t sizeX, size_t sizeY)
+  // (efs: one error factor per image, else errorFactor for all)
+  std::vector<ListItem> as_items(size_t n, const uint32_t *const *ppIn, uint8_t *const *ppStreams, size_t capacityEach, size_t sizeX, size_t sizeY, uint32_t errorFactor = 0,
+                                 const uint32_t *efs = nullptr)
   {
     std::vector<ListItem> items(n);
-    for (size_t i = 0; i < n; i++) items[i] = { ppIn[i], ppStreams[i], (uint64_t)capacityEach, (uint32_t)sizeX, (uint32_t)sizeY, 0u, 0u };
+    for (size_t i = 0; i < n; i++) items[i] = { ppIn[i], ppStreams[i], (uint64_t)capacityEach, (uint32_t)sizeX, (uint32_t)sizeY, efs ? efs[i] : errorFactor, 0u };
     return items;
   }
   struct ItemArrays
@@ -310,134 +348,288 @@ namespace
     return download_sizes(c->stream.sizes.p, count, pBytes, s);
   }
 
-  // ---- a list of same-shape images to streams: what the batch entries do, with one error factor (efs == NULL) or one per image (efs: host, count) ----
-  // The images of [0, n) sorted by error factor, one existing call per distinct value -- the single call for a group of one, the shared-factor batch otherwise:
-  // what a list with one factor per image falls back to where k_encode_list_rated does not apply.  The same bytes.
-  limg_hip_result encode_grouped(limg_hip_context *c, size_t n, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha, uint8_t *const *ppStreams,
-                                 size_t capacityEach, const uint32_t *efs, int poolThreads, int fastBitCrushing, void *stream)
+  // ---- the lists' routes.  limg_hip_list_plan.h decides (list_route: which items take which launches, in which order, what restarts the statistics, what the
+  // largest chunk needs); the walkers -- encode_list here, budget_list and sizes_list below -- grow what the plan's `most` says, loop over its steps and finish with
+  // the sizes or the results.  They decide nothing.  Their lists are checked, not empty, and counted in 31 bits (open_list) ----
+  ListPlan route(const limg_hip_context *c, const std::vector<ListItem> &items, ListJob job, bool sameShape, int fastBitCrushing)
   {
-    std::vector<uint32_t> order(n); // the images sorted by their error factor
-    std::vector<const uint32_t *> groupIn;
-    std::vector<uint8_t *> groupOut;
-    for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return efs[a] < efs[b]; });
-    limg_hip_result r = limg_hip_success;
-    for (size_t g0 = 0; g0 < n;)
-    {
-      const uint32_t ef = efs[order[g0]];
-      size_t g1 = g0;
-      groupIn.clear(); groupOut.clear();
-      for (; g1 < n && efs[order[g1]] == ef; g1++) { groupIn.push_back(ppIn[order[g1]]); groupOut.push_back(ppStreams[order[g1]]); }
-      if (g1 - g0 == 1) r = limg_hip_encode_stream_device(c, groupIn[0], sizeX, sizeY, hasAlpha, groupOut[0], capacityEach, nullptr, ef, poolThreads, fastBitCrushing, stream);
-      else r = limg_hip_encode_stream_batch_device(c, g1 - g0, groupIn.data(), sizeX, sizeY, hasAlpha, groupOut.data(), capacityEach, nullptr, ef, poolThreads, fastBitCrushing,
-                                                   stream);
-      if (r != limg_hip_success) return r;
-      g0 = g1;
-    }
-    return r;
+    std::vector<ListPlanItem> in(items.size());
+    for (size_t i = 0; i < items.size(); i++) in[i] = list_plan_item(items[i].sizeX, items[i].sizeY, items[i].errorFactor, fastBitCrushing, c->opt);
+    return list_route(in.data(), in.size(), job, sameShape, fastBitCrushing, c->opt, batch_hook(c));
+  }
+  // a step's items, in the step's order
+  std::vector<ListItem> step_items(const std::vector<ListItem> &items, const ListPlan &plan, const ListStep &st)
+  {
+    std::vector<ListItem> its(st.count);
+    for (size_t k = 0; k < st.count; k++) its[k] = items[plan.order[st.first + k]];
+    return its;
   }
 
-  // Lists of whole-block images go chunk by chunk (the plane batch's rule) through ONE compact-mode batched encode -- records, shift words and the strips' payload
-  // words in the context's raster arrays, image after image; the factor planes in per-image slices of stream.fac -- and one scan + one pack launch over the chunk.
-  // With efs the chunk's encode is k_encode_list_rated's (thresholds per image from a device table) and the scan writes every header's own error factor.
-  // pointers: the entry's other pointers (pErrorFactors) are there.  ratedStorage: device memory for the threshold table of a chunk (32 bytes per image) where the
-  // caller has some to spare -- the budgeted list's search states, which its searches are done with --, else the context's own (stream.rated).
-  limg_hip_result stream_list_device(limg_hip_context *c, bool pointers, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
-                                     uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, const uint32_t *efs, int poolThreads,
-                                     int fastBitCrushing, void *stream, RatedImage *ratedStorage = nullptr)
+  // One chunk of n > 1 images of one shape: ONE compact-mode batched encode -- records, shift words and the strips' payload words in the context's raster arrays,
+  // image after image; the factor planes in per-image slices of stream.fac -- and one scan + one pack launch over the chunk.  own: the encode is
+  // k_encode_list_rated's (thresholds per image from a device table: `rated`, 32 bytes per image) and the scan writes every header's own error factor; else the
+  // chunk shares its first image's.  table: the chunk's n entries of the streams' table.  Everything it needs has been grown by the caller.
+  limg_hip_result same_chunk(limg_hip_context *c, const ListItem *its, size_t n, bool own, RatedImage *rated, StreamImage *table, int hasAlpha, int poolThreads,
+                             int fastBitCrushing, hipStream_t s)
   {
-    const StreamShape sh(sizeX, sizeY);
-    limg_hip_result r;
-    if ((r = check_list(c, pointers, count, ppIn, ppStreams, sh, capacityEach, true)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    const StreamShape sh(its[0].sizeX, its[0].sizeY);
+    std::vector<ImageIO> io(n, ImageIO{});
+    std::vector<StreamImage> images(n);
+    std::vector<uint32_t> efs(n);
+    for (size_t i = 0; i < n; i++)
+    {
+      uint8_t *fac = (uint8_t *)c->stream.fac.p + i * 3 * sh.planeStride; // 256-byte aligned slices
+      io[i].in = its[i].pIn;
+      io[i].info.pFactorsA = fac; io[i].info.pFactorsB = fac + sh.planeStride; io[i].info.pFactorsC = fac + 2 * sh.planeStride;
+      images[i].stream = its[i].pStream;
+      images[i].fac[0] = fac; images[i].fac[1] = fac + sh.planeStride; images[i].fac[2] = fac + 2 * sh.planeStride;
+      efs[i] = its[i].errorFactor;
+    }
+    limg_hip_compact_out comp = { (limg_hip_block_record *)c->enc.records.p, (uint32_t *)c->enc.shifts.p };
+    EncodeExtra x;
+    x.batch = io.data(); x.batchCount = n;
+    x.streamRaw = true; x.stripWords = (uint32_t *)c->stream.units.p;
+    if (own) { x.errorFactors = efs.data(); x.ratedTable = rated; }
+    const limg_hip_result r = encode_device(c, its[0].pIn, sh.sizeX, sh.sizeY, hasAlpha, &io[0].info, &comp, efs[0], poolThreads, fastBitCrushing, s, x);
+    if (r != limg_hip_success) return r;
+    launch_set_stream_table(table, images.data(), n, s);
+    StreamBatchParams b;
+    memset(&b, 0, sizeof(b));
+    b.sizeX = (uint32_t)sh.sizeX; b.sizeY = (uint32_t)sh.sizeY; b.blocksX = (uint32_t)sh.blocksX; b.blocksY = (uint32_t)sh.blocksY; b.nBlocks = (uint32_t)sh.blocks;
+    b.channels = hasAlpha ? 4 : 3; b.errorFactor = efs[0]; b.flags = stream_flags(c, fastBitCrushing);
+    b.stripsX = (uint32_t)sh.stripsX; b.imageStrips = (uint32_t)sh.strips; b.nImages = (uint32_t)n; b.nStrips = (uint32_t)(n * sh.strips);
+    b.nWaves = pack_waves(c, n * sh.strips); // as the single call -- for the whole chunk
+    b.images = table;
+    b.records = comp.pRecords; b.shifts = comp.pShifts; b.stripWords = (uint32_t *)c->stream.units.p;
+    b.rated = own ? rated : nullptr; // (the chunk's table, as the encode just wrote it)
+    Timeline tl(c, s, 4); // {scan + pack of the chunk, -, -}
+    tl.mark();
+    launch_stream_pack_batch(b, s);
+    tl.close();
+    HIP_TRY(hipGetLastError());
+    return limg_hip_success;
+  }
+
+  // One chunk of eligible items of more than one shape: the images' factor planes in slices of stream.fac, the chunk's table block with this layer's part of it
+  // (the StreamImage entries), the encode layer's launch pair on them (encode_list_chunk), ONE scan, ONE pack.  Everything it needs has been grown by the caller.
+  limg_hip_result mixed_chunk(limg_hip_context *c, const ListItem *its, size_t n, int hasAlpha, int poolThreads, int fastBitCrushing, hipStream_t s)
+  {
+    const ChunkTables T = chunk_tables(n);
+    std::vector<uint8_t> host(T.bytes, 0);
+    uint8_t *const dev = (uint8_t *)c->stream.listTable.p;
+    StreamImage *streams = (StreamImage *)(host.data() + T.streams);
+    std::vector<ListChunkImage> images(n);
+    size_t facAt = 0;
+    for (size_t i = 0; i < n; i++)
+    {
+      const ListItem &it = its[i];
+      images[i].in = it.pIn; images[i].sizeX = it.sizeX; images[i].sizeY = it.sizeY; images[i].errorFactor = it.errorFactor;
+      for (int k = 0; k < 3; k++) { streams[i].fac[k] = images[i].fac[k] = (uint8_t *)c->stream.fac.p + facAt; facAt += list_plane_stride(it.sizeX, it.sizeY); }
+      streams[i].stream = it.pStream;
+    }
+    uint32_t *const stripWords = (uint32_t *)c->stream.units.p;
+    ListChunkTotals tot;
+    const limg_hip_result r = encode_list_chunk(c, images.data(), n, hasAlpha, poolThreads, stripWords, host.data(), dev, s, tot);
+    if (r != limg_hip_success) return r;
+    StreamListParams b;
+    memset(&b, 0, sizeof(b));
+    b.images = (const ListImage *)(dev + T.images); b.streams = (const StreamImage *)(dev + T.streams); b.rated = (const RatedImage *)(dev + T.rated); b.firstStrip = (const uint32_t *)(dev + T.firstStrip);
+    b.nImages = (uint32_t)n; b.nStrips = tot.strips; b.nWaves = pack_waves(c, tot.strips);
+    b.channels = hasAlpha ? 4u : 3u; b.flags = stream_flags(c, fastBitCrushing);
+    b.records = (const limg_hip_block_record *)c->enc.records.p; b.shifts = (const uint32_t *)c->enc.shifts.p; b.stripWords = stripWords;
+    Timeline tl(c, s, 4); // {scan + pack of the chunk, -, -}
+    tl.mark();
+    launch_stream_pack_list(b, s);
+    tl.close();
+    HIP_TRY(hipGetLastError());
+    return limg_hip_success;
+  }
+
+  // The encode of a list, item i at its own errorFactor (job: kListShared -- they are all the same -- or kListOwn), stream i what the single call writes for item i.
+  // sameShape: a same-shape entry's list.  ratedStorage: device memory for the threshold table of an own-factor chunk (32 bytes per image) where the caller has some
+  // to spare -- the budgeted list's search states, which its searches are done with --, else the context's own (stream.rated).  Everything the largest chunk needs
+  // is there before the first launch: nothing is grown (and so freed) between the steps of a list.  limg_hip_last_stats: as the plan's `restart` says.
+  limg_hip_result encode_list(limg_hip_context *c, const std::vector<ListItem> &items, ListJob job, bool sameShape, int hasAlpha, size_t *pBytes, int poolThreads,
+                              int fastBitCrushing, void *stream, RatedImage *ratedStorage = nullptr)
+  {
+    const size_t count = items.size();
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const size_t chunk = list_chunk(c, sh.blocks, sh.strips);
-    // one factor per image outside the rated kernel's reach (partial edge blocks, the split path, the float stage inside the encode kernel, the accurate search, a
-    // list of one): one existing call per distinct factor
-    const bool grouped = efs && (count == 1 || !batch_applies(c, sh) || fastBitCrushing == 0);
-    const bool oneByOne = grouped || count == 1 || !batch_applies(c, sh);
-    const size_t most = oneByOne ? 1 : (count < chunk ? count : chunk); // images of the largest chunk
+    const ListPlan plan = route(c, items, job, sameShape, fastBitCrushing);
+    const ListNeeds &most = plan.most;
+    limg_hip_result r;
     if ((r = c->stream.table.ensure(count * sizeof(StreamImage))) != limg_hip_success) return r;
-    if (most > 1)
-    { // everything a chunk needs, before the first launch: nothing is grown (and so freed) between the chunks of a list
-      if ((r = c->stream.fac.ensure(most * sh.planeStride * 3)) != limg_hip_success) return r;
-      if ((r = c->stream.units.ensure(most * sh.strips * 4)) != limg_hip_success) return r;
-      if ((r = c->enc.records.ensure(most * sh.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
-      if ((r = c->enc.shifts.ensure(most * sh.blocks * 4)) != limg_hip_success) return r;
-      if (efs && !ratedStorage)
+    if (most.images > 1)
+    {
+      PersistentScratch ps;
+      if (plan.mixed && (r = c->stream.listTable.ensure(chunk_tables(most.images).bytes)) != limg_hip_success) return r;
+      if ((r = c->stream.fac.ensure(most.facBytes)) != limg_hip_success) return r;
+      if ((r = c->stream.units.ensure((size_t)most.strips * 4)) != limg_hip_success) return r;
+      if ((r = c->enc.records.ensure((size_t)most.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+      if ((r = c->enc.shifts.ensure((size_t)most.blocks * 4)) != limg_hip_success) return r;
+      if (plan.mixed && (r = c->enc.invN.ensure((size_t)most.blocks * 16)) != limg_hip_success) return r;
+      if (plan.mixed && (r = persistent_scratch(c, (size_t)most.strips, 2, s, ps)) != limg_hip_success) return r;
+      if (plan.rated && !ratedStorage)
       {
-        if ((r = c->stream.rated.ensure(most * sizeof(RatedImage))) != limg_hip_success) return r;
+        if ((r = c->stream.rated.ensure(most.images * sizeof(RatedImage))) != limg_hip_success) return r;
         ratedStorage = (RatedImage *)c->stream.rated.p;
       }
     }
-    std::vector<StreamImage> images(count);
-    for (size_t i = 0; i < count; i++) images[i].stream = ppStreams[i];
-    std::vector<ImageIO> table;
-    if (grouped) r = encode_grouped(c, count, ppIn, sizeX, sizeY, hasAlpha, ppStreams, capacityEach, efs, poolThreads, fastBitCrushing, stream);
-    for (size_t i0 = 0; !grouped && i0 < count && r == limg_hip_success;)
+    std::vector<StreamImage> images(count); // the streams in list order, for the sizes
+    for (size_t i = 0; i < count; i++) images[i].stream = items[i].pStream;
+    StreamImage *const table = (StreamImage *)c->stream.table.p;
+    for (const ListStep &st : plan.steps)
     {
-      const size_t n = oneByOne ? 1 : (count - i0 < chunk ? count - i0 : chunk);
-      c->stats.accumulate = i0 != 0; // limg_hip_last_stats: all images of the list together, as the plane batch
-      if (n == 1)
-      { // the single call (images with partial edge blocks, the split path, the float stage inside the encode kernel, a list or a last chunk of one image)
-        r = limg_hip_encode_stream_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, ppStreams[i0], capacityEach, nullptr, efs ? efs[i0] : errorFactor, poolThreads, fastBitCrushing,
-                                          stream);
-        if (r == limg_hip_success && pBytes && !oneByOne) launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], 1, s); // (for the sizes below)
-      }
-      else
+      const size_t i = plan.order[st.first];
+      c->stats.accumulate = !st.restart;
+      if (st.kind == kStepSingle)
       {
-        table.assign(n, ImageIO{});
-        for (size_t i = 0; i < n; i++)
-        {
-          uint8_t *fac = (uint8_t *)c->stream.fac.p + i * 3 * sh.planeStride; // 256-byte aligned slices
-          table[i].in = ppIn[i0 + i];
-          table[i].info.pFactorsA = fac; table[i].info.pFactorsB = fac + sh.planeStride; table[i].info.pFactorsC = fac + 2 * sh.planeStride;
-          images[i0 + i].fac[0] = fac; images[i0 + i].fac[1] = fac + sh.planeStride; images[i0 + i].fac[2] = fac + 2 * sh.planeStride;
-        }
-        limg_hip_compact_out comp = { (limg_hip_block_record *)c->enc.records.p, (uint32_t *)c->enc.shifts.p };
-        EncodeExtra x;
-        x.batch = table.data(); x.batchCount = n;
-        x.streamRaw = true; x.stripWords = (uint32_t *)c->stream.units.p;
-        if (efs) { x.errorFactors = efs + i0; x.ratedTable = ratedStorage; }
-        if ((r = encode_device(c, ppIn[i0], sizeX, sizeY, hasAlpha, &table[0].info, &comp, efs ? efs[i0] : errorFactor, poolThreads, fastBitCrushing, s, x)) != limg_hip_success) break;
-        launch_set_stream_table((StreamImage *)c->stream.table.p + i0, &images[i0], n, s);
-        StreamBatchParams b;
-        memset(&b, 0, sizeof(b));
-        b.sizeX = (uint32_t)sizeX; b.sizeY = (uint32_t)sizeY; b.blocksX = (uint32_t)sh.blocksX; b.blocksY = (uint32_t)sh.blocksY; b.nBlocks = (uint32_t)sh.blocks;
-        b.channels = hasAlpha ? 4 : 3; b.errorFactor = errorFactor; b.flags = stream_flags(c, fastBitCrushing);
-        b.stripsX = (uint32_t)sh.stripsX; b.imageStrips = (uint32_t)sh.strips; b.nImages = (uint32_t)n; b.nStrips = (uint32_t)(n * sh.strips);
-        b.nWaves = pack_waves(c, n * sh.strips); // as the single call -- for the whole chunk
-        b.images = (const StreamImage *)c->stream.table.p + i0;
-        b.records = comp.pRecords; b.shifts = comp.pShifts; b.stripWords = (uint32_t *)c->stream.units.p;
-        b.rated = efs ? ratedStorage : nullptr; // (the chunk's table, as the encode just wrote it)
-        Timeline tl(c, s, 4); // {scan + pack of the chunk, -, -}
-        tl.mark();
-        launch_stream_pack_batch(b, s);
-        tl.close();
-        const hipError_t launched = hipGetLastError();
-        if (launched != hipSuccess) { c->stats.accumulate = false; HIP_TRY(launched); }
+        const ListItem &it = items[i];
+        r = limg_hip_encode_stream_device(c, it.pIn, it.sizeX, it.sizeY, hasAlpha, it.pStream, (size_t)it.capacity, nullptr, it.errorFactor, poolThreads, fastBitCrushing, stream);
+        if (r == limg_hip_success && pBytes && plan.inPlace) launch_set_stream_table(table + i, &images[i], 1, s); // (for the sizes below)
       }
-      i0 += n;
+      else if (st.kind == kStepSame) // (its table entries: at the step's place in the plan's order, which under inPlace is the list's)
+        r = same_chunk(c, step_items(items, plan, st).data(), st.count, st.own, ratedStorage, table + st.first, hasAlpha, poolThreads, fastBitCrushing, s);
+      else r = mixed_chunk(c, step_items(items, plan, st).data(), st.count, hasAlpha, poolThreads, fastBitCrushing, s);
+      if (r != limg_hip_success) break;
     }
     c->stats.accumulate = false;
     if (r != limg_hip_success || !pBytes) return r;
-    return list_bytes(c, oneByOne ? images.data() : nullptr, count, pBytes, s);
+    return list_bytes(c, plan.inPlace ? nullptr : images.data(), count, pBytes, s);
   }
 
-  // the host form: upload, stream_list_device on the null stream, status, the streams down at their own sizes (capacityEach holds the bound: every stream fits)
+  // ---- the same-shape encode entries, with one error factor (efs == NULL) or one per image (efs: host, count).  pointers: the entry's other pointers are there ----
+  limg_hip_result stream_list_device(limg_hip_context *c, bool pointers, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
+                                     uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, const uint32_t *efs, int poolThreads,
+                                     int fastBitCrushing, void *stream)
+  {
+    bool go;
+    const limg_hip_result r = open_list(check_list(c, pointers, count, ppIn, ppStreams, StreamShape(sizeX, sizeY), capacityEach, true), count, no_search, go);
+    if (!go) return r;
+    return encode_list(c, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY, errorFactor, efs), efs ? kListOwn : kListShared, true, hasAlpha, pBytes, poolThreads,
+                       fastBitCrushing, stream);
+  }
+  // the host form: upload, encode_list on the null stream, status, the streams down at their own sizes (capacityEach holds the bound: every stream fits)
   limg_hip_result stream_list_host(limg_hip_context *c, bool pointers, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
                                    uint8_t *const *ppStreams, size_t capacityEach, size_t *pBytes, uint32_t errorFactor, const uint32_t *efs, int poolThreads, int fastBitCrushing)
   {
-    const StreamShape sh(sizeX, sizeY);
-    limg_hip_result r;
-    if ((r = check_list(c, pointers && pBytes != nullptr, count, ppIn, ppStreams, sh, capacityEach, false)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    return host_list(c, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY), pBytes, pBytes, [&](const std::vector<ListItem> &staged) {
-      const ItemArrays a(staged);
-      return stream_list_device(c, true, count, a.in.data(), sizeX, sizeY, hasAlpha, a.streams.data(), a.capacityEach, pBytes, errorFactor, efs, poolThreads, fastBitCrushing, nullptr);
+    bool go;
+    const limg_hip_result r = open_list(check_list(c, pointers && pBytes != nullptr, count, ppIn, ppStreams, StreamShape(sizeX, sizeY), capacityEach, false), count, no_search, go);
+    if (!go) return r;
+    return host_list(c, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY, errorFactor, efs), pBytes, pBytes, [&](const std::vector<ListItem> &staged) {
+      return encode_list(c, staged, efs ? kListOwn : kListShared, true, hasAlpha, pBytes, poolThreads, fastBitCrushing, nullptr);
     });
+  }
+
+  // ---- the byte budget and the size probe of a list (kernels: limg_hip_rate.hip -- of a mixed chunk k_rate_probe_list and the _batch begin / step with the chunk's
+  // ListImage table) ----
+  // everything the probes of the largest mixed chunk need, before the first launch: the tables, the fit grid's records, invN and look-back words, one state and one
+  // counter per image
+  limg_hip_result grow_list_probe(limg_hip_context *c, const ListNeeds &most)
+  {
+    limg_hip_result r;
+    if ((r = c->stream.listTable.ensure(chunk_tables(most.images).bytes)) != limg_hip_success) return r;
+    if ((r = c->enc.records.ensure((size_t)most.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
+    if ((r = c->enc.invN.ensure((size_t)most.blocks * 16)) != limg_hip_success) return r;
+    if ((r = c->enc.lookback.ensure(16 * 2 + (size_t)most.strips * 8)) != limg_hip_success) return r;
+    if ((r = c->stream.rateState.ensure(most.images * sizeof(RateDevice))) != limg_hip_success) return r;
+    return c->stream.rateCounter.ensure(most.images * 8);
+  }
+
+  // The budgeted list: result i and stream i the single budget call's for item i with pMaxBytes[i].  A chunk's records come from ONE grid (k_fit_tpb for one shape,
+  // k_fit_tpb_list for a mixed chunk), its searches are 1 + 2 x rate_max_probes launches with ONE download and ONE wait; then the chunk is ONE list encode at the
+  // error factors the searches chose -- encode_list on the chunk (it runs its own float stage: reusing the probe's records is a follow-up), whose statistics are
+  // those limg_hip_last_stats reports.
+  limg_hip_result budget_list(limg_hip_context *c, const std::vector<ListItem> &items, bool sameShape, int hasAlpha, const size_t *pMaxBytes, uint32_t minErrorFactor,
+                              uint32_t maxErrorFactor, uint32_t hLo, uint32_t hHi, int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults, void *stream)
+  {
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const ListPlan plan = route(c, items, kListBudget, sameShape, fastBitCrushing);
+    limg_hip_result r;
+    if (plan.mixed && (r = grow_list_probe(c, plan.most)) != limg_hip_success) return r;
+    std::vector<RateDevice> states;
+    std::vector<size_t> budgets;
+    for (const ListStep &st : plan.steps)
+    {
+      const size_t *idx = &plan.order[st.first], m = st.count;
+      if (st.kind == kStepSingle)
+      {
+        const ListItem &it = items[idx[0]];
+        if ((r = limg_hip_encode_stream_budget_device(c, it.pIn, it.sizeX, it.sizeY, hasAlpha, it.pStream, (size_t)it.capacity, pMaxBytes[idx[0]], minErrorFactor, maxErrorFactor,
+                                                      poolThreads, fastBitCrushing, &pResults[idx[0]], stream)) != limg_hip_success)
+          return r;
+        continue;
+      }
+      // 1. + 2. the chunk's records and its searches
+      std::vector<ListItem> its = step_items(items, plan, st);
+      states.resize(m); budgets.resize(m);
+      for (size_t k = 0; k < m; k++) budgets[k] = pMaxBytes[idx[k]];
+      Probe pr;
+      if (st.kind == kStepMixed) r = list_probe_setup(c, its.data(), m, hasAlpha, poolThreads, s, pr);
+      else r = probe_setup(c, StreamShape(its[0].sizeX, its[0].sizeY), ItemArrays(its).in.data(), m, hasAlpha, poolThreads, s, pr);
+      if (r != limg_hip_success || (r = run_searches(pr, budgets.data(), hLo, hHi, s, states.data())) != limg_hip_success) return r;
+      // 3. the final encodes, whatever the searches chose: the chunk as a list at the chosen factors.  One shape: thresholds per image, or, where all chose the same
+      // value, the shared-factor list, whose thresholds are kernel arguments; the threshold table -- 32 bytes per image -- in the chunk's search states -- 72 per
+      // image --, which are on the host by now: no context memory of its own
+      static_assert(sizeof(RatedImage) <= sizeof(RateDevice), "the threshold table fits the search states");
+      bool same = true;
+      for (size_t k = 0; k < m; k++) { its[k].errorFactor = 2u * states[k].search.next; same = same && its[k].errorFactor == its[0].errorFactor; }
+      if (st.kind == kStepMixed) r = encode_list(c, its, kListOwn, false, hasAlpha, nullptr, poolThreads, fastBitCrushing, stream);
+      else r = encode_list(c, its, same ? kListShared : kListOwn, true, hasAlpha, nullptr, poolThreads, fastBitCrushing, stream, (RatedImage *)c->stream.rateState.p);
+      if (r != limg_hip_success) return r;
+      for (size_t k = 0; k < m; k++) // bytes: what the probe measured at the result -- the packer's totalBytes
+        fill_result(pResults[idx[k]], its[k].errorFactor, states[k].search.probes, states[k].search.within, states[k].search.bestBytes);
+    }
+    return limg_hip_success;
+  }
+
+  // The sizes of every item at every factor (factorCount in 1 .. 2^31 - 1): pBytes[i * factorCount + k].  Per mixed chunk ONE k_fit_tpb_list grid, one begin,
+  // factorCount pairs of k_rate_probe_list and the list form of the step, ONE download and ONE wait.  The single call is limg_hip_stream_sizes_device, which has its
+  // own fallback.
+  limg_hip_result sizes_list(limg_hip_context *c, const std::vector<ListItem> &items, int hasAlpha, const uint32_t *pErrorFactors, size_t factorCount, size_t *pBytes,
+                             int poolThreads, int fastBitCrushing, void *stream)
+  {
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const ListPlan plan = route(c, items, kListSizes, false, fastBitCrushing);
+    limg_hip_result r;
+    if (plan.mixed)
+    {
+      if ((r = grow_list_probe(c, plan.most)) != limg_hip_success) return r;
+      if ((r = c->stream.rateList.ensure(plan.most.images * factorCount * 8 + factorCount * 4)) != limg_hip_success) return r;
+    }
+    const std::vector<uint32_t> list(pErrorFactors, pErrorFactors + factorCount); // (the caller's array may be pageable and may die when the call returns)
+    std::vector<size_t> sizes;
+    for (const ListStep &st : plan.steps)
+    {
+      const size_t *idx = &plan.order[st.first], m = st.count;
+      if (st.kind == kStepSingle)
+      {
+        const ListItem &it = items[idx[0]];
+        if ((r = limg_hip_stream_sizes_device(c, it.pIn, it.sizeX, it.sizeY, hasAlpha, pErrorFactors, factorCount, pBytes + idx[0] * factorCount, poolThreads, fastBitCrushing,
+                                              stream)) != limg_hip_success)
+          return r;
+        continue;
+      }
+      Probe pr;
+      if ((r = list_probe_setup(c, step_items(items, plan, st).data(), m, hasAlpha, poolThreads, s, pr)) != limg_hip_success) return r;
+      unsigned long long *dBytes = (unsigned long long *)c->stream.rateList.p;
+      uint32_t *dList = (uint32_t *)(dBytes + m * factorCount);
+      HIP_TRY(hipMemcpyAsync(dList, list.data(), factorCount * 4, hipMemcpyHostToDevice, s));
+      launch_rate_begin_batch(pr.states, pr.counters, nullptr, m, 0, 0, s, dList);
+      for (size_t k = 0; k < factorCount; k++)
+      {
+        pr.launch(s);
+        pr.step(s, dList, dBytes, (uint32_t)factorCount);
+      }
+      HIP_TRY(hipGetLastError());
+      sizes.resize(m * factorCount);
+      if ((r = download_sizes(dBytes, m * factorCount, sizes.data(), s)) != limg_hip_success) return r; // (its wait also: `list` is no longer read by this chunk)
+      for (size_t k = 0; k < m; k++)
+        for (size_t f = 0; f < factorCount; f++) pBytes[idx[k] * factorCount + f] = sizes[k * factorCount + f];
+    }
+    return limg_hip_success;
   }
 }
 
@@ -540,15 +732,14 @@ extern "C"
   limg_hip_result limg_hip_stream_sizes(limg_hip_context *c, const uint32_t *pIn, size_t sizeX, size_t sizeY, int hasAlpha, const uint32_t *pErrorFactors, size_t count,
                                         size_t *pBytes, int poolThreads, int fastBitCrushing)
   {
-    const StreamShape sh(sizeX, sizeY);
     limg_hip_result r;
-    if ((r = check_single(c, pIn, pErrorFactors && pBytes, sh)) != limg_hip_success) return r;
+    if ((r = check_single(c, pIn, pErrorFactors && pBytes, StreamShape(sizeX, sizeY))) != limg_hip_success) return r;
     if (count == 0) return limg_hip_success;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
-    HIP_TRY(hipSetDevice(c->device));
-    if ((r = c->host.in.ensure(sh.px * 4)) != limg_hip_success) return r;
-    HIP_TRY(hipMemcpy(c->host.in.p, pIn, sh.px * 4, hipMemcpyHostToDevice));
-    r = limg_hip_stream_sizes_device(c, (const uint32_t *)c->host.in.p, sizeX, sizeY, hasAlpha, pErrorFactors, count, pBytes, poolThreads, fastBitCrushing, nullptr);
+    uint8_t *const noStream = nullptr;
+    std::vector<ListItem> staged;
+    if ((r = stage_inputs(c, as_items(1, &pIn, &noStream, 0, sizeX, sizeY), staged)) != limg_hip_success) return r;
+    r = limg_hip_stream_sizes_device(c, staged[0].pIn, sizeX, sizeY, hasAlpha, pErrorFactors, count, pBytes, poolThreads, fastBitCrushing, nullptr);
     return r != limg_hip_success ? r : limg_hip_check_device_status(c);
   }
 
@@ -632,72 +823,32 @@ extern "C"
     return stream_list_host(c, pErrorFactors != nullptr, count, ppIn, sizeX, sizeY, hasAlpha, ppStreams, capacityEach, pBytes, 0, pErrorFactors, poolThreads, fastBitCrushing);
   }
 
-  // ---- budgeted stream encode of a list: result i = limg_hip_encode_stream_budget_device of image i with pMaxBytes[i] (contract: include/limg_hip.h) ----
-  // Chunk by chunk (the plane batch's rule): the records of the chunk from ONE k_fit_tpb grid, one search state and one counter per image, the whole chunk's searches
-  // as 1 + 2 x rate_max_probes launches and ONE wait; then the chunk's stream encode at the error factors the searches chose, as one list.
+  // ---- budgeted stream encode of a list: result i = limg_hip_encode_stream_budget_device of image i with pMaxBytes[i] (contract: include/limg_hip.h; budget_list above) ----
   limg_hip_result limg_hip_encode_stream_budget_batch_device(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
                                                              uint8_t *const *ppStreams, size_t capacityEach, const size_t *pMaxBytes, uint32_t minErrorFactor,
                                                              uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults, void *stream)
   {
-    const StreamShape sh(sizeX, sizeY);
     uint32_t hLo, hHi;
-    limg_hip_result r;
-    if ((r = check_list(c, pMaxBytes && pResults, count, ppIn, ppStreams, sh, capacityEach, true)) != limg_hip_success) return r;
-    if ((r = check_search(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
-    HIP_TRY(hipSetDevice(c->device));
-    auto single = [&](size_t i) {
-      return limg_hip_encode_stream_budget_device(c, ppIn[i], sizeX, sizeY, hasAlpha, ppStreams[i], capacityEach, pMaxBytes[i], minErrorFactor, maxErrorFactor, poolThreads,
-                                                  fastBitCrushing, &pResults[i], stream);
-    };
-    // no probe kernel (or nothing to share): the loop of single calls, which a chunk (or a last chunk) of one image takes too
-    const size_t chunk = count == 1 || !rate_probe_applies(c, sh, fastBitCrushing) ? 1 : list_chunk(c, sh.blocks, sh.strips);
-    std::vector<RateDevice> states;
-    std::vector<uint32_t> efs; // the error factors the chunk's searches chose
-    for (size_t i0 = 0; i0 < count;)
-    {
-      const size_t n = count - i0 < chunk ? count - i0 : chunk;
-      if (n == 1)
-      {
-        if ((r = single(i0++)) != limg_hip_success) return r;
-        continue;
-      }
-      // 1. + 2. the chunk's records and its searches
-      states.resize(n);
-      if ((r = run_searches(c, sh, ppIn + i0, pMaxBytes + i0, n, hLo, hHi, hasAlpha, poolThreads, (hipStream_t)stream, states.data())) != limg_hip_success) return r;
-      // 3. the final encodes, in ONE launch pair + scan + pack whatever the searches chose: the chunk at the chosen factors, thresholds per image (where all chose
-      // the same value: the shared-factor batch, whose thresholds are kernel arguments)
-      efs.resize(n);
-      bool same = true;
-      for (size_t i = 0; i < n; i++) { efs[i] = 2u * states[i].search.next; same = same && efs[i] == efs[0]; }
-      // (the threshold table -- 32 bytes per image -- in the chunk's search states -- 72 per image --, which are on the host by now: no context memory of its own)
-      static_assert(sizeof(RatedImage) <= sizeof(RateDevice), "the threshold table fits the search states");
-      if ((r = stream_list_device(c, true, n, ppIn + i0, sizeX, sizeY, hasAlpha, ppStreams + i0, capacityEach, nullptr, efs[0], same ? nullptr : efs.data(), poolThreads,
-                                  fastBitCrushing, stream, (RatedImage *)c->stream.rateState.p)) != limg_hip_success)
-        return r;
-      for (size_t i = 0; i < n; i++) // bytes: what the probe measured at the result -- the packer's totalBytes
-        fill_result(pResults[i0 + i], 2u * states[i].search.next, states[i].search.probes, states[i].search.within, states[i].search.bestBytes);
-      i0 += n;
-    }
-    return limg_hip_success;
+    bool go;
+    const limg_hip_result r = open_list(check_list(c, pMaxBytes && pResults, count, ppIn, ppStreams, StreamShape(sizeX, sizeY), capacityEach, true), count,
+                                        [&](size_t n) { return check_search(n, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi); }, go);
+    if (!go) return r;
+    return budget_list(c, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY), true, hasAlpha, pMaxBytes, minErrorFactor, maxErrorFactor, hLo, hHi, poolThreads,
+                       fastBitCrushing, pResults, stream);
   }
 
   limg_hip_result limg_hip_encode_stream_budget_batch(limg_hip_context *c, size_t count, const uint32_t *const *ppIn, size_t sizeX, size_t sizeY, int hasAlpha,
                                                       uint8_t *const *ppStreams, size_t capacityEach, const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor,
                                                       int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults)
   {
-    const StreamShape sh(sizeX, sizeY);
     uint32_t hLo, hHi;
-    limg_hip_result r;
-    if ((r = check_list(c, pMaxBytes && pResults, count, ppIn, ppStreams, sh, SIZE_MAX, false)) != limg_hip_success) return r; // (capacityEach: the rule below)
-    if ((r = check_search(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
+    bool go; // (capacityEach: host_list's rule, behind the encode)
+    const limg_hip_result r = open_list(check_list(c, pMaxBytes && pResults, count, ppIn, ppStreams, StreamShape(sizeX, sizeY), SIZE_MAX, false), count,
+                                        [&](size_t n) { return check_search(n, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi); }, go);
+    if (!go) return r;
     std::vector<limg_hip_budget_result> results = own_results<limg_hip_budget_result>(count);
     return host_list(c, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY), results.data(), pResults, [&](const std::vector<ListItem> &staged) {
-      const ItemArrays a(staged);
-      return limg_hip_encode_stream_budget_batch_device(c, count, a.in.data(), sizeX, sizeY, hasAlpha, a.streams.data(), a.capacityEach, pMaxBytes, minErrorFactor, maxErrorFactor,
-                                                        poolThreads, fastBitCrushing, results.data(), nullptr);
+      return budget_list(c, staged, true, hasAlpha, pMaxBytes, minErrorFactor, maxErrorFactor, hLo, hHi, poolThreads, fastBitCrushing, results.data(), nullptr);
     });
   }
 }
@@ -823,13 +974,11 @@ extern "C"
                                                               uint8_t *const *ppStreams, size_t capacityEach, const uint64_t *pMaxErrorSums, uint32_t minErrorFactor,
                                                               uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing, limg_hip_quality_result *pResults, void *stream)
   {
-    const StreamShape sh(sizeX, sizeY);
     uint32_t hLo, hHi;
-    limg_hip_result r;
-    if ((r = check_list(c, pMaxErrorSums && pResults, count, ppIn, ppStreams, sh, capacityEach, true)) != limg_hip_success) return r;
-    if ((r = check_search(count, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    bool go;
+    const limg_hip_result r = open_list(check_list(c, pMaxErrorSums && pResults, count, ppIn, ppStreams, StreamShape(sizeX, sizeY), capacityEach, true), count,
+                                        [&](size_t n) { return check_search(n, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi); }, go);
+    if (!go) return r;
     return quality_searches(c, count, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY).data(), false, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults,
                             stream);
   }
@@ -838,321 +987,37 @@ extern "C"
                                                        uint8_t *const *ppStreams, size_t capacityEach, const uint64_t *pMaxErrorSums, uint32_t minErrorFactor,
                                                        uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing, limg_hip_quality_result *pResults)
   {
-    const StreamShape sh(sizeX, sizeY);
     uint32_t hLo, hHi;
-    limg_hip_result r;
-    if ((r = check_list(c, pMaxErrorSums && pResults, count, ppIn, ppStreams, sh, SIZE_MAX, false)) != limg_hip_success) return r; // (capacityEach: the rule below)
-    if ((r = check_search(count, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    bool go; // (capacityEach: host_list's rule, behind the encode)
+    const limg_hip_result r = open_list(check_list(c, pMaxErrorSums && pResults, count, ppIn, ppStreams, StreamShape(sizeX, sizeY), SIZE_MAX, false), count,
+                                        [&](size_t n) { return check_search(n, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi); }, go);
+    if (!go) return r;
     return quality_list_host(c, as_items(count, ppIn, ppStreams, capacityEach, sizeX, sizeY), false, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults);
   }
 }
 
-// ---- stream encode of a list of mixed shapes (contract: include/limg_hip.h; the layout: limg_hip_list_plan.h) ----
-namespace
-{
-  // The items as the caller's array holds them (itemSize apart), checked in the contract's order.  deviceForm: the streams are device buffers.  streams == false:
-  // the call writes no stream (the sizes list) -- pStream and capacity are not read.
-  limg_hip_result check_items(const void *c, bool pointers, size_t count, const ListItem *pItems, size_t itemSize, bool deviceForm, std::vector<ListItem> &items,
-                              bool streams = true)
-  {
-    if (!c || !pItems || !pointers) return limg_hip_error_ArgumentNull;
-    if (itemSize < sizeof(ListItem)) return limg_hip_error_InvalidParameter;
-    items.resize(count);
-    for (size_t i = 0; i < count; i++)
-    {
-      memcpy(&items[i], (const uint8_t *)pItems + i * itemSize, sizeof(ListItem));
-      const ListItem &it = items[i];
-      if (!it.pIn || (streams && !it.pStream)) return limg_hip_error_ArgumentNull;
-      const size_t bound = (it.sizeX && it.sizeY) ? limg_hip_stream_bound(it.sizeX, it.sizeY) : 0;
-      if (bound == 0) return limg_hip_error_InvalidParameter;
-      if (streams && deviceForm && ((uintptr_t)it.pStream & 15u) != 0) return limg_hip_error_InvalidParameter;
-      if (streams && deviceForm && it.capacity < bound) return limg_hip_error_OutOfBounds;
-      if (it.reserved != 0) return limg_hip_error_InvalidParameter;
-    }
-    return limg_hip_success;
-  }
-
-  // One chunk of eligible items of more than one shape: the images' factor planes in slices of stream.fac, the chunk's table block with this layer's part of it
-  // (the StreamImage entries), the encode layer's launch pair on them (encode_list_chunk), ONE scan, ONE pack.  Everything it needs has been grown by the caller.
-  limg_hip_result mixed_chunk(limg_hip_context *c, const ListItem *its, size_t n, int hasAlpha, int poolThreads, int fastBitCrushing, hipStream_t s)
-  {
-    const ChunkTables T = chunk_tables(n);
-    std::vector<uint8_t> host(T.bytes, 0);
-    uint8_t *const dev = (uint8_t *)c->stream.listTable.p;
-    StreamImage *streams = (StreamImage *)(host.data() + T.streams);
-    std::vector<ListChunkImage> images(n);
-    size_t facAt = 0;
-    for (size_t i = 0; i < n; i++)
-    {
-      const ListItem &it = its[i];
-      images[i].in = it.pIn; images[i].sizeX = it.sizeX; images[i].sizeY = it.sizeY; images[i].errorFactor = it.errorFactor;
-      for (int k = 0; k < 3; k++) { streams[i].fac[k] = images[i].fac[k] = (uint8_t *)c->stream.fac.p + facAt; facAt += list_plane_stride(it.sizeX, it.sizeY); }
-      streams[i].stream = it.pStream;
-    }
-    uint32_t *const stripWords = (uint32_t *)c->stream.units.p;
-    ListChunkTotals tot;
-    const limg_hip_result r = encode_list_chunk(c, images.data(), n, hasAlpha, poolThreads, stripWords, host.data(), dev, s, tot);
-    if (r != limg_hip_success) return r;
-    StreamListParams b;
-    memset(&b, 0, sizeof(b));
-    b.images = (const ListImage *)(dev + T.images); b.streams = (const StreamImage *)(dev + T.streams); b.rated = (const RatedImage *)(dev + T.rated); b.firstStrip = (const uint32_t *)(dev + T.firstStrip);
-    b.nImages = (uint32_t)n; b.nStrips = tot.strips; b.nWaves = pack_waves(c, tot.strips);
-    b.channels = hasAlpha ? 4u : 3u; b.flags = stream_flags(c, fastBitCrushing);
-    b.records = (const limg_hip_block_record *)c->enc.records.p; b.shifts = (const uint32_t *)c->enc.shifts.p; b.stripWords = stripWords;
-    Timeline tl(c, s, 4); // {scan + pack of the chunk, -, -}
-    tl.mark();
-    launch_stream_pack_list(b, s);
-    tl.close();
-    HIP_TRY(hipGetLastError());
-    return limg_hip_success;
-  }
-
-  // The whole route (the items have been checked): the eligible items through the shared launches -- the same-shape list as it is where they share one shape,
-  // else chunk by chunk --, the others through the single call, on the same stream; then the sizes.
-  limg_hip_result stream_items_device(limg_hip_context *c, const std::vector<ListItem> &items, int hasAlpha, size_t *pBytes, int poolThreads, int fastBitCrushing, void *stream)
-  {
-    const size_t count = items.size();
-    if (count == 0) return limg_hip_success;
-    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<ListItem> shared, alone;
-    for (const ListItem &it : items) (list_item_eligible(it.sizeX, it.sizeY, fastBitCrushing, c->opt) ? shared : alone).push_back(it);
-    bool oneShape = true;
-    for (const ListItem &it : shared) oneShape = oneShape && it.sizeX == shared[0].sizeX && it.sizeY == shared[0].sizeY;
-    limg_hip_result r = limg_hip_success;
-    if ((r = c->stream.table.ensure(count * sizeof(StreamImage))) != limg_hip_success) return r;
-    bool first = true; // limg_hip_last_stats: all images of the list together, whichever way each went
-    auto single = [&](const ListItem &it) {
-      c->stats.accumulate = !first; first = false;
-      return limg_hip_encode_stream_device(c, it.pIn, it.sizeX, it.sizeY, hasAlpha, it.pStream, (size_t)it.capacity, nullptr, it.errorFactor, poolThreads, fastBitCrushing, stream);
-    };
-    if (shared.size() == 1) r = single(shared[0]);
-    else if (!shared.empty() && oneShape)
-    { // the same-shape list, as it is: limg_hip_encode_stream_batch_ef_device's route
-      const ItemArrays a(shared);
-      r = stream_list_device(c, true, shared.size(), a.in.data(), shared[0].sizeX, shared[0].sizeY, hasAlpha, a.streams.data(), a.capacityEach, nullptr, 0, a.efs.data(), poolThreads,
-                             fastBitCrushing, stream);
-      first = false;
-    }
-    else if (!shared.empty())
-    {
-      // the chunks, and everything the largest of them needs, before the first launch: nothing is grown (and so freed) between the chunks of a list
-      std::vector<uint64_t> blocks(shared.size()), strips(shared.size());
-      std::vector<size_t> fac(shared.size());
-      for (size_t i = 0; i < shared.size(); i++) { const EncodeShape sh(shared[i].sizeX, shared[i].sizeY); blocks[i] = sh.blocks; strips[i] = sh.strips; fac[i] = 3 * list_plane_stride(sh.sizeX, sh.sizeY); }
-      const size_t hook = TOPT(c, batch_chunk) > 0 ? (size_t)TOPT(c, batch_chunk) : 0;
-      const ListNeeds most = list_needs(blocks.data(), strips.data(), fac.data(), shared.size(), hook);
-      if (most.images > 1)
-      {
-        PersistentScratch ps;
-        if ((r = c->stream.listTable.ensure(chunk_tables(most.images).bytes)) != limg_hip_success) return r;
-        if ((r = c->stream.fac.ensure(most.facBytes)) != limg_hip_success) return r;
-        if ((r = c->stream.units.ensure((size_t)most.strips * 4)) != limg_hip_success) return r;
-        if ((r = c->enc.records.ensure((size_t)most.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
-        if ((r = c->enc.shifts.ensure((size_t)most.blocks * 4)) != limg_hip_success) return r;
-        if ((r = c->enc.invN.ensure((size_t)most.blocks * 16)) != limg_hip_success) return r;
-        if ((r = persistent_scratch(c, (size_t)most.strips, 2, s, ps)) != limg_hip_success) return r;
-      }
-      for (size_t i0 = 0; i0 < shared.size() && r == limg_hip_success;)
-      {
-        const size_t i1 = list_chunk_end(blocks.data(), strips.data(), shared.size(), i0, hook);
-        if (i1 - i0 == 1) r = single(shared[i0]); // a chunk that holds one item: the single call
-        else
-        {
-          c->stats.accumulate = !first; first = false;
-          r = mixed_chunk(c, &shared[i0], i1 - i0, hasAlpha, poolThreads, fastBitCrushing, s);
-        }
-        i0 = i1;
-      }
-    }
-    for (size_t i = 0; i < alone.size() && r == limg_hip_success; i++) r = single(alone[i]);
-    c->stats.accumulate = false;
-    if (r != limg_hip_success || !pBytes) return r;
-    std::vector<StreamImage> images(count);
-    for (size_t i = 0; i < count; i++) images[i].stream = items[i].pStream;
-    return list_bytes(c, images.data(), count, pBytes, s);
-  }
-}
-
-// ---- the byte budget and the size probe for a list of mixed shapes (contract: include/limg_hip.h; kernels: k_rate_probe_list and the _batch begin / step with the
-// chunk's ListImage table, limg_hip_rate.hip) ----
-namespace
-{
-  // The eligible items of a list as the mixed routes walk them: which they are, their blocks and strips, and what the largest chunk of more than one item needs.
-  struct ListRoute
-  {
-    std::vector<size_t> shared, alone; // indices into the list
-    std::vector<ListItem> items;       // the eligible items, in list order
-    std::vector<uint64_t> blocks, strips;
-    size_t hook;
-    ListNeeds most;
-    bool oneShape = true;
-    ListRoute(const limg_hip_context *c, const std::vector<ListItem> &all, int fastBitCrushing)
-    {
-      for (size_t i = 0; i < all.size(); i++) (list_item_eligible(all[i].sizeX, all[i].sizeY, fastBitCrushing, c->opt) ? shared : alone).push_back(i);
-      for (size_t i : shared)
-      {
-        const EncodeShape sh(all[i].sizeX, all[i].sizeY);
-        items.push_back(all[i]); blocks.push_back(sh.blocks); strips.push_back(sh.strips);
-        oneShape = oneShape && all[i].sizeX == items[0].sizeX && all[i].sizeY == items[0].sizeY;
-      }
-      hook = TOPT(c, batch_chunk) > 0 ? (size_t)TOPT(c, batch_chunk) : 0;
-      const std::vector<size_t> noPlanes(items.size(), 0);
-      most = list_needs(blocks.data(), strips.data(), noPlanes.data(), items.size(), hook);
-    }
-    size_t chunk_end(size_t i0) const { return list_chunk_end(blocks.data(), strips.data(), items.size(), i0, hook); }
-  };
-
-  // everything the probes of the route's largest chunk need, before the first launch: the tables, the fit grid's records, invN and look-back words, one state and one
-  // counter per image
-  limg_hip_result grow_list_probe(limg_hip_context *c, const ListRoute &route)
-  {
-    const ListNeeds &most = route.most;
-    if (most.images < 2) return limg_hip_success;
-    limg_hip_result r;
-    if ((r = c->stream.listTable.ensure(chunk_tables(most.images).bytes)) != limg_hip_success) return r;
-    if ((r = c->enc.records.ensure((size_t)most.blocks * sizeof(limg_hip_block_record))) != limg_hip_success) return r;
-    if ((r = c->enc.invN.ensure((size_t)most.blocks * 16)) != limg_hip_success) return r;
-    if ((r = c->enc.lookback.ensure(16 * 2 + (size_t)most.strips * 8)) != limg_hip_success) return r;
-    if ((r = c->stream.rateState.ensure(most.images * sizeof(RateDevice))) != limg_hip_success) return r;
-    return c->stream.rateCounter.ensure(most.images * 8);
-  }
-
-  // The whole route of the budgeted list (the arguments have been checked): result i and stream i the single budget call's for item i.  Eligible items of more than
-  // one shape go chunk by chunk -- the chunk's records from ONE k_fit_tpb_list grid, its searches as 1 + 2 x rate_max_probes launches with ONE download and ONE wait,
-  // then the chunk through the mixed-list encode at the error factors the searches chose (that encode runs its own float stage: reusing the probe's records is a
-  // follow-up) --; a chunk of one item, and every ineligible item, takes the single call on the same stream; eligible items of ONE shape take the same-shape list.
-  limg_hip_result budget_items_device(limg_hip_context *c, const std::vector<ListItem> &items, int hasAlpha, const size_t *pMaxBytes, uint32_t minErrorFactor,
-                                      uint32_t maxErrorFactor, uint32_t hLo, uint32_t hHi, int poolThreads, int fastBitCrushing, limg_hip_budget_result *pResults, void *stream)
-  {
-    const size_t count = items.size();
-    if (count == 0) return limg_hip_success;
-    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const ListRoute route(c, items, fastBitCrushing);
-    auto single = [&](size_t i) {
-      const ListItem &it = items[i];
-      return limg_hip_encode_stream_budget_device(c, it.pIn, it.sizeX, it.sizeY, hasAlpha, it.pStream, (size_t)it.capacity, pMaxBytes[i], minErrorFactor, maxErrorFactor, poolThreads,
-                                                  fastBitCrushing, &pResults[i], stream);
-    };
-    limg_hip_result r = limg_hip_success;
-    const size_t n = route.items.size();
-    std::vector<size_t> budgets(n);
-    for (size_t k = 0; k < n; k++) budgets[k] = pMaxBytes[route.shared[k]];
-    if (n == 1) r = single(route.shared[0]);
-    else if (n > 1 && route.oneShape)
-    { // the same-shape list, as it is: limg_hip_encode_stream_budget_batch_device with the smallest capacity
-      const ItemArrays a(route.items);
-      std::vector<limg_hip_budget_result> own = own_results<limg_hip_budget_result>(n);
-      r = limg_hip_encode_stream_budget_batch_device(c, n, a.in.data(), route.items[0].sizeX, route.items[0].sizeY, hasAlpha, a.streams.data(), a.capacityEach, budgets.data(),
-                                                     minErrorFactor, maxErrorFactor, poolThreads, fastBitCrushing, own.data(), stream);
-      for (size_t k = 0; r == limg_hip_success && k < n; k++) report(pResults + route.shared[k], own.data() + k, 0);
-    }
-    else if (n > 1)
-    {
-      if ((r = grow_list_probe(c, route)) != limg_hip_success) return r;
-      std::vector<RateDevice> states;
-      std::vector<ListItem> chosen;
-      for (size_t i0 = 0; i0 < n && r == limg_hip_success;)
-      {
-        const size_t i1 = route.chunk_end(i0), m = i1 - i0;
-        if (m == 1) r = single(route.shared[i0]); // a chunk that holds one item: the single call
-        else
-        {
-          Probe pr;
-          states.resize(m);
-          if ((r = list_probe_setup(c, &route.items[i0], m, hasAlpha, poolThreads, s, pr)) != limg_hip_success) break;
-          if ((r = run_searches(pr, &budgets[i0], hLo, hHi, s, states.data())) != limg_hip_success) break;
-          chosen.assign(route.items.begin() + i0, route.items.begin() + i1);
-          for (size_t k = 0; k < m; k++) { chosen[k].errorFactor = 2u * states[k].search.next; chosen[k].reserved = 0; }
-          if ((r = stream_items_device(c, chosen, hasAlpha, nullptr, poolThreads, fastBitCrushing, stream)) != limg_hip_success) break;
-          for (size_t k = 0; k < m; k++) // bytes: what the probe measured at the result -- the packer's totalBytes
-            fill_result(pResults[route.shared[i0 + k]], 2u * states[k].search.next, states[k].search.probes, states[k].search.within, states[k].search.bestBytes);
-        }
-        i0 = i1;
-      }
-    }
-    for (size_t k = 0; k < route.alone.size() && r == limg_hip_success; k++) r = single(route.alone[k]);
-    return r;
-  }
-
-  // The sizes of every item at every factor (the arguments have been checked; factorCount > 0): pBytes[i * factorCount + k].  The eligible items go chunk by chunk,
-  // whatever their shapes: ONE k_fit_tpb_list grid, one begin, factorCount pairs of k_rate_probe_list and the list form of the step, ONE download and ONE wait per
-  // chunk.  A chunk of one item and every ineligible item take limg_hip_stream_sizes_device, which has its own fallback.
-  limg_hip_result sizes_items_device(limg_hip_context *c, const std::vector<ListItem> &items, int hasAlpha, const uint32_t *pErrorFactors, size_t factorCount, size_t *pBytes,
-                                     int poolThreads, int fastBitCrushing, void *stream)
-  {
-    const size_t count = items.size();
-    if (count > 0x7FFFFFFFull || factorCount > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const ListRoute route(c, items, fastBitCrushing);
-    auto single = [&](size_t i) {
-      return limg_hip_stream_sizes_device(c, items[i].pIn, items[i].sizeX, items[i].sizeY, hasAlpha, pErrorFactors, factorCount, pBytes + i * factorCount, poolThreads, fastBitCrushing,
-                                          stream);
-    };
-    limg_hip_result r = limg_hip_success;
-    const size_t n = route.items.size();
-    if (route.most.images > 1)
-    {
-      if ((r = grow_list_probe(c, route)) != limg_hip_success) return r;
-      if ((r = c->stream.rateList.ensure(route.most.images * factorCount * 8 + factorCount * 4)) != limg_hip_success) return r;
-    }
-    const std::vector<uint32_t> list(pErrorFactors, pErrorFactors + factorCount); // (the caller's array may be pageable and may die when the call returns)
-    std::vector<size_t> sizes;
-    for (size_t i0 = 0; i0 < n && r == limg_hip_success;)
-    {
-      const size_t i1 = route.chunk_end(i0), m = i1 - i0;
-      if (m == 1) r = single(route.shared[i0]);
-      else
-      {
-        Probe pr;
-        if ((r = list_probe_setup(c, &route.items[i0], m, hasAlpha, poolThreads, s, pr)) != limg_hip_success) break;
-        unsigned long long *dBytes = (unsigned long long *)c->stream.rateList.p;
-        uint32_t *dList = (uint32_t *)(dBytes + m * factorCount);
-        HIP_TRY(hipMemcpyAsync(dList, list.data(), factorCount * 4, hipMemcpyHostToDevice, s));
-        launch_rate_begin_batch(pr.states, pr.counters, nullptr, m, 0, 0, s, dList);
-        for (size_t k = 0; k < factorCount; k++)
-        {
-          pr.launch(s);
-          pr.step(s, dList, dBytes, (uint32_t)factorCount);
-        }
-        HIP_TRY(hipGetLastError());
-        sizes.resize(m * factorCount);
-        if ((r = download_sizes(dBytes, m * factorCount, sizes.data(), s)) != limg_hip_success) break; // (its wait also: `list` is no longer read by this chunk)
-        for (size_t k = 0; k < m; k++)
-          for (size_t f = 0; f < factorCount; f++) pBytes[route.shared[i0 + k] * factorCount + f] = sizes[k * factorCount + f];
-      }
-      i0 = i1;
-    }
-    for (size_t k = 0; k < route.alone.size() && r == limg_hip_success; k++) r = single(route.alone[k]);
-    return r;
-  }
-}
-
+// ---- the lists of mixed shapes (contract: include/limg_hip.h; the layout and the route: limg_hip_list_plan.h; the walkers: encode_list, budget_list, sizes_list above) ----
 extern "C"
 {
   limg_hip_result limg_hip_encode_stream_list_device(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha, size_t *pBytes,
                                                      int poolThreads, int fastBitCrushing, void *stream)
   {
     std::vector<ListItem> items;
-    const limg_hip_result r = check_items(c, true, count, pItems, itemSize, true, items);
-    return r != limg_hip_success ? r : stream_items_device(c, items, hasAlpha, pBytes, poolThreads, fastBitCrushing, stream);
+    bool go;
+    const limg_hip_result r = open_list(check_items(c, true, count, pItems, itemSize, true, items), count, no_search, go);
+    return !go ? r : encode_list(c, items, kListOwn, false, hasAlpha, pBytes, poolThreads, fastBitCrushing, stream);
   }
 
   limg_hip_result limg_hip_encode_stream_list(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha, size_t *pBytes,
                                               int poolThreads, int fastBitCrushing)
   {
     std::vector<ListItem> items;
-    const limg_hip_result r = check_items(c, pBytes != nullptr, count, pItems, itemSize, false, items);
-    if (r != limg_hip_success || count == 0) return r;
+    bool go;
+    const limg_hip_result r = open_list(check_items(c, pBytes != nullptr, count, pItems, itemSize, false, items), count, no_search, go);
+    if (!go) return r;
     std::vector<size_t> bytes(count);
     return host_list(c, items, bytes.data(), pBytes, [&](const std::vector<ListItem> &staged) {
-      return stream_items_device(c, staged, hasAlpha, bytes.data(), poolThreads, fastBitCrushing, nullptr);
+      return encode_list(c, staged, kListOwn, false, hasAlpha, bytes.data(), poolThreads, fastBitCrushing, nullptr);
     });
   }
 
@@ -1162,12 +1027,10 @@ extern "C"
   {
     std::vector<ListItem> items;
     uint32_t hLo, hHi;
-    limg_hip_result r;
-    if ((r = check_items(c, pMaxErrorSums && pResults, count, pItems, itemSize, true, items)) != limg_hip_success) return r;
-    if ((r = check_search(count, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
-    return quality_searches(c, count, items.data(), true, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults, stream);
+    bool go;
+    const limg_hip_result r = open_list(check_items(c, pMaxErrorSums && pResults, count, pItems, itemSize, true, items), count,
+                                        [&](size_t n) { return check_search(n, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi); }, go);
+    return !go ? r : quality_searches(c, count, items.data(), true, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults, stream);
   }
 
   limg_hip_result limg_hip_encode_stream_quality_list(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
@@ -1176,24 +1039,23 @@ extern "C"
   {
     std::vector<ListItem> items;
     uint32_t hLo, hHi;
-    limg_hip_result r;
-    if ((r = check_items(c, pMaxErrorSums && pResults, count, pItems, itemSize, false, items)) != limg_hip_success) return r;
-    if ((r = check_search(count, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    return quality_list_host(c, items, true, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults);
+    bool go;
+    const limg_hip_result r = open_list(check_items(c, pMaxErrorSums && pResults, count, pItems, itemSize, false, items), count,
+                                        [&](size_t n) { return check_search(n, nullptr, minErrorFactor, maxErrorFactor, pResults, hLo, hHi); }, go);
+    return !go ? r : quality_list_host(c, items, true, hasAlpha, pMaxErrorSums, hLo, hHi, poolThreads, fastBitCrushing, pResults);
   }
 
-  // ---- ... to a byte budget per item, and the sizes of every item at a list of error factors (budget_items_device / sizes_items_device above) ----
+  // ---- ... to a byte budget per item, and the sizes of every item at a list of error factors (budget_list / sizes_list above) ----
   limg_hip_result limg_hip_encode_stream_budget_list_device(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
                                                             const size_t *pMaxBytes, uint32_t minErrorFactor, uint32_t maxErrorFactor, int poolThreads, int fastBitCrushing,
                                                             limg_hip_budget_result *pResults, void *stream)
   {
     std::vector<ListItem> items;
     uint32_t hLo, hHi;
-    limg_hip_result r;
-    if ((r = check_items(c, pMaxBytes && pResults, count, pItems, itemSize, true, items)) != limg_hip_success) return r;
-    if ((r = check_search(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
-    return budget_items_device(c, items, hasAlpha, pMaxBytes, minErrorFactor, maxErrorFactor, hLo, hHi, poolThreads, fastBitCrushing, pResults, stream);
+    bool go;
+    const limg_hip_result r = open_list(check_items(c, pMaxBytes && pResults, count, pItems, itemSize, true, items), count,
+                                        [&](size_t n) { return check_search(n, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi); }, go);
+    return !go ? r : budget_list(c, items, false, hasAlpha, pMaxBytes, minErrorFactor, maxErrorFactor, hLo, hHi, poolThreads, fastBitCrushing, pResults, stream);
   }
 
   limg_hip_result limg_hip_encode_stream_budget_list(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
@@ -1202,36 +1064,39 @@ extern "C"
   {
     std::vector<ListItem> items;
     uint32_t hLo, hHi;
-    limg_hip_result r;
-    if ((r = check_items(c, pMaxBytes && pResults, count, pItems, itemSize, false, items)) != limg_hip_success) return r;
-    if ((r = check_search(count, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi)) != limg_hip_success) return r;
-    if (count == 0) return limg_hip_success;
-    if (count > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    bool go;
+    const limg_hip_result r = open_list(check_items(c, pMaxBytes && pResults, count, pItems, itemSize, false, items), count,
+                                        [&](size_t n) { return check_search(n, pMaxBytes, minErrorFactor, maxErrorFactor, pResults, hLo, hHi); }, go);
+    if (!go) return r;
     std::vector<limg_hip_budget_result> results = own_results<limg_hip_budget_result>(count);
     return host_list(c, items, results.data(), pResults, [&](const std::vector<ListItem> &staged) {
-      return budget_items_device(c, staged, hasAlpha, pMaxBytes, minErrorFactor, maxErrorFactor, hLo, hHi, poolThreads, fastBitCrushing, results.data(), nullptr);
+      return budget_list(c, staged, false, hasAlpha, pMaxBytes, minErrorFactor, maxErrorFactor, hLo, hHi, poolThreads, fastBitCrushing, results.data(), nullptr);
     });
   }
 
+  // (an empty factor list, like an empty list: success with nothing done)
   limg_hip_result limg_hip_stream_sizes_list_device(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
                                                     const uint32_t *pErrorFactors, size_t factorCount, size_t *pBytes, int poolThreads, int fastBitCrushing, void *stream)
   {
     std::vector<ListItem> items;
-    const limg_hip_result r = check_items(c, pErrorFactors && pBytes, count, pItems, itemSize, true, items, false);
-    if (r != limg_hip_success || count == 0 || factorCount == 0) return r;
-    return sizes_items_device(c, items, hasAlpha, pErrorFactors, factorCount, pBytes, poolThreads, fastBitCrushing, stream);
+    bool go;
+    const limg_hip_result r = open_list(check_items(c, pErrorFactors && pBytes, count, pItems, itemSize, true, items, false), factorCount ? count : 0, no_search, go);
+    if (!go) return r;
+    if (factorCount > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    return sizes_list(c, items, hasAlpha, pErrorFactors, factorCount, pBytes, poolThreads, fastBitCrushing, stream);
   }
 
   limg_hip_result limg_hip_stream_sizes_list(limg_hip_context *c, size_t count, const limg_hip_stream_list_item *pItems, size_t itemSize, int hasAlpha,
                                              const uint32_t *pErrorFactors, size_t factorCount, size_t *pBytes, int poolThreads, int fastBitCrushing)
   {
     std::vector<ListItem> items, staged;
-    limg_hip_result r = check_items(c, pErrorFactors && pBytes, count, pItems, itemSize, false, items, false);
-    if (r != limg_hip_success || count == 0 || factorCount == 0) return r;
-    if (count > 0x7FFFFFFFull || factorCount > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
+    bool go;
+    limg_hip_result r = open_list(check_items(c, pErrorFactors && pBytes, count, pItems, itemSize, false, items, false), factorCount ? count : 0, no_search, go);
+    if (!go) return r;
+    if (factorCount > 0x7FFFFFFFull) return limg_hip_error_InvalidParameter;
     std::lock_guard<std::recursive_mutex> hostLock(c->hostEntry);
     if ((r = stage_inputs(c, items, staged)) != limg_hip_success) return r;
-    r = sizes_items_device(c, staged, hasAlpha, pErrorFactors, factorCount, pBytes, poolThreads, fastBitCrushing, nullptr);
+    r = sizes_list(c, staged, hasAlpha, pErrorFactors, factorCount, pBytes, poolThreads, fastBitCrushing, nullptr);
     return r != limg_hip_success ? r : limg_hip_check_device_status(c);
   }
 }

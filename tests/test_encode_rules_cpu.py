@@ -60,11 +60,11 @@ def test_forced_shifts(ask):
 
 
 def restated_chunk(blocks, strips, hook, record):
-    if hook > 0:
-        return hook
     chunk = (1 << 30) // (blocks * record)
     if chunk * strips > 0x7FFFFFFF:
         chunk = 0x7FFFFFFF // strips
+    if hook > 0:
+        chunk = min(chunk, hook)
     return max(chunk, 1)
 
 
@@ -86,4 +86,5 @@ def test_list_chunk(ask):
     assert free[one_block] == 1 << 24
     assert free[strip_rule] == 0x7FFFFFFF // 1000 < (1 << 30) // record
     assert free[huge] == 1
-    assert [g[0] for g in got[1::2]] == [3, 3, 3, 3], "the hook overrides each"
+    # the hook asks for fewer images per pair and never lifts a bound (list_chunk_end's rule for a list of mixed shapes: tests/test_list_plan_cpu.py)
+    assert [g[0] for g in got[1::2]] == [3, 3, 3, 1], "the hook overrides each but the image that is alone over a bound"

@@ -2,7 +2,13 @@
 its OWN 16-byte access flags and dither-chain partition; per chunk the totals, the noise need (the maximum over the images, not the sum), the chunk boundaries and
 eligibility; the layout of a chunk's table block and what a list grows before its first launch -- without a GPU: tests/helpers/list_plan_check.cpp is built by
 the host compiler alone (under the undefined-behaviour sanitizer) and prints the header's answers, which are compared with the rules restated here on the lists
-tests/test_gpu_stream_list.py encodes."""
+tests/test_gpu_stream_list.py encodes.
+
+The ROUTE of every list entry of the stream encode family (list_route: which items go through which launches, in which order, what restarts the statistics, what the
+largest chunk needs) is asked three times: the header's plan, the decisions of the five walkers as they stood before the plan (lifted into the helper), and the rules
+restated in route() below.  All three agree on every list of one to four of five shapes under every option, hook, job and entry form that exists: there is no
+same-shape entry for the sizes and no items entry at a shared factor, so those two combinations are not asked."""
+import itertools
 import os
 import shutil
 import subprocess
@@ -210,3 +216,179 @@ def test_needs(ask):
         assert tuple(int(x) for x in line.split()) == needs(b, s, f, hook), (hook, b, s, f, line)
     assert got[0].split()[0] == "7" and got[1].split()[0] == "3" and got[2].split()[0] == "66" and got[3].split()[0] == "3"
     assert [int(x) for x in got[4].split()] == [3, M, 140, 300] and got[5].split() == ["0"] * 4
+
+
+# ---- the route ----
+SHARED, OWN, BUDGET, SIZES = 0, 1, 2, 3
+ROUTE_SHAPES = ((8, 8), (256, 8), (264, 24), (13, 9), (256, 20))
+
+
+def _blocks(shape):
+    return ((shape[0] + 7) // 8) * ((shape[1] + 7) // 8)
+
+
+def _strips(shape):
+    return (((shape[0] + 7) // 8 + 31) // 32) * ((shape[1] + 7) // 8)
+
+
+def list_chunk(blocks, strips, hook):
+    chunk = (1 << 30) // (blocks * 64)
+    if chunk * strips > 0x7FFFFFFF:
+        chunk = 0x7FFFFFFF // strips
+    if hook:
+        chunk = min(chunk, hook)
+    return max(chunk, 1)
+
+
+def route(shapes, efs, job, same, fast, split, legacy, hook):
+    """the rules, restated: -> (steps [(kind, own, restart, item indices)], most (images, blocks, strips, facBytes), inPlace)"""
+    steps = []
+    encode = job in (SHARED, OWN)
+
+    def pair(idx):
+        w, h = shapes[idx[0]]
+        return w % 8 == 0 and h % 8 == 0 and not split and not legacy
+
+    def chunk_of(idx):
+        return list_chunk(_blocks(shapes[idx[0]]), _strips(shapes[idx[0]]), hook)
+
+    def cut(idx, chunk, own, restart):
+        for i0 in range(0, len(idx), chunk):
+            part = tuple(idx[i0:i0 + chunk])
+            steps.append(("S", False, restart, part) if len(part) == 1 else ("C", own, restart, part))
+            restart = False
+
+    def same_shape(idx, own, restart):
+        """-> cut in list order by the chunk rule"""
+        pairs = len(idx) > 1 and pair(idx)
+        if own and (not pairs or not fast):
+            for _, group in itertools.groupby(sorted(idx, key=lambda i: efs[i]), key=lambda i: efs[i]):  # (sorted is stable)
+                same_shape(list(group), False, True)
+            return False
+        cut(idx, chunk_of(idx) if pairs else 1, own, restart)
+        return pairs
+
+    def budget_same(idx):
+        cut(idx, chunk_of(idx) if len(idx) > 1 and pair(idx) and fast else 1, False, not steps)
+
+    in_place = False
+    everything = list(range(len(shapes)))
+    if same:
+        if job == BUDGET:
+            budget_same(everything)
+        else:
+            in_place = same_shape(everything, job == OWN, True)
+    else:
+        eligible = [i for i in everything if fast and pair([i])]
+        others = [i for i in everything if i not in eligible]
+        if len(eligible) == 1:
+            steps.append(("S", False, True, (eligible[0],)))
+        elif eligible and job != SIZES and len({shapes[i] for i in eligible}) == 1:
+            if job == BUDGET:
+                budget_same(eligible)
+            else:
+                same_shape(eligible, True, True)
+        elif eligible:
+            i0 = 0
+            for i1 in chunk_ends([_blocks(shapes[i]) for i in eligible], [_strips(shapes[i]) for i in eligible], hook):
+                part = tuple(eligible[i0:i1])
+                steps.append(("S" if len(part) == 1 else "M", True, not steps, part))
+                i0 = i1
+        for i in others:
+            steps.append(("S", False, not steps, (i,)))
+    most = [0, 0, 0, 0]
+    for _, _, _, part in steps:
+        if len(part) > 1:
+            need = (len(part), sum(_blocks(shapes[i]) for i in part), sum(_strips(shapes[i]) for i in part),
+                    sum(3 * ((shapes[i][0] * shapes[i][1] + 255) // 256 * 256) for i in part) if encode else 0)
+            most = [max(a, b) for a, b in zip(most, need)]
+    return steps, tuple(most), in_place
+
+
+def route_line(shapes, efs, job, same, fast, split, legacy, hook):
+    steps, most, in_place = route(shapes, efs, job, same, fast, split, legacy, hook)
+    text = "".join("%s%s%s %s;" % ("!" if restart and job in (SHARED, OWN) else "", kind, int(own) if kind == "C" else "", " ".join(str(i) for i in part))
+                   for kind, own, restart, part in steps)
+    return "%s | %d %d %d %d | %d" % ((text,) + most + (int(in_place),))
+
+
+def route_question(shapes, efs, job, same, fast, split, legacy, hook):
+    return "%d %d %d %d %d %d %d " % (job, same, fast, split, legacy, hook, len(shapes)) + " ".join("%d %d %d" % (w, h, ef) for (w, h), ef in zip(shapes, efs))
+
+
+def factor_patterns(n):
+    """all equal, the first two equal, all distinct"""
+    return sorted({(100,) * n, ((100, 100, 40, 20)[:n]), ((100, 40, 20, 60)[:n])})
+
+
+def route_cases():
+    for n in (1, 2, 3, 4):
+        for shapes in itertools.product(ROUTE_SHAPES, repeat=n):
+            forms = [(False, OWN, p) for p in factor_patterns(n)] + [(False, BUDGET, (0,) * n), (False, SIZES, (0,) * n)]
+            if len(set(shapes)) == 1:
+                forms += [(True, SHARED, (100,) * n), (True, BUDGET, (0,) * n)] + [(True, OWN, p) for p in factor_patterns(n)]
+            for same, job, efs in forms:
+                for fast, split, legacy in itertools.product((0, 1), repeat=3):
+                    for hook in (0, 1, 2, 3):
+                        yield shapes, efs, job, int(same), fast, split, legacy, hook
+
+
+def test_route_three_ways(ask):
+    """the header's plan = the walkers' decisions as they stood = the rules restated here, on every question"""
+    cases = list(route_cases())
+    assert len({c[0] for c in cases}) == 780 and len(cases) > 100000
+    new = ask(["R " + route_question(*c) for c in cases])
+    old = ask(["O " + route_question(*c) for c in cases])
+    for c, a, b in zip(cases, new, old):
+        assert a == b == route_line(*c), (c, a, b, route_line(*c))
+
+
+def _steps(line):
+    return line.split(" |")[0]
+
+
+def test_route_named_lists(ask):
+    """the lists tests/test_gpu_stream_list.py encodes, whole and in chunks of three, for every job of the items entries -- and what a reader expects of them"""
+    cases = [(LISTS[name], tuple(20 + 10 * i for i in range(len(LISTS[name]))), job, 0, 1, 0, 0, hook)
+             for name in ("edges", "ragged_inside", "one_strip_each") for job in (OWN, BUDGET, SIZES) for hook in (0, 3)]
+    new = ask(["R " + route_question(*c) for c in cases])
+    old = ask(["O " + route_question(*c) for c in cases])
+    for c, a, b in zip(cases, new, old):
+        assert a == b == route_line(*c), (c, a, b, route_line(*c))
+    got = {(name, job, hook): _steps(line) for (name, job, hook), line in
+           zip([(name, job, hook) for name in ("edges", "ragged_inside", "one_strip_each") for job in (OWN, BUDGET, SIZES) for hook in (0, 3)], new)}
+    assert got[("edges", OWN, 0)] == "!M 0 1 2 3 4 5 6;" and got[("edges", OWN, 3)] == "!M 0 1 2;M 3 4 5;S 6;"
+    assert got[("edges", BUDGET, 0)] == got[("edges", SIZES, 0)] == "M 0 1 2 3 4 5 6;" and got[("edges", BUDGET, 3)] == got[("edges", SIZES, 3)] == "M 0 1 2;M 3 4 5;S 6;"
+    # one mixed chunk of (264, 24) and (8, 8), then (13, 9) and (256, 20) through the single call, in that order
+    assert got[("ragged_inside", OWN, 0)] == got[("ragged_inside", OWN, 3)] == "!M 0 3;S 1;S 2;"
+    assert got[("one_strip_each", OWN, 0)] == "!M 0 1 2 3 4;" and got[("one_strip_each", OWN, 3)] == "!M 0 1 2;M 3 4;"
+
+
+def test_route_same_shape_by_hand(ask):
+    """three (264, 24) images: own factors (20, 20, 400) under the accurate search are a shared-factor chunk of the first two, then a single, each with statistics of
+    its own; under the default search one own-factor chunk, cut in list order; four at a shared factor in chunks of three: a chunk and a last chunk of one"""
+    three = ((264, 24),) * 3
+    got = ask(["R " + route_question(three, (20, 20, 400), OWN, 1, 0, 0, 0, 0), "R " + route_question(three, (400, 20, 20), OWN, 1, 0, 0, 0, 0),
+               "R " + route_question(three, (20, 20, 400), OWN, 1, 1, 0, 0, 0), "R " + route_question(three, (20, 20, 400), OWN, 1, 1, 1, 0, 0),
+               "R " + route_question(((264, 24),) * 4, (100,) * 4, SHARED, 1, 1, 0, 0, 3), "R " + route_question(((264, 24),) * 5, (0,) * 5, BUDGET, 1, 1, 0, 0, 2),
+               "R " + route_question(three, (20, 100, 400), OWN, 0, 0, 0, 0, 0)])
+    plane = (264 * 24 + 255) // 256 * 256
+    assert got[0] == "!C0 0 1;!S 2; | 2 198 12 %d | 0" % (2 * 3 * plane)
+    assert _steps(got[1]) == "!C0 1 2;!S 0;"
+    assert got[2] == "!C1 0 1 2; | 3 297 18 %d | 1" % (3 * 3 * plane)
+    assert _steps(got[3]) == "!S 0;S 1;!S 2;"  # the split path: no launch pair, the group of two is two singles
+    assert got[4] == "!C0 0 1 2;S 3; | 3 297 18 %d | 1" % (3 * 3 * plane)
+    assert got[5] == "C0 0 1;C0 2 3;S 4; | 2 198 12 0 | 0"
+    assert _steps(got[6]) == "!S 0;S 1;S 2;"  # an items entry under the accurate search: nothing is eligible
+
+
+def test_chunk_rules_agree_on_one_shape(ask):
+    """list_chunk(blocks, strips, hook) images at a time = the chunks of list_chunk_end over n equal items, with synthetic counts and no shapes behind them"""
+    cases = [(hook, n, b, s) for b in (1, 5, 1 << 23, (1 << 24) - 1, 1 << 24, (1 << 24) + 5) for s in (1, 0x3FFFFFFF, 0x40000000, 0x7FFFFFFF) for hook in (0, 1, 3)
+             for n in range(1, 10)]
+    by_count = ask(["K %d %d %d %d" % c for c in cases])
+    by_end = ask(["C %d %d " % (hook, n) + " ".join(["%d %d" % (b, s)] * n) for hook, n, b, s in cases])
+    for (hook, n, b, s), a, e in zip(cases, by_count, by_end):
+        chunk = list_chunk(b, s, hook)
+        want = [min(i0 + chunk, n) for i0 in range(0, n, chunk)]
+        assert [int(x) for x in a.split()] == [int(x) for x in e.split()] == want == chunk_ends([b] * n, [s] * n, hook), (hook, n, b, s, a, e)
