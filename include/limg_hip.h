@@ -1057,6 +1057,59 @@ limg_hip_result limg_hip_decode_stream_windows_resized_tensor(limg_hip_context *
 limg_hip_result limg_hip_blocked_decode_stream_windows_resized_tensor(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes,
                                                                       const limg_hip_resized_tensor_window *pWindows, size_t count, const limg_hip_tensor_format *pFormat);
 
+/* ---- stream splice: a version 1 stream made from version 1 streams, on the GPU, without decoding -------------------------------------------
+ * A version 1 block is self-contained: its entry holds record, shift word and payloadWord, its payload is whole 8-byte words, and no decoder needs a neighbour.
+ * A rectangle of blocks of one stream can therefore be placed in the block grid of another stream by copying entries and payload and rebasing payloadWord: a
+ * lossless crop (one piece), join (strips, tiles) or any mix.  decode(splice) equals the matching rectangles of decode(source) bit for bit; no factor bit changes,
+ * no dither chain restarts.  Version 2 streams (rectangles that cross crop lines) are not handled.
+ *
+ * A PIECE is a rectangle of blocksW x blocksH blocks of a source stream from block (srcBx, srcBy), landing at block (dstBx, dstBy) of the output's grid.  Rules,
+ * all decided on the host before anything is launched; a breach is limg_hip_error_InvalidParameter and nothing is written:
+ *   exact cover    the pieces cover the output's blocksX x blocksY grid (of sizeX x sizeY) exactly once: no gap, no overlap; count >= 1, no piece is empty;
+ *   inside         each piece lies inside its source's block grid (of srcSizeX x srcSizeY);
+ *   edge rule      an output block the output size clips (last column when sizeX % 8 != 0, last row when sizeY % 8 != 0) comes from a source block clipped to
+ *                  the same extent on that axis -- the source's own last column / row with the same size % 8; a whole output block comes from a whole source
+ *                  block.  ("pixels outside the image are 0" then holds by copying alone; a whole block is never masked down to a partial one.)
+ *   sizes          limg_hip_stream_bound(sizeX, sizeY) != 0 and the same for every source size; streamBytes holds at least the header and the source's table;
+ *   device form    capacity >= limg_hip_stream_bound(sizeX, sizeY); pOut and every pStream 16-byte aligned; [pOut, pOut + capacity) overlaps no source;
+ *   pieceSize      = sizeof(limg_hip_splice_piece) versions the struct, as itemSize does in the list calls: below the struct's is refused, a larger stride is walked.
+ * NULL context, pPieces, pOut or a piece's pStream: limg_hip_error_ArgumentNull.  errorFactor and flags are the header's informational fields, written as given.
+ *
+ * The sources are untrusted, as in the decoders: the kernels check every source header (version 1, the channel count of hasAlpha, srcSizeX x srcSizeY) and that
+ * every run of entries they copy is canonical -- each payloadWord the run's start plus the words of the blocks before it, the run's end inside the source's
+ * payload, in 64-bit arithmetic.  A failure raises the context's status (limg_hip_check_device_status: limg_hip_error_InvalidParameter, once); nothing but the
+ * 64 header bytes of pOut is written, the header comes back zeroed (totalBytes 0) and *pBytes is 0.
+ *
+ * The output is canonical: entries in raster order, payloadWord the exact exclusive prefix of the blocks' words, payloadWords / totalBytes set on the device;
+ * every decode entry accepts it.  Three kernel launches whatever `count` is; context memory: 24 bytes per block row of a piece + 48 per piece. */
+typedef struct limg_hip_splice_piece
+{
+  const uint8_t *pStream; /* the source stream: DEVICE pointer in the _device forms, host pointer otherwise */
+  size_t streamBytes;
+  uint32_t srcSizeX, srcSizeY; /* the source image's size; the kernel checks it against the header, as the decode calls do */
+  uint32_t srcBx, srcBy;       /* first source block of the rectangle */
+  uint32_t dstBx, dstBy;       /* where that block lands in the output's block grid */
+  uint32_t blocksW, blocksH;   /* rectangle size in 8x8 blocks */
+} limg_hip_splice_piece;
+
+/* DEVICE pointers inside the pieces; pPieces is HOST memory and may be reused or freed when the call returns.  Asynchronous on `stream`; the size lands in the
+ * header (`totalBytes`); pBytes (host, may be NULL) receives it too, which makes the call wait. */
+limg_hip_result limg_hip_stream_splice_device(limg_hip_context *pCtx, const limg_hip_splice_piece *pPieces /* host */, size_t count, size_t pieceSize, size_t sizeX,
+                                              size_t sizeY, int hasAlpha, uint32_t errorFactor, uint32_t flags, uint8_t *pOut, size_t capacity, size_t *pBytes, void *stream);
+/* HOST pointers, blocking, under the context's mutex.  Every source must pass limg_hip_stream_info (its error otherwise; limg_hip_error_OutOfBounds when the
+ * stream is longer than streamBytes).  capacity may be below the bound: *pBytes is set, and limg_hip_error_OutOfBounds returned with nothing written, when the
+ * finished stream is longer than `capacity`. */
+limg_hip_result limg_hip_stream_splice(limg_hip_context *pCtx, const limg_hip_splice_piece *pPieces, size_t count, size_t pieceSize, size_t sizeX, size_t sizeY,
+                                       int hasAlpha, uint32_t errorFactor, uint32_t flags, uint8_t *pOut, size_t capacity, size_t *pBytes);
+/* One piece from a pixel window: the stream of the width x height image at (x0, y0) of the source.  x0 and y0 must be multiples of 8; x0 + width a multiple of 8
+ * or equal to sizeX, y0 + height a multiple of 8 or equal to sizeY; width, height >= 1 and the window inside the image: anything else is
+ * limg_hip_error_InvalidParameter.  (An unaligned origin would need the blocks re-cut: not done.)  Otherwise the splice call's rules. */
+limg_hip_result limg_hip_stream_crop_device(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, size_t sizeX, size_t sizeY, int hasAlpha, size_t x0, size_t y0,
+                                            size_t width, size_t height, uint32_t errorFactor, uint32_t flags, uint8_t *pOut, size_t capacity, size_t *pBytes, void *stream);
+/* HOST pointers, blocking: size, channels, errorFactor and flags come from the source's header. */
+limg_hip_result limg_hip_stream_crop(limg_hip_context *pCtx, const uint8_t *pStream, size_t streamBytes, size_t x0, size_t y0, size_t width, size_t height, uint8_t *pOut,
+                                     size_t capacity, size_t *pBytes);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ---------------------------------------------------------------------------------
  * The reference's only parallelism is row strips over a std::thread pool (src/limg.cpp:2105-2138); across GPUs the same strips
  * go one per rank.  Blocks are independent except for the dither chain, so the data path needs no collective in strip-restart mode (each strip

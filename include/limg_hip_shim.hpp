@@ -540,4 +540,23 @@ inline limg_result limg_decode_windows_resized_tensor(const uint8_t *pIn, const 
   return (limg_result)limg_hip_decode_stream_windows_resized_tensor(c, pIn, size, pWindows, count, pFormat);
 }
 
+// Streams from streams, version 1, without decoding (limg_hip.h "stream splice"): the result decodes to the sources' pixels bit for bit.
+// The stream of the w x h window at (x, y): x, y multiples of 8, x + w and y + h multiples of 8 or the image's edge.
+inline limg_result limg_crop_stream(const uint8_t *pIn, const size_t size, const size_t x, const size_t y, const size_t w, const size_t h, uint8_t *pOut, const size_t outCapacity,
+                                    size_t *pOutSize)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  return (limg_result)limg_hip_stream_crop(c, pIn, size, x, y, w, h, pOut, outCapacity, pOutSize);
+}
+
+// the stream of the sizeX x sizeY image whose block grid the pieces -- rectangles of blocks of other streams -- cover exactly once
+inline limg_result limg_splice_streams(const limg_hip_splice_piece *pPieces, const size_t count, const size_t sizeX, const size_t sizeY, const bool hasAlpha, uint8_t *pOut,
+                                       const size_t outCapacity, size_t *pOutSize, const uint32_t errorFactor = 0, const uint32_t flags = 0)
+{
+  limg_hip_context *c = limg_hip_shim::context();
+  if (!c) return limg_error_Generic;
+  return (limg_result)limg_hip_stream_splice(c, pPieces, count, sizeof(limg_hip_splice_piece), sizeX, sizeY, hasAlpha ? 1 : 0, errorFactor, flags, pOut, outCapacity, pOutSize);
+}
+
 #endif // LIMG_HIP_SHIM_HPP

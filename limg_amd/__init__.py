@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "limg_hip_decode_stream_windows_resized_device", "limg_hip_blocked_decode_stream_windows_resized_device", "limg_hip_decode_stream_windows_resized_tensor_device",
     "limg_hip_blocked_decode_stream_windows_resized_tensor_device", "limg_hip_decode_stream_windows_resized", "limg_hip_blocked_decode_stream_windows_resized",
     "limg_hip_decode_stream_windows_resized_tensor", "limg_hip_blocked_decode_stream_windows_resized_tensor",
+    "limg_hip_stream_splice_device", "limg_hip_stream_splice", "limg_hip_stream_crop_device", "limg_hip_stream_crop",
     "limg_hip_blocked_encode3d", "limg_hip_blocked_encode3d_device", "limg_hip_blocked_regions", "limg_hip_blocked_timing", "limg_hip_blocked_kernel_timing", "limg_hip_blocked_match_bits", "limg_hip_host_blocked_matches",
     "limg_hip_host_blocked_merge", "limg_hip_host_blocked_match_words", "limg_hip_host_blocked_match_bits",
     "limg_hip_comm_unique_id", "limg_hip_comm_init", "limg_hip_comm_destroy", "limg_hip_comm_info", "limg_hip_gather_stream", "limg_hip_encode3d_single_chain_device",
@@ -197,6 +198,12 @@ class StreamListItem(C.Structure):
     """limg_hip_stream_list_item: one image of a list of mixed shapes -- its pixels, its stream buffer and capacity, its size and its error factor"""
     _fields_ = [("pIn", C.c_void_p), ("pStream", C.c_void_p), ("capacity", C.c_uint64), ("sizeX", C.c_uint32), ("sizeY", C.c_uint32), ("errorFactor", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class SplicePiece(C.Structure):
+    """limg_hip_splice_piece: a rectangle of blocks of a source stream and where its first block lands in the output's block grid"""
+    _fields_ = [("pStream", C.c_void_p), ("streamBytes", C.c_size_t), ("srcSizeX", C.c_uint32), ("srcSizeY", C.c_uint32), ("srcBx", C.c_uint32), ("srcBy", C.c_uint32),
+                ("dstBx", C.c_uint32), ("dstBy", C.c_uint32), ("blocksW", C.c_uint32), ("blocksH", C.c_uint32)]
 
 
 class Options(C.Structure):
@@ -424,6 +431,18 @@ def load_library(path=None):
     L.limg_hip_host_gather_offsets.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.limg_hip_host_chain_bases.restype = C.c_int
     L.limg_hip_host_chain_bases.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    # ctx, pieces (host array), count, pieceSize, sizeX, sizeY, hasAlpha, errorFactor, flags, out, capacity, bytes[, hipStream]
+    L.limg_hip_stream_splice_device.restype = C.c_int
+    L.limg_hip_stream_splice_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                C.POINTER(C.c_size_t), C.c_void_p]
+    L.limg_hip_stream_splice.restype = C.c_int
+    L.limg_hip_stream_splice.argtypes = L.limg_hip_stream_splice_device.argtypes[:-1]
+    # ctx, stream, streamBytes, sizeX, sizeY, hasAlpha, x0, y0, width, height, errorFactor, flags, out, capacity, bytes, hipStream
+    L.limg_hip_stream_crop_device.restype = C.c_int
+    L.limg_hip_stream_crop_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32,
+                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.limg_hip_stream_crop.restype = C.c_int
+    L.limg_hip_stream_crop.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     return L
 
 
@@ -1394,6 +1413,92 @@ class LimgHip:
         table = [(*j[:4], level, RESIZE_FLIP_X if len(j) == 9 and j[8] else 0, *j[4:8], w, h, out[i], w, h * w) for i, j in enumerate(jobs)]
         getattr(self, ("blocked_" if blocked else "") + "decode_stream_windows_resized_tensor_device")(table, fmt)
         return out
+
+    # ---- stream splice: a version 1 stream from rectangles of blocks of version 1 streams, copied on the GPU, never decoded (contract: include/limg_hip.h) ----
+    # A piece: (stream, src_bx, src_by, dst_bx, dst_by, blocks_w, blocks_h[, src_w, src_h]) in blocks of 8x8; the source's size is its header's unless given.
+    # Host form: stream is a numpy uint8 array.  Device form: stream is (torch uint8 CUDA tensor, nbytes) and the source's size must be given.
+    @staticmethod
+    def _splice_pieces(pieces, device):
+        keep, table = [], (SplicePiece * max(1, len(pieces)))()
+        for i, pc in enumerate(pieces):
+            stream, geometry, size = pc[0], pc[1:7], pc[7:9]
+            if device:
+                tensor, nbytes = stream
+                assert len(size) == 2, "device form: (..., src_w, src_h) ends a piece"
+                ptr = C.c_void_p(tensor.data_ptr())
+            elif stream is None:  # (a NULL source: the library's to refuse)
+                nbytes, ptr = 0, None
+            else:
+                stream = np.ascontiguousarray(stream, dtype=np.uint8)
+                keep.append(stream)
+                nbytes, ptr = stream.size, _np_ptr(stream)
+                if len(size) != 2:
+                    hdr = stream[:STREAM_HEADER_DTYPE.itemsize].view(STREAM_HEADER_DTYPE)[0]
+                    size = (int(hdr["sizeX"]), int(hdr["sizeY"]))
+            table[i] = SplicePiece(ptr, int(nbytes), size[0], size[1], *[int(v) for v in geometry])
+        return table, keep
+
+    def stream_splice(self, pieces, w, h, has_alpha, error_factor=0, flags=0, out=None):
+        """host streams -> the stream (numpy uint8) of the w x h image whose block grid the pieces cover exactly once; `out`: a uint8 buffer of the caller's (its
+        leading bytes are returned as a view)"""
+        table, keep = self._splice_pieces(pieces, False)
+        buf = np.zeros(self.stream_bound(w, h), dtype=np.uint8) if out is None else out
+        n = C.c_size_t(0)
+        self._stream_call("limg_hip_stream_splice", table, len(pieces), C.sizeof(SplicePiece), w, h, int(has_alpha), error_factor, flags, _np_ptr(buf), buf.size, C.byref(n))
+        return buf[:n.value].copy() if out is None else buf[:n.value]
+
+    def stream_splice_device(self, pieces, w, h, has_alpha, error_factor=0, flags=0, out=None, want_size=True):
+        """-> (torch uint8 CUDA stream buffer of worst-case size, bytes used or None).  Asynchronous on torch's current stream unless the size is wanted."""
+        import torch
+        table, _ = self._splice_pieces(pieces, True)
+        if out is None:
+            out = torch.empty(self.stream_bound(w, h), dtype=torch.uint8, device=pieces[0][0][0].device)
+        n = C.c_size_t(0)
+        self._stream_call("limg_hip_stream_splice_device", table, len(pieces), C.sizeof(SplicePiece), w, h, int(has_alpha), error_factor, flags, C.c_void_p(out.data_ptr()),
+                          out.numel(), C.byref(n) if want_size else None, self._stream())
+        return out, (n.value if want_size else None)
+
+    def stream_crop(self, stream, x, y, w, h, out=None):
+        """host stream bytes -> the stream of its w x h window at (x, y): x, y multiples of 8, x + w and y + h multiples of 8 or the image's edge"""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        buf = np.zeros(max(self.stream_bound(w, h), 64), dtype=np.uint8) if out is None else out
+        n = C.c_size_t(0)
+        self._stream_call("limg_hip_stream_crop", _np_ptr(stream), stream.size, x, y, w, h, _np_ptr(buf), buf.size, C.byref(n))
+        return buf[:n.value].copy() if out is None else buf[:n.value]
+
+    def stream_crop_device(self, stream, nbytes, W, H, has_alpha, x, y, w, h, error_factor=0, flags=0, out=None, want_size=True):
+        """stream: torch uint8 CUDA tensor holding a stream of a W x H image -> (stream buffer of the window's image, bytes used or None)"""
+        import torch
+        if out is None:
+            out = torch.empty(max(self.stream_bound(w, h), 64), dtype=torch.uint8, device=stream.device)
+        n = C.c_size_t(0)
+        self._stream_call("limg_hip_stream_crop_device", C.c_void_p(stream.data_ptr()), int(nbytes), W, H, int(has_alpha), x, y, w, h, error_factor, flags,
+                          C.c_void_p(out.data_ptr()), out.numel(), C.byref(n) if want_size else None, self._stream())
+        return out, (n.value if want_size else None)
+
+    def join_strip_streams(self, streams, has_alpha=None):
+        """The streams of an image's strips, top to bottom (every strip but the last a multiple of 8 rows, one width, one channel count) -> the stream of the image:
+        what turns limg_hip_gather_stream's pieces into one stream.  streams: numpy uint8 arrays, or (torch uint8 CUDA tensor, nbytes, w, h) tuples, which are
+        joined on the device (has_alpha stated) and give (stream buffer, bytes used).  Error factor and flags are the first strip's (host form) / 0 (device form)."""
+        device = not isinstance(streams[0], np.ndarray)
+        pieces, y, first = [], 0, None
+        for s in streams:
+            if device:
+                tensor, nbytes, w, h = s
+                src = (tensor, nbytes)
+            else:
+                src = np.ascontiguousarray(s, dtype=np.uint8)
+                hdr = src[:STREAM_HEADER_DTYPE.itemsize].view(STREAM_HEADER_DTYPE)[0]
+                w, h = int(hdr["sizeX"]), int(hdr["sizeY"])
+                first = hdr if first is None else first
+            if y % 8 != 0:
+                raise ValueError("only the last strip may have a height that is no multiple of 8")
+            pieces.append((src, 0, 0, 0, y // 8, (w + 7) // 8, (h + 7) // 8, w, h))
+            y += h
+        if device:
+            assert has_alpha is not None, "device form: the strips' channel count is the caller's to state"
+            return self.stream_splice_device(pieces, pieces[0][7], y, has_alpha)
+        return self.stream_splice(pieces, pieces[0][7], y, int(first["channels"]) == 4, int(first["errorFactor"]), int(first["flags"]))
 
     def check(self):
         _check(self.lib.limg_hip_check_device_status(self.ctx), "limg_hip_check_device_status")

@@ -16,7 +16,7 @@ TEST_FLAGS = ["-DLIMG_HIP_TEST_HOOKS"]
 SOURCES = ["limg_hip_kernels.hip", "limg_hip_fit_tpb.hip", "limg_hip_stream.hip", "limg_hip_blocked.hip", "limg_hip_synth.hip", "limg_hip_noise_gpu.hip",
            "limg_hip_api.hip", "limg_hip_noise_table.hip", "limg_hip_encode.hip", "limg_hip_encode_ragged.hip", "limg_hip_host_entry.hip", "limg_hip_stream_api.hip",
            "limg_hip_blocked_api.hip", "limg_hip_multi.hip", "limg_hip_noise.cpp", "limg_hip_blocked_host.cpp", "limg_hip_blocked_stream.hip", "limg_hip_stream_window.hip",
-           "limg_hip_stream_window_api.hip", "limg_hip_rate.hip", "limg_hip_stream_encode_api.hip"]
+           "limg_hip_stream_window_api.hip", "limg_hip_rate.hip", "limg_hip_stream_encode_api.hip", "limg_hip_stream_splice.hip", "limg_hip_stream_splice_api.hip"]
 # the library exports the C ABI of include/limg_hip.h (limg_hip_*) and nothing else: the host units' shared internals and the C++ runtime's template instances stay local
 EXPORTS = os.path.join(CSRC, "limg_hip.map")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]

@@ -149,6 +149,10 @@ struct limg_hip_context
     // version 2 stream of the merged-block encoder: per rectangle its first 64-pixel run, per tile of rectangles its totals; the decoder's block -> rectangle map and
     // its per-call words
     DevBuf bsUnits{ n }, bsTiles{ n }, bsMap{ n }, bsState{ n };
+    DevBuf splice{ n }; // stream splice: the call's fail word, its sources, runs and item prefix, and a payload total per run -- nothing that scales with pixels
+    HostBuf spliceHost; // ... the table as the call builds it (pinned), copied to `splice` on the call's stream
+    Event spliceDone;   // ... recorded behind the call's last kernel, waited for on the host before the next call touches either
+    bool spliceBusy = false;
     Events packTimers;      // begin / end of the last stream encode's scan + pack kernels ...
     bool packTimed = false; // ... which limg_hip_blocked_kernel_timing still has to add to blocked.kernelMs[3]
   } stream{ deviceBytes };

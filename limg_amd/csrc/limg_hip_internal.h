@@ -447,6 +447,30 @@ namespace limg_hip
   void launch_set_stream_table(StreamImage *dTable, const StreamImage *hTable, size_t count, hipStream_t s);                // as launch_set_batch_table: through kernel arguments
   void launch_stream_gather_bytes(const StreamImage *dTable, size_t count, unsigned long long *dBytes, hipStream_t s);      // dBytes[i] = totalBytes of image i's header
   void launch_stream_decode(const DecodeParams &p, int cus, hipStream_t s);
+  // k_stream_tile_scan<1> alone: the exclusive prefix of `n` payload-word totals in place (any n: it loops beyond 1024), and the version 1 header of that geometry
+  void launch_stream_scan(uint32_t *totals, uint32_t n, uint8_t *stream, uint32_t sizeX, uint32_t sizeY, uint32_t channels, uint32_t errorFactor, uint32_t flags, hipStream_t s);
+
+  // ---- stream splice (limg_hip_stream_splice.hip): a version 1 stream from rectangles of blocks of version 1 streams, copied, never decoded ----
+  struct SpliceRun; // limg_hip_splice_plan.h: one block row of one piece
+  struct SpliceSource // a piece's stream and the geometry its header is checked against (the members stream_header_ok reads)
+  {
+    const uint8_t *stream;
+    unsigned long long streamBytes;
+    uint32_t sizeX, sizeY, blocksX, blocksY, nBlocks, reserved[3];
+  };
+  struct SpliceParams
+  {
+    const SpliceSource *sources;  // per piece
+    const SpliceRun *runs;        // nRuns, in the output's raster order
+    const uint32_t *itemBase;     // nRuns + 1: exclusive prefix of the runs' copy items (kSpliceItemBlocks blocks each)
+    uint32_t *totals;             // nRuns + 1, zero: a run's payload words (k_splice_measure), then their exclusive prefix (the scan)
+    uint32_t *fail;               // the call's own verdict word, zero: a source was refused and nothing is copied
+    uint32_t *status;             // the context's sticky word (limg_hip_check_device_status)
+    uint8_t *out;
+    uint32_t nRuns, nItems;
+    uint32_t sizeX, sizeY, blocksX, blocksY, nBlocks, channels, errorFactor, flags; // the output's header
+  };
+  void launch_stream_splice(const SpliceParams &p, int cus, hipStream_t s); // three launches whatever the pieces are: measure, scan + header, copy
 
   // ---- the stream's size probe (limg_hip_rate.hip) ----
   // What the probes of one call read on the device and the step kernel between them writes: the search (limg_hip_rate_step.h) or the position in a list of error

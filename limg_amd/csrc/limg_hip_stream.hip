@@ -902,6 +902,14 @@ namespace limg_hip
     hipLaunchKernelGGL(k_stream_pack, dim3(p.nTiles), dim3(kTile), 0, s, p);
   }
 
+  // the scan of launch_stream_pack on its own, for a packer whose totals are not tiles of blocks (the splice's runs): the kernel exists once in the library
+  void launch_stream_scan(uint32_t *totals, uint32_t n, uint8_t *stream, uint32_t sizeX, uint32_t sizeY, uint32_t channels, uint32_t errorFactor, uint32_t flags, hipStream_t s)
+  {
+    const uint32_t blocksX = (sizeX + kBlock - 1) / kBlock, blocksY = (sizeY + kBlock - 1) / kBlock;
+    const StreamHeaderInfo info = { LIMG_HIP_STREAM_VERSION, sizeX, sizeY, channels, errorFactor, blocksX, blocksY, flags, blocksX * blocksY, (uint32_t)kEntry, 0u };
+    hipLaunchKernelGGL(k_stream_tile_scan<1>, dim3(1), dim3(1024), 0, s, totals, n, stream, info);
+  }
+
   void launch_stream_pack_list(const StreamListParams &b, hipStream_t s)
   {
     hipLaunchKernelGGL(k_stream_scan_strips_list, dim3(b.nImages), dim3(1024), 0, s, b);

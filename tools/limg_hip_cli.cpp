@@ -15,7 +15,8 @@
 // `--blocked-stream <file>` (single-file merged-block mode: write the version 2 stream of that very encode and verify that it decodes to its image),
 // and the extra mode `limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]` (either version; with --window only that pixel rectangle
 // is decoded; with --scale k the image reduced by k x k box means, the window then in the reduced image's coordinates; with --resize WxH the image or the window,
-// stated in full-resolution pixels, resampled to W x H pixels, mirrored with --flip).
+// stated in full-resolution pixels, resampled to W x H pixels, mirrored with --flip).  `--crop-stream` and `--join-streams` make version 1 streams from version 1
+// streams without decoding (a window as a stream of its own; strips stacked into one stream).
 #include <inttypes.h>
 #include <math.h>
 #include <stdio.h>
@@ -242,7 +243,9 @@ static const char *const kUsage =
     "--stream <file> [--max-bytes <N> | --min-psnr <dB> [--min-error-factor <A>] [--max-error-factor <B>]] | --blocked-stream <file>] \n  if input file is --:\n    [--count <Count>] -- <list of files>)\n"
     "limg_hip_cli --decode <file.lmg3> [<out.tga>] [--scale 1|2|4|8] [--window x,y,w,h]\n"
     "limg_hip_cli --decode <file.lmg3> [<out.tga>] --resize WxH [--window x,y,w,h] [--flip]\n"
-    "limg_hip_cli --decode <file.lmg3> --compare <original image>\n";
+    "limg_hip_cli --decode <file.lmg3> --compare <original image>\n"
+    "limg_hip_cli --crop-stream <in.lmg3> <out.lmg3> --window x,y,w,h\n"
+    "limg_hip_cli --join-streams <out.lmg3> <a.lmg3> <b.lmg3> ...\n";
 
 static bool parse_number(const char *text, uint64_t &value)
 {
@@ -690,10 +693,101 @@ static int run_decode(int argc, const char **argv)
   return EXIT_SUCCESS;
 }
 
+// extra modes: streams from streams, without decoding (limg_hip.h "stream splice"; version 1 streams only)
+//   limg_hip_cli --crop-stream <in.lmg3> <out.lmg3> --window x,y,w,h   limg_crop_stream: the stream of that window (x, y multiples of 8; x + w, y + h multiples of 8
+//                                                                     or the image's edge), which decodes to the window's pixels of the input bit for bit
+//   limg_hip_cli --join-streams <out.lmg3> <a.lmg3> <b.lmg3> ...       limg_splice_streams: the inputs stacked top to bottom (one width; every height but the last
+//                                                                     a multiple of 8)
+static const char *const kSpliceUsage = "Usage: limg_hip_cli --crop-stream <in.lmg3> <out.lmg3> --window x,y,w,h\n"
+                                        "       limg_hip_cli --join-streams <out.lmg3> <a.lmg3> <b.lmg3> ...\n";
+
+static bool write_file(const char *path, const uint8_t *data, size_t bytes)
+{
+  FILE *f = fopen(path, "wb");
+  if (!f) return false;
+  const bool ok = fwrite(data, 1, bytes, f) == bytes;
+  return fclose(f) == 0 && ok;
+}
+
+static int run_crop_stream(int argc, const char **argv)
+{
+  const char *in = nullptr, *out = nullptr;
+  size_t win[4] = { 0, 0, 0, 0 };
+  bool window = false;
+  for (int i = 2; i < argc; i++)
+  {
+    if (!strcmp(argv[i], "--window"))
+    {
+      if (i + 1 >= argc || !parse_window(argv[++i], win)) FAIL(EXIT_FAILURE, "'--window' takes x,y,w,h in pixels.\n%s", kSpliceUsage);
+      window = true;
+    }
+    else if (!in) in = argv[i];
+    else if (!out) out = argv[i];
+    else FAIL(EXIT_FAILURE, "%s", kSpliceUsage);
+  }
+  if (!in || !out || !window) FAIL(EXIT_FAILURE, "%s", kSpliceUsage);
+  std::vector<uint8_t> stream;
+  if (!read_file(in, stream)) FAIL(EXIT_FAILURE, "Failed to read '%s'.\n", in);
+  size_t sx = 0, sy = 0;
+  if (limg_hip_stream_info(stream.data(), stream.size(), &sx, &sy, nullptr, nullptr) != limg_hip_success) FAIL(EXIT_FAILURE, "'%s' is not a version 1 LMG3 stream.\n", in);
+  std::vector<uint8_t> cropped(limg_encode_bound(win[2], win[3]));
+  size_t bytes = 0;
+  const limg_result r = cropped.empty() ? limg_error_InvalidParameter : limg_crop_stream(stream.data(), stream.size(), win[0], win[1], win[2], win[3], cropped.data(), cropped.size(), &bytes);
+  if (r == limg_error_InvalidParameter)
+    FAIL(EXIT_FAILURE, "The window %" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 " cannot be cropped from %" PRIu64 " x %" PRIu64 " pixels: x and y must be multiples of 8, and x + w and "
+         "y + h multiples of 8 or the image's edge.\n", (uint64_t)win[0], (uint64_t)win[1], (uint64_t)win[2], (uint64_t)win[3], (uint64_t)sx, (uint64_t)sy);
+  if (r != limg_success) FAIL(EXIT_FAILURE, "limg_crop_stream failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
+  printf("%" PRIu64 " x %" PRIu64 " pixels; window %" PRIu64 " x %" PRIu64 " at (%" PRIu64 ", %" PRIu64 "): %" PRIu64 " of %" PRIu64 " bytes.\n", (uint64_t)sx, (uint64_t)sy, (uint64_t)win[2],
+         (uint64_t)win[3], (uint64_t)win[0], (uint64_t)win[1], (uint64_t)bytes, (uint64_t)stream.size());
+  if (!write_file(out, cropped.data(), bytes)) FAIL(EXIT_FAILURE, "Failed to write '%s'.\n", out);
+  puts("Wrote stream file.");
+  return EXIT_SUCCESS;
+}
+
+static int run_join_streams(int argc, const char **argv)
+{
+  if (argc < 4) FAIL(EXIT_FAILURE, "%s", kSpliceUsage);
+  const char *out = argv[2];
+  std::vector<std::vector<uint8_t>> strips((size_t)argc - 3);
+  std::vector<limg_hip_splice_piece> pieces(strips.size());
+  size_t width = 0, height = 0;
+  int alpha = 0;
+  uint32_t errorFactor = 0, flags = 0;
+  for (size_t i = 0; i < strips.size(); i++)
+  {
+    const char *in = argv[3 + i];
+    if (!read_file(in, strips[i])) FAIL(EXIT_FAILURE, "Failed to read '%s'.\n", in);
+    size_t sx = 0, sy = 0;
+    int a = 0;
+    if (limg_hip_stream_info(strips[i].data(), strips[i].size(), &sx, &sy, &a, nullptr) != limg_hip_success) FAIL(EXIT_FAILURE, "'%s' is not a version 1 LMG3 stream.\n", in);
+    if (i == 0)
+    {
+      const limg_hip_stream_header *h = reinterpret_cast<const limg_hip_stream_header *>(strips[0].data());
+      width = sx; alpha = a; errorFactor = h->errorFactor; flags = h->flags;
+    }
+    if (sx != width || a != alpha) FAIL(EXIT_FAILURE, "'%s' is %" PRIu64 " pixels wide, %s: the strips of one image share width and channels.\n", in, (uint64_t)sx, a ? "RGBA" : "RGB");
+    if (height % 8 != 0) FAIL(EXIT_FAILURE, "Only the last strip may have a height that is no multiple of 8 ('%s' would start at row %" PRIu64 ").\n", in, (uint64_t)height);
+    pieces[i] = { strips[i].data(), strips[i].size(), (uint32_t)sx, (uint32_t)sy, 0u, 0u, 0u, (uint32_t)(height / 8), (uint32_t)((sx + 7) / 8), (uint32_t)((sy + 7) / 8) };
+    height += sy;
+  }
+  std::vector<uint8_t> joined(limg_encode_bound(width, height));
+  if (joined.empty()) FAIL(EXIT_FAILURE, "%" PRIu64 " x %" PRIu64 " pixels is too large for one stream.\n", (uint64_t)width, (uint64_t)height);
+  size_t bytes = 0;
+  const limg_result r = limg_splice_streams(pieces.data(), pieces.size(), width, height, alpha != 0, joined.data(), joined.size(), &bytes, errorFactor, flags);
+  if (r != limg_success) FAIL(EXIT_FAILURE, "limg_splice_streams failed with exit code 0x%" PRIX32 ".\n", (uint32_t)r);
+  printf("%" PRIu64 " strips joined: %" PRIu64 " x %" PRIu64 " pixels, %s, %" PRIu64 " bytes.\n", (uint64_t)strips.size(), (uint64_t)width, (uint64_t)height, alpha ? "RGBA" : "RGB",
+         (uint64_t)bytes);
+  if (!write_file(out, joined.data(), bytes)) FAIL(EXIT_FAILURE, "Failed to write '%s'.\n", out);
+  puts("Wrote stream file.");
+  return EXIT_SUCCESS;
+}
+
 int main(const int argc, const char **argv)
 {
   if (argc == 1) FAIL(EXIT_SUCCESS, "%s", kUsage);
   if (!strcmp(argv[1], "--decode")) return run_decode(argc, argv);
+  if (!strcmp(argv[1], "--crop-stream")) return run_crop_stream(argc, argv);
+  if (!strcmp(argv[1], "--join-streams")) return run_join_streams(argc, argv);
   Options o;
   if (!parse_args(argc, argv, o)) return EXIT_FAILURE;
   limg_thread_pool *pool = o.usePool ? limg_thread_pool_new(o.threads) : nullptr;
