@@ -562,7 +562,7 @@ namespace limg_hip
     // own): the NEXT unit's entries are requested before the current unit's groups are decoded, and a unit's first payload run is requested as soon as its offsets are
     // known, ahead of the (long) constant preparation.  Units go to waves with a fixed stride: there is no dependence between units, so no ticket is needed.
     // The re-expansion multiplier is folded into the normals (value * (mul * n) == (value * mul) * n exactly: 8 + 21 bits for records the packed form accepts);
-    // blocks with larger records (never from a fit of byte pixels) keep both apart and take the generic loop.
+    // blocks with larger records (never from a fit of byte pixels: tests/test_gpu_synthetic_streams.py builds such streams by hand) keep both apart and take the generic loop.
     // a16 for the 8 pixels of one block row in the packed form of the F step (limg_hip_phase_f.h phase_f_rows), factor by factor: per factor and pixel one v_bfe_u32 and
     // three 24-bit multiply-adds (the re-expansion multiplier sits in the normals).  The terms never live as 32-bit values: one v_perm_b32 packs a pixel's R and G terms
     // (>> 8 included) into the halves of a register, another the B terms of a PAIR of pixels; the additive constants carry biases (0x3000 + 0x3000 + 0x2000 = 0x8000
@@ -838,7 +838,8 @@ namespace limg_hip
             }
             else
             { // record values beyond the packed form's range somewhere in this group (never from a fit of byte pixels): 32-bit terms, the low 32 bits of the products
-              // like PMULLD; a block of the group that is NOT beyond the range has its multiplier in its normals and 1 here
+              // like PMULLD; a block of the group that is NOT beyond the range has its multiplier in its normals and 1 here.  Covered by the hand-built streams of
+              // tests/test_gpu_synthetic_streams.py: groups with one large block at each position and with eight, values at +-2700 / +-2701, any int16 record
               const uint32_t mulw = S.mul[t];
               const uint32_t mulA = mulw & 0x3FF, mulB = (mulw >> 10) & 0x3FF, mulC = (mulw >> 20) & 0x3FF;
 #pragma unroll

@@ -16,7 +16,8 @@
 //                              a wave's stores are 8 row pieces of 256 contiguous bytes.  Nothing is read through an offset the map kernel has not checked against
 //                              the stream's size.
 // The full version 2 decode (limg_hip_blocked_decode_stream[_device]) is these two kernels on the window (0, 0, sizeX, sizeY) at stride sizeX: version 2 has no other decoder.
-// Both versions decode with a16_constants / a16_pixel (limg_hip_stream_format.h): the reference's decoder in 32-bit terms, exact for every record.  Of the full version 1
+// Both versions decode with a16_constants / a16_pixel (limg_hip_stream_format.h): the reference's decoder in 32-bit terms, exact for every record (any int16 record, every shift triple and
+// escape pattern: tests/test_gpu_synthetic_streams.py and tests/test_gpu_synthetic_blocked_streams.py, against the oracle's decode of hand-built streams).  Of the full version 1
 // decoder's devices this file uses the next-run prefetch only: no counted wait (and so no store sink), no packed 16-bit decode, no per-block constants in LDS -- every
 // lane prepares the constants of its block itself.
 // Lanes whose image row or columns fall outside the window store nothing, or only the pixels inside it: nothing but the window's pixels is ever written.
